@@ -23,6 +23,10 @@ Prints ONE JSON line on rank 0 (contract in the task description), including
   roofline     -- dominant kernel, achieved vs peak, timed live with HIP events on its stream
   cpu_baseline -- the CPU restatement of the reference path (oracle/, "port") timed on the host
                   cores of this box on a bounded sample (rank 0, N = 1 only)
+
+--dump-outputs DIR writes what the last timed inference step returned (features, logits, predicted indices) as .npy
+files.  Clips and weights are seeded, so the same arguments give the same inputs on every run and two builds of the
+project can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -56,6 +60,7 @@ PEAK_F16X3_TFLOPS = 2500.0 / 3.0
 # ALGORITHMIC fp32 FLOP/s on that path is 2500/6 TFLOP/s
 PEAK_BF16X6_TFLOPS = PEAK_BF16_MFMA_TFLOPS / 6.0
 PEAK_HBM_GBS = 8000.0            # MI355X_MICROARCH.md: HBM3E spec peak
+DUMP_LIMIT_BYTES = 64 * 10 ** 6  # --dump-outputs: every file of one run together, all ranks
 
 # algorithmic work per utterance at T = 200 frames
 _CONV2 = 2 * 64 * 288 * 32 * 100
@@ -233,6 +238,33 @@ def pmc_traffic(kernel):
         return v, f"{os.path.relpath(files[-1], ROOT)} (committed rocprofv3 --pmc pass, not measured in this run)"
     except Exception:
         return None, None
+
+
+def dump_outputs(out_dir, arrays, limit, suffix=""):
+    """Write `arrays` (name -> tensor, first axis = utterance) as <out_dir>/<name><suffix>.npy: float32 stays float32,
+    any other dtype becomes float64.  When the files would exceed `limit` bytes, every array keeps the same fixed,
+    seeded sample of utterances (ascending), and their indices are written as sample_rows<suffix>.npy.  Returns the paths."""
+    import numpy as np
+    arrs = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        arrs[name] = a if a.dtype == np.float32 else a.astype(np.float64)
+    n = len(next(iter(arrs.values())))
+    header = 128                                               # .npy header of a version 1.0 file
+    if sum(a.nbytes + header for a in arrs.values()) > limit:
+        per_row = sum(a.nbytes // n for a in arrs.values()) + 8
+        keep = (limit - header * (len(arrs) + 1)) // per_row
+        if keep < 1:
+            raise ValueError(f"--dump-outputs: {limit} bytes cannot hold one utterance's outputs")
+        rows = np.sort(np.random.default_rng(0).choice(n, size=min(n, keep), replace=False))
+        arrs = {name: a[rows] for name, a in arrs.items()}
+        arrs["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    paths = []
+    for name, a in arrs.items():
+        paths.append(os.path.join(out_dir, f"{name}{suffix}.npy"))
+        np.save(paths[-1], np.ascontiguousarray(a))
+    return paths
 
 
 def device_clips(n, length, seed, device):
@@ -593,7 +625,13 @@ def main():
                     help="N = 1 only: skip the training leg that runs the RCCL gradient exchange in a one-rank nccl group")
     ap.add_argument("--streams", type=int, default=int(os.environ.get("SIR_BENCH_STREAMS", "2")),
                     help="HIP streams the inference batches alternate over (each with its own buffers/workspace)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed regions, write what the last timed inference step returned (features, logits, "
+                         "predictions) as DIR/<name>.npy (DIR/<name>_rank<r>.npy with N > 1), float32 / float64, at most "
+                         "64 MB in all; the inputs depend only on the arguments")
     args = ap.parse_args()
+    if args.steps < 1 or args.repeats < 1:
+        ap.error("--steps and --repeats must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))       # parent: launcher only, before any GPU call
@@ -656,7 +694,7 @@ def main():
     fz = get_featurizer()
     pool = [device_clips(batch, CLIP_LEN, 1234 + 1000 * rank + i, dev) for i in range(N_POOL)]
     lengths = torch.full((batch,), CLIP_LEN, dtype=torch.int32, device=dev)
-    preds = [None]
+    last = [None]                # (slot, logits, predictions) of the latest inference step
     # batch pipelining INSIDE the library (sir_pipeline, include/sir_hip.h; sir_amd/pipeline.py wraps it): this process
     # stays on ONE stream; the library alternates consecutive batches over `--streams` streams of its own, each with its
     # own feature buffer and model workspace (weights shared), so that the latency-bound GRU recurrence of one batch
@@ -669,7 +707,7 @@ def main():
     def step(i):
         k = pipe.slot(i)
         pipe.features(i, pool[i % N_POOL], lengths, t_pad=T_PAD, out=feats[k])
-        _, preds[0] = pipe.infer(i, feats[k])
+        last[0] = (k,) + pipe.infer(i, feats[k])
 
     nk = lib.sir_profile_kernel_count()
     names = [lib.sir_profile_kernel_name(i).decode() for i in range(nk)]
@@ -728,6 +766,12 @@ def main():
     if rank == 0:
         log(f"timed {args.repeats} x {args.steps} steps: median {elapsed:.4f} s")
     dom_ms, dom_cnt = collect()
+    if args.dump_outputs:
+        # the last timed step (index repeats * steps - 1); its slot's buffers are reused by the legs below
+        k, logits, pred = last[0]
+        paths = dump_outputs(args.dump_outputs, {"features": feats[k], "logits": logits, "predictions": pred},
+                             DUMP_LIMIT_BYTES // world, f"_rank{rank}" if world > 1 else "")
+        log(f"rank {rank}: outputs of timed step {args.repeats * args.steps - 1} written: {' '.join(paths)}")
     # reference leg: the same regions strictly serial (sir_pipeline with one slot = the caller's stream), dominant kernel
     # timed in isolation.  (A single batch cannot be made to overlap with itself: all its utterances already advance in
     # parallel inside the recurrence, so any split only lengthens the dependent chain -- DESIGN.md section 4.)

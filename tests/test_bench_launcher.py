@@ -56,11 +56,18 @@ def _run(args, env_extra):
                           timeout=600)
 
 
-def test_refuses_instead_of_degrading():
-    """More ranks than visible GPUs -> exit code 2 and no result line; WORLD_SIZE != --gpus -> the same."""
-    if (bench.visible_gpu_count() or 0) < 2:
+def test_refuses_instead_of_degrading(monkeypatch, capsys):
+    """More ranks than visible GPUs -> exit code 2 and no result line; WORLD_SIZE != --gpus -> the same.  The script runs end
+    to end where this host's GPU count is known: with an unreadable KFD topology (None) the launcher lets the ranks fail by
+    design, so the refusal itself is also checked on launch_ranks with the count given (it returns before starting any rank)."""
+    n = bench.visible_gpu_count()
+    if n is not None and n < 2:
         r = _run(["--gpus", "2", "--steps", "1", "--warmup", "0"], {"SIR_BENCH_SHARE_GPU": "0"})
         assert r.returncode == 2 and "only" in r.stderr and bench.pick_json_line(r.stdout.splitlines()) is None
+    monkeypatch.setenv("SIR_BENCH_SHARE_GPU", "0")
+    monkeypatch.setattr(bench, "visible_gpu_count", lambda: 1)
+    assert bench.launch_ranks(2, ["--gpus", "2", "--steps", "1", "--warmup", "0"]) == 2
+    assert "only 1 GPU(s) are visible" in capsys.readouterr().err
     r = _run(["--gpus", "4", "--steps", "1", "--warmup", "0"], {"WORLD_SIZE": "2", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode == 2 and "refusing" in r.stderr and bench.pick_json_line(r.stdout.splitlines()) is None
 

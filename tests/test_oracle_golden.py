@@ -87,11 +87,24 @@ def test_model_ten_step_trajectory_matches_reference(sd, traj_golden):
 
 
 def test_features_f32_reproduce_committed(features_golden):
+    """Pure tones (> 100 dB dynamic range) are pinned to the committed float64 values instead: most of their bins are
+    float32 FFT rounding noise, which differs between host CPUs (0.2 dB apart at -99 dB), so the float32 oracle on this
+    host must be as close to float64 as the committed float32 run was (2x its error, the bound test_features_gpu.py
+    puts on the HIP kernel for the same clips)."""
     for name, wave in cases.feature_cases().items():
         st = features_ref.extract_features_f32(wave, stages=True)
-        np.testing.assert_allclose(st["db"].numpy(), features_golden[f"{name}/db"], rtol=0, atol=2e-4, err_msg=name)
-        np.testing.assert_allclose(features_ref.pad_or_trim(st["norm"]).numpy(), features_golden[f"{name}/padded"],
-                                   rtol=0, atol=2e-5, err_msg=name)
+        db, padded = st["db"].numpy(), features_ref.pad_or_trim(st["norm"]).numpy()
+        if name.startswith("tone"):
+            t = db.shape[1]
+            for now, committed, f64, floor in (
+                    (db, features_golden[f"{name}/db"], features_golden[f"{name}/db_f64"], 1e-3),
+                    (padded[:, :t], features_golden[f"{name}/padded"][:, :t], features_golden[f"{name}/norm_f64"], 5e-4)):
+                err_now, err_committed = np.abs(now - f64).max(), np.abs(committed - f64).max()
+                assert err_now <= max(2.0 * err_committed, floor), (name, err_now, err_committed)
+            assert (padded[:, t:] == 0).all(), name
+            continue
+        np.testing.assert_allclose(db, features_golden[f"{name}/db"], rtol=0, atol=2e-4, err_msg=name)
+        np.testing.assert_allclose(padded, features_golden[f"{name}/padded"], rtol=0, atol=2e-5, err_msg=name)
 
 
 def test_features_f32_vs_f64():

@@ -286,13 +286,15 @@ static void run_wino2(const char* name, int B, int H, int W, int reps = 60) {
     CK_(hipMemcpy(dx, hx.data(), nx * 4, hipMemcpyHostToDevice)); CK_(hipMemcpy(dw, hw.data(), nw * 4, hipMemcpyHostToDevice));
     CK_(hipMemcpy(ds, hs.data(), COUT * 4, hipMemcpyHostToDevice)); CK_(hipMemcpy(dt, ht.data(), COUT * 4, hipMemcpyHostToDevice));
     hipStream_t st; CK_(hipStreamCreate(&st));
-    // forward: weights [COUT][CIN][3][3]; data gradient: the layer's weights are [CIN][COUT][3][3] (forward cout = this CIN)
+    // forward: weights [COUT][CIN][3][3]; data gradient: the layer's weights are [CIN][COUT][3][3] (forward cout = this CIN).
+    // The direct kernel takes bf16x3 planes, the Winograd kernel (f16x3 arithmetic) f16x3 planes.
+    unsigned int* dstat; CK_(hipMalloc(&dstat, 256)); CK_(hipMemset(dstat, 0, 256));
     if (DGRAD) {
         hipLaunchKernelGGL(prep_conv_wT_bf16x3_kernel, dim3((CIN * 9 * COUT + 255) / 256), dim3(256), 0, st, (const float*)dw, wpb, COUT, CIN);
-        hipLaunchKernelGGL(prep_conv_wT_wino_bf16x3_kernel, dim3((CIN * 16 * COUT + 255) / 256), dim3(256), 0, st, (const float*)dw, wpw, COUT, CIN);
+        hipLaunchKernelGGL(prep_conv_wT_wino_f16x3_kernel, dim3((CIN * 16 * COUT + 255) / 256), dim3(256), 0, st, (const float*)dw, wpw, COUT, CIN, dstat);
     } else {
         hipLaunchKernelGGL(prep_conv_w_bf16x3_kernel, dim3((CIN * 9 * COUT + 255) / 256), dim3(256), 0, st, (const float*)dw, wpb, CIN, COUT);
-        hipLaunchKernelGGL(prep_conv_w_wino_bf16x3_kernel, dim3((CIN * 16 * COUT + 255) / 256), dim3(256), 0, st, (const float*)dw, wpw, CIN, COUT);
+        hipLaunchKernelGGL(prep_conv_w_wino_f16x3_kernel, dim3((CIN * 16 * COUT + 255) / 256), dim3(256), 0, st, (const float*)dw, wpw, CIN, COUT, dstat);
     }
     CK_(hipMemsetAsync(o1, 0, nout * 4, st)); CK_(hipMemsetAsync(o2, 0, nout * 4, st));
     constexpr int DM = MODE == 3 ? 2 : MODE;              // the direct kernel's raw mode
@@ -355,46 +357,6 @@ static void run_wino2(const char* name, int B, int H, int W, int reps = 60) {
         const float tp1 = time_us(st, reps, [&] { CK_((launch_conv_wino2<CIN, COUT, MODE, 0, 1>(st, &atp[0], dxr[rot++ & 3], wpw, ds, dt, o2, B, H, W, MODE == 1 ? (float2*)pl2 : st2, dzero))); });
         const float tp2 = time_us(st, reps, [&] { CK_((launch_conv_wino2<CIN, COUT, MODE, 0, 3>(st, &atp[1], dxr[rot++ & 3], wpw, ds, dt, o2, B, H, W, MODE == 1 ? (float2*)pl2 : st2, dzero))); });
         printf("  rotating inputs: direct %.1f us (%.1f TF)   wino2 %.1f us (%.1f TF algorithmic); producers at s_setprio 1: %.1f, 3: %.1f us\n", t1, gf * 1e3 / t1, t2, gf * 1e3 / t2, tp1, tp2);
-        // round 4: the same kernel on the f16x3 arithmetic (F16 = true; weights from prep_conv_w(T)_wino_f16x3)
-        {
-            unsigned short* wph; CK_(hipMalloc(&wph, (size_t)COUT * CIN * 16 * 6));
-            unsigned int* dstat; CK_(hipMalloc(&dstat, 256)); CK_(hipMemset(dstat, 0, 256));
-            if (DGRAD) hipLaunchKernelGGL(prep_conv_wT_wino_f16x3_kernel, dim3((CIN * 16 * COUT + 255) / 256), dim3(256), 0, st, (const float*)dw, wph, COUT, CIN, dstat);
-            else hipLaunchKernelGGL(prep_conv_w_wino_f16x3_kernel, dim3((CIN * 16 * COUT + 255) / 256), dim3(256), 0, st, (const float*)dw, wph, CIN, COUT, dstat);
-            bool ah = false;
-            auto wino2h = [&](const float* in) {
-                CK_((launch_conv_wino2<CIN, COUT, MODE, 0, 3, true>(st, &ah, in, wph, ds, dt, o2, B, H, W, MODE == 1 ? (float2*)pl2 : st2, dzero))); };
-            CK_(hipMemsetAsync(o2, 0, nout * 4, st));
-            direct(dx); wino2h(dx);
-            CK_(hipStreamSynchronize(st));
-            std::vector<float> h1(nout), h2(nout);
-            CK_(hipMemcpy(h1.data(), o1, nout * 4, hipMemcpyDeviceToHost)); CK_(hipMemcpy(h2.data(), o2, nout * 4, hipMemcpyDeviceToHost));
-            double d = 0; size_t bad = 0;
-            for (size_t i = 0; i < nout; ++i) { const double e = fabs((double)h1[i] - h2[i]); d = fmax(d, e); bad += e > 1e-4; }
-            const float th = time_us(st, reps, [&] { wino2h(dxr[rot++ & 3]); });
-            auto koh = [&](auto kc) {
-                bool at = false;
-                return time_us(st, reps, [&] { CK_((launch_conv_wino2<CIN, COUT, MODE, decltype(kc)::value, 3, true>(st, &at, dx, wph, ds, dt, o2, B, H, W, MODE == 1 ? (float2*)pl2 : st2, dzero))); });
-            };
-            using std::integral_constant;
-            printf("  f16x3 arithmetic: max |direct(bf16x6) - wino2(f16x3)| = %.3e, %zu elements off by > 1e-4; rotating inputs %.1f us (%.1f TF algorithmic, bf16x6 %.1f us)\n",
-                   d, bad, th, gf * 1e3 / th, t2);
-            printf("  f16x3 knock-outs (one cached input): full %.1f, no DMA %.1f, no transform %.1f, no MFMA %.1f, no epilogue %.1f, only barriers+epilogue %.1f, weights once %.1f us\n",
-                   koh(integral_constant<int, 32>{}), koh(integral_constant<int, 2>{}), koh(integral_constant<int, 4>{}), koh(integral_constant<int, 8>{}),
-                   koh(integral_constant<int, 16>{}), koh(integral_constant<int, 14>{}), koh(integral_constant<int, 64>{}));
-            {   // fine-grained producer stamps of the f16x3 kernel (DBG = 1: complete kernel + stamps)
-                bool atf = false;
-                for (int rep = 0; rep < 3; ++rep)
-                    CK_((launch_conv_wino2<CIN, COUT, MODE, 1, 3, true>(st, &atf, dx, wph, ds, dt, o2, B, H, W, MODE == 1 ? (float2*)pl2 : st2, dzero)));
-                CK_(hipStreamSynchronize(st));
-                long long hf_[8][8];
-                CK_(hipMemcpyFromSymbol(hf_, HIP_SYMBOL(w2_dbg_fine), sizeof(hf_)));
-                printf("  f16x3 producer wave 0, steps 8..15, cycles from the step's top: DMA issued | raw patches read | V written | DMA wait over | barrier passed\n   ");
-                for (int k = 0; k < 8; ++k) printf(" [%lld %lld %lld %lld %lld]", hf_[k][1] - hf_[k][0], hf_[k][2] - hf_[k][0], hf_[k][3] - hf_[k][0], hf_[k][4] - hf_[k][0], hf_[k][5] - hf_[k][0]);
-                printf("\n");
-            }
-            (void)hipFree(wph); (void)hipFree(dstat);
-        }
         for (int k = 0; k < 4; ++k) (void)hipFree(dxr[k]);
         // phase stamps of workgroup 0, second task (cycles relative to the first stamp): group A | group B
         bool attr2 = false;
@@ -428,7 +390,7 @@ static void run_wino2(const char* name, int B, int H, int W, int reps = 60) {
             printf("\n");
         }
     }
-    hipFree(dx); hipFree(dw); hipFree(ds); hipFree(dt); hipFree(o1); hipFree(o2); hipFree(wpb); hipFree(wpw);
+    hipFree(dx); hipFree(dw); hipFree(ds); hipFree(dt); hipFree(o1); hipFree(o2); hipFree(wpb); hipFree(wpw); hipFree(dstat);
     if (pl1) hipFree(pl1); if (pl2) hipFree(pl2); if (st1) hipFree(st1); if (st2) hipFree(st2);
     fflush(stdout);
 }

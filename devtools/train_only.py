@@ -2,7 +2,7 @@
 """Training step alone (features -> forward/backward -> Adam at batch 256, dropout 0.5), for A/B runs of environment switches
 inside ONE box session: median ms / step over `--repeats` regions and the per-kernel HIP-event averages of `sir_profile_*`.
 
-    SIR_BPTT=1 python devtools/train_only.py --steps 30 --tag bptt1      # prints one JSON line
+    SIR_GRU_DBG=256 python devtools/train_only.py --steps 30 --tag delay1      # prints one JSON line
 
 Developer tool (run through gpurun); the product path only, nothing from oracle/."""
 import argparse

@@ -34,31 +34,9 @@ static int upload(T** dst, const std::vector<T>& src) {
     return SIR_OK;
 }
 
-int sir_wino2_mask() {
-    static const int m = getenv("SIR_WINO2") ? atoi(getenv("SIR_WINO2")) : 15;
-    return m;
-}
-
-int sir_wgw_mask() {
-    static const int m = getenv("SIR_WGW") ? atoi(getenv("SIR_WGW")) : 3;
-    return m;
-}
-
-int sir_tn2_mask() {
-    static const int m = getenv("SIR_TN2") ? atoi(getenv("SIR_TN2")) : 15;
-    return m;
-}
-
-int sir_f16_mask() {
-    static const int m = getenv("SIR_F16") ? atoi(getenv("SIR_F16")) : 63;
-    return m;
-}
-
-int sir_bwd_streams() {
-    // default 3: the weight-gradient launches of the backward run on a second stream owned by the handle (model_train.hip);
-    // 0 = everything on the caller's stream (profiles/r04/ab_bwd_streams.txt)
-    static const int m = getenv("SIR_BWD_STREAMS") ? atoi(getenv("SIR_BWD_STREAMS")) : 3;
-    return m;
+bool sir_conv_stage_fits(int conv, bool shape_ok) {
+    static const int forced = getenv("SIR_CONV_FALLBACK") ? atoi(getenv("SIR_CONV_FALLBACK")) : 0;
+    return shape_ok && forced < (conv == 2 ? 1 : 2);
 }
 
 extern "C" int sir_create(const sir_feature_config* cfg, sir_handle** out) {
@@ -79,9 +57,7 @@ extern "C" int sir_create(const sir_feature_config* cfg, sir_handle** out) {
     h->status = nullptr;
     h->cluster_done = nullptr; h->cluster_stream = nullptr; h->cluster_pending = false;
     h->cluster_seen = false; h->cluster_multi = false; h->cluster_run = 0;
-    h->cluster_always = getenv("SIR_CLUSTER_EVENTS") && atoi(getenv("SIR_CLUSTER_EVENTS")) == 1;   // A/B switch: chained mode throughout
-    if (h->cluster_always) h->cluster_multi = true;
-    h->attr_gemm_v3 = h->attr_gru_quad = h->attr_gru_bwd = h->attr_gru_bwd_quad = h->attr_tn = h->attr_wgrad = false;
+    h->attr_gemm_v3 = h->attr_gru_quad = h->attr_gru_bwd_quad = h->attr_tn = h->attr_wgrad = false;
     for (auto& a : h->attr_wino2) a = false;
     h->zero_page = nullptr; h->num_cus = 256;
     for (auto& x : h->xbufs) { x.st = nullptr; x.p = nullptr; x.kind = 0; x.cap = 0; x.bytes = 0; x.epoch = 0; x.used = 0; }

@@ -29,6 +29,8 @@
 //                 the V buffer the task's last chunk just left (each wave finishes one tile column: it receives 3 x 2 KB; two
 //                 extra barriers per task), then BN + ReLU + 2x2 max (the 2x2 outputs of a tile ARE the pooling window) or raw
 //                 outputs (+ channel statistics, accumulated in registers over the workgroup's tasks: 4 blocks per workgroup).
+// The kernel now runs only in the f16x3 form described further down (two planes instead of three, a dedicated exchange area in
+// place of the epilogue's borrowed V buffer); the bf16x6 form it grew from is what the paragraphs above and the numbers below measure.
 // Weights: prep_conv_w_wino_bf16x3 layout wpb[plane][chunk * 16 + f][cout][16 ch] with column j = 3 negated (shared with the
 // first generation); data gradients use the same kernel on the transposed / flipped taps (prep_conv_wT_wino_bf16x3).
 // Measured (devtools/kernel_ab/bench_conv.hip `wino2`, batch 256, four rotating inputs, one box): conv2 143 us against 184 direct
@@ -48,13 +50,11 @@ constexpr int W2_NPOS = 18 * W2_RS;
 constexpr int W2_RAW_PIECES = (W2_NPOS * 4 + 63) / 64;      // 13 DMA pieces of 1 KB
 constexpr int W2_RAW_BYTES = W2_RAW_PIECES * 1024;          // 13,312
 constexpr int W2_PLB = 16 * 1024;                           // bytes per V plane: [f][1 KB]
-constexpr int W2_V_BYTES = 3 * W2_PLB;                      // 49,152 per chunk; two buffers
 constexpr int W2_NRAW = 3;                                  // raw ring slots: a chunk's DMA pieces get two steps to land
-constexpr int W2_LDS_BYTES = 2 * W2_V_BYTES + W2_NRAW * W2_RAW_BYTES;   // 138,240
-// F16: two V planes per buffer (32 KB) + a DEDICATED 48 KB exchange area for the epilogue's row transform: 64 + 39 + 48 KB
+// two V planes per buffer (32 KB, two buffers) + the raw ring + a DEDICATED 48 KB exchange area for the epilogue's row transform: 64 + 39 + 48 KB
+constexpr int W2_V_BYTES = 2 * W2_PLB;
 constexpr int W2_XCH_BYTES = 3 * W2_PLB;
-constexpr int w2_v_bytes(bool f16) { return f16 ? 2 * W2_PLB : W2_V_BYTES; }
-constexpr int w2_lds_bytes(bool f16) { return f16 ? 2 * 2 * W2_PLB + W2_NRAW * W2_RAW_BYTES + W2_XCH_BYTES : W2_LDS_BYTES; }   // 154,624 / 138,240
+constexpr int W2_LDS_BYTES = 2 * W2_V_BYTES + W2_NRAW * W2_RAW_BYTES + W2_XCH_BYTES;   // 154,624
 constexpr int W2_THREADS = 768;                             // 4 producer waves + 8 consumer waves
 constexpr int W2_PPW = (W2_RAW_PIECES + 3) / 4;             // DMA pieces per wave of group B
 
@@ -74,9 +74,6 @@ static inline W2Div w2_div_make(unsigned d) {
 }
 __device__ __forceinline__ int w2_div(int n, const W2Div& d) {
     const unsigned un = (unsigned)n;
-#ifdef SIR_W2_OLDADDR                                        // A/B build only (devtools/gpu_r4ac.sh): the ISA's division sequence
-    return (int)(un / d.d);
-#endif
     if (d.pow2) return (int)(un >> d.sh);
     const unsigned t = __umulhi(d.m, un);
     return (int)((t + ((un - t) >> 1)) >> d.sh);
@@ -140,22 +137,22 @@ __device__ long long w2_dbg_fine[8][8];              // producer wave 0 of workg
 // registers, so the U stream that bounds the kernel is a third shorter as well).  The part runs at its power
 // cap: the matrix products ARE the energy.  Needs inputs inside fp16's range (activations: yes; gradients only under the loss
 // scale of the backward).  With 32 KB V buffers the LDS has room for a DEDICATED exchange area of the epilogue's row transform
-// (the bf16x6 form borrows the V buffer the task's last chunk just left and needs two extra barriers, A and B, around that, with
+// (the bf16x6 form borrowed the V buffer the task's last chunk just left and needed two extra barriers, A and B, around that, with
 // the producers parked at them): a consumer writes its pieces right behind its last MFMAs, the step's ONE barrier publishes them,
 // and the producers are transforming the next chunk meanwhile -- the epilogue was 26 of the f16x3 kernel's 109 us (knock-outs,
 // profiles/r04/bench_conv_wino2_f16x3.txt).
-template <int CIN, int COUT, int OUT_MODE, int DBG = 0, int PRIO = 3, bool F16 = false>
+template <int CIN, int COUT, int OUT_MODE, int DBG = 0, int PRIO = 3>
 __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_bf16x6_kernel(
     const float* __restrict__ x, const unsigned short* __restrict__ wpb, const float* __restrict__ scale,
     const float* __restrict__ shift, float* __restrict__ out, Wino2Geo geo, float2* __restrict__ stats, const float* __restrict__ zeros) {
     constexpr int NCH = CIN / 16, G = NCH * 16, NCHO = COUT >= 64 ? COUT / 64 : 1;
     static_assert(CIN % 16 == 0 && (COUT % 64 == 0 || COUT == 32), "16-channel chunks; 64-channel tasks (32: the n = 1 consumer waves only keep the barriers)");
-    static_assert(!F16 || NCH >= 2, "F16: a task's exchange pieces are read behind its closing barrier; the next task's are written >= one barrier later");
+    static_assert(NCH >= 2, "a task's exchange pieces are read behind its closing barrier; the next task's are written >= one barrier later");
     extern __shared__ __attribute__((aligned(1024))) unsigned char w2s[];
-    constexpr int VB = w2_v_bytes(F16);                                 // bytes per V buffer
-    unsigned char* const vbuf = w2s;                                    // [2][3 (F16: 2) planes][16 f][1 KB]
+    constexpr int VB = W2_V_BYTES;                                      // bytes per V buffer
+    unsigned char* const vbuf = w2s;                                    // [2][2 planes][16 f][1 KB]
     unsigned char* const rawbuf = w2s + 2 * VB;                         // [3][13 KB]
-    unsigned char* const xchbuf = rawbuf + W2_NRAW * W2_RAW_BYTES;      // F16 only: [8 waves][3 pieces][2 KB]
+    unsigned char* const xchbuf = rawbuf + W2_NRAW * W2_RAW_BYTES;      // [8 waves][3 pieces][2 KB]
 
     // the wave index as a SCALAR (readfirstlane): everything derived from it -- roles, rows, channel slices, weight addresses -- then
     // lives in SGPRs; derived from threadIdx alone hipcc keeps it all in vector registers (+40 VGPRs in the consumer loop: spills)
@@ -174,17 +171,13 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_bf16x6_kernel(
         g0 = 4 * cb; ty0 = 8 * rb;
     };
     // ---- raw-patch DMA: WHO issues it ------------------------------------------------------------------------------------------
-    // The four producer waves (piece k = wave + 4 i, counted vmcnt waits in their loop) -- except in the F16 form of a 32-channel layer (the
+    // The four producer waves (piece k = wave + 4 i, counted vmcnt waits in their loop) -- except in a 32-channel layer (the
     // conv2 data gradient), where the four consumer waves of the missing second channel slice have nothing to do but keep the barriers: they take
     // the DMA over, on the producers' own schedule (chunk s + 2 at the top of step s, landed by the end of step s + 1).  Stamps inside a producer's
     // step put the issue of its 3-4 LDS-DMA pieces at ~620 of ~3500 cycles (155 per piece) on the kernel's critical waves.  (Handing the pieces to
     // the WORKING consumers of the 64-channel forms was measured and lost 10 %: behind their MFMAs a chunk has one step instead of two to land,
     // and the in-order return puts it in front of their weight fragments -- profiles/r04/bench_conv_wino2_f16x3.txt.)
-#ifdef SIR_W2_PRODDMA                                        // A/B build only (devtools/gpu_r4af.sh)
-    constexpr bool IDLE_DMA = false;
-#else
-    constexpr bool IDLE_DMA = F16 && COUT < 64;
-#endif
+    constexpr bool IDLE_DMA = COUT < 64;
     constexpr int D_STRIDE = 4, D_PPW = (W2_RAW_PIECES + D_STRIDE - 1) / D_STRIDE;
     const int d_stride = D_STRIDE;
     const int d_rank = producer ? wv : ((wv - 4) >> 1);               // (the idle waves are 5, 7, 9, 11)
@@ -202,23 +195,6 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_bf16x6_kernel(
         pre_part[ii] = (sp ^ (((lr >> 2) & 1) << 1)) * 4;
     }
     auto raw_offsets = [&](int g0, int ty0, unsigned (&off)[D_PPW]) {
-#ifdef SIR_W2_OLDADDR                                        // A/B build only (devtools/gpu_r4ac.sh): everything recomputed per task, the ISA's division
-#pragma unroll
-        for (int ii = 0; ii < D_PPW; ++ii) {
-            const int slot = 64 * (d_rank + d_stride * ii) + lane, pos = slot >> 2, sp = slot & 3;
-            int lr = pos / W2_RS;
-            int lc = pos - lr * W2_RS - ((lr >> 1) & 1);
-            const bool hole = lr > 17 || lc < 0 || lc > 9;
-            const int part = sp ^ (((lr >> 2) & 1) << 1);
-            const int gy = 2 * ty0 - 1 + lr;
-            const int P = 2 * g0 - 1 + lc;
-            const int Pc = min(max(P, 0), 2 * NG - 1);
-            const int bb = Pc / (2 * TW), px = Pc - bb * 2 * TW;
-            const bool ok = !hole && gy >= 0 && gy < H && P >= 0 && P < 2 * NG && px < W;
-            off[ii] = ok ? (unsigned)(((bb * H + gy) * W + px) * CIN + part * 4) : ~0u;
-        }
-        return;
-#endif
 #pragma unroll
         for (int ii = 0; ii < D_PPW; ++ii) {
             const int gy = 2 * ty0 - 1 + pre_lr[ii];
@@ -259,11 +235,9 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_bf16x6_kernel(
         // ================= producers ==============================================================================================
         // (their VALU stream competes with two MFMA-issuing consumer waves for the SIMD's issue port: priority to the producer)
         if (PRIO) __builtin_amdgcn_s_setprio(PRIO);
-#ifndef SIR_W2_CLAMP
         // MODE.FP16_OVFL = 1 for the producer waves: a conversion to fp16 that overflows gives +-65504 instead of infinity, which is what
         // the split's two v_med3 clamps per pair were for (32 of the ~170 vector instructions per row pair and step)
-        if (F16) __builtin_amdgcn_s_setreg((1 /* HW_REG_MODE */) | (23 << 6) | (0 << 11), 1);
-#endif
+        __builtin_amdgcn_s_setreg((1 /* HW_REG_MODE */) | (23 << 6) | (0 << 11), 1);
         const int wg = wv;
         // wave wg = (row pair tR of the transform, 8-channel half tH); lane = (tile tm, 4-channel group tP1)
         const int tR = wg >> 1, tH = wg & 1, tm = lane >> 1, tP1 = lane & 1;
@@ -335,25 +309,11 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_bf16x6_kernel(
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
                             const unsigned d = vd + (4 * il + j) * 1024;
-                            if constexpr (F16) {
-                                uint2 sh, sl;
-#ifdef SIR_W2_CLAMP                                          // A/B build only: the split's own clamps (v_med3 per value)
-                                split2h_pair(V[j].x, V[j].y, sh.x, sl.x);
-                                split2h_pair(V[j].z, V[j].w, sh.y, sl.y);
-#else
-                                split2h_pair_ovfl(V[j].x, V[j].y, sh.x, sl.x);
-                                split2h_pair_ovfl(V[j].z, V[j].w, sh.y, sl.y);
-#endif
-                                w2_write64<0>(d, sh);
-                                w2_write64<W2_PLB>(d, sl);
-                            } else {
-                                uint2 sh, sm, sl;
-                                split3_pair(V[j].x, V[j].y, sh.x, sm.x, sl.x);
-                                split3_pair(V[j].z, V[j].w, sh.y, sm.y, sl.y);
-                                w2_write64<0>(d, sh);
-                                w2_write64<W2_PLB>(d, sm);
-                                w2_write64<2 * W2_PLB>(d, sl);
-                            }
+                            uint2 sh, sl;
+                            split2h_pair_ovfl(V[j].x, V[j].y, sh.x, sl.x);
+                            split2h_pair_ovfl(V[j].z, V[j].w, sh.y, sl.y);
+                            w2_write64<0>(d, sh);
+                            w2_write64<W2_PLB>(d, sl);
                         }
                     }
                 };
@@ -371,7 +331,6 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_bf16x6_kernel(
             }
             stamp();
             fine(s, 4);
-            if (!F16 && s >= 1 && (s - 1) % NCH == NCH - 1) { w2_barrier(); w2_barrier(); }     // bf16x6: the consumers' row-transform exchange (barriers A, B)
             w2_barrier();
             fine(s, 5);
         }
@@ -382,7 +341,7 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_bf16x6_kernel(
     // wave (n = cw & 1, i = cw >> 1): channel slice 32 n.., transform row i (frequencies 4 i .. 4 i + 3, 4 accumulators)
     const int cw = wv - 4, mn = cw & 1, mi = cw >> 1, m = lane & 31, h = lane >> 5;
     if (COUT < 64 && mn == 1) {                                         // a 32-channel layer has no second slice: join the barriers --
-        if (IDLE_DMA) {                                                 // -- and (F16) feed the raw-patch ring in the producers' stead
+        if (IDLE_DMA) {                                                 // -- and feed the raw-patch ring in the producers' stead
             if (!(DBG & 2)) { issue_chunk(0); issue_chunk(1); }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             w2_barrier();                                               // raw chunks 0 and 1 have landed
@@ -401,13 +360,13 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_bf16x6_kernel(
         w2_barrier();
         w2_barrier();
         for (int lt = 0; lt < ntask; ++lt)
-            for (int c = 0; c < NCH + (F16 ? 0 : 2); ++c) w2_barrier();
+            for (int c = 0; c < NCH; ++c) w2_barrier();
         return;
     }
     // U fragment address = uniform part (plane, frequency, channel block, slice: scalar registers) + this lane's 32-bit byte offset
     const unsigned wlane = (unsigned)((m * 2 + h) * 16);
     const unsigned char* const wbase = reinterpret_cast<const unsigned char*>(wpb) + (size_t)mn * 1024;
-    constexpr int NPW = F16 ? 2 : 3;                                    // weight planes
+    constexpr int NPW = 2;                                              // weight planes
     uint4 wq[4][NPW];                                                   // U fragments of the wave's four frequencies, one chunk ahead
     auto load_w = [&](int gidx, int chh, uint4 (&q)[NPW]) {
 #pragma unroll
@@ -450,29 +409,25 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_bf16x6_kernel(
             // step starts with an L2 round trip
 #pragma unroll
             for (int jp = 0; jp < 2; ++jp) {
-                constexpr int NPA = F16 ? 2 : 3;
+                constexpr int NPA = 2;
                 bf16x8 a[2][NPA], bq[2][3];
 #pragma unroll
                 for (int jj = 0; jj < 2; ++jj) {
 #pragma unroll
                     for (int p = 0; p < NPA; ++p)
                         a[jj][p] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(abase + p * W2_PLB + (2 * jp + jj) * 1024));
-                    if constexpr (F16) {                               // planes (Uh, Ul') -> fragments (Uh, Uh 2^11, Ul')
-                        const f16x8 uh = __builtin_bit_cast(f16x8, wq[2 * jp + jj][0]);
-                        bq[jj][0] = __builtin_bit_cast(bf16x8, uh);
-                        bq[jj][1] = __builtin_bit_cast(bf16x8, uh * (_Float16)2048.0f);
-                        bq[jj][2] = __builtin_bit_cast(bf16x8, wq[2 * jp + jj][1]);
-                    } else {
-#pragma unroll
-                        for (int p = 0; p < 3; ++p) bq[jj][p] = __builtin_bit_cast(bf16x8, wq[2 * jp + jj][p < NPW ? p : 0]);
-                    }
+                    // planes (Uh, Ul') -> fragments (Uh, Uh 2^11, Ul')
+                    const f16x8 uh = __builtin_bit_cast(f16x8, wq[2 * jp + jj][0]);
+                    bq[jj][0] = __builtin_bit_cast(bf16x8, uh);
+                    bq[jj][1] = __builtin_bit_cast(bf16x8, uh * (_Float16)2048.0f);
+                    bq[jj][2] = __builtin_bit_cast(bf16x8, wq[2 * jp + jj][1]);
                 }
                 if (DBG & 8) {
 #pragma unroll
                     for (int jj = 0; jj < 2; ++jj)
                         acc[2 * jp + jj][0] += __builtin_bit_cast(float4, a[jj][0]).x + __builtin_bit_cast(float4, a[jj][1]).y + __builtin_bit_cast(float4, a[jj][NPA - 1]).z +
                                                __builtin_bit_cast(float4, bq[jj][0]).x + __builtin_bit_cast(float4, bq[jj][1]).y + __builtin_bit_cast(float4, bq[jj][2]).z;
-                } else if constexpr (F16) {
+                } else {
                     // a: 0 = Vh, 1 = Vl'; bq: 0 = Uh, 1 = Uh 2^11, 2 = Ul' -- the two cross terms first, then the main one
                     constexpr int HA[3] = {1, 0, 0}, HB[3] = {0, 2, 1};
 #pragma unroll
@@ -481,13 +436,6 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_bf16x6_kernel(
                         for (int jj = 0; jj < 2; ++jj)
                             acc[2 * jp + jj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a[jj][HA[t3]]),
                                                                                       __builtin_bit_cast(f16x8, bq[jj][HB[t3]]), acc[2 * jp + jj], 0, 0, 0);
-                } else {
-                    constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};   // small terms first
-#pragma unroll
-                    for (int t6 = 0; t6 < 6; ++t6)
-#pragma unroll
-                        for (int jj = 0; jj < 2; ++jj)
-                            acc[2 * jp + jj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[jj][PA[t6]], bq[jj][PB[t6]], acc[2 * jp + jj], 0, 0, 0);
                 }
 #pragma unroll
                 for (int jj = 0; jj < 2; ++jj) if (!(DBG & 64)) load_w(gnxt + 2 * jp + jj, task_end ? chn : ch, wq[2 * jp + jj]);
@@ -496,14 +444,12 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_bf16x6_kernel(
             stamp();
             if (!task_end) w2_barrier();
         }
-        const int sc = lt * NCH + NCH - 1;                              // the task's last chunk: its V buffer becomes the exchange area
-        if (DBG & 16) { if (!F16) { w2_barrier(); w2_barrier(); } w2_barrier(); if (acc[0][0] == 1234.5f && acc[1][1] + acc[2][2] + acc[3][3] == 4.0f) out[0] = 1.0f; }
+        if (DBG & 16) { w2_barrier(); if (acc[0][0] == 1234.5f && acc[1][1] + acc[2][2] + acc[3][3] == 4.0f) out[0] = 1.0f; }
         else {
             {
-                if (!F16) w2_barrier();                              // A (bf16x6): every consumer has read its last fragments of V[sc & 1]
                 // column inverse transform (U_{i3} is stored negated); finisher k = row index of slice mn completes accumulator registers
                 // 4 k .. 4 k + 3 (tile column k, tile rows 4 h + e).  Piece (source i -> finisher k): W_i[b][4 k + e] as two float4 (b)
-                float4* const xch = reinterpret_cast<float4*>(F16 ? xchbuf : vbuf + (sc & 1) * VB);
+                float4* const xch = reinterpret_cast<float4*>(xchbuf);
                 float own[2][4];
 #pragma unroll
                 for (int b = 0; b < 2; ++b) {                          // one b at a time: 16 live registers instead of 32 beside the accumulators
@@ -519,7 +465,7 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_bf16x6_kernel(
                         }
                     }
                 }
-                w2_barrier();                                        // B: the pieces are in LDS (F16: this IS the step's closing barrier -- the
+                w2_barrier();                                        // the pieces are in LDS (this IS the step's closing barrier -- the
                                                                      // producers are already on the next chunk, nobody parks)
                 // Y[0][b] = (W0 + W1) + W2, Y[1][b] = (W1 - W2) - W3: always in THIS order, whichever row the finishing wave holds itself --
                 // the tile column a clip lands on depends on its position in the batch, and a clip's logits must not (bit for bit)
@@ -541,12 +487,10 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_bf16x6_kernel(
                         }
                     }
                 }
-                if (!F16) w2_barrier();                              // C (bf16x6: this step's closing barrier, early): the pieces are in registers, the
-                                                                     // producers may overwrite this V buffer -- they transform the next chunk while the outputs are finished here
                 const int co = ch * 64 + mn * 32 + m;
                 float ssum = 0.0f, ssq = 0.0f;
                 float sc_ = 1.0f, sh_ = 0.0f;
-                constexpr float DESC = F16 ? H3_LO_INV : 1.0f;         // the f16x3 accumulators are 2^11 too large (exact power of two)
+                constexpr float DESC = H3_LO_INV;                      // the f16x3 accumulators are 2^11 too large (exact power of two)
                 if (OUT_MODE <= 1) { sc_ = scale[co] * DESC; sh_ = shift[co]; }
                 {
                     const int gc = g0 + mi;
@@ -625,17 +569,17 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_bf16x6_kernel(
 }
 
 // `attr_done`: the caller's per-device latch of the dynamic-LDS opt-in of THIS instantiation (sir_handle::attr_wino2[...])
-template <int CIN, int COUT, int OUT_MODE, int DBG = 0, int PRIO = 3, bool F16 = false>
+template <int CIN, int COUT, int OUT_MODE, int DBG = 0, int PRIO = 3>
 static inline hipError_t launch_conv_wino2(hipStream_t st, bool* attr_done, const float* x, const unsigned short* wpb, const float* scale,
                                            const float* shift, float* out, int B, int H, int W, float2* stats, const float* zeros, int max_wg = 256) {
     Wino2Geo g;
     if (!wino2_geo(B, H, W, CIN > COUT ? CIN : COUT, &g)) return hipErrorInvalidValue;
     if (!*attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)conv3x3_wino2_bf16x6_kernel<CIN, COUT, OUT_MODE, DBG, PRIO, F16>, hipFuncAttributeMaxDynamicSharedMemorySize, w2_lds_bytes(F16));
+        hipError_t e = hipFuncSetAttribute((const void*)conv3x3_wino2_bf16x6_kernel<CIN, COUT, OUT_MODE, DBG, PRIO>, hipFuncAttributeMaxDynamicSharedMemorySize, W2_LDS_BYTES);
         if (e != hipSuccess) return e;
         *attr_done = true;
     }
     const int nwg = g.NS < max_wg ? g.NS : max_wg;
-    hipLaunchKernelGGL((conv3x3_wino2_bf16x6_kernel<CIN, COUT, OUT_MODE, DBG, PRIO, F16>), dim3(nwg), dim3(W2_THREADS), w2_lds_bytes(F16), st, x, wpb, scale, shift, out, g, stats, zeros);
+    hipLaunchKernelGGL((conv3x3_wino2_bf16x6_kernel<CIN, COUT, OUT_MODE, DBG, PRIO>), dim3(nwg), dim3(W2_THREADS), W2_LDS_BYTES, st, x, wpb, scale, shift, out, g, stats, zeros);
     return hipGetLastError();
 }

@@ -24,7 +24,7 @@ __device__ __forceinline__ void split2h_pair(float a, float b, unsigned& h, unsi
 }
 // the same without the clamps, for waves that run with MODE.FP16_OVFL = 1 (an overflowing conversion then saturates at +-65504 by itself)
 __device__ __forceinline__ void split2h_pair_ovfl(float a, float b, unsigned& h, unsigned& l) {
-    // (lo' as one v_fma_mixlo / mixhi_f16 per value -- 4 instead of 6 instructions per pair, the same rounding -- was measured: no faster, devtools/gpu_r4ae.sh)
+    // (lo' as one v_fma_mixlo / mixhi_f16 per value -- 4 instead of 6 instructions per pair, the same rounding -- was measured: no faster)
     sir_f32x2 v = {a, b};
     const sir_f16x2 hi = __builtin_convertvector(v, sir_f16x2);
     v -= __builtin_convertvector(hi, sir_f32x2);

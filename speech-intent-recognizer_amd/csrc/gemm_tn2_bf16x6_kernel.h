@@ -26,7 +26,7 @@ constexpr int TN2_THREADS = 64 * (TN2_NPW + 8);              // + 8 consumer wav
 constexpr int TN2_BM = 128;
 constexpr size_t tn2_lds_bytes(bool a_km, int bm = TN2_BM) { return 2 * tn_lds_bytes(a_km, bm); }     // two stage buffers: 147,456 / 159,744 B (BM = 128)
 
-// F16 (round 4): the products on the fp16 matrix cores with the two-way split of f16_split.h.  A (the gate gradients, which carry the
+// f16x3 (round 4; the only form now -- the bf16x6 form's staging and six products are gone): the products on the fp16 matrix cores with the two-way split of f16_split.h.  A (the gate gradients, which carry the
 // backward's loss scale and therefore sit in fp16's range) is staged as TWO planes (Ah, Al' = residual 2^11); B (activations / weights)
 // is first scaled by TN2_BS = 2^-4 (exact) and staged as two planes as well (Bh, Bl'); the consumers form Bh 2^11 in registers (four
 // v_pk_mul_f16 per fragment), so that the three products Al' Bh + Ah Bl' + Ah (Bh 2^11) = 2^11 A B go into ONE accumulator (the
@@ -65,12 +65,12 @@ __device__ __forceinline__ bf16x8 tn2_hi2(const bf16x8& bh) {
 
 __device__ __forceinline__ void tn2_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-template <bool A_KM, int dbg = 0, int BM = TN2_BM, bool F16 = false>
+template <bool A_KM, int dbg = 0, int BM = TN2_BM>
 __global__ __launch_bounds__(TN2_THREADS, TN2_THREADS / 256) void gemm_tn2_bf16x6_kernel(TnJobs jobs, int M, int K, int kchunk, int seq) {
     constexpr int NC = BM >= 128 ? 2 : 1;                    // BM = 128: consumers 2 x 4, wave tile 64 x 64; BM = 64: 1 x 8, wave tile 64 x 32
     constexpr int AXW = BM * 2, BXW = TN_BN * 2;             // row bytes of the k-major images
     constexpr int APLANE = A_KM ? TN_BK * AXW : BM * TN_ROWB, BPLANE = TN_BK * BXW;
-    constexpr int NPA = F16 ? 2 : 3, NPB = NPA;              // operand planes in LDS
+    constexpr int NPA = 2, NPB = 2;                          // operand planes in LDS
     constexpr int STAGE = NPA * APLANE + NPB * BPLANE;
     constexpr int NPT = 64 * TN2_NPW;                         // producer threads
     constexpr int NAQ = BM * 8 / NPT, NBQ = TN_BN * 8 / NPT;  // staging items per PRODUCER thread
@@ -102,11 +102,7 @@ __global__ __launch_bounds__(TN2_THREADS, TN2_THREADS / 256) void gemm_tn2_bf16x
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     // fp16 overflow mode + unclamped splits for the weight-gradient form only (dW 77 -> 74 / 114 -> 109 us; the dX form measured 1.5-2 us SLOWER
     // with it and keeps the clamps: profiles/r04/ab_fp16_ovfl.txt)
-#ifdef SIR_W2_CLAMP
-    constexpr bool OVFL = false;
-#else
-    constexpr bool OVFL = F16 && A_KM;
-#endif
+    constexpr bool OVFL = A_KM;
     if (OVFL) sir_fp16_ovfl_on();                            // producers: unclamped splits; consumers: Bh 2^11 saturates instead of overflowing
 
     if (wv < TN2_NPW) {
@@ -179,37 +175,21 @@ __global__ __launch_bounds__(TN2_THREADS, TN2_THREADS / 256) void gemm_tn2_bf16x
                 const int it = ptid + NPT * q;
                 unsigned char* d = A_KM ? AT + tn_kmaj_off<AXW>(it / (BM / 4), 8 * (it % (BM / 4)))
                                         : AT + (size_t)(it >> 3) * TN_ROWB + (it & 7) * 8;
-                if constexpr (F16) {
-                    uint2 hh, ll;
-                    if constexpr (OVFL) split2h_quad_ovfl(pa[q], hh, ll);
-                    else split2h_quad(pa[q], hh, ll);
-                    *reinterpret_cast<uint2*>(d) = hh;
-                    *reinterpret_cast<uint2*>(d + APLANE) = ll;
-                } else {
-                    uint2 hh, mm, ll;
-                    split3_quad(pa[q], hh, mm, ll);
-                    *reinterpret_cast<uint2*>(d) = hh;
-                    *reinterpret_cast<uint2*>(d + APLANE) = mm;
-                    *reinterpret_cast<uint2*>(d + 2 * APLANE) = ll;
-                }
+                uint2 hh, ll;
+                if constexpr (OVFL) split2h_quad_ovfl(pa[q], hh, ll);
+                else split2h_quad(pa[q], hh, ll);
+                *reinterpret_cast<uint2*>(d) = hh;
+                *reinterpret_cast<uint2*>(d + APLANE) = ll;
             }
 #pragma unroll
             for (int q = 0; q < NBQ; ++q) {
                 const int it = ptid + NPT * q;
                 unsigned char* d = BT + tn_kmaj_off<BXW>(it >> 6, 8 * (it & 63));
-                if constexpr (F16) {
-                    uint2 hh, ll;
-                    if constexpr (OVFL) tn2_split_b_ovfl(pb[q], hh, ll);   // (Bh, Bl') of B / 16
-                    else tn2_split_b(pb[q], hh, ll);
-                    *reinterpret_cast<uint2*>(d) = hh;
-                    *reinterpret_cast<uint2*>(d + BPLANE) = ll;
-                } else {
-                    uint2 hh, mm, ll;
-                    split3_quad(pb[q], hh, mm, ll);
-                    *reinterpret_cast<uint2*>(d) = hh;
-                    *reinterpret_cast<uint2*>(d + BPLANE) = mm;
-                    *reinterpret_cast<uint2*>(d + 2 * BPLANE) = ll;
-                }
+                uint2 hh, ll;
+                if constexpr (OVFL) tn2_split_b_ovfl(pb[q], hh, ll);       // (Bh, Bl') of B / 16
+                else tn2_split_b(pb[q], hh, ll);
+                *reinterpret_cast<uint2*>(d) = hh;
+                *reinterpret_cast<uint2*>(d + BPLANE) = ll;
             }
         };
         fetch(k_begin, pa0, pb0);
@@ -251,41 +231,26 @@ __global__ __launch_bounds__(TN2_THREADS, TN2_THREADS / 256) void gemm_tn2_bf16x
         for (int ks = 0; ks < 2; ++ks) {
             bf16x8 af[2][NPA], bf[NC][3];
 #pragma unroll
-            for (int p = 0; p < 3; ++p) {
-                if (p < NPA) {
+            for (int p = 0; p < NPA; ++p) {
 #pragma unroll
-                    for (int a = 0; a < 2; ++a)
-                        af[a][p < NPA ? p : 0] = A_KM ? tn_tr_fragment<AXW>(sb + aoff[a] + p * APLANE + ks * 16 * AXW)
-                                                      : __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(sb + aoff[a] + p * APLANE + ks * 32));
-                }
-                if (p < NPB) {
+                for (int a = 0; a < 2; ++a)
+                    af[a][p] = A_KM ? tn_tr_fragment<AXW>(sb + aoff[a] + p * APLANE + ks * 16 * AXW)
+                                    : __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(sb + aoff[a] + p * APLANE + ks * 32));
 #pragma unroll
-                    for (int c = 0; c < NC; ++c) bf[c][F16 && p == 1 ? 2 : p] = tn_tr_fragment<BXW>(sb + boff[c] + p * BPLANE + ks * 16 * BXW);
-                }
+                for (int c = 0; c < NC; ++c) bf[c][p == 1 ? 2 : p] = tn_tr_fragment<BXW>(sb + boff[c] + p * BPLANE + ks * 16 * BXW);
             }
-            if constexpr (F16) {
 #pragma unroll
-                for (int c = 0; c < NC; ++c) bf[c][1] = tn2_hi2(bf[c][0]);
-                // af: 0 = Ah, 1 = Al'; bf: 0 = Bh, 1 = Bh 2^11, 2 = Bl' -- the two cross terms first, then the main one
-                constexpr int HA[3] = {1, 0, 0}, HB[3] = {0, 2, 1};
+            for (int c = 0; c < NC; ++c) bf[c][1] = tn2_hi2(bf[c][0]);
+            // af: 0 = Ah, 1 = Al'; bf: 0 = Bh, 1 = Bh 2^11, 2 = Bl' -- the two cross terms first, then the main one
+            constexpr int HA[3] = {1, 0, 0}, HB[3] = {0, 2, 1};
 #pragma unroll
-                for (int t3 = 0; t3 < 3; ++t3)
+            for (int t3 = 0; t3 < 3; ++t3)
 #pragma unroll
-                    for (int a = 0; a < 2; ++a)
+                for (int a = 0; a < 2; ++a)
 #pragma unroll
-                        for (int c = 0; c < NC; ++c)
-                            acc[a][c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, af[a][HA[t3]]), __builtin_bit_cast(f16x8, bf[c][HB[t3]]),
-                                                                              acc[a][c], 0, 0, 0);
-            } else {
-                constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};   // small terms first
-#pragma unroll
-                for (int t6 = 0; t6 < 6; ++t6)
-#pragma unroll
-                    for (int a = 0; a < 2; ++a)
-#pragma unroll
-                        for (int c = 0; c < NC; ++c)
-                            acc[a][c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[a][PA[t6] % NPA], bf[c][PB[t6]], acc[a][c], 0, 0, 0);
-            }
+                    for (int c = 0; c < NC; ++c)
+                        acc[a][c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, af[a][HA[t3]]), __builtin_bit_cast(f16x8, bf[c][HB[t3]]),
+                                                                          acc[a][c], 0, 0, 0);
         }
         tn2_barrier();
     }
@@ -301,7 +266,7 @@ __global__ __launch_bounds__(TN2_THREADS, TN2_THREADS / 256) void gemm_tn2_bf16x
             for (int r = 0; r < 16; ++r) {
                 const int m = m0 + wm * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * kgrp;
                 if (m < M) {
-                    float v = acc[a][c][r] * (F16 ? H3_LO_INV / TN2_BS : 1.0f);
+                    float v = acc[a][c][r] * (H3_LO_INV / TN2_BS);
                     if (jobs.drop_p > 0.0f) v = tn_dropout_keep(jobs.drop_seed, (size_t)m * N + n, jobs.drop_p) ? v * (1.0f / (1.0f - jobs.drop_p)) : 0.0f;
                     out[(size_t)m * N + n] = v;
                 }

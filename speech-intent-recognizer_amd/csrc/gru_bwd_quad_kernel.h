@@ -1,6 +1,6 @@
 // Quad-workgroup GRU back-propagation through time on the matrix cores (round 4): the backward mirror of gru_quad_kernel.h.
 //
-// gru_bwd_pair_kernel.h computes  (W_hh^T dgh)  with fp32 FMAs: 768 per thread and step on all 256 CUs, ~2.6 us of FMA issue
+// The retired fp32-FMA kernel (gru_bwd_pair_kernel) computed  (W_hh^T dgh)  with fp32 FMAs: 768 per thread and step on all 256 CUs, ~2.6 us of FMA issue
 // per step, 112-117 us per layer launch at batch 256 (profiles/r04/ab_bptt.txt).  Here, as in the forward recurrence:
 //   * one CLUSTER of four workgroups owns 16 utterances of one direction for all S steps;
 //   * workgroup q owns hidden units [64 q, 64 q + 64): it does their gate-gradient arithmetic and holds THEIR 192 gate rows of
@@ -62,11 +62,7 @@ __global__ __launch_bounds__(GQ_THREADS) void gru_bwd_quad_kernel(
             for (int s = 0; s < 6; ++s)
 #pragma unroll
                 for (int p = 0; p < 2; ++p)
-#ifdef SIR_GQ_BUILTIN_MFMA
-                    wf[d][s][p] = __builtin_bit_cast(f16x8, wsrc[((d * 6 + s) * 2 + p) * 64]);
-#else
                     asm volatile("global_load_dwordx4 %0, %1, off" : "=a"(wf[d][s][p]) : "v"(wsrc + ((d * 6 + s) * 2 + p) * 64));
-#endif
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
 

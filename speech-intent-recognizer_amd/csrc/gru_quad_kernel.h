@@ -4,7 +4,7 @@
 // MFMAs per wave and step, 192 instead of 288 resident weight registers, 2 instead of 3 h planes in LDS and in the granules.
 // h is in (-1, 1) and W_hh O(0.1): well inside fp16's range.  The description below is of the structure, unchanged since round 2:
 //
-// gru_pair_kernel computes W_hh h with fp32 FMAs and is bound by VALU issue (~64 us of FMA issue per
+// The retired fp32-FMA kernel (gru_pair_kernel) computed W_hh h with fp32 FMAs and was bound by VALU issue (~64 us of FMA issue per
 // layer at batch 256 plus 25 dependent exchanges).  Here the recurrent product runs on MFMA:
 //   * one CLUSTER of four workgroups owns 16 utterances of one direction for all S steps;
 //   * workgroup q owns hidden units [64 q, 64 q + 64), i.e. 192 gate rows of W_hh; its 4 waves each own 16
@@ -53,11 +53,7 @@ typedef float f32x4_t __attribute__((ext_vector_type(4)));
 // MFMA inside inline asm: the wait states it would insert between the matrix results and their first vector use are added by hand
 // (gq_mfma_fence: 16 idle cycles cover the 4-pass result latency; gq_mfma_enter: 4 in front of the block cover vector writes of its operands).
 __device__ __forceinline__ void gq_mfma_aw(f32x4_t& acc, const f16x8& w, const f16x8& h) {
-#ifdef SIR_GQ_BUILTIN_MFMA                                   // A/B build only (devtools/gpu_r4q.sh): compiler-managed registers
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(w, h, acc, 0, 0, 0);
-#else
     asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "a"(w), "v"(h));
-#endif
 }
 __device__ __forceinline__ void gq_mfma_wa(f32x4_t& acc, const f16x8& h, const f16x8& w) {        // the fragment as the B operand
     asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(h), "a"(w));
@@ -148,11 +144,7 @@ __global__ __launch_bounds__(GQ_THREADS) void gru_quad_kernel(
             for (int s = 0; s < 8; ++s)
 #pragma unroll
                 for (int p = 0; p < GQ_NPL; ++p)
-#ifdef SIR_GQ_BUILTIN_MFMA
-                    wf[g][s][p] = __builtin_bit_cast(f16x8, wsrc[((g * 8 + s) * GQ_NPL + p) * 64]);
-#else
                     asm volatile("global_load_dwordx4 %0, %1, off" : "=a"(wf[g][s][p]) : "v"(wsrc + ((g * 8 + s) * GQ_NPL + p) * 64));
-#endif
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     float4 bh[3];

@@ -129,9 +129,7 @@ extern "C" int sir_model_infer(sir_handle* h, const sir_model_weights* w, const 
     // conv2 / conv3 as Winograd F(2x2, 3x3) -- the 2x2 output tile is the pooling window -- on the producer / consumer kernel
     // (conv_wino2_bf16x6_kernel.h); shapes it does not cover (batch x map beyond 32-bit offsets) keep the first-generation kernels
     Wino2Geo geo2, geo3;
-    const bool w2ok = wino2_geo(B, 32, d.wp1, 64, &geo2) && wino2_geo(B, 16, d.wp2, 128, &geo3);
-    const bool w2c2 = w2ok && (sir_wino2_mask() & 1), w2c3 = w2ok && (sir_wino2_mask() & 2);
-    const bool f16c2 = w2c2 && (sir_f16_mask() & 1), f16c3 = w2c3 && (sir_f16_mask() & 2);
+    const bool w2 = sir_conv_stage_fits(2, wino2_geo(B, 32, d.wp1, 64, &geo2)) && sir_conv_stage_fits(3, wino2_geo(B, 16, d.wp2, 128, &geo3));
 
     // ---- weight preparation -------------------------------------------------------------
     // skipped when the caller vouches (sir_model_set_weights_version) that the weights are the ones prepared
@@ -150,9 +148,9 @@ extern "C" int sir_model_infer(sir_handle* h, const sir_model_weights* w, const 
         for (int i = 0; i < 4; ++i) sir_prep_whh_quad(st, w->gru_w_hh[i], (unsigned char*)wht + (size_t)i * GRU_FRAG_BYTES);
         // (the weight planes are prepared in the arithmetic of the kernel that will read them: f16x3 for the second-generation
         // Winograd kernel's forward stages, bf16x3 for the first-generation / direct fallbacks)
-        if (f16c2) hipLaunchKernelGGL(prep_conv_w_wino_f16x3_kernel, dim3((32 * 16 * 64 + 255) / 256), dim3(256), 0, st, w->conv_w[1], wcb2, 32, 64, h->status);
+        if (w2) hipLaunchKernelGGL(prep_conv_w_wino_f16x3_kernel, dim3((32 * 16 * 64 + 255) / 256), dim3(256), 0, st, w->conv_w[1], wcb2, 32, 64, h->status);
         else hipLaunchKernelGGL(prep_conv_w_wino_bf16x3_kernel, dim3((32 * 16 * 64 + 255) / 256), dim3(256), 0, st, w->conv_w[1], wcb2, 32, 64);
-        if (f16c3) hipLaunchKernelGGL(prep_conv_w_wino_f16x3_kernel, dim3((64 * 16 * 128 + 255) / 256), dim3(256), 0, st, w->conv_w[2], wcb3, 64, 128, h->status);
+        if (w2) hipLaunchKernelGGL(prep_conv_w_wino_f16x3_kernel, dim3((64 * 16 * 128 + 255) / 256), dim3(256), 0, st, w->conv_w[2], wcb3, 64, 128, h->status);
         else hipLaunchKernelGGL(prep_conv_w_wino_bf16x3_kernel, dim3((64 * 16 * 128 + 255) / 256), dim3(256), 0, st, w->conv_w[2], wcb3, 64, 128);
         hipLaunchKernelGGL(prep_conv_w_bf16x3_kernel, dim3((64 * 9 * 128 + 255) / 256), dim3(256), 0, st, w->conv_w[2], wcb3d, 64, 128);
         for (int dir = 0; dir < 2; ++dir) {
@@ -172,10 +170,7 @@ extern "C" int sir_model_infer(sir_handle* h, const sir_model_weights* w, const 
     }
     {
         SirProfScope prof(h, SIR_K_CONV2, st);
-        if (f16c2)
-            SIR_HIP_TRY((launch_conv_wino2<32, 64, 0, 0, 3, true>(st, &h->attr_wino2[5], a1, (const unsigned short*)wcb2, bns + 32, bnt + 32, a2, B, 32, d.wp1,
-                                                                (float2*)nullptr, h->zero_page, h->num_cus)));
-        else if (w2c2)
+        if (w2)
             SIR_HIP_TRY((launch_conv_wino2<32, 64, 0>(st, &h->attr_wino2[0], a1, (const unsigned short*)wcb2, bns + 32, bnt + 32, a2, B, 32, d.wp1,
                                                     (float2*)nullptr, h->zero_page, h->num_cus)));
         else
@@ -186,10 +181,7 @@ extern "C" int sir_model_infer(sir_handle* h, const sir_model_weights* w, const 
         // conv3 stores straight into the GRU input layout [B][S][c*8+h] (models.py:55-57) and writes the f16x2 planes of
         // the first input projection's A operand beside it
         SirProfScope prof(h, SIR_K_CONV3, st);
-        if (f16c3)
-            SIR_HIP_TRY((launch_conv_wino2<64, 128, 1, 0, 3, true>(st, &h->attr_wino2[6], a2, (const unsigned short*)wcb3, bns + 96, bnt + 96, x0, B, 16, d.wp2,
-                                                                 (float2*)xs, h->zero_page, h->num_cus)));
-        else if (w2c3)
+        if (w2)
             SIR_HIP_TRY((launch_conv_wino2<64, 128, 1>(st, &h->attr_wino2[1], a2, (const unsigned short*)wcb3, bns + 96, bnt + 96, x0, B, 16, d.wp2,
                                                      (float2*)xs, h->zero_page, h->num_cus)));
         else

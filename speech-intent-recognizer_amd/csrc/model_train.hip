@@ -8,7 +8,6 @@
 #include "train_kernels.h"
 #include "conv_wino2_bf16x6_kernel.h"
 #include "wgrad_bf16x6_kernel.h"
-#include "gemm_tn_bf16x6_kernel.h"
 #include "gemm_tn2_bf16x6_kernel.h"
 #include "wgrad_wino_bf16x6_kernel.h"
 
@@ -26,18 +25,15 @@ enum TrainBuf {
     TB_XS,        // f16x2 planes (f16_split.h) of the forward GEMM A operand [2][B*S][1024]
     TB_WS,        // f16x2 planes of W_ih (l0 [2 directions][2][768][1024], l1 [2][2][768][512])
     TB_WCB,       // bf16x3 conv weights: conv2, conv3 forward, then conv2, conv3 data-gradient forms
-    TB_GXB,       // (unused: exchange granules live in handle-owned buffers, sir_xbuf_acquire)
-    TB_GFL,       // paired GRU status word
     TB_C1M,       // conv1 input moments: 54 doubles (conv1_moments_kernel), forward -> backward
     TB_DGI1, TB_DGH1,   // gate gradients of GRU layer 1 (TB_DGI / TB_DGH hold layer 0's): layer 1's weight-gradient GEMM may run after layer 0's BPTT
-    TB_SLAB2,           // split-K slabs of the GRU weight-gradient GEMMs when they run on the side stream beside the BPTT of the layer below (SIR_BWD_STREAMS=2)
+    TB_SLAB2,           // split-K slabs of the GRU weight-gradient GEMMs when they run on the side stream beside the BPTT of the layer below
     TB_COUNT
 };
 
-// K splits of the four-job bf16x6 weight-gradient launch of one GRU layer (gemm_tn_bf16x6_kernel) and its slab floats
+// K splits of the four-job weight-gradient launch of one GRU layer (gemm_tn2_bf16x6_kernel) and its slab floats
 static inline void tn_x6_plan(int tokens, int in_sz, int* tiles, int* kchunk, int* nsplit, size_t* slab_floats) {
-    const int bm = (sir_tn2_mask() & 1) ? TN2_BM : TN_BM_DW;
-    const int t = 2 * ((768 / bm) * ((in_sz + TN_BN - 1) / TN_BN) + (768 / bm) * 1);
+    const int t = 2 * ((768 / TN2_BM) * ((in_sz + TN_BN - 1) / TN_BN) + (768 / TN2_BM) * 1);
     int ks = 256 / t;
     ks = ks < 1 ? 1 : (ks > 16 ? 16 : ks);
     const int kc = (((tokens + ks - 1) / ks) + TN_BK - 1) / TN_BK * TN_BK;
@@ -50,7 +46,7 @@ static inline void tn_x6_plan(int tokens, int in_sz, int* tiles, int* kchunk, in
 // tiles) runs as TWO K halves on 128-row tiles (wave tile 64 x 64) plus an ordered add, instead of 64-row tiles (wave tile 64 x 32)
 static inline bool dx_splitk(int tokens, int in_sz) {
     const int nt = ((tokens + TN2_BM - 1) / TN2_BM) * ((in_sz + TN_BN - 1) / TN_BN);
-    return (sir_tn2_mask() & 2) && (sir_tn2_mask() & 8) && nt < 160 && 2 * nt >= 96;
+    return nt < 160 && 2 * nt >= 96;
 }
 
 struct TDims {
@@ -61,6 +57,10 @@ struct TDims {
     int wg2_blocks, wg3_blocks, wg2_rb, wg3_rb;
     int ksplits, kchunk;
 };
+
+// the data gradients on the second-generation Winograd kernel (the forward's weight preparation and the backward agree on it)
+static inline bool dgrad3_wino(const TDims& d) { Wino2Geo g; return sir_conv_stage_fits(3, wino2_geo(d.B, 16, d.wp2, 128, &g)); }
+static inline bool dgrad2_wino(const TDims& d) { Wino2Geo g; return sir_conv_stage_fits(2, wino2_geo(d.B, 32, d.wp1, 64, &g)); }
 
 bool make_tdims(int batch, int t, TDims* d) {
     d->B = batch; d->T = t;
@@ -136,8 +136,6 @@ void tws_sizes(const TDims& d, size_t* n) {           // element counts (floats)
     n[TB_WS] = ((size_t)2 * 2 * 768 * 1024 + (size_t)2 * 2 * 768 * 512 + 1) / 2;
     // conv2 / conv3 forward and both data gradients in Winograd form (16 frequencies; the conv2 data gradient's slot also holds its 9-tap form when the direct kernel runs it), conv3 forward again with 9 taps for the direct fallback
     n[TB_WCB] = ((size_t)(3 * 32 * 16 * 64 + 3 * 32 * 16 * 64) + (size_t)3 * 64 * 16 * 128 + (size_t)3 * 128 * 16 * 64 + (size_t)3 * 64 * 9 * 128 + 1) / 2;
-    n[TB_GXB] = 64;
-    n[TB_GFL] = 64;
     n[TB_C1M] = 2 * C1_NMOM;
     n[TB_DGI1] = B * S * 1536;
     n[TB_DGH1] = B * S * 1536;
@@ -169,7 +167,6 @@ struct TPtrs {
     float *dy1, *dy0, *dgi, *dgh, *dx0, *dz3, *da2, *dz2, *da1, *small, *slab;
     float2* stats;
     unsigned short *xs, *wsl0, *wsl1, *wcb2, *wcb3, *wcb2t, *wcb3t, *wcb3d;
-    unsigned int* gfl;
     double* c1m;
 };
 
@@ -192,7 +189,6 @@ TPtrs carve(void* ws, const size_t* off) {
     p.wcb2 = (unsigned short*)(b + off[TB_WCB]); p.wcb3 = p.wcb2 + (size_t)3 * 32 * 16 * 64;
     p.wcb2t = p.wcb3 + (size_t)3 * 64 * 16 * 128; p.wcb3t = p.wcb2t + (size_t)3 * 32 * 16 * 64;
     p.wcb3d = p.wcb3t + (size_t)3 * 128 * 16 * 64;           // conv3 forward with 9 taps: only for shapes the Winograd kernel does not cover
-    p.gfl = (unsigned int*)(b + off[TB_GFL]);
     p.c1m = (double*)(b + off[TB_C1M]);
     p.dgi1 = (float*)(b + off[TB_DGI1]); p.dgh1 = (float*)(b + off[TB_DGH1]);
     p.slab2 = (float*)(b + off[TB_SLAB2]);
@@ -262,12 +258,10 @@ extern "C" int sir_model_train_fwd(sir_handle* h, const sir_model_weights* w, fl
     const int B = d.B, S = d.S, T = d.T;
     float *scale = p.bn, *shift = p.bn + 224, *smean = p.bn + 448, *sinv = p.bn + 672;
 
-    // conv2 / conv3 forward and the conv3 data gradient run on the producer / consumer Winograd kernel (conv_wino2_bf16x6_kernel.h);
-    // shapes it does not cover keep the first-generation / direct kernels
+    // conv2 / conv3 forward and both data gradients run on the producer / consumer Winograd kernel (conv_wino2_bf16x6_kernel.h);
+    // shapes it does not cover keep the first-generation / direct kernels.  The forward needs both maps to fit.
     Wino2Geo geo2, geo3;
-    const bool w2ok_all = wino2_geo(B, 32, d.wp1, 64, &geo2) && wino2_geo(B, 16, d.wp2, 128, &geo3);
-    const bool w2c2 = w2ok_all && (sir_wino2_mask() & 1), w2c3 = w2ok_all && (sir_wino2_mask() & 2);
-    const bool f16c2 = w2c2 && (sir_f16_mask() & 1), f16c3 = w2c3 && (sir_f16_mask() & 2);     // forward stages on the f16x3 arithmetic
+    const bool w2 = sir_conv_stage_fits(2, wino2_geo(B, 32, d.wp1, 64, &geo2)) && sir_conv_stage_fits(3, wino2_geo(B, 16, d.wp2, 128, &geo3));
     {   // all weight re-layouts of this step, the backward's included (the weights do not change before it runs)
         SirProfScope prof(h, SIR_K_T_PREP, st);
         PrepJobs pj{};
@@ -277,21 +271,16 @@ extern "C" int sir_model_train_fwd(sir_handle* h, const sir_model_weights* w, fl
             blocks += nblk; ++nj;
         };
         pj.status = h->status;
-        add(f16c2 ? 6 : 4, w->conv_w[1], p.wcb2, 32, 64, (32 * 16 * 64 + 255) / 256);       // conv2 forward: Winograd frequencies
-        add(f16c3 ? 6 : 4, w->conv_w[2], p.wcb3, 64, 128, (64 * 16 * 128 + 255) / 256);     // conv3 forward: Winograd frequencies
-        if (!w2c3) add(1, w->conv_w[2], p.wcb3d, 64, 128, (64 * 9 * 128 + 255) / 256);
-        {   // conv2 data gradient (64 -> 32): the second-generation Winograd kernel on f16x3 (its transform feeds only 32 outputs -- on
-            // bf16x6 that lost to the direct kernel, with half the matrix products it wins: profiles/r04/bench_conv_f16x3.txt), else direct
-            Wino2Geo geo2b;
-            const bool f16d2 = wino2_geo(B, 32, d.wp1, 64, &geo2b) && (sir_wino2_mask() & 8) && (sir_f16_mask() & 16);
-            if (f16d2) add(7, w->conv_w[1], p.wcb2t, 32, 64, (64 * 16 * 32 + 255) / 256);
-            else add(2, w->conv_w[1], p.wcb2t, 32, 64, (32 * 9 * 64 + 255) / 256);
-        }
-        {   // conv3 data gradient: Winograd frequencies of the flipped taps (f16x3 planes when that stage runs on them)
-            Wino2Geo geo3b;
-            const bool f16d3 = wino2_geo(B, 16, d.wp2, 128, &geo3b) && (sir_wino2_mask() & 4) && (sir_f16_mask() & 4);
-            add(f16d3 ? 7 : 5, w->conv_w[2], p.wcb3t, 64, 128, (128 * 16 * 64 + 255) / 256);
-        }
+        // (f16x3 planes for the second-generation Winograd kernel, bf16x3 planes for the first-generation / direct fallbacks)
+        add(w2 ? 6 : 4, w->conv_w[1], p.wcb2, 32, 64, (32 * 16 * 64 + 255) / 256);       // conv2 forward: Winograd frequencies
+        add(w2 ? 6 : 4, w->conv_w[2], p.wcb3, 64, 128, (64 * 16 * 128 + 255) / 256);     // conv3 forward: Winograd frequencies
+        if (!w2) add(1, w->conv_w[2], p.wcb3d, 64, 128, (64 * 9 * 128 + 255) / 256);
+        // conv2 data gradient (64 -> 32): the second-generation Winograd kernel (its transform feeds only 32 outputs -- on bf16x6 that
+        // lost to the direct kernel, on f16x3 with half the matrix products it wins: profiles/r04/bench_conv_f16x3.txt), else direct
+        if (dgrad2_wino(d)) add(7, w->conv_w[1], p.wcb2t, 32, 64, (64 * 16 * 32 + 255) / 256);
+        else add(2, w->conv_w[1], p.wcb2t, 32, 64, (32 * 9 * 64 + 255) / 256);
+        // conv3 data gradient: Winograd frequencies of the flipped taps
+        add(dgrad3_wino(d) ? 7 : 5, w->conv_w[2], p.wcb3t, 64, 128, (128 * 16 * 64 + 255) / 256);
         for (int dir = 0; dir < 2; ++dir) {
             add(0, w->gru_w_ih[dir], p.wsl0 + (size_t)dir * 2 * 768 * 1024, 1024, 768, 384);
             add(0, w->gru_w_ih[2 + dir], p.wsl1 + (size_t)dir * 2 * 768 * 512, 512, 768, 192);
@@ -326,10 +315,7 @@ extern "C" int sir_model_train_fwd(sir_handle* h, const sir_model_weights* w, fl
     // conv2 block: raw conv + partial statistics on MFMA, finalize, BN+ReLU+pool
     {
         { SirProfScope prof(h, SIR_K_T_CONV2, st);
-        if (f16c2)
-            SIR_HIP_TRY((launch_conv_wino2<32, 64, 2, 0, 3, true>(st, &h->attr_wino2[7], (const float*)p.a1, (const unsigned short*)p.wcb2, (const float*)nullptr,
-                                                                (const float*)nullptr, p.z2, B, 32, d.wp1, p.stats, h->zero_page, h->num_cus)));
-        else if (w2c2)
+        if (w2)
             SIR_HIP_TRY((launch_conv_wino2<32, 64, 2>(st, &h->attr_wino2[2], (const float*)p.a1, (const unsigned short*)p.wcb2, (const float*)nullptr,
                                                     (const float*)nullptr, p.z2, B, 32, d.wp1, p.stats, h->zero_page, h->num_cus)));
         else
@@ -337,7 +323,7 @@ extern "C" int sir_model_train_fwd(sir_handle* h, const sir_model_weights* w, fl
                                (const unsigned short*)p.wcb2, (const float*)nullptr, (const float*)nullptr, p.z2, 32, d.wp1, 16, d.wp2, p.stats);
         }
         SirProfScope prof(h, SIR_K_T_BN2, st);
-        hipLaunchKernelGGL(bn_finalize_kernel, dim3(64), dim3(256), 0, st, (const float2*)p.stats, w2c2 ? (int)wino2_stat_blocks(B, 32, d.wp1, h->num_cus) : d.c2wx * B, 64,
+        hipLaunchKernelGGL(bn_finalize_kernel, dim3(64), dim3(256), 0, st, (const float2*)p.stats, w2 ? (int)wino2_stat_blocks(B, 32, d.wp1, h->num_cus) : d.c2wx * B, 64,
                            (double)B * 32 * d.wp1, w->bn_w[1], w->bn_b[1], bn_running_mean[1], bn_running_var[1], bn_momentum,
                            scale + 32, shift + 32, smean + 32, sinv + 32);
         hipLaunchKernelGGL(bn_relu_pool_kernel<false>, dim3(grid_for((size_t)B * 16 * d.wp2 * 16)), dim3(256), 0, st, p.z2,
@@ -345,10 +331,7 @@ extern "C" int sir_model_train_fwd(sir_handle* h, const sir_model_weights* w, fl
     }
     {
         { SirProfScope prof(h, SIR_K_T_CONV3, st);
-        if (f16c3)
-            SIR_HIP_TRY((launch_conv_wino2<64, 128, 2, 0, 3, true>(st, &h->attr_wino2[8], (const float*)p.a2, (const unsigned short*)p.wcb3, (const float*)nullptr,
-                                                                 (const float*)nullptr, p.z3, B, 16, d.wp2, p.stats, h->zero_page, h->num_cus)));
-        else if (w2c3)
+        if (w2)
             SIR_HIP_TRY((launch_conv_wino2<64, 128, 2>(st, &h->attr_wino2[3], (const float*)p.a2, (const unsigned short*)p.wcb3, (const float*)nullptr,
                                                      (const float*)nullptr, p.z3, B, 16, d.wp2, p.stats, h->zero_page, h->num_cus)));
         else
@@ -356,7 +339,7 @@ extern "C" int sir_model_train_fwd(sir_handle* h, const sir_model_weights* w, fl
                                (const unsigned short*)p.wcb3d, (const float*)nullptr, (const float*)nullptr, p.z3, 16, d.wp2, 8, d.wp3, p.stats);
         }
         SirProfScope prof(h, SIR_K_T_BN3, st);
-        hipLaunchKernelGGL(bn_finalize_kernel, dim3(128), dim3(256), 0, st, (const float2*)p.stats, w2c3 ? (int)wino2_stat_blocks(B, 16, d.wp2, h->num_cus) : d.c3fx * B, 128,
+        hipLaunchKernelGGL(bn_finalize_kernel, dim3(128), dim3(256), 0, st, (const float2*)p.stats, w2 ? (int)wino2_stat_blocks(B, 16, d.wp2, h->num_cus) : d.c3fx * B, 128,
                            (double)B * 16 * d.wp2, w->bn_w[2], w->bn_b[2], bn_running_mean[2], bn_running_var[2], bn_momentum,
                            scale + 96, shift + 96, smean + 96, sinv + 96);
         hipLaunchKernelGGL(bn_relu_pool_kernel<true>, dim3(grid_for((size_t)B * 8 * d.wp3 * 32)), dim3(256), 0, st, p.z3,
@@ -447,43 +430,30 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
     const float* y0in = dropout_p > 0.0f ? p.y0d : p.y0;
     const float gscale = sir_bwd_loss_scale(B), unscale = 1.0f / gscale;
 
-    // ---- two-stream form (SIR_BWD_STREAMS, default 3; A/B in profiles/r04/ab_bwd_streams.txt) -------------------------------
+    // ---- two-stream form (A/B in profiles/r04/ab_bwd_streams.txt) ------------------------------------------------------------
     // The launches that nothing downstream waits for -- the GRU weight gradients of both layers and the two convolution weight
     // gradients, with their slab reduces -- go to a stream owned by the handle.  Each GRU weight-gradient GEMM forks right behind
-    // ITS layer's BPTT (bit 1 of the mode): layer 1's then runs beside layer 0's BPTT, which occupies half of the CUs and leaves the
-    // rest idle.  Each convolution weight gradient forks behind the BatchNorm backward that produces its dz (bit 0).  One join
-    // before the call returns.  The chain dX -> BN3 -> dgrad3 -> BN2 -> dgrad2 -> conv1 stays on the caller's stream.  In the split
-    // form (SIR_BWD_HEAD_GRU / SIR_BWD_CNN, data parallel) the first half joins before it returns -- its gradients are reduced
-    // next.  Mode 1 (round 4's first experiment): the GRU GEMMs fork once, behind the last dX.
-    if (sir_bwd_streams() && !h->bwd_side) {                 // (first use: the only allocating step, as for the exchange buffers)
+    // ITS layer's BPTT: layer 1's then runs beside layer 0's BPTT, which keeps one workgroup on half of the CUs
+    // (gru_bwd_quad_kernel.h) and leaves the rest idle.  Each convolution weight gradient forks behind the BatchNorm backward that
+    // produces its dz.  One join before the call returns.  The chain dX -> BN3 -> dgrad3 -> BN2 -> dgrad2 -> conv1 stays on the
+    // caller's stream.  In the split form (SIR_BWD_HEAD_GRU / SIR_BWD_CNN, data parallel) the first half joins before it returns --
+    // its gradients are reduced next.
+    if (!h->bwd_side) {                                      // (first use: the only allocating step, as for the exchange buffers)
         SIR_HIP_TRY(hipStreamCreateWithFlags(&h->bwd_side, hipStreamNonBlocking));
         for (auto& e : h->bwd_ev) SIR_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
     if (!h->attr_tn) {
-        SIR_HIP_TRY(hipFuncSetAttribute((const void*)gemm_tn_bf16x6_kernel<true, TN_BM_DW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tn_lds_bytes(true, TN_BM_DW)));
-        SIR_HIP_TRY(hipFuncSetAttribute((const void*)gemm_tn_bf16x6_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TN_LDS_BYTES));
-        SIR_HIP_TRY(hipFuncSetAttribute((const void*)gemm_tn_bf16x6_kernel<false, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TN_LDS_BYTES_64));
         SIR_HIP_TRY(hipFuncSetAttribute((const void*)gemm_tn2_bf16x6_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tn2_lds_bytes(true)));
         SIR_HIP_TRY(hipFuncSetAttribute((const void*)gemm_tn2_bf16x6_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tn2_lds_bytes(false)));
         SIR_HIP_TRY(hipFuncSetAttribute((const void*)gemm_tn2_bf16x6_kernel<false, 0, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tn2_lds_bytes(false, 64)));
-        SIR_HIP_TRY(hipFuncSetAttribute((const void*)gemm_tn2_bf16x6_kernel<true, 0, TN2_BM, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tn2_lds_bytes(true)));
-        SIR_HIP_TRY(hipFuncSetAttribute((const void*)gemm_tn2_bf16x6_kernel<false, 0, TN2_BM, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tn2_lds_bytes(false)));
-        SIR_HIP_TRY(hipFuncSetAttribute((const void*)gemm_tn2_bf16x6_kernel<false, 0, 64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tn2_lds_bytes(false, 64)));
         h->attr_tn = true;
     }
     // (while every kernel is being timed -- sir_profile_enable mode 1 -- the backward stays on one stream: per-kernel times of overlapped
     // launches would say nothing about the kernels)
-    const bool two = sir_bwd_streams() && h->bwd_side != nullptr && h->prof_mode != 1;
-    hipStream_t side = two ? h->bwd_side : st;
-    // SIR_BWD_STREAMS bits: 1 = the convolution weight gradients fork to the side stream (behind the BatchNorm backward that produces
-    // their dz), and in mode 1 the GRU weight-gradient GEMMs follow behind the last dX; 2 = the GRU weight-gradient GEMMs leave the
-    // caller's stream right behind THEIR layer's BPTT -- layer 1's then runs beside layer 0's BPTT, which keeps one workgroup on
-    // half of the CUs (gru_bwd_quad_kernel.h) and leaves the rest idle; 3 = both
-    const bool dw_beside = two && (sir_bwd_streams() & 2);
-    const bool fork_conv = two && (sir_bwd_streams() & 1);
-    const bool defer_dw = two && !dw_beside && part == SIR_BWD_ALL;
+    const bool two = h->bwd_side != nullptr && h->prof_mode != 1;
+    hipStream_t side = two ? h->bwd_side : st;            // stream of the weight gradients
 
-    // all four weight-gradient GEMMs of a GRU layer (2 directions x {W_ih, W_hh}) in one bf16x6 launch + the slab reduce
+    // all four weight-gradient GEMMs of a GRU layer (2 directions x {W_ih, W_hh}) in one launch + the slab reduce
     auto launch_dw = [&](int layer, hipStream_t s_) -> int {
         const float* dgi_l = layer ? p.dgi1 : p.dgi;
         const float* dgh_l = layer ? p.dgh1 : p.dgh;
@@ -491,7 +461,6 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
         const float* xin = layer ? y0in : p.x0;
         const int in_sz = layer ? 512 : 1024;
         SirProfScope prof(h, layer ? SIR_K_B_DW1 : SIR_K_B_DW0, s_);
-        const bool tn2_dw = sir_tn2_mask() & 1;
         TnJobs jb{};
         float* outs[4];
         size_t sizes[4];
@@ -509,7 +478,7 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
         }
         for (int j = 0; j < 4; ++j) {
             jb.tile0[j] = tiles;
-            tiles += (768 / (tn2_dw ? TN2_BM : TN_BM_DW)) * ((jb.N[j] + TN_BN - 1) / TN_BN);
+            tiles += (768 / TN2_BM) * ((jb.N[j] + TN_BN - 1) / TN_BN);
             sizes[j] = (size_t)768 * jb.N[j];
         }
         jb.tile0[4] = tiles;
@@ -518,16 +487,12 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
         tn_x6_plan(M, in_sz, &tiles_chk, &kchunk, &nsplit, &need);
         size_t pos = 0;
         for (int j = 0; j < 4; ++j) {
-            jb.slab[j] = (dw_beside ? p.slab2 : p.slab) + pos;
+            jb.slab[j] = (two ? p.slab2 : p.slab) + pos;
             jb.slab_stride[j] = sizes[j];
             pos += sizes[j] * nsplit;
         }
-        if (tn2_dw && (sir_f16_mask() & 8))                     // f16x3: the gate gradients carry the loss scale
-            hipLaunchKernelGGL((gemm_tn2_bf16x6_kernel<true, 0, TN2_BM, true>), dim3(tiles, nsplit), dim3(TN2_THREADS), tn2_lds_bytes(true), s_, jb, 768, M, kchunk, S);
-        else if (tn2_dw)
-            hipLaunchKernelGGL(gemm_tn2_bf16x6_kernel<true>, dim3(tiles, nsplit), dim3(TN2_THREADS), tn2_lds_bytes(true), s_, jb, 768, M, kchunk, S);
-        else
-            hipLaunchKernelGGL((gemm_tn_bf16x6_kernel<true, TN_BM_DW>), dim3(tiles, nsplit), dim3(512), tn_lds_bytes(true, TN_BM_DW), s_, jb, 768, M, kchunk, S);
+        // (f16x3: the gate gradients carry the loss scale)
+        hipLaunchKernelGGL(gemm_tn2_bf16x6_kernel<true>, dim3(tiles, nsplit), dim3(TN2_THREADS), tn2_lds_bytes(true), s_, jb, 768, M, kchunk, S);
         SlabJobs sj{};
         for (int j = 0; j < 4; ++j) { sj.src[j] = jb.slab[j]; sj.out[j] = outs[j]; sj.n[j] = sizes[j]; }
         hipLaunchKernelGGL(slab_reduce_jobs_kernel, dim3(grid_for(sizes[0]), 4), dim3(256), 0, s_, sj, nsplit, unscale);
@@ -552,7 +517,7 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
         const int in_sz = layer ? 512 : 1024;
         { SirProfScope prof(h, layer ? SIR_K_B_GRU1 : SIR_K_B_GRU0, st);
         if (sir_cluster_enter(h, st) != SIR_OK) return SIR_EHIP;
-        rc = sir_launch_gru_bwd_pair(h, st, dy, gates, yout, w->gru_w_hh[2 * layer], w->gru_w_hh[2 * layer + 1], dgi_l, dgh_l, bsum_i, bsum_h,
+        rc = sir_launch_gru_bwd_quad(h, st, dy, gates, yout, w->gru_w_hh[2 * layer], w->gru_w_hh[2 * layer + 1], dgi_l, dgh_l, bsum_i, bsum_h,
                                      B, S, (const char*)p.wr4 + (size_t)(2 * layer) * GRU_FRAG_BYTES,
                                      (const char*)p.wr4 + (size_t)(2 * layer + 1) * GRU_FRAG_BYTES);
         if (rc != SIR_OK) return rc;
@@ -560,21 +525,20 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
         // bias gradients first: bsum_* alias the slab area used below
         hipLaunchKernelGGL(gru_bias_colsum_kernel, dim3(24, 2), dim3(256), 0, st, (const float*)bsum_i, (const float*)bsum_h, B,
                            g->gru_b_ih[2 * layer], g->gru_b_ih[2 * layer + 1], g->gru_b_hh[2 * layer], g->gru_b_hh[2 * layer + 1], unscale); }
-        if (dw_beside) {                                     // (layer 0's GEMM queues behind layer 1's on the side stream: they share the slabs)
+        if (two) {                                           // (layer 0's GEMM queues behind layer 1's on the side stream: they share the slabs)
             SIR_HIP_TRY(hipEventRecord(h->bwd_ev[4 + layer], st));
             SIR_HIP_TRY(hipStreamWaitEvent(side, h->bwd_ev[4 + layer], 0));
             // Layer 0's saved gates and outputs (65 MB) were written early in the forward and have left the 256 MB last-level cache by now;
             // layer 1's are still there, and layer 0's BPTT -- a latency chain whose polls share the L2 channels with its input misses --
             // pays 16-26 us for the difference (profiles/r04/ab_bptt.txt).  A read-and-drop pass on the side stream, beside layer 1's dX on
-            // the caller's, brings them back: step -28 .. -40 us (SIR_BPTT_TOUCH=0 turns it off).  The same for the raw conv outputs ahead
-            // of the BatchNorm backward was measured and LOSES (those kernels are bandwidth-bound: the reads are only moved earlier).
-            static const bool touch = !getenv("SIR_BPTT_TOUCH") || atoi(getenv("SIR_BPTT_TOUCH")) != 0;
-            if (touch && layer == 1)
+            // the caller's, brings them back: step -28 .. -40 us.  The same for the raw conv outputs ahead of the BatchNorm backward was
+            // measured and LOSES (those kernels are bandwidth-bound: the reads are only moved earlier).
+            if (layer == 1)
                 hipLaunchKernelGGL(cache_touch_kernel, dim3(256), dim3(256), 0, side, (const float4*)p.g0, (size_t)M * 2048 / 4, (const float4*)p.y0,
                                    (size_t)M * 512 / 4, p.small);
             rc = launch_dw(layer, side);
             if (rc != SIR_OK) return rc;
-        } else if (!defer_dw) { rc = launch_dw(layer, st); if (rc != SIR_OK) return rc; }
+        } else { rc = launch_dw(layer, st); if (rc != SIR_OK) return rc; }
         // gradient wrt the layer input: dgi [M][1536] x [W_ih; W_ih_reverse] [1536][in]
         SirProfScope prof(h, layer ? SIR_K_B_DX1 : SIR_K_B_DX0, st);
         float* dxin = layer ? p.dy0 : p.dx0;
@@ -594,62 +558,38 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
                 jn.drop_p = 0.0f;                                // (the dropout mask is applied by the add)
                 jn.slab[0] = p.slab; jn.slab_stride[0] = (size_t)M * in_sz;
                 jn.tile0[1] = ntiles;
-                if (sir_f16_mask() & 8)
-                    hipLaunchKernelGGL((gemm_tn2_bf16x6_kernel<false, 0, TN2_BM, true>), dim3(ntiles, 2), dim3(TN2_THREADS), tn2_lds_bytes(false), st, jn, M, 1536, 768, 1);
-                else
-                    hipLaunchKernelGGL(gemm_tn2_bf16x6_kernel<false>, dim3(ntiles, 2), dim3(TN2_THREADS), tn2_lds_bytes(false), st, jn, M, 1536, 768, 1);
+                hipLaunchKernelGGL(gemm_tn2_bf16x6_kernel<false>, dim3(ntiles, 2), dim3(TN2_THREADS), tn2_lds_bytes(false), st, jn, M, 1536, 768, 1);
                 const bool drop = layer == 1 && dropout_p > 0.0f;
                 hipLaunchKernelGGL(dx_halves_add_kernel, dim3(grid_for((size_t)M * in_sz / 4)), dim3(256), 0, st, (const float*)p.slab, (size_t)M * in_sz / 4,
                                    dxin, drop ? dropout_p : 0.0f, (unsigned long long)dropout_seed);
             } else if (ntiles < 160) {                       // too few 128-row tiles to fill the CUs: 64-row tiles
                 ntiles = ((M + 63) / 64) * ntn;
                 jn.tile0[1] = ntiles;
-                if ((sir_tn2_mask() & 4) && (sir_f16_mask() & 8))
-                    hipLaunchKernelGGL((gemm_tn2_bf16x6_kernel<false, 0, 64, true>), dim3(ntiles, 1), dim3(TN2_THREADS), tn2_lds_bytes(false, 64), st, jn, M, 1536, 1536, 1);
-                else if (sir_tn2_mask() & 4)
-                    hipLaunchKernelGGL((gemm_tn2_bf16x6_kernel<false, 0, 64>), dim3(ntiles, 1), dim3(TN2_THREADS), tn2_lds_bytes(false, 64), st, jn, M, 1536, 1536, 1);
-                else
-                    hipLaunchKernelGGL((gemm_tn_bf16x6_kernel<false, 64>), dim3(ntiles, 1), dim3(512), TN_LDS_BYTES_64, st, jn, M, 1536, 1536, 1);
+                hipLaunchKernelGGL((gemm_tn2_bf16x6_kernel<false, 0, 64>), dim3(ntiles, 1), dim3(TN2_THREADS), tn2_lds_bytes(false, 64), st, jn, M, 1536, 1536, 1);
             } else {
                 jn.tile0[1] = ntiles;
-                if ((sir_tn2_mask() & 2) && (sir_f16_mask() & 8))
-                    hipLaunchKernelGGL((gemm_tn2_bf16x6_kernel<false, 0, TN2_BM, true>), dim3(ntiles, 1), dim3(TN2_THREADS), tn2_lds_bytes(false), st, jn, M, 1536, 1536, 1);
-                else if (sir_tn2_mask() & 2)
-                    hipLaunchKernelGGL(gemm_tn2_bf16x6_kernel<false>, dim3(ntiles, 1), dim3(TN2_THREADS), tn2_lds_bytes(false), st, jn, M, 1536, 1536, 1);
-                else
-                    hipLaunchKernelGGL(gemm_tn_bf16x6_kernel<false>, dim3(ntiles, 1), dim3(512), TN_LDS_BYTES, st, jn, M, 1536, 1536, 1);
+                hipLaunchKernelGGL(gemm_tn2_bf16x6_kernel<false>, dim3(ntiles, 1), dim3(TN2_THREADS), tn2_lds_bytes(false), st, jn, M, 1536, 1536, 1);
             }
         }
         KCHECK();
     }
-    if (defer_dw) {
-        // fork: the weight-gradient GEMMs of both layers behind the last dX (their slabs reuse the area the dX halves and the bias
-        // partial sums used on the caller's stream)
-        SIR_HIP_TRY(hipEventRecord(h->bwd_ev[0], st));
-        SIR_HIP_TRY(hipStreamWaitEvent(side, h->bwd_ev[0], 0));
-        for (int layer = 1; layer >= 0; --layer) { rc = launch_dw(layer, side); if (rc != SIR_OK) return rc; }
-        KCHECK();
     }
-    }
-    if (dw_beside) {                                         // join: the GRU gradients are final on the caller's stream (the conv chain
+    if (two) {                                         // join: the GRU gradients are final on the caller's stream (the conv chain
         SIR_HIP_TRY(hipEventRecord(h->bwd_ev[3], side));     // below does not depend on them, but the data-parallel caller reduces them next)
         if (part == SIR_BWD_HEAD_GRU) SIR_HIP_TRY(hipStreamWaitEvent(st, h->bwd_ev[3], 0));
     }
     if (part == SIR_BWD_HEAD_GRU) return SIR_OK;
-    if (fork_conv && !defer_dw) {                                  // SIR_BWD_CNN of the split form: the side stream starts behind the first half
+    if (two) {                                               // SIR_BWD_CNN of the split form: the side stream starts behind the first half
         SIR_HIP_TRY(hipEventRecord(h->bwd_ev[0], st));
         SIR_HIP_TRY(hipStreamWaitEvent(side, h->bwd_ev[0], 0));
     }
 
-    hipStream_t cside = fork_conv ? side : st;               // stream of the convolution weight gradients
     // ---- conv3 block -------------------------------------------------------------------------
     if (!h->attr_wgrad) {
         SIR_HIP_TRY(hipFuncSetAttribute((const void*)conv_wgrad_bf16x6_kernel<64, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         SIR_HIP_TRY(hipFuncSetAttribute((const void*)conv_wgrad_bf16x6_kernel<32, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         SIR_HIP_TRY(hipFuncSetAttribute((const void*)conv_wgrad_wino_bf16x6_kernel<64, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WgwCfg<64, 128>::lds_bytes));
         SIR_HIP_TRY(hipFuncSetAttribute((const void*)conv_wgrad_wino_bf16x6_kernel<32, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WgwCfg<32, 64>::lds_bytes));
-        SIR_HIP_TRY(hipFuncSetAttribute((const void*)conv_wgrad_wino_bf16x6_kernel<64, 128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WgwCfg<64, 128>::lds_bytes));
-        SIR_HIP_TRY(hipFuncSetAttribute((const void*)conv_wgrad_wino_bf16x6_kernel<32, 64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WgwCfg<32, 64>::lds_bytes));
         h->attr_wgrad = true;
     }
     {
@@ -667,36 +607,32 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
                                (const float*)p.dx0, scale + 96, shift + 96, smean + 96, sinv + 96, mdy + 96, mdyx + 96, p.dz3, B, 16,
                                d.wp2, 128, 8, d.wp3);
         }
-        if (fork_conv) {
+        if (two) {
             SIR_HIP_TRY(hipEventRecord(h->bwd_ev[1], st));
             SIR_HIP_TRY(hipStreamWaitEvent(side, h->bwd_ev[1], 0));
         }
         {
-            SirProfScope prof(h, SIR_K_B_WGRAD3, cside);
-            if ((sir_wgw_mask() & 2) && (size_t)B * 16 * d.wp2 * 128 * 4 < ((size_t)1 << 31)) {      // (32-bit buffer offsets)
+            SirProfScope prof(h, SIR_K_B_WGRAD3, side);
+            if (sir_conv_stage_fits(3, (size_t)B * 16 * d.wp2 * 128 * 4 < ((size_t)1 << 31))) {      // (32-bit buffer offsets)
                 // Winograd form: 16 products per tile and channel pair instead of 36 (wgrad_wino_bf16x6_kernel.h)
                 using Cfg3 = WgwCfg<64, 128>;
                 const int strips = wgrad_wino_strips(B, 16, d.wp2, Cfg3::TPS, Cfg3::groups, h->num_cus);
-                if (sir_f16_mask() & 32)
-                    hipLaunchKernelGGL((conv_wgrad_wino_bf16x6_kernel<64, 128, true>), dim3(Cfg3::groups * strips), dim3(WGW_THREADS), Cfg3::lds_bytes, cside,
-                                       (const float*)p.dz3, (const float*)p.a2, p.slab, B, 16, d.wp2);
-                else
-                hipLaunchKernelGGL((conv_wgrad_wino_bf16x6_kernel<64, 128>), dim3(Cfg3::groups * strips), dim3(WGW_THREADS), Cfg3::lds_bytes, cside,
+                hipLaunchKernelGGL((conv_wgrad_wino_bf16x6_kernel<64, 128>), dim3(Cfg3::groups * strips), dim3(WGW_THREADS), Cfg3::lds_bytes, side,
                                    (const float*)p.dz3, (const float*)p.a2, p.slab, B, 16, d.wp2);
                 float* part = p.slab + (size_t)strips * 16 * 128 * 64;
-                hipLaunchKernelGGL(wgrad_wino_sum_kernel, dim3((16 * 128 * 64 / 4 + 255) / 256), dim3(256), 0, cside, (const float*)p.slab, strips,
+                hipLaunchKernelGGL(wgrad_wino_sum_kernel, dim3((16 * 128 * 64 / 4 + 255) / 256), dim3(256), 0, side, (const float*)p.slab, strips,
                                    16 * 128 * 64 / 4, part);
-                hipLaunchKernelGGL(wgrad_wino_finish_kernel, dim3((128 * 64 + 255) / 256), dim3(256), 0, cside, (const float*)part, 64, 128, g->conv_w[2], unscale);
+                hipLaunchKernelGGL(wgrad_wino_finish_kernel, dim3((128 * 64 + 255) / 256), dim3(256), 0, side, (const float*)part, 64, 128, g->conv_w[2], unscale);
             } else {
             const size_t ldsx = wgrad_x6_lds_bytes(64, 128, d.wp2);
             if (ldsx > 160 * 1024 || d.wp2 > wgrad_x6_max_w(128)) { sir_set_error("sir_model_train_bwd: t_frames too large for the weight-gradient tile"); return SIR_EUNSUPPORTED; }
             const int nslab3 = d.wg3_blocks;                  // one slab per workgroup
-            hipLaunchKernelGGL((conv_wgrad_bf16x6_kernel<64, 128>), dim3(d.wg3_blocks), dim3(512), ldsx, cside, (const float*)p.dz3,
+            hipLaunchKernelGGL((conv_wgrad_bf16x6_kernel<64, 128>), dim3(d.wg3_blocks), dim3(512), ldsx, side, (const float*)p.dz3,
                                (const float*)p.a2, p.slab, 16, d.wp2, d.wg3_rb);
             float* part = p.slab + (size_t)nslab3 * 9 * 128 * 64;
-            hipLaunchKernelGGL(wgrad_reduce_partial_kernel, dim3((9 * 128 * 64 / 4 + 255) / 256, WGR_PARTS), dim3(256), 0, cside,
+            hipLaunchKernelGGL(wgrad_reduce_partial_kernel, dim3((9 * 128 * 64 / 4 + 255) / 256, WGR_PARTS), dim3(256), 0, side,
                                (const float*)p.slab, nslab3, 9 * 128 * 64 / 4, part);
-            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((9 * 128 * 64 + 255) / 256), dim3(256), 0, cside, (const float*)part, WGR_PARTS, 64, 128,
+            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((9 * 128 * 64 + 255) / 256), dim3(256), 0, side, (const float*)part, WGR_PARTS, 64, 128,
                                g->conv_w[2], unscale);
             }
         }
@@ -704,11 +640,7 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
             // data gradient = a 128 -> 64 convolution with the flipped / transposed taps: the Winograd kernel (16 of 36 products), blocks
             // of 8 x 4 tiles for the 16-row map, raw output (train_prep_kernel of the forward built p.wcb3t)
             SirProfScope prof(h, SIR_K_B_DGRAD3, st);
-            Wino2Geo geo3b;
-            if (wino2_geo(B, 16, d.wp2, 128, &geo3b) && (sir_wino2_mask() & 4) && (sir_f16_mask() & 4))     // dz3 carries the loss scale: inside fp16's range
-                SIR_HIP_TRY((launch_conv_wino2<128, 64, 3, 0, 3, true>(st, &h->attr_wino2[9], (const float*)p.dz3, (const unsigned short*)p.wcb3t, (const float*)nullptr,
-                                                                     (const float*)nullptr, p.da2, B, 16, d.wp2, (float2*)nullptr, h->zero_page, h->num_cus)));
-            else if (wino2_geo(B, 16, d.wp2, 128, &geo3b) && (sir_wino2_mask() & 4))
+            if (dgrad3_wino(d))                                  // (dz3 carries the loss scale: inside fp16's range)
                 SIR_HIP_TRY((launch_conv_wino2<128, 64, 3>(st, &h->attr_wino2[4], (const float*)p.dz3, (const unsigned short*)p.wcb3t, (const float*)nullptr,
                                                          (const float*)nullptr, p.da2, B, 16, d.wp2, (float2*)nullptr, h->zero_page, h->num_cus)));
             else
@@ -734,44 +666,39 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
                                (const float*)p.da2, scale + 32, shift + 32, smean + 32, sinv + 32, mdy + 32, mdyx + 32, p.dz2, B, 32,
                                d.wp1, 64, 16, d.wp2);
         }
-        if (fork_conv) {
+        if (two) {
             SIR_HIP_TRY(hipEventRecord(h->bwd_ev[2], st));
             SIR_HIP_TRY(hipStreamWaitEvent(side, h->bwd_ev[2], 0));
         }
         {
-            SirProfScope prof(h, SIR_K_B_WGRAD2, cside);
-            if ((sir_wgw_mask() & 1) && (size_t)B * 32 * d.wp1 * 64 * 4 < ((size_t)1 << 31)) {
+            SirProfScope prof(h, SIR_K_B_WGRAD2, side);
+            if (sir_conv_stage_fits(2, (size_t)B * 32 * d.wp1 * 64 * 4 < ((size_t)1 << 31))) {
                 using Cfg2 = WgwCfg<32, 64>;
                 const int strips = wgrad_wino_strips(B, 32, d.wp1, Cfg2::TPS, Cfg2::groups, h->num_cus);
-                if (sir_f16_mask() & 32)
-                    hipLaunchKernelGGL((conv_wgrad_wino_bf16x6_kernel<32, 64, true>), dim3(Cfg2::groups * strips), dim3(WGW_THREADS), Cfg2::lds_bytes, cside,
-                                       (const float*)p.dz2, (const float*)p.a1, p.slab, B, 32, d.wp1);
-                else
-                hipLaunchKernelGGL((conv_wgrad_wino_bf16x6_kernel<32, 64>), dim3(Cfg2::groups * strips), dim3(WGW_THREADS), Cfg2::lds_bytes, cside,
+                hipLaunchKernelGGL((conv_wgrad_wino_bf16x6_kernel<32, 64>), dim3(Cfg2::groups * strips), dim3(WGW_THREADS), Cfg2::lds_bytes, side,
                                    (const float*)p.dz2, (const float*)p.a1, p.slab, B, 32, d.wp1);
                 float* part = p.slab + (size_t)strips * 16 * 64 * 32;
-                hipLaunchKernelGGL(wgrad_wino_sum_kernel, dim3((16 * 64 * 32 / 4 + 255) / 256), dim3(256), 0, cside, (const float*)p.slab, strips,
+                hipLaunchKernelGGL(wgrad_wino_sum_kernel, dim3((16 * 64 * 32 / 4 + 255) / 256), dim3(256), 0, side, (const float*)p.slab, strips,
                                    16 * 64 * 32 / 4, part);
-                hipLaunchKernelGGL(wgrad_wino_finish_kernel, dim3((64 * 32 + 255) / 256), dim3(256), 0, cside, (const float*)part, 32, 64, g->conv_w[1], unscale);
+                hipLaunchKernelGGL(wgrad_wino_finish_kernel, dim3((64 * 32 + 255) / 256), dim3(256), 0, side, (const float*)part, 32, 64, g->conv_w[1], unscale);
             } else {
             const size_t ldsx = wgrad_x6_lds_bytes(32, 64, d.wp1);
             if (ldsx > 160 * 1024 || d.wp1 > wgrad_x6_max_w(64)) { sir_set_error("sir_model_train_bwd: t_frames too large for the weight-gradient tile"); return SIR_EUNSUPPORTED; }
             const int nslab2 = d.wg2_blocks;                  // one slab per workgroup (its four k-split waves add up in LDS)
-            hipLaunchKernelGGL((conv_wgrad_bf16x6_kernel<32, 64>), dim3(d.wg2_blocks), dim3(512), ldsx, cside, (const float*)p.dz2,
+            hipLaunchKernelGGL((conv_wgrad_bf16x6_kernel<32, 64>), dim3(d.wg2_blocks), dim3(512), ldsx, side, (const float*)p.dz2,
                                (const float*)p.a1, p.slab, 32, d.wp1, d.wg2_rb);
             float* part = p.slab + (size_t)nslab2 * 9 * 64 * 32;
-            hipLaunchKernelGGL(wgrad_reduce_partial_kernel, dim3((9 * 64 * 32 / 4 + 255) / 256, WGR_PARTS), dim3(256), 0, cside,
+            hipLaunchKernelGGL(wgrad_reduce_partial_kernel, dim3((9 * 64 * 32 / 4 + 255) / 256, WGR_PARTS), dim3(256), 0, side,
                                (const float*)p.slab, nslab2, 9 * 64 * 32 / 4, part);
-            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((9 * 64 * 32 + 255) / 256), dim3(256), 0, cside, (const float*)part, WGR_PARTS, 32, 64,
+            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((9 * 64 * 32 + 255) / 256), dim3(256), 0, side, (const float*)part, WGR_PARTS, 32, 64,
                                g->conv_w[1], unscale);
             }
         }
-        if (fork_conv) SIR_HIP_TRY(hipEventRecord(h->bwd_ev[3], side));     // (the side stream's last launch)
+        if (two) SIR_HIP_TRY(hipEventRecord(h->bwd_ev[3], side));     // (the side stream's last launch)
         {
             SirProfScope prof(h, SIR_K_B_DGRAD2, st);
-            Wino2Geo geo2b;
-            if (wino2_geo(B, 32, d.wp1, 64, &geo2b) && (sir_wino2_mask() & 8) && (sir_f16_mask() & 16))
-                SIR_HIP_TRY((launch_conv_wino2<64, 32, 3, 0, 3, true>(st, &h->attr_wino2[10], (const float*)p.dz2, (const unsigned short*)p.wcb2t, (const float*)nullptr,
+            if (dgrad2_wino(d))
+                SIR_HIP_TRY((launch_conv_wino2<64, 32, 3>(st, &h->attr_wino2[5], (const float*)p.dz2, (const unsigned short*)p.wcb2t, (const float*)nullptr,
                                                                     (const float*)nullptr, p.da1, B, 32, d.wp1, (float2*)nullptr, h->zero_page, h->num_cus)));
             else
             hipLaunchKernelGGL((conv3x3_bf16x6_ns_kernel<64, 32, 4, 2, 2, 0, 4>), dim3(d.c2gx, 1, B), dim3(256), conv_ns_lds_bytes(4, 2), st,

@@ -70,12 +70,12 @@ struct sir_handle {
     // therefore chained: one on another stream first waits for the previous one's completion event (sir_cluster_enter).
     hipEvent_t cluster_done;
     hipStream_t cluster_stream;        // stream of the latest cluster launch (compared, never dereferenced)
-    bool cluster_pending, cluster_seen, cluster_multi, cluster_always;
+    bool cluster_pending, cluster_seen, cluster_multi;
     int cluster_run;                   // chained mode: launches in a row that came from cluster_stream
     // hipFuncSetAttribute(MaxDynamicSharedMemorySize) latches, per handle = per device (a process-wide static would skip
     // the second device of a process that drives several)
-    bool attr_gemm_v3, attr_gru_quad, attr_gru_bwd, attr_gru_bwd_quad, attr_tn, attr_wgrad;
-    bool attr_wino2[16];               // conv3x3_wino2_bf16x6_kernel instantiations (model_infer.hip / model_train.hip index them)
+    bool attr_gemm_v3, attr_gru_quad, attr_gru_bwd_quad, attr_tn, attr_wgrad;
+    bool attr_wino2[6];                // conv3x3_wino2_bf16x6_kernel instantiations (model_infer.hip: 0, 1; model_train.hip: 2 .. 5)
     float* zero_page;                  // 4 KB of zeros: DMA source of the second-generation Winograd kernel's out-of-image pixels
     int num_cus;                       // persistent kernels launch one workgroup per CU
     // Exchange-granule buffers of the cluster kernels (GRU recurrences).  They are OWNED by the handle (hipMalloc), one per
@@ -90,14 +90,14 @@ struct sir_handle {
     XbufEntry xbufs[16];
     unsigned long long xbuf_clock;
     unsigned long long xbuf_evictions;   // LRU evictions so far (each costs a device-synchronising hipFree + hipMalloc on the launch path)
-    // second stream of the training backward (SIR_BWD_STREAMS=1, model_train.hip): the off-chain weight-gradient launches; created on
-    // first use.  ev: 0 fork behind the GRU part, 1 / 2 dz3 / dz2 ready, 3 join
+    // second stream of the training backward (model_train.hip): the off-chain weight-gradient launches; created on first use.
+    // ev: 0 fork behind the GRU part, 1 / 2 dz3 / dz2 ready, 3 join, 4 / 5 GRU layer 0 / 1 BPTT done
     hipStream_t bwd_side;
     hipEvent_t bwd_ev[6];
 };
 
 // granule buffer + launch epoch for a cluster kernel launched on `st`; allocates / grows / zeroes the buffer when needed.
-// `kind` separates kernels with different granule formats (gru_quad_kernel.h / gru_bwd_pair_kernel.h).
+// `kind` separates kernels with different granule formats (gru_quad_kernel.h / gru_bwd_quad_kernel.h).
 static inline int sir_xbuf_acquire(sir_handle* h, hipStream_t st, int kind, size_t bytes, unsigned mask, void** xbuf, unsigned* epoch) {
     sir_handle::XbufEntry* e = nullptr;
     for (auto& x : h->xbufs)
@@ -157,21 +157,16 @@ static inline int sir_cluster_leave(sir_handle* h, hipStream_t st) {
         if (hipEventRecord(h->cluster_done, st) != hipSuccess) return SIR_EHIP;
         h->cluster_pending = true;
         h->cluster_run = (h->cluster_stream == st) ? h->cluster_run + 1 : 0;
-        if (h->cluster_run >= 64 && !h->cluster_always) { h->cluster_multi = false; h->cluster_pending = false; }
+        if (h->cluster_run >= 64) { h->cluster_multi = false; h->cluster_pending = false; }
     }
     h->cluster_stream = st;
     h->cluster_seen = true;
     return SIR_OK;
 }
 
-// SIR_WINO2 (default 15): bit 0 = conv2, bit 1 = conv3, bit 2 = conv3 data gradient, bit 3 = conv2 data gradient (f16x3 only) on the producer / consumer Winograd kernel
-// (conv_wino2_bf16x6_kernel.h); a cleared bit keeps the first-generation / direct kernel of that stage (A/B on one box:
-// devtools/gpu_ab_wino2.sh, profiles/r03/ab_wino2.txt)
-int sir_wino2_mask();
-int sir_wgw_mask();      // SIR_WGW: convolution weight gradients in Winograd form: bit 0 = conv2, bit 1 = conv3 (default 3)
-int sir_tn2_mask();      // SIR_TN2: GRU backward GEMMs on the producer / consumer kernel: bit 0 = dW, bit 1 = dX on 128-row tiles, bit 2 = dX on 64-row tiles, bit 3 = a dX that would take 64-row tiles runs as two K halves on 128-row tiles instead (default 15)
-int sir_f16_mask();      // SIR_F16: stages on the f16x3 arithmetic (f16_split.h) instead of bf16x6: bit 0 = conv2 forward, bit 1 = conv3 forward (inference and training), bit 2 = conv3 data gradient, bit 3 = GRU backward GEMMs (dW, dX), bit 4 = conv2 data gradient (on the second-generation Winograd kernel: needs SIR_WINO2 bit 3), bit 5 = convolution weight gradients (default 63)
-int sir_bwd_streams();   // SIR_BWD_STREAMS: which of the backward's weight-gradient launches run on a second, handle-owned stream (default 3; model_train.hip)
+// conv stage `conv` (2 or 3) runs on its Winograd kernel (second-generation forward / data gradient, Winograd weight gradient) if
+// `shape_ok` -- else on the first-generation / direct fallback.  Test-only SIR_CONV_FALLBACK: 1 = conv2's stages do not fit, 2 = none do.
+bool sir_conv_stage_fits(int conv, bool shape_ok);
 
 int sir_check_hip(hipError_t e, const char* what);
 
@@ -213,15 +208,12 @@ int sir_features_launch(sir_handle* h, const void* wave, int wave_dtype, int64_t
                         float* db_out, void* workspace, size_t workspace_bytes, const sir_augment* aug,
                         hipStream_t stream);
 
-// GRU recurrences (gru_quad.hip: forward, clusters of four workgroups on the matrix cores; gru_pair.hip: BPTT, pairs of
-// workgroups).  Both write h->status if an exchange spin times out.
+// GRU recurrences (gru_quad.hip: forward and BPTT, clusters of four workgroups on the matrix cores).  Both write h->status if an
+// exchange spin times out.
 int sir_launch_gru_quad(sir_handle* h, hipStream_t st, bool save, const float* gi, const float* whh0, const float* whh1, const float* bhh0,
                         const float* bhh1, float* y, int B, int S, float* gates,
                         unsigned short* yplanes = nullptr, const void* wfrag0 = nullptr, const void* wfrag1 = nullptr);
 void sir_prep_whh_quad(hipStream_t st, const float* whh, void* frag);     // -> GRU_FRAG_BYTES (gru_frag_prep.h)
-int sir_launch_gru_bwd_pair(sir_handle* h, hipStream_t st, const float* dy, const float* gates, const float* y, const float* whh0,
-                            const float* whh1, float* dgi, float* dgh, float* bsum_i, float* bsum_h, int B, int S,
-                            const void* wfrag0 = nullptr, const void* wfrag1 = nullptr);
 int sir_launch_gru_bwd_quad(sir_handle* h, hipStream_t st, const float* dy, const float* gates, const float* y, const float* whh0,
                             const float* whh1, float* dgi, float* dgh, float* bsum_i, float* bsum_h, int B, int S,
                             const void* wfrag0 = nullptr, const void* wfrag1 = nullptr);

@@ -56,12 +56,12 @@ __device__ __forceinline__ float4 wgw_sub(const float4& x, const float4& y) { re
 __device__ __forceinline__ float4 wgw_neg(const float4& x) { return make_float4(-x.x, -x.y, -x.z, -x.w); }
 
 // dz: [B][H][W][COUT] (gradient of the raw conv output), a: [B][H][W][CIN] (the layer input), slab: [strips][4 i][4 j][COUT][CIN]
-// F16 (round 4): the products on the fp16 matrix cores (f16_split.h), as in gemm_tn2_bf16x6_kernel's F16 form: the transformed output
+// f16x3 (round 4; the only form now): the products on the fp16 matrix cores (f16_split.h), as in gemm_tn2_bf16x6_kernel: the transformed output
 // gradient P (it carries the backward's loss scale) as two planes (Ph, Pl'), the transformed input V scaled by 2^-5 (|V| <= 4 max |input|:
 // exact below |input| = 256, clamped beyond) as two as well (Vh, Vl'; the consumers form Vh 2^11 in registers); Pl' Vh + Ph Vl' +
 // Ph (Vh 2^11) into the one accumulator set, 2^-11 x 2^5 in the epilogue.  The frequency stride of the LDS images stays three planes.
 constexpr int WGW_VS_LOG2 = -5;
-template <int CIN, int COUT, bool F16 = false>
+template <int CIN, int COUT>
 __global__ __launch_bounds__(WGW_THREADS, WGW_THREADS / 256) void conv_wgrad_wino_bf16x6_kernel(
     const float* __restrict__ dz, const float* __restrict__ a, float* __restrict__ slab, int B, int H, int W) {
     using C = WgwCfg<CIN, COUT>;
@@ -74,9 +74,7 @@ __global__ __launch_bounds__(WGW_THREADS, WGW_THREADS / 256) void conv_wgrad_win
     static_assert(TPS * PQ == (KPW == 1 ? 512 : 256) && TPS * VQ * KPW == 256, "item counts");
     extern __shared__ __attribute__((aligned(16))) unsigned char wgl[];
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifndef SIR_W2_CLAMP
-    if (F16) sir_fp16_ovfl_on();                             // producers: unclamped splits; consumers: Vh 2^11 saturates instead of overflowing
-#endif
+    sir_fp16_ovfl_on();                                      // producers: unclamped splits; consumers: Vh 2^11 saturates instead of overflowing
     const int TH = H >> 1, TW = (W + 1) >> 1;
     const int ntiles = B * TH * TW, nstages = (ntiles + TPS - 1) / TPS;
     // blockIdx -> (strip, group of rows): the groups of a strip on one XCD (workgroup L runs on XCD L % 8) when the strips come in eights
@@ -153,24 +151,11 @@ __global__ __launch_bounds__(WGW_THREADS, WGW_THREADS / 256) void conv_wgrad_win
             }
         };
         auto put = [&](unsigned char* img, int plane, const float4& v) {           // img: the item's address in a frequency's first plane
-            uint2 hh, mm, ll;
-            if constexpr (F16) {
-#ifdef SIR_W2_CLAMP
-                if (plane == PPLANE) split2h_quad(v, hh, ll);                        // P (gradient side): (Ph, Pl')
-                else tn2_split_b<WGW_VS_LOG2>(v, hh, ll);                            // V: (Vh, Vl') of V / 32
-#else                                                        // (the kernel runs with MODE.FP16_OVFL = 1: no clamps, see tn2_split_b_ovfl)
-                if (plane == PPLANE) split2h_quad_ovfl(v, hh, ll);
-                else tn2_split_b_ovfl<WGW_VS_LOG2>(v, hh, ll);
-#endif
-                *reinterpret_cast<uint2*>(img) = hh;
-                *reinterpret_cast<uint2*>(img + plane) = ll;
-                return;
-            } else {
-                split3_quad(v, hh, mm, ll);
-            }
+            uint2 hh, ll;                                    // (the kernel runs with MODE.FP16_OVFL = 1: no clamps, see tn2_split_b_ovfl)
+            if (plane == PPLANE) split2h_quad_ovfl(v, hh, ll);                       // P (gradient side): (Ph, Pl')
+            else tn2_split_b_ovfl<WGW_VS_LOG2>(v, hh, ll);                           // V: (Vh, Vl') of V / 32
             *reinterpret_cast<uint2*>(img) = hh;
-            *reinterpret_cast<uint2*>(img + plane) = mm;
-            *reinterpret_cast<uint2*>(img + 2 * plane) = ll;
+            *reinterpret_cast<uint2*>(img + plane) = ll;
         };
         auto stage_p = [&](unsigned char* buf, const float4 (&y)[2][2]) {
 #pragma unroll
@@ -265,41 +250,26 @@ __global__ __launch_bounds__(WGW_THREADS, WGW_THREADS / 256) void conv_wgrad_win
         const unsigned char* sb = wgl + ((s - 1) & 1) * STAGE;
 #pragma unroll
         for (int ks = 0; ks < TPS / 16; ++ks) {
-            constexpr int NPA = F16 ? 2 : 3;
+            constexpr int NPA = 2;
             bf16x8 af[MTW][NPA], bf[NT][3];
 #pragma unroll
-            for (int p = 0; p < 3; ++p) {
-                if (p < NPA) {
+            for (int p = 0; p < NPA; ++p) {
 #pragma unroll
-                    for (int m = 0; m < MTW; ++m) af[m][p < NPA ? p : 0] = tn_tr_fragment<ZW>(sb + poff[m] + p * PPLANE + ks * 16 * ZW);
-                }
-                if (p < NPA) {
+                for (int m = 0; m < MTW; ++m) af[m][p] = tn_tr_fragment<ZW>(sb + poff[m] + p * PPLANE + ks * 16 * ZW);
 #pragma unroll
-                    for (int n = 0; n < NT; ++n) bf[n][F16 && p == 1 ? 2 : p] = tn_tr_fragment<AW>(sb + voff[n] + p * VPLANE + ks * 16 * AW);
-                }
+                for (int n = 0; n < NT; ++n) bf[n][p == 1 ? 2 : p] = tn_tr_fragment<AW>(sb + voff[n] + p * VPLANE + ks * 16 * AW);
             }
-            if constexpr (F16) {
 #pragma unroll
-                for (int n = 0; n < NT; ++n) bf[n][1] = tn2_hi2(bf[n][0]);
-                constexpr int HA[3] = {1, 0, 0}, HB[3] = {0, 2, 1};       // Pl' Vh, Ph Vl', Ph (Vh 2^11)
+            for (int n = 0; n < NT; ++n) bf[n][1] = tn2_hi2(bf[n][0]);
+            constexpr int HA[3] = {1, 0, 0}, HB[3] = {0, 2, 1};           // Pl' Vh, Ph Vl', Ph (Vh 2^11)
 #pragma unroll
-                for (int t3 = 0; t3 < 3; ++t3)
+            for (int t3 = 0; t3 < 3; ++t3)
 #pragma unroll
-                    for (int m = 0; m < MTW; ++m)
+                for (int m = 0; m < MTW; ++m)
 #pragma unroll
-                        for (int n = 0; n < NT; ++n)
-                            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, af[m][HA[t3]]), __builtin_bit_cast(f16x8, bf[n][HB[t3]]),
-                                                                              acc[m][n], 0, 0, 0);
-            } else {
-                constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};   // small terms first
-#pragma unroll
-                for (int t6 = 0; t6 < 6; ++t6)
-#pragma unroll
-                    for (int m = 0; m < MTW; ++m)
-#pragma unroll
-                        for (int n = 0; n < NT; ++n)
-                            acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[m][PA[t6] % NPA], bf[n][PB[t6]], acc[m][n], 0, 0, 0);
-            }
+                    for (int n = 0; n < NT; ++n)
+                        acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, af[m][HA[t3]]), __builtin_bit_cast(f16x8, bf[n][HB[t3]]),
+                                                                          acc[m][n], 0, 0, 0);
         }
         tn2_barrier();
     }
@@ -312,7 +282,7 @@ __global__ __launch_bounds__(WGW_THREADS, WGW_THREADS / 256) void conv_wgrad_win
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int co = (mh * MTW + m) * 32 + (r & 3) + 8 * (r >> 2) + 4 * kgrp, ci = n * 32 + i32;
-                out[(size_t)co * CIN + ci] = acc[m][n][r] * (F16 ? H3_LO_INV * (float)(1 << (-WGW_VS_LOG2)) : 1.0f);
+                out[(size_t)co * CIN + ci] = acc[m][n][r] * (H3_LO_INV * (float)(1 << (-WGW_VS_LOG2)));
             }
 }
 

@@ -202,15 +202,14 @@ def test_teardown_in_any_order_exits_cleanly(order, backend, tmp_path):
     assert r.returncode == 0 and "TEARDOWN-OK" in r.stdout, (r.returncode, r.stdout[-500:], r.stderr[-3000:])
 
 
-@pytest.mark.parametrize("mask", ["0", "5"])
-def test_fallback_conv_kernels_keep_parity(mask):
-    """SIR_WINO2 selects per stage between the producer / consumer Winograd kernel (default: conv2, conv3, conv3 data gradient) and
-    the first-generation / direct kernels, which shapes outside the new kernel's range still use.  The switch is read once per
-    process, so the reference-golden inference and training-step tests run again in a child with the stages switched off
-    (0) or mixed (5: conv3 direct, the others on): both sets of kernels stay correct.  SIR_TN2 does the same for the GRU backward
-    GEMMs (producer / consumer kernel by default; 0 = the first kernel everywhere, 2 = only the 128-row dX on the new one) and
-    SIR_WGW for the convolution weight gradients (Winograd form by default; 0 = the nine-tap kernel, 1 = conv2 only)."""
-    env = dict(os.environ, SIR_WINO2=mask, SIR_TN2={"0": "0", "5": "2"}[mask], SIR_WGW={"0": "0", "5": "1"}[mask])
+@pytest.mark.parametrize("fallback", ["2", "1"])
+def test_fallback_conv_kernels_keep_parity(fallback):
+    """Shapes outside the second-generation Winograd kernels' range (32-bit element offsets) run the convolution stages on the
+    first-generation / direct kernels and the nine-tap weight gradients.  SIR_CONV_FALLBACK makes the stages' shape gates report
+    "does not fit" (read once per process), so the reference-golden inference and training-step tests run again in a child with
+    every conv stage on the fallbacks (2) or only conv2's (1: what a shape between the two layers' limits gets -- the forward then
+    falls back for both layers, conv3's data and weight gradients stay on the Winograd kernels): both sets of kernels stay correct."""
+    env = dict(os.environ, SIR_CONV_FALLBACK=fallback)
     r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-m", "gpu",
                         os.path.join(ROOT, "tests", "test_model_gpu.py::test_eval_golden_from_reference"),
                         os.path.join(ROOT, "tests", "test_model_gpu.py::test_stages_vs_oracle"),

@@ -671,7 +671,7 @@ def test_gru_timeout_is_reported_not_swallowed(tmp_path):
 
 @pytest.mark.parametrize("bsz", [256, 21])
 def test_two_stream_backward_is_bit_identical_to_one_stream(sd, bsz):
-    """The backward's weight-gradient launches run on a second, library-owned stream (SIR_BWD_STREAMS, csrc/model_train.hip); while every
+    """The backward's weight-gradient launches run on a second, library-owned stream (csrc/model_train.hip); while every
     kernel is timed (sir_profile_enable mode 1) the same call keeps everything on the caller's stream.  No reduction depends on the
     order in which the two streams finish, so every parameter gradient must be BIT-identical between the two forms, run after run (a
     missing fork / join edge or a shared slab shows up here as a difference)."""

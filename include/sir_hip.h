@@ -159,7 +159,12 @@ typedef struct sir_model_weights {
  * feats  : [batch][64][t_frames] f32 (t_frames >= 8; 200 on the training path)
  * logits : [batch][num_classes] f32
  * argmax : int64[batch] or NULL
- * workspace: sir_model_workspace_bytes(batch, t_frames, 0) bytes, 256-byte aligned */
+ * workspace: sir_model_workspace_bytes(batch, t_frames, 0) bytes, 256-byte aligned
+ * Trailing frame columns whose 64 values are all exactly +0.0 (bit pattern 0) are treated as padding: conv1-3 and the
+ * layer-0 input projection skip every position that sees only such columns, and the recurrence takes those positions'
+ * values from an all-zero template utterance computed beside the batch.  Results are bit-identical to the full
+ * computation; a tail of -0.0 (or any other non-zero bits) is computed in full.  The intermediate buffers listed by
+ * sir_model_workspace_offsets hold valid values only for the computed positions: past them they are left unwritten. */
 size_t sir_model_workspace_bytes(const sir_handle* h, int batch, int t_frames, int train);
 /* Byte offsets of the intermediate buffers inside the workspace, in the order
  *   0 conv1 out NHWC [B][32][T/2][32]   1 conv2 out NHWC [B][16][T/4][64]

@@ -88,11 +88,16 @@ struct Wino2Geo {
     int Hp, Wp;          // pooled map (OUT_MODE 0 / 1)
     int B;
     W2Div dTW, d2TW, dRBN;   // divisions by TW, 2 TW, RBN (all operands are non-negative)
+    // nullptr: tile columns are numbered across the whole batch (above).  Otherwise a COMPACTED column list in device memory
+    // (inference pad skip, model_infer.hip): ctab[0] = number of task columns n, ctab[1 + k] = first tile column (img * TW + tx0,
+    // tx0 a multiple of 4) of task column k, k < n; NS = RBN * n.  A task then holds 4 tile columns of ONE image, its halo pixels
+    // come from that image (or the zero page outside it), and tile columns past the image's TW are neither computed nor stored.
+    const int* ctab;
 };
 // false: shape outside what the kernel covers (whole 8-tile-row blocks, 32-bit element offsets) -- the caller keeps the
 // first-generation / direct kernel for it
 static inline bool wino2_geo(int B, int H, int W, int cmax, Wino2Geo* g) {
-    g->B = B; g->H = H; g->W = W; g->TW = (W + 1) / 2; g->NG = B * g->TW; g->RBN = H / 16;
+    g->B = B; g->H = H; g->W = W; g->TW = (W + 1) / 2; g->NG = B * g->TW; g->RBN = H / 16; g->ctab = nullptr;
     g->NS = g->RBN * ((g->NG + 3) / 4); g->Hp = H / 2; g->Wp = W / 2;
     g->dTW = w2_div_make((unsigned)g->TW); g->d2TW = w2_div_make(2u * (unsigned)g->TW); g->dRBN = w2_div_make((unsigned)(g->RBN > 0 ? g->RBN : 1));
     return H % 16 == 0 && W >= 1 && B >= 1 && (size_t)B * H * W * cmax < ((size_t)1 << 31) && (size_t)g->NG * 2 < ((size_t)1 << 30);
@@ -159,7 +164,9 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_bf16x6_kernel(
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool producer = wv < 4;
     const int H = geo.H, W = geo.W, TW = geo.TW, NG = geo.NG, RBN = geo.RBN;
-    const int ntask_s = (geo.NS - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;     // spatial tasks of this workgroup
+    const int* const ctab = OUT_MODE <= 1 ? geo.ctab : nullptr;      // (compacted lists: inference forms only)
+    const int NS = ctab ? RBN * ctab[0] : geo.NS;
+    const int ntask_s = (NS - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;        // spatial tasks of this workgroup
     const int ntask = ntask_s * NCHO;
     if (ntask <= 0) return;
     const int nsteps = ntask * NCH;                                     // chunks of this workgroup; step s: producers chunk s, consumers chunk s - 1
@@ -168,7 +175,7 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_bf16x6_kernel(
         s = (int)blockIdx.x + (lt / NCHO) * (int)gridDim.x;
         ch = lt % NCHO;
         const int cb = w2_div(s, geo.dRBN), rb = s - cb * RBN;
-        g0 = 4 * cb; ty0 = 8 * rb;
+        g0 = ctab ? ctab[1 + cb] : 4 * cb; ty0 = 8 * rb;
     };
     // ---- raw-patch DMA: WHO issues it ------------------------------------------------------------------------------------------
     // The four producer waves (piece k = wave + 4 i, counted vmcnt waits in their loop) -- except in a 32-channel layer (the
@@ -195,13 +202,15 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_bf16x6_kernel(
         pre_part[ii] = (sp ^ (((lr >> 2) & 1) << 1)) * 4;
     }
     auto raw_offsets = [&](int g0, int ty0, unsigned (&off)[D_PPW]) {
+        // pixel columns P of the flattened batch that may be read: all of it, or (compacted list) the task's own image only
+        const int plo = ctab ? 2 * TW * w2_div(g0, geo.dTW) : 0, phi = ctab ? plo + W : 2 * NG;
 #pragma unroll
         for (int ii = 0; ii < D_PPW; ++ii) {
             const int gy = 2 * ty0 - 1 + pre_lr[ii];
             const int P = 2 * g0 - 1 + pre_lc[ii];
             const int Pc = min(max(P, 0), 2 * NG - 1);
             const int bb = w2_div(Pc, geo.d2TW), px = Pc - bb * 2 * TW;
-            const bool ok = gy >= 0 && gy < H && P >= 0 && P < 2 * NG && px < W;
+            const bool ok = gy >= 0 && gy < H && P >= plo && P < phi && px < W;
             off[ii] = ok ? (unsigned)(((bb * H + gy) * W + px) * CIN + pre_part[ii]) : ~0u;
         }
     };
@@ -273,7 +282,7 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_bf16x6_kernel(
                     int cg0, cty0, cch, cs;
                     task_geo(s / NCH, cg0, cty0, cch, cs);
                     const int t0 = cg0 - w2_div(cg0, geo.dTW) * TW;     // tile column of the task's first column inside its image
-                    edge = t0 == 0 || t0 + 3 >= TW - 1;
+                    edge = !ctab && (t0 == 0 || t0 + 3 >= TW - 1);    // (compacted: no neighbouring image in the patch)
                     const int txx = (t0 + ttx) - w2_div(t0 + ttx, geo.dTW) * TW;
                     z0 = txx == 0; z3 = txx == TW - 1;
                 }
@@ -495,7 +504,7 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_bf16x6_kernel(
                 {
                     const int gc = g0 + mi;
                     const int img = w2_div(gc, geo.dTW), tx = gc - img * TW;
-                    const bool tvalid = gc < NG;
+                    const bool tvalid = gc < (ctab ? (w2_div(g0, geo.dTW) + 1) * TW : NG);
                     if (OUT_MODE <= 1) {
                         float pooled[4];
 #pragma unroll
@@ -571,9 +580,16 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_bf16x6_kernel(
 // `attr_done`: the caller's per-device latch of the dynamic-LDS opt-in of THIS instantiation (sir_handle::attr_wino2[...])
 template <int CIN, int COUT, int OUT_MODE, int DBG = 0, int PRIO = 3>
 static inline hipError_t launch_conv_wino2(hipStream_t st, bool* attr_done, const float* x, const unsigned short* wpb, const float* scale,
-                                           const float* shift, float* out, int B, int H, int W, float2* stats, const float* zeros, int max_wg = 256) {
+                                           const float* shift, float* out, int B, int H, int W, float2* stats, const float* zeros, int max_wg = 256,
+                                           const int* ctab = nullptr, int ncol_max = 0) {
+    // ctab (OUT_MODE 0 / 1 only): compacted task-column list in device memory (Wino2Geo::ctab), at most ncol_max columns
     Wino2Geo g;
     if (!wino2_geo(B, H, W, CIN > COUT ? CIN : COUT, &g)) return hipErrorInvalidValue;
+    if (ctab) {
+        if (OUT_MODE > 1 || ncol_max < 1) return hipErrorInvalidValue;
+        g.ctab = ctab;
+        g.NS = g.RBN * ncol_max;                                    // (grid size only: the kernel reads the real count)
+    }
     if (!*attr_done) {
         hipError_t e = hipFuncSetAttribute((const void*)conv3x3_wino2_bf16x6_kernel<CIN, COUT, OUT_MODE, DBG, PRIO>, hipFuncAttributeMaxDynamicSharedMemorySize, W2_LDS_BYTES);
         if (e != hipSuccess) return e;

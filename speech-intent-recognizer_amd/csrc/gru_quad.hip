@@ -5,7 +5,7 @@
 
 int sir_launch_gru_quad(sir_handle* h, hipStream_t st, bool save, const float* gi, const float* whh0, const float* whh1, const float* bhh0,
                         const float* bhh1, float* y, int B, int S, float* gates, unsigned short* yplanes, const void* wfrag0,
-                        const void* wfrag1) {
+                        const void* wfrag1, const int* nlive) {
     if (!h->attr_gru_quad) {
         SIR_HIP_TRY(hipFuncSetAttribute((const void*)gru_quad_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GQ_LDS_BYTES));
         SIR_HIP_TRY(hipFuncSetAttribute((const void*)gru_quad_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GQ_LDS_BYTES));
@@ -27,10 +27,10 @@ int sir_launch_gru_quad(sir_handle* h, hipStream_t st, bool save, const float* g
     // stores per lane and step were fully exposed (layer 0: 79.5 -> 71.4 us); not for the inference form, where the extra barrier costs
     // more than its one to three stores (71.6 -> 74.7 us).  profiles/r04/ab_gq_roles.txt
     typedef void (*kern_t)(const float*, const float*, const float*, const float*, const float*, float*, int, int, float*, unsigned long long*,
-                           unsigned int*, int, unsigned, unsigned short*, const uint4*, const uint4*);
+                           unsigned int*, int, unsigned, unsigned short*, const uint4*, const uint4*, const int*);
     const kern_t kern = save ? gru_quad_kernel<true, true> : gru_quad_kernel<false, false>;
     hipLaunchKernelGGL(kern, grid, dim3(GQ_THREADS), GQ_LDS_BYTES, st, gi, whh0, whh1, bhh0, bhh1, y, B, S, gates,
-                       (unsigned long long*)xbuf, h->status, dbg, epoch, yplanes, (const uint4*)wfrag0, (const uint4*)wfrag1);
+                       (unsigned long long*)xbuf, h->status, dbg, epoch, yplanes, (const uint4*)wfrag0, (const uint4*)wfrag1, nlive);
     SIR_HIP_TRY(hipGetLastError());
     return SIR_OK;
 }

@@ -104,8 +104,10 @@ __global__ __launch_bounds__(GQ_THREADS) void gru_quad_kernel(
     const float* __restrict__ gi, const float* __restrict__ whh0, const float* __restrict__ whh1,
     const float* __restrict__ bhh0, const float* __restrict__ bhh1, float* __restrict__ y, int B, int S,
     float* __restrict__ gates, unsigned long long* xbuf, unsigned int* status, int dbg, unsigned epoch, unsigned short* __restrict__ yplanes,
-    const uint4* __restrict__ wfrag0, const uint4* __restrict__ wfrag1) {
+    const uint4* __restrict__ wfrag0, const uint4* __restrict__ wfrag1, const int* __restrict__ nlive) {
     // wfrag0/1: prep_whh_quad_elem output for direction 0 / 1 (required)
+    // nlive (optional, inference pad skip: model_infer.hip): steps t >= nlive[b] read gi row B * S + t (the template utterance's)
+    // instead of b * S + t
     // yplanes (optional): f16x2 planes [2][B * S][512] (f16_split.h) of y, the A operand of the next layer's input projection
     // dbg (timing experiments only, results invalid): bit 0 = do not wait for the granules, bit 1 = skip the MFMAs,
     // bit 2 = skip publish + receive; fault injection for the status-word test: bit 3 = quarter 3 never publishes (its
@@ -156,11 +158,12 @@ __global__ __launch_bounds__(GQ_THREADS) void gru_quad_kernel(
 
     // gate pre-activations of the input side, fetched one step ahead
     float4 gin[3];
+    const int nlb = (!SAVE && nlive && bvalid) ? nlive[b] : S;
     auto load_gi = [&](int t, float4 (&dst)[3]) {
 #pragma unroll
         for (int g = 0; g < 3; ++g) dst[g] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (bvalid) {
-            const float* gp = gi + ((size_t)b * S + t) * 1536 + dir * 768 + u0;
+            const float* gp = gi + ((size_t)(t < nlb ? b : B) * S + t) * 1536 + dir * 768 + u0;
 #pragma unroll
             for (int g = 0; g < 3; ++g) dst[g] = *reinterpret_cast<const float4*>(gp + g * 256);
         }

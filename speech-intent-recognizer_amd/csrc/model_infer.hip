@@ -1,5 +1,18 @@
 // sir_model_infer: eval-mode CNNAudioGRU.forward + argmax (models/models.py:41-68, scripts/evaluate.py:82-83)
 // as a fixed sequence of hand-written kernels on one stream.  See model_kernels.h for the kernels.
+//
+// Pad skip.  Features are zero-padded to a fixed frame count (bench / pipeline: 200 frames for 94 real ones at 3 s).  A conv
+// output whose receptive field sees only trailing all-+0.0 frame columns does not depend on the utterance: it equals what an
+// all-zero utterance of the same width produces at that position.  So one extra "template" utterance (index B, fed from an
+// all-zero feature row in the workspace) rides along at full width through conv1-3 and the layer-0 input projection, and for
+// every real utterance only the columns that some non-template GRU step depends on are computed:
+//   E0  = 1 + last frame column with any bit set (pad_extent_kernel; -0.0, NaN, denormals count as data)
+//   d3  = min(S, (E0 + 14) / 8)   GRU steps s < d3 see data (conv3 output s reads frame columns >= 8 s - 7)
+//   d2  = min(wp2, 2 d3 + 1), d1 = min(wp1, 2 d2 + 1)   columns of conv2 / conv1 those steps read
+// conv1 stores pooled columns < d1; conv2 / conv3 run over a compacted list of 4-tile-column tasks (Wino2Geo::ctab), ceil(d / 4)
+// of them per utterance; the layer-0 recurrence reads the template's gi row for steps s >= d3.  Columns past the computed ones
+// are left unwritten in a1 / a2 / x0 / xs / gi.  The conv fallback kernels (shapes the Winograd kernel does not cover) keep the
+// full path.
 #include "bf16x6_kernels.h"
 #include "f16x3_kernels.h"
 #include "conv_wino_bf16x6_kernel.h"
@@ -16,8 +29,8 @@ enum WsBuf {
     WS_Y0,       // GRU layer 0 output [B][S][512]
     WS_Y1,       // GRU layer 1 output [B][S][512]
     WS_CTX,      // attention-pooled context [B][512]
-    WS_WP2,      // (unused, kept so that the buffer indices of sir_model_workspace_offsets stay put)
-    WS_WP3,      // (unused)
+    WS_PAD,      // pad-skip tables (int): E0[B], conv1 columns d1[B + 1], GRU steps d3[B + 1], conv2 / conv3 task-column lists
+    WS_XZ,       // all-zero feature row [64][T] of the template utterance (zeroed by pad_tables_kernel on every call)
     WS_BN,       // folded BN: scale[224] then shift[224] (channels of bn1|bn2|bn3)
     WS_WHT,      // W_hh fragments of the recurrence kernel, [4 (layer, direction)][GRU_FRAG_BYTES]
     WS_XS,       // f16x2 planes (f16_split.h) of the current GEMM A operand, [2][B*S][1024] fp16
@@ -30,25 +43,36 @@ enum WsBuf {
 
 struct Dims {
     int B, T, wp1, wp2, wp3, S;
+    int tw2, tw3, k2max, k3max;     // Winograd tile columns of conv2 / conv3, and 4-column task columns per utterance
 };
 
 bool make_dims(int batch, int t_frames, Dims* d) {
     d->B = batch; d->T = t_frames;
     d->wp1 = t_frames / 2; d->wp2 = d->wp1 / 2; d->wp3 = d->wp2 / 2; d->S = d->wp3;
+    d->tw2 = (d->wp1 + 1) / 2; d->tw3 = (d->wp2 + 1) / 2; d->k2max = (d->tw2 + 3) / 4; d->k3max = (d->tw3 + 3) / 4;
     return batch > 0 && d->S >= 1 && d->S <= ATT_MAX_S && batch <= 65535;
 }
 
+// int offsets inside WS_PAD
+struct PadTabs { size_t e0, d1, d3, tab2, tab3, count; };
+PadTabs pad_tabs(const Dims& d) {
+    PadTabs t;
+    const size_t n = (size_t)d.B + 1;
+    t.e0 = 0; t.d1 = d.B; t.d3 = t.d1 + n; t.tab2 = t.d3 + n; t.tab3 = t.tab2 + 1 + n * d.k2max; t.count = t.tab3 + 1 + n * d.k3max;
+    return t;
+}
+
 void ws_sizes(const Dims& d, size_t* bytes) {
-    const size_t B = d.B;
+    const size_t B = d.B + 1;       // activation buffers: the batch + the template utterance (index B)
     bytes[WS_A1] = B * 32 * d.wp1 * 32 * 4;
     bytes[WS_A2] = B * 16 * d.wp2 * 64 * 4;
     bytes[WS_X0] = B * d.S * 1024 * 4;
     bytes[WS_GI] = B * d.S * 1536 * 4;
-    bytes[WS_Y0] = B * d.S * 512 * 4;
-    bytes[WS_Y1] = B * d.S * 512 * 4;
-    bytes[WS_CTX] = B * 512 * 4;
-    bytes[WS_WP2] = 0;
-    bytes[WS_WP3] = 0;
+    bytes[WS_Y0] = (size_t)d.B * d.S * 512 * 4;
+    bytes[WS_Y1] = (size_t)d.B * d.S * 512 * 4;
+    bytes[WS_CTX] = (size_t)d.B * 512 * 4;
+    bytes[WS_PAD] = pad_tabs(d).count * 4;
+    bytes[WS_XZ] = (size_t)64 * d.T * 4;
     bytes[WS_BN] = (size_t)2 * 224 * 4;
     bytes[WS_WHT] = 4 * GRU_FRAG_BYTES;                         // W_hh as the resident f16x2 MFMA fragments of the recurrence kernel
     bytes[WS_XS] = B * d.S * 1024 * 2 * 2;
@@ -66,6 +90,61 @@ size_t ws_layout(const Dims& d, size_t* off) {
         pos += sir_align_up(bytes[i], 256);
     }
     return pos;
+}
+
+// E0[b] = 1 + the last frame column of utterance b with any bit set in any of the 64 mel rows, 0 if none (bits, not values:
+// -0.0, NaN and denormals are data)
+static __global__ __launch_bounds__(256) void pad_extent_kernel(const float* __restrict__ x, int T, int* __restrict__ e0) {
+    const unsigned* xb = reinterpret_cast<const unsigned*>(x) + (size_t)blockIdx.x * 64 * T;
+    int last = -1;
+    for (int c = threadIdx.x; c < T; c += 256) {
+        unsigned acc = 0;
+#pragma unroll 32
+        for (int r = 0; r < 64; ++r) acc |= xb[(size_t)r * T + c];
+        if (acc) last = c;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) last = max(last, __shfl_xor(last, o));
+    __shared__ int wl[4];
+    if ((threadIdx.x & 63) == 0) wl[threadIdx.x >> 6] = last;
+    __syncthreads();
+    if (threadIdx.x == 0) e0[blockIdx.x] = max(max(wl[0], wl[1]), max(wl[2], wl[3])) + 1;
+}
+
+// one workgroup: demanded columns per utterance from E0 (see the head of this file; utterance B = the template, full width),
+// prefix sums over the batch -> compacted task-column lists of conv2 / conv3 (Wino2Geo::ctab), and the template's zero features
+static __global__ __launch_bounds__(1024) void pad_tables_kernel(const int* __restrict__ e0, Dims d, int* __restrict__ d1o, int* __restrict__ d3o,
+                                                                 int* __restrict__ tab2, int* __restrict__ tab3, float* __restrict__ xz) {
+    const int tid = threadIdx.x;
+    for (int i = tid; i < 64 * d.T; i += 1024) xz[i] = 0.0f;
+    const int nu = d.B + 1, per = (nu + 1023) / 1024, u0 = min(nu, tid * per), u1 = min(nu, u0 + per);
+    auto need = [&](int u, int& c1, int& c3, int& k2, int& k3) {
+        if (u == d.B) { c1 = d.wp1; c3 = d.S; k2 = d.k2max; k3 = d.k3max; return; }
+        c3 = min(d.S, (e0[u] + 14) / 8);
+        const int c2 = min(d.wp2, 2 * c3 + 1);
+        c1 = min(d.wp1, 2 * c2 + 1);
+        k2 = (c2 + 3) / 4; k3 = (c3 + 3) / 4;
+    };
+    int s2 = 0, s3 = 0, c1, c3, k2, k3;
+    for (int u = u0; u < u1; ++u) { need(u, c1, c3, k2, k3); s2 += k2; s3 += k3; }
+    __shared__ int p2[1024], p3[1024];
+    p2[tid] = s2; p3[tid] = s3;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {                     // inclusive scan (Hillis-Steele)
+        const int a2 = tid >= o ? p2[tid - o] : 0, a3 = tid >= o ? p3[tid - o] : 0;
+        __syncthreads();
+        p2[tid] += a2; p3[tid] += a3;
+        __syncthreads();
+    }
+    int o2 = p2[tid] - s2, o3 = p3[tid] - s3;
+    for (int u = u0; u < u1; ++u) {
+        need(u, c1, c3, k2, k3);
+        d1o[u] = c1; d3o[u] = c3;
+        for (int k = 0; k < k2; ++k) tab2[1 + o2 + k] = u * d.tw2 + 4 * k;
+        for (int k = 0; k < k3; ++k) tab3[1 + o3 + k] = u * d.tw3 + 4 * k;
+        o2 += k2; o3 += k3;
+    }
+    if (tid == 1023) { tab2[0] = p2[1023]; tab3[0] = p3[1023]; }
 }
 
 }  // namespace
@@ -125,11 +204,16 @@ extern "C" int sir_model_infer(sir_handle* h, const sir_model_weights* w, const 
     unsigned short* wcb3 = wcb2 + (size_t)3 * 32 * 16 * 64;       // Winograd form
     unsigned short* wcb3d = wcb3 + (size_t)3 * 64 * 16 * 128;     // direct form (fallback)
     const int B = d.B, S = d.S;
+    const PadTabs pt = pad_tabs(d);
+    int* const ptab = (int*)(ws + off[WS_PAD]);
+    float* const xz = (float*)(ws + off[WS_XZ]);
 
     // conv2 / conv3 as Winograd F(2x2, 3x3) -- the 2x2 output tile is the pooling window -- on the producer / consumer kernel
-    // (conv_wino2_bf16x6_kernel.h); shapes it does not cover (batch x map beyond 32-bit offsets) keep the first-generation kernels
+    // (conv_wino2_bf16x6_kernel.h); shapes it does not cover (batch x map beyond 32-bit offsets) keep the first-generation kernels.
+    // The pad skip (head of this file) runs with the Winograd kernels, over the batch + the template utterance.
     Wino2Geo geo2, geo3;
-    const bool w2 = sir_conv_stage_fits(2, wino2_geo(B, 32, d.wp1, 64, &geo2)) && sir_conv_stage_fits(3, wino2_geo(B, 16, d.wp2, 128, &geo3));
+    const bool w2 = sir_conv_stage_fits(2, wino2_geo(B + 1, 32, d.wp1, 64, &geo2)) && sir_conv_stage_fits(3, wino2_geo(B + 1, 16, d.wp2, 128, &geo3));
+    const int BT = w2 ? B + 1 : B;                                // utterances through conv1-3 and the layer-0 projection
 
     // ---- weight preparation -------------------------------------------------------------
     // skipped when the caller vouches (sir_model_set_weights_version) that the weights are the ones prepared
@@ -165,14 +249,19 @@ extern "C" int sir_model_infer(sir_handle* h, const sir_model_weights* w, const 
     // ---- CNN stack: conv + folded BN + ReLU + 2x2 max-pool per launch ------------------------------
     {
         SirProfScope prof(h, SIR_K_CONV1, st);
-        hipLaunchKernelGGL(conv1_mfma_bn_relu_pool_kernel, dim3((d.wp1 + C1_PCOLS - 1) / C1_PCOLS, 1, B), dim3(256), 0, st, feats,
-                           w->conv_w[0], bns, bnt, a1, 64, d.T, 32, d.wp1);
+        if (w2) {                                                 // pad-skip extents and tables (two small launches, counted with conv1)
+            hipLaunchKernelGGL(pad_extent_kernel, dim3(B), dim3(256), 0, st, feats, d.T, ptab + pt.e0);
+            hipLaunchKernelGGL(pad_tables_kernel, dim3(1), dim3(1024), 0, st, (const int*)(ptab + pt.e0), d, ptab + pt.d1, ptab + pt.d3,
+                               ptab + pt.tab2, ptab + pt.tab3, xz);
+        }
+        hipLaunchKernelGGL(conv1_mfma_bn_relu_pool_kernel, dim3((d.wp1 + C1_PCOLS - 1) / C1_PCOLS, 1, BT), dim3(256), 0, st, feats,
+                           w->conv_w[0], bns, bnt, a1, 64, d.T, 32, d.wp1, (const float*)xz, B, w2 ? (const int*)(ptab + pt.d1) : (const int*)nullptr);
     }
     {
         SirProfScope prof(h, SIR_K_CONV2, st);
         if (w2)
-            SIR_HIP_TRY((launch_conv_wino2<32, 64, 0>(st, &h->attr_wino2[0], a1, (const unsigned short*)wcb2, bns + 32, bnt + 32, a2, B, 32, d.wp1,
-                                                    (float2*)nullptr, h->zero_page, h->num_cus)));
+            SIR_HIP_TRY((launch_conv_wino2<32, 64, 0>(st, &h->attr_wino2[0], a1, (const unsigned short*)wcb2, bns + 32, bnt + 32, a2, BT, 32, d.wp1,
+                                                    (float2*)nullptr, h->zero_page, h->num_cus, ptab + pt.tab2, (B + 1) * d.k2max)));
         else
             hipLaunchKernelGGL((conv3x3_wino_bf16x6_kernel<32, 64, 0>), dim3(((d.wp1 + 1) / 2 + 1) / 2, 1, B), dim3(256), WINO_LDS_BYTES, st,
                                a1, (const unsigned short*)wcb2, bns + 32, bnt + 32, a2, 32, d.wp1, 16, d.wp2, (float2*)nullptr);
@@ -182,8 +271,8 @@ extern "C" int sir_model_infer(sir_handle* h, const sir_model_weights* w, const 
         // the first input projection's A operand beside it
         SirProfScope prof(h, SIR_K_CONV3, st);
         if (w2)
-            SIR_HIP_TRY((launch_conv_wino2<64, 128, 1>(st, &h->attr_wino2[1], a2, (const unsigned short*)wcb3, bns + 96, bnt + 96, x0, B, 16, d.wp2,
-                                                     (float2*)xs, h->zero_page, h->num_cus)));
+            SIR_HIP_TRY((launch_conv_wino2<64, 128, 1>(st, &h->attr_wino2[1], a2, (const unsigned short*)wcb3, bns + 96, bnt + 96, x0, BT, 16, d.wp2,
+                                                     (float2*)xs, h->zero_page, h->num_cus, ptab + pt.tab3, (B + 1) * d.k3max)));
         else
             hipLaunchKernelGGL((conv3x3_bf16x6_ns_kernel<64, 128, 2, 2, 1, 0, 2, 1, 1>), dim3((d.wp2 + 7) / 8, 1, B), dim3(256), conv_ns_lds_bytes(2, 2, 2), st,
                                a2, (const unsigned short*)wcb3d, bns + 96, bnt + 96, x0, 16, d.wp2, 8, d.wp3, (float2*)xs);
@@ -193,16 +282,17 @@ extern "C" int sir_model_infer(sir_handle* h, const sir_model_weights* w, const 
     // ---- 2-layer bidirectional GRU ----------------------------------------------------------
     const int M = B * S;
     {
+        // (over the template's rows too; rows of skipped steps hold whatever their unwritten xs rows give and are never read)
         SirProfScope prof(h, SIR_K_GEMM_IH0, st);
         SIR_HIP_TRY(launch_gemm_nt_f16x3(h, st, (const unsigned short*)xs, (const unsigned short*)wsl0,
-                                         (const unsigned short*)(wsl0 + (size_t)2 * 768 * 1024), w->gru_b_ih[0], w->gru_b_ih[1], gi, 1536, M, 768, 1024));
+                                         (const unsigned short*)(wsl0 + (size_t)2 * 768 * 1024), w->gru_b_ih[0], w->gru_b_ih[1], gi, 1536, BT * S, 768, 1024));
     }
     {
         SirProfScope prof(h, SIR_K_GRU0, st);
         if (sir_cluster_enter(h, st) != SIR_OK) return SIR_EHIP;
         // layer 0 also writes the f16x2 planes of ITS output: the A operand of the layer-1 projection
         const int rc = sir_launch_gru_quad(h, st, false, gi, w->gru_w_hh[0], w->gru_w_hh[1], w->gru_b_hh[0], w->gru_b_hh[1], y0, B, S, nullptr,
-                                           xs, wht, (unsigned char*)wht + GRU_FRAG_BYTES);
+                                           xs, wht, (unsigned char*)wht + GRU_FRAG_BYTES, w2 ? (const int*)(ptab + pt.d3) : (const int*)nullptr);
         if (rc != SIR_OK) return rc;
         if (sir_cluster_leave(h, st) != SIR_OK) return SIR_EHIP;
     }

@@ -49,14 +49,19 @@ constexpr int C1_TR = 2 * C1_PROWS + 2, C1_TC = 2 * C1_PCOLS + 2;
 // 0, 1 and odd lanes groups 2, 3 of pooled pixel j / 2 (two float4 stores per lane).
 static __global__ __launch_bounds__(256, 4) void conv1_mfma_bn_relu_pool_kernel(
     const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ scale,
-    const float* __restrict__ shift, float* __restrict__ out, int H, int W, int Hp, int Wp) {
+    const float* __restrict__ shift, float* __restrict__ out, int H, int W, int Hp, int Wp,
+    const float* __restrict__ xtail, int nx, const int* __restrict__ lim) {
     // One block walks ALL row tiles of its column strip (grid = (column strips, 1, B)): weights / scale / shift are
     // loaded once, and the next tile's pixels are fetched into registers while the matrix pipe works on the current one
     // (one short block per tile spent most of its life waiting for its own loads: 50 us for 17 us of MFMA work).
+    // Inference pad skip (model_infer.hip): image b >= nx reads `xtail` instead of x (the all-zero template utterance), and
+    // only pooled columns < lim[b] are computed and stored (lim == nullptr: all Wp).
     __shared__ float tiles[2][C1_TR * C1_TC];
     const int b = blockIdx.z, px0 = blockIdx.x * C1_PCOLS;
+    const int wlim = lim ? min(Wp, lim[b]) : Wp;
+    if (px0 >= wlim) return;                                 // (whole block, before any barrier)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, j = lane & 31, kh = lane >> 5;
-    const float* xb = x + (size_t)b * H * W;
+    const float* xb = b < nx ? x + (size_t)b * H * W : xtail;
     constexpr int NPRE = (C1_TR * C1_TC + 255) / 256;
     float pre[NPRE];
     auto fetch = [&](int py0) {
@@ -97,7 +102,7 @@ static __global__ __launch_bounds__(256, 4) void conv1_mfma_bn_relu_pool_kernel(
         const float* trow = tile + (2 * wv) * C1_TC;
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
-            if (px0 + 16 * h >= Wp) break;                   // the last strip of a 100-column image has 4 valid columns
+            if (px0 + 16 * h >= wlim) break;                 // the last strip of a 100-column image has 4 valid columns
             f32x16 acc0, acc1;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { acc0[r] = 0.0f; acc1[r] = 0.0f; }
@@ -127,7 +132,7 @@ static __global__ __launch_bounds__(256, 4) void conv1_mfma_bn_relu_pool_kernel(
             const int px = px0 + 16 * h + (j >> 1);
             const float4 lo = odd ? make_float4(m[8], m[9], m[10], m[11]) : make_float4(m[0], m[1], m[2], m[3]);
             const float4 hi = odd ? make_float4(m[12], m[13], m[14], m[15]) : make_float4(m[4], m[5], m[6], m[7]);
-            if (px < Wp) {
+            if (px < wlim) {
                 float* o = out + (((size_t)b * Hp + py) * Wp + px) * 32 + 4 * kh + (odd ? 16 : 0);
                 *reinterpret_cast<float4*>(o) = lo;
                 *reinterpret_cast<float4*>(o + 8) = hi;

@@ -2,6 +2,7 @@
 // library): random fp32 operands -> bf16x3 planes -> every kernel generation, HIP-event timing,
 // max difference against generation 1 and against an fp64 host dot product on sampled entries.
 //   build: make -C speech-intent-recognizer_amd/csrc tools     run (GPU box): lib/bench_gemm [M] [K] [A.f32 B.f32 [bias.f32]]
+//                                                                           lib/bench_gemm gather [B] [S] [d3]   (row-list mode, below)
 // (A.f32 = [M][K], B.f32 = [2 * 768][K] raw float32 files: the REAL projection operands dumped by devtools/dump_gemm_operands.py)
 // Round 4: the two-way fp16 split ("f16x3": 3 products, 2 planes; f16x3_kernels.h) beside bf16x6, with a float64 product of the
 // same fp32 operands (computed on the GPU) as the error reference for both.
@@ -9,6 +10,9 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <string>
+#include <type_traits>
+#include <algorithm>
 #include <vector>
 #include "../../speech-intent-recognizer_amd/csrc/bf16x6_kernels.h"
 #include "../../speech-intent-recognizer_amd/csrc/f16x3_kernels.h"
@@ -144,6 +148,111 @@ static float time_h3w4(hipStream_t st, const unsigned short* Ap, const unsigned 
     return ms * 1000.0f / reps;
 }
 
+// ---- row-list ("gathered") f16x3 GEMM: the layer-0 projection of the inference pad skip ---------------------------------------
+// A has MA = (B + 1) S rows (B utterances + the template); the list holds u S + s for s < d3 of every utterance and all S template rows.
+// Each tile size (forced) and the device-side choice run against the dense kernel over all MA rows: listed rows must be bit-identical,
+// the others must keep their 0xFF sentinel.  Then the list of ALL rows (unpadded input) against today's dense launch.
+template <int FBM>
+static float time_gather(hipStream_t st, const unsigned short* Ap, const unsigned short* B0, const unsigned short* B1, const float* bias,
+                         float* C, const int* rows, int MA, int N, int K, int reps, int ncu) {
+    hipFuncSetAttribute((const void*)gemm_nt_f16x3_gather_kernel<0, FBM>, hipFuncAttributeMaxDynamicSharedMemorySize, h3_lds_bytes(3));
+    const int nwg = h3_gather_tiles(96, MA, N);
+    hipEvent_t e0, e1;
+    hipEventCreate(&e0); hipEventCreate(&e1);
+    hipLaunchKernelGGL((gemm_nt_f16x3_gather_kernel<0, FBM>), dim3(nwg), dim3(512), h3_lds_bytes(3), st, Ap, B0, B1, bias, bias + N, C, 2 * N, rows, MA, N, K, ncu);
+    hipEventRecord(e0, st);
+    for (int i = 0; i < reps; ++i)
+        hipLaunchKernelGGL((gemm_nt_f16x3_gather_kernel<0, FBM>), dim3(nwg), dim3(512), h3_lds_bytes(3), st, Ap, B0, B1, bias, bias + N, C, 2 * N, rows, MA, N, K, ncu);
+    hipEventRecord(e1, st);
+    hipEventSynchronize(e1);
+    float ms = 0;
+    hipEventElapsedTime(&ms, e0, e1);
+    return ms * 1000.0f / reps;
+}
+
+static int gather_main(int B, int S, int d3) {
+    const int K = 1024, N = 768, MA = (B + 1) * S, reps = 50;
+    int ncu = 256;
+    CK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, 0));
+    std::vector<float> hA((size_t)MA * K), hB((size_t)2 * N * K), hbias(2 * N);
+    srand(7);
+    for (auto& v : hA) v = (rand() / (float)RAND_MAX - 0.5f) * 2.0f;
+    for (auto& v : hB) v = (rand() / (float)RAND_MAX - 0.5f) * 0.1f;
+    for (auto& v : hbias) v = rand() / (float)RAND_MAX;
+    std::vector<int> list(1), all(1);
+    for (int u = 0; u <= B; ++u)
+        for (int s = 0; s < (u == B ? S : std::min(S, d3)); ++s) list.push_back(u * S + s);
+    for (int r = 0; r < MA; ++r) all.push_back(r);
+    list[0] = (int)list.size() - 1; all[0] = MA;
+    float *dA, *dB, *dbias, *Cd, *Cg;
+    unsigned short *pA, *pB;
+    int *dlist, *dall;
+    const size_t cbytes = (size_t)MA * 2 * N * 4;
+    CK(hipMalloc(&dA, hA.size() * 4)); CK(hipMalloc(&dB, hB.size() * 4)); CK(hipMalloc(&dbias, hbias.size() * 4));
+    CK(hipMalloc(&pA, hA.size() * 4)); CK(hipMalloc(&pB, hB.size() * 4));
+    CK(hipMalloc(&Cd, cbytes)); CK(hipMalloc(&Cg, cbytes));
+    CK(hipMalloc(&dlist, list.size() * 4)); CK(hipMalloc(&dall, all.size() * 4));
+    CK(hipMemcpy(dA, hA.data(), hA.size() * 4, hipMemcpyHostToDevice));
+    CK(hipMemcpy(dB, hB.data(), hB.size() * 4, hipMemcpyHostToDevice));
+    CK(hipMemcpy(dbias, hbias.data(), hbias.size() * 4, hipMemcpyHostToDevice));
+    CK(hipMemcpy(dlist, list.data(), list.size() * 4, hipMemcpyHostToDevice));
+    CK(hipMemcpy(dall, all.data(), all.size() * 4, hipMemcpyHostToDevice));
+    hipStream_t st; CK(hipStreamCreate(&st));
+    hipLaunchKernelGGL(split2h_kernel, dim3(2048), dim3(256), 0, st, (const float*)dA, K, pA, (size_t)MA, K);
+    for (int d = 0; d < 2; ++d)
+        hipLaunchKernelGGL(split2h_kernel, dim3(512), dim3(256), 0, st, (const float*)(dB + (size_t)d * N * K), K, pB + (size_t)d * 2 * N * K, (size_t)N, K);
+    const unsigned short *B0 = pB, *B1 = pB + (size_t)2 * N * K;
+    CK(hipStreamSynchronize(st));
+    const float td = time_h3<3, 0>(st, pA, B0, B1, dbias, Cd, MA, N, K, reps);
+    const float tdc = time_h3<3, 0>(st, pA, B0, B1, dbias, Cg, list[0], N, K, reps);
+    std::vector<unsigned> hd((size_t)MA * 2 * N), hg((size_t)MA * 2 * N);
+    CK(hipMemcpy(hd.data(), Cd, cbytes, hipMemcpyDeviceToHost));
+    printf("row-list f16x3 GEMM: B=%d S=%d d3=%d  MA=%d rows, %d listed, K=%d N=2x%d, %d CUs\n", B, S, d3, MA, list[0], K, N, ncu);
+    printf("dense, all %d rows (today's l0 launch)          %8.1f us  %4d WGs\n", MA, td, (MA + H3_BM - 1) / H3_BM * 2 * (N / H3_BN));
+    printf("dense, first %d rows (contiguous, for context)  %8.1f us\n", list[0], tdc);
+    bool ok = true;
+    auto check = [&](const char* name, const std::vector<int>& l, float t, int bm) {
+        CK(hipMemcpy(hg.data(), Cg, cbytes, hipMemcpyDeviceToHost));
+        std::vector<char> in(MA, 0);
+        for (int i = 1; i <= l[0]; ++i) in[l[i]] = 1;
+        size_t bad = 0, touched = 0;
+        for (int r = 0; r < MA; ++r)
+            for (int c = 0; c < 2 * N; ++c) {
+                const size_t i = (size_t)r * 2 * N + c;
+                if (in[r]) bad += hg[i] != hd[i];
+                else touched += hg[i] != 0xFFFFFFFFu;
+            }
+        printf("%-44s %8.1f us  %4d WGs   listed rows differing bits: %zu, unlisted rows written: %zu%s\n", name, t,
+               h3_gather_tiles(bm, l[0], N), bad, touched, bad || touched ? "  -- FAIL" : "");
+        ok = ok && !bad && !touched;
+        return 0;
+    };
+    auto run = [&](auto fbm_c, const char* name, const std::vector<int>& l, const int* dl) {
+        constexpr int FBM = decltype(fbm_c)::value;
+        CK(hipMemset(Cg, 0xFF, cbytes));
+        const float t = time_gather<FBM>(st, pA, B0, B1, dbias, Cg, dl, MA, N, K, reps, ncu);
+        const int c = l[0], bm = FBM ? FBM : (h3_gather_tiles(96, c, N) <= ncu ? 96 : h3_gather_tiles(128, c, N) <= ncu ? 128 : 160);
+        return check(name, l, t, bm);
+    };
+    run(std::integral_constant<int, 96>{}, "row list, BM = 96", list, dlist);
+    run(std::integral_constant<int, 128>{}, "row list, BM = 128", list, dlist);
+    run(std::integral_constant<int, 160>{}, "row list, BM = 160", list, dlist);
+    run(std::integral_constant<int, 0>{}, "row list, device choice", list, dlist);
+    run(std::integral_constant<int, 0>{}, "all rows (unpadded), device choice", all, dall);
+    run(std::integral_constant<int, 160>{}, "all rows (unpadded), BM = 160", all, dall);
+    // unpadded input: the list of all rows against today's dense launch, alternated, medians of 7 (timing drifts by a few us between runs)
+    std::vector<float> tdv, tgv;
+    for (int i = 0; i < 7; ++i) {
+        tdv.push_back(time_h3<3, 0>(st, pA, B0, B1, dbias, Cd, MA, N, K, reps));
+        tgv.push_back(time_gather<0>(st, pA, B0, B1, dbias, Cg, dall, MA, N, K, reps, ncu));
+    }
+    std::sort(tdv.begin(), tdv.end()); std::sort(tgv.begin(), tgv.end());
+    printf("alternated x7, all %d rows: dense median %.1f us (min %.1f), row list (device choice) median %.1f us (min %.1f)\n", MA,
+           tdv[3], tdv[0], tgv[3], tgv[0]);
+    printf("%s\n", ok ? "row-list GEMM: all bit-identical, sentinels intact" : "row-list GEMM: MISMATCH");
+    return ok ? 0 : 1;
+}
+
 static bool read_f32(const char* path, std::vector<float>& v) {
     FILE* f = fopen(path, "rb");
     if (!f) { printf("cannot open %s\n", path); return false; }
@@ -154,6 +263,8 @@ static bool read_f32(const char* path, std::vector<float>& v) {
 }
 
 int main(int argc, char** argv) {
+    if (argc > 1 && std::string(argv[1]) == "gather")
+        return gather_main(argc > 2 ? atoi(argv[2]) : 256, argc > 3 ? atoi(argv[3]) : 25, argc > 4 ? atoi(argv[4]) : 13);
     const int M = argc > 1 ? atoi(argv[1]) : 6400, K = argc > 2 ? atoi(argv[2]) : 1024, N = 768, reps = 20;
     std::vector<float> hA((size_t)M * K), hB((size_t)2 * N * K), hbias(2 * N);
     srand(1);

@@ -39,74 +39,149 @@ constexpr int H3_APIECES = 2 * H3_BM / 16, H3_PIECES = H3_APIECES + 2 * H3_BN / 
 constexpr int H3_PPW = (H3_PIECES + 7) / 8;                             // 7 (waves 0-3: 7 pieces, waves 4-7: 6)
 constexpr int h3_lds_bytes(int nst) { return nst * H3_STAGE; }
 
-// five A fragments of one plane pair + the wave's B fragments of one 16-deep step, then the wait: 12 x ds_read_b128
-__device__ __forceinline__ void h3_read_step(unsigned aaddr, unsigned baddr, f16x8 (&ah)[5], f16x8 (&al)[5], f16x8& bh, f16x8& bl) {
-    asm volatile(
-        "ds_read_b128 %0, %12\n\t"
-        "ds_read_b128 %10, %13 offset:20480\n\t"
-        "ds_read_b128 %5, %12 offset:10240\n\t"
-        "ds_read_b128 %11, %13 offset:36864\n\t"
-        "ds_read_b128 %1, %12 offset:2048\n\t"
-        "ds_read_b128 %6, %12 offset:12288\n\t"
-        "ds_read_b128 %2, %12 offset:4096\n\t"
-        "ds_read_b128 %7, %12 offset:14336\n\t"
-        "ds_read_b128 %3, %12 offset:6144\n\t"
-        "ds_read_b128 %8, %12 offset:16384\n\t"
-        "ds_read_b128 %4, %12 offset:8192\n\t"
-        "ds_read_b128 %9, %12 offset:18432\n\t"
-        "s_waitcnt lgkmcnt(0)"
-        : "=&v"(ah[0]), "=&v"(ah[1]), "=&v"(ah[2]), "=&v"(ah[3]), "=&v"(ah[4]),
-          "=&v"(al[0]), "=&v"(al[1]), "=&v"(al[2]), "=&v"(al[3]), "=&v"(al[4]), "=&v"(bh), "=&v"(bl)
-        : "v"(aaddr), "v"(baddr)
-        : "memory");
+// A tile of BM = 96 / 128 / 160 rows (3 / 4 / 5 fragments of 32 rows per wave; the same 8 waves of 32-column strips, the same
+// B tile, K order and MFMA sequence per output element, so every BM gives bit-identical results).  The stage holds A [2][BM][64 B]
+// then B [2][256][64 B]; piece g < APIECES is A rows 16 (g % (BM / 16)).. of plane g / (BM / 16).
+template <int BM>
+struct H3Geo {
+    static_assert(BM == 96 || BM == 128 || BM == 160, "BM = 96, 128 or 160");
+    static constexpr int FR = BM / 32, ARG = BM / 16;
+    static constexpr int APLANE = BM * 64, BOFF = 2 * APLANE, STAGE = BOFF + 2 * H3_BPLANE;
+    static constexpr int APIECES = 2 * ARG, PIECES = APIECES + 2 * H3_BN / 16;
+    static constexpr int PPW = (PIECES + 7) / 8, PREM = PIECES & 7;     // pieces of waves 0..PREM-1 (all if PREM = 0); the others one fewer
+    static constexpr int ISTRIDE = 3 * FR / PPW;                        // a piece goes out after every ISTRIDE-th MFMA of the issuing step
+};
+static_assert(H3Geo<H3_BM>::STAGE == H3_STAGE && H3Geo<H3_BM>::PIECES == H3_PIECES && H3Geo<H3_BM>::PPW == H3_PPW, "160-row geometry");
+
+// FR A fragments of one plane pair + the wave's B fragments of one 16-deep step, then the wait: 2 FR + 2 x ds_read_b128
+// (offsets: A lo plane at APLANE, B hi at BOFF, B lo at BOFF + 16384 bytes)
+template <int FR>
+__device__ __forceinline__ void h3_read_step(unsigned aaddr, unsigned baddr, f16x8 (&ah)[FR], f16x8 (&al)[FR], f16x8& bh, f16x8& bl) {
+    if constexpr (FR == 5) {
+        asm volatile(
+            "ds_read_b128 %0, %12\n\t"
+            "ds_read_b128 %10, %13 offset:20480\n\t"
+            "ds_read_b128 %5, %12 offset:10240\n\t"
+            "ds_read_b128 %11, %13 offset:36864\n\t"
+            "ds_read_b128 %1, %12 offset:2048\n\t"
+            "ds_read_b128 %6, %12 offset:12288\n\t"
+            "ds_read_b128 %2, %12 offset:4096\n\t"
+            "ds_read_b128 %7, %12 offset:14336\n\t"
+            "ds_read_b128 %3, %12 offset:6144\n\t"
+            "ds_read_b128 %8, %12 offset:16384\n\t"
+            "ds_read_b128 %4, %12 offset:8192\n\t"
+            "ds_read_b128 %9, %12 offset:18432\n\t"
+            "s_waitcnt lgkmcnt(0)"
+            : "=&v"(ah[0]), "=&v"(ah[1]), "=&v"(ah[2]), "=&v"(ah[3]), "=&v"(ah[4]),
+              "=&v"(al[0]), "=&v"(al[1]), "=&v"(al[2]), "=&v"(al[3]), "=&v"(al[4]), "=&v"(bh), "=&v"(bl)
+            : "v"(aaddr), "v"(baddr)
+            : "memory");
+    } else if constexpr (FR == 4) {
+        asm volatile(
+            "ds_read_b128 %0, %10\n\t"
+            "ds_read_b128 %8, %11 offset:16384\n\t"
+            "ds_read_b128 %4, %10 offset:8192\n\t"
+            "ds_read_b128 %9, %11 offset:32768\n\t"
+            "ds_read_b128 %1, %10 offset:2048\n\t"
+            "ds_read_b128 %5, %10 offset:10240\n\t"
+            "ds_read_b128 %2, %10 offset:4096\n\t"
+            "ds_read_b128 %6, %10 offset:12288\n\t"
+            "ds_read_b128 %3, %10 offset:6144\n\t"
+            "ds_read_b128 %7, %10 offset:14336\n\t"
+            "s_waitcnt lgkmcnt(0)"
+            : "=&v"(ah[0]), "=&v"(ah[1]), "=&v"(ah[2]), "=&v"(ah[3]),
+              "=&v"(al[0]), "=&v"(al[1]), "=&v"(al[2]), "=&v"(al[3]), "=&v"(bh), "=&v"(bl)
+            : "v"(aaddr), "v"(baddr)
+            : "memory");
+    } else {
+        static_assert(FR == 3, "3, 4 or 5 fragments");
+        asm volatile(
+            "ds_read_b128 %0, %8\n\t"
+            "ds_read_b128 %6, %9 offset:12288\n\t"
+            "ds_read_b128 %3, %8 offset:6144\n\t"
+            "ds_read_b128 %7, %9 offset:28672\n\t"
+            "ds_read_b128 %1, %8 offset:2048\n\t"
+            "ds_read_b128 %4, %8 offset:8192\n\t"
+            "ds_read_b128 %2, %8 offset:4096\n\t"
+            "ds_read_b128 %5, %8 offset:10240\n\t"
+            "s_waitcnt lgkmcnt(0)"
+            : "=&v"(ah[0]), "=&v"(ah[1]), "=&v"(ah[2]), "=&v"(al[0]), "=&v"(al[1]), "=&v"(al[2]), "=&v"(bh), "=&v"(bl)
+            : "v"(aaddr), "v"(baddr)
+            : "memory");
+    }
 }
 
-template <int NST = 3, int KNOCK = 0>
-static __global__ __launch_bounds__(512) void gemm_nt_f16x3_kernel(
+// One (BM x 256) output tile `wgid` of C = A x [B0; B1]^T.  A's planes hold MA rows.  Dense (GATHER = false): output rows are A
+// rows 0..M-1.  GATHER: output row i < M is A / C row rows[i] (a row list; model_infer.hip), and `rtab` is 512 ints of LDS.
+template <int NST, int KNOCK, int BM, bool GATHER>
+__device__ __forceinline__ void h3_gemm_tile(
     const unsigned short* __restrict__ Ap, const unsigned short* __restrict__ Bp0, const unsigned short* __restrict__ Bp1,
-    const float* __restrict__ bias0, const float* __restrict__ bias1, float* __restrict__ C, int ldc, int M, int N, int K) {
+    const float* __restrict__ bias0, const float* __restrict__ bias1, float* __restrict__ C, int ldc, int M, int MA, int N, int K,
+    int wgid, const int* __restrict__ rows, int* rtab) {
     static_assert(NST == 2 || NST == 3, "two or three stages");
+    using G = H3Geo<BM>;
+    constexpr int FR = G::FR, PPW = G::PPW;
     extern __shared__ __attribute__((aligned(1024))) unsigned char h3_smem[];
-    const int nwg = gridDim.x, orig = blockIdx.x, xcd = orig & 7, q = nwg >> 3, rem = nwg & 7;
-    const int wgid = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (orig >> 3);
     const int nbd = N / H3_BN, nb = 2 * nbd;
     const int mblk = wgid / nb, nbk = wgid - mblk * nb, z = nbk / nbd;
-    const int m0 = mblk * H3_BM, n0 = (nbk - z * nbd) * H3_BN;
+    const int m0 = mblk * BM, n0 = (nbk - z * nbd) * H3_BN;
     const unsigned short* __restrict__ Bp = z ? Bp1 : Bp0;
     const float* __restrict__ bias = z ? bias1 : bias0;
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6), m = lane & 31, h = lane >> 5;
-    const size_t planeA = (size_t)M * K, planeB = (size_t)N * K;
+    const size_t planeA = (size_t)MA * K, planeB = (size_t)N * K;
 
-    // LDS-DMA pieces of this wave: g = wv + 8 i; pieces 0..19 = A (plane g / 10, rows 16 (g % 10)..), 20..51 = B (plane (g - 20) / 16,
-    // rows 16 ((g - 20) % 16)..); piece g lands at byte g * 1024 of its stage
+    // LDS-DMA pieces of this wave: g = wv + 8 i; pieces 0..APIECES-1 = A (plane g / ARG, rows 16 (g % ARG)..), then B (plane
+    // (g - APIECES) / 16, rows 16 ((g - APIECES) % 16)..); piece g lands at byte g * 1024 of its stage
     const int lr = lane >> 2;
     const int csrc = (lane & 3) ^ ((lr >> 2) & 3);
-    unsigned int poff[H3_PPW];
+    // A row of piece i (clamped to the last row; GATHER: looked up in the list, every lookup issued before the first is waited for)
+    constexpr int AI = (G::APIECES + 7) / 8;                // pieces i < AI can be A pieces
+    int arow[AI];
 #pragma unroll
-    for (int i = 0; i < H3_PPW; ++i) {
+    for (int i = 0; i < AI; ++i) {
+        const int g = wv + 8 * i < G::APIECES ? wv + 8 * i : 0;
+        const int row = m0 + (g % G::ARG) * 16 + lr;
+        arow[i] = row < M ? row : M - 1;
+    }
+    int orow = 0;
+    if (GATHER) {
+        const int ro = m0 + tid < M ? m0 + tid : M - 1;
+        orow = rows[ro];
+#pragma unroll
+        for (int i = 0; i < AI; ++i) arow[i] = rows[arow[i]];
+    }
+    unsigned int poff[PPW];
+#pragma unroll
+    for (int i = 0; i < PPW; ++i) {
         const int g = wv + 8 * i;
-        if (g < H3_APIECES) {
-            const int pl = g / 10, rg = g - pl * 10;
-            int row = m0 + rg * 16 + lr;
-            row = row < M ? row : M - 1;
-            poff[i] = (unsigned int)(pl * planeA + (size_t)row * K + csrc * 8);
+        const int gb = g - G::APIECES, pl = (gb >> 4) & 1, rg = gb & 15;
+        if (GATHER) {                                       // both offsets, then a select: a lookup consumed on one side of a branch
+            const unsigned pa = i < AI ? (unsigned)((g < G::APIECES ? g / G::ARG : 0) * planeA + (size_t)arow[i < AI ? i : 0] * K + csrc * 8) : 0u;
+            const unsigned pb = (unsigned)(pl * planeB + (size_t)(n0 + rg * 16 + lr) * K + csrc * 8);
+            poff[i] = g < G::APIECES ? pa : pb;             // only made hipcc wait for the prologue's LDS-DMA before reusing its register
+        } else if (g < G::APIECES) {
+            poff[i] = (unsigned int)(g / G::ARG * planeA + (size_t)arow[i < AI ? i : 0] * K + csrc * 8);
         } else {
-            const int gb = g - H3_APIECES, pl = (gb >> 4) & 1, rg = gb & 15;
             poff[i] = (unsigned int)(pl * planeB + (size_t)(n0 + rg * 16 + lr) * K + csrc * 8);
         }
     }
+    // GATHER: the tile's output rows for the epilogue (orow, loaded beside the A rows above).  Rows past the list are clamped like
+    // their A rows: they compute row M - 1's A row, so they store the very bits of output row M - 1 to its own C row again, and the
+    // epilogue needs no branch (a branch per store made hipcc wait for every earlier store at each join).  No barrier of its own:
+    // every wave's LDS writes have completed at its first h3_read_step (lgkmcnt(0)), before the barrier of K tile 1 (K >= 2 BK)
+    if (GATHER) rtab[tid] = orow;                           // (all 512 threads: an unconditional store consumes every lookup)
     auto piece = [&](int i, int kt, int buf) {
         if (KNOCK & 1) return;
         const int g = wv + 8 * i;
-        if (g < H3_PIECES) {
-            const unsigned short* src = (g < H3_APIECES ? Ap : Bp) + poff[i] + (size_t)kt * H3_BK;
-            __builtin_amdgcn_global_load_lds((sir_gptr_t)src, (sir_lptr_t)(h3_smem + buf * H3_STAGE + g * 1024), 16, 0, 0);
+        if (g < G::PIECES) {
+            const unsigned short* src = (g < G::APIECES ? Ap : Bp) + poff[i] + (size_t)kt * H3_BK;
+            __builtin_amdgcn_global_load_lds((sir_gptr_t)src, (sir_lptr_t)(h3_smem + buf * G::STAGE + g * 1024), 16, 0, 0);
         }
     };
 
-    f32x16 acc0[5], acc1[5];
+    f32x16 acc0[FR], acc1[FR];
 #pragma unroll
-    for (int mt = 0; mt < 5; ++mt)
+    for (int mt = 0; mt < FR; ++mt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) { acc0[mt][r] = 0.0f; acc1[mt][r] = 0.0f; }
 
@@ -123,15 +198,15 @@ static __global__ __launch_bounds__(512) void gemm_nt_f16x3_kernel(
     // ISSUE: tile `ktn` (< nk) is staged into `bufn` between the MFMAs: waves 0-3 during step 0, their SIMD partners 4-7 during step 1
     auto compute = [&](int buf, auto issue_c, int ktn, int bufn) {
         constexpr bool ISSUE = decltype(issue_c)::value;
-        const unsigned so = (unsigned)(buf * H3_STAGE);
+        const unsigned so = (unsigned)(buf * G::STAGE);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            f16x8 ah[5], al[5], bh, bl;
-            h3_read_step(fa[ks] + so, fb[ks] + so, ah, al, bh, bl);
+            f16x8 ah[FR], al[FR], bh, bl;
+            h3_read_step<FR>(fa[ks] + so, fb[ks] + so, ah, al, bh, bl);
 #pragma unroll
             for (int t = 0; t < 3; ++t)
 #pragma unroll
-                for (int mt = 0; mt < 5; ++mt) {
+                for (int mt = 0; mt < FR; ++mt) {
                     if (KNOCK & 4) {
                         acc0[mt][0] += (float)ah[mt][0] * (float)bh[0] + (float)al[mt][1] * (float)bl[1];
                     } else {
@@ -139,8 +214,9 @@ static __global__ __launch_bounds__(512) void gemm_nt_f16x3_kernel(
                         if (t == 1) acc1[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mt], bl, acc1[mt], 0, 0, 0);
                         if (t == 2) acc0[mt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mt], bh, acc0[mt], 0, 0, 0);
                     }
-                    const int idx = t * 5 + mt;
-                    if (ISSUE && (idx & 1) && (idx >> 1) < H3_PPW && ks == (wv >> 2)) piece(idx >> 1, ktn, bufn);
+                    const int idx = t * FR + mt;
+                    if (ISSUE && idx % G::ISTRIDE == G::ISTRIDE - 1 && idx / G::ISTRIDE < PPW && ks == (wv >> 2))
+                        piece(idx / G::ISTRIDE, ktn, bufn);
                 }
             __builtin_amdgcn_sched_barrier(0);              // (left alone hipcc sinks this step's MFMAs below the next step's reads: both fragment sets live, spills)
         }
@@ -151,15 +227,15 @@ static __global__ __launch_bounds__(512) void gemm_nt_f16x3_kernel(
     for (int s = 0; s < NST - 1; ++s)
         if (s < nk) {
 #pragma unroll
-            for (int i = 0; i < H3_PPW; ++i) piece(i, s, s);
+            for (int i = 0; i < PPW; ++i) piece(i, s, s);
         }
     // tile kt must have landed before its barrier; the pieces of the tiles behind it (NST = 3: tile kt + 1, issued during the previous
     // tile) may still fly.  Main loop (stages the tile NST - 1 ahead) and tail (nothing left to stage) are two loops, not two branches
     // of one: with both bodies under one loop hipcc accumulated out of place (twice the accumulator registers, 290 spilled)
     auto tile_wait = [&](bool more) {
         if (NST == 2 || !more) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else if (wv < 4) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(H3_PPW) : "memory");
-        else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(H3_PPW - 1) : "memory");
+        else if (G::PREM == 0 || wv < G::PREM) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(PPW) : "memory");
+        else asm volatile("s_waitcnt vmcnt(%0)" :: "n"(PPW - 1) : "memory");
         asm volatile("s_barrier" ::: "memory");             // every wave's pieces of the tile are in LDS; the stage of the tile before it is free
     };
     int buf = 0, bufn = NST - 1, kt = 0;
@@ -177,22 +253,81 @@ static __global__ __launch_bounds__(512) void gemm_nt_f16x3_kernel(
 
     const int n = n0 + wv * 32 + m;
     const float bv = bias ? bias[n] : 0.0f;
-    float* crow = C + (size_t)(m0 + 4 * h) * ldc + (size_t)z * N + n;
-    if (m0 + H3_BM <= M) {                                  // whole tile in range: straight-line stores
+    if (GATHER) {                                           // each output row to its listed row (32-bit offsets: the launcher checks MA * ldc)
+        float* cz = C + (size_t)z * N + n;
 #pragma unroll
-        for (int mt = 0; mt < 5; ++mt)
+        for (int mt = 0; mt < FR; ++mt)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int4 g4 = *reinterpret_cast<const int4*>(rtab + mt * 32 + 8 * i + 4 * h);
+                const int gr[4] = {g4.x, g4.y, g4.z, g4.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) cz[gr[j] * ldc] = fmaf(acc1[mt][4 * i + j], H3_LO_INV, acc0[mt][4 * i + j]) + bv;
+            }
+        return;
+    }
+    float* crow = C + (size_t)(m0 + 4 * h) * ldc + (size_t)z * N + n;
+    if (m0 + BM <= M) {                                     // whole tile in range: straight-line stores
+#pragma unroll
+        for (int mt = 0; mt < FR; ++mt)
 #pragma unroll
             for (int r = 0; r < 16; ++r)
                 crow[(size_t)(mt * 32 + (r & 3) + 8 * (r >> 2)) * ldc] = fmaf(acc1[mt][r], H3_LO_INV, acc0[mt][r]) + bv;
     } else {
 #pragma unroll
-        for (int mt = 0; mt < 5; ++mt)
+        for (int mt = 0; mt < FR; ++mt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int ro = mt * 32 + (r & 3) + 8 * (r >> 2);
                 if (m0 + 4 * h + ro < M) crow[(size_t)ro * ldc] = fmaf(acc1[mt][r], H3_LO_INV, acc0[mt][r]) + bv;
             }
     }
+}
+
+// workgroup orig -> tile id: the hardware deals workgroups round-robin to the 8 XCDs (orig & 7); each XCD gets a contiguous range
+// of the `nt` tile ids, so the N-blocks of one M-tile (which read the same A rows) share an L2
+__device__ __forceinline__ int h3_xcd_tile(int orig, int nt) {
+    const int xcd = orig & 7, q = nt >> 3, rem = nt & 7;
+    return (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + (orig >> 3);
+}
+
+template <int NST = 3, int KNOCK = 0>
+static __global__ __launch_bounds__(512) void gemm_nt_f16x3_kernel(
+    const unsigned short* __restrict__ Ap, const unsigned short* __restrict__ Bp0, const unsigned short* __restrict__ Bp1,
+    const float* __restrict__ bias0, const float* __restrict__ bias1, float* __restrict__ C, int ldc, int M, int N, int K) {
+    h3_gemm_tile<NST, KNOCK, H3_BM, false>(Ap, Bp0, Bp1, bias0, bias1, C, ldc, M, M, N, K, h3_xcd_tile(blockIdx.x, gridDim.x), nullptr, nullptr);
+}
+
+// ------------------------------------------------------------------------------------------
+// The same contraction over a ROW LIST (the inference pad skip, model_infer.hip): rows[0] = count, rows[1..count] = the A rows to
+// compute, distinct and in ascending order; C row rows[1 + i] receives output row i, and every other C row is left alone.  A list
+// of all MA rows is the identity: on the 160-row tile it runs the dense kernel's tile, without the lookups.  The list lives in
+// device memory, so the grid is sized on the host for the worst case (count = MA) at the smallest tile, and each workgroup reads the
+// real count: the tile is the SMALLEST of 96 / 128 / 160 rows (FBM: forced, for the harness) whose tiles fit one workgroup per CU
+// (ncu), else 160 -- an unpadded batch keeps the dense kernel's 160-row schedule and code -- and workgroups past the real tile count
+// exit before any barrier.  Tile ids are dealt to the XCDs over the REAL tile count.  Each output element sees the same MFMA
+// sequence as in the dense kernel: the results are bit-identical to it.  LDS request: h3_lds_bytes(3) (the 160-row stages).
+// ------------------------------------------------------------------------------------------
+__host__ __device__ constexpr int h3_gather_tiles(int bm, int count, int N) { return (count + bm - 1) / bm * 2 * (N / H3_BN); }
+__device__ __forceinline__ int h3_gather_bm(int count, int N, int ncu) {
+    return h3_gather_tiles(96, count, N) <= ncu ? 96 : h3_gather_tiles(128, count, N) <= ncu ? 128 : 160;
+}
+
+template <int KNOCK = 0, int FBM = 0>
+static __global__ __launch_bounds__(512) void gemm_nt_f16x3_gather_kernel(
+    const unsigned short* __restrict__ Ap, const unsigned short* __restrict__ Bp0, const unsigned short* __restrict__ Bp1,
+    const float* __restrict__ bias0, const float* __restrict__ bias1, float* __restrict__ C, int ldc, const int* __restrict__ rows,
+    int MA, int N, int K, int ncu) {
+    __shared__ __attribute__((aligned(16))) int rtab[512];
+    const int count = rows[0];
+    const int bm = FBM ? FBM : h3_gather_bm(count, N, ncu);
+    const int nt = h3_gather_tiles(bm, count, N);
+    if ((int)blockIdx.x >= nt) return;
+    const int wgid = h3_xcd_tile(blockIdx.x, nt);
+    if (bm == 96) h3_gemm_tile<3, KNOCK, 96, true>(Ap, Bp0, Bp1, bias0, bias1, C, ldc, count, MA, N, K, wgid, rows + 1, rtab);
+    else if (bm == 128) h3_gemm_tile<3, KNOCK, 128, true>(Ap, Bp0, Bp1, bias0, bias1, C, ldc, count, MA, N, K, wgid, rows + 1, rtab);
+    else if (count < MA) h3_gemm_tile<3, KNOCK, 160, true>(Ap, Bp0, Bp1, bias0, bias1, C, ldc, count, MA, N, K, wgid, rows + 1, rtab);
+    else h3_gemm_tile<3, KNOCK, 160, false>(Ap, Bp0, Bp1, bias0, bias1, C, ldc, MA, MA, N, K, wgid, nullptr, nullptr);   // every row: the dense tile
 }
 
 static inline bool gemm_f16x3_ok(int M, int N, int K) {
@@ -211,5 +346,20 @@ static inline hipError_t launch_gemm_nt_f16x3(sir_handle* h, hipStream_t st, con
     }
     const int nwg = ((M + H3_BM - 1) / H3_BM) * 2 * (N / H3_BN);
     hipLaunchKernelGGL((gemm_nt_f16x3_kernel<3, 0>), dim3(nwg), dim3(512), h3_lds_bytes(3), st, Ap, Bp0, Bp1, bias0, bias1, C, ldc, M, N, K);
+    return hipGetLastError();
+}
+
+// the same over the row list `rows` (device memory: rows[0] = count <= MA, then the rows) of A's MA-row planes; no host sync
+static inline hipError_t launch_gemm_nt_f16x3_gather(sir_handle* h, hipStream_t st, const unsigned short* Ap, const unsigned short* Bp0,
+                                                     const unsigned short* Bp1, const float* bias0, const float* bias1, float* C, int ldc,
+                                                     const int* rows, int MA, int N, int K) {
+    if (!gemm_f16x3_ok(MA, N, K) || K < 2 * H3_BK || (size_t)MA * ldc >= ((size_t)1 << 31)) return hipErrorInvalidValue;   // (K >= 2 BK: the K loop's barriers publish rtab)
+    if (!h->attr_gemm_gather) {
+        hipError_t e = hipFuncSetAttribute((const void*)gemm_nt_f16x3_gather_kernel<0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, h3_lds_bytes(3));
+        if (e != hipSuccess) return e;
+        h->attr_gemm_gather = true;
+    }
+    hipLaunchKernelGGL((gemm_nt_f16x3_gather_kernel<0, 0>), dim3(h3_gather_tiles(96, MA, N)), dim3(512), h3_lds_bytes(3), st, Ap, Bp0, Bp1,
+                       bias0, bias1, C, ldc, rows, MA, N, K, h->num_cus);
     return hipGetLastError();
 }

@@ -10,7 +10,8 @@
 //   d3  = min(S, (E0 + 14) / 8)   GRU steps s < d3 see data (conv3 output s reads frame columns >= 8 s - 7)
 //   d2  = min(wp2, 2 d3 + 1), d1 = min(wp1, 2 d2 + 1)   columns of conv2 / conv1 those steps read
 // conv1 stores pooled columns < d1; conv2 / conv3 run over a compacted list of 4-tile-column tasks (Wino2Geo::ctab), ceil(d / 4)
-// of them per utterance; the layer-0 recurrence reads the template's gi row for steps s >= d3.  Columns past the computed ones
+// of them per utterance; the layer-0 input projection runs over a row list (steps s < d3 of each utterance + the template's S
+// rows) and the layer-0 recurrence reads the template's gi row for steps s >= d3.  Columns past the computed ones
 // are left unwritten in a1 / a2 / x0 / xs / gi.  The conv fallback kernels (shapes the Winograd kernel does not cover) keep the
 // full path.
 #include "bf16x6_kernels.h"
@@ -29,7 +30,8 @@ enum WsBuf {
     WS_Y0,       // GRU layer 0 output [B][S][512]
     WS_Y1,       // GRU layer 1 output [B][S][512]
     WS_CTX,      // attention-pooled context [B][512]
-    WS_PAD,      // pad-skip tables (int): E0[B], conv1 columns d1[B + 1], GRU steps d3[B + 1], conv2 / conv3 task-column lists
+    WS_PAD,      // pad-skip tables (int): E0[B], conv1 columns d1[B + 1], GRU steps d3[B + 1], conv2 / conv3 task-column lists,
+                 // layer-0 projection row list
     WS_XZ,       // all-zero feature row [64][T] of the template utterance (zeroed by pad_tables_kernel on every call)
     WS_BN,       // folded BN: scale[224] then shift[224] (channels of bn1|bn2|bn3)
     WS_WHT,      // W_hh fragments of the recurrence kernel, [4 (layer, direction)][GRU_FRAG_BYTES]
@@ -54,11 +56,12 @@ bool make_dims(int batch, int t_frames, Dims* d) {
 }
 
 // int offsets inside WS_PAD
-struct PadTabs { size_t e0, d1, d3, tab2, tab3, count; };
+struct PadTabs { size_t e0, d1, d3, tab2, tab3, rows, count; };
 PadTabs pad_tabs(const Dims& d) {
     PadTabs t;
     const size_t n = (size_t)d.B + 1;
-    t.e0 = 0; t.d1 = d.B; t.d3 = t.d1 + n; t.tab2 = t.d3 + n; t.tab3 = t.tab2 + 1 + n * d.k2max; t.count = t.tab3 + 1 + n * d.k3max;
+    t.e0 = 0; t.d1 = d.B; t.d3 = t.d1 + n; t.tab2 = t.d3 + n; t.tab3 = t.tab2 + 1 + n * d.k2max; t.rows = t.tab3 + 1 + n * d.k3max;
+    t.count = t.rows + 1 + n * d.S;
     return t;
 }
 
@@ -112,9 +115,11 @@ static __global__ __launch_bounds__(256) void pad_extent_kernel(const float* __r
 }
 
 // one workgroup: demanded columns per utterance from E0 (see the head of this file; utterance B = the template, full width),
-// prefix sums over the batch -> compacted task-column lists of conv2 / conv3 (Wino2Geo::ctab), and the template's zero features
+// prefix sums over the batch -> compacted task-column lists of conv2 / conv3 (Wino2Geo::ctab), the layer-0 projection's row list
+// (u * S + s for s < d3[u], ascending; the template's S rows last), and the template's zero features
 static __global__ __launch_bounds__(1024) void pad_tables_kernel(const int* __restrict__ e0, Dims d, int* __restrict__ d1o, int* __restrict__ d3o,
-                                                                 int* __restrict__ tab2, int* __restrict__ tab3, float* __restrict__ xz) {
+                                                                 int* __restrict__ tab2, int* __restrict__ tab3, int* __restrict__ prow,
+                                                                 float* __restrict__ xz) {
     const int tid = threadIdx.x;
     for (int i = tid; i < 64 * d.T; i += 1024) xz[i] = 0.0f;
     const int nu = d.B + 1, per = (nu + 1023) / 1024, u0 = min(nu, tid * per), u1 = min(nu, u0 + per);
@@ -125,26 +130,27 @@ static __global__ __launch_bounds__(1024) void pad_tables_kernel(const int* __re
         c1 = min(d.wp1, 2 * c2 + 1);
         k2 = (c2 + 3) / 4; k3 = (c3 + 3) / 4;
     };
-    int s2 = 0, s3 = 0, c1, c3, k2, k3;
-    for (int u = u0; u < u1; ++u) { need(u, c1, c3, k2, k3); s2 += k2; s3 += k3; }
-    __shared__ int p2[1024], p3[1024];
-    p2[tid] = s2; p3[tid] = s3;
+    int s2 = 0, s3 = 0, sr = 0, c1, c3, k2, k3;
+    for (int u = u0; u < u1; ++u) { need(u, c1, c3, k2, k3); s2 += k2; s3 += k3; sr += c3; }
+    __shared__ int p2[1024], p3[1024], pr[1024];
+    p2[tid] = s2; p3[tid] = s3; pr[tid] = sr;
     __syncthreads();
     for (int o = 1; o < 1024; o <<= 1) {                     // inclusive scan (Hillis-Steele)
-        const int a2 = tid >= o ? p2[tid - o] : 0, a3 = tid >= o ? p3[tid - o] : 0;
+        const int a2 = tid >= o ? p2[tid - o] : 0, a3 = tid >= o ? p3[tid - o] : 0, ar = tid >= o ? pr[tid - o] : 0;
         __syncthreads();
-        p2[tid] += a2; p3[tid] += a3;
+        p2[tid] += a2; p3[tid] += a3; pr[tid] += ar;
         __syncthreads();
     }
-    int o2 = p2[tid] - s2, o3 = p3[tid] - s3;
+    int o2 = p2[tid] - s2, o3 = p3[tid] - s3, orw = pr[tid] - sr;
     for (int u = u0; u < u1; ++u) {
         need(u, c1, c3, k2, k3);
         d1o[u] = c1; d3o[u] = c3;
         for (int k = 0; k < k2; ++k) tab2[1 + o2 + k] = u * d.tw2 + 4 * k;
         for (int k = 0; k < k3; ++k) tab3[1 + o3 + k] = u * d.tw3 + 4 * k;
-        o2 += k2; o3 += k3;
+        for (int s = 0; s < c3; ++s) prow[1 + orw + s] = u * d.S + s;
+        o2 += k2; o3 += k3; orw += c3;
     }
-    if (tid == 1023) { tab2[0] = p2[1023]; tab3[0] = p3[1023]; }
+    if (tid == 1023) { tab2[0] = p2[1023]; tab3[0] = p3[1023]; prow[0] = pr[1023]; }
 }
 
 }  // namespace
@@ -252,7 +258,7 @@ extern "C" int sir_model_infer(sir_handle* h, const sir_model_weights* w, const 
         if (w2) {                                                 // pad-skip extents and tables (two small launches, counted with conv1)
             hipLaunchKernelGGL(pad_extent_kernel, dim3(B), dim3(256), 0, st, feats, d.T, ptab + pt.e0);
             hipLaunchKernelGGL(pad_tables_kernel, dim3(1), dim3(1024), 0, st, (const int*)(ptab + pt.e0), d, ptab + pt.d1, ptab + pt.d3,
-                               ptab + pt.tab2, ptab + pt.tab3, xz);
+                               ptab + pt.tab2, ptab + pt.tab3, ptab + pt.rows, xz);
         }
         hipLaunchKernelGGL(conv1_mfma_bn_relu_pool_kernel, dim3((d.wp1 + C1_PCOLS - 1) / C1_PCOLS, 1, BT), dim3(256), 0, st, feats,
                            w->conv_w[0], bns, bnt, a1, 64, d.T, 32, d.wp1, (const float*)xz, B, w2 ? (const int*)(ptab + pt.d1) : (const int*)nullptr);
@@ -282,10 +288,16 @@ extern "C" int sir_model_infer(sir_handle* h, const sir_model_weights* w, const 
     // ---- 2-layer bidirectional GRU ----------------------------------------------------------
     const int M = B * S;
     {
-        // (over the template's rows too; rows of skipped steps hold whatever their unwritten xs rows give and are never read)
+        // pad skip: only the rows the recurrence reads (the row list of pad_tables_kernel: steps s < d3 of every utterance and the
+        // template's S rows), on a tile the compacted count fills the chip with; the other gi rows are left unwritten
         SirProfScope prof(h, SIR_K_GEMM_IH0, st);
-        SIR_HIP_TRY(launch_gemm_nt_f16x3(h, st, (const unsigned short*)xs, (const unsigned short*)wsl0,
-                                         (const unsigned short*)(wsl0 + (size_t)2 * 768 * 1024), w->gru_b_ih[0], w->gru_b_ih[1], gi, 1536, BT * S, 768, 1024));
+        if (w2)
+            SIR_HIP_TRY(launch_gemm_nt_f16x3_gather(h, st, (const unsigned short*)xs, (const unsigned short*)wsl0,
+                                                    (const unsigned short*)(wsl0 + (size_t)2 * 768 * 1024), w->gru_b_ih[0], w->gru_b_ih[1], gi, 1536,
+                                                    (const int*)(ptab + pt.rows), BT * S, 768, 1024));
+        else
+            SIR_HIP_TRY(launch_gemm_nt_f16x3(h, st, (const unsigned short*)xs, (const unsigned short*)wsl0,
+                                             (const unsigned short*)(wsl0 + (size_t)2 * 768 * 1024), w->gru_b_ih[0], w->gru_b_ih[1], gi, 1536, M, 768, 1024));
     }
     {
         SirProfScope prof(h, SIR_K_GRU0, st);

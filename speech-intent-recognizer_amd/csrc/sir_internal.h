@@ -74,7 +74,7 @@ struct sir_handle {
     int cluster_run;                   // chained mode: launches in a row that came from cluster_stream
     // hipFuncSetAttribute(MaxDynamicSharedMemorySize) latches, per handle = per device (a process-wide static would skip
     // the second device of a process that drives several)
-    bool attr_gemm_v3, attr_gru_quad, attr_gru_bwd_quad, attr_tn, attr_wgrad;
+    bool attr_gemm_v3, attr_gemm_gather, attr_gru_quad, attr_gru_bwd_quad, attr_tn, attr_wgrad;
     bool attr_wino2[6];                // conv3x3_wino2_bf16x6_kernel instantiations (model_infer.hip: 0, 1; model_train.hip: 2 .. 5)
     float* zero_page;                  // 4 KB of zeros: DMA source of the second-generation Winograd kernel's out-of-image pixels
     int num_cus;                       // persistent kernels launch one workgroup per CU

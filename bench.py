@@ -19,10 +19,16 @@ launcher (WORLD_SIZE set) it is one rank; WORLD_SIZE != --gpus is an error, not 
 Every timed figure is the MEDIAN of `--repeats` (5) timed regions of exactly K steps, each bracketed by
 barrier + synchronize on both sides and max-reduced over ranks; min / max are reported.
 
-Prints ONE JSON line on rank 0 (contract in the task description), including
-  roofline     -- dominant kernel, achieved vs peak, timed live with HIP events on its stream
-  cpu_baseline -- the CPU restatement of the reference path (oracle/, "port") timed on the host
-                  cores of this box on a bounded sample (rank 0, N = 1 only)
+A plain run does only what the headline figure needs: set-up, W warm-up steps, the untimed per-kernel pass that picks
+the kernel bracketed with HIP events in the timed regions, the timed regions, --dump-outputs, and ONE JSON line on rank 0
+(value, ms_per_step, timed_regions, kernels_avg_ms, features_stage, gru_recurrence).  --full adds every other leg to
+the same line:
+  roofline       -- dominant kernel, achieved vs peak, timed live with HIP events on its stream (single-stream leg)
+  single_stream  -- the same regions strictly serial
+  sustained      -- >= --sustain-seconds of pipelined steps with package power / sclk
+  train, train_aug -- the training-step legs (with rccl_world1, host_fed, dropin_epoch at N = 1)
+  cpu_baseline   -- the CPU restatement of the reference path (oracle/, "port") timed on the host
+                    cores of this box on a bounded sample (rank 0, N = 1 only), with the argmax parity flag
 
 --dump-outputs DIR writes what the last timed inference step returned (features, logits, predicted indices) as .npy
 files.  Clips and weights are seeded, so the same arguments give the same inputs on every run and two builds of the
@@ -608,6 +614,10 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps each; the median is reported")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed regions, also run the legs that take runs of their own: single-stream regions and "
+                         "roofline, sustained region, training legs, CPU baselines and parity (the --no-* switches below "
+                         "and --train-steps, --dropin-clips, --sustain-seconds apply to them)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-train", action="store_true", help="skip the training-step legs")
     ap.add_argument("--augment", dest="augment", action="store_true", default=True,
@@ -760,7 +770,8 @@ def main():
     dominant = max(infer_names, key=lambda k: kernel_ms[k])
     lib.sir_profile_enable(fz.handle, 2, names.index(dominant))
 
-    # timed regions: exactly K steps each; the dominant kernel is bracketed by a HIP event pair on its own stream
+    # timed regions: exactly K steps each; the dominant kernel is bracketed by a HIP event pair on its own stream.  A plain
+    # run reports no roofline, but keeps the pass above and the event pair so that its timed steps are the --full run's
     times = timed_regions(step, args.steps, args.repeats)
     elapsed = statistics.median(times)
     if rank == 0:
@@ -776,7 +787,7 @@ def main():
     # timed in isolation.  (A single batch cannot be made to overlap with itself: all its utterances already advance in
     # parallel inside the recurrence, so any split only lengthens the dependent chain -- DESIGN.md section 4.)
     single = None
-    if ns > 1:
+    if args.full and ns > 1:
         pipe1 = BatchPipeline(model, n_streams=1)
 
         def step1(i):
@@ -798,7 +809,7 @@ def main():
     # an external SMI sampler sees the load, with package power / sclk sampled from sysfs beside it (the "matrix-core
     # kernels sit at the power cap" claim of DESIGN.md section 4 then shows up in this line)
     sustained = None
-    if args.sustain_seconds > 0:
+    if args.full and args.sustain_seconds > 0:
         chunk = 256
         if dist is not None:
             dist.barrier()
@@ -824,12 +835,13 @@ def main():
     # -- fused HIP features + forward/backward + Adam at per-GPU batch 256; with N > 1 each step
     # ends in the RCCL all-reduce (mean) of the flat 13 MB gradient buffer (two buckets, overlapped).
     gpu_pred32 = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    cpu_leg = args.full and world == 1 and not args.no_cpu_baseline
+    if rank == 0 and cpu_leg:
         # predictions of the sample the CPU baseline runs, taken before the training leg moves the weights
         _, gpu_pred32 = model.predict(fz(synth.synth_clips(32, CLIP_LEN, seed=1234).to(dev)))
         gpu_pred32 = gpu_pred32.cpu()
     train_info = train_aug_info = None
-    if not args.no_train:
+    if args.full and not args.no_train:
         from sir_amd import train_ops
         from sir_amd.optim import FusedAdam
         from sir_amd.scripts import augment as aug
@@ -969,41 +981,43 @@ def main():
     if rank == 0:
         total_utts = batch * world * args.steps
         value = total_utts / elapsed
-        d_ms = dom_ms[dominant]
-        if dominant in FLOPS_PER_UTT:
-            roofline = mfma_roofline(dominant, d_ms, dom_cnt[dominant], batch)
-            if single is not None:
-                # with several streams the kernel's launches in the pipelined region share the CUs with the other stream's
-                # kernels (its "duration" then includes co-scheduling); the roofline of the KERNEL is taken from the
-                # single-stream timed leg of this same run (K steps, HIP events on the launch stream), and the pipelined
-                # figures are kept beside it
-                iso = mfma_roofline(dominant, single["dominant_avg_launch_ms"], single["dominant_launches"], batch)
-                iso["pipelined"] = {"streams": ns, "avg_launch_ms": roofline["avg_launch_ms"], "achieved": roofline["achieved"],
-                                    "frac": roofline["frac"],
-                                    "note": "same kernel inside the multi-stream timed region: it shares the GPU with the other "
-                                            "stream's kernels, so its launch duration includes co-scheduling"}
-                iso["measured_in"] = "single-stream timed leg of this run (same K steps, one HIP stream)"
-                roofline = iso
-        else:
-            achieved = FEATURE_BYTES_PER_UTT * batch / (d_ms * 1e-3) / 1e9
-            roofline = {"kernel": dominant, "bound": "hbm", "achieved": round(achieved, 2), "peak": PEAK_HBM_GBS,
-                        "unit": "GB/s", "frac": round(achieved / PEAK_HBM_GBS, 4), "traffic": None,
-                        "avg_launch_ms": round(d_ms, 5), "launches": dom_cnt[dominant],
-                        "bytes_per_launch": FEATURE_BYTES_PER_UTT * batch}
-        # the kernel SYMBOL with the largest total time of a step (two launches of one symbol add up), beside the largest single launch
-        sym_ms, sym_flops = {}, {}
-        for k in infer_names:
-            if kernel_ms.get(k, 0.0) > 0.0 and k in KERNEL_SYMBOL:
-                sym_ms[KERNEL_SYMBOL[k]] = sym_ms.get(KERNEL_SYMBOL[k], 0.0) + kernel_ms[k]
-                sym_flops[KERNEL_SYMBOL[k]] = sym_flops.get(KERNEL_SYMBOL[k], 0) + FLOPS_PER_UTT.get(k, 0) * batch
-        if sym_ms:
-            top = max(sym_ms, key=lambda k: sym_ms[k])
-            tf = sym_flops[top] / (sym_ms[top] * 1e-3) / 1e12 if sym_flops[top] else None
-            roofline["by_symbol"] = {"symbol": top, "total_ms_per_step": round(sym_ms[top], 5),
-                                     "share_of_serial_step": round(sym_ms[top] / sum(sym_ms.values()), 4),
-                                     "achieved": round(tf, 3) if tf else None, "peak": round(PEAK_F16X3_TFLOPS, 1), "unit": "TFLOP/s",
-                                     "frac": round(tf / PEAK_F16X3_TFLOPS, 4) if tf else None,
-                                     "measured_in": "untimed HIP-event pass, one batch at a time (5 steps)"}
+        roofline = None
+        if args.full:
+            d_ms = dom_ms[dominant]
+            if dominant in FLOPS_PER_UTT:
+                roofline = mfma_roofline(dominant, d_ms, dom_cnt[dominant], batch)
+                if single is not None:
+                    # with several streams the kernel's launches in the pipelined region share the CUs with the other stream's
+                    # kernels (its "duration" then includes co-scheduling); the roofline of the KERNEL is taken from the
+                    # single-stream timed leg of this same run (K steps, HIP events on the launch stream), and the pipelined
+                    # figures are kept beside it
+                    iso = mfma_roofline(dominant, single["dominant_avg_launch_ms"], single["dominant_launches"], batch)
+                    iso["pipelined"] = {"streams": ns, "avg_launch_ms": roofline["avg_launch_ms"], "achieved": roofline["achieved"],
+                                        "frac": roofline["frac"],
+                                        "note": "same kernel inside the multi-stream timed region: it shares the GPU with the other "
+                                                "stream's kernels, so its launch duration includes co-scheduling"}
+                    iso["measured_in"] = "single-stream timed leg of this run (same K steps, one HIP stream)"
+                    roofline = iso
+            else:
+                achieved = FEATURE_BYTES_PER_UTT * batch / (d_ms * 1e-3) / 1e9
+                roofline = {"kernel": dominant, "bound": "hbm", "achieved": round(achieved, 2), "peak": PEAK_HBM_GBS,
+                            "unit": "GB/s", "frac": round(achieved / PEAK_HBM_GBS, 4), "traffic": None,
+                            "avg_launch_ms": round(d_ms, 5), "launches": dom_cnt[dominant],
+                            "bytes_per_launch": FEATURE_BYTES_PER_UTT * batch}
+            # the kernel SYMBOL with the largest total time of a step (two launches of one symbol add up), beside the largest single launch
+            sym_ms, sym_flops = {}, {}
+            for k in infer_names:
+                if kernel_ms.get(k, 0.0) > 0.0 and k in KERNEL_SYMBOL:
+                    sym_ms[KERNEL_SYMBOL[k]] = sym_ms.get(KERNEL_SYMBOL[k], 0.0) + kernel_ms[k]
+                    sym_flops[KERNEL_SYMBOL[k]] = sym_flops.get(KERNEL_SYMBOL[k], 0) + FLOPS_PER_UTT.get(k, 0) * batch
+            if sym_ms:
+                top = max(sym_ms, key=lambda k: sym_ms[k])
+                tf = sym_flops[top] / (sym_ms[top] * 1e-3) / 1e12 if sym_flops[top] else None
+                roofline["by_symbol"] = {"symbol": top, "total_ms_per_step": round(sym_ms[top], 5),
+                                         "share_of_serial_step": round(sym_ms[top] / sum(sym_ms.values()), 4),
+                                         "achieved": round(tf, 3) if tf else None, "peak": round(PEAK_F16X3_TFLOPS, 1), "unit": "TFLOP/s",
+                                         "frac": round(tf / PEAK_F16X3_TFLOPS, 4) if tf else None,
+                                         "measured_in": "untimed HIP-event pass, one batch at a time (5 steps)"}
         feat_ms = kernel_ms.get("feat_frames", 0.0)      # ONE fused kernel since round 2 (profile id "feat_frames")
         gru = {}
         for k, algo in GRU_ALGO_BYTES.items():
@@ -1029,7 +1043,6 @@ def main():
                                      "0.45-0.5x bf16x6's on the real GRU operands, profiles/r04/ab_f16x3.txt), the backward under a "
                                      "power-of-two loss scale (exact), everything else fp32 VALU"},
             "dist": dist_info,
-            "roofline": roofline,
             "kernels_avg_ms": {k: round(kernel_ms[k], 5) for k in infer_names if kernel_ms[k] > 0.0},
             "features_stage": {"bound": "hbm", "avg_ms": round(feat_ms, 5),
                                "achieved_GBs": round(FEATURE_BYTES_PER_UTT * batch / (feat_ms * 1e-3) / 1e9, 1) if feat_ms else None,
@@ -1037,6 +1050,8 @@ def main():
                                "bytes_per_launch": FEATURE_BYTES_PER_UTT * batch},
             "gru_recurrence": gru,
         }
+        if roofline is not None:
+            out["roofline"] = roofline
         if single is not None:
             out["single_stream"] = single
         if sustained is not None:
@@ -1045,7 +1060,7 @@ def main():
             out["train"] = train_info
         if train_aug_info is not None:
             out["train_aug"] = train_aug_info
-        if world == 1 and not args.no_cpu_baseline:
+        if cpu_leg:
             base, cpu_pred = cpu_baseline()
             out["cpu_baseline"] = base
             out["speedup_vs_cpu_all_cores"] = round(value / base["value"], 1)

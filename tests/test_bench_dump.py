@@ -1,6 +1,7 @@
 """bench.py --dump-outputs: what the last timed inference step returned, written as .npy files (float32 / float64, at most
 64 MB in all) so that two builds can be compared output for output.  The CPU tests cover the writer; the GPU test runs
 the benchmark and recomputes that step from the same seeded batch."""
+import json
 import os
 import subprocess
 import sys
@@ -62,10 +63,12 @@ def test_dump_is_the_last_timed_step(tmp_path):
     from sir_amd.models.models import CNNAudioGRU
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
-                        "--repeats", "2", "--no-train", "--no-cpu-baseline", "--sustain-seconds", "0",
-                        "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+                        "--repeats", "2", "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
-    assert bench.pick_json_line(r.stdout.splitlines()) is not None
+    d = json.loads(bench.pick_json_line(r.stdout.splitlines()))
+    # a plain run carries the timed regions only: every leg that takes runs of its own waits for --full
+    assert d["timed_regions"]["repeats"] == 2 and d["ms_per_step"] > 0
+    assert not {"roofline", "single_stream", "sustained", "train", "train_aug", "cpu_baseline", "parity"} & set(d)
     assert sorted(os.listdir(tmp_path)) == ["features.npy", "logits.npy", "predictions.npy"]
     feats, logits, pred = (np.load(tmp_path / f"{n}.npy") for n in ("features", "logits", "predictions"))
 

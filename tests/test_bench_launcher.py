@@ -76,8 +76,8 @@ def test_refuses_instead_of_degrading(monkeypatch, capsys):
 def test_two_ranks_on_one_gpu_without_an_external_launcher():
     """`SIR_BENCH_SHARE_GPU=1 python bench.py --gpus 2` prints n_gpus 2 and a 2-rank process group (gloo rehearsal of the
     RCCL path: same code, both ranks on cuda:0)."""
-    r = _run(["--gpus", "2", "--steps", "3", "--warmup", "2", "--repeats", "2", "--train-steps", "2", "--no-cpu-baseline"],
-             {"SIR_BENCH_SHARE_GPU": "1"})
+    r = _run(["--gpus", "2", "--full", "--steps", "3", "--warmup", "2", "--repeats", "2", "--train-steps", "2",
+              "--no-cpu-baseline"], {"SIR_BENCH_SHARE_GPU": "1"})
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads(bench.pick_json_line(r.stdout.splitlines()))
     assert d["n_gpus"] == 2 and d["dist"]["world_size"] == 2 and d["dist"]["backend"] == "gloo"

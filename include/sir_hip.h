@@ -98,6 +98,31 @@ int sir_resample(sir_handle* h, const void* wave, int wave_dtype, int64_t wave_s
                  const int32_t* lengths, int batch, int max_len, int orig_freq, int new_freq, float* out,
                  int64_t out_stride, int max_out_len, int32_t* out_lengths, void* stream);
 
+/* ---- waveform perturbation: pitch and tempo ---------------------------------
+ * sir_wave_perturb replaces, for a whole batch, the two sox effects of scripts/augment.py:30-80 -- pitch_shift (`pitch c`
+ * then `rate sr`) and speed_change (`tempo f` then `rate sr`) -- applied per utterance after the time shift, in the
+ * reference's order (augment.py:119-133): shift, pitch, speed.  Noise and SpecAugment stay in sir_features_fwd.
+ * Tempo is WSOLA as sox 14.4's `tempo` (default profile, linear search; segment / search / overlap from
+ * h->cfg.sample_rate); pitch is tempo 1/d (d = 2^(c/1200)) resampled back to the clip's length at fractional positions
+ * with sir_resample's windowed-sinc filter, not sox's `rate` filter.  No sample-level parity with sox is claimed.
+ *   wave       : [batch][wave_stride] f32 or i16 (wave_dtype; i16 dequantised as s / 32768), row length lengths[b]
+ *   shift      : optional device int32[batch], samples, as sir_augment.shift (NULL = none)
+ *   pitch_cents: optional device f32[batch] in [-200, 200]; 0 = not drawn (NULL = none)
+ *   tempo      : optional device f32[batch] in [0.5, 2] (> 1 faster and shorter); 1 = not drawn (NULL = none)
+ *                A value outside its range zeroes that row (length 0) and is reported by sir_check_status (SIR_EINVAL).
+ *   out        : [batch][out_stride] f32, zero beyond each row's output length
+ *   out_lengths: optional device int32[batch] = min(sir_perturb_out_len(lengths[b], tempo[b]), max_out_len)
+ *   offsets_out: optional test hook (NULL in production): int32 [batch][2][max_segments], the chosen WSOLA offset of each
+ *                segment of the pitch pass (index 0) and the speed pass (index 1), -1 where unused
+ *   workspace  : sir_perturb_workspace_bytes(batch, max_len) bytes, 256-byte aligned (may be NULL without pitch_cents)
+ * sir_perturb_out_len: host helper, int(length / tempo + 0.5) in double (-1 on bad input). */
+int sir_perturb_out_len(int length, float tempo);
+size_t sir_perturb_workspace_bytes(const sir_handle* h, int batch, int max_len);
+int sir_wave_perturb(sir_handle* h, const void* wave, int wave_dtype, int64_t wave_stride, const int32_t* lengths, int batch,
+                     int max_len, const int32_t* shift, const float* pitch_cents, const float* tempo, float* out,
+                     int64_t out_stride, int max_out_len, int32_t* out_lengths, int32_t* offsets_out, int max_segments,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- feature path --------------------------------------------------------------------------
  * sir_features_fwd replaces, for a whole batch in one launch pair,
  *   AudioFeatureExtractor.extract_features  scripts/precompute_features.py:59-73

@@ -60,6 +60,11 @@ SIGNATURES = {
     "sir_resample_out_len": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "sir_resample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
                                C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+    "sir_perturb_out_len": (C.c_int, [C.c_int, C.c_float]),
+    "sir_perturb_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    "sir_wave_perturb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                   C.c_void_p, C.c_size_t, C.c_void_p]),
     "sir_gather_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
     "sir_model_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),

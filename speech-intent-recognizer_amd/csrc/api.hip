@@ -288,6 +288,11 @@ static int check_status_impl(sir_handle* h, hipStream_t st, const char* who) {
                       "computed from the clamped value are invalid", who, v);
         return SIR_EINVAL;
     }
+    if (v & 16u) {
+        sir_set_error("%s: sir_wave_perturb was given a pitch outside [-200, 200] cents or a tempo outside [0.5, 2] (status %u): "
+                      "those rows are zero with length 0", who, v);
+        return SIR_EINVAL;
+    }
     if (v & 4u) {
         sir_set_error("%s: sir_gather_features was given an index outside its store (status %u): those rows are zero", who, v);
         return SIR_EINVAL;

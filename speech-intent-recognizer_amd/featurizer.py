@@ -46,6 +46,7 @@ class HipFeaturizer:
         self._h = C.c_void_p()
         _native.check(_native.lib().sir_create(C.byref(cfg), C.byref(self._h)), "sir_create")
         self._ws = None
+        self._pws = None        # workspace of perturb()
         self._pins = 0          # library objects (sir_pipeline) created from this handle that are still alive
 
     def pin(self):
@@ -157,6 +158,64 @@ class HipFeaturizer:
                               int(orig_freq), int(new_freq), out.data_ptr(), out.stride(0), max_out,
                               out_len.data_ptr(), _native.current_stream_ptr())
         _native.check(rc, "sir_resample")
+        return out, out_len
+
+    # ---- pitch / tempo perturbation (scripts/augment.py:30-80 pitch_shift / speed_change) -------------------------
+    def perturb(self, wave, lengths=None, shift=None, pitch_cents=None, tempo=None, max_out_len=None, offsets_out=None):
+        """Per-utterance shift -> pitch -> speed (``sir_wave_perturb``) of a GPU batch: wave [B, L]
+        float32/int16, lengths int32 [B] (default all L); ``shift`` int32 [B] samples, ``pitch_cents`` float32 [B] in
+        [-200, 200] (0 = not drawn), ``tempo`` float32 [B] in [0.5, 2] (1 = not drawn), each optional (None = off).
+        ``max_out_len`` defaults to the longest output of the reference's tempo range (L at tempo 0.85; rows of a slower
+        tempo are cut there).
+        ``offsets_out`` (test hook): int32 [B, 2, max_segments] receives the chosen WSOLA offsets, -1 where unused.
+        Returns (out [B, max_out_len] float32, zero beyond each row's length, out_lengths int32 [B])."""
+        _native.require_hip(wave, lengths, offsets_out)
+        if wave.dim() != 2 or wave.stride(1) != 1:
+            raise _native.SirError("wave must be [B, L] with unit inner stride")
+        dt = {torch.float32: _native.WAVE_F32, torch.int16: _native.WAVE_I16}.get(wave.dtype)
+        if dt is None:
+            raise _native.SirError(f"unsupported waveform dtype {wave.dtype}")
+        bsz, max_len = wave.shape
+        if bsz == 0 or max_len == 0:
+            raise _native.SirError("perturb needs a non-empty [B, L] batch")
+        lib = _native.lib()
+        if lengths is None:
+            lengths = torch.full((bsz,), max_len, dtype=torch.int32, device=wave.device)
+        lengths = lengths.to(torch.int32).contiguous()
+        keep = []
+
+        def ptr(t, dtype):
+            if t is None:
+                return None
+            t = t.to(device=wave.device, dtype=dtype).contiguous()
+            if t.numel() != bsz:
+                raise _native.SirError(f"per-utterance argument of {t.numel()} values for a batch of {bsz}")
+            keep.append(t)
+            return t.data_ptr()
+        p_shift, p_cents, p_tempo = ptr(shift, torch.int32), ptr(pitch_cents, torch.float32), ptr(tempo, torch.float32)
+        if max_out_len is None:
+            max_out_len = lib.sir_perturb_out_len(max_len, 0.85) if tempo is not None else max_len
+            max_out_len = max(max_out_len, max_len)
+        max_out_len = int(max_out_len)
+        out = torch.empty((bsz, max_out_len), dtype=torch.float32, device=wave.device)
+        out_len = torch.empty((bsz,), dtype=torch.int32, device=wave.device)
+        ws, nbytes = None, 0
+        if pitch_cents is not None:
+            nbytes = lib.sir_perturb_workspace_bytes(self._h, bsz, max_len)
+            if self._pws is None or self._pws.numel() < nbytes or self._pws.device != wave.device:
+                self._pws = torch.empty(nbytes, dtype=torch.uint8, device=wave.device)
+            ws, nbytes = self._pws.data_ptr(), self._pws.numel()
+        max_seg = 0
+        if offsets_out is not None:
+            if offsets_out.dtype != torch.int32 or not offsets_out.is_contiguous() or offsets_out.dim() != 3 \
+                    or tuple(offsets_out.shape[:2]) != (bsz, 2):
+                raise _native.SirError("offsets_out must be a contiguous int32 [B, 2, max_segments] tensor")
+            max_seg = offsets_out.shape[2]
+        rc = lib.sir_wave_perturb(self._h, wave.data_ptr(), dt, wave.stride(0), lengths.data_ptr(), bsz, max_len,
+                                  p_shift, p_cents, p_tempo, out.data_ptr(), out.stride(0), max_out_len, out_len.data_ptr(),
+                                  offsets_out.data_ptr() if offsets_out is not None else None, max_seg, ws, nbytes,
+                                  _native.current_stream_ptr())
+        _native.check(rc, "sir_wave_perturb")
         return out, out_len
 
 

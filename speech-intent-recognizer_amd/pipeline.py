@@ -156,8 +156,14 @@ class FeaturePrefetcher:
             self.stream.wait_event(self.freed[k])           # the step that read this buffer has finished
         if self.bufs[k] is None or self.bufs[k].shape[0] != wave.shape[0]:
             self.bufs[k] = torch.empty((wave.shape[0], 64, self.t_pad), dtype=torch.float32, device=wave.device)
+        kw = self.kw
         with torch.cuda.stream(self.stream):
-            self.fz(wave, lengths, t_pad=self.t_pad, out=self.bufs[k], **self.kw)
+            if kw.get("pitch_cents") is not None or kw.get("tempo") is not None:
+                # pitch / speed (sir_wave_perturb, with the shift) first, then the feature kernel with the noise and masks
+                kw = dict(kw)
+                wave, lengths = self.fz.perturb(wave, lengths, shift=kw.pop("shift", None),
+                                                pitch_cents=kw.pop("pitch_cents", None), tempo=kw.pop("tempo", None))
+            self.fz(wave, lengths, t_pad=self.t_pad, out=self.bufs[k], **kw)
             self.ready[k].record(self.stream)
         self.head += 1
 

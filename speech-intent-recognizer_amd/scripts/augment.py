@@ -4,9 +4,11 @@ The reference's ``time_shift`` (:6-28) and ``add_noise`` (:82-96) operate on one
 tensor at a time (and are not called from anywhere in the reference).  Here they are parameters of
 ``sir_features_fwd``: the shift moves the read index and the noise is a counter-based N(0,1) keyed
 by (seed, utterance, sample), both applied while the samples are loaded for the FFT, so an
-augmented batch costs no extra pass over HBM.  ``pitch_shift`` / ``speed_change`` need libsox and are
-out of scope: calling them raises, and ``apply_augmentation`` skips them
-(drawing their random numbers, so the shift / noise draws stay on the reference's RNG stream).
+augmented batch costs no extra pass over HBM.  The reference's ``pitch_shift`` / ``speed_change`` run libsox on one
+clip; here their batch form is ``sir_wave_perturb`` (``HipFeaturizer.perturb``: WSOLA tempo and a tempo + resample
+pitch on the GPU), fed by ``draw_batch_params_full`` and used by ``scripts.train`` with
+``pitch_speed_augment: true``.  The per-clip host forms still raise, and ``apply_augmentation`` skips them (drawing
+their random numbers, so the shift / noise draws stay on the reference's RNG stream): this project has no CPU path.
 
 Host forms with the reference's signatures (``time_shift``, ``add_noise``, ``apply_augmentation``,
 ``apply_spec_augmentation``) are kept for API compatibility; the training path uses ``draw_batch_params`` /
@@ -16,6 +18,7 @@ Host forms with the reference's signatures (``time_shift``, ``add_noise``, ``app
 import logging
 import random
 
+import numpy as np
 import torch
 
 logger = logging.getLogger(__name__)
@@ -46,6 +49,40 @@ def draw_batch_params(lengths, augment_prob=0.7, rng=random):
         shifts.append(s)
         sigmas.append(g)
     return torch.tensor(shifts, dtype=torch.int32), torch.tensor(sigmas, dtype=torch.float32)
+
+
+def draw_batch_params_full(lengths, augment_prob=0.7, rng=random):
+    """Per-utterance (shift, pitch_cents, tempo, sigma) with the reference's gating and draw order (augment.py:119-133):
+    the whole augmentation with probability ``augment_prob``, then each of time shift (:18), pitch shift (:43, U(-2, 2)
+    semitones * 100 = cents), speed change (:68, U(0.85, 1.15)) and noise (:93) with probability 0.5.  An effect not
+    drawn is 0 shift / 0 cents / tempo 1 / sigma 0 -- the identity of ``sir_wave_perturb`` and the feature kernel."""
+    shifts, cents, tempos, sigmas = [], [], [], []
+    for n in lengths:
+        s, c, t, g = 0, 0.0, 1.0, 0.0
+        if rng.random() < augment_prob:
+            if rng.random() < 0.5:
+                s = draw_time_shift(int(n), rng=rng)
+            if rng.random() < 0.5:
+                c = float(rng.uniform(-2.0, 2.0)) * 100.0
+            if rng.random() < 0.5:
+                t = float(rng.uniform(0.85, 1.15))
+            if rng.random() < 0.5:
+                g = draw_noise_level(rng=rng)
+        shifts.append(s)
+        cents.append(c)
+        tempos.append(t)
+        sigmas.append(g)
+    return (torch.tensor(shifts, dtype=torch.int32), torch.tensor(cents, dtype=torch.float32),
+            torch.tensor(tempos, dtype=torch.float32), torch.tensor(sigmas, dtype=torch.float32))
+
+
+def perturbed_out_len(length, tempo):
+    """Samples of a clip of ``length`` samples after ``sir_wave_perturb`` with this tempo (as ``sir_perturb_out_len``):
+    int(length / f + 0.5) in double with f rounded to float32 as the kernel sees it; pitch keeps the length."""
+    f = float(np.float32(tempo))
+    if f == 1.0:
+        return int(length)
+    return int(int(length) / f + 0.5)
 
 
 def draw_spec_masks(frames, augment_prob=0.5, time_mask_param=20, freq_mask_param=10, n_mels=64, rng=random):
@@ -93,13 +130,17 @@ def add_noise(waveform, noise_level_range=(0.001, 0.01)):
 
 
 def pitch_shift(waveform, sample_rate, pitch_factor_range=(-2.0, 2.0)):
-    """augment.py:30-54 runs libsox's ``pitch`` effect; sox is not part of this build."""
-    raise NotImplementedError("pitch_shift needs torchaudio.sox_effects (libsox); it is out of scope of the MI355X build")
+    """augment.py:30-54 runs libsox's ``pitch`` effect on one clip; there is no host form here.  The batch form runs on
+    the GPU: ``HipFeaturizer.perturb(wave, lengths, pitch_cents=...)`` (``sir_wave_perturb``)."""
+    raise NotImplementedError("pitch_shift needs torchaudio.sox_effects (libsox) on the host; the GPU batch form is "
+                              "HipFeaturizer.perturb(..., pitch_cents=...)")
 
 
 def speed_change(waveform, sample_rate, speed_factor_range=(0.85, 1.15)):
-    """augment.py:56-80 runs libsox's ``tempo`` effect; sox is not part of this build."""
-    raise NotImplementedError("speed_change needs torchaudio.sox_effects (libsox); it is out of scope of the MI355X build")
+    """augment.py:56-80 runs libsox's ``tempo`` effect on one clip; there is no host form here.  The batch form runs on
+    the GPU: ``HipFeaturizer.perturb(wave, lengths, tempo=...)`` (``sir_wave_perturb``)."""
+    raise NotImplementedError("speed_change needs torchaudio.sox_effects (libsox) on the host; the GPU batch form is "
+                              "HipFeaturizer.perturb(..., tempo=...)")
 
 
 def _skip_sox(name, lo, hi):

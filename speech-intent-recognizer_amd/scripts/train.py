@@ -143,7 +143,8 @@ def train_epoch_waveforms(model, wave_loader, optimizer, criterion, device, t_pa
     ``WaveformStore.epoch_batches`` yields), so that augmentation parameters can be drawn without a device sync.
     ``augment(wave_batch_index, batch_size, host_lengths | None) -> dict`` may return the featurizer's on-the-fly
     augmentation arguments (``shift``, ``noise_sigma``, ``noise_seed``, ``time_mask``, ``freq_mask``: scripts/augment.py,
-    dataset.py:160-176) for that batch.  Returns the mean of the per-step losses."""
+    dataset.py:160-176) for that batch, and ``pitch_cents`` / ``tempo`` (``sir_wave_perturb`` ahead of the feature kernel).
+    Returns the mean of the per-step losses."""
     from sir_amd import ops
     from sir_amd.pipeline import FeaturePrefetcher
     model.train()
@@ -186,11 +187,15 @@ def make_waveform_augment(config, seed=0, epoch=0, rng=None):
     """The ``augment`` callable of ``train_epoch_waveforms`` for the YAML keys of scripts/train.py: time shift + noise
     (scripts/augment.py:98-135 gating, ``waveform_augment_prob``, default 0.7 as augment.py:98) when
     ``waveform_augment`` is on, and the dataset's SpecAugment (dataset.py:105-106, :160-176, ``augment_prob``) always --
-    the cached-feature route applies that one in ``FSCIntentDataset.__getitem__``, the fused route has no dataset."""
+    the cached-feature route applies that one in ``FSCIntentDataset.__getitem__``, the fused route has no dataset.
+    ``pitch_speed_augment`` (implies ``waveform_augment``) draws all four waveform effects of augment.py:119-133 --
+    shift, pitch, speed, noise -- and adds ``pitch_cents`` / ``tempo``; the time masks are then drawn against the frame
+    counts of the PERTURBED clips (known on the host from the tempo, no device sync)."""
     import random
     from sir_amd.scripts import augment as aug
     rng = rng or random.Random((int(seed) << 20) ^ int(epoch))
-    wave_aug = bool(config.get("waveform_augment", False))
+    pitch_speed = bool(config.get("pitch_speed_augment", False))
+    wave_aug = bool(config.get("waveform_augment", False)) or pitch_speed
     wave_prob = float(config.get("waveform_augment_prob", 0.7))
     spec_prob = float(config.get("augment_prob", 0.5))
 
@@ -198,11 +203,17 @@ def make_waveform_augment(config, seed=0, epoch=0, rng=None):
         if host_lengths is None:
             raise ValueError("waveform augmentation needs the clip lengths on the host (WaveformStore yields them)")
         kw = {}
-        if wave_aug:
+        frame_lengths = host_lengths
+        if pitch_speed:
+            shift, cents, tempo, sigma = aug.draw_batch_params_full(host_lengths, wave_prob, rng)
+            kw.update(shift=shift, pitch_cents=cents, tempo=tempo, noise_sigma=sigma,
+                      noise_seed=(int(seed) << 40) ^ (int(epoch) << 24) ^ int(idx))
+            frame_lengths = [aug.perturbed_out_len(n, f) for n, f in zip(host_lengths, tempo.tolist())]
+        elif wave_aug:
             shift, sigma = aug.draw_batch_params(host_lengths, wave_prob, rng)
             kw.update(shift=shift, noise_sigma=sigma, noise_seed=(int(seed) << 40) ^ (int(epoch) << 24) ^ int(idx))
         if spec_prob > 0.0:
-            tm, fm = aug.draw_spec_masks([1 + n // 512 for n in host_lengths], spec_prob, rng=rng)
+            tm, fm = aug.draw_spec_masks([1 + n // 512 for n in frame_lengths], spec_prob, rng=rng)
             kw.update(time_mask=tm, freq_mask=fm)
         return kw
     return fn
@@ -266,7 +277,9 @@ def train(args, config):
     # assembles each batch with one gather launch instead of DataLoader workers + a host -> device copy per step -- same files,
     # same item semantics; false = the reference's DataLoader route, which at batch 256 delivers a fraction of what the training
     # step consumes (bench.py `dropin_epoch`).
-    wave_aug = bool(config.get("waveform_augment", False))
+    # `pitch_speed_augment: true` (implies waveform_augment) adds the pitch and speed effects of scripts/augment.py on the GPU
+    # (sir_wave_perturb ahead of the feature kernel).
+    wave_aug = bool(config.get("waveform_augment", False)) or bool(config.get("pitch_speed_augment", False))
     fused = bool(config.get("fused_features", False)) or wave_aug
     hbm_cache = bool(config.get("hbm_feature_cache", True)) and not fused
     train_store = None

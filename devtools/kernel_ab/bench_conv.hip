@@ -13,10 +13,25 @@
 #include "../../speech-intent-recognizer_amd/csrc/bf16x6_kernels.h"
 #include "legacy_kernels.h"
 #include "../../speech-intent-recognizer_amd/csrc/conv_wino_bf16x6_kernel.h"
-#include "../../speech-intent-recognizer_amd/csrc/conv_wino2_bf16x6_kernel.h"
+#include "../../speech-intent-recognizer_amd/csrc/conv_wino2_f16x3_kernel.h"
 #include "conv_direct_f16x3_kernel.h"
 
 #define CK_(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %s:%d\n", hipGetErrorString(e), __FILE__, __LINE__); exit(1); } } while (0)
+
+// the library keeps the Winograd kernel's geometry in its conv plan and opts in to the dynamic LDS through its handle; the harness
+// does both here, per instantiation (`attr_done`)
+template <int CIN, int COUT, int OUT_MODE, int DBG = 0, int PRIO = 3>
+static hipError_t launch_conv_wino2(hipStream_t st, bool* attr_done, const float* x, const unsigned short* wpb, const float* scale, const float* shift,
+                                    float* out, int B, int H, int W, float2* stats, const float* zeros) {
+    Wino2Geo g;
+    if (!wino2_geo(B, H, W, CIN > COUT ? CIN : COUT, &g)) return hipErrorInvalidValue;
+    if (!*attr_done) {
+        hipError_t e = hipFuncSetAttribute((const void*)conv3x3_wino2_f16x3_kernel<CIN, COUT, OUT_MODE, DBG, PRIO>, hipFuncAttributeMaxDynamicSharedMemorySize, W2_LDS_BYTES);
+        if (e != hipSuccess) return e;
+        *attr_done = true;
+    }
+    return launch_conv_wino2<CIN, COUT, OUT_MODE, DBG, PRIO>(st, g, x, wpb, scale, shift, out, stats, zeros);
+}
 
 template <typename F>
 static float time_us(hipStream_t st, int reps, F launch) {
@@ -260,7 +275,7 @@ static void load_loop(double seconds) {
     }
 }
 
-// Second-generation Winograd kernel (conv_wino2_bf16x6_kernel.h) against the direct kernel: same input, same weights.
+// Second-generation Winograd kernel (conv_wino2_f16x3_kernel.h) against the direct kernel: same input, same weights.
 //   MODE 0: pooled NHWC, 1: pooled GRU layout + f16x2 planes, 2: raw + statistics, 3: raw (data gradient: DGRAD weights)
 template <int CIN, int COUT, int PR, int PC, int MODE, bool DGRAD, int MINB>
 static void run_wino2(const char* name, int B, int H, int W, int reps = 60) {

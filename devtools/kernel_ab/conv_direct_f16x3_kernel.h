@@ -1,5 +1,5 @@
 // 3x3 convolution as a DIRECT implicit GEMM on the fp16 matrix cores in the f16x3 arithmetic (f16_split.h): M = pixels in 8x4 patches,
-// N = output channels, K = (tap, ci).  Companion of the Winograd kernels (conv_wino2_bf16x6_kernel.h): those do 4/9 of the matrix work
+// N = output channels, K = (tap, ci).  Companion of the Winograd kernels (conv_wino2_f16x3_kernel.h): those do 4/9 of the matrix work
 // but hand the two-way split SIXTEEN transformed values per 2x2 output tile and channel and are bound by that vector work
 // (DESIGN.md "What the profile says to do next"); here every input value is split ONCE while its tile is staged, the matrix pipe does
 // 2.25 x the products, and with f16x3 (3 MFMAs per product instead of bf16x6's 6) that is the cheaper side on this chip.
@@ -22,7 +22,7 @@
 // following GEMM's operand when `stats` is given); 2: raw output + per-workgroup channel sums / sums of squares in `stats`.
 #pragma once
 #include "../../speech-intent-recognizer_amd/csrc/bf16x6_kernels.h"
-#include "../../speech-intent-recognizer_amd/csrc/conv_wino_bf16x6_kernel.h"   // split_w_f16x3
+#include "../../speech-intent-recognizer_amd/csrc/conv_wino2_f16x3_kernel.h"   // split_w_f16x3
 
 constexpr size_t conv_d16_lds_bytes(int PR, int PC) { return (size_t)2 * 2 * (8 * PR + 2) * conv_ns_row_bytes(PC); }
 

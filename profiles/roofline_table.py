@@ -39,9 +39,13 @@ Y = B * S * 512 * 4
 ROWS = [
     # ---- training step ----
     ("conv3x3_wino2_bf16x6_kernel<32, 64, 2", "train conv2 fwd (Winograd 2nd gen, raw out + BN partials)", "train", "mfma6", F["train_conv2_fwd"] * B, A1 + Z2),
+    ("conv3x3_wino2_f16x3_kernel<32, 64, 2", "train conv2 fwd (Winograd 2nd gen, raw out + BN partials)", "train", "mfma6", F["train_conv2_fwd"] * B, A1 + Z2),
     ("conv3x3_wino2_bf16x6_kernel<64, 128, 2", "train conv3 fwd (Winograd 2nd gen, raw out + BN partials)", "train", "mfma6", F["train_conv3_fwd"] * B, A2 + Z3),
+    ("conv3x3_wino2_f16x3_kernel<64, 128, 2", "train conv3 fwd (Winograd 2nd gen, raw out + BN partials)", "train", "mfma6", F["train_conv3_fwd"] * B, A2 + Z3),
     ("conv3x3_wino2_bf16x6_kernel<128, 64, 3", "bwd conv3 dgrad (Winograd 2nd gen)", "train", "mfma6", F["bwd_conv3_dgrad"] * B, Z3 + A2),
+    ("conv3x3_wino2_f16x3_kernel<128, 64, 3", "bwd conv3 dgrad (Winograd 2nd gen)", "train", "mfma6", F["bwd_conv3_dgrad"] * B, Z3 + A2),
     ("conv3x3_wino2_bf16x6_kernel<64, 32, 3", "bwd conv2 dgrad (Winograd 2nd gen)", "train", "mfma6", F["bwd_conv2_dgrad"] * B, Z2 + A1),
+    ("conv3x3_wino2_f16x3_kernel<64, 32, 3", "bwd conv2 dgrad (Winograd 2nd gen)", "train", "mfma6", F["bwd_conv2_dgrad"] * B, Z2 + A1),
     ("conv3x3_wino_bf16x6_kernel<32, 64, 2", "train conv2 fwd (Winograd, raw out + BN partials)", "train", "mfma6", F["train_conv2_fwd"] * B, A1 + Z2),
     ("conv3x3_wino_bf16x6_kernel<64, 128, 2", "train conv3 fwd (Winograd, raw out + BN partials)", "train", "mfma6", F["train_conv3_fwd"] * B, A2 + Z3),
     ("conv3x3_bf16x6_ns_kernel<64, 128, 2, 2, 2", "train conv3 fwd (direct, raw out + BN partials)", "train", "mfma6", F["train_conv3_fwd"] * B, A2 + Z3),
@@ -50,7 +54,9 @@ ROWS = [
     ("conv3x3_bf16x6_ns_kernel<64, 32", "bwd conv2 dgrad (direct)", "train", "mfma6", F["bwd_conv2_dgrad"] * B, Z2 + A1),
     ("conv3x3_bf16x6_ns_kernel<128, 64", "bwd conv3 dgrad (direct)", "train", "mfma6", F["bwd_conv3_dgrad"] * B, Z3 + A2),
     ("conv_wgrad_wino_bf16x6_kernel<32, 64", "bwd conv2 wgrad (Winograd)", "train", "mfma6", F["bwd_conv2_wgrad"] * B, A1 + Z2),
+    ("conv_wgrad_wino_f16x3_kernel<32, 64", "bwd conv2 wgrad (Winograd)", "train", "mfma6", F["bwd_conv2_wgrad"] * B, A1 + Z2),
     ("conv_wgrad_wino_bf16x6_kernel<64, 128", "bwd conv3 wgrad (Winograd)", "train", "mfma6", F["bwd_conv3_wgrad"] * B, A2 + Z3),
+    ("conv_wgrad_wino_f16x3_kernel<64, 128", "bwd conv3 wgrad (Winograd)", "train", "mfma6", F["bwd_conv3_wgrad"] * B, A2 + Z3),
     ("conv_wgrad_bf16x6_kernel<32, 64>", "bwd conv2 wgrad", "train", "mfma6", F["bwd_conv2_wgrad"] * B, A1 + Z2),
     ("conv_wgrad_bf16x6_kernel<64, 128>", "bwd conv3 wgrad", "train", "mfma6", F["bwd_conv3_wgrad"] * B, A2 + Z3),
     ("gru_quad_kernel<true", "train GRU recurrence (l0, l1)", "train", "mfma6", F["train_gru_l0"] * B, GI + Y + B * S * 2048 * 4),
@@ -60,8 +66,13 @@ ROWS = [
     ("gru_bwd_quad_kernel", "BPTT recurrence, MFMA cluster (l1, l0)", "train", "mfma6", F["bwd_gru_l0"] * B, B * S * (2048 + 512 + 512 + 1536 + 1536) * 4),
     ("gemm_tn2_bf16x6_kernel<true", "GRU dW = dG^T X (l1, l0: mean)", "train", "mfma6", (F["bwd_gru_dw_l0"] + F["bwd_gru_dw_l1"]) * B // 2,
      (2 * B * S * 1536 * 4 + B * S * (1024 + 512) * 4 // 2 + B * S * 512 * 4)),
+    ("gemm_tn2_f16x3_kernel<true", "GRU dW = dG^T X (l1, l0: mean)", "train", "mfma6", (F["bwd_gru_dw_l0"] + F["bwd_gru_dw_l1"]) * B // 2,
+     (2 * B * S * 1536 * 4 + B * S * (1024 + 512) * 4 // 2 + B * S * 512 * 4)),
     ("gemm_tn2_bf16x6_kernel<false, 0, 64", "GRU dX l1", "train", "mfma6", F["bwd_gru_dx_l1"] * B, GI + Y),
+    ("gemm_tn2_f16x3_kernel<false, 0, 64", "GRU dX l1", "train", "mfma6", F["bwd_gru_dx_l1"] * B, GI + Y),
     ("gemm_tn2_bf16x6_kernel<false, 0, 128", "GRU dX (l0; l1 as two K halves: mean of the two launches)", "train", "mfma6",
+     (F["bwd_gru_dx_l0"] + F["bwd_gru_dx_l1"]) * B // 2, GI + (X0 + Y) // 2),
+    ("gemm_tn2_f16x3_kernel<false, 0, 128", "GRU dX (l0; l1 as two K halves: mean of the two launches)", "train", "mfma6",
      (F["bwd_gru_dx_l0"] + F["bwd_gru_dx_l1"]) * B // 2, GI + (X0 + Y) // 2),
     ("gemm_tn_bf16x6_kernel<true", "GRU dW = dG^T X (l1, l0: mean)", "train", "mfma6", (F["bwd_gru_dw_l0"] + F["bwd_gru_dw_l1"]) * B // 2,
      (2 * B * S * 1536 * 4 + B * S * (1024 + 512) * 4 // 2 + B * S * 512 * 4)),
@@ -80,7 +91,9 @@ ROWS = [
      (X0 + Y) // 2 + GI),
     # ---- inference ----
     ("conv3x3_wino2_bf16x6_kernel<32, 64, 0", "conv2 + BN + ReLU + pool (Winograd 2nd gen)", "infer", "mfma6", F["conv2_mfma_bn_relu_pool"] * B, A1 + A2),
+    ("conv3x3_wino2_f16x3_kernel<32, 64, 0", "conv2 + BN + ReLU + pool (Winograd 2nd gen)", "infer", "mfma6", F["conv2_mfma_bn_relu_pool"] * B, A1 + A2),
     ("conv3x3_wino2_bf16x6_kernel<64, 128, 1", "conv3 + BN + ReLU + pool (Winograd 2nd gen)", "infer", "mfma6", F["conv3_mfma_bn_relu_pool"] * B, A2 + X0 + X0 * 3 // 2),
+    ("conv3x3_wino2_f16x3_kernel<64, 128, 1", "conv3 + BN + ReLU + pool (Winograd 2nd gen)", "infer", "mfma6", F["conv3_mfma_bn_relu_pool"] * B, A2 + X0 + X0 * 3 // 2),
     ("feat_utt_kernel", "feature kernel (waveform -> normalised log-mel)", "infer", "hbm", None, bench.FEATURE_BYTES_PER_UTT * B),
     ("conv1_conv2_fused", "conv1+conv2 fused (Winograd)", "infer", "mfma6", (F["conv1_bn_relu_pool"] + F["conv2_mfma_bn_relu_pool"]) * B, FEAT + A2),
     ("conv1_mfma_bn_relu_pool_kernel", "conv1 + BN + ReLU + pool (f32 MFMA)", "infer", "hbm", None, FEAT + A1),

@@ -1,6 +1,7 @@
 // C ABI entry points of libsir_hip.so (see include/sir_hip.h): handle management, error state,
 // argument validation.  Kernels live in features.hip / model_*.hip.
 #include "sir_internal.h"
+#include "model_shape.h"
 
 #include <math.h>
 #include <stdarg.h>
@@ -57,8 +58,6 @@ extern "C" int sir_create(const sir_feature_config* cfg, sir_handle** out) {
     h->status = nullptr;
     h->cluster_done = nullptr; h->cluster_stream = nullptr; h->cluster_pending = false;
     h->cluster_seen = false; h->cluster_multi = false; h->cluster_run = 0;
-    h->attr_gemm_v3 = h->attr_gemm_gather = h->attr_gru_quad = h->attr_gru_bwd_quad = h->attr_tn = h->attr_wgrad = false;
-    for (auto& a : h->attr_wino2) a = false;
     h->zero_page = nullptr; h->num_cus = 256;
     for (auto& x : h->xbufs) { x.st = nullptr; x.p = nullptr; x.kind = 0; x.cap = 0; x.bytes = 0; x.epoch = 0; x.used = 0; }
     h->xbuf_clock = 0;
@@ -127,7 +126,6 @@ extern "C" int sir_create(const sir_feature_config* cfg, sir_handle** out) {
     }
     h->mel_nnz = (int)melw.size();
     melw.resize((melw.size() + 3) / 4 * 4 + 4, 0.0f);
-    h->feat_attr_set = false;
 
     int rc = upload(&h->tw512, tw512);
     if (rc == SIR_OK) rc = upload(&h->tw1024, tw1024);

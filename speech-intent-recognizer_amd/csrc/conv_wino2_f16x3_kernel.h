@@ -1,13 +1,14 @@
-// conv 3x3 (pad 1) as Winograd F(2x2, 3x3) on the bf16 matrix cores with bf16x6 products (fp32 accuracy), second
-// generation: ONE persistent 768-thread workgroup per CU with SPECIALISED waves -- 4 producers (input transform: VALU + LDS)
-// and 8 consumers (matrix cores) -- so that on every SIMD one producer wave transforms the next 16-channel chunk while two
-// consumer waves multiply the current one.  The first generation (conv_wino_bf16x6_kernel.h: 4 waves, loads -> transform ->
-// barrier -> MFMA -> barrier per chunk, 3 workgroups per CU) ran those phases back to back and its time was their SUM (timing
-// knock-outs on MI355X at batch 256, conv2: patch loads 34 us, transform 29, weights 16, MFMA 18, stores 7, skeleton 43 of 138).
+// conv 3x3 (pad 1) as Winograd F(2x2, 3x3) on the fp16 matrix cores with f16x3 products (two-way split of f16_split.h, fp32
+// accuracy for inputs inside fp16's range): the default kernel of conv2 / conv3 forward and of both data gradients (the same
+// kernel on the transposed / flipped taps).  Shapes it does not cover run on the bf16x6 fallbacks (conv_wino_bf16x6_kernel.h,
+// bf16x6_kernels.h).
 //
 //   Y = A^T [ sum_cin (G g G^T) . (B^T d B) ] A     d: 4x4 input patch, g: 3x3 taps, Y: 2x2 outputs (= one pooling window)
 //   per frequency f = 4 i + j of the transform one GEMM  M_f[tile][cout] = sum_cin V_f[tile][cin] U_f[cin][cout].
 //
+// ONE persistent 768-thread workgroup per CU with SPECIALISED waves -- 4 producers (input transform: VALU + LDS) and 8 consumers
+// (matrix cores) -- so that on every SIMD one producer wave transforms the next 16-channel chunk while two consumer waves multiply
+// the current one.
 // Task = 32 tiles (8 tile rows x 4 tile columns; columns are numbered across the whole batch, g = image * TW + tx, so a task
 // may straddle two images and no column is wasted) x 64 output channels (layers with 128: two tasks per block); a workgroup
 // walks its tasks chunk by chunk, step s: producers chunk s, consumers chunk s - 1, ONE barrier per step.
@@ -18,32 +19,31 @@
 //                 ((lr >> 1) & 1), its four 16-byte channel groups XOR-swizzled by ((lr >> 2) & 1) << 1: the ds_read_b128
 //                 lane groups (8 tiles x 2 channel groups) hit 16 different slots of the 256-byte bank line for every patch
 //                 offset (brute-forced: devtools/kernel_ab/wino2_lds_layout.py) while a DMA piece still reads whole 64-byte
-//                 pixels.  B^T d B, the three-way bf16 split and 24 ds_write_b64 into V[step & 1] follow.  The producers' LDS
-//                 accesses are inline asm and the barrier is a bare s_barrier behind s_waitcnt lgkmcnt(0): hipcc orders every LDS
-//                 access it can see behind ALL outstanding LDS-DMA (vmcnt(0)) and __syncthreads() drains vmcnt as well.
+//                 pixels.  B^T d B, the two-way fp16 split (Vh, Vl' = residual * 2^11) and the ds_write_b64 into V[step & 1]
+//                 follow.  The producers' LDS accesses are inline asm and the barrier is a bare s_barrier behind
+//                 s_waitcnt lgkmcnt(0): hipcc orders every LDS access it can see behind ALL outstanding LDS-DMA (vmcnt(0)) and
+//                 __syncthreads() drains vmcnt as well.
 //   consumers     wave (i, n): transform row i (4 frequencies), channel slice 32 n..: 4 accumulators that live across all chunks
-//                 (no per-chunk folding); V fragments from LDS (ds_read_b128, 1 KB runs), U fragments (3 x 16 B per lane) streamed
-//                 from L2 one chunk ahead, two frequencies at a time and fenced (left alone hipcc sinks all twelve loads to the
-//                 end of the step and the next step starts with an L2 round trip).
+//                 (no per-chunk folding); V fragments from LDS (ds_read_b128, 1 KB runs), U fragments (2 x 16 B per lane) streamed
+//                 from L2 one chunk ahead, two frequencies at a time and fenced (left alone hipcc sinks the loads to the end of
+//                 the step and the next step starts with an L2 round trip).  THREE products per frequency and 16-deep step --
+//                 Vl' Uh, Vh Ul', Vh (Uh 2^11) -- into one accumulator that is 2^11 too large and scaled back in the epilogue;
+//                 Uh 2^11 is formed in registers, so the U stream that bounds the kernel carries two planes.
 //   epilogue      column inverse transform in registers, row transform across the four consumer waves of a channel slice through
-//                 the V buffer the task's last chunk just left (each wave finishes one tile column: it receives 3 x 2 KB; two
-//                 extra barriers per task), then BN + ReLU + 2x2 max (the 2x2 outputs of a tile ARE the pooling window) or raw
+//                 a DEDICATED exchange area (each wave finishes one tile column: it receives 3 x 2 KB): a consumer writes its
+//                 pieces right behind its last MFMAs, the step's one barrier publishes them, and the producers are transforming
+//                 the next chunk meanwhile.  Then BN + ReLU + 2x2 max (the 2x2 outputs of a tile ARE the pooling window) or raw
 //                 outputs (+ channel statistics, accumulated in registers over the workgroup's tasks: 4 blocks per workgroup).
-// The kernel now runs only in the f16x3 form described further down (two planes instead of three, a dedicated exchange area in
-// place of the epilogue's borrowed V buffer); the bf16x6 form it grew from is what the paragraphs above and the numbers below measure.
-// Weights: prep_conv_w_wino_bf16x3 layout wpb[plane][chunk * 16 + f][cout][16 ch] with column j = 3 negated (shared with the
-// first generation); data gradients use the same kernel on the transposed / flipped taps (prep_conv_wT_wino_bf16x3).
-// Measured (devtools/kernel_ab/bench_conv.hip `wino2`, batch 256, four rotating inputs, one box): conv2 143 us against 184 direct
-// (first generation ~0.90 of direct), conv3 131 / 160, conv3 data gradient 124 / 183; outputs within 1.4e-5 of the direct kernel
-// on |out| <= 8.6 for every mode, ragged shapes included.  Timing knock-outs say what bounds it now: the 96 KB of U fragments a
-// step pulls through the CU's vector-memory path (a fragment serves ONE 32-tile accumulator: 64-tile tasks need 128
-// accumulator registers per consumer, more than the 168 of a three-wave SIMD) and the task epilogue (~2 us of exchange, output
-// arithmetic and stores per task with the producers parked at its barriers); transform and MFMAs hide behind each other.
-// Earlier structures of this kernel (two wave groups alternating roles with 64- and 32-tile tasks, 4 producers + 4 two-row
-// consumers) were slower than the first generation -- spilled accumulators, weights one frequency ahead of an L2 round trip,
-// LDS reads serialised behind DMA waits; their numbers are in DESIGN.md section 4.
+// Weights: prep_conv_w_wino_f16x3 (below), wpb[plane][chunk * 16 + f][cout][16 ch], two fp16 planes, column j = 3 negated; the data
+// gradients take prep_conv_wT_wino_f16x3.  Needs inputs inside fp16's range (activations: yes; gradients only under the loss scale
+// of the backward).
+// What bounds it (timing knock-outs and stamps, profiles/r04/bench_conv_wino2_f16x3.txt): the U fragments a step pulls through the
+// CU's vector-memory path (a fragment serves ONE 32-tile accumulator: 64-tile tasks need 128 accumulator registers per consumer,
+// more than a three-wave SIMD has) and the instruction count of the producers' step; the part runs at its power cap, the matrix
+// products are the energy.  Numbers and the structures that came before: DESIGN.md section 4.
 #pragma once
-#include "conv_wino_bf16x6_kernel.h"
+#include "conv_wino_bf16x6_kernel.h"   // (bf16x6_kernels.h / f16_split.h: vector types and the split)
+#include "wino2_geo.h"
 
 constexpr int W2_RS = 11;                                   // pixel positions per raw row (10 + skew)
 constexpr int W2_NPOS = 18 * W2_RS;
@@ -58,20 +58,7 @@ constexpr int W2_LDS_BYTES = 2 * W2_V_BYTES + W2_NRAW * W2_RAW_BYTES + W2_XCH_BY
 constexpr int W2_THREADS = 768;                             // 4 producer waves + 8 consumer waves
 constexpr int W2_PPW = (W2_RAW_PIECES + 3) / 4;             // DMA pieces per wave of group B
 
-// Exact unsigned division by a launch-time constant (the round-up method: q = (t + ((n - t) >> 1)) >> sh with t = mulhi(m, n); a shift for
-// powers of two).  A hardware-free 32-bit division costs ~25 vector instructions on this ISA; the producers' per-task address set-up held ten
-// of them -- ~1000 of the ~8000 cycles of a two-chunk task on the kernel's critical waves (fine-grained stamps in
-// profiles/r04/bench_conv_wino2_f16x3.txt).
-struct W2Div { unsigned m; int sh; int pow2; unsigned d; };
-static inline W2Div w2_div_make(unsigned d) {
-    W2Div r{0u, 0, 0, d};
-    if ((d & (d - 1)) == 0) { r.pow2 = 1; while ((1u << r.sh) < d) ++r.sh; return r; }
-    int l = 0;
-    while ((1ull << l) < d) ++l;                             // ceil(log2 d)
-    r.m = (unsigned)((((1ull << l) - d) << 32) / d + 1);
-    r.sh = l - 1;
-    return r;
-}
+// (W2Div, w2_div_make: wino2_geo.h)
 __device__ __forceinline__ int w2_div(int n, const W2Div& d) {
     const unsigned un = (unsigned)n;
     if (d.pow2) return (int)(un >> d.sh);
@@ -79,33 +66,67 @@ __device__ __forceinline__ int w2_div(int n, const W2Div& d) {
     return (int)((t + ((un - t) >> 1)) >> d.sh);
 }
 
-struct Wino2Geo {
-    int H, W;            // input = output map (pixels)
-    int TW;              // tile columns per image = ceil(W / 2)
-    int NG;              // tile columns of the batch = B * TW
-    int RBN;             // 8-row tile blocks per image = (H / 2) / 8
-    int NS;              // spatial tasks = RBN * ceil(NG / 4)
-    int Hp, Wp;          // pooled map (OUT_MODE 0 / 1)
-    int B;
-    W2Div dTW, d2TW, dRBN;   // divisions by TW, 2 TW, RBN (all operands are non-negative)
-    // nullptr: tile columns are numbered across the whole batch (above).  Otherwise a COMPACTED column list in device memory
-    // (inference pad skip, model_infer.hip): ctab[0] = number of task columns n, ctab[1 + k] = first tile column (img * TW + tx0,
-    // tx0 a multiple of 4) of task column k, k < n; NS = RBN * n.  A task then holds 4 tile columns of ONE image, its halo pixels
-    // come from that image (or the zero page outside it), and tile columns past the image's TW are neither computed nor stored.
-    const int* ctab;
-};
-// false: shape outside what the kernel covers (whole 8-tile-row blocks, 32-bit element offsets) -- the caller keeps the
-// first-generation / direct kernel for it
-static inline bool wino2_geo(int B, int H, int W, int cmax, Wino2Geo* g) {
-    g->B = B; g->H = H; g->W = W; g->TW = (W + 1) / 2; g->NG = B * g->TW; g->RBN = H / 16; g->ctab = nullptr;
-    g->NS = g->RBN * ((g->NG + 3) / 4); g->Hp = H / 2; g->Wp = W / 2;
-    g->dTW = w2_div_make((unsigned)g->TW); g->d2TW = w2_div_make(2u * (unsigned)g->TW); g->dRBN = w2_div_make((unsigned)(g->RBN > 0 ? g->RBN : 1));
-    return H % 16 == 0 && W >= 1 && B >= 1 && (size_t)B * H * W * cmax < ((size_t)1 << 31) && (size_t)g->NG * 2 < ((size_t)1 << 30);
+// ---- weights: U = G g G^T (transform as in conv_wino_bf16x6_kernel.h) as f16x3 planes (f16_split.h) ------------------------------
+// TWO fp16 planes per value, same layout: plane 0 = Uh = fp16(U), plane 1 = Ul' = fp16((U - Uh) * 2^11).  With the activations
+// split into (Vh, Vl') the kernel accumulates Vl' Uh + Vh Ul' + Vh (Uh 2^11) = 2^11 V U into ONE accumulator (three MFMAs, no
+// second accumulator: the consumers' registers are full) and the epilogue scales by 2^-11; Uh 2^11 is formed in registers by the
+// consumer (four v_pk_mul_f16 per fragment: its VALU is idle, and the U stream is what bounds the kernel -- a third plane would be
+// a third more of it).  Uh * 2^11 is exact for |U| < 32; larger transformed weights are clamped and flagged in the handle's status
+// word (bit 3: SIR_EINVAL at the next sir_check_status) -- conv weights of this model are O(0.1).
+__device__ __forceinline__ void split_w_f16x3(float u, unsigned short& p0, unsigned short& p1, unsigned int* status) {
+    constexpr float LIM = 31.984375f;                       // 65504 / 2048
+    if (status && !(fabsf(u) <= LIM)) __hip_atomic_fetch_or(status, 8u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    u = __builtin_fminf(__builtin_fmaxf(u, -LIM), LIM);
+    const _Float16 hi = (_Float16)u;
+    const _Float16 lo = (_Float16)((u - (float)hi) * H3_LO_SCALE);
+    p0 = __builtin_bit_cast(unsigned short, hi);
+    p1 = __builtin_bit_cast(unsigned short, lo);
 }
-// statistics blocks of OUT_MODE 2: one per (workgroup, transform-row wave); `max_wg` as passed to launch_conv_wino2
-static inline size_t wino2_stat_blocks(int B, int H, int W, int max_wg) {
-    const size_t ns = (size_t)(H / 16) * (((size_t)B * ((W + 1) / 2) + 3) / 4);
-    return (ns < (size_t)max_wg ? ns : (size_t)max_wg) * 4;
+__device__ __forceinline__ void prep_conv_w_wino_f16x3_elem(const float* __restrict__ w, unsigned short* __restrict__ wpb, int cin, int cout, int idx,
+                                                            unsigned int* status) {
+    const int total = cin * 16 * cout;
+    if (idx >= total) return;
+    const int e = idx & 15, co = (idx >> 4) % cout, g = (idx >> 4) / cout;
+    const int ci = (g / 16) * 16 + e, f = g % 16, i = f >> 2, j = f & 3;
+    const float* gk = w + ((size_t)co * cin + ci) * 9;
+    const float Gm[4][3] = {{1.f, 0.f, 0.f}, {.5f, .5f, .5f}, {.5f, -.5f, .5f}, {0.f, 0.f, 1.f}};
+    float u = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        float t = 0.0f;
+#pragma unroll
+        for (int l = 0; l < 3; ++l) t = fmaf(gk[k * 3 + l], Gm[j][l], t);
+        u = fmaf(Gm[i][k], t, u);
+    }
+    if (j == 3) u = -u;
+    split_w_f16x3(u, wpb[idx], wpb[(size_t)total + idx], status);
+}
+static __global__ void prep_conv_w_wino_f16x3_kernel(const float* __restrict__ w, unsigned short* __restrict__ wpb, int cin, int cout,
+                                                     unsigned int* status) {
+    prep_conv_w_wino_f16x3_elem(w, wpb, cin, cout, blockIdx.x * blockDim.x + threadIdx.x, status);
+}
+__device__ __forceinline__ void prep_conv_wT_wino_f16x3_elem(const float* __restrict__ w, unsigned short* __restrict__ wpb, int cin_f, int cout_f,
+                                                             int idx, unsigned int* status) {
+    const int total = cout_f * 16 * cin_f;
+    if (idx >= total) return;
+    const int e = idx & 15, cop = (idx >> 4) % cin_f, g = (idx >> 4) / cin_f;
+    const int co_f = (g / 16) * 16 + e, f = g % 16, i = f >> 2, j = f & 3;
+    const float* gk = w + ((size_t)co_f * cin_f + cop) * 9;
+    const float Gm[4][3] = {{1.f, 0.f, 0.f}, {.5f, .5f, .5f}, {.5f, -.5f, .5f}, {0.f, 0.f, 1.f}};
+    float u = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        float t = 0.0f;
+#pragma unroll
+        for (int l = 0; l < 3; ++l) t = fmaf(gk[8 - (k * 3 + l)], Gm[j][l], t);
+        u = fmaf(Gm[i][k], t, u);
+    }
+    if (j == 3) u = -u;
+    split_w_f16x3(u, wpb[idx], wpb[(size_t)total + idx], status);
+}
+static __global__ void prep_conv_wT_wino_f16x3_kernel(const float* __restrict__ w, unsigned short* __restrict__ wpb, int cin_f, int cout_f,
+                                                       unsigned int* status) {
+    prep_conv_wT_wino_f16x3_elem(w, wpb, cin_f, cout_f, blockIdx.x * blockDim.x + threadIdx.x, status);
 }
 
 // OUT_MODE 0: pooled NHWC (BN + ReLU + max), 1: pooled in the GRU layout [b][tx][co * Hp + ty] (+ its f16x2 planes through
@@ -132,22 +153,8 @@ __device__ __forceinline__ void w2_write64(unsigned base, uint2 v) {
 // DBG (devtools/kernel_ab/bench_conv.hip only): s_memtime stamps of the first producer and the first consumer wave of workgroup 0
 __device__ long long w2_dbg_stamps[2][32];
 __device__ long long w2_dbg_fine[8][8];              // producer wave 0 of workgroup 0, steps 8..15: loop top, DMA issued, raw patches read, V written, DMA wait over, barrier passed
-// Fourth structure: 12 waves per workgroup -- 4 producers (raw patches by LDS-DMA three chunks deep, B^T d B, bf16x3, V[step & 1])
-// and 8 consumers (wave (i, n): transform row i, channel slice n: 4 accumulators, weights of its 4 frequencies one chunk ahead),
-// one barrier per chunk; a task's row transform goes through the V buffer its last chunk just left (two extra barriers per task).
-// F16 (round 4): the contraction on the fp16 matrix cores with the two-way split (f16_split.h) instead of bf16x6 -- the producers
-// write TWO planes (Vh, Vl' = residual * 2^11) instead of three (a third fewer split instructions and LDS writes), the consumers
-// issue THREE products per frequency and 16-deep step instead of six (Vl' Uh, Vh Ul', Vh (Uh 2^11): one accumulator, 2^11 too large,
-// scaled back in the epilogue; weights from prep_conv_w_wino_f16x3: same layout, TWO fp16 planes (Uh, Ul') -- Uh 2^11 is formed in
-// registers, so the U stream that bounds the kernel is a third shorter as well).  The part runs at its power
-// cap: the matrix products ARE the energy.  Needs inputs inside fp16's range (activations: yes; gradients only under the loss
-// scale of the backward).  With 32 KB V buffers the LDS has room for a DEDICATED exchange area of the epilogue's row transform
-// (the bf16x6 form borrowed the V buffer the task's last chunk just left and needed two extra barriers, A and B, around that, with
-// the producers parked at them): a consumer writes its pieces right behind its last MFMAs, the step's ONE barrier publishes them,
-// and the producers are transforming the next chunk meanwhile -- the epilogue was 26 of the f16x3 kernel's 109 us (knock-outs,
-// profiles/r04/bench_conv_wino2_f16x3.txt).
 template <int CIN, int COUT, int OUT_MODE, int DBG = 0, int PRIO = 3>
-__global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_bf16x6_kernel(
+__global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_f16x3_kernel(
     const float* __restrict__ x, const unsigned short* __restrict__ wpb, const float* __restrict__ scale,
     const float* __restrict__ shift, float* __restrict__ out, Wino2Geo geo, float2* __restrict__ stats, const float* __restrict__ zeros) {
     constexpr int NCH = CIN / 16, G = NCH * 16, NCHO = COUT >= 64 ? COUT / 64 : 1;
@@ -577,25 +584,19 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_bf16x6_kernel(
     }
 }
 
-// `attr_done`: the caller's per-device latch of the dynamic-LDS opt-in of THIS instantiation (sir_handle::attr_wino2[...])
+// `g`: wino2_geo of the launch (model_shape.h keeps the model's).  The dynamic-LDS opt-in (W2_LDS_BYTES) is the caller's: the library's
+// goes through sir_lds_opt_in at its launch sites (model_infer.hip / model_train.hip).
+// ctab (OUT_MODE 0 / 1 only): compacted task-column list in device memory (Wino2Geo::ctab), at most ncol_max columns
 template <int CIN, int COUT, int OUT_MODE, int DBG = 0, int PRIO = 3>
-static inline hipError_t launch_conv_wino2(hipStream_t st, bool* attr_done, const float* x, const unsigned short* wpb, const float* scale,
-                                           const float* shift, float* out, int B, int H, int W, float2* stats, const float* zeros, int max_wg = 256,
+static inline hipError_t launch_conv_wino2(hipStream_t st, Wino2Geo g, const float* x, const unsigned short* wpb, const float* scale,
+                                           const float* shift, float* out, float2* stats, const float* zeros, int max_wg = 256,
                                            const int* ctab = nullptr, int ncol_max = 0) {
-    // ctab (OUT_MODE 0 / 1 only): compacted task-column list in device memory (Wino2Geo::ctab), at most ncol_max columns
-    Wino2Geo g;
-    if (!wino2_geo(B, H, W, CIN > COUT ? CIN : COUT, &g)) return hipErrorInvalidValue;
     if (ctab) {
         if (OUT_MODE > 1 || ncol_max < 1) return hipErrorInvalidValue;
         g.ctab = ctab;
         g.NS = g.RBN * ncol_max;                                    // (grid size only: the kernel reads the real count)
     }
-    if (!*attr_done) {
-        hipError_t e = hipFuncSetAttribute((const void*)conv3x3_wino2_bf16x6_kernel<CIN, COUT, OUT_MODE, DBG, PRIO>, hipFuncAttributeMaxDynamicSharedMemorySize, W2_LDS_BYTES);
-        if (e != hipSuccess) return e;
-        *attr_done = true;
-    }
     const int nwg = g.NS < max_wg ? g.NS : max_wg;
-    hipLaunchKernelGGL((conv3x3_wino2_bf16x6_kernel<CIN, COUT, OUT_MODE, DBG, PRIO>), dim3(nwg), dim3(W2_THREADS), W2_LDS_BYTES, st, x, wpb, scale, shift, out, g, stats, zeros);
+    hipLaunchKernelGGL((conv3x3_wino2_f16x3_kernel<CIN, COUT, OUT_MODE, DBG, PRIO>), dim3(nwg), dim3(W2_THREADS), W2_LDS_BYTES, st, x, wpb, scale, shift, out, g, stats, zeros);
     return hipGetLastError();
 }

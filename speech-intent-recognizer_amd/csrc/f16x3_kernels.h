@@ -19,8 +19,8 @@
 #include "bf16x6_kernels.h"     // (includes f16_split.h: the two-way split itself)
 
 // ------------------------------------------------------------------------------------------
-// C[m][z*N + n] = sum_k A[m][k] * Bz[n][k] + biasz[n] with A, B given as f16x2 planes (same contract as
-// gemm_nt_bf16x6_v3_kernel with two planes per operand): Ap [2][M][K], Bp0 / Bp1 [2][N][K] fp16.
+// C[m][z*N + n] = sum_k A[m][k] * Bz[n][k] + biasz[n] with A, B given as f16x2 planes (same contract as the
+// bf16x6 GEMM it replaced, devtools/kernel_ab/legacy_kernels.h, with two planes per operand): Ap [2][M][K], Bp0 / Bp1 [2][N][K] fp16.
 // Tile 160 x 256, BK = 32 (64 bytes per row and plane), 8 waves, wave = 160 x 32 strip: five hi*hi and five cross accumulators
 // (160 registers).  Stage = A [2][160][64 B] + B [2][256][64 B] = 53,248 B; NST = 3 stages (159,744 B, the whole LDS of a CU):
 // a K tile is now 30 MFMAs per wave (960 cycles; two waves per SIMD: ~0.8 us) -- shorter than an L2 round trip under load, so
@@ -335,31 +335,26 @@ static inline bool gemm_f16x3_ok(int M, int N, int K) {
 }
 
 // C[M][2 N] (+ bias) = A x [B0; B1]^T from pre-split f16x2 planes (the GRU input projections: N = 768 per direction)
-static inline hipError_t launch_gemm_nt_f16x3(sir_handle* h, hipStream_t st, const unsigned short* Ap, const unsigned short* Bp0,
+static inline int launch_gemm_nt_f16x3(sir_handle* h, hipStream_t st, const unsigned short* Ap, const unsigned short* Bp0,
                                               const unsigned short* Bp1, const float* bias0, const float* bias1, float* C, int ldc,
                                               int M, int N, int K) {
-    if (!gemm_f16x3_ok(M, N, K)) return hipErrorInvalidValue;
-    if (!h->attr_gemm_v3) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_nt_f16x3_kernel<3, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, h3_lds_bytes(3));
-        if (e != hipSuccess) return e;
-        h->attr_gemm_v3 = true;
-    }
+    SIR_HIP_TRY(gemm_f16x3_ok(M, N, K) ? hipSuccess : hipErrorInvalidValue);
+    SIR_TRY(sir_lds_opt_in(h, (const void*)gemm_nt_f16x3_kernel<3, 0>, h3_lds_bytes(3)));
     const int nwg = ((M + H3_BM - 1) / H3_BM) * 2 * (N / H3_BN);
     hipLaunchKernelGGL((gemm_nt_f16x3_kernel<3, 0>), dim3(nwg), dim3(512), h3_lds_bytes(3), st, Ap, Bp0, Bp1, bias0, bias1, C, ldc, M, N, K);
-    return hipGetLastError();
+    SIR_KCHECK();
+    return SIR_OK;
 }
 
 // the same over the row list `rows` (device memory: rows[0] = count <= MA, then the rows) of A's MA-row planes; no host sync
-static inline hipError_t launch_gemm_nt_f16x3_gather(sir_handle* h, hipStream_t st, const unsigned short* Ap, const unsigned short* Bp0,
+static inline int launch_gemm_nt_f16x3_gather(sir_handle* h, hipStream_t st, const unsigned short* Ap, const unsigned short* Bp0,
                                                      const unsigned short* Bp1, const float* bias0, const float* bias1, float* C, int ldc,
                                                      const int* rows, int MA, int N, int K) {
-    if (!gemm_f16x3_ok(MA, N, K) || K < 2 * H3_BK || (size_t)MA * ldc >= ((size_t)1 << 31)) return hipErrorInvalidValue;   // (K >= 2 BK: the K loop's barriers publish rtab)
-    if (!h->attr_gemm_gather) {
-        hipError_t e = hipFuncSetAttribute((const void*)gemm_nt_f16x3_gather_kernel<0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, h3_lds_bytes(3));
-        if (e != hipSuccess) return e;
-        h->attr_gemm_gather = true;
-    }
+    // (K >= 2 BK: the K loop's barriers publish rtab)
+    SIR_HIP_TRY(gemm_f16x3_ok(MA, N, K) && K >= 2 * H3_BK && (size_t)MA * ldc < ((size_t)1 << 31) ? hipSuccess : hipErrorInvalidValue);
+    SIR_TRY(sir_lds_opt_in(h, (const void*)gemm_nt_f16x3_gather_kernel<0, 0>, h3_lds_bytes(3)));
     hipLaunchKernelGGL((gemm_nt_f16x3_gather_kernel<0, 0>), dim3(h3_gather_tiles(96, MA, N)), dim3(512), h3_lds_bytes(3), st, Ap, Bp0, Bp1,
                        bias0, bias1, C, ldc, rows, MA, N, K, h->num_cus);
-    return hipGetLastError();
+    SIR_KCHECK();
+    return SIR_OK;
 }

@@ -498,21 +498,16 @@ int sir_features_launch(sir_handle* h, const void* wave, int wave_dtype, int64_t
     }
     const size_t lds = (size_t)NW * XBUF * sizeof(float2) + NW * sizeof(double) + (size_t)2 * NW * PROW * sizeof(float) +
                        (size_t)((h->mel_nnz + 3) & ~3) * sizeof(float) + (1024 + 8 * TW2S) * sizeof(float2);
-    if (!h->feat_attr_set) {          // > 64 KB of dynamic LDS needs the opt-in, once per handle (= per device)
-        SIR_HIP_TRY(hipFuncSetAttribute((const void*)feat_utt_kernel<float, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        SIR_HIP_TRY(hipFuncSetAttribute((const void*)feat_utt_kernel<float, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        SIR_HIP_TRY(hipFuncSetAttribute((const void*)feat_utt_kernel<short, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        SIR_HIP_TRY(hipFuncSetAttribute((const void*)feat_utt_kernel<short, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        h->feat_attr_set = true;
-    }
     dim3 grid(batch), block(THREADS);
+    // (> 64 KB of dynamic LDS needs the opt-in)
 #define SIR_LAUNCH_FEAT(TY, AUGF)                                                                            \
+    SIR_TRY(sir_lds_opt_in(h, (const void*)feat_utt_kernel<TY, AUGF>, (int)lds));                           \
     hipLaunchKernelGGL((feat_utt_kernel<TY, AUGF>), grid, block, lds, stream, (const TY*)wave,              \
                        (long long)wave_stride, lengths, max_len, out, db_out, t_pad, tb, ag, tmask, fmask)
     {
     SirProfScope prof(h, SIR_K_FEAT_FRAMES, stream);
-    if (wave_dtype == SIR_WAVE_F32) { if (wave_aug) SIR_LAUNCH_FEAT(float, true); else SIR_LAUNCH_FEAT(float, false); }
-    else { if (wave_aug) SIR_LAUNCH_FEAT(short, true); else SIR_LAUNCH_FEAT(short, false); }
+    if (wave_dtype == SIR_WAVE_F32) { if (wave_aug) { SIR_LAUNCH_FEAT(float, true); } else { SIR_LAUNCH_FEAT(float, false); } }
+    else { if (wave_aug) { SIR_LAUNCH_FEAT(short, true); } else { SIR_LAUNCH_FEAT(short, false); } }
     }
 #undef SIR_LAUNCH_FEAT
     SIR_HIP_TRY(hipGetLastError());

@@ -1,38 +1,28 @@
-// Token-reduction GEMMs of the GRU backward (dW = dG^T X, dX = dG [W; W_reverse]) with SPECIALISED waves: the same tiles, LDS
-// images, transposed fragment reads and epilogue as gemm_tn_bf16x6_kernel (gemm_tn_bf16x6_kernel.h: read that header first), but
-// a BM x 256 x 32 stage is prepared by 8 PRODUCER waves (fp32 loads a whole stage ahead into a second register set, three-way
-// bf16 split, ds_write_b64 into stage buffer s & 1) while 8 CONSUMER waves multiply stage s - 1 from the other buffer: one bare
-// s_barrier per stage, 1024 threads, one workgroup per CU.  In the first kernel all 8 waves do both with two barriers per stage, and
-// the split sits between the MFMA phases (matrix pipe 35-39 % busy, profiles/r03/roofline.md).  The recipe is the producer /
-// consumer Winograd kernel's (conv_wino2_bf16x6_kernel.h): a role's registers are live only in its own branch, the wave index is a
-// scalar, the barrier does not drain vmcnt.  What the knock-outs (template parameter dbg: 1 = no split / LDS stores, 2 = no
-// loads, 16 = idle consumers) showed on the way, B = 256 layer-0 dX, first kernel 140 us:
-//   * 4 producer waves, loads under per-lane bounds branches: 171 us -- the compiler cannot count loads issued under branches and
-//     waits for vmcnt(0) before every use, draining the next stage's loads too;
-//   * branch-free loads a stage ahead (vmcnt(22) .. vmcnt(12) in the ISA): 156 us, producers alone 77 us = 1.6 us per stage for
-//     580 instructions: ONE wave per SIMD issues an instruction every ~6 cycles and that, not the VALU, was the producers' limit;
-//   * 8 producer waves (two per SIMD, half the items each): 120 us; producers alone 61, consumers alone 88 us (MFMA 73 % busy).
-//   * tried and removed: the B operand of dX (the weights) taken from the forward GEMM's bf16x3 planes by LDS-DMA with the chunk
-//     swizzle on the source address -- no split, no LDS stores, 4 producer waves.  Parity-correct, slower: 139 us (consumers alone
-//     88, producers alone 73, without the DMA 97, without the A operand 116).  6 bytes per element instead of 4 come through L2, and
-//     whatever the producers do -- VALU or DMA -- ADDS to the consumers' time instead of hiding behind it: with the matrix pipe this
-//     busy the step runs at the board's power limit, so energy per stage, not issue slots, is what counts.
-// Measured in the training step (profiles/r03): dX l0 140 -> 120 us, dX l1 (64-row tiles) 100 -> 84, dW 114 -> 110 (mean of layers).
+// Token-reduction GEMMs of the GRU backward (dW = dG^T X, dX = dG [W; W_reverse]) on the fp16 matrix cores with f16x3 products
+// (f16_split.h), SPECIALISED waves.  Tiles, LDS images, transposed fragment reads and the job table: gemm_tn_common.h (read that
+// header first).  A BM x 256 x 32 stage is prepared by 8 PRODUCER waves (fp32 loads a whole stage ahead into a second register
+// set, two-way fp16 split, ds_write_b64 into stage buffer s & 1) while 8 CONSUMER waves multiply stage s - 1 from the other
+// buffer: one bare s_barrier per stage, 1024 threads, one workgroup per CU.  The recipe is the producer / consumer Winograd
+// kernel's (conv_wino2_f16x3_kernel.h): a role's registers are live only in its own branch, the wave index is a scalar, the
+// barrier does not drain vmcnt.  Two producer waves per SIMD: one wave issues an instruction every ~6 cycles and that, not the
+// VALU, limits a producer; loads are branch-free (the compiler cannot count loads issued under branches and would wait for
+// vmcnt(0) before every use).
+// Operands: A (the gate gradients, which carry the backward's loss scale and therefore sit in fp16's range) is staged as TWO planes
+// (Ah, Al' = residual 2^11); B (activations / weights) is first scaled by TN2_BS = 2^-4 (exact) and staged as two planes as well
+// (Bh, Bl'); the consumers form Bh 2^11 in registers (four v_pk_mul_f16 per fragment), so that the three products
+// Al' Bh + Ah Bl' + Ah (Bh 2^11) = 2^11 A B go into ONE accumulator (the consumers' 64 accumulator registers are what the
+// 128-register budget of a 1024-thread workgroup allows) and the epilogue scales by 2^-11 / TN2_BS = 2^-7.  Bh 2^11 is exact while
+// |B| TN2_BS < 32, i.e. |B| < 512 (larger values are clamped: activations behind BatchNorm and weights are nowhere near).
+// What bounds it: with the matrix pipe this busy the step runs at the board's power limit, so energy per
+// stage, not issue slots, is what counts.  The knock-out numbers of the structures tried on the way: DESIGN.md section 4.
 #pragma once
-#include "gemm_tn_bf16x6_kernel.h"
+#include "gemm_tn_common.h"
 
 constexpr int TN2_NPW = 8;                                   // producer waves (two per SIMD: one wave issues too slowly, see below)
 constexpr int TN2_THREADS = 64 * (TN2_NPW + 8);              // + 8 consumer waves
 constexpr int TN2_BM = 128;
 constexpr size_t tn2_lds_bytes(bool a_km, int bm = TN2_BM) { return 2 * tn_lds_bytes(a_km, bm); }     // two stage buffers: 147,456 / 159,744 B (BM = 128)
 
-// f16x3 (round 4; the only form now -- the bf16x6 form's staging and six products are gone): the products on the fp16 matrix cores with the two-way split of f16_split.h.  A (the gate gradients, which carry the
-// backward's loss scale and therefore sit in fp16's range) is staged as TWO planes (Ah, Al' = residual 2^11); B (activations / weights)
-// is first scaled by TN2_BS = 2^-4 (exact) and staged as two planes as well (Bh, Bl'); the consumers form Bh 2^11 in registers (four
-// v_pk_mul_f16 per fragment), so that the three products Al' Bh + Ah Bl' + Ah (Bh 2^11) = 2^11 A B go into ONE accumulator (the
-// consumers' 64 accumulator registers are what the 128-register budget of a 1024-thread workgroup allows) and the epilogue scales by
-// 2^-11 / TN2_BS = 2^-7.  Bh 2^11 is exact while |B| TN2_BS < 32, i.e. |B| < 512 (larger values are clamped: activations behind
-// BatchNorm and weights are nowhere near).  3 instead of 6 MFMAs per product, 4 instead of 6 planes through LDS, a shorter split.
 constexpr float TN2_BS = 0.0625f;
 constexpr float TN2_BLIM = 31.984375f;                       // 65504 / 2048
 // (Bh, Bl') of v * SCALE (SCALE a power of two; |v| SCALE clamped below 32 so that Bh 2^11 stays finite)
@@ -66,7 +56,7 @@ __device__ __forceinline__ bf16x8 tn2_hi2(const bf16x8& bh) {
 __device__ __forceinline__ void tn2_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 template <bool A_KM, int dbg = 0, int BM = TN2_BM>
-__global__ __launch_bounds__(TN2_THREADS, TN2_THREADS / 256) void gemm_tn2_bf16x6_kernel(TnJobs jobs, int M, int K, int kchunk, int seq) {
+__global__ __launch_bounds__(TN2_THREADS, TN2_THREADS / 256) void gemm_tn2_f16x3_kernel(TnJobs jobs, int M, int K, int kchunk, int seq) {
     constexpr int NC = BM >= 128 ? 2 : 1;                    // BM = 128: consumers 2 x 4, wave tile 64 x 64; BM = 64: 1 x 8, wave tile 64 x 32
     constexpr int AXW = BM * 2, BXW = TN_BN * 2;             // row bytes of the k-major images
     constexpr int APLANE = A_KM ? TN_BK * AXW : BM * TN_ROWB, BPLANE = TN_BK * BXW;

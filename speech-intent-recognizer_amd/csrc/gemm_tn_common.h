@@ -1,23 +1,18 @@
-// Shared pieces of the token-reduction ("TN") GEMMs of the GRU backward: tile sizes, the swizzled k-major LDS image and its
-// transposed reads, the job table.  The kernel that runs is gemm_tn2_bf16x6_kernel.h; the first-generation kernel this header
-// was written for (described below) has been retired.
-//
+// Shared pieces of the token-reduction ("TN") GEMMs of the GRU backward (gemm_tn2_f16x3_kernel.h) and of the convolution weight
+// gradients that are built the same way (wgrad_wino_f16x3_kernel.h, wgrad_bf16x6_kernel.h): tile sizes, the swizzled k-major LDS
+// image and its transposed reads, the job table.
 //
 //   dW[m][n] = sum_tok A[tok][m] * B[tok (+shift)][n]       A = dgi / dgh slice [tokens][768], B = layer input or h_prev
-// Both operands are token-major in memory, i.e. TRANSPOSED with respect to what v_mfma_f32_32x32x16_bf16 wants (eight
-// consecutive k = tokens per lane).  The transposition is done by the LDS hardware on the way OUT: a 32-token stage is
-// written in its natural [token][column] order -- thread = (token, 4 columns) reads a float4 (lanes along the columns:
-// 512-byte coalesced rows), splits it into the three bf16 planes and issues ONE ds_write_b64 per plane -- and the MFMA
-// fragments are fetched with ds_read_b64_tr_b16 (gfx950), which hands lane i column i of a 4-token x 16-column block:
-// two of them make the lane's eight consecutive tokens.  64-byte chunks of a row are XOR-swizzled with the token index so
-// that the four rows of a transposed read fall on the four quarters of the bank line (conflict-free reads AND stores).
-// The first version transposed on the way IN with twelve 2-byte LDS stores per float4 (lanes along the tokens): timing
-// knock-outs put that staging at 67 of the dW launch's 214 us and 48 of dX's 167 us, serial with the MFMAs.
+// Both operands are token-major in memory, i.e. TRANSPOSED with respect to what a 16-bit MFMA wants (eight consecutive
+// k = tokens per lane).  The transposition is done by the LDS hardware on the way OUT: a 32-token stage is written in its natural
+// [token][column] order -- thread = (token, 4 columns) reads a float4 (lanes along the columns: 512-byte coalesced rows), splits
+// it into the operand planes and issues ONE ds_write_b64 per plane -- and the MFMA fragments are fetched with
+// ds_read_b64_tr_b16 (gfx950), which hands lane i column i of a 4-token x 16-column block: two of them make the lane's eight
+// consecutive tokens.  64-byte chunks of a row are XOR-swizzled with the token index so that the four rows of a transposed read
+// fall on the four quarters of the bank line (conflict-free reads AND stores).
 // One launch covers up to four jobs (both directions x {W_ih, W_hh} of a layer): blockIdx.x walks the 128 x 256 output
 // tiles of all jobs, blockIdx.y the K splits; every (tile, split) writes its partial to the job's slab z (deterministic
-// slab_reduce afterwards).  8 waves, wave tile 64 x 64 (2 x 2 accumulators), 24 MFMAs per 16-token step.
-// Tried and removed: 16-token stages in two LDS buffers with the next stage's stores placed between the MFMAs
-// (sched_group_barrier 2 MFMA : 10 VALU : 3 LDS stores) and one barrier per stage -- slower than the plain two-barrier loop.
+// slab_reduce afterwards).
 //   seq / shift: row tok of B is taken from row tok + shift of the same length-`seq` sequence, zero outside it (the
 //   h_{t-1} / h_{t+1} operand of the W_hh gradient).
 #pragma once

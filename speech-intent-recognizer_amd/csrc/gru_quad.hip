@@ -6,19 +6,9 @@
 int sir_launch_gru_quad(sir_handle* h, hipStream_t st, bool save, const float* gi, const float* whh0, const float* whh1, const float* bhh0,
                         const float* bhh1, float* y, int B, int S, float* gates, unsigned short* yplanes, const void* wfrag0,
                         const void* wfrag1, const int* nlive) {
-    if (!h->attr_gru_quad) {
-        SIR_HIP_TRY(hipFuncSetAttribute((const void*)gru_quad_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GQ_LDS_BYTES));
-        SIR_HIP_TRY(hipFuncSetAttribute((const void*)gru_quad_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)GQ_LDS_BYTES));
-        h->attr_gru_quad = true;
-    }
     if (S >= 511) { sir_set_error("gru_quad: %d steps exceed the 9-bit step field of the granule tag", S); return SIR_EUNSUPPORTED; }
     if (!wfrag0 || !wfrag1) { sir_set_error("gru_quad: the prepared W_hh fragments are required (sir_prep_whh_quad / train_prep_kernel)"); return SIR_EINVAL; }
     const int clusters = ((B + GQ_NU - 1) / GQ_NU) * 2;
-    unsigned epoch = 0;
-    void* xbuf = nullptr;
-    if (sir_xbuf_acquire(h, st, 1, (size_t)clusters * GQ_XBUF_PER_CLUSTER, 127u, &xbuf, &epoch) != SIR_OK) {
-        return SIR_EHIP;
-    }
     const dim3 grid(4 * (unsigned)clusters);
     // SIR_GRU_DBG: timing knock-outs and fault injection of gru_quad_kernel (see its `dbg` comment); 0 in production
     static const int dbg0 = getenv("SIR_GRU_DBG") ? atoi(getenv("SIR_GRU_DBG")) : 0;
@@ -29,10 +19,19 @@ int sir_launch_gru_quad(sir_handle* h, hipStream_t st, bool save, const float* g
     typedef void (*kern_t)(const float*, const float*, const float*, const float*, const float*, float*, int, int, float*, unsigned long long*,
                            unsigned int*, int, unsigned, unsigned short*, const uint4*, const uint4*, const int*);
     const kern_t kern = save ? gru_quad_kernel<true, true> : gru_quad_kernel<false, false>;
-    hipLaunchKernelGGL(kern, grid, dim3(GQ_THREADS), GQ_LDS_BYTES, st, gi, whh0, whh1, bhh0, bhh1, y, B, S, gates,
-                       (unsigned long long*)xbuf, h->status, dbg, epoch, yplanes, (const uint4*)wfrag0, (const uint4*)wfrag1, nlive);
-    SIR_HIP_TRY(hipGetLastError());
-    return SIR_OK;
+    SIR_TRY(sir_lds_opt_in(h, (const void*)kern, (int)GQ_LDS_BYTES));
+    // the launch is chained with the handle's other cluster launches (sir_cluster_enter); leave runs whenever enter succeeded
+    SIR_TRY(sir_cluster_enter(h, st));
+    unsigned epoch = 0;
+    void* xbuf = nullptr;
+    int rc = sir_xbuf_acquire(h, st, 1, (size_t)clusters * GQ_XBUF_PER_CLUSTER, 127u, &xbuf, &epoch);
+    if (rc == SIR_OK) {
+        hipLaunchKernelGGL(kern, grid, dim3(GQ_THREADS), GQ_LDS_BYTES, st, gi, whh0, whh1, bhh0, bhh1, y, B, S, gates,
+                           (unsigned long long*)xbuf, h->status, dbg, epoch, yplanes, (const uint4*)wfrag0, (const uint4*)wfrag1, nlive);
+        rc = sir_check_hip(hipGetLastError(), "gru_quad_kernel");
+    }
+    const int rc_leave = sir_cluster_leave(h, st);
+    return rc != SIR_OK ? rc : rc_leave;
 }
 
 // inference-side preparation of one direction's resident fragments (GRU_FRAG_BYTES)
@@ -44,19 +43,20 @@ void sir_prep_whh_quad(hipStream_t st, const float* whh, void* frag) {
 int sir_launch_gru_bwd_quad(sir_handle* h, hipStream_t st, const float* dy, const float* gates, const float* y, const float* whh0,
                             const float* whh1, float* dgi, float* dgh, float* bsum_i, float* bsum_h, int B, int S, const void* wfrag0,
                             const void* wfrag1) {
-    if (!h->attr_gru_bwd_quad) {
-        SIR_HIP_TRY(hipFuncSetAttribute((const void*)gru_bwd_quad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)BQ_LDS_BYTES));
-        h->attr_gru_bwd_quad = true;
-    }
     if (S >= 65535) { sir_set_error("gru_bwd_quad: %d steps exceed the 16-bit step field of the granule tag", S); return SIR_EUNSUPPORTED; }
     if (!wfrag0 || !wfrag1) { sir_set_error("gru_bwd_quad: the prepared W_hh fragments are required (train_prep_kernel)"); return SIR_EINVAL; }
     const int clusters = ((B + GQ_NU - 1) / GQ_NU) * 2;
+    const int dbg = GQ_POLL_DELAY << 8;                      // (`dbg` of gru_bwd_quad_kernel: no knock-outs, the first poll's delay)
+    SIR_TRY(sir_lds_opt_in(h, (const void*)gru_bwd_quad_kernel, (int)BQ_LDS_BYTES));
+    SIR_TRY(sir_cluster_enter(h, st));
     unsigned epoch = 0;
     void* xbuf = nullptr;
-    if (sir_xbuf_acquire(h, st, 3, (size_t)clusters * BQ_XBUF_PER_CLUSTER, 0xFFFFu, &xbuf, &epoch) != SIR_OK) return SIR_EHIP;
-    const int dbg = GQ_POLL_DELAY << 8;                      // (`dbg` of gru_bwd_quad_kernel: no knock-outs, the first poll's delay)
-    hipLaunchKernelGGL(gru_bwd_quad_kernel, dim3(4 * (unsigned)clusters), dim3(GQ_THREADS), BQ_LDS_BYTES, st, dy, gates, y, whh0, whh1, dgi, dgh,
-                       bsum_i, bsum_h, B, S, (unsigned long long*)xbuf, h->status, epoch, dbg, (const uint4*)wfrag0, (const uint4*)wfrag1);
-    SIR_HIP_TRY(hipGetLastError());
-    return SIR_OK;
+    int rc = sir_xbuf_acquire(h, st, 3, (size_t)clusters * BQ_XBUF_PER_CLUSTER, 0xFFFFu, &xbuf, &epoch);
+    if (rc == SIR_OK) {
+        hipLaunchKernelGGL(gru_bwd_quad_kernel, dim3(4 * (unsigned)clusters), dim3(GQ_THREADS), BQ_LDS_BYTES, st, dy, gates, y, whh0, whh1, dgi, dgh,
+                           bsum_i, bsum_h, B, S, (unsigned long long*)xbuf, h->status, epoch, dbg, (const uint4*)wfrag0, (const uint4*)wfrag1);
+        rc = sir_check_hip(hipGetLastError(), "gru_bwd_quad_kernel");
+    }
+    const int rc_leave = sir_cluster_leave(h, st);
+    return rc != SIR_OK ? rc : rc_leave;
 }

@@ -14,10 +14,8 @@
 // rows) and the layer-0 recurrence reads the template's gi row for steps s >= d3.  Columns past the computed ones
 // are left unwritten in a1 / a2 / x0 / xs / gi.  The conv fallback kernels (shapes the Winograd kernel does not cover) keep the
 // full path.
-#include "bf16x6_kernels.h"
 #include "f16x3_kernels.h"
-#include "conv_wino_bf16x6_kernel.h"
-#include "conv_wino2_bf16x6_kernel.h"
+#include "conv_fwd.h"
 #include "gru_frag_prep.h"
 
 namespace {
@@ -43,16 +41,14 @@ enum WsBuf {
     WS_COUNT
 };
 
-struct Dims {
-    int B, T, wp1, wp2, wp3, S;
+struct Dims : SirDims {
     int tw2, tw3, k2max, k3max;     // Winograd tile columns of conv2 / conv3, and 4-column task columns per utterance
 };
 
 bool make_dims(int batch, int t_frames, Dims* d) {
-    d->B = batch; d->T = t_frames;
-    d->wp1 = t_frames / 2; d->wp2 = d->wp1 / 2; d->wp3 = d->wp2 / 2; d->S = d->wp3;
+    if (!sir_make_dims(batch, t_frames, d)) return false;
     d->tw2 = (d->wp1 + 1) / 2; d->tw3 = (d->wp2 + 1) / 2; d->k2max = (d->tw2 + 3) / 4; d->k3max = (d->tw3 + 3) / 4;
-    return batch > 0 && d->S >= 1 && d->S <= ATT_MAX_S && batch <= 65535;
+    return true;
 }
 
 // int offsets inside WS_PAD
@@ -175,8 +171,6 @@ extern "C" int sir_model_workspace_offsets(const sir_handle* h, int batch, int t
     return WS_COUNT;
 }
 
-#define SIR_KCHECK() SIR_HIP_TRY(hipGetLastError())
-
 extern "C" int sir_model_infer(sir_handle* h, const sir_model_weights* w, const float* feats, int batch, int t_frames,
                                float* logits, int64_t* argmax, void* workspace, size_t workspace_bytes, void* stream_) {
     if (!h || !w || !feats || !logits || !workspace) { sir_set_error("sir_model_infer: NULL argument"); return SIR_EINVAL; }
@@ -215,10 +209,10 @@ extern "C" int sir_model_infer(sir_handle* h, const sir_model_weights* w, const 
     float* const xz = (float*)(ws + off[WS_XZ]);
 
     // conv2 / conv3 as Winograd F(2x2, 3x3) -- the 2x2 output tile is the pooling window -- on the producer / consumer kernel
-    // (conv_wino2_bf16x6_kernel.h); shapes it does not cover (batch x map beyond 32-bit offsets) keep the first-generation kernels.
+    // (conv_wino2_f16x3_kernel.h); shapes it does not cover (batch x map beyond 32-bit offsets) keep the bf16x6 fallback kernels.
     // The pad skip (head of this file) runs with the Winograd kernels, over the batch + the template utterance.
-    Wino2Geo geo2, geo3;
-    const bool w2 = sir_conv_stage_fits(2, wino2_geo(B + 1, 32, d.wp1, 64, &geo2)) && sir_conv_stage_fits(3, wino2_geo(B + 1, 16, d.wp2, 128, &geo3));
+    const SirConvPlan cp = sir_conv_plan(&d, true);             // (true: the template utterance)
+    const bool w2 = cp.fwd_wino;
     const int BT = w2 ? B + 1 : B;                                // utterances through conv1-3 and the layer-0 projection
 
     // ---- weight preparation -------------------------------------------------------------
@@ -265,23 +259,13 @@ extern "C" int sir_model_infer(sir_handle* h, const sir_model_weights* w, const 
     }
     {
         SirProfScope prof(h, SIR_K_CONV2, st);
-        if (w2)
-            SIR_HIP_TRY((launch_conv_wino2<32, 64, 0>(st, &h->attr_wino2[0], a1, (const unsigned short*)wcb2, bns + 32, bnt + 32, a2, BT, 32, d.wp1,
-                                                    (float2*)nullptr, h->zero_page, h->num_cus, ptab + pt.tab2, (B + 1) * d.k2max)));
-        else
-            hipLaunchKernelGGL((conv3x3_wino_bf16x6_kernel<32, 64, 0>), dim3(((d.wp1 + 1) / 2 + 1) / 2, 1, B), dim3(256), WINO_LDS_BYTES, st,
-                               a1, (const unsigned short*)wcb2, bns + 32, bnt + 32, a2, 32, d.wp1, 16, d.wp2, (float2*)nullptr);
+        SIR_TRY((conv_fwd<32, 64, 0>(h, st, w2, cp.geo2, BT, a1, wcb2, nullptr, bns + 32, bnt + 32, a2, nullptr, ptab + pt.tab2, (B + 1) * d.k2max)));
     }
     {
         // conv3 stores straight into the GRU input layout [B][S][c*8+h] (models.py:55-57) and writes the f16x2 planes of
         // the first input projection's A operand beside it
         SirProfScope prof(h, SIR_K_CONV3, st);
-        if (w2)
-            SIR_HIP_TRY((launch_conv_wino2<64, 128, 1>(st, &h->attr_wino2[1], a2, (const unsigned short*)wcb3, bns + 96, bnt + 96, x0, BT, 16, d.wp2,
-                                                     (float2*)xs, h->zero_page, h->num_cus, ptab + pt.tab3, (B + 1) * d.k3max)));
-        else
-            hipLaunchKernelGGL((conv3x3_bf16x6_ns_kernel<64, 128, 2, 2, 1, 0, 2, 1, 1>), dim3((d.wp2 + 7) / 8, 1, B), dim3(256), conv_ns_lds_bytes(2, 2, 2), st,
-                               a2, (const unsigned short*)wcb3d, bns + 96, bnt + 96, x0, 16, d.wp2, 8, d.wp3, (float2*)xs);
+        SIR_TRY((conv_fwd<64, 128, 1>(h, st, w2, cp.geo3, BT, a2, wcb3, wcb3d, bns + 96, bnt + 96, x0, (float2*)xs, ptab + pt.tab3, (B + 1) * d.k3max)));
     }
     SIR_KCHECK();
 
@@ -292,34 +276,28 @@ extern "C" int sir_model_infer(sir_handle* h, const sir_model_weights* w, const 
         // template's S rows), on a tile the compacted count fills the chip with; the other gi rows are left unwritten
         SirProfScope prof(h, SIR_K_GEMM_IH0, st);
         if (w2)
-            SIR_HIP_TRY(launch_gemm_nt_f16x3_gather(h, st, (const unsigned short*)xs, (const unsigned short*)wsl0,
+            SIR_TRY(launch_gemm_nt_f16x3_gather(h, st, (const unsigned short*)xs, (const unsigned short*)wsl0,
                                                     (const unsigned short*)(wsl0 + (size_t)2 * 768 * 1024), w->gru_b_ih[0], w->gru_b_ih[1], gi, 1536,
                                                     (const int*)(ptab + pt.rows), BT * S, 768, 1024));
         else
-            SIR_HIP_TRY(launch_gemm_nt_f16x3(h, st, (const unsigned short*)xs, (const unsigned short*)wsl0,
+            SIR_TRY(launch_gemm_nt_f16x3(h, st, (const unsigned short*)xs, (const unsigned short*)wsl0,
                                              (const unsigned short*)(wsl0 + (size_t)2 * 768 * 1024), w->gru_b_ih[0], w->gru_b_ih[1], gi, 1536, M, 768, 1024));
     }
     {
         SirProfScope prof(h, SIR_K_GRU0, st);
-        if (sir_cluster_enter(h, st) != SIR_OK) return SIR_EHIP;
         // layer 0 also writes the f16x2 planes of ITS output: the A operand of the layer-1 projection
-        const int rc = sir_launch_gru_quad(h, st, false, gi, w->gru_w_hh[0], w->gru_w_hh[1], w->gru_b_hh[0], w->gru_b_hh[1], y0, B, S, nullptr,
-                                           xs, wht, (unsigned char*)wht + GRU_FRAG_BYTES, w2 ? (const int*)(ptab + pt.d3) : (const int*)nullptr);
-        if (rc != SIR_OK) return rc;
-        if (sir_cluster_leave(h, st) != SIR_OK) return SIR_EHIP;
+        SIR_TRY(sir_launch_gru_quad(h, st, false, gi, w->gru_w_hh[0], w->gru_w_hh[1], w->gru_b_hh[0], w->gru_b_hh[1], y0, B, S, nullptr,
+                                    xs, wht, (unsigned char*)wht + GRU_FRAG_BYTES, w2 ? (const int*)(ptab + pt.d3) : (const int*)nullptr));
     }
     {
         SirProfScope prof(h, SIR_K_GEMM_IH1, st);
-        SIR_HIP_TRY(launch_gemm_nt_f16x3(h, st, (const unsigned short*)xs, (const unsigned short*)wsl1,
+        SIR_TRY(launch_gemm_nt_f16x3(h, st, (const unsigned short*)xs, (const unsigned short*)wsl1,
                                          (const unsigned short*)(wsl1 + (size_t)2 * 768 * 512), w->gru_b_ih[2], w->gru_b_ih[3], gi, 1536, M, 768, 512));
     }
     {
         SirProfScope prof(h, SIR_K_GRU1, st);
-        if (sir_cluster_enter(h, st) != SIR_OK) return SIR_EHIP;
-        const int rc = sir_launch_gru_quad(h, st, false, gi, w->gru_w_hh[2], w->gru_w_hh[3], w->gru_b_hh[2], w->gru_b_hh[3], y1, B, S, nullptr,
-                                           nullptr, (unsigned char*)wht + 2 * GRU_FRAG_BYTES, (unsigned char*)wht + 3 * GRU_FRAG_BYTES);
-        if (rc != SIR_OK) return rc;
-        if (sir_cluster_leave(h, st) != SIR_OK) return SIR_EHIP;
+        SIR_TRY(sir_launch_gru_quad(h, st, false, gi, w->gru_w_hh[2], w->gru_w_hh[3], w->gru_b_hh[2], w->gru_b_hh[3], y1, B, S, nullptr,
+                                    nullptr, (unsigned char*)wht + 2 * GRU_FRAG_BYTES, (unsigned char*)wht + 3 * GRU_FRAG_BYTES));
     }
     SIR_KCHECK();
 

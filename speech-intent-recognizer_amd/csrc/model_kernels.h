@@ -10,6 +10,7 @@
 // row=(r&3)+8*(r>>2)+4*(l>>5).
 #pragma once
 #include "sir_internal.h"
+#include "model_shape.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float mk_f32x2 __attribute__((ext_vector_type(2)));
@@ -192,7 +193,7 @@ __device__ __forceinline__ void gru_fma4(float (&acc)[NB], const float4 w, const
 // attention pooling (models/models.py:63-64): scores = y a + b; softmax over time; ctx = sum_t w_t y_t
 // one workgroup per utterance, wave shuffles for the 512-wide dots
 // ------------------------------------------------------------------------------------------
-constexpr int ATT_MAX_S = 256;
+// (ATT_MAX_S: model_shape.h)
 
 static __global__ __launch_bounds__(256) void attention_pool_kernel(const float* __restrict__ y, const float* __restrict__ aw,
                                                              const float* __restrict__ ab, float* __restrict__ ctx,

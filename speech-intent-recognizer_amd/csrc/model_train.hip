@@ -3,13 +3,12 @@
 // (sir_model_train_bwd) and multi-tensor Adam (sir_adam_step).  Replaces the body of
 // train_epoch (scripts/train.py:90-107: forward, criterion, loss.backward(), optimizer.step()).
 #include <cstdlib>
-#include "bf16x6_kernels.h"
 #include "f16x3_kernels.h"
 #include "train_kernels.h"
-#include "conv_wino2_bf16x6_kernel.h"
+#include "conv_fwd.h"
 #include "wgrad_bf16x6_kernel.h"
-#include "gemm_tn2_bf16x6_kernel.h"
-#include "wgrad_wino_bf16x6_kernel.h"
+#include "gemm_tn2_f16x3_kernel.h"
+#include "wgrad_wino_f16x3_kernel.h"
 
 namespace {
 
@@ -31,8 +30,8 @@ enum TrainBuf {
     TB_COUNT
 };
 
-// K splits of the four-job weight-gradient launch of one GRU layer (gemm_tn2_bf16x6_kernel) and its slab floats
-static inline void tn_x6_plan(int tokens, int in_sz, int* tiles, int* kchunk, int* nsplit, size_t* slab_floats) {
+// K splits of the four-job weight-gradient launch of one GRU layer (gemm_tn2_f16x3_kernel<true>) and its slab floats
+static inline void tn_dw_plan(int tokens, int in_sz, int* tiles, int* kchunk, int* nsplit, size_t* slab_floats) {
     const int t = 2 * ((768 / TN2_BM) * ((in_sz + TN_BN - 1) / TN_BN) + (768 / TN2_BM) * 1);
     int ks = 256 / t;
     ks = ks < 1 ? 1 : (ks > 16 ? 16 : ks);
@@ -49,32 +48,25 @@ static inline bool dx_splitk(int tokens, int in_sz) {
     return nt < 160 && 2 * nt >= 96;
 }
 
-struct TDims {
-    int B, T, wp1, wp2, wp3, S;
+struct TDims : SirDims {
+    SirConvPlan conv;
     int c1gx, c1gy;          // conv1 grids (ceil over un-pooled odd columns)
     int c2gx, c3gx, c3fx;      // c3fx: conv3 FORWARD grid (16x8-pixel tiles); c3gx: conv3 data-gradient grid (16x16)
     int c2wx;                  // conv2 FORWARD grid: Winograd blocks of two tile columns (4 pixels)
-    int wg2_blocks, wg3_blocks, wg2_rb, wg3_rb;
+    int wg2_blocks, wg3_blocks;  // workgroups (= slabs) of the nine-tap weight-gradient fallback: one image each
     int ksplits, kchunk;
 };
 
-// the data gradients on the second-generation Winograd kernel (the forward's weight preparation and the backward agree on it)
-static inline bool dgrad3_wino(const TDims& d) { Wino2Geo g; return sir_conv_stage_fits(3, wino2_geo(d.B, 16, d.wp2, 128, &g)); }
-static inline bool dgrad2_wino(const TDims& d) { Wino2Geo g; return sir_conv_stage_fits(2, wino2_geo(d.B, 32, d.wp1, 64, &g)); }
-
 bool make_tdims(int batch, int t, TDims* d) {
-    d->B = batch; d->T = t;
-    d->wp1 = t / 2; d->wp2 = d->wp1 / 2; d->wp3 = d->wp2 / 2; d->S = d->wp3;
-    if (!(batch > 0 && d->S >= 1 && d->S <= ATT_MAX_S && batch <= 65535)) return false;
+    if (!sir_make_dims(batch, t, d)) return false;
+    d->conv = sir_conv_plan(d, false);
     d->c1gx = ((t + 1) / 2 + C1_PCOLS - 1) / C1_PCOLS;
     d->c1gy = (32 + C1_PROWS - 1) / C1_PROWS;
     d->c2gx = (d->wp1 + 7) / 8;
     d->c2wx = ((d->wp1 + 1) / 2 + 1) / 2;
     d->c3gx = (d->wp2 + 15) / 16;
     d->c3fx = (d->wp2 + 7) / 8;
-    d->wg2_rb = 32; d->wg3_rb = 16;                    // rows per workgroup of the weight-gradient kernels: one image each (256 workgroups at batch 256)
-    d->wg2_blocks = batch * (32 / d->wg2_rb);
-    d->wg3_blocks = batch * (16 / d->wg3_rb);
+    d->wg2_blocks = d->wg3_blocks = batch;
     const int K = batch * d->S;
     d->ksplits = K >= 2048 ? 8 : (K >= 256 ? 2 : 1);
     d->kchunk = ((K + d->ksplits - 1) / d->ksplits + 31) / 32 * 32;
@@ -123,10 +115,10 @@ void tws_sizes(const TDims& d, size_t* n) {           // element counts (floats)
     const size_t s_w2 = (size_t)d.wg2_blocks * 9 * 64 * 32, s_g = (size_t)d.ksplits * 768 * 1024;
     if (s_w2 > slab) slab = s_w2;
     if (s_g > slab) slab = s_g;
-    for (int in_sz : {1024, 512}) {                       // slabs of the four-job bf16x6 weight-gradient launch (size independent of the batch)
+    for (int in_sz : {1024, 512}) {                       // slabs of the four-job GRU weight-gradient launch (size independent of the batch)
         int t_, kc_, ns_;
         size_t need;
-        tn_x6_plan(d.B * d.S, in_sz, &t_, &kc_, &ns_, &need);
+        tn_dw_plan(d.B * d.S, in_sz, &t_, &kc_, &ns_, &need);
         if (need > slab) slab = need;
         if (dx_splitk((int)(d.B * d.S), in_sz) && (size_t)2 * d.B * d.S * in_sz > slab) slab = (size_t)2 * d.B * d.S * in_sz;
     }
@@ -143,7 +135,7 @@ void tws_sizes(const TDims& d, size_t* n) {           // element counts (floats)
     for (int in_sz : {1024, 512}) {
         int t_, kc_, ns_;
         size_t need;
-        tn_x6_plan(d.B * d.S, in_sz, &t_, &kc_, &ns_, &need);
+        tn_dw_plan(d.B * d.S, in_sz, &t_, &kc_, &ns_, &need);
         if (need > n[TB_SLAB2]) n[TB_SLAB2] = need;
     }
 }
@@ -158,11 +150,8 @@ size_t tws_layout(const TDims& d, size_t* off) {
     return pos;
 }
 
-
-#define KCHECK() SIR_HIP_TRY(hipGetLastError())
-
 struct TPtrs {
-    float *a1, *z2, *a2, *z3, *x0, *gi, *g0, *g1, *y0, *y0d, *y1, *ctx, *bn, *bnb, *wp2, *wp3, *wht, *wr4, *wp2t, *wp3t;
+    float *a1, *z2, *a2, *z3, *x0, *gi, *g0, *g1, *y0, *y0d, *y1, *ctx, *bn, *bnb, *wht, *wr4;
     float *dgi1, *dgh1, *slab2;
     float *dy1, *dy0, *dgi, *dgh, *dx0, *dz3, *da2, *dz2, *da1, *small, *slab;
     float2* stats;
@@ -178,8 +167,7 @@ TPtrs carve(void* ws, const size_t* off) {
     p.g0 = (float*)(b + off[TB_G0]); p.g1 = (float*)(b + off[TB_G1]); p.y0 = (float*)(b + off[TB_Y0]);
     p.y0d = (float*)(b + off[TB_Y0D]); p.y1 = (float*)(b + off[TB_Y1]); p.ctx = (float*)(b + off[TB_CTX]);
     p.bn = (float*)(b + off[TB_BN]); p.bnb = (float*)(b + off[TB_BNB]); p.stats = (float2*)(b + off[TB_STATS]);
-    p.wp2 = (float*)(b + off[TB_WP2]); p.wp3 = (float*)(b + off[TB_WP3]); p.wht = (float*)(b + off[TB_WHT]);
-    p.wr4 = (float*)(b + off[TB_WR4]); p.wp2t = (float*)(b + off[TB_WP2T]); p.wp3t = (float*)(b + off[TB_WP3T]);
+    p.wht = (float*)(b + off[TB_WHT]); p.wr4 = (float*)(b + off[TB_WR4]);
     p.dy1 = (float*)(b + off[TB_DY1]); p.dy0 = (float*)(b + off[TB_DY0]); p.dgi = (float*)(b + off[TB_DGI]);
     p.dgh = (float*)(b + off[TB_DGH]); p.dx0 = (float*)(b + off[TB_DX0]); p.dz3 = (float*)(b + off[TB_DZ3]);
     p.da2 = (float*)(b + off[TB_DA2]); p.dz2 = (float*)(b + off[TB_DZ2]); p.da1 = (float*)(b + off[TB_DA1]);
@@ -224,6 +212,52 @@ inline int grid_for(size_t n, int per_block = 256, int cap = 8192) {
     return (int)(g > (size_t)cap ? cap : (g < 1 ? 1 : g));
 }
 
+// Weight gradient of a conv stage (CIN -> COUT forward channels, H x W map) into dw, on stream st: the Winograd kernel
+// (16 products per tile and channel pair instead of 36, wgrad_wino_f16x3_kernel.h) + strip sum + G^T . G, or the nine-tap fallback,
+// one slab per image, + its two-pass reduce
+template <int CIN, int COUT>
+int conv_wgrad(sir_handle* h, hipStream_t st, bool wino, int B, int H, int W, const float* dz, const float* a, float* slab, float* dw, float unscale) {
+    if (wino) {
+        using Cfg = WgwCfg<CIN, COUT>;
+        const int strips = wgrad_wino_strips(B, H, W, Cfg::TPS, Cfg::groups, h->num_cus);
+        SIR_TRY(sir_lds_opt_in(h, (const void*)conv_wgrad_wino_f16x3_kernel<CIN, COUT>, (int)Cfg::lds_bytes));
+        hipLaunchKernelGGL((conv_wgrad_wino_f16x3_kernel<CIN, COUT>), dim3(Cfg::groups * strips), dim3(WGW_THREADS), Cfg::lds_bytes, st, dz, a, slab, B, H, W);
+        float* part = slab + (size_t)strips * 16 * COUT * CIN;
+        hipLaunchKernelGGL(wgrad_wino_sum_kernel, dim3((16 * COUT * CIN / 4 + 255) / 256), dim3(256), 0, st, (const float*)slab, strips, 16 * COUT * CIN / 4, part);
+        hipLaunchKernelGGL(wgrad_wino_finish_kernel, dim3((COUT * CIN + 255) / 256), dim3(256), 0, st, (const float*)part, CIN, COUT, dw, unscale);
+        return SIR_OK;
+    }
+    const size_t ldsx = wgrad_x6_lds_bytes(CIN, COUT, W);
+    if (ldsx > 160 * 1024 || W > wgrad_x6_max_w(COUT)) { sir_set_error("sir_model_train_bwd: t_frames too large for the weight-gradient tile"); return SIR_EUNSUPPORTED; }
+    SIR_TRY(sir_lds_opt_in(h, (const void*)conv_wgrad_bf16x6_kernel<CIN, COUT>, 160 * 1024));
+    // one workgroup and one slab per image (H rows; its four k-split waves add up in LDS)
+    hipLaunchKernelGGL((conv_wgrad_bf16x6_kernel<CIN, COUT>), dim3(B), dim3(512), ldsx, st, dz, a, slab, H, W, H);
+    float* part = slab + (size_t)B * 9 * COUT * CIN;
+    hipLaunchKernelGGL(wgrad_reduce_partial_kernel, dim3((9 * COUT * CIN / 4 + 255) / 256, WGR_PARTS), dim3(256), 0, st, (const float*)slab, B, 9 * COUT * CIN / 4, part);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((9 * COUT * CIN + 255) / 256), dim3(256), 0, st, (const float*)part, WGR_PARTS, CIN, COUT, dw, unscale);
+    return SIR_OK;
+}
+
+// Data gradient of a conv stage = a CIN -> COUT convolution (forward COUT -> CIN) with the flipped / transposed taps, raw output: the
+// Winograd kernel on the weights PREP_CONV_WT_WINO_F16X3 built, or the stage's fallback on the form train_prep_kernel built for it
+// (conv3: first-generation Winograd, blocks of 8 x 4 tiles for the 16-row map; conv2: direct)
+template <int CIN, int COUT>
+int conv_dgrad(sir_handle* h, hipStream_t st, bool wino, const Wino2Geo& geo, const float* dz, const unsigned short* wt, float* da) {
+    static_assert((CIN == 128 && COUT == 64) || (CIN == 64 && COUT == 32), "conv3 or conv2");
+    const int H = geo.H, W = geo.W, B = geo.B;
+    if (wino) {
+        SIR_TRY(sir_lds_opt_in(h, (const void*)conv3x3_wino2_f16x3_kernel<CIN, COUT, 3, 0, 3>, W2_LDS_BYTES));
+        SIR_HIP_TRY((launch_conv_wino2<CIN, COUT, 3>(st, geo, dz, wt, (const float*)nullptr, (const float*)nullptr, da, (float2*)nullptr, h->zero_page, h->num_cus)));
+    } else if constexpr (CIN == 128) {
+        hipLaunchKernelGGL((conv3x3_wino_bf16x6_kernel<128, 64, 2, 3, 1, 0, 4>), dim3(((W + 1) / 2 + 3) / 4, 1, B), dim3(256), WINO_LDS_BYTES, st,
+                           dz, wt, (const float*)nullptr, (const float*)nullptr, da, H, W, H / 2, W / 2, (float2*)nullptr);
+    } else {
+        hipLaunchKernelGGL((conv3x3_bf16x6_ns_kernel<64, 32, 4, 2, 2, 0, 4>), dim3((W + 7) / 8, 1, B), dim3(256), conv_ns_lds_bytes(4, 2), st,
+                           dz, wt, (const float*)nullptr, (const float*)nullptr, da, H, W, H / 2, W / 2, (float2*)nullptr);
+    }
+    return SIR_OK;
+}
+
 }  // namespace
 
 size_t sir_train_workspace_bytes_impl(int batch, int t_frames) {
@@ -258,43 +292,43 @@ extern "C" int sir_model_train_fwd(sir_handle* h, const sir_model_weights* w, fl
     const int B = d.B, S = d.S, T = d.T;
     float *scale = p.bn, *shift = p.bn + 224, *smean = p.bn + 448, *sinv = p.bn + 672;
 
-    // conv2 / conv3 forward and both data gradients run on the producer / consumer Winograd kernel (conv_wino2_bf16x6_kernel.h);
-    // shapes it does not cover keep the first-generation / direct kernels.  The forward needs both maps to fit.
-    Wino2Geo geo2, geo3;
-    const bool w2 = sir_conv_stage_fits(2, wino2_geo(B, 32, d.wp1, 64, &geo2)) && sir_conv_stage_fits(3, wino2_geo(B, 16, d.wp2, 128, &geo3));
+    // conv2 / conv3 forward and both data gradients run on the producer / consumer Winograd kernel (conv_wino2_f16x3_kernel.h);
+    // shapes it does not cover keep the first-generation / direct kernels (the plan: model_shape.h).
+    const SirConvPlan& cp = d.conv;
+    const bool w2 = cp.fwd_wino;
     {   // all weight re-layouts of this step, the backward's included (the weights do not change before it runs)
         SirProfScope prof(h, SIR_K_T_PREP, st);
         PrepJobs pj{};
         int nj = 0, blocks = 0;
-        auto add = [&](int kind, const float* src, void* dst, int a, int b, int nblk) {
+        auto add = [&](PrepKind kind, const float* src, void* dst, int a, int b, int nblk) {
             pj.kind[nj] = kind; pj.src[nj] = src; pj.dst[nj] = dst; pj.a[nj] = a; pj.b[nj] = b; pj.block0[nj] = blocks;
             blocks += nblk; ++nj;
         };
         pj.status = h->status;
         // (f16x3 planes for the second-generation Winograd kernel, bf16x3 planes for the first-generation / direct fallbacks)
-        add(w2 ? 6 : 4, w->conv_w[1], p.wcb2, 32, 64, (32 * 16 * 64 + 255) / 256);       // conv2 forward: Winograd frequencies
-        add(w2 ? 6 : 4, w->conv_w[2], p.wcb3, 64, 128, (64 * 16 * 128 + 255) / 256);     // conv3 forward: Winograd frequencies
-        if (!w2) add(1, w->conv_w[2], p.wcb3d, 64, 128, (64 * 9 * 128 + 255) / 256);
+        add(w2 ? PREP_CONV_W_WINO_F16X3 : PREP_CONV_W_WINO_BF16X3, w->conv_w[1], p.wcb2, 32, 64, (32 * 16 * 64 + 255) / 256);       // conv2 forward: Winograd frequencies
+        add(w2 ? PREP_CONV_W_WINO_F16X3 : PREP_CONV_W_WINO_BF16X3, w->conv_w[2], p.wcb3, 64, 128, (64 * 16 * 128 + 255) / 256);     // conv3 forward: Winograd frequencies
+        if (!w2) add(PREP_CONV_W_BF16X3, w->conv_w[2], p.wcb3d, 64, 128, (64 * 9 * 128 + 255) / 256);
         // conv2 data gradient (64 -> 32): the second-generation Winograd kernel (its transform feeds only 32 outputs -- on bf16x6 that
         // lost to the direct kernel, on f16x3 with half the matrix products it wins: profiles/r04/bench_conv_f16x3.txt), else direct
-        if (dgrad2_wino(d)) add(7, w->conv_w[1], p.wcb2t, 32, 64, (64 * 16 * 32 + 255) / 256);
-        else add(2, w->conv_w[1], p.wcb2t, 32, 64, (32 * 9 * 64 + 255) / 256);
+        if (cp.dgrad2_wino) add(PREP_CONV_WT_WINO_F16X3, w->conv_w[1], p.wcb2t, 32, 64, (64 * 16 * 32 + 255) / 256);
+        else add(PREP_CONV_WT_BF16X3, w->conv_w[1], p.wcb2t, 32, 64, (32 * 9 * 64 + 255) / 256);
         // conv3 data gradient: Winograd frequencies of the flipped taps
-        add(dgrad3_wino(d) ? 7 : 5, w->conv_w[2], p.wcb3t, 64, 128, (128 * 16 * 64 + 255) / 256);
+        add(cp.dgrad3_wino ? PREP_CONV_WT_WINO_F16X3 : PREP_CONV_WT_WINO_BF16X3, w->conv_w[2], p.wcb3t, 64, 128, (128 * 16 * 64 + 255) / 256);
         for (int dir = 0; dir < 2; ++dir) {
-            add(0, w->gru_w_ih[dir], p.wsl0 + (size_t)dir * 2 * 768 * 1024, 1024, 768, 384);
-            add(0, w->gru_w_ih[2 + dir], p.wsl1 + (size_t)dir * 2 * 768 * 512, 512, 768, 192);
+            add(PREP_SPLIT2H, w->gru_w_ih[dir], p.wsl0 + (size_t)dir * 2 * 768 * 1024, 1024, 768, 384);
+            add(PREP_SPLIT2H, w->gru_w_ih[2 + dir], p.wsl1 + (size_t)dir * 2 * 768 * 512, 512, 768, 192);
         }
         for (int i = 0; i < 4; ++i) {                        // W_hh (layer i / 2, direction i % 2) as the recurrences' resident fragments
-            add(8, w->gru_w_hh[i], (char*)p.wht + (size_t)i * GRU_FRAG_BYTES, 0, 0, GQ_FRAG_THREADS / 256);
-            add(9, w->gru_w_hh[i], (char*)p.wr4 + (size_t)i * GRU_FRAG_BYTES, 0, 0, BQ_FRAG_THREADS / 256);
+            add(PREP_WHH_QUAD, w->gru_w_hh[i], (char*)p.wht + (size_t)i * GRU_FRAG_BYTES, 0, 0, GQ_FRAG_THREADS / 256);
+            add(PREP_WHH_BWD_QUAD, w->gru_w_hh[i], (char*)p.wr4 + (size_t)i * GRU_FRAG_BYTES, 0, 0, BQ_FRAG_THREADS / 256);
         }
         pj.block0[nj] = blocks;
         pj.njobs = nj;
         static_assert(PREP_MAX_JOBS >= 18, "job table");
         hipLaunchKernelGGL(train_prep_kernel, dim3(blocks), dim3(256), 0, st, pj);
     }
-    KCHECK();
+    SIR_KCHECK();
 
     // conv1 block: statistics pass (recompute), finalize, then the fused conv+BN+ReLU+pool pass
     {
@@ -315,12 +349,7 @@ extern "C" int sir_model_train_fwd(sir_handle* h, const sir_model_weights* w, fl
     // conv2 block: raw conv + partial statistics on MFMA, finalize, BN+ReLU+pool
     {
         { SirProfScope prof(h, SIR_K_T_CONV2, st);
-        if (w2)
-            SIR_HIP_TRY((launch_conv_wino2<32, 64, 2>(st, &h->attr_wino2[2], (const float*)p.a1, (const unsigned short*)p.wcb2, (const float*)nullptr,
-                                                    (const float*)nullptr, p.z2, B, 32, d.wp1, p.stats, h->zero_page, h->num_cus)));
-        else
-            hipLaunchKernelGGL((conv3x3_wino_bf16x6_kernel<32, 64, 2>), dim3(d.c2wx, 1, B), dim3(256), WINO_LDS_BYTES, st, (const float*)p.a1,
-                               (const unsigned short*)p.wcb2, (const float*)nullptr, (const float*)nullptr, p.z2, 32, d.wp1, 16, d.wp2, p.stats);
+        SIR_TRY((conv_fwd<32, 64, 2>(h, st, w2, cp.geo2, B, p.a1, p.wcb2, nullptr, nullptr, nullptr, p.z2, p.stats)));
         }
         SirProfScope prof(h, SIR_K_T_BN2, st);
         hipLaunchKernelGGL(bn_finalize_kernel, dim3(64), dim3(256), 0, st, (const float2*)p.stats, w2 ? (int)wino2_stat_blocks(B, 32, d.wp1, h->num_cus) : d.c2wx * B, 64,
@@ -331,12 +360,7 @@ extern "C" int sir_model_train_fwd(sir_handle* h, const sir_model_weights* w, fl
     }
     {
         { SirProfScope prof(h, SIR_K_T_CONV3, st);
-        if (w2)
-            SIR_HIP_TRY((launch_conv_wino2<64, 128, 2>(st, &h->attr_wino2[3], (const float*)p.a2, (const unsigned short*)p.wcb3, (const float*)nullptr,
-                                                     (const float*)nullptr, p.z3, B, 16, d.wp2, p.stats, h->zero_page, h->num_cus)));
-        else
-            hipLaunchKernelGGL((conv3x3_bf16x6_ns_kernel<64, 128, 2, 2, 2, 0, 2, 1, 1>), dim3(d.c3fx, 1, B), dim3(256), conv_ns_lds_bytes(2, 2, 2), st, (const float*)p.a2,
-                               (const unsigned short*)p.wcb3d, (const float*)nullptr, (const float*)nullptr, p.z3, 16, d.wp2, 8, d.wp3, p.stats);
+        SIR_TRY((conv_fwd<64, 128, 2>(h, st, w2, cp.geo3, B, p.a2, p.wcb3, p.wcb3d, nullptr, nullptr, p.z3, p.stats)));
         }
         SirProfScope prof(h, SIR_K_T_BN3, st);
         hipLaunchKernelGGL(bn_finalize_kernel, dim3(128), dim3(256), 0, st, (const float2*)p.stats, w2 ? (int)wino2_stat_blocks(B, 16, d.wp2, h->num_cus) : d.c3fx * B, 128,
@@ -345,19 +369,16 @@ extern "C" int sir_model_train_fwd(sir_handle* h, const sir_model_weights* w, fl
         hipLaunchKernelGGL(bn_relu_pool_kernel<true>, dim3(grid_for((size_t)B * 8 * d.wp3 * 32)), dim3(256), 0, st, p.z3,
                            scale + 96, shift + 96, p.x0, B, 16, d.wp2, 128, 8, d.wp3);
     }
-    KCHECK();
+    SIR_KCHECK();
 
     const int M = B * S;
     { SirProfScope prof(h, SIR_K_T_GEMM_IH0, st);
     hipLaunchKernelGGL(split2h_kernel, dim3(2048), dim3(256), 0, st, (const float*)p.x0, 1024, p.xs, (size_t)M, 1024);
-    SIR_HIP_TRY(launch_gemm_nt_f16x3(h, st, (const unsigned short*)p.xs, (const unsigned short*)p.wsl0,
+    SIR_TRY(launch_gemm_nt_f16x3(h, st, (const unsigned short*)p.xs, (const unsigned short*)p.wsl0,
                        (const unsigned short*)(p.wsl0 + (size_t)2 * 768 * 1024), w->gru_b_ih[0], w->gru_b_ih[1], p.gi, 1536, M, 768, 1024)); }
     { SirProfScope prof(h, SIR_K_T_GRU0, st);
-    if (sir_cluster_enter(h, st) != SIR_OK) return SIR_EHIP;
-    rc = sir_launch_gru_quad(h, st, true, p.gi, w->gru_w_hh[0], w->gru_w_hh[1], w->gru_b_hh[0], w->gru_b_hh[1], p.y0, B, S, p.g0, nullptr,
-                             (const char*)p.wht, (const char*)p.wht + GRU_FRAG_BYTES);
-    if (sir_cluster_leave(h, st) != SIR_OK) return SIR_EHIP; }
-    if (rc != SIR_OK) return rc;
+    SIR_TRY(sir_launch_gru_quad(h, st, true, p.gi, w->gru_w_hh[0], w->gru_w_hh[1], w->gru_b_hh[0], w->gru_b_hh[1], p.y0, B, S, p.g0, nullptr,
+                                (const char*)p.wht, (const char*)p.wht + GRU_FRAG_BYTES)); }
     const float* y0in = p.y0;
     { SirProfScope prof(h, SIR_K_T_GEMM_IH1, st);
     if (dropout_p > 0.0f) {                                   // dropout + the f16x2 planes of its output in one pass
@@ -367,18 +388,15 @@ extern "C" int sir_model_train_fwd(sir_handle* h, const sir_model_weights* w, fl
     } else {
         hipLaunchKernelGGL(split2h_kernel, dim3(2048), dim3(256), 0, st, y0in, 512, p.xs, (size_t)M, 512);
     }
-    SIR_HIP_TRY(launch_gemm_nt_f16x3(h, st, (const unsigned short*)p.xs, (const unsigned short*)p.wsl1,
+    SIR_TRY(launch_gemm_nt_f16x3(h, st, (const unsigned short*)p.xs, (const unsigned short*)p.wsl1,
                        (const unsigned short*)(p.wsl1 + (size_t)2 * 768 * 512), w->gru_b_ih[2], w->gru_b_ih[3], p.gi, 1536, M, 768, 512)); }
     { SirProfScope prof(h, SIR_K_T_GRU1, st);
-    if (sir_cluster_enter(h, st) != SIR_OK) return SIR_EHIP;
-    rc = sir_launch_gru_quad(h, st, true, p.gi, w->gru_w_hh[2], w->gru_w_hh[3], w->gru_b_hh[2], w->gru_b_hh[3], p.y1, B, S, p.g1, nullptr,
-                             (const char*)p.wht + 2 * GRU_FRAG_BYTES, (const char*)p.wht + 3 * GRU_FRAG_BYTES);
-    if (sir_cluster_leave(h, st) != SIR_OK) return SIR_EHIP; }
-    if (rc != SIR_OK) return rc;
+    SIR_TRY(sir_launch_gru_quad(h, st, true, p.gi, w->gru_w_hh[2], w->gru_w_hh[3], w->gru_b_hh[2], w->gru_b_hh[3], p.y1, B, S, p.g1, nullptr,
+                                (const char*)p.wht + 2 * GRU_FRAG_BYTES, (const char*)p.wht + 3 * GRU_FRAG_BYTES)); }
     SirProfScope prof_head(h, SIR_K_T_HEAD, st);
     hipLaunchKernelGGL(attention_pool_kernel, dim3(B), dim3(256), 0, st, p.y1, w->attn_w, w->attn_b, p.ctx, S, w->fc_w,
                        w->fc_b, w->num_classes, logits, (long long*)nullptr);
-    KCHECK();
+    SIR_KCHECK();
     return SIR_OK;
 }
 
@@ -393,7 +411,7 @@ extern "C" int sir_ce_loss(sir_handle* h, const float* logits, const int64_t* la
     else
         hipLaunchKernelGGL(ce_loss_kernel<64>, dim3(1), dim3(256), 0, (hipStream_t)stream_, logits, (const long long*)labels, batch,
                            num_classes, loss, dlogits, grad_scale, h->status);
-    KCHECK();
+    SIR_KCHECK();
     return SIR_OK;
 }
 
@@ -422,6 +440,7 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
     const int B = d.B, S = d.S, T = d.T, C = w->num_classes, M = B * S;
     float *scale = p.bn, *shift = p.bn + 224, *smean = p.bn + 448, *sinv = p.bn + 672;
     float *mdy = p.bnb, *mdyx = p.bnb + 224;
+    const SirConvPlan& cp = d.conv;
     float* daw_part = p.small;
     float* dab_part = p.small + (size_t)B * 512;
     float* c1part = p.small + (size_t)B * 512 + B + 64;
@@ -441,12 +460,6 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
     if (!h->bwd_side) {                                      // (first use: the only allocating step, as for the exchange buffers)
         SIR_HIP_TRY(hipStreamCreateWithFlags(&h->bwd_side, hipStreamNonBlocking));
         for (auto& e : h->bwd_ev) SIR_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    if (!h->attr_tn) {
-        SIR_HIP_TRY(hipFuncSetAttribute((const void*)gemm_tn2_bf16x6_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tn2_lds_bytes(true)));
-        SIR_HIP_TRY(hipFuncSetAttribute((const void*)gemm_tn2_bf16x6_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tn2_lds_bytes(false)));
-        SIR_HIP_TRY(hipFuncSetAttribute((const void*)gemm_tn2_bf16x6_kernel<false, 0, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tn2_lds_bytes(false, 64)));
-        h->attr_tn = true;
     }
     // (while every kernel is being timed -- sir_profile_enable mode 1 -- the backward stays on one stream: per-kernel times of overlapped
     // launches would say nothing about the kernels)
@@ -484,7 +497,7 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
         jb.tile0[4] = tiles;
         int tiles_chk, kchunk, nsplit;
         size_t need;
-        tn_x6_plan(M, in_sz, &tiles_chk, &kchunk, &nsplit, &need);
+        tn_dw_plan(M, in_sz, &tiles_chk, &kchunk, &nsplit, &need);
         size_t pos = 0;
         for (int j = 0; j < 4; ++j) {
             jb.slab[j] = (two ? p.slab2 : p.slab) + pos;
@@ -492,7 +505,8 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
             pos += sizes[j] * nsplit;
         }
         // (f16x3: the gate gradients carry the loss scale)
-        hipLaunchKernelGGL(gemm_tn2_bf16x6_kernel<true>, dim3(tiles, nsplit), dim3(TN2_THREADS), tn2_lds_bytes(true), s_, jb, 768, M, kchunk, S);
+        SIR_TRY(sir_lds_opt_in(h, (const void*)gemm_tn2_f16x3_kernel<true>, (int)tn2_lds_bytes(true)));
+        hipLaunchKernelGGL(gemm_tn2_f16x3_kernel<true>, dim3(tiles, nsplit), dim3(TN2_THREADS), tn2_lds_bytes(true), s_, jb, 768, M, kchunk, S);
         SlabJobs sj{};
         for (int j = 0; j < 4; ++j) { sj.src[j] = jb.slab[j]; sj.out[j] = outs[j]; sj.n[j] = sizes[j]; }
         hipLaunchKernelGGL(slab_reduce_jobs_kernel, dim3(grid_for(sizes[0]), 4), dim3(256), 0, s_, sj, nsplit, unscale);
@@ -505,7 +519,7 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
     hipLaunchKernelGGL(head_bwd_kernel, dim3(B + 2 * C), dim3(256), 0, st, dlogits, w->fc_w, (const float*)p.y1, w->attn_w, w->attn_b,
                        (const float*)p.ctx, p.dy1, daw_part, dab_part, g->fc_w, g->fc_b, B, S, C, gscale);
     hipLaunchKernelGGL(head_colsum_kernel, dim3(9), dim3(256), 0, st, (const float*)daw_part, (const float*)dab_part, B, g->attn_w, g->attn_b); }
-    KCHECK();
+    SIR_KCHECK();
 
     // ---- GRU layers, top down ----------------------------------------------------------------
     for (int layer = 1; layer >= 0; --layer) {
@@ -516,12 +530,9 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
         float* dgh_l = layer ? p.dgh1 : p.dgh;
         const int in_sz = layer ? 512 : 1024;
         { SirProfScope prof(h, layer ? SIR_K_B_GRU1 : SIR_K_B_GRU0, st);
-        if (sir_cluster_enter(h, st) != SIR_OK) return SIR_EHIP;
-        rc = sir_launch_gru_bwd_quad(h, st, dy, gates, yout, w->gru_w_hh[2 * layer], w->gru_w_hh[2 * layer + 1], dgi_l, dgh_l, bsum_i, bsum_h,
-                                     B, S, (const char*)p.wr4 + (size_t)(2 * layer) * GRU_FRAG_BYTES,
-                                     (const char*)p.wr4 + (size_t)(2 * layer + 1) * GRU_FRAG_BYTES);
-        if (rc != SIR_OK) return rc;
-        if (sir_cluster_leave(h, st) != SIR_OK) return SIR_EHIP;
+        SIR_TRY(sir_launch_gru_bwd_quad(h, st, dy, gates, yout, w->gru_w_hh[2 * layer], w->gru_w_hh[2 * layer + 1], dgi_l, dgh_l, bsum_i, bsum_h,
+                                        B, S, (const char*)p.wr4 + (size_t)(2 * layer) * GRU_FRAG_BYTES,
+                                        (const char*)p.wr4 + (size_t)(2 * layer + 1) * GRU_FRAG_BYTES));
         // bias gradients first: bsum_* alias the slab area used below
         hipLaunchKernelGGL(gru_bias_colsum_kernel, dim3(24, 2), dim3(256), 0, st, (const float*)bsum_i, (const float*)bsum_h, B,
                            g->gru_b_ih[2 * layer], g->gru_b_ih[2 * layer + 1], g->gru_b_hh[2 * layer], g->gru_b_hh[2 * layer + 1], unscale); }
@@ -536,9 +547,8 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
             if (layer == 1)
                 hipLaunchKernelGGL(cache_touch_kernel, dim3(256), dim3(256), 0, side, (const float4*)p.g0, (size_t)M * 2048 / 4, (const float4*)p.y0,
                                    (size_t)M * 512 / 4, p.small);
-            rc = launch_dw(layer, side);
-            if (rc != SIR_OK) return rc;
-        } else { rc = launch_dw(layer, st); if (rc != SIR_OK) return rc; }
+            SIR_TRY(launch_dw(layer, side));
+        } else { SIR_TRY(launch_dw(layer, st)); }
         // gradient wrt the layer input: dgi [M][1536] x [W_ih; W_ih_reverse] [1536][in]
         SirProfScope prof(h, layer ? SIR_K_B_DX1 : SIR_K_B_DX0, st);
         float* dxin = layer ? p.dy0 : p.dx0;
@@ -558,20 +568,23 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
                 jn.drop_p = 0.0f;                                // (the dropout mask is applied by the add)
                 jn.slab[0] = p.slab; jn.slab_stride[0] = (size_t)M * in_sz;
                 jn.tile0[1] = ntiles;
-                hipLaunchKernelGGL(gemm_tn2_bf16x6_kernel<false>, dim3(ntiles, 2), dim3(TN2_THREADS), tn2_lds_bytes(false), st, jn, M, 1536, 768, 1);
+                SIR_TRY(sir_lds_opt_in(h, (const void*)gemm_tn2_f16x3_kernel<false>, (int)tn2_lds_bytes(false)));
+                hipLaunchKernelGGL(gemm_tn2_f16x3_kernel<false>, dim3(ntiles, 2), dim3(TN2_THREADS), tn2_lds_bytes(false), st, jn, M, 1536, 768, 1);
                 const bool drop = layer == 1 && dropout_p > 0.0f;
                 hipLaunchKernelGGL(dx_halves_add_kernel, dim3(grid_for((size_t)M * in_sz / 4)), dim3(256), 0, st, (const float*)p.slab, (size_t)M * in_sz / 4,
                                    dxin, drop ? dropout_p : 0.0f, (unsigned long long)dropout_seed);
             } else if (ntiles < 160) {                       // too few 128-row tiles to fill the CUs: 64-row tiles
                 ntiles = ((M + 63) / 64) * ntn;
                 jn.tile0[1] = ntiles;
-                hipLaunchKernelGGL((gemm_tn2_bf16x6_kernel<false, 0, 64>), dim3(ntiles, 1), dim3(TN2_THREADS), tn2_lds_bytes(false, 64), st, jn, M, 1536, 1536, 1);
+                SIR_TRY(sir_lds_opt_in(h, (const void*)gemm_tn2_f16x3_kernel<false, 0, 64>, (int)tn2_lds_bytes(false, 64)));
+                hipLaunchKernelGGL((gemm_tn2_f16x3_kernel<false, 0, 64>), dim3(ntiles, 1), dim3(TN2_THREADS), tn2_lds_bytes(false, 64), st, jn, M, 1536, 1536, 1);
             } else {
                 jn.tile0[1] = ntiles;
-                hipLaunchKernelGGL(gemm_tn2_bf16x6_kernel<false>, dim3(ntiles, 1), dim3(TN2_THREADS), tn2_lds_bytes(false), st, jn, M, 1536, 1536, 1);
+                SIR_TRY(sir_lds_opt_in(h, (const void*)gemm_tn2_f16x3_kernel<false>, (int)tn2_lds_bytes(false)));
+                hipLaunchKernelGGL(gemm_tn2_f16x3_kernel<false>, dim3(ntiles, 1), dim3(TN2_THREADS), tn2_lds_bytes(false), st, jn, M, 1536, 1536, 1);
             }
         }
-        KCHECK();
+        SIR_KCHECK();
     }
     }
     if (two) {                                         // join: the GRU gradients are final on the caller's stream (the conv chain
@@ -585,13 +598,6 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
     }
 
     // ---- conv3 block -------------------------------------------------------------------------
-    if (!h->attr_wgrad) {
-        SIR_HIP_TRY(hipFuncSetAttribute((const void*)conv_wgrad_bf16x6_kernel<64, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        SIR_HIP_TRY(hipFuncSetAttribute((const void*)conv_wgrad_bf16x6_kernel<32, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        SIR_HIP_TRY(hipFuncSetAttribute((const void*)conv_wgrad_wino_bf16x6_kernel<64, 128>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WgwCfg<64, 128>::lds_bytes));
-        SIR_HIP_TRY(hipFuncSetAttribute((const void*)conv_wgrad_wino_bf16x6_kernel<32, 64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WgwCfg<32, 64>::lds_bytes));
-        h->attr_wgrad = true;
-    }
     {
         // BatchNorm backward sums from the POOLED activations x0 (GRU layout) and their gradient -- dy = da wherever a > 0 and
         // xhat at the routed maximum is (a - beta) / gamma -- instead of the four times larger raw conv output z3
@@ -613,42 +619,15 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
         }
         {
             SirProfScope prof(h, SIR_K_B_WGRAD3, side);
-            if (sir_conv_stage_fits(3, (size_t)B * 16 * d.wp2 * 128 * 4 < ((size_t)1 << 31))) {      // (32-bit buffer offsets)
-                // Winograd form: 16 products per tile and channel pair instead of 36 (wgrad_wino_bf16x6_kernel.h)
-                using Cfg3 = WgwCfg<64, 128>;
-                const int strips = wgrad_wino_strips(B, 16, d.wp2, Cfg3::TPS, Cfg3::groups, h->num_cus);
-                hipLaunchKernelGGL((conv_wgrad_wino_bf16x6_kernel<64, 128>), dim3(Cfg3::groups * strips), dim3(WGW_THREADS), Cfg3::lds_bytes, side,
-                                   (const float*)p.dz3, (const float*)p.a2, p.slab, B, 16, d.wp2);
-                float* part = p.slab + (size_t)strips * 16 * 128 * 64;
-                hipLaunchKernelGGL(wgrad_wino_sum_kernel, dim3((16 * 128 * 64 / 4 + 255) / 256), dim3(256), 0, side, (const float*)p.slab, strips,
-                                   16 * 128 * 64 / 4, part);
-                hipLaunchKernelGGL(wgrad_wino_finish_kernel, dim3((128 * 64 + 255) / 256), dim3(256), 0, side, (const float*)part, 64, 128, g->conv_w[2], unscale);
-            } else {
-            const size_t ldsx = wgrad_x6_lds_bytes(64, 128, d.wp2);
-            if (ldsx > 160 * 1024 || d.wp2 > wgrad_x6_max_w(128)) { sir_set_error("sir_model_train_bwd: t_frames too large for the weight-gradient tile"); return SIR_EUNSUPPORTED; }
-            const int nslab3 = d.wg3_blocks;                  // one slab per workgroup
-            hipLaunchKernelGGL((conv_wgrad_bf16x6_kernel<64, 128>), dim3(d.wg3_blocks), dim3(512), ldsx, side, (const float*)p.dz3,
-                               (const float*)p.a2, p.slab, 16, d.wp2, d.wg3_rb);
-            float* part = p.slab + (size_t)nslab3 * 9 * 128 * 64;
-            hipLaunchKernelGGL(wgrad_reduce_partial_kernel, dim3((9 * 128 * 64 / 4 + 255) / 256, WGR_PARTS), dim3(256), 0, side,
-                               (const float*)p.slab, nslab3, 9 * 128 * 64 / 4, part);
-            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((9 * 128 * 64 + 255) / 256), dim3(256), 0, side, (const float*)part, WGR_PARTS, 64, 128,
-                               g->conv_w[2], unscale);
-            }
+            SIR_TRY((conv_wgrad<64, 128>(h, side, cp.wgrad3_wino, B, 16, d.wp2, p.dz3, p.a2, p.slab, g->conv_w[2], unscale)));
         }
         {
             // data gradient = a 128 -> 64 convolution with the flipped / transposed taps: the Winograd kernel (16 of 36 products), blocks
             // of 8 x 4 tiles for the 16-row map, raw output (train_prep_kernel of the forward built p.wcb3t)
             SirProfScope prof(h, SIR_K_B_DGRAD3, st);
-            if (dgrad3_wino(d))                                  // (dz3 carries the loss scale: inside fp16's range)
-                SIR_HIP_TRY((launch_conv_wino2<128, 64, 3>(st, &h->attr_wino2[4], (const float*)p.dz3, (const unsigned short*)p.wcb3t, (const float*)nullptr,
-                                                         (const float*)nullptr, p.da2, B, 16, d.wp2, (float2*)nullptr, h->zero_page, h->num_cus)));
-            else
-                hipLaunchKernelGGL((conv3x3_wino_bf16x6_kernel<128, 64, 2, 3, 1, 0, 4>), dim3(((d.wp2 + 1) / 2 + 3) / 4, 1, B), dim3(256), WINO_LDS_BYTES, st,
-                                   (const float*)p.dz3, (const unsigned short*)p.wcb3t, (const float*)nullptr, (const float*)nullptr, p.da2, 16, d.wp2,
-                                   8, d.wp3, (float2*)nullptr);
+            SIR_TRY((conv_dgrad<128, 64>(h, st, cp.dgrad3_wino, cp.geo3, p.dz3, p.wcb3t, p.da2)));      // (dz3 carries the loss scale: inside fp16's range)
         }
-        KCHECK();
+        SIR_KCHECK();
     }
     // ---- conv2 block -------------------------------------------------------------------------
     {
@@ -672,40 +651,14 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
         }
         {
             SirProfScope prof(h, SIR_K_B_WGRAD2, side);
-            if (sir_conv_stage_fits(2, (size_t)B * 32 * d.wp1 * 64 * 4 < ((size_t)1 << 31))) {
-                using Cfg2 = WgwCfg<32, 64>;
-                const int strips = wgrad_wino_strips(B, 32, d.wp1, Cfg2::TPS, Cfg2::groups, h->num_cus);
-                hipLaunchKernelGGL((conv_wgrad_wino_bf16x6_kernel<32, 64>), dim3(Cfg2::groups * strips), dim3(WGW_THREADS), Cfg2::lds_bytes, side,
-                                   (const float*)p.dz2, (const float*)p.a1, p.slab, B, 32, d.wp1);
-                float* part = p.slab + (size_t)strips * 16 * 64 * 32;
-                hipLaunchKernelGGL(wgrad_wino_sum_kernel, dim3((16 * 64 * 32 / 4 + 255) / 256), dim3(256), 0, side, (const float*)p.slab, strips,
-                                   16 * 64 * 32 / 4, part);
-                hipLaunchKernelGGL(wgrad_wino_finish_kernel, dim3((64 * 32 + 255) / 256), dim3(256), 0, side, (const float*)part, 32, 64, g->conv_w[1], unscale);
-            } else {
-            const size_t ldsx = wgrad_x6_lds_bytes(32, 64, d.wp1);
-            if (ldsx > 160 * 1024 || d.wp1 > wgrad_x6_max_w(64)) { sir_set_error("sir_model_train_bwd: t_frames too large for the weight-gradient tile"); return SIR_EUNSUPPORTED; }
-            const int nslab2 = d.wg2_blocks;                  // one slab per workgroup (its four k-split waves add up in LDS)
-            hipLaunchKernelGGL((conv_wgrad_bf16x6_kernel<32, 64>), dim3(d.wg2_blocks), dim3(512), ldsx, side, (const float*)p.dz2,
-                               (const float*)p.a1, p.slab, 32, d.wp1, d.wg2_rb);
-            float* part = p.slab + (size_t)nslab2 * 9 * 64 * 32;
-            hipLaunchKernelGGL(wgrad_reduce_partial_kernel, dim3((9 * 64 * 32 / 4 + 255) / 256, WGR_PARTS), dim3(256), 0, side,
-                               (const float*)p.slab, nslab2, 9 * 64 * 32 / 4, part);
-            hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((9 * 64 * 32 + 255) / 256), dim3(256), 0, side, (const float*)part, WGR_PARTS, 32, 64,
-                               g->conv_w[1], unscale);
-            }
+            SIR_TRY((conv_wgrad<32, 64>(h, side, cp.wgrad2_wino, B, 32, d.wp1, p.dz2, p.a1, p.slab, g->conv_w[1], unscale)));
         }
         if (two) SIR_HIP_TRY(hipEventRecord(h->bwd_ev[3], side));     // (the side stream's last launch)
         {
             SirProfScope prof(h, SIR_K_B_DGRAD2, st);
-            if (dgrad2_wino(d))
-                SIR_HIP_TRY((launch_conv_wino2<64, 32, 3>(st, &h->attr_wino2[5], (const float*)p.dz2, (const unsigned short*)p.wcb2t, (const float*)nullptr,
-                                                                    (const float*)nullptr, p.da1, B, 32, d.wp1, (float2*)nullptr, h->zero_page, h->num_cus)));
-            else
-            hipLaunchKernelGGL((conv3x3_bf16x6_ns_kernel<64, 32, 4, 2, 2, 0, 4>), dim3(d.c2gx, 1, B), dim3(256), conv_ns_lds_bytes(4, 2), st,
-                               (const float*)p.dz2, (const unsigned short*)p.wcb2t, (const float*)nullptr, (const float*)nullptr, p.da1, 32, d.wp1,
-                               16, d.wp2, (float2*)nullptr);
+            SIR_TRY((conv_dgrad<64, 32>(h, st, cp.dgrad2_wino, cp.geo2, p.dz2, p.wcb2t, p.da1)));
         }
-        KCHECK();
+        SIR_KCHECK();
     }
     // ---- conv1 block ------------------------------------------------------------------------
     {
@@ -723,7 +676,7 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
         hipLaunchKernelGGL(colsum_kernel, dim3((352 + 63) / 64), dim3(256), 0, st, (const float*)c1tmp, 128, 352, 352, c1tot);
         hipLaunchKernelGGL(conv1_bwd_finalize_kernel, dim3(1), dim3(320), 0, st, (const float*)c1tot, (const double*)p.c1m,
                            w->conv_w[0], scale, smean, sinv, (double)B * 64 * T, g->bn_w[0], g->bn_b[0], g->conv_w[0], unscale);
-        KCHECK();
+        SIR_KCHECK();
     }
     if (two) SIR_HIP_TRY(hipStreamWaitEvent(st, h->bwd_ev[3], 0));   // join: every gradient is final on the caller's stream
     return SIR_OK;
@@ -747,6 +700,6 @@ extern "C" int sir_adam_step(sir_handle* h, int n_tensors, float* const* params,
     SirProfScope prof(h, SIR_K_ADAM, (hipStream_t)stream_);
     hipLaunchKernelGGL(adam_multi_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, ts, lr, beta1, beta2, eps, weight_decay,
                        (float)bc1, (float)sqrt(bc2));
-    KCHECK();
+    SIR_KCHECK();
     return SIR_OK;
 }

@@ -27,7 +27,7 @@ enum SirKernelId {
 };
 
 struct SirProfRec { int id; hipEvent_t e0, e1; };
-static inline size_t sir_align_up_sz(size_t x, size_t a) { return (x + a - 1) / a * a; }
+static inline size_t sir_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // polyphase resampling filter of one (orig_freq, new_freq) pair (frontend.hip), device tables
 struct sir_resample_table {
@@ -58,7 +58,6 @@ struct sir_handle {
     float* melw;        // compact filter weights: filter after filter, taps ascending in frequency (mel_nnz floats)
     int4* mel_desc;     // [64] per slot, filters sorted by tap count: {filter (-1 = unused), first FFT bin, taps, offset into melw}
     int mel_nnz;
-    bool feat_attr_set; // the feature kernel's dynamic-LDS opt-in has been made on this handle's device
     std::vector<sir_resample_table> resample_tables;   // built on first use of a rate pair
     // device word set to 1 by a GRU recurrence kernel whose inter-workgroup exchange timed out (its results are then
     // invalid); zeroed at creation, read and cleared by sir_check_status / sir_profile_collect
@@ -72,10 +71,9 @@ struct sir_handle {
     hipStream_t cluster_stream;        // stream of the latest cluster launch (compared, never dereferenced)
     bool cluster_pending, cluster_seen, cluster_multi;
     int cluster_run;                   // chained mode: launches in a row that came from cluster_stream
-    // hipFuncSetAttribute(MaxDynamicSharedMemorySize) latches, per handle = per device (a process-wide static would skip
-    // the second device of a process that drives several)
-    bool attr_gemm_v3, attr_gemm_gather, attr_gru_quad, attr_gru_bwd_quad, attr_tn, attr_wgrad;
-    bool attr_wino2[6];                // conv3x3_wino2_bf16x6_kernel instantiations (model_infer.hip: 0, 1; model_train.hip: 2 .. 5)
+    // kernels whose dynamic-LDS opt-in has been made (sir_lds_opt_in), per handle = per device (a process-wide static would
+    // skip the second device of a process that drives several)
+    std::vector<const void*> lds_opted;
     float* zero_page;                  // 4 KB of zeros: DMA source of the second-generation Winograd kernel's out-of-image pixels
     int num_cus;                       // persistent kernels launch one workgroup per CU
     // Exchange-granule buffers of the cluster kernels (GRU recurrences).  They are OWNED by the handle (hipMalloc), one per
@@ -118,7 +116,7 @@ static inline int sir_xbuf_acquire(sir_handle* h, hipStream_t st, int kind, size
     if (bytes > e->cap) {
         if (e->p && hipFree(e->p) != hipSuccess) { sir_set_error("exchange buffer: hipFree before growing failed"); return SIR_EHIP; }
         e->p = nullptr; e->cap = 0; e->bytes = 0;
-        const size_t cap = sir_align_up_sz(bytes, (size_t)1 << 20);
+        const size_t cap = sir_align_up(bytes, (size_t)1 << 20);
         if (hipMalloc(&e->p, cap) != hipSuccess) { e->p = nullptr; sir_set_error("exchange buffer: hipMalloc of %zu bytes failed", cap); return SIR_EHIP; }
         e->cap = cap;
     }
@@ -164,10 +162,6 @@ static inline int sir_cluster_leave(sir_handle* h, hipStream_t st) {
     return SIR_OK;
 }
 
-// conv stage `conv` (2 or 3) runs on its Winograd kernel (second-generation forward / data gradient, Winograd weight gradient) if
-// `shape_ok` -- else on the first-generation / direct fallback.  Test-only SIR_CONV_FALLBACK: 1 = conv2's stages do not fit, 2 = none do.
-bool sir_conv_stage_fits(int conv, bool shape_ok);
-
 int sir_check_hip(hipError_t e, const char* what);
 
 #define SIR_HIP_TRY(expr)                                   \
@@ -175,6 +169,22 @@ int sir_check_hip(hipError_t e, const char* what);
         int _rc = sir_check_hip((expr), #expr);             \
         if (_rc != SIR_OK) return _rc;                      \
     } while (0)
+#define SIR_KCHECK() SIR_HIP_TRY(hipGetLastError())
+#define SIR_TRY(expr)                                       \
+    do {                                                    \
+        int _rc = (expr);                                   \
+        if (_rc != SIR_OK) return _rc;                      \
+    } while (0)
+
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) for `kernel`, once per handle; called at the kernel's launch site.  A linear
+// search is enough: the host path launches <= ~20 kernels that need the opt-in.
+static inline int sir_lds_opt_in(sir_handle* h, const void* kernel, int bytes) {
+    for (const void* k : h->lds_opted)
+        if (k == kernel) return SIR_OK;
+    SIR_HIP_TRY(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    h->lds_opted.push_back(kernel);
+    return SIR_OK;
+}
 
 // RAII: records a HIP event pair on `st` around the launches issued while it is alive
 struct SirProfScope {
@@ -196,8 +206,6 @@ struct SirProfScope {
         h->prof_pending.push_back(SirProfRec{id, e0, e1});
     }
 };
-
-static inline size_t sir_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // model_train.hip
 size_t sir_train_workspace_bytes_impl(int batch, int t_frames);

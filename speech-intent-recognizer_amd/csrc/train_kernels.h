@@ -3,7 +3,7 @@
 #pragma once
 #include "model_kernels.h"
 #include "bf16x6_kernels.h"
-#include "conv_wino_bf16x6_kernel.h"
+#include "conv_wino2_f16x3_kernel.h"
 #include "gru_frag_prep.h"
 
 // ------------------------------------------------------------------------------------------
@@ -525,10 +525,19 @@ __device__ __forceinline__ void prep_whh_bwd_elem(const float* __restrict__ w, f
 }
 
 // Every per-step re-layout of the weights (they change with each optimizer step) in ONE launch: a dozen ~5 us launches
-// otherwise.  kind 0: split2h_rows (a = ld_in = K, b = rows), 1: prep_conv_w_bf16x3 (a = cin, b = cout),
-// 2: prep_conv_wT_bf16x3 (a = cin_f, b = cout_f), 3: prep_whh_bwd, 4: prep_conv_w_wino_bf16x3 (a = cin, b = cout),
-// 5: prep_conv_wT_wino_bf16x3 (a = cin_f, b = cout_f), 6 / 7: the f16x3 forms of 4 / 5 (conv_wino_bf16x6_kernel.h), 8 / 9: W_hh as
-// the resident fragments of the forward / backward cluster recurrence (gru_frag_prep.h).  Job j owns blocks [block0[j], block0[j+1]).
+// otherwise.  Job j owns blocks [block0[j], block0[j+1]).
+enum PrepKind {
+    PREP_SPLIT2H = 0,               // split2h_rows (a = ld_in = K, b = rows)
+    PREP_CONV_W_BF16X3 = 1,         // prep_conv_w_bf16x3 (a = cin, b = cout): nine taps, direct fallback
+    PREP_CONV_WT_BF16X3 = 2,        // prep_conv_wT_bf16x3 (a = cin_f, b = cout_f)
+    PREP_WHH_BWD = 3,               // prep_whh_bwd
+    PREP_CONV_W_WINO_BF16X3 = 4,    // prep_conv_w_wino_bf16x3 (a = cin, b = cout): first-generation Winograd fallback
+    PREP_CONV_WT_WINO_BF16X3 = 5,   // prep_conv_wT_wino_bf16x3 (a = cin_f, b = cout_f)
+    PREP_CONV_W_WINO_F16X3 = 6,     // the f16x3 forms of 4 / 5 (conv_wino2_f16x3_kernel.h)
+    PREP_CONV_WT_WINO_F16X3 = 7,
+    PREP_WHH_QUAD = 8,              // W_hh as the resident fragments of the forward / backward cluster recurrence (gru_frag_prep.h)
+    PREP_WHH_BWD_QUAD = 9
+};
 constexpr int PREP_MAX_JOBS = 20;
 struct PrepJobs {
     const float* src[PREP_MAX_JOBS];
@@ -545,15 +554,15 @@ static __global__ __launch_bounds__(256) void train_prep_kernel(PrepJobs jobs) {
     const int idx = lb * 256 + threadIdx.x;
     const float* __restrict__ src = jobs.src[j];
     switch (jobs.kind[j]) {
-        case 0: split2h_rows(src, jobs.a[j], (unsigned short*)jobs.dst[j], (size_t)jobs.b[j], jobs.a[j], (size_t)idx, (size_t)nb * 256); break;
-        case 1: prep_conv_w_bf16x3_elem(src, (unsigned short*)jobs.dst[j], jobs.a[j], jobs.b[j], idx); break;
-        case 2: prep_conv_wT_bf16x3_elem(src, (unsigned short*)jobs.dst[j], jobs.a[j], jobs.b[j], idx); break;
-        case 4: prep_conv_w_wino_bf16x3_elem(src, (unsigned short*)jobs.dst[j], jobs.a[j], jobs.b[j], idx); break;
-        case 5: prep_conv_wT_wino_bf16x3_elem(src, (unsigned short*)jobs.dst[j], jobs.a[j], jobs.b[j], idx); break;
-        case 6: prep_conv_w_wino_f16x3_elem(src, (unsigned short*)jobs.dst[j], jobs.a[j], jobs.b[j], idx, jobs.status); break;
-        case 7: prep_conv_wT_wino_f16x3_elem(src, (unsigned short*)jobs.dst[j], jobs.a[j], jobs.b[j], idx, jobs.status); break;
-        case 8: prep_whh_quad_elem(src, (uint4*)jobs.dst[j], idx); break;
-        case 9: prep_whh_bwd_quad_elem(src, (uint4*)jobs.dst[j], idx); break;
+        case PREP_SPLIT2H: split2h_rows(src, jobs.a[j], (unsigned short*)jobs.dst[j], (size_t)jobs.b[j], jobs.a[j], (size_t)idx, (size_t)nb * 256); break;
+        case PREP_CONV_W_BF16X3: prep_conv_w_bf16x3_elem(src, (unsigned short*)jobs.dst[j], jobs.a[j], jobs.b[j], idx); break;
+        case PREP_CONV_WT_BF16X3: prep_conv_wT_bf16x3_elem(src, (unsigned short*)jobs.dst[j], jobs.a[j], jobs.b[j], idx); break;
+        case PREP_CONV_W_WINO_BF16X3: prep_conv_w_wino_bf16x3_elem(src, (unsigned short*)jobs.dst[j], jobs.a[j], jobs.b[j], idx); break;
+        case PREP_CONV_WT_WINO_BF16X3: prep_conv_wT_wino_bf16x3_elem(src, (unsigned short*)jobs.dst[j], jobs.a[j], jobs.b[j], idx); break;
+        case PREP_CONV_W_WINO_F16X3: prep_conv_w_wino_f16x3_elem(src, (unsigned short*)jobs.dst[j], jobs.a[j], jobs.b[j], idx, jobs.status); break;
+        case PREP_CONV_WT_WINO_F16X3: prep_conv_wT_wino_f16x3_elem(src, (unsigned short*)jobs.dst[j], jobs.a[j], jobs.b[j], idx, jobs.status); break;
+        case PREP_WHH_QUAD: prep_whh_quad_elem(src, (uint4*)jobs.dst[j], idx); break;
+        case PREP_WHH_BWD_QUAD: prep_whh_bwd_quad_elem(src, (uint4*)jobs.dst[j], idx); break;
         default: prep_whh_bwd_elem(src, (float*)jobs.dst[j], idx); break;
     }
 }

@@ -1,3 +1,5 @@
+// FALLBACK GENERATION (bf16x6): runs only for shapes the default wgrad_wino_f16x3_kernel.h does not cover.
+//
 // Convolution weight gradient on the bf16 matrix cores (bf16x6 products, fp32 accuracy).
 //
 //   dW[co][ci][ky][kx] = sum_{b,y,x} dz[b][y][x][co] * a[b][y+ky-1][x+kx-1][ci]
@@ -17,7 +19,7 @@
 #include "bf16x6_kernels.h"
 
 #include <type_traits>
-#include "gemm_tn_bf16x6_kernel.h"      // tn_kmaj_off / tn_tr_fragment: the swizzled k-major LDS image and its transposed reads
+#include "gemm_tn_common.h"      // tn_kmaj_off / tn_tr_fragment: the swizzled k-major LDS image and its transposed reads
 
 constexpr int wgrad_x6_kpx(int W) { return (W + 15) / 16 * 16; }
 constexpr int wgrad_x6_arows(int W) { return wgrad_x6_kpx(W) + 8; }                   // pixel rows of one a-image: + halo and shifted reads

@@ -1,13 +1,15 @@
-// Convolution weight gradient in Winograd F(2x2, 3x3) form on the bf16 matrix cores (bf16x6 products, fp32 accuracy):
+// Convolution weight gradient in Winograd F(2x2, 3x3) form on the fp16 matrix cores (f16x3 products of f16_split.h, fp32 accuracy
+// under the backward's loss scale): the default weight-gradient kernel of conv2 / conv3; shapes beyond its 32-bit byte offsets run
+// on the nine-tap bf16x6 fallback (wgrad_bf16x6_kernel.h).
 //
 //   forward        Y = A^T [ (G g G^T) . (B^T d B) ] A          (d: 4 x 4 input patch of a 2 x 2 output tile)
 //   so             dU[xi][co][ci] = sum_tiles (A dY A^T)[xi][co] * (B^T d B)[xi][ci],      dg = G^T dU G
 //
 // 16 products per tile, output and input channel instead of the 36 of the nine taps (conv_wgrad_bf16x6_kernel): per frequency xi a
-// GEMM M = co, N = ci, K = tiles -- the token-reduction shape of gemm_tn2_bf16x6_kernel, and built the same way:
+// GEMM M = co, N = ci, K = tiles -- the token-reduction shape of gemm_tn2_f16x3_kernel, and built the same way:
 //   * 1024 threads, one workgroup per CU: 8 PRODUCER waves load the dY / input rows of a stage of TPS tiles (all addresses valid:
-//     a pixel outside the image is read from the handle's zero page, no load sits under a branch), transform, split into three bf16
-//     planes and store k-major images [frequency][plane][tile][channel] into stage buffer s & 1; 8 CONSUMER waves multiply stage
+//     a pixel outside the image is read from the handle's zero page, no load sits under a branch), transform, split into two fp16
+//     planes and store k-major images [frequency][plane][tile][channel] (plane stride: three planes) into stage buffer s & 1; 8 CONSUMER waves multiply stage
 //     s - 1 through the hardware-transposed LDS reads; one bare s_barrier per stage.  A producer thread owns the same items in every
 //     stage and re-issues an item's loads for stage s + 1 right after it has consumed those of stage s: one register set, a whole
 //     stage of latency cover.
@@ -19,7 +21,7 @@
 //   * every workgroup writes one slab [4 j][co][ci]; wgrad_wino_sum_kernel adds the strips in a fixed order and
 //     wgrad_wino_finish_kernel applies G^T . G and writes the torch layout.  Deterministic.
 #pragma once
-#include "gemm_tn2_bf16x6_kernel.h"
+#include "gemm_tn2_f16x3_kernel.h"
 
 constexpr int WGW_THREADS = 1024;
 // KPW = rows of the frequency grid per workgroup: 1 for 64 -> 128 (4 frequencies x 128 x 64 accumulators fill the consumers' registers),
@@ -56,13 +58,13 @@ __device__ __forceinline__ float4 wgw_sub(const float4& x, const float4& y) { re
 __device__ __forceinline__ float4 wgw_neg(const float4& x) { return make_float4(-x.x, -x.y, -x.z, -x.w); }
 
 // dz: [B][H][W][COUT] (gradient of the raw conv output), a: [B][H][W][CIN] (the layer input), slab: [strips][4 i][4 j][COUT][CIN]
-// f16x3 (round 4; the only form now): the products on the fp16 matrix cores (f16_split.h), as in gemm_tn2_bf16x6_kernel: the transformed output
+// The products on the fp16 matrix cores (f16_split.h), as in gemm_tn2_f16x3_kernel: the transformed output
 // gradient P (it carries the backward's loss scale) as two planes (Ph, Pl'), the transformed input V scaled by 2^-5 (|V| <= 4 max |input|:
 // exact below |input| = 256, clamped beyond) as two as well (Vh, Vl'; the consumers form Vh 2^11 in registers); Pl' Vh + Ph Vl' +
 // Ph (Vh 2^11) into the one accumulator set, 2^-11 x 2^5 in the epilogue.  The frequency stride of the LDS images stays three planes.
 constexpr int WGW_VS_LOG2 = -5;
 template <int CIN, int COUT>
-__global__ __launch_bounds__(WGW_THREADS, WGW_THREADS / 256) void conv_wgrad_wino_bf16x6_kernel(
+__global__ __launch_bounds__(WGW_THREADS, WGW_THREADS / 256) void conv_wgrad_wino_f16x3_kernel(
     const float* __restrict__ dz, const float* __restrict__ a, float* __restrict__ slab, int B, int H, int W) {
     using C = WgwCfg<CIN, COUT>;
     constexpr int KPW = C::KPW, NF = C::NF, TPS = C::TPS, ZW = C::ZW, AW = C::AW, PPLANE = C::PPLANE, VPLANE = C::VPLANE, STAGE = C::STAGE;

@@ -1,4 +1,5 @@
-"""The Winograd F(2x2, 3x3) algebra that ``csrc/conv_wino_bf16x6_kernel.h`` (conv2's forward) is built on, restated in
+"""The Winograd F(2x2, 3x3) algebra that ``csrc/conv_wino2_f16x3_kernel.h`` (conv2 / conv3 forward and data gradients) and its
+bf16x6 fallback ``csrc/conv_wino_bf16x6_kernel.h`` are built on, restated in
 numpy and checked against the direct 3x3 cross-correlation ``nn.Conv2d`` computes (models/models.py:15-17, padding 1):
 
 * the transform matrices and their orientation (``V = B^T d B``, ``U = G g G^T``, ``Y = A^T (U . V) A``);

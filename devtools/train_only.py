@@ -24,6 +24,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--tag", default="")
+    ap.add_argument("--freeze", default="", help="comma-separated subset of bn_stats,cnn,gru,attention (sir_amd/finetune.py): time a fine-tuning step")
     ap.add_argument("--kernels", default="", help="comma-separated substrings: only these kernel averages are printed")
     args = ap.parse_args()
     import bench
@@ -37,12 +38,15 @@ def main():
     model = CNNAudioGRU(bench.NUM_CLASSES)
     model.load_state_dict(synth.synth_state_dict(bench.NUM_CLASSES, seed=0))
     model = model.to(dev).train()
+    if args.freeze:
+        from sir_amd import finetune
+        finetune.freeze(model, args.freeze.split(","))
     fz = get_featurizer()
     pool = [bench.device_clips(args.batch, bench.CLIP_LEN, 1234 + i, dev) for i in range(4)]
     lengths = torch.full((args.batch,), bench.CLIP_LEN, dtype=torch.int32, device=dev)
     labels = torch.randint(0, bench.NUM_CLASSES, (args.batch,), device=dev)
     feats = torch.empty(args.batch, 64, bench.T_PAD, device=dev)
-    opt = FusedAdam(model.parameters(), lr=5e-5, weight_decay=1e-4)
+    opt = FusedAdam([p for p in model.parameters() if p.requires_grad], lr=5e-5, weight_decay=1e-4)
 
     def step(i):
         x = fz(pool[i % 4], lengths, t_pad=bench.T_PAD, out=feats)
@@ -79,7 +83,7 @@ def main():
         times.append((time.perf_counter() - t0) / args.steps * 1e3)
     ops.check_status()
     sw = {k: v for k, v in os.environ.items() if k.startswith("SIR_")}
-    print(json.dumps({"tag": args.tag, "env": sw, "ms_per_step_median": round(statistics.median(times), 4),
+    print(json.dumps({"tag": args.tag, "freeze": args.freeze, "env": sw, "ms_per_step_median": round(statistics.median(times), 4),
                       "ms_per_step_min": round(min(times), 4), "ms_per_step_max": round(max(times), 4),
                       "loss": round(float(loss), 6), "kernels_us": kern}), flush=True)
 

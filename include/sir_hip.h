@@ -293,6 +293,36 @@ int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* w, const fl
                              void* stream);
 int sir_model_train_workspace_offsets(const sir_handle* h, int batch, int t_frames, size_t* offsets, int n);
 
+/* ---- fine-tuning step -------------------------------------------------------------------------
+ * The torch recipe for adapting a checkpoint: model.train(), then bnK.eval() for the blocks whose pretrained statistics
+ * are kept and p.requires_grad_(False) for the layers that stay fixed.
+ *   bn_frozen[k] != 0 : BatchNorm k+1 normalises with bn_running_mean / bn_running_var (and eps) and does not touch them;
+ *                       its backward is the affine form dz = dy * gamma * invstd_running (no mean terms),
+ *                       dgamma = sum dy * xhat (xhat from the running statistics), dbeta = sum dy.
+ * The three flags are independent.  cfg == NULL means {0, 0, 0}: exactly sir_model_train_fwd / _bwd_part. */
+typedef struct sir_train_config {
+    int bn_frozen[3];
+} sir_train_config;
+
+/* sir_model_train_fwd with per-block frozen statistics.  For a frozen block the statistics work is not launched
+ * (conv1: the input-moment kernels; conv2 / conv3: the finalise pass); one small kernel folds the running statistics
+ * into the per-channel scale / shift / mean / invstd arrays the apply kernels and the backward read. */
+int sir_model_train_fwd_cfg(sir_handle* h, const sir_model_weights* w, float* const bn_running_mean[3],
+                            float* const bn_running_var[3], const float* feats, int batch, int t_frames,
+                            float bn_momentum, float dropout_p, uint64_t dropout_seed, const sir_train_config* cfg,
+                            float* logits, void* workspace, size_t workspace_bytes, void* stream);
+/* sir_model_train_bwd_part for the workspace a sir_model_train_fwd_cfg call with the SAME cfg left behind.  A NULL pointer
+ * in `grads` means "not wanted": the chain head -> GRU layer 1 -> GRU layer 0 -> conv3 -> conv2 -> conv1 stops below the
+ * lowest block that still has a wanted gradient, and a launch that only feeds unwanted gradients is not issued (the four
+ * weight-gradient GEMMs of a GRU layer, its bias sums, a convolution's weight gradient, a frozen BatchNorm's reduce, the
+ * layer-0 input gradient and everything under it when no conv / bn gradient is wanted).  Where one launch writes wanted
+ * and unwanted gradients the unwanted stores are left out.  Every wanted gradient is bit-identical to
+ * what the call writes for it with no NULL pointer and the same cfg.  `part` as for sir_model_train_bwd_part. */
+int sir_model_train_bwd_cfg(sir_handle* h, const sir_model_weights* w, const float* feats, const float* dlogits,
+                            int batch, int t_frames, float dropout_p, uint64_t dropout_seed,
+                            const sir_train_config* cfg, const sir_model_grads* grads, void* workspace,
+                            size_t workspace_bytes, int part, void* stream);
+
 /* optimizer.step() for torch.optim.Adam(lr, betas, eps, weight_decay) with coupled L2
  * (train.py:246-250, :107): one multi-tensor launch.  The pointer arrays are HOST arrays of device
  * pointers (n_tensors <= 32); `step` is the 1-based step count used for bias correction. */

@@ -45,6 +45,10 @@ class ModelGrads(C.Structure):
                 ("attn_w", C.c_void_p), ("attn_b", C.c_void_p), ("fc_w", C.c_void_p), ("fc_b", C.c_void_p)]
 
 
+class TrainConfig(C.Structure):
+    _fields_ = [("bn_frozen", C.c_int * 3)]
+
+
 # name -> (restype, argtypes); must list every function declared in include/sir_hip.h
 SIGNATURES = {
     "sir_abi_version": (C.c_int, []),
@@ -89,6 +93,12 @@ SIGNATURES = {
                                            C.c_float, C.c_uint64, C.POINTER(ModelGrads), C.c_void_p, C.c_size_t, C.c_int,
                                            C.c_void_p]),
     "sir_model_train_workspace_offsets": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.c_int]),
+    "sir_model_train_fwd_cfg": (C.c_int, [C.c_void_p, C.POINTER(ModelWeights), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                          C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint64, C.POINTER(TrainConfig),
+                                          C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "sir_model_train_bwd_cfg": (C.c_int, [C.c_void_p, C.POINTER(ModelWeights), C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                          C.c_float, C.c_uint64, C.POINTER(TrainConfig), C.POINTER(ModelGrads), C.c_void_p,
+                                          C.c_size_t, C.c_int, C.c_void_p]),
     "sir_adam_step": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                 C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int, C.c_float, C.c_float, C.c_float,
                                 C.c_float, C.c_float, C.c_void_p]),

@@ -277,10 +277,21 @@ extern "C" int sir_model_train_workspace_offsets(const sir_handle* h, int batch,
     return TB_COUNT;
 }
 
+static const sir_train_config kTrainAllLive = {{0, 0, 0}};
+
 extern "C" int sir_model_train_fwd(sir_handle* h, const sir_model_weights* w, float* const bn_running_mean[3],
                                    float* const bn_running_var[3], const float* feats, int batch, int t_frames,
                                    float bn_momentum, float dropout_p, uint64_t dropout_seed, float* logits,
                                    void* workspace, size_t workspace_bytes, void* stream_) {
+    return sir_model_train_fwd_cfg(h, w, bn_running_mean, bn_running_var, feats, batch, t_frames, bn_momentum, dropout_p, dropout_seed,
+                                   nullptr, logits, workspace, workspace_bytes, stream_);
+}
+
+extern "C" int sir_model_train_fwd_cfg(sir_handle* h, const sir_model_weights* w, float* const bn_running_mean[3],
+                                       float* const bn_running_var[3], const float* feats, int batch, int t_frames,
+                                       float bn_momentum, float dropout_p, uint64_t dropout_seed, const sir_train_config* cfg,
+                                       float* logits, void* workspace, size_t workspace_bytes, void* stream_) {
+    if (!cfg) cfg = &kTrainAllLive;
     TDims d;
     size_t off[TB_COUNT];
     int rc = check_common("sir_model_train_fwd", h, w, batch, t_frames, workspace, workspace_bytes, &d, off);
@@ -335,6 +346,10 @@ extern "C" int sir_model_train_fwd(sir_handle* h, const sir_model_weights* w, fl
         SirProfScope prof(h, SIR_K_T_CONV1, st);
         // conv1's BatchNorm statistics come from 54 moments of the INPUT (z_c = sum_t w_c[t] x_t: sums and sums of squares
         // of z are bilinear in the taps), so conv1 itself runs once, fused with BN + ReLU + pool
+        if (cfg->bn_frozen[0]) {                      // frozen statistics: no moments (the frozen conv1 backward needs none either)
+            hipLaunchKernelGGL(bn_fold_running_kernel, dim3(1), dim3(64), 0, st, w->bn_w[0], w->bn_b[0], (const float*)bn_running_mean[0],
+                               (const float*)bn_running_var[0], 32, scale, shift, smean, sinv);
+        } else {
         const int tiles = d.c1gx * d.c1gy;
         int per_img = (2048 + B - 1) / B;             // workgroups per image: >= 2048 in all when the batch allows it
         per_img = per_img < 1 ? 1 : (per_img > tiles ? tiles : per_img);
@@ -343,6 +358,7 @@ extern "C" int sir_model_train_fwd(sir_handle* h, const sir_model_weights* w, fl
         hipLaunchKernelGGL(conv1_bn_from_moments_kernel, dim3(1), dim3(64), 0, st, (const double*)p.c1m, w->conv_w[0],
                            (double)B * 64 * T, w->bn_w[0], w->bn_b[0], bn_running_mean[0], bn_running_var[0], bn_momentum,
                            scale, shift, smean, sinv);
+        }
         hipLaunchKernelGGL(conv1_mfma_bn_relu_pool_kernel, dim3((d.wp1 + C1_PCOLS - 1) / C1_PCOLS, 1, B), dim3(256), 0, st,
                            feats, w->conv_w[0], scale, shift, p.a1, 64, T, 32, d.wp1, (const float*)nullptr, B, (const int*)nullptr);
     }
@@ -352,6 +368,10 @@ extern "C" int sir_model_train_fwd(sir_handle* h, const sir_model_weights* w, fl
         SIR_TRY((conv_fwd<32, 64, 2>(h, st, w2, cp.geo2, B, p.a1, p.wcb2, nullptr, nullptr, nullptr, p.z2, p.stats)));
         }
         SirProfScope prof(h, SIR_K_T_BN2, st);
+        if (cfg->bn_frozen[1])                        // (the convolution's partial statistics are simply not read)
+            hipLaunchKernelGGL(bn_fold_running_kernel, dim3(1), dim3(64), 0, st, w->bn_w[1], w->bn_b[1], (const float*)bn_running_mean[1],
+                               (const float*)bn_running_var[1], 64, scale + 32, shift + 32, smean + 32, sinv + 32);
+        else
         hipLaunchKernelGGL(bn_finalize_kernel, dim3(64), dim3(256), 0, st, (const float2*)p.stats, w2 ? (int)wino2_stat_blocks(B, 32, d.wp1, h->num_cus) : d.c2wx * B, 64,
                            (double)B * 32 * d.wp1, w->bn_w[1], w->bn_b[1], bn_running_mean[1], bn_running_var[1], bn_momentum,
                            scale + 32, shift + 32, smean + 32, sinv + 32);
@@ -363,6 +383,10 @@ extern "C" int sir_model_train_fwd(sir_handle* h, const sir_model_weights* w, fl
         SIR_TRY((conv_fwd<64, 128, 2>(h, st, w2, cp.geo3, B, p.a2, p.wcb3, p.wcb3d, nullptr, nullptr, p.z3, p.stats)));
         }
         SirProfScope prof(h, SIR_K_T_BN3, st);
+        if (cfg->bn_frozen[2])
+            hipLaunchKernelGGL(bn_fold_running_kernel, dim3(1), dim3(128), 0, st, w->bn_w[2], w->bn_b[2], (const float*)bn_running_mean[2],
+                               (const float*)bn_running_var[2], 128, scale + 96, shift + 96, smean + 96, sinv + 96);
+        else
         hipLaunchKernelGGL(bn_finalize_kernel, dim3(128), dim3(256), 0, st, (const float2*)p.stats, w2 ? (int)wino2_stat_blocks(B, 16, d.wp2, h->num_cus) : d.c3fx * B, 128,
                            (double)B * 16 * d.wp2, w->bn_w[2], w->bn_b[2], bn_running_mean[2], bn_running_var[2], bn_momentum,
                            scale + 96, shift + 96, smean + 96, sinv + 96);
@@ -426,6 +450,15 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
                                         int batch, int t_frames, float dropout_p, uint64_t dropout_seed,
                                         const sir_model_grads* g, void* workspace, size_t workspace_bytes, int part,
                                         void* stream_) {
+    return sir_model_train_bwd_cfg(h, w, feats, dlogits, batch, t_frames, dropout_p, dropout_seed, nullptr, g, workspace, workspace_bytes,
+                                   part, stream_);
+}
+
+extern "C" int sir_model_train_bwd_cfg(sir_handle* h, const sir_model_weights* w, const float* feats, const float* dlogits,
+                                       int batch, int t_frames, float dropout_p, uint64_t dropout_seed,
+                                       const sir_train_config* cfg, const sir_model_grads* g_, void* workspace,
+                                       size_t workspace_bytes, int part, void* stream_) {
+    if (!cfg) cfg = &kTrainAllLive;
     if (part != SIR_BWD_ALL && part != SIR_BWD_HEAD_GRU && part != SIR_BWD_CNN) {
         sir_set_error("sir_model_train_bwd_part: unknown part %d", part);
         return SIR_EINVAL;
@@ -434,9 +467,26 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
     size_t off[TB_COUNT];
     int rc = check_common("sir_model_train_bwd", h, w, batch, t_frames, workspace, workspace_bytes, &d, off);
     if (rc != SIR_OK) return rc;
-    if (!feats || !dlogits || !g) { sir_set_error("sir_model_train_bwd: NULL argument"); return SIR_EINVAL; }
+    if (!feats || !dlogits || !g_) { sir_set_error("sir_model_train_bwd: NULL argument"); return SIR_EINVAL; }
     hipStream_t st = (hipStream_t)stream_;
     TPtrs p = carve(workspace, off);
+
+    // ---- what is wanted (a NULL gradient pointer = frozen parameter) and how far down the chain has to run ----
+    const sir_model_grads& gw = *g_;
+    const bool w_fc = gw.fc_w || gw.fc_b, w_attn = gw.attn_w || gw.attn_b;
+    bool w_gru_w[2], w_gru_b[2], w_blk[3], w_gb[3];
+    for (int l = 0; l < 2; ++l) {
+        w_gru_w[l] = gw.gru_w_ih[2 * l] || gw.gru_w_ih[2 * l + 1] || gw.gru_w_hh[2 * l] || gw.gru_w_hh[2 * l + 1];
+        w_gru_b[l] = gw.gru_b_ih[2 * l] || gw.gru_b_ih[2 * l + 1] || gw.gru_b_hh[2 * l] || gw.gru_b_hh[2 * l + 1];
+    }
+    for (int i = 0; i < 3; ++i) { w_gb[i] = gw.bn_w[i] || gw.bn_b[i]; w_blk[i] = gw.conv_w[i] || w_gb[i]; }
+    const bool w_cnn = w_blk[0] || w_blk[1] || w_blk[2];
+    const bool need_bptt[2] = {w_gru_w[0] || w_gru_b[0] || w_cnn, w_gru_w[1] || w_gru_b[1] || w_gru_w[0] || w_gru_b[0] || w_cnn};
+    const bool need_head = w_fc || w_attn || need_bptt[1];
+    const bool need_dz3 = gw.conv_w[2] || w_blk[1] || w_blk[0], need_da2 = w_blk[1] || w_blk[0];
+    const bool need_dz2 = gw.conv_w[1] || w_blk[0], need_da1 = w_blk[0];
+    // (a launch that writes wanted and unwanted gradients gets NULL for the unwanted ones: the kernels test the pointer at the store)
+    const sir_model_grads* g = &gw;
     const int B = d.B, S = d.S, T = d.T, C = w->num_classes, M = B * S;
     float *scale = p.bn, *shift = p.bn + 224, *smean = p.bn + 448, *sinv = p.bn + 672;
     float *mdy = p.bnb, *mdyx = p.bnb + 224;
@@ -484,10 +534,10 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
             const int gi_idx = 2 * layer + dir;
             const int ja = 2 * dir, jh = 2 * dir + 1;
             jb.A[ja] = dgi_l + dir * 768; jb.lda[ja] = 1536; jb.B[ja] = xin; jb.ldb[ja] = in_sz; jb.N[ja] = in_sz; jb.shift[ja] = 0;
-            outs[ja] = g->gru_w_ih[gi_idx];
+            outs[ja] = gw.gru_w_ih[gi_idx];
             jb.A[jh] = dgh_l + dir * 768; jb.lda[jh] = 1536; jb.B[jh] = yout + dir * 256; jb.ldb[jh] = 512; jb.N[jh] = 256;
             jb.shift[jh] = dir ? 1 : -1;
-            outs[jh] = g->gru_w_hh[gi_idx];
+            outs[jh] = gw.gru_w_hh[gi_idx];
         }
         for (int j = 0; j < 4; ++j) {
             jb.tile0[j] = tiles;
@@ -508,21 +558,25 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
         SIR_TRY(sir_lds_opt_in(h, (const void*)gemm_tn2_f16x3_kernel<true>, (int)tn2_lds_bytes(true)));
         hipLaunchKernelGGL(gemm_tn2_f16x3_kernel<true>, dim3(tiles, nsplit), dim3(TN2_THREADS), tn2_lds_bytes(true), s_, jb, 768, M, kchunk, S);
         SlabJobs sj{};
-        for (int j = 0; j < 4; ++j) { sj.src[j] = jb.slab[j]; sj.out[j] = outs[j]; sj.n[j] = sizes[j]; }
+        for (int j = 0; j < 4; ++j) { sj.src[j] = jb.slab[j]; sj.out[j] = outs[j]; sj.n[j] = outs[j] ? sizes[j] : 0; }     // (n = 0: a frozen matrix is not reduced)
         hipLaunchKernelGGL(slab_reduce_jobs_kernel, dim3(grid_for(sizes[0]), 4), dim3(256), 0, s_, sj, nsplit, unscale);
         return SIR_OK;
     };
 
+    bool side_used = false, ev3_recorded = false;           // launches on the side stream in this call / its last one marked
     if (part != SIR_BWD_CNN) {
     // ---- head: fc + attention pooling ----------------------------------------------------
-    { SirProfScope prof(h, SIR_K_B_HEAD, st);
-    hipLaunchKernelGGL(head_bwd_kernel, dim3(B + 2 * C), dim3(256), 0, st, dlogits, w->fc_w, (const float*)p.y1, w->attn_w, w->attn_b,
+    if (need_head) { SirProfScope prof(h, SIR_K_B_HEAD, st);
+    // (workgroups [B, B + 2 C) are the fc weight / bias gradient: left out when fc is frozen)
+    hipLaunchKernelGGL(head_bwd_kernel, dim3(B + (w_fc ? 2 * C : 0)), dim3(256), 0, st, dlogits, w->fc_w, (const float*)p.y1, w->attn_w, w->attn_b,
                        (const float*)p.ctx, p.dy1, daw_part, dab_part, g->fc_w, g->fc_b, B, S, C, gscale);
+    if (w_attn)
     hipLaunchKernelGGL(head_colsum_kernel, dim3(9), dim3(256), 0, st, (const float*)daw_part, (const float*)dab_part, B, g->attn_w, g->attn_b); }
     SIR_KCHECK();
 
     // ---- GRU layers, top down ----------------------------------------------------------------
     for (int layer = 1; layer >= 0; --layer) {
+        if (!need_bptt[layer]) break;                        // nothing trainable in this layer or below it
         const float* dy = layer ? p.dy1 : p.dy0;
         const float* gates = layer ? p.g1 : p.g0;
         const float* yout = layer ? p.y1 : p.y0;
@@ -534,9 +588,13 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
                                         B, S, (const char*)p.wr4 + (size_t)(2 * layer) * GRU_FRAG_BYTES,
                                         (const char*)p.wr4 + (size_t)(2 * layer + 1) * GRU_FRAG_BYTES));
         // bias gradients first: bsum_* alias the slab area used below
+        if (w_gru_b[layer])
         hipLaunchKernelGGL(gru_bias_colsum_kernel, dim3(24, 2), dim3(256), 0, st, (const float*)bsum_i, (const float*)bsum_h, B,
                            g->gru_b_ih[2 * layer], g->gru_b_ih[2 * layer + 1], g->gru_b_hh[2 * layer], g->gru_b_hh[2 * layer + 1], unscale); }
-        if (two) {                                           // (layer 0's GEMM queues behind layer 1's on the side stream: they share the slabs)
+        const bool touch = layer == 1 && need_bptt[0];       // (the prefetch belongs to layer 0's BPTT, not to layer 1's weight gradient)
+        if (!two) { if (w_gru_w[layer]) SIR_TRY(launch_dw(layer, st)); }
+        else if (w_gru_w[layer] || touch) {                  // (layer 0's GEMM queues behind layer 1's on the side stream: they share the slabs)
+            side_used = true;
             SIR_HIP_TRY(hipEventRecord(h->bwd_ev[4 + layer], st));
             SIR_HIP_TRY(hipStreamWaitEvent(side, h->bwd_ev[4 + layer], 0));
             // Layer 0's saved gates and outputs (65 MB) were written early in the forward and have left the 256 MB last-level cache by now;
@@ -544,11 +602,12 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
             // pays 16-26 us for the difference (profiles/r04/ab_bptt.txt).  A read-and-drop pass on the side stream, beside layer 1's dX on
             // the caller's, brings them back: step -28 .. -40 us.  The same for the raw conv outputs ahead of the BatchNorm backward was
             // measured and LOSES (those kernels are bandwidth-bound: the reads are only moved earlier).
-            if (layer == 1)
+            if (touch)
                 hipLaunchKernelGGL(cache_touch_kernel, dim3(256), dim3(256), 0, side, (const float4*)p.g0, (size_t)M * 2048 / 4, (const float4*)p.y0,
                                    (size_t)M * 512 / 4, p.small);
-            SIR_TRY(launch_dw(layer, side));
-        } else { SIR_TRY(launch_dw(layer, st)); }
+            if (w_gru_w[layer]) SIR_TRY(launch_dw(layer, side));
+        }
+        if (!(layer ? need_bptt[0] : w_cnn)) break;          // nobody reads this layer's input gradient
         // gradient wrt the layer input: dgi [M][1536] x [W_ih; W_ih_reverse] [1536][in]
         SirProfScope prof(h, layer ? SIR_K_B_DX1 : SIR_K_B_DX0, st);
         float* dxin = layer ? p.dy0 : p.dx0;
@@ -587,12 +646,19 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
         SIR_KCHECK();
     }
     }
-    if (two) {                                         // join: the GRU gradients are final on the caller's stream (the conv chain
+    if (two && side_used) {                            // join: the GRU gradients are final on the caller's stream (the conv chain
         SIR_HIP_TRY(hipEventRecord(h->bwd_ev[3], side));     // below does not depend on them, but the data-parallel caller reduces them next)
+        ev3_recorded = true;
         if (part == SIR_BWD_HEAD_GRU) SIR_HIP_TRY(hipStreamWaitEvent(st, h->bwd_ev[3], 0));
     }
     if (part == SIR_BWD_HEAD_GRU) return SIR_OK;
-    if (two) {                                               // SIR_BWD_CNN of the split form: the side stream starts behind the first half
+    if (!w_cnn) {                                            // whole CNN frozen: the chain ended at layer 0's BPTT
+        SIR_KCHECK();
+        if (two && ev3_recorded) SIR_HIP_TRY(hipStreamWaitEvent(st, h->bwd_ev[3], 0));
+        return SIR_OK;
+    }
+    const bool fz1 = cfg->bn_frozen[0] != 0, fz2 = cfg->bn_frozen[1] != 0, fz3 = cfg->bn_frozen[2] != 0;
+    if (two && (gw.conv_w[1] || gw.conv_w[2])) {             // SIR_BWD_CNN of the split form: the side stream starts behind the first half
         SIR_HIP_TRY(hipEventRecord(h->bwd_ev[0], st));
         SIR_HIP_TRY(hipStreamWaitEvent(side, h->bwd_ev[0], 0));
     }
@@ -602,26 +668,42 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
         // BatchNorm backward sums from the POOLED activations x0 (GRU layout) and their gradient -- dy = da wherever a > 0 and
         // xhat at the routed maximum is (a - beta) / gamma -- instead of the four times larger raw conv output z3
         const int rows = B * d.wp3, rpb = 16, nfin = (rows + rpb - 1) / rpb;
-        {
+        // frozen statistics: the pooled sums feed only dgamma / dbeta (same kernel: xhat = (a - beta) / gamma holds for the running
+        // statistics too, and the small-gamma path reads the folded arrays), and dz waits for no reduce at all
+        if (fz3 ? (w_gb[2] || need_dz3) : true) {
             SirProfScope prof(h, SIR_K_B_BN3, st);
+            if (!fz3 || w_gb[2])
             hipLaunchKernelGGL(bn_bwd_reduce_pooled_gru_kernel, dim3(nfin), dim3(256), 0, st, (const float*)p.x0, (const float*)p.dx0,
                                (const float*)p.z3, w->bn_w[2], w->bn_b[2], scale + 96, shift + 96, smean + 96, sinv + 96, p.stats, rows,
                                16, d.wp2, d.wp3, rpb);
+            if (fz3) {
+                if (w_gb[2])
+                    hipLaunchKernelGGL(bn_bwd_finalize_frozen_kernel, dim3(128), dim3(256), 0, st, (const float2*)p.stats, nfin, 128, gw.bn_w[2], gw.bn_b[2], unscale);
+                if (need_dz3)
+                    hipLaunchKernelGGL((bn_bwd_dz_kernel<true, true>), dim3(grid_for((size_t)B * 8 * ((d.wp2 + 1) / 2) * 32)), dim3(256), 0, st, (const float*)p.z3,
+                                       (const float*)p.dx0, scale + 96, shift + 96, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,
+                                       (const float*)nullptr, p.dz3, B, 16, d.wp2, 128, 8, d.wp3);
+            } else {
             hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(128), dim3(256), 0, st, (const float2*)p.stats, nfin, 128,
                                (double)B * 16 * d.wp2, g->bn_w[2], g->bn_b[2], mdy + 96, mdyx + 96, unscale);
+            if (need_dz3)
             hipLaunchKernelGGL(bn_bwd_dz_kernel<true>, dim3(grid_for((size_t)B * 8 * ((d.wp2 + 1) / 2) * 32)), dim3(256), 0, st, (const float*)p.z3,
                                (const float*)p.dx0, scale + 96, shift + 96, smean + 96, sinv + 96, mdy + 96, mdyx + 96, p.dz3, B, 16,
                                d.wp2, 128, 8, d.wp3);
+            }
         }
-        if (two) {
-            SIR_HIP_TRY(hipEventRecord(h->bwd_ev[1], st));
-            SIR_HIP_TRY(hipStreamWaitEvent(side, h->bwd_ev[1], 0));
-        }
-        {
+        if (gw.conv_w[2]) {
+            if (two) {
+                SIR_HIP_TRY(hipEventRecord(h->bwd_ev[1], st));
+                SIR_HIP_TRY(hipStreamWaitEvent(side, h->bwd_ev[1], 0));
+            }
+            {
             SirProfScope prof(h, SIR_K_B_WGRAD3, side);
             SIR_TRY((conv_wgrad<64, 128>(h, side, cp.wgrad3_wino, B, 16, d.wp2, p.dz3, p.a2, p.slab, g->conv_w[2], unscale)));
+            }
+            if (two && !gw.conv_w[1]) { SIR_HIP_TRY(hipEventRecord(h->bwd_ev[3], side)); ev3_recorded = true; }     // (the side stream's last launch)
         }
-        {
+        if (need_da2) {
             // data gradient = a 128 -> 64 convolution with the flipped / transposed taps: the Winograd kernel (16 of 36 products), blocks
             // of 8 x 4 tiles for the 16-row map, raw output (train_prep_kernel of the forward built p.wcb3t)
             SirProfScope prof(h, SIR_K_B_DGRAD3, st);
@@ -630,38 +712,51 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
         SIR_KCHECK();
     }
     // ---- conv2 block -------------------------------------------------------------------------
-    {
+    if (need_da2) {
         const int ppb = 64;
         const size_t npix = (size_t)B * 16 * d.wp2;
         const int nblk = (int)((npix + ppb - 1) / ppb);
-        {
+        if (fz2 ? (w_gb[1] || need_dz2) : true) {
             SirProfScope prof(h, SIR_K_B_BN2, st);
+            if (!fz2 || w_gb[1])
             hipLaunchKernelGGL(bn_bwd_reduce_pooled_kernel, dim3(nblk), dim3(256), 0, st, (const float*)p.a2, (const float*)p.da2,
                                (const float*)p.z2, w->bn_w[1], w->bn_b[1], scale + 32, shift + 32, smean + 32, sinv + 32, p.stats, B, 32,
                                d.wp1, 64, 16, d.wp2, ppb);
+            if (fz2) {
+                if (w_gb[1])
+                    hipLaunchKernelGGL(bn_bwd_finalize_frozen_kernel, dim3(64), dim3(256), 0, st, (const float2*)p.stats, nblk, 64, gw.bn_w[1], gw.bn_b[1], unscale);
+                if (need_dz2)
+                    hipLaunchKernelGGL((bn_bwd_dz_kernel<false, true>), dim3(grid_for((size_t)B * 16 * ((d.wp1 + 1) / 2) * 16)), dim3(256), 0, st, (const float*)p.z2,
+                                       (const float*)p.da2, scale + 32, shift + 32, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr,
+                                       (const float*)nullptr, p.dz2, B, 32, d.wp1, 64, 16, d.wp2);
+            } else {
             hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(64), dim3(256), 0, st, (const float2*)p.stats, nblk, 64,
                                (double)B * 32 * d.wp1, g->bn_w[1], g->bn_b[1], mdy + 32, mdyx + 32, unscale);
+            if (need_dz2)
             hipLaunchKernelGGL(bn_bwd_dz_kernel<false>, dim3(grid_for((size_t)B * 16 * ((d.wp1 + 1) / 2) * 16)), dim3(256), 0, st, (const float*)p.z2,
                                (const float*)p.da2, scale + 32, shift + 32, smean + 32, sinv + 32, mdy + 32, mdyx + 32, p.dz2, B, 32,
                                d.wp1, 64, 16, d.wp2);
+            }
         }
-        if (two) {
-            SIR_HIP_TRY(hipEventRecord(h->bwd_ev[2], st));
-            SIR_HIP_TRY(hipStreamWaitEvent(side, h->bwd_ev[2], 0));
-        }
-        {
+        if (gw.conv_w[1]) {
+            if (two) {
+                SIR_HIP_TRY(hipEventRecord(h->bwd_ev[2], st));
+                SIR_HIP_TRY(hipStreamWaitEvent(side, h->bwd_ev[2], 0));
+            }
+            {
             SirProfScope prof(h, SIR_K_B_WGRAD2, side);
             SIR_TRY((conv_wgrad<32, 64>(h, side, cp.wgrad2_wino, B, 32, d.wp1, p.dz2, p.a1, p.slab, g->conv_w[1], unscale)));
+            }
+            if (two) { SIR_HIP_TRY(hipEventRecord(h->bwd_ev[3], side)); ev3_recorded = true; }     // (the side stream's last launch)
         }
-        if (two) SIR_HIP_TRY(hipEventRecord(h->bwd_ev[3], side));     // (the side stream's last launch)
-        {
+        if (need_da1) {
             SirProfScope prof(h, SIR_K_B_DGRAD2, st);
             SIR_TRY((conv_dgrad<64, 32>(h, st, cp.dgrad2_wino, cp.geo2, p.dz2, p.wcb2t, p.da1)));
         }
         SIR_KCHECK();
     }
     // ---- conv1 block ------------------------------------------------------------------------
-    {
+    if (need_da1) {
         // ONE recompute pass: (sum dy, sum dy*xhat, sum dy*x_tap) per channel; the mean terms of dz = s (dy - m1 - xhat m2) and
         // with them the rest of dW1 are closed forms in the input moments of the forward (conv1_bwd_finalize_kernel, in double)
         SirProfScope prof(h, SIR_K_B_CONV1, st);
@@ -674,11 +769,15 @@ extern "C" int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* 
         hipLaunchKernelGGL(colsum_partial_kernel, dim3((352 + 63) / 64, 128), dim3(256), 0, st, (const float*)c1part, nblk, 352,
                            352, c1tmp);
         hipLaunchKernelGGL(colsum_kernel, dim3((352 + 63) / 64), dim3(256), 0, st, (const float*)c1tmp, 128, 352, 352, c1tot);
+        if (fz1)                                             // frozen statistics: plain sums, no input moments
+            hipLaunchKernelGGL(conv1_bwd_finalize_frozen_kernel, dim3(1), dim3(320), 0, st, (const float*)c1tot, (const float*)scale, gw.bn_w[0], gw.bn_b[0],
+                               gw.conv_w[0], unscale);
+        else
         hipLaunchKernelGGL(conv1_bwd_finalize_kernel, dim3(1), dim3(320), 0, st, (const float*)c1tot, (const double*)p.c1m,
                            w->conv_w[0], scale, smean, sinv, (double)B * 64 * T, g->bn_w[0], g->bn_b[0], g->conv_w[0], unscale);
         SIR_KCHECK();
     }
-    if (two) SIR_HIP_TRY(hipStreamWaitEvent(st, h->bwd_ev[3], 0));   // join: every gradient is final on the caller's stream
+    if (two && ev3_recorded) SIR_HIP_TRY(hipStreamWaitEvent(st, h->bwd_ev[3], 0));   // join: every gradient is final on the caller's stream
     return SIR_OK;
 }
 

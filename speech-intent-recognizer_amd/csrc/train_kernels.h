@@ -165,6 +165,24 @@ static __global__ __launch_bounds__(256) void bn_finalize_kernel(const float2* _
         bn_finalize_channel(rs[0], rq[0], count, c, gamma, beta, run_mean, run_var, momentum, scale, shift, save_mean, save_invstd);
 }
 
+// Frozen statistics (bnK.eval() inside a training step): the running mean / variance take the place of the batch ones in the
+// four per-channel arrays that the apply kernels and the backward read; nothing is reduced and the running statistics stay as
+// they are.  One thread per channel.
+static __global__ void bn_fold_running_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
+                                              const float* __restrict__ run_mean, const float* __restrict__ run_var, int C,
+                                              float* __restrict__ scale, float* __restrict__ shift,
+                                              float* __restrict__ save_mean, float* __restrict__ save_invstd) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= C) return;
+    const float mean = run_mean[c];
+    const float invstd = (float)(1.0 / sqrt((double)run_var[c] + (double)SIR_BN_EPS));
+    const float sc = gamma[c] * invstd;
+    scale[c] = sc;
+    shift[c] = beta[c] - mean * sc;
+    save_mean[c] = mean;
+    save_invstd[c] = invstd;
+}
+
 // z (raw conv output, NHWC [B][H][W][C]) -> relu(bn(z)) -> 2x2 max-pool.
 // GRU_OUT = false: NHWC [B][Hp][Wp][C];  true: [B][Wp][C*Hp] with feature = c*Hp + py (models.py:55-57)
 template <bool GRU_OUT>
@@ -422,7 +440,7 @@ static __global__ __launch_bounds__(256) void head_colsum_kernel(const float* __
     __syncthreads();
     if (part == 0 && (!bias || l == 0)) {
         const float v = red[0][l] + red[1][l] + red[2][l] + red[3][l];
-        if (bias) out_b[0] = v; else out_w[col] = v;
+        if (bias) { if (out_b) out_b[0] = v; } else if (out_w) out_w[col] = v;     // (NULL = that gradient is not wanted)
     }
 }
 
@@ -442,7 +460,7 @@ static __global__ __launch_bounds__(256) void gru_bias_colsum_kernel(const float
     if (part == 0) {
         const float v = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
         float* out = blockIdx.y ? (col < 768 ? bh0 : bh1) : (col < 768 ? bi0 : bi1);
-        out[col < 768 ? col : col - 768] = v * unscale;
+        if (out) out[col < 768 ? col : col - 768] = v * unscale;     // (NULL = that gradient is not wanted)
     }
 }
 
@@ -487,8 +505,8 @@ __device__ __forceinline__ void fc_wgrad_block(int j, int half, const float* __r
         }
         for (; b < nb; ++b) { a = fmaf(dl[b], ctx[(size_t)(b0 + b) * 512 + c], a); sb += dl[b]; }
     }
-    dw[(size_t)j * 512 + c] = a;
-    if (c == 0) db[j] = sb;
+    if (dw) dw[(size_t)j * 512 + c] = a;          // (NULL = that gradient is not wanted)
+    if (db && c == 0) db[j] = sb;
 }
 
 // head backward, ONE launch for two independent jobs (both only need dlogits): workgroups [0, B) = one utterance each
@@ -764,10 +782,31 @@ static __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float
         __syncthreads();
     }
     if (tid == 0) {
-        dbeta[c] = (float)rs[0] * unscale;              // parameter gradients leave the loss scale; the means below feed dz and keep it
-        dgamma[c] = (float)rq[0] * unscale;
+        if (dbeta) dbeta[c] = (float)rs[0] * unscale;   // parameter gradients leave the loss scale; the means below feed dz and keep it
+        if (dgamma) dgamma[c] = (float)rq[0] * unscale; // (NULL = that gradient is not wanted)
         mdy[c] = (float)(rs[0] / count);
         mdyx[c] = (float)(rq[0] / count);
+    }
+}
+
+// frozen statistics: the same ordered sum of the partials, but only dbeta / dgamma come out of it (dz has no mean terms, so
+// nothing downstream waits for this kernel); either output may be NULL
+static __global__ __launch_bounds__(256) void bn_bwd_finalize_frozen_kernel(const float2* __restrict__ part, int nblk, int C,
+                                                                      float* __restrict__ dgamma, float* __restrict__ dbeta, float unscale) {
+    __shared__ double rs[256], rq[256];
+    const int c = blockIdx.x, tid = threadIdx.x;
+    double s = 0.0, q = 0.0;
+#pragma unroll 4
+    for (int i = tid; i < nblk; i += 256) { const float2 v = part[(size_t)i * C + c]; s += v.x; q += v.y; }
+    rs[tid] = s; rq[tid] = q;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) { rs[tid] += rs[tid + o]; rq[tid] += rq[tid + o]; }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        if (dbeta) dbeta[c] = (float)rs[0] * unscale;
+        if (dgamma) dgamma[c] = (float)rq[0] * unscale;
     }
 }
 
@@ -782,7 +821,9 @@ __device__ __forceinline__ int route_arg(float y00, float y01, float y10, float 
 
 // thread = one 2x2 window x 4 channels: the four z values are read once (a thread per PIXEL re-read its three window
 // neighbours for the routing: 5 loads per output against 1.25 here), the pooled gradient once per window
-template <bool GRU_IN>
+// FROZEN (running statistics): dz = gamma * invstd_running * dy -- the mean terms are gone, and with them the mean / invstd /
+// mdy / mdyx reads (pass NULL) and the dependence on the reduce pass; z is still read for the routing
+template <bool GRU_IN, bool FROZEN = false>
 __global__ __launch_bounds__(256) void bn_bwd_dz_kernel(const float* __restrict__ z, const float* __restrict__ da,
                                                          const float* __restrict__ scale, const float* __restrict__ shift,
                                                          const float* __restrict__ mean, const float* __restrict__ invstd,
@@ -808,8 +849,11 @@ __global__ __launch_bounds__(256) void bn_bwd_dz_kernel(const float* __restrict_
             b = rest / Hc;
         }
         const float4 s = *reinterpret_cast<const float4*>(scale + cc * 4), t = *reinterpret_cast<const float4*>(shift + cc * 4);
-        const float4 mu = *reinterpret_cast<const float4*>(mean + cc * 4), is = *reinterpret_cast<const float4*>(invstd + cc * 4);
-        const float4 m1 = *reinterpret_cast<const float4*>(mdy + cc * 4), m2 = *reinterpret_cast<const float4*>(mdyx + cc * 4);
+        float4 mu = make_float4(0.f, 0.f, 0.f, 0.f), is = mu, m1 = mu, m2 = mu;
+        if (!FROZEN) {
+            mu = *reinterpret_cast<const float4*>(mean + cc * 4); is = *reinterpret_cast<const float4*>(invstd + cc * 4);
+            m1 = *reinterpret_cast<const float4*>(mdy + cc * 4); m2 = *reinterpret_cast<const float4*>(mdyx + cc * 4);
+        }
         float4 zq[4];
         bool ok[4];
 #pragma unroll
@@ -832,6 +876,12 @@ __global__ __launch_bounds__(256) void bn_bwd_dz_kernel(const float* __restrict_
             if (!ok[q]) continue;
             const int y = 2 * cy + (q >> 1), x = 2 * cx + (q & 1);
             float4 o;
+            if (FROZEN) {
+                o.x = s.x * (ax == q ? g.x : 0.0f); o.y = s.y * (ay == q ? g.y : 0.0f);
+                o.z = s.z * (az == q ? g.z : 0.0f); o.w = s.w * (aw == q ? g.w : 0.0f);
+                *reinterpret_cast<float4*>(dz + (((size_t)b * H + y) * W + x) * C + cc * 4) = o;
+                continue;
+            }
             o.x = s.x * ((ax == q ? g.x : 0.0f) - m1.x - (zq[q].x - mu.x) * is.x * m2.x);
             o.y = s.y * ((ay == q ? g.y : 0.0f) - m1.y - (zq[q].y - mu.y) * is.y * m2.y);
             o.z = s.z * ((az == q ? g.z : 0.0f) - m1.z - (zq[q].z - mu.z) * is.z * m2.z);
@@ -958,8 +1008,23 @@ static __global__ void conv1_bwd_finalize_kernel(const float* __restrict__ total
     double zx = 0.0;                                             // sum z * x_tap
     for (int t = 0; t < 9; ++t) zx += (double)w[c * 9 + t] * M[t <= tap ? c1_r_index(t, tap) : c1_r_index(tap, t)];
     const double xhx = (double)invstd[c] * (zx - (double)mean[c] * M[tap]);
-    dw[c * 9 + tap] = (float)((double)scale[c] * (A - m1 * M[tap] - m2 * xhx)) * unscale;
-    if (tap == 0) { dbeta[c] = (float)sdy * unscale; dgamma[c] = (float)sdx * unscale; }
+    if (dw) dw[c * 9 + tap] = (float)((double)scale[c] * (A - m1 * M[tap] - m2 * xhx)) * unscale;     // (NULL = not wanted)
+    if (tap == 0) { if (dbeta) dbeta[c] = (float)sdy * unscale; if (dgamma) dgamma[c] = (float)sdx * unscale; }
+}
+
+// frozen statistics: dz = s dy, so dW[c][tap] = s_c A[tap], dbeta = sum dy, dgamma = sum dy*xhat are plain sums of the same
+// totals (xhat from the running statistics); no input moments.  Any output may be NULL.
+static __global__ void conv1_bwd_finalize_frozen_kernel(const float* __restrict__ totals, const float* __restrict__ scale,
+                                                        float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ dw,
+                                                        float unscale) {
+    const int idx = threadIdx.x;
+    if (idx >= 288) return;
+    const int c = idx / 9, tap = idx % 9;
+    if (dw) dw[c * 9 + tap] = (float)((double)scale[c] * (double)totals[c * 11 + 2 + tap]) * unscale;
+    if (tap == 0) {
+        if (dbeta) dbeta[c] = totals[c * 11] * unscale;
+        if (dgamma) dgamma[c] = totals[c * 11 + 1] * unscale;
+    }
 }
 
 // dW[co][ci][tap] = sum_blk slab[blk][tap][co][ci], in two ordered (deterministic) passes: WGR_PARTS partial sums over

@@ -51,8 +51,24 @@ class CNNAudioGRU(nn.Module):
         self._sir_token = ops.new_model_token()
         return out
 
+    def train(self, mode=True):
+        """``nn.Module.train`` plus one thing: BatchNorm blocks frozen by ``sir_amd.finetune.freeze(model, {"bn_stats"})``
+        go back to ``eval()`` afterwards, so that the ``model.train()`` at the top of every epoch does not silently bring
+        the batch statistics back.  Without such a freeze this is ``nn.Module.train`` exactly."""
+        super().train(mode)
+        if mode:
+            for name in getattr(self, "_sir_frozen_modules", ()):
+                getattr(self, name).eval()
+        return self
+
     def forward(self, x):
-        """x: [B, 64, T] or [B, 1, 64, T] float32 on the GPU -> logits [B, num_classes]."""
+        """x: [B, 64, T] or [B, 1, 64, T] float32 on the GPU -> logits [B, num_classes].
+
+        ``self.training and torch.is_grad_enabled()`` selects the differentiable path, as before; ``model.eval()`` keeps
+        calling ``sir_model_infer``.  Inside the differentiable path the sub-modules are consulted the way torch consults
+        them: ``bnK.training == False`` uses (and keeps) that block's running statistics, ``gru.training == False`` turns the
+        inter-layer dropout off, and parameters with ``requires_grad == False`` receive no gradient and cost no backward
+        work where it can be skipped.  With every sub-module in training mode and every parameter trainable nothing changes."""
         if self.training and torch.is_grad_enabled():
             from sir_amd import train_ops
             return train_ops.forward_train(self, x)

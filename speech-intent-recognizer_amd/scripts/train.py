@@ -311,9 +311,23 @@ def train(args, config):
     val_loader = None if hbm_cache else DataLoader(val_dataset, batch_size=bs * 2, sampler=val_sampler, collate_fn=collate_fn, **lkw)
 
     model = CNNAudioGRU(num_classes=config.get("num_labels", 31)).to(device)
+    # Two more YAML keys, both absent by default (= the reference: train everything from scratch).  `init_checkpoint`: a
+    # state dict or {'model_state_dict': ...} file whose body is kept and whose `fc` is re-initialised when its label set
+    # differs from `num_labels`; `freeze`: a list out of bn_stats / cnn / gru / attention (sir_amd/finetune.py).
+    if config.get("init_checkpoint"):
+        from sir_amd import finetune
+        report = finetune.load_pretrained(model, config["init_checkpoint"])
+        if rank == 0:
+            print(f"init_checkpoint: kept {len(report['kept'])} tensors, re-initialised {report['reset'] or 'nothing'}")
+    if config.get("freeze"):
+        from sir_amd import finetune
+        what = [config["freeze"]] if isinstance(config["freeze"], str) else list(config["freeze"])      # (a YAML scalar or a list)
+        trainable = finetune.freeze(model, what)
+        if rank == 0:
+            print(f"freeze {sorted(what)}: {len(trainable)} trainable tensors")
     train_ops.broadcast_module_(model)             # identical initial weights / BN buffers on every rank
     criterion = nn.CrossEntropyLoss()
-    optimizer = FusedAdam(model.parameters(), lr=float(config.get("lr", 0.0003)),
+    optimizer = FusedAdam([p for p in model.parameters() if p.requires_grad], lr=float(config.get("lr", 0.0003)),
                           weight_decay=float(config.get("weight_decay", 0.0001)))
     if config.get("use_amp", True) and rank == 0:
         print("use_amp requested: the HIP path computes in fp32 (parity with the fp32 CPU path); no GradScaler")

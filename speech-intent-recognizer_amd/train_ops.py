@@ -71,6 +71,21 @@ class GradBuffer:
         g.fc_w = by_name["fc.weight"].data_ptr()
         g.fc_b = by_name["fc.bias"].data_ptr()
         self.struct = g
+        # (named_parameters order: conv1.weight, bn1.weight, bn1.bias, conv2.weight, ... -- looked up by name, not by position)
+        self._slot = {}
+        for i in range(3):
+            self._slot[f"conv{i + 1}.weight"] = ("conv_w", i)
+            self._slot[f"bn{i + 1}.weight"] = ("bn_w", i)
+            self._slot[f"bn{i + 1}.bias"] = ("bn_b", i)
+        for i, suf in enumerate(ops.GRU_SUFFIXES):
+            self._slot["gru.weight_ih" + suf] = ("gru_w_ih", i)
+            self._slot["gru.weight_hh" + suf] = ("gru_w_hh", i)
+            self._slot["gru.bias_ih" + suf] = ("gru_b_ih", i)
+            self._slot["gru.bias_hh" + suf] = ("gru_b_hh", i)
+        for n, f in (("attention.weight", "attn_w"), ("attention.bias", "attn_b"), ("fc.weight", "fc_w"), ("fc.bias", "fc_b")):
+            self._slot[n] = (f, None)
+        self.names = [n for n, _ in mod.named_parameters()]
+        self._pruned = {}
         # the conv / BatchNorm gradients come first in named_parameters order; everything behind them (GRU, attention, fc)
         # is final after the first half of the backward
         self.n_cnn = sum(p.numel() for n, p in mod.named_parameters() if n.startswith(("conv", "bn")))
@@ -78,6 +93,70 @@ class GradBuffer:
         first_other = next(i for i, n in enumerate(names) if not n.startswith(("conv", "bn")))
         assert all(n.startswith(("conv", "bn")) for n in names[:first_other]) and \
             not any(n.startswith(("conv", "bn")) for n in names[first_other:]), "parameter order changed"
+
+
+    def struct_for(self, need):
+        """``sir_model_grads`` with NULL for every parameter whose gradient is not wanted (``need``: one bool per
+        parameter, ``named_parameters`` order): the backward then skips what only feeds those.  Returns the struct and
+        whether any conv / BatchNorm gradient is wanted."""
+        hit = self._pruned.get(need)                 # (keyed by autograd's own tuple: nothing is rebuilt per step)
+        if hit is not None:
+            return hit
+        key, need = need, tuple(bool(n) for n in need)
+        if all(need):
+            g = self.struct
+        else:
+            g = _native.ModelGrads()
+            for name, v, n in zip(self.names, self.views, need):
+                field, i = self._slot[name]
+                ptr = v.data_ptr() if n else None
+                if i is None:
+                    setattr(g, field, ptr)
+                else:
+                    getattr(g, field)[i] = ptr
+        cnn = any(n for name, n in zip(self.names, need) if name.startswith(("conv", "bn")))
+        self._pruned[key] = (g, cnn)
+        return g, cnn
+
+
+def bn_config(mod):
+    """``sir_train_config`` of the next step: ``bnK.training == False`` freezes that block's statistics, as in torch."""
+    key = (mod.bn1.training, mod.bn2.training, mod.bn3.training)
+    cfg = _configs.get(key)
+    if cfg is None:
+        cfg = _configs[key] = _native.TrainConfig()
+        for i in range(3):
+            cfg.bn_frozen[i] = 0 if key[i] else 1
+    return cfg
+
+
+_configs = {}
+
+
+def step_config(mod):
+    """(``sir_train_config``, dropout p) of the next step from the sub-modules' own flags, as torch reads them
+    (``gru.training == False`` turns the inter-layer dropout off)."""
+    return bn_config(mod), (float(mod.gru.dropout) if mod.gru.training else 0.0)
+
+
+_freeze_checked = set()
+
+
+def _check_same_freeze(need, cfg, device="cuda"):
+    """Data parallel: every rank must freeze the same set (the collectives are sized by it).  Checked once per set with
+    the MAX-reduce pattern of ``ops.check_status``: a 64-bit digest and its complement agree on all ranks only if equal."""
+    import torch.distributed as dist
+    key = (tuple(bool(n) for n in need), tuple(cfg.bn_frozen))
+    if key in _freeze_checked:
+        return
+    bits = sum(1 << i for i, b in enumerate(key[0] + tuple(bool(f) for f in key[1])) if b)
+    t = torch.tensor([bits, -bits], dtype=torch.int64, device=device)
+    dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    hi, neg_lo = (int(v) for v in t.tolist())
+    if hi != bits or -neg_lo != bits:
+        raise _native.SirError("the ranks of this job froze different parameter / BatchNorm sets: every rank must call "
+                               "finetune.freeze with the same arguments")
+    _freeze_checked.add(key)
 
 
 def _train_state(mod):
@@ -108,15 +187,19 @@ class _TrainStep(torch.autograd.Function):
         w, keep = ops.cached_weights(mod)
         rm, rv = _bn_ptr_arrays(mod)
         logits = torch.empty((bsz, w.num_classes), dtype=torch.float32, device=x.device)
+        cfg = bn_config(mod)
         seed = dropout_seed(next(_seed_counter))
         mod._sir_last_dropout = (seed, float(dropout_p))      # lets tests rebuild the mask (tests/dropout_host.py)
         momentum = float(mod.bn1.momentum if mod.bn1.momentum is not None else 0.1)
-        rc = lib.sir_model_train_fwd(h, C.byref(w), rm, rv, x.data_ptr(), bsz, t, momentum, float(dropout_p), seed,
-                                     logits.data_ptr(), ws.data_ptr(), ws.numel(), _native.current_stream_ptr())
-        _native.check(rc, "sir_model_train_fwd")
-        ops.bump_weights_epoch()                     # BN running statistics were updated in place
-        torch._foreach_add_([getattr(mod, f"bn{i}").num_batches_tracked for i in (1, 2, 3)], 1)
-        ctx.mod, ctx.x, ctx.seed, ctx.dropout_p, ctx.ws = mod, x, seed, float(dropout_p), ws
+        rc = lib.sir_model_train_fwd_cfg(h, C.byref(w), rm, rv, x.data_ptr(), bsz, t, momentum, float(dropout_p), seed,
+                                         C.byref(cfg), logits.data_ptr(), ws.data_ptr(), ws.numel(),
+                                         _native.current_stream_ptr())
+        _native.check(rc, "sir_model_train_fwd_cfg")
+        live = [getattr(mod, f"bn{i + 1}").num_batches_tracked for i in range(3) if not cfg.bn_frozen[i]]
+        if live:                                     # frozen statistics: nothing was written, cached layouts stay valid
+            ops.bump_weights_epoch()                 # BN running statistics were updated in place
+            torch._foreach_add_(live, 1)
+        ctx.mod, ctx.x, ctx.seed, ctx.dropout_p, ctx.ws, ctx.cfg = mod, x, seed, float(dropout_p), ws, cfg
         return logits
 
     @staticmethod
@@ -136,14 +219,18 @@ class _TrainStep(torch.autograd.Function):
             if p.grad is not None and p.grad.data_ptr() == v.data_ptr():
                 p.grad = p.grad.clone()
 
-        def run(part):
-            rc = lib.sir_model_train_bwd_part(h, C.byref(w), x.data_ptr(), dlogits.data_ptr(), bsz, t, ctx.dropout_p, ctx.seed,
-                                              C.byref(grads.struct), ctx.ws.data_ptr(), ctx.ws.numel(), part,
-                                              _native.current_stream_ptr())
-            _native.check(rc, "sir_model_train_bwd_part")
-
-        _exchange_and_scale(grads, run)
         need = ctx.needs_input_grad[3:]
+        gstruct, cnn = grads.struct_for(need)        # only the trainable views: NULL = not wanted, not computed
+        if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
+            _check_same_freeze(need, ctx.cfg)
+
+        def run(part):
+            rc = lib.sir_model_train_bwd_cfg(h, C.byref(w), x.data_ptr(), dlogits.data_ptr(), bsz, t, ctx.dropout_p, ctx.seed,
+                                             C.byref(ctx.cfg), C.byref(gstruct), ctx.ws.data_ptr(), ctx.ws.numel(), part,
+                                             _native.current_stream_ptr())
+            _native.check(rc, "sir_model_train_bwd_cfg")
+
+        _exchange_and_scale(grads, run, cnn=cnn)
         if HAND_OVER_GRADS and all(p.grad is None and not _has_grad_hooks(p) for p in params):
             # zero_grad(set_to_none=True) (train.py:90): the views of the flat buffer BECOME the .grad tensors; returning
             # them through autograd would make AccumulateGrad clone all 29 of them (29 copy launches per step)
@@ -154,9 +241,10 @@ class _TrainStep(torch.autograd.Function):
         return (None, None, None) + tuple(v if n else None for v, n in zip(grads.views, need))
 
 
-def _exchange_and_scale(grads, run):
+def _exchange_and_scale(grads, run, cnn=True):
     """The per-step gradient exchange around the two halves of the backward (``run(part)`` launches one half, or
-    nothing for a rank that has no batch)."""
+    nothing for a rank that has no batch).  ``cnn=False`` (every conv / BatchNorm parameter frozen): the second half and
+    its bucket are left out -- on every rank alike, ``zero_contribution_step`` included."""
     import torch.distributed as dist
     world = world_size()
     forced = FORCE_EXCHANGE and dist.is_available() and dist.is_initialized()
@@ -166,17 +254,19 @@ def _exchange_and_scale(grads, run):
         run(_native.BWD_HEAD_GRU)
         tail = grads.flat[grads.n_cnn:]
         work = dist.all_reduce(tail, op=dist.ReduceOp.SUM, async_op=True)
-        run(_native.BWD_CNN)
-        dist.all_reduce(grads.flat[:grads.n_cnn], op=dist.ReduceOp.SUM)
+        if cnn:
+            run(_native.BWD_CNN)
+            dist.all_reduce(grads.flat[:grads.n_cnn], op=dist.ReduceOp.SUM)
         work.wait()
-        grads.flat.mul_(1.0 / world)
+        (grads.flat if cnn else tail).mul_(1.0 / world)
     else:
         run(_native.BWD_ALL)
+        bucket = grads.flat if cnn else grads.flat[grads.n_cnn:]     # (a frozen CNN's region was not written: not exchanged)
         if forced:                              # un-overlapped form of the same exchange
-            dist.all_reduce(grads.flat, op=dist.ReduceOp.SUM)
-            grads.flat.mul_(1.0 / world)
+            dist.all_reduce(bucket, op=dist.ReduceOp.SUM)
+            bucket.mul_(1.0 / world)
         else:
-            all_reduce_mean_(grads.flat)        # the one exchange step of data-parallel training
+            all_reduce_mean_(bucket)            # the one exchange step of data-parallel training
 
 
 def zero_contribution_step(mod):
@@ -191,7 +281,8 @@ def zero_contribution_step(mod):
         if p.grad is not None and p.grad.data_ptr() == v.data_ptr():
             p.grad = None
     grads.flat.zero_()
-    _exchange_and_scale(grads, lambda part: None)
+    _exchange_and_scale(grads, lambda part: None,
+                        cnn=any(p.requires_grad for n, p in mod.named_parameters() if n.startswith(("conv", "bn"))))
     for p, v in zip(params, grads.views):
         if p.requires_grad:
             p.grad = v
@@ -199,10 +290,13 @@ def zero_contribution_step(mod):
 
 def forward_train(mod, x):
     """Training-mode forward of ``CNNAudioGRU`` (batch-statistics BN, inter-layer dropout
-    ``mod.gru.dropout``), differentiable wrt the module's parameters."""
+    ``mod.gru.dropout``), differentiable wrt the module's parameters.  The sub-modules' own flags are honoured as torch
+    honours them: ``bnK.eval()`` freezes that block's statistics (forward and backward), ``gru.eval()`` turns the dropout
+    off, and a parameter with ``requires_grad == False`` gets no gradient -- the backward stops where the trainable
+    parameters stop (``sir_model_train_bwd_cfg``)."""
     _native.require_hip(x)
     x = ops._as_features(x)
-    return _TrainStep.apply(x, mod, float(mod.gru.dropout), *param_list(mod))
+    return _TrainStep.apply(x, mod, step_config(mod)[1], *param_list(mod))
 
 
 class _FusedCE(torch.autograd.Function):

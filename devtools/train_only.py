@@ -25,6 +25,9 @@ def main():
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--tag", default="")
     ap.add_argument("--freeze", default="", help="comma-separated subset of bn_stats,cnn,gru,attention (sir_amd/finetune.py): time a fine-tuning step")
+    ap.add_argument("--mixup", type=float, default=0.0, help="alpha: mix every batch with a permutation of itself (train_ops.Mixup)")
+    ap.add_argument("--label-smoothing", type=float, default=0.0)
+    ap.add_argument("--clip", type=float, default=0.0, help="max_norm: FusedAdam(max_grad_norm=...)")
     ap.add_argument("--kernels", default="", help="comma-separated substrings: only these kernel averages are printed")
     args = ap.parse_args()
     import bench
@@ -46,12 +49,20 @@ def main():
     lengths = torch.full((args.batch,), bench.CLIP_LEN, dtype=torch.int32, device=dev)
     labels = torch.randint(0, bench.NUM_CLASSES, (args.batch,), device=dev)
     feats = torch.empty(args.batch, 64, bench.T_PAD, device=dev)
-    opt = FusedAdam([p for p in model.parameters() if p.requires_grad], lr=5e-5, weight_decay=1e-4)
+    opt = FusedAdam([p for p in model.parameters() if p.requires_grad], lr=5e-5, weight_decay=1e-4,
+                    max_grad_norm=args.clip or None)
+    mixup = train_ops.Mixup(args.mixup, seed=0) if args.mixup else None
 
     def step(i):
         x = fz(pool[i % 4], lengths, t_pad=bench.T_PAD, out=feats)
         opt.zero_grad(set_to_none=True)
-        loss = train_ops.fused_cross_entropy(model(x), labels)
+        if mixup is not None:
+            x, labels_b, lam = mixup(x, labels)
+            loss = train_ops.fused_cross_entropy(model(x), labels, labels_b, lam, label_smoothing=args.label_smoothing)
+        elif args.label_smoothing:
+            loss = train_ops.fused_cross_entropy(model(x), labels, label_smoothing=args.label_smoothing)
+        else:
+            loss = train_ops.fused_cross_entropy(model(x), labels)
         loss.backward()
         opt.step()
         return loss
@@ -83,7 +94,8 @@ def main():
         times.append((time.perf_counter() - t0) / args.steps * 1e3)
     ops.check_status()
     sw = {k: v for k, v in os.environ.items() if k.startswith("SIR_")}
-    print(json.dumps({"tag": args.tag, "freeze": args.freeze, "env": sw, "ms_per_step_median": round(statistics.median(times), 4),
+    print(json.dumps({"tag": args.tag, "freeze": args.freeze, "mixup": args.mixup, "label_smoothing": args.label_smoothing,
+                      "clip": args.clip, "env": sw, "ms_per_step_median": round(statistics.median(times), 4),
                       "ms_per_step_min": round(min(times), 4), "ms_per_step_max": round(max(times), 4),
                       "loss": round(float(loss), 6), "kernels_us": kern}), flush=True)
 

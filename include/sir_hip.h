@@ -159,6 +159,18 @@ int sir_gather_features(sir_handle* h, const float* store, int64_t n_store, cons
                         int n_mels, int t_pad, const int32_t* time_mask, const int32_t* freq_mask, float* out,
                         void* stream);
 
+/* sir_mix_features: mixup (Zhang et al. 2018) on an ASSEMBLED feature batch -- after each item's own SpecAugment bands, so
+ * that it serves every data route (sir_gather_features, a DataLoader batch, sir_features_fwd).  Replaces the torch lines
+ * `x = lam * x + (1 - lam) * x[perm]`; the reference has no mixup (its configs/config.yaml carries an unread `mixup_alpha`).
+ *   x    : [batch][n_mels][t] f32, 16-byte aligned, t a multiple of 4 (else SIR_EINVAL)
+ *   perm : device int64[batch], batch-local partner rows; an entry outside [0, batch) yields a zero row and SIR_EINVAL at
+ *          the next sir_check_status
+ *   lam  : device f32[batch]
+ *   out  : [batch][n_mels][t] f32, must not alias x; out[b] = fmaf(lam[b], x[b], (1.0f - lam[b]) * x[perm[b]]) in fp32,
+ *          and a row with lam[b] == 1.0f is a bit-exact copy of x[b] whatever its partner holds (select, not multiply) */
+int sir_mix_features(sir_handle* h, const float* x, const int64_t* perm, const float* lam, int batch, int n_mels, int t,
+                     float* out, void* stream);
+
 /* ---- model path ----------------------------------------------------------------------------
  * Device pointers to the reference's parameters/buffers under their state_dict names
  * (models/models.py:10-39): index 0..2 = conv1..3 / bn1..3; GRU index = 2*layer + reverse. */
@@ -213,7 +225,7 @@ int sir_model_infer(sir_handle* h, const sir_model_weights* w, const float* feat
  * recurrence launched on this handle since the last check timed out (and clears the word), SIR_OK otherwise.
  * Call it wherever the host synchronises anyway -- once per batch of predictions (scripts/evaluate.py:85-86's
  * .cpu()) or per epoch (scripts/train.py:116's loss.item()); sir_profile_collect performs the same check.
- * The same word carries sir_ce_loss's "label outside [0, num_classes)" flag (nn.CrossEntropyLoss raises on such a
+ * The same word carries sir_ce_loss's / sir_ce_loss_soft's "label outside [0, num_classes)" flag (nn.CrossEntropyLoss raises on such a
  * target, train.py:242/:105; the kernel makes that step's loss NaN): reported here as SIR_EINVAL. */
 int sir_check_status(sir_handle* h, void* stream);
 
@@ -276,6 +288,21 @@ int sir_model_train_fwd(sir_handle* h, const sir_model_weights* w, float* const 
 int sir_ce_loss(sir_handle* h, const float* logits, const int64_t* labels, int batch, int num_classes,
                 float* loss, float* dlogits, float grad_scale, void* stream);
 
+/* sir_ce_loss with a soft target q_b = (1 - eps) * (lam_b * e[ya_b] + (1 - lam_b) * e[yb_b]) + eps / C:
+ *   loss = mean over non-ignored rows of -sum_c q_b[c] * log softmax(logits_b)[c]
+ *   dlogits_b = (softmax(logits_b) - q_b) * grad_scale / n_valid
+ * i.e. what torch computes for lam * F.cross_entropy(l, ya, label_smoothing=eps) + (1 - lam) * F.cross_entropy(l, yb,
+ * label_smoothing=eps) with a per-row lam (mixup's loss, and nn.CrossEntropyLoss(label_smoothing=eps) without labels_b).
+ *   labels_b        : device int64[batch], NULL = no second label
+ *   lam             : device f32[batch], NULL = all 1; read only when labels_b is given
+ *   label_smoothing : host float in [0, 1) (else SIR_EINVAL)
+ * A row is ignored iff labels_a[b] == -100 (labels_b of such a row is not read); any other label of either array outside
+ * [0, num_classes) makes the loss NaN and is reported by sir_check_status (SIR_EINVAL), as for sir_ce_loss.  With
+ * labels_b == NULL and label_smoothing == 0 the results are bit-identical to sir_ce_loss (the same kernel is launched). */
+int sir_ce_loss_soft(sir_handle* h, const float* logits, const int64_t* labels_a, const int64_t* labels_b, const float* lam,
+                     float label_smoothing, int batch, int num_classes, float* loss, float* dlogits, float grad_scale,
+                     void* stream);
+
 /* loss.backward() (train.py:106): all 29 parameter gradients from dlogits and the saved workspace. */
 int sir_model_train_bwd(sir_handle* h, const sir_model_weights* w, const float* feats, const float* dlogits,
                         int batch, int t_frames, float dropout_p, uint64_t dropout_seed,
@@ -329,6 +356,31 @@ int sir_model_train_bwd_cfg(sir_handle* h, const sir_model_weights* w, const flo
 int sir_adam_step(sir_handle* h, int n_tensors, float* const* params, const float* const* grads,
                   float* const* exp_avg, float* const* exp_avg_sq, const int64_t* sizes, int step,
                   float lr, float beta1, float beta2, float eps, float weight_decay, void* stream);
+
+/* ---- gradient norm and clipping ----------------------------------------------------------------
+ * torch.nn.utils.clip_grad_norm_(parameters, max_norm) (norm_type 2, error_if_nonfinite=False) between loss.backward() and
+ * optimizer.step(); the reference's configs/config.yaml carries an unread `grad_clip`.  The gradient tensors are described
+ * as for sir_adam_step (HOST arrays of device pointers and element counts, n_tensors <= 32).
+ * sir_grad_norm_partials: host helper, the number of floats `partials` must hold (one per 4096-element chunk of every
+ *   tensor); -1 on bad input.  The library allocates nothing.
+ * sir_grad_norm: launch 1 writes one fp32 sum of squares per chunk into `partials` (ordered in-block reduction).  Launch 2
+ *   sums the partials in index order in double and writes out2 = {total_norm, coef} (device f32[2]),
+ *   coef = min(1, max_norm / (total_norm + 1e-6)); with scale_in_place != 0 it runs over the gradients' grid, every
+ *   workgroup forms the same sum itself and multiplies its chunk by coef (torch's in-place semantics: a non-finite norm
+ *   leaves non-finite gradients; nothing is skipped).  No atomics: the norm is bit-reproducible run to run.
+ *   out2 == NULL (scale_in_place must be 0): launch 1 only -- the partials are then consumed by sir_adam_step_clipped.
+ *   max_norm <= 0 or NaN: SIR_EINVAL (not looked at when out2 == NULL); partials_floats too small: SIR_ENOMEM.
+ * sir_adam_step_clipped: sir_adam_step on g * coef (rounded to fp32, taken before the weight-decay term -- the order of
+ *   clip_grad_norm_ followed by optimizer.step()), coef formed from `partials` (n_partials floats, as sir_grad_norm left
+ *   them for the SAME tensors) exactly as sir_grad_norm forms it.  The gradient buffers are left unscaled; workgroup 0
+ *   writes out2 = {total_norm, coef}.  Nothing synchronises with the host: coef never leaves the device. */
+int sir_grad_norm_partials(int n_tensors, const int64_t* sizes);
+int sir_grad_norm(sir_handle* h, int n_tensors, float* const* grads, const int64_t* sizes, float max_norm, float* partials,
+                  int partials_floats, float* out2, int scale_in_place, void* stream);
+int sir_adam_step_clipped(sir_handle* h, int n_tensors, float* const* params, const float* const* grads,
+                          float* const* exp_avg, float* const* exp_avg_sq, const int64_t* sizes, int step, float lr,
+                          float beta1, float beta2, float eps, float weight_decay, const float* partials, int n_partials,
+                          float max_norm, float* out2, void* stream);
 
 /* ---- measurement -----------------------------------------------------------------------------
  * HIP-event timing of the kernels of the path, recorded on the stream they are launched on

@@ -71,6 +71,8 @@ SIGNATURES = {
                                    C.c_void_p, C.c_size_t, C.c_void_p]),
     "sir_gather_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
+    "sir_mix_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                   C.c_void_p]),
     "sir_model_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "sir_model_workspace_offsets": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.c_int]),
     "sir_model_set_weights_version": (C.c_int, [C.c_void_p, C.c_uint64]),
@@ -87,6 +89,8 @@ SIGNATURES = {
                                       C.c_void_p, C.c_size_t, C.c_void_p]),
     "sir_ce_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_float,
                               C.c_void_p]),
+    "sir_ce_loss_soft": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_int,
+                                   C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
     "sir_model_train_bwd": (C.c_int, [C.c_void_p, C.POINTER(ModelWeights), C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                       C.c_float, C.c_uint64, C.POINTER(ModelGrads), C.c_void_p, C.c_size_t, C.c_void_p]),
     "sir_model_train_bwd_part": (C.c_int, [C.c_void_p, C.POINTER(ModelWeights), C.c_void_p, C.c_void_p, C.c_int, C.c_int,
@@ -102,6 +106,12 @@ SIGNATURES = {
     "sir_adam_step": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                 C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int, C.c_float, C.c_float, C.c_float,
                                 C.c_float, C.c_float, C.c_void_p]),
+    "sir_grad_norm_partials": (C.c_int, [C.c_int, C.POINTER(C.c_int64)]),
+    "sir_grad_norm": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_float, C.c_void_p,
+                                C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "sir_adam_step_clipped": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                        C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int, C.c_float, C.c_float, C.c_float,
+                                        C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "sir_profile_kernel_count": (C.c_int, []),
     "sir_profile_kernel_name": (C.c_char_p, [C.c_int]),
     "sir_profile_enable": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),

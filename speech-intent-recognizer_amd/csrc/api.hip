@@ -256,7 +256,8 @@ static const char* const kKernelNames[SIR_K_COUNT] = {
     "train_weight_prep", "train_conv1_fwd", "train_conv2_fwd", "train_bn2_relu_pool", "train_conv3_fwd", "train_bn3_relu_pool",
     "train_gemm_ih_l0", "train_gru_l0", "train_dropout", "train_gemm_ih_l1", "train_gru_l1", "train_attention_fc", "ce_loss",
     "bwd_head", "bwd_gru_l1", "bwd_gru_dw_l1", "bwd_gru_dx_l1", "bwd_gru_l0", "bwd_gru_dw_l0", "bwd_gru_dx_l0",
-    "bwd_bn3", "bwd_conv3_wgrad", "bwd_conv3_dgrad", "bwd_bn2", "bwd_conv2_wgrad", "bwd_conv2_dgrad", "bwd_conv1", "adam"};
+    "bwd_bn3", "bwd_conv3_wgrad", "bwd_conv3_dgrad", "bwd_bn2", "bwd_conv2_wgrad", "bwd_conv2_dgrad", "bwd_conv1", "adam",
+    "mix_features", "grad_sumsq", "grad_norm_clip", "adam_clipped"};
 
 extern "C" int sir_profile_kernel_count(void) { return SIR_K_COUNT; }
 extern "C" const char* sir_profile_kernel_name(int id) { return (id >= 0 && id < SIR_K_COUNT) ? kKernelNames[id] : ""; }
@@ -289,6 +290,10 @@ static int check_status_impl(sir_handle* h, hipStream_t st, const char* who) {
     if (v & 16u) {
         sir_set_error("%s: sir_wave_perturb was given a pitch outside [-200, 200] cents or a tempo outside [0.5, 2] (status %u): "
                       "those rows are zero with length 0", who, v);
+        return SIR_EINVAL;
+    }
+    if (v & 32u) {
+        sir_set_error("%s: sir_mix_features was given a permutation entry outside [0, batch) (status %u): those rows are zero", who, v);
         return SIR_EINVAL;
     }
     if (v & 4u) {

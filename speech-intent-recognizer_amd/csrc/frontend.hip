@@ -236,3 +236,56 @@ extern "C" int sir_gather_features(sir_handle* h, const float* store, int64_t n_
                        (long long)n_store, n_mels, t_pad, (const int*)time_mask, (const int*)freq_mask, out, h->status);
     return sir_check_hip(hipGetLastError(), "gather_features_kernel");
 }
+
+// ---- mixup on an assembled feature batch ----------------------------------------------------------------------------------
+// out[b] = lam[b] x[b] + (1 - lam[b]) x[perm[b]], float4 per thread.  lam == 1 SELECTS the row (the partner is not even read:
+// its Inf / NaN cannot leak into an unmixed row through 0 * Inf).  Arithmetic: fmaf(lam, a, (1 - lam) * b), two roundings.
+namespace {
+__device__ __forceinline__ float mix1(float lam, float om, float a, float b) { return fmaf(lam, a, __fmul_rn(om, b)); }
+
+__global__ __launch_bounds__(256) void mix_features_kernel(const float* __restrict__ x, const long long* __restrict__ perm,
+                                                           const float* __restrict__ lam, int batch, int per,
+                                                           float* __restrict__ out, unsigned int* __restrict__ status) {
+    const int b = blockIdx.y;
+    long long src = perm[b];
+    const bool bad = src < 0 || src >= (long long)batch;
+    if (bad) {                                              // zeros + the handle's status word (SIR_EINVAL at the next check)
+        if (threadIdx.x == 0 && blockIdx.x == 0) __hip_atomic_fetch_or(status, 32u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        src = 0;
+    }
+    const float l = lam[b], om = 1.0f - l;
+    const bool copy = l == 1.0f;
+    const float4* a4 = reinterpret_cast<const float4*>(x) + (size_t)b * per;
+    const float4* b4 = reinterpret_cast<const float4*>(x) + (size_t)src * per;
+    float4* o4 = reinterpret_cast<float4*>(out) + (size_t)b * per;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < per; i += gridDim.x * 256) {
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (!bad) {
+            v = a4[i];
+            if (!copy) {
+                const float4 w = b4[i];
+                v = make_float4(mix1(l, om, v.x, w.x), mix1(l, om, v.y, w.y), mix1(l, om, v.z, w.z), mix1(l, om, v.w, w.w));
+            }
+        }
+        o4[i] = v;
+    }
+}
+}  // namespace
+
+extern "C" int sir_mix_features(sir_handle* h, const float* x, const int64_t* perm, const float* lam, int batch, int n_mels, int t,
+                                float* out, void* stream) {
+    if (!h || !x || !perm || !lam || !out) { sir_set_error("sir_mix_features: NULL argument"); return SIR_EINVAL; }
+    if (batch <= 0 || batch > 65535 || n_mels <= 0 || t <= 0 || (t & 3) != 0 || (long long)n_mels * t > (1ll << 30)) {
+        sir_set_error("sir_mix_features: bad sizes (batch %d, n_mels %d, t %d: t must be a multiple of 4)", batch, n_mels, t);
+        return SIR_EINVAL;
+    }
+    if (out == x) { sir_set_error("sir_mix_features: out must not alias x (a row is also another row's partner)"); return SIR_EINVAL; }
+    if ((((uintptr_t)x) | ((uintptr_t)out)) & 15u) { sir_set_error("sir_mix_features: x and out must be 16-byte aligned"); return SIR_EINVAL; }
+    const int per = n_mels * t / 4;
+    int gx = (per + 255) / 256;
+    gx = gx > 16 ? 16 : gx;
+    SirProfScope prof(h, SIR_K_MIX, (hipStream_t)stream);
+    hipLaunchKernelGGL(mix_features_kernel, dim3(gx, batch), dim3(256), 0, (hipStream_t)stream, x, (const long long*)perm, lam, batch, per,
+                       out, h->status);
+    return sir_check_hip(hipGetLastError(), "mix_features_kernel");
+}

@@ -424,19 +424,39 @@ extern "C" int sir_model_train_fwd_cfg(sir_handle* h, const sir_model_weights* w
     return SIR_OK;
 }
 
-extern "C" int sir_ce_loss(sir_handle* h, const float* logits, const int64_t* labels, int batch, int num_classes,
-                           float* loss, float* dlogits, float grad_scale, void* stream_) {
-    if (!h || !logits || !labels || !loss) { sir_set_error("sir_ce_loss: NULL argument"); return SIR_EINVAL; }
-    if (batch < 1 || num_classes < 1 || num_classes > 64) { sir_set_error("sir_ce_loss: bad shape batch=%d num_classes=%d (1..64)", batch, num_classes); return SIR_EINVAL; }
-    SirProfScope prof(h, SIR_K_CE, (hipStream_t)stream_);
-    if (num_classes <= 32)
-        hipLaunchKernelGGL(ce_loss_kernel<32>, dim3(1), dim3(256), 0, (hipStream_t)stream_, logits, (const long long*)labels, batch,
-                           num_classes, loss, dlogits, grad_scale, h->status);
-    else
-        hipLaunchKernelGGL(ce_loss_kernel<64>, dim3(1), dim3(256), 0, (hipStream_t)stream_, logits, (const long long*)labels, batch,
-                           num_classes, loss, dlogits, grad_scale, h->status);
+// sir_ce_loss and sir_ce_loss_soft share one kernel template; a hard target (no second label, no smoothing) takes the
+// instantiation sir_ce_loss has always launched, so the two entry points agree bit for bit there.
+static int ce_loss_launch(sir_handle* h, const char* who, const float* logits, const int64_t* labels, const int64_t* labels_b,
+                          const float* lam, float eps, int batch, int num_classes, float* loss, float* dlogits, float grad_scale,
+                          hipStream_t st) {
+    if (!h || !logits || !labels || !loss) { sir_set_error("%s: NULL argument", who); return SIR_EINVAL; }
+    if (batch < 1 || num_classes < 1 || num_classes > 64) { sir_set_error("%s: bad shape batch=%d num_classes=%d (1..64)", who, batch, num_classes); return SIR_EINVAL; }
+    if (!(eps >= 0.0f && eps < 1.0f)) { sir_set_error("%s: label_smoothing %g outside [0, 1)", who, (double)eps); return SIR_EINVAL; }
+    const long long* la = (const long long*)labels;
+    const long long* lb = (const long long*)labels_b;
+    const bool soft = labels_b != nullptr || eps != 0.0f;
+    SirProfScope prof(h, SIR_K_CE, st);
+#define SIR_CE_LAUNCH(CMAX, SOFT) \
+    hipLaunchKernelGGL((ce_loss_kernel<CMAX, SOFT>), dim3(1), dim3(256), 0, st, logits, la, batch, num_classes, loss, dlogits, grad_scale, \
+                       h->status, lb, lam, eps)
+    if (num_classes <= 32) { if (soft) SIR_CE_LAUNCH(32, true); else SIR_CE_LAUNCH(32, false); }
+    else                   { if (soft) SIR_CE_LAUNCH(64, true); else SIR_CE_LAUNCH(64, false); }
+#undef SIR_CE_LAUNCH
     SIR_KCHECK();
     return SIR_OK;
+}
+
+extern "C" int sir_ce_loss(sir_handle* h, const float* logits, const int64_t* labels, int batch, int num_classes,
+                           float* loss, float* dlogits, float grad_scale, void* stream_) {
+    return ce_loss_launch(h, "sir_ce_loss", logits, labels, nullptr, nullptr, 0.0f, batch, num_classes, loss, dlogits, grad_scale,
+                          (hipStream_t)stream_);
+}
+
+extern "C" int sir_ce_loss_soft(sir_handle* h, const float* logits, const int64_t* labels_a, const int64_t* labels_b,
+                                const float* lam, float label_smoothing, int batch, int num_classes, float* loss, float* dlogits,
+                                float grad_scale, void* stream_) {
+    return ce_loss_launch(h, "sir_ce_loss_soft", logits, labels_a, labels_b, lam, label_smoothing, batch, num_classes, loss, dlogits,
+                          grad_scale, (hipStream_t)stream_);
 }
 
 extern "C" int sir_model_train_bwd(sir_handle* h, const sir_model_weights* w, const float* feats, const float* dlogits,
@@ -799,6 +819,74 @@ extern "C" int sir_adam_step(sir_handle* h, int n_tensors, float* const* params,
     SirProfScope prof(h, SIR_K_ADAM, (hipStream_t)stream_);
     hipLaunchKernelGGL(adam_multi_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, ts, lr, beta1, beta2, eps, weight_decay,
                        (float)bc1, (float)sqrt(bc2));
+    SIR_KCHECK();
+    return SIR_OK;
+}
+
+// ---- global gradient norm, clipping, clipped Adam ---------------------------------------------------------------------
+static int grad_blocks(int n_tensors, const int64_t* sizes) {
+    if (!sizes || n_tensors < 1 || n_tensors > SIR_ADAM_MAX_TENSORS) return -1;
+    long long blocks = 0;
+    for (int i = 0; i < n_tensors; ++i) {
+        if (sizes[i] < 0) return -1;
+        blocks += (sizes[i] + SIR_ADAM_CHUNK - 1) / SIR_ADAM_CHUNK;
+    }
+    return blocks > 0 && blocks < (1ll << 30) ? (int)blocks : -1;
+}
+
+extern "C" int sir_grad_norm_partials(int n_tensors, const int64_t* sizes) { return grad_blocks(n_tensors, sizes); }
+
+extern "C" int sir_grad_norm(sir_handle* h, int n_tensors, float* const* grads, const int64_t* sizes, float max_norm,
+                             float* partials, int partials_floats, float* out2, int scale_in_place, void* stream_) {
+    if (!h || !grads || !sizes || !partials) { sir_set_error("sir_grad_norm: NULL argument"); return SIR_EINVAL; }
+    const int blocks = grad_blocks(n_tensors, sizes);
+    if (blocks < 0) { sir_set_error("sir_grad_norm: n_tensors=%d (1..%d) or a bad size", n_tensors, SIR_ADAM_MAX_TENSORS); return SIR_EINVAL; }
+    if (partials_floats < blocks) { sir_set_error("sir_grad_norm: partials holds %d floats, %d needed", partials_floats, blocks); return SIR_ENOMEM; }
+    if (scale_in_place && !out2) { sir_set_error("sir_grad_norm: scale_in_place needs out2"); return SIR_EINVAL; }
+    if (out2 && !(max_norm > 0.0f)) { sir_set_error("sir_grad_norm: max_norm %g must be > 0", (double)max_norm); return SIR_EINVAL; }
+    GradTensors ts;
+    int b = 0;
+    for (int i = 0; i < n_tensors; ++i) {
+        if (!grads[i] && sizes[i] > 0) { sir_set_error("sir_grad_norm: NULL gradient %d", i); return SIR_EINVAL; }
+        ts.g[i] = grads[i]; ts.n[i] = sizes[i]; ts.first_block[i] = b;
+        b += (int)((sizes[i] + SIR_ADAM_CHUNK - 1) / SIR_ADAM_CHUNK);
+    }
+    ts.first_block[n_tensors] = b;
+    ts.count = n_tensors;
+    hipStream_t st = (hipStream_t)stream_;
+    { SirProfScope prof(h, SIR_K_GRAD_SUMSQ, st);
+      hipLaunchKernelGGL(grad_sumsq_kernel, dim3(blocks), dim3(256), 0, st, ts, partials);
+      SIR_KCHECK(); }
+    if (!out2) return SIR_OK;
+    SirProfScope prof(h, SIR_K_GRAD_CLIP, st);
+    if (scale_in_place)
+        hipLaunchKernelGGL(grad_scale_kernel, dim3(blocks), dim3(256), 0, st, ts, (const float*)partials, blocks, max_norm, out2);
+    else
+        hipLaunchKernelGGL(grad_norm_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)partials, blocks, max_norm, out2);
+    SIR_KCHECK();
+    return SIR_OK;
+}
+
+extern "C" int sir_adam_step_clipped(sir_handle* h, int n_tensors, float* const* params, const float* const* grads,
+                                     float* const* exp_avg, float* const* exp_avg_sq, const int64_t* sizes, int step, float lr,
+                                     float beta1, float beta2, float eps, float weight_decay, const float* partials,
+                                     int n_partials, float max_norm, float* out2, void* stream_) {
+    if (!h || !params || !grads || !exp_avg || !exp_avg_sq || !sizes || !partials || !out2) { sir_set_error("sir_adam_step_clipped: NULL argument"); return SIR_EINVAL; }
+    if (n_tensors < 1 || n_tensors > SIR_ADAM_MAX_TENSORS || step < 1) { sir_set_error("sir_adam_step_clipped: n_tensors=%d step=%d", n_tensors, step); return SIR_EINVAL; }
+    if (!(max_norm > 0.0f) || n_partials < 1) { sir_set_error("sir_adam_step_clipped: max_norm %g must be > 0, n_partials %d >= 1", (double)max_norm, n_partials); return SIR_EINVAL; }
+    AdamTensors ts;
+    int blocks = 0;
+    for (int i = 0; i < n_tensors; ++i) {
+        ts.p[i] = params[i]; ts.g[i] = grads[i]; ts.m[i] = exp_avg[i]; ts.v[i] = exp_avg_sq[i]; ts.n[i] = sizes[i];
+        ts.first_block[i] = blocks;
+        blocks += (int)((sizes[i] + SIR_ADAM_CHUNK - 1) / SIR_ADAM_CHUNK);
+    }
+    ts.first_block[n_tensors] = blocks;
+    ts.count = n_tensors;
+    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
+    SirProfScope prof(h, SIR_K_ADAM_CLIPPED, (hipStream_t)stream_);
+    hipLaunchKernelGGL(adam_multi_clipped_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream_, ts, lr, beta1, beta2, eps,
+                       weight_decay, (float)bc1, (float)sqrt(bc2), partials, n_partials, max_norm, out2);
     SIR_KCHECK();
     return SIR_OK;
 }

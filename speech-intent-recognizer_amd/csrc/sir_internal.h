@@ -23,6 +23,8 @@ enum SirKernelId {
     SIR_K_T_DROPOUT, SIR_K_T_GEMM_IH1, SIR_K_T_GRU1, SIR_K_T_HEAD, SIR_K_CE,
     SIR_K_B_HEAD, SIR_K_B_GRU1, SIR_K_B_DW1, SIR_K_B_DX1, SIR_K_B_GRU0, SIR_K_B_DW0, SIR_K_B_DX0,
     SIR_K_B_BN3, SIR_K_B_WGRAD3, SIR_K_B_DGRAD3, SIR_K_B_BN2, SIR_K_B_WGRAD2, SIR_K_B_DGRAD2, SIR_K_B_CONV1, SIR_K_ADAM,
+    // training recipe (appended: the ids above keep their meaning): batch mixing, gradient norm / clip, clipped Adam
+    SIR_K_MIX, SIR_K_GRAD_SUMSQ, SIR_K_GRAD_CLIP, SIR_K_ADAM_CLIPPED,
     SIR_K_COUNT
 };
 

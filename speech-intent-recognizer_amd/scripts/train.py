@@ -45,13 +45,26 @@ def collate_fn(batch):
 
 
 def _loss_fn(criterion):
-    """The HIP cross-entropy when the criterion is the reference's ``nn.CrossEntropyLoss()``
-    (mean reduction, no weights / smoothing, train.py:242); any other criterion is called as is."""
+    """The HIP cross-entropy when the criterion is the reference's ``nn.CrossEntropyLoss()`` (mean reduction, no
+    weights, default ``ignore_index``, train.py:242) or that with ``label_smoothing=eps`` (``sir_ce_loss_soft``); any
+    other criterion is called as is."""
+    import functools
     from sir_amd import train_ops
     if (isinstance(criterion, nn.CrossEntropyLoss) and criterion.reduction == "mean" and criterion.weight is None
-            and criterion.label_smoothing == 0.0 and criterion.ignore_index == -100):
-        return train_ops.fused_cross_entropy
+            and criterion.ignore_index == -100):
+        if criterion.label_smoothing == 0.0:
+            return train_ops.fused_cross_entropy
+        return functools.partial(train_ops.fused_cross_entropy, label_smoothing=float(criterion.label_smoothing))
     return criterion
+
+
+def _mixed_loss(loss_fn, output, label, label_b, lam):
+    """The loss of a mixed batch: the HIP loss takes both labels; a foreign criterion is weighed as mixup defines it
+    (``lam`` holds one value per batch, repeated per row)."""
+    from sir_amd import train_ops
+    if getattr(loss_fn, "func", loss_fn) is train_ops.fused_cross_entropy:
+        return loss_fn(output, label, label_b, lam)
+    return lam[0] * loss_fn(output, label) + (1.0 - lam[0]) * loss_fn(output, label_b)
 
 
 class HostStager:
@@ -100,10 +113,11 @@ def loader_kwargs(num_workers):
     return kw
 
 
-def train_epoch(model, train_loader, optimizer, criterion, device, scaler=None):
+def train_epoch(model, train_loader, optimizer, criterion, device, scaler=None, mixup=None):
     """One epoch (train.py:72-118); returns the mean of the per-step losses.  ``scaler`` is accepted
     for signature compatibility: the HIP path always computes in fp32 (the parity target is the fp32
-    CPU path), so no loss scaling is needed or applied."""
+    CPU path), so no loss scaling is needed or applied.  ``mixup`` (a ``train_ops.Mixup``): every assembled batch is
+    mixed with a permutation of itself on the GPU and the loss takes both label sets."""
     from sir_amd import ops, train_ops
     model.train()
     loss_fn = _loss_fn(criterion)
@@ -122,8 +136,12 @@ def train_epoch(model, train_loader, optimizer, criterion, device, scaler=None):
         mel = stage(mel)                                   # host batches: persistent pinned ring (see HostStager)
         label = stage(label)
         optimizer.zero_grad(set_to_none=True)
-        output = model(mel)
-        loss = loss_fn(output, label)
+        if mixup is not None:
+            mel, label_b, lam = mixup(mel, label)
+            loss = _mixed_loss(loss_fn, model(mel), label, label_b, lam)
+        else:
+            output = model(mel)
+            loss = loss_fn(output, label)
         loss.backward()
         optimizer.step()
         losses.append(loss.detach())
@@ -135,7 +153,7 @@ def train_epoch(model, train_loader, optimizer, criterion, device, scaler=None):
     return mean
 
 
-def train_epoch_waveforms(model, wave_loader, optimizer, criterion, device, t_pad=200, augment=None):
+def train_epoch_waveforms(model, wave_loader, optimizer, criterion, device, t_pad=200, augment=None, mixup=None):
     """``train_epoch`` fed with RAW waveform batches: ``wave_loader`` yields ``(wave [B, L] float32 | int16, lengths int32
     [B] | None, label int64 [B])``; the log-mel features are computed on the GPU (BASELINE configs[2]: fused HIP feature
     extraction + forward/backward + Adam) one batch ahead of the training step on a side stream
@@ -144,6 +162,7 @@ def train_epoch_waveforms(model, wave_loader, optimizer, criterion, device, t_pa
     ``augment(wave_batch_index, batch_size, host_lengths | None) -> dict`` may return the featurizer's on-the-fly
     augmentation arguments (``shift``, ``noise_sigma``, ``noise_seed``, ``time_mask``, ``freq_mask``: scripts/augment.py,
     dataset.py:160-176) for that batch, and ``pitch_cents`` / ``tempo`` (``sir_wave_perturb`` ahead of the feature kernel).
+    ``mixup`` as for ``train_epoch``: applied to the computed feature batch, after its SpecAugment bands.
     Returns the mean of the per-step losses."""
     from sir_amd import ops
     from sir_amd.pipeline import FeaturePrefetcher
@@ -166,7 +185,11 @@ def train_epoch_waveforms(model, wave_loader, optimizer, criterion, device, t_pa
     def step():
         mel, label = pre.get(), pending.pop(0)
         optimizer.zero_grad(set_to_none=True)
-        loss = loss_fn(model(mel), label)
+        if mixup is not None:
+            mixed, label_b, lam = mixup(mel, label)
+            loss = _mixed_loss(loss_fn, model(mixed), label, label_b, lam)
+        else:
+            loss = loss_fn(model(mel), label)
         loss.backward()
         optimizer.step()
         pre.release()
@@ -326,9 +349,16 @@ def train(args, config):
         if rank == 0:
             print(f"freeze {sorted(what)}: {len(trainable)} trainable tensors")
     train_ops.broadcast_module_(model)             # identical initial weights / BN buffers on every rank
+    # Three more YAML keys, all absent by default (= the reference's step: hard labels, unclipped gradients).
+    # `label_smoothing: <eps>` and `mixup: <alpha>` change the training loss (validation keeps the plain criterion);
+    # `clip_grad_norm: <max_norm>` clips the global gradient norm inside the optimizer step.  The reference's own
+    # `grad_clip` / `mixup_alpha` keys stay unread, as the reference leaves them.
     criterion = nn.CrossEntropyLoss()
+    train_criterion = nn.CrossEntropyLoss(label_smoothing=float(config["label_smoothing"])) if config.get("label_smoothing") else criterion
+    mixup = train_ops.Mixup(float(config["mixup"]), seed=seed + 977 * rank) if config.get("mixup") else None
     optimizer = FusedAdam([p for p in model.parameters() if p.requires_grad], lr=float(config.get("lr", 0.0003)),
-                          weight_decay=float(config.get("weight_decay", 0.0001)))
+                          weight_decay=float(config.get("weight_decay", 0.0001)),
+                          max_grad_norm=float(config["clip_grad_norm"]) if config.get("clip_grad_norm") else None)
     if config.get("use_amp", True) and rank == 0:
         print("use_amp requested: the HIP path computes in fp32 (parity with the fp32 CPU path); no GradScaler")
 
@@ -341,16 +371,17 @@ def train(args, config):
             print(f"\nEpoch {epoch + 1}/{epochs}")
         if fused:
             batches = train_store.epoch_batches(bs, rank, world, shuffle=True, seed=seed, epoch=epoch)
-            train_loss = train_epoch_waveforms(model, batches, optimizer, criterion, device,
+            train_loss = train_epoch_waveforms(model, batches, optimizer, train_criterion, device,
                                                t_pad=t_pad,
-                                               augment=make_waveform_augment(config, seed=seed + 977 * rank, epoch=epoch))
+                                               augment=make_waveform_augment(config, seed=seed + 977 * rank, epoch=epoch),
+                                               mixup=mixup)
         elif hbm_cache:
             batches = train_dataset.epoch_batches(bs, rank, world, shuffle=True, seed=seed, epoch=epoch,
                                                   augment_prob=float(config.get("augment_prob", 0.5)))
-            train_loss = train_epoch(model, batches, optimizer, criterion, device, None)
+            train_loss = train_epoch(model, batches, optimizer, train_criterion, device, None, mixup=mixup)
         else:
             train_sampler.set_epoch(epoch)
-            train_loss = train_epoch(model, train_loader, optimizer, criterion, device, None)
+            train_loss = train_epoch(model, train_loader, optimizer, train_criterion, device, None, mixup=mixup)
         if hbm_cache:
             val_loader = val_dataset.epoch_batches(bs * 2, rank, world, shuffle=False, pad=False)
         val_loss, val_acc = validate(model, val_loader, criterion, device, None)

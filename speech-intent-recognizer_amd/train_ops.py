@@ -301,7 +301,7 @@ def forward_train(mod, x):
 
 class _FusedCE(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, labels):
+    def forward(ctx, logits, labels, labels_b=None, lam=None, label_smoothing=0.0):
         lib = _native.lib()
         logits = logits.contiguous()
         labels = labels.to(torch.int64).contiguous()
@@ -309,18 +309,134 @@ class _FusedCE(torch.autograd.Function):
         bsz, ncls = logits.shape
         loss = torch.empty((), dtype=torch.float32, device=logits.device)
         dlogits = torch.empty_like(logits) if ctx.needs_input_grad[0] else None
-        rc = lib.sir_ce_loss(get_featurizer().handle, logits.data_ptr(), labels.data_ptr(), bsz, ncls, loss.data_ptr(),
-                             dlogits.data_ptr() if dlogits is not None else None, 1.0, _native.current_stream_ptr())
-        _native.check(rc, "sir_ce_loss")
+        h, dptr = get_featurizer().handle, dlogits.data_ptr() if dlogits is not None else None
+        if labels_b is None and lam is None and label_smoothing == 0.0:
+            rc = lib.sir_ce_loss(h, logits.data_ptr(), labels.data_ptr(), bsz, ncls, loss.data_ptr(), dptr, 1.0,
+                                 _native.current_stream_ptr())
+            _native.check(rc, "sir_ce_loss")
+        else:
+            if lam is not None and labels_b is None:
+                raise _native.SirError("fused_cross_entropy: lam weighs labels against labels_b, which was not given")
+            if labels_b is not None:
+                labels_b = labels_b.to(torch.int64).contiguous()
+                if labels_b.shape != labels.shape:
+                    raise _native.SirError("fused_cross_entropy: labels_b must have the shape of labels")
+            if lam is not None:
+                lam = lam.to(torch.float32).contiguous()
+                if lam.numel() != bsz:
+                    raise _native.SirError("fused_cross_entropy: lam must hold one value per row")
+            _native.require_hip(labels_b, lam)
+            rc = lib.sir_ce_loss_soft(h, logits.data_ptr(), labels.data_ptr(),
+                                      labels_b.data_ptr() if labels_b is not None else None,
+                                      lam.data_ptr() if lam is not None else None, float(label_smoothing), bsz, ncls,
+                                      loss.data_ptr(), dptr, 1.0, _native.current_stream_ptr())
+            _native.check(rc, "sir_ce_loss_soft")
         ctx.dlogits = dlogits
         return loss
 
     @staticmethod
     def backward(ctx, grad_out):
         # loss.backward() passes 1.0; a general scalar is applied by the (tiny) multiply below
-        return ctx.dlogits * grad_out, None
+        return ctx.dlogits * grad_out, None, None, None, None
 
 
-def fused_cross_entropy(logits, labels):
-    """``nn.CrossEntropyLoss()`` (mean over the batch) computed by ``sir_ce_loss``."""
-    return _FusedCE.apply(logits, labels)
+def fused_cross_entropy(logits, labels, labels_b=None, lam=None, label_smoothing=0.0):
+    """``nn.CrossEntropyLoss()`` (mean over the batch) computed by ``sir_ce_loss``.  With any of the three optional
+    arguments, ``sir_ce_loss_soft``: the target of row b is ``(1 - eps) * (lam[b] * e[labels[b]] + (1 - lam[b]) *
+    e[labels_b[b]]) + eps / C`` -- ``nn.CrossEntropyLoss(label_smoothing=eps)``, and mixup's two-label loss
+    ``lam * CE(l, ya) + (1 - lam) * CE(l, yb)`` with a per-row ``lam`` (device float32 ``[B]``; ``None`` = all 1)."""
+    return _FusedCE.apply(logits, labels, labels_b, lam, label_smoothing)
+
+
+def mix_features(x, perm, lam):
+    """``lam[:, None, None] * x + (1 - lam[:, None, None]) * x[perm]`` for a feature batch ``[B, 64, T]`` (``T % 4 == 0``)
+    by ``sir_mix_features``: out of place, fp32 ``fma(lam, a, (1 - lam) * b)``; a row with ``lam == 1`` is a bit-exact
+    copy.  ``perm`` int64 ``[B]`` and ``lam`` float32 ``[B]`` are device tensors; an entry of ``perm`` outside ``[0, B)``
+    gives a zero row and ``SirError`` at the next ``ops.check_status()``."""
+    _native.require_hip(x, perm, lam)
+    x = ops._as_features(x)
+    bsz, n_mels, t = x.shape
+    perm = perm.to(torch.int64).contiguous()
+    lam = lam.to(torch.float32).contiguous()
+    if perm.numel() != bsz or lam.numel() != bsz:
+        raise _native.SirError("mix_features: perm and lam must hold one value per row")
+    out = torch.empty_like(x)
+    rc = _native.lib().sir_mix_features(get_featurizer().handle, x.data_ptr(), perm.data_ptr(), lam.data_ptr(), bsz, n_mels, t,
+                                        out.data_ptr(), _native.current_stream_ptr())
+    _native.check(rc, "sir_mix_features")
+    return out
+
+
+class Mixup:
+    """mixup (Zhang et al. 2018) for ``train_epoch`` / ``train_epoch_waveforms``: per batch ONE ``lam ~ Beta(alpha, alpha)``
+    and one permutation of the rows, drawn on the host (``random.Random(seed)``: same seed, same sequence; no device
+    call).  ``draw(bsz)`` returns the host tensors ``(perm int64 [B], lam float32 [B])``; calling the object with a device
+    batch stages them through pinned buffers, mixes the features with ``mix_features`` and returns
+    ``(mixed, labels[perm], lam)`` -- the arguments ``fused_cross_entropy`` takes after ``labels``."""
+
+    def __init__(self, alpha, seed=0):
+        import random
+        if not alpha > 0:
+            raise ValueError("mixup alpha must be > 0")
+        self.alpha = float(alpha)
+        self.rng = random.Random(int(seed))
+        self._stage = None
+
+    def draw(self, bsz):
+        lam = self.rng.betavariate(self.alpha, self.alpha)
+        perm = list(range(bsz))
+        self.rng.shuffle(perm)
+        return torch.tensor(perm, dtype=torch.int64), torch.full((bsz,), lam, dtype=torch.float32)
+
+    def __call__(self, x, labels):
+        from .scripts.train import HostStager
+        if self._stage is None or self._stage.device != x.device:
+            self._stage = HostStager(x.device)
+        perm, lam = self.draw(x.shape[0])
+        perm, lam = self._stage(perm), self._stage(lam)
+        return mix_features(x, perm, lam), labels[perm], lam
+
+
+_norm_partials = {}
+
+
+def _grad_arrays(grads):
+    n = len(grads)
+    G, N = (C.c_void_p * n)(), (C.c_int64 * n)()
+    for i, g in enumerate(grads):
+        if g.dtype != torch.float32 or not g.is_contiguous():
+            raise _native.SirError("gradient clipping needs contiguous float32 gradients")
+        _native.require_hip(g)
+        G[i], N[i] = g.data_ptr(), g.numel()
+    return G, N
+
+
+def norm_partials(n_floats, device):
+    """Grow-only device slab for the per-chunk sums of squares (reused step after step: stream order protects it)."""
+    buf = _norm_partials.get(device)
+    if buf is None or buf.numel() < n_floats:
+        buf = _norm_partials[device] = torch.empty(max(n_floats, 1024), dtype=torch.float32, device=device)
+    return buf
+
+
+def clip_grad_norm_(parameters, max_norm):
+    """``torch.nn.utils.clip_grad_norm_(parameters, max_norm)`` (2-norm, ``error_if_nonfinite=False``) in two launches of
+    ``sir_grad_norm``: the gradients are scaled in place by ``min(1, max_norm / (norm + 1e-6))`` and the total norm comes
+    back as a device scalar -- nothing synchronises with the host.  Parameters without a gradient (frozen) are left out;
+    the norm is an ordered reduction, bit-reproducible run to run."""
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    grads = [p.grad for p in parameters if p.grad is not None]
+    if not grads:
+        return torch.zeros(())
+    if len(grads) > 32:
+        raise _native.SirError(f"clip_grad_norm_: {len(grads)} gradient tensors, at most 32 per call (the model has 29)")
+    lib = _native.lib()
+    G, N = _grad_arrays(grads)
+    n = lib.sir_grad_norm_partials(len(grads), N)
+    part = norm_partials(n, grads[0].device)
+    out2 = torch.empty(2, dtype=torch.float32, device=grads[0].device)
+    rc = lib.sir_grad_norm(get_featurizer().handle, len(grads), G, N, float(max_norm), part.data_ptr(), part.numel(),
+                           out2.data_ptr(), 1, _native.current_stream_ptr())
+    _native.check(rc, "sir_grad_norm")
+    return out2[0]

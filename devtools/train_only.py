@@ -3,6 +3,7 @@
 inside ONE box session: median ms / step over `--repeats` regions and the per-kernel HIP-event averages of `sir_profile_*`.
 
     SIR_GRU_DBG=256 python devtools/train_only.py --steps 30 --tag delay1      # prints one JSON line
+    python devtools/train_only.py --adamw --ema 0.999 --cosine --clip 1 --mixup 0.2 --label-smoothing 0.1      # every option on
 
 Developer tool (run through gpurun); the product path only, nothing from oracle/."""
 import argparse
@@ -28,6 +29,9 @@ def main():
     ap.add_argument("--mixup", type=float, default=0.0, help="alpha: mix every batch with a permutation of itself (train_ops.Mixup)")
     ap.add_argument("--label-smoothing", type=float, default=0.0)
     ap.add_argument("--clip", type=float, default=0.0, help="max_norm: FusedAdam(max_grad_norm=...)")
+    ap.add_argument("--adamw", action="store_true", help="FusedAdam(decoupled_weight_decay=True)")
+    ap.add_argument("--ema", type=float, default=0.0, help="decay: FusedAdam(ema_decay=..., ema_warmup=True), the shadow updated inside the step")
+    ap.add_argument("--cosine", action="store_true", help="warm-up + cosine LR schedule stepped after every optimizer step")
     ap.add_argument("--kernels", default="", help="comma-separated substrings: only these kernel averages are printed")
     args = ap.parse_args()
     import bench
@@ -50,7 +54,11 @@ def main():
     labels = torch.randint(0, bench.NUM_CLASSES, (args.batch,), device=dev)
     feats = torch.empty(args.batch, 64, bench.T_PAD, device=dev)
     opt = FusedAdam([p for p in model.parameters() if p.requires_grad], lr=5e-5, weight_decay=1e-4,
-                    max_grad_norm=args.clip or None)
+                    max_grad_norm=args.clip or None, decoupled_weight_decay=args.adamw, ema_decay=args.ema or None,
+                    ema_warmup=bool(args.ema))
+    if args.cosine:
+        from sir_amd.scripts import train as tr
+        tr.step_scheduler_with(opt, tr.build_lr_scheduler(opt, {"kind": "cosine", "warmup_steps": 100, "total_steps": 100000}))
     mixup = train_ops.Mixup(args.mixup, seed=0) if args.mixup else None
 
     def step(i):
@@ -95,7 +103,7 @@ def main():
     ops.check_status()
     sw = {k: v for k, v in os.environ.items() if k.startswith("SIR_")}
     print(json.dumps({"tag": args.tag, "freeze": args.freeze, "mixup": args.mixup, "label_smoothing": args.label_smoothing,
-                      "clip": args.clip, "env": sw, "ms_per_step_median": round(statistics.median(times), 4),
+                      "clip": args.clip, "adamw": args.adamw, "ema": args.ema, "cosine": args.cosine, "env": sw, "ms_per_step_median": round(statistics.median(times), 4),
                       "ms_per_step_min": round(min(times), 4), "ms_per_step_max": round(max(times), 4),
                       "loss": round(float(loss), 6), "kernels_us": kern}), flush=True)
 

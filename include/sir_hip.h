@@ -382,6 +382,31 @@ int sir_adam_step_clipped(sir_handle* h, int n_tensors, float* const* params, co
                           float beta1, float beta2, float eps, float weight_decay, const float* partials, int n_partials,
                           float max_norm, float* out2, void* stream);
 
+/* ---- every variant of the optimizer step --------------------------------------------------------
+ * sir_adam_step_ex: one multi-tensor launch for torch.optim.Adam / torch.optim.AdamW, with or without the clip coefficient of
+ * sir_adam_step_clipped, with or without an exponential moving average ("shadow") of the parameters updated in the same
+ * pass.  Tensors as for sir_adam_step (HOST arrays of device pointers and element counts, n_tensors <= 32).
+ *   decoupled == 0, ema_decay == 0: the call IS sir_adam_step (max_norm == 0) or sir_adam_step_clipped (max_norm > 0): the same
+ *     kernel, the same bits.
+ *   decoupled != 0: p is first multiplied by (float)(1.0 - (double)lr * (double)weight_decay), formed on the host; the Adam
+ *     update then runs on the gradient alone (clipped if asked for), no weight_decay * p term: torch.optim.AdamW's order.
+ *   ema_decay = d in (0, 1): ema[i] = fmaf(d, ema[i], (1.0f - d) * p_new) with the parameter value the step has just formed.
+ *     d is read per call (the host may warm it up).  `ema` holds n_tensors device pointers, none NULL, none aliasing its
+ *     parameter; ema must be NULL when ema_decay == 0.  The caller initialises the shadow (a copy of the parameters).
+ *   max_norm > 0: `partials` / `n_partials` / `out2` as for sir_adam_step_clipped; max_norm == 0: they are not read.
+ * SIR_EINVAL: NaN in any float of cfg, ema_decay outside [0, 1), ema == NULL with ema_decay > 0 (or the reverse),
+ * max_norm < 0, max_norm > 0 without partials / out2.  The library allocates nothing. */
+typedef struct sir_adam_config {
+    float lr, beta1, beta2, eps, weight_decay;
+    int   decoupled;      /* 0: coupled L2 (torch.optim.Adam); 1: torch.optim.AdamW */
+    float max_norm;       /* 0 = no clipping; > 0: as sir_adam_step_clipped (partials / n_partials / out2 required) */
+    float ema_decay;      /* 0 = no shadow; in (0, 1): shadow update with THIS step's decay */
+} sir_adam_config;
+int sir_adam_step_ex(sir_handle* h, int n_tensors, float* const* params, const float* const* grads,
+                     float* const* exp_avg, float* const* exp_avg_sq, float* const* ema /* NULL iff ema_decay == 0 */,
+                     const int64_t* sizes, int step, const sir_adam_config* cfg,
+                     const float* partials, int n_partials, float* out2, void* stream);
+
 /* ---- measurement -----------------------------------------------------------------------------
  * HIP-event timing of the kernels of the path, recorded on the stream they are launched on
  * (bench.py's roofline figures come from here).  mode 0 = off, 1 = every kernel, 2 = only

@@ -49,6 +49,11 @@ class TrainConfig(C.Structure):
     _fields_ = [("bn_frozen", C.c_int * 3)]
 
 
+class AdamConfig(C.Structure):
+    _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float),
+                ("decoupled", C.c_int), ("max_norm", C.c_float), ("ema_decay", C.c_float)]
+
+
 # name -> (restype, argtypes); must list every function declared in include/sir_hip.h
 SIGNATURES = {
     "sir_abi_version": (C.c_int, []),
@@ -112,6 +117,9 @@ SIGNATURES = {
     "sir_adam_step_clipped": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                         C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int, C.c_float, C.c_float, C.c_float,
                                         C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    "sir_adam_step_ex": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                   C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int, C.POINTER(AdamConfig),
+                                   C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "sir_profile_kernel_count": (C.c_int, []),
     "sir_profile_kernel_name": (C.c_char_p, [C.c_int]),
     "sir_profile_enable": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),

@@ -890,3 +890,60 @@ extern "C" int sir_adam_step_clipped(sir_handle* h, int n_tensors, float* const*
     SIR_KCHECK();
     return SIR_OK;
 }
+
+// ---- every variant of the optimizer step behind one call ---------------------------------------------------------------
+template <bool CLIP>
+static void launch_adam_ex(bool decoupled, bool ema, int blocks, hipStream_t st, const AdamTensors& ts, const AdamShadow& sh,
+                           const sir_adam_config* c, float decay_f, float bc1, float bc2_sqrt, const float* partials, int n_partials,
+                           float* out2) {
+#define SIR_ADAM_EX_LAUNCH(D, E)                                                                                               \
+    hipLaunchKernelGGL((adam_multi_ex_kernel<CLIP, D, E>), dim3(blocks), dim3(256), 0, st, ts, sh, c->lr, c->beta1, c->beta2,    \
+                       c->eps, c->weight_decay, decay_f, c->ema_decay, bc1, bc2_sqrt, partials, n_partials, c->max_norm, out2)
+    if (decoupled && ema) SIR_ADAM_EX_LAUNCH(true, true);
+    else if (decoupled) SIR_ADAM_EX_LAUNCH(true, false);
+    else SIR_ADAM_EX_LAUNCH(false, true);
+#undef SIR_ADAM_EX_LAUNCH
+}
+
+extern "C" int sir_adam_step_ex(sir_handle* h, int n_tensors, float* const* params, const float* const* grads, float* const* exp_avg,
+                                float* const* exp_avg_sq, float* const* ema, const int64_t* sizes, int step,
+                                const sir_adam_config* cfg, const float* partials, int n_partials, float* out2, void* stream_) {
+    if (!h || !params || !grads || !exp_avg || !exp_avg_sq || !sizes || !cfg) { sir_set_error("sir_adam_step_ex: NULL argument"); return SIR_EINVAL; }
+    const float fl[7] = {cfg->lr, cfg->beta1, cfg->beta2, cfg->eps, cfg->weight_decay, cfg->max_norm, cfg->ema_decay};
+    for (float f : fl)
+        if (f != f) { sir_set_error("sir_adam_step_ex: NaN in the configuration"); return SIR_EINVAL; }
+    if (!(cfg->ema_decay >= 0.0f && cfg->ema_decay < 1.0f)) { sir_set_error("sir_adam_step_ex: ema_decay %g outside [0, 1)", (double)cfg->ema_decay); return SIR_EINVAL; }
+    const bool use_ema = cfg->ema_decay > 0.0f, clip = cfg->max_norm > 0.0f, decoupled = cfg->decoupled != 0;
+    if (use_ema != (ema != nullptr)) { sir_set_error("sir_adam_step_ex: `ema` must be given exactly when ema_decay > 0"); return SIR_EINVAL; }
+    if (cfg->max_norm < 0.0f) { sir_set_error("sir_adam_step_ex: max_norm %g must be >= 0", (double)cfg->max_norm); return SIR_EINVAL; }
+    if (clip && (!partials || !out2 || n_partials < 1)) { sir_set_error("sir_adam_step_ex: max_norm > 0 needs partials, n_partials >= 1 and out2"); return SIR_EINVAL; }
+    if (!decoupled && !use_ema)              // nothing new asked for: the existing launches, bit for bit
+        return clip ? sir_adam_step_clipped(h, n_tensors, params, grads, exp_avg, exp_avg_sq, sizes, step, cfg->lr, cfg->beta1, cfg->beta2,
+                                            cfg->eps, cfg->weight_decay, partials, n_partials, cfg->max_norm, out2, stream_)
+                    : sir_adam_step(h, n_tensors, params, grads, exp_avg, exp_avg_sq, sizes, step, cfg->lr, cfg->beta1, cfg->beta2, cfg->eps,
+                                    cfg->weight_decay, stream_);
+    if (n_tensors < 1 || n_tensors > SIR_ADAM_MAX_TENSORS || step < 1) { sir_set_error("sir_adam_step_ex: n_tensors=%d step=%d", n_tensors, step); return SIR_EINVAL; }
+    AdamTensors ts;
+    AdamShadow sh;
+    int blocks = 0;
+    for (int i = 0; i < n_tensors; ++i) {
+        if (sizes[i] < 0) { sir_set_error("sir_adam_step_ex: size %d is negative", i); return SIR_EINVAL; }
+        if (use_ema && (!ema[i] || ema[i] == params[i])) { sir_set_error("sir_adam_step_ex: shadow %d is NULL or aliases its parameter", i); return SIR_EINVAL; }
+        ts.p[i] = params[i]; ts.g[i] = grads[i]; ts.m[i] = exp_avg[i]; ts.v[i] = exp_avg_sq[i]; ts.n[i] = sizes[i];
+        sh.e[i] = use_ema ? ema[i] : nullptr;
+        ts.first_block[i] = blocks;
+        blocks += (int)((sizes[i] + SIR_ADAM_CHUNK - 1) / SIR_ADAM_CHUNK);
+    }
+    for (int i = n_tensors; i < SIR_ADAM_MAX_TENSORS; ++i) sh.e[i] = nullptr;
+    ts.first_block[n_tensors] = blocks;
+    ts.count = n_tensors;
+    if (blocks < 1) return SIR_OK;           // every tensor empty
+    const double bc1 = 1.0 - pow((double)cfg->beta1, step), bc2 = 1.0 - pow((double)cfg->beta2, step);
+    const float decay_f = (float)(1.0 - (double)cfg->lr * (double)cfg->weight_decay);
+    hipStream_t st = (hipStream_t)stream_;
+    SirProfScope prof(h, clip ? SIR_K_ADAM_EX_CLIPPED : SIR_K_ADAM_EX, st);
+    if (clip) launch_adam_ex<true>(decoupled, use_ema, blocks, st, ts, sh, cfg, decay_f, (float)bc1, (float)sqrt(bc2), partials, n_partials, out2);
+    else launch_adam_ex<false>(decoupled, use_ema, blocks, st, ts, sh, cfg, decay_f, (float)bc1, (float)sqrt(bc2), nullptr, 0, nullptr);
+    SIR_KCHECK();
+    return SIR_OK;
+}

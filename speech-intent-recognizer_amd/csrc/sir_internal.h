@@ -25,6 +25,8 @@ enum SirKernelId {
     SIR_K_B_BN3, SIR_K_B_WGRAD3, SIR_K_B_DGRAD3, SIR_K_B_BN2, SIR_K_B_WGRAD2, SIR_K_B_DGRAD2, SIR_K_B_CONV1, SIR_K_ADAM,
     // training recipe (appended: the ids above keep their meaning): batch mixing, gradient norm / clip, clipped Adam
     SIR_K_MIX, SIR_K_GRAD_SUMSQ, SIR_K_GRAD_CLIP, SIR_K_ADAM_CLIPPED,
+    // sir_adam_step_ex with decoupled weight decay and / or the EMA shadow on (appended), without / with clipping
+    SIR_K_ADAM_EX, SIR_K_ADAM_EX_CLIPPED,
     SIR_K_COUNT
 };
 

@@ -1116,11 +1116,22 @@ struct AdamTensors {
     int count;
 };
 
+// the EMA shadow of each tensor (sir_adam_step_ex): a kernel argument of its own, so that the launches of sir_adam_step /
+// sir_adam_step_clipped keep the arguments they have
+struct AdamShadow {
+    float* e[SIR_ADAM_MAX_TENSORS];
+};
+
 // One block's 4096-element chunk.  CLIP: the gradient is g * coef (rounded to fp32 first, exactly what an in-place
 // clip_grad_norm_ would have left in memory) before the weight-decay term.
-template <bool CLIP>
+// DECOUPLED (torch.optim.AdamW): p is first multiplied by decay_f = 1 - lr * weight_decay (formed on the host, rounded to
+// fp32 once; the product is rounded too, as torch's p.mul_ leaves it), then the update runs on the gradient alone:
+// `weight_decay` is not read.  EMA: shadow = fma(d, shadow, (1 - d) * p_new) with the p_new this thread has just formed --
+// one more load and store in the same pass, two roundings.  Both false: the code of the two switches is not there.
+template <bool CLIP, bool DECOUPLED = false, bool EMA = false>
 __device__ __forceinline__ void adam_chunk(const AdamTensors& ts, float lr, float beta1, float beta2, float eps, float weight_decay,
-                                           float bc1, float bc2_sqrt, float coef) {
+                                           float bc1, float bc2_sqrt, float coef, float decay_f = 1.0f,
+                                           const AdamShadow* shadow = nullptr, float ema_d = 0.0f) {
     int ti = 0;
     while (ti + 1 < ts.count && (int)blockIdx.x >= ts.first_block[ti + 1]) ++ti;
     const long long base = (long long)((int)blockIdx.x - ts.first_block[ti]) * SIR_ADAM_CHUNK;
@@ -1136,14 +1147,20 @@ __device__ __forceinline__ void adam_chunk(const AdamTensors& ts, float lr, floa
         if (i >= n) break;
         float gi = g[i];
         if constexpr (CLIP) gi = __fmul_rn(gi, coef);
-        const float pi = p[i];
-        if (weight_decay != 0.0f) gi = fmaf(weight_decay, pi, gi);
+        float pi = p[i];
+        if constexpr (DECOUPLED) pi = __fmul_rn(pi, decay_f);
+        else if (weight_decay != 0.0f) gi = fmaf(weight_decay, pi, gi);
         const float mi = beta1 * m[i] + (1.0f - beta1) * gi;
         const float vi = beta2 * v[i] + (1.0f - beta2) * gi * gi;
         m[i] = mi;
         v[i] = vi;
         const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        p[i] = pi - step_size * (mi / denom);
+        const float pn = pi - step_size * (mi / denom);
+        p[i] = pn;
+        if constexpr (EMA) {
+            float* __restrict__ e = shadow->e[ti];
+            e[i] = fmaf(ema_d, e[i], __fmul_rn(1.0f - ema_d, pn));
+        }
     }
 }
 
@@ -1240,4 +1257,20 @@ static __global__ __launch_bounds__(256) void adam_multi_clipped_kernel(AdamTens
     const float2 nc = grad_norm_coef(partials, n_partials, max_norm);
     if (blockIdx.x == 0 && threadIdx.x == 0) { out2[0] = nc.x; out2[1] = nc.y; }
     adam_chunk<true>(ts, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, nc.y);
+}
+
+// sir_adam_step_ex with decoupled weight decay and / or the EMA shadow on (with both off the host launches the two kernels
+// above): same grid, same chunk map; CLIP as adam_multi_clipped_kernel, otherwise `partials` / `out2` are not read
+template <bool CLIP, bool DECOUPLED, bool EMA>
+static __global__ __launch_bounds__(256) void adam_multi_ex_kernel(AdamTensors ts, AdamShadow shadow, float lr, float beta1, float beta2,
+                                                             float eps, float weight_decay, float decay_f, float ema_d, float bc1,
+                                                             float bc2_sqrt, const float* __restrict__ partials, int n_partials,
+                                                             float max_norm, float* __restrict__ out2) {
+    float coef = 1.0f;
+    if constexpr (CLIP) {
+        const float2 nc = grad_norm_coef(partials, n_partials, max_norm);
+        if (blockIdx.x == 0 && threadIdx.x == 0) { out2[0] = nc.x; out2[1] = nc.y; }
+        coef = nc.y;
+    }
+    adam_chunk<CLIP, DECOUPLED, EMA>(ts, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, coef, decay_f, &shadow, ema_d);
 }

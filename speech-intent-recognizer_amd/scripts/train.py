@@ -117,7 +117,9 @@ def train_epoch(model, train_loader, optimizer, criterion, device, scaler=None, 
     """One epoch (train.py:72-118); returns the mean of the per-step losses.  ``scaler`` is accepted
     for signature compatibility: the HIP path always computes in fp32 (the parity target is the fp32
     CPU path), so no loss scaling is needed or applied.  ``mixup`` (a ``train_ops.Mixup``): every assembled batch is
-    mixed with a permutation of itself on the GPU and the loss takes both label sets."""
+    mixed with a permutation of itself on the GPU and the loss takes both label sets.  An LR scheduler rides on the
+    optimizer (``step_scheduler_with``): it is stepped after every ``optimizer.step()`` below, the zero-contribution step of
+    an empty shard included, so every rank keeps the same learning rate."""
     from sir_amd import ops, train_ops
     model.train()
     loss_fn = _loss_fn(criterion)
@@ -242,6 +244,74 @@ def make_waveform_augment(config, seed=0, epoch=0, rng=None):
     return fn
 
 
+def build_lr_scheduler(optimizer, spec):
+    """The ``lr_schedule`` YAML key -> a ``torch.optim.lr_scheduler`` object on ``optimizer`` (``FusedAdam`` reads
+    ``group["lr"]`` every step), stepped once per optimizer step; ``None`` for an absent / empty key.
+
+    ``{warmup_steps: W, kind: constant | cosine | step, min_lr, total_steps, step_size, gamma}``:
+    ``W > 0`` puts ``LinearLR(start_factor=1 / (W + 1), total_iters=W)`` in front (step k runs at ``lr * (k + 1) / (W + 1)``,
+    the full rate from step W on) under ``SequentialLR``; behind it ``cosine`` is ``CosineAnnealingLR(T_max=total_steps - W,
+    eta_min=min_lr)`` (``total_steps`` optimizer steps in all: ``train()`` fills it in from the epoch count), ``step`` is
+    ``StepLR(step_size, gamma)``, ``constant`` is ``LambdaLR`` with factor 1."""
+    from torch.optim import lr_scheduler as sched
+    if not spec:
+        return None
+    unknown = set(spec) - {"warmup_steps", "kind", "min_lr", "total_steps", "step_size", "gamma"}
+    if unknown:
+        raise ValueError(f"lr_schedule: unknown keys {sorted(unknown)}")
+    kind = spec.get("kind", "constant")
+    warm = int(spec.get("warmup_steps", 0))
+    if warm < 0:
+        raise ValueError("lr_schedule: warmup_steps must be >= 0")
+    if kind == "constant":
+        main = sched.LambdaLR(optimizer, lambda step: 1.0)
+    elif kind == "cosine":
+        if "total_steps" not in spec:
+            raise ValueError("lr_schedule: kind cosine needs total_steps")
+        t_max = int(spec["total_steps"]) - warm
+        if t_max < 1:
+            raise ValueError(f"lr_schedule: total_steps {spec['total_steps']} must exceed warmup_steps {warm}")
+        main = sched.CosineAnnealingLR(optimizer, T_max=t_max, eta_min=float(spec.get("min_lr", 0.0)))
+    elif kind == "step":
+        if "step_size" not in spec:
+            raise ValueError("lr_schedule: kind step needs step_size")
+        main = sched.StepLR(optimizer, step_size=int(spec["step_size"]), gamma=float(spec.get("gamma", 0.1)))
+    else:
+        raise ValueError(f"lr_schedule: kind {kind!r} is not one of constant, cosine, step")
+    if warm == 0:
+        return main
+    warmup = sched.LinearLR(optimizer, start_factor=1.0 / (warm + 1), end_factor=1.0, total_iters=warm)
+    return sched.SequentialLR(optimizer, [warmup, main], milestones=[warm])
+
+
+def step_scheduler_with(optimizer, scheduler):
+    """Step ``scheduler`` once after every ``optimizer.step()`` (a step post-hook of the optimizer: ``train_epoch`` and
+    ``train_epoch_waveforms`` keep the reference's signatures, and no call site of ``optimizer.step()`` can forget it -- the
+    zero-contribution step of an empty shard steps it too).  Returns the hook's handle (``.remove()`` detaches it)."""
+    return optimizer.register_step_post_hook(lambda opt, args, kwargs: scheduler.step())
+
+
+def run_options(config):
+    """The run-management YAML keys of ``train()`` as one dict, every one absent by default (= no scheduler, no shadow, no
+    ``latest_checkpoint.pt``, plain Adam): ``optimizer: adam | adamw``, ``lr_schedule``, ``ema_decay`` / ``ema_warmup``,
+    ``checkpoint_every_epoch``, ``resume: <path> | true`` (``true`` = ``save_path/latest_checkpoint.pt``)."""
+    from sir_amd import run_state
+    kind = str(config.get("optimizer", "adam")).lower()
+    if kind not in ("adam", "adamw"):
+        raise ValueError(f"optimizer: {kind!r} is not one of adam, adamw")
+    ema = config.get("ema_decay")
+    if not ema and config.get("ema_warmup"):
+        raise ValueError("ema_warmup needs ema_decay")
+    latest = os.path.join(config.get("save_path", "checkpoints/"), run_state.LATEST)
+    resume = config.get("resume")
+    return {"decoupled_weight_decay": kind == "adamw",
+            "ema_decay": float(ema) if ema else None,
+            "ema_warmup": bool(config.get("ema_warmup", False)),
+            "lr_schedule": dict(config["lr_schedule"]) if config.get("lr_schedule") else None,
+            "checkpoint_path": latest if config.get("checkpoint_every_epoch") else None,
+            "resume_path": None if not resume else (latest if resume is True else str(resume))}
+
+
 def validate(model, val_loader, criterion, device, scaler=None):
     """(avg_loss, accuracy) over the loader (train.py:120-155); under data parallelism the counts are
     summed over ranks."""
@@ -276,8 +346,15 @@ def _quiet():
 
 def train(args, config):
     """Main training function (train.py:164-302): same YAML keys, same best-checkpoint rule
-    (bare ``state_dict`` at ``save_path/best_model.pt``), same early stopping."""
-    from sir_amd import _native, train_ops  # noqa: F401
+    (bare ``state_dict`` at ``save_path/best_model.pt``), same early stopping.
+
+    Run management (``run_options``, all keys absent by default): with ``checkpoint_every_epoch`` the whole run state
+    (``sir_amd.run_state``) goes to ``save_path/latest_checkpoint.pt`` after each epoch's validation, and ``resume`` picks a
+    run up at that epoch boundary.  On the ``hbm_feature_cache`` (default) and ``fused_features`` / ``waveform_augment``
+    routes the resumed run is bit-identical to the uninterrupted one: data order and augmentation there are pure functions
+    of ``(seed, epoch, rank)``.  The DataLoader route (``hbm_feature_cache: false``) draws SpecAugment from its worker
+    processes' global RNGs: it resumes, but not bit-exactly.  A run cut off inside an epoch repeats that epoch."""
+    from sir_amd import _native, run_state, train_ops  # noqa: F401
     from sir_amd.models.models import CNNAudioGRU
     from sir_amd.optim import FusedAdam
     from sir_amd.scripts.dataset import FSCIntentDataset
@@ -353,12 +430,15 @@ def train(args, config):
     # `label_smoothing: <eps>` and `mixup: <alpha>` change the training loss (validation keeps the plain criterion);
     # `clip_grad_norm: <max_norm>` clips the global gradient norm inside the optimizer step.  The reference's own
     # `grad_clip` / `mixup_alpha` keys stay unread, as the reference leaves them.
+    opts = run_options(config)
     criterion = nn.CrossEntropyLoss()
     train_criterion = nn.CrossEntropyLoss(label_smoothing=float(config["label_smoothing"])) if config.get("label_smoothing") else criterion
     mixup = train_ops.Mixup(float(config["mixup"]), seed=seed + 977 * rank) if config.get("mixup") else None
     optimizer = FusedAdam([p for p in model.parameters() if p.requires_grad], lr=float(config.get("lr", 0.0003)),
                           weight_decay=float(config.get("weight_decay", 0.0001)),
-                          max_grad_norm=float(config["clip_grad_norm"]) if config.get("clip_grad_norm") else None)
+                          max_grad_norm=float(config["clip_grad_norm"]) if config.get("clip_grad_norm") else None,
+                          decoupled_weight_decay=opts["decoupled_weight_decay"], ema_decay=opts["ema_decay"],
+                          ema_warmup=opts["ema_warmup"])
     if config.get("use_amp", True) and rank == 0:
         print("use_amp requested: the HIP path computes in fp32 (parity with the fp32 CPU path); no GradScaler")
 
@@ -366,7 +446,24 @@ def train(args, config):
     patience = config.get("early_stop_patience", 5)
     best_val_acc = 0
     no_improve_count = 0
-    for epoch in range(epochs):
+    scheduler = None
+    if opts["lr_schedule"]:
+        spec = opts["lr_schedule"]
+        if spec.get("kind") == "cosine" and "total_steps" not in spec:      # the whole run: every rank takes the same step count
+            n_shard = len(train_ops.ShardSampler(len(train_dataset), rank, world))
+            spec["total_steps"] = epochs * ((n_shard + bs - 1) // bs)
+        scheduler = build_lr_scheduler(optimizer, spec)
+        step_scheduler_with(optimizer, scheduler)
+    first_epoch = 0
+    if opts["resume_path"]:
+        got = run_state.load_run_state(opts["resume_path"], model, optimizer, scheduler, mixup, config=config)
+        first_epoch, best_val_acc, no_improve_count = got["epoch"] + 1, got["best_val_acc"], got["no_improve_count"]
+        if rank == 0:
+            print(f"Resumed {opts['resume_path']}: epoch {first_epoch} done, best accuracy {best_val_acc:.4f}"
+                  + (f"; config keys that differ from the saved run: {got['config_changed']}" if got["config_changed"] else ""))
+    for epoch in range(first_epoch, epochs):
+        if no_improve_count >= patience:              # (a resumed run that had already stopped early)
+            break
         if rank == 0:
             print(f"\nEpoch {epoch + 1}/{epochs}")
         if fused:
@@ -384,7 +481,11 @@ def train(args, config):
             train_loss = train_epoch(model, train_loader, optimizer, train_criterion, device, None, mixup=mixup)
         if hbm_cache:
             val_loader = val_dataset.epoch_batches(bs * 2, rank, world, shuffle=False, pad=False)
-        val_loss, val_acc = validate(model, val_loader, criterion, device, None)
+        if opts["ema_decay"] is not None:             # validate (and keep as best model) the averaged weights
+            with optimizer.swapped_ema():
+                val_loss, val_acc = validate(model, val_loader, criterion, device, None)
+        else:
+            val_loss, val_acc = validate(model, val_loader, criterion, device, None)
         if rank == 0:
             print(f"Train loss: {train_loss:.4f}, Val loss: {val_loss:.4f}, Val accuracy: {val_acc:.4f}")
         if val_acc > best_val_acc:
@@ -393,12 +494,16 @@ def train(args, config):
             if rank == 0:
                 save_path = config.get("save_path", "checkpoints/")
                 os.makedirs(save_path, exist_ok=True)
-                torch.save(model.state_dict(), os.path.join(save_path, "best_model.pt"))
+                best_sd = optimizer.ema_state_dict(model) if opts["ema_decay"] is not None else model.state_dict()
+                torch.save(best_sd, os.path.join(save_path, "best_model.pt"))
                 print(f"New best model saved with accuracy: {val_acc:.4f}")
         else:
             no_improve_count += 1
             if rank == 0:
                 print(f"No improvement for {no_improve_count} epochs")
+        if opts["checkpoint_path"]:                   # after the bookkeeping above: a resumed run starts at epoch + 1
+            run_state.save_run_state(opts["checkpoint_path"], model, optimizer, scheduler, mixup, epoch=epoch,
+                                     best_val_acc=best_val_acc, no_improve_count=no_improve_count, config=config)
         if no_improve_count >= patience:
             if rank == 0:
                 print(f"Early stopping after {epoch + 1} epochs")

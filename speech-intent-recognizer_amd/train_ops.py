@@ -8,7 +8,6 @@ views are returned, so the update equals single-GPU training on the global batch
 Only pointers move through Python; no arithmetic of the step is done by torch ops.
 """
 import ctypes as C
-import itertools
 import os
 
 import torch
@@ -18,7 +17,37 @@ from .dist_utils import (ShardSampler, all_reduce_mean_, all_reduce_sum_, broadc
                          init_distributed, limit_host_threads, shutdown_distributed, world_size)
 from .featurizer import get_featurizer
 
-_seed_counter = itertools.count(1)
+
+
+class _StepCounter:
+    """The process-wide dropout step counter: ``next()`` hands out 1, 2, ... as ``itertools.count(1)`` did; ``value`` (the
+    number the NEXT training forward will draw) can be read and set, which is what lets a resumed run continue the mask
+    sequence instead of drawing the masks of steps 1, 2, ... again (``sir_amd.run_state``)."""
+
+    def __init__(self):
+        self.value = 1
+
+    def __next__(self):
+        v = self.value
+        self.value = v + 1
+        return v
+
+
+_seed_counter = _StepCounter()
+
+
+def dropout_step():
+    """The counter value the next training forward of this process draws its dropout key from (1 in a new process)."""
+    return _seed_counter.value
+
+
+def set_dropout_step(value):
+    value = int(value)
+    if value < 1:
+        raise ValueError("the dropout step counter starts at 1")
+    _seed_counter.value = value
+
+
 OVERLAP_GRAD_EXCHANGE = os.environ.get("SIR_DDP_OVERLAP", "1") != "0"
 HAND_OVER_GRADS = os.environ.get("SIR_HAND_OVER_GRADS", "1") != "0"
 # take the data-parallel exchange path even in a ONE-rank process group (bench.py's `rccl_world1` leg and the nccl tests

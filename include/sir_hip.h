@@ -318,6 +318,47 @@ int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* w, const fl
                              int batch, int t_frames, float dropout_p, uint64_t dropout_seed,
                              const sir_model_grads* grads, void* workspace, size_t workspace_bytes, int part,
                              void* stream);
+/* Byte offsets of the training workspace's slots for one shape (debugging and tests: the library's own calls need none of
+ * this).  Writes min(n, slot count) offsets and returns the slot count; touches no device (`h` may be NULL).  Every slot is
+ * 256-byte aligned; fp32 unless noted; B = batch, S = t_frames / 8 GRU steps, wp1 = t_frames / 2, wp2 = t_frames / 4.
+ * Indices are stable: slots are appended, never renumbered.
+ *    0  a1     conv1 block output (pooled)         [B][32][wp1][32]
+ *    1  z2     conv2 raw output                    [B][32][wp1][64]
+ *    2  a2     conv2 block output                  [B][16][wp2][64]
+ *    3  z3     conv3 raw output                    [B][16][wp2][128]
+ *    4  x0     conv3 block output = GRU layer 0 input   [B][S][1024]
+ *    5  gi     input projection of the running layer    [B][S][1536]
+ *    6  g0     saved gates of GRU layer 0          [B][S][2][4][256]
+ *    7  g1     saved gates of GRU layer 1
+ *    8  y0     GRU layer 0 output                  [B][S][512]
+ *    9  y0d    layer 0 output behind the dropout   [B][S][512]
+ *   10  y1     GRU layer 1 output                  [B][S][512]
+ *   11  ctx    attention-pooled context            [B][512]
+ *   12  bn     BatchNorm scale, shift, mean, invstd     [4][224] (bn1 | bn2 | bn3 at channels 0, 32, 96)
+ *   13  bnb    backward: mean dy, mean dy * xhat   [2][224]
+ *   14  stats  partial sums of the BatchNorm reductions (float2)
+ *   15, 16     reserved
+ *   17  wht    W_hh as the forward recurrence's resident fragments
+ *   18  wr4    W_hh as the backward recurrence's resident fragments
+ *   19, 20     reserved
+ *   21  dy1    gradient of y1                      [B][S][512]
+ *   22  dy0    gradient of y0                      [B][S][512]
+ *   23  dgi    gate gradients of layer 0, input side    [B][S][1536]
+ *   24  dgh    gate gradients of layer 0, hidden side   [B][S][1536]
+ *   25  dx0    gradient of x0                      [B][S][1024]
+ *   26  dz3    gradient of z3
+ *   27  da2    gradient of a2
+ *   28  dz2    gradient of z2
+ *   29  da1    gradient of a1
+ *   30  small  attention-gradient and conv1-backward partials
+ *   31  slab   split-K / weight-gradient slabs
+ *   32  xs     16-bit planes of the input-projection GEMM's A operand
+ *   33  ws     16-bit planes of W_ih (both layers, both directions)
+ *   34  wcb    16-bit planes of the conv2 / conv3 weights (forward and data-gradient forms)
+ *   35  c1m    conv1 input moments (54 doubles)
+ *   36  dgi1   gate gradients of layer 1, input side
+ *   37  dgh1   gate gradients of layer 1, hidden side
+ *   38  slab2  GRU weight-gradient slabs of the side stream */
 int sir_model_train_workspace_offsets(const sir_handle* h, int batch, int t_frames, size_t* offsets, int n);
 
 /* ---- fine-tuning step -------------------------------------------------------------------------

@@ -99,9 +99,11 @@ __device__ __forceinline__ void prep_conv_w_bf16x3_elem(const float* __restrict_
     wpb[(size_t)total + idx] = m;
     wpb[2 * (size_t)total + idx] = l;
 }
+#ifndef SIR_NO_STANDALONE_KERNELS
 static __global__ void prep_conv_w_bf16x3_kernel(const float* __restrict__ w, unsigned short* __restrict__ wpb, int cin, int cout) {
     prep_conv_w_bf16x3_elem(w, wpb, cin, cout, blockIdx.x * blockDim.x + threadIdx.x);
 }
+#endif
 
 // data-gradient weights as bf16x3 planes: roles of the channel axes swapped, taps flipped (cf. prep_conv_wT_kernel);
 // output channels co' = forward INPUT channels, 16-groups over the forward OUTPUT channels
@@ -116,9 +118,11 @@ __device__ __forceinline__ void prep_conv_wT_bf16x3_elem(const float* __restrict
     wpb[(size_t)total + idx] = m;
     wpb[2 * (size_t)total + idx] = l;
 }
+#ifndef SIR_NO_STANDALONE_KERNELS
 static __global__ void prep_conv_wT_bf16x3_kernel(const float* __restrict__ w, unsigned short* __restrict__ wpb, int cin_f, int cout_f) {
     prep_conv_wT_bf16x3_elem(w, wpb, cin_f, cout_f, blockIdx.x * blockDim.x + threadIdx.x);
 }
+#endif
 
 // ------------------------------------------------------------------------------------------
 // Second generation of the bf16x6 convolution: output channels split ACROSS the waves.

@@ -1,5 +1,5 @@
 // Host launcher of one forward conv stage (conv2: 32 -> 64 channels on 32-row maps, conv3: 64 -> 128 on 16-row maps), shared by
-// model_infer.hip and model_train.hip: the Winograd f16x3 kernel, or the bf16x6 fallback of that stage.
+// model_infer.hip and model_train_fwd.hip: the Winograd f16x3 kernel, or the bf16x6 fallback of that stage.
 #pragma once
 #include "conv_wino2_f16x3_kernel.h"
 

@@ -101,10 +101,12 @@ __device__ __forceinline__ void prep_conv_w_wino_f16x3_elem(const float* __restr
     if (j == 3) u = -u;
     split_w_f16x3(u, wpb[idx], wpb[(size_t)total + idx], status);
 }
+#ifndef SIR_NO_STANDALONE_KERNELS
 static __global__ void prep_conv_w_wino_f16x3_kernel(const float* __restrict__ w, unsigned short* __restrict__ wpb, int cin, int cout,
                                                      unsigned int* status) {
     prep_conv_w_wino_f16x3_elem(w, wpb, cin, cout, blockIdx.x * blockDim.x + threadIdx.x, status);
 }
+#endif
 __device__ __forceinline__ void prep_conv_wT_wino_f16x3_elem(const float* __restrict__ w, unsigned short* __restrict__ wpb, int cin_f, int cout_f,
                                                              int idx, unsigned int* status) {
     const int total = cout_f * 16 * cin_f;
@@ -124,10 +126,12 @@ __device__ __forceinline__ void prep_conv_wT_wino_f16x3_elem(const float* __rest
     if (j == 3) u = -u;
     split_w_f16x3(u, wpb[idx], wpb[(size_t)total + idx], status);
 }
+#ifndef SIR_NO_STANDALONE_KERNELS
 static __global__ void prep_conv_wT_wino_f16x3_kernel(const float* __restrict__ w, unsigned short* __restrict__ wpb, int cin_f, int cout_f,
                                                        unsigned int* status) {
     prep_conv_wT_wino_f16x3_elem(w, wpb, cin_f, cout_f, blockIdx.x * blockDim.x + threadIdx.x, status);
 }
+#endif
 
 // OUT_MODE 0: pooled NHWC (BN + ReLU + max), 1: pooled in the GRU layout [b][tx][co * Hp + ty] (+ its f16x2 planes through
 // `stats`), 2: raw NHWC + channel statistics (float2 {sum, sum of squares} at stats[(workgroup * 4 + row wave) * COUT + co]), 3: raw NHWC
@@ -585,7 +589,7 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_f16x3_kernel(
 }
 
 // `g`: wino2_geo of the launch (model_shape.h keeps the model's).  The dynamic-LDS opt-in (W2_LDS_BYTES) is the caller's: the library's
-// goes through sir_lds_opt_in at its launch sites (model_infer.hip / model_train.hip).
+// goes through sir_lds_opt_in at its launch sites (model_infer.hip / model_train_fwd.hip / model_train_bwd.hip).
 // ctab (OUT_MODE 0 / 1 only): compacted task-column list in device memory (Wino2Geo::ctab), at most ncol_max columns
 template <int CIN, int COUT, int OUT_MODE, int DBG = 0, int PRIO = 3>
 static inline hipError_t launch_conv_wino2(hipStream_t st, Wino2Geo g, const float* x, const unsigned short* wpb, const float* scale,

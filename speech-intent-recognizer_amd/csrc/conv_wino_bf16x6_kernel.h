@@ -54,9 +54,11 @@ __device__ __forceinline__ void prep_conv_w_wino_bf16x3_elem(const float* __rest
     wpb[(size_t)total + idx] = m;
     wpb[2 * (size_t)total + idx] = l;
 }
+#ifndef SIR_NO_STANDALONE_KERNELS
 static __global__ void prep_conv_w_wino_bf16x3_kernel(const float* __restrict__ w, unsigned short* __restrict__ wpb, int cin, int cout) {
     prep_conv_w_wino_bf16x3_elem(w, wpb, cin, cout, blockIdx.x * blockDim.x + threadIdx.x);
 }
+#endif
 
 // U = G g G^T of the DATA-GRADIENT convolution (channel roles swapped, taps flipped: cf. prep_conv_wT_bf16x3_elem) as
 // bf16x3 planes wpb[plane][(co_f / 16) * 16 + f][ci_f][co_f % 16]; "output" channels = forward INPUT channels
@@ -82,9 +84,11 @@ __device__ __forceinline__ void prep_conv_wT_wino_bf16x3_elem(const float* __res
     wpb[(size_t)total + idx] = m;
     wpb[2 * (size_t)total + idx] = l;
 }
+#ifndef SIR_NO_STANDALONE_KERNELS
 static __global__ void prep_conv_wT_wino_bf16x3_kernel(const float* __restrict__ w, unsigned short* __restrict__ wpb, int cin_f, int cout_f) {
     prep_conv_wT_wino_bf16x3_elem(w, wpb, cin_f, cout_f, blockIdx.x * blockDim.x + threadIdx.x);
 }
+#endif
 
 // grid (ceil(ceil(W / 2) / 2), ceil(H / 32), B): one block of 16 x 2 tiles per workgroup
 // KNOCK (devtools/kernel_ab/bench_conv.hip timing experiments, results invalid; 0 in the product): bit 0 = no patch loads, bit 1 = no

@@ -62,7 +62,9 @@ __device__ __forceinline__ void split2h_rows(const float* __restrict__ in, int l
         *reinterpret_cast<uint4*>(out + plane + o) = make_uint4(l0.x, l0.y, l1.x, l1.y);
     }
 }
+#ifndef SIR_NO_STANDALONE_KERNELS
 static __global__ __launch_bounds__(256) void split2h_kernel(const float* __restrict__ in, int ld_in, unsigned short* __restrict__ out,
                                                               size_t rows, int K) {
     split2h_rows(in, ld_in, out, rows, K, (size_t)blockIdx.x * 256 + threadIdx.x, (size_t)gridDim.x * 256);
 }
+#endif

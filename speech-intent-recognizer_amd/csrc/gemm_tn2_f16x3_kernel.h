@@ -20,7 +20,6 @@
 
 constexpr int TN2_NPW = 8;                                   // producer waves (two per SIMD: one wave issues too slowly, see below)
 constexpr int TN2_THREADS = 64 * (TN2_NPW + 8);              // + 8 consumer waves
-constexpr int TN2_BM = 128;
 constexpr size_t tn2_lds_bytes(bool a_km, int bm = TN2_BM) { return 2 * tn_lds_bytes(a_km, bm); }     // two stage buffers: 147,456 / 159,744 B (BM = 128)
 
 constexpr float TN2_BS = 0.0625f;

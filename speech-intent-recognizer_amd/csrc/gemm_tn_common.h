@@ -19,6 +19,7 @@
 #include "bf16x6_kernels.h"
 
 constexpr int TN_BM = 128, TN_BN = 256, TN_BK = 32;
+constexpr int TN2_BM = 128;                                   // (gemm_tn2_f16x3_kernel.h; here because the workspace sizing reads it too)
 constexpr int TN_ROWB = TN_BK * 2 + 16;                      // k-contiguous image (A of dX): 80 B per row, 5 sixteen-byte slots (odd -> conflict-free b128 reads)
 // k-major image of an operand given as [k][x] (x contiguous): per plane 32 rows of 2 X bytes, 64-byte chunks swizzled
 constexpr size_t tn_lds_bytes(bool a_km, int bm) {
@@ -43,7 +44,7 @@ __device__ __forceinline__ bf16x8 tn_tr_fragment(const unsigned char* p) {
     return __builtin_bit_cast(bf16x8, f);
 }
 
-// keep mask of the inter-layer dropout (same function as train_kernels.h dropout_keep; the dX GEMM of layer 1 applies the
+// keep mask of the inter-layer dropout (same function as train_fwd_kernels.h dropout_keep; the dX GEMM of layer 1 applies the
 // dropout BACKWARD in its epilogue: its output IS d(dropout(y0)), and y0's gradient is that times the mask / (1 - p))
 __device__ __forceinline__ bool tn_dropout_keep(unsigned long long seed, size_t idx, float p) {
     unsigned long long x = seed ^ (idx * 0x9E3779B97F4A7C15ull);

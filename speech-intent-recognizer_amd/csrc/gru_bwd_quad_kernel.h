@@ -18,7 +18,7 @@
 //     other quarters sent: a reduce-scatter where the forward kernel has an all-gather.  Summation order is fixed: bit-reproducible.
 //     The completed values go back to the gate role through a 4 KB LDS image (one more barrier per step).
 // Accuracy: the f16x3 product (three MFMAs per fp32 product, hi * hi and the two cross terms in separate f32 accumulators); the
-// gate gradients carry the loss scale of the backward (model_train.hip) and sit inside fp16's range like the dW operands.
+// gate gradients carry the loss scale of the backward (model_train_bwd.hip) and sit inside fp16's range like the dW operands.
 #pragma once
 #include "gru_quad_kernel.h"
 

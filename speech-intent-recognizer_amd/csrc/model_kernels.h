@@ -16,12 +16,17 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float mk_f32x2 __attribute__((ext_vector_type(2)));
 
 #define SIR_BN_EPS 1e-5f
+// SIR_NO_STANDALONE_KERNELS, defined by a translation unit in front of its includes: the non-template kernels of the shared headers
+// (this one, f16_split.h, bf16x6_kernels.h, conv_wino_bf16x6_kernel.h, conv_wino2_f16x3_kernel.h) are left out.  A static __global__
+// is compiled into every unit that sees it, launched there or not; a unit that only wants the device functions, templates and
+// constants says so and the library holds no further copy.
 
 // ------------------------------------------------------------------------------------------
 // weight preparation (tiny, runs at the head of every forward so it always sees current weights)
 // ------------------------------------------------------------------------------------------
 
 // eval-mode BatchNorm folded to y = x*scale + shift (models/models.py:50-52, running stats)
+#ifndef SIR_NO_STANDALONE_KERNELS
 static __global__ void prep_bn_kernel(const float* __restrict__ g, const float* __restrict__ b, const float* __restrict__ mean,
                                const float* __restrict__ var, float* __restrict__ scale, float* __restrict__ shift, int c) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -30,6 +35,7 @@ static __global__ void prep_bn_kernel(const float* __restrict__ g, const float* 
     scale[i] = s;
     shift[i] = b[i] - mean[i] * s;
 }
+#endif
 
 // ------------------------------------------------------------------------------------------
 // conv1 (1 -> 32 channels) + BN + ReLU + 2x2 max-pool, direct form (K = 9: memory-bound)
@@ -48,6 +54,7 @@ constexpr int C1_TR = 2 * C1_PROWS + 2, C1_TC = 2 * C1_PCOLS + 2;
 // Wave w = pooled row w of the 4 x 32 pooled-pixel block; per half (32 conv columns) two accumulators (the two conv rows
 // of the pooled row); 2x2 max = max of the two accumulators and of lanes j, j ^ 1.  Even lanes then store channel groups
 // 0, 1 and odd lanes groups 2, 3 of pooled pixel j / 2 (two float4 stores per lane).
+#ifndef SIR_NO_STANDALONE_KERNELS
 static __global__ __launch_bounds__(256, 4) void conv1_mfma_bn_relu_pool_kernel(
     const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ scale,
     const float* __restrict__ shift, float* __restrict__ out, int H, int W, int Hp, int Wp,
@@ -141,6 +148,7 @@ static __global__ __launch_bounds__(256, 4) void conv1_mfma_bn_relu_pool_kernel(
         }
     }
 }
+#endif
 
 // ------------------------------------------------------------------------------------------
 // C[m][z*N + n] = sum_k A[m][k] * Bz[n][k] + biasz[n]    (fp32 MFMA, "NT": both operands k-contiguous)
@@ -195,6 +203,7 @@ __device__ __forceinline__ void gru_fma4(float (&acc)[NB], const float4 w, const
 // ------------------------------------------------------------------------------------------
 // (ATT_MAX_S: model_shape.h)
 
+#ifndef SIR_NO_STANDALONE_KERNELS
 static __global__ __launch_bounds__(256) void attention_pool_kernel(const float* __restrict__ y, const float* __restrict__ aw,
                                                              const float* __restrict__ ab, float* __restrict__ ctx,
                                                              int S, const float* __restrict__ fcw,
@@ -279,4 +288,5 @@ static __global__ __launch_bounds__(256) void attention_pool_kernel(const float*
         amax[b] = bi;
     }
 }
+#endif
 

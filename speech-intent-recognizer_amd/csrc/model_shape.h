@@ -5,7 +5,7 @@
 #pragma once
 #include "wino2_geo.h"
 
-constexpr int ATT_MAX_S = 256;      // GRU steps the attention kernels hold in LDS (model_kernels.h, train_kernels.h)
+constexpr int ATT_MAX_S = 256;      // GRU steps the attention kernels hold in LDS (model_kernels.h, train_bwd_kernels.h)
 
 // conv stage `conv` (2 or 3) runs on its Winograd kernel (second-generation forward / data gradient, Winograd weight gradient) if
 // `shape_ok` -- else on the first-generation / direct fallback.  Test-only SIR_CONV_FALLBACK: 1 = conv2's stages do not fit, 2 = none do.

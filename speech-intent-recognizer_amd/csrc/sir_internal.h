@@ -18,7 +18,7 @@ void sir_set_error(const char* fmt, ...);
 enum SirKernelId {
     SIR_K_FEAT_FRAMES = 0, SIR_K_FEAT_NORM, SIR_K_PREP, SIR_K_CONV1, SIR_K_CONV2, SIR_K_CONV3,
     SIR_K_GEMM_IH0, SIR_K_GRU0, SIR_K_GEMM_IH1, SIR_K_GRU1, SIR_K_ATTN, SIR_K_FC,
-    // training step (model_train.hip): forward groups, loss, backward groups, optimizer
+    // training step (model_train_fwd.hip, train_loss_optim.hip, model_train_bwd.hip): forward groups, loss, backward groups, optimizer
     SIR_K_T_PREP, SIR_K_T_CONV1, SIR_K_T_CONV2, SIR_K_T_BN2, SIR_K_T_CONV3, SIR_K_T_BN3, SIR_K_T_GEMM_IH0, SIR_K_T_GRU0,
     SIR_K_T_DROPOUT, SIR_K_T_GEMM_IH1, SIR_K_T_GRU1, SIR_K_T_HEAD, SIR_K_CE,
     SIR_K_B_HEAD, SIR_K_B_GRU1, SIR_K_B_DW1, SIR_K_B_DX1, SIR_K_B_GRU0, SIR_K_B_DW0, SIR_K_B_DX0,
@@ -92,7 +92,7 @@ struct sir_handle {
     XbufEntry xbufs[16];
     unsigned long long xbuf_clock;
     unsigned long long xbuf_evictions;   // LRU evictions so far (each costs a device-synchronising hipFree + hipMalloc on the launch path)
-    // second stream of the training backward (model_train.hip): the off-chain weight-gradient launches; created on first use.
+    // second stream of the training backward (model_train_bwd.hip): the off-chain weight-gradient launches; created on first use.
     // ev: 0 fork behind the GRU part, 1 / 2 dz3 / dz2 ready, 3 join, 4 / 5 GRU layer 0 / 1 BPTT done
     hipStream_t bwd_side;
     hipEvent_t bwd_ev[6];
@@ -211,7 +211,7 @@ struct SirProfScope {
     }
 };
 
-// model_train.hip
+// model_train_fwd.hip
 size_t sir_train_workspace_bytes_impl(int batch, int t_frames);
 
 // features.hip

@@ -1,366 +1,9 @@
-// Training-only device kernels (forward pieces that differ from inference, backward, optimiser).
-// Included by model_train.hip.  Layouts as in model_kernels.h (NHWC activations).
+// Training-only device kernels of the BACKWARD: head, BatchNorm / pool / ReLU, conv1, the slab reduces of the weight gradients.
+// Included by model_train_bwd.hip.  Layouts as in model_kernels.h (NHWC activations).
 #pragma once
 #include "model_kernels.h"
-#include "bf16x6_kernels.h"
-#include "conv_wino2_f16x3_kernel.h"
-#include "gru_frag_prep.h"
+#include "train_workspace.h"
 
-// ------------------------------------------------------------------------------------------
-// BatchNorm with batch statistics
-// ------------------------------------------------------------------------------------------
-
-// ------------------------------------------------------------------------------------------
-// conv1 BatchNorm statistics WITHOUT computing conv1: z_c = sum_t w_c[t] x_t with x_t the nine shifted copies of the
-// (zero-padded) feature image, hence
-//     sum z_c   = sum_t w_c[t] S[t]                       S[t]     = sum_pixels x_t
-//     sum z_c^2 = sum_{t,u} w_c[t] w_c[u] R[t][u]         R[t][u]  = sum_pixels x_t x_u
-// -- 9 + 45 moments of the INPUT, the same for all 32 channels (one pass over 13 MB instead of recomputing 105 M conv
-// outputs x 32 channels).  The backward reuses them for the mean terms of the weight gradient (conv1_bwd_finalize_kernel).
-// Moment layout M[54]: S[0..8], then R packed by rows, t <= u: index 9 + t*9 - t*(t-1)/2 + (u - t).
-// ------------------------------------------------------------------------------------------
-constexpr int C1_NMOM = 54;
-__host__ __device__ constexpr int c1_r_index(int t, int u) { return 9 + t * 9 - t * (t - 1) / 2 + (u - t); }   // t <= u
-
-// wave WV of a block accumulates the moments [14 WV, 14 WV + 14) -- over ALL pixels of a tile -- so that each of the 54 sums
-// is reduced across 64 lanes exactly once per block (with 54 accumulators in every thread the wave reductions cost more than
-// the accumulation itself)
-constexpr int C1_MPW = 14;
-template <int WV>
-__device__ __forceinline__ void c1_moments_accum(const float (&v)[9], float (&m)[C1_MPW]) {
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-        if (t / C1_MPW == WV) m[t - C1_MPW * WV] += v[t];
-#pragma unroll
-        for (int u = t; u < 9; ++u)
-            if (c1_r_index(t, u) / C1_MPW == WV) m[c1_r_index(t, u) - C1_MPW * WV] = fmaf(v[t], v[u], m[c1_r_index(t, u) - C1_MPW * WV]);
-    }
-}
-
-// block (g, b) walks the 8 x 64-pixel tiles g, g + gridDim.x, ... of image b; part[54][gridDim.y * gridDim.x] (moment-major: the
-// reduce kernel then reads contiguous rows -- block-major rows of 54 floats made it a 216-byte-stride gather, 37 us for 442 KB)
-static __global__ __launch_bounds__(256) void conv1_moments_kernel(const float* __restrict__ x, float* __restrict__ part, int H, int W,
-                                                                    int tiles_x, int tiles_y) {
-    __shared__ float tile[C1_TR * C1_TC];
-    const int b = blockIdx.y;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const float* xb = x + (size_t)b * H * W;
-    float m[C1_MPW];
-#pragma unroll
-    for (int i = 0; i < C1_MPW; ++i) m[i] = 0.0f;
-    for (int tl = blockIdx.x; tl < tiles_x * tiles_y; tl += gridDim.x) {
-        const int y0 = 2 * (tl / tiles_x) * C1_PROWS, x0 = 2 * (tl % tiles_x) * C1_PCOLS;
-        __syncthreads();                                   // previous tile consumed
-        for (int i = tid; i < C1_TR * C1_TC; i += 256) {
-            const int ty = i / C1_TC, tx = i - ty * C1_TC;
-            const int gy = y0 - 1 + ty, gx = x0 - 1 + tx;
-            tile[i] = (gy >= 0 && gy < H && gx >= 0 && gx < W) ? xb[(size_t)gy * W + gx] : 0.0f;
-        }
-        __syncthreads();
-        for (int k = 0; k < (4 * C1_PROWS * C1_PCOLS) / 64; ++k) {          // 512 pixels / 64 lanes
-            const int pix = lane + 64 * k, ly = pix / (2 * C1_PCOLS), lx = pix % (2 * C1_PCOLS);
-            if (y0 + ly >= H || x0 + lx >= W) continue;
-            float v[9];
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx) v[ky * 3 + kx] = tile[(ly + ky) * C1_TC + lx + kx];
-            switch (wv) {                                   // wave-uniform
-                case 0: c1_moments_accum<0>(v, m); break;
-                case 1: c1_moments_accum<1>(v, m); break;
-                case 2: c1_moments_accum<2>(v, m); break;
-                default: c1_moments_accum<3>(v, m); break;
-            }
-        }
-    }
-    const size_t blk = (size_t)b * gridDim.x + blockIdx.x, nblk = (size_t)gridDim.x * gridDim.y;
-#pragma unroll
-    for (int i = 0; i < C1_MPW; ++i) {
-        float a = m[i];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
-        if (lane == 0 && C1_MPW * wv + i < C1_NMOM) part[(size_t)(C1_MPW * wv + i) * nblk + blk] = a;
-    }
-}
-
-// M[i] = sum over blocks (double); one block per moment
-static __global__ __launch_bounds__(256) void conv1_moments_reduce_kernel(const float* __restrict__ part, int nblk, double* __restrict__ M) {
-    __shared__ double rs[256];
-    const int i = blockIdx.x, tid = threadIdx.x;
-    double s = 0.0;
-#pragma unroll 8
-    for (int r = tid; r < nblk; r += 256) s += part[(size_t)i * nblk + r];
-    rs[tid] = s;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) rs[tid] += rs[tid + o];
-        __syncthreads();
-    }
-    if (tid == 0) M[i] = rs[0];
-}
-
-__device__ __forceinline__ void bn_finalize_channel(double sum, double sumsq, double count, int c, const float* __restrict__ gamma,
-                                                    const float* __restrict__ beta, float* __restrict__ run_mean,
-                                                    float* __restrict__ run_var, float momentum, float* __restrict__ scale,
-                                                    float* __restrict__ shift, float* __restrict__ save_mean,
-                                                    float* __restrict__ save_invstd) {
-    const double mean = sum / count;
-    double var = sumsq / count - mean * mean;
-    if (var < 0.0) var = 0.0;
-    const float invstd = (float)(1.0 / sqrt(var + (double)SIR_BN_EPS));
-    const float sc = gamma[c] * invstd;
-    scale[c] = sc;
-    shift[c] = beta[c] - (float)mean * sc;
-    save_mean[c] = (float)mean;
-    save_invstd[c] = invstd;
-    const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-    run_mean[c] = (1.0f - momentum) * run_mean[c] + momentum * (float)mean;
-    run_var[c] = (1.0f - momentum) * run_var[c] + momentum * (float)unbiased;
-}
-
-// per channel: (sum z, sum z^2) from the moments and the nine weights, then the usual BatchNorm finalisation; 32 threads
-static __global__ void conv1_bn_from_moments_kernel(const double* __restrict__ M, const float* __restrict__ w, double count,
-                                                    const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                    float* __restrict__ run_mean, float* __restrict__ run_var, float momentum,
-                                                    float* __restrict__ scale, float* __restrict__ shift,
-                                                    float* __restrict__ save_mean, float* __restrict__ save_invstd) {
-    const int c = threadIdx.x;
-    if (c >= 32) return;
-    double wk[9];
-    for (int t = 0; t < 9; ++t) wk[t] = (double)w[c * 9 + t];
-    double sum = 0.0, sumsq = 0.0;
-    for (int t = 0; t < 9; ++t) {
-        sum += wk[t] * M[t];
-        sumsq += wk[t] * wk[t] * M[c1_r_index(t, t)];
-        for (int u = t + 1; u < 9; ++u) sumsq += 2.0 * wk[t] * wk[u] * M[c1_r_index(t, u)];
-    }
-    bn_finalize_channel(sum, sumsq, count, c, gamma, beta, run_mean, run_var, momentum, scale, shift, save_mean, save_invstd);
-}
-
-// partial (sum, sumsq) [nblk][C] -> batch mean / biased var -> folded scale/shift for the forward,
-// saved mean / invstd for the backward, running statistics updated in place
-// (momentum 0.1, unbiased variance: torch.nn.BatchNorm2d training semantics).  One block per channel.
-static __global__ __launch_bounds__(256) void bn_finalize_kernel(const float2* __restrict__ stats, int nblk, int C, double count,
-                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                           float* __restrict__ run_mean, float* __restrict__ run_var,
-                                                           float momentum, float* __restrict__ scale,
-                                                           float* __restrict__ shift, float* __restrict__ save_mean,
-                                                           float* __restrict__ save_invstd) {
-    __shared__ double rs[256], rq[256];
-    const int c = blockIdx.x, tid = threadIdx.x;
-    double s = 0.0, q = 0.0;
-#pragma unroll 4
-    for (int i = tid; i < nblk; i += 256) {
-        const float2 v = stats[(size_t)i * C + c];
-        s += v.x;
-        q += v.y;
-    }
-    rs[tid] = s; rq[tid] = q;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) { rs[tid] += rs[tid + o]; rq[tid] += rq[tid + o]; }
-        __syncthreads();
-    }
-    if (tid == 0)
-        bn_finalize_channel(rs[0], rq[0], count, c, gamma, beta, run_mean, run_var, momentum, scale, shift, save_mean, save_invstd);
-}
-
-// Frozen statistics (bnK.eval() inside a training step): the running mean / variance take the place of the batch ones in the
-// four per-channel arrays that the apply kernels and the backward read; nothing is reduced and the running statistics stay as
-// they are.  One thread per channel.
-static __global__ void bn_fold_running_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
-                                              const float* __restrict__ run_mean, const float* __restrict__ run_var, int C,
-                                              float* __restrict__ scale, float* __restrict__ shift,
-                                              float* __restrict__ save_mean, float* __restrict__ save_invstd) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= C) return;
-    const float mean = run_mean[c];
-    const float invstd = (float)(1.0 / sqrt((double)run_var[c] + (double)SIR_BN_EPS));
-    const float sc = gamma[c] * invstd;
-    scale[c] = sc;
-    shift[c] = beta[c] - mean * sc;
-    save_mean[c] = mean;
-    save_invstd[c] = invstd;
-}
-
-// z (raw conv output, NHWC [B][H][W][C]) -> relu(bn(z)) -> 2x2 max-pool.
-// GRU_OUT = false: NHWC [B][Hp][Wp][C];  true: [B][Wp][C*Hp] with feature = c*Hp + py (models.py:55-57)
-template <bool GRU_OUT>
-__global__ __launch_bounds__(256) void bn_relu_pool_kernel(const float* __restrict__ z, const float* __restrict__ scale,
-                                                            const float* __restrict__ shift, float* __restrict__ out,
-                                                            int B, int H, int W, int C, int Hp, int Wp) {
-    const int c4n = C / 4;
-    const size_t total = (size_t)B * Hp * Wp * c4n;
-    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
-        int c4, px, py, b;
-        if (!GRU_OUT) {
-            c4 = idx % c4n;
-            size_t rest = idx / c4n;
-            px = rest % Wp; rest /= Wp;
-            py = rest % Hp;
-            b = rest / Hp;
-        } else {                                      // py fastest: the lanes of a wave then fill whole 32-byte sectors of
-            py = idx % Hp;                            // the [c*Hp + py] feature rows (c4 fastest scattered single floats)
-            size_t rest = idx / Hp;
-            c4 = rest % c4n; rest /= c4n;
-            px = rest % Wp;
-            b = rest / Wp;
-        }
-        const float4 s = *reinterpret_cast<const float4*>(scale + c4 * 4);
-        const float4 t = *reinterpret_cast<const float4*>(shift + c4 * 4);
-        float4 best = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int dy = 0; dy < 2; ++dy)
-#pragma unroll
-            for (int dx = 0; dx < 2; ++dx) {
-                const float4 v = *reinterpret_cast<const float4*>(
-                    z + (((size_t)b * H + 2 * py + dy) * W + 2 * px + dx) * C + c4 * 4);
-                best.x = fmaxf(best.x, fmaf(v.x, s.x, t.x));
-                best.y = fmaxf(best.y, fmaf(v.y, s.y, t.y));
-                best.z = fmaxf(best.z, fmaf(v.z, s.z, t.z));
-                best.w = fmaxf(best.w, fmaf(v.w, s.w, t.w));
-            }
-        if (!GRU_OUT) {
-            *reinterpret_cast<float4*>(out + (((size_t)b * Hp + py) * Wp + px) * C + c4 * 4) = best;
-        } else {
-            float* o = out + ((size_t)b * Wp + px) * ((size_t)C * Hp) + (size_t)(c4 * 4) * Hp + py;
-            o[0] = best.x; o[Hp] = best.y; o[2 * Hp] = best.z; o[3 * Hp] = best.w;
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// inter-layer GRU dropout (models.py:32, p = 0.5 in train()): counter-based keep mask, a pure
-// function of (seed, element index) so the backward pass regenerates it.
-// ------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool dropout_keep(unsigned long long seed, size_t idx, float p) {
-    unsigned long long x = seed ^ (idx * 0x9E3779B97F4A7C15ull);
-    x ^= x >> 33; x *= 0xFF51AFD7ED558CCDull; x ^= x >> 33; x *= 0xC4CEB9FE1A85EC53ull; x ^= x >> 33;
-    return (float)(unsigned)(x >> 40) * (1.0f / 16777216.0f) >= p;
-}
-
-// out = dropout(in) AND the f16x2 planes [2][n] of out (the A operand of the next layer's input projection) in one pass;
-// one thread = 8 consecutive elements (n is a multiple of 8: rows of 512)
-static __global__ __launch_bounds__(256) void dropout_split2h_kernel(const float* __restrict__ in, float* __restrict__ out,
-                                                                      unsigned short* __restrict__ planes, size_t n, float p,
-                                                                      unsigned long long seed) {
-    const float sc = 1.0f / (1.0f - p);
-    for (size_t i8 = (size_t)blockIdx.x * 256 + threadIdx.x; i8 < n / 8; i8 += (size_t)gridDim.x * 256) {
-        const size_t i = i8 * 8;
-        float v[8];
-        *reinterpret_cast<float4*>(v) = *reinterpret_cast<const float4*>(in + i);
-        *reinterpret_cast<float4*>(v + 4) = *reinterpret_cast<const float4*>(in + i + 4);
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = dropout_keep(seed, i + e, p) ? v[e] * sc : 0.0f;
-        const float4 v0 = make_float4(v[0], v[1], v[2], v[3]), v1 = make_float4(v[4], v[5], v[6], v[7]);
-        *reinterpret_cast<float4*>(out + i) = v0;
-        *reinterpret_cast<float4*>(out + i + 4) = v1;
-        uint2 h0, l0, h1, l1;
-        split2h_quad(v0, h0, l0);
-        split2h_quad(v1, h1, l1);
-        *reinterpret_cast<uint4*>(planes + i) = make_uint4(h0.x, h0.y, h1.x, h1.y);
-        *reinterpret_cast<uint4*>(planes + n + i) = make_uint4(l0.x, l0.y, l1.x, l1.y);
-    }
-}
-
-// ------------------------------------------------------------------------------------------
-// cross-entropy (mean) forward + gradient wrt logits:  loss = -mean_b log softmax(l_b)[y_b],
-// dlogits = (softmax - onehot) * grad_scale / (rows whose label is not ignore_index)      (nn.CrossEntropyLoss(), train.py:242)
-// single workgroup, deterministic reduction
-// SOFT (sir_ce_loss_soft): the target of row b is q = (1 - eps) (lam e[ya] + (1 - lam) e[yb]) + eps / C instead of e[ya]
-// (mixup's two labels and label smoothing); loss_b = -sum_c q[c] log softmax[c] = log(den) - sum_c q[c] (l[c] - max) because
-// sum q = 1, dlogits = softmax - q.  SOFT = false is sir_ce_loss's kernel, instruction for instruction: `labels_b`, `lam`
-// and `eps` are not read.
-// ------------------------------------------------------------------------------------------
-template <int CMAX, bool SOFT>
-static __global__ __launch_bounds__(256) void ce_loss_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
-                                                       int B, int C, float* __restrict__ loss, float* __restrict__ dlogits,
-                                                       float grad_scale, unsigned int* status,
-                                                       const long long* __restrict__ labels_b, const float* __restrict__ lam,
-                                                       float eps) {
-    __shared__ float red[256];
-    __shared__ int cnt[256];
-    // nn.CrossEntropyLoss() has ignore_index = -100 by default: such a row contributes neither loss nor gradient and the mean is
-    // taken over the remaining rows (all rows ignored: 0 / 0 = NaN, as torch)
-    int nv = 0;
-    for (int b = threadIdx.x; b < B; b += 256) nv += labels[b] != -100ll ? 1 : 0;
-    cnt[threadIdx.x] = nv;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) cnt[threadIdx.x] += cnt[threadIdx.x + o];
-        __syncthreads();
-    }
-    const float nvalid = (float)cnt[0];
-    float acc = 0.0f;
-    for (int b = threadIdx.x; b < B; b += 256) {
-        // the row goes into registers with ALL its loads in flight (C <= CMAX, dispatched by the host): the per-class loops of
-        // the first version waited for one dependent load after the other, 15 us for 256 x 31 logits
-        const float* r = logits + (size_t)b * C;
-        // any OTHER label outside [0, C) (nn.CrossEntropyLoss raises on it; train.py:242): flag the handle's status word (bit 1 ->
-        // SIR_EINVAL at the next sir_check_status) and make the loss NaN instead of reading out of bounds
-        const long long yl = labels[b];
-        const bool ignored = yl == -100ll;
-        const bool bad = !ignored && (yl < 0 || yl >= (long long)C);
-        if (bad) __hip_atomic_fetch_or(status, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int y = (bad || ignored) ? 0 : (int)yl;
-        if constexpr (SOFT) {
-            // the second label of an ignored row is not read; a bad one is flagged like a bad first label
-            const long long yl2 = (labels_b && !ignored) ? labels_b[b] : yl;
-            const bool bad2 = !ignored && (yl2 < 0 || yl2 >= (long long)C);
-            if (bad2) __hip_atomic_fetch_or(status, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int y2 = (bad2 || ignored) ? 0 : (int)yl2;
-            const float lm = (labels_b && lam) ? lam[b] : 1.0f;
-            const float wa = (1.0f - eps) * lm, wb = (1.0f - eps) * (1.0f - lm), u = eps / (float)C;
-            float v[CMAX];
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c) v[c] = c < C ? r[c] : 0.0f;
-            const float ra = r[y], rb = r[y2];
-            float mx = v[0];
-#pragma unroll
-            for (int c = 1; c < CMAX; ++c) if (c < C) mx = fmaxf(mx, v[c]);
-            float den = 0.0f, dsum = 0.0f;
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c) if (c < C) { const float d = v[c] - mx; dsum += d; v[c] = expf(d); den += v[c]; }
-            const float row = logf(den) - (wa * (ra - mx) + wb * (rb - mx) + u * dsum);
-            acc += (bad || bad2) ? __builtin_nanf("") : (ignored ? 0.0f : row);
-            if (dlogits) {
-                const float inv = 1.0f / den, gs = ignored ? 0.0f : grad_scale / nvalid;
-#pragma unroll
-                for (int c = 0; c < CMAX; ++c)
-                    if (c < C) {
-                        const float q = u + (c == y ? wa : 0.0f) + (c == y2 ? wb : 0.0f);
-                        dlogits[(size_t)b * C + c] = ignored ? 0.0f : (v[c] * inv - q) * gs;
-                    }
-            }
-            continue;
-        }
-        float v[CMAX];
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c) v[c] = c < C ? r[c] : 0.0f;
-        const float ry = r[y];
-        float mx = v[0];
-#pragma unroll
-        for (int c = 1; c < CMAX; ++c) if (c < C) mx = fmaxf(mx, v[c]);
-        float den = 0.0f;
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c) if (c < C) { v[c] = expf(v[c] - mx); den += v[c]; }
-        const float lse = mx + logf(den);
-        acc += bad ? __builtin_nanf("") : (ignored ? 0.0f : lse - ry);
-        if (dlogits) {
-            const float inv = 1.0f / den, gs = ignored ? 0.0f : grad_scale / nvalid;
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c)
-                if (c < C) dlogits[(size_t)b * C + c] = ignored ? 0.0f : (v[c] * inv - (c == y ? 1.0f : 0.0f)) * gs;
-        }
-    }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) loss[0] = red[0] / nvalid;
-}
 // ------------------------------------------------------------------------------------------
 // head backward: fc + attention pooling (models.py:63-67)
 //   dctx = dlogits fc_w;  w = softmax_t(y a + b);  dw_t = <dctx, y_t>;  ds_t = w_t (dw_t - sum w dw)
@@ -564,65 +207,7 @@ static __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __res
     head_bwd_utt(blockIdx.x, dlogits, fcw, y, aw, ab, dy, daw_part, dab_part, S, C, gscale);
 }
 
-// ------------------------------------------------------------------------------------------
-// GRU back-propagation through time, one layer, both directions (mirror of gru_recurrence_kernel).
-//   dy    [B][S][512]  gradient wrt the layer output (both directions)
-//   gates [B][S][2][4][256] saved (r, z, n, W_hn h + b_hn);  y = layer output (h_prev = neighbour step)
-//   wr4   [2][192][256][4]  W_hh regrouped by 4 gate rows (prep_whh_bwd_kernel): lane = k
-//   dgi / dgh [B*S][1536]   gradients wrt the input-side / hidden-side gate pre-activations
-// Thread (u, b): gate math for hidden unit u of utterance b; thread (k, rs): partial of W_hh^T dgh
-// over gate rows [192 rs, 192 rs + 192).
-// ------------------------------------------------------------------------------------------
-__device__ __forceinline__ void prep_whh_bwd_elem(const float* __restrict__ w, float* __restrict__ wr4, int idx) {
-    if (idx >= 768 * 256) return;                                 // over 768*256, layout [row/4][k][4]
-    const int e = idx & 3, k = (idx >> 2) & 255, r4 = idx >> 10;
-    wr4[idx] = w[(size_t)(r4 * 4 + e) * 256 + k];
-}
-
-// Every per-step re-layout of the weights (they change with each optimizer step) in ONE launch: a dozen ~5 us launches
-// otherwise.  Job j owns blocks [block0[j], block0[j+1]).
-enum PrepKind {
-    PREP_SPLIT2H = 0,               // split2h_rows (a = ld_in = K, b = rows)
-    PREP_CONV_W_BF16X3 = 1,         // prep_conv_w_bf16x3 (a = cin, b = cout): nine taps, direct fallback
-    PREP_CONV_WT_BF16X3 = 2,        // prep_conv_wT_bf16x3 (a = cin_f, b = cout_f)
-    PREP_WHH_BWD = 3,               // prep_whh_bwd
-    PREP_CONV_W_WINO_BF16X3 = 4,    // prep_conv_w_wino_bf16x3 (a = cin, b = cout): first-generation Winograd fallback
-    PREP_CONV_WT_WINO_BF16X3 = 5,   // prep_conv_wT_wino_bf16x3 (a = cin_f, b = cout_f)
-    PREP_CONV_W_WINO_F16X3 = 6,     // the f16x3 forms of 4 / 5 (conv_wino2_f16x3_kernel.h)
-    PREP_CONV_WT_WINO_F16X3 = 7,
-    PREP_WHH_QUAD = 8,              // W_hh as the resident fragments of the forward / backward cluster recurrence (gru_frag_prep.h)
-    PREP_WHH_BWD_QUAD = 9
-};
-constexpr int PREP_MAX_JOBS = 20;
-struct PrepJobs {
-    const float* src[PREP_MAX_JOBS];
-    void* dst[PREP_MAX_JOBS];
-    int kind[PREP_MAX_JOBS], a[PREP_MAX_JOBS], b[PREP_MAX_JOBS];
-    int block0[PREP_MAX_JOBS + 1];
-    int njobs;
-    unsigned int* status;        // the handle's status word (kinds 6 / 7 flag weights outside the f16x3 range)
-};
-static __global__ __launch_bounds__(256) void train_prep_kernel(PrepJobs jobs) {
-    int j = 0;
-    while (j + 1 < jobs.njobs && (int)blockIdx.x >= jobs.block0[j + 1]) ++j;
-    const int lb = blockIdx.x - jobs.block0[j], nb = jobs.block0[j + 1] - jobs.block0[j];
-    const int idx = lb * 256 + threadIdx.x;
-    const float* __restrict__ src = jobs.src[j];
-    switch (jobs.kind[j]) {
-        case PREP_SPLIT2H: split2h_rows(src, jobs.a[j], (unsigned short*)jobs.dst[j], (size_t)jobs.b[j], jobs.a[j], (size_t)idx, (size_t)nb * 256); break;
-        case PREP_CONV_W_BF16X3: prep_conv_w_bf16x3_elem(src, (unsigned short*)jobs.dst[j], jobs.a[j], jobs.b[j], idx); break;
-        case PREP_CONV_WT_BF16X3: prep_conv_wT_bf16x3_elem(src, (unsigned short*)jobs.dst[j], jobs.a[j], jobs.b[j], idx); break;
-        case PREP_CONV_W_WINO_BF16X3: prep_conv_w_wino_bf16x3_elem(src, (unsigned short*)jobs.dst[j], jobs.a[j], jobs.b[j], idx); break;
-        case PREP_CONV_WT_WINO_BF16X3: prep_conv_wT_wino_bf16x3_elem(src, (unsigned short*)jobs.dst[j], jobs.a[j], jobs.b[j], idx); break;
-        case PREP_CONV_W_WINO_F16X3: prep_conv_w_wino_f16x3_elem(src, (unsigned short*)jobs.dst[j], jobs.a[j], jobs.b[j], idx, jobs.status); break;
-        case PREP_CONV_WT_WINO_F16X3: prep_conv_wT_wino_f16x3_elem(src, (unsigned short*)jobs.dst[j], jobs.a[j], jobs.b[j], idx, jobs.status); break;
-        case PREP_WHH_QUAD: prep_whh_quad_elem(src, (uint4*)jobs.dst[j], idx); break;
-        case PREP_WHH_BWD_QUAD: prep_whh_bwd_quad_elem(src, (uint4*)jobs.dst[j], idx); break;
-        default: prep_whh_bwd_elem(src, (float*)jobs.dst[j], idx); break;
-    }
-}
-
-// Reads two buffers and keeps nothing: a software prefetch into the last-level cache, launched on the backward's side stream (model_train.hip:
+// Reads two buffers and keeps nothing: a software prefetch into the last-level cache, launched on the backward's side stream (model_train_bwd.hip:
 // layer 0's saved gates and outputs ahead of its BPTT)
 static __global__ __launch_bounds__(256) void cache_touch_kernel(const float4* __restrict__ a, size_t na, const float4* __restrict__ b, size_t nb,
                                                                   float* __restrict__ sink) {
@@ -647,8 +232,6 @@ static __global__ void slab_reduce_jobs_kernel(SlabJobs jobs, int nslab, float u
         o[i] = a * unscale;
     }
 }
-
-constexpr int GRU_BBW = 4;      // utterances per workgroup of the backward recurrence
 
 // ------------------------------------------------------------------------------------------
 // backward through max-pool -> ReLU -> BatchNorm (batch statistics).
@@ -1066,7 +649,6 @@ static __global__ void conv1_bwd_finalize_frozen_kernel(const float* __restrict_
 
 // dW[co][ci][tap] = sum_blk slab[blk][tap][co][ci], in two ordered (deterministic) passes: WGR_PARTS partial sums over
 // interleaved-free contiguous slab ranges (grid.y), then their sum + the transpose to the torch layout
-constexpr int WGR_PARTS = 16;
 static __global__ __launch_bounds__(256) void wgrad_reduce_partial_kernel(const float* __restrict__ slab, int nblk, int total4,
                                                                      float* __restrict__ part) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;       // float4 index into one slab
@@ -1097,180 +679,4 @@ static __global__ void wgrad_reduce_kernel(const float* __restrict__ part, int n
 #pragma unroll 8
     for (int k = 0; k < nparts; ++k) s += part[(size_t)k * total + idx];
     dw[((size_t)co * cin + ci) * 9 + tap] = s * unscale;
-}
-
-// ------------------------------------------------------------------------------------------
-// multi-tensor Adam, coupled L2 weight decay (torch.optim.Adam, train.py:246-250): one launch
-// updates every parameter tensor.  Tensors are described by value in the kernel argument.
-// ------------------------------------------------------------------------------------------
-#define SIR_ADAM_MAX_TENSORS 32
-#define SIR_ADAM_CHUNK 4096
-
-struct AdamTensors {
-    float* p[SIR_ADAM_MAX_TENSORS];
-    const float* g[SIR_ADAM_MAX_TENSORS];
-    float* m[SIR_ADAM_MAX_TENSORS];
-    float* v[SIR_ADAM_MAX_TENSORS];
-    long long n[SIR_ADAM_MAX_TENSORS];
-    int first_block[SIR_ADAM_MAX_TENSORS + 1];
-    int count;
-};
-
-// the EMA shadow of each tensor (sir_adam_step_ex): a kernel argument of its own, so that the launches of sir_adam_step /
-// sir_adam_step_clipped keep the arguments they have
-struct AdamShadow {
-    float* e[SIR_ADAM_MAX_TENSORS];
-};
-
-// One block's 4096-element chunk.  CLIP: the gradient is g * coef (rounded to fp32 first, exactly what an in-place
-// clip_grad_norm_ would have left in memory) before the weight-decay term.
-// DECOUPLED (torch.optim.AdamW): p is first multiplied by decay_f = 1 - lr * weight_decay (formed on the host, rounded to
-// fp32 once; the product is rounded too, as torch's p.mul_ leaves it), then the update runs on the gradient alone:
-// `weight_decay` is not read.  EMA: shadow = fma(d, shadow, (1 - d) * p_new) with the p_new this thread has just formed --
-// one more load and store in the same pass, two roundings.  Both false: the code of the two switches is not there.
-template <bool CLIP, bool DECOUPLED = false, bool EMA = false>
-__device__ __forceinline__ void adam_chunk(const AdamTensors& ts, float lr, float beta1, float beta2, float eps, float weight_decay,
-                                           float bc1, float bc2_sqrt, float coef, float decay_f = 1.0f,
-                                           const AdamShadow* shadow = nullptr, float ema_d = 0.0f) {
-    int ti = 0;
-    while (ti + 1 < ts.count && (int)blockIdx.x >= ts.first_block[ti + 1]) ++ti;
-    const long long base = (long long)((int)blockIdx.x - ts.first_block[ti]) * SIR_ADAM_CHUNK;
-    float* __restrict__ p = ts.p[ti];
-    const float* __restrict__ g = ts.g[ti];
-    float* __restrict__ m = ts.m[ti];
-    float* __restrict__ v = ts.v[ti];
-    const long long n = ts.n[ti];
-    const float step_size = lr / bc1;
-#pragma unroll 4
-    for (int k = 0; k < SIR_ADAM_CHUNK / 256; ++k) {
-        const long long i = base + threadIdx.x + 256 * k;
-        if (i >= n) break;
-        float gi = g[i];
-        if constexpr (CLIP) gi = __fmul_rn(gi, coef);
-        float pi = p[i];
-        if constexpr (DECOUPLED) pi = __fmul_rn(pi, decay_f);
-        else if (weight_decay != 0.0f) gi = fmaf(weight_decay, pi, gi);
-        const float mi = beta1 * m[i] + (1.0f - beta1) * gi;
-        const float vi = beta2 * v[i] + (1.0f - beta2) * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        const float pn = pi - step_size * (mi / denom);
-        p[i] = pn;
-        if constexpr (EMA) {
-            float* __restrict__ e = shadow->e[ti];
-            e[i] = fmaf(ema_d, e[i], __fmul_rn(1.0f - ema_d, pn));
-        }
-    }
-}
-
-static __global__ __launch_bounds__(256) void adam_multi_kernel(AdamTensors ts, float lr, float beta1, float beta2, float eps,
-                                                          float weight_decay, float bc1, float bc2_sqrt) {
-    adam_chunk<false>(ts, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, 1.0f);
-}
-
-// ------------------------------------------------------------------------------------------
-// global gradient norm and clipping (torch.nn.utils.clip_grad_norm_, norm_type 2, error_if_nonfinite=False).
-// Launch 1 leaves one fp32 sum of squares per 4096-element chunk (the block <-> chunk map of adam_multi_kernel) in a slab;
-// whoever needs the norm sums the slab IN INDEX ORDER IN DOUBLE, so every block of every launch forms the same bits:
-// no atomics, no last-block election ("What the profile says", item 4a).
-// Summation tree of one partial: per thread a chain of 16 fmas (elements threadIdx.x + 256 k), then a binary tree of depth 8
-// over the 256 threads in LDS.
-// ------------------------------------------------------------------------------------------
-struct GradTensors {
-    float* g[SIR_ADAM_MAX_TENSORS];
-    long long n[SIR_ADAM_MAX_TENSORS];
-    int first_block[SIR_ADAM_MAX_TENSORS + 1];
-    int count;
-};
-
-static __global__ __launch_bounds__(256) void grad_sumsq_kernel(GradTensors ts, float* __restrict__ partials) {
-    __shared__ float red[256];
-    int ti = 0;
-    while (ti + 1 < ts.count && (int)blockIdx.x >= ts.first_block[ti + 1]) ++ti;
-    const long long base = (long long)((int)blockIdx.x - ts.first_block[ti]) * SIR_ADAM_CHUNK;
-    const float* __restrict__ g = ts.g[ti];
-    const long long n = ts.n[ti];
-    float v[SIR_ADAM_CHUNK / 256];
-#pragma unroll
-    for (int k = 0; k < SIR_ADAM_CHUNK / 256; ++k) {             // all 16 loads in flight; past the end: +0, which adds nothing
-        const long long i = base + threadIdx.x + 256 * k;
-        v[k] = i < n ? g[i] : 0.0f;
-    }
-    float acc = 0.0f;
-#pragma unroll
-    for (int k = 0; k < SIR_ADAM_CHUNK / 256; ++k) acc = fmaf(v[k], v[k], acc);
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) partials[blockIdx.x] = red[0];
-}
-
-// {total_norm, coef} from the slab: thread 0 sums in index order in double, the block gets both through LDS.
-// coef = min(1, max_norm / (total_norm + 1e-6)) in fp32 as torch forms it; a NaN stays a NaN (torch.clamp), an infinite norm
-// gives coef 0 (and 0 * Inf = NaN in the gradient that caused it), as clip_grad_norm_ with error_if_nonfinite=False.
-__device__ __forceinline__ float2 grad_norm_coef(const float* __restrict__ partials, int n_partials, float max_norm) {
-    __shared__ float2 nc;
-    if (threadIdx.x == 0) {
-        double s = 0.0;
-#pragma unroll 8
-        for (int i = 0; i < n_partials; ++i) s += (double)partials[i];
-        const float total = (float)sqrt(s);
-        const float c = max_norm / (total + 1e-6f);
-        nc = make_float2(total, c > 1.0f ? 1.0f : c);
-    }
-    __syncthreads();
-    return nc;
-}
-
-static __global__ __launch_bounds__(256) void grad_norm_finalize_kernel(const float* __restrict__ partials, int n_partials,
-                                                                  float max_norm, float* __restrict__ out2) {
-    const float2 nc = grad_norm_coef(partials, n_partials, max_norm);
-    if (threadIdx.x == 0) { out2[0] = nc.x; out2[1] = nc.y; }
-}
-
-// clip_grad_norm_'s in-place scale: same grid as launch 1, g *= coef (always multiplied, as torch does: coef == 1 leaves the bits)
-static __global__ __launch_bounds__(256) void grad_scale_kernel(GradTensors ts, const float* __restrict__ partials, int n_partials,
-                                                          float max_norm, float* __restrict__ out2) {
-    const float2 nc = grad_norm_coef(partials, n_partials, max_norm);
-    if (blockIdx.x == 0 && threadIdx.x == 0) { out2[0] = nc.x; out2[1] = nc.y; }
-    int ti = 0;
-    while (ti + 1 < ts.count && (int)blockIdx.x >= ts.first_block[ti + 1]) ++ti;
-    const long long base = (long long)((int)blockIdx.x - ts.first_block[ti]) * SIR_ADAM_CHUNK;
-    float* __restrict__ g = ts.g[ti];
-    const long long n = ts.n[ti];
-#pragma unroll 4
-    for (int k = 0; k < SIR_ADAM_CHUNK / 256; ++k) {
-        const long long i = base + threadIdx.x + 256 * k;
-        if (i >= n) break;
-        g[i] = __fmul_rn(g[i], nc.y);
-    }
-}
-
-static __global__ __launch_bounds__(256) void adam_multi_clipped_kernel(AdamTensors ts, float lr, float beta1, float beta2, float eps,
-                                                                  float weight_decay, float bc1, float bc2_sqrt,
-                                                                  const float* __restrict__ partials, int n_partials,
-                                                                  float max_norm, float* __restrict__ out2) {
-    const float2 nc = grad_norm_coef(partials, n_partials, max_norm);
-    if (blockIdx.x == 0 && threadIdx.x == 0) { out2[0] = nc.x; out2[1] = nc.y; }
-    adam_chunk<true>(ts, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, nc.y);
-}
-
-// sir_adam_step_ex with decoupled weight decay and / or the EMA shadow on (with both off the host launches the two kernels
-// above): same grid, same chunk map; CLIP as adam_multi_clipped_kernel, otherwise `partials` / `out2` are not read
-template <bool CLIP, bool DECOUPLED, bool EMA>
-static __global__ __launch_bounds__(256) void adam_multi_ex_kernel(AdamTensors ts, AdamShadow shadow, float lr, float beta1, float beta2,
-                                                             float eps, float weight_decay, float decay_f, float ema_d, float bc1,
-                                                             float bc2_sqrt, const float* __restrict__ partials, int n_partials,
-                                                             float max_norm, float* __restrict__ out2) {
-    float coef = 1.0f;
-    if constexpr (CLIP) {
-        const float2 nc = grad_norm_coef(partials, n_partials, max_norm);
-        if (blockIdx.x == 0 && threadIdx.x == 0) { out2[0] = nc.x; out2[1] = nc.y; }
-        coef = nc.y;
-    }
-    adam_chunk<CLIP, DECOUPLED, EMA>(ts, lr, beta1, beta2, eps, weight_decay, bc1, bc2_sqrt, coef, decay_f, &shadow, ema_d);
 }

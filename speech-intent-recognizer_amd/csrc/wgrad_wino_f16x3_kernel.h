@@ -38,7 +38,7 @@ template <int CIN, int COUT> struct WgwCfg {
     static constexpr int groups = 4 / KPW;                                // workgroups per strip
 };
 // `num_cus`: CUs of the device (sir_handle::num_cus); at most 256 workgroups in all, which is what the slab plan of
-// model_train.hip (64 strips of conv3, 128 of conv2) is sized for
+// train_workspace.h (64 strips of conv3, 128 of conv2) is sized for
 inline int wgrad_wino_strips(int B, int H, int W, int tps, int groups, int num_cus = 256) {
     const long long ntiles = (long long)B * (H / 2) * ((W + 1) / 2), nst = (ntiles + tps - 1) / tps;
     const int cap = (num_cus < 256 ? (num_cus < groups ? groups : num_cus) : 256) / groups;     // one workgroup per CU

@@ -73,6 +73,15 @@ def param_list(mod):
     return [p for _, p in mod.named_parameters()]
 
 
+# parameter name -> (field of sir_model_grads, index in it or None for a scalar field)
+GRAD_FIELDS = {"attention.weight": ("attn_w", None), "attention.bias": ("attn_b", None), "fc.weight": ("fc_w", None), "fc.bias": ("fc_b", None)}
+for _i in range(3):
+    GRAD_FIELDS.update({f"conv{_i + 1}.weight": ("conv_w", _i), f"bn{_i + 1}.weight": ("bn_w", _i), f"bn{_i + 1}.bias": ("bn_b", _i)})
+for _i, _suf in enumerate(ops.GRU_SUFFIXES):
+    GRAD_FIELDS.update({"gru.weight_ih" + _suf: ("gru_w_ih", _i), "gru.weight_hh" + _suf: ("gru_w_hh", _i),
+                        "gru.bias_ih" + _suf: ("gru_b_ih", _i), "gru.bias_hh" + _suf: ("gru_b_hh", _i)})
+
+
 class GradBuffer:
     """One flat gradient buffer with per-parameter views + the matching ``sir_model_grads`` struct."""
 
@@ -84,45 +93,27 @@ class GradBuffer:
         for p in params:
             self.views.append(self.flat[off: off + p.numel()].view_as(p))
             off += p.numel()
-        by_name = {n: v for (n, _), v in zip(mod.named_parameters(), self.views)}
-        g = _native.ModelGrads()
-        for i in range(3):
-            g.conv_w[i] = by_name[f"conv{i + 1}.weight"].data_ptr()
-            g.bn_w[i] = by_name[f"bn{i + 1}.weight"].data_ptr()
-            g.bn_b[i] = by_name[f"bn{i + 1}.bias"].data_ptr()
-        for i, suf in enumerate(ops.GRU_SUFFIXES):
-            g.gru_w_ih[i] = by_name["gru.weight_ih" + suf].data_ptr()
-            g.gru_w_hh[i] = by_name["gru.weight_hh" + suf].data_ptr()
-            g.gru_b_ih[i] = by_name["gru.bias_ih" + suf].data_ptr()
-            g.gru_b_hh[i] = by_name["gru.bias_hh" + suf].data_ptr()
-        g.attn_w = by_name["attention.weight"].data_ptr()
-        g.attn_b = by_name["attention.bias"].data_ptr()
-        g.fc_w = by_name["fc.weight"].data_ptr()
-        g.fc_b = by_name["fc.bias"].data_ptr()
-        self.struct = g
         # (named_parameters order: conv1.weight, bn1.weight, bn1.bias, conv2.weight, ... -- looked up by name, not by position)
-        self._slot = {}
-        for i in range(3):
-            self._slot[f"conv{i + 1}.weight"] = ("conv_w", i)
-            self._slot[f"bn{i + 1}.weight"] = ("bn_w", i)
-            self._slot[f"bn{i + 1}.bias"] = ("bn_b", i)
-        for i, suf in enumerate(ops.GRU_SUFFIXES):
-            self._slot["gru.weight_ih" + suf] = ("gru_w_ih", i)
-            self._slot["gru.weight_hh" + suf] = ("gru_w_hh", i)
-            self._slot["gru.bias_ih" + suf] = ("gru_b_ih", i)
-            self._slot["gru.bias_hh" + suf] = ("gru_b_hh", i)
-        for n, f in (("attention.weight", "attn_w"), ("attention.bias", "attn_b"), ("fc.weight", "fc_w"), ("fc.bias", "fc_b")):
-            self._slot[n] = (f, None)
-        self.names = [n for n, _ in mod.named_parameters()]
+        self.names = names = [n for n, _ in mod.named_parameters()]
+        self.struct = self._fill(_native.ModelGrads(), [True] * len(names))
         self._pruned = {}
         # the conv / BatchNorm gradients come first in named_parameters order; everything behind them (GRU, attention, fc)
         # is final after the first half of the backward
         self.n_cnn = sum(p.numel() for n, p in mod.named_parameters() if n.startswith(("conv", "bn")))
-        names = [n for n, _ in mod.named_parameters()]
         first_other = next(i for i, n in enumerate(names) if not n.startswith(("conv", "bn")))
         assert all(n.startswith(("conv", "bn")) for n in names[:first_other]) and \
             not any(n.startswith(("conv", "bn")) for n in names[first_other:]), "parameter order changed"
 
+    def _fill(self, g, need):
+        """Writes the gradient view of every wanted parameter into its ``sir_model_grads`` field, NULL for the others."""
+        for name, v, n in zip(self.names, self.views, need):
+            field, i = GRAD_FIELDS[name]
+            ptr = v.data_ptr() if n else None
+            if i is None:
+                setattr(g, field, ptr)
+            else:
+                getattr(g, field)[i] = ptr
+        return g
 
     def struct_for(self, need):
         """``sir_model_grads`` with NULL for every parameter whose gradient is not wanted (``need``: one bool per
@@ -135,14 +126,7 @@ class GradBuffer:
         if all(need):
             g = self.struct
         else:
-            g = _native.ModelGrads()
-            for name, v, n in zip(self.names, self.views, need):
-                field, i = self._slot[name]
-                ptr = v.data_ptr() if n else None
-                if i is None:
-                    setattr(g, field, ptr)
-                else:
-                    getattr(g, field)[i] = ptr
+            g = self._fill(_native.ModelGrads(), need)
         cnn = any(n for name, n in zip(self.names, need) if name.startswith(("conv", "bn")))
         self._pruned[key] = (g, cnn)
         return g, cnn

@@ -1,7 +1,7 @@
 """Host restatements of the two counter-based random streams of the HIP path, so that tests can feed the SAME random
 draws to the CPU oracle:
 
-* ``dropout_keep``  -- csrc/train_kernels.h ``dropout_keep(seed, idx, p)``: the keep mask of the inter-layer GRU dropout
+* ``dropout_keep``  -- csrc/train_fwd_kernels.h ``dropout_keep(seed, idx, p)``: the keep mask of the inter-layer GRU dropout
   (reference models/models.py:26-33, ``nn.GRU(dropout=0.5)``), a pure function of (seed, element index);
 * ``gauss_noise``   -- csrc/features.hip ``gauss_pair(seed, b, i >> 1)``: the N(0,1) sample added to sample i of utterance b
   by the fused ``add_noise`` (reference scripts/augment.py:82-96).

@@ -43,7 +43,7 @@ def _model(sd, dropout=0.0):
 
 def _views(m, bsz, t):
     lib = _native.lib()
-    offs = (C.c_size_t * 40)()
+    offs = (C.c_size_t * 40)()       # (slot indices: the list at sir_model_train_workspace_offsets in include/sir_hip.h)
     n = lib.sir_model_train_workspace_offsets(get_featurizer().handle, bsz, t, offs, 40)
     assert n > 0
     ws = m._sir_train["ws"].buf
@@ -61,7 +61,7 @@ def _views(m, bsz, t):
 
 
 def _loss_scale(bsz):
-    """The backward's internal loss scale (csrc/model_train.hip::sir_bwd_loss_scale): 2^8 x batch rounded up to a power of two.  The
+    """The backward's internal loss scale (csrc/train_workspace.h::sir_bwd_loss_scale): 2^8 x batch rounded up to a power of two.  The
     intermediate gradients in the workspace carry it (the parameter gradients do not)."""
     k = 8
     while (1 << (k - 8)) < bsz and k < 24:
@@ -671,7 +671,7 @@ def test_gru_timeout_is_reported_not_swallowed(tmp_path):
 
 @pytest.mark.parametrize("bsz", [256, 21])
 def test_two_stream_backward_is_bit_identical_to_one_stream(sd, bsz):
-    """The backward's weight-gradient launches run on a second, library-owned stream (csrc/model_train.hip); while every
+    """The backward's weight-gradient launches run on a second, library-owned stream (csrc/model_train_bwd.hip); while every
     kernel is timed (sir_profile_enable mode 1) the same call keeps everything on the caller's stream.  No reduction depends on the
     order in which the two streams finish, so every parameter gradient must be BIT-identical between the two forms, run after run (a
     missing fork / join edge or a shared slab shows up here as a difference)."""

@@ -218,6 +218,22 @@ int sir_model_set_weights_version(sir_handle* h, uint64_t version);
 int sir_model_infer(sir_handle* h, const sir_model_weights* w, const float* feats, int batch,
                     int t_frames, float* logits, int64_t* argmax, void* workspace,
                     size_t workspace_bytes, void* stream);
+/* sir_model_infer_ragged replaces the un-padded scoring of scripts/test_tts_samples.py:83-96 -- each file fed at its own
+ * length as [1, 1, 64, T] through model(features), softmax / torch.max / topk left to the caller -- for a whole batch of
+ * mixed-length clips in one call.
+ * feats  : [batch][64][t_frames] f32; row b holds frames[b] feature columns, the columns behind them are never read as data
+ * frames : int32[batch] in DEVICE memory, 8 <= frames[b] <= t_frames
+ * logits : row b = CNNAudioGRU.forward(feats[b:b+1, :, :frames[b]]) in eval(): widths W1 = frames / 2, W2 = W1 / 2,
+ *          S_b = W2 / 2; every convolution takes its right edge at the utterance's own width (the odd column MaxPool2d(2)
+ *          drops is dropped), the GRU runs S_b steps (the reverse direction starts at S_b - 1 from h = 0) and the attention
+ *          softmax runs over t < S_b.  A clip's logits do not depend on its position in the batch or on its neighbours.
+ * argmax, workspace (sir_model_workspace_bytes(h, batch, t_frames, 0) bytes, the size sir_model_infer asks for), stream: as
+ * sir_model_infer; the prepared weights are shared with it (same workspace and shape: nothing is rebuilt, whatever `frames` holds).
+ * A frames[b] outside [8, t_frames] makes row b of logits NaN (argmax 0) and raises the handle's status word: SIR_EINVAL at the
+ * next sir_check_status.  The other rows are unaffected.  Intermediate buffers are written only inside each utterance's widths. */
+int sir_model_infer_ragged(sir_handle* h, const sir_model_weights* w, const float* feats,
+                           const int32_t* frames, int batch, int t_frames, float* logits,
+                           int64_t* argmax, void* workspace, size_t workspace_bytes, void* stream);
 /* The GRU recurrence kernels (forward and backward) exchange hidden-state slices between the workgroups of a
  * cluster through tagged granules in global memory and rely on the cluster being co-resident.  A workgroup that
  * spins past its limit (a partitioned / oversubscribed GPU, a stalled peer) sets a device status word owned by the

@@ -83,6 +83,8 @@ SIGNATURES = {
     "sir_model_set_weights_version": (C.c_int, [C.c_void_p, C.c_uint64]),
     "sir_model_infer": (C.c_int, [C.c_void_p, C.POINTER(ModelWeights), C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "sir_model_infer_ragged": (C.c_int, [C.c_void_p, C.POINTER(ModelWeights), C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "sir_check_status": (C.c_int, [C.c_void_p, C.c_void_p]),
     "sir_pipeline_create": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "sir_pipeline_destroy": (C.c_int, [C.c_void_p]),

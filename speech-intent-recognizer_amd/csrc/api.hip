@@ -296,6 +296,10 @@ static int check_status_impl(sir_handle* h, hipStream_t st, const char* who) {
         sir_set_error("%s: sir_mix_features was given a permutation entry outside [0, batch) (status %u): those rows are zero", who, v);
         return SIR_EINVAL;
     }
+    if (v & 64u) {
+        sir_set_error("%s: sir_model_infer_ragged was given a length outside [8, t_frames] (status %u): those rows' logits are NaN", who, v);
+        return SIR_EINVAL;
+    }
     if (v & 4u) {
         sir_set_error("%s: sir_gather_features was given an index outside its store (status %u): those rows are zero", who, v);
         return SIR_EINVAL;

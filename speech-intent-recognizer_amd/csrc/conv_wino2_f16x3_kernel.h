@@ -157,7 +157,10 @@ __device__ __forceinline__ void w2_write64(unsigned base, uint2 v) {
 // DBG (devtools/kernel_ab/bench_conv.hip only): s_memtime stamps of the first producer and the first consumer wave of workgroup 0
 __device__ long long w2_dbg_stamps[2][32];
 __device__ long long w2_dbg_fine[8][8];              // producer wave 0 of workgroup 0, steps 8..15: loop top, DMA issued, raw patches read, V written, DMA wait over, barrier passed
-template <int CIN, int COUT, int OUT_MODE, int DBG = 0, int PRIO = 3>
+// RAGGED (OUT_MODE 0 / 1 with a compacted column list; un-padded batch inference, model_infer.hip): image b is geo.wtab[b] >> geo.wsh pixel
+// columns wide.  Columns past that width are the image edge: the raw-patch DMA sources them from the zero page (no selects in the
+// transform, and whatever the map holds there is never read), and pooled columns past half that width are not stored.
+template <int CIN, int COUT, int OUT_MODE, int DBG = 0, int PRIO = 3, bool RAGGED = false>
 __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_f16x3_kernel(
     const float* __restrict__ x, const unsigned short* __restrict__ wpb, const float* __restrict__ scale,
     const float* __restrict__ shift, float* __restrict__ out, Wino2Geo geo, float2* __restrict__ stats, const float* __restrict__ zeros) {
@@ -214,7 +217,8 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_f16x3_kernel(
     }
     auto raw_offsets = [&](int g0, int ty0, unsigned (&off)[D_PPW]) {
         // pixel columns P of the flattened batch that may be read: all of it, or (compacted list) the task's own image only
-        const int plo = ctab ? 2 * TW * w2_div(g0, geo.dTW) : 0, phi = ctab ? plo + W : 2 * NG;
+        const int gimg = ctab ? w2_div(g0, geo.dTW) : 0;
+        const int plo = ctab ? 2 * TW * gimg : 0, phi = ctab ? plo + (RAGGED ? min(W, geo.wtab[gimg] >> geo.wsh) : W) : 2 * NG;
 #pragma unroll
         for (int ii = 0; ii < D_PPW; ++ii) {
             const int gy = 2 * ty0 - 1 + pre_lr[ii];
@@ -516,6 +520,8 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_f16x3_kernel(
                     const int gc = g0 + mi;
                     const int img = w2_div(gc, geo.dTW), tx = gc - img * TW;
                     const bool tvalid = gc < (ctab ? (w2_div(g0, geo.dTW) + 1) * TW : NG);
+                    // pooled columns of this image (RAGGED: of its own width; the task's columns all belong to the image of g0)
+                    const int wpi = RAGGED ? min(geo.Wp, geo.wtab[w2_div(g0, geo.dTW)] >> (geo.wsh + 1)) : geo.Wp;
                     if (OUT_MODE <= 1) {
                         float pooled[4];
 #pragma unroll
@@ -527,7 +533,7 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_f16x3_kernel(
                                 for (int b = 0; b < 2; ++b) v = fmaxf(v, fmaf(Y[a][b][e], sc_, sh_));
                             pooled[e] = v;
                         }
-                        if (tvalid && tx < geo.Wp) {
+                        if (tvalid && tx < wpi) {
                             if (OUT_MODE == 0) {
 #pragma unroll
                                 for (int e = 0; e < 4; ++e)
@@ -591,16 +597,19 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_f16x3_kernel(
 // `g`: wino2_geo of the launch (model_shape.h keeps the model's).  The dynamic-LDS opt-in (W2_LDS_BYTES) is the caller's: the library's
 // goes through sir_lds_opt_in at its launch sites (model_infer.hip / model_train_fwd.hip / model_train_bwd.hip).
 // ctab (OUT_MODE 0 / 1 only): compacted task-column list in device memory (Wino2Geo::ctab), at most ncol_max columns
-template <int CIN, int COUT, int OUT_MODE, int DBG = 0, int PRIO = 3>
+// RAGGED: per-image widths wtab[b] >> wsh (see the kernel); needs ctab
+template <int CIN, int COUT, int OUT_MODE, int DBG = 0, int PRIO = 3, bool RAGGED = false>
 static inline hipError_t launch_conv_wino2(hipStream_t st, Wino2Geo g, const float* x, const unsigned short* wpb, const float* scale,
                                            const float* shift, float* out, float2* stats, const float* zeros, int max_wg = 256,
-                                           const int* ctab = nullptr, int ncol_max = 0) {
+                                           const int* ctab = nullptr, int ncol_max = 0, const int* wtab = nullptr, int wsh = 0) {
+    if (RAGGED && (!ctab || !wtab)) return hipErrorInvalidValue;
+    g.wtab = wtab; g.wsh = wsh;
     if (ctab) {
         if (OUT_MODE > 1 || ncol_max < 1) return hipErrorInvalidValue;
         g.ctab = ctab;
         g.NS = g.RBN * ncol_max;                                    // (grid size only: the kernel reads the real count)
     }
     const int nwg = g.NS < max_wg ? g.NS : max_wg;
-    hipLaunchKernelGGL((conv3x3_wino2_f16x3_kernel<CIN, COUT, OUT_MODE, DBG, PRIO>), dim3(nwg), dim3(W2_THREADS), W2_LDS_BYTES, st, x, wpb, scale, shift, out, g, stats, zeros);
+    hipLaunchKernelGGL((conv3x3_wino2_f16x3_kernel<CIN, COUT, OUT_MODE, DBG, PRIO, RAGGED>), dim3(nwg), dim3(W2_THREADS), W2_LDS_BYTES, st, x, wpb, scale, shift, out, g, stats, zeros);
     return hipGetLastError();
 }

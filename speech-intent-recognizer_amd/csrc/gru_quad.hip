@@ -5,7 +5,8 @@
 
 int sir_launch_gru_quad(sir_handle* h, hipStream_t st, bool save, const float* gi, const float* whh0, const float* whh1, const float* bhh0,
                         const float* bhh1, float* y, int B, int S, float* gates, unsigned short* yplanes, const void* wfrag0,
-                        const void* wfrag1, const int* nlive) {
+                        const void* wfrag1, const int* nlive, bool ragged) {
+    if (ragged && (save || !nlive)) { sir_set_error("gru_quad: the ragged form is inference only and needs the step counts"); return SIR_EINVAL; }
     if (S >= 511) { sir_set_error("gru_quad: %d steps exceed the 9-bit step field of the granule tag", S); return SIR_EUNSUPPORTED; }
     if (!wfrag0 || !wfrag1) { sir_set_error("gru_quad: the prepared W_hh fragments are required (sir_prep_whh_quad / train_prep_kernel)"); return SIR_EINVAL; }
     const int clusters = ((B + GQ_NU - 1) / GQ_NU) * 2;
@@ -18,7 +19,7 @@ int sir_launch_gru_quad(sir_handle* h, hipStream_t st, bool save, const float* g
     // more than its one to three stores (71.6 -> 74.7 us).  profiles/r04/ab_gq_roles.txt
     typedef void (*kern_t)(const float*, const float*, const float*, const float*, const float*, float*, int, int, float*, unsigned long long*,
                            unsigned int*, int, unsigned, unsigned short*, const uint4*, const uint4*, const int*);
-    const kern_t kern = save ? gru_quad_kernel<true, true> : gru_quad_kernel<false, false>;
+    const kern_t kern = save ? gru_quad_kernel<true, true> : ragged ? gru_quad_kernel<false, false, true> : gru_quad_kernel<false, false>;
     SIR_TRY(sir_lds_opt_in(h, (const void*)kern, (int)GQ_LDS_BYTES));
     // the launch is chained with the handle's other cluster launches (sir_cluster_enter); leave runs whenever enter succeeded
     SIR_TRY(sir_cluster_enter(h, st));

@@ -99,7 +99,10 @@ static __global__ __launch_bounds__(256) void prep_whh_quad_kernel(const float* 
 // only for the product; the gate arithmetic and everything that touches global memory (gi loads, y / gate / plane stores) in a GATE layout
 // (utterance 4 wave + lane / 16, units 4 (lane & 15) + j): 256 contiguous bytes per 16 lanes instead of 64 separate 16-byte requests per
 // instruction.  The pre-activations cross over through a 13 KB LDS image and one more barrier per step.
-template <bool SAVE, bool ROLES = false>
+// RAGGED (inference, un-padded batch: model_infer.hip): utterance b has nlive[b] <= S steps of its own.  The cluster runs as many steps as
+// its longest utterance; an utterance's h is HELD (selected, never computed from the unwritten gi rows) while t >= nlive[b], so its
+// forward direction ends at nlive[b] - 1, its reverse direction starts there from h = 0, and its y rows t >= nlive[b] are not written.
+template <bool SAVE, bool ROLES = false, bool RAGGED = false>
 __global__ __launch_bounds__(GQ_THREADS) void gru_quad_kernel(
     const float* __restrict__ gi, const float* __restrict__ whh0, const float* __restrict__ whh1,
     const float* __restrict__ bhh0, const float* __restrict__ bhh1, float* __restrict__ y, int B, int S,
@@ -135,6 +138,22 @@ __global__ __launch_bounds__(GQ_THREADS) void gru_quad_kernel(
     const float* __restrict__ bhh = dir ? bhh1 : bhh0;
     unsigned long long* xc = xbuf + (size_t)cluster * (2 * 4 * GQ_NU * GQ_UQ);
 
+    // steps of this cluster (the same in its four workgroups).  RAGGED: the longest of its 16 utterances -- one nlive load per lane and a
+    // 16-lane max, issued ahead of the weight-fragment loads so that its latency hides behind them
+    int sr_ = S;
+    if constexpr (RAGGED) {
+        const int ui = grp * GQ_NU + (lane & 15);
+        sr_ = ui < B ? min(S, nlive[ui]) : 0;
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) sr_ = max(sr_, __shfl_xor(sr_, o));
+        // never fewer than two steps (S allowing): every launch then rewrites BOTH parity blocks of the cluster's granules under its own
+        // epoch, as a padded launch does (the extra steps hold).  A granule of 128 launches ago could otherwise carry the current epoch
+        // and step.  Like the padded path's, the argument covers the clusters a launch runs: a cluster that a run of smaller batches
+        // leaves out keeps its old granules (sir_xbuf_acquire zeroes the buffer when a launch covers more bytes than the previous one).
+        sr_ = max(sr_, min(S, 2));
+    }
+    const int SR = sr_;
+
     // ---- resident weights: A fragments of the three gate tiles, f16x2 planes ----------------------------
     // (loaded straight INTO accumulation registers, where gq_mfma_aw reads them: see its comment; the launcher insists on prepared fragments)
     f16x8 wf[3][8][GQ_NPL];
@@ -158,17 +177,17 @@ __global__ __launch_bounds__(GQ_THREADS) void gru_quad_kernel(
 
     // gate pre-activations of the input side, fetched one step ahead
     float4 gin[3];
-    const int nlb = (!SAVE && nlive && bvalid) ? nlive[b] : S;
+    const int nlb = (!SAVE && nlive && bvalid) ? nlive[b] : (RAGGED ? 0 : S);
     auto load_gi = [&](int t, float4 (&dst)[3]) {
 #pragma unroll
         for (int g = 0; g < 3; ++g) dst[g] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (bvalid) {
-            const float* gp = gi + ((size_t)(t < nlb ? b : B) * S + t) * 1536 + dir * 768 + u0;
+        if (RAGGED ? (bvalid && t < nlb) : bvalid) {
+            const float* gp = gi + ((size_t)(RAGGED || t < nlb ? b : B) * S + t) * 1536 + dir * 768 + u0;
 #pragma unroll
             for (int g = 0; g < 3; ++g) dst[g] = *reinterpret_cast<const float4*>(gp + g * 256);
         }
     };
-    load_gi(dir ? S - 1 : 0, gin);
+    load_gi(dir ? SR - 1 : 0, gin);
     const int frag_off = n * GQ_ROWB + kg * 16;              // this lane's chunk inside a k-step of an h plane row
     // receive role: thread t fetches what thread t of each of the three other quarters stored (same utterance n, same units
     // relative to the quarter): granule order in the buffer is [wave][store 0 | store 1][lane][2], so that every store and
@@ -176,8 +195,8 @@ __global__ __launch_bounds__(GQ_THREADS) void gru_quad_kernel(
     const int xoff = wv * 256 + lane * 2;                    // granule offset of this thread inside a (parity, quarter) block
     bool timed_out = false;
 
-    for (int step = 0; step < S; ++step) {
-        const int t = dir ? (S - 1 - step) : step;
+    for (int step = 0; step < SR; ++step) {
+        const int t = dir ? (SR - 1 - step) : step;
         float4 gcur[3] = {gin[0], gin[1], gin[2]};
         const unsigned char* hb = qlds + (step & 1) * GQ_BUFB;
         unsigned char* hnb = qlds + ((step + 1) & 1) * GQ_BUFB;
@@ -239,6 +258,7 @@ __global__ __launch_bounds__(GQ_THREADS) void gru_quad_kernel(
             z4[j] = gq_sigmoid(gz[j] + hz);
             n4[j] = gq_tanh(gn[j] + r4[j] * hh4[j]);
             hn4[j] = (1.0f - z4[j]) * n4[j] + z4[j] * hp[j];
+            if (RAGGED) hn4[j] = t < nlb ? hn4[j] : hp[j];
         }
         hprev = make_float4(hn4[0], hn4[1], hn4[2], hn4[3]);
 
@@ -267,7 +287,7 @@ __global__ __launch_bounds__(GQ_THREADS) void gru_quad_kernel(
                          :: "v"(gs), "v"(g01), "v"(g23) : "memory");
         }
         // ---- receive the other three quarters' values of this step into the next-parity planes ------------
-        if (step + 1 < S && !(dbg & 4)) {
+        if (step + 1 < SR && !(dbg & 4)) {
             // all 12 granule loads of a poll round are independent (issued back to back, one wait); a round is
             // repeated as a whole until every tag matches -- a per-granule retry serialises the round trips
             unsigned long long v[3][4];
@@ -329,7 +349,7 @@ __global__ __launch_bounds__(GQ_THREADS) void gru_quad_kernel(
         }
         // the stores of this step and the loads of the next one are issued only now: a hand-off costs what sits in the
         // CONSUMER CU's memory queue ahead of the poll (MI355X_MICROARCH.md, handoff-1to1: 0.8 us idle, 2.5-2.9 loaded)
-        if (bvalid) {
+        if (RAGGED ? (bvalid && t < nlb) : bvalid) {
             const size_t yidx = ((size_t)b * S + t) * 512 + dir * 256 + u0;
             *reinterpret_cast<float4*>(y + yidx) = hprev;
             if (yplanes) {
@@ -346,7 +366,7 @@ __global__ __launch_bounds__(GQ_THREADS) void gru_quad_kernel(
             }
         }
 
-        if (step + 1 < S) load_gi(dir ? (S - 2 - step) : step + 1, gin);
+        if (step + 1 < SR) load_gi(dir ? (SR - 2 - step) : step + 1, gin);
         __syncthreads();                                     // next-parity planes complete; this parity's reads are done
     }
 }

@@ -14,6 +14,14 @@
 // rows) and the layer-0 recurrence reads the template's gi row for steps s >= d3.  Columns past the computed ones
 // are left unwritten in a1 / a2 / x0 / xs / gi.  The conv fallback kernels (shapes the Winograd kernel does not cover) keep the
 // full path.
+//
+// Ragged (sir_model_infer_ragged): the UN-PADDED function -- utterance b is computed as if it were alone in a batch of its own width
+// frames[b] (scripts/test_tts_samples.py:83-96 feeds each file at its own length).  The same tables, given rather than scanned: no
+// template utterance, W1 = frames / 2 columns of conv1, ceil((frames / 4) / 4) and ceil((frames / 8) / 4) task columns of conv2 /
+// conv3, S_b = frames / 8 projection rows and GRU steps.  Every stage takes its right edge at the utterance's own width: conv1 reads
+// frame columns >= frames[b] as zeros, the Winograd kernels source map columns past the width from the zero page and store no pooled
+// column past half of it, both input projections run over the row list, the recurrences hold h while t >= S_b and the attention
+// softmax runs over t < S_b.  On the conv fallback kernels the maps are masked to zero past the width by a pass of their own.
 #include "f16x3_kernels.h"
 #include "conv_fwd.h"
 #include "gru_frag_prep.h"
@@ -29,7 +37,7 @@ enum WsBuf {
     WS_Y1,       // GRU layer 1 output [B][S][512]
     WS_CTX,      // attention-pooled context [B][512]
     WS_PAD,      // pad-skip tables (int): E0[B], conv1 columns d1[B + 1], GRU steps d3[B + 1], conv2 / conv3 task-column lists,
-                 // layer-0 projection row list
+                 // layer-0 projection row list.  Ragged: validated frames[B] in E0's place, d1 = W1, d3 = S_b, the tight lists
     WS_XZ,       // all-zero feature row [64][T] of the template utterance (zeroed by pad_tables_kernel on every call)
     WS_BN,       // folded BN: scale[224] then shift[224] (channels of bn1|bn2|bn3)
     WS_WHT,      // W_hh fragments of the recurrence kernel, [4 (layer, direction)][GRU_FRAG_BYTES]
@@ -110,22 +118,14 @@ static __global__ __launch_bounds__(256) void pad_extent_kernel(const float* __r
     if (threadIdx.x == 0) e0[blockIdx.x] = max(max(wl[0], wl[1]), max(wl[2], wl[3])) + 1;
 }
 
-// one workgroup: demanded columns per utterance from E0 (see the head of this file; utterance B = the template, full width),
-// prefix sums over the batch -> compacted task-column lists of conv2 / conv3 (Wino2Geo::ctab), the layer-0 projection's row list
-// (u * S + s for s < d3[u], ascending; the template's S rows last), and the template's zero features
-static __global__ __launch_bounds__(1024) void pad_tables_kernel(const int* __restrict__ e0, Dims d, int* __restrict__ d1o, int* __restrict__ d3o,
-                                                                 int* __restrict__ tab2, int* __restrict__ tab3, int* __restrict__ prow,
-                                                                 float* __restrict__ xz) {
+// prefix sums over `nu` utterances of what `need(u, c1, c3, k2, k3)` demands -> conv1 columns d1o, GRU steps d3o, the compacted
+// task-column lists of conv2 / conv3 (Wino2Geo::ctab) and the projection's row list (u * S + s for s < c3, ascending).  One workgroup
+// of 1024 threads.
+template <typename Need>
+__device__ __forceinline__ void pad_tables_emit(const Dims& d, int nu, Need need, int* __restrict__ d1o, int* __restrict__ d3o,
+                                                int* __restrict__ tab2, int* __restrict__ tab3, int* __restrict__ prow) {
     const int tid = threadIdx.x;
-    for (int i = tid; i < 64 * d.T; i += 1024) xz[i] = 0.0f;
-    const int nu = d.B + 1, per = (nu + 1023) / 1024, u0 = min(nu, tid * per), u1 = min(nu, u0 + per);
-    auto need = [&](int u, int& c1, int& c3, int& k2, int& k3) {
-        if (u == d.B) { c1 = d.wp1; c3 = d.S; k2 = d.k2max; k3 = d.k3max; return; }
-        c3 = min(d.S, (e0[u] + 14) / 8);
-        const int c2 = min(d.wp2, 2 * c3 + 1);
-        c1 = min(d.wp1, 2 * c2 + 1);
-        k2 = (c2 + 3) / 4; k3 = (c3 + 3) / 4;
-    };
+    const int per = (nu + 1023) / 1024, u0 = min(nu, tid * per), u1 = min(nu, u0 + per);
     int s2 = 0, s3 = 0, sr = 0, c1, c3, k2, k3;
     for (int u = u0; u < u1; ++u) { need(u, c1, c3, k2, k3); s2 += k2; s3 += k3; sr += c3; }
     __shared__ int p2[1024], p3[1024], pr[1024];
@@ -147,6 +147,55 @@ static __global__ __launch_bounds__(1024) void pad_tables_kernel(const int* __re
         o2 += k2; o3 += k3; orw += c3;
     }
     if (tid == 1023) { tab2[0] = p2[1023]; tab3[0] = p3[1023]; prow[0] = pr[1023]; }
+}
+
+// one workgroup: demanded columns per utterance from E0 (see the head of this file; utterance B = the template, full width),
+// prefix sums over the batch -> compacted task-column lists of conv2 / conv3 (Wino2Geo::ctab), the layer-0 projection's row list
+// (u * S + s for s < d3[u], ascending; the template's S rows last), and the template's zero features
+static __global__ __launch_bounds__(1024) void pad_tables_kernel(const int* __restrict__ e0, Dims d, int* __restrict__ d1o, int* __restrict__ d3o,
+                                                                 int* __restrict__ tab2, int* __restrict__ tab3, int* __restrict__ prow,
+                                                                 float* __restrict__ xz) {
+    const int tid = threadIdx.x;
+    for (int i = tid; i < 64 * d.T; i += 1024) xz[i] = 0.0f;
+    auto need = [&](int u, int& c1, int& c3, int& k2, int& k3) {
+        if (u == d.B) { c1 = d.wp1; c3 = d.S; k2 = d.k2max; k3 = d.k3max; return; }
+        c3 = min(d.S, (e0[u] + 14) / 8);
+        const int c2 = min(d.wp2, 2 * c3 + 1);
+        c1 = min(d.wp1, 2 * c2 + 1);
+        k2 = (c2 + 3) / 4; k3 = (c3 + 3) / 4;
+    };
+    pad_tables_emit(d, d.B + 1, need, d1o, d3o, tab2, tab3, prow);
+}
+
+// Ragged: the same tables from the GIVEN lengths, B utterances, no template.  fw[b] = frames[b], or 0 where it is outside [8, T]:
+// such an utterance gets no column, no row and no step (its logits become NaN in attention_pool_ragged_kernel) and raises bit 6 of
+// the handle's status word.  Widths follow from fw alone: W1 = fw / 2 (conv1 out), W2 = fw / 4 (conv2 out), S_b = fw / 8.
+static __global__ __launch_bounds__(1024) void ragged_tables_kernel(const int* __restrict__ frames, Dims d, int* __restrict__ fw, int* __restrict__ d1o,
+                                                                    int* __restrict__ d3o, int* __restrict__ tab2, int* __restrict__ tab3,
+                                                                    int* __restrict__ prow, unsigned int* __restrict__ status) {
+    bool bad = false;
+    for (int u = threadIdx.x; u < d.B; u += 1024) {
+        const int f0 = frames[u], f = f0 >= 8 && f0 <= d.T ? f0 : 0;
+        fw[u] = f;
+        bad |= f == 0;
+    }
+    if (bad) __hip_atomic_fetch_or(status, 64u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();                                          // fw is read back below by other threads of this (one) workgroup
+    auto need = [&](int u, int& c1, int& c3, int& k2, int& k3) {
+        const int f = fw[u];
+        c1 = f >> 1; c3 = f >> 3;
+        k2 = ((f >> 2) + 3) / 4; k3 = (c3 + 3) / 4;
+    };
+    pad_tables_emit(d, d.B, need, d1o, d3o, tab2, tab3, prow);
+}
+
+// Ragged on the conv fallback kernels (they run at full width): map columns >= fw[b] >> sh of image b become zeros -- the image edge
+// the next conv reads, and no stale workspace bits behind it.  a: NHWC [B][H][W][C], grid (H, B).
+static __global__ __launch_bounds__(256) void ragged_mask_kernel(float* __restrict__ a, const int* __restrict__ fw, int sh, int H, int W, int C) {
+    const int b = blockIdx.y, r = blockIdx.x, w0 = min(W, fw[b] >> sh);
+    float4* row = reinterpret_cast<float4*>(a + (((size_t)b * H + r) * W + w0) * C);
+    const int n4 = (W - w0) * (C / 4);
+    for (int i = threadIdx.x; i < n4; i += 256) row[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 }
 
 }  // namespace
@@ -171,20 +220,22 @@ extern "C" int sir_model_workspace_offsets(const sir_handle* h, int batch, int t
     return WS_COUNT;
 }
 
-extern "C" int sir_model_infer(sir_handle* h, const sir_model_weights* w, const float* feats, int batch, int t_frames,
-                               float* logits, int64_t* argmax, void* workspace, size_t workspace_bytes, void* stream_) {
-    if (!h || !w || !feats || !logits || !workspace) { sir_set_error("sir_model_infer: NULL argument"); return SIR_EINVAL; }
+// frames == nullptr: the padded function with the pad skip (sir_model_infer); else the ragged one (head of this file)
+static int model_infer_impl(const char* who, sir_handle* h, const sir_model_weights* w, const float* feats, const int32_t* frames, int batch,
+                            int t_frames, float* logits, int64_t* argmax, void* workspace, size_t workspace_bytes, void* stream_) {
+    if (!h || !w || !feats || !logits || !workspace) { sir_set_error("%s: NULL argument", who); return SIR_EINVAL; }
     Dims d;
     if (!make_dims(batch, t_frames, &d)) {
-        sir_set_error("sir_model_infer: unsupported shape batch=%d t_frames=%d (need t_frames >= 8)", batch, t_frames);
+        sir_set_error("%s: unsupported shape batch=%d t_frames=%d (need t_frames >= 8)", who, batch, t_frames);
         return SIR_EINVAL;
     }
-    if (h->cfg.n_mels != 64) { sir_set_error("sir_model_infer: the model is wired for 64 mels (models.py:23)"); return SIR_EUNSUPPORTED; }
-    if (w->num_classes < 1 || w->num_classes > 64) { sir_set_error("sir_model_infer: num_classes=%d", w->num_classes); return SIR_EINVAL; }
+    if (h->cfg.n_mels != 64) { sir_set_error("%s: the model is wired for 64 mels (models.py:23)", who); return SIR_EUNSUPPORTED; }
+    if (w->num_classes < 1 || w->num_classes > 64) { sir_set_error("%s: num_classes=%d", who, w->num_classes); return SIR_EINVAL; }
     size_t off[WS_COUNT];
     const size_t need = ws_layout(d, off);
-    if (workspace_bytes < need) { sir_set_error("sir_model_infer: workspace %zu < %zu", workspace_bytes, need); return SIR_ENOMEM; }
-    if (((uintptr_t)workspace & 255) != 0) { sir_set_error("sir_model_infer: workspace must be 256-byte aligned"); return SIR_EINVAL; }
+    if (workspace_bytes < need) { sir_set_error("%s: workspace %zu < %zu", who, workspace_bytes, need); return SIR_ENOMEM; }
+    if (((uintptr_t)workspace & 255) != 0) { sir_set_error("%s: workspace must be 256-byte aligned", who); return SIR_EINVAL; }
+    const bool ragged = frames != nullptr;
     hipStream_t st = (hipStream_t)stream_;
     char* ws = (char*)workspace;
     float* a1 = (float*)(ws + off[WS_A1]);
@@ -214,6 +265,8 @@ extern "C" int sir_model_infer(sir_handle* h, const sir_model_weights* w, const 
     const SirConvPlan cp = sir_conv_plan(&d, true);             // (true: the template utterance)
     const bool w2 = cp.fwd_wino;
     const int BT = w2 ? B + 1 : B;                                // utterances through conv1-3 and the layer-0 projection
+    // (ragged: no template utterance is computed, but the plan, the plane stride of xs and the table offsets stay those of the
+    // padded call -- and so does the prepared-weight key: a ragged and a padded call may alternate on one workspace)
 
     // ---- weight preparation -------------------------------------------------------------
     // skipped when the caller vouches (sir_model_set_weights_version) that the weights are the ones prepared
@@ -249,6 +302,14 @@ extern "C" int sir_model_infer(sir_handle* h, const sir_model_weights* w, const 
     // ---- CNN stack: conv + folded BN + ReLU + 2x2 max-pool per launch ------------------------------
     {
         SirProfScope prof(h, SIR_K_CONV1, st);
+        if (ragged) {                                             // tables from the given lengths; conv1 at each utterance's own width
+            hipLaunchKernelGGL(ragged_tables_kernel, dim3(1), dim3(1024), 0, st, (const int*)frames, d, ptab + pt.e0, ptab + pt.d1, ptab + pt.d3,
+                               ptab + pt.tab2, ptab + pt.tab3, ptab + pt.rows, h->status);
+            hipLaunchKernelGGL(conv1_mfma_bn_relu_pool_ragged_kernel, dim3((d.wp1 + C1_PCOLS - 1) / C1_PCOLS, 1, B), dim3(256), 0, st, feats,
+                               w->conv_w[0], bns, bnt, a1, 64, d.T, 32, d.wp1, (const int*)(ptab + pt.d1), (const int*)(ptab + pt.e0));
+            // (fallback path only: the mask of conv1's map is counted with conv1, that of conv2's map with conv2 in sir_profile_*)
+            if (!w2) hipLaunchKernelGGL(ragged_mask_kernel, dim3(32, B), dim3(256), 0, st, a1, (const int*)(ptab + pt.e0), 1, 32, d.wp1, 32);
+        } else {
         if (w2) {                                                 // pad-skip extents and tables (two small launches, counted with conv1)
             hipLaunchKernelGGL(pad_extent_kernel, dim3(B), dim3(256), 0, st, feats, d.T, ptab + pt.e0);
             hipLaunchKernelGGL(pad_tables_kernel, dim3(1), dim3(1024), 0, st, (const int*)(ptab + pt.e0), d, ptab + pt.d1, ptab + pt.d3,
@@ -256,15 +317,25 @@ extern "C" int sir_model_infer(sir_handle* h, const sir_model_weights* w, const 
         }
         hipLaunchKernelGGL(conv1_mfma_bn_relu_pool_kernel, dim3((d.wp1 + C1_PCOLS - 1) / C1_PCOLS, 1, BT), dim3(256), 0, st, feats,
                            w->conv_w[0], bns, bnt, a1, 64, d.T, 32, d.wp1, (const float*)xz, B, w2 ? (const int*)(ptab + pt.d1) : (const int*)nullptr);
+        }
     }
     {
         SirProfScope prof(h, SIR_K_CONV2, st);
+        if (ragged) {
+            SIR_TRY((conv_fwd<32, 64, 0, true>(h, st, w2, cp.geo2, B, a1, wcb2, nullptr, bns + 32, bnt + 32, a2, nullptr, ptab + pt.tab2, (B + 1) * d.k2max,
+                                               ptab + pt.e0, 1)));
+            if (!w2) hipLaunchKernelGGL(ragged_mask_kernel, dim3(16, B), dim3(256), 0, st, a2, (const int*)(ptab + pt.e0), 2, 16, d.wp2, 64);
+        } else
         SIR_TRY((conv_fwd<32, 64, 0>(h, st, w2, cp.geo2, BT, a1, wcb2, nullptr, bns + 32, bnt + 32, a2, nullptr, ptab + pt.tab2, (B + 1) * d.k2max)));
     }
     {
         // conv3 stores straight into the GRU input layout [B][S][c*8+h] (models.py:55-57) and writes the f16x2 planes of
         // the first input projection's A operand beside it
         SirProfScope prof(h, SIR_K_CONV3, st);
+        if (ragged)
+            SIR_TRY((conv_fwd<64, 128, 1, true>(h, st, w2, cp.geo3, B, a2, wcb3, wcb3d, bns + 96, bnt + 96, x0, (float2*)xs, ptab + pt.tab3, (B + 1) * d.k3max,
+                                                ptab + pt.e0, 2)));
+        else
         SIR_TRY((conv_fwd<64, 128, 1>(h, st, w2, cp.geo3, BT, a2, wcb3, wcb3d, bns + 96, bnt + 96, x0, (float2*)xs, ptab + pt.tab3, (B + 1) * d.k3max)));
     }
     SIR_KCHECK();
@@ -275,7 +346,7 @@ extern "C" int sir_model_infer(sir_handle* h, const sir_model_weights* w, const 
         // pad skip: only the rows the recurrence reads (the row list of pad_tables_kernel: steps s < d3 of every utterance and the
         // template's S rows), on a tile the compacted count fills the chip with; the other gi rows are left unwritten
         SirProfScope prof(h, SIR_K_GEMM_IH0, st);
-        if (w2)
+        if (w2 || ragged)                                         // (ragged: the rows s < S_b of every utterance, on either conv path)
             SIR_TRY(launch_gemm_nt_f16x3_gather(h, st, (const unsigned short*)xs, (const unsigned short*)wsl0,
                                                     (const unsigned short*)(wsl0 + (size_t)2 * 768 * 1024), w->gru_b_ih[0], w->gru_b_ih[1], gi, 1536,
                                                     (const int*)(ptab + pt.rows), BT * S, 768, 1024));
@@ -287,26 +358,48 @@ extern "C" int sir_model_infer(sir_handle* h, const sir_model_weights* w, const 
         SirProfScope prof(h, SIR_K_GRU0, st);
         // layer 0 also writes the f16x2 planes of ITS output: the A operand of the layer-1 projection
         SIR_TRY(sir_launch_gru_quad(h, st, false, gi, w->gru_w_hh[0], w->gru_w_hh[1], w->gru_b_hh[0], w->gru_b_hh[1], y0, B, S, nullptr,
-                                    xs, wht, (unsigned char*)wht + GRU_FRAG_BYTES, w2 ? (const int*)(ptab + pt.d3) : (const int*)nullptr));
+                                    xs, wht, (unsigned char*)wht + GRU_FRAG_BYTES, w2 || ragged ? (const int*)(ptab + pt.d3) : (const int*)nullptr, ragged));
     }
     {
         SirProfScope prof(h, SIR_K_GEMM_IH1, st);
+        if (ragged)                                               // the same row list: layer 0 wrote y0's planes for exactly these rows
+            SIR_TRY(launch_gemm_nt_f16x3_gather(h, st, (const unsigned short*)xs, (const unsigned short*)wsl1,
+                                                    (const unsigned short*)(wsl1 + (size_t)2 * 768 * 512), w->gru_b_ih[2], w->gru_b_ih[3], gi, 1536,
+                                                    (const int*)(ptab + pt.rows), M, 768, 512));
+        else
         SIR_TRY(launch_gemm_nt_f16x3(h, st, (const unsigned short*)xs, (const unsigned short*)wsl1,
                                          (const unsigned short*)(wsl1 + (size_t)2 * 768 * 512), w->gru_b_ih[2], w->gru_b_ih[3], gi, 1536, M, 768, 512));
     }
     {
         SirProfScope prof(h, SIR_K_GRU1, st);
         SIR_TRY(sir_launch_gru_quad(h, st, false, gi, w->gru_w_hh[2], w->gru_w_hh[3], w->gru_b_hh[2], w->gru_b_hh[3], y1, B, S, nullptr,
-                                    nullptr, (unsigned char*)wht + 2 * GRU_FRAG_BYTES, (unsigned char*)wht + 3 * GRU_FRAG_BYTES));
+                                    nullptr, (unsigned char*)wht + 2 * GRU_FRAG_BYTES, (unsigned char*)wht + 3 * GRU_FRAG_BYTES,
+                                    ragged ? (const int*)(ptab + pt.d3) : (const int*)nullptr, ragged));
     }
     SIR_KCHECK();
 
     // ---- attention pooling + classifier head ------------------------------------------------
     {
         SirProfScope prof(h, SIR_K_ATTN, st);
+        if (ragged)
+            hipLaunchKernelGGL(attention_pool_ragged_kernel, dim3(B), dim3(256), 0, st, y1, w->attn_w, w->attn_b, ctx, S, w->fc_w, w->fc_b,
+                               w->num_classes, logits, (long long*)argmax, (const int*)(ptab + pt.d3));
+        else
         hipLaunchKernelGGL(attention_pool_kernel, dim3(B), dim3(256), 0, st, y1, w->attn_w, w->attn_b, ctx, S, w->fc_w, w->fc_b,
                            w->num_classes, logits, (long long*)argmax);
     }
     SIR_KCHECK();
     return SIR_OK;
+}
+
+extern "C" int sir_model_infer(sir_handle* h, const sir_model_weights* w, const float* feats, int batch, int t_frames,
+                               float* logits, int64_t* argmax, void* workspace, size_t workspace_bytes, void* stream_) {
+    return model_infer_impl("sir_model_infer", h, w, feats, nullptr, batch, t_frames, logits, argmax, workspace, workspace_bytes, stream_);
+}
+
+extern "C" int sir_model_infer_ragged(sir_handle* h, const sir_model_weights* w, const float* feats, const int32_t* frames, int batch,
+                                      int t_frames, float* logits, int64_t* argmax, void* workspace, size_t workspace_bytes,
+                                      void* stream_) {
+    if (!frames) { sir_set_error("sir_model_infer_ragged: NULL frames"); return SIR_EINVAL; }
+    return model_infer_impl("sir_model_infer_ragged", h, w, feats, frames, batch, t_frames, logits, argmax, workspace, workspace_bytes, stream_);
 }

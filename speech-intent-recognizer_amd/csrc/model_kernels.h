@@ -54,11 +54,14 @@ constexpr int C1_TR = 2 * C1_PROWS + 2, C1_TC = 2 * C1_PCOLS + 2;
 // Wave w = pooled row w of the 4 x 32 pooled-pixel block; per half (32 conv columns) two accumulators (the two conv rows
 // of the pooled row); 2x2 max = max of the two accumulators and of lanes j, j ^ 1.  Even lanes then store channel groups
 // 0, 1 and odd lanes groups 2, 3 of pooled pixel j / 2 (two float4 stores per lane).
+// RAGGED (un-padded batch inference, model_infer.hip): frame columns >= xlim[b] of image b are the image edge -- read as zeros,
+// whatever bits they hold -- and lim[b] = xlim[b] / 2 pooled columns are stored.
 #ifndef SIR_NO_STANDALONE_KERNELS
-static __global__ __launch_bounds__(256, 4) void conv1_mfma_bn_relu_pool_kernel(
+template <bool RAGGED>
+__device__ __forceinline__ void conv1_mfma_bn_relu_pool_body(
     const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ scale,
     const float* __restrict__ shift, float* __restrict__ out, int H, int W, int Hp, int Wp,
-    const float* __restrict__ xtail, int nx, const int* __restrict__ lim) {
+    const float* __restrict__ xtail, int nx, const int* __restrict__ lim, const int* __restrict__ xlim) {
     // One block walks ALL row tiles of its column strip (grid = (column strips, 1, B)): weights / scale / shift are
     // loaded once, and the next tile's pixels are fetched into registers while the matrix pipe works on the current one
     // (one short block per tile spent most of its life waiting for its own loads: 50 us for 17 us of MFMA work).
@@ -70,6 +73,7 @@ static __global__ __launch_bounds__(256, 4) void conv1_mfma_bn_relu_pool_kernel(
     if (px0 >= wlim) return;                                 // (whole block, before any barrier)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, j = lane & 31, kh = lane >> 5;
     const float* xb = b < nx ? x + (size_t)b * H * W : xtail;
+    const int Wx = RAGGED ? min(W, xlim[b]) : W;             // columns of this image that hold data
     constexpr int NPRE = (C1_TR * C1_TC + 255) / 256;
     float pre[NPRE];
     auto fetch = [&](int py0) {
@@ -77,7 +81,7 @@ static __global__ __launch_bounds__(256, 4) void conv1_mfma_bn_relu_pool_kernel(
         for (int q = 0; q < NPRE; ++q) {
             const int i = tid + 256 * q, ty = i / C1_TC, tx = i - ty * C1_TC;
             const int gy = 2 * py0 - 1 + ty, gx = 2 * px0 - 1 + tx;
-            pre[q] = (i < C1_TR * C1_TC && gy >= 0 && gy < H && gx >= 0 && gx < W) ? xb[(size_t)gy * W + gx] : 0.0f;
+            pre[q] = (i < C1_TR * C1_TC && gy >= 0 && gy < H && gx >= 0 && gx < Wx) ? xb[(size_t)gy * W + gx] : 0.0f;
         }
     };
     fetch(0);
@@ -148,6 +152,18 @@ static __global__ __launch_bounds__(256, 4) void conv1_mfma_bn_relu_pool_kernel(
         }
     }
 }
+static __global__ __launch_bounds__(256, 4) void conv1_mfma_bn_relu_pool_kernel(
+    const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ scale,
+    const float* __restrict__ shift, float* __restrict__ out, int H, int W, int Hp, int Wp,
+    const float* __restrict__ xtail, int nx, const int* __restrict__ lim) {
+    conv1_mfma_bn_relu_pool_body<false>(x, w, scale, shift, out, H, W, Hp, Wp, xtail, nx, lim, nullptr);
+}
+static __global__ __launch_bounds__(256, 4) void conv1_mfma_bn_relu_pool_ragged_kernel(
+    const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ scale,
+    const float* __restrict__ shift, float* __restrict__ out, int H, int W, int Hp, int Wp,
+    const int* __restrict__ lim, const int* __restrict__ xlim) {
+    conv1_mfma_bn_relu_pool_body<true>(x, w, scale, shift, out, H, W, Hp, Wp, nullptr, (int)gridDim.z, lim, xlim);
+}
 #endif
 
 // ------------------------------------------------------------------------------------------
@@ -203,12 +219,16 @@ __device__ __forceinline__ void gru_fma4(float (&acc)[NB], const float4 w, const
 // ------------------------------------------------------------------------------------------
 // (ATT_MAX_S: model_shape.h)
 
+// RAGGED (un-padded batch inference): utterance b has slen[b] <= SR steps in rows of stride SR; the softmax and the context sum run
+// over those alone.  slen[b] = 0 marks an utterance whose length was rejected: its logits are NaN.
 #ifndef SIR_NO_STANDALONE_KERNELS
-static __global__ __launch_bounds__(256) void attention_pool_kernel(const float* __restrict__ y, const float* __restrict__ aw,
-                                                             const float* __restrict__ ab, float* __restrict__ ctx,
-                                                             int S, const float* __restrict__ fcw,
-                                                             const float* __restrict__ fcb, int C,
-                                                             float* __restrict__ logits, long long* __restrict__ amax) {
+template <bool RAGGED>
+__device__ __forceinline__ void attention_pool_body(const float* __restrict__ y, const float* __restrict__ aw,
+                                                    const float* __restrict__ ab, float* __restrict__ ctx,
+                                                    int SR, const float* __restrict__ fcw,
+                                                    const float* __restrict__ fcb, int C,
+                                                    float* __restrict__ logits, long long* __restrict__ amax,
+                                                    const int* __restrict__ slen) {
     // fused tail (models.py:63-67 + evaluate.py:83): attention pooling, the 512 -> C classifier and the
     // arg-max of one utterance per workgroup.  The head is 31.7 kFLOP per utterance; as a separate
     // 128x64-tile MFMA GEMM it occupied 2 workgroups and cost 34 us per batch, fused here it is free.
@@ -216,7 +236,15 @@ static __global__ __launch_bounds__(256) void attention_pool_kernel(const float*
     __shared__ float cs[512];
     __shared__ float lg[64];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const float* yb = y + (size_t)b * S * 512;
+    const int S = RAGGED ? min(SR, slen[b]) : SR;
+    if (RAGGED && S < 1) {                                    // (whole block, before any barrier)
+        const float qnan = __builtin_nanf("");
+        for (int c = tid; c < 512; c += 256) ctx[(size_t)b * 512 + c] = qnan;
+        if (logits && tid < C) logits[(size_t)b * C + tid] = qnan;
+        if (logits && amax && tid == 0) amax[b] = 0;
+        return;
+    }
+    const float* yb = y + (size_t)b * SR * 512;
     float a[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) a[i] = aw[lane + 64 * i];
@@ -287,6 +315,21 @@ static __global__ __launch_bounds__(256) void attention_pool_kernel(const float*
             if (lg[c] > best) { best = lg[c]; bi = c; }      // first maximum, as torch.argmax
         amax[b] = bi;
     }
+}
+static __global__ __launch_bounds__(256) void attention_pool_kernel(const float* __restrict__ y, const float* __restrict__ aw,
+                                                             const float* __restrict__ ab, float* __restrict__ ctx,
+                                                             int S, const float* __restrict__ fcw,
+                                                             const float* __restrict__ fcb, int C,
+                                                             float* __restrict__ logits, long long* __restrict__ amax) {
+    attention_pool_body<false>(y, aw, ab, ctx, S, fcw, fcb, C, logits, amax, nullptr);
+}
+static __global__ __launch_bounds__(256) void attention_pool_ragged_kernel(const float* __restrict__ y, const float* __restrict__ aw,
+                                                             const float* __restrict__ ab, float* __restrict__ ctx,
+                                                             int S, const float* __restrict__ fcw,
+                                                             const float* __restrict__ fcb, int C,
+                                                             float* __restrict__ logits, long long* __restrict__ amax,
+                                                             const int* __restrict__ slen) {
+    attention_pool_body<true>(y, aw, ab, ctx, S, fcw, fcb, C, logits, amax, slen);
 }
 #endif
 

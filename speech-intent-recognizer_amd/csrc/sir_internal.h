@@ -221,11 +221,12 @@ int sir_features_launch(sir_handle* h, const void* wave, int wave_dtype, int64_t
                         hipStream_t stream);
 
 // GRU recurrences (gru_quad.hip: forward and BPTT, clusters of four workgroups on the matrix cores).  Both write h->status if an
-// exchange spin times out.  nlive (forward, optional): per-utterance step count past which gi rows come from utterance B (gru_quad_kernel.h)
+// exchange spin times out.  nlive (forward, optional): per-utterance step count past which gi rows come from utterance B, or -- `ragged` --
+// past which the utterance's h is held and nothing of it is read or written (gru_quad_kernel.h)
 int sir_launch_gru_quad(sir_handle* h, hipStream_t st, bool save, const float* gi, const float* whh0, const float* whh1, const float* bhh0,
                         const float* bhh1, float* y, int B, int S, float* gates,
                         unsigned short* yplanes = nullptr, const void* wfrag0 = nullptr, const void* wfrag1 = nullptr,
-                        const int* nlive = nullptr);
+                        const int* nlive = nullptr, bool ragged = false);
 void sir_prep_whh_quad(hipStream_t st, const float* whh, void* frag);     // -> GRU_FRAG_BYTES (gru_frag_prep.h)
 int sir_launch_gru_bwd_quad(sir_handle* h, hipStream_t st, const float* dy, const float* gates, const float* y, const float* whh0,
                             const float* whh1, float* dgi, float* dgh, float* bsum_i, float* bsum_h, int B, int S,

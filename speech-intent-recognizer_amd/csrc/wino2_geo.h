@@ -32,11 +32,14 @@ struct Wino2Geo {
     // tx0 a multiple of 4) of task column k, k < n; NS = RBN * n.  A task then holds 4 tile columns of ONE image, its halo pixels
     // come from that image (or the zero page outside it), and tile columns past the image's TW are neither computed nor stored.
     const int* ctab;
+    // un-padded batch inference (the kernel's RAGGED form; needs ctab): image b is wtab[b] >> wsh pixel columns wide.  nullptr otherwise.
+    const int* wtab;
+    int wsh;
 };
 // false: shape outside what the kernel covers (whole 8-tile-row blocks, 32-bit element offsets) -- the caller keeps the
 // first-generation / direct kernel for it
 static inline bool wino2_geo(int B, int H, int W, int cmax, Wino2Geo* g) {
-    g->B = B; g->H = H; g->W = W; g->TW = (W + 1) / 2; g->NG = B * g->TW; g->RBN = H / 16; g->ctab = nullptr;
+    g->B = B; g->H = H; g->W = W; g->TW = (W + 1) / 2; g->NG = B * g->TW; g->RBN = H / 16; g->ctab = nullptr; g->wtab = nullptr; g->wsh = 0;
     g->NS = g->RBN * ((g->NG + 3) / 4); g->Hp = H / 2; g->Wp = W / 2;
     g->dTW = w2_div_make((unsigned)g->TW); g->d2TW = w2_div_make(2u * (unsigned)g->TW); g->dRBN = w2_div_make((unsigned)(g->RBN > 0 ? g->RBN : 1));
     return H % 16 == 0 && W >= 1 && B >= 1 && (size_t)B * H * W * cmax < ((size_t)1 << 31) && (size_t)g->NG * 2 < ((size_t)1 << 30);

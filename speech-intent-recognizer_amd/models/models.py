@@ -61,8 +61,12 @@ class CNNAudioGRU(nn.Module):
                 getattr(self, name).eval()
         return self
 
-    def forward(self, x):
+    def forward(self, x, lengths=None):
         """x: [B, 64, T] or [B, 1, 64, T] float32 on the GPU -> logits [B, num_classes].
+
+        ``lengths`` (int tensor or list, frames per clip; inference only): the un-padded function -- row b is what the model
+        gives ``x[b:b+1, ..., :lengths[b]]`` on its own (scripts/test_tts_samples.py feeds each file that way), for a whole
+        batch of mixed-length clips in one launch sequence.
 
         ``self.training and torch.is_grad_enabled()`` selects the differentiable path, as before; ``model.eval()`` keeps
         calling ``sir_model_infer``.  Inside the differentiable path the sub-modules are consulted the way torch consults
@@ -70,14 +74,17 @@ class CNNAudioGRU(nn.Module):
         inter-layer dropout off, and parameters with ``requires_grad == False`` receive no gradient and cost no backward
         work where it can be skipped.  With every sub-module in training mode and every parameter trainable nothing changes."""
         if self.training and torch.is_grad_enabled():
+            if lengths is not None:
+                raise _native.SirError("lengths (un-padded batch inference) is not available on the differentiable training "
+                                       "path: call model.eval() or run under torch.no_grad()")
             from sir_amd import train_ops
             return train_ops.forward_train(self, x)
-        return ops.model_infer(self, x, self._ws)
+        return ops.model_infer(self, x, self._ws, lengths=lengths)
 
     @torch.no_grad()
-    def predict(self, x):
-        """logits and argmax (scripts/evaluate.py:82-83) in one launch sequence."""
-        return ops.model_infer(self, x, self._ws, want_argmax=True)
+    def predict(self, x, lengths=None):
+        """logits and argmax (scripts/evaluate.py:82-83) in one launch sequence; ``lengths`` as in ``forward``."""
+        return ops.model_infer(self, x, self._ws, want_argmax=True, lengths=lengths)
 
 
 if __name__ == "__main__":

@@ -147,8 +147,28 @@ def _as_features(x):
     return _f32c(x.contiguous(), "input")
 
 
-def model_infer(mod, x, workspace, want_argmax=False, debug=None):
-    """eval-mode forward of ``CNNAudioGRU`` on the GPU -> logits [B, C] (and argmax int64 [B])."""
+def _as_lengths(lengths, bsz, t, device):
+    """``lengths`` of a ragged call as an int32 device tensor [B].  A host list (or a CPU tensor) is validated here and now;
+    a device tensor is validated by the kernels (bad rows come back NaN and ``check_status`` raises)."""
+    if not torch.is_tensor(lengths):
+        lengths = torch.as_tensor(list(lengths))
+    if lengths.dim() != 1 or lengths.numel() != bsz:
+        raise _native.SirError(f"lengths must hold one entry per clip: got shape {tuple(lengths.shape)} for a batch of {bsz}")
+    if lengths.is_floating_point() or lengths.dtype == torch.bool:
+        raise _native.SirError("lengths must be integers (frames per clip)")
+    if not lengths.is_cuda:
+        bad = [(i, int(v)) for i, v in enumerate(lengths.tolist()) if not 8 <= int(v) <= t]
+        if bad:
+            raise _native.SirError(f"lengths outside [8, {t}] (clip, frames): {bad[:8]}")
+        lengths = lengths.to(device)
+    return lengths.to(torch.int32).contiguous()
+
+
+def model_infer(mod, x, workspace, want_argmax=False, debug=None, lengths=None):
+    """eval-mode forward of ``CNNAudioGRU`` on the GPU -> logits [B, C] (and argmax int64 [B]).
+
+    ``lengths`` (int tensor or list, frames per clip): the un-padded function (``sir_model_infer_ragged``) -- row b is
+    what the model gives ``x[b:b+1, :, :lengths[b]]`` on its own; the columns behind a clip's length are never read as data."""
     _native.require_hip(x)
     x = _as_features(x)
     bsz, _, t = x.shape
@@ -157,15 +177,23 @@ def model_infer(mod, x, workspace, want_argmax=False, debug=None):
     need = lib.sir_model_workspace_bytes(h, bsz, t, 0)
     if need == 0:
         raise _native.SirError(f"unsupported shape batch={bsz} frames={t}")
+    if lengths is not None:
+        lengths = _as_lengths(lengths, bsz, t, x.device)
     ws = workspace.get(need, x.device)
     w, keep = cached_weights(mod)
     logits = torch.empty((bsz, w.num_classes), dtype=torch.float32, device=x.device)
     amax = torch.empty((bsz,), dtype=torch.int64, device=x.device) if want_argmax else None
     lib.sir_model_set_weights_version(h, weights_version(mod, keep, workspace))
-    rc = lib.sir_model_infer(h, C.byref(w), x.data_ptr(), bsz, t, logits.data_ptr(),
-                             amax.data_ptr() if amax is not None else None, ws.data_ptr(), ws.numel(),
-                             _native.current_stream_ptr())
-    _native.check(rc, "sir_model_infer")
+    if lengths is None:
+        rc = lib.sir_model_infer(h, C.byref(w), x.data_ptr(), bsz, t, logits.data_ptr(),
+                                 amax.data_ptr() if amax is not None else None, ws.data_ptr(), ws.numel(),
+                                 _native.current_stream_ptr())
+        _native.check(rc, "sir_model_infer")
+    else:
+        rc = lib.sir_model_infer_ragged(h, C.byref(w), x.data_ptr(), lengths.data_ptr(), bsz, t, logits.data_ptr(),
+                                        amax.data_ptr() if amax is not None else None, ws.data_ptr(), ws.numel(),
+                                        _native.current_stream_ptr())
+        _native.check(rc, "sir_model_infer_ragged")
     if debug is not None:
         debug.update(stage_views(ws, bsz, t))
     del keep

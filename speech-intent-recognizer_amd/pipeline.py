@@ -98,13 +98,16 @@ class BatchPipeline:
             return self.featurizer(wave, lengths, **kw)
 
     @torch.no_grad()
-    def infer(self, i, feats, want_argmax=True):
-        """eval-mode forward (+ argmax) of batch ``i`` on its slot's stream; closes the submission of batch ``i``."""
+    def infer(self, i, feats, want_argmax=True, lengths=None):
+        """eval-mode forward (+ argmax) of batch ``i`` on its slot's stream; closes the submission of batch ``i``.
+        ``lengths`` (frames per clip): the un-padded function, as ``CNNAudioGRU.forward(x, lengths)``."""
         k, st = self._begin(i)
         if self.n > 1:
             feats.record_stream(st)
+            if torch.is_tensor(lengths) and lengths.is_cuda:
+                lengths.record_stream(st)
         with torch.cuda.stream(st):
-            out = ops.model_infer(self.model, feats, self.workspaces[k], want_argmax=want_argmax)
+            out = ops.model_infer(self.model, feats, self.workspaces[k], want_argmax=want_argmax, lengths=lengths)
         self._end()
         return out
 

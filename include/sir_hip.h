@@ -234,6 +234,61 @@ int sir_model_infer(sir_handle* h, const sir_model_weights* w, const float* feat
 int sir_model_infer_ragged(sir_handle* h, const sir_model_weights* w, const float* feats,
                            const int32_t* frames, int batch, int t_frames, float* logits,
                            int64_t* argmax, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- utterance segmentation of long recordings --------------------------------
+ * sir_vad_segment replaces, for a whole batch of recordings resident in HBM, the energy detector of the continuous-audio
+ * recogniser: MicrophoneListener._calculate_energy / _is_speech (scripts/testing.py:38-47) and the state machine of
+ * MicrophoneListener.listen (:63-133).  sir_vad_gather cuts the found utterances out as the float rows IntentRecognizer.predict
+ * (:222-266) is handed (`audio_float`, :118-119), trimmed in samples as :231-232 trims in frames.
+ * For recording r of lengths[r] samples and chunk size c: n_chunks = ceil(lengths[r] / c); a trailing partial chunk is judged on
+ * its own samples (the reference's stream never delivers one).
+ *   energy  : e_k = mean |x| over the chunk's samples (:38-42).  i16: the integer sum S of |s| is exact and
+ *             e_k = (float)((double)S / (count * 32768.0)), the correctly rounded mean.  f32: an ordered, atomic-free fp32
+ *             reduction (at most chunk_size / 64 + 6 additions on any path, then one division): bit-reproducible run to run.
+ *             speech_k = e_k > threshold, strict, in float (:44-47); a NaN energy is silence.
+ *   segments: with P = prior_chunks, n_stop = silence_chunks -- a segment TRIGGERS at speech chunk i if no speech chunk precedes
+ *             it or the previous one lies more than n_stop back (:85-92); it ENDS at chunk j if speech_{j - n_stop} holds and
+ *             the n_stop chunks after it are silent (:104-115; n_stop == 0: every speech chunk is its own segment).  The k-th
+ *             trigger pairs with the k-th end; the segment's first chunk is max(0, i - P + 1) for P >= 1 (the prior buffer of
+ *             :79-82 already holds chunk i) and i for P == 0; its samples are [first * c, min((j + 1) * c, length)).
+ *             As the reference: the prior buffer is not cleared between utterances, so a segment may start up to P - 1 chunks
+ *             inside the previous one, and the trailing n_stop silent chunks belong to the segment.
+ *             Unlike the reference: (1) it appends the trigger chunk twice (from the prior buffer and at :96); here a segment is
+ *             a contiguous sample range and that chunk appears once.  (2) it drops an utterance still open when the stream
+ *             stops; flush_tail != 0 emits it, ending at `length`; flush_tail == 0 drops it.
+ *   wave, wave_dtype, wave_stride, lengths, max_len: as sir_features_fwd (lengths are clamped to [0, max_len])
+ *   energy_out: optional test hook (NULL in production): f32 [n_rec][max_chunks], max_chunks = ceil(max_len / chunk_size), zero
+ *               behind a recording's own chunks.  Without it only the packed speech flags are written (into the workspace).
+ *   seg_count : int32 [n_rec], the TRUE number of segments of each recording
+ *   seg_table : int32 [seg_cap][3] = {recording, start sample, end sample}, recording-major, then by time; rows at or beyond
+ *               min(total, seg_cap) are left unwritten (may be NULL when seg_cap == 0)
+ *   total     : int32 [1], the true total.  It stays on the device; a total above seg_cap is not an error of the call -- the host
+ *               sees it in `total`, grows the table and calls again.  (The total must stay below 2^31.)
+ *   workspace : sir_vad_workspace_bytes(h, n_rec, max_len, chunk_size) bytes, 16-byte aligned (too small: SIR_ENOMEM)
+ * Nothing allocates, nothing synchronises; the numbering uses prefix scans, no atomics: the table order is exact.
+ * sir_vad_gather: row s < min(total, seg_cap) of `out` ([seg_cap][out_stride] f32) = the segment's samples (i16 dequantised as
+ *   s / 32768), cut at max_clip_len, zero behind its length up to max_clip_len; out_lengths[s] = min(end - start, max_clip_len).
+ *   Rows at or beyond min(total, seg_cap) get out_lengths = 0 and are not otherwise written.  A table row with a recording
+ *   outside [0, n_rec) or a range outside 0 <= start <= end <= wave_stride yields a zero row of length 0 and raises the handle's
+ *   status word (bit 128): SIR_EINVAL at the next sir_check_status.  The other rows are unaffected.
+ * sir_vad_stop_chunks: host helper, the smallest n with n * (chunk_size / sample_rate) >= silence_limit evaluated in double as
+ *   the listener's own test (:110-111); 16 at its defaults.  -1 on bad input (a rate or chunk size <= 0, a limit that is
+ *   negative, NaN or infinite).  prior_chunks is int(prior_recording * sample_rate / chunk_size) (:63), 7 at the defaults. */
+typedef struct sir_vad_config {
+    int   chunk_size;      /* 1024; in [64, 4096], a multiple of 64 (else SIR_EINVAL) */
+    float threshold;       /* 0.01; NaN or < 0: SIR_EINVAL */
+    int   silence_chunks;  /* >= 0 */
+    int   prior_chunks;    /* >= 0 */
+    int   flush_tail;      /* != 0: emit an utterance still open at the end of the recording */
+} sir_vad_config;
+int sir_vad_stop_chunks(int sample_rate, int chunk_size, double silence_limit);
+size_t sir_vad_workspace_bytes(const sir_handle* h, int n_rec, int max_len, int chunk_size);
+int sir_vad_segment(sir_handle* h, const void* wave, int wave_dtype, int64_t wave_stride, const int32_t* lengths, int n_rec,
+                    int max_len, const sir_vad_config* cfg, float* energy_out, int32_t* seg_count, int32_t* seg_table, int seg_cap,
+                    int32_t* total, void* workspace, size_t workspace_bytes, void* stream);
+int sir_vad_gather(sir_handle* h, const void* wave, int wave_dtype, int64_t wave_stride, int n_rec, const int32_t* seg_table,
+                   const int32_t* total, int seg_cap, float* out, int64_t out_stride, int max_clip_len, int32_t* out_lengths,
+                   void* stream);
+
 /* The GRU recurrence kernels (forward and backward) exchange hidden-state slices between the workgroups of a
  * cluster through tagged granules in global memory and rely on the cluster being co-resident.  A workgroup that
  * spins past its limit (a partitioned / oversubscribed GPU, a stalled peer) sets a device status word owned by the

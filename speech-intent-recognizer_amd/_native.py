@@ -54,6 +54,11 @@ class AdamConfig(C.Structure):
                 ("decoupled", C.c_int), ("max_norm", C.c_float), ("ema_decay", C.c_float)]
 
 
+class VadConfig(C.Structure):
+    _fields_ = [("chunk_size", C.c_int), ("threshold", C.c_float), ("silence_chunks", C.c_int), ("prior_chunks", C.c_int),
+                ("flush_tail", C.c_int)]
+
+
 # name -> (restype, argtypes); must list every function declared in include/sir_hip.h
 SIGNATURES = {
     "sir_abi_version": (C.c_int, []),
@@ -74,6 +79,12 @@ SIGNATURES = {
     "sir_wave_perturb": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
                                    C.c_void_p, C.c_size_t, C.c_void_p]),
+    "sir_vad_stop_chunks": (C.c_int, [C.c_int, C.c_int, C.c_double]),
+    "sir_vad_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "sir_vad_segment": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.POINTER(VadConfig),
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "sir_vad_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                 C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "sir_gather_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
     "sir_mix_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,

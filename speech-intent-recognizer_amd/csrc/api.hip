@@ -257,7 +257,8 @@ static const char* const kKernelNames[SIR_K_COUNT] = {
     "train_gemm_ih_l0", "train_gru_l0", "train_dropout", "train_gemm_ih_l1", "train_gru_l1", "train_attention_fc", "ce_loss",
     "bwd_head", "bwd_gru_l1", "bwd_gru_dw_l1", "bwd_gru_dx_l1", "bwd_gru_l0", "bwd_gru_dw_l0", "bwd_gru_dx_l0",
     "bwd_bn3", "bwd_conv3_wgrad", "bwd_conv3_dgrad", "bwd_bn2", "bwd_conv2_wgrad", "bwd_conv2_dgrad", "bwd_conv1", "adam",
-    "mix_features", "grad_sumsq", "grad_norm_clip", "adam_clipped", "adam_ex", "adam_ex_clipped"};
+    "mix_features", "grad_sumsq", "grad_norm_clip", "adam_clipped", "adam_ex", "adam_ex_clipped",
+    "vad_chunk_energy", "vad_segment", "vad_gather"};
 
 extern "C" int sir_profile_kernel_count(void) { return SIR_K_COUNT; }
 extern "C" const char* sir_profile_kernel_name(int id) { return (id >= 0 && id < SIR_K_COUNT) ? kKernelNames[id] : ""; }
@@ -298,6 +299,11 @@ static int check_status_impl(sir_handle* h, hipStream_t st, const char* who) {
     }
     if (v & 64u) {
         sir_set_error("%s: sir_model_infer_ragged was given a length outside [8, t_frames] (status %u): those rows' logits are NaN", who, v);
+        return SIR_EINVAL;
+    }
+    if (v & 128u) {
+        sir_set_error("%s: sir_vad_gather was given a table row whose recording or sample range is outside the batch (status %u): those "
+                      "rows are zero with length 0", who, v);
         return SIR_EINVAL;
     }
     if (v & 4u) {

@@ -27,6 +27,8 @@ enum SirKernelId {
     SIR_K_MIX, SIR_K_GRAD_SUMSQ, SIR_K_GRAD_CLIP, SIR_K_ADAM_CLIPPED,
     // sir_adam_step_ex with decoupled weight decay and / or the EMA shadow on (appended), without / with clipping
     SIR_K_ADAM_EX, SIR_K_ADAM_EX_CLIPPED,
+    // utterance segmentation of long recordings (vad.hip, appended): chunk energy, state machine (count + bases + table), clip gather
+    SIR_K_VAD_ENERGY, SIR_K_VAD_SEGMENT, SIR_K_VAD_GATHER,
     SIR_K_COUNT
 };
 

@@ -1,0 +1,180 @@
+"""Drop-in for the recogniser half of the reference's scripts/testing.py, plus its batch form for long recordings.
+
+``IntentRecognizer(model_path, label_map_path, device)`` keeps the reference's surface (testing.py:158-281): ``predict(audio_data,
+sample_rate)`` -> ``{"predicted_label", "confidence", "top_predictions"}`` (:262-266) and ``process_audio``.  What the reference
+does live -- ``MicrophoneListener.listen`` (:49-143) cuts a microphone stream into utterances and calls ``predict`` on each --
+``recognize_recordings`` does for many recordings at once on MI355X: ``sir_amd.segmenter.Segmenter`` finds the utterances
+(``sir_vad_segment``), cuts them out (``sir_vad_gather``), ``HipFeaturizer`` turns the clip batch into features and one forward
+per group of recordings scores them.
+
+Features are THIS project's training features (``sir_features_fwd``: torchaudio-style mel power, dB, whole-utterance z-norm),
+not the librosa ``power_to_db(ref=np.max)`` features with the fixed -30.1 / 12.7 normalisation of testing.py:189-209 -- SURVEY.md
+row 11 records that those differ from what the model was trained on.  ``MicrophoneListener`` itself, PyAudio and the saving of
+recordings (hardware and file I/O) are not ported.
+"""
+import argparse
+import json
+import logging
+
+import numpy as np
+import torch
+
+from sir_amd import ops
+from sir_amd.featurizer import HOP, get_featurizer
+from sir_amd.segmenter import Segmenter
+from sir_amd.scripts import test_model, test_tts_samples
+
+logger = logging.getLogger(__name__)
+
+MAX_LENGTH = 200                 # testing.py:230
+MIN_FRAMES = test_tts_samples.MIN_FRAMES
+GROUP = 32                       # recordings per segmentation call and forward
+MAX_RECORDING_S = 3600.0         # a longer file is cut here
+MAX_CLIP_S = 600.0               # un-padded scoring: a longer utterance is cut here (test_model.extract_features' bound)
+
+
+class IntentRecognizer:
+    def __init__(self, model_path, label_map_path, device=None, segmenter=None):
+        """Load the label map and the checkpoint (testing.py:159-191; the class count comes from the checkpoint's ``fc.weight``
+        as in scripts/test_tts_samples.py, where the reference hard-codes 31).  ``segmenter``: the ``Segmenter`` that
+        ``recognize_recordings`` uses (default: the listener's defaults)."""
+        self.device = torch.device("cuda") if device is None else torch.device(device)
+        self.model, self.label_map = test_tts_samples.load_model(model_path, label_map_path, self.device)
+        self._finish(segmenter)
+
+    @classmethod
+    def from_model(cls, model, label_map, device=None, segmenter=None):
+        """The recogniser around an already loaded ``CNNAudioGRU`` and label map."""
+        self = cls.__new__(cls)
+        self.device = torch.device("cuda") if device is None else torch.device(device)
+        self.model, self.label_map = model.to(self.device).eval(), dict(label_map)
+        self._finish(segmenter)
+        return self
+
+    def _finish(self, segmenter):
+        self.inv_label_map = {v: k for k, v in self.label_map.items()}
+        self.segmenter = segmenter if segmenter is not None else Segmenter()
+        self.sample_rate = self.segmenter.sample_rate
+
+    # ---- one utterance (testing.py:222-266) ------------------------------------------------------------------------------
+    def predict(self, audio_data, sample_rate):
+        """audio_data: 1-D float array in [-1, 1] (or int16 PCM) -> the result dictionary of :262-266, or ``None`` on failure.
+        Pad or trim to 200 frames (:229-235), softmax, top-3."""
+        try:
+            wave = torch.as_tensor(np.ascontiguousarray(audio_data)).reshape(1, -1)
+            if wave.dtype not in (torch.float32, torch.int16):
+                wave = wave.to(torch.float32)
+            fz = get_featurizer()
+            wave = wave.to(self.device)
+            lens = torch.tensor([wave.shape[1]], dtype=torch.int32, device=self.device)
+            if int(sample_rate) != self.sample_rate:
+                wave, lens = fz.resample(wave, int(sample_rate), self.sample_rate, lens)
+            feats = fz(wave, lens, t_pad=MAX_LENGTH)
+            with torch.no_grad():
+                output = self.model(feats).cpu()
+            ops.check_status()
+            return test_model._result(output, self.inv_label_map)
+        except Exception as e:
+            logger.error(f"Error during prediction: {str(e)}")
+            return None
+
+    def process_audio(self, audio_data, sample_rate):
+        """testing.py:268-281"""
+        result = self.predict(audio_data, sample_rate)
+        if result:
+            print("\n=== INTENT RECOGNITION RESULTS ===")
+            print(f"Predicted Intent: {result['predicted_label']}")
+            print(f"Confidence: {result['confidence'] * 100:.2f}%")
+            print("\nTop Predictions:")
+            for i, pred in enumerate(result["top_predictions"]):
+                print(f"  {i + 1}. {pred['label']} ({pred['probability'] * 100:.2f}%)")
+            print("=" * 35)
+
+    # ---- many long recordings --------------------------------------------------------------------------------------------
+    def _load_group(self, items):
+        """recordings of one group (1-D arrays / tensors at the segmenter's rate, or paths) -> (wave [n, L], lengths) on the GPU"""
+        if all(isinstance(x, str) for x in items):
+            ext = test_model._get_extractor()
+            loaded = [ext._load(p, MAX_RECORDING_S) for p in items]
+            if any(x is None for x in loaded):
+                raise FileNotFoundError("a recording of this group is missing")
+            keys = {(ch, sr, d.dtype) for d, ch, sr in loaded}
+            if len(keys) == 1:
+                (ch, sr, _), = keys
+                return ext.waveforms_of_group([d for d, _, _ in loaded], ch, sr, MAX_RECORDING_S)
+            parts = [ext.waveforms_of_group([d], ch, sr, MAX_RECORDING_S) for d, ch, sr in loaded]
+            items = [(w[0, :int(n.item())].float() / 32768.0 if w.dtype == torch.int16 else w[0, :int(n.item())]) for w, n in parts]
+        waves = [torch.as_tensor(x).reshape(-1) for x in items]
+        dtype = torch.int16 if all(w.dtype == torch.int16 for w in waves) else torch.float32
+        waves = [w if w.dtype == dtype else (w.float() / 32768.0 if w.dtype == torch.int16 else w.to(torch.float32)) for w in waves]
+        lens = [int(w.numel()) for w in waves]
+        width = (max(max(lens), 1) + 7) // 8 * 8                 # rows stay 16-byte aligned for the vector loads
+        batch = torch.zeros((len(waves), width), dtype=dtype, device=self.device)
+        for k, w in enumerate(waves):
+            batch[k, :lens[k]] = w.to(self.device)
+        return batch, torch.tensor(lens, dtype=torch.int32, device=self.device)
+
+    def score_segments(self, wave, lengths, pad_to=MAX_LENGTH):
+        """Segment a GPU batch of recordings and score every utterance -> (seg_table int32 [n, 3] on the CPU, logits [n, C] on
+        the CPU).  ``pad_to`` frames: every clip is cut to fewer than ``pad_to * hop`` samples (the trim of :231-232, in samples)
+        and padded to ``pad_to`` frames; ``pad_to=None``: every clip is scored at its own length through the ragged forward
+        (``lengths=``), a clip with fewer than 8 frames at 8."""
+        seg = self.segmenter
+        table, _, total = seg.segment(wave, lengths)
+        host_table = table.cpu()
+        n = host_table.shape[0]
+        num_classes = self.model.fc.weight.shape[0]
+        if n == 0:
+            return host_table, torch.zeros((0, num_classes), dtype=torch.float32)
+        longest = int((host_table[:, 2] - host_table[:, 1]).max())
+        limit = pad_to * HOP - 1 if pad_to is not None else int(MAX_CLIP_S * seg.sample_rate)
+        clips, clip_lens = seg.gather(wave, table, total, max(1, min(longest, limit)))
+        fz = get_featurizer()
+        frames = (clip_lens // HOP + 1).clamp(min=MIN_FRAMES)
+        t_pad = pad_to if pad_to is not None else int(frames.max().item())
+        feats = fz(clips, clip_lens, t_pad=t_pad)
+        with torch.no_grad():
+            logits = self.model(feats) if pad_to is not None else self.model(feats, lengths=frames)
+        logits = logits.cpu()
+        ops.check_status()
+        return host_table, logits
+
+    def recognize_recordings(self, waves_or_paths, pad_to=MAX_LENGTH):
+        """waves_or_paths: recordings as 1-D float32 / int16 arrays or tensors at the segmenter's sample rate, or paths of WAVE
+        files (decoded, mixed to mono and resampled on the GPU).  -> per recording, the list of its utterances in time order:
+        ``{"start": seconds, "end": seconds, "predicted_label", "confidence", "top_predictions"}``; ``None`` for the recordings of
+        a group that failed (logged, as the reference's ``predict`` does)."""
+        items = list(waves_or_paths)
+        results = [None] * len(items)
+        sr = float(self.segmenter.sample_rate)
+        for g in range(0, len(items), GROUP):
+            group = items[g:g + GROUP]
+            try:
+                wave, lens = self._load_group(group)
+                table, logits = self.score_segments(wave, lens, pad_to=pad_to)
+                found = [[] for _ in group]
+                for row, (r, a, b) in enumerate(table.tolist()):
+                    res = test_model._result(logits[row:row + 1], self.inv_label_map)
+                    found[r].append({"start": a / sr, "end": b / sr, **res})
+                results[g:g + len(group)] = found
+            except Exception as e:
+                logger.error(f"Error recognising recordings {g}..{g + len(group) - 1}: {str(e)}")
+        return results
+
+
+def main():
+    parser = argparse.ArgumentParser(description="Speech intent recognition of the utterances of long recordings")
+    parser.add_argument("--model", type=str, default="checkpoints/best_model.pt", help="Path to the trained model")
+    parser.add_argument("--label_map", type=str, default="data/processed/label_map.json", help="Path to the label map")
+    parser.add_argument("--threshold", type=float, default=0.01, help="Energy threshold for speech detection")
+    parser.add_argument("--silence_limit", type=float, default=1.0, help="Seconds of silence that end an utterance")
+    parser.add_argument("recordings", nargs="+", help="WAVE files to segment and recognise")
+    args = parser.parse_args()
+    recognizer = IntentRecognizer(args.model, args.label_map,
+                                  segmenter=Segmenter(threshold=args.threshold, silence_limit=args.silence_limit))
+    for path, found in zip(args.recordings, recognizer.recognize_recordings(args.recordings)):
+        print(json.dumps({"file": path, "utterances": found}))
+
+
+if __name__ == "__main__":
+    main()

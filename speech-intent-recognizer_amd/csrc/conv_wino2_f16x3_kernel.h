@@ -12,6 +12,10 @@
 // Task = 32 tiles (8 tile rows x 4 tile columns; columns are numbered across the whole batch, g = image * TW + tx, so a task
 // may straddle two images and no column is wasted) x 64 output channels (layers with 128: two tasks per block); a workgroup
 // walks its tasks chunk by chunk, step s: producers chunk s, consumers chunk s - 1, ONE barrier per step.
+// With a compacted task list (inference pad skip, Wino2Geo::ctab) a task holds up to two SEGMENTS instead, each a run of tile
+// columns of one image: segment A in the first tile slots and an optional guest segment B of another image in the last ones, their
+// patch columns disjoint.  The DMA sources every patch column from its own segment's image, validity and stores map slot ->
+// segment -> (image, tile column); transform, LDS layout and MFMA sequence do not know about it.
 //   producers     raw 18 x 10 pixel patches of a chunk arrive by LDS-DMA (global_load_lds_dwordx4: no VGPRs, asynchronous) into
 //                 a three-slot ring, issued two steps ahead; rows above / below the image, the pad column of an odd-width map
 //                 and tile columns past the batch are sourced from a zero page, so the transform needs selects only in the one
@@ -180,16 +184,38 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_f16x3_kernel(
     const int H = geo.H, W = geo.W, TW = geo.TW, NG = geo.NG, RBN = geo.RBN;
     const int* const ctab = OUT_MODE <= 1 ? geo.ctab : nullptr;      // (compacted lists: inference forms only)
     const int NS = ctab ? RBN * ctab[0] : geo.NS;
-    const int ntask_s = (NS - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;        // spatial tasks of this workgroup
-    const int ntask = ntask_s * NCHO;
+    // Dealing is static, round-robin over the resident workgroups.  A unit is (spatial task, 64-channel half).  The inference forms of a
+    // 128-channel layer (HALF_DEAL) deal whole spatial tasks (both halves back to back on one workgroup) for the NS / gridDim full rounds and
+    // the HALVES of the remaining spatial tasks one by one, so that a remainder costs one task-time, not two.  The other forms deal
+    // spatial tasks only (OUT_MODE 2: the statistics' summation order is part of the result).
+    constexpr bool HALF_DEAL = OUT_MODE <= 1 && NCHO > 1;
+    const int GD = (int)gridDim.x, bx = (int)blockIdx.x;
+    const int nfull = HALF_DEAL ? NS / GD : 0;                          // full rounds of spatial tasks (HALF_DEAL only)
+    const int nfull_t = nfull * NCHO;
+    const int ntask = HALF_DEAL ? nfull_t + ((NS - nfull * GD) * NCHO - bx + GD - 1) / GD : ((NS - bx + GD - 1) / GD) * NCHO;
     if (ntask <= 0) return;
     const int nsteps = ntask * NCH;                                     // chunks of this workgroup; step s: producers chunk s, consumers chunk s - 1
 
-    auto task_geo = [&](int lt, int& g0, int& ty0, int& ch, int& s) {
-        s = (int)blockIdx.x + (lt / NCHO) * (int)gridDim.x;
-        ch = lt % NCHO;
+    // task lt of this workgroup: segment A's first tile column g0 and its tile count na, the guest word bw (Wino2Geo::ctab; -1: no guest),
+    // first tile row ty0, output-channel half ch, spatial task s
+    auto task_geo = [&](int lt, int& g0, int& na, int& bw, int& ty0, int& ch, int& s) {
+        if (HALF_DEAL && lt >= nfull_t) {
+            const int r = bx + (lt - nfull_t) * GD;
+            s = nfull * GD + r / NCHO;
+            ch = r % NCHO;
+        } else {
+            s = bx + (lt / NCHO) * GD;
+            ch = lt % NCHO;
+        }
         const int cb = w2_div(s, geo.dRBN), rb = s - cb * RBN;
-        g0 = ctab ? ctab[1 + cb] : 4 * cb; ty0 = 8 * rb;
+        // (both words in ONE 8-byte load: hipcc reads the list with vector loads and waits for each at once)
+        const int2 tw = ctab ? reinterpret_cast<const int2*>(ctab)[1 + cb] : make_int2((4 * cb) << 2 | 3, -1);
+        g0 = tw.x >> 2; na = 1 + (tw.x & 3); bw = RAGGED ? -1 : tw.y; ty0 = 8 * rb;
+    };
+    // guest word -> first tile slot (8: none, no slot or patch column reaches it), first tile column and tile count of segment B
+    auto guest_geo = [&](int g0, int bw, int& sB, int& gB, int& nB) {
+        const bool guest = bw >= 0;
+        sB = guest ? 2 + ((bw >> 1) & 1) : 8; gB = guest ? bw >> 2 : g0; nB = guest ? 1 + (bw & 1) : 0;
     };
     // ---- raw-patch DMA: WHO issues it ------------------------------------------------------------------------------------------
     // The four producer waves (piece k = wave + 4 i, counted vmcnt waits in their loop) -- except in a 32-channel layer (the
@@ -215,14 +241,22 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_f16x3_kernel(
         pre_lc[ii] = lc;
         pre_part[ii] = (sp ^ (((lr >> 2) & 1) << 1)) * 4;
     }
-    auto raw_offsets = [&](int g0, int ty0, unsigned (&off)[D_PPW]) {
-        // pixel columns P of the flattened batch that may be read: all of it, or (compacted list) the task's own image only
-        const int gimg = ctab ? w2_div(g0, geo.dTW) : 0;
-        const int plo = ctab ? 2 * TW * gimg : 0, phi = ctab ? plo + (RAGGED ? min(W, geo.wtab[gimg] >> geo.wsh) : W) : 2 * NG;
+    auto raw_offsets = [&](int g0, int bw, int ty0, unsigned (&off)[D_PPW]) {
+        // pixel columns P of the flattened batch that may be read: all of it, or (compacted list) the own image of the lane's segment
+        // only.  Patch columns >= 2 sB belong to the guest segment, whose tile slot sB sits at patch column 2 sB: a per-lane SELECT
+        // of the segment's column origin and bounds (no branch: nothing here may wait on the DMA pieces in flight)
+        int sB, gB, nB;
+        guest_geo(g0, bw, sB, gB, nB);
+        const int gimg = ctab ? w2_div(g0, geo.dTW) : 0, gimgB = ctab ? w2_div(gB, geo.dTW) : 0;
+        const int ploA = ctab ? 2 * TW * gimg : 0, phiA = ctab ? ploA + (RAGGED ? min(W, geo.wtab[gimg] >> geo.wsh) : W) : 2 * NG;
+        const int ploB = 2 * TW * gimgB, phiB = ploB + W;
+        const int cA = 2 * g0 - 1, cB = 2 * (gB - sB) - 1, lcB = 2 * sB;
 #pragma unroll
         for (int ii = 0; ii < D_PPW; ++ii) {
             const int gy = 2 * ty0 - 1 + pre_lr[ii];
-            const int P = 2 * g0 - 1 + pre_lc[ii];
+            const bool inB = pre_lc[ii] >= lcB;
+            const int plo = inB ? ploB : ploA, phi = inB ? phiB : phiA;
+            const int P = (inB ? cB : cA) + pre_lc[ii];
             const int Pc = min(max(P, 0), 2 * NG - 1);
             const int bb = w2_div(Pc, geo.d2TW), px = Pc - bb * 2 * TW;
             const bool ok = gy >= 0 && gy < H && P >= plo && P < phi && px < W;
@@ -240,13 +274,13 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_f16x3_kernel(
         }
     };
     // chunk q (global index over this workgroup's tasks) -> issue its pieces into ring slot q % 3
-    int ig0, ity0, ich, is_;
+    int ig0, ina, ibw, ity0, ich, is_;
     unsigned roff[D_PPW];
     int roff_task = -1;
     auto issue_chunk = [&](int q) {
         if (q >= nsteps) return;
         const int lt = q / NCH, c = q - lt * NCH;
-        if (lt != roff_task) { task_geo(lt, ig0, ity0, ich, is_); raw_offsets(ig0, ity0, roff); roff_task = lt; }
+        if (lt != roff_task) { task_geo(lt, ig0, ina, ibw, ity0, ich, is_); raw_offsets(ig0, ibw, ity0, roff); roff_task = lt; }
         raw_issue(roff, c, q % W2_NRAW);
     };
     int nst = 0;
@@ -293,9 +327,9 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_f16x3_kernel(
             if (s < nsteps) {
                 if (!IDLE_DMA && !(DBG & 2)) issue_chunk(s + 2);        // into the slot chunk s - 1 left (its reads ended before the last barrier)
                 fine(s, 1);
-                if (s % NCH == 0) {                                     // first chunk of a task: where are its image boundaries
-                    int cg0, cty0, cch, cs;
-                    task_geo(s / NCH, cg0, cty0, cch, cs);
+                if (s % NCH == 0 && !ctab) {                            // first chunk of a task: where are its image boundaries (none in a compacted list)
+                    int cg0, cna, cbw, cty0, cch, cs;
+                    task_geo(s / NCH, cg0, cna, cbw, cty0, cch, cs);
                     const int t0 = cg0 - w2_div(cg0, geo.dTW) * TW;     // tile column of the task's first column inside its image
                     edge = !ctab && (t0 == 0 || t0 + 3 >= TW - 1);    // (compacted: no neighbouring image in the patch)
                     const int txx = (t0 + ttx) - w2_div(t0 + ttx, geo.dTW) * TW;
@@ -397,8 +431,8 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_f16x3_kernel(
         for (int p = 0; p < NPW; ++p)
             q[p] = *reinterpret_cast<const uint4*>(wbase + ((size_t)(p * G + gidx) * (COUT * 2) + (size_t)chh * 128) * 16 + wlane);
     };
-    int g0, ty0, ch, s_idx;
-    task_geo(0, g0, ty0, ch, s_idx);
+    int g0, na, bw, ty0, ch, s_idx;
+    task_geo(0, g0, na, bw, ty0, ch, s_idx);
 #pragma unroll
     for (int j = 0; j < 4; ++j) load_w(4 * mi + j, ch, wq[j]);
     f32x16 acc[4];
@@ -419,8 +453,8 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_f16x3_kernel(
     // spilled the weight ring into them (376-480 B of scratch per lane for 64 and 128 input channels)
 #pragma unroll 1
     for (int lt = 0; lt < ntask; ++lt) {
-        int g0n = g0, ty0n = ty0, chn = ch, sn = s_idx;
-        if (lt + 1 < ntask) task_geo(lt + 1, g0n, ty0n, chn, sn);
+        int g0n = g0, nan_ = na, bwn = bw, ty0n = ty0, chn = ch, sn = s_idx;
+        if (lt + 1 < ntask) task_geo(lt + 1, g0n, nan_, bwn, ty0n, chn, sn);
 #pragma unroll 1
         for (int c = 0; c < NCH; ++c) {
             stamp();
@@ -517,11 +551,17 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_f16x3_kernel(
                 constexpr float DESC = H3_LO_INV;                      // the f16x3 accumulators are 2^11 too large (exact power of two)
                 if (OUT_MODE <= 1) { sc_ = scale[co] * DESC; sh_ = shift[co]; }
                 {
-                    const int gc = g0 + mi;
+                    // tile slot mi -> segment -> (image, tile column).  Slots between the segments and past a segment's count hold
+                    // garbage: not stored, not counted
+                    int sB, gB, nB;
+                    guest_geo(g0, bw, sB, gB, nB);
+                    const bool inB = mi >= sB;
+                    const int sfirst = inB ? gB : g0, sk = inB ? mi - sB : mi, scnt = inB ? nB : na;
+                    const int gc = sfirst + sk, img0 = w2_div(sfirst, geo.dTW);
                     const int img = w2_div(gc, geo.dTW), tx = gc - img * TW;
-                    const bool tvalid = gc < (ctab ? (w2_div(g0, geo.dTW) + 1) * TW : NG);
-                    // pooled columns of this image (RAGGED: of its own width; the task's columns all belong to the image of g0)
-                    const int wpi = RAGGED ? min(geo.Wp, geo.wtab[w2_div(g0, geo.dTW)] >> (geo.wsh + 1)) : geo.Wp;
+                    const bool tvalid = sk < scnt && gc < (ctab ? (img0 + 1) * TW : NG);
+                    // pooled columns of this image (RAGGED: of its own width; a segment's columns all belong to the image of its first)
+                    const int wpi = RAGGED ? min(geo.Wp, geo.wtab[img0] >> (geo.wsh + 1)) : geo.Wp;
                     if (OUT_MODE <= 1) {
                         float pooled[4];
 #pragma unroll
@@ -576,7 +616,7 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_f16x3_kernel(
                 }
             }
         }
-        g0 = g0n; ty0 = ty0n; ch = chn; s_idx = sn;
+        g0 = g0n; na = nan_; bw = bwn; ty0 = ty0n; ch = chn; s_idx = sn;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -596,7 +636,7 @@ __global__ __launch_bounds__(W2_THREADS, 3) void conv3x3_wino2_f16x3_kernel(
 
 // `g`: wino2_geo of the launch (model_shape.h keeps the model's).  The dynamic-LDS opt-in (W2_LDS_BYTES) is the caller's: the library's
 // goes through sir_lds_opt_in at its launch sites (model_infer.hip / model_train_fwd.hip / model_train_bwd.hip).
-// ctab (OUT_MODE 0 / 1 only): compacted task-column list in device memory (Wino2Geo::ctab), at most ncol_max columns
+// ctab (OUT_MODE 0 / 1 only): compacted task list in device memory (Wino2Geo::ctab), at most ncol_max tasks
 // RAGGED: per-image widths wtab[b] >> wsh (see the kernel); needs ctab
 template <int CIN, int COUT, int OUT_MODE, int DBG = 0, int PRIO = 3, bool RAGGED = false>
 static inline hipError_t launch_conv_wino2(hipStream_t st, Wino2Geo g, const float* x, const unsigned short* wpb, const float* scale,

@@ -27,10 +27,19 @@ struct Wino2Geo {
     int Hp, Wp;          // pooled map (OUT_MODE 0 / 1)
     int B;
     W2Div dTW, d2TW, dRBN;   // divisions by TW, 2 TW, RBN (all operands are non-negative)
-    // nullptr: tile columns are numbered across the whole batch (above).  Otherwise a COMPACTED column list in device memory
-    // (inference pad skip, model_infer.hip): ctab[0] = number of task columns n, ctab[1 + k] = first tile column (img * TW + tx0,
-    // tx0 a multiple of 4) of task column k, k < n; NS = RBN * n.  A task then holds 4 tile columns of ONE image, its halo pixels
-    // come from that image (or the zero page outside it), and tile columns past the image's TW are neither computed nor stored.
+    // nullptr: tile columns are numbered across the whole batch (above).  Otherwise a COMPACTED task list in device memory
+    // (inference pad skip, model_infer.hip): ctab[0] = number of task columns n, NS = RBN * n, ctab[1] unused, and two words per task column k < n
+    // (ctab is 8-byte aligned: the kernel loads the pair at once):
+    //   ctab[2 + 2 k] = gA << 2 | (nA - 1)     segment A: nA = 1..4 tile columns of ONE image from gA = img * TW + tx0 (any tx0), in
+    //                                          tile slots 0 .. nA - 1
+    //   ctab[3 + 2 k] = -1, or gB << 2 | (sB - 2) << 1 | (nB - 1)
+    //                                          guest segment B: nB = 1..2 tile columns of ANOTHER image from gB, in tile slots
+    //                                          sB .. sB + nB - 1 (sB = 2 or 3, sB + nB <= 4)
+    // Tile slot k reads patch columns 2 k .. 2 k + 3 of the task's 10-column raw patch, so the segments' patch columns must be
+    // disjoint: 2 nA + 2 <= 2 sB ([1 | idle | 2], [1 | idle | idle | 1], [2 | idle | 1]).  Every patch column is sourced from the
+    // image of its own segment (or the zero page outside that image); slots between the segments and past a segment's count
+    // compute garbage that is neither stored nor counted, and a segment never runs past its image's TW.  The RAGGED form reads
+    // the first word only (its lists carry no guests).
     const int* ctab;
     // un-padded batch inference (the kernel's RAGGED form; needs ctab): image b is wtab[b] >> wsh pixel columns wide.  nullptr otherwise.
     const int* wtab;

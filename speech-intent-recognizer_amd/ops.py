@@ -219,3 +219,28 @@ def stage_views(ws, bsz, t):
             numel *= v
         out[name] = ws[offs[i]: offs[i] + 4 * numel].view(torch.float32).view(shp)
     return out
+
+
+def pad_skip_tables(ws, bsz, t):
+    """The pad-skip tables the last padded ``model_infer`` call on ``ws`` left (csrc/model_infer.hip, WS_PAD), on the host:
+    ``e0`` [B], ``d3`` [B + 1] (the template utterance last) and the conv2 / conv3 task lists (``Wino2Geo::ctab`` in
+    csrc/wino2_geo.h) as int32 arrays ``tab2`` / ``tab3`` of shape [n, 2]: the two words of each listed task."""
+    lib = _native.lib()
+    offs = (C.c_size_t * 16)()
+    if lib.sir_model_workspace_offsets(get_featurizer().handle, bsz, t, 0, offs, 16) <= 7:
+        raise _native.SirError("sir_model_workspace_offsets failed")
+    wp1, wp2 = t // 2, t // 4
+    k2max, k3max = ((wp1 + 1) // 2 + 3) // 4, ((wp2 + 1) // 2 + 3) // 4
+    n = bsz + 1
+    o_d3 = bsz + n
+    o_rows = o_d3 + n + 1 + n * k2max + 1 + n * k3max
+    o_tab2 = o_rows + 1 + n * (wp2 // 2)
+    o_tab2 += o_tab2 & 1
+    o_tab3 = o_tab2 + 2 + 2 * n * k2max
+    o_end = o_tab3 + 2 + 2 * n * k3max
+    tab = ws[offs[7]: offs[7] + 4 * o_end].view(torch.int32).cpu()
+    out = {"e0": tab[:bsz], "d3": tab[o_d3: o_d3 + n]}
+    for name, o in (("tab2", o_tab2), ("tab3", o_tab3)):
+        cnt = int(tab[o])
+        out[name] = tab[o + 2: o + 2 + 2 * cnt].view(cnt, 2)
+    return out

@@ -462,6 +462,28 @@ int sir_model_train_bwd_cfg(sir_handle* h, const sir_model_weights* w, const flo
                             const sir_train_config* cfg, const sir_model_grads* grads, void* workspace,
                             size_t workspace_bytes, int part, void* stream);
 
+/* ---- gradient with respect to the input features ------------------------------------------------
+ * sir_model_train_bwd_cfg that also returns d(loss)/d(feats): what torch leaves in x.grad after
+ *     x.requires_grad_(True); loss = criterion(model(x), label); loss.backward()
+ * (saliency maps, FGSM-style robustness checks, a differentiable stage in front of the model).
+ *   dfeats : device f32 [batch][64][t_frames], the layout of feats; written (not accumulated), without the backward's
+ *            internal loss scale; a buffer of its own.  NULL: the call IS sir_model_train_bwd_cfg -- same launches, same bits.
+ * With dfeats the data chain head -> GRU 1 -> GRU 0 -> conv3 -> conv2 -> conv1 runs to the bottom whatever `grads` holds:
+ * all 29 pointers NULL is legal and launches no weight-gradient GEMM, no bias sum and no convolution weight gradient.  Every
+ * wanted parameter gradient is bit-identical to what the call writes for it with dfeats == NULL.  The last link is one
+ * kernel: dz1 = d(loss)/d(conv1 output) is recomputed per tile from feats and da1 (slot 29) -- conv1's nine-fma chain, the
+ * BatchNorm fold of slot 12, the forward's ReLU / max-pool routing -- and convolved with the transposed taps; it is never
+ * stored.  With live bn1 statistics conv1's reduce pass runs even when no conv1 / bn1 gradient is wanted (its parameter
+ * stores are then left out) and leaves mean dy, mean dy * xhat of bn1 in channels 0..31 of slot 13; with bn_frozen[0] and
+ * no conv1 / bn1 gradient wanted it is not launched.
+ *   part : SIR_BWD_ALL and SIR_BWD_CNN write dfeats; SIR_BWD_HEAD_GRU ignores it (but runs the chain down to dx0, slot 25,
+ *          which the SIR_BWD_CNN call that follows reads).  Both halves of a split call must get the same dfeats-or-NULL.
+ * Every argument is validated before anything is launched. */
+int sir_model_train_bwd_x(sir_handle* h, const sir_model_weights* w, const float* feats, const float* dlogits,
+                          int batch, int t_frames, float dropout_p, uint64_t dropout_seed,
+                          const sir_train_config* cfg, const sir_model_grads* grads, float* dfeats,
+                          void* workspace, size_t workspace_bytes, int part, void* stream);
+
 /* optimizer.step() for torch.optim.Adam(lr, betas, eps, weight_decay) with coupled L2
  * (train.py:246-250, :107): one multi-tensor launch.  The pointer arrays are HOST arrays of device
  * pointers (n_tensors <= 32); `step` is the 1-based step count used for bias correction. */
@@ -524,6 +546,11 @@ int sir_adam_step_ex(sir_handle* h, int n_tensors, float* const* params, const f
  * (bench.py's roofline figures come from here).  mode 0 = off, 1 = every kernel, 2 = only
  * `kernel_id`.  sir_profile_collect waits for the recorded events, returns per-kernel total
  * milliseconds and launch counts since the last collect (arrays of length n), and resets. */
+/* Extended ids: kernels of optional calls are numbered BEHIND sir_profile_kernel_count(), so that a caller walking
+ * [0, sir_profile_kernel_count()) sees the list it always saw.  sir_profile_kernel_name, sir_profile_enable and
+ * sir_profile_collect (n up to count + SIR_PROFILE_EXTRA_IDS) serve them:
+ *   count + 0  "bwd_conv1_dgrad"   conv1's data gradient (sir_model_train_bwd_x with dfeats) */
+#define SIR_PROFILE_EXTRA_IDS 1
 int sir_profile_kernel_count(void);
 const char* sir_profile_kernel_name(int kernel_id);
 int sir_profile_enable(sir_handle* h, int mode, int kernel_id);

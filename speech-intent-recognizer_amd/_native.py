@@ -17,6 +17,7 @@ SIR_OK = 0
 SIR_ETIMEOUT = -5
 WAVE_F32, WAVE_I16 = 0, 1
 BWD_ALL, BWD_HEAD_GRU, BWD_CNN = 0, 1, 2
+PROFILE_EXTRA_IDS = 1           # SIR_PROFILE_EXTRA_IDS: profile ids behind sir_profile_kernel_count() (include/sir_hip.h)
 
 
 class FeatureConfig(C.Structure):
@@ -121,6 +122,9 @@ SIGNATURES = {
     "sir_model_train_bwd_cfg": (C.c_int, [C.c_void_p, C.POINTER(ModelWeights), C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                           C.c_float, C.c_uint64, C.POINTER(TrainConfig), C.POINTER(ModelGrads), C.c_void_p,
                                           C.c_size_t, C.c_int, C.c_void_p]),
+    "sir_model_train_bwd_x": (C.c_int, [C.c_void_p, C.POINTER(ModelWeights), C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                        C.c_float, C.c_uint64, C.POINTER(TrainConfig), C.POINTER(ModelGrads), C.c_void_p,
+                                        C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
     "sir_adam_step": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                 C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int, C.c_float, C.c_float, C.c_float,
                                 C.c_float, C.c_float, C.c_void_p]),

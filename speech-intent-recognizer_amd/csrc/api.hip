@@ -249,7 +249,7 @@ extern "C" int sir_pipeline_join(sir_pipeline* p, void* caller_stream) {
 }
 
 // ---- event profiling ------------------------------------------------------------------------
-static const char* const kKernelNames[SIR_K_COUNT] = {
+static const char* const kKernelNames[SIR_K_COUNT_ALL] = {
     "feat_frames", "feat_normalise", "weight_prep", "conv1_bn_relu_pool", "conv2_mfma_bn_relu_pool",
     "conv3_mfma_bn_relu_pool", "gemm_ih_l0", "gru_recurrence_l0", "gemm_ih_l1", "gru_recurrence_l1",
     "attention_pool_fc_argmax", "unused",
@@ -258,10 +258,10 @@ static const char* const kKernelNames[SIR_K_COUNT] = {
     "bwd_head", "bwd_gru_l1", "bwd_gru_dw_l1", "bwd_gru_dx_l1", "bwd_gru_l0", "bwd_gru_dw_l0", "bwd_gru_dx_l0",
     "bwd_bn3", "bwd_conv3_wgrad", "bwd_conv3_dgrad", "bwd_bn2", "bwd_conv2_wgrad", "bwd_conv2_dgrad", "bwd_conv1", "adam",
     "mix_features", "grad_sumsq", "grad_norm_clip", "adam_clipped", "adam_ex", "adam_ex_clipped",
-    "vad_chunk_energy", "vad_segment", "vad_gather"};
+    "vad_chunk_energy", "vad_segment", "vad_gather", "bwd_conv1_dgrad"};
 
 extern "C" int sir_profile_kernel_count(void) { return SIR_K_COUNT; }
-extern "C" const char* sir_profile_kernel_name(int id) { return (id >= 0 && id < SIR_K_COUNT) ? kKernelNames[id] : ""; }
+extern "C" const char* sir_profile_kernel_name(int id) { return (id >= 0 && id < SIR_K_COUNT_ALL) ? kKernelNames[id] : ""; }
 
 extern "C" int sir_profile_enable(sir_handle* h, int mode, int kernel_id) {
     if (!h || mode < 0 || mode > 2) { sir_set_error("sir_profile_enable: bad argument"); return SIR_EINVAL; }

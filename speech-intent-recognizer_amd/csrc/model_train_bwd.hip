@@ -1,4 +1,4 @@
-// Training step of CNNAudioGRU on MI355X, backward (sir_model_train_bwd and its split / fine-tuning forms): what is wanted
+// Training step of CNNAudioGRU on MI355X, backward (sir_model_train_bwd and its split / fine-tuning / input-gradient forms): what is wanted
 // (BwdPlan), then head -> GRU layer 1 -> GRU layer 0 -> conv3 -> conv2 -> conv1, one function per stage.
 #define SIR_NO_STANDALONE_KERNELS       // (the backward launches none of them: model_kernels.h)
 #include "train_bwd_kernels.h"
@@ -61,12 +61,13 @@ struct BwdPlan {
     bool fc, attn;                  // head: fc weight or bias / attention weight or bias
     bool gru_w[2], gru_b[2];        // per GRU layer: any weight matrix / any bias
     bool gb[3], blk[3];             // per conv block: gamma or beta / those or the conv weight
-    bool cnn;                       // anything in the CNN
+    bool cnn;                       // anything in the CNN, the gradient of the input features (sir_model_train_bwd_x) included
     bool head, bptt[2];             // stages that run: the head, the BPTT of layer 0 / 1 (something trainable in it or below it)
     bool dz3, da2, dz2, da1;        // gradients of the CNN chain that somebody reads
 };
 
-BwdPlan bwd_plan(const sir_model_grads& g) {
+// dx: d(loss)/d(features) is wanted -- the data chain then runs to the bottom whatever `g` holds
+BwdPlan bwd_plan(const sir_model_grads& g, bool dx) {
     BwdPlan w;
     w.fc = g.fc_w || g.fc_b;
     w.attn = g.attn_w || g.attn_b;
@@ -75,14 +76,14 @@ BwdPlan bwd_plan(const sir_model_grads& g) {
         w.gru_b[l] = g.gru_b_ih[2 * l] || g.gru_b_ih[2 * l + 1] || g.gru_b_hh[2 * l] || g.gru_b_hh[2 * l + 1];
     }
     for (int i = 0; i < 3; ++i) { w.gb[i] = g.bn_w[i] || g.bn_b[i]; w.blk[i] = g.conv_w[i] || w.gb[i]; }
-    w.cnn = w.blk[0] || w.blk[1] || w.blk[2];
+    w.cnn = w.blk[0] || w.blk[1] || w.blk[2] || dx;
     w.bptt[0] = w.gru_w[0] || w.gru_b[0] || w.cnn;
     w.bptt[1] = w.gru_w[1] || w.gru_b[1] || w.gru_w[0] || w.gru_b[0] || w.cnn;
     w.head = w.fc || w.attn || w.bptt[1];
-    w.dz3 = g.conv_w[2] || w.blk[1] || w.blk[0];
-    w.da2 = w.blk[1] || w.blk[0];
-    w.dz2 = g.conv_w[1] || w.blk[0];
-    w.da1 = w.blk[0];
+    w.dz3 = g.conv_w[2] || w.blk[1] || w.blk[0] || dx;
+    w.da2 = w.blk[1] || w.blk[0] || dx;
+    w.dz2 = g.conv_w[1] || w.blk[0] || dx;
+    w.da1 = w.blk[0] || dx;
     return w;
 }
 
@@ -101,6 +102,7 @@ struct Bwd {
     bool two;                       // side is a stream of its own
     const sir_model_weights* w; const sir_model_grads* g; const sir_train_config* cfg;
     const float *feats, *dlogits, *y0in;      // y0in: what GRU layer 1 read (layer 0's output, behind the dropout if there is one)
+    float* dfeats;                  // d(loss)/d(feats) [B][64][T], or NULL: not wanted
     float dropout_p; uint64_t dropout_seed;
     TPtrs p; TDims d; BwdPlan want;
     float gscale, unscale;          // sir_bwd_loss_scale and its inverse
@@ -353,27 +355,44 @@ int bwd_conv2(Bwd& c) {
 
 // ---- conv1 block: ONE recompute pass: (sum dy, sum dy*xhat, sum dy*x_tap) per channel; the mean terms of dz = s (dy - m1 - xhat m2)
 // and with them the rest of dW1 are closed forms in the input moments of the forward (conv1_bwd_finalize_kernel, in double) ------
+// With dfeats (sir_model_train_bwd_x) the block's data gradient follows: conv1_bwd_data_kernel, the last link of the chain.
 int bwd_conv1(Bwd& c) {
     const TPtrs& p = c.p;
     const TDims& d = c.d;
     const sir_model_grads* g = c.g;
     const int B = d.B, T = d.T;
-    float* c1part = p.small + (size_t)B * 512 + B + 64;
-    SirProfScope prof(c.h, SIR_K_B_CONV1, c.st);
-    const dim3 g1(d.c1gx, d.c1gy, B);
-    const int nblk = d.c1gx * d.c1gy * B;
-    hipLaunchKernelGGL(conv1_bwd_kernel<2>, g1, dim3(256), 0, c.st, c.feats, c.w->conv_w[0], (const float*)p.da1, c.scale, c.shift,
-                       c.smean, c.sinv, (const float*)nullptr, (const float*)nullptr, c1part, 64, T, 32, d.wp1);
-    float* c1tmp = (float*)p.stats;           // [128][352] partial column sums, then [352] totals behind them
-    float* c1tot = c1tmp + 128 * 352;
-    hipLaunchKernelGGL(colsum_partial_kernel, dim3((352 + 63) / 64, 128), dim3(256), 0, c.st, (const float*)c1part, nblk, 352, 352, c1tmp);
-    hipLaunchKernelGGL(colsum_kernel, dim3((352 + 63) / 64), dim3(256), 0, c.st, (const float*)c1tmp, 128, 352, 352, c1tot);
-    if (c.cfg->bn_frozen[0])                             // frozen statistics: plain sums, no input moments
-        hipLaunchKernelGGL(conv1_bwd_finalize_frozen_kernel, dim3(1), dim3(320), 0, c.st, (const float*)c1tot, (const float*)c.scale, g->bn_w[0], g->bn_b[0],
-                           g->conv_w[0], c.unscale);
-    else
-        hipLaunchKernelGGL(conv1_bwd_finalize_kernel, dim3(1), dim3(320), 0, c.st, (const float*)c1tot, (const double*)p.c1m,
-                           c.w->conv_w[0], c.scale, c.smean, c.sinv, (double)B * 64 * T, g->bn_w[0], g->bn_b[0], g->conv_w[0], c.unscale);
+    const bool frozen = c.cfg->bn_frozen[0] != 0;
+    // the reduce pass feeds the three parameter gradients and, with live statistics, the two means of the data gradient's dz
+    if (c.want.blk[0] || (c.dfeats && !frozen)) {
+        float* c1part = p.small + (size_t)B * 512 + B + 64;
+        SirProfScope prof(c.h, SIR_K_B_CONV1, c.st);
+        const dim3 g1(d.c1gx, d.c1gy, B);
+        const int nblk = d.c1gx * d.c1gy * B;
+        hipLaunchKernelGGL(conv1_bwd_kernel<2>, g1, dim3(256), 0, c.st, c.feats, c.w->conv_w[0], (const float*)p.da1, c.scale, c.shift,
+                           c.smean, c.sinv, (const float*)nullptr, (const float*)nullptr, c1part, 64, T, 32, d.wp1);
+        float* c1tmp = (float*)p.stats;           // [128][352] partial column sums, then [352] totals behind them
+        float* c1tot = c1tmp + 128 * 352;
+        hipLaunchKernelGGL(colsum_partial_kernel, dim3((352 + 63) / 64, 128), dim3(256), 0, c.st, (const float*)c1part, nblk, 352, 352, c1tmp);
+        hipLaunchKernelGGL(colsum_kernel, dim3((352 + 63) / 64), dim3(256), 0, c.st, (const float*)c1tmp, 128, 352, 352, c1tot);
+        if (frozen)                                          // frozen statistics: plain sums, no input moments
+            hipLaunchKernelGGL(conv1_bwd_finalize_frozen_kernel, dim3(1), dim3(320), 0, c.st, (const float*)c1tot, (const float*)c.scale, g->bn_w[0], g->bn_b[0],
+                               g->conv_w[0], c.unscale);
+        else                                                 // (the means go to bn1's channels of TB_BNB, which nothing else uses)
+            hipLaunchKernelGGL(conv1_bwd_finalize_kernel, dim3(1), dim3(320), 0, c.st, (const float*)c1tot, (const double*)p.c1m,
+                               c.w->conv_w[0], c.scale, c.smean, c.sinv, (double)B * 64 * T, g->bn_w[0], g->bn_b[0], g->conv_w[0], c.unscale,
+                               c.dfeats ? c.mdy : (float*)nullptr, c.dfeats ? c.mdyx : (float*)nullptr);
+    }
+    if (c.dfeats) {
+        // data gradient: dz1 recomputed per tile, transposed 3x3 convolution onto the features (conv1_bwd_data_kernel)
+        SirProfScope prof(c.h, SIR_K_B_CONV1_DGRAD, c.st);
+        const dim3 gd((T + C1D_TW - 1) / C1D_TW, (64 + C1D_TH - 1) / C1D_TH, B);
+        if (frozen)
+            hipLaunchKernelGGL(conv1_bwd_data_kernel<true>, gd, dim3(256), 0, c.st, c.feats, c.w->conv_w[0], (const float*)p.da1, c.scale, c.shift,
+                               (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, c.dfeats, 64, T, 32, d.wp1, c.unscale);
+        else
+            hipLaunchKernelGGL(conv1_bwd_data_kernel<false>, gd, dim3(256), 0, c.st, c.feats, c.w->conv_w[0], (const float*)p.da1, c.scale, c.shift,
+                               c.smean, c.sinv, (const float*)c.mdy, (const float*)c.mdyx, c.dfeats, 64, T, 32, d.wp1, c.unscale);
+    }
     SIR_KCHECK();
     return SIR_OK;
 }
@@ -396,6 +415,13 @@ extern "C" int sir_model_train_bwd_cfg(sir_handle* h, const sir_model_weights* w
                                        int batch, int t_frames, float dropout_p, uint64_t dropout_seed,
                                        const sir_train_config* cfg, const sir_model_grads* g, void* workspace,
                                        size_t workspace_bytes, int part, void* stream_) {
+    return sir_model_train_bwd_x(h, w, feats, dlogits, batch, t_frames, dropout_p, dropout_seed, cfg, g, nullptr, workspace, workspace_bytes, part, stream_);
+}
+
+extern "C" int sir_model_train_bwd_x(sir_handle* h, const sir_model_weights* w, const float* feats, const float* dlogits,
+                                     int batch, int t_frames, float dropout_p, uint64_t dropout_seed,
+                                     const sir_train_config* cfg, const sir_model_grads* g, float* dfeats, void* workspace,
+                                     size_t workspace_bytes, int part, void* stream_) {
     if (!cfg) cfg = &kTrainAllLive;
     if (part != SIR_BWD_ALL && part != SIR_BWD_HEAD_GRU && part != SIR_BWD_CNN) {
         sir_set_error("sir_model_train_bwd_part: unknown part %d", part);
@@ -406,17 +432,21 @@ extern "C" int sir_model_train_bwd_cfg(sir_handle* h, const sir_model_weights* w
     int rc = check_common("sir_model_train_bwd", h, w, batch, t_frames, workspace, workspace_bytes, &c.d, off);
     if (rc != SIR_OK) return rc;
     if (!feats || !dlogits || !g) { sir_set_error("sir_model_train_bwd: NULL argument"); return SIR_EINVAL; }
+    if (dfeats && (((uintptr_t)dfeats & 3) != 0 || dfeats == feats)) {
+        sir_set_error("sir_model_train_bwd_x: dfeats must be a float buffer of its own");
+        return SIR_EINVAL;
+    }
     if (!h->bwd_side) {                                      // (first use: the only allocating step, as for the exchange buffers)
         SIR_HIP_TRY(hipStreamCreateWithFlags(&h->bwd_side, hipStreamNonBlocking));
         for (auto& e : h->bwd_ev) SIR_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
-    c.h = h; c.w = w; c.g = g; c.cfg = cfg; c.feats = feats; c.dlogits = dlogits;
+    c.h = h; c.w = w; c.g = g; c.cfg = cfg; c.feats = feats; c.dlogits = dlogits; c.dfeats = dfeats;
     c.dropout_p = dropout_p; c.dropout_seed = dropout_seed;
     c.st = (hipStream_t)stream_;
     c.two = h->bwd_side != nullptr && h->prof_mode != 1;
     c.side = c.two ? h->bwd_side : c.st;
     c.p = carve(workspace, off);
-    c.want = bwd_plan(*g);
+    c.want = bwd_plan(*g, dfeats != nullptr);
     c.gscale = sir_bwd_loss_scale(c.d.B);
     c.unscale = 1.0f / c.gscale;
     c.scale = c.p.bn; c.shift = c.p.bn + 224; c.smean = c.p.bn + 448; c.sinv = c.p.bn + 672;
@@ -432,7 +462,7 @@ extern "C" int sir_model_train_bwd_cfg(sir_handle* h, const sir_model_weights* w
         if (c.forked) SIR_TRY(c.mark_side());
         if (part == SIR_BWD_HEAD_GRU) return c.join();
     }
-    if (!c.want.cnn) {                                       // whole CNN frozen: the chain ended at layer 0's BPTT
+    if (!c.want.cnn) {                                       // whole CNN frozen, no input gradient: the chain ended at layer 0's BPTT
         SIR_KCHECK();
         return c.join();
     }

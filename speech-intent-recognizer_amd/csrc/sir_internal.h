@@ -29,8 +29,15 @@ enum SirKernelId {
     SIR_K_ADAM_EX, SIR_K_ADAM_EX_CLIPPED,
     // utterance segmentation of long recordings (vad.hip, appended): chunk energy, state machine (count + bases + table), clip gather
     SIR_K_VAD_ENERGY, SIR_K_VAD_SEGMENT, SIR_K_VAD_GATHER,
-    SIR_K_COUNT
+    SIR_K_COUNT,        // what sir_profile_kernel_count() returns: the ids of the paths every caller runs
+    // Extended ids (SIR_PROFILE_EXTRA_IDS of them, include/sir_hip.h), appended BEHIND the count: kernels that run only when a caller
+    // asks for something optional.  Callers that walk [0, count) -- the benchmark's roofline table, its per-kernel FLOP / byte
+    // tables -- never see them; sir_profile_kernel_name and sir_profile_collect serve them to callers that ask for count + extra.
+    // Gradient of the training step with respect to its input features (sir_model_train_bwd_x): conv1's data gradient
+    SIR_K_B_CONV1_DGRAD = SIR_K_COUNT,
+    SIR_K_COUNT_ALL
 };
+static_assert(SIR_K_COUNT_ALL - SIR_K_COUNT == SIR_PROFILE_EXTRA_IDS, "include/sir_hip.h: SIR_PROFILE_EXTRA_IDS");
 
 struct SirProfRec { int id; hipEvent_t e0, e1; };
 static inline size_t sir_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }

@@ -616,10 +616,13 @@ __global__ __launch_bounds__(256) void conv1_bwd_kernel(const float* __restrict_
 //   dW[c][tap] = s_c (A[tap] - m1 S[tap] - m2 invstd_c (sum_t w_c[t] R[t][tap] - mean_c S[tap])),   m1 = sum dy / N, m2 = sum dy*xhat / N
 // (dz = s (dy - m1 - xhat m2), xhat = (z - mean) invstd, z = sum_t w[t] x_t), evaluated in double; thread (c, 0) also writes
 // dbeta = sum dy and dgamma = sum dy*xhat.
+// m1_out / m2_out (both or neither; NULL = not wanted): the two means as floats, still carrying the loss scale, for
+// conv1_bwd_data_kernel.
 static __global__ void conv1_bwd_finalize_kernel(const float* __restrict__ totals, const double* __restrict__ M, const float* __restrict__ w,
                                                  const float* __restrict__ scale, const float* __restrict__ mean,
                                                  const float* __restrict__ invstd, double count, float* __restrict__ dgamma,
-                                                 float* __restrict__ dbeta, float* __restrict__ dw, float unscale) {
+                                                 float* __restrict__ dbeta, float* __restrict__ dw, float unscale,
+                                                 float* __restrict__ m1_out, float* __restrict__ m2_out) {
     const int idx = threadIdx.x;
     if (idx >= 288) return;
     const int c = idx / 9, tap = idx % 9;
@@ -629,7 +632,11 @@ static __global__ void conv1_bwd_finalize_kernel(const float* __restrict__ total
     for (int t = 0; t < 9; ++t) zx += (double)w[c * 9 + t] * M[t <= tap ? c1_r_index(t, tap) : c1_r_index(tap, t)];
     const double xhx = (double)invstd[c] * (zx - (double)mean[c] * M[tap]);
     if (dw) dw[c * 9 + tap] = (float)((double)scale[c] * (A - m1 * M[tap] - m2 * xhx)) * unscale;     // (NULL = not wanted)
-    if (tap == 0) { if (dbeta) dbeta[c] = (float)sdy * unscale; if (dgamma) dgamma[c] = (float)sdx * unscale; }
+    if (tap == 0) {
+        if (dbeta) dbeta[c] = (float)sdy * unscale;
+        if (dgamma) dgamma[c] = (float)sdx * unscale;
+        if (m1_out) { m1_out[c] = (float)m1; m2_out[c] = (float)m2; }
+    }
 }
 
 // frozen statistics: dz = s dy, so dW[c][tap] = s_c A[tap], dbeta = sum dy, dgamma = sum dy*xhat are plain sums of the same
@@ -644,6 +651,145 @@ static __global__ void conv1_bwd_finalize_frozen_kernel(const float* __restrict_
     if (tap == 0) {
         if (dbeta) dbeta[c] = totals[c * 11] * unscale;
         if (dgamma) dgamma[c] = totals[c * 11 + 1] * unscale;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// conv1 block DATA gradient: d(loss)/d(features), the last link of the chain (sir_model_train_bwd_x).
+//   dx[b][h][w] = unscale * sum_c sum_{kh,kw} w1[c][kh][kw] * dz1[b][c][h + 1 - kh][w + 1 - kw]        (dz1 = 0 outside the image)
+// dz1 is never stored in global memory.  A workgroup owns C1D_TH x C1D_TW input pixels of one utterance.  It stages the features of
+// its tile with a 3-pixel halo in LDS, then, for one half of the channels at a time:
+//   recompute -- thread = one 2x2 pooling window x 4 channels, windows aligned to even coordinates and covering the tile with a
+//     one-window halo: z1 as the forward's chain of nine fmas in tap order ky * 3 + kx, y = fma(z, scale, shift), the routing of
+//     conv1_bwd_kernel (route1: first maximum, strict >, blocked by the ReLU); one 16-byte read of da1 (channel-innermost NHWC)
+//     per thread and window;  dz = s (dy - m1 - xhat m2), or s dy with FROZEN statistics;  a pixel outside the image gets 0, a
+//     pixel of a column the pooling drops gets dy = 0;  dz goes to LDS as [pixel][16 channels + 4 pad] (the tile + 1 pixel around);
+//   gather -- thread = two vertically adjacent output pixels: 16 channels x 9 taps from 4 x 3 16-byte LDS reads per four channels
+//     (pixel stride 80 bytes: the 16 lanes of a ds_read_b128 group fall on 16 different 16-byte slots), weights from scalar loads.
+// Everything is summed in a fixed order: the result is bit-reproducible.  Output written, not accumulated, without the loss scale.
+// ------------------------------------------------------------------------------------------
+constexpr int C1D_TH = 16, C1D_TW = 32;                       // output tile (even: pooling windows stay whole)
+constexpr int C1D_XR = C1D_TH + 6, C1D_XC = C1D_TW + 6;       // feature tile with its 3-pixel halo
+constexpr int C1D_CR = C1D_TH / 2 + 2, C1D_CC = C1D_TW / 2 + 2;   // pooling windows with a one-window halo
+constexpr int C1D_ZR = C1D_TH + 2, C1D_ZC = C1D_TW + 2;       // dz pixels kept: the tile + 1 pixel around
+constexpr int C1D_ZS = 20;                                    // floats per dz pixel in LDS: 16 channels + 4 pad
+static_assert(C1D_TH * C1D_TW == 2 * 256, "two output pixels per thread");
+
+template <bool FROZEN>
+__global__ __launch_bounds__(256, 3) void conv1_bwd_data_kernel(const float* __restrict__ x, const float* __restrict__ w,
+                                                              const float* __restrict__ da, const float* __restrict__ scale,
+                                                              const float* __restrict__ shift, const float* __restrict__ mean,
+                                                              const float* __restrict__ invstd, const float* __restrict__ mdy,
+                                                              const float* __restrict__ mdyx, float* __restrict__ dx,
+                                                              int H, int W, int Hp, int Wp, float unscale) {
+    __shared__ float xt[C1D_XR * C1D_XC];
+    __shared__ __attribute__((aligned(16))) float dzs[C1D_ZR * C1D_ZC * C1D_ZS];
+    const int b = blockIdx.z, h0 = blockIdx.y * C1D_TH, w0 = blockIdx.x * C1D_TW;
+    const int tid = threadIdx.x;
+    const float* xb = x + (size_t)b * H * W;
+    for (int i = tid; i < C1D_XR * C1D_XC; i += 256) {
+        const int ty = i / C1D_XC, tx = i - ty * C1D_XC;
+        const int gy = h0 - 3 + ty, gx = w0 - 3 + tx;
+        xt[i] = (gy >= 0 && gy < H && gx >= 0 && gx < W) ? xb[(size_t)gy * W + gx] : 0.0f;
+    }
+    const int lc = tid & 31, rp = tid >> 5;                   // gather: output column, pair of output rows
+    float acc0 = 0.0f, acc1 = 0.0f;
+    constexpr int NIT = (C1D_CR * C1D_CC * 4 + 255) / 256;    // recompute items (window, 4 channels) per thread and channel half
+    for (int half = 0; half < 2; ++half) {
+        // ---- recompute: dz of 16 channels into LDS ----
+        const int c0 = half * 16 + (tid & 3) * 4;             // this thread's four channels (256 % 4 == 0: the same for all its items)
+        float4 g[NIT];
+        int wcy[NIT], wcx[NIT];
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {                    // all da1 reads of the half are issued first
+            const int cell = (it * 256 + tid) >> 2;
+            wcy[it] = cell / C1D_CC; wcx[it] = cell - wcy[it] * C1D_CC;
+            const int gcy = (h0 >> 1) - 1 + wcy[it], gcx = (w0 >> 1) - 1 + wcx[it];
+            const bool pooled = cell < C1D_CR * C1D_CC && gcy >= 0 && gcy < Hp && gcx >= 0 && gcx < Wp;
+            g[it] = pooled ? *reinterpret_cast<const float4*>(da + (((size_t)b * Hp + gcy) * Wp + gcx) * 32 + c0) : make_float4(0.f, 0.f, 0.f, 0.f);
+            if (!pooled) wcy[it] |= 0x100;                    // (bit 8: no pooled gradient for this window)
+            if (cell >= C1D_CR * C1D_CC) wcy[it] = -1;
+        }
+        float wk[4][9], s[4], t[4], mu[4], is[4], m1[4], m2[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+#pragma unroll
+            for (int i = 0; i < 9; ++i) wk[e][i] = w[(c0 + e) * 9 + i];
+            s[e] = scale[c0 + e]; t[e] = shift[c0 + e];
+            mu[e] = FROZEN ? 0.0f : mean[c0 + e]; is[e] = FROZEN ? 0.0f : invstd[c0 + e];
+            m1[e] = FROZEN ? 0.0f : mdy[c0 + e]; m2[e] = FROZEN ? 0.0f : mdyx[c0 + e];
+        }
+        __syncthreads();                                      // xt is staged (first half) / the last half's gather is done
+#pragma unroll
+        for (int it = 0; it < NIT; ++it) {
+            if (wcy[it] < 0) continue;
+            const bool pooled = !(wcy[it] & 0x100);
+            const int cy = wcy[it] & 0xff, cx = wcx[it];
+            float in[4][4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) in[r][k] = xt[(2 * cy + r) * C1D_XC + 2 * cx + k];
+            const float gv[4] = {g[it].x, g[it].y, g[it].z, g[it].w};
+            float o[4][4];                                    // [window pixel][channel]
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float a[4], yv[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    float v = 0.0f;
+#pragma unroll
+                    for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+                        for (int kx = 0; kx < 3; ++kx) v = fmaf(in[(q >> 1) + ky][(q & 1) + kx], wk[e][ky * 3 + kx], v);
+                    a[q] = v;
+                    yv[q] = fmaf(v, s[e], t[e]);
+                }
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float dyq = pooled ? route1(yv[0], yv[1], yv[2], yv[3], q, gv[e]) : 0.0f;
+                    if (FROZEN) o[q][e] = s[e] * dyq;
+                    else { const float xh = (a[q] - mu[e]) * is[e]; o[q][e] = s[e] * (dyq - m1[e] - xh * m2[e]); }
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int zr = 2 * cy - 1 + (q >> 1), zc = 2 * cx - 1 + (q & 1);      // pixel (h0 - 1 + zr, w0 - 1 + zc)
+                if (zr < 0 || zr >= C1D_ZR || zc < 0 || zc >= C1D_ZC) continue;
+                const int gy = h0 - 1 + zr, gx = w0 - 1 + zc;
+                const bool inside = gy >= 0 && gy < H && gx >= 0 && gx < W;
+                *reinterpret_cast<float4*>(&dzs[(zr * C1D_ZC + zc) * C1D_ZS + (tid & 3) * 4]) =
+                    inside ? make_float4(o[q][0], o[q][1], o[q][2], o[q][3]) : make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+        }
+        __syncthreads();
+        // ---- gather: rows 2 rp, 2 rp + 1 of the tile, column lc; dz rows 2 rp .. 2 rp + 3, columns lc .. lc + 2 ----
+#pragma unroll
+        for (int c4 = 0; c4 < 4; ++c4) {
+            float4 v[4][3];
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int k = 0; k < 3; ++k) v[r][k] = *reinterpret_cast<const float4*>(&dzs[((2 * rp + r) * C1D_ZC + lc + k) * C1D_ZS + c4 * 4]);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float* wc = w + (half * 16 + c4 * 4 + e) * 9;      // (uniform address: scalar loads)
+#pragma unroll
+                for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+                    for (int kw = 0; kw < 3; ++kw) {
+                        const float wv = wc[kh * 3 + kw];
+                        const float4 u0 = v[2 - kh][2 - kw], u1 = v[3 - kh][2 - kw];
+                        acc0 = fmaf(wv, e == 0 ? u0.x : (e == 1 ? u0.y : (e == 2 ? u0.z : u0.w)), acc0);
+                        acc1 = fmaf(wv, e == 0 ? u1.x : (e == 1 ? u1.y : (e == 2 ? u1.z : u1.w)), acc1);
+                    }
+            }
+        }
+    }
+    const int gx = w0 + lc, gy = h0 + 2 * rp;
+    if (gx < W) {
+        if (gy < H) dx[((size_t)b * H + gy) * W + gx] = acc0 * unscale;
+        if (gy + 1 < H) dx[((size_t)b * H + gy + 1) * W + gx] = acc1 * unscale;
     }
 }
 

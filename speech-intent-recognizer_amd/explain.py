@@ -1,0 +1,106 @@
+"""Gradients of ``CNNAudioGRU`` with respect to its input features: saliency maps and FGSM-style robustness checks.
+
+Everything here runs the model with EVAL semantics on the differentiable path -- all three BatchNorms on their running
+statistics, no inter-layer dropout, no parameter gradient -- whatever mode the module is in, and leaves the module as it
+found it: sub-module flags, running statistics, ``num_batches_tracked``, the dropout step counter, cached weight layouts
+and every ``p.grad`` are untouched.  The forward is ``sir_model_train_fwd_cfg`` with ``bn_frozen = {1, 1, 1}``, the backward
+``sir_model_train_bwd_x`` with all 29 gradient pointers NULL: the data chain alone, down through conv1
+(``conv1_bwd_data_kernel``).  With frozen statistics the clips of a batch do not see each other, so row ``b`` of every
+result is what clip ``b`` gives on its own.
+
+Arguments are validated before any device call; there is no CPU path and no ragged (``lengths=``) form.
+"""
+import torch
+
+from . import _native
+
+
+def _frozen_cfg():
+    cfg = _native.TrainConfig()
+    for i in range(3):
+        cfg.bn_frozen[i] = 1
+    return cfg
+
+
+def _on_device(model, x):
+    return x.is_cuda and next(model.parameters()).is_cuda
+
+
+def _validate(model, x, lengths):
+    if lengths is not None:
+        raise ValueError("lengths= (ragged batches) is not available on the differentiable path: pass clips of one length")
+    if not torch.is_tensor(x) or x.dtype != torch.float32:
+        raise ValueError("x must be a float32 tensor [B,64,T] or [B,1,64,T]")
+    shape = tuple(x.shape)
+    if not ((len(shape) == 3 and shape[1] == 64) or (len(shape) == 4 and shape[1] == 1 and shape[2] == 64)) or shape[-1] < 8:
+        raise ValueError(f"expected [B,64,T] or [B,1,64,T] with T >= 8, got {shape}")
+    if not _on_device(model, x):
+        raise _native.SirError("tensor is not on a HIP device: this path runs on MI355X only (no CPU fallback)")
+
+
+def _index_vector(v, bsz, name):
+    """``target`` / ``labels``: an integer tensor (or list) with one entry per clip."""
+    if not torch.is_tensor(v):
+        v = torch.as_tensor(list(v))
+    if v.is_floating_point() or v.dtype == torch.bool:
+        raise ValueError(f"{name} must be an integer tensor")
+    if v.dim() != 1 or v.numel() != bsz:
+        raise ValueError(f"{name} must hold one class index per clip: got shape {tuple(v.shape)} for a batch of {bsz}")
+    return v
+
+
+def _forward(model, x):
+    """logits of the eval-semantics differentiable forward and the leaf they hang on (``x`` detached, in its own shape)."""
+    from . import train_ops
+    leaf = x.detach().requires_grad_(True)
+    with torch.enable_grad():
+        # (detached parameters: the node sees no parameter that wants a gradient)
+        logits = train_ops._TrainStep.apply(leaf, model, (_frozen_cfg(), 0.0, False), *[p.detach() for p in train_ops.param_list(model)])
+    return logits, leaf
+
+
+def input_gradient(model, x, target=None, lengths=None):
+    """``(logits, dx)`` with ``dx[b] = d logits[b, target[b]] / d x[b]`` in the shape of ``x``.  ``target``: int tensor
+    ``[B]``; ``None`` = each row's own argmax.  ``logits`` are those of ``model.eval()(x)`` (detached)."""
+    _validate(model, x, lengths)
+    bsz = x.shape[0]
+    if target is not None:
+        target = _index_vector(target, bsz, "target")
+        if not target.is_cuda:
+            ncls = model.fc.weight.shape[0]
+            bad = [(i, int(v)) for i, v in enumerate(target.tolist()) if not 0 <= int(v) < ncls]
+            if bad:
+                raise ValueError(f"target outside [0, {ncls}) (clip, class): {bad[:8]}")
+    logits, leaf = _forward(model, x)
+    if target is None:
+        target = logits.detach().argmax(dim=1)
+    target = target.to(device=x.device, dtype=torch.int64)
+    # the backward's internal loss scale is 2^8 x batch (rounded up to a power of two), sized for the 1 / batch of a mean loss:
+    # the one-hot seed carries that power of two, and the result gives it back -- both exact
+    k = (bsz - 1).bit_length()
+    seed = torch.zeros_like(logits).scatter_(1, target[:, None], 2.0 ** -k)
+    (dx,) = torch.autograd.grad(logits, leaf, grad_outputs=seed)
+    return logits.detach(), dx.mul_(2.0 ** k)
+
+
+def saliency(model, x, target=None, lengths=None):
+    """Gradient x input, ``|dx * x|``, shape ``[B,64,T]``: which part of the spectrogram decided ``target`` (default: the
+    predicted intent)."""
+    _, dx = input_gradient(model, x, target, lengths)
+    return (dx * x.detach()).abs_().view(x.shape[0], 64, x.shape[-1])
+
+
+def fgsm(model, x, labels, eps, lengths=None):
+    """The fast-gradient-sign adversarial example ``x + eps * sign(d CE(model(x), labels) / d x)`` (Goodfellow et al. 2015),
+    in the shape of ``x``; the cross-entropy is the mean over the batch (``fused_cross_entropy``)."""
+    eps = float(eps)
+    if not eps >= 0.0:
+        raise ValueError("eps must be >= 0")
+    _validate(model, x, lengths)
+    labels = _index_vector(labels, x.shape[0], "labels")
+    from . import train_ops
+    logits, leaf = _forward(model, x)
+    with torch.enable_grad():
+        loss = train_ops.fused_cross_entropy(logits, labels.to(x.device))
+    (dx,) = torch.autograd.grad(loss, leaf)
+    return x.detach() + eps * dx.sign_()

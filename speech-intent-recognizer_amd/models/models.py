@@ -69,7 +69,10 @@ class CNNAudioGRU(nn.Module):
         batch of mixed-length clips in one launch sequence.
 
         ``self.training and torch.is_grad_enabled()`` selects the differentiable path, as before; ``model.eval()`` keeps
-        calling ``sir_model_infer``.  Inside the differentiable path the sub-modules are consulted the way torch consults
+        calling ``sir_model_infer``.  The differentiable path is differentiable with respect to the 29 parameters and, if
+        ``x.requires_grad``, with respect to ``x``: ``x.grad`` has the shape of ``x`` (``sir_model_train_bwd_x``; rank-local under
+        data parallelism; a double backward raises).  For the input gradient of a model in ``eval()`` mode -- saliency, FGSM --
+        see ``sir_amd.explain``.  Inside the differentiable path the sub-modules are consulted the way torch consults
         them: ``bnK.training == False`` uses (and keeps) that block's running statistics, ``gru.training == False`` turns the
         inter-layer dropout off, and parameters with ``requires_grad == False`` receive no gradient and cost no backward
         work where it can be skipped.  With every sub-module in training mode and every parameter trainable nothing changes."""

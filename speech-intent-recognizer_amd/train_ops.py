@@ -4,6 +4,8 @@
 autograd the 29 parameter gradients as views of ONE flat fp32 buffer (3 261 184 elements); with
 ``WORLD_SIZE > 1`` that buffer is averaged over ranks with a single RCCL all-reduce before the
 views are returned, so the update equals single-GPU training on the global batch.
+If ``x.requires_grad`` the backward also returns ``d loss / d x`` (``sir_model_train_bwd_x``: the
+data chain runs down through conv1); it is rank-local and is not exchanged.
 ``fused_cross_entropy`` is the HIP form of the reference's ``nn.CrossEntropyLoss()`` (train.py:242).
 Only pointers move through Python; no arithmetic of the step is done by torch ops.
 """
@@ -11,6 +13,7 @@ import ctypes as C
 import os
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _native, ops
 from .dist_utils import (ShardSampler, all_reduce_mean_, all_reduce_sum_, broadcast_module_,  # noqa: F401
@@ -188,9 +191,14 @@ def _bn_ptr_arrays(mod):
 
 class _TrainStep(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, mod, dropout_p, *params):
+    def forward(ctx, x, mod, opts, *params):
+        # opts = (sir_train_config, dropout p, step): step == False (sir_amd.explain) draws no dropout key and leaves the
+        # step counter and ``mod._sir_last_dropout`` alone
+        cfg, dropout_p, step = opts
         lib = _native.lib()
         h = get_featurizer().handle
+        x_shape = x.shape
+        x = ops._as_features(x)
         bsz, _, t = x.shape
         st = _train_state(mod)
         need = lib.sir_model_workspace_bytes(h, bsz, t, 1)
@@ -200,9 +208,10 @@ class _TrainStep(torch.autograd.Function):
         w, keep = ops.cached_weights(mod)
         rm, rv = _bn_ptr_arrays(mod)
         logits = torch.empty((bsz, w.num_classes), dtype=torch.float32, device=x.device)
-        cfg = bn_config(mod)
-        seed = dropout_seed(next(_seed_counter))
-        mod._sir_last_dropout = (seed, float(dropout_p))      # lets tests rebuild the mask (tests/dropout_host.py)
+        seed = 0
+        if step:
+            seed = dropout_seed(next(_seed_counter))
+            mod._sir_last_dropout = (seed, float(dropout_p))  # lets tests rebuild the mask (tests/dropout_host.py)
         momentum = float(mod.bn1.momentum if mod.bn1.momentum is not None else 0.1)
         rc = lib.sir_model_train_fwd_cfg(h, C.byref(w), rm, rv, x.data_ptr(), bsz, t, momentum, float(dropout_p), seed,
                                          C.byref(cfg), logits.data_ptr(), ws.data_ptr(), ws.numel(),
@@ -213,9 +222,11 @@ class _TrainStep(torch.autograd.Function):
             ops.bump_weights_epoch()                 # BN running statistics were updated in place
             torch._foreach_add_(live, 1)
         ctx.mod, ctx.x, ctx.seed, ctx.dropout_p, ctx.ws, ctx.cfg = mod, x, seed, float(dropout_p), ws, cfg
+        ctx.x_shape = x_shape
         return logits
 
     @staticmethod
+    @once_differentiable
     def backward(ctx, dlogits):
         lib = _native.lib()
         mod, x = ctx.mod, ctx.x
@@ -226,38 +237,55 @@ class _TrainStep(torch.autograd.Function):
         bsz, _, t = x.shape
         grads = st["grads"]
         params = param_list(mod)
+        need = ctx.needs_input_grad[3:]
+        # d loss / d x, returned in the caller's shape ([B,64,T] and [B,1,64,T] are the same memory); None: not wanted
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+
+        def run(part):
+            if dx is None:
+                rc = lib.sir_model_train_bwd_cfg(h, C.byref(w), x.data_ptr(), dlogits.data_ptr(), bsz, t, ctx.dropout_p, ctx.seed,
+                                                 C.byref(ctx.cfg), C.byref(gstruct), ctx.ws.data_ptr(), ctx.ws.numel(), part,
+                                                 _native.current_stream_ptr())
+                return _native.check(rc, "sir_model_train_bwd_cfg")
+            rc = lib.sir_model_train_bwd_x(h, C.byref(w), x.data_ptr(), dlogits.data_ptr(), bsz, t, ctx.dropout_p, ctx.seed,
+                                           C.byref(ctx.cfg), C.byref(gstruct), dx.data_ptr(),
+                                           ctx.ws.data_ptr(), ctx.ws.numel(), part, _native.current_stream_ptr())
+            _native.check(rc, "sir_model_train_bwd_x")
+
+        if not any(need):
+            # only the input gradient is wanted: no parameter gradient is written, so nothing is exchanged between ranks
+            # and no .grad is touched
+            gstruct, _ = grads.struct_for(need)
+            run(_native.BWD_ALL)
+            return (dx.view(ctx.x_shape), None, None) + (None,) * len(params)
         # a .grad left over from the previous step that still aliases the flat buffer (no zero_grad in between:
         # gradient accumulation) must be detached from it before the kernels overwrite the buffer
         for p, v in zip(params, grads.views):
             if p.grad is not None and p.grad.data_ptr() == v.data_ptr():
                 p.grad = p.grad.clone()
 
-        need = ctx.needs_input_grad[3:]
         gstruct, cnn = grads.struct_for(need)        # only the trainable views: NULL = not wanted, not computed
         if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
             _check_same_freeze(need, ctx.cfg)
 
-        def run(part):
-            rc = lib.sir_model_train_bwd_cfg(h, C.byref(w), x.data_ptr(), dlogits.data_ptr(), bsz, t, ctx.dropout_p, ctx.seed,
-                                             C.byref(ctx.cfg), C.byref(gstruct), ctx.ws.data_ptr(), ctx.ws.numel(), part,
-                                             _native.current_stream_ptr())
-            _native.check(rc, "sir_model_train_bwd_cfg")
-
-        _exchange_and_scale(grads, run, cnn=cnn)
+        _exchange_and_scale(grads, run, cnn=cnn, dx=dx is not None)
+        dx = dx.view(ctx.x_shape) if dx is not None else None
         if HAND_OVER_GRADS and all(p.grad is None and not _has_grad_hooks(p) for p in params):
             # zero_grad(set_to_none=True) (train.py:90): the views of the flat buffer BECOME the .grad tensors; returning
             # them through autograd would make AccumulateGrad clone all 29 of them (29 copy launches per step)
             for p, v, n in zip(params, grads.views, need):
                 if n:
                     p.grad = v
-            return (None, None, None) + (None,) * len(params)
-        return (None, None, None) + tuple(v if n else None for v, n in zip(grads.views, need))
+            return (dx, None, None) + (None,) * len(params)
+        return (dx, None, None) + tuple(v if n else None for v, n in zip(grads.views, need))
 
 
-def _exchange_and_scale(grads, run, cnn=True):
+def _exchange_and_scale(grads, run, cnn=True, dx=False):
     """The per-step gradient exchange around the two halves of the backward (``run(part)`` launches one half, or
     nothing for a rank that has no batch).  ``cnn=False`` (every conv / BatchNorm parameter frozen): the second half and
-    its bucket are left out -- on every rank alike, ``zero_contribution_step`` included."""
+    its bucket are left out -- on every rank alike, ``zero_contribution_step`` included.  ``dx=True`` (the gradient of
+    the input features is wanted): the second half runs even then -- it writes that gradient, which stays on its rank --
+    but its bucket is still left out."""
     import torch.distributed as dist
     world = world_size()
     forced = FORCE_EXCHANGE and dist.is_available() and dist.is_initialized()
@@ -267,8 +295,9 @@ def _exchange_and_scale(grads, run, cnn=True):
         run(_native.BWD_HEAD_GRU)
         tail = grads.flat[grads.n_cnn:]
         work = dist.all_reduce(tail, op=dist.ReduceOp.SUM, async_op=True)
-        if cnn:
+        if cnn or dx:
             run(_native.BWD_CNN)
+        if cnn:
             dist.all_reduce(grads.flat[:grads.n_cnn], op=dist.ReduceOp.SUM)
         work.wait()
         (grads.flat if cnn else tail).mul_(1.0 / world)
@@ -303,13 +332,14 @@ def zero_contribution_step(mod):
 
 def forward_train(mod, x):
     """Training-mode forward of ``CNNAudioGRU`` (batch-statistics BN, inter-layer dropout
-    ``mod.gru.dropout``), differentiable wrt the module's parameters.  The sub-modules' own flags are honoured as torch
+    ``mod.gru.dropout``), differentiable wrt the module's parameters and, if ``x.requires_grad``, wrt ``x`` (``x.grad`` has
+    the shape of ``x``; a double backward raises).  The sub-modules' own flags are honoured as torch
     honours them: ``bnK.eval()`` freezes that block's statistics (forward and backward), ``gru.eval()`` turns the dropout
     off, and a parameter with ``requires_grad == False`` gets no gradient -- the backward stops where the trainable
     parameters stop (``sir_model_train_bwd_cfg``)."""
     _native.require_hip(x)
-    x = ops._as_features(x)
-    return _TrainStep.apply(x, mod, step_config(mod)[1], *param_list(mod))
+    ops._as_features(x)                              # (shape / dtype checks; the node itself takes x in the caller's shape)
+    return _TrainStep.apply(x, mod, step_config(mod) + (True,), *param_list(mod))
 
 
 class _FusedCE(torch.autograd.Function):

@@ -143,6 +143,30 @@ int sir_features_fwd(sir_handle* h, const void* wave, int wave_dtype, int64_t wa
                      float* db_out, void* workspace, size_t workspace_bytes, const sir_augment* aug,
                      void* stream);
 
+/* sir_features_bwd: the gradient of sir_features_fwd's `out` with respect to the waveform -- the chain z-norm, dB, mel filterbank,
+ * power spectrum, real FFT, Hann window, framing with reflect padding, time shift -- in one launch (feat_utt_bwd_kernel:
+ * DESIGN.md "Gradients down to the waveform").  The reference has no such path; torch autograd through the same operations
+ * is the arithmetic it restates.  Asynchronous on `stream`; allocates nothing, uses no atomics and no workspace; bit-reproducible,
+ * and row b depends on nothing but row b.
+ *   wave, wave_dtype, wave_stride, lengths, max_len, t_pad, aug: exactly what the matching sir_features_fwd call got (lengths
+ *            are clamped to max_len; noise is regenerated from aug->noise_seed, so the spectra are the forward's)
+ *   db     : [batch][n_mels][t_pad] f32, the db_out that forward call wrote (required)
+ *   dout   : [batch][n_mels][t_pad] f32, d loss / d out; entries in frames beyond the clip and in the SpecAugment bands of `aug`
+ *            are ignored (those outputs are the constant 0 -- their positions still count in the statistics)
+ *   dwave  : [batch][dwave_stride] f32, dwave_stride >= max_len; row b receives d loss / d sample for samples [0, lengths[b])
+ *            (for PCM16 with respect to the dequantised s / 32768) and exact zeros in [lengths[b], max_len); written, not
+ *            accumulated; columns >= max_len are not touched.  A clip with length <= n_fft/2 gives a zero row.
+ * The statistics run over all frames of a clip and db holds t_pad of them: 1 + max_len / hop > t_pad is SIR_EUNSUPPORTED (no
+ * partial answer).  A filterbank (sir_feature_config.mel_fb) with an FFT bin under more than two filters is SIR_EUNSUPPORTED.
+ * Departures from autograd: where the mel power is at or below the 1e-10 clamp the gradient is 0 (the forward's own test), and a
+ * clip whose dB tile is constant (sigma == 0, e.g. digital silence) gets dD = (g - mean g) / 1e-5 with the sigma term dropped,
+ * where torch returns NaN.  NULL pointers, a bad dtype, misaligned pointers and strides < max_len are SIR_EINVAL; every
+ * argument is checked before anything is launched. */
+int sir_features_bwd(sir_handle* h, const void* wave, int wave_dtype, int64_t wave_stride,
+                     const int32_t* lengths, int batch, int max_len,
+                     const float* db, const float* dout, int t_pad, const sir_augment* aug,
+                     float* dwave, int64_t dwave_stride, void* stream);
+
 /* ---- batch assembly from an HBM-resident feature store -----------------------------------------
  * sir_gather_features replaces, for a whole batch in one launch, what the reference does per item in DataLoader worker
  * processes and then copies over PCIe: FSCIntentDataset.__getitem__ (scripts/dataset.py:78-115: cache lookup, SpecAugment,

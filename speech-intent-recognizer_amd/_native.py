@@ -14,6 +14,8 @@ LIB_PATH = os.path.join(_HERE, "lib", "libsir_hip.so")
 CSRC_DIR = os.path.join(_HERE, "csrc")
 
 SIR_OK = 0
+SIR_EINVAL = -1
+SIR_EUNSUPPORTED = -4
 SIR_ETIMEOUT = -5
 WAVE_F32, WAVE_I16 = 0, 1
 BWD_ALL, BWD_HEAD_GRU, BWD_CNN = 0, 1, 2
@@ -70,6 +72,8 @@ SIGNATURES = {
     "sir_features_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int,
                                    C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(Augment),
                                    C.c_void_p]),
+    "sir_features_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int,
+                                   C.c_void_p, C.c_void_p, C.c_int, C.POINTER(Augment), C.c_void_p, C.c_int64, C.c_void_p]),
     "sir_mix_to_mono": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                   C.c_int64, C.c_void_p]),
     "sir_resample_out_len": (C.c_int, [C.c_int, C.c_int, C.c_int]),

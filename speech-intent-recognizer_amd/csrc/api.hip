@@ -55,6 +55,7 @@ extern "C" int sir_create(const sir_feature_config* cfg, sir_handle** out) {
     h->weights_version = 0; h->prep_next = 0;
     for (auto& e : h->prep) { e.ws = nullptr; e.version = 0; e.key = -1; }
     h->tw512 = nullptr; h->tw1024 = nullptr; h->window = nullptr; h->melw = nullptr; h->mel_desc = nullptr;
+    h->mel_taps = nullptr; h->mel_max_cover = 0;
     h->status = nullptr;
     h->cluster_done = nullptr; h->cluster_stream = nullptr; h->cluster_pending = false;
     h->cluster_seen = false; h->cluster_multi = false; h->cluster_run = 0;
@@ -125,6 +126,20 @@ extern "C" int sir_create(const sir_feature_config* cfg, sir_handle** out) {
         return SIR_EUNSUPPORTED;
     }
     h->mel_nnz = (int)melw.size();
+    // transposed for the gradient (sir_features_bwd): the filters over each bin, ascending; neighbouring triangles overlap in pairs
+    struct Tap { int fa; float wa; int fb; float wb; };
+    std::vector<Tap> taps(SIR_NFREQ, Tap{0, 0.0f, 0, 0.0f});
+    for (int k = 0; k < SIR_NFREQ; ++k) {
+        int cover = 0;
+        for (int j = 0; j < nm; ++j) {
+            const float w = fb[(size_t)k * nm + j];
+            if (w == 0.0f) continue;
+            if (cover == 0) { taps[k].fa = j; taps[k].wa = w; }
+            else if (cover == 1) { taps[k].fb = j; taps[k].wb = w; }
+            ++cover;
+        }
+        h->mel_max_cover = std::max(h->mel_max_cover, cover);
+    }
     melw.resize((melw.size() + 3) / 4 * 4 + 4, 0.0f);
 
     int rc = upload(&h->tw512, tw512);
@@ -132,6 +147,7 @@ extern "C" int sir_create(const sir_feature_config* cfg, sir_handle** out) {
     if (rc == SIR_OK) rc = upload(&h->window, window);
     if (rc == SIR_OK) rc = upload(&h->melw, melw);
     if (rc == SIR_OK) rc = upload(&h->mel_desc, desc);
+    if (rc == SIR_OK) rc = upload((Tap**)&h->mel_taps, taps);
     if (rc == SIR_OK) rc = upload(&h->status, std::vector<unsigned int>(64, 0u));
     if (rc == SIR_OK) rc = upload(&h->zero_page, std::vector<float>(1024, 0.0f));
     if (rc == SIR_OK) {
@@ -147,7 +163,7 @@ extern "C" int sir_create(const sir_feature_config* cfg, sir_handle** out) {
 extern "C" int sir_destroy(sir_handle* h) {
     if (!h) return SIR_OK;
     (void)hipFree(h->tw512); (void)hipFree(h->tw1024); (void)hipFree(h->window);
-    (void)hipFree(h->melw); (void)hipFree(h->mel_desc); (void)hipFree(h->status);
+    (void)hipFree(h->melw); (void)hipFree(h->mel_desc); (void)hipFree(h->mel_taps); (void)hipFree(h->status);
     if (h->cluster_done) (void)hipEventDestroy(h->cluster_done);
     if (h->bwd_side) { (void)hipStreamSynchronize(h->bwd_side); (void)hipStreamDestroy(h->bwd_side); }
     for (auto e : h->bwd_ev) if (e) (void)hipEventDestroy(e);
@@ -166,6 +182,13 @@ extern "C" int sir_features_fwd(sir_handle* h, const void* wave, int wave_dtype,
                                 void* stream) {
     return sir_features_launch(h, wave, wave_dtype, wave_stride, lengths, batch, max_len, out, t_pad, db_out,
                                workspace, workspace_bytes, aug, (hipStream_t)stream);
+}
+
+extern "C" int sir_features_bwd(sir_handle* h, const void* wave, int wave_dtype, int64_t wave_stride,
+                                const int32_t* lengths, int batch, int max_len, const float* db, const float* dout,
+                                int t_pad, const sir_augment* aug, float* dwave, int64_t dwave_stride, void* stream) {
+    return sir_features_bwd_launch(h, wave, wave_dtype, wave_stride, lengths, batch, max_len, db, dout, t_pad, aug, dwave,
+                                   dwave_stride, (hipStream_t)stream);
 }
 
 extern "C" int sir_model_set_weights_version(sir_handle* h, uint64_t version) {

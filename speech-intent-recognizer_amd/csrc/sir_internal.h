@@ -71,6 +71,10 @@ struct sir_handle {
     float* melw;        // compact filter weights: filter after filter, taps ascending in frequency (mel_nnz floats)
     int4* mel_desc;     // [64] per slot, filters sorted by tap count: {filter (-1 = unused), first FFT bin, taps, offset into melw}
     int mel_nnz;
+    // the filterbank transposed for sir_features_bwd: per FFT bin the (at most) two filters that cover it, {filter, weight, filter,
+    // weight} (int, float, int, float; weight 0 = none), [513]; mel_max_cover = filters on the busiest bin (the kernel serves <= 2)
+    void* mel_taps;
+    int mel_max_cover;
     std::vector<sir_resample_table> resample_tables;   // built on first use of a rate pair
     // device word set to 1 by a GRU recurrence kernel whose inter-workgroup exchange timed out (its results are then
     // invalid); zeroed at creation, read and cleared by sir_check_status / sir_profile_collect
@@ -228,6 +232,9 @@ int sir_features_launch(sir_handle* h, const void* wave, int wave_dtype, int64_t
                         const int32_t* lengths, int batch, int max_len, float* out, int t_pad,
                         float* db_out, void* workspace, size_t workspace_bytes, const sir_augment* aug,
                         hipStream_t stream);
+int sir_features_bwd_launch(sir_handle* h, const void* wave, int wave_dtype, int64_t wave_stride, const int32_t* lengths,
+                            int batch, int max_len, const float* db, const float* dout, int t_pad, const sir_augment* aug,
+                            float* dwave, int64_t dwave_stride, hipStream_t stream);
 
 // GRU recurrences (gru_quad.hip: forward and BPTT, clusters of four workgroups on the matrix cores).  Both write h->status if an
 // exchange spin times out.  nlive (forward, optional): per-utterance step count past which gi rows come from utterance B, or -- `ragged` --

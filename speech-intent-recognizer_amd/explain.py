@@ -1,4 +1,5 @@
-"""Gradients of ``CNNAudioGRU`` with respect to its input features: saliency maps and FGSM-style robustness checks.
+"""Gradients of ``CNNAudioGRU`` with respect to its input features -- and, through the feature extractor, its input waveform:
+saliency maps and FGSM-style robustness checks.
 
 Everything here runs the model with EVAL semantics on the differentiable path -- all three BatchNorms on their running
 statistics, no inter-layer dropout, no parameter gradient -- whatever mode the module is in, and leaves the module as it
@@ -7,6 +8,10 @@ and every ``p.grad`` are untouched.  The forward is ``sir_model_train_fwd_cfg`` 
 ``sir_model_train_bwd_x`` with all 29 gradient pointers NULL: the data chain alone, down through conv1
 (``conv1_bwd_data_kernel``).  With frozen statistics the clips of a batch do not see each other, so row ``b`` of every
 result is what clip ``b`` gives on its own.
+
+The ``*_wave`` forms start from audio: features by ``sir_features_fwd`` (no augmentation), the model as above, then
+``sir_features_bwd`` carries ``dx`` down to the samples.  Their ``lengths`` are SAMPLE counts of zero-padded clips (what the
+featurizer takes), not the ragged model path; every clip must fit ``t_pad`` frames (``1 + L // 512 <= t_pad``).
 
 Arguments are validated before any device call; there is no CPU path and no ragged (``lengths=``) form.
 """
@@ -104,3 +109,76 @@ def fgsm(model, x, labels, eps, lengths=None):
         loss = train_ops.fused_cross_entropy(logits, labels.to(x.device))
     (dx,) = torch.autograd.grad(loss, leaf)
     return x.detach() + eps * dx.sign_()
+
+
+# ---- down to the waveform -------------------------------------------------------------------------------------------------
+def _class_vector(model, v, bsz, name):
+    """``_index_vector`` plus, for a host tensor, the range check (a device tensor is checked by the loss kernel / scatter)."""
+    v = _index_vector(v, bsz, name)
+    if not v.is_cuda:
+        ncls = model.fc.weight.shape[0]
+        bad = [(i, int(c)) for i, c in enumerate(v.tolist()) if not 0 <= int(c) < ncls]
+        if bad:
+            raise ValueError(f"{name} outside [0, {ncls}) (clip, class): {bad[:8]}")
+    return v
+
+
+def _validate_wave(model, wave, lengths, t_pad):
+    from . import featurizer
+    if not torch.is_tensor(wave) or wave.dtype != torch.float32 or wave.dim() != 2 or wave.shape[0] < 1 or wave.shape[1] < 1:
+        raise ValueError("wave must be a float32 tensor [B, L] (dequantise PCM16 first: wave.float() / 32768)")
+    t_pad = int(t_pad)
+    if t_pad < 8 or 1 + wave.shape[1] // featurizer.HOP > t_pad:
+        raise ValueError(f"clips of {wave.shape[1]} samples have {1 + wave.shape[1] // featurizer.HOP} frames: t_pad must be "
+                         f"at least that and >= 8 (got {t_pad})")
+    if lengths is not None:
+        lengths = _index_vector(lengths, wave.shape[0], "lengths")
+    if not _on_device(model, wave):
+        raise _native.SirError("tensor is not on a HIP device: this path runs on MI355X only (no CPU fallback)")
+    return lengths.to(device=wave.device, dtype=torch.int32) if lengths is not None else None, t_pad
+
+
+def _wave_features(wave, lengths, t_pad):
+    from . import featurizer
+    fz = featurizer.get_featurizer()
+    wave = wave.detach().contiguous()
+    db = torch.empty((wave.shape[0], fz.n_mels, t_pad), dtype=torch.float32, device=wave.device)
+    return fz, wave, fz(wave, lengths, t_pad=t_pad, db_out=db), db
+
+
+def wave_gradient(model, wave, lengths=None, target=None, t_pad=200):
+    """``(logits, dwave)`` with ``dwave[b] = d logits[b, target[b]] / d wave[b]``, float32 ``[B, L]``, zero from ``lengths[b]``
+    on: ``input_gradient`` of the clip's features, carried through the feature extractor (``sir_features_bwd``)."""
+    lengths, t_pad = _validate_wave(model, wave, lengths, t_pad)
+    if target is not None:
+        target = _class_vector(model, target, wave.shape[0], "target")
+    fz, wave, feats, db = _wave_features(wave, lengths, t_pad)
+    logits, dx = input_gradient(model, feats, target)
+    return logits, fz.features_bwd(wave, lengths, db, dx, t_pad=t_pad)
+
+
+def fgsm_wave(model, wave, labels, eps, lengths=None, t_pad=200, clamp=(-1.0, 1.0)):
+    """The fast-gradient-sign example on the audio itself: ``clamp(wave + eps * sign(d CE(model(features(wave)), labels) / d
+    wave))``; samples at or beyond ``lengths[b]`` are returned as they came.  ``clamp=None``: no clamp."""
+    eps = float(eps)
+    if not eps >= 0.0:
+        raise ValueError("eps must be >= 0")
+    if clamp is not None:
+        lo, hi = (float(c) for c in clamp)
+        if not lo <= hi:
+            raise ValueError("clamp must be (low, high) with low <= high, or None")
+    lengths, t_pad = _validate_wave(model, wave, lengths, t_pad)
+    labels = _class_vector(model, labels, wave.shape[0], "labels")
+    from . import train_ops
+    fz, wave, feats, db = _wave_features(wave, lengths, t_pad)
+    logits, leaf = _forward(model, feats)
+    with torch.enable_grad():
+        loss = train_ops.fused_cross_entropy(logits, labels.to(wave.device))
+    (dx,) = torch.autograd.grad(loss, leaf)
+    adv = wave + eps * fz.features_bwd(wave, lengths, db, dx, t_pad=t_pad).sign_()
+    if clamp is not None:
+        adv.clamp_(lo, hi)
+    if lengths is not None:
+        inside = torch.arange(wave.shape[1], device=wave.device)[None, :] < lengths[:, None]
+        adv = torch.where(inside, adv, wave)
+    return adv

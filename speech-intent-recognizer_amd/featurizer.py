@@ -9,6 +9,7 @@ import ctypes as C
 import math
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _native
 
@@ -30,6 +31,43 @@ def htk_mel_fbanks(n_freqs, f_min, f_max, n_mels, sample_rate):
     down = (-1.0 * slopes[:, :-2]) / f_diff[:-1]
     up = slopes[:, 2:] / f_diff[1:]
     return torch.clamp(torch.min(down, up), min=0.0).contiguous()
+
+
+def _check_wave_grad_args(wave, lengths, t_pad, hop=HOP):
+    """Host-only checks of the differentiable feature path (no device call): float32 ``[B, L]`` on the GPU, one length per
+    clip, and every frame of the longest clip inside ``t_pad`` (the z-norm statistics run over all of them)."""
+    if not torch.is_tensor(wave) or wave.dtype != torch.float32:
+        raise _native.SirError("the differentiable feature path takes a float32 waveform (an int16 tensor cannot carry a "
+                               "gradient; dequantise it first: wave.float() / 32768)")
+    if wave.dim() != 2 or wave.shape[0] < 1 or wave.shape[1] < 1 or wave.stride(1) != 1:
+        raise _native.SirError(f"wave must be [B, L] with unit inner stride, got {tuple(wave.shape)}")
+    if lengths is not None:
+        if not torch.is_tensor(lengths) or lengths.is_floating_point() or lengths.dtype == torch.bool \
+                or lengths.dim() != 1 or lengths.numel() != wave.shape[0]:
+            raise _native.SirError(f"lengths must be an integer tensor with one sample count per clip (batch {wave.shape[0]})")
+    t_pad = int(t_pad)
+    if t_pad < 1 or 1 + wave.shape[1] // hop > t_pad:
+        raise _native.SirError(f"clips of {wave.shape[1]} samples have {1 + wave.shape[1] // hop} frames: the gradient needs "
+                               f"t_pad >= that (got {t_pad})")
+    if not wave.is_cuda or (lengths is not None and not lengths.is_cuda):
+        raise _native.SirError("tensor is not on a HIP device: this path runs on MI355X only (no CPU fallback)")
+
+
+class _DifferentiableFeatures(torch.autograd.Function):
+    """``sir_features_fwd`` (keeping its dB tile) / ``sir_features_bwd``."""
+
+    @staticmethod
+    def forward(ctx, wave, fz, lengths, t_pad, aug):
+        db = torch.empty((wave.shape[0], fz.n_mels, t_pad), dtype=torch.float32, device=wave.device)
+        out = fz(wave, lengths, t_pad=t_pad, db_out=db, **aug)
+        ctx.fz, ctx.wave, ctx.lengths, ctx.t_pad, ctx.aug, ctx.db = fz, wave, lengths, t_pad, aug, db
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dout):
+        dwave = ctx.fz.features_bwd(ctx.wave, ctx.lengths, ctx.db, dout, t_pad=ctx.t_pad, **ctx.aug)
+        return dwave, None, None, None, None
 
 
 class HipFeaturizer:
@@ -112,6 +150,62 @@ class HipFeaturizer:
                                   C.byref(aug) if aug is not None else None, _native.current_stream_ptr())
         _native.check(rc, "sir_features_fwd")
         return out
+
+    def differentiable(self, wave, lengths=None, t_pad=200, shift=None, noise_sigma=None, noise_seed=0,
+                       time_mask=None, freq_mask=None):
+        """``__call__`` as a node of the autograd graph: the same ``[B, n_mels, t_pad]`` features (the same launch), and
+        ``wave.grad`` after a backward (``sir_features_bwd``; DESIGN.md "Gradients down to the waveform").  ``wave`` must be
+        float32 ``[B, L]`` with ``1 + L // hop <= t_pad``; once differentiable (a double backward raises).  The noise of
+        ``noise_sigma`` is regenerated from ``noise_seed`` in the backward; masked outputs pass no gradient."""
+        _check_wave_grad_args(wave, lengths, t_pad, self.hop_length)
+        if lengths is not None:
+            lengths = lengths.to(torch.int32).contiguous()
+        aug = dict(shift=shift, noise_sigma=noise_sigma, noise_seed=noise_seed, time_mask=time_mask, freq_mask=freq_mask)
+        return _DifferentiableFeatures.apply(wave, self, lengths, int(t_pad), aug)
+
+    def features_bwd(self, wave, lengths, db, dout, t_pad=200, shift=None, noise_sigma=None, noise_seed=0,
+                     time_mask=None, freq_mask=None, out=None):
+        """``sir_features_bwd``: d loss / d wave ``[B, L]`` float32 from ``dout = d loss / d features`` and the ``db_out`` of the
+        matching ``__call__`` (same wave -- float32 or int16 --, lengths, t_pad and augmentation arguments).  ``out``
+        (optional): float32 ``[B, >= L]`` with unit inner stride; columns from L on are left alone."""
+        _native.require_hip(wave, lengths, db, dout, out)
+        if wave.dim() != 2 or wave.stride(1) != 1:
+            raise _native.SirError("wave must be [B, L] with unit inner stride")
+        dt = {torch.float32: _native.WAVE_F32, torch.int16: _native.WAVE_I16}.get(wave.dtype)
+        if dt is None:
+            raise _native.SirError(f"unsupported waveform dtype {wave.dtype}")
+        bsz, max_len = wave.shape
+        shape = (bsz, self.n_mels, int(t_pad))
+        for name, t in (("db", db), ("dout", dout)):
+            if t.dtype != torch.float32 or tuple(t.shape) != shape:
+                raise _native.SirError(f"{name} must be float32 {shape}, got {t.dtype} {tuple(t.shape)}")
+        db, dout = db.contiguous(), dout.contiguous()
+        if lengths is None:
+            lengths = torch.full((bsz,), max_len, dtype=torch.int32, device=wave.device)
+        lengths = lengths.to(torch.int32).contiguous()
+        if out is None:
+            out = torch.empty((bsz, max_len), dtype=torch.float32, device=wave.device)
+        elif out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != bsz or out.stride(1) != 1:
+            raise _native.SirError("out must be float32 [B, >= L] with unit inner stride")
+        keep = []
+
+        def ptr(t, dtype):
+            if t is None:
+                return None
+            t = t.to(device=wave.device, dtype=dtype).contiguous()
+            keep.append(t)
+            return t.data_ptr()
+        aug = None
+        if any(a is not None for a in (shift, noise_sigma, time_mask, freq_mask)):
+            aug = _native.Augment(ptr(shift, torch.int32), ptr(noise_sigma, torch.float32), int(noise_seed),
+                                  ptr(time_mask, torch.int32), ptr(freq_mask, torch.int32))
+        rc = _native.lib().sir_features_bwd(self._h, wave.data_ptr(), dt, wave.stride(0), lengths.data_ptr(), bsz, max_len,
+                                            db.data_ptr(), dout.data_ptr(), int(t_pad),
+                                            C.byref(aug) if aug is not None else None, out.data_ptr(),
+                                            out.stride(0) if bsz > 1 else max(out.stride(0), out.shape[1]),
+                                            _native.current_stream_ptr())
+        _native.check(rc, "sir_features_bwd")
+        return out[:, :max_len] if out.shape[1] != max_len else out
 
 
     # ---- waveform front-end (channel mix-down, sample-rate conversion) -----------------------------

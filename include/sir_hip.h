@@ -239,6 +239,8 @@ int sir_model_workspace_offsets(const sir_handle* h, int batch, int t_frames, in
  * version is non-zero and unchanged since the previous call with the same workspace and shape, they are
  * reused instead of rebuilt (~40 us per call).  0 (the default) = always rebuild. */
 int sir_model_set_weights_version(sir_handle* h, uint64_t version);
+/* Batch regimes (256 CUs): the GRU recurrences hold half the chip at batch 256 and all of it at 512; beyond that they are oversubscribed and rest
+ * on in-order dispatch.  Tested against the oracle up to batch 1041 (tests/test_large_batch_gpu.py); batches above 1100 are untested. */
 int sir_model_infer(sir_handle* h, const sir_model_weights* w, const float* feats, int batch,
                     int t_frames, float* logits, int64_t* argmax, void* workspace,
                     size_t workspace_bytes, void* stream);
@@ -370,7 +372,9 @@ typedef struct sir_model_grads {
  * GRU dropout (models.py:32) uses a counter-based mask keyed by dropout_seed (dropout_p = 0 turns it
  * off); activations needed by the backward pass stay in `workspace`
  * (sir_model_workspace_bytes(h, batch, t_frames, 1) bytes), which must be handed unchanged to
- * sir_model_train_bwd. */
+ * sir_model_train_bwd.
+ * Batch regimes as at sir_model_infer (half chip at 256, full chip at 512, oversubscribed beyond); the step is tested against the float64
+ * oracle at batches 257, 512, 528 and 1041 of 24 frames.  Untested: token counts batch * (t_frames / 8) above 6400, and batches above 1100. */
 int sir_model_train_fwd(sir_handle* h, const sir_model_weights* w, float* const bn_running_mean[3],
                         float* const bn_running_var[3], const float* feats, int batch, int t_frames,
                         float bn_momentum, float dropout_p, uint64_t dropout_seed, float* logits,

@@ -123,6 +123,35 @@ int sir_wave_perturb(sir_handle* h, const void* wave, int wave_dtype, int64_t wa
                      int64_t out_stride, int max_out_len, int32_t* out_lengths, int32_t* offsets_out, int max_segments,
                      void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- room reverberation and background noise at a chosen SNR ----------------
+ * sir_wave_reverb_mix: per row, with L = lengths[b] clamped to [0, max_len] and x the row's samples (i16 dequantised as
+ * s / 32768), after sir_wave_perturb and ahead of sir_features_fwd:
+ *   reverb  y[n] = sum_{k < min(K, n + 1)} x[n - k] h_r[k] for n in [0, L), r = rir_index[b], K = rir_lengths[r]: the head
+ *           of the convolution with the room impulse response as given (no gain compensation; the tail beyond L is
+ *           dropped, so lengths do not change).  r = -1: y = x bit for bit.  1 <= K <= max_rir_len <= 8192.
+ *   noise   out[n] = y[n] + g v[(o + n) mod M], v = row noise_index[b] of the noise bank, M = noise_lengths[v] >= 1, o =
+ *           noise_offset[b], g = sqrt(P_y / (P_v 10^(snr_db[b] / 10))), P_y = mean of y^2 over [0, L), P_v = mean square of
+ *           the L noise samples used (with wrapping); g = 0 when P_y or P_v is 0.  v = -1: out = y bit for bit.
+ *   out[b] is zero on [L, max_len) and untouched from max_len on; it must not overlap wave.  Nothing behind lengths[b] in
+ *   wave, nor behind a bank row's length, is read.  Reductions are ordered (no atomics): results are bit-reproducible and
+ *   row b depends on row b alone.
+ *   rir_bank / noise_bank: [n][stride] f32 with device int32 lengths[n]; rir_index / noise_index: device int32[batch], NULL
+ *   = that effect off for every row (its bank arguments are then ignored); noise_offset / snr_db: device [batch], read
+ *   only where noise_index >= 0.
+ *   An index outside [-1, n), a bank length outside its range or a NaN / infinite snr_db zeroes that row and is
+ *   reported by sir_check_status (SIR_EINVAL); the other rows are unaffected.  max_rir_len > 8192: SIR_EINVAL.
+ *   workspace: sir_reverb_workspace_bytes(batch, max_len, max_rir_len) bytes, 256-byte aligned (SIR_ENOMEM otherwise);
+ *   its first `batch` floats receive the gain g applied to each row (0 where no noise was added). */
+size_t sir_reverb_workspace_bytes(const sir_handle* h, int batch, int max_len, int max_rir_len);
+int sir_wave_reverb_mix(sir_handle* h,
+        const void* wave, int wave_dtype, int64_t wave_stride, const int32_t* lengths, int batch, int max_len,
+        const float* rir_bank, int64_t rir_stride, const int32_t* rir_lengths, int n_rir, int max_rir_len,
+        const int32_t* rir_index,                       /* device int32[batch]; -1 = no reverb for that row; NULL = none */
+        const float* noise_bank, int64_t noise_stride, const int32_t* noise_lengths, int n_noise,
+        const int32_t* noise_index,                     /* device int32[batch]; -1 = none; NULL = none */
+        const int32_t* noise_offset, const float* snr_db,  /* device [batch]; read only where noise_index >= 0 */
+        float* out, int64_t out_stride, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- feature path --------------------------------------------------------------------------
  * sir_features_fwd replaces, for a whole batch in one launch pair,
  *   AudioFeatureExtractor.extract_features  scripts/precompute_features.py:59-73

@@ -329,6 +329,11 @@ static int check_status_impl(sir_handle* h, hipStream_t st, const char* who) {
                       "rows are zero with length 0", who, v);
         return SIR_EINVAL;
     }
+    if (v & 256u) {
+        sir_set_error("%s: sir_wave_reverb_mix was given an index outside its bank, a bank length outside its range or a NaN / "
+                      "infinite snr_db (status %u): those rows are zero", who, v);
+        return SIR_EINVAL;
+    }
     if (v & 4u) {
         sir_set_error("%s: sir_gather_features was given an index outside its store (status %u): those rows are zero", who, v);
         return SIR_EINVAL;

@@ -146,9 +146,12 @@ def _wave_features(wave, lengths, t_pad):
     return fz, wave, fz(wave, lengths, t_pad=t_pad, db_out=db), db
 
 
-def wave_gradient(model, wave, lengths=None, target=None, t_pad=200):
+def wave_gradient(model, wave, lengths=None, target=None, t_pad=200, **reverb_kw):
     """``(logits, dwave)`` with ``dwave[b] = d logits[b, target[b]] / d wave[b]``, float32 ``[B, L]``, zero from ``lengths[b]``
-    on: ``input_gradient`` of the clip's features, carried through the feature extractor (``sir_features_bwd``)."""
+    on: ``input_gradient`` of the clip's features, carried through the feature extractor (``sir_features_bwd``).  The arguments
+    of ``HipFeaturizer.reverb_mix`` are rejected with ``ValueError``: there is no gradient through the convolution."""
+    from .featurizer import reject_reverb_args
+    reject_reverb_args(reverb_kw, "wave_gradient")
     lengths, t_pad = _validate_wave(model, wave, lengths, t_pad)
     if target is not None:
         target = _class_vector(model, target, wave.shape[0], "target")
@@ -157,9 +160,12 @@ def wave_gradient(model, wave, lengths=None, target=None, t_pad=200):
     return logits, fz.features_bwd(wave, lengths, db, dx, t_pad=t_pad)
 
 
-def fgsm_wave(model, wave, labels, eps, lengths=None, t_pad=200, clamp=(-1.0, 1.0)):
+def fgsm_wave(model, wave, labels, eps, lengths=None, t_pad=200, clamp=(-1.0, 1.0), **reverb_kw):
     """The fast-gradient-sign example on the audio itself: ``clamp(wave + eps * sign(d CE(model(features(wave)), labels) / d
-    wave))``; samples at or beyond ``lengths[b]`` are returned as they came.  ``clamp=None``: no clamp."""
+    wave))``; samples at or beyond ``lengths[b]`` are returned as they came.  ``clamp=None``: no clamp.  The arguments of
+    ``HipFeaturizer.reverb_mix`` are rejected with ``ValueError``."""
+    from .featurizer import reject_reverb_args
+    reject_reverb_args(reverb_kw, "fgsm_wave")
     eps = float(eps)
     if not eps >= 0.0:
         raise ValueError("eps must be >= 0")

@@ -53,6 +53,20 @@ def _check_wave_grad_args(wave, lengths, t_pad, hop=HOP):
         raise _native.SirError("tensor is not on a HIP device: this path runs on MI355X only (no CPU fallback)")
 
 
+REVERB_KEYS = ("rir", "noise", "rir_index", "noise_index", "noise_offset", "snr_db")
+
+
+def reject_reverb_args(kw, who):
+    """The differentiable forms stop at the feature extractor: the gradient through ``sir_wave_reverb_mix`` does not exist."""
+    given = sorted(k for k in REVERB_KEYS if kw.get(k) is not None)
+    if given:
+        raise ValueError(f"{who} does not take reverb / background-noise arguments ({', '.join(given)}): the gradient through "
+                         "the convolution is not implemented; apply HipFeaturizer.reverb_mix first and differentiate from there")
+    unknown = sorted(k for k in kw if k not in REVERB_KEYS)
+    if unknown:
+        raise TypeError(f"{who} got unexpected keyword arguments: {', '.join(unknown)}")
+
+
 class _DifferentiableFeatures(torch.autograd.Function):
     """``sir_features_fwd`` (keeping its dB tile) / ``sir_features_bwd``."""
 
@@ -85,6 +99,7 @@ class HipFeaturizer:
         _native.check(_native.lib().sir_create(C.byref(cfg), C.byref(self._h)), "sir_create")
         self._ws = None
         self._pws = None        # workspace of perturb()
+        self._rws = None        # workspace of reverb_mix()
         self._pins = 0          # library objects (sir_pipeline) created from this handle that are still alive
 
     def pin(self):
@@ -152,11 +167,13 @@ class HipFeaturizer:
         return out
 
     def differentiable(self, wave, lengths=None, t_pad=200, shift=None, noise_sigma=None, noise_seed=0,
-                       time_mask=None, freq_mask=None):
+                       time_mask=None, freq_mask=None, **reverb_kw):
         """``__call__`` as a node of the autograd graph: the same ``[B, n_mels, t_pad]`` features (the same launch), and
         ``wave.grad`` after a backward (``sir_features_bwd``; DESIGN.md "Gradients down to the waveform").  ``wave`` must be
         float32 ``[B, L]`` with ``1 + L // hop <= t_pad``; once differentiable (a double backward raises).  The noise of
-        ``noise_sigma`` is regenerated from ``noise_seed`` in the backward; masked outputs pass no gradient."""
+        ``noise_sigma`` is regenerated from ``noise_seed`` in the backward; masked outputs pass no gradient.  The arguments of
+        ``reverb_mix`` are rejected with ``ValueError`` (no gradient through the convolution)."""
+        reject_reverb_args(reverb_kw, "HipFeaturizer.differentiable")
         _check_wave_grad_args(wave, lengths, t_pad, self.hop_length)
         if lengths is not None:
             lengths = lengths.to(torch.int32).contiguous()
@@ -311,6 +328,71 @@ class HipFeaturizer:
                                   _native.current_stream_ptr())
         _native.check(rc, "sir_wave_perturb")
         return out, out_len
+
+    # ---- room reverberation and background noise at a chosen SNR (sir_wave_reverb_mix) -----------------------------
+    def reverb_mix(self, wave, lengths=None, rir=None, noise=None, rir_index=None, noise_index=None, noise_offset=None,
+                   snr_db=None, out=None, return_gain=False):
+        """Per-utterance reverb -> background noise (``sir_wave_reverb_mix``) of a GPU batch: wave [B, L]
+        float32/int16, lengths int32 [B] (default all L).  ``rir`` / ``noise``: ``SoundBank``s (sir_amd/sound_bank.py);
+        ``rir_index`` / ``noise_index`` int32 [B] rows of them, -1 = not drawn for that clip (None = effect off);
+        ``noise_offset`` int32 [B] first noise sample (the noise wraps), ``snr_db`` float32 [B].  A clip keeps its length.
+        ``out`` (optional): float32 [B, >= L] with unit inner stride, not overlapping ``wave``; columns from L on are left alone.
+        Returns out [B, L] float32, zero beyond each row's length (``return_gain``: also the gain applied to each row's noise)."""
+        _native.require_hip(wave, lengths, out)
+        if wave.dim() != 2 or wave.stride(1) != 1:
+            raise _native.SirError("wave must be [B, L] with unit inner stride")
+        dt = {torch.float32: _native.WAVE_F32, torch.int16: _native.WAVE_I16}.get(wave.dtype)
+        if dt is None:
+            raise _native.SirError(f"unsupported waveform dtype {wave.dtype}")
+        bsz, max_len = wave.shape
+        if bsz == 0 or max_len == 0:
+            raise _native.SirError("reverb_mix needs a non-empty [B, L] batch")
+        if (rir_index is not None and rir is None) or (noise_index is not None and noise is None):
+            raise _native.SirError("rir_index / noise_index need their SoundBank (rir= / noise=)")
+        if noise_index is not None and (noise_offset is None or snr_db is None):
+            raise _native.SirError("noise_index needs noise_offset and snr_db")
+        lib = _native.lib()
+        if lengths is None:
+            lengths = torch.full((bsz,), max_len, dtype=torch.int32, device=wave.device)
+        lengths = lengths.to(torch.int32).contiguous()
+        keep = []
+
+        def ptr(t, dtype):
+            if t is None:
+                return None
+            t = torch.as_tensor(t).to(device=wave.device, dtype=dtype).contiguous()
+            if t.numel() != bsz:
+                raise _native.SirError(f"per-utterance argument of {t.numel()} values for a batch of {bsz}")
+            keep.append(t)
+            return t.data_ptr()
+
+        def bank(b, on):
+            if not on:
+                return None, 0, None, 0, 0
+            b = b.on(wave.device)
+            keep.append(b)
+            return b.data.data_ptr(), b.data.stride(0), b.lengths.data_ptr(), len(b), b.max_len
+        p_ri, p_ni = ptr(rir_index, torch.int32), ptr(noise_index, torch.int32)
+        p_off, p_snr = (ptr(noise_offset, torch.int32), ptr(snr_db, torch.float32)) if noise_index is not None else (None, None)
+        r_data, r_stride, r_len, n_rir, max_rir = bank(rir, rir_index is not None)
+        n_data, n_stride, n_len, n_noise, _ = bank(noise, noise_index is not None)
+        if out is None:
+            out = torch.empty((bsz, max_len), dtype=torch.float32, device=wave.device)
+        elif out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != bsz or out.shape[1] < max_len or out.stride(1) != 1:
+            raise _native.SirError("out must be float32 [B, >= L] with unit inner stride")
+        nbytes = max(lib.sir_reverb_workspace_bytes(self._h, bsz, max_len, max_rir), 256)
+        if self._rws is None or self._rws.numel() < nbytes or self._rws.device != wave.device:
+            self._rws = torch.empty(nbytes, dtype=torch.uint8, device=wave.device)
+        rc = lib.sir_wave_reverb_mix(self._h, wave.data_ptr(), dt, wave.stride(0), lengths.data_ptr(), bsz, max_len,
+                                     r_data, r_stride, r_len, n_rir, max_rir, p_ri,
+                                     n_data, n_stride, n_len, n_noise, p_ni, p_off, p_snr,
+                                     out.data_ptr(), out.stride(0) if bsz > 1 else max(out.stride(0), out.shape[1]),
+                                     self._rws.data_ptr(), self._rws.numel(), _native.current_stream_ptr())
+        _native.check(rc, "sir_wave_reverb_mix")
+        res = out[:, :max_len] if out.shape[1] != max_len else out
+        if return_gain:
+            return res, self._rws[:bsz * 4].view(torch.float32).clone()
+        return res
 
 
 _featurizers = {}

@@ -10,7 +10,7 @@ path -- only the launch order across batches changes.  Measured on MI355X at bat
 import torch
 
 from . import _native, ops
-from .featurizer import HipFeaturizer, get_featurizer  # noqa: F401
+from .featurizer import REVERB_KEYS, HipFeaturizer, get_featurizer  # noqa: F401
 
 
 # sir_pipeline objects per (device, n_slots), kept for the life of the process: torch's caching allocator remembers every
@@ -29,6 +29,26 @@ def _library_pipeline(n):
         fz.pin()                           # the sir_handle must outlive the pipeline made from it
         _pipelines[key] = (p, {}, fz)      # handle, raw hipStream_t -> torch ExternalStream, the pinned featurizer
     return _pipelines[key]
+
+
+def wave_stages(fz, wave, lengths, kw):
+    """The waveform stages ahead of the feature kernel, on the current stream: shift -> pitch -> speed (``sir_wave_perturb``)
+    when ``kw`` carries ``pitch_cents`` / ``tempo``, then reverb -> background noise (``sir_wave_reverb_mix``) when it carries
+    ``rir_index`` / ``noise_index`` -- in which case a ``shift`` goes through ``sir_wave_perturb`` too, so that it stays
+    ahead of the reverb.  Returns (wave, lengths, what is left of ``kw`` for the feature kernel: Gaussian noise, SpecAugment
+    and, without those stages, the shift).  Without any of those keys nothing is launched and ``kw`` comes back as it is."""
+    mix = kw.get("rir_index") is not None or kw.get("noise_index") is not None
+    perturb = kw.get("pitch_cents") is not None or kw.get("tempo") is not None
+    if not (mix or perturb):
+        return wave, lengths, kw
+    kw = dict(kw)
+    mix_kw = {k: kw.pop(k, None) for k in REVERB_KEYS}
+    if perturb or (mix and kw.get("shift") is not None):
+        wave, lengths = fz.perturb(wave, lengths, shift=kw.pop("shift", None), pitch_cents=kw.pop("pitch_cents", None),
+                                   tempo=kw.pop("tempo", None))
+    if mix:
+        wave = fz.reverb_mix(wave, lengths, **mix_kw)
+    return wave, lengths, kw
 
 
 class BatchPipeline:
@@ -95,6 +115,7 @@ class BatchPipeline:
             if lengths is not None:
                 lengths.record_stream(st)
         with torch.cuda.stream(st):
+            wave, lengths, kw = wave_stages(self.featurizer, wave, lengths, kw)
             return self.featurizer(wave, lengths, **kw)
 
     @torch.no_grad()
@@ -159,13 +180,10 @@ class FeaturePrefetcher:
             self.stream.wait_event(self.freed[k])           # the step that read this buffer has finished
         if self.bufs[k] is None or self.bufs[k].shape[0] != wave.shape[0]:
             self.bufs[k] = torch.empty((wave.shape[0], 64, self.t_pad), dtype=torch.float32, device=wave.device)
-        kw = self.kw
         with torch.cuda.stream(self.stream):
-            if kw.get("pitch_cents") is not None or kw.get("tempo") is not None:
-                # pitch / speed (sir_wave_perturb, with the shift) first, then the feature kernel with the noise and masks
-                kw = dict(kw)
-                wave, lengths = self.fz.perturb(wave, lengths, shift=kw.pop("shift", None),
-                                                pitch_cents=kw.pop("pitch_cents", None), tempo=kw.pop("tempo", None))
+            # pitch / speed (sir_wave_perturb, with the shift), reverb / background noise (sir_wave_reverb_mix), then the
+            # feature kernel with the Gaussian noise and the masks
+            wave, lengths, kw = wave_stages(self.fz, wave, lengths, self.kw)
             self.fz(wave, lengths, t_pad=self.t_pad, out=self.bufs[k], **kw)
             self.ready[k].record(self.stream)
         self.head += 1

@@ -76,6 +76,41 @@ def draw_batch_params_full(lengths, augment_prob=0.7, rng=random):
             torch.tensor(tempos, dtype=torch.float32), torch.tensor(sigmas, dtype=torch.float32))
 
 
+def draw_reverb_noise_params(host_lengths, cfg, rng=random):
+    """Per-utterance arguments of ``HipFeaturizer.reverb_mix`` (the reference has neither effect).  ``cfg``: ``n_rir`` and
+    ``reverb_prob`` (reverb drawn with that probability, the RIR uniformly from the bank), ``noise_lengths`` (host list, one
+    entry per noise clip), ``noise_prob`` and ``snr_db_range`` (noise drawn with that probability: clip uniformly, first
+    sample uniformly inside it, SNR uniformly in the range).  An effect whose bank is missing from ``cfg`` or whose
+    probability is not positive draws NOTHING from ``rng`` and is left out of the result; otherwise the result holds
+    ``rir_index`` int32 [B] (-1 = not drawn) and / or ``noise_index`` int32, ``noise_offset`` int32, ``snr_db`` float32."""
+    n_rir = int(cfg.get("n_rir", 0))
+    p_rev = float(cfg.get("reverb_prob", 0.0))
+    noise_lengths = list(cfg.get("noise_lengths", ()))
+    p_noise = float(cfg.get("noise_prob", 0.0))
+    lo, hi = (float(v) for v in cfg.get("snr_db_range", (5.0, 20.0)))
+    reverb, noise = n_rir > 0 and p_rev > 0.0, len(noise_lengths) > 0 and p_noise > 0.0
+    ri, ni, off, snr = [], [], [], []
+    for _ in host_lengths:
+        r, v, o, s = -1, -1, 0, 0.0
+        if reverb and rng.random() < p_rev:
+            r = rng.randrange(n_rir)
+        if noise and rng.random() < p_noise:
+            v = rng.randrange(len(noise_lengths))
+            o = rng.randrange(int(noise_lengths[v]))
+            s = float(rng.uniform(lo, hi))
+        ri.append(r)
+        ni.append(v)
+        off.append(o)
+        snr.append(s)
+    out = {}
+    if reverb:
+        out["rir_index"] = torch.tensor(ri, dtype=torch.int32)
+    if noise:
+        out.update(noise_index=torch.tensor(ni, dtype=torch.int32), noise_offset=torch.tensor(off, dtype=torch.int32),
+                   snr_db=torch.tensor(snr, dtype=torch.float32))
+    return out
+
+
 def perturbed_out_len(length, tempo):
     """Samples of a clip of ``length`` samples after ``sir_wave_perturb`` with this tempo (as ``sir_perturb_out_len``):
     int(length / f + 0.5) in double with f rounded to float32 as the kernel sees it; pitch keeps the length."""

@@ -163,7 +163,8 @@ def train_epoch_waveforms(model, wave_loader, optimizer, criterion, device, t_pa
     ``WaveformStore.epoch_batches`` yields), so that augmentation parameters can be drawn without a device sync.
     ``augment(wave_batch_index, batch_size, host_lengths | None) -> dict`` may return the featurizer's on-the-fly
     augmentation arguments (``shift``, ``noise_sigma``, ``noise_seed``, ``time_mask``, ``freq_mask``: scripts/augment.py,
-    dataset.py:160-176) for that batch, and ``pitch_cents`` / ``tempo`` (``sir_wave_perturb`` ahead of the feature kernel).
+    dataset.py:160-176) for that batch, ``pitch_cents`` / ``tempo`` (``sir_wave_perturb`` ahead of the feature kernel) and the
+    reverb / background-noise arguments of ``HipFeaturizer.reverb_mix`` (between the two).
     ``mixup`` as for ``train_epoch``: applied to the computed feature batch, after its SpecAugment bands.
     Returns the mean of the per-step losses."""
     from sir_amd import ops
@@ -215,10 +216,17 @@ def make_waveform_augment(config, seed=0, epoch=0, rng=None):
     the cached-feature route applies that one in ``FSCIntentDataset.__getitem__``, the fused route has no dataset.
     ``pitch_speed_augment`` (implies ``waveform_augment``) draws all four waveform effects of augment.py:119-133 --
     shift, pitch, speed, noise -- and adds ``pitch_cents`` / ``tempo``; the time masks are then drawn against the frame
-    counts of the PERTURBED clips (known on the host from the tempo, no device sync)."""
+    counts of the PERTURBED clips (known on the host from the tempo, no device sync).
+    ``reverb_augment`` (``reverb_prob``, default 0.5; RIRs from the WAV files below ``rir_dir``, else 32 synthetic ones with
+    RT60 drawn from ``rt60_range``, default 0.2-0.8 s) and ``background_noise_augment`` (``noise_prob``, default 0.5; clips
+    from ``noise_dir``, else 8 synthetic coloured-noise clips; ``snr_db_range``, default 5-20 dB) add the arguments of
+    ``HipFeaturizer.reverb_mix``: ``rir`` / ``noise`` (the banks) and ``rir_index``, ``noise_index``, ``noise_offset``,
+    ``snr_db``, drawn after every other draw of the batch.  Neither changes a clip's length.  With both keys absent or
+    false the random stream and the returned dictionary are what they were without them."""
     import random
     from sir_amd.scripts import augment as aug
     rng = rng or random.Random((int(seed) << 20) ^ int(epoch))
+    banks = _reverb_noise_banks(config, seed)
     pitch_speed = bool(config.get("pitch_speed_augment", False))
     wave_aug = bool(config.get("waveform_augment", False)) or pitch_speed
     wave_prob = float(config.get("waveform_augment_prob", 0.7))
@@ -240,8 +248,52 @@ def make_waveform_augment(config, seed=0, epoch=0, rng=None):
         if spec_prob > 0.0:
             tm, fm = aug.draw_spec_masks([1 + n // 512 for n in frame_lengths], spec_prob, rng=rng)
             kw.update(time_mask=tm, freq_mask=fm)
+        if banks:
+            kw.update(aug.draw_reverb_noise_params(frame_lengths, banks["cfg"], rng))
+            if "rir_index" in kw:
+                kw["rir"] = banks["rir"]
+            if "noise_index" in kw:
+                kw["noise"] = banks["noise"]
         return kw
     return fn
+
+
+_bank_cache = {}
+
+
+def _reverb_noise_banks(config, seed=0):
+    """The ``SoundBank``s and draw settings of ``reverb_augment`` / ``background_noise_augment`` (None when both are off),
+    built once per distinct setting and kept on the host until the first batch stages them on its device."""
+    reverb = bool(config.get("reverb_augment", False))
+    noise = bool(config.get("background_noise_augment", False))
+    if not (reverb or noise):
+        return None
+    import numpy as np
+    from sir_amd import synth
+    from sir_amd.sound_bank import SoundBank
+    rt60 = tuple(float(v) for v in config.get("rt60_range", (0.2, 0.8)))
+    key = (reverb, config.get("rir_dir"), rt60, noise, config.get("noise_dir"), int(seed))
+    if key not in _bank_cache:
+        gen = np.random.default_rng([int(seed) & 0xFFFFFFFF, 0x52495253])      # its own stream: not the batch draws' rng
+        rir = nb = None
+        if reverb:
+            if config.get("rir_dir"):
+                rir = SoundBank.from_dir(config["rir_dir"], kind="rir")
+            else:
+                rir = SoundBank([synth.synthetic_rir(gen.uniform(*rt60), rng=gen) for _ in range(32)], kind="rir")
+        if noise:
+            if config.get("noise_dir"):
+                nb = SoundBank.from_dir(config["noise_dir"], kind="noise", max_seconds=60.0)
+            else:
+                nb = SoundBank([synth.coloured_noise(10 * synth.SAMPLE_RATE, gen, exponent=e) for e in (0.0, 0.5, 1.0, 1.0, 1.5, 1.5, 2.0, 2.0)])
+        _bank_cache[key] = (rir, nb)
+    rir, nb = _bank_cache[key]
+    cfg = {"snr_db_range": tuple(config.get("snr_db_range", (5.0, 20.0)))}
+    if rir is not None:
+        cfg.update(n_rir=len(rir), reverb_prob=float(config.get("reverb_prob", 0.5)))
+    if nb is not None:
+        cfg.update(noise_lengths=nb.host_lengths, noise_prob=float(config.get("noise_prob", 0.5)))
+    return {"rir": rir, "noise": nb, "cfg": cfg}
 
 
 def build_lr_scheduler(optimizer, spec):
@@ -379,8 +431,11 @@ def train(args, config):
     # step consumes (bench.py `dropin_epoch`).
     # `pitch_speed_augment: true` (implies waveform_augment) adds the pitch and speed effects of scripts/augment.py on the GPU
     # (sir_wave_perturb ahead of the feature kernel).
+    # `reverb_augment: true` / `background_noise_augment: true` (each implies fused_features, not waveform_augment) add room
+    # reverberation and background noise at a drawn SNR (sir_wave_reverb_mix between the two).
     wave_aug = bool(config.get("waveform_augment", False)) or bool(config.get("pitch_speed_augment", False))
-    fused = bool(config.get("fused_features", False)) or wave_aug
+    fused = bool(config.get("fused_features", False)) or wave_aug or bool(config.get("reverb_augment", False)) \
+        or bool(config.get("background_noise_augment", False))
     hbm_cache = bool(config.get("hbm_feature_cache", True)) and not fused
     train_store = None
     if fused:

@@ -30,6 +30,37 @@ def synth_clips(n, length=48000, seed=1234, dtype=torch.float32):
     return x.clamp_(-1.0, 1.0).to(dtype)
 
 
+def synthetic_rir(rt60_s, sample_rate=SAMPLE_RATE, rng=None, tail_level=0.15, max_taps=8192):
+    """A stand-in room impulse response: a unit direct path at tap 0 followed by Gaussian noise of standard deviation
+    ``tail_level`` under an exponential envelope that falls by 60 dB in ``rt60_s`` seconds (10^(-3 t / rt60)), cut where the
+    envelope has fallen by 60 dB or at ``max_taps``.  ``rng``: a ``numpy.random.Generator``.  float32 [K] (CPU)."""
+    rt60_s = float(rt60_s)
+    if not rt60_s > 0.0:
+        raise ValueError("rt60_s must be > 0")
+    rng = rng if rng is not None else np.random.default_rng(0)
+    k = max(1, min(int(rt60_s * sample_rate), int(max_taps)))
+    t = np.arange(k, dtype=np.float64) / float(sample_rate)
+    h = tail_level * rng.standard_normal(k) * np.power(10.0, -3.0 * t / rt60_s)
+    h = np.clip(h, -0.999, 0.999)
+    h[0] = 1.0
+    return torch.from_numpy(h.astype(np.float32))
+
+
+def coloured_noise(n, rng=None, exponent=1.0, rms=0.05):
+    """``n`` samples of noise with a power spectrum ~ 1 / f^exponent (0 white, 1 pink, 2 brown), scaled to ``rms``: a
+    stand-in for a background-noise recording.  ``rng``: a ``numpy.random.Generator``.  float32 [n] (CPU)."""
+    n = int(n)
+    if n < 2:
+        raise ValueError("coloured_noise needs n >= 2")
+    rng = rng if rng is not None else np.random.default_rng(0)
+    spec = np.fft.rfft(rng.standard_normal(n))
+    f = np.arange(spec.shape[0], dtype=np.float64)
+    f[0] = 1.0
+    x = np.fft.irfft(spec * np.power(f, -0.5 * float(exponent)), n)
+    x *= rms / max(float(np.sqrt(np.mean(x * x))), 1e-30)
+    return torch.from_numpy(x.astype(np.float32))
+
+
 def synth_labels(n, num_classes=31, seed=1235):
     g = torch.Generator().manual_seed(seed)
     return torch.randint(0, num_classes, (n,), generator=g, dtype=torch.int64)

@@ -393,7 +393,7 @@ static int model_infer_impl(const char* who, sir_handle* h, const sir_model_weig
         if (ragged) {                                             // tables from the given lengths; conv1 at each utterance's own width
             hipLaunchKernelGGL(ragged_tables_kernel, dim3(1), dim3(1024), 0, st, (const int*)frames, d, ptab + pt.e0, ptab + pt.d1, ptab + pt.d3,
                                ptab + pt.tab2, ptab + pt.tab3, ptab + pt.rows, h->status);
-            hipLaunchKernelGGL(conv1_mfma_bn_relu_pool_ragged_kernel, dim3((d.wp1 + C1_PCOLS - 1) / C1_PCOLS, 1, B), dim3(256), 0, st, feats,
+            hipLaunchKernelGGL(conv1_mfma_bn_relu_pool_ragged_kernel, conv1_grid(B, d.wp1), dim3(256), 0, st, feats,
                                w->conv_w[0], bns, bnt, a1, 64, d.T, 32, d.wp1, (const int*)(ptab + pt.d1), (const int*)(ptab + pt.e0));
             // (fallback path only: the mask of conv1's map is counted with conv1, that of conv2's map with conv2 in sir_profile_*)
             if (!w2) hipLaunchKernelGGL(ragged_mask_kernel, dim3(32, B), dim3(256), 0, st, a1, (const int*)(ptab + pt.e0), 1, 32, d.wp1, 32);
@@ -403,7 +403,7 @@ static int model_infer_impl(const char* who, sir_handle* h, const sir_model_weig
             hipLaunchKernelGGL(pad_tables_kernel, dim3(1), dim3(1024), 0, st, (const int*)(ptab + pt.e0), d, ptab + pt.d1, ptab + pt.d3,
                                ptab + pt.tab2, ptab + pt.tab3, ptab + pt.rows, xz);
         }
-        hipLaunchKernelGGL(conv1_mfma_bn_relu_pool_kernel, dim3((d.wp1 + C1_PCOLS - 1) / C1_PCOLS, 1, BT), dim3(256), 0, st, feats,
+        hipLaunchKernelGGL(conv1_mfma_bn_relu_pool_kernel, conv1_grid(BT, d.wp1), dim3(256), 0, st, feats,
                            w->conv_w[0], bns, bnt, a1, 64, d.T, 32, d.wp1, (const float*)xz, B, w2 ? (const int*)(ptab + pt.d1) : (const int*)nullptr);
         }
     }

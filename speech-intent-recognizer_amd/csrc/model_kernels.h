@@ -43,6 +43,8 @@ static __global__ void prep_bn_kernel(const float* __restrict__ g, const float* 
 // ------------------------------------------------------------------------------------------
 constexpr int C1_PROWS = 4, C1_PCOLS = 32;          // pooled pixels per block: 4 x 32
 constexpr int C1_TR = 2 * C1_PROWS + 2, C1_TC = 2 * C1_PCOLS + 2;
+// launch grid of the MFMA kernels below: the image in x, the 32-column strip in z (see the body)
+inline dim3 conv1_grid(int images, int Wp) { return dim3(images, 1, (Wp + C1_PCOLS - 1) / C1_PCOLS); }
 
 // The same block on the f32 matrix pipe: the direct form above is bound by VALU issue (36 FMAs per output), and
 // v_mfma_f32_32x32x2_f32 does 2048 of them per instruction at the packed-f32 vector rate while the VALU is free for the
@@ -62,13 +64,19 @@ __device__ __forceinline__ void conv1_mfma_bn_relu_pool_body(
     const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ scale,
     const float* __restrict__ shift, float* __restrict__ out, int H, int W, int Hp, int Wp,
     const float* __restrict__ xtail, int nx, const int* __restrict__ lim, const int* __restrict__ xlim) {
-    // One block walks ALL row tiles of its column strip (grid = (column strips, 1, B)): weights / scale / shift are
+    // One block walks ALL row tiles of its column strip (grid = (B, 1, column strips)): weights / scale / shift are
     // loaded once, and the next tile's pixels are fetched into registers while the matrix pipe works on the current one
     // (one short block per tile spent most of its life waiting for its own loads: 50 us for 17 us of MFMA work).
+    // The image is the FASTEST-varying part of the linear workgroup id, x + gridDim.x * (y + gridDim.y * z).  Under the pad
+    // skip a strip is live (px0 < lim[b]) for some images and returns at once for the others; with the strip fastest, the live
+    // ids of a batch of equal lengths were a fixed set of residues mod 8, and workgroups are dealt to the 8 XCDs round-robin by
+    // id (observed, nothing relies on it but speed: see gru_quad_kernel), so at the bench shape -- 2 live strips of 4 -- half
+    // the chip received only workgroups that exit.  Walking the images of one strip before the next strip begins makes the
+    // live ids runs of consecutive numbers, whatever the lengths.
     // Inference pad skip (model_infer.hip): image b >= nx reads `xtail` instead of x (the all-zero template utterance), and
     // only pooled columns < lim[b] are computed and stored (lim == nullptr: all Wp).
     __shared__ float tiles[2][C1_TR * C1_TC];
-    const int b = blockIdx.z, px0 = blockIdx.x * C1_PCOLS;
+    const int b = blockIdx.x, px0 = blockIdx.z * C1_PCOLS;
     const int wlim = lim ? min(Wp, lim[b]) : Wp;
     if (px0 >= wlim) return;                                 // (whole block, before any barrier)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, j = lane & 31, kh = lane >> 5;
@@ -162,7 +170,7 @@ static __global__ __launch_bounds__(256, 4) void conv1_mfma_bn_relu_pool_ragged_
     const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ scale,
     const float* __restrict__ shift, float* __restrict__ out, int H, int W, int Hp, int Wp,
     const int* __restrict__ lim, const int* __restrict__ xlim) {
-    conv1_mfma_bn_relu_pool_body<true>(x, w, scale, shift, out, H, W, Hp, Wp, nullptr, (int)gridDim.z, lim, xlim);
+    conv1_mfma_bn_relu_pool_body<true>(x, w, scale, shift, out, H, W, Hp, Wp, nullptr, (int)gridDim.x, lim, xlim);
 }
 #endif
 

@@ -100,7 +100,7 @@ extern "C" int sir_model_train_fwd_cfg(sir_handle* h, const sir_model_weights* w
             hipLaunchKernelGGL(conv1_bn_from_moments_kernel, dim3(1), dim3(64), 0, st, (const double*)p.c1m, w->conv_w[0],
                                (double)B * 64 * T, w->bn_w[0], w->bn_b[0], bn_running_mean[0], bn_running_var[0], bn_momentum, scale, shift, smean, sinv);
         }
-        hipLaunchKernelGGL(conv1_mfma_bn_relu_pool_kernel, dim3((d.wp1 + C1_PCOLS - 1) / C1_PCOLS, 1, B), dim3(256), 0, st,
+        hipLaunchKernelGGL(conv1_mfma_bn_relu_pool_kernel, conv1_grid(B, d.wp1), dim3(256), 0, st,
                            feats, w->conv_w[0], scale, shift, p.a1, 64, T, 32, d.wp1, (const float*)nullptr, B, (const int*)nullptr);
     }
     // conv2 block: raw conv + partial statistics on MFMA, finalize, BN+ReLU+pool

@@ -1,5 +1,9 @@
 """Runs only the feature kernel (batch 256, 3 s clips) -- for rocprofv3 passes and quick timings.
-usage: python3 devtools/feat_only.py [iters] [i16|f32] [aug] [--backward]
+usage: python3 devtools/feat_only.py [iters] [i16|f32] [aug] [--backward] [--n-fft N[,N..] --hop H[,H..] --win W[,W..]]
+--n-fft / --hop / --win: time the feature stage at other front-ends (comma-separated lists time several in the SAME run, e.g.
+  --n-fft 512,1024,1024 --hop 160,256,512 --win 400,1024,1024: the last one is the specialised kernel, the yardstick); HIP events
+  around regions of `iters` launches, median of 7 regions after a warm-up region, the configurations alternating region by
+  region; prints microseconds per batch and nanoseconds per frame.  t_pad is the clips' frame count rounded up to 4.
 --backward: also times sir_features_bwd beside the forward in the same process, both with HIP events around regions of `iters`
 launches (median of 7 regions after a warm-up region), and prints the ratio."""
 import os
@@ -14,6 +18,19 @@ from sir_amd.featurizer import get_featurizer  # noqa: E402
 
 backward = "--backward" in sys.argv
 sys.argv = [a for a in sys.argv if a != "--backward"]
+
+
+def _take(flag):
+    """value list of `flag` (removed from sys.argv), or None"""
+    if flag not in sys.argv:
+        return None
+    i = sys.argv.index(flag)
+    vals = [int(v) for v in sys.argv[i + 1].split(",")]
+    del sys.argv[i:i + 2]
+    return vals
+
+
+n_ffts, hops, wins = _take("--n-fft"), _take("--hop"), _take("--win")
 iters = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 i16 = len(sys.argv) > 2 and sys.argv[2] == "i16"
 aug = len(sys.argv) > 3 and sys.argv[3] == "aug"
@@ -37,6 +54,32 @@ for i in range(iters):
     fz(pool[i % 8], lengths, t_pad=200, out=out, **kw)
 torch.cuda.synchronize()
 print(f"feature stage: {(time.perf_counter() - t0) / iters * 1e6:.1f} us per batch of 256 ({'i16' if i16 else 'f32'}{', aug' if aug else ''})")
+
+if n_ffts or hops or wins:
+    import statistics
+    n = max(len(v) for v in (n_ffts, hops, wins) if v)
+    n_ffts = n_ffts or [1024] * n
+    hops = hops or [f // 2 for f in n_ffts]
+    wins = wins or list(n_ffts)
+    runs = []
+    for n_fft, hop, win in zip(n_ffts, hops, wins):
+        t_pad = (1 + 48000 // hop + 3) // 4 * 4
+        runs.append(((n_fft, hop, win), get_featurizer(16000, 64, n_fft, hop, win), t_pad,
+                     torch.empty(256, 64, t_pad, device=dev), []))
+    for rep in range(8):                  # region 0 is the warm-up
+        for cfg, f, t_pad, o, ts in runs:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(iters):
+                f(pool[i % 8], lengths, t_pad=t_pad, out=o, **kw)
+            e1.record()
+            e1.synchronize()
+            if rep:
+                ts.append(e0.elapsed_time(e1) * 1e3 / iters)
+    for cfg, f, t_pad, o, ts in runs:
+        us, frames = statistics.median(ts), 256 * (1 + 48000 // cfg[1])
+        print(f"n_fft {cfg[0]} hop {cfg[1]} win {cfg[2]}: {us:.1f} us per batch of 256 (min {min(ts):.1f}), {frames} frames, "
+              f"{us * 1e3 / frames:.1f} ns per frame")
 
 if backward:
     import statistics

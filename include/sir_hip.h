@@ -39,15 +39,19 @@ typedef struct sir_handle sir_handle;
 /* Feature-extractor configuration.
  * Replaces AudioFeatureExtractor.__init__ (scripts/precompute_features.py:21-36), i.e.
  * torchaudio MelSpectrogram(sample_rate, n_fft, hop_length, n_mels) + AmplitudeToDB() with their
- * defaults: win_length = n_fft, periodic Hann, power 2, center + reflect pad, HTK mel, norm None,
- * f_min 0, f_max sample_rate/2, 10*log10(max(x,1e-10)).
- * `window` / `mel_fb` are optional HOST arrays (n_fft floats; [n_fft/2+1][n_mels] dense, row-major)
+ * defaults: win_length = n_fft (sir_create_ex takes another), periodic Hann, power 2, center + reflect pad, HTK mel,
+ * norm None, f_min 0, f_max sample_rate/2, 10*log10(max(x,1e-10)).
+ * `window` / `mel_fb` are optional HOST arrays (win_length floats; [n_fft/2+1][n_mels] dense, row-major)
  * so that the host can hand over torch's own float32 tables bit for bit; NULL = computed in double
- * here and rounded to float. */
+ * here and rounded to float.
+ * Supported front-ends: n_fft in {256, 512, 1024}, n_fft/16 <= hop_length <= n_fft (any integer), 1 <= win_length <= n_fft;
+ * anything else is SIR_EUNSUPPORTED, and so is a caller's mel_fb whose taps do not fit the general kernel's LDS beside its other
+ * buffers (about 3000 taps at n_fft 1024; the built-in bank has about 1000).  n_fft 1024 / hop 512 / win_length 1024 runs the specialised one-launch kernel
+ * (feat_utt_kernel), every other one the general launch pair (DESIGN.md section 4 "Other front-ends"). */
 typedef struct sir_feature_config {
     int sample_rate;   /* 16000 */
-    int n_fft;         /* 1024 (the only size built) */
-    int hop_length;    /* 512  (= n_fft/2, the only hop built) */
+    int n_fft;         /* 1024; 256 and 512 are built too */
+    int hop_length;    /* 512; any n_fft/16 .. n_fft */
     int n_mels;        /* 64 (<= 64) */
     float f_min;       /* 0 */
     float f_max;       /* sample_rate/2 */
@@ -72,6 +76,10 @@ const char* sir_last_error(void);
 /* Create / destroy a handle.  Uploads window, twiddles and the sparse mel filterbank to the
  * current HIP device (the only allocating calls).  Host-synchronous. */
 int sir_create(const sir_feature_config* cfg, sir_handle** out);
+/* sir_create with torch.stft's win_length: the window of win_length samples (cfg->window holds win_length floats, NULL = periodic
+ * Hann of win_length computed in double) is centred in the frame of n_fft samples, (n_fft - win_length) / 2 zeros on its left.
+ * win_length == 0 means n_fft; sir_create(cfg, out) is sir_create_ex(cfg, 0, out). */
+int sir_create_ex(const sir_feature_config* cfg, int win_length, sir_handle** out);
 int sir_destroy(sir_handle* h);
 
 /* ---- waveform front-end --------------------------------------------
@@ -165,7 +173,10 @@ int sir_wave_reverb_mix(sir_handle* h,
  * db_out : optional (NULL = off) [batch][n_mels][t_pad] f32 copy of the un-normalised dB values
  *          (10*log10(max(mel,1e-10)), zero in the padding) -- the AmplitudeToDB output of
  *          precompute_features.py:67, exposed so that the mel/dB stage can be checked on its own
- * workspace: sir_features_workspace_bytes(batch, max_len) bytes, 16-byte aligned */
+ * workspace: sir_features_workspace_bytes(batch, max_len) bytes, 16-byte aligned: 256 on a handle of the default front-end
+ *          (statistics stay on chip), on any other handle the dB slab [batch][n_mels][1 + max_len/hop] of the launch pair (every
+ *          frame of a clip counts in its statistics, also those beyond t_pad); a smaller one is SIR_ENOMEM.
+ * On the default front-end clips of more than 160 frames need t_pad >= their frame count; the general path has no such rule. */
 size_t sir_features_workspace_bytes(const sir_handle* h, int batch, int max_len);
 int sir_features_fwd(sir_handle* h, const void* wave, int wave_dtype, int64_t wave_stride,
                      const int32_t* lengths, int batch, int max_len, float* out, int t_pad,
@@ -190,7 +201,8 @@ int sir_features_fwd(sir_handle* h, const void* wave, int wave_dtype, int64_t wa
  * Departures from autograd: where the mel power is at or below the 1e-10 clamp the gradient is 0 (the forward's own test), and a
  * clip whose dB tile is constant (sigma == 0, e.g. digital silence) gets dD = (g - mean g) / 1e-5 with the sigma term dropped,
  * where torch returns NaN.  NULL pointers, a bad dtype, misaligned pointers and strides < max_len are SIR_EINVAL; every
- * argument is checked before anything is launched. */
+ * argument is checked before anything is launched.  The waveform gradient is built for the default front-end only: on a handle
+ * that is not n_fft 1024 / hop 512 / win_length 1024 the call is SIR_EUNSUPPORTED and writes nothing. */
 int sir_features_bwd(sir_handle* h, const void* wave, int wave_dtype, int64_t wave_stride,
                      const int32_t* lengths, int batch, int max_len,
                      const float* db, const float* dout, int t_pad, const sir_augment* aug,

@@ -67,6 +67,7 @@ SIGNATURES = {
     "sir_abi_version": (C.c_int, []),
     "sir_last_error": (C.c_char_p, []),
     "sir_create": (C.c_int, [C.POINTER(FeatureConfig), C.POINTER(C.c_void_p)]),
+    "sir_create_ex": (C.c_int, [C.POINTER(FeatureConfig), C.c_int, C.POINTER(C.c_void_p)]),
     "sir_destroy": (C.c_int, [C.c_void_p]),
     "sir_features_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
     "sir_features_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int,

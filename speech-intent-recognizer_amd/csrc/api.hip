@@ -40,22 +40,31 @@ bool sir_conv_stage_fits(int conv, bool shape_ok) {
     return shape_ok && forced < (conv == 2 ? 1 : 2);
 }
 
-extern "C" int sir_create(const sir_feature_config* cfg, sir_handle** out) {
+extern "C" int sir_create(const sir_feature_config* cfg, sir_handle** out) { return sir_create_ex(cfg, 0, out); }
+
+extern "C" int sir_create_ex(const sir_feature_config* cfg, int win_length, sir_handle** out) {
     if (!cfg || !out) { sir_set_error("sir_create: NULL argument"); return SIR_EINVAL; }
-    if (cfg->n_fft != SIR_NFFT || cfg->hop_length != SIR_HOP) {
-        sir_set_error("sir_create: only n_fft=1024 / hop=512 are built (got %d / %d)", cfg->n_fft, cfg->hop_length);
+    const int n_fft = cfg->n_fft, hop = cfg->hop_length;
+    if (win_length == 0) win_length = n_fft;
+    if ((n_fft != 256 && n_fft != 512 && n_fft != 1024) || hop < n_fft / 16 || hop > n_fft || win_length < 1 || win_length > n_fft) {
+        sir_set_error("sir_create: n_fft=%d hop_length=%d win_length=%d is not built; supported: n_fft in {256, 512, 1024}, "
+                      "n_fft/16 <= hop_length <= n_fft, 1 <= win_length <= n_fft", n_fft, hop, win_length);
         return SIR_EUNSUPPORTED;
     }
     if (cfg->n_mels < 1 || cfg->n_mels > SIR_MAX_MELS || cfg->sample_rate <= 0) {
         sir_set_error("sir_create: n_mels=%d sample_rate=%d out of range", cfg->n_mels, cfg->sample_rate);
         return SIR_EINVAL;
     }
+    const int nfreq = n_fft / 2 + 1;
     sir_handle* h = new sir_handle();
     h->prof_mode = 0; h->prof_only = -1;
     h->weights_version = 0; h->prep_next = 0;
     for (auto& e : h->prep) { e.ws = nullptr; e.version = 0; e.key = -1; }
     h->tw512 = nullptr; h->tw1024 = nullptr; h->window = nullptr; h->melw = nullptr; h->mel_desc = nullptr;
     h->mel_taps = nullptr; h->mel_max_cover = 0;
+    h->win_length = win_length;
+    h->general = !(n_fft == SIR_NFFT && hop == SIR_HOP && win_length == SIR_NFFT);
+    h->gen_twn = nullptr; h->gen_tw2n = nullptr;
     h->status = nullptr;
     h->cluster_done = nullptr; h->cluster_stream = nullptr; h->cluster_pending = false;
     h->cluster_seen = false; h->cluster_multi = false; h->cluster_run = 0;
@@ -74,13 +83,25 @@ extern "C" int sir_create(const sir_feature_config* cfg, sir_handle** out) {
     std::vector<float2> tw512(512), tw1024(SIR_NFREQ);
     for (int j = 0; j < 512; ++j) tw512[j] = make_float2((float)cos(-2.0 * PI * j / 512.0), (float)sin(-2.0 * PI * j / 512.0));
     for (int k = 0; k < SIR_NFREQ; ++k) tw1024[k] = make_float2((float)cos(-2.0 * PI * k / 1024.0), (float)sin(-2.0 * PI * k / 1024.0));
-    std::vector<float> window(SIR_NFFT);
-    for (int n = 0; n < SIR_NFFT; ++n)
-        window[n] = cfg->window ? cfg->window[n] : (float)(0.5 - 0.5 * cos(2.0 * PI * n / SIR_NFFT));
+    // the window of win_length samples, centred in the frame as torch.stft does ((n_fft - win_length) / 2 zeros on the left)
+    std::vector<float> window(n_fft, 0.0f);
+    const int wleft = (n_fft - win_length) / 2;
+    for (int n = 0; n < win_length; ++n)
+        window[wleft + n] = cfg->window ? cfg->window[n] : (float)(0.5 - 0.5 * cos(2.0 * PI * n / win_length));
+    // general path: twiddles of the n_fft/2-point packed transform and of its untangle step
+    std::vector<float2> gen_twn, gen_tw2n;
+    if (h->general) {
+        const int np = n_fft / 2;
+        gen_twn.resize(np); gen_tw2n.resize(np);
+        for (int k = 0; k < np; ++k) {
+            gen_twn[k] = make_float2((float)cos(-2.0 * PI * k / np), (float)sin(-2.0 * PI * k / np));
+            gen_tw2n[k] = make_float2((float)cos(-2.0 * PI * k / n_fft), (float)sin(-2.0 * PI * k / n_fft));
+        }
+    }
 
     // dense HTK filterbank (torchaudio melscale_fbanks, norm=None), then compacted per filter
     const int nm = cfg->n_mels;
-    std::vector<float> fb((size_t)SIR_NFREQ * nm);
+    std::vector<float> fb((size_t)nfreq * nm);
     if (cfg->mel_fb) {
         memcpy(fb.data(), cfg->mel_fb, fb.size() * sizeof(float));
     } else {
@@ -88,8 +109,8 @@ extern "C" int sir_create(const sir_feature_config* cfg, sir_handle** out) {
         const double mmin = 2595.0 * log10(1.0 + f_lo / 700.0), mmax = 2595.0 * log10(1.0 + f_hi / 700.0);
         std::vector<double> fpts(nm + 2);
         for (int i = 0; i < nm + 2; ++i) fpts[i] = 700.0 * (pow(10.0, (mmin + (mmax - mmin) * i / (nm + 1)) / 2595.0) - 1.0);
-        for (int k = 0; k < SIR_NFREQ; ++k) {
-            const double f = (double)(cfg->sample_rate / 2) * k / (SIR_NFREQ - 1);
+        for (int k = 0; k < nfreq; ++k) {
+            const double f = (double)(cfg->sample_rate / 2) * k / (nfreq - 1);
             for (int j = 0; j < nm; ++j) {
                 const double up = (f - fpts[j]) / (fpts[j + 1] - fpts[j]), down = (fpts[j + 2] - f) / (fpts[j + 2] - fpts[j + 1]);
                 const double v = up < down ? up : down;
@@ -102,7 +123,7 @@ extern "C" int sir_create(const sir_feature_config* cfg, sir_handle** out) {
     std::vector<int> start(SIR_MAX_MELS, 0), count(SIR_MAX_MELS, 0);
     for (int j = 0; j < nm; ++j) {
         int lo = -1, hi = -1;
-        for (int k = 0; k < SIR_NFREQ; ++k)
+        for (int k = 0; k < nfreq; ++k)
             if (fb[(size_t)k * nm + j] != 0.0f) { if (lo < 0) lo = k; hi = k; }
         if (lo >= 0) { start[j] = lo; count[j] = hi - lo + 1; }
     }
@@ -126,10 +147,17 @@ extern "C" int sir_create(const sir_feature_config* cfg, sir_handle** out) {
         return SIR_EUNSUPPORTED;
     }
     h->mel_nnz = (int)melw.size();
+    if (h->general && sir_features_gen_lds_bytes(n_fft, h->mel_nnz) > SIR_LDS_BYTES) {
+        // (the built-in HTK bank of n_fft 1024 has ~1000 taps and fits; a caller's dense bank may not)
+        sir_set_error("sir_create: a filterbank of %d taps at n_fft=%d needs %zu bytes of LDS in the general feature kernel (limit %d)",
+                      h->mel_nnz, n_fft, sir_features_gen_lds_bytes(n_fft, h->mel_nnz), SIR_LDS_BYTES);
+        delete h;
+        return SIR_EUNSUPPORTED;
+    }
     // transposed for the gradient (sir_features_bwd): the filters over each bin, ascending; neighbouring triangles overlap in pairs
     struct Tap { int fa; float wa; int fb; float wb; };
-    std::vector<Tap> taps(SIR_NFREQ, Tap{0, 0.0f, 0, 0.0f});
-    for (int k = 0; k < SIR_NFREQ; ++k) {
+    std::vector<Tap> taps(nfreq, Tap{0, 0.0f, 0, 0.0f});
+    for (int k = 0; k < nfreq; ++k) {
         int cover = 0;
         for (int j = 0; j < nm; ++j) {
             const float w = fb[(size_t)k * nm + j];
@@ -147,6 +175,8 @@ extern "C" int sir_create(const sir_feature_config* cfg, sir_handle** out) {
     if (rc == SIR_OK) rc = upload(&h->window, window);
     if (rc == SIR_OK) rc = upload(&h->melw, melw);
     if (rc == SIR_OK) rc = upload(&h->mel_desc, desc);
+    if (rc == SIR_OK && h->general) rc = upload(&h->gen_twn, gen_twn);
+    if (rc == SIR_OK && h->general) rc = upload(&h->gen_tw2n, gen_tw2n);
     if (rc == SIR_OK) rc = upload((Tap**)&h->mel_taps, taps);
     if (rc == SIR_OK) rc = upload(&h->status, std::vector<unsigned int>(64, 0u));
     if (rc == SIR_OK) rc = upload(&h->zero_page, std::vector<float>(1024, 0.0f));
@@ -163,6 +193,7 @@ extern "C" int sir_create(const sir_feature_config* cfg, sir_handle** out) {
 extern "C" int sir_destroy(sir_handle* h) {
     if (!h) return SIR_OK;
     (void)hipFree(h->tw512); (void)hipFree(h->tw1024); (void)hipFree(h->window);
+    (void)hipFree(h->gen_twn); (void)hipFree(h->gen_tw2n);
     (void)hipFree(h->melw); (void)hipFree(h->mel_desc); (void)hipFree(h->mel_taps); (void)hipFree(h->status);
     if (h->cluster_done) (void)hipEventDestroy(h->cluster_done);
     if (h->bwd_side) { (void)hipStreamSynchronize(h->bwd_side); (void)hipStreamDestroy(h->bwd_side); }
@@ -187,6 +218,11 @@ extern "C" int sir_features_fwd(sir_handle* h, const void* wave, int wave_dtype,
 extern "C" int sir_features_bwd(sir_handle* h, const void* wave, int wave_dtype, int64_t wave_stride,
                                 const int32_t* lengths, int batch, int max_len, const float* db, const float* dout,
                                 int t_pad, const sir_augment* aug, float* dwave, int64_t dwave_stride, void* stream) {
+    if (h && h->general) {
+        sir_set_error("sir_features_bwd: the waveform gradient is built for the default front-end only (n_fft 1024 / hop_length 512 / "
+                      "win_length 1024; this handle has %d / %d / %d)", h->cfg.n_fft, h->cfg.hop_length, h->win_length);
+        return SIR_EUNSUPPORTED;
+    }
     return sir_features_bwd_launch(h, wave, wave_dtype, wave_stride, lengths, batch, max_len, db, dout, t_pad, aug, dwave,
                                    dwave_stride, (hipStream_t)stream);
 }

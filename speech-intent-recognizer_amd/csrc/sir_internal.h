@@ -71,6 +71,13 @@ struct sir_handle {
     float* melw;        // compact filter weights: filter after filter, taps ascending in frequency (mel_nnz floats)
     int4* mel_desc;     // [64] per slot, filters sorted by tap count: {filter (-1 = unused), first FFT bin, taps, offset into melw}
     int mel_nnz;
+    // front-end geometry.  `general` = anything but n_fft 1024 / hop 512 / win_length 1024: sir_features_fwd then runs the general
+    // launch pair (features.hip: feat_gen_frames_kernel + feat_gen_norm_kernel) with the tables below, and `window` holds n_fft
+    // floats, the win_length window centred between zeros.  The specialised kernels keep their SIR_NFFT / SIR_HOP constants.
+    int win_length;
+    bool general;
+    float2* gen_twn;    // general path: exp(-2*pi*i*k/(n_fft/2)), k = 0 .. n_fft/2 - 1 (the packed transform's twiddles)
+    float2* gen_tw2n;   // general path: exp(-2*pi*i*k/n_fft),     k = 0 .. n_fft/2 - 1 (the untangle twiddles)
     // the filterbank transposed for sir_features_bwd: per FFT bin the (at most) two filters that cover it, {filter, weight, filter,
     // weight} (int, float, int, float; weight 0 = none), [513]; mel_max_cover = filters on the busiest bin (the kernel serves <= 2)
     void* mel_taps;
@@ -228,6 +235,8 @@ struct SirProfScope {
 size_t sir_train_workspace_bytes_impl(int batch, int t_frames);
 
 // features.hip
+size_t sir_features_gen_lds_bytes(int n_fft, int mel_nnz);   // dynamic LDS the general frames kernel needs on such a handle
+#define SIR_LDS_BYTES (160 * 1024)                            // per workgroup on gfx950
 int sir_features_launch(sir_handle* h, const void* wave, int wave_dtype, int64_t wave_stride,
                         const int32_t* lengths, int batch, int max_len, float* out, int t_pad,
                         float* db_out, void* workspace, size_t workspace_bytes, const sir_augment* aug,

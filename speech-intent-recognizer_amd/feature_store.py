@@ -30,15 +30,17 @@ class FeatureStore:
     device tensors in ``ShardSampler`` order (rank r takes i = r mod world of the shuffled epoch)."""
 
     def __init__(self, csv_path, label_map_path, device, use_cache=True, cache_dir="data/cached_features",
-                 mel_spec_length=200, stage_items=4096):
+                 mel_spec_length=200, stage_items=4096, frontend=None):
         _native.require_hip()
         from .scripts.dataset import FSCIntentDataset
         if mel_spec_length % 4 != 0:
             raise ValueError("mel_spec_length must be a multiple of 4 (16-byte rows)")
         self.device = torch.device(device)
         self.t_pad = int(mel_spec_length)
+        from .frontend_config import as_frontend
+        fe = as_frontend(frontend)                    # the split's cache file (and any miss) is this front-end's
         ds = FSCIntentDataset(csv_path, label_map_path, is_training=False, use_cache=use_cache, cache_dir=cache_dir,
-                              mel_spec_length=mel_spec_length)
+                              mel_spec_length=mel_spec_length, n_fft=fe.n_fft, hop_length=fe.hop_length, win_length=fe.win_length)
         n = len(ds)
         self.n_mels = ds.n_mels
         self.store = torch.zeros((n, self.n_mels, self.t_pad), dtype=torch.float32, device=self.device)

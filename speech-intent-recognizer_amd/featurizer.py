@@ -16,6 +16,15 @@ from . import _native
 N_FFT = 1024
 HOP = 512
 MAX_DURATION_S = 5.0
+# what sir_features_bwd answers on a handle of another front-end (csrc/api.hip); HipFeaturizer.differentiable raises it before
+# any device call
+GRAD_DEFAULT_ONLY = ("sir_features_bwd: the waveform gradient is built for the default front-end only (n_fft 1024 / "
+                     "hop_length 512 / win_length 1024; this handle has {} / {} / {})")
+
+
+def is_default_frontend(n_fft, hop_length, win_length=None):
+    """True for the front-end the specialised one-launch kernel (and the waveform gradient) is built for."""
+    return (int(n_fft), int(hop_length), int(n_fft if win_length is None else win_length)) == (N_FFT, HOP, N_FFT)
 
 
 def htk_mel_fbanks(n_freqs, f_min, f_max, n_mels, sample_rate):
@@ -87,17 +96,22 @@ class _DifferentiableFeatures(torch.autograd.Function):
 class HipFeaturizer:
     """Owns one ``sir_handle`` on the current HIP device."""
 
-    def __init__(self, sample_rate=16000, n_mels=64, n_fft=N_FFT, hop_length=HOP):
+    def __init__(self, sample_rate=16000, n_mels=64, n_fft=N_FFT, hop_length=HOP, win_length=None):
         _native.require_hip()
+        win_length = int(n_fft if win_length is None else win_length)
         self.sample_rate, self.n_mels, self.n_fft, self.hop_length = sample_rate, n_mels, n_fft, hop_length
+        self.win_length = win_length
         self.device = torch.device("cuda", torch.cuda.current_device())
-        window = torch.hann_window(n_fft, periodic=True, dtype=torch.float32).contiguous()
+        # (sir_create_ex rejects an unsupported front-end before it reads the window)
+        window = torch.hann_window(max(win_length, 1), periodic=True, dtype=torch.float32).contiguous()
         fb = htk_mel_fbanks(n_fft // 2 + 1, 0.0, float(sample_rate // 2), n_mels, sample_rate).float().contiguous()
         cfg = _native.FeatureConfig(sample_rate, n_fft, hop_length, n_mels, 0.0, float(sample_rate // 2),
                                     window.data_ptr(), fb.data_ptr())
         self._h = C.c_void_p()
-        _native.check(_native.lib().sir_create(C.byref(cfg), C.byref(self._h)), "sir_create")
-        self._ws = None
+        _native.check(_native.lib().sir_create_ex(C.byref(cfg), win_length, C.byref(self._h)), "sir_create_ex")
+        # feature workspaces, one per stream that calls: on a general front-end the workspace is the live dB slab between the
+        # two launches, and callers such as BatchPipeline run batches of one featurizer on several streams at once
+        self._ws = {}
         self._pws = None        # workspace of perturb()
         self._rws = None        # workspace of reverb_mix()
         self._pins = 0          # library objects (sir_pipeline) created from this handle that are still alive
@@ -146,8 +160,11 @@ class HipFeaturizer:
             out = torch.empty((bsz, self.n_mels, t_pad), dtype=torch.float32, device=wave.device)
         lib = _native.lib()
         need = lib.sir_features_workspace_bytes(self._h, bsz, max_len)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != wave.device:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=wave.device)
+        # (allocated under the calling stream, so the allocator hands a replaced block to that stream only)
+        key = (wave.device, torch.cuda.current_stream(wave.device).cuda_stream)
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < need:
+            ws = self._ws[key] = torch.empty(need, dtype=torch.uint8, device=wave.device)
         aug = None
         keep = []
         if any(a is not None for a in (shift, noise_sigma, time_mask, freq_mask)):
@@ -161,7 +178,7 @@ class HipFeaturizer:
                                   ptr(time_mask, torch.int32), ptr(freq_mask, torch.int32))
         rc = lib.sir_features_fwd(self._h, wave.data_ptr(), dt, wave.stride(0), lengths.data_ptr(), bsz, max_len,
                                   out.data_ptr(), t_pad, db_out.data_ptr() if db_out is not None else None,
-                                  self._ws.data_ptr(), self._ws.numel(),
+                                  ws.data_ptr(), ws.numel(),
                                   C.byref(aug) if aug is not None else None, _native.current_stream_ptr())
         _native.check(rc, "sir_features_fwd")
         return out
@@ -174,6 +191,10 @@ class HipFeaturizer:
         ``noise_sigma`` is regenerated from ``noise_seed`` in the backward; masked outputs pass no gradient.  The arguments of
         ``reverb_mix`` are rejected with ``ValueError`` (no gradient through the convolution)."""
         reject_reverb_args(reverb_kw, "HipFeaturizer.differentiable")
+        n_fft = getattr(self, "n_fft", N_FFT)
+        win_length = getattr(self, "win_length", n_fft)
+        if not is_default_frontend(n_fft, self.hop_length, win_length):
+            raise _native.SirError(GRAD_DEFAULT_ONLY.format(n_fft, self.hop_length, win_length))
         _check_wave_grad_args(wave, lengths, t_pad, self.hop_length)
         if lengths is not None:
             lengths = lengths.to(torch.int32).contiguous()
@@ -398,10 +419,11 @@ class HipFeaturizer:
 _featurizers = {}
 
 
-def get_featurizer(sample_rate=16000, n_mels=64, n_fft=N_FFT, hop_length=HOP):
-    """Per-device cached featurizer."""
+def get_featurizer(sample_rate=16000, n_mels=64, n_fft=N_FFT, hop_length=HOP, win_length=None):
+    """Per-device cached featurizer (``win_length`` None = ``n_fft``)."""
     _native.require_hip()
-    key = (torch.cuda.current_device(), sample_rate, n_mels, n_fft, hop_length)
+    win_length = int(n_fft if win_length is None else win_length)
+    key = (torch.cuda.current_device(), sample_rate, n_mels, n_fft, hop_length, win_length)
     if key not in _featurizers:
-        _featurizers[key] = HipFeaturizer(sample_rate, n_mels, n_fft, hop_length)
+        _featurizers[key] = HipFeaturizer(sample_rate, n_mels, n_fft, hop_length, win_length)
     return _featurizers[key]

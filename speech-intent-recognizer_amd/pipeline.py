@@ -61,13 +61,14 @@ class BatchPipeline:
     buffers are reused ``n_streams`` batches later, so consume or copy results before that.  Results are bit-identical
     to the single-stream order."""
 
-    def __init__(self, model, n_streams=2):
+    def __init__(self, model, n_streams=2, frontend=None):
         _native.require_hip()
+        from .frontend_config import as_frontend
         self.model = model
         self.n = max(1, int(n_streams))
         self._lib = _native.lib()
         self._p, self._ext = _library_pipeline(self.n)[:2]
-        self.featurizer = get_featurizer()
+        self.featurizer = as_frontend(frontend).featurizer()       # ``features`` runs this front-end (None = the default)
         self.workspaces = [model._ws] + [ops.Workspace() for _ in range(self.n - 1)]
         self._cur = None                   # (batch index, slot, torch stream) of the open submission
 
@@ -156,11 +157,13 @@ class FeaturePrefetcher:
     features again) lets the side stream overwrite it ``depth`` submissions later.  Values are bit-identical to the
     in-line ``HipFeaturizer`` call: same kernels, another stream."""
 
-    def __init__(self, t_pad=200, depth=2, **feat_kw):
+    def __init__(self, t_pad=200, depth=2, frontend=None, **feat_kw):
         _native.require_hip()
+        from .frontend_config import as_frontend
+        fe = as_frontend(frontend)
         self.t_pad, self.depth, self.kw = int(t_pad), max(2, int(depth)), feat_kw
         self.stream = torch.cuda.Stream()
-        self.fz = HipFeaturizer()
+        self.fz = HipFeaturizer(n_fft=fe.n_fft, hop_length=fe.hop_length, win_length=fe.win_length)
         self.bufs = [None] * self.depth
         self.ready = [torch.cuda.Event() for _ in range(self.depth)]
         self.freed = [None] * self.depth

@@ -20,6 +20,7 @@ import tempfile
 
 import yaml
 
+from sir_amd.frontend_config import FrontEnd
 from sir_amd.scripts.preprocess_fsc import preprocess_dataset
 
 logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
@@ -58,6 +59,9 @@ def stage_commands(config_path, config, train_csv, valid_csv, test_csv, label_ma
     cache_dir = config.get("cache_dir", "data/cached_features")
     precompute = [py, "-m", "sir_amd.scripts.precompute_features", "--train_csv", train_csv, "--valid_csv", valid_csv,
                   "--test_csv", test_csv, "--output_dir", cache_dir, "--label_map", label_map]
+    fe = FrontEnd.from_config(config)
+    if not fe.is_default:                   # (train / evaluate read the keys from the config file themselves)
+        precompute += ["--n_fft", str(fe.n_fft), "--hop_length", str(fe.hop_length), "--win_length", str(fe.win_length)]
     train_tail = ["-m", "sir_amd.scripts.train", "--config", config_path, "--train_csv", train_csv, "--val_csv", valid_csv,
                   "--label_map", label_map]
     if gpus > 1:
@@ -106,7 +110,7 @@ def run_pipeline(config_path, gpus=None):
         logger.info("=== STEP 2: PRECOMPUTING FEATURES ===")
         cache_dir = config.get("cache_dir", "data/cached_features")
         os.makedirs(cache_dir, exist_ok=True)
-        train_cache = os.path.join(cache_dir, f"{os.path.basename(train_csv).replace('.csv', '')}_features.pt")
+        train_cache = os.path.join(cache_dir, FrontEnd.from_config(config).cache_name(os.path.basename(train_csv).replace(".csv", "")))
         if config.get("force_precompute", False) or not os.path.exists(train_cache):
             if not run_subprocess(cmds["precompute"], "Feature Precomputation"):
                 # the reference carries on without the cache (run_pipeline.py:165-169); so does this pipeline:

@@ -52,7 +52,10 @@ class FSCIntentDataset(Dataset):
     """Fluent Speech Commands items from the feature cache (dataset.py:12-176)."""
 
     def __init__(self, csv_path, label_map_path, is_training=True, augment_prob=0.5,
-                 use_cache=True, cache_dir="data/cached_features", mel_spec_length=200):
+                 use_cache=True, cache_dir="data/cached_features", mel_spec_length=200,
+                 n_fft=1024, hop_length=512, win_length=None):
+        from sir_amd.frontend_config import FrontEnd
+        self.frontend = FrontEnd(n_fft, hop_length, win_length)      # (beyond the reference, whose front-end is 1024 / 512 / 1024)
         self.data = pd.read_csv(csv_path)
         self.sample_rate = 16000
         self.is_training = is_training
@@ -66,7 +69,8 @@ class FSCIntentDataset(Dataset):
         self.features_dict = {}
         if use_cache:
             dataset_name = os.path.basename(csv_path).replace(".csv", "")
-            self.cache_file = os.path.join(cache_dir, f"{dataset_name}_features.pt")
+            # another front-end has its own file: a cache is never taken for one of another front-end
+            self.cache_file = os.path.join(cache_dir, self.frontend.cache_name(dataset_name))
             if os.path.exists(self.cache_file):
                 logger.info(f"Loading cached features from {self.cache_file}")
                 self.features_dict = torch.load(self.cache_file)
@@ -99,8 +103,7 @@ class FSCIntentDataset(Dataset):
         missing = self.missing_paths()
         if not missing or not torch.cuda.is_available():
             return 0
-        from sir_amd.scripts.precompute_features import AudioFeatureExtractor
-        extractor = AudioFeatureExtractor(self.sample_rate, self.n_mels, 1024, 512)
+        extractor = self._new_extractor()
         logger.info(f"{len(missing)} clips are not in the feature cache: extracting them on the GPU")
         failed = 0
         for start in range(0, len(missing), batch_size):
@@ -118,6 +121,11 @@ class FSCIntentDataset(Dataset):
         if failed:
             logger.error(f"{failed} of {len(missing)} uncached clips could not be processed (zero spectrograms)")
         return len(missing)
+
+    def _new_extractor(self):
+        from sir_amd.scripts.precompute_features import AudioFeatureExtractor
+        fe = self.frontend
+        return AudioFeatureExtractor(self.sample_rate, self.n_mels, fe.n_fft, fe.hop_length, fe.win_length)
 
     def __len__(self):
         return len(self.data)
@@ -154,9 +162,8 @@ class FSCIntentDataset(Dataset):
                 raise WorkerCacheMiss(f"{audio_path}: not in the feature cache and the GPU cannot be used from a DataLoader "
                                    "worker process; call dataset.prefetch_missing() in the main process, run "
                                    "scripts.precompute_features, or use num_workers=0")
-            from sir_amd.scripts.precompute_features import AudioFeatureExtractor
             if not hasattr(self, "_extractor"):
-                self._extractor = AudioFeatureExtractor(self.sample_rate, self.n_mels, 1024, 512)
+                self._extractor = self._new_extractor()
             feat = self._extractor.extract_features(audio_path, max_duration=5.0)
             return feat if feat is not None else zeros
         except WorkerCacheMiss:             # a set-up error of the job, not a bad clip: must not turn into silent zeros

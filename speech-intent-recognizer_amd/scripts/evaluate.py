@@ -65,9 +65,13 @@ def evaluate(args, config):
         state = state["model_state_dict"]
     model.load_state_dict(state)
     logger.info(f"Loaded model from {args.model_path}")
+    from sir_amd.frontend_config import FrontEnd
+    fe = FrontEnd.from_config(config)       # the checkpoint does not record its front-end: the keys must accompany it
     test_dataset = FSCIntentDataset(csv_path=args.test_csv, label_map_path=args.label_map, is_training=False,
                                     use_cache=config.get("use_feature_cache", True),
-                                    cache_dir=config.get("cache_dir", "data/cached_features"))
+                                    cache_dir=config.get("cache_dir", "data/cached_features"),
+                                    mel_spec_length=int(config.get("mel_spec_length", 200)),
+                                    n_fft=fe.n_fft, hop_length=fe.hop_length, win_length=fe.win_length)
     from sir_amd.scripts.train import loader_kwargs
     test_loader = DataLoader(test_dataset, batch_size=config.get("batch_size", 32), shuffle=False, collate_fn=collate_fn,
                              **loader_kwargs(config.get("num_workers", 4)))

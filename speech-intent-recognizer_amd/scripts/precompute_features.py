@@ -3,7 +3,9 @@
 Same surface: ``AudioFeatureExtractor(sample_rate, n_mels, n_fft, hop_length).extract_features(path,
 max_duration)`` -> ``FloatTensor[64, T]`` or ``None``; ``precompute_dataset_features(csv_path,
 output_dir, label_map_path, max_duration)`` -> cache path; the same CLI flags; the same
-``<csv-stem>_features.pt`` / ``cache_info.json`` formats.  What differs is how the work is done:
+``<csv-stem>_features.pt`` / ``cache_info.json`` formats.  Beyond the reference: ``win_length`` and the
+other supported front-ends (sir_amd/frontend_config.py; ``--n_fft / --hop_length / --win_length``), whose
+caches carry the front-end in their file name.  What differs is how the work is done:
 files are decoded on the host and pushed through ``sir_features_fwd`` in batches of several hundred
 clips (one launch pair per batch) instead of one torchaudio call chain per file
 (reference :124-130).  Errors follow the reference's convention: they are logged and the clip is
@@ -19,6 +21,7 @@ import torch
 
 from sir_amd import _native
 from sir_amd.featurizer import get_featurizer
+from sir_amd.frontend_config import as_frontend
 from sir_amd.scripts.utils import wav_io
 
 logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
@@ -30,16 +33,17 @@ DEFAULT_BATCH = 256
 class AudioFeatureExtractor:
     """Log-mel features with the reference's parameters (precompute_features.py:21-36)."""
 
-    def __init__(self, sample_rate=16000, n_mels=64, n_fft=1024, hop_length=512):
+    def __init__(self, sample_rate=16000, n_mels=64, n_fft=1024, hop_length=512, win_length=None):
         self.sample_rate = sample_rate
         self.n_mels = n_mels
         self.n_fft = n_fft
         self.hop_length = hop_length
+        self.win_length = n_fft if win_length is None else win_length
         self._fz = None
 
     def _featurizer(self):
         if self._fz is None:
-            self._fz = get_featurizer(self.sample_rate, self.n_mels, self.n_fft, self.hop_length)
+            self._fz = get_featurizer(self.sample_rate, self.n_mels, self.n_fft, self.hop_length, self.win_length)
         return self._fz
 
     # -- host side: decode only (precompute_features.py:47); mono / resample / truncate run on the GPU ----
@@ -136,15 +140,17 @@ class AudioFeatureExtractor:
 
 
 def precompute_dataset_features(csv_path, output_dir, label_map_path=None, max_duration=5.0,
-                                batch_size=DEFAULT_BATCH):
+                                batch_size=DEFAULT_BATCH, frontend=None):
     """CSV -> ``{path: {'features': FloatTensor[64,T], 'label': str}}`` saved with ``torch.save`` to
-    ``<output_dir>/<csv-stem>_features.pt`` (precompute_features.py:81-147)."""
+    ``<output_dir>/<csv-stem>_features.pt`` (precompute_features.py:81-147).  ``frontend`` (a ``FrontEnd``, a config dict
+    or None = default): another front-end writes ``<csv-stem>_features_n{n_fft}_h{hop}_w{win}.pt``."""
+    fe = as_frontend(frontend)
     df = pd.read_csv(csv_path)
     logger.info(f"Loaded {len(df)} samples from {csv_path}")
-    extractor = AudioFeatureExtractor()
+    extractor = AudioFeatureExtractor(n_fft=fe.n_fft, hop_length=fe.hop_length, win_length=fe.win_length)
     os.makedirs(output_dir, exist_ok=True)
     dataset_name = os.path.basename(csv_path).replace(".csv", "")
-    cache_file = os.path.join(output_dir, f"{dataset_name}_features.pt")
+    cache_file = os.path.join(output_dir, fe.cache_name(dataset_name))
 
     # label column fallbacks of precompute_features.py:108-120
     if "label" in df.columns:
@@ -186,14 +192,18 @@ def main():
     parser.add_argument("--output_dir", type=str, default="data/cached_features",
                         help="Output directory for cached features")
     parser.add_argument("--label_map", type=str, default=None, help="Path to label map JSON file")
+    parser.add_argument("--n_fft", type=int, default=None, help="FFT size: 256, 512 or 1024 (default 1024)")
+    parser.add_argument("--hop_length", type=int, default=None, help="Hop in samples, n_fft/16 .. n_fft (default 512)")
+    parser.add_argument("--win_length", type=int, default=None, help="Window length, <= n_fft (default n_fft)")
     args = parser.parse_args()
+    fe = as_frontend({"n_fft": args.n_fft, "hop_length": args.hop_length, "win_length": args.win_length})
     _native.require_hip()
     os.makedirs(args.output_dir, exist_ok=True)
     logger.info("Starting feature precomputation...")
     cache_info = {
-        "train_features": precompute_dataset_features(args.train_csv, args.output_dir, args.label_map),
-        "valid_features": precompute_dataset_features(args.valid_csv, args.output_dir, args.label_map),
-        "test_features": precompute_dataset_features(args.test_csv, args.output_dir, args.label_map),
+        "train_features": precompute_dataset_features(args.train_csv, args.output_dir, args.label_map, frontend=fe),
+        "valid_features": precompute_dataset_features(args.valid_csv, args.output_dir, args.label_map, frontend=fe),
+        "test_features": precompute_dataset_features(args.test_csv, args.output_dir, args.label_map, frontend=fe),
     }
     with open(os.path.join(args.output_dir, "cache_info.json"), "w") as f:
         json.dump(cache_info, f, indent=2)

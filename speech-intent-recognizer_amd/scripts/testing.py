@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from sir_amd import ops
-from sir_amd.featurizer import HOP, get_featurizer
+from sir_amd.frontend_config import as_frontend
 from sir_amd.segmenter import Segmenter
 from sir_amd.scripts import test_model, test_tts_samples
 
@@ -30,28 +30,33 @@ MAX_LENGTH = 200                 # testing.py:230
 MIN_FRAMES = test_tts_samples.MIN_FRAMES
 GROUP = 32                       # recordings per segmentation call and forward
 MAX_RECORDING_S = 3600.0         # a longer file is cut here
+TRAINED_LENGTH = "mel_spec_length"   # ``pad_to`` default: the recogniser's own ``mel_spec_length`` (200 unless it was given another)
 MAX_CLIP_S = 600.0               # un-padded scoring: a longer utterance is cut here (test_model.extract_features' bound)
 
 
 class IntentRecognizer:
-    def __init__(self, model_path, label_map_path, device=None, segmenter=None):
+    def __init__(self, model_path, label_map_path, device=None, segmenter=None, frontend=None, mel_spec_length=MAX_LENGTH):
         """Load the label map and the checkpoint (testing.py:159-191; the class count comes from the checkpoint's ``fc.weight``
         as in scripts/test_tts_samples.py, where the reference hard-codes 31).  ``segmenter``: the ``Segmenter`` that
-        ``recognize_recordings`` uses (default: the listener's defaults)."""
+        ``recognize_recordings`` uses (default: the listener's defaults).  ``frontend`` (a ``FrontEnd``, a config dict or None =
+        1024 / 512 / 1024) and ``mel_spec_length``: the front-end and frame count the checkpoint was trained with -- the
+        checkpoint does not record them."""
         self.device = torch.device("cuda") if device is None else torch.device(device)
         self.model, self.label_map = test_tts_samples.load_model(model_path, label_map_path, self.device)
-        self._finish(segmenter)
+        self._finish(segmenter, frontend, mel_spec_length)
 
     @classmethod
-    def from_model(cls, model, label_map, device=None, segmenter=None):
+    def from_model(cls, model, label_map, device=None, segmenter=None, frontend=None, mel_spec_length=MAX_LENGTH):
         """The recogniser around an already loaded ``CNNAudioGRU`` and label map."""
         self = cls.__new__(cls)
         self.device = torch.device("cuda") if device is None else torch.device(device)
         self.model, self.label_map = model.to(self.device).eval(), dict(label_map)
-        self._finish(segmenter)
+        self._finish(segmenter, frontend, mel_spec_length)
         return self
 
-    def _finish(self, segmenter):
+    def _finish(self, segmenter, frontend=None, mel_spec_length=MAX_LENGTH):
+        self.frontend = as_frontend(frontend)
+        self.mel_spec_length = int(mel_spec_length)
         self.inv_label_map = {v: k for k, v in self.label_map.items()}
         self.segmenter = segmenter if segmenter is not None else Segmenter()
         self.sample_rate = self.segmenter.sample_rate
@@ -64,12 +69,12 @@ class IntentRecognizer:
             wave = torch.as_tensor(np.ascontiguousarray(audio_data)).reshape(1, -1)
             if wave.dtype not in (torch.float32, torch.int16):
                 wave = wave.to(torch.float32)
-            fz = get_featurizer()
+            fz = self.frontend.featurizer()
             wave = wave.to(self.device)
             lens = torch.tensor([wave.shape[1]], dtype=torch.int32, device=self.device)
             if int(sample_rate) != self.sample_rate:
                 wave, lens = fz.resample(wave, int(sample_rate), self.sample_rate, lens)
-            feats = fz(wave, lens, t_pad=MAX_LENGTH)
+            feats = fz(wave, lens, t_pad=self.mel_spec_length)
             with torch.no_grad():
                 output = self.model(feats).cpu()
             ops.check_status()
@@ -114,12 +119,15 @@ class IntentRecognizer:
             batch[k, :lens[k]] = w.to(self.device)
         return batch, torch.tensor(lens, dtype=torch.int32, device=self.device)
 
-    def score_segments(self, wave, lengths, pad_to=MAX_LENGTH):
+    def score_segments(self, wave, lengths, pad_to=TRAINED_LENGTH):
         """Segment a GPU batch of recordings and score every utterance -> (seg_table int32 [n, 3] on the CPU, logits [n, C] on
         the CPU).  ``pad_to`` frames: every clip is cut to fewer than ``pad_to * hop`` samples (the trim of :231-232, in samples)
         and padded to ``pad_to`` frames; ``pad_to=None``: every clip is scored at its own length through the ragged forward
         (``lengths=``), a clip with fewer than 8 frames at 8."""
         seg = self.segmenter
+        hop = self.frontend.hop_length
+        if pad_to == TRAINED_LENGTH:
+            pad_to = self.mel_spec_length
         table, _, total = seg.segment(wave, lengths)
         host_table = table.cpu()
         n = host_table.shape[0]
@@ -127,10 +135,10 @@ class IntentRecognizer:
         if n == 0:
             return host_table, torch.zeros((0, num_classes), dtype=torch.float32)
         longest = int((host_table[:, 2] - host_table[:, 1]).max())
-        limit = pad_to * HOP - 1 if pad_to is not None else int(MAX_CLIP_S * seg.sample_rate)
+        limit = self.frontend.max_samples(pad_to) if pad_to is not None else int(MAX_CLIP_S * seg.sample_rate)
         clips, clip_lens = seg.gather(wave, table, total, max(1, min(longest, limit)))
-        fz = get_featurizer()
-        frames = (clip_lens // HOP + 1).clamp(min=MIN_FRAMES)
+        fz = self.frontend.featurizer()
+        frames = (clip_lens // hop + 1).clamp(min=MIN_FRAMES)
         t_pad = pad_to if pad_to is not None else int(frames.max().item())
         feats = fz(clips, clip_lens, t_pad=t_pad)
         with torch.no_grad():
@@ -139,7 +147,7 @@ class IntentRecognizer:
         ops.check_status()
         return host_table, logits
 
-    def recognize_recordings(self, waves_or_paths, pad_to=MAX_LENGTH):
+    def recognize_recordings(self, waves_or_paths, pad_to=TRAINED_LENGTH):
         """waves_or_paths: recordings as 1-D float32 / int16 arrays or tensors at the segmenter's sample rate, or paths of WAVE
         files (decoded, mixed to mono and resampled on the GPU).  -> per recording, the list of its utterances in time order:
         ``{"start": seconds, "end": seconds, "predicted_label", "confidence", "top_predictions"}``; ``None`` for the recordings of

@@ -155,7 +155,7 @@ def train_epoch(model, train_loader, optimizer, criterion, device, scaler=None, 
     return mean
 
 
-def train_epoch_waveforms(model, wave_loader, optimizer, criterion, device, t_pad=200, augment=None, mixup=None):
+def train_epoch_waveforms(model, wave_loader, optimizer, criterion, device, t_pad=200, augment=None, frontend=None, mixup=None):
     """``train_epoch`` fed with RAW waveform batches: ``wave_loader`` yields ``(wave [B, L] float32 | int16, lengths int32
     [B] | None, label int64 [B])``; the log-mel features are computed on the GPU (BASELINE configs[2]: fused HIP feature
     extraction + forward/backward + Adam) one batch ahead of the training step on a side stream
@@ -166,12 +166,13 @@ def train_epoch_waveforms(model, wave_loader, optimizer, criterion, device, t_pa
     dataset.py:160-176) for that batch, ``pitch_cents`` / ``tempo`` (``sir_wave_perturb`` ahead of the feature kernel) and the
     reverb / background-noise arguments of ``HipFeaturizer.reverb_mix`` (between the two).
     ``mixup`` as for ``train_epoch``: applied to the computed feature batch, after its SpecAugment bands.
+    ``frontend`` (sir_amd/frontend_config.py; None = 1024 / 512 / 1024): the front-end the features are computed with.
     Returns the mean of the per-step losses."""
     from sir_amd import ops
     from sir_amd.pipeline import FeaturePrefetcher
     model.train()
     loss_fn = _loss_fn(criterion)
-    pre = FeaturePrefetcher(t_pad=t_pad)
+    pre = FeaturePrefetcher(t_pad=t_pad, frontend=frontend)
     losses, pending = [], []
 
     def submit(idx, item):
@@ -224,7 +225,9 @@ def make_waveform_augment(config, seed=0, epoch=0, rng=None):
     ``snr_db``, drawn after every other draw of the batch.  Neither changes a clip's length.  With both keys absent or
     false the random stream and the returned dictionary are what they were without them."""
     import random
+    from sir_amd.frontend_config import FrontEnd
     from sir_amd.scripts import augment as aug
+    fe = FrontEnd.from_config(config)                   # the time masks are drawn against the clips' frame counts
     rng = rng or random.Random((int(seed) << 20) ^ int(epoch))
     banks = _reverb_noise_banks(config, seed)
     pitch_speed = bool(config.get("pitch_speed_augment", False))
@@ -246,7 +249,7 @@ def make_waveform_augment(config, seed=0, epoch=0, rng=None):
             shift, sigma = aug.draw_batch_params(host_lengths, wave_prob, rng)
             kw.update(shift=shift, noise_sigma=sigma, noise_seed=(int(seed) << 40) ^ (int(epoch) << 24) ^ int(idx))
         if spec_prob > 0.0:
-            tm, fm = aug.draw_spec_masks([1 + n // 512 for n in frame_lengths], spec_prob, rng=rng)
+            tm, fm = aug.draw_spec_masks([fe.num_frames(n) for n in frame_lengths], spec_prob, rng=rng)
             kw.update(time_mask=tm, freq_mask=fm)
         if banks:
             kw.update(aug.draw_reverb_noise_params(frame_lengths, banks["cfg"], rng))
@@ -407,6 +410,7 @@ def train(args, config):
     of ``(seed, epoch, rank)``.  The DataLoader route (``hbm_feature_cache: false``) draws SpecAugment from its worker
     processes' global RNGs: it resumes, but not bit-exactly.  A run cut off inside an epoch repeats that epoch."""
     from sir_amd import _native, run_state, train_ops  # noqa: F401
+    from sir_amd.frontend_config import FrontEnd
     from sir_amd.models.models import CNNAudioGRU
     from sir_amd.optim import FusedAdam
     from sir_amd.scripts.dataset import FSCIntentDataset
@@ -421,6 +425,10 @@ def train(args, config):
 
     cache_dir = config.get("cache_dir", "data/cached_features")
     use_cache = config.get("use_feature_cache", True)
+    # `n_fft` / `hop_length` / `win_length` (defaults 1024 / 512 / n_fft): the feature front-end, read once and handed to every
+    # route below; `mel_spec_length` is the model's t_pad (3 s at hop 160 is 301 frames).
+    fe = FrontEnd.from_config(config)
+    fe_kw = dict(n_fft=fe.n_fft, hop_length=fe.hop_length, win_length=fe.win_length)
     # Two YAML keys beyond the reference's, both off by default (= reference behaviour: cached features through
     # DataLoader workers).  `fused_features: true` trains from RAW waveforms staged once in HBM, features computed on
     # the GPU inside the step (BASELINE configs[2]); `waveform_augment: true` (implies fused_features) adds the
@@ -445,14 +453,17 @@ def train(args, config):
     t_pad = int(config.get("mel_spec_length", MAX_LENGTH))
     if hbm_cache:
         from sir_amd.feature_store import FeatureStore
-        train_dataset = FeatureStore(args.train_csv, args.label_map, device, use_cache=use_cache, cache_dir=cache_dir, mel_spec_length=t_pad)
-        val_dataset = FeatureStore(args.val_csv, args.label_map, device, use_cache=use_cache, cache_dir=cache_dir, mel_spec_length=t_pad)
+        train_dataset = FeatureStore(args.train_csv, args.label_map, device, use_cache=use_cache, cache_dir=cache_dir, mel_spec_length=t_pad,
+                                     frontend=fe)
+        val_dataset = FeatureStore(args.val_csv, args.label_map, device, use_cache=use_cache, cache_dir=cache_dir, mel_spec_length=t_pad,
+                                   frontend=fe)
     else:
         train_dataset = train_store if fused else \
             FSCIntentDataset(csv_path=args.train_csv, label_map_path=args.label_map, is_training=True,
-                             augment_prob=config.get("augment_prob", 0.5), use_cache=use_cache, cache_dir=cache_dir)
+                             augment_prob=config.get("augment_prob", 0.5), use_cache=use_cache, cache_dir=cache_dir,
+                             mel_spec_length=t_pad, **fe_kw)
         val_dataset = FSCIntentDataset(csv_path=args.val_csv, label_map_path=args.label_map, is_training=False,
-                                       use_cache=use_cache, cache_dir=cache_dir)
+                                       use_cache=use_cache, cache_dir=cache_dir, mel_spec_length=t_pad, **fe_kw)
     if rank == 0:
         print(f"Datasets loaded - Train: {len(train_dataset)}, Val: {len(val_dataset)}")
 
@@ -526,7 +537,7 @@ def train(args, config):
             train_loss = train_epoch_waveforms(model, batches, optimizer, train_criterion, device,
                                                t_pad=t_pad,
                                                augment=make_waveform_augment(config, seed=seed + 977 * rank, epoch=epoch),
-                                               mixup=mixup)
+                                               mixup=mixup, frontend=fe)
         elif hbm_cache:
             batches = train_dataset.epoch_batches(bs, rank, world, shuffle=True, seed=seed, epoch=epoch,
                                                   augment_prob=float(config.get("augment_prob", 0.5)))

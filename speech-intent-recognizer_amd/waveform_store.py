@@ -113,6 +113,9 @@ class WaveformStore:
             yield self.wave.index_select(0, idx), self.lengths.index_select(0, idx), self.labels.index_select(0, idx), host_lens
 
 
-def frames_of(lengths, hop=512):
-    """Un-padded frame count per clip (1 + L // hop), host list."""
+def frames_of(lengths, hop=512, frontend=None):
+    """Un-padded frame count per clip (1 + L // hop), host list.  ``frontend`` (sir_amd/frontend_config.py): take its hop."""
+    if frontend is not None:
+        from .frontend_config import as_frontend
+        hop = as_frontend(frontend).hop_length
     return [1 + int(v) // hop for v in lengths]

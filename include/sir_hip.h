@@ -236,6 +236,34 @@ int sir_gather_features(sir_handle* h, const float* store, int64_t n_store, cons
 int sir_mix_features(sir_handle* h, const float* x, const int64_t* perm, const float* lam, int batch, int n_mels, int t,
                      float* out, void* stream);
 
+/* sir_adv_step: one ascent / projection step of an L-infinity adversary (FGSM: Goodfellow et al. 2015; PGD: Madry et al. 2018) on
+ * an ASSEMBLED feature batch, in one launch.  Replaces the torch lines `x + eps * dx.sign()` of sir_amd.explain.fgsm and the
+ * `x = clamp(x + alpha * g.sign(), x0 - eps, x0 + eps)` of a PGD loop; the reference has neither (it never attacks its model).
+ *   x0, x, g, out : [batch][n_mels][t] f32 (device); n_mels in [1, 64], any t >= 1
+ *   active        : device int32[batch], 0 = leave that row alone; NULL = every row is active
+ * Gradient step (g != NULL; x is the current iterate and may be x0 itself): with s = +1 where g > 0, -1 where g < 0, else 0 (a
+ * NaN gradient gives 0; a select, not a multiply),
+ *     out = fminf(fmaxf(x + s * alpha, x0 - eps), x0 + eps)
+ * in fp32, every operation rounded on its own (nothing is contracted).  out may BE x (in place); it must not overlap x0 or g.
+ * Random start (g == NULL; x must be NULL too, alpha is not read): U = the 24-bit uniform of the dropout mask's hash (hash of
+ * start_seed and the element index (b * n_mels + m) * t + j, >> 40, * 2^-24), r = 2 U - 1 (exact),
+ *     out = fminf(fmaxf(x0 + eps * r, x0 - eps), x0 + eps).
+ * Left alone -- bit-exact copies of x0, -0.0 and NaN payloads included (a select between words, no arithmetic): every row with
+ * active[b] == 0 and, with keep_zero_columns, every frame column j of row b whose n_mels values of x0 are all bit pattern 0.
+ * Zero padding and SpecAugment time bands so stay what they were (sir_model_infer's pad-skip rule: a column of -0.0 is data).
+ * NULL h / x0 / out / cfg, batch or t < 1, n_mels outside [1, 64], a negative or NaN eps (or alpha, on a gradient step), x
+ * without g, g without x, a forbidden overlap and a pointer that is not 4-byte aligned are SIR_EINVAL; every argument is checked
+ * before the launch and a refused call writes nothing.  No allocation, no workspace, no atomics, no status bit; row b depends
+ * on row b alone.  16-byte accesses when t % 4 == 0 and all pointers are 16-byte aligned, element accesses otherwise. */
+typedef struct sir_adv_config {
+    float eps;                /* radius of the L-infinity ball around x0, >= 0 */
+    float alpha;              /* step size, >= 0 (not read on a random-start call) */
+    int   keep_zero_columns;  /* != 0: a frame column of x0 whose n_mels values are all +0.0 (bit pattern 0) is left as it is */
+} sir_adv_config;
+int sir_adv_step(sir_handle* h, const float* x0, const float* x, const float* g, const int32_t* active,
+                 int batch, int n_mels, int t, const sir_adv_config* cfg, uint64_t start_seed,
+                 float* out, void* stream);
+
 /* ---- model path ----------------------------------------------------------------------------
  * Device pointers to the reference's parameters/buffers under their state_dict names
  * (models/models.py:10-39): index 0..2 = conv1..3 / bn1..3; GRU index = 2*layer + reverse. */

@@ -62,6 +62,10 @@ class VadConfig(C.Structure):
                 ("flush_tail", C.c_int)]
 
 
+class AdvConfig(C.Structure):
+    _fields_ = [("eps", C.c_float), ("alpha", C.c_float), ("keep_zero_columns", C.c_int)]
+
+
 # name -> (restype, argtypes); must list every function declared in include/sir_hip.h
 SIGNATURES = {
     "sir_abi_version": (C.c_int, []),
@@ -100,6 +104,8 @@ SIGNATURES = {
                                       C.c_void_p, C.c_void_p]),
     "sir_mix_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                    C.c_void_p]),
+    "sir_adv_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                               C.POINTER(AdvConfig), C.c_uint64, C.c_void_p, C.c_void_p]),
     "sir_model_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "sir_model_workspace_offsets": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.c_int]),
     "sir_model_set_weights_version": (C.c_int, [C.c_void_p, C.c_uint64]),

@@ -111,6 +111,51 @@ def fgsm(model, x, labels, eps, lengths=None):
     return x.detach() + eps * dx.sign_()
 
 
+def pgd(model, x, labels, eps, alpha=None, steps=10, random_start=False, seed=0, keep_zero_columns=False, lengths=None):
+    """The projected-gradient-descent adversarial example (Madry et al. 2018) inside the L-infinity ball of radius ``eps`` around
+    ``x``, in the shape of ``x``: ``steps`` iterations of ``clamp(x_k + alpha * sign(d CE(model(x_k), labels) / d x_k), x - eps,
+    x + eps)``, each one eval-semantics forward / data-only backward (``_forward``) and ONE ``sir_adv_step`` launch; with
+    ``random_start`` the first iterate is ``x + eps * (2 U - 1)`` keyed by ``seed``.  ``alpha=None``: ``train_ops.default_adv_alpha``.
+    ``keep_zero_columns``: all-zero frame columns of ``x`` (padding) stay zero.  ``pgd(steps=1, alpha=eps)`` returns the bits of
+    ``fgsm``."""
+    from . import train_ops
+    eps, steps = float(eps), int(steps)
+    if not eps >= 0.0:
+        raise ValueError("eps must be >= 0")
+    if steps < 1:
+        raise ValueError("steps must be >= 1")
+    alpha = train_ops.default_adv_alpha(eps, steps, bool(random_start)) if alpha is None else float(alpha)
+    if not alpha >= 0.0:
+        raise ValueError("alpha must be >= 0")
+    seed = int(seed)
+    if not 0 <= seed < (1 << 64):
+        raise ValueError("seed must fit 64 bits")
+    _validate(model, x, lengths)
+    labels = _index_vector(labels, x.shape[0], "labels").to(x.device)
+    x0 = x.detach().contiguous()
+    cur = x0
+    if random_start:
+        cur = train_ops.adv_step(x0, None, None, eps, alpha, seed=seed, keep_zero_columns=keep_zero_columns)
+    for _ in range(steps):
+        logits, leaf = _forward(model, cur)
+        with torch.enable_grad():
+            loss = train_ops.fused_cross_entropy(logits, labels)
+        (dx,) = torch.autograd.grad(loss, leaf)
+        cur = train_ops.adv_step(x0, cur, dx, eps, alpha, keep_zero_columns=keep_zero_columns, out=None if cur is x0 else cur)
+    return cur
+
+
+def robust_accuracy(model, x, labels, eps, **pgd_kw):
+    """``(clean_correct, adversarial_correct)``: how many clips of the batch the model (eval semantics, ``model.predict``) gets
+    right as they are and after ``pgd(model, x, labels, eps, **pgd_kw)``, as device int64 scalars (no host sync)."""
+    x_adv = pgd(model, x, labels, eps, **pgd_kw)
+    labels = _index_vector(labels, x.shape[0], "labels").to(x.device)
+    _, clean = model.predict(x.detach())
+    clean = (clean == labels).sum()
+    _, adv = model.predict(x_adv)
+    return clean, (adv == labels).sum()
+
+
 # ---- down to the waveform -------------------------------------------------------------------------------------------------
 def _class_vector(model, v, bsz, name):
     """``_index_vector`` plus, for a host tensor, the range check (a device tensor is checked by the loss kernel / scatter)."""

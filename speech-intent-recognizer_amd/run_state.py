@@ -7,7 +7,7 @@ What a run carries from one epoch into the next is defined by what the step read
   group index -- plus the learning rate the scheduler left in ``param_groups``;
 * the LR scheduler's own counters;
 * the dropout step counter of ``train_ops`` (the key of every inter-layer dropout mask), per rank;
-* ``Mixup.rng`` (one host ``random.Random`` per rank);
+* ``Mixup.rng`` and ``Adversary.rng`` (one host ``random.Random`` each per rank);
 * the epoch number, ``best_val_acc`` and the early-stopping count.
 
 Data order and augmentation are NOT part of it on the two routes that guarantee a bit-exact resume: there they are pure
@@ -34,7 +34,7 @@ LATEST = "latest_checkpoint.pt"
 # the YAML keys of scripts/train.py that shape the saved state (kept in the file; `load_run_state` reports the ones that
 # differ from the resuming run's)
 STATE_KEYS = ("optimizer", "lr", "weight_decay", "clip_grad_norm", "lr_schedule", "ema_decay", "ema_warmup", "mixup",
-              "label_smoothing", "batch_size", "seed", "num_labels", "freeze")
+              "label_smoothing", "batch_size", "seed", "num_labels", "freeze", "adversarial")
 
 
 def _rank_world(rank, world):
@@ -55,11 +55,12 @@ def state_config(config):
 
 
 def save_run_state(path, model, optimizer, scheduler=None, mixup=None, epoch=0, best_val_acc=0.0, no_improve_count=0,
-                   config=None, rank=None, world=None):
+                   config=None, rank=None, world=None, adversary=None):
     """Write the run state AFTER epoch ``epoch`` (0-based: the resumed run starts at ``epoch + 1``).  Collective when
     ``world > 1``: every rank calls it; rank 0 writes.  Returns ``path`` on rank 0, ``None`` elsewhere."""
     rank, world = _rank_world(rank, world)
-    mine = {"dropout_step": train_ops.dropout_step(), "mixup_rng": mixup.rng.getstate() if mixup is not None else None}
+    mine = {"dropout_step": train_ops.dropout_step(), "mixup_rng": mixup.rng.getstate() if mixup is not None else None,
+            "adversary_rng": adversary.rng.getstate() if adversary is not None else None}
     per_rank = [mine]
     if world > 1 and torch.distributed.is_available() and torch.distributed.is_initialized():
         per_rank = [None] * world
@@ -91,11 +92,12 @@ def save_run_state(path, model, optimizer, scheduler=None, mixup=None, epoch=0, 
     return path
 
 
-def load_run_state(path, model, optimizer, scheduler=None, mixup=None, config=None, rank=None, world=None, map_location=None):
+def load_run_state(path, model, optimizer, scheduler=None, mixup=None, config=None, rank=None, world=None, map_location=None,
+                   adversary=None):
     """Put a saved run state back into fresh objects; every rank calls it and takes its own per-rank entry.  Returns
     ``{"epoch", "best_val_acc", "no_improve_count", "config", "config_changed"}`` (``epoch``: the last finished one).
     Raises ``ValueError`` -- before anything is loaded -- when the world size, the parameter layout, or the presence of a
-    scheduler / mixup differs from the saved run's."""
+    scheduler / mixup / adversary differs from the saved run's (a file from before ``adversary_rng`` existed had none)."""
     rank, world = _rank_world(rank, world)
     if map_location is None:
         params = [p for group in optimizer.param_groups for p in group["params"]]
@@ -105,7 +107,7 @@ def load_run_state(path, model, optimizer, scheduler=None, mixup=None, config=No
         raise ValueError(f"{path}: not a run state of format {FORMAT} (a bare state dict such as best_model.pt cannot be resumed)")
     if int(state["world_size"]) != world:
         raise ValueError(f"{path}: saved by a run of world size {state['world_size']}, this run has world size {world}: the "
-                         "per-rank dropout and mixup state does not carry over")
+                         "per-rank dropout, mixup and adversary state does not carry over")
     layout = param_layout(optimizer)
     if state["param_layout"] != layout:
         def brief(lay):
@@ -113,7 +115,8 @@ def load_run_state(path, model, optimizer, scheduler=None, mixup=None, config=No
         raise ValueError(f"{path}: saved parameter layout {brief(state['param_layout'])} differs from this run's {brief(layout)} "
                          "(another model, label set or freeze list)")
     for name, obj, saved in (("LR scheduler", scheduler, state["scheduler_state_dict"]),
-                             ("mixup", mixup, state["per_rank"][rank]["mixup_rng"])):
+                             ("mixup", mixup, state["per_rank"][rank]["mixup_rng"]),
+                             ("adversary", adversary, state["per_rank"][rank].get("adversary_rng"))):
         if (obj is None) != (saved is None):
             raise ValueError(f"{path}: the saved run had {'a' if saved is not None else 'no'} {name}, this run has "
                              f"{'one' if obj is not None else 'none'}")
@@ -124,6 +127,8 @@ def load_run_state(path, model, optimizer, scheduler=None, mixup=None, config=No
     mine = state["per_rank"][rank]
     if mixup is not None:
         mixup.rng.setstate(mine["mixup_rng"])
+    if adversary is not None:
+        adversary.rng.setstate(mine["adversary_rng"])
     train_ops.set_dropout_step(mine["dropout_step"])
     saved_cfg, now = state.get("config") or {}, state_config(config)
     changed = sorted(k for k in set(saved_cfg) | set(now) if saved_cfg.get(k) != now.get(k)) if config is not None else []

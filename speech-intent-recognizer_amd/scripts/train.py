@@ -119,8 +119,12 @@ def train_epoch(model, train_loader, optimizer, criterion, device, scaler=None, 
     CPU path), so no loss scaling is needed or applied.  ``mixup`` (a ``train_ops.Mixup``): every assembled batch is
     mixed with a permutation of itself on the GPU and the loss takes both label sets.  An LR scheduler rides on the
     optimizer (``step_scheduler_with``): it is stepped after every ``optimizer.step()`` below, the zero-contribution step of
-    an empty shard included, so every rank keeps the same learning rate."""
+    an empty shard included, so every rank keeps the same learning rate.  A ``train_ops.Adversary`` rides on the model the same
+    way (``train_ops.set_adversary(model, adversary)``: the signature stays the reference's): after mixup, the assembled batch is
+    replaced by its adversarial example against the step's own loss (label smoothing and both mixup label sets included);
+    crafting leaves the module untouched and holds no collective, so an empty-shard rank simply skips it."""
     from sir_amd import ops, train_ops
+    adversary = train_ops.adversary_of(model)
     model.train()
     loss_fn = _loss_fn(criterion)
     losses = []
@@ -140,8 +144,12 @@ def train_epoch(model, train_loader, optimizer, criterion, device, scaler=None, 
         optimizer.zero_grad(set_to_none=True)
         if mixup is not None:
             mel, label_b, lam = mixup(mel, label)
+            if adversary is not None:
+                mel = adversary(model, mel, lambda out: _mixed_loss(loss_fn, out, label, label_b, lam))
             loss = _mixed_loss(loss_fn, model(mel), label, label_b, lam)
         else:
+            if adversary is not None:
+                mel = adversary(model, mel, lambda out: loss_fn(out, label))
             output = model(mel)
             loss = loss_fn(output, label)
         loss.backward()
@@ -166,10 +174,13 @@ def train_epoch_waveforms(model, wave_loader, optimizer, criterion, device, t_pa
     dataset.py:160-176) for that batch, ``pitch_cents`` / ``tempo`` (``sir_wave_perturb`` ahead of the feature kernel) and the
     reverb / background-noise arguments of ``HipFeaturizer.reverb_mix`` (between the two).
     ``mixup`` as for ``train_epoch``: applied to the computed feature batch, after its SpecAugment bands.
+    An adversary set on the model (``train_ops.set_adversary``) as for ``train_epoch``: applied to the feature batch after mixup
+    (the attack is on the features, not the audio).
     ``frontend`` (sir_amd/frontend_config.py; None = 1024 / 512 / 1024): the front-end the features are computed with.
     Returns the mean of the per-step losses."""
-    from sir_amd import ops
+    from sir_amd import ops, train_ops
     from sir_amd.pipeline import FeaturePrefetcher
+    adversary = train_ops.adversary_of(model)
     model.train()
     loss_fn = _loss_fn(criterion)
     pre = FeaturePrefetcher(t_pad=t_pad, frontend=frontend)
@@ -191,8 +202,12 @@ def train_epoch_waveforms(model, wave_loader, optimizer, criterion, device, t_pa
         optimizer.zero_grad(set_to_none=True)
         if mixup is not None:
             mixed, label_b, lam = mixup(mel, label)
+            if adversary is not None:
+                mixed = adversary(model, mixed, lambda out: _mixed_loss(loss_fn, out, label, label_b, lam))
             loss = _mixed_loss(loss_fn, model(mixed), label, label_b, lam)
         else:
+            if adversary is not None:                   # (a new tensor: the prefetcher's buffer is read, never written)
+                mel = adversary(model, mel, lambda out: loss_fn(out, label))
             loss = loss_fn(model(mel), label)
         loss.backward()
         optimizer.step()
@@ -346,6 +361,57 @@ def step_scheduler_with(optimizer, scheduler):
     return optimizer.register_step_post_hook(lambda opt, args, kwargs: scheduler.step())
 
 
+ADVERSARIAL_KEYS = ("eps", "alpha", "steps", "random_start", "prob", "validate")
+
+
+def adversarial_options(config):
+    """The ``adversarial`` YAML key of ``train()`` -- ``{eps, alpha, steps, random_start, prob, validate}``, absent by default --
+    as the keyword arguments of ``train_ops.Adversary`` plus ``validate``; ``None`` when the key is absent or empty.  Raises
+    ``ValueError`` for unknown keys, a missing or negative ``eps``, ``steps < 1``, ``prob`` outside [0, 1] or a negative
+    ``alpha``: on the host, before any device call."""
+    spec = config.get("adversarial")
+    if not spec:
+        return None
+    if not isinstance(spec, dict):
+        raise ValueError("adversarial: expected a mapping {eps, alpha, steps, random_start, prob, validate}")
+    unknown = set(spec) - set(ADVERSARIAL_KEYS)
+    if unknown:
+        raise ValueError(f"adversarial: unknown keys {sorted(unknown)}")
+    if "eps" not in spec:
+        raise ValueError("adversarial: eps is required")
+    eps, steps, prob = float(spec["eps"]), int(spec.get("steps", 1)), float(spec.get("prob", 1.0))
+    alpha = float(spec["alpha"]) if spec.get("alpha") is not None else None
+    if not eps >= 0.0:
+        raise ValueError("adversarial: eps must be >= 0")
+    if steps < 1:
+        raise ValueError("adversarial: steps must be >= 1")
+    if not 0.0 <= prob <= 1.0:
+        raise ValueError("adversarial: prob must be in [0, 1]")
+    if alpha is not None and not alpha >= 0.0:
+        raise ValueError("adversarial: alpha must be >= 0")
+    return {"eps": eps, "alpha": alpha, "steps": steps, "random_start": bool(spec.get("random_start", True)), "prob": prob,
+            "validate": bool(spec.get("validate", False))}
+
+
+def validate_robust(model, val_loader, device, eps, **pgd_kw):
+    """Robust validation accuracy: the share of the loader's clips still classified correctly after ``explain.pgd`` (eval
+    semantics; all-zero padding columns kept) at radius ``eps``; under data parallelism the counts are summed over ranks."""
+    from sir_amd import explain, ops, train_ops
+    model.eval()
+    stage = HostStager(device)
+    counts = torch.zeros(3, dtype=torch.int64, device=device)         # clean correct, adversarial correct, clips
+    for mel, label in val_loader:
+        if mel is None or label is None or mel.size(0) == 0:
+            continue
+        mel, label = stage(mel), stage(label)
+        clean, adv = explain.robust_accuracy(model, mel, label, eps, keep_zero_columns=True, **pgd_kw)
+        counts += torch.stack([clean, adv, torch.full_like(clean, label.size(0))])
+    ops.check_status()
+    train_ops.all_reduce_sum_(counts)
+    clean, adv, total = (int(v) for v in counts.tolist())
+    return clean / max(total, 1), adv / max(total, 1)
+
+
 def run_options(config):
     """The run-management YAML keys of ``train()`` as one dict, every one absent by default (= no scheduler, no shadow, no
     ``latest_checkpoint.pt``, plain Adam): ``optimizer: adam | adamw``, ``lr_schedule``, ``ema_decay`` / ``ema_warmup``,
@@ -415,6 +481,7 @@ def train(args, config):
     from sir_amd.optim import FusedAdam
     from sir_amd.scripts.dataset import FSCIntentDataset
 
+    adv_opts = adversarial_options(config)            # (a bad `adversarial` key raises here, before any device call)
     _native.require_hip()
     train_ops.limit_host_threads(reserve=int(config.get("num_workers", 2)))     # (the DataLoader workers get their share of the CPU quota)
     rank, world, local_rank = train_ops.init_distributed()
@@ -496,10 +563,18 @@ def train(args, config):
     # `label_smoothing: <eps>` and `mixup: <alpha>` change the training loss (validation keeps the plain criterion);
     # `clip_grad_norm: <max_norm>` clips the global gradient norm inside the optimizer step.  The reference's own
     # `grad_clip` / `mixup_alpha` keys stay unread, as the reference leaves them.
+    # `adversarial: {eps, alpha, steps, random_start, prob, validate}` (absent by default): FGSM / PGD adversarial training in
+    # the feature domain -- each assembled batch is replaced by its adversarial example against the step's own loss
+    # (train_ops.Adversary); `validate: true` also logs the robust validation accuracy per epoch.
     opts = run_options(config)
     criterion = nn.CrossEntropyLoss()
     train_criterion = nn.CrossEntropyLoss(label_smoothing=float(config["label_smoothing"])) if config.get("label_smoothing") else criterion
     mixup = train_ops.Mixup(float(config["mixup"]), seed=seed + 977 * rank) if config.get("mixup") else None
+    adversary = None
+    if adv_opts:
+        adversary = train_ops.Adversary(adv_opts["eps"], alpha=adv_opts["alpha"], steps=adv_opts["steps"],
+                                        random_start=adv_opts["random_start"], prob=adv_opts["prob"], seed=seed + 1231 * rank)
+    train_ops.set_adversary(model, adversary)         # rides on the model: train_epoch / train_epoch_waveforms keep their signatures
     optimizer = FusedAdam([p for p in model.parameters() if p.requires_grad], lr=float(config.get("lr", 0.0003)),
                           weight_decay=float(config.get("weight_decay", 0.0001)),
                           max_grad_norm=float(config["clip_grad_norm"]) if config.get("clip_grad_norm") else None,
@@ -522,7 +597,7 @@ def train(args, config):
         step_scheduler_with(optimizer, scheduler)
     first_epoch = 0
     if opts["resume_path"]:
-        got = run_state.load_run_state(opts["resume_path"], model, optimizer, scheduler, mixup, config=config)
+        got = run_state.load_run_state(opts["resume_path"], model, optimizer, scheduler, mixup, config=config, adversary=adversary)
         first_epoch, best_val_acc, no_improve_count = got["epoch"] + 1, got["best_val_acc"], got["no_improve_count"]
         if rank == 0:
             print(f"Resumed {opts['resume_path']}: epoch {first_epoch} done, best accuracy {best_val_acc:.4f}"
@@ -554,6 +629,13 @@ def train(args, config):
             val_loss, val_acc = validate(model, val_loader, criterion, device, None)
         if rank == 0:
             print(f"Train loss: {train_loss:.4f}, Val loss: {val_loss:.4f}, Val accuracy: {val_acc:.4f}")
+        if adv_opts and adv_opts["validate"]:         # the same attack as in training, from the clip itself, eval semantics
+            if hbm_cache:
+                val_loader = val_dataset.epoch_batches(bs * 2, rank, world, shuffle=False, pad=False)
+            _, robust_acc = validate_robust(model, val_loader, device, adv_opts["eps"], alpha=adv_opts["alpha"],
+                                            steps=adv_opts["steps"])
+            if rank == 0:
+                print(f"Robust val accuracy (eps {adv_opts['eps']:g}, {adv_opts['steps']} steps): {robust_acc:.4f}")
         if val_acc > best_val_acc:
             best_val_acc = val_acc
             no_improve_count = 0
@@ -569,7 +651,8 @@ def train(args, config):
                 print(f"No improvement for {no_improve_count} epochs")
         if opts["checkpoint_path"]:                   # after the bookkeeping above: a resumed run starts at epoch + 1
             run_state.save_run_state(opts["checkpoint_path"], model, optimizer, scheduler, mixup, epoch=epoch,
-                                     best_val_acc=best_val_acc, no_improve_count=no_improve_count, config=config)
+                                     best_val_acc=best_val_acc, no_improve_count=no_improve_count, config=config,
+                                     adversary=adversary)
         if no_improve_count >= patience:
             if rank == 0:
                 print(f"Early stopping after {epoch + 1} epochs")

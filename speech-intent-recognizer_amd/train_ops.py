@@ -189,12 +189,29 @@ def _bn_ptr_arrays(mod):
     return rm, rv
 
 
+def _scratch_running_stats(mod, st, cfg, rm, rv):
+    """Crafting pass: point the running-statistics update of every LIVE BatchNorm block at a scratch buffer kept beside the
+    module's training state (the kernels only write it for such a block: its forward and backward use the batch statistics),
+    so that ``running_mean`` / ``running_var`` stay as they are bit for bit.  Frozen blocks keep the module's pointers: they
+    are read, never written."""
+    dev = next(mod.parameters()).device
+    scratch = st.get("craft_bn")
+    if scratch is None or scratch[0].device != dev:
+        scratch = st["craft_bn"] = [torch.zeros(2, getattr(mod, f"bn{i}").num_features, dtype=torch.float32, device=dev)
+                                    for i in (1, 2, 3)]
+    for i in range(3):
+        if not cfg.bn_frozen[i]:
+            rm[i], rv[i] = scratch[i][0].data_ptr(), scratch[i][1].data_ptr()
+
+
 class _TrainStep(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mod, opts, *params):
-        # opts = (sir_train_config, dropout p, step): step == False (sir_amd.explain) draws no dropout key and leaves the
-        # step counter and ``mod._sir_last_dropout`` alone
-        cfg, dropout_p, step = opts
+        # opts = (sir_train_config, dropout p, step[, craft]): step == False (sir_amd.explain) draws no dropout key and leaves
+        # the step counter and ``mod._sir_last_dropout`` alone; craft == True (``forward_craft``) also keeps the LIVE BatchNorm
+        # blocks' running statistics, ``num_batches_tracked`` and the cached-weights epoch as they are
+        cfg, dropout_p, step = opts[:3]
+        craft = len(opts) > 3 and bool(opts[3])
         lib = _native.lib()
         h = get_featurizer().handle
         x_shape = x.shape
@@ -207,6 +224,8 @@ class _TrainStep(torch.autograd.Function):
         ws = st["ws"].get(need, x.device)
         w, keep = ops.cached_weights(mod)
         rm, rv = _bn_ptr_arrays(mod)
+        if craft:
+            _scratch_running_stats(mod, st, cfg, rm, rv)
         logits = torch.empty((bsz, w.num_classes), dtype=torch.float32, device=x.device)
         seed = 0
         if step:
@@ -217,7 +236,7 @@ class _TrainStep(torch.autograd.Function):
                                          C.byref(cfg), logits.data_ptr(), ws.data_ptr(), ws.numel(),
                                          _native.current_stream_ptr())
         _native.check(rc, "sir_model_train_fwd_cfg")
-        live = [getattr(mod, f"bn{i + 1}").num_batches_tracked for i in range(3) if not cfg.bn_frozen[i]]
+        live = [] if craft else [getattr(mod, f"bn{i + 1}").num_batches_tracked for i in range(3) if not cfg.bn_frozen[i]]
         if live:                                     # frozen statistics: nothing was written, cached layouts stay valid
             ops.bump_weights_epoch()                 # BN running statistics were updated in place
             torch._foreach_add_(live, 1)
@@ -340,6 +359,156 @@ def forward_train(mod, x):
     _native.require_hip(x)
     ops._as_features(x)                              # (shape / dtype checks; the node itself takes x in the caller's shape)
     return _TrainStep.apply(x, mod, step_config(mod) + (True,), *param_list(mod))
+
+
+def forward_craft(mod, x):
+    """``(logits, leaf)`` of the crafting pass of an adversary: the training-path forward with the module's own flags
+    (``bnK.eval()`` blocks on their running statistics, the others on batch statistics) and NO side effect -- inter-layer
+    dropout off and no key drawn (``dropout_step()`` unchanged), running statistics, ``num_batches_tracked`` and the
+    cached-weights epoch untouched.  ``leaf`` is ``x`` detached with ``requires_grad``; ``torch.autograd.grad(loss, leaf)`` runs
+    ``sir_model_train_bwd_x`` with all 29 gradient pointers NULL: no ``p.grad`` is touched and nothing is exchanged between
+    ranks."""
+    _native.require_hip(x)
+    ops._as_features(x)
+    leaf = x.detach().requires_grad_(True)
+    with torch.enable_grad():
+        logits = _TrainStep.apply(leaf, mod, (bn_config(mod), 0.0, False, True), *[p.detach() for p in param_list(mod)])
+    return logits, leaf
+
+
+def _adv_check(eps, alpha, *tensors):
+    """Host-side validation of ``adv_step``: raises before any device call."""
+    eps, alpha = float(eps), float(alpha)
+    if not eps >= 0.0:
+        raise ValueError("eps must be >= 0")
+    if not alpha >= 0.0:
+        raise ValueError("alpha must be >= 0")
+    shape = None
+    for name, v in tensors:
+        if v is None:
+            continue
+        if not torch.is_tensor(v) or v.dtype != torch.float32:
+            raise ValueError(f"{name} must be a float32 tensor [B,64,T] or [B,1,64,T]")
+        sh = tuple(v.shape)
+        if not ((len(sh) == 3 and sh[1] == 64) or (len(sh) == 4 and sh[1] == 1 and sh[2] == 64)) or sh[0] < 1 or sh[-1] < 1:
+            raise ValueError(f"{name}: expected [B,64,T] or [B,1,64,T], got {sh}")
+        if shape is not None and (sh[0], sh[-1]) != shape:
+            raise ValueError(f"{name}: shape {sh} does not match x0's batch {shape[0]} and {shape[1]} frames")
+        shape = (sh[0], sh[-1])
+    if any(v is not None and not v.is_cuda for _, v in tensors):
+        raise _native.SirError("tensor is not on a HIP device: this path runs on MI355X only (no CPU fallback)")
+    return eps, alpha, shape
+
+
+def adv_step(x0, x, g, eps, alpha, active=None, seed=0, keep_zero_columns=True, out=None):
+    """One ascent / projection step of an L-infinity adversary by ``sir_adv_step`` (include/sir_hip.h has the arithmetic).
+    ``g`` given: ``clamp(x + alpha * sign(g), x0 - eps, x0 + eps)``; ``x`` and ``g`` both ``None``: the random start
+    ``x0 + eps * (2 U - 1)`` keyed by ``seed``.  Rows with ``active[b] == 0`` (device int32 ``[B]``; ``None`` = all active) and,
+    with ``keep_zero_columns``, all-zero frame columns of ``x0`` come back as bit-exact copies of ``x0``.  float32 HIP tensors
+    ``[B,64,T]`` or ``[B,1,64,T]`` only; ``out`` may be ``x`` (in place), never ``x0`` or ``g``.  Returns ``out`` (a new tensor
+    in the shape of ``x0`` when not given).  Every argument is validated before any device call."""
+    if g is None and x is not None:
+        raise ValueError("x given without g: a random start is drawn around x0 alone")
+    if g is not None and x is None:
+        raise ValueError("a gradient step needs the iterate x (pass x0 for the first step)")
+    eps, alpha, (bsz, t) = _adv_check(eps, alpha, ("x0", x0), ("x", x), ("g", g), ("out", out))
+    if active is not None:
+        if not torch.is_tensor(active) or active.dtype != torch.int32 or active.dim() != 1 or active.numel() != bsz:
+            raise ValueError("active must be an int32 tensor with one flag per row")
+        if not active.is_cuda:
+            raise _native.SirError("tensor is not on a HIP device: this path runs on MI355X only (no CPU fallback)")
+    for name, v in (("x0", x0), ("x", x), ("g", g), ("out", out)):
+        if v is not None and not v.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    if out is not None and (out is x0 or out is g):
+        raise ValueError("out must not be x0 or g (it may be x)")
+    seed = int(seed)
+    if not 0 <= seed < (1 << 64):
+        raise ValueError("seed must fit 64 bits")
+    if out is None:
+        out = torch.empty_like(x0)
+    cfg = _native.AdvConfig(eps, alpha, 1 if keep_zero_columns else 0)
+    rc = _native.lib().sir_adv_step(get_featurizer().handle, x0.data_ptr(), x.data_ptr() if x is not None else None,
+                                    g.data_ptr() if g is not None else None,
+                                    active.contiguous().data_ptr() if active is not None else None, bsz, 64, t, C.byref(cfg), seed,
+                                    out.data_ptr(), _native.current_stream_ptr())
+    _native.check(rc, "sir_adv_step")
+    return out
+
+
+def default_adv_alpha(eps, steps, random_start):
+    """The step size of an ``Adversary`` that was given none: ``eps`` for one step from ``x`` itself (FGSM), ``1.25 eps`` for one
+    step from a random start (Wong et al. 2020), ``2.5 eps / steps`` otherwise (Madry et al. 2018)."""
+    if steps == 1:
+        return 1.25 * eps if random_start else eps
+    return 2.5 * eps / steps
+
+
+def set_adversary(mod, adversary):
+    """Make ``train_epoch`` / ``train_epoch_waveforms`` craft adversarial examples for ``mod`` with ``adversary`` (``None``: stop).
+    The adversary rides on the model as the LR scheduler rides on the optimizer (``step_scheduler_with``): both epoch functions
+    keep the reference's signatures.  Nothing else reads it -- ``validate``, ``predict`` and ``sir_amd.explain`` are unaffected,
+    and it is not part of ``state_dict()`` (its generator travels in the run state, ``sir_amd.run_state``)."""
+    if adversary is not None and not isinstance(adversary, Adversary):
+        raise TypeError("set_adversary takes a train_ops.Adversary or None")
+    mod._sir_adversary = adversary
+    return adversary
+
+
+def adversary_of(mod):
+    return getattr(mod, "_sir_adversary", None)
+
+
+class Adversary:
+    """L-infinity adversarial training (FGSM / PGD) for ``train_epoch`` / ``train_epoch_waveforms`` (``set_adversary``), modelled on ``Mixup``: the
+    host ``random.Random(seed)`` in ``.rng`` draws, per batch, the ``active`` flags (each row with probability ``prob``: clean
+    and adversarial rows share one batch and one BatchNorm pass) and one 64-bit ``start_seed``.  ``draw(bsz)`` returns them as
+    ``(int32 [B] host tensor, int)``; both are drawn for every batch whatever the settings, so the sequence depends on the
+    seed and the batch sizes alone.  The flags are staged through pinned buffers (no device sync); the seed travels by value.
+
+    ``adversary(model, x, loss_closure)`` returns the detached ``x_adv`` in the shape of ``x`` after ``steps`` crafting passes
+    (``forward_craft``: the module is left as it was found); ``loss_closure(logits)`` is the loss to ascend -- the step's own
+    training loss.  All-zero frame columns of ``x`` (padding, SpecAugment time bands) are kept.  ``eps == 0`` still runs the
+    passes and returns the bits of ``x`` (for an ``x`` without -0.0)."""
+
+    def __init__(self, eps, alpha=None, steps=1, random_start=True, prob=1.0, seed=0):
+        import random
+        eps, steps, prob = float(eps), int(steps), float(prob)
+        if not eps >= 0.0:
+            raise ValueError("adversarial eps must be >= 0")
+        if steps < 1:
+            raise ValueError("adversarial steps must be >= 1")
+        if not 0.0 <= prob <= 1.0:
+            raise ValueError("adversarial prob must be in [0, 1]")
+        self.eps, self.steps, self.prob, self.random_start = eps, steps, prob, bool(random_start)
+        self.alpha = default_adv_alpha(eps, steps, self.random_start) if alpha is None else float(alpha)
+        if not self.alpha >= 0.0:
+            raise ValueError("adversarial alpha must be >= 0")
+        self.rng = random.Random(int(seed))
+        self._stage = None
+
+    def draw(self, bsz):
+        flags = [1 if self.rng.random() < self.prob else 0 for _ in range(bsz)]
+        return torch.tensor(flags, dtype=torch.int32), self.rng.getrandbits(64)
+
+    def __call__(self, model, x, loss_closure):
+        from .scripts.train import HostStager
+        _adv_check(self.eps, self.alpha, ("x", x))
+        if self._stage is None or self._stage.device != x.device:
+            self._stage = HostStager(x.device)
+        flags, start_seed = self.draw(x.shape[0])
+        active = self._stage(flags)
+        x0 = x.detach().contiguous()
+        cur = x0
+        if self.random_start:
+            cur = adv_step(x0, None, None, self.eps, self.alpha, active, seed=start_seed)
+        for _ in range(self.steps):
+            logits, leaf = forward_craft(model, cur)
+            with torch.enable_grad():
+                loss = loss_closure(logits)
+            (g,) = torch.autograd.grad(loss, leaf)
+            cur = adv_step(x0, cur, g, self.eps, self.alpha, active, out=None if cur is x0 else cur)
+        return cur
 
 
 class _FusedCE(torch.autograd.Function):

@@ -392,7 +392,8 @@ int sir_vad_gather(sir_handle* h, const void* wave, int wave_dtype, int64_t wave
  * Call it wherever the host synchronises anyway -- once per batch of predictions (scripts/evaluate.py:85-86's
  * .cpu()) or per epoch (scripts/train.py:116's loss.item()); sir_profile_collect performs the same check.
  * The same word carries sir_ce_loss's / sir_ce_loss_soft's "label outside [0, num_classes)" flag (nn.CrossEntropyLoss raises on such a
- * target, train.py:242/:105; the kernel makes that step's loss NaN): reported here as SIR_EINVAL. */
+ * target, train.py:242/:105; the kernel makes that step's loss NaN): reported here as SIR_EINVAL.  sir_eval_accumulate and
+ * sir_temperature_fit raise it (bit 512) for such a label too. */
 int sir_check_status(sir_handle* h, void* stream);
 
 /* ---- cross-batch pipelining (owned by the library) ------------------------------------------------
@@ -637,6 +638,69 @@ int sir_adam_step_ex(sir_handle* h, int n_tensors, float* const* params, const f
                      float* const* exp_avg, float* const* exp_avg_sq, float* const* ema /* NULL iff ema_decay == 0 */,
                      const int64_t* sizes, int step, const sir_adam_config* cfg,
                      const float* partials, int n_partials, float* out2, void* stream);
+
+/* ---- classification and evaluation of logits (csrc/evaluate.hip) ----------------------------------
+ * What follows the forward pass, for a whole batch on the device: softmax + top-k (sir_classify), the counts and sums an
+ * evaluation report is made of (sir_eval_accumulate) and temperature scaling (sir_temperature_fit; Guo et al. 2017).
+ * Common to the calls: logits [rows][num_classes] f32, 4-byte aligned, 1 <= num_classes <= 64 (as sir_model_weights),
+ * 1 <= rows <= 2^30 (sir_temperature_fit: 2^22), anything else SIR_EINVAL;
+ * one wavefront per row, one lane per class.  Nothing allocates, nothing synchronises with the host, only kernels are
+ * launched (legal under stream capture), and every argument is checked before the first launch: a refused call writes nothing.
+ *   inv_temperature : DEVICE f32[1], beta = 1 / T, > 0; NULL = 1.
+ *   order           : classes rank by descending logit, equal logits by ascending class index.  Rank 0 is therefore the
+ *                     "first maximum" sir_model_infer's argmax returns, on every finite row, whatever beta > 0 is.
+ *   softmax         : p = softmax(l * beta) as p = exp(d) / den with d = (l - max l) * beta -- the row maximum is subtracted first,
+ *                     then one product -- den = 1 + rest, rest = the sum of exp(d) over every class but the first maximum
+ *                     (whose term is exactly 1), all in fp32; log den is taken as log1pf(rest).
+ *   non-finite row  : a row that holds a NaN or an infinity (tested on the logits themselves, not on l * beta).
+ *
+ * sir_classify: probs (optional, [batch][num_classes]) = p; topk_idx int32 [batch][k] / topk_prob f32 [batch][k] = the classes
+ *   of rank 0 .. k - 1 and their p.  1 <= k <= min(8, num_classes), else SIR_EINVAL.  A non-finite row yields NaN in probs and
+ *   topk_prob and -1 in topk_idx; the other rows are unaffected.
+ *
+ * sir_eval_accumulate adds one batch into `state`, a caller-owned device buffer of sir_eval_state_bytes(num_classes, n_bins)
+ *   bytes (0 for arguments out of range), 8-byte aligned, zeroed by the caller before the first batch.  1 <= n_bins <= 64.
+ *   A smaller state_bytes is SIR_ENOMEM.  Layout, every field 8 bytes wide, in this order (C = num_classes, M = n_bins):
+ *     int64  confusion[C][C]   row = true label, column = predicted class (rank 0)
+ *     int64  n                 rows counted
+ *     int64  topk_correct[8]   entry j: rows whose label has rank < min(j + 1, C)
+ *     double nll_sum           sum of -log p[label], per row log1pf(rest) - d[label] in fp32
+ *     int64  bin_count[M]      rows by confidence bin: min(M - 1, (int)floorf(p_max * M)), p_max = p of rank 0, fp32
+ *     int64  bin_correct[M]    of those, the rows whose prediction is the label
+ *     double bin_conf_sum[M]   sum of p_max over the bin's rows
+ *     int64  n_ignored         rows whose label is -100 (nn.CrossEntropyLoss's ignore_index, as sir_ce_loss)
+ *     int64  n_nonfinite       rows with a valid label and a non-finite logit row
+ *     double scratch[64][M+1]  the call's own workspace (per workgroup {NLL partial, bin_conf_sum partials}); need not be zero,
+ *                              holds nothing a caller reads
+ *   A row is looked at in this order: label -100 -> n_ignored and nothing else; any other label outside [0, C) -> no field
+ *   moves and the handle's status word is raised (SIR_EINVAL at the next sir_check_status, as sir_ce_loss); a non-finite row ->
+ *   n_nonfinite and nothing else; every other row counts in all remaining fields.
+ *   The integer fields are added with integer atomics (exact, order-independent).  The doubles are summed in a fixed order -- G =
+ *   min(64, ceil(batch / 16)) workgroups of 16 waves, wave g of the 16 G takes rows g, g + 16 G, ...; a workgroup's 16 wave sums
+ *   are added in wave order into its partial (scratch), and a second single-workgroup launch adds the G partials in order to
+ *   the state -- with no floating-point atomic: bit-reproducible run to run.  Calls into one state add up; they must be
+ *   ordered (one stream, or events).
+ *
+ * sir_temperature_fit minimises f(beta) = mean_i [logsumexp(beta l_i) - beta l_{i, y_i}] over beta = 1 / T (convex:
+ *   f' = mean(E_p[l] - l_y), f'' = mean(Var_p(l)), p = softmax(beta l)).  From beta = 1 it runs `iters` (0 .. 1000; 20 is plenty)
+ *   safeguarded Newton steps  b = clamp(beta - f' / max(f'', 1e-12), beta / 2, 2 beta), beta = (float)clamp(b, 1/64, 64), the
+ *   step evaluated in double; a NaN step keeps beta.  Each step is one reduction launch (per-row terms in fp32 on the centred
+ *   logits c = l - max l: log1pf(rest) - beta c_y, E_p[c] - c_y, E_p[(c - E_p[c])^2]; sums over rows in double in a fixed
+ *   order: run-to-run reproducible) and one single-thread update launch; beta
+ *   never leaves the device.  Rows are left out (label -100, non-finite row) or flagged (other label outside [0, C)) as by
+ *   sir_eval_accumulate; the means run over the remaining rows (none left: beta stays 1, the two nll are NaN).
+ *   out       : device f32[3] = {beta, f(1), f(beta)}; out (also out + 0 alone) may be passed on as inv_temperature
+ *   n_rows    : 1 .. 2^22
+ *   workspace : sir_temperature_fit_workspace_bytes(n_rows) bytes, 8-byte aligned (too small: SIR_ENOMEM); contents need not
+ *               be initialised */
+int sir_classify(sir_handle* h, const float* logits, int batch, int num_classes, const float* inv_temperature, int k,
+                 float* probs, int32_t* topk_idx, float* topk_prob, void* stream);
+size_t sir_eval_state_bytes(int num_classes, int n_bins);
+int sir_eval_accumulate(sir_handle* h, const float* logits, const int64_t* labels, int batch, int num_classes,
+                        const float* inv_temperature, int n_bins, void* state, size_t state_bytes, void* stream);
+size_t sir_temperature_fit_workspace_bytes(int n_rows);
+int sir_temperature_fit(sir_handle* h, const float* logits, const int64_t* labels, int n_rows, int num_classes, int iters,
+                        float* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- measurement -----------------------------------------------------------------------------
  * HIP-event timing of the kernels of the path, recorded on the stream they are launched on

@@ -17,6 +17,7 @@ SIR_OK = 0
 SIR_EINVAL = -1
 SIR_EUNSUPPORTED = -4
 SIR_ETIMEOUT = -5
+SIR_ENOMEM = -2
 WAVE_F32, WAVE_I16 = 0, 1
 BWD_ALL, BWD_HEAD_GRU, BWD_CNN = 0, 1, 2
 PROFILE_EXTRA_IDS = 1           # SIR_PROFILE_EXTRA_IDS: profile ids behind sir_profile_kernel_count() (include/sir_hip.h)
@@ -153,6 +154,14 @@ SIGNATURES = {
     "sir_adam_step_ex": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                    C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int, C.POINTER(AdamConfig),
                                    C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "sir_classify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p]),
+    "sir_eval_state_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "sir_eval_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                      C.c_size_t, C.c_void_p]),
+    "sir_temperature_fit_workspace_bytes": (C.c_size_t, [C.c_int]),
+    "sir_temperature_fit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_size_t, C.c_void_p]),
     "sir_profile_kernel_count": (C.c_int, []),
     "sir_profile_kernel_name": (C.c_char_p, [C.c_int]),
     "sir_profile_enable": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),

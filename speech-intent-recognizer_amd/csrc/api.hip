@@ -370,6 +370,11 @@ static int check_status_impl(sir_handle* h, hipStream_t st, const char* who) {
                       "infinite snr_db (status %u): those rows are zero", who, v);
         return SIR_EINVAL;
     }
+    if (v & 512u) {
+        sir_set_error("%s: sir_eval_accumulate / sir_temperature_fit saw a label outside [0, num_classes) that is not -100 (status %u): "
+                      "those rows were left out", who, v);
+        return SIR_EINVAL;
+    }
     if (v & 4u) {
         sir_set_error("%s: sir_gather_features was given an index outside its store (status %u): those rows are zero", who, v);
         return SIR_EINVAL;

@@ -1,0 +1,359 @@
+// What follows the forward pass, on the device (include/sir_hip.h: sir_classify, sir_eval_accumulate, sir_temperature_fit).
+//
+// A row has at most 64 classes, so ONE WAVE OWNS A ROW, one lane per class: the row maximum and the softmax denominator are
+// xor-butterfly reductions over the 64 lanes (every lane ends with the same bits: each level adds the same two values in both
+// partners, and fp32 addition commutes), and a class's rank is counted, not sorted for -- lane c walks the C logits of its row
+// (a readlane per class, the index is wave-uniform) and counts those that beat its own: larger, or equal with a lower index.
+// The classes of rank < k are the top-k in order, rank 0 is the first maximum, and the rank of the label's lane answers "is
+// the label among the first j + 1" for all eight j at once.
+//   sir_classify        : grid-stride over rows, 4 waves per workgroup.
+//   sir_eval_accumulate : up to 64 workgroups of 16 waves (global wave g takes rows g, g + waves, ...).  Counters and the
+//                         workgroup's confusion counts are gathered in LDS (integer atomics) and flushed once, one global
+//                         integer atomic per non-zero word.  The two floating sums have a fixed order: per-wave doubles in
+//                         row order, added in wave order into the workgroup's partial, which goes to a scratch area behind
+//                         the state's fields; a second, single-workgroup launch adds the partials in workgroup order.
+//   sir_temperature_fit : per Newton step a reduction launch (<= 256 workgroups of 16 waves, global wave g takes rows g,
+//                         g + waves, ...; per-workgroup partials in the workspace) and a one-thread update launch.
+#include <cmath>
+#include "sir_internal.h"
+
+namespace {
+
+constexpr int kEvalWaves = 16;                       // waves of the accumulate / fit workgroups
+constexpr int kEvalThreads = kEvalWaves * SIR_WAVE;
+constexpr int kClsWaves = 4;
+constexpr int kFitMaxBlocks = 256;
+constexpr int kMaxRows = 1 << 30;                    // rows per call: row indices and their grid strides stay far inside an int
+constexpr int kEvalMaxBlocks = 64;                   // workgroups of sir_eval_accumulate = partial rows of the state's scratch area
+constexpr int kFitHeader = 64;                       // workspace: {float beta, float nll at beta = 1} then the partials
+constexpr unsigned int kStatusBadLabel = 512u;       // api.hip check_status_impl
+
+__device__ __forceinline__ float wave_max(float x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o));
+    return x;
+}
+__device__ __forceinline__ float wave_sum(float x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+    return x;
+}
+__device__ __forceinline__ bool is_nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+
+// One row in one wave.  l: this lane's logit (lanes >= C hold 0 and take no part).  The row maximum is subtracted BEFORE the
+// scaling: d = (l - max l) * beta is one rounding of an (almost always exact) difference, so a small gap keeps its relative
+// precision whatever the magnitude of the logits and of beta; l * beta - max(l * beta) would carry the absolute rounding of
+// the two products.
+struct RowSoftmax {
+    float d, e;             // (l - max l) * beta <= 0, exp(d) (0 on lanes >= C)
+    float rest, den;        // sum of e without the first maximum's exact 1, and 1 + rest: log(den) = log1pf(rest) keeps the small
+                            // tail of a confident row that 1 + rest rounds away
+    int rank;               // of this lane's class (meaningless on lanes >= C and on non-finite rows)
+    bool finite;            // wave-uniform
+};
+
+__device__ __forceinline__ RowSoftmax row_softmax(float l, int lane, int C, float beta) {
+    RowSoftmax r;
+    const bool on = lane < C;
+    r.finite = __ballot(on && is_nonfinite(l)) == 0ull;
+    const float m = wave_max(on ? l : -INFINITY);
+    r.d = (l - m) * beta;
+    r.e = on ? expf(r.d) : 0.0f;
+    const unsigned long long at_max = __ballot(on && l == m);
+    const int first = at_max ? __ffsll((long long)at_max) - 1 : -1;                     // (no lane on a NaN row)
+    r.rest = wave_sum(lane == first ? 0.0f : r.e);
+    r.den = 1.0f + r.rest;
+    int rank = 0;
+    for (int j = 0; j < C; ++j) {
+        const float lj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(l), j));
+        rank += (lj > l || (lj == l && j < lane)) ? 1 : 0;
+    }
+    r.rank = rank;
+    return r;
+}
+
+__global__ __launch_bounds__(kClsWaves * SIR_WAVE) void classify_kernel(const float* __restrict__ logits, int B, int C,
+                                                                         const float* __restrict__ inv_t, int k, float* __restrict__ probs,
+                                                                         int* __restrict__ topk_idx, float* __restrict__ topk_prob) {
+    const int lane = threadIdx.x & (SIR_WAVE - 1), wave = threadIdx.x / SIR_WAVE;
+    const float beta = inv_t ? inv_t[0] : 1.0f;
+    const float nan = __builtin_nanf("");
+    for (int b = blockIdx.x * kClsWaves + wave; b < B; b += gridDim.x * kClsWaves) {      // wave-uniform
+        const float l = lane < C ? logits[(size_t)b * C + lane] : 0.0f;
+        const RowSoftmax r = row_softmax(l, lane, C, beta);
+        const float p = r.e / r.den;
+        if (r.finite) {
+            if (lane < C) {
+                if (probs) probs[(size_t)b * C + lane] = p;
+                if (r.rank < k) { topk_idx[(size_t)b * k + r.rank] = lane; topk_prob[(size_t)b * k + r.rank] = p; }
+            }
+        } else {
+            if (lane < C && probs) probs[(size_t)b * C + lane] = nan;
+            if (lane < k) { topk_idx[(size_t)b * k + lane] = -1; topk_prob[(size_t)b * k + lane] = nan; }
+        }
+    }
+}
+
+// offsets into the evaluation state, in 8-byte words (include/sir_hip.h)
+struct EvalLayout {
+    int n, topk, nll, bin_count, bin_correct, bin_conf, ignored, nonfinite, scratch, words;
+};
+__host__ __device__ inline EvalLayout eval_layout(int C, int M) {
+    EvalLayout o;
+    o.n = C * C; o.topk = o.n + 1; o.nll = o.topk + 8; o.bin_count = o.nll + 1; o.bin_correct = o.bin_count + M;
+    o.bin_conf = o.bin_correct + M; o.ignored = o.bin_conf + M; o.nonfinite = o.ignored + 1; o.scratch = o.nonfinite + 1;
+    o.words = o.scratch + kEvalMaxBlocks * (M + 1);         // scratch: per workgroup {nll partial, bin_conf partial[M]}
+    return o;
+}
+
+// how a row is treated, wave-uniform: 0 counted, 1 ignored (label -100), 2 label outside [0, C), 3 non-finite row
+__device__ __forceinline__ int row_kind(long long y, int C, bool finite) {
+    if (y == -100ll) return 1;
+    if (y < 0 || y >= (long long)C) return 2;
+    return finite ? 0 : 3;
+}
+
+__global__ __launch_bounds__(kEvalThreads) void eval_accumulate_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
+                                                                       int B, int C, const float* __restrict__ inv_t, int M,
+                                                                       unsigned long long* state, unsigned int* status) {
+    __shared__ double s_conf[kEvalWaves][64];
+    __shared__ double s_nll[kEvalWaves];
+    __shared__ unsigned int s_bin_count[64], s_bin_correct[64], s_topk[8], s_misc[3];      // misc: n, ignored, non-finite
+    __shared__ unsigned int s_cm[64 * 64];                                              // this workgroup's confusion counts, [C][C]
+    const int lane = threadIdx.x & (SIR_WAVE - 1), wave = threadIdx.x / SIR_WAVE;
+    const float beta = inv_t ? inv_t[0] : 1.0f;
+    const EvalLayout o = eval_layout(C, M);
+    s_conf[wave][lane] = 0.0;
+    for (int i = threadIdx.x; i < C * C; i += kEvalThreads) s_cm[i] = 0u;
+    if (threadIdx.x < 64) { s_bin_count[threadIdx.x] = 0u; s_bin_correct[threadIdx.x] = 0u; }
+    if (threadIdx.x < 8) s_topk[threadIdx.x] = 0u;
+    if (threadIdx.x < 3) s_misc[threadIdx.x] = 0u;
+    __syncthreads();
+    double nll = 0.0;                                                                   // the same value on every lane of the wave
+    // the next row's logit and label are loaded before this row's arithmetic: the wave's rows are one dependent chain
+    // otherwise, a memory latency each
+    const int first_row = blockIdx.x * kEvalWaves + wave, stride = gridDim.x * kEvalWaves;
+    float l_next = (first_row < B && lane < C) ? logits[(size_t)first_row * C + lane] : 0.0f;
+    long long y_next = first_row < B ? labels[first_row] : 0ll;
+    for (int b = first_row; b < B; b += stride) {                                       // wave-uniform
+        const float l = l_next;
+        const long long y = y_next;
+        const int nb = b + stride;
+        if (nb < B) {
+            l_next = lane < C ? logits[(size_t)nb * C + lane] : 0.0f;
+            y_next = labels[nb];
+        }
+        const RowSoftmax r = row_softmax(l, lane, C, beta);
+        const int kind = row_kind(y, C, r.finite);
+        if (kind != 0) {
+            if (lane == 0) {
+                if (kind == 1) atomicAdd(&s_misc[1], 1u);
+                else if (kind == 3) atomicAdd(&s_misc[2], 1u);
+                else __hip_atomic_fetch_or(status, kStatusBadLabel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            continue;
+        }
+        const int yi = (int)y;
+        const int rank_y = __shfl(r.rank, yi);
+        const float dy = __shfl(r.d, yi);
+        const unsigned long long top = __ballot(lane < C && r.rank == 0);              // exactly one lane
+        const int pred = top ? __ffsll((long long)top) - 1 : 0;                        // (a finite row always has a rank 0)
+        const float pmax = __shfl(r.e, pred) / r.den;
+        int bin = (int)floorf(pmax * (float)M);
+        bin = bin < M - 1 ? bin : M - 1;
+        bin = bin > 0 ? bin : 0;                                                        // (a NaN beta must not index outside the bins)
+        nll += (double)(log1pf(r.rest) - dy);
+        if (lane == 0) {
+            s_conf[wave][bin] += (double)pmax;                                          // this wave's rows, in row order
+            atomicAdd(&s_misc[0], 1u);
+            atomicAdd(&s_bin_count[bin], 1u);
+            if (pred == yi) atomicAdd(&s_bin_correct[bin], 1u);
+            atomicAdd(&s_cm[yi * C + pred], 1u);
+        }
+        if (lane < 8 && rank_y <= lane) atomicAdd(&s_topk[lane], 1u);
+    }
+    if (lane == 0) s_nll[wave] = nll;
+    __syncthreads();
+    const int t = threadIdx.x;
+    for (int i = t; i < C * C; i += kEvalThreads)
+        if (s_cm[i]) atomicAdd(&state[i], (unsigned long long)s_cm[i]);
+    double* part = reinterpret_cast<double*>(state + o.scratch) + (size_t)blockIdx.x * (M + 1);
+    if (t < M) {
+        double c = 0.0;
+        for (int w = 0; w < kEvalWaves; ++w) c += s_conf[w][t];
+        part[1 + t] = c;
+        if (s_bin_count[t]) atomicAdd(&state[o.bin_count + t], (unsigned long long)s_bin_count[t]);
+        if (s_bin_correct[t]) atomicAdd(&state[o.bin_correct + t], (unsigned long long)s_bin_correct[t]);
+    } else if (t == 64) {
+        double c = 0.0;
+        for (int w = 0; w < kEvalWaves; ++w) c += s_nll[w];
+        part[0] = c;
+    } else if (t >= 128 && t < 136) {
+        if (s_topk[t - 128]) atomicAdd(&state[o.topk + (t - 128)], (unsigned long long)s_topk[t - 128]);
+    } else if (t == 192) {
+        if (s_misc[0]) atomicAdd(&state[o.n], (unsigned long long)s_misc[0]);
+        if (s_misc[1]) atomicAdd(&state[o.ignored], (unsigned long long)s_misc[1]);
+        if (s_misc[2]) atomicAdd(&state[o.nonfinite], (unsigned long long)s_misc[2]);
+    }
+}
+
+// adds the workgroups' partials to the state's two floating fields, in workgroup order: thread 0 the NLL, thread 1 + m bin m
+__global__ __launch_bounds__(128) void eval_finish_kernel(unsigned long long* state, int C, int M, int blocks) {
+    const EvalLayout o = eval_layout(C, M);
+    const int t = threadIdx.x;
+    if (t > M) return;
+    const double* part = reinterpret_cast<const double*>(state + o.scratch);
+    double c = 0.0;
+    for (int b = 0; b < blocks; ++b) c += part[(size_t)b * (M + 1) + t];
+    double* dst = reinterpret_cast<double*>(state + (t == 0 ? o.nll : o.bin_conf + (t - 1)));
+    *dst += c;
+}
+
+inline int eval_blocks(int batch) {
+    const int b = (batch + kEvalWaves - 1) / kEvalWaves;
+    return b > kEvalMaxBlocks ? kEvalMaxBlocks : b;
+}
+
+inline int fit_blocks(int n_rows) {
+    const int b = (n_rows + 63) / 64;
+    return b < 1 ? 1 : (b > kFitMaxBlocks ? kFitMaxBlocks : b);
+}
+
+// partial[block] = {sum f_i, sum g_i, sum h_i, rows} over the block's rows at *beta_ptr (NULL: 1):
+// f_i = logsumexp(beta l) - beta l_y, g_i = E_p[l] - l_y, h_i = Var_p(l)
+__global__ __launch_bounds__(kEvalThreads) void fit_reduce_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
+                                                                  int N, int C, const float* __restrict__ beta_ptr,
+                                                                  double* __restrict__ partials, unsigned int* status) {
+    __shared__ double s_part[kEvalWaves][4];
+    const int lane = threadIdx.x & (SIR_WAVE - 1), wave = threadIdx.x / SIR_WAVE;
+    const float beta = beta_ptr ? beta_ptr[0] : 1.0f;
+    double f = 0.0, g = 0.0, hs = 0.0, cnt = 0.0;                                        // the same values on every lane
+    const int stride = gridDim.x * kEvalWaves;
+    for (int b = blockIdx.x * kEvalWaves + wave; b < N; b += stride) {                  // wave-uniform
+        const bool on = lane < C;
+        const float l = on ? logits[(size_t)b * C + lane] : 0.0f;
+        const long long y = labels[b];
+        const bool finite = __ballot(on && is_nonfinite(l)) == 0ull;
+        const int kind = row_kind(y, C, finite);
+        if (kind != 0) {
+            if (kind == 2 && lane == 0) __hip_atomic_fetch_or(status, kStatusBadLabel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            continue;
+        }
+        const float m = wave_max(on ? l : -INFINITY);
+        const float c = l - m;                                                           // centred logit: the moments below are of c
+        const float e = on ? expf(c * beta) : 0.0f;
+        const unsigned long long at_max = __ballot(on && l == m);
+        const int first = __ffsll((long long)at_max) - 1;
+        const float rest = wave_sum(lane == first ? 0.0f : e);                           // as row_softmax
+        const float den = 1.0f + rest;
+        const float mean = wave_sum(e * c) / den;
+        const float dc = c - mean;
+        const float var = wave_sum(e * dc * dc) / den;
+        const float cy = __shfl(c, (int)y);
+        f += (double)(log1pf(rest) - cy * beta);
+        g += (double)(mean - cy);
+        hs += (double)var;
+        cnt += 1.0;
+    }
+    if (lane == 0) { s_part[wave][0] = f; s_part[wave][1] = g; s_part[wave][2] = hs; s_part[wave][3] = cnt; }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        double c = 0.0;
+        for (int w = 0; w < kEvalWaves; ++w) c += s_part[w][threadIdx.x];
+        partials[(size_t)blockIdx.x * 4 + threadIdx.x] = c;
+    }
+}
+
+// One thread.  step >= 0: the Newton update after the reduction at the current beta (step 0: beta = 1, and f(1) is kept).
+// step < 0: the reduction was the closing one at the fitted beta -> out.
+__global__ void fit_update_kernel(const double* __restrict__ partials, int blocks, int step, int iters, float* hdr, float* out) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double F = 0.0, G = 0.0, H = 0.0, n = 0.0;
+    for (int i = 0; i < blocks; ++i) { F += partials[4 * i]; G += partials[4 * i + 1]; H += partials[4 * i + 2]; n += partials[4 * i + 3]; }
+    const double f = F / n;                                                             // no rows: 0 / 0 = NaN
+    if (step < 0) {
+        const float beta = iters > 0 ? hdr[0] : 1.0f;
+        out[0] = beta;
+        out[1] = iters > 0 ? hdr[1] : (float)f;
+        out[2] = (float)f;
+        return;
+    }
+    const double beta = step > 0 ? (double)hdr[0] : 1.0;
+    if (step == 0) hdr[1] = (float)f;
+    const double g = G / n, h = H / n;
+    double b = beta - g / fmax(h, 1e-12);
+    b = fmin(fmax(b, 0.5 * beta), 2.0 * beta);
+    b = fmin(fmax(b, 1.0 / 64.0), 64.0);
+    if (!(g == g) || !(h == h)) b = beta;                                               // a NaN step keeps beta
+    hdr[0] = (float)b;
+}
+
+}  // namespace
+
+extern "C" int sir_classify(sir_handle* h, const float* logits, int batch, int num_classes, const float* inv_temperature, int k,
+                            float* probs, int32_t* topk_idx, float* topk_prob, void* stream) {
+    if (!h || !logits || !topk_idx || !topk_prob) { sir_set_error("sir_classify: NULL argument (h, logits, topk_idx and topk_prob are required)"); return SIR_EINVAL; }
+    if (batch < 1 || batch > kMaxRows || num_classes < 1 || num_classes > 64) { sir_set_error("sir_classify: bad shape batch=%d (1..2^30) num_classes=%d (1..64)", batch, num_classes); return SIR_EINVAL; }
+    if (k < 1 || k > 8 || k > num_classes) { sir_set_error("sir_classify: k=%d outside [1, min(8, num_classes=%d)]", k, num_classes); return SIR_EINVAL; }
+    const uintptr_t bits = (uintptr_t)logits | (uintptr_t)inv_temperature | (uintptr_t)probs | (uintptr_t)topk_idx | (uintptr_t)topk_prob;
+    if (bits & 3u) { sir_set_error("sir_classify: pointers must be 4-byte aligned"); return SIR_EINVAL; }
+    int blocks = (batch + kClsWaves - 1) / kClsWaves;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(classify_kernel, dim3(blocks), dim3(kClsWaves * SIR_WAVE), 0, (hipStream_t)stream, logits, batch, num_classes,
+                       inv_temperature, k, probs, (int*)topk_idx, topk_prob);
+    return sir_check_hip(hipGetLastError(), "classify_kernel");
+}
+
+extern "C" size_t sir_eval_state_bytes(int num_classes, int n_bins) {
+    if (num_classes < 1 || num_classes > 64 || n_bins < 1 || n_bins > 64) return 0;
+    return (size_t)eval_layout(num_classes, n_bins).words * 8;
+}
+
+extern "C" int sir_eval_accumulate(sir_handle* h, const float* logits, const int64_t* labels, int batch, int num_classes,
+                                   const float* inv_temperature, int n_bins, void* state, size_t state_bytes, void* stream) {
+    if (!h || !logits || !labels || !state) { sir_set_error("sir_eval_accumulate: NULL argument"); return SIR_EINVAL; }
+    if (batch < 1 || batch > kMaxRows || num_classes < 1 || num_classes > 64) { sir_set_error("sir_eval_accumulate: bad shape batch=%d (1..2^30) num_classes=%d (1..64)", batch, num_classes); return SIR_EINVAL; }
+    if (n_bins < 1 || n_bins > 64) { sir_set_error("sir_eval_accumulate: n_bins=%d outside [1, 64]", n_bins); return SIR_EINVAL; }
+    if ((((uintptr_t)logits | (uintptr_t)inv_temperature) & 3u) || (((uintptr_t)labels | (uintptr_t)state) & 7u)) {
+        sir_set_error("sir_eval_accumulate: logits / inv_temperature must be 4-byte aligned, labels / state 8-byte aligned");
+        return SIR_EINVAL;
+    }
+    const size_t need = sir_eval_state_bytes(num_classes, n_bins);
+    if (state_bytes < need) { sir_set_error("sir_eval_accumulate: state of %zu bytes, %zu needed", state_bytes, need); return SIR_ENOMEM; }
+    const int blocks = eval_blocks(batch);
+    hipLaunchKernelGGL(eval_accumulate_kernel, dim3(blocks), dim3(kEvalThreads), 0, (hipStream_t)stream, logits, (const long long*)labels, batch,
+                       num_classes, inv_temperature, n_bins, (unsigned long long*)state, h->status);
+    hipLaunchKernelGGL(eval_finish_kernel, dim3(1), dim3(128), 0, (hipStream_t)stream, (unsigned long long*)state, num_classes, n_bins, blocks);
+    return sir_check_hip(hipGetLastError(), "sir_eval_accumulate kernels");
+}
+
+extern "C" size_t sir_temperature_fit_workspace_bytes(int n_rows) {
+    if (n_rows < 1 || n_rows > (1 << 22)) return 0;
+    return (size_t)kFitHeader + (size_t)fit_blocks(n_rows) * 4 * sizeof(double);
+}
+
+extern "C" int sir_temperature_fit(sir_handle* h, const float* logits, const int64_t* labels, int n_rows, int num_classes, int iters,
+                                   float* out, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!h || !logits || !labels || !out || !workspace) { sir_set_error("sir_temperature_fit: NULL argument"); return SIR_EINVAL; }
+    if (n_rows < 1 || n_rows > (1 << 22) || num_classes < 1 || num_classes > 64) {
+        sir_set_error("sir_temperature_fit: bad shape n_rows=%d (1..2^22) num_classes=%d (1..64)", n_rows, num_classes);
+        return SIR_EINVAL;
+    }
+    if (iters < 0 || iters > 1000) { sir_set_error("sir_temperature_fit: iters=%d outside [0, 1000]", iters); return SIR_EINVAL; }
+    if ((((uintptr_t)logits | (uintptr_t)out) & 3u) || (((uintptr_t)labels | (uintptr_t)workspace) & 7u)) {
+        sir_set_error("sir_temperature_fit: logits / out must be 4-byte aligned, labels / workspace 8-byte aligned");
+        return SIR_EINVAL;
+    }
+    const size_t need = sir_temperature_fit_workspace_bytes(n_rows);
+    if (workspace_bytes < need) { sir_set_error("sir_temperature_fit: workspace of %zu bytes, %zu needed", workspace_bytes, need); return SIR_ENOMEM; }
+    const hipStream_t st = (hipStream_t)stream;
+    const int blocks = fit_blocks(n_rows);
+    float* hdr = (float*)workspace;
+    double* partials = (double*)((char*)workspace + kFitHeader);
+    for (int step = 0; step <= iters; ++step) {
+        hipLaunchKernelGGL(fit_reduce_kernel, dim3(blocks), dim3(kEvalThreads), 0, st, logits, (const long long*)labels, n_rows, num_classes,
+                           step > 0 ? hdr : (const float*)nullptr, partials, h->status);
+        hipLaunchKernelGGL(fit_update_kernel, dim3(1), dim3(1), 0, st, partials, blocks, step < iters ? step : -1, iters, hdr, out);
+    }
+    return sir_check_hip(hipGetLastError(), "sir_temperature_fit kernels");
+}

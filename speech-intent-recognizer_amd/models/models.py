@@ -89,6 +89,15 @@ class CNNAudioGRU(nn.Module):
         """logits and argmax (scripts/evaluate.py:82-83) in one launch sequence; ``lengths`` as in ``forward``."""
         return ops.model_infer(self, x, self._ws, want_argmax=True, lengths=lengths)
 
+    @torch.no_grad()
+    def classify(self, x, lengths=None, k=3, inv_temperature=None):
+        """The forward plus ``ops.classify`` on the device -> ``(logits [B, C], topk_idx int32 [B, k], topk_prob [B, k])``: the
+        ``k`` most probable classes of every clip in order and their softmax probabilities (``topk_idx[:, 0]`` is ``predict``'s
+        argmax).  ``lengths`` as in ``forward`` (the ragged route), ``inv_temperature`` as in ``ops.classify``."""
+        logits = ops.model_infer(self, x, self._ws, lengths=lengths)
+        idx, prob = ops.classify(logits, k=k, inv_temperature=inv_temperature)
+        return logits, idx, prob
+
 
 if __name__ == "__main__":
     model = CNNAudioGRU(num_classes=31).cuda().eval()

@@ -200,6 +200,33 @@ def model_infer(mod, x, workspace, want_argmax=False, debug=None, lengths=None):
     return (logits, amax) if want_argmax else logits
 
 
+def classify(logits, k=3, inv_temperature=None, want_probs=False):
+    """Softmax and top-k of a batch of logits in one ``sir_classify`` launch -> ``(topk_idx int32 [B, k], topk_prob float32
+    [B, k])``, classes by descending logit (equal logits: the lower index first), so ``topk_idx[:, 0]`` is the argmax
+    ``model_infer`` returns and ``topk_prob[:, 0]`` the confidence.  ``inv_temperature``: None, a positive number or a device
+    scalar (``metrics.fit_temperature``) that scales the logits first.  A row with a NaN or an infinity comes back as -1 / NaN.
+    ``want_probs=True`` appends the full softmax [B, C]."""
+    from .metrics import _inv_temperature_tensor
+    _native.require_hip(logits)
+    if logits.dim() != 2 or logits.shape[0] < 1 or not 1 <= logits.shape[1] <= 64:
+        raise _native.SirError(f"logits must be [rows >= 1, classes in 1..64], got {tuple(logits.shape)}")
+    logits = _f32c(logits.contiguous(), "logits")
+    bsz, ncls = logits.shape
+    if isinstance(k, bool) or not hasattr(k, "__index__") or not 1 <= int(k) <= min(8, ncls):
+        raise _native.SirError(f"k must be an integer in [1, min(8, {ncls})], got {k!r}")
+    k = int(k)
+    beta = _inv_temperature_tensor(inv_temperature, logits.device)
+    idx = torch.empty((bsz, k), dtype=torch.int32, device=logits.device)
+    prob = torch.empty((bsz, k), dtype=torch.float32, device=logits.device)
+    probs = torch.empty_like(logits) if want_probs else None
+    rc = _native.lib().sir_classify(get_featurizer().handle, logits.data_ptr(), bsz, ncls,
+                                    beta.data_ptr() if beta is not None else None, k,
+                                    probs.data_ptr() if probs is not None else None, idx.data_ptr(), prob.data_ptr(),
+                                    _native.current_stream_ptr())
+    _native.check(rc, "sir_classify")
+    return (idx, prob, probs) if want_probs else (idx, prob)
+
+
 def stage_views(ws, bsz, t):
     """Views of the intermediate buffers inside the workspace (for stage-level parity tests)."""
     lib = _native.lib()

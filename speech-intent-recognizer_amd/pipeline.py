@@ -120,17 +120,24 @@ class BatchPipeline:
             return self.featurizer(wave, lengths, **kw)
 
     @torch.no_grad()
-    def infer(self, i, feats, want_argmax=True, lengths=None):
+    def infer(self, i, feats, want_argmax=True, lengths=None, then=None):
         """eval-mode forward (+ argmax) of batch ``i`` on its slot's stream; closes the submission of batch ``i``.
-        ``lengths`` (frames per clip): the un-padded function, as ``CNNAudioGRU.forward(x, lengths)``."""
+        ``lengths`` (frames per clip): the un-padded function, as ``CNNAudioGRU.forward(x, lengths)``.
+        ``then(slot, out)`` (optional) is called with the slot's stream current before the submission closes: what it
+        queues (``EvalAccumulator.update`` of a per-slot accumulator, say) runs behind the forward on that stream and is
+        covered by ``join()``."""
         k, st = self._begin(i)
         if self.n > 1:
             feats.record_stream(st)
             if torch.is_tensor(lengths) and lengths.is_cuda:
                 lengths.record_stream(st)
-        with torch.cuda.stream(st):
-            out = ops.model_infer(self.model, feats, self.workspaces[k], want_argmax=want_argmax, lengths=lengths)
-        self._end()
+        try:
+            with torch.cuda.stream(st):
+                out = ops.model_infer(self.model, feats, self.workspaces[k], want_argmax=want_argmax, lengths=lengths)
+                if then is not None:
+                    then(k, out)
+        finally:
+            self._end()                    # also when the forward or ``then`` raises: the shared pipeline's slot must not stay open
         return out
 
     def synchronize(self):

@@ -1,7 +1,13 @@
 """Drop-in for /root/reference/scripts/evaluate.py::evaluate with the forward + argmax loop
 (evaluate.py:74-86) on MI355X: one ``sir_model_infer`` launch sequence per batch, predictions kept
 on the device until the loop ends (one device->host copy instead of one per batch).  Metrics and the
-report files (evaluate.py:89-114) are unchanged stock sklearn / matplotlib."""
+report files (evaluate.py:89-114) are unchanged stock sklearn / matplotlib.
+
+YAML key ``device_metrics: true`` (default false) builds the report on the device instead: every batch is added to a
+``sir_amd.metrics.EvalAccumulator`` behind its forward, the few kilobytes of counts come back once, and
+``classification_report.txt`` (same text), ``confusion_matrix.png`` plus ``calibration.json`` (top-k accuracy, NLL, ECE / MCE, reliability table) are
+written from them.  ``--fit_temperature VALID_CSV`` fits the softmax temperature on that split (``sir_temperature_fit``)
+and writes ``temperature.json`` beside the checkpoint; ``--temperature_file`` reads one back for the calibration figures."""
 import argparse
 import json
 import logging
@@ -27,12 +33,25 @@ def load_config(config_path):
 
 
 @torch.no_grad()
-def predict_loader(model, loader, device):
-    """argmax predictions and labels over a loader (the hot loop of evaluate.py:79-86)."""
+def predict_loader(model, loader, device, device_metrics=None, collect_logits=False):
+    """argmax predictions and labels over a loader (the hot loop of evaluate.py:79-86).
+
+    ``device_metrics`` (a dict of ``EvalAccumulator`` arguments: ``num_classes``, optionally ``n_bins``, ``inv_temperature``):
+    every batch is also added to an accumulator on the device -- one per pipeline slot, so that the updates of a slot are
+    ordered on its stream; the slots' states are merged on the host at the end -- and the result is
+    ``(None, None, state arrays)``: no prediction leaves the device and no per-batch synchronisation is added.
+    ``collect_logits=True`` returns ``(logits [N, C] on the device, labels [N] on the device)`` instead (for
+    ``metrics.fit_temperature``)."""
     from sir_amd.pipeline import BatchPipeline
     model.eval()
     pipe = BatchPipeline(model, n_streams=2)          # consecutive batches alternate over two HIP streams
     preds, labels = [], []
+    if device_metrics is not None or collect_logits:
+        accs = None
+        if device_metrics is not None:
+            from sir_amd.metrics import EvalAccumulator
+            accs = [EvalAccumulator(**device_metrics) for _ in range(pipe.n)]
+        return _predict_loader_device(model, loader, device, pipe, accs, collect_logits)
     from sir_amd.scripts.train import HostStager
     stage = HostStager(device, slots=4)               # host batches: persistent pinned ring (see HostStager)
     for i, (mel, label) in enumerate(tqdm(loader, desc="Evaluating")):
@@ -47,6 +66,64 @@ def predict_loader(model, loader, device):
     from sir_amd import ops
     ops.check_status()                    # a timed-out GRU recurrence would have produced invalid predictions: raise
     return torch.cat(preds).cpu().numpy(), torch.cat(labels).numpy()
+
+
+def _predict_loader_device(model, loader, device, pipe, accs, collect_logits):
+    from sir_amd import ops
+    from sir_amd.scripts.train import HostStager
+    stage = HostStager(device, slots=4)
+    logits_all, labels_all = [], []
+    for i, (mel, label) in enumerate(tqdm(loader, desc="Evaluating")):
+        if mel is None or label is None or mel.size(0) == 0:
+            continue
+
+        def then(slot, out, label=label):
+            lab = label.to(device=device, dtype=torch.int64, non_blocking=True)
+            if accs is not None:
+                accs[slot].update(out[0], lab)
+            if collect_logits:
+                logits_all.append(out[0])
+                labels_all.append(lab)
+
+        pipe.infer(i, stage(mel), then=then)
+    pipe.synchronize()
+    ops.check_status()                    # a timed-out recurrence, or a label outside the classes
+    if collect_logits:
+        if not logits_all:
+            return None, None
+        return torch.cat(logits_all), torch.cat(labels_all)
+    from sir_amd.metrics import merge
+    state = accs[0].state_arrays()
+    for a in accs[1:]:
+        state = merge(state, a.state_arrays())
+    return None, None, state
+
+
+def fit_temperature_file(model, loader, device, out_path, source=None, iters=20):
+    """Fit beta = 1 / T on a loader's split and write ``temperature.json`` -> the dict written."""
+    from sir_amd.metrics import fit_temperature
+    logits, labels = predict_loader(model, loader, device, collect_logits=True)
+    if logits is None:
+        raise _native.SirError("fit_temperature: the split holds no usable batch")
+    beta, nll_before, nll_after = (float(v) for v in fit_temperature(logits, labels, iters=iters).cpu().tolist())
+    from sir_amd import ops
+    ops.check_status()
+    info = {"inv_temperature": beta, "temperature": 1.0 / beta, "nll_before": nll_before, "nll_after": nll_after,
+            "n": int(logits.shape[0]), "iters": int(iters), "source": source}
+    with open(out_path, "w") as f:
+        json.dump(info, f, indent=2)
+    logger.info(f"Fitted temperature T = {info['temperature']:.4f} (NLL {nll_before:.4f} -> {nll_after:.4f}); wrote {out_path}")
+    return info
+
+
+def read_temperature_file(path):
+    """``temperature.json`` -> inv_temperature (beta = 1 / T), validated."""
+    with open(path, "r") as f:
+        info = json.load(f)
+    beta = float(info["inv_temperature"])
+    if not (beta > 0.0 and beta != float("inf")):
+        raise ValueError(f"{path}: inv_temperature {beta!r} is not a positive finite number")
+    return beta
 
 
 def evaluate(args, config):
@@ -75,7 +152,23 @@ def evaluate(args, config):
     from sir_amd.scripts.train import loader_kwargs
     test_loader = DataLoader(test_dataset, batch_size=config.get("batch_size", 32), shuffle=False, collate_fn=collate_fn,
                              **loader_kwargs(config.get("num_workers", 4)))
+    inv_temperature = None
+    if getattr(args, "fit_temperature", None):
+        valid_dataset = FSCIntentDataset(csv_path=args.fit_temperature, label_map_path=args.label_map, is_training=False,
+                                         use_cache=config.get("use_feature_cache", True),
+                                         cache_dir=config.get("cache_dir", "data/cached_features"),
+                                         mel_spec_length=int(config.get("mel_spec_length", 200)),
+                                         n_fft=fe.n_fft, hop_length=fe.hop_length, win_length=fe.win_length)
+        valid_loader = DataLoader(valid_dataset, batch_size=config.get("batch_size", 32), shuffle=False, collate_fn=collate_fn,
+                                  **loader_kwargs(config.get("num_workers", 4)))
+        out_path = os.path.join(os.path.dirname(os.path.abspath(args.model_path)), "temperature.json")
+        inv_temperature = fit_temperature_file(model, valid_loader, device, out_path,
+                                               source=os.path.basename(args.fit_temperature))["inv_temperature"]
+    if getattr(args, "temperature_file", None):
+        inv_temperature = read_temperature_file(args.temperature_file)
     logger.info("Starting evaluation...")
+    if config.get("device_metrics", False):
+        return _evaluate_on_device(model, test_loader, device, config, inv_label_map, num_classes, inv_temperature)
     all_preds, all_labels = predict_loader(model, test_loader, device)
 
     from sklearn.metrics import accuracy_score, classification_report, confusion_matrix
@@ -92,6 +185,13 @@ def evaluate(args, config):
     with open(os.path.join(results_dir, "classification_report.txt"), "w") as f:
         f.write(f"Test Accuracy: {accuracy:.4f}\n\n")
         f.write(cls_report)
+    _plot_confusion(cm, target_names, results_dir)
+    logger.info(f"Evaluation results saved to {results_dir}")
+    return accuracy
+
+
+def _plot_confusion(cm, target_names, results_dir):
+    """``confusion_matrix.png`` of evaluate.py:100-114, for both routes."""
     try:
         import matplotlib
         matplotlib.use("Agg")
@@ -104,6 +204,36 @@ def evaluate(args, config):
         plt.close("all")
     except Exception as e:  # plotting is reporting, not part of the hot path
         logger.error(f"confusion matrix plot skipped: {e}")
+
+
+def _evaluate_on_device(model, test_loader, device, config, inv_label_map, num_classes, inv_temperature):
+    """The report of ``evaluate`` from an ``EvalAccumulator`` state: the same log lines, ``classification_report.txt`` and
+    ``confusion_matrix.png``, plus ``calibration.json``.  The model's head may be wider than the label map (31 classes, evaluate.py:45): the state
+    covers the head, the report the label map's classes, as ``classification_report(labels=...)`` does."""
+    from sir_amd import metrics
+    head = model.fc.weight.shape[0]
+    _, _, state = predict_loader(model, test_loader, device,
+                                 device_metrics={"num_classes": head, "n_bins": int(config.get("calibration_bins", 15)),
+                                                 "inv_temperature": inv_temperature})
+    report = metrics.report_from_state(state)
+    accuracy = report["accuracy"]
+    logger.info(f"Test Accuracy: {accuracy:.4f}")
+    labels_idx = list(range(num_classes))
+    target_names = [inv_label_map[i] for i in labels_idx]
+    cls_report = metrics.format_report(metrics.classification_from_confusion(state["confusion"], target_names, labels=labels_idx))
+    logger.info(f"Classification Report:\n{cls_report}")
+    results_dir = os.path.join(config["save_path"], "evaluation_results")
+    os.makedirs(results_dir, exist_ok=True)
+    with open(os.path.join(results_dir, "classification_report.txt"), "w") as f:
+        f.write(f"Test Accuracy: {accuracy:.4f}\n\n")
+        f.write(cls_report)
+    calib = metrics.calibration_json(report)
+    calib["inv_temperature"] = 1.0 if inv_temperature is None else float(inv_temperature)
+    with open(os.path.join(results_dir, "calibration.json"), "w") as f:
+        json.dump(calib, f, indent=2)
+    # the label map's block of the matrix: what confusion_matrix(labels=labels_idx) holds on the default route
+    _plot_confusion(state["confusion"][:num_classes, :num_classes], target_names, results_dir)
+    logger.info(f"Top-3 accuracy {report['top3']:.4f}, NLL {report['nll']:.4f}, ECE {report['ece']:.4f}, MCE {report['mce']:.4f}")
     logger.info(f"Evaluation results saved to {results_dir}")
     return accuracy
 
@@ -114,5 +244,8 @@ if __name__ == "__main__":
     parser.add_argument("--test_csv", type=str, required=True, help="Path to test CSV file")
     parser.add_argument("--label_map", type=str, required=True, help="Path to label map JSON file")
     parser.add_argument("--model_path", type=str, required=True, help="Path to trained model")
+    parser.add_argument("--fit_temperature", type=str, default=None, metavar="VALID_CSV",
+                        help="Fit the softmax temperature on this split and write temperature.json beside the checkpoint")
+    parser.add_argument("--temperature_file", type=str, default=None, help="temperature.json to calibrate the confidences with")
     args = parser.parse_args()
     evaluate(args, load_config(args.config))

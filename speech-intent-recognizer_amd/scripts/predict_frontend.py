@@ -16,7 +16,7 @@ import torch
 
 from sir_amd import ops
 from sir_amd.frontend_config import FrontEnd, as_frontend
-from sir_amd.scripts import test_model
+from sir_amd.scripts import classify_results, test_model
 from sir_amd.scripts.precompute_features import AudioFeatureExtractor
 
 logger = logging.getLogger(__name__)
@@ -32,9 +32,14 @@ def get_extractor(frontend=None):
     return _extractors[fe]
 
 
-def predict_many(model, audio_paths, label_map, device, pad_to=test_model.MAX_LENGTH, frontend=None):
+def predict_many(model, audio_paths, label_map, device, pad_to=test_model.MAX_LENGTH, frontend=None, on_device=False,
+                 temperature=None, min_confidence=None):
     """One feature pass at ``frontend`` and one forward for all files -> list of result dictionaries / ``None``.
-    ``pad_to=None`` needs a single file (un-padded features, ``T >= 8``)."""
+    ``pad_to=None`` needs a single file (un-padded features, ``T >= 8``).  ``on_device``, ``temperature``, ``min_confidence``:
+    the results come from ``classify_results.results_from_logits`` (one ``sir_classify`` launch and one copy for the batch instead of
+    several host round trips per file); ``temperature`` (T; probabilities of ``softmax(logits / T)``) and ``min_confidence`` (adds
+    ``"rejected"``) belong to that route: without ``on_device=True`` they raise ``ValueError``."""
+    classify_results.check_route(on_device, temperature, min_confidence)       # a caller's mistake: raised, not logged
     audio_paths = list(audio_paths)
     try:
         feats = get_extractor(frontend).extract_batch(audio_paths, max_duration=600.0)
@@ -51,8 +56,13 @@ def predict_many(model, audio_paths, label_map, device, pad_to=test_model.MAX_LE
         with torch.no_grad():
             output = model(batch)
         inv = {v: k for k, v in label_map.items()}
-        for row, i in enumerate(keep):
-            results[i] = test_model._result(output[row:row + 1], inv)
+        if on_device:
+            for res, i in zip(classify_results.results_from_logits(output, inv, inv_temperature=classify_results.inv_temperature_of(temperature),
+                                                             min_confidence=min_confidence), keep):
+                results[i] = res
+        else:
+            for row, i in enumerate(keep):
+                results[i] = test_model._result(output[row:row + 1], inv)
         ops.check_status()
         return results
     except Exception as e:

@@ -119,11 +119,12 @@ class IntentRecognizer:
             batch[k, :lens[k]] = w.to(self.device)
         return batch, torch.tensor(lens, dtype=torch.int32, device=self.device)
 
-    def score_segments(self, wave, lengths, pad_to=TRAINED_LENGTH):
+    def score_segments(self, wave, lengths, pad_to=TRAINED_LENGTH, logits_on_device=False):
         """Segment a GPU batch of recordings and score every utterance -> (seg_table int32 [n, 3] on the CPU, logits [n, C] on
         the CPU).  ``pad_to`` frames: every clip is cut to fewer than ``pad_to * hop`` samples (the trim of :231-232, in samples)
         and padded to ``pad_to`` frames; ``pad_to=None``: every clip is scored at its own length through the ragged forward
-        (``lengths=``), a clip with fewer than 8 frames at 8."""
+        (``lengths=``), a clip with fewer than 8 frames at 8.  ``logits_on_device=True`` leaves the logits where they were
+        computed (for ``classify_results.results_from_logits``)."""
         seg = self.segmenter
         hop = self.frontend.hop_length
         if pad_to == TRAINED_LENGTH:
@@ -143,15 +144,22 @@ class IntentRecognizer:
         feats = fz(clips, clip_lens, t_pad=t_pad)
         with torch.no_grad():
             logits = self.model(feats) if pad_to is not None else self.model(feats, lengths=frames)
-        logits = logits.cpu()
+        if not logits_on_device:
+            logits = logits.cpu()
         ops.check_status()
         return host_table, logits
 
-    def recognize_recordings(self, waves_or_paths, pad_to=TRAINED_LENGTH):
+    def recognize_recordings(self, waves_or_paths, pad_to=TRAINED_LENGTH, on_device=False, temperature=None, min_confidence=None):
         """waves_or_paths: recordings as 1-D float32 / int16 arrays or tensors at the segmenter's sample rate, or paths of WAVE
         files (decoded, mixed to mono and resampled on the GPU).  -> per recording, the list of its utterances in time order:
         ``{"start": seconds, "end": seconds, "predicted_label", "confidence", "top_predictions"}``; ``None`` for the recordings of
-        a group that failed (logged, as the reference's ``predict`` does)."""
+        a group that failed (logged, as the reference's ``predict`` does).
+        ``on_device=True``: softmax, confidence and top-3 of all utterances of a group come from one ``sir_classify`` launch and
+        one copy (``classify_results.results_from_logits``) instead of several host round trips per utterance; ``temperature`` (T,
+        probabilities of ``softmax(logits / T)``) and ``min_confidence`` (every utterance also carries ``"rejected"``) belong
+        to that route: without ``on_device=True`` they raise ``ValueError``."""
+        from sir_amd.scripts import classify_results
+        classify_results.check_route(on_device, temperature, min_confidence)
         items = list(waves_or_paths)
         results = [None] * len(items)
         sr = float(self.segmenter.sample_rate)
@@ -159,10 +167,15 @@ class IntentRecognizer:
             group = items[g:g + GROUP]
             try:
                 wave, lens = self._load_group(group)
-                table, logits = self.score_segments(wave, lens, pad_to=pad_to)
+                table, logits = self.score_segments(wave, lens, pad_to=pad_to, logits_on_device=on_device)
                 found = [[] for _ in group]
+                batch_res = None
+                if on_device and table.shape[0] > 0:
+                    batch_res = classify_results.results_from_logits(logits, self.inv_label_map,
+                                                                     inv_temperature=classify_results.inv_temperature_of(temperature),
+                                                                     min_confidence=min_confidence)
                 for row, (r, a, b) in enumerate(table.tolist()):
-                    res = test_model._result(logits[row:row + 1], self.inv_label_map)
+                    res = batch_res[row] if batch_res is not None else test_model._result(logits[row:row + 1], self.inv_label_map)
                     found[r].append({"start": a / sr, "end": b / sr, **res})
                 results[g:g + len(group)] = found
             except Exception as e:

@@ -2,7 +2,7 @@
 // library): random fp32 operands -> bf16x3 planes -> every kernel generation, HIP-event timing,
 // max difference against generation 1 and against an fp64 host dot product on sampled entries.
 //   build: make -C speech-intent-recognizer_amd/csrc tools     run (GPU box): lib/bench_gemm [M] [K] [A.f32 B.f32 [bias.f32]]
-//                                                                           lib/bench_gemm gather [B] [S] [d3]   (row-list mode, below)
+//                                                                           lib/bench_gemm gather [B] [S] [d3] [K]   (row-list mode, below)
 // (A.f32 = [M][K], B.f32 = [2 * 768][K] raw float32 files: the REAL projection operands dumped by devtools/dump_gemm_operands.py)
 // Round 4: the two-way fp16 split ("f16x3": 3 products, 2 planes; f16x3_kernels.h) beside bf16x6, with a float64 product of the
 // same fp32 operands (computed on the GPU) as the error reference for both.
@@ -154,15 +154,15 @@ static float time_h3w4(hipStream_t st, const unsigned short* Ap, const unsigned 
 // the others must keep their 0xFF sentinel.  Then the list of ALL rows (unpadded input) against today's dense launch.
 template <int FBM>
 static float time_gather(hipStream_t st, const unsigned short* Ap, const unsigned short* B0, const unsigned short* B1, const float* bias,
-                         float* C, const int* rows, int MA, int N, int K, int reps, int ncu) {
+                         float* C, const int* rows, int MA, int N, int K, int reps, int ncu, int throughput = 0) {
     hipFuncSetAttribute((const void*)gemm_nt_f16x3_gather_kernel<0, FBM>, hipFuncAttributeMaxDynamicSharedMemorySize, h3_lds_bytes(3));
     const int nwg = h3_gather_tiles(96, MA, N);
     hipEvent_t e0, e1;
     hipEventCreate(&e0); hipEventCreate(&e1);
-    hipLaunchKernelGGL((gemm_nt_f16x3_gather_kernel<0, FBM>), dim3(nwg), dim3(512), h3_lds_bytes(3), st, Ap, B0, B1, bias, bias + N, C, 2 * N, rows, MA, N, K, ncu);
+    hipLaunchKernelGGL((gemm_nt_f16x3_gather_kernel<0, FBM>), dim3(nwg), dim3(512), h3_lds_bytes(3), st, Ap, B0, B1, bias, bias + N, C, 2 * N, rows, MA, N, K, ncu, throughput, (int*)nullptr);
     hipEventRecord(e0, st);
     for (int i = 0; i < reps; ++i)
-        hipLaunchKernelGGL((gemm_nt_f16x3_gather_kernel<0, FBM>), dim3(nwg), dim3(512), h3_lds_bytes(3), st, Ap, B0, B1, bias, bias + N, C, 2 * N, rows, MA, N, K, ncu);
+        hipLaunchKernelGGL((gemm_nt_f16x3_gather_kernel<0, FBM>), dim3(nwg), dim3(512), h3_lds_bytes(3), st, Ap, B0, B1, bias, bias + N, C, 2 * N, rows, MA, N, K, ncu, throughput, (int*)nullptr);
     hipEventRecord(e1, st);
     hipEventSynchronize(e1);
     float ms = 0;
@@ -170,8 +170,8 @@ static float time_gather(hipStream_t st, const unsigned short* Ap, const unsigne
     return ms * 1000.0f / reps;
 }
 
-static int gather_main(int B, int S, int d3) {
-    const int K = 1024, N = 768, MA = (B + 1) * S, reps = 50;
+static int gather_main(int B, int S, int d3, int K) {
+    const int N = 768, MA = (B + 1) * S, reps = 50;
     int ncu = 256;
     CK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, 0));
     std::vector<float> hA((size_t)MA * K), hB((size_t)2 * N * K), hbias(2 * N);
@@ -227,17 +227,18 @@ static int gather_main(int B, int S, int d3) {
         ok = ok && !bad && !touched;
         return 0;
     };
-    auto run = [&](auto fbm_c, const char* name, const std::vector<int>& l, const int* dl) {
+    auto run = [&](auto fbm_c, const char* name, const std::vector<int>& l, const int* dl, int throughput = 0) {
         constexpr int FBM = decltype(fbm_c)::value;
         CK(hipMemset(Cg, 0xFF, cbytes));
-        const float t = time_gather<FBM>(st, pA, B0, B1, dbias, Cg, dl, MA, N, K, reps, ncu);
-        const int c = l[0], bm = FBM ? FBM : (h3_gather_tiles(96, c, N) <= ncu ? 96 : h3_gather_tiles(128, c, N) <= ncu ? 128 : 160);
+        const float t = time_gather<FBM>(st, pA, B0, B1, dbias, Cg, dl, MA, N, K, reps, ncu, throughput);
+        const int c = l[0], bm = FBM ? FBM : throughput ? h3_gather_bm_throughput(c, N, K, ncu) : h3_gather_bm(c, N, ncu);
         return check(name, l, t, bm);
     };
     run(std::integral_constant<int, 96>{}, "row list, BM = 96", list, dlist);
     run(std::integral_constant<int, 128>{}, "row list, BM = 128", list, dlist);
     run(std::integral_constant<int, 160>{}, "row list, BM = 160", list, dlist);
-    run(std::integral_constant<int, 0>{}, "row list, device choice", list, dlist);
+    run(std::integral_constant<int, 0>{}, "row list, device choice (latency rule)", list, dlist);
+    run(std::integral_constant<int, 0>{}, "row list, device choice (throughput rule)", list, dlist, 1);
     run(std::integral_constant<int, 0>{}, "all rows (unpadded), device choice", all, dall);
     run(std::integral_constant<int, 160>{}, "all rows (unpadded), BM = 160", all, dall);
     // unpadded input: the list of all rows against today's dense launch, alternated, medians of 7 (timing drifts by a few us between runs)
@@ -264,7 +265,8 @@ static bool read_f32(const char* path, std::vector<float>& v) {
 
 int main(int argc, char** argv) {
     if (argc > 1 && std::string(argv[1]) == "gather")
-        return gather_main(argc > 2 ? atoi(argv[2]) : 256, argc > 3 ? atoi(argv[3]) : 25, argc > 4 ? atoi(argv[4]) : 13);
+        return gather_main(argc > 2 ? atoi(argv[2]) : 256, argc > 3 ? atoi(argv[3]) : 25, argc > 4 ? atoi(argv[4]) : 13,
+                           argc > 5 ? atoi(argv[5]) : 1024);
     const int M = argc > 1 ? atoi(argv[1]) : 6400, K = argc > 2 ? atoi(argv[2]) : 1024, N = 768, reps = 20;
     std::vector<float> hA((size_t)M * K), hB((size_t)2 * N * K), hbias(2 * N);
     srand(1);

@@ -303,25 +303,51 @@ static __global__ __launch_bounds__(512) void gemm_nt_f16x3_kernel(
 // compute, distinct and in ascending order; C row rows[1 + i] receives output row i, and every other C row is left alone.  A list
 // of all MA rows is the identity: on the 160-row tile it runs the dense kernel's tile, without the lookups.  The list lives in
 // device memory, so the grid is sized on the host for the worst case (count = MA) at the smallest tile, and each workgroup reads the
-// real count: the tile is the SMALLEST of 96 / 128 / 160 rows (FBM: forced, for the harness) whose tiles fit one workgroup per CU
-// (ncu), else 160 -- an unpadded batch keeps the dense kernel's 160-row schedule and code -- and workgroups past the real tile count
-// exit before any barrier.  Tile ids are dealt to the XCDs over the REAL tile count.  Each output element sees the same MFMA
-// sequence as in the dense kernel: the results are bit-identical to it.  LDS request: h3_lds_bytes(3) (the 160-row stages).
+// real count and picks the tile (FBM: forced, for the harness) by one of two rules; workgroups past the real tile count exit before
+// any barrier.  Tile ids are dealt to the XCDs over the REAL tile count.  Each output element sees the same MFMA sequence as in the
+// dense kernel under every tile: the results are bit-identical to it.  LDS request: h3_lds_bytes(3) (the 160-row stages).
+//
+// LATENCY rule (h3_gather_bm; a launch that has the chip to itself): the SMALLEST of 96 / 128 / 160 rows whose tiles fit one
+// workgroup per CU (ncu), else 160 -- an unpadded batch keeps the dense kernel's 160-row schedule and code.  It minimises the
+// duration of the launch.
+// THROUGHPUT rule (h3_gather_bm_throughput; launches that alternate between streams, sir_handle::cluster_multi): a workgroup holds
+// a whole CU (full LDS), so while another stream's kernels want the CUs what counts is the CU time held, tiles x time per tile.
+// The rule takes the tile that minimises ceil(count / bm) * cost(bm) (the smaller tile on a tie), cost = the measured time of one
+// tile on a CU of its own (h3_gather_cost, 0.1 us; profiles/r10/README.md: MI355X, lib/bench_gemm gather, 3 353 listed rows):
+//     K = 1024:  96 rows 40.2 us   128 rows 44.7 us   160 rows 51.3 us  (r06: 40.8 / 45.3 / 51.8)
+//     K =  512:  96 rows 23.6 us   128 rows 26.1 us   160 rows 29.4 us  (the ragged path's layer-1 call)
+// At the bench shape that is 126 workgroups of 160 rows, 6 464 workgroup-us, against 210 of 96 rows, 8 442 -- and 126 fit the 128
+// CUs beside a GRU launch in one wave.  Pipelined step at batch 256: +2.6 to +3.4 % (r10), the 128-row tile forced: +1.2 %.
+// FLOOR: CU time only matters when other work wants the CUs.  At or below H3_TP_FLOOR tiles of 96 rows the latency rule stays:
+// pipelined over two streams (r10), the throughput rule loses 2 % at batch 128 per stream (1 689 rows, 108 tiles of 96 rows) and
+// 4 % at batch 64 (54 tiles), ties at 32 and 16, and wins at 256 (210 tiles); the floor is the largest count at which it lost.
 // ------------------------------------------------------------------------------------------
 __host__ __device__ constexpr int h3_gather_tiles(int bm, int count, int N) { return (count + bm - 1) / bm * 2 * (N / H3_BN); }
-__device__ __forceinline__ int h3_gather_bm(int count, int N, int ncu) {
+__host__ __device__ constexpr int h3_gather_bm(int count, int N, int ncu) {
     return h3_gather_tiles(96, count, N) <= ncu ? 96 : h3_gather_tiles(128, count, N) <= ncu ? 128 : 160;
 }
+__host__ __device__ constexpr int h3_gather_cost(int bm, int K) {
+    return K > 512 ? (bm == 96 ? 402 : bm == 128 ? 447 : 513) : (bm == 96 ? 236 : bm == 128 ? 261 : 294);
+}
+constexpr int H3_TP_FLOOR = 108;
+__host__ __device__ constexpr int h3_gather_bm_throughput(int count, int N, int K, int ncu) {
+    if (h3_gather_tiles(96, count, N) <= H3_TP_FLOOR) return h3_gather_bm(count, N, ncu);
+    const int c96 = (count + 95) / 96 * h3_gather_cost(96, K), c128 = (count + 127) / 128 * h3_gather_cost(128, K),
+              c160 = (count + 159) / 160 * h3_gather_cost(160, K);
+    return c96 <= c128 && c96 <= c160 ? 96 : c128 <= c160 ? 128 : 160;
+}
 
+// `throughput`: the tile rule (above).  `rec` (optional, 2 ints): workgroup 0 leaves the row count it read and the tile it chose.
 template <int KNOCK = 0, int FBM = 0>
 static __global__ __launch_bounds__(512) void gemm_nt_f16x3_gather_kernel(
     const unsigned short* __restrict__ Ap, const unsigned short* __restrict__ Bp0, const unsigned short* __restrict__ Bp1,
     const float* __restrict__ bias0, const float* __restrict__ bias1, float* __restrict__ C, int ldc, const int* __restrict__ rows,
-    int MA, int N, int K, int ncu) {
+    int MA, int N, int K, int ncu, int throughput, int* __restrict__ rec) {
     __shared__ __attribute__((aligned(16))) int rtab[512];
     const int count = rows[0];
-    const int bm = FBM ? FBM : h3_gather_bm(count, N, ncu);
+    const int bm = FBM ? FBM : throughput ? h3_gather_bm_throughput(count, N, K, ncu) : h3_gather_bm(count, N, ncu);
     const int nt = h3_gather_tiles(bm, count, N);
+    if (blockIdx.x == 0 && threadIdx.x == 0 && rec) { rec[0] = count; rec[1] = bm; }
     if ((int)blockIdx.x >= nt) return;
     const int wgid = h3_xcd_tile(blockIdx.x, nt);
     if (bm == 96) h3_gemm_tile<3, KNOCK, 96, true>(Ap, Bp0, Bp1, bias0, bias1, C, ldc, count, MA, N, K, wgid, rows + 1, rtab);
@@ -346,15 +372,16 @@ static inline int launch_gemm_nt_f16x3(sir_handle* h, hipStream_t st, const unsi
     return SIR_OK;
 }
 
-// the same over the row list `rows` (device memory: rows[0] = count <= MA, then the rows) of A's MA-row planes; no host sync
+// the same over the row list `rows` (device memory: rows[0] = count <= MA, then the rows) of A's MA-row planes; no host sync.
+// `throughput`: the tile rule for launches that share the chip with another stream's (above); `rec`: 2 ints or nullptr
 static inline int launch_gemm_nt_f16x3_gather(sir_handle* h, hipStream_t st, const unsigned short* Ap, const unsigned short* Bp0,
                                                      const unsigned short* Bp1, const float* bias0, const float* bias1, float* C, int ldc,
-                                                     const int* rows, int MA, int N, int K) {
+                                                     const int* rows, int MA, int N, int K, bool throughput, int* rec) {
     // (K >= 2 BK: the K loop's barriers publish rtab)
     SIR_HIP_TRY(gemm_f16x3_ok(MA, N, K) && K >= 2 * H3_BK && (size_t)MA * ldc < ((size_t)1 << 31) ? hipSuccess : hipErrorInvalidValue);
     SIR_TRY(sir_lds_opt_in(h, (const void*)gemm_nt_f16x3_gather_kernel<0, 0>, h3_lds_bytes(3)));
     hipLaunchKernelGGL((gemm_nt_f16x3_gather_kernel<0, 0>), dim3(h3_gather_tiles(96, MA, N)), dim3(512), h3_lds_bytes(3), st, Ap, Bp0, Bp1,
-                       bias0, bias1, C, ldc, rows, MA, N, K, h->num_cus);
+                       bias0, bias1, C, ldc, rows, MA, N, K, h->num_cus, throughput ? 1 : 0, rec);
     SIR_KCHECK();
     return SIR_OK;
 }

@@ -38,7 +38,8 @@ enum WsBuf {
     WS_Y1,       // GRU layer 1 output [B][S][512]
     WS_CTX,      // attention-pooled context [B][512]
     WS_PAD,      // pad-skip tables (int): E0[B], conv1 columns d1[B + 1], GRU steps d3[B + 1], conv2 / conv3 task-column lists,
-                 // layer-0 projection row list.  Ragged: validated frames[B] in E0's place, d1 = W1, d3 = S_b, the tight lists
+                 // layer-0 projection row list.  Ragged: validated frames[B] in E0's place, d1 = W1, d3 = S_b, the tight lists.
+                 // Behind the tables: what the latest row-list projection read and chose, {rows, tile} (ops.proj_tile_record)
     WS_XZ,       // all-zero feature row [64][T] of the template utterance (zeroed by pad_tables_kernel on every call)
     WS_BN,       // folded BN: scale[224] then shift[224] (channels of bn1|bn2|bn3)
     WS_WHT,      // W_hh fragments of the recurrence kernel, [4 (layer, direction)][GRU_FRAG_BYTES]
@@ -61,7 +62,7 @@ bool make_dims(int batch, int t_frames, Dims* d) {
 }
 
 // int offsets inside WS_PAD
-struct PadTabs { size_t e0, d1, d3, tab2, tab3, rows, count; };
+struct PadTabs { size_t e0, d1, d3, tab2, tab3, rows, count; };     // (count: the tables' ints; behind them the projection's record, 2 ints)
 PadTabs pad_tabs(const Dims& d) {
     PadTabs t;
     const size_t n = (size_t)d.B + 1;
@@ -83,7 +84,7 @@ void ws_sizes(const Dims& d, size_t* bytes) {
     bytes[WS_Y0] = (size_t)d.B * d.S * 512 * 4;
     bytes[WS_Y1] = (size_t)d.B * d.S * 512 * 4;
     bytes[WS_CTX] = (size_t)d.B * 512 * 4;
-    bytes[WS_PAD] = pad_tabs(d).count * 4;
+    bytes[WS_PAD] = (pad_tabs(d).count + 2) * 4;                // + {row count read, tile chosen} of the latest row-list projection
     bytes[WS_XZ] = (size_t)64 * d.T * 4;
     bytes[WS_BN] = (size_t)2 * 224 * 4;
     bytes[WS_WHT] = 4 * GRU_FRAG_BYTES;                         // W_hh as the resident f16x2 MFMA fragments of the recurrence kernel
@@ -346,6 +347,10 @@ static int model_infer_impl(const char* who, sir_handle* h, const sir_model_weig
     const PadTabs pt = pad_tabs(d);
     int* const ptab = (int*)(ws + off[WS_PAD]);
     float* const xz = (float*)(ws + off[WS_XZ]);
+    // tile rule of the row-list projections (f16x3_kernels.h): CU time instead of latency while launches alternate between streams.
+    // Read once per call (the recurrence launches below may flip it)
+    const bool proj_throughput = h->cluster_multi;
+    int* const proj_rec = ptab + pt.count;
 
     // conv2 / conv3 as Winograd F(2x2, 3x3) -- the 2x2 output tile is the pooling window -- on the producer / consumer kernel
     // (conv_wino2_f16x3_kernel.h); shapes it does not cover (batch x map beyond 32-bit offsets) keep the bf16x6 fallback kernels.
@@ -439,7 +444,7 @@ static int model_infer_impl(const char* who, sir_handle* h, const sir_model_weig
         if (w2 || ragged)                                         // (ragged: the rows s < S_b of every utterance, on either conv path)
             SIR_TRY(launch_gemm_nt_f16x3_gather(h, st, (const unsigned short*)xs, (const unsigned short*)wsl0,
                                                     (const unsigned short*)(wsl0 + (size_t)2 * 768 * 1024), w->gru_b_ih[0], w->gru_b_ih[1], gi, 1536,
-                                                    (const int*)(ptab + pt.rows), BT * S, 768, 1024));
+                                                    (const int*)(ptab + pt.rows), BT * S, 768, 1024, proj_throughput, proj_rec));
         else
             SIR_TRY(launch_gemm_nt_f16x3(h, st, (const unsigned short*)xs, (const unsigned short*)wsl0,
                                              (const unsigned short*)(wsl0 + (size_t)2 * 768 * 1024), w->gru_b_ih[0], w->gru_b_ih[1], gi, 1536, M, 768, 1024));
@@ -455,7 +460,7 @@ static int model_infer_impl(const char* who, sir_handle* h, const sir_model_weig
         if (ragged)                                               // the same row list: layer 0 wrote y0's planes for exactly these rows
             SIR_TRY(launch_gemm_nt_f16x3_gather(h, st, (const unsigned short*)xs, (const unsigned short*)wsl1,
                                                     (const unsigned short*)(wsl1 + (size_t)2 * 768 * 512), w->gru_b_ih[2], w->gru_b_ih[3], gi, 1536,
-                                                    (const int*)(ptab + pt.rows), M, 768, 512));
+                                                    (const int*)(ptab + pt.rows), M, 768, 512, proj_throughput, proj_rec));
         else
         SIR_TRY(launch_gemm_nt_f16x3(h, st, (const unsigned short*)xs, (const unsigned short*)wsl1,
                                          (const unsigned short*)(wsl1 + (size_t)2 * 768 * 512), w->gru_b_ih[2], w->gru_b_ih[3], gi, 1536, M, 768, 512));

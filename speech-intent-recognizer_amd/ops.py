@@ -248,10 +248,8 @@ def stage_views(ws, bsz, t):
     return out
 
 
-def pad_skip_tables(ws, bsz, t):
-    """The pad-skip tables the last padded ``model_infer`` call on ``ws`` left (csrc/model_infer.hip, WS_PAD), on the host:
-    ``e0`` [B], ``d3`` [B + 1] (the template utterance last) and the conv2 / conv3 task lists (``Wino2Geo::ctab`` in
-    csrc/wino2_geo.h) as int32 arrays ``tab2`` / ``tab3`` of shape [n, 2]: the two words of each listed task."""
+def _pad_table_offsets(bsz, t):
+    """int offsets inside WS_PAD (PadTabs in csrc/model_infer.hip) and the byte offset of WS_PAD in the workspace"""
     lib = _native.lib()
     offs = (C.c_size_t * 16)()
     if lib.sir_model_workspace_offsets(get_featurizer().handle, bsz, t, 0, offs, 16) <= 7:
@@ -265,9 +263,27 @@ def pad_skip_tables(ws, bsz, t):
     o_tab2 += o_tab2 & 1
     o_tab3 = o_tab2 + 2 + 2 * n * k2max
     o_end = o_tab3 + 2 + 2 * n * k3max
-    tab = ws[offs[7]: offs[7] + 4 * o_end].view(torch.int32).cpu()
+    return offs[7], o_d3, o_tab2, o_tab3, o_end
+
+
+def pad_skip_tables(ws, bsz, t):
+    """The pad-skip tables the last padded ``model_infer`` call on ``ws`` left (csrc/model_infer.hip, WS_PAD), on the host:
+    ``e0`` [B], ``d3`` [B + 1] (the template utterance last) and the conv2 / conv3 task lists (``Wino2Geo::ctab`` in
+    csrc/wino2_geo.h) as int32 arrays ``tab2`` / ``tab3`` of shape [n, 2]: the two words of each listed task."""
+    base, o_d3, o_tab2, o_tab3, o_end = _pad_table_offsets(bsz, t)
+    n = bsz + 1
+    tab = ws[base: base + 4 * o_end].view(torch.int32).cpu()
     out = {"e0": tab[:bsz], "d3": tab[o_d3: o_d3 + n]}
     for name, o in (("tab2", o_tab2), ("tab3", o_tab3)):
         cnt = int(tab[o])
         out[name] = tab[o + 2: o + 2 + 2 * cnt].view(cnt, 2)
     return out
+
+
+def proj_tile_record(ws, bsz, t):
+    """What the latest row-list input projection of a ``model_infer`` call on ``ws`` read and chose (two ints behind the pad-skip
+    tables, written by workgroup 0 of ``gemm_nt_f16x3_gather_kernel``): ``(rows, tile)`` -- the listed row count and the tile
+    height, 96 / 128 / 160 rows.  A padded call leaves layer 0's record, a ragged call layer 1's (K = 512, the same row list)."""
+    base, _, _, _, o_end = _pad_table_offsets(bsz, t)
+    rec = ws[base + 4 * o_end: base + 4 * o_end + 8].view(torch.int32).cpu()
+    return int(rec[0]), int(rec[1])

@@ -286,7 +286,7 @@ typedef struct sir_model_weights {
 
 /* sir_model_infer replaces CNNAudioGRU.forward in eval() (models/models.py:41-68) followed by
  * torch.argmax(outputs, dim=1) (scripts/evaluate.py:82-83) / torch.max (scripts/train.py:149).
- * feats  : [batch][64][t_frames] f32 (t_frames >= 8; 200 on the training path)
+ * feats  : [batch][64][t_frames] f32 (8 <= t_frames <= 2055; 200 on the training path)
  * logits : [batch][num_classes] f32
  * argmax : int64[batch] or NULL
  * workspace: sir_model_workspace_bytes(batch, t_frames, 0) bytes, 256-byte aligned
@@ -309,7 +309,12 @@ int sir_model_workspace_offsets(const sir_handle* h, int batch, int t_frames, in
  * reused instead of rebuilt (~40 us per call).  0 (the default) = always rebuild. */
 int sir_model_set_weights_version(sir_handle* h, uint64_t version);
 /* Batch regimes (256 CUs): the GRU recurrences hold half the chip at batch 256 and all of it at 512; beyond that they are oversubscribed and rest
- * on in-order dispatch.  Tested against the oracle up to batch 1041 (tests/test_large_batch_gpu.py); batches above 1100 are untested. */
+ * on in-order dispatch.  Tested against the oracle up to batch 1041 (tests/test_large_batch_gpu.py); batches above 1100 are untested.
+ * Sequence regimes: 8 <= t_frames <= 2055 on every model entry point, inference and training alike (a shape outside it, or a batch above
+ * 65535, is SIR_EINVAL; sir_model_workspace_bytes returns 0).  The GRU runs S = t_frames / 8 steps and the attention kernels hold one
+ * score per step in LDS arrays of 256, which is what limits the range: 2055 frames are 256 steps -- 20 s at a 10 ms hop, 65 s at the default
+ * 32 ms one.  The step field of a recurrence exchange tag (9 bits, step + 1) ends there as well.  Tested against the oracle up to 2055 frames
+ * (tests/test_long_sequence_gpu.py), at batches up to 17 in inference and up to 8 in training. */
 int sir_model_infer(sir_handle* h, const sir_model_weights* w, const float* feats, int batch,
                     int t_frames, float* logits, int64_t* argmax, void* workspace,
                     size_t workspace_bytes, void* stream);

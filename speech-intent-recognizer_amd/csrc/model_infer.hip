@@ -302,7 +302,10 @@ extern "C" int sir_model_workspace_offsets(const sir_handle* h, int batch, int t
                                            int n) {
     (void)h; (void)train;
     Dims d;
-    if (!make_dims(batch, t_frames, &d) || !offsets) { sir_set_error("sir_model_workspace_offsets: bad shape"); return SIR_EINVAL; }
+    if (!make_dims(batch, t_frames, &d) || !offsets) {
+        sir_set_error("sir_model_workspace_offsets: bad shape batch=%d t_frames=%d (need " SIR_SHAPE_LIMITS ")", batch, t_frames);
+        return SIR_EINVAL;
+    }
     size_t off[WS_COUNT];
     ws_layout(d, off);
     for (int i = 0; i < n && i < WS_COUNT; ++i) offsets[i] = off[i];
@@ -315,7 +318,7 @@ static int model_infer_impl(const char* who, sir_handle* h, const sir_model_weig
     if (!h || !w || !feats || !logits || !workspace) { sir_set_error("%s: NULL argument", who); return SIR_EINVAL; }
     Dims d;
     if (!make_dims(batch, t_frames, &d)) {
-        sir_set_error("%s: unsupported shape batch=%d t_frames=%d (need t_frames >= 8)", who, batch, t_frames);
+        sir_set_error("%s: unsupported shape batch=%d t_frames=%d (need " SIR_SHAPE_LIMITS ")", who, batch, t_frames);
         return SIR_EINVAL;
     }
     if (h->cfg.n_mels != 64) { sir_set_error("%s: the model is wired for 64 mels (models.py:23)", who); return SIR_EUNSUPPORTED; }

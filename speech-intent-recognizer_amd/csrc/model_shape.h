@@ -6,6 +6,8 @@
 #include "wino2_geo.h"
 
 constexpr int ATT_MAX_S = 256;      // GRU steps the attention kernels hold in LDS (model_kernels.h, train_bwd_kernels.h)
+// what sir_make_dims accepts, for the refusal messages: S = t_frames / 8 in [1, ATT_MAX_S] (2055 / 8 = 256, 2056 / 8 = 257)
+#define SIR_SHAPE_LIMITS "8 <= t_frames <= 2055 (at most 256 GRU steps), batch <= 65535"
 
 // conv stage `conv` (2 or 3) runs on its Winograd kernel (second-generation forward / data gradient, Winograd weight gradient) if
 // `shape_ok` -- else on the first-generation / direct fallback.  Test-only SIR_CONV_FALLBACK: 1 = conv2's stages do not fit, 2 = none do.

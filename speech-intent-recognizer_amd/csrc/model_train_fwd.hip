@@ -16,7 +16,10 @@ size_t sir_train_workspace_bytes_impl(int batch, int t_frames) {
 extern "C" int sir_model_train_workspace_offsets(const sir_handle* h, int batch, int t_frames, size_t* offsets, int n) {
     (void)h;
     TDims d;
-    if (!make_tdims(batch, t_frames, &d) || !offsets) { sir_set_error("sir_model_train_workspace_offsets: bad shape"); return SIR_EINVAL; }
+    if (!make_tdims(batch, t_frames, &d) || !offsets) {
+        sir_set_error("sir_model_train_workspace_offsets: bad shape batch=%d t_frames=%d (need " SIR_SHAPE_LIMITS ")", batch, t_frames);
+        return SIR_EINVAL;
+    }
     size_t off[TB_COUNT];
     tws_layout(d, off);
     for (int i = 0; i < n && i < TB_COUNT; ++i) offsets[i] = off[i];

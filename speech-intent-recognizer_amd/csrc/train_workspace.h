@@ -184,7 +184,7 @@ static const sir_train_config kTrainAllLive = {{0, 0, 0}};      // what a NULL s
 static inline int check_common(const char* who, sir_handle* h, const sir_model_weights* w, int batch, int t, void* ws, size_t bytes,
                                TDims* d, size_t* off) {
     if (!h || !w || !ws) { sir_set_error("%s: NULL argument", who); return SIR_EINVAL; }
-    if (!make_tdims(batch, t, d)) { sir_set_error("%s: unsupported shape batch=%d t_frames=%d", who, batch, t); return SIR_EINVAL; }
+    if (!make_tdims(batch, t, d)) { sir_set_error("%s: unsupported shape batch=%d t_frames=%d (need " SIR_SHAPE_LIMITS ")", who, batch, t); return SIR_EINVAL; }
     if (h->cfg.n_mels != 64) { sir_set_error("%s: the model is wired for 64 mels", who); return SIR_EUNSUPPORTED; }
     if (w->num_classes < 1 || w->num_classes > 64) { sir_set_error("%s: num_classes=%d", who, w->num_classes); return SIR_EINVAL; }
     const size_t need = tws_layout(*d, off);

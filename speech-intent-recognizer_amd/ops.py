@@ -14,6 +14,8 @@ from .featurizer import get_featurizer
 
 GRU_SUFFIXES = ("_l0", "_l0_reverse", "_l1", "_l1_reverse")
 WS_NAMES = ("conv1", "conv2", "gru_in", "gi", "gru_l0", "gru_l1", "ctx")
+# what every model entry point accepts (csrc/model_shape.h: the GRU runs frames / 8 steps, the attention kernels hold 256)
+SHAPE_LIMITS = "need 8 <= frames <= 2055 (at most 256 GRU steps), batch <= 65535"
 
 
 def _f32c(t, name):
@@ -143,7 +145,7 @@ def _as_features(x):
     if x.dim() != 3 or x.shape[1] != 64:
         raise _native.SirError(f"expected [B,64,T] or [B,1,64,T], got {tuple(x.shape)}")
     if x.shape[2] < 8:
-        raise _native.SirError("need at least 8 frames")
+        raise _native.SirError(f"need at least 8 frames, got {x.shape[2]} ({SHAPE_LIMITS})")
     return _f32c(x.contiguous(), "input")
 
 
@@ -176,7 +178,7 @@ def model_infer(mod, x, workspace, want_argmax=False, debug=None, lengths=None):
     h = get_featurizer().handle
     need = lib.sir_model_workspace_bytes(h, bsz, t, 0)
     if need == 0:
-        raise _native.SirError(f"unsupported shape batch={bsz} frames={t}")
+        raise _native.SirError(f"unsupported shape batch={bsz} frames={t} ({SHAPE_LIMITS})")
     if lengths is not None:
         lengths = _as_lengths(lengths, bsz, t, x.device)
     ws = workspace.get(need, x.device)

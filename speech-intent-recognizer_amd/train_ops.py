@@ -220,7 +220,7 @@ class _TrainStep(torch.autograd.Function):
         st = _train_state(mod)
         need = lib.sir_model_workspace_bytes(h, bsz, t, 1)
         if need == 0:
-            raise _native.SirError(f"unsupported shape batch={bsz} frames={t}")
+            raise _native.SirError(f"unsupported shape batch={bsz} frames={t} ({ops.SHAPE_LIMITS})")
         ws = st["ws"].get(need, x.device)
         w, keep = ops.cached_weights(mod)
         rm, rv = _bn_ptr_arrays(mod)

@@ -51,14 +51,12 @@ import pytest
 import torch
 
 import cases
-import host_rng
-import input_grad_ref
 import recipe_ref
 from oracle import model_ref
 from sir_amd import _native, ops, synth, train_ops
 from sir_amd.featurizer import get_featurizer
 from sir_amd.models.models import CNNAudioGRU
-from train_step_ref import _device_forward_values, _grad_errors, _loss_scale, _oracle_f64, _rel, _views
+from train_step_ref import _training_case
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -325,76 +323,9 @@ def _c_backward(m, x, dlogits, parts):
     return buf.flat
 
 
-def _training_case(sd, bsz, dropout=0.0, want_dx=False):
-    x = cases.varied_features(bsz, T, seed=3000 + bsz)
-    y = synth.synth_labels(bsz, 31, seed=3001 + bsz)
-    m = _train_model(sd, dropout)
-    m.zero_grad(set_to_none=True)
-    xd = x.to(DEV).requires_grad_(want_dx)
-    logits = m(xd)
-    loss = train_ops.fused_cross_entropy(logits, y.to(DEV))
-    loss.backward()
-    torch.cuda.synchronize()
-    mask = None
-    if dropout:
-        seed, p_used = m._sir_last_dropout
-        assert p_used == dropout
-        keep = torch.from_numpy(host_rng.dropout_keep(seed, bsz * S * 512, dropout)).view(bsz, S, 512)
-        assert 0.45 < keep.float().mean().item() < 0.55
-        offs = (C.c_size_t * 40)()
-        _native.lib().sir_model_train_workspace_offsets(get_featurizer().handle, bsz, T, offs, 40)
-        ws, n = m._sir_train["ws"].buf, bsz * S * 512
-        y0 = ws[offs[8]: offs[8] + 4 * n].view(torch.float32).view(bsz, S, 512).cpu()
-        y0d = ws[offs[9]: offs[9] + 4 * n].view(torch.float32).view(bsz, S, 512).cpu()
-        assert torch.equal(y0d, torch.where(keep, y0 * (1.0 / (1.0 - dropout)), torch.zeros_like(y0)))
-        mask = keep.float() / (1.0 - dropout)
-    v = _views(m, bsz, T)
-    zo, yo = _device_forward_values(m, sd, x, bsz, T, v)
-    st = {}
-    ref_loss, ref_grads, ref_stats, ref_logits = _oracle_f64(sd, x, y, zo, yo, dropout_mask=mask, stages=st)
-    # the float32 oracle's own distance from the float64 one at the same forward values (printed, not asserted)
-    _, g32, _, _ = model_ref.loss_and_grads(sd, x, y, dropout_mask=mask, z_override=zo, y_override=yo)
-    own = {k: _rel(g32[k], ref_grads[k])[0] for k in g32 if ref_grads[k].abs().max() > 1e-7}
-    own_norm = max(abs(g32[k].double().norm().item() / ref_grads[k].norm().item() - 1.0) for k in own)
-    worst = max(own, key=own.get)
-    print(f"B={bsz} dropout={dropout}: float32 oracle vs float64 oracle: worst gradient {own[worst]:.1e} * rms ({worst}), worst norm {own_norm:.1e}")
-    lerr = abs(loss.item() - ref_loss.item())
-    gerr_logits = (logits.detach().cpu().double() - ref_logits).abs().max().item()
-    nhwc = lambda a: a.permute(0, 2, 3, 1)
-    stages = {"dy1": st["d_gru_l1"], "dy0": st["d_gru_l0"], "dx0": st["d_gru_in"], "da2": nhwc(st["d_conv2"]), "da1": nhwc(st["d_conv1"])}
-    serr = {k: _rel(v[k] / _loss_scale(bsz), r)[0] for k, r in stages.items()}
-    gerr = _grad_errors(m, ref_grads)
-    nerr = {n: abs(p.grad.double().norm().item() - ref_grads[n].norm().item()) / (ref_grads[n].norm().item() + 1e-30)
-            for n, p in m.named_parameters() if ref_grads[n].abs().max() > 1e-7}
-    print(f"B={bsz}: loss err {lerr:.1e}, logits err {gerr_logits:.1e}, worst gradient {max(gerr.values()):.1e} * rms "
-          f"({max(gerr, key=gerr.get)}), worst norm {max(nerr.values()):.1e}, stage gradients / 2^{int(_loss_scale(bsz)).bit_length() - 1}:",
-          {k: f"{e:.1e}" for k, e in serr.items()})
-    assert lerr < 2e-5
-    assert gerr_logits < 5e-5
-    for k, e in serr.items():
-        assert e < 2e-3, (k, e)
-    assert len(gerr) == 29
-    for k, e in gerr.items():
-        assert e < 2e-3, (k, e)
-    for name, p in m.named_parameters():
-        rn = ref_grads[name].double().norm().item()
-        assert abs(p.grad.double().norm().item() - rn) <= 1e-3 * rn + 1e-7, name
-    for i in (1, 2, 3):
-        bn = getattr(m, f"bn{i}")
-        assert torch.allclose(bn.running_mean.cpu().double(), ref_stats[f"bn{i}.running_mean"], rtol=1e-4, atol=1e-6)
-        assert torch.allclose(bn.running_var.cpu().double(), ref_stats[f"bn{i}.running_var"], rtol=1e-4, atol=1e-6)
-    if want_dx:
-        _, _, ref_dx = input_grad_ref.reference(sd, x, zo, yo, labels=y, dropout_mask=mask)
-        r = input_grad_ref.ratio(xd.grad, ref_dx)
-        print(f"B={bsz}: max|dfeats - ref| / rms(ref) = {r:.2e}")
-        assert xd.grad.shape == xd.shape
-        assert r <= input_grad_ref.GRAD_BOUND
-    ops.check_status()
-
-
 @pytest.mark.parametrize("bsz", [257, 512])
 def test_training_step_vs_oracle_up_to_full_chip(sd, bsz):
-    _training_case(sd, bsz)
+    _training_case(sd, bsz, T)
 
 
 @pytest.mark.parametrize("check", CHECKS)
@@ -447,17 +378,17 @@ def test_inference_vs_oracle_oversubscribed(sd, sharp_sd, data, bsz, check):
 def test_training_step_vs_oracle_528_with_input_gradient(sd):
     """B = 528 (264 workgroups: the first oversubscription) with ``dfeats`` requested (sir_model_train_bwd_x) and compared with
     the oracle's x.grad at test_input_grad_gpu.py's bound, next to everything the other batches check."""
-    _training_case(sd, 528, want_dx=True)
+    _training_case(sd, 528, T, want_dx=True)
 
 
 def test_training_step_vs_oracle_1041(sd):
-    _training_case(sd, NMAX)
+    _training_case(sd, NMAX, T)
 
 
 def test_training_step_vs_oracle_1041_with_dropout(sd):
     """The method of test_train_gpu.py::test_dropout_on_training_step_vs_oracle: the mask rebuilt on the host, checked bit for
     bit against what the dropout kernel wrote, fed to the oracle."""
-    _training_case(sd, NMAX, dropout=0.5)
+    _training_case(sd, NMAX, T, dropout=0.5)
 
 
 def test_backward_forms_are_bit_identical_at_528(sd):

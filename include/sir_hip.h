@@ -389,6 +389,64 @@ int sir_vad_gather(sir_handle* h, const void* wave, int wave_dtype, int64_t wave
                    const int32_t* total, int seg_cap, float* out, int64_t out_stride, int max_clip_len, int32_t* out_lengths,
                    void* stream);
 
+/* ---- live streams: segment audio that arrives piece by piece -------------------
+ * The same detector with carried state: S independent streams, each fed a few samples per call, the way MicrophoneListener.listen
+ * (scripts/testing.py:63-133) reads its microphone 1024 samples at a time.  All state lives in ONE caller-owned device buffer
+ * (`state`, sir_stream_state_bytes bytes, 256-byte aligned): per stream the counters of the state machine and a ring of
+ * R = ring_chunks chunks of samples, plus the flag bytes of the latest push.  Nothing allocates, nothing synchronises, no atomics on
+ * the numbering path: every output is bit-reproducible, and the table a stream produces does not depend on how its samples were
+ * cut into pushes.  With c = vad.chunk_size, P = vad.prior_chunks, n_stop = vad.silence_chunks, M = max_utt_chunks:
+ *   state per stream: n samples received and j chunks judged since its last reset, recording, silence, first.  Sample positions
+ *     in the table count from the stream's last reset (int64).  Chunk k lives at ring offset (k mod R) * c, always contiguous.
+ *   sir_stream_reset: zeroes the state of the streams with mask[s] != 0 (mask == NULL: all).  Must run once before the first push.
+ *   sir_stream_push : appends m_s = clamp(in_lengths[s], 0, min(in_width, max_in)) samples of row s of `in` ([S][in_stride],
+ *     wave_dtype) to stream s, then judges, in order, every complete chunk not judged yet.  m_s == 0 (and no close): untouched.
+ *     chunk i: speech = e_i > threshold, e_i exactly sir_vad_segment's energy (same integer sum for i16, same fp32 reduction order
+ *       for f32, however many pushes assembled the chunk).
+ *       1. not recording and speech: recording starts, silence = 0, first = max(0, i - P + 1) (P == 0: first = i).
+ *       2. recording: silence = speech ? 0 : silence + 1; if silence >= n_stop the row {s, first * c, min((i + 1) * c, n), 0} is
+ *          emitted and recording stops; else if i - first + 1 >= M the same row is emitted with flag bit 0 (1, forced) and
+ *          recording stops: the next speech chunk triggers a new utterance, whose `first` may lie inside the previous one as the
+ *          reference's uncleared prior buffer allows.
+ *     close[s] != 0 (close == NULL: none), after the above: a trailing partial chunk is judged on its own samples as the batch
+ *       form does; an utterance still open is emitted ending at n with flag bit 1 (2, flushed) if vad.flush_tail != 0; the
+ *       stream's state returns to zero (the slot can take a new caller); its ring stays readable until the next push.
+ *     energy_out: optional test hook (NULL in production), f32 [S][K], K = ceil(max_in / c) + 1: the energies of the chunks this
+ *       push judged, in order, zero behind them.
+ *     seg_table : int64 [seg_cap][4] = {stream, start sample, end sample, flags}, stream-major then by time, rows [0, total);
+ *       seg_cap < sir_stream_max_rows(cfg) is SIR_EINVAL before anything is launched (the state has not moved: a push never
+ *       loses a row).  total: int32 [1], stays on the device.
+ *   sir_stream_gather: as sir_vad_gather, but position p of stream s is read at ring offset p mod (R * c) and the stream comes
+ *     from column 0 of the row.  It must be queued before the next push on the same state: R >= sir_stream_min_ring_chunks keeps
+ *     every row of the latest push intact until then.  A row with a stream outside [0, S) or a range that is not
+ *     0 <= start <= end <= start + R * c yields a zero row of length 0 and raises the handle's status word (bit 1024): SIR_EINVAL
+ *     at the next sir_check_status; the other rows are unaffected.
+ * SIR_EINVAL: NULL pointers, a bad wave_dtype, a vad part sir_vad_segment would refuse, n_streams outside [1, 65535], max_in
+ * outside [1, 2^24], M <= P or M > 2^20, R below the minimum or above 2^21 (the upper bounds keep every byte count and row count
+ * far from overflow; a sir_stream_max_rows above 2^31 - 1 is refused too), a state that is not 256-byte aligned, in_width outside
+ * [1, max_in] or above in_stride.  sir_stream_state_bytes returns 0 for a config the calls would refuse.  state_bytes too small:
+ * SIR_ENOMEM.  These launches carry no profile ids (sir_profile_kernel_count is unchanged). */
+#define SIR_STREAM_FORCED  1   /* flags column: the utterance reached max_utt_chunks and was ended there */
+#define SIR_STREAM_FLUSHED 2   /* flags column: the utterance was still open when its stream was closed */
+typedef struct sir_stream_config {
+    sir_vad_config vad;      /* chunk_size, threshold, silence_chunks, prior_chunks, flush_tail: same meaning and same checks */
+    int n_streams;           /* S, 1 .. 65535 */
+    int wave_dtype;          /* SIR_WAVE_I16 | SIR_WAVE_F32: dtype of the pushes and of the ring */
+    int max_in;              /* most samples one push may bring per stream, >= 1 */
+    int max_utt_chunks;      /* M > prior_chunks: an utterance that reaches M chunks is ended there (forced) */
+    int ring_chunks;         /* R >= sir_stream_min_ring_chunks(cfg) */
+} sir_stream_config;
+int sir_stream_min_ring_chunks(const sir_stream_config* cfg);   /* M + ceil(max_in / c) + 2; -1 on a bad config */
+int sir_stream_max_rows(const sir_stream_config* cfg);          /* S * (ceil(max_in / c) + 2): the most rows one push can emit; -1 on a bad config */
+size_t sir_stream_state_bytes(const sir_handle* h, const sir_stream_config* cfg);
+int sir_stream_reset(sir_handle* h, void* state, size_t state_bytes, const sir_stream_config* cfg, const uint8_t* mask, void* stream);
+int sir_stream_push(sir_handle* h, void* state, size_t state_bytes, const sir_stream_config* cfg, const void* in, int64_t in_stride,
+                    int in_width, const int32_t* in_lengths, const uint8_t* close, float* energy_out, int64_t* seg_table, int seg_cap,
+                    int32_t* total, void* stream);
+int sir_stream_gather(sir_handle* h, const void* state, size_t state_bytes, const sir_stream_config* cfg, const int64_t* seg_table,
+                      const int32_t* total, int seg_cap, float* out, int64_t out_stride, int max_clip_len, int32_t* out_lengths,
+                      void* stream);
+
 /* The GRU recurrence kernels (forward and backward) exchange hidden-state slices between the workgroups of a
  * cluster through tagged granules in global memory and rely on the cluster being co-resident.  A workgroup that
  * spins past its limit (a partitioned / oversubscribed GPU, a stalled peer) sets a device status word owned by the

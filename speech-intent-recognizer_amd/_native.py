@@ -20,6 +20,7 @@ SIR_ETIMEOUT = -5
 SIR_ENOMEM = -2
 WAVE_F32, WAVE_I16 = 0, 1
 BWD_ALL, BWD_HEAD_GRU, BWD_CNN = 0, 1, 2
+STREAM_FORCED, STREAM_FLUSHED = 1, 2     # flags column of a sir_stream_push table row
 PROFILE_EXTRA_IDS = 1           # SIR_PROFILE_EXTRA_IDS: profile ids behind sir_profile_kernel_count() (include/sir_hip.h)
 
 
@@ -63,6 +64,11 @@ class VadConfig(C.Structure):
                 ("flush_tail", C.c_int)]
 
 
+class StreamConfig(C.Structure):
+    _fields_ = [("vad", VadConfig), ("n_streams", C.c_int), ("wave_dtype", C.c_int), ("max_in", C.c_int), ("max_utt_chunks", C.c_int),
+                ("ring_chunks", C.c_int)]
+
+
 class AdvConfig(C.Structure):
     _fields_ = [("eps", C.c_float), ("alpha", C.c_float), ("keep_zero_columns", C.c_int)]
 
@@ -101,6 +107,14 @@ SIGNATURES = {
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "sir_vad_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                  C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+    "sir_stream_min_ring_chunks": (C.c_int, [C.POINTER(StreamConfig)]),
+    "sir_stream_max_rows": (C.c_int, [C.POINTER(StreamConfig)]),
+    "sir_stream_state_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(StreamConfig)]),
+    "sir_stream_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(StreamConfig), C.c_void_p, C.c_void_p]),
+    "sir_stream_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(StreamConfig), C.c_void_p, C.c_int64, C.c_int, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "sir_stream_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(StreamConfig), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                    C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
     "sir_gather_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
     "sir_mix_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,

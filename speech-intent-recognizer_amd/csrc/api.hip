@@ -375,6 +375,11 @@ static int check_status_impl(sir_handle* h, hipStream_t st, const char* who) {
                       "those rows were left out", who, v);
         return SIR_EINVAL;
     }
+    if (v & 1024u) {
+        sir_set_error("%s: sir_stream_gather was given a table row whose stream or sample range is impossible (status %u): those rows "
+                      "are zero with length 0", who, v);
+        return SIR_EINVAL;
+    }
     if (v & 4u) {
         sir_set_error("%s: sir_gather_features was given an index outside its store (status %u): those rows are zero", who, v);
         return SIR_EINVAL;

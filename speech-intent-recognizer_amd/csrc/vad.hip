@@ -11,68 +11,18 @@
 //   end at j     : last_upto(j) == j - n_stop          (n_stop == 0: every speech chunk ends its own segment)
 // `last` is a prefix maximum, the k-th trigger pairs with the k-th end, so prefix sums of the two flag kinds number the rows.
 // No atomics anywhere on the numbering path: the table order is part of the contract and every output is bit-reproducible.
-#include "sir_internal.h"
+#include "vad_common.h"
 
 #include <math.h>
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / SIR_WAVE;
 constexpr unsigned int kStatusBadSegment = 128u;      // sir_vad_gather: a table row outside the batch (SIR_EINVAL at the next check)
 
-__device__ __forceinline__ int clamp_len(int len, int max_len) { return len < 0 ? 0 : (len > max_len ? max_len : len); }
-
 // ---- 1. chunk energy -------------------------------------------------------------------------------------------------------
-// One wave owns one 32-bit flag word = 32 consecutive chunks of one recording.  A chunk is read by a sub-wave of LPC lanes, 16
-// bytes per lane and step, 64 samples per step (chunk_size is a multiple of 64): i16 -> 8 lanes x 8 samples, 8 chunks per pass;
-// f32 -> 16 lanes x 4 samples, 4 chunks per pass.  Reduction order (fixed):
-//   i16: exact integer sum of |s| (<= 4096 * 32768 = 2^27), e = (float)((double)S / (count * 32768.0))
-//   f32: lane: four accumulators, one per vector component, each a chain over the steps; (a0 + a1) + (a2 + a3); xor butterfly
-//        over the 16 lanes (distance 1, 2, 4, 8: the same bits in every lane, fp add commutes); e = sum / (float)count.
-//        Additions on the longest path: chunk_size / 64 (chain) + 2 + 4 (tree).
+// One wave owns one 32-bit flag word = 32 consecutive chunks of one recording.  The accumulator, the sub-wave read pattern and the
+// reduction order are those of vad_common.h (shared with the live-stream detector, stream.hip).
 // Samples behind the recording's length enter as +0 (no rounding); a vector load is issued only where all its samples exist.
-template <typename T> struct Acc;
-template <> struct Acc<short> {
-    int s = 0;
-    __device__ __forceinline__ void add_vec(const void* p) {
-        const int4 v = *reinterpret_cast<const int4*>(p);
-        const int w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int lo = (int)(short)(w[i] & 0xffff), hi = w[i] >> 16;
-            s += (lo < 0 ? -lo : lo) + (hi < 0 ? -hi : hi);
-        }
-    }
-    __device__ __forceinline__ void add_one(int, short x) { const int v = x; s += v < 0 ? -v : v; }
-    __device__ __forceinline__ float finish(int lpc, int count) {
-#pragma unroll
-        for (int m = 1; m < 8; m <<= 1) s += __shfl_xor(s, m);
-        (void)lpc;
-        return (float)((double)s / ((double)count * 32768.0));
-    }
-};
-template <> struct Acc<float> {
-    float a[4] = {0.f, 0.f, 0.f, 0.f};
-    __device__ __forceinline__ void add_vec(const void* p) {
-        const float4 v = *reinterpret_cast<const float4*>(p);
-        a[0] = __fadd_rn(a[0], fabsf(v.x)); a[1] = __fadd_rn(a[1], fabsf(v.y));
-        a[2] = __fadd_rn(a[2], fabsf(v.z)); a[3] = __fadd_rn(a[3], fabsf(v.w));
-    }
-    __device__ __forceinline__ void add_one(int e, float x) {
-        const float v = fabsf(x);                            // e is a compile-time constant after unrolling
-        if (e == 0) a[0] = __fadd_rn(a[0], v);
-        else if (e == 1) a[1] = __fadd_rn(a[1], v);
-        else if (e == 2) a[2] = __fadd_rn(a[2], v);
-        else a[3] = __fadd_rn(a[3], v);
-    }
-    __device__ __forceinline__ float finish(int, int count) {
-        float s = __fadd_rn(__fadd_rn(a[0], a[1]), __fadd_rn(a[2], a[3]));
-#pragma unroll
-        for (int m = 1; m < 16; m <<= 1) s = __fadd_rn(s, __shfl_xor(s, m));
-        return __fdiv_rn(s, (float)count);
-    }
-};
 
 template <typename T, bool VEC>
 __global__ __launch_bounds__(kThreads) void vad_energy_kernel(const T* __restrict__ wave, long long stride, const int* __restrict__ lengths,
@@ -100,18 +50,7 @@ __global__ __launch_bounds__(kThreads) void vad_energy_kernel(const T* __restric
                 const long long begin = (long long)k * c;
                 const long long rest = (long long)len - begin;
                 count = rest < c ? (int)rest : c;
-                const T* p = row + begin + sl * V;
-                int left = count - sl * V;      // samples of this chunk at or behind this lane's first one
-#pragma unroll 4
-                for (int s = 0; s < steps; ++s, p += 64, left -= 64) {
-                    if (VEC && left >= V) {
-                        acc.add_vec(p);
-                    } else if (left > 0) {
-#pragma unroll
-                        for (int e = 0; e < V; ++e)
-                            if (e < left) acc.add_one(e, p[e]);
-                    }
-                }
+                chunk_accumulate<T, VEC>(acc, row + begin + sl * V, count - sl * V, steps);
             }
             const float e = acc.finish(LPC, count);               // every lane takes part in the butterfly
             const bool live = k < nch;
@@ -129,31 +68,11 @@ __global__ __launch_bounds__(kThreads) void vad_energy_kernel(const T* __restric
 }
 
 // ---- 2. segmentation -------------------------------------------------------------------------------------------------------
-// inclusive scans over the 256 threads of the block: wave scan by shuffles, the four wave totals through LDS
-__device__ __forceinline__ int wave_incl_add(int v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(v, d); if (lane >= d) v += o; }
-    return v;
-}
 __device__ __forceinline__ int wave_incl_max(int v) {
     const int lane = threadIdx.x & 63;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(v, d); if (lane >= d) v = o > v ? o : v; }
     return v;
-}
-// exclusive prefix sum of v over the block; *total = the block's sum.  `sh` holds kWaves ints and is free again on return.
-__device__ __forceinline__ int block_excl_add(int v, int* sh, int* total) {
-    const int incl = wave_incl_add(v);
-    const int wv = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 63) sh[wv] = incl;
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < kWaves; ++i) { const int t = sh[i]; if (i < wv) off += t; tot += t; }
-    __syncthreads();
-    *total = tot;
-    return off + incl - v;
 }
 // exclusive prefix maximum (identity -1); *total = the block's maximum
 __device__ __forceinline__ int block_excl_max(int v, int* sh, int* total) {
@@ -273,10 +192,6 @@ __global__ __launch_bounds__(kThreads) void vad_base_kernel(const int* __restric
 
 // ---- 3. gather -------------------------------------------------------------------------------------------------------------
 // grid (segment, column block); a thread moves 16 source bytes (8 i16 / 4 f32 samples) and zero-fills behind the clip
-template <typename T> __device__ __forceinline__ float deq(T v);
-template <> __device__ __forceinline__ float deq<short>(short v) { return (float)v * (1.0f / 32768.0f); }
-template <> __device__ __forceinline__ float deq<float>(float v) { return v; }
-
 template <typename T, bool VEC>
 __global__ __launch_bounds__(kThreads) void vad_gather_kernel(const T* __restrict__ wave, long long stride, int n_rec,
                                                               const int* __restrict__ table, const int* __restrict__ total, int seg_cap,
@@ -338,8 +253,6 @@ WsLayout ws_layout(int n_rec, int max_len, int c) {
     w.total = sir_align_up(w.base_off + (size_t)n_rec * sizeof(int), 256);
     return w;
 }
-
-bool chunk_ok(int c) { return c >= 64 && c <= 4096 && c % 64 == 0; }
 
 template <typename T>
 int segment_impl(sir_handle* h, const T* wave, int64_t wave_stride, const int32_t* lengths, int n_rec, int max_len, const sir_vad_config* cfg,

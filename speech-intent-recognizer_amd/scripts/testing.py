@@ -5,7 +5,8 @@ sample_rate)`` -> ``{"predicted_label", "confidence", "top_predictions"}`` (:262
 does live -- ``MicrophoneListener.listen`` (:49-143) cuts a microphone stream into utterances and calls ``predict`` on each --
 ``recognize_recordings`` does for many recordings at once on MI355X: ``sir_amd.segmenter.Segmenter`` finds the utterances
 (``sir_vad_segment``), cuts them out (``sir_vad_gather``), ``HipFeaturizer`` turns the clip batch into features and one forward
-per group of recordings scores them.
+per group of recordings scores them.  ``open_streams`` is the incremental form of the same: a ``StreamSession`` takes the audio of
+many live sources piece by piece (``sir_amd.streaming.StreamSegmenter``) and scores every utterance as it ends.
 
 Features are THIS project's training features (``sir_features_fwd``: torchaudio-style mel power, dB, whole-utterance z-norm),
 not the librosa ``power_to_db(ref=np.max)`` features with the fixed -30.1 / 12.7 normalisation of testing.py:189-209 -- SURVEY.md
@@ -126,7 +127,6 @@ class IntentRecognizer:
         (``lengths=``), a clip with fewer than 8 frames at 8.  ``logits_on_device=True`` leaves the logits where they were
         computed (for ``classify_results.results_from_logits``)."""
         seg = self.segmenter
-        hop = self.frontend.hop_length
         if pad_to == TRAINED_LENGTH:
             pad_to = self.mel_spec_length
         table, _, total = seg.segment(wave, lengths)
@@ -136,8 +136,18 @@ class IntentRecognizer:
         if n == 0:
             return host_table, torch.zeros((0, num_classes), dtype=torch.float32)
         longest = int((host_table[:, 2] - host_table[:, 1]).max())
-        limit = self.frontend.max_samples(pad_to) if pad_to is not None else int(MAX_CLIP_S * seg.sample_rate)
+        limit = self._clip_limit(pad_to)
         clips, clip_lens = seg.gather(wave, table, total, max(1, min(longest, limit)))
+        return host_table, self._score_clips(clips, clip_lens, pad_to, logits_on_device)
+
+    def _clip_limit(self, pad_to):
+        """most samples of an utterance that are scored (``pad_to`` already resolved)"""
+        return self.frontend.max_samples(pad_to) if pad_to is not None else int(MAX_CLIP_S * self.segmenter.sample_rate)
+
+    def _score_clips(self, clips, clip_lens, pad_to, logits_on_device=False):
+        """The scoring half of ``score_segments``, shared with ``StreamSession``: zero-tailed clips [n, L] and their lengths on the
+        GPU -> logits [n, C]; ``pad_to`` is a frame count or None (ragged), already resolved."""
+        hop = self.frontend.hop_length
         fz = self.frontend.featurizer()
         frames = (clip_lens // hop + 1).clamp(min=MIN_FRAMES)
         t_pad = pad_to if pad_to is not None else int(frames.max().item())
@@ -147,7 +157,7 @@ class IntentRecognizer:
         if not logits_on_device:
             logits = logits.cpu()
         ops.check_status()
-        return host_table, logits
+        return logits
 
     def recognize_recordings(self, waves_or_paths, pad_to=TRAINED_LENGTH, on_device=False, temperature=None, min_confidence=None):
         """waves_or_paths: recordings as 1-D float32 / int16 arrays or tensors at the segmenter's sample rate, or paths of WAVE
@@ -181,6 +191,77 @@ class IntentRecognizer:
             except Exception as e:
                 logger.error(f"Error recognising recordings {g}..{g + len(group) - 1}: {str(e)}")
         return results
+
+    # ---- live streams ----------------------------------------------------------------------------------------------------
+    def open_streams(self, n_streams, max_push=1024, max_utterance=10.0, dtype=torch.float32, pad_to=TRAINED_LENGTH, on_device=False,
+                     temperature=None, min_confidence=None):
+        """What ``MicrophoneListener.listen`` + ``predict`` do for one microphone (testing.py:49-143), for ``n_streams`` sources
+        that deliver at most ``max_push`` samples of ``dtype`` per ``feed``: -> a ``StreamSession``.  The detector takes the
+        listener values of this recogniser's ``segmenter``; an utterance longer than ``max_utterance`` seconds is ended there.
+        ``pad_to`` / ``on_device`` / ``temperature`` / ``min_confidence`` as in ``recognize_recordings``."""
+        return StreamSession(self, n_streams, max_push, max_utterance, dtype, pad_to, on_device, temperature, min_confidence)
+
+
+class StreamSession:
+    """Utterances of many live streams, scored as they end (``IntentRecognizer.open_streams``)."""
+
+    def __init__(self, recognizer, n_streams, max_push, max_utterance, dtype, pad_to, on_device, temperature, min_confidence):
+        from sir_amd.scripts import classify_results
+        from sir_amd.streaming import StreamSegmenter
+        classify_results.check_route(on_device, temperature, min_confidence)
+        seg = recognizer.segmenter
+        self.recognizer = recognizer
+        self.segmenter = StreamSegmenter(n_streams, max_push, max_utterance, dtype, recognizer.device, sample_rate=seg.sample_rate,
+                                         chunk_size=seg.chunk_size, threshold=seg.threshold, silence_limit=seg.silence_limit,
+                                         prior_recording=seg.prior_recording, flush_tail=seg.flush_tail)
+        self.pad_to = recognizer.mel_spec_length if pad_to == TRAINED_LENGTH else pad_to
+        self.on_device, self.temperature, self.min_confidence = on_device, temperature, min_confidence
+        self.last_logits = None
+
+    def feed(self, chunks, lengths=None, close=()):
+        """chunks: ``{stream: 1-D array of new samples}`` (streams not named get nothing), or a padded [n_streams, <= max_push]
+        tensor with ``lengths``.  ``close``: the streams that end with this call.  -> the utterances that completed, stream-major
+        then by time, as the dictionaries of ``recognize_recordings`` plus ``"stream"`` and ``"forced"`` (the utterance reached
+        ``max_utterance`` and was cut there); ``start`` / ``end`` count from the stream's last close.  ``last_logits`` holds the
+        logits of the utterances the latest call returned, row for row (None if there were none)."""
+        from sir_amd.scripts import classify_results
+        seg, reco = self.segmenter, self.recognizer
+        if isinstance(chunks, dict):
+            width = max([1] + [int(np.asarray(x).size) for x in chunks.values()])
+            host = torch.zeros((seg.n_streams, width), dtype=seg.dtype)
+            host_len = torch.zeros((seg.n_streams,), dtype=torch.int32)
+            for s, x in chunks.items():
+                if not 0 <= int(s) < seg.n_streams:
+                    raise ValueError(f"stream {s!r} outside [0, {seg.n_streams})")
+                x = torch.as_tensor(np.ascontiguousarray(x)).reshape(-1)
+                if x.dtype != seg.dtype:
+                    x = x.float() / 32768.0 if x.dtype == torch.int16 else x.to(seg.dtype)
+                host[int(s), :x.numel()] = x
+                host_len[int(s)] = x.numel()
+            chunks, lengths = host.to(reco.device), host_len.to(reco.device)
+        table, total = seg.push_table(chunks, lengths, close=close if torch.is_tensor(close) else list(close))
+        host_table = table.cpu()
+        self.last_logits = None
+        if host_table.shape[0] == 0:
+            return []
+        longest = int((host_table[:, 2] - host_table[:, 1]).max())
+        clips, clip_lens = seg.gather(table, total, max(1, min(longest, reco._clip_limit(self.pad_to))))
+        logits = self.last_logits = reco._score_clips(clips, clip_lens, self.pad_to, self.on_device)
+        batch_res = None
+        if self.on_device:
+            batch_res = classify_results.results_from_logits(logits, reco.inv_label_map,
+                                                             inv_temperature=classify_results.inv_temperature_of(self.temperature),
+                                                             min_confidence=self.min_confidence)
+        sr = float(seg.sample_rate)
+        found = []
+        for row, (s, a, b, flag) in enumerate(host_table.tolist()):
+            res = batch_res[row] if batch_res is not None else test_model._result(logits[row:row + 1], reco.inv_label_map)
+            found.append({"stream": s, "forced": bool(flag & 1), "start": a / sr, "end": b / sr, **res})
+        return found
+
+    def close(self, streams):
+        """End ``streams`` without new samples: their open utterances are flushed and scored, the slots start again at 0."""
+        return self.feed({}, close=streams)
 
 
 def main():

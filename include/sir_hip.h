@@ -314,7 +314,40 @@ int sir_model_set_weights_version(sir_handle* h, uint64_t version);
  * 65535, is SIR_EINVAL; sir_model_workspace_bytes returns 0).  The GRU runs S = t_frames / 8 steps and the attention kernels hold one
  * score per step in LDS arrays of 256, which is what limits the range: 2055 frames are 256 steps -- 20 s at a 10 ms hop, 65 s at the default
  * 32 ms one.  The step field of a recurrence exchange tag (9 bits, step + 1) ends there as well.  Tested against the oracle up to 2055 frames
- * (tests/test_long_sequence_gpu.py), at batches up to 17 in inference and up to 8 in training. */
+ * (tests/test_long_sequence_gpu.py), at batches up to 17 in inference and up to 8 in training.
+ *
+ * Operand range and non-finite values (sir_model_infer, sir_model_infer_ragged, sir_model_train_fwd*, sir_model_train_bwd*;
+ * tests/test_operand_range_gpu.py).  The contractions split every fp32 operand into two fp16 planes, and the convolution kernels
+ * apply ReLU and max-pool as fmaxf; neither carries a NaN.  What the callers get instead:
+ *   features   inference: a NaN or an infinity anywhere in utterance b (ragged: in its frames[b] columns) makes ALL of row b of
+ *              logits NaN (argmax 0); every other row is bit-identical to what it is without that value.  No status bit.
+ *              training forward with live bn1 statistics: a non-finite feature anywhere makes EVERY row of logits NaN (batch
+ *              statistics carry it into all of them), hence a NaN loss, NaN dlogits and NaN fc gradients -- isfinite(loss) and the
+ *              total norm of sir_grad_norm both see it.  No status bit.  The test is on the fp32 sum of the squared features, so a
+ *              finite feature beyond ~1.8e19 in magnitude (its square overflows fp32) counts as non-finite.
+ *              training forward with bn_frozen[0] (a frozen-statistics fine-tune, sir_amd.explain): the features are NOT looked at;
+ *              a non-finite feature gives finite, meaningless logits and loss there.
+ *   conv2 / conv3 weights   a transformed weight U = G g G^T with |U| >= 32, or not finite: status bit 3 (SIR_EINVAL at the next
+ *              sir_check_status); the outputs are computed from the clamped value.  Below 32 the planes are exact.
+ *   GRU weight_ih / weight_hh   an element beyond +-65504 or not finite: status bit 11 (SIR_EINVAL); outputs from the clamped value.
+ *   attention, fc   used in fp32 behind the last ReLU: a non-finite value comes out where torch has it (a NaN in fc.weight[j][.]
+ *              makes exactly logit column j NaN).
+ *   conv1 weights, BatchNorm weight / bias / running statistics   sit in front of an fmaxf ReLU / max-pool, which drops a NaN (the
+ *              logits come out finite): a non-finite value raises status bit 13 (SIR_EINVAL) in the kernels that fold them --
+ *              inference and frozen blocks: weight, bias and both running statistics; a block on batch statistics: weight and
+ *              bias (its running statistics are written, not used); conv1's weights with bn1 either way.
+ *   GRU biases   not tested, unspecified.
+ *   activations   the training forward raises status bit 12 (SIR_EINVAL) when the conv2 block writes an output >= 256 or the conv3
+ *              block one >= 512: beyond these the backward's single-accumulator WEIGHT-gradient contractions (the conv3 weight
+ *              gradient, the GRU layer-0 weight-gradient GEMM) clamp or saturate that operand.  Up to there gradients are tested
+ *              against float64.  The forward does not know what the backward will be asked for, so the bit is raised whatever
+ *              follows: logits, loss and the input gradient (sir_model_train_bwd_x) do not read these operands and stay valid.
+ *              The conv1 block output feeds the conv2 weight gradient under the same limit of 256 and is NOT checked.
+ *   dlogits    sir_model_train_bwd* accepts any finite magnitude: one small kernel picks the backward's internal power-of-two scale
+ *              from max |dlogits| (workspace slot 39), so gradients are as accurate at (softmax - onehot) ~ 2^-24 as at ~ 1, and a
+ *              scaled loss (dlogits x 2^16) does not saturate.  A NaN / infinite dlogits makes the fc gradients (fp32, straight from
+ *              dlogits) non-finite, and with them the total norm of sir_grad_norm; the other gradients pass clamping splits and
+ *              are unspecified. */
 int sir_model_infer(sir_handle* h, const sir_model_weights* w, const float* feats, int batch,
                     int t_frames, float* logits, int64_t* argmax, void* workspace,
                     size_t workspace_bytes, void* stream);
@@ -456,7 +489,11 @@ int sir_stream_gather(sir_handle* h, const void* state, size_t state_bytes, cons
  * .cpu()) or per epoch (scripts/train.py:116's loss.item()); sir_profile_collect performs the same check.
  * The same word carries sir_ce_loss's / sir_ce_loss_soft's "label outside [0, num_classes)" flag (nn.CrossEntropyLoss raises on such a
  * target, train.py:242/:105; the kernel makes that step's loss NaN): reported here as SIR_EINVAL.  sir_eval_accumulate and
- * sir_temperature_fit raise it (bit 512) for such a label too. */
+ * sir_temperature_fit raise it (bit 512) for such a label too.
+ * The model's operand-range reports (see sir_model_infer) share the word, all SIR_EINVAL: bit 3 (value 8) a transformed conv2 / conv3
+ * weight with |U| >= 32 or not finite; bit 11 (2048) a GRU weight matrix element beyond +-65504 or not finite; bit 12 (4096) a
+ * training forward whose conv2 / conv3 block output reached 256 / 512 (the weight gradients of that workspace are invalid); bit 13
+ * (8192) a conv1 weight or a BatchNorm weight / bias / running statistic that is not finite. */
 int sir_check_status(sir_handle* h, void* stream);
 
 /* ---- cross-batch pipelining (owned by the library) ------------------------------------------------
@@ -506,6 +543,7 @@ typedef struct sir_model_grads {
  * off); activations needed by the backward pass stay in `workspace`
  * (sir_model_workspace_bytes(h, batch, t_frames, 1) bytes), which must be handed unchanged to
  * sir_model_train_bwd.
+ * Operand limits, non-finite features and weights: the paragraph at sir_model_infer (status bits 3, 11, 12, 13).
  * Batch regimes as at sir_model_infer (half chip at 256, full chip at 512, oversubscribed beyond); the step is tested against the float64
  * oracle at batches 257, 512, 528 and 1041 of 24 frames.  Untested: token counts batch * (t_frames / 8) above 6400, and batches above 1100. */
 int sir_model_train_fwd(sir_handle* h, const sir_model_weights* w, float* const bn_running_mean[3],
@@ -535,7 +573,8 @@ int sir_ce_loss_soft(sir_handle* h, const float* logits, const int64_t* labels_a
                      float label_smoothing, int batch, int num_classes, float* loss, float* dlogits, float grad_scale,
                      void* stream);
 
-/* loss.backward() (train.py:106): all 29 parameter gradients from dlogits and the saved workspace. */
+/* loss.backward() (train.py:106): all 29 parameter gradients from dlogits and the saved workspace.  dlogits may have any finite
+ * magnitude (the internal loss scale follows max |dlogits|: slot 39 below, and the paragraph at sir_model_infer). */
 int sir_model_train_bwd(sir_handle* h, const sir_model_weights* w, const float* feats, const float* dlogits,
                         int batch, int t_frames, float dropout_p, uint64_t dropout_seed,
                         const sir_model_grads* grads, void* workspace, size_t workspace_bytes, void* stream);
@@ -590,7 +629,12 @@ int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* w, const fl
  *   35  c1m    conv1 input moments (54 doubles)
  *   36  dgi1   gate gradients of layer 1, input side
  *   37  dgh1   gate gradients of layer 1, hidden side
- *   38  slab2  GRU weight-gradient slabs of the side stream */
+ *   38  slab2  GRU weight-gradient slabs of the side stream
+ *   39  bsc    the backward's loss scale as pairs {scale, 1 / scale} of powers of two, [1 + B][2]: pair 0 is the call's (from the
+ *              maximum of |dlogits|; the static 2^8 x batch, rounded up to a power of two, while that maximum times the static
+ *              scale lies in [2^5, 2^10), else the power of two that puts it into [2^7, 2^8)); pair 1 + b is utterance b's own,
+ *              written and used only by a sir_model_train_bwd_x call with all three bn_frozen set and no parameter gradient wanted
+ *              (rows are then independent, and each is scaled by its own row of dlogits).  Slots 21..29 carry the scale. */
 int sir_model_train_workspace_offsets(const sir_handle* h, int batch, int t_frames, size_t* offsets, int n);
 
 /* ---- fine-tuning step -------------------------------------------------------------------------

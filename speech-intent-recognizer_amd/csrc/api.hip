@@ -347,6 +347,22 @@ static int check_status_impl(sir_handle* h, hipStream_t st, const char* who) {
                       "computed from the clamped value are invalid", who, v);
         return SIR_EINVAL;
     }
+    if (v & 2048u) {
+        sir_set_error("%s: a GRU weight matrix (weight_ih / weight_hh) holds a value that is not finite or lies outside +-65504 (status %u): "
+                      "the f16x3 planes were prepared from the clamped value and the outputs computed from them are invalid", who, v);
+        return SIR_EINVAL;
+    }
+    if (v & 4096u) {
+        sir_set_error("%s: a training forward wrote an activation beyond the range the backward's weight-gradient contractions take "
+                      "exactly (conv2 block output >= 256 or conv3 block output >= 512, status %u): the conv3 / GRU layer-0 WEIGHT gradients "
+                      "computed from that workspace are invalid (logits, the loss and the input gradient are not affected)", who, v);
+        return SIR_EINVAL;
+    }
+    if (v & 8192u) {
+        sir_set_error("%s: a conv1 weight or a BatchNorm weight / bias / running statistic is not finite (status %u): ReLU and max-pool "
+                      "drop the NaN, so the logits computed from it are finite and meaningless", who, v);
+        return SIR_EINVAL;
+    }
     if (v & 16u) {
         sir_set_error("%s: sir_wave_perturb was given a pitch outside [-200, 200] cents or a tempo outside [0.5, 2] (status %u): "
                       "those rows are zero with length 0", who, v);

@@ -2,8 +2,11 @@
 //     hi = fp16(x)  (round to nearest, 11 significant bits)         lo = fp16((x - hi) * 2^11)
 // x - hi is exact in fp32; the residual is scaled by 2^11 so that it sits in fp16's normal range wherever hi does.
 // hi + lo * 2^-11 carries 22-23 significant bits of x for 2^-14 <= |x| <= 65504; smaller values keep an ABSOLUTE error of
-// 2^-36.  Values beyond fp16's range are clamped to +-65504 first (BatchNorm / ReLU outputs, GRU states and weights are
-// nowhere near; an overflow to infinity would turn 0 * inf products into NaNs).
+// 2^-36 (the backward keeps its operands above that by choosing its loss scale from the gradients it is handed: train_workspace.h).
+// Values beyond fp16's range are clamped to +-65504 first (an overflow to infinity would turn 0 * inf products into NaNs), and
+// the clamp (fminf / fmaxf) turns a NaN into a finite number too: nothing non-finite survives a split.  Where that could hide a
+// fault from the caller it is reported instead -- weights by the preparation kernels (split_flag_range below, split_w_f16x3),
+// features by the scans that read them anyway (include/sir_hip.h at sir_model_infer has the whole contract).
 #pragma once
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -44,9 +47,19 @@ __device__ __forceinline__ void split2h_quad(const float4& v, uint2& h, uint2& l
     split2h_pair(v.z, v.w, h.y, l.y);
 }
 
-// in [rows][K] fp32 (row stride ld_in) -> planes [2][rows][K] fp16; one thread = 8 consecutive k
+// Weight preparation only: a GRU matrix element the split would clamp (|w| > 65504) or that is not finite -- the clamp turns a NaN into
+// a finite number -- raises bit 11 of the handle's status word (SIR_EINVAL at the next sir_check_status).  status == NULL: no check.
+constexpr unsigned int SIR_STATUS_GRU_WEIGHT = 2048u;
+__device__ __forceinline__ void split_flag_range(const float4& a, const float4& b, unsigned int* status) {
+    if (!status) return;
+    const bool ok = fabsf(a.x) <= 65504.0f && fabsf(a.y) <= 65504.0f && fabsf(a.z) <= 65504.0f && fabsf(a.w) <= 65504.0f &&
+                    fabsf(b.x) <= 65504.0f && fabsf(b.y) <= 65504.0f && fabsf(b.z) <= 65504.0f && fabsf(b.w) <= 65504.0f;
+    if (!ok) __hip_atomic_fetch_or(status, SIR_STATUS_GRU_WEIGHT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// in [rows][K] fp32 (row stride ld_in) -> planes [2][rows][K] fp16; one thread = 8 consecutive k.  status: split_flag_range (weights)
 __device__ __forceinline__ void split2h_rows(const float* __restrict__ in, int ld_in, unsigned short* __restrict__ out, size_t rows, int K,
-                                             size_t gidx, size_t nthreads) {
+                                             size_t gidx, size_t nthreads, unsigned int* status = nullptr) {
     const int k8n = K / 8;
     const size_t total = rows * k8n, plane = rows * (size_t)K;
     for (size_t idx = gidx; idx < total; idx += nthreads) {
@@ -55,6 +68,7 @@ __device__ __forceinline__ void split2h_rows(const float* __restrict__ in, int l
         const float4 v0 = *reinterpret_cast<const float4*>(in + row * ld_in + k8 * 8);
         const float4 v1 = *reinterpret_cast<const float4*>(in + row * ld_in + k8 * 8 + 4);
         uint2 h0, l0, h1, l1;
+        split_flag_range(v0, v1, status);
         split2h_quad(v0, h0, l0);
         split2h_quad(v1, h1, l1);
         const size_t o = row * K + (size_t)k8 * 8;
@@ -66,5 +80,10 @@ __device__ __forceinline__ void split2h_rows(const float* __restrict__ in, int l
 static __global__ __launch_bounds__(256) void split2h_kernel(const float* __restrict__ in, int ld_in, unsigned short* __restrict__ out,
                                                               size_t rows, int K) {
     split2h_rows(in, ld_in, out, rows, K, (size_t)blockIdx.x * 256 + threadIdx.x, (size_t)gridDim.x * 256);
+}
+// the same for a weight matrix (inference prepares W_ih with it): out-of-range / non-finite elements are reported
+static __global__ __launch_bounds__(256) void split2h_weights_kernel(const float* __restrict__ in, int ld_in, unsigned short* __restrict__ out,
+                                                                      size_t rows, int K, unsigned int* status) {
+    split2h_rows(in, ld_in, out, rows, K, (size_t)blockIdx.x * 256 + threadIdx.x, (size_t)gridDim.x * 256, status);
 }
 #endif

@@ -12,7 +12,8 @@
 // (Bh, Bl'); the consumers form Bh 2^11 in registers (four v_pk_mul_f16 per fragment), so that the three products
 // Al' Bh + Ah Bl' + Ah (Bh 2^11) = 2^11 A B go into ONE accumulator (the consumers' 64 accumulator registers are what the
 // 128-register budget of a 1024-thread workgroup allows) and the epilogue scales by 2^-11 / TN2_BS = 2^-7.  Bh 2^11 is exact while
-// |B| TN2_BS < 32, i.e. |B| < 512 (larger values are clamped: activations behind BatchNorm and weights are nowhere near).
+// |B| TN2_BS < 32, i.e. |B| < 512 (larger values are clamped, or saturate under MODE.FP16_OVFL: the training forward raises status
+// bit 12 when it writes a conv3 block output that large, bn_relu_pool_kernel; GRU outputs lie in (-1, 1)).
 // What bounds it: with the matrix pipe this busy the step runs at the board's power limit, so energy per
 // stage, not issue slots, is what counts.  The knock-out numbers of the structures tried on the way: DESIGN.md section 4.
 #pragma once

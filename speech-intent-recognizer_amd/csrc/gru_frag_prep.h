@@ -10,13 +10,15 @@ constexpr int BQ_FRAG_THREADS = 4 * 4 * 4 * 6 * 64;          // backward: [quart
 constexpr size_t GRU_FRAG_BYTES = (size_t)768 * 256 * 4;     // either form: 2 planes x 2 bytes per weight
 
 // forward (gru_quad_kernel.h): [quarter][wave][gate][k-step][plane (hi, lo')][lane] uint4; A row = unit, 8 consecutive k per lane
-__device__ __forceinline__ void prep_whh_quad_elem(const float* __restrict__ whh, uint4* __restrict__ frag, int idx) {
+__device__ __forceinline__ void prep_whh_quad_elem(const float* __restrict__ whh, uint4* __restrict__ frag, int idx, unsigned int* status) {
     if (idx >= GQ_FRAG_THREADS) return;                      // ((((q*4 + wv)*3 + g)*8 + s)*64 + lane)
     const int lane = idx & 63, s = (idx >> 6) & 7, g = (idx >> 9) % 3, qw = idx / (64 * 8 * 3), wv = qw & 3, q = qw >> 2;
     const float* wrow = whh + (size_t)(g * 256 + q * 64 + wv * 16 + (lane & 15)) * 256 + s * 32 + (lane >> 4) * 8;
     uint2 h0, l0, h1, l1;
-    split2h_quad(*reinterpret_cast<const float4*>(wrow), h0, l0);
-    split2h_quad(*reinterpret_cast<const float4*>(wrow + 4), h1, l1);
+    const float4 w0 = *reinterpret_cast<const float4*>(wrow), w1 = *reinterpret_cast<const float4*>(wrow + 4);
+    split_flag_range(w0, w1, status);                        // (every element of W_hh passes here once: the backward form need not look again)
+    split2h_quad(w0, h0, l0);
+    split2h_quad(w1, h1, l1);
     uint4* o = frag + ((size_t)(((qw * 3 + g) * 8 + s) * 2) * 64 + lane);
     o[0] = make_uint4(h0.x, h0.y, h1.x, h1.y);
     o[64] = make_uint4(l0.x, l0.y, l1.x, l1.y);

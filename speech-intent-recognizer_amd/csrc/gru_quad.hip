@@ -36,8 +36,8 @@ int sir_launch_gru_quad(sir_handle* h, hipStream_t st, bool save, const float* g
 }
 
 // inference-side preparation of one direction's resident fragments (GRU_FRAG_BYTES)
-void sir_prep_whh_quad(hipStream_t st, const float* whh, void* frag) {
-    hipLaunchKernelGGL(prep_whh_quad_kernel, dim3(GQ_FRAG_THREADS / 256), dim3(256), 0, st, whh, (uint4*)frag);
+void sir_prep_whh_quad(sir_handle* h, hipStream_t st, const float* whh, void* frag) {
+    hipLaunchKernelGGL(prep_whh_quad_kernel, dim3(GQ_FRAG_THREADS / 256), dim3(256), 0, st, whh, (uint4*)frag, h->status);
 }
 
 // BPTT on the matrix cores, clusters of four workgroups x 16 utterances (gru_bwd_quad_kernel.h)

@@ -87,8 +87,8 @@ __device__ __forceinline__ float gq_tanh(float x) {
 // W_hh of one direction as the kernel's resident MFMA fragments (gru_frag_prep.h: [quarter][wave][gate][k-step][plane][lane] uint4);
 // inference prepares this once per weights version, training once per step inside train_prep_kernel: the kernel prologue is then
 // 48 coalesced 16-byte loads per lane instead of 48 row-strided fp32 loads and the split
-static __global__ __launch_bounds__(256) void prep_whh_quad_kernel(const float* __restrict__ whh, uint4* __restrict__ frag) {
-    prep_whh_quad_elem(whh, frag, blockIdx.x * 256 + threadIdx.x);
+static __global__ __launch_bounds__(256) void prep_whh_quad_kernel(const float* __restrict__ whh, uint4* __restrict__ frag, unsigned int* status) {
+    prep_whh_quad_elem(whh, frag, blockIdx.x * 256 + threadIdx.x, status);
 }
 
 // xbuf   [clusters][2 parity][4 quarters][16 utterances][64 units] 8-byte granules; the 16-bit tag is {7-bit launch epoch of

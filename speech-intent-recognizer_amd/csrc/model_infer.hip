@@ -62,7 +62,8 @@ bool make_dims(int batch, int t_frames, Dims* d) {
 }
 
 // int offsets inside WS_PAD
-struct PadTabs { size_t e0, d1, d3, tab2, tab3, rows, count; };     // (count: the tables' ints; behind them the projection's record, 2 ints)
+struct PadTabs { size_t e0, d1, d3, tab2, tab3, rows, count; };     // (count: the tables' ints; behind them the projection's record, 2 ints,
+                                                                     // and behind that one non-finite flag per utterance, B ints)
 PadTabs pad_tabs(const Dims& d) {
     PadTabs t;
     const size_t n = (size_t)d.B + 1;
@@ -84,7 +85,7 @@ void ws_sizes(const Dims& d, size_t* bytes) {
     bytes[WS_Y0] = (size_t)d.B * d.S * 512 * 4;
     bytes[WS_Y1] = (size_t)d.B * d.S * 512 * 4;
     bytes[WS_CTX] = (size_t)d.B * 512 * 4;
-    bytes[WS_PAD] = (pad_tabs(d).count + 2) * 4;                // + {row count read, tile chosen} of the latest row-list projection
+    bytes[WS_PAD] = (pad_tabs(d).count + 2 + (size_t)d.B) * 4;  // + {row count read, tile chosen} of the latest row-list projection + the flags
     bytes[WS_XZ] = (size_t)64 * d.T * 4;
     bytes[WS_BN] = (size_t)2 * 224 * 4;
     bytes[WS_WHT] = 4 * GRU_FRAG_BYTES;                         // W_hh as the resident f16x2 MFMA fragments of the recurrence kernel
@@ -106,22 +107,35 @@ size_t ws_layout(const Dims& d, size_t* off) {
 }
 
 // E0[b] = 1 + the last frame column of utterance b with any bit set in any of the 64 mel rows, 0 if none (bits, not values:
-// -0.0, NaN and denormals are data)
-static __global__ __launch_bounds__(256) void pad_extent_kernel(const float* __restrict__ x, int T, int* __restrict__ e0) {
+// -0.0, NaN and denormals are data).  nonfinite[b] = 1 if any of its features is a NaN or an infinity (exponent bits all set), else 0:
+// the head kernel turns such a row into NaNs, which the ReLU / max-pool of the conv kernels (fmaxf) would not carry there.
+// frames != NULL (ragged): only the columns below frames[b] are looked at (none if that length is invalid) and e0 is not written.
+static __global__ __launch_bounds__(256) void pad_extent_kernel(const float* __restrict__ x, int T, int* __restrict__ e0,
+                                                                 const int* __restrict__ frames, int* __restrict__ nonfinite) {
     const unsigned* xb = reinterpret_cast<const unsigned*>(x) + (size_t)blockIdx.x * 64 * T;
-    int last = -1;
-    for (int c = threadIdx.x; c < T; c += 256) {
+    int last = -1, cols = T;
+    if (frames) { const int f = frames[blockIdx.x]; cols = f >= 8 && f <= T ? f : 0; }
+    unsigned nf = 0;                                          // the largest magnitude seen, as bits
+    for (int c = threadIdx.x; c < cols; c += 256) {
         unsigned acc = 0;
 #pragma unroll 32
-        for (int r = 0; r < 64; ++r) acc |= xb[(size_t)r * T + c];
+        for (int r = 0; r < 64; ++r) {
+            const unsigned v = xb[(size_t)r * T + c];
+            acc |= v;
+            nf = max(nf, v & 0x7fffffffu);
+        }
         if (acc) last = c;
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) last = max(last, __shfl_xor(last, o));
-    __shared__ int wl[4];
-    if ((threadIdx.x & 63) == 0) wl[threadIdx.x >> 6] = last;
+    const bool wave_nf = __ballot(nf >= 0x7f800000u) != 0;    // exponent bits all set: an infinity or a NaN
+    __shared__ int wl[4], wn[4];
+    if ((threadIdx.x & 63) == 0) { wl[threadIdx.x >> 6] = last; wn[threadIdx.x >> 6] = wave_nf ? 1 : 0; }
     __syncthreads();
-    if (threadIdx.x == 0) e0[blockIdx.x] = max(max(wl[0], wl[1]), max(wl[2], wl[3])) + 1;
+    if (threadIdx.x == 0) {
+        if (e0) e0[blockIdx.x] = max(max(wl[0], wl[1]), max(wl[2], wl[3])) + 1;
+        nonfinite[blockIdx.x] = wn[0] | wn[1] | wn[2] | wn[3];
+    }
 }
 
 // Leftover packing of the conv2 / conv3 task lists (Wino2Geo::ctab).  Image u, having given its first g columns away, lists its
@@ -354,6 +368,7 @@ static int model_infer_impl(const char* who, sir_handle* h, const sir_model_weig
     // Read once per call (the recurrence launches below may flip it)
     const bool proj_throughput = h->cluster_multi;
     int* const proj_rec = ptab + pt.count;
+    int* const nonfinite = proj_rec + 2;                        // [B]: pad_extent_kernel -> the head kernel
 
     // conv2 / conv3 as Winograd F(2x2, 3x3) -- the 2x2 output tile is the pooling window -- on the producer / consumer kernel
     // (conv_wino2_f16x3_kernel.h); shapes it does not cover (batch x map beyond 32-bit offsets) keep the bf16x6 fallback kernels.
@@ -377,8 +392,8 @@ static int model_infer_impl(const char* who, sir_handle* h, const sir_model_weig
         const int bn_c[3] = {32, 64, 128}, bn_o[3] = {0, 32, 96};
         for (int i = 0; i < 3; ++i)
             hipLaunchKernelGGL(prep_bn_kernel, dim3(1), dim3(128), 0, st, w->bn_w[i], w->bn_b[i], w->bn_mean[i], w->bn_var[i],
-                               bns + bn_o[i], bnt + bn_o[i], bn_c[i]);
-        for (int i = 0; i < 4; ++i) sir_prep_whh_quad(st, w->gru_w_hh[i], (unsigned char*)wht + (size_t)i * GRU_FRAG_BYTES);
+                               bns + bn_o[i], bnt + bn_o[i], bn_c[i], i == 0 ? w->conv_w[0] : (const float*)nullptr, i == 0 ? 288 : 0, h->status);
+        for (int i = 0; i < 4; ++i) sir_prep_whh_quad(h, st, w->gru_w_hh[i], (unsigned char*)wht + (size_t)i * GRU_FRAG_BYTES);
         // (the weight planes are prepared in the arithmetic of the kernel that will read them: f16x3 for the second-generation
         // Winograd kernel's forward stages, bf16x3 for the first-generation / direct fallbacks)
         if (w2) hipLaunchKernelGGL(prep_conv_w_wino_f16x3_kernel, dim3((32 * 16 * 64 + 255) / 256), dim3(256), 0, st, w->conv_w[1], wcb2, 32, 64, h->status);
@@ -387,8 +402,8 @@ static int model_infer_impl(const char* who, sir_handle* h, const sir_model_weig
         else hipLaunchKernelGGL(prep_conv_w_wino_bf16x3_kernel, dim3((64 * 16 * 128 + 255) / 256), dim3(256), 0, st, w->conv_w[2], wcb3, 64, 128);
         hipLaunchKernelGGL(prep_conv_w_bf16x3_kernel, dim3((64 * 9 * 128 + 255) / 256), dim3(256), 0, st, w->conv_w[2], wcb3d, 64, 128);
         for (int dir = 0; dir < 2; ++dir) {
-            hipLaunchKernelGGL(split2h_kernel, dim3(384), dim3(256), 0, st, w->gru_w_ih[dir], 1024, wsl0 + (size_t)dir * 2 * 768 * 1024, (size_t)768, 1024);
-            hipLaunchKernelGGL(split2h_kernel, dim3(192), dim3(256), 0, st, w->gru_w_ih[2 + dir], 512, wsl1 + (size_t)dir * 2 * 768 * 512, (size_t)768, 512);
+            hipLaunchKernelGGL(split2h_weights_kernel, dim3(384), dim3(256), 0, st, w->gru_w_ih[dir], 1024, wsl0 + (size_t)dir * 2 * 768 * 1024, (size_t)768, 1024, h->status);
+            hipLaunchKernelGGL(split2h_weights_kernel, dim3(192), dim3(256), 0, st, w->gru_w_ih[2 + dir], 512, wsl1 + (size_t)dir * 2 * 768 * 512, (size_t)768, 512, h->status);
         }
         if (!pe) { pe = &h->prep[h->prep_next]; h->prep_next = (h->prep_next + 1) % 4; }
         pe->ws = workspace; pe->version = h->weights_version; pe->key = prep_key;
@@ -399,6 +414,7 @@ static int model_infer_impl(const char* who, sir_handle* h, const sir_model_weig
     {
         SirProfScope prof(h, SIR_K_CONV1, st);
         if (ragged) {                                             // tables from the given lengths; conv1 at each utterance's own width
+            hipLaunchKernelGGL(pad_extent_kernel, dim3(B), dim3(256), 0, st, feats, d.T, (int*)nullptr, (const int*)frames, nonfinite);
             hipLaunchKernelGGL(ragged_tables_kernel, dim3(1), dim3(1024), 0, st, (const int*)frames, d, ptab + pt.e0, ptab + pt.d1, ptab + pt.d3,
                                ptab + pt.tab2, ptab + pt.tab3, ptab + pt.rows, h->status);
             hipLaunchKernelGGL(conv1_mfma_bn_relu_pool_ragged_kernel, conv1_grid(B, d.wp1), dim3(256), 0, st, feats,
@@ -406,8 +422,9 @@ static int model_infer_impl(const char* who, sir_handle* h, const sir_model_weig
             // (fallback path only: the mask of conv1's map is counted with conv1, that of conv2's map with conv2 in sir_profile_*)
             if (!w2) hipLaunchKernelGGL(ragged_mask_kernel, dim3(32, B), dim3(256), 0, st, a1, (const int*)(ptab + pt.e0), 1, 32, d.wp1, 32);
         } else {
-        if (w2) {                                                 // pad-skip extents and tables (two small launches, counted with conv1)
-            hipLaunchKernelGGL(pad_extent_kernel, dim3(B), dim3(256), 0, st, feats, d.T, ptab + pt.e0);
+        // (the scan also flags non-finite features for the head kernel: it runs on the fallback path too, where nothing reads e0)
+        hipLaunchKernelGGL(pad_extent_kernel, dim3(B), dim3(256), 0, st, feats, d.T, ptab + pt.e0, (const int*)nullptr, nonfinite);
+        if (w2) {                                                 // pad-skip tables (the scan and this: two small launches, counted with conv1)
             hipLaunchKernelGGL(pad_tables_kernel, dim3(1), dim3(1024), 0, st, (const int*)(ptab + pt.e0), d, ptab + pt.d1, ptab + pt.d3,
                                ptab + pt.tab2, ptab + pt.tab3, ptab + pt.rows, xz);
         }
@@ -481,10 +498,10 @@ static int model_infer_impl(const char* who, sir_handle* h, const sir_model_weig
         SirProfScope prof(h, SIR_K_ATTN, st);
         if (ragged)
             hipLaunchKernelGGL(attention_pool_ragged_kernel, dim3(B), dim3(256), 0, st, y1, w->attn_w, w->attn_b, ctx, S, w->fc_w, w->fc_b,
-                               w->num_classes, logits, (long long*)argmax, (const int*)(ptab + pt.d3));
+                               w->num_classes, logits, (long long*)argmax, (const int*)(ptab + pt.d3), (const int*)nonfinite);
         else
         hipLaunchKernelGGL(attention_pool_kernel, dim3(B), dim3(256), 0, st, y1, w->attn_w, w->attn_b, ctx, S, w->fc_w, w->fc_b,
-                           w->num_classes, logits, (long long*)argmax);
+                           w->num_classes, logits, (long long*)argmax, (const int*)nonfinite, (const double*)nullptr);
     }
     SIR_KCHECK();
     return SIR_OK;

@@ -25,15 +25,30 @@ typedef float mk_f32x2 __attribute__((ext_vector_type(2)));
 // weight preparation (tiny, runs at the head of every forward so it always sees current weights)
 // ------------------------------------------------------------------------------------------
 
-// eval-mode BatchNorm folded to y = x*scale + shift (models/models.py:50-52, running stats)
+// A conv1 weight or a BatchNorm weight / bias / statistic that is not finite sits in front of a ReLU and a max-pool that are fmaxf
+// and drop a NaN: the kernels that fold these parameters raise bit 13 of the handle's status word instead (SIR_EINVAL at the next
+// sir_check_status).
+constexpr unsigned int SIR_STATUS_BN_PARAM = 8192u;
+__device__ __forceinline__ bool sir_finite(float v) { return fabsf(v) < INFINITY; }
+__device__ __forceinline__ void sir_flag_bn_param(bool ok, unsigned int* status) {
+    if (!ok) __hip_atomic_fetch_or(status, SIR_STATUS_BN_PARAM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// eval-mode BatchNorm folded to y = x*scale + shift (models/models.py:50-52, running stats).  w1 / n1: conv1's weights, looked at
+// for non-finite values beside bn1's (NULL / 0 for the other blocks)
 #ifndef SIR_NO_STANDALONE_KERNELS
 static __global__ void prep_bn_kernel(const float* __restrict__ g, const float* __restrict__ b, const float* __restrict__ mean,
-                               const float* __restrict__ var, float* __restrict__ scale, float* __restrict__ shift, int c) {
+                               const float* __restrict__ var, float* __restrict__ scale, float* __restrict__ shift, int c,
+                               const float* __restrict__ w1, int n1, unsigned int* __restrict__ status) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= c) return;
     const float s = g[i] / sqrtf(var[i] + SIR_BN_EPS);
+    const float t = b[i] - mean[i] * s;
     scale[i] = s;
-    shift[i] = b[i] - mean[i] * s;
+    shift[i] = t;
+    bool ok = sir_finite(s) && sir_finite(t);                // (a NaN or an infinity in any of the four reaches one of the two)
+    for (int j = i; j < n1; j += c) ok = ok && sir_finite(w1[j]);
+    sir_flag_bn_param(ok, status);
 }
 #endif
 
@@ -236,7 +251,8 @@ __device__ __forceinline__ void attention_pool_body(const float* __restrict__ y,
                                                     int SR, const float* __restrict__ fcw,
                                                     const float* __restrict__ fcb, int C,
                                                     float* __restrict__ logits, long long* __restrict__ amax,
-                                                    const int* __restrict__ slen) {
+                                                    const int* __restrict__ slen, const int* __restrict__ bad_row,
+                                                    const double* __restrict__ sumsq) {
     // fused tail (models.py:63-67 + evaluate.py:83): attention pooling, the 512 -> C classifier and the
     // arg-max of one utterance per workgroup.  The head is 31.7 kFLOP per utterance; as a separate
     // 128x64-tile MFMA GEMM it occupied 2 workgroups and cost 34 us per batch, fused here it is free.
@@ -245,6 +261,11 @@ __device__ __forceinline__ void attention_pool_body(const float* __restrict__ y,
     __shared__ float lg[64];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int S = RAGGED ? min(SR, slen[b]) : SR;
+    // a non-finite feature in this utterance (bad_row: pad_extent_kernel) or anywhere in a batch-normalised batch (sumsq: the sum of
+    // the squared features) makes the row's logits NaN, as they are in torch: ReLU and max-pool as fmaxf dropped the NaN on the way.
+    // The flag is loaded here and applied at the stores at the end: nothing in between waits for it.
+    bool bad = bad_row && bad_row[b] != 0;
+    if (sumsq) bad |= (__double2hiint(sumsq[0]) & 0x7ff00000) == 0x7ff00000;
     if (RAGGED && S < 1) {                                    // (whole block, before any barrier)
         const float qnan = __builtin_nanf("");
         for (int c = tid; c < 512; c += 256) ctx[(size_t)b * 512 + c] = qnan;
@@ -310,6 +331,7 @@ __device__ __forceinline__ void attention_pool_body(const float* __restrict__ y,
         d += __shfl_xor(d, 1); d += __shfl_xor(d, 2); d += __shfl_xor(d, 4);
         if (part == 0) {
             d += fcb[j];
+            if (bad) d = __builtin_nanf("");
             lg[j] = d;
             logits[(size_t)b * C + j] = d;
         }
@@ -328,16 +350,17 @@ static __global__ __launch_bounds__(256) void attention_pool_kernel(const float*
                                                              const float* __restrict__ ab, float* __restrict__ ctx,
                                                              int S, const float* __restrict__ fcw,
                                                              const float* __restrict__ fcb, int C,
-                                                             float* __restrict__ logits, long long* __restrict__ amax) {
-    attention_pool_body<false>(y, aw, ab, ctx, S, fcw, fcb, C, logits, amax, nullptr);
+                                                             float* __restrict__ logits, long long* __restrict__ amax,
+                                                             const int* __restrict__ bad_row, const double* __restrict__ sumsq) {
+    attention_pool_body<false>(y, aw, ab, ctx, S, fcw, fcb, C, logits, amax, nullptr, bad_row, sumsq);
 }
 static __global__ __launch_bounds__(256) void attention_pool_ragged_kernel(const float* __restrict__ y, const float* __restrict__ aw,
                                                              const float* __restrict__ ab, float* __restrict__ ctx,
                                                              int S, const float* __restrict__ fcw,
                                                              const float* __restrict__ fcb, int C,
                                                              float* __restrict__ logits, long long* __restrict__ amax,
-                                                             const int* __restrict__ slen) {
-    attention_pool_body<true>(y, aw, ab, ctx, S, fcw, fcb, C, logits, amax, slen);
+                                                             const int* __restrict__ slen, const int* __restrict__ bad_row) {
+    attention_pool_body<true>(y, aw, ab, ctx, S, fcw, fcb, C, logits, amax, slen, bad_row, nullptr);
 }
 #endif
 

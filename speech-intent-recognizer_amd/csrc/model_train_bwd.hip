@@ -13,7 +13,7 @@ namespace {
 // (16 products per tile and channel pair instead of 36, wgrad_wino_f16x3_kernel.h) + strip sum + G^T . G, or the nine-tap fallback,
 // one slab per image, + its two-pass reduce
 template <int CIN, int COUT>
-int conv_wgrad(sir_handle* h, hipStream_t st, bool wino, int B, int H, int W, const float* dz, const float* a, float* slab, float* dw, float unscale) {
+int conv_wgrad(sir_handle* h, hipStream_t st, bool wino, int B, int H, int W, const float* dz, const float* a, float* slab, float* dw, const float* bsc) {
     if (wino) {
         using Cfg = WgwCfg<CIN, COUT>;
         const int strips = wgrad_wino_strips(B, H, W, Cfg::TPS, Cfg::groups, h->num_cus);
@@ -21,7 +21,7 @@ int conv_wgrad(sir_handle* h, hipStream_t st, bool wino, int B, int H, int W, co
         hipLaunchKernelGGL((conv_wgrad_wino_f16x3_kernel<CIN, COUT>), dim3(Cfg::groups * strips), dim3(WGW_THREADS), Cfg::lds_bytes, st, dz, a, slab, B, H, W);
         float* part = slab + (size_t)strips * 16 * COUT * CIN;
         hipLaunchKernelGGL(wgrad_wino_sum_kernel, dim3((16 * COUT * CIN / 4 + 255) / 256), dim3(256), 0, st, (const float*)slab, strips, 16 * COUT * CIN / 4, part);
-        hipLaunchKernelGGL(wgrad_wino_finish_kernel, dim3((COUT * CIN + 255) / 256), dim3(256), 0, st, (const float*)part, CIN, COUT, dw, unscale);
+        hipLaunchKernelGGL(wgrad_wino_finish_kernel, dim3((COUT * CIN + 255) / 256), dim3(256), 0, st, (const float*)part, CIN, COUT, dw, bsc);
         return SIR_OK;
     }
     const size_t ldsx = wgrad_x6_lds_bytes(CIN, COUT, W);
@@ -31,7 +31,7 @@ int conv_wgrad(sir_handle* h, hipStream_t st, bool wino, int B, int H, int W, co
     hipLaunchKernelGGL((conv_wgrad_bf16x6_kernel<CIN, COUT>), dim3(B), dim3(512), ldsx, st, dz, a, slab, H, W, H);
     float* part = slab + (size_t)B * 9 * COUT * CIN;
     hipLaunchKernelGGL(wgrad_reduce_partial_kernel, dim3((9 * COUT * CIN / 4 + 255) / 256, WGR_PARTS), dim3(256), 0, st, (const float*)slab, B, 9 * COUT * CIN / 4, part);
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((9 * COUT * CIN + 255) / 256), dim3(256), 0, st, (const float*)part, WGR_PARTS, CIN, COUT, dw, unscale);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((9 * COUT * CIN + 255) / 256), dim3(256), 0, st, (const float*)part, WGR_PARTS, CIN, COUT, dw, bsc);
     return SIR_OK;
 }
 
@@ -105,7 +105,8 @@ struct Bwd {
     float* dfeats;                  // d(loss)/d(feats) [B][64][T], or NULL: not wanted
     float dropout_p; uint64_t dropout_seed;
     TPtrs p; TDims d; BwdPlan want;
-    float gscale, unscale;          // sir_bwd_loss_scale and its inverse
+    const float* bsc;               // TB_BSC: this call's loss scale and its inverse, written by bwd_scale_kernel (pair 0; pair 1 + b: utterance b's)
+    bool row_scaled;                // every utterance on a scale of its own (the data-only backward under frozen statistics)
     float *scale, *shift, *smean, *sinv, *mdy, *mdyx;      // the [224]-channel BatchNorm arrays (bn1 | bn2 | bn3 at 0, 32, 96) in p.bn, p.bnb
     bool forked, side_marked;       // side has work of this call / its last launch is marked by event 3 (sir_handle::bwd_ev)
 
@@ -135,9 +136,11 @@ int bwd_head(Bwd& c) {
     float* dab_part = c.p.small + (size_t)B * 512;
     if (c.want.head) {
         SirProfScope prof(c.h, SIR_K_B_HEAD, c.st);
+        hipLaunchKernelGGL(bwd_scale_kernel, dim3(c.row_scaled ? (B + 15) / 16 : 1), dim3(1024), 0, c.st, c.dlogits, B, C, sir_bwd_loss_scale_exp(B),
+                           c.row_scaled ? 1 : 0, c.p.bsc);
         // (workgroups [B, B + 2 C) are the fc weight / bias gradient: left out when fc is frozen)
         hipLaunchKernelGGL(head_bwd_kernel, dim3(B + (c.want.fc ? 2 * C : 0)), dim3(256), 0, c.st, c.dlogits, c.w->fc_w, (const float*)c.p.y1, c.w->attn_w,
-                           c.w->attn_b, (const float*)c.p.ctx, c.p.dy1, daw_part, dab_part, c.g->fc_w, c.g->fc_b, B, S, C, c.gscale);
+                           c.w->attn_b, (const float*)c.p.ctx, c.p.dy1, daw_part, dab_part, c.g->fc_w, c.g->fc_b, B, S, C, c.bsc, c.row_scaled ? 1 : 0);
         if (c.want.attn)
             hipLaunchKernelGGL(head_colsum_kernel, dim3(9), dim3(256), 0, c.st, (const float*)daw_part, (const float*)dab_part, B, c.g->attn_w, c.g->attn_b);
     }
@@ -190,7 +193,7 @@ int bwd_gru_dw(Bwd& c, int layer, hipStream_t s_) {
     hipLaunchKernelGGL(gemm_tn2_f16x3_kernel<true>, dim3(tiles, nsplit), dim3(TN2_THREADS), tn2_lds_bytes(true), s_, jb, 768, M, kchunk, c.d.S);
     SlabJobs sj{};
     for (int j = 0; j < 4; ++j) { sj.src[j] = jb.slab[j]; sj.out[j] = outs[j]; sj.n[j] = outs[j] ? sizes[j] : 0; }     // (n = 0: a frozen matrix is not reduced)
-    hipLaunchKernelGGL(slab_reduce_jobs_kernel, dim3(grid_for(sizes[0]), 4), dim3(256), 0, s_, sj, nsplit, c.unscale);
+    hipLaunchKernelGGL(slab_reduce_jobs_kernel, dim3(grid_for(sizes[0]), 4), dim3(256), 0, s_, sj, nsplit, c.bsc);
     return SIR_OK;
 }
 
@@ -247,7 +250,7 @@ int bwd_gru_layer(Bwd& c, int layer) {
         // bias gradients first: bsum_* alias the slab area used below
         if (want.gru_b[layer])
             hipLaunchKernelGGL(gru_bias_colsum_kernel, dim3(24, 2), dim3(256), 0, c.st, (const float*)bsum_i, (const float*)bsum_h, B,
-                               c.g->gru_b_ih[2 * layer], c.g->gru_b_ih[2 * layer + 1], c.g->gru_b_hh[2 * layer], c.g->gru_b_hh[2 * layer + 1], c.unscale);
+                               c.g->gru_b_ih[2 * layer], c.g->gru_b_ih[2 * layer + 1], c.g->gru_b_hh[2 * layer], c.g->gru_b_hh[2 * layer + 1], c.bsc);
     }
     // Layer 0's saved gates and outputs (65 MB) were written early in the forward and have left the 256 MB last-level cache by now;
     // layer 1's are still there, and layer 0's BPTT -- a latency chain whose polls share the L2 channels with its input misses --
@@ -299,13 +302,13 @@ int bwd_conv_block(Bwd& c, const ConvBlock& k, Reduce reduce) {
         if (frozen) {
             if (gb)
                 hipLaunchKernelGGL(bn_bwd_finalize_frozen_kernel, dim3(COUT), dim3(256), 0, c.st, (const float2*)c.p.stats, k.nblk, COUT, c.g->bn_w[k.i],
-                                   c.g->bn_b[k.i], c.unscale);
+                                   c.g->bn_b[k.i], c.bsc);
             if (k.need_dz)
                 hipLaunchKernelGGL((bn_bwd_dz_kernel<GRU_IN, true>), dim3(dz_grid), dim3(256), 0, c.st, k.z, k.da, scale, shift, (const float*)nullptr,
                                    (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, k.dz, B, k.H, k.W, COUT, Hp, k.Wp);
         } else {
             hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(COUT), dim3(256), 0, c.st, (const float2*)c.p.stats, k.nblk, COUT, (double)B * k.H * k.W,
-                               c.g->bn_w[k.i], c.g->bn_b[k.i], c.mdy + k.ch, c.mdyx + k.ch, c.unscale);
+                               c.g->bn_w[k.i], c.g->bn_b[k.i], c.mdy + k.ch, c.mdyx + k.ch, c.bsc);
             if (k.need_dz)
                 hipLaunchKernelGGL(bn_bwd_dz_kernel<GRU_IN>, dim3(dz_grid), dim3(256), 0, c.st, k.z, k.da, scale, shift, c.smean + k.ch, c.sinv + k.ch,
                                    c.mdy + k.ch, c.mdyx + k.ch, k.dz, B, k.H, k.W, COUT, Hp, k.Wp);
@@ -314,7 +317,7 @@ int bwd_conv_block(Bwd& c, const ConvBlock& k, Reduce reduce) {
     if (c.g->conv_w[k.i]) {
         SIR_TRY(c.fork(k.ev));
         {   SirProfScope prof(c.h, k.prof_wgrad, c.side);
-            SIR_TRY((conv_wgrad<CIN, COUT>(c.h, c.side, k.wgrad_wino, B, k.H, k.W, k.dz, k.a_in, c.p.slab, c.g->conv_w[k.i], c.unscale)));
+            SIR_TRY((conv_wgrad<CIN, COUT>(c.h, c.side, k.wgrad_wino, B, k.H, k.W, k.dz, k.a_in, c.p.slab, c.g->conv_w[k.i], c.bsc)));
         }
         if (k.last_on_side) SIR_TRY(c.mark_side());
     }
@@ -376,10 +379,10 @@ int bwd_conv1(Bwd& c) {
         hipLaunchKernelGGL(colsum_kernel, dim3((352 + 63) / 64), dim3(256), 0, c.st, (const float*)c1tmp, 128, 352, 352, c1tot);
         if (frozen)                                          // frozen statistics: plain sums, no input moments
             hipLaunchKernelGGL(conv1_bwd_finalize_frozen_kernel, dim3(1), dim3(320), 0, c.st, (const float*)c1tot, (const float*)c.scale, g->bn_w[0], g->bn_b[0],
-                               g->conv_w[0], c.unscale);
+                               g->conv_w[0], c.bsc);
         else                                                 // (the means go to bn1's channels of TB_BNB, which nothing else uses)
             hipLaunchKernelGGL(conv1_bwd_finalize_kernel, dim3(1), dim3(320), 0, c.st, (const float*)c1tot, (const double*)p.c1m,
-                               c.w->conv_w[0], c.scale, c.smean, c.sinv, (double)B * 64 * T, g->bn_w[0], g->bn_b[0], g->conv_w[0], c.unscale,
+                               c.w->conv_w[0], c.scale, c.smean, c.sinv, (double)B * 64 * T, g->bn_w[0], g->bn_b[0], g->conv_w[0], c.bsc,
                                c.dfeats ? c.mdy : (float*)nullptr, c.dfeats ? c.mdyx : (float*)nullptr);
     }
     if (c.dfeats) {
@@ -388,10 +391,10 @@ int bwd_conv1(Bwd& c) {
         const dim3 gd((T + C1D_TW - 1) / C1D_TW, (64 + C1D_TH - 1) / C1D_TH, B);
         if (frozen)
             hipLaunchKernelGGL(conv1_bwd_data_kernel<true>, gd, dim3(256), 0, c.st, c.feats, c.w->conv_w[0], (const float*)p.da1, c.scale, c.shift,
-                               (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, c.dfeats, 64, T, 32, d.wp1, c.unscale);
+                               (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, c.dfeats, 64, T, 32, d.wp1, c.bsc, c.row_scaled ? 1 : 0);
         else
             hipLaunchKernelGGL(conv1_bwd_data_kernel<false>, gd, dim3(256), 0, c.st, c.feats, c.w->conv_w[0], (const float*)p.da1, c.scale, c.shift,
-                               c.smean, c.sinv, (const float*)c.mdy, (const float*)c.mdyx, c.dfeats, 64, T, 32, d.wp1, c.unscale);
+                               c.smean, c.sinv, (const float*)c.mdy, (const float*)c.mdyx, c.dfeats, 64, T, 32, d.wp1, c.bsc, c.row_scaled ? 1 : 0);
     }
     SIR_KCHECK();
     return SIR_OK;
@@ -447,8 +450,11 @@ extern "C" int sir_model_train_bwd_x(sir_handle* h, const sir_model_weights* w, 
     c.side = c.two ? h->bwd_side : c.st;
     c.p = carve(workspace, off);
     c.want = bwd_plan(*g, dfeats != nullptr);
-    c.gscale = sir_bwd_loss_scale(c.d.B);
-    c.unscale = 1.0f / c.gscale;
+    c.bsc = c.p.bsc;
+    // rows on scales of their own: only where no gradient sums over the batch -- every BatchNorm on its running statistics and no
+    // parameter gradient wanted (sir_amd.explain, a crafting pass of an adversary under frozen statistics)
+    c.row_scaled = dfeats && cfg->bn_frozen[0] && cfg->bn_frozen[1] && cfg->bn_frozen[2] && !c.want.fc && !c.want.attn && !c.want.gru_w[0] &&
+                   !c.want.gru_w[1] && !c.want.gru_b[0] && !c.want.gru_b[1] && !c.want.blk[0] && !c.want.blk[1] && !c.want.blk[2];
     c.scale = c.p.bn; c.shift = c.p.bn + 224; c.smean = c.p.bn + 448; c.sinv = c.p.bn + 672;
     c.mdy = c.p.bnb; c.mdyx = c.p.bnb + 224;
     c.y0in = dropout_p > 0.0f ? c.p.y0d : c.p.y0;

@@ -93,7 +93,7 @@ extern "C" int sir_model_train_fwd_cfg(sir_handle* h, const sir_model_weights* w
         // of z are bilinear in the taps), so conv1 itself runs once, fused with BN + ReLU + pool
         if (cfg->bn_frozen[0]) {                      // frozen statistics: no moments (the frozen conv1 backward needs none either)
             hipLaunchKernelGGL(bn_fold_running_kernel, dim3(1), dim3(64), 0, st, w->bn_w[0], w->bn_b[0], (const float*)bn_running_mean[0],
-                               (const float*)bn_running_var[0], 32, scale, shift, smean, sinv);
+                               (const float*)bn_running_var[0], 32, scale, shift, smean, sinv, w->conv_w[0], 288, h->status);
         } else {
             const int tiles = d.c1gx * d.c1gy;
             int per_img = (2048 + B - 1) / B;             // workgroups per image: >= 2048 in all when the batch allows it
@@ -101,7 +101,7 @@ extern "C" int sir_model_train_fwd_cfg(sir_handle* h, const sir_model_weights* w
             hipLaunchKernelGGL(conv1_moments_kernel, dim3(per_img, B), dim3(256), 0, st, feats, (float*)p.stats, 64, T, d.c1gx, d.c1gy);
             hipLaunchKernelGGL(conv1_moments_reduce_kernel, dim3(C1_NMOM), dim3(256), 0, st, (const float*)p.stats, per_img * B, p.c1m);
             hipLaunchKernelGGL(conv1_bn_from_moments_kernel, dim3(1), dim3(64), 0, st, (const double*)p.c1m, w->conv_w[0],
-                               (double)B * 64 * T, w->bn_w[0], w->bn_b[0], bn_running_mean[0], bn_running_var[0], bn_momentum, scale, shift, smean, sinv);
+                               (double)B * 64 * T, w->bn_w[0], w->bn_b[0], bn_running_mean[0], bn_running_var[0], bn_momentum, scale, shift, smean, sinv, h->status);
         }
         hipLaunchKernelGGL(conv1_mfma_bn_relu_pool_kernel, conv1_grid(B, d.wp1), dim3(256), 0, st,
                            feats, w->conv_w[0], scale, shift, p.a1, 64, T, 32, d.wp1, (const float*)nullptr, B, (const int*)nullptr);
@@ -114,13 +114,13 @@ extern "C" int sir_model_train_fwd_cfg(sir_handle* h, const sir_model_weights* w
         SirProfScope prof(h, SIR_K_T_BN2, st);
         if (cfg->bn_frozen[1])                        // (the convolution's partial statistics are simply not read)
             hipLaunchKernelGGL(bn_fold_running_kernel, dim3(1), dim3(64), 0, st, w->bn_w[1], w->bn_b[1], (const float*)bn_running_mean[1],
-                               (const float*)bn_running_var[1], 64, scale + 32, shift + 32, smean + 32, sinv + 32);
+                               (const float*)bn_running_var[1], 64, scale + 32, shift + 32, smean + 32, sinv + 32, (const float*)nullptr, 0, h->status);
         else
             hipLaunchKernelGGL(bn_finalize_kernel, dim3(64), dim3(256), 0, st, (const float2*)p.stats, w2 ? (int)wino2_stat_blocks(B, 32, d.wp1, h->num_cus) : d.c2wx * B, 64,
                                (double)B * 32 * d.wp1, w->bn_w[1], w->bn_b[1], bn_running_mean[1], bn_running_var[1], bn_momentum,
-                               scale + 32, shift + 32, smean + 32, sinv + 32);
+                               scale + 32, shift + 32, smean + 32, sinv + 32, h->status);
         hipLaunchKernelGGL(bn_relu_pool_kernel<false>, dim3(grid_for((size_t)B * 16 * d.wp2 * 16)), dim3(256), 0, st, p.z2,
-                           scale + 32, shift + 32, p.a2, B, 32, d.wp1, 64, 16, d.wp2);
+                           scale + 32, shift + 32, p.a2, B, 32, d.wp1, 64, 16, d.wp2, 256.0f, h->status);
     }
     {
         {   SirProfScope prof(h, SIR_K_T_CONV3, st);
@@ -129,13 +129,13 @@ extern "C" int sir_model_train_fwd_cfg(sir_handle* h, const sir_model_weights* w
         SirProfScope prof(h, SIR_K_T_BN3, st);
         if (cfg->bn_frozen[2])
             hipLaunchKernelGGL(bn_fold_running_kernel, dim3(1), dim3(128), 0, st, w->bn_w[2], w->bn_b[2], (const float*)bn_running_mean[2],
-                               (const float*)bn_running_var[2], 128, scale + 96, shift + 96, smean + 96, sinv + 96);
+                               (const float*)bn_running_var[2], 128, scale + 96, shift + 96, smean + 96, sinv + 96, (const float*)nullptr, 0, h->status);
         else
             hipLaunchKernelGGL(bn_finalize_kernel, dim3(128), dim3(256), 0, st, (const float2*)p.stats, w2 ? (int)wino2_stat_blocks(B, 16, d.wp2, h->num_cus) : d.c3fx * B, 128,
                                (double)B * 16 * d.wp2, w->bn_w[2], w->bn_b[2], bn_running_mean[2], bn_running_var[2], bn_momentum,
-                               scale + 96, shift + 96, smean + 96, sinv + 96);
+                               scale + 96, shift + 96, smean + 96, sinv + 96, h->status);
         hipLaunchKernelGGL(bn_relu_pool_kernel<true>, dim3(grid_for((size_t)B * 8 * d.wp3 * 32)), dim3(256), 0, st, p.z3,
-                           scale + 96, shift + 96, p.x0, B, 16, d.wp2, 128, 8, d.wp3);
+                           scale + 96, shift + 96, p.x0, B, 16, d.wp2, 128, 8, d.wp3, 512.0f, h->status);
     }
     SIR_KCHECK();
 
@@ -166,8 +166,11 @@ extern "C" int sir_model_train_fwd_cfg(sir_handle* h, const sir_model_weights* w
                                     (const char*)p.wht + 2 * GRU_FRAG_BYTES, (const char*)p.wht + 3 * GRU_FRAG_BYTES));
     }
     SirProfScope prof_head(h, SIR_K_T_HEAD, st);
+    // live bn1 statistics: the sum of the squared features (a moment of conv1_moments_kernel) is finite only if every feature is; if
+    // it is not, every row's logits are NaN -- batch statistics carry one bad feature into all of them (ReLU / max-pool drop NaNs)
     hipLaunchKernelGGL(attention_pool_kernel, dim3(B), dim3(256), 0, st, p.y1, w->attn_w, w->attn_b, p.ctx, S, w->fc_w,
-                       w->fc_b, w->num_classes, logits, (long long*)nullptr);
+                       w->fc_b, w->num_classes, logits, (long long*)nullptr, (const int*)nullptr,
+                       cfg->bn_frozen[0] ? (const double*)nullptr : (const double*)p.c1m + c1_r_index(4, 4));
     SIR_KCHECK();
     return SIR_OK;
 }

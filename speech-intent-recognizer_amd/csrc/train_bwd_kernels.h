@@ -5,6 +5,56 @@
 #include "train_workspace.h"
 
 // ------------------------------------------------------------------------------------------
+// The backward's loss scale for one call (train_workspace.h: sir_bwd_loss_scale), from the dlogits it was handed.  Writes pairs
+// {scale, 1 / scale} of powers of two into TB_BSC: pair 0 for the call, pair 1 + b for utterance b.
+//   max |dlogits| * 2^static_exp lies in [2^(x-1), 2^x); x = 8 for a mean cross-entropy far from convergence.  While x stays in
+//   [BSC_X_LO, BSC_X_HI] the static scale is kept (bit for bit what a fixed scale computes); outside it the exponent moves by 8 - x,
+//   which puts the scaled maximum back into [2^7, 2^8).  A zero, subnormal or non-finite maximum keeps the static scale (NaN and
+//   infinity then travel through the backward as they are).
+//   per_row == 0: one workgroup, pair 0 from the maximum over all of dlogits (pairs 1.. are not written).
+//   per_row != 0: one wave per utterance (16 per workgroup), pair 1 + b from the maximum of row b alone -- for the data-only
+//   backward under frozen statistics, where utterance b's gradients depend on row b of dlogits and nothing else; pair 0 = static.
+// ------------------------------------------------------------------------------------------
+constexpr int BSC_X_LO = 6, BSC_X_HI = 10;
+__device__ __forceinline__ void bwd_scale_pair(unsigned maxbits, int static_exp, float* __restrict__ out) {
+    const int e = (int)(maxbits >> 23);                       // biased exponent (the sign bit is already cleared)
+    int g = static_exp;
+    if (e != 0 && e != 255) {
+        const int x = e - 126 + static_exp;
+        if (x < BSC_X_LO || x > BSC_X_HI) g = min(max(static_exp + 8 - x, -100), 100);
+    }
+    out[0] = __uint_as_float((unsigned)(127 + g) << 23);
+    out[1] = __uint_as_float((unsigned)(127 - g) << 23);
+}
+static __global__ __launch_bounds__(1024) void bwd_scale_kernel(const float* __restrict__ dlogits, int B, int C, int static_exp, int per_row,
+                                                                float* __restrict__ bsc) {
+    __shared__ unsigned red[16];
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    if (per_row) {
+        const int b = blockIdx.x * 16 + wv;
+        if (b < B) {
+            unsigned v = lane < C ? (__float_as_uint(dlogits[(size_t)b * C + lane]) & 0x7fffffffu) : 0u;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o));
+            if (lane == 0) bwd_scale_pair(v, static_exp, bsc + 2 * (1 + b));
+        }
+        if (blockIdx.x == 0 && tid == 0) bwd_scale_pair(0u, static_exp, bsc);
+        return;
+    }
+    unsigned m = 0u;
+    const size_t n = (size_t)B * C;
+    for (size_t i = tid; i < n; i += 1024) m = max(m, __float_as_uint(dlogits[i]) & 0x7fffffffu);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
+    if (lane == 0) red[wv] = m;
+    __syncthreads();
+    if (tid == 0) {
+        for (int i = 1; i < 16; ++i) m = max(m, red[i]);
+        bwd_scale_pair(m, static_exp, bsc);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // head backward: fc + attention pooling (models.py:63-67)
 //   dctx = dlogits fc_w;  w = softmax_t(y a + b);  dw_t = <dctx, y_t>;  ds_t = w_t (dw_t - sum w dw)
 //   dy_t = w_t dctx + ds_t a;  per-utterance partials of d attention.weight / d attention.bias
@@ -128,7 +178,8 @@ static __global__ __launch_bounds__(256) void head_colsum_kernel(const float* __
 // the array), columns [0, 768) -> direction 0, [768, 1536) -> direction 1
 static __global__ __launch_bounds__(256) void gru_bias_colsum_kernel(const float* __restrict__ bsum_i, const float* __restrict__ bsum_h, int rows,
                                                                       float* __restrict__ bi0, float* __restrict__ bi1,
-                                                                      float* __restrict__ bh0, float* __restrict__ bh1, float unscale) {
+                                                                      float* __restrict__ bh0, float* __restrict__ bh1, const float* __restrict__ bsc) {
+    const float unscale = bsc[1];
     __shared__ float red[4][64];
     const float* in = blockIdx.y ? bsum_h : bsum_i;
     const int col = blockIdx.x * 64 + (threadIdx.x & 63), part = threadIdx.x >> 6;     // col < 1536 (grid.x = 24)
@@ -191,20 +242,20 @@ __device__ __forceinline__ void fc_wgrad_block(int j, int half, const float* __r
 
 // head backward, ONE launch for two independent jobs (both only need dlogits): workgroups [0, B) = one utterance each
 // (head_bwd_utt: fc + attention pooling backward, per-utterance attention partials; its dy output -- and with it everything the
-// rest of the backward computes -- carries the loss scale `gscale`, see sir_bwd_loss_scale); workgroups [B, B + 2 C) = the fc weight /
+// rest of the backward computes -- carries the loss scale of bwd_scale_kernel, pair 0 or the row's own); workgroups [B, B + 2 C) = the fc weight /
 // bias gradients (fc_wgrad_block).  head_colsum_kernel adds the attention partials afterwards.
 static __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __restrict__ dlogits, const float* __restrict__ fcw,
                                                               const float* __restrict__ y, const float* __restrict__ aw,
                                                               const float* __restrict__ ab, const float* __restrict__ ctx,
                                                               float* __restrict__ dy, float* __restrict__ daw_part,
                                                               float* __restrict__ dab_part, float* __restrict__ d_fc_w,
-                                                              float* __restrict__ d_fc_b, int B, int S, int C, float gscale) {
+                                                              float* __restrict__ d_fc_b, int B, int S, int C, const float* __restrict__ bsc, int row_scaled) {
     if ((int)blockIdx.x >= B) {
         const int i = blockIdx.x - B;
         fc_wgrad_block(i >> 1, i & 1, dlogits, ctx, d_fc_w, d_fc_b, B, C);
         return;
     }
-    head_bwd_utt(blockIdx.x, dlogits, fcw, y, aw, ab, dy, daw_part, dab_part, S, C, gscale);
+    head_bwd_utt(blockIdx.x, dlogits, fcw, y, aw, ab, dy, daw_part, dab_part, S, C, bsc[row_scaled ? 2 * (1 + blockIdx.x) : 0]);
 }
 
 // Reads two buffers and keeps nothing: a software prefetch into the last-level cache, launched on the backward's side stream (model_train_bwd.hip:
@@ -220,7 +271,8 @@ static __global__ __launch_bounds__(256) void cache_touch_kernel(const float4* _
 
 // out_j[i] = sum_z slabs_j[z][i] for up to four jobs (blockIdx.y) with a common slab count; slab stride = n_j
 struct SlabJobs { const float* src[4]; float* out[4]; size_t n[4]; };
-static __global__ void slab_reduce_jobs_kernel(SlabJobs jobs, int nslab, float unscale) {
+static __global__ void slab_reduce_jobs_kernel(SlabJobs jobs, int nslab, const float* __restrict__ bsc) {
+    const float unscale = bsc[1];
     const int j = blockIdx.y;
     const size_t n = jobs.n[j];
     const float* __restrict__ s = jobs.src[j];
@@ -389,7 +441,8 @@ static __global__ __launch_bounds__(256) void bn_bwd_reduce_pooled_gru_kernel(
 // sums the (sum dy, sum dy*xhat) partials -> dbeta, dgamma and the two per-channel means used by dz
 static __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float2* __restrict__ part, int nblk, int C, double count,
                                                                float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                               float* __restrict__ mdy, float* __restrict__ mdyx, float unscale) {
+                                                               float* __restrict__ mdy, float* __restrict__ mdyx, const float* __restrict__ bsc) {
+    const float unscale = bsc[1];
     __shared__ double rs[256], rq[256];
     const int c = blockIdx.x, tid = threadIdx.x;
     double s = 0.0, q = 0.0;
@@ -412,7 +465,8 @@ static __global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(const float
 // frozen statistics: the same ordered sum of the partials, but only dbeta / dgamma come out of it (dz has no mean terms, so
 // nothing downstream waits for this kernel); either output may be NULL
 static __global__ __launch_bounds__(256) void bn_bwd_finalize_frozen_kernel(const float2* __restrict__ part, int nblk, int C,
-                                                                      float* __restrict__ dgamma, float* __restrict__ dbeta, float unscale) {
+                                                                      float* __restrict__ dgamma, float* __restrict__ dbeta, const float* __restrict__ bsc) {
+    const float unscale = bsc[1];
     __shared__ double rs[256], rq[256];
     const int c = blockIdx.x, tid = threadIdx.x;
     double s = 0.0, q = 0.0;
@@ -621,8 +675,9 @@ __global__ __launch_bounds__(256) void conv1_bwd_kernel(const float* __restrict_
 static __global__ void conv1_bwd_finalize_kernel(const float* __restrict__ totals, const double* __restrict__ M, const float* __restrict__ w,
                                                  const float* __restrict__ scale, const float* __restrict__ mean,
                                                  const float* __restrict__ invstd, double count, float* __restrict__ dgamma,
-                                                 float* __restrict__ dbeta, float* __restrict__ dw, float unscale,
+                                                 float* __restrict__ dbeta, float* __restrict__ dw, const float* __restrict__ bsc,
                                                  float* __restrict__ m1_out, float* __restrict__ m2_out) {
+    const float unscale = bsc[1];
     const int idx = threadIdx.x;
     if (idx >= 288) return;
     const int c = idx / 9, tap = idx % 9;
@@ -643,7 +698,8 @@ static __global__ void conv1_bwd_finalize_kernel(const float* __restrict__ total
 // totals (xhat from the running statistics); no input moments.  Any output may be NULL.
 static __global__ void conv1_bwd_finalize_frozen_kernel(const float* __restrict__ totals, const float* __restrict__ scale,
                                                         float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ dw,
-                                                        float unscale) {
+                                                        const float* __restrict__ bsc) {
+    const float unscale = bsc[1];
     const int idx = threadIdx.x;
     if (idx >= 288) return;
     const int c = idx / 9, tap = idx % 9;
@@ -681,7 +737,8 @@ __global__ __launch_bounds__(256, 3) void conv1_bwd_data_kernel(const float* __r
                                                               const float* __restrict__ shift, const float* __restrict__ mean,
                                                               const float* __restrict__ invstd, const float* __restrict__ mdy,
                                                               const float* __restrict__ mdyx, float* __restrict__ dx,
-                                                              int H, int W, int Hp, int Wp, float unscale) {
+                                                              int H, int W, int Hp, int Wp, const float* __restrict__ bsc, int row_scaled) {
+    const float unscale = bsc[row_scaled ? 2 * (1 + blockIdx.z) + 1 : 1];    // (the utterance's own scale: bwd_scale_kernel)
     __shared__ float xt[C1D_XR * C1D_XC];
     __shared__ __attribute__((aligned(16))) float dzs[C1D_ZR * C1D_ZC * C1D_ZS];
     const int b = blockIdx.z, h0 = blockIdx.y * C1D_TH, w0 = blockIdx.x * C1D_TW;
@@ -816,7 +873,8 @@ static __global__ __launch_bounds__(256) void wgrad_reduce_partial_kernel(const 
     }
     reinterpret_cast<float4*>(part)[(size_t)blockIdx.y * total4 + idx] = acc;
 }
-static __global__ void wgrad_reduce_kernel(const float* __restrict__ part, int nparts, int cin, int cout, float* __restrict__ dw, float unscale) {
+static __global__ void wgrad_reduce_kernel(const float* __restrict__ part, int nparts, int cin, int cout, float* __restrict__ dw, const float* __restrict__ bsc) {
+    const float unscale = bsc[1];
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;       // (tap, co, ci), ci fastest
     const int total = 9 * cout * cin;
     if (idx >= total) return;

@@ -103,7 +103,9 @@ __device__ __forceinline__ void bn_finalize_channel(double sum, double sumsq, do
                                                     const float* __restrict__ beta, float* __restrict__ run_mean,
                                                     float* __restrict__ run_var, float momentum, float* __restrict__ scale,
                                                     float* __restrict__ shift, float* __restrict__ save_mean,
-                                                    float* __restrict__ save_invstd) {
+                                                    float* __restrict__ save_invstd, unsigned int* __restrict__ status) {
+    // (the PARAMETERS only: batch statistics that are not finite come from the features, which the head kernel answers for)
+    sir_flag_bn_param(sir_finite(gamma[c]) && sir_finite(beta[c]), status);
     const double mean = sum / count;
     double var = sumsq / count - mean * mean;
     if (var < 0.0) var = 0.0;
@@ -123,18 +125,21 @@ static __global__ void conv1_bn_from_moments_kernel(const double* __restrict__ M
                                                     const float* __restrict__ gamma, const float* __restrict__ beta,
                                                     float* __restrict__ run_mean, float* __restrict__ run_var, float momentum,
                                                     float* __restrict__ scale, float* __restrict__ shift,
-                                                    float* __restrict__ save_mean, float* __restrict__ save_invstd) {
+                                                    float* __restrict__ save_mean, float* __restrict__ save_invstd,
+                                                    unsigned int* __restrict__ status) {
     const int c = threadIdx.x;
     if (c >= 32) return;
     double wk[9];
-    for (int t = 0; t < 9; ++t) wk[t] = (double)w[c * 9 + t];
+    bool ok = true;
+    for (int t = 0; t < 9; ++t) { wk[t] = (double)w[c * 9 + t]; ok = ok && sir_finite(w[c * 9 + t]); }
+    sir_flag_bn_param(ok, status);
     double sum = 0.0, sumsq = 0.0;
     for (int t = 0; t < 9; ++t) {
         sum += wk[t] * M[t];
         sumsq += wk[t] * wk[t] * M[c1_r_index(t, t)];
         for (int u = t + 1; u < 9; ++u) sumsq += 2.0 * wk[t] * wk[u] * M[c1_r_index(t, u)];
     }
-    bn_finalize_channel(sum, sumsq, count, c, gamma, beta, run_mean, run_var, momentum, scale, shift, save_mean, save_invstd);
+    bn_finalize_channel(sum, sumsq, count, c, gamma, beta, run_mean, run_var, momentum, scale, shift, save_mean, save_invstd, status);
 }
 
 // partial (sum, sumsq) [nblk][C] -> batch mean / biased var -> folded scale/shift for the forward,
@@ -145,7 +150,7 @@ static __global__ __launch_bounds__(256) void bn_finalize_kernel(const float2* _
                                                            float* __restrict__ run_mean, float* __restrict__ run_var,
                                                            float momentum, float* __restrict__ scale,
                                                            float* __restrict__ shift, float* __restrict__ save_mean,
-                                                           float* __restrict__ save_invstd) {
+                                                           float* __restrict__ save_invstd, unsigned int* __restrict__ status) {
     __shared__ double rs[256], rq[256];
     const int c = blockIdx.x, tid = threadIdx.x;
     double s = 0.0, q = 0.0;
@@ -162,7 +167,7 @@ static __global__ __launch_bounds__(256) void bn_finalize_kernel(const float2* _
         __syncthreads();
     }
     if (tid == 0)
-        bn_finalize_channel(rs[0], rq[0], count, c, gamma, beta, run_mean, run_var, momentum, scale, shift, save_mean, save_invstd);
+        bn_finalize_channel(rs[0], rq[0], count, c, gamma, beta, run_mean, run_var, momentum, scale, shift, save_mean, save_invstd, status);
 }
 
 // Frozen statistics (bnK.eval() inside a training step): the running mean / variance take the place of the batch ones in the
@@ -171,7 +176,8 @@ static __global__ __launch_bounds__(256) void bn_finalize_kernel(const float2* _
 static __global__ void bn_fold_running_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
                                               const float* __restrict__ run_mean, const float* __restrict__ run_var, int C,
                                               float* __restrict__ scale, float* __restrict__ shift,
-                                              float* __restrict__ save_mean, float* __restrict__ save_invstd) {
+                                              float* __restrict__ save_mean, float* __restrict__ save_invstd,
+                                              const float* __restrict__ w1, int n1, unsigned int* __restrict__ status) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
     const float mean = run_mean[c];
@@ -181,15 +187,23 @@ static __global__ void bn_fold_running_kernel(const float* __restrict__ gamma, c
     shift[c] = beta[c] - mean * sc;
     save_mean[c] = mean;
     save_invstd[c] = invstd;
+    bool ok = sir_finite(sc) && sir_finite(beta[c] - mean * sc);      // (w1 / n1: conv1's weights beside bn1's, as prep_bn_kernel)
+    for (int j = c; j < n1; j += C) ok = ok && sir_finite(w1[j]);
+    sir_flag_bn_param(ok, status);
 }
 
 // z (raw conv output, NHWC [B][H][W][C]) -> relu(bn(z)) -> 2x2 max-pool.
 // GRU_OUT = false: NHWC [B][Hp][Wp][C];  true: [B][Wp][C*Hp] with feature = c*Hp + py (models.py:55-57)
+// An output that is not below `limit` -- the range inside which the backward's single-accumulator f16x3 contractions take this
+// tensor exactly (a2: wgrad_wino_f16x3_kernel.h, 256; x0: gemm_tn2_f16x3_kernel.h, 512) -- raises bit 12 of the status word.
+constexpr unsigned int SIR_STATUS_ACT_RANGE = 4096u;
 template <bool GRU_OUT>
 __global__ __launch_bounds__(256) void bn_relu_pool_kernel(const float* __restrict__ z, const float* __restrict__ scale,
                                                             const float* __restrict__ shift, float* __restrict__ out,
-                                                            int B, int H, int W, int C, int Hp, int Wp) {
+                                                            int B, int H, int W, int C, int Hp, int Wp, float limit,
+                                                            unsigned int* __restrict__ status) {
     const int c4n = C / 4;
+    bool beyond = false;
     const size_t total = (size_t)B * Hp * Wp * c4n;
     for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
         int c4, px, py, b;
@@ -220,6 +234,7 @@ __global__ __launch_bounds__(256) void bn_relu_pool_kernel(const float* __restri
                 best.z = fmaxf(best.z, fmaf(v.z, s.z, t.z));
                 best.w = fmaxf(best.w, fmaf(v.w, s.w, t.w));
             }
+        beyond |= !(fmaxf(fmaxf(best.x, best.y), fmaxf(best.z, best.w)) < limit);
         if (!GRU_OUT) {
             *reinterpret_cast<float4*>(out + (((size_t)b * Hp + py) * Wp + px) * C + c4 * 4) = best;
         } else {
@@ -227,6 +242,7 @@ __global__ __launch_bounds__(256) void bn_relu_pool_kernel(const float* __restri
             o[0] = best.x; o[Hp] = best.y; o[2 * Hp] = best.z; o[3 * Hp] = best.w;
         }
     }
+    if (beyond) __hip_atomic_fetch_or(status, SIR_STATUS_ACT_RANGE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -291,7 +307,7 @@ struct PrepJobs {
     int kind[PREP_MAX_JOBS], a[PREP_MAX_JOBS], b[PREP_MAX_JOBS];
     int block0[PREP_MAX_JOBS + 1];
     int njobs;
-    unsigned int* status;        // the handle's status word (kinds 6 / 7 flag weights outside the f16x3 range)
+    unsigned int* status;        // the handle's status word (kinds 6 / 7 flag conv weights outside the f16x3 range, 0 / 8 GRU weights)
 };
 static __global__ __launch_bounds__(256) void train_prep_kernel(PrepJobs jobs) {
     int j = 0;
@@ -300,14 +316,14 @@ static __global__ __launch_bounds__(256) void train_prep_kernel(PrepJobs jobs) {
     const int idx = lb * 256 + threadIdx.x;
     const float* __restrict__ src = jobs.src[j];
     switch (jobs.kind[j]) {
-        case PREP_SPLIT2H: split2h_rows(src, jobs.a[j], (unsigned short*)jobs.dst[j], (size_t)jobs.b[j], jobs.a[j], (size_t)idx, (size_t)nb * 256); break;
+        case PREP_SPLIT2H: split2h_rows(src, jobs.a[j], (unsigned short*)jobs.dst[j], (size_t)jobs.b[j], jobs.a[j], (size_t)idx, (size_t)nb * 256, jobs.status); break;
         case PREP_CONV_W_BF16X3: prep_conv_w_bf16x3_elem(src, (unsigned short*)jobs.dst[j], jobs.a[j], jobs.b[j], idx); break;
         case PREP_CONV_WT_BF16X3: prep_conv_wT_bf16x3_elem(src, (unsigned short*)jobs.dst[j], jobs.a[j], jobs.b[j], idx); break;
         case PREP_CONV_W_WINO_BF16X3: prep_conv_w_wino_bf16x3_elem(src, (unsigned short*)jobs.dst[j], jobs.a[j], jobs.b[j], idx); break;
         case PREP_CONV_WT_WINO_BF16X3: prep_conv_wT_wino_bf16x3_elem(src, (unsigned short*)jobs.dst[j], jobs.a[j], jobs.b[j], idx); break;
         case PREP_CONV_W_WINO_F16X3: prep_conv_w_wino_f16x3_elem(src, (unsigned short*)jobs.dst[j], jobs.a[j], jobs.b[j], idx, jobs.status); break;
         case PREP_CONV_WT_WINO_F16X3: prep_conv_wT_wino_f16x3_elem(src, (unsigned short*)jobs.dst[j], jobs.a[j], jobs.b[j], idx, jobs.status); break;
-        case PREP_WHH_QUAD: prep_whh_quad_elem(src, (uint4*)jobs.dst[j], idx); break;
+        case PREP_WHH_QUAD: prep_whh_quad_elem(src, (uint4*)jobs.dst[j], idx, jobs.status); break;
         case PREP_WHH_BWD_QUAD: prep_whh_bwd_quad_elem(src, (uint4*)jobs.dst[j], idx); break;
         default: prep_whh_bwd_elem(src, (float*)jobs.dst[j], idx); break;
     }

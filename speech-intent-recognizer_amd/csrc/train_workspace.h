@@ -145,7 +145,8 @@ static inline size_t tws_slab_floats(const TDims& d, bool side) {
     X(C1M, c1m, double, C1_NMOM)                 /* conv1 input moments (conv1_moments_kernel), forward -> backward */                 \
     X(DGI1, dgi1, float, B * S * 1536)           /* gate gradients of layer 1 (TB_DGI / TB_DGH hold layer 0's): layer 1's */          \
     X(DGH1, dgh1, float, B * S * 1536)           /*   weight-gradient GEMM may run after layer 0's BPTT */                             \
-    X(SLAB2, slab2, float, tws_slab_floats(d, true))         /* GRU weight-gradient slabs when that GEMM runs on the side stream */
+    X(SLAB2, slab2, float, tws_slab_floats(d, true))         /* GRU weight-gradient slabs when that GEMM runs on the side stream */ \
+    X(BSC, bsc, float, 2 + 2 * B)                /* the backward's loss scale, pairs {scale, 1 / scale}: pair 0 the call's, pair 1 + b utterance b's */
 
 #define SIR_SLOT_ENUM(id, member, type, count) TB_##id,
 #define SIR_SLOT_OFFSET(id, member, type, count) off[TB_##id] = pos; pos += sir_align_up((size_t)(count) * sizeof(type), 256);
@@ -196,14 +197,19 @@ static inline int check_common(const char* who, sir_handle* h, const sir_model_w
 // Loss scale of the backward (a power of two, exact in fp32 both ways): head_bwd_kernel multiplies d(loss)/d(GRU output) by it and
 // every kernel that writes a PARAMETER gradient behind it multiplies by its inverse, so that the intermediate gradients -- 1e-5 to
 // 1e-7 at batch 256 unscaled -- sit around 2^-4 .. 2^4: inside fp16's normal range for the f16x3 contractions of the backward
-// (f16_split.h), with 2^10 of head room on either side.  2^8 x batch (rounded up to a power of two) makes the scaled d(logits)
-// (softmax - onehot) x 2^8 whatever the batch.  Results are bit-identical to the unscaled backward wherever the arithmetic is fp32
-// or bf16x6 (scaling by 2^k commutes with every rounding there).
-inline float sir_bwd_loss_scale(int batch) {
+// (f16_split.h).  The STATIC scale, 2^8 x batch (rounded up to a power of two), makes the scaled d(logits) (softmax - onehot) x 2^8
+// whatever the batch.  That holds for a mean cross-entropy far from convergence only: below 2^-14 the split keeps an absolute
+// 2^-36, so a batch whose softmax - onehot is 2^-24 would lose all but 8 bits.  bwd_scale_kernel (train_bwd_kernels.h) therefore
+// reads max |dlogits| at the head of every backward and writes the scale the kernels use into TB_BSC: the static one while the scaled
+// maximum stays within [2^5, 2^10), else the power of two that brings it back to [2^7, 2^8) -- any finite dlogits, 2^-24 or 2^16
+// times the usual, gives the same relative accuracy (tests/test_operand_range_gpu.py).  Results are bit-identical to the unscaled
+// backward wherever the arithmetic is fp32 or bf16x6 (scaling by 2^k commutes with every rounding there).
+inline int sir_bwd_loss_scale_exp(int batch) {
     int k = 8;
     while ((1 << (k - 8)) < batch && k < 24) ++k;
-    return (float)(1u << k);
+    return k;
 }
+inline float sir_bwd_loss_scale(int batch) { return (float)(1u << sir_bwd_loss_scale_exp(batch)); }
 
 inline int grid_for(size_t n, int per_block = 256, int cap = 8192) {
     size_t g = (n + per_block - 1) / per_block;

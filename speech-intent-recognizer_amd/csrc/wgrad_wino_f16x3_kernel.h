@@ -60,7 +60,8 @@ __device__ __forceinline__ float4 wgw_neg(const float4& x) { return make_float4(
 // dz: [B][H][W][COUT] (gradient of the raw conv output), a: [B][H][W][CIN] (the layer input), slab: [strips][4 i][4 j][COUT][CIN]
 // The products on the fp16 matrix cores (f16_split.h), as in gemm_tn2_f16x3_kernel: the transformed output
 // gradient P (it carries the backward's loss scale) as two planes (Ph, Pl'), the transformed input V scaled by 2^-5 (|V| <= 4 max |input|:
-// exact below |input| = 256, clamped beyond) as two as well (Vh, Vl'; the consumers form Vh 2^11 in registers); Pl' Vh + Ph Vl' +
+// exact below |input| = 256, saturated beyond -- conv3's input is the conv2 block output, and the training forward raises status bit 12
+// when it writes one that large; conv2's input, behind bn1, is not checked) as two as well (Vh, Vl'; the consumers form Vh 2^11 in registers); Pl' Vh + Ph Vl' +
 // Ph (Vh 2^11) into the one accumulator set, 2^-11 x 2^5 in the epilogue.  The frequency stride of the LDS images stays three planes.
 constexpr int WGW_VS_LOG2 = -5;
 template <int CIN, int COUT>
@@ -311,7 +312,8 @@ static __global__ __launch_bounds__(256) void wgrad_wino_sum_kernel(const float*
 
 // dw[co][ci][ky][kx] = (G^T dU G)[ky][kx],  dU: [4 i][4 j][co][ci];  G = (1 0 0; .5 .5 .5; .5 -.5 .5; 0 0 1)
 static __global__ __launch_bounds__(256) void wgrad_wino_finish_kernel(const float* __restrict__ du, int cin, int cout, float* __restrict__ dw,
-                                                                       float unscale) {
+                                                                       const float* __restrict__ bsc) {
+    const float unscale = bsc[1];
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;       // (co, ci), ci fastest
     const int n = cout * cin;
     if (idx >= n) return;

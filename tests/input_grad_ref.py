@@ -62,9 +62,10 @@ def device_forward_values(m, sd, x, bsz, t):
     return z, y
 
 
-def reference(sd, x, zo, yo, labels=None, target=None, bn_frozen=(False, False, False), dropout_mask=None):
+def reference(sd, x, zo, yo, labels=None, target=None, bn_frozen=(False, False, False), dropout_mask=None, dlogits=None):
     """float64: ``(out, logits, d out / d x)`` with ``out`` = mean cross-entropy against ``labels``, or the sum over the rows
-    of ``logits[b, target[b]]`` (rows are independent when every BatchNorm is frozen, the only use of ``target``)."""
+    of ``logits[b, target[b]]`` (rows are independent when every BatchNorm is frozen, the only use of ``target``), or, with
+    ``dlogits`` [B, C], ``(logits * dlogits).sum()``: the vector-Jacobian product the device computes for that upstream gradient."""
     sd64 = {k: _d(v) for k, v in sd.items()}
     zo64, yo64 = {k: _d(v) for k, v in zo.items()}, {k: _d(v) for k, v in yo.items()}
     x64 = x.detach().cpu().double().view(x.shape[0], 64, x.shape[-1]).requires_grad_()
@@ -74,7 +75,10 @@ def reference(sd, x, zo, yo, labels=None, target=None, bn_frozen=(False, False, 
         logits = model_ref.forward(sd64, x64, train=not frozen[0], dropout_mask=mask, z_override=zo64, y_override=yo64)
     else:
         logits = finetune_ref.forward(sd64, x64, frozen, None, mask, zo64, yo64)
-    out = F.cross_entropy(logits, labels) if target is None else logits.gather(1, target.view(-1, 1)).sum()
+    if dlogits is not None:
+        out = (logits * dlogits.detach().cpu().double()).sum()
+    else:
+        out = F.cross_entropy(logits, labels) if target is None else logits.gather(1, target.view(-1, 1)).sum()
     (dx,) = torch.autograd.grad(out, x64)
     return out.detach(), logits.detach(), dx
 

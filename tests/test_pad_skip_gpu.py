@@ -144,6 +144,8 @@ def test_nan_in_tail(sd):
     assert torch.equal(lg.isnan(), lgf.isnan())
     assert torch.equal(torch.nan_to_num(lg), torch.nan_to_num(lgf))
     assert torch.equal(am, amf)
+    # the NaN is data on both paths: its rows are NaN throughout (include/sir_hip.h at sir_model_infer), the others untouched
+    assert lg[[1, 5]].isnan().all() and not lg[[0, 2, 3, 4, 6, 7]].isnan().any()
 
 
 @pytest.mark.parametrize("n_streams", [2, 3])

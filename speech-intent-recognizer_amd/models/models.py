@@ -51,6 +51,29 @@ class CNNAudioGRU(nn.Module):
         self._sir_token = ops.new_model_token()
         return out
 
+    def __getstate__(self):
+        """``copy.deepcopy`` and pickling take the module without what belongs to THIS object: the pointer struct (ctypes
+        pointers cannot be copied, and would point at this object's tensors), the training step's gradient buffer and both
+        workspaces.  ``__setstate__`` gives the copy a workspace and a token of its own."""
+        state = self.__dict__.copy()
+        for k in ("_sir_wcache", "_sir_wsrc", "_sir_wptrs", "_sir_train", "_ws", "_sir_token"):
+            state.pop(k, None)
+        return state
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        self._ws = ops.Workspace()
+        self._sir_wcache = None
+        self._sir_token = ops.new_model_token()
+
+    def weights_changed(self):
+        """Tell the model that parameters or buffers were rewritten in place behind torch's back -- ``p.data.copy_(...)``,
+        ``p.data.mul_(...)``, a write through a raw pointer: no version counter moves, so the next call would reuse weight
+        layouts prepared from the old values.  (Replaced tensors and modules, in-place updates under ``torch.no_grad()``,
+        ``load_state_dict``, ``.to()`` and this package's own optimizer need no such call.)"""
+        ops.bump_weights_epoch()
+        return self
+
     def train(self, mode=True):
         """``nn.Module.train`` plus one thing: BatchNorm blocks frozen by ``sir_amd.finetune.freeze(model, {"bn_stats"})``
         go back to ``eval()`` afterwards, so that the ``model.train()`` at the top of every epoch does not silently bring

@@ -6,6 +6,7 @@ and nothing falls back to ``torch.nn`` compute.
 """
 import ctypes as C
 import itertools
+import operator
 
 import torch
 
@@ -26,55 +27,92 @@ def _f32c(t, name):
     return t
 
 
-def weights_struct(mod):
-    """sir_model_weights filled with the module's parameter/buffer pointers (reference key names)."""
-    w = _native.ModelWeights()
-    keep = []
+_WEIGHT_MODULES = ("conv1", "bn1", "conv2", "bn2", "conv3", "bn3", "gru", "attention", "fc")
 
-    def p(t, name):
-        t = _f32c(t.detach(), name)
-        keep.append(t)
-        return t.data_ptr()
 
+def _weight_slots(mod):
+    """``(sub-modules, slots)``: the nine sub-modules that own weights and, per tensor ``sir_model_weights`` points at,
+    ``(the owner's _parameters / _buffers dict, key, reference name)``.  The order is the one ``weights_struct`` fills."""
+    try:
+        mods = [mod._modules[n] for n in _WEIGHT_MODULES]
+    except KeyError as e:
+        raise _native.SirError(f"sub-module {e} is missing from the module") from None
+    slots = []
     for i in range(3):
-        conv, bn = getattr(mod, f"conv{i + 1}"), getattr(mod, f"bn{i + 1}")
-        w.conv_w[i] = p(conv.weight, f"conv{i + 1}.weight")
-        w.bn_w[i] = p(bn.weight, f"bn{i + 1}.weight")
-        w.bn_b[i] = p(bn.bias, f"bn{i + 1}.bias")
-        w.bn_mean[i] = p(bn.running_mean, f"bn{i + 1}.running_mean")
-        w.bn_var[i] = p(bn.running_var, f"bn{i + 1}.running_var")
-    for i, suf in enumerate(GRU_SUFFIXES):
-        w.gru_w_ih[i] = p(getattr(mod.gru, "weight_ih" + suf), "gru.weight_ih" + suf)
-        w.gru_w_hh[i] = p(getattr(mod.gru, "weight_hh" + suf), "gru.weight_hh" + suf)
-        w.gru_b_ih[i] = p(getattr(mod.gru, "bias_ih" + suf), "gru.bias_ih" + suf)
-        w.gru_b_hh[i] = p(getattr(mod.gru, "bias_hh" + suf), "gru.bias_hh" + suf)
-    w.attn_w = p(mod.attention.weight, "attention.weight")
-    w.attn_b = p(mod.attention.bias, "attention.bias")
-    w.fc_w = p(mod.fc.weight, "fc.weight")
-    w.fc_b = p(mod.fc.bias, "fc.bias")
-    w.num_classes = mod.fc.weight.shape[0]
+        conv, bn = mods[2 * i], mods[2 * i + 1]
+        slots.append((conv._parameters, "weight", f"conv{i + 1}.weight"))
+        slots.append((bn._parameters, "weight", f"bn{i + 1}.weight"))
+        slots.append((bn._parameters, "bias", f"bn{i + 1}.bias"))
+        slots.append((bn._buffers, "running_mean", f"bn{i + 1}.running_mean"))
+        slots.append((bn._buffers, "running_var", f"bn{i + 1}.running_var"))
+    gru = mods[6]._parameters
+    for suf in GRU_SUFFIXES:
+        for kind in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"):
+            slots.append((gru, kind + suf, "gru." + kind + suf))
+    for name, m in (("attention", mods[7]), ("fc", mods[8])):
+        slots.append((m._parameters, "weight", name + ".weight"))
+        slots.append((m._parameters, "bias", name + ".bias"))
+    return mods, slots
+
+
+def weights_struct(mod, slots=None):
+    """sir_model_weights filled with the module's parameter/buffer pointers (reference key names)."""
+    if slots is None:
+        slots = _weight_slots(mod)[1]
+    keep = []
+    for d, k, name in slots:
+        t = d.get(k)
+        if t is None:
+            raise _native.SirError(f"{name} is missing from the module")
+        keep.append(_f32c(t.detach(), name))
+    ptrs = iter([t.data_ptr() for t in keep])
+    w = _native.ModelWeights()
+    for i in range(3):
+        w.conv_w[i], w.bn_w[i], w.bn_b[i], w.bn_mean[i], w.bn_var[i] = (next(ptrs) for _ in range(5))
+    for i in range(4):
+        w.gru_w_ih[i], w.gru_w_hh[i], w.gru_b_ih[i], w.gru_b_hh[i] = (next(ptrs) for _ in range(4))
+    w.attn_w, w.attn_b, w.fc_w, w.fc_b = (next(ptrs) for _ in range(4))
+    w.num_classes = keep[-2].shape[0]
     return w, keep
 
 
 def cached_weights(mod):
-    """The pointer struct is rebuilt only when the module's storage may have moved
-    (``CNNAudioGRU._apply`` drops the cache); in-place updates keep the pointers valid."""
+    """The pointer struct and the tensors it points at, rebuilt when the module no longer holds those tensors.
+    ``CNNAudioGRU._apply`` / ``load_state_dict`` drop the cache; every other route that REPLACES a tensor -- a new head
+    (``model.fc = nn.Linear(...)``), ``nn.Parameter`` assignment, ``p.data = t``, ``vector_to_parameters``, a child's own
+    ``.cpu()`` / ``.to()`` -- is caught here, per call, by comparing the nine sub-modules and the storage addresses the module
+    holds NOW with the cached ones; the model then takes a new token, as after ``load_state_dict``.  In-place updates keep
+    the pointers valid (``weights_version`` covers those that torch counts, ``CNNAudioGRU.weights_changed`` the rest)."""
     cache = getattr(mod, "_sir_wcache", None)
-    if cache is None:
-        cache = weights_struct(mod)
-        mod._sir_wcache = cache
-        mod._sir_wptrs = None
+    if cache is not None:
+        try:
+            mods, slots = mod._sir_wsrc
+            m = mod._modules
+            if [m[n] for n in _WEIGHT_MODULES] == mods and \
+                    tuple(map(_tensor_address, [d[k] for d, k, _ in slots])) == mod._sir_wptrs:
+                return cache
+        except (AttributeError, KeyError, TypeError):    # a tensor or sub-module was removed: the rebuild below names it
+            pass
+        mod._sir_token = new_model_token()
+    mods, slots = _weight_slots(mod)
+    cache = weights_struct(mod, slots)
+    mod._sir_wcache = cache
+    mod._sir_wsrc = (mods, slots)
+    mod._sir_wptrs = tuple(t.data_ptr() for t in cache[1])
     return cache
 
 
 _weights_epoch = [1]
+_tensor_version = operator.attrgetter("_version")
+_tensor_address = torch.Tensor.data_ptr              # (unbound, mapped at C level: this runs on every model call)
 _model_tokens = itertools.count(1)
 
 
 def new_model_token():
     """Process-unique id of one set of weights: ``CNNAudioGRU`` takes one in ``__init__`` and a fresh one whenever its
-    storage or contents are replaced wholesale (``_apply``, ``load_state_dict``).  ``id(module)`` is NOT such an id: a
-    freed module's address is reused by the next one built in the same place."""
+    storage or contents are replaced wholesale (``_apply``, ``load_state_dict``, a copy of the module) or ``cached_weights``
+    finds a tensor or sub-module replaced.  ``id(module)`` is NOT such an id: a freed module's address is reused by the next
+    one built in the same place."""
     return next(_model_tokens)
 
 
@@ -97,7 +135,7 @@ def weights_version(mod, keep, workspace=None):
     if ptrs is None or len(ptrs) != len(keep):
         ptrs = mod._sir_wptrs = tuple(t.data_ptr() for t in keep)      # constant while the pointer struct is cached
     key = (_weights_epoch[0], token, workspace.generation if workspace is not None else 0,
-           tuple(t._version for t in keep), ptrs)
+           tuple(map(_tensor_version, keep)), ptrs)
     return (hash(key) & 0xFFFFFFFFFFFFFFFF) or 1
 
 

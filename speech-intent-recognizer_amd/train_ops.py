@@ -176,9 +176,13 @@ def _check_same_freeze(need, cfg, device="cuda"):
 
 
 def _train_state(mod):
+    """The module's gradient buffer and training workspace.  The buffer's views are cut for one set of parameters: it is
+    rebuilt whenever the model took a new token since (``ops.cached_weights`` -- call it first -- hands one out when a
+    parameter or sub-module was replaced, e.g. a new head with another class count), never written through stale views."""
     st = getattr(mod, "_sir_train", None)
-    if st is None or st["grads"].flat.device != next(mod.parameters()).device:
-        st = {"grads": GradBuffer(mod), "ws": ops.Workspace()}
+    token = getattr(mod, "_sir_token", None)
+    if st is None or st["token"] != token or st["grads"].flat.device != next(mod.parameters()).device:
+        st = {"grads": GradBuffer(mod), "ws": st["ws"] if st is not None else ops.Workspace(), "token": token}
         mod._sir_train = st
     return st
 
@@ -217,12 +221,12 @@ class _TrainStep(torch.autograd.Function):
         x_shape = x.shape
         x = ops._as_features(x)
         bsz, _, t = x.shape
+        w, keep = ops.cached_weights(mod)
         st = _train_state(mod)
         need = lib.sir_model_workspace_bytes(h, bsz, t, 1)
         if need == 0:
             raise _native.SirError(f"unsupported shape batch={bsz} frames={t} ({ops.SHAPE_LIMITS})")
         ws = st["ws"].get(need, x.device)
-        w, keep = ops.cached_weights(mod)
         rm, rv = _bn_ptr_arrays(mod)
         if craft:
             _scratch_running_stats(mod, st, cfg, rm, rv)
@@ -250,8 +254,8 @@ class _TrainStep(torch.autograd.Function):
         lib = _native.lib()
         mod, x = ctx.mod, ctx.x
         h = get_featurizer().handle
-        st = _train_state(mod)
         w, keep = ops.cached_weights(mod)
+        st = _train_state(mod)
         dlogits = dlogits.contiguous()
         bsz, _, t = x.shape
         grads = st["grads"]

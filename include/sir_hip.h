@@ -296,13 +296,42 @@ typedef struct sir_model_weights {
  * computation; a tail of -0.0 (or any other non-zero bits) is computed in full.  The intermediate buffers listed by
  * sir_model_workspace_offsets hold valid values only for the computed positions: past them they are left unwritten. */
 size_t sir_model_workspace_bytes(const sir_handle* h, int batch, int t_frames, int train);
-/* Byte offsets of the intermediate buffers inside the workspace, in the order
- *   0 conv1 out NHWC [B][32][T/2][32]   1 conv2 out NHWC [B][16][T/4][64]
- *   2 GRU input [B][S][1024] (feature = c*8+h, models.py:55-57)   3 input projections [B*S][1536]
- *   4 GRU layer-0 out [B][S][512]   5 GRU layer-1 out [B][S][512]   6 context [B][512]  ...
- * so that tests can check every stage against the oracle.  Returns the number of buffers. */
+/* Byte offsets of the buffers inside the inference workspace (S = t_frames / 8 GRU steps; n = B + 1: the batch and, at index B,
+ * the all-zero template utterance of the pad skip), so that tests can check every stage against the oracle:
+ *    0  a1     conv1 block output (pooled), NHWC           [n][32][T/2][32]
+ *    1  a2     conv2 block output, NHWC                    [n][16][T/4][64]
+ *    2  x0     conv3 block output = GRU layer 0 input      [n][S][1024] (feature = c*8+h, models.py:55-57)
+ *    3  gi     input projection of the running layer       [n*S][1536]
+ *    4  y0     GRU layer 0 output                          [B][S][512]
+ *    5  y1     GRU layer 1 output                          [B][S][512]
+ *    6  ctx    attention-pooled context                    [B][512]
+ *    7  pad    the int tables of the pad skip / of a ragged call: sir_model_infer_table_offsets
+ *    8  xz     the template utterance's all-zero features  [64][T]
+ *    9  bn     folded BatchNorm: scale, shift              [2][224] (bn1 | bn2 | bn3 at channels 0, 32, 96)
+ *   10  wht    W_hh as the recurrence's resident fragments, (layer, direction)
+ *   11  xs     16-bit planes of the input-projection GEMM's A operand   [2][n*S][1024]
+ *   12  ws     16-bit planes of W_ih (both layers, both directions)
+ *   13  wcb    16-bit planes of the conv2 / conv3 weights
+ *   14, 15     reserved (no bytes)
+ * Slots 0..3 and 11 hold values only for the computed positions (see above; a ragged call: the positions inside each utterance's
+ * own width); slots 4..6 are written in full by a padded call, and for t < frames[b] / 8 by a ragged one.  Slots 9, 10, 12 and 13
+ * are the prepared weights (sir_model_set_weights_version).  `train` is ignored: the training workspace has a list of its own,
+ * sir_model_train_workspace_offsets.  Needs no device and ignores h.  Returns the number of buffers (16), or SIR_EINVAL for an
+ * unsupported shape. */
 int sir_model_workspace_offsets(const sir_handle* h, int batch, int t_frames, int train,
                                 size_t* offsets, int n);
+/* The int tables inside slot 7 of the list above.  Writes up to n values: the offsets, in ints from the slot's start, of
+ *   0 e0         [B]      1 + last frame column with any bit set (a ragged call: frames[b], or 0 where that is outside [8, T])
+ *   1 d1         [B + 1]  conv1 columns computed per utterance (the template utterance last)
+ *   2 d3         [B + 1]  GRU steps of each utterance that see data (a ragged call: its own steps, frames[b] / 8)
+ *   3 rows       the layer-0 projection's row list: the count, then that many rows u * S + s, ascending
+ *   4 tab2       conv2's task list: {count, unused}, then two words per task
+ *   5 tab3       conv3's task list, likewise
+ *   6 record     {rows read, tile height chosen} of the latest row-list input projection
+ *   7 nonfinite  [B]      1 where an utterance's features hold a NaN or an infinity
+ * then (8) the slot's size in ints and (9) the slot's index in sir_model_workspace_offsets.  Needs no device and ignores h.
+ * Returns the number of values (10), or SIR_EINVAL for an unsupported shape. */
+int sir_model_infer_table_offsets(const sir_handle* h, int batch, int t_frames, size_t* offsets, int n);
 /* Optional: tell the library which version of the weights the next sir_model_infer calls will see.  The
  * derived weight layouts (bf16x3 planes, folded BatchNorm, ...) live in the caller's workspace; when the
  * version is non-zero and unchanged since the previous call with the same workspace and shape, they are

@@ -20,7 +20,7 @@ struct SirConvPlan {
     Wino2Geo geo2, geo3;                // the forward's launch geometry (batch + template utterance); the data gradients' too when there is none
 };
 
-// (plain ints only: model_infer.hip passes its extension of this struct to a kernel by value)
+// (plain ints only: the table kernels of infer_tables.h take an extension of this struct, Dims of infer_workspace.h, by value)
 struct SirDims {
     int B, T, wp1, wp2, wp3, S;         // batch, frames, map widths behind conv1 / conv2 / conv3, GRU steps
 };

@@ -6,6 +6,7 @@
 #include "model_kernels.h"       // C1_PROWS / C1_PCOLS (model_shape.h, sir_internal.h)
 #include "gemm_tn_common.h"      // TN_* tile sizes
 #include "gru_frag_prep.h"       // GRU_FRAG_BYTES
+#include "workspace_slots.h"     // the slot generators; WS_DIR* / WCB_* sub-buffer sizes, prep_blocks
 
 constexpr int C1_NMOM = 54;      // conv1 input moments (layout: train_fwd_kernels.h), forward -> backward through TB_C1M
 __host__ __device__ constexpr int c1_r_index(int t, int u) { return 9 + t * 9 - t * (t - 1) / 2 + (u - t); }   // t <= u
@@ -53,17 +54,6 @@ static inline bool make_tdims(int batch, int t, TDims* d) {
     d->kchunk = ((K + d->ksplits - 1) / d->ksplits + 31) / 32 * 32;
     return true;
 }
-
-// ---- sub-buffers of TB_WS and TB_WCB (16-bit elements) and the blocks of the prep jobs that fill them (train_prep_kernel) ----
-constexpr int prep_blocks(size_t elems, int per_block = 256) { return (int)((elems + per_block - 1) / per_block); }
-// TB_WS: f16x2 planes of W_ih, one direction = [2 planes][768][in]; a PREP_SPLIT2H block covers 2048 weights
-constexpr size_t WS_DIR0 = (size_t)2 * 768 * 1024, WS_DIR1 = (size_t)2 * 768 * 512;          // layer 0 / layer 1
-constexpr int WS_DIR0_BLOCKS = prep_blocks(768 * 1024, 2048), WS_DIR1_BLOCKS = prep_blocks(768 * 512, 2048);
-// TB_WCB: three planes of conv weights per form; one prep thread per weight of a plane
-constexpr size_t WCB_W2 = 32 * 16 * 64;        // conv2, 16 Winograd frequencies: the forward's form, and the data gradient's (64 -> 32)
-constexpr size_t WCB_W3 = 64 * 16 * 128;       // conv3 likewise (data gradient 128 -> 64)
-constexpr size_t WCB_W2_TAPS = 32 * 9 * 64;    // conv2 data gradient with 9 taps (direct fallback; written into the Winograd-sized sub-buffer)
-constexpr size_t WCB_W3_TAPS = 64 * 9 * 128;   // conv3 forward with 9 taps (direct fallback)
 
 // per-(task, tile column) statistics of the producer / consumer Winograd kernel (or per-workgroup ones of the fallback kernels), the
 // conv1 partials and the BatchNorm backward partials share TB_STATS: float2 elements
@@ -148,12 +138,8 @@ static inline size_t tws_slab_floats(const TDims& d, bool side) {
     X(SLAB2, slab2, float, tws_slab_floats(d, true))         /* GRU weight-gradient slabs when that GEMM runs on the side stream */ \
     X(BSC, bsc, float, 2 + 2 * B)                /* the backward's loss scale, pairs {scale, 1 / scale}: pair 0 the call's, pair 1 + b utterance b's */
 
-#define SIR_SLOT_ENUM(id, member, type, count) TB_##id,
-#define SIR_SLOT_OFFSET(id, member, type, count) off[TB_##id] = pos; pos += sir_align_up((size_t)(count) * sizeof(type), 256);
-#define SIR_SLOT_MEMBER(id, member, type, count) type* member;
-#define SIR_SLOT_CARVE(id, member, type, count) p.member = (type*)(b + off[TB_##id]);
-
-enum TrainBuf { SIR_TRAIN_SLOTS(SIR_SLOT_ENUM) TB_COUNT };
+#define SIR_TRAIN_SLOT_ENUM(id, member, type, count) TB_##id,
+enum TrainBuf { SIR_TRAIN_SLOTS(SIR_TRAIN_SLOT_ENUM) TB_COUNT };
 
 // byte offset of every slot; returns the workspace size
 static inline size_t tws_layout(const TDims& d, size_t* off) {

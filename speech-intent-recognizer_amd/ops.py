@@ -288,35 +288,36 @@ def stage_views(ws, bsz, t):
     return out
 
 
+_PAD_TABLES = ("e0", "d1", "d3", "rows", "tab2", "tab3", "record", "nonfinite")
+
+
 def _pad_table_offsets(bsz, t):
-    """int offsets inside WS_PAD (PadTabs in csrc/model_infer.hip) and the byte offset of WS_PAD in the workspace"""
+    """``sir_model_infer_table_offsets`` (include/sir_hip.h) as a dict: the int offset of every pad-skip table inside its workspace
+    slot, ``ints`` (the slot's size) and ``base`` (the slot's byte offset in the workspace)"""
     lib = _native.lib()
-    offs = (C.c_size_t * 16)()
-    if lib.sir_model_workspace_offsets(get_featurizer().handle, bsz, t, 0, offs, 16) <= 7:
+    vals, offs = (C.c_size_t * 10)(), (C.c_size_t * 16)()
+    if lib.sir_model_infer_table_offsets(None, bsz, t, vals, 10) != 10:
+        raise _native.SirError("sir_model_infer_table_offsets failed")
+    if lib.sir_model_workspace_offsets(None, bsz, t, 0, offs, 16) <= vals[9]:
         raise _native.SirError("sir_model_workspace_offsets failed")
-    wp1, wp2 = t // 2, t // 4
-    k2max, k3max = ((wp1 + 1) // 2 + 3) // 4, ((wp2 + 1) // 2 + 3) // 4
-    n = bsz + 1
-    o_d3 = bsz + n
-    o_rows = o_d3 + n + 1 + n * k2max + 1 + n * k3max
-    o_tab2 = o_rows + 1 + n * (wp2 // 2)
-    o_tab2 += o_tab2 & 1
-    o_tab3 = o_tab2 + 2 + 2 * n * k2max
-    o_end = o_tab3 + 2 + 2 * n * k3max
-    return offs[7], o_d3, o_tab2, o_tab3, o_end
+    out = dict(zip(_PAD_TABLES + ("ints",), vals))
+    out["base"] = offs[vals[9]]
+    return out
 
 
 def pad_skip_tables(ws, bsz, t):
-    """The pad-skip tables the last padded ``model_infer`` call on ``ws`` left (csrc/model_infer.hip, WS_PAD), on the host:
-    ``e0`` [B], ``d3`` [B + 1] (the template utterance last) and the conv2 / conv3 task lists (``Wino2Geo::ctab`` in
-    csrc/wino2_geo.h) as int32 arrays ``tab2`` / ``tab3`` of shape [n, 2]: the two words of each listed task."""
-    base, o_d3, o_tab2, o_tab3, o_end = _pad_table_offsets(bsz, t)
+    """The pad-skip tables the last padded ``model_infer`` call on ``ws`` left (csrc/infer_tables.h), on the host: ``e0`` [B],
+    ``d1`` and ``d3`` [B + 1] (the template utterance last), ``nonfinite`` [B], ``rows`` (the listed rows of the layer-0 projection,
+    by the count word) and the conv2 / conv3 task lists (``Wino2Geo::ctab`` in csrc/wino2_geo.h) as int32 arrays ``tab2`` / ``tab3``
+    of shape [n, 2]: the two words of each listed task."""
+    o = _pad_table_offsets(bsz, t)
     n = bsz + 1
-    tab = ws[base: base + 4 * o_end].view(torch.int32).cpu()
-    out = {"e0": tab[:bsz], "d3": tab[o_d3: o_d3 + n]}
-    for name, o in (("tab2", o_tab2), ("tab3", o_tab3)):
-        cnt = int(tab[o])
-        out[name] = tab[o + 2: o + 2 + 2 * cnt].view(cnt, 2)
+    tab = ws[o["base"]: o["base"] + 4 * o["ints"]].view(torch.int32).cpu()
+    out = {name: tab[o[name]: o[name] + cnt] for name, cnt in (("e0", bsz), ("d1", n), ("d3", n), ("nonfinite", bsz))}
+    out["rows"] = tab[o["rows"] + 1: o["rows"] + 1 + int(tab[o["rows"]])]
+    for name in ("tab2", "tab3"):
+        cnt = int(tab[o[name]])
+        out[name] = tab[o[name] + 2: o[name] + 2 + 2 * cnt].view(cnt, 2)
     return out
 
 
@@ -324,6 +325,6 @@ def proj_tile_record(ws, bsz, t):
     """What the latest row-list input projection of a ``model_infer`` call on ``ws`` read and chose (two ints behind the pad-skip
     tables, written by workgroup 0 of ``gemm_nt_f16x3_gather_kernel``): ``(rows, tile)`` -- the listed row count and the tile
     height, 96 / 128 / 160 rows.  A padded call leaves layer 0's record, a ragged call layer 1's (K = 512, the same row list)."""
-    base, _, _, _, o_end = _pad_table_offsets(bsz, t)
-    rec = ws[base + 4 * o_end: base + 4 * o_end + 8].view(torch.int32).cpu()
+    o = _pad_table_offsets(bsz, t)
+    rec = ws[o["base"] + 4 * o["record"]: o["base"] + 4 * o["record"] + 8].view(torch.int32).cpu()
     return int(rec[0]), int(rec[1])

@@ -61,7 +61,7 @@ def _neg_tail(x):
 
 
 def _d1(e0, t_pad):
-    """conv1 columns an utterance of extent e0 demands: the formulas at the head of csrc/model_infer.hip, on the host"""
+    """conv1 columns an utterance of extent e0 demands: the formulas at the head of csrc/infer_tables.h, on the host"""
     wp1, wp2 = t_pad // 2, t_pad // 4
     s = wp2 // 2
     d3 = min(s, (e0 + 14) // 8)

@@ -23,7 +23,7 @@ def model():
 
 
 def _frames_for_d3(v):
-    """real frames E0 of an utterance whose GRU steps s < v see data: v = min(S, (E0 + 14) // 8) (head of csrc/model_infer.hip).
+    """real frames E0 of an utterance whose GRU steps s < v see data: v = min(S, (E0 + 14) // 8) (head of csrc/infer_tables.h).
     An empty utterance (E0 = 0) has v = 1 as well: conv3 column 0 sees no data then, but it is listed all the same."""
     return 1 if v == 1 else T if v == S else 8 * v - 11
 

@@ -1,10 +1,8 @@
-"""Layer-0 input projection over a row list (csrc/model_infer.hip, f16x3_kernels.h): with the pad skip on, the projection
+"""Layer-0 input projection over a row list (csrc/model_infer.hip, infer_tables.h, f16x3_kernels.h): with the pad skip on, the projection
 computes only the rows the layer-0 recurrence reads (steps s < d3 of every utterance and the template utterance's S rows), on
 a 96-, 128- or 160-row tile chosen on the device from the real row count.  Every output element keeps the dense kernel's MFMA
 sequence, so logits stay bit-identical to the full path, which the same features with -0.0 tails force.  The workspace starts
 as 0xFF (NaN bits): a listed row left unwritten would surface as NaN."""
-import ctypes as C
-
 import pytest
 import torch
 
@@ -14,7 +12,6 @@ from sir_amd.models.models import CNNAudioGRU
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-WS_PAD = 7                                                            # WsBuf index of the pad-skip tables
 
 
 @pytest.fixture(scope="module")
@@ -43,21 +40,6 @@ def _neg_tail(x):
     return torch.where(tail, torch.full_like(x, -0.0), x)
 
 
-def _pad_tables(ws, bsz, t):
-    """(d3 [B + 1], row list) read back from the workspace (layout: PadTabs in model_infer.hip)"""
-    offs = (C.c_size_t * 16)()
-    assert ops._native.lib().sir_model_workspace_offsets(get_featurizer().handle, bsz, t, 0, offs, 16) > WS_PAD
-    wp1, wp2 = t // 2, t // 4
-    s = wp2 // 2
-    k2max, k3max = ((wp1 + 1) // 2 + 3) // 4, ((wp2 + 1) // 2 + 3) // 4
-    n = bsz + 1
-    tab = ws[offs[WS_PAD]:].view(torch.int32)
-    d3 = tab[2 * bsz + 1: 2 * bsz + 1 + n]
-    rows = 2 * bsz + 1 + n + 1 + n * k2max + 1 + n * k3max
-    count = int(tab[rows])
-    return d3.cpu(), tab[rows + 1: rows + 1 + count].cpu(), s
-
-
 def _tile(count, ncu, n_tiles=6):
     """the tile the row-list kernel picks: the smallest whose workgroups fit one per CU, else 160 rows"""
     for bm in (96, 128):
@@ -74,7 +56,8 @@ def _check(model, d3, t=200, seed=0):
     lg, am = ops.model_infer(model, x, ws, want_argmax=True)
     lgf, amf = ops.model_infer(model, _neg_tail(x), ops.Workspace(), want_argmax=True)
     torch.cuda.synchronize()
-    d3w, rows, s = _pad_tables(ws.buf, bsz, t)
+    tabs, s = ops.pad_skip_tables(ws.buf, bsz, t), t // 8
+    d3w, rows = tabs["d3"], tabs["rows"]
     want = [u * s + k for u in range(bsz + 1) for k in range(int(d3w[u]))]
     assert d3w[:bsz].tolist() == list(d3) and int(d3w[bsz]) == s
     assert rows.tolist() == want
@@ -122,3 +105,22 @@ def test_tile_switch_boundaries(model, bm):
         d3 = [base + 1] * extra + [base] * (bsz - extra)
         assert _check(model, d3, seed=count) == count
     assert _tile(edge, ncu) == bm and _tile(edge + 1, ncu) > bm
+
+
+def test_published_tables_d1_rows_nonfinite(model):
+    """the tables ops.pad_skip_tables reads through sir_model_infer_table_offsets, after a padded call: conv1 columns d1 from d3
+    (formulas at the head of csrc/infer_tables.h; the template at full width), the row list with the template's rows last, and the
+    non-finite flags -- one inf inside utterance 1's data"""
+    t, d3 = 24, [3, 1, 2]
+    bsz, s, wp1, wp2 = len(d3), t // 8, t // 2, t // 4
+    x = _feats_d3(d3, t)
+    x[1, 5, 0] = float("inf")
+    ws = ops.Workspace()
+    ws.get(ops._native.lib().sir_model_workspace_bytes(get_featurizer().handle, bsz, t, 0), x.device).fill_(0xFF)
+    ops.model_infer(model, x, ws)
+    torch.cuda.synchronize()
+    tabs = ops.pad_skip_tables(ws.buf, bsz, t)
+    assert tabs["d3"].tolist() == d3 + [s]
+    assert tabs["d1"].tolist() == [min(wp1, 2 * min(wp2, 2 * d + 1) + 1) for d in d3] + [wp1]
+    assert tabs["rows"].tolist() == [u * s + k for u, d in enumerate(d3 + [s]) for k in range(d)]
+    assert tabs["nonfinite"].tolist() == [0, 1, 0]

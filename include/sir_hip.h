@@ -338,7 +338,10 @@ int sir_model_infer_table_offsets(const sir_handle* h, int batch, int t_frames, 
  * reused instead of rebuilt (~40 us per call).  0 (the default) = always rebuild. */
 int sir_model_set_weights_version(sir_handle* h, uint64_t version);
 /* Batch regimes (256 CUs): the GRU recurrences hold half the chip at batch 256 and all of it at 512; beyond that they are oversubscribed and rest
- * on in-order dispatch.  Tested against the oracle up to batch 1041 (tests/test_large_batch_gpu.py); batches above 1100 are untested.
+ * on in-order dispatch.  Tested against the oracle up to batch 1041 (tests/test_large_batch_gpu.py).  Token range: the training step is
+ * tested against the float64 oracle from 1 token (batch 1 of 8 frames; token count = batch * (t_frames / 8)) to 10240 tokens (batch 405 of
+ * 200 frames, batch 40 of 2048), dense and ragged inference at every length from 8 to 17 frames, 23, 24 and 31
+ * (tests/test_token_range_gpu.py).  Untested: token counts above 10240 in training, and batches above 1100.
  * Sequence regimes: 8 <= t_frames <= 2055 on every model entry point, inference and training alike (a shape outside it, or a batch above
  * 65535, is SIR_EINVAL; sir_model_workspace_bytes returns 0).  The GRU runs S = t_frames / 8 steps and the attention kernels hold one
  * score per step in LDS arrays of 256, which is what limits the range: 2055 frames are 256 steps -- 20 s at a 10 ms hop, 65 s at the default
@@ -574,7 +577,9 @@ typedef struct sir_model_grads {
  * sir_model_train_bwd.
  * Operand limits, non-finite features and weights: the paragraph at sir_model_infer (status bits 3, 11, 12, 13).
  * Batch regimes as at sir_model_infer (half chip at 256, full chip at 512, oversubscribed beyond); the step is tested against the float64
- * oracle at batches 257, 512, 528 and 1041 of 24 frames.  Untested: token counts batch * (t_frames / 8) above 6400, and batches above 1100. */
+ * oracle at batches 257, 512, 528 and 1041 of 24 frames, and from 1 token (batch 1 of 8 frames; token count = batch * (t_frames / 8)) to
+ * 10240 tokens (batch 405 of 200 frames, batch 40 of 2048: tests/test_token_range_gpu.py).  Untested: token counts above 10240, and
+ * batches above 1100. */
 int sir_model_train_fwd(sir_handle* h, const sir_model_weights* w, float* const bn_running_mean[3],
                         float* const bn_running_var[3], const float* feats, int batch, int t_frames,
                         float bn_momentum, float dropout_p, uint64_t dropout_seed, float* logits,

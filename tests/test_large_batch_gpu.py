@@ -25,7 +25,7 @@ map = block-to-cluster map of the recurrences (x8: the multiple-of-8 form, plain
 Both sides of every threshold a batch <= 1100 reaches at t = 24 are in the table: ksplits 2 | 8 (1 at B = 8 / 16),
 dx_splitk of layer 0 off (257) | on (512 ...) and of layer 1 off (... 528) | on (1024, 1041), conv3's statistics blocks
 uncapped (257) | capped, nsplit and the strips below their caps at B = 8 / 16 and at them above.  dx_splitk's upper
-ends (160 tiles: B >= 1665 / 3329) lie beyond 1100.  Inference runs B = 512, 528, 1024, 1041; training 257, 512, 528, 1041.
+ends (160 tiles: B >= 1665 / 3329) lie beyond 1100 (test_token_range_gpu.py crosses them at t = 200 and t = 2048).  Inference runs B = 512, 528, 1024, 1041; training 257, 512, 528, 1041.
 ce_loss_kernel's second trip needs B > 256, fc_wgrad_block's second chunk B > 1024 (1041 = 1024 + 2 * 8 + 1: the unrolled
 body and the scalar tail behind it).
 

@@ -1,9 +1,10 @@
 """Shared pieces of the training-step parity tests (``test_train_gpu.py``, ``test_large_batch_gpu.py``,
-``test_long_sequence_gpu.py``): views of the step's workspace slots, the values the device's ReLU / max-pool compared (reproduced
+``test_long_sequence_gpu.py``, ``test_token_range_gpu.py``): views of the step's workspace slots, the values the device's ReLU / max-pool compared (reproduced
 bit for bit on the host), the float64 oracle differentiated at those values, and the per-tensor gradient error.  Moved here
 unchanged from ``test_train_gpu.py``, whose module docstring gives the method and the bounds.  ``_training_case`` is the whole
 check of one step at a batch size and a frame count, moved here from ``test_large_batch_gpu.py``."""
 import ctypes as C
+import time
 
 import numpy as np
 import torch
@@ -107,7 +108,7 @@ def _grad_errors(m, ref_grads):
     return out
 
 
-def _training_case(sd, bsz, t, dropout=0.0, want_dx=False, compare_f32=True, norm_atol=None):
+def _training_case(sd, bsz, t, dropout=0.0, want_dx=False, compare_f32=True, norm_atol=None, oracle_time=False):
     """One training step of ``bsz`` clips of ``t`` frames against the float64 oracle differentiated at the device's own z / y
     values: loss 2e-5, logits 5e-5, all 29 gradients and the five intermediate gradients of the workspace (divided by the loss
     scale) max |a - b| <= 2e-3 * rms, norms within 1e-3, BN running statistics rtol 1e-4, the input gradient (``want_dx``)
@@ -116,7 +117,9 @@ def _training_case(sd, bsz, t, dropout=0.0, want_dx=False, compare_f32=True, nor
     before it asserts.  (``test_large_batch_gpu.py``'s, with the frame count as a parameter.)  ``norm_atol`` {parameter name:
     absolute term of that tensor's norm bound in place of 1e-7} is for a gradient that is zero in exact arithmetic, where the
     float32 oracle's own rounding noise exceeds 1e-7 at a shape (the caller's docstring gives both figures); the device's, the
-    float32 oracle's and the float64 oracle's values of such a tensor are printed."""
+    float32 oracle's and the float64 oracle's values of such a tensor are printed.  ``oracle_time`` prints the CPU seconds of the
+    host reproduction of z / y and of the float64 oracle.  Returns the model, its 29 gradients in place, for what a caller
+    asserts on top (``test_token_range_gpu.py``: exact zeros)."""
     T, S = t, t // 8
     x = cases.varied_features(bsz, T, seed=3000 + bsz)
     y = synth.synth_labels(bsz, 31, seed=3001 + bsz)
@@ -143,10 +146,14 @@ def _training_case(sd, bsz, t, dropout=0.0, want_dx=False, compare_f32=True, nor
         y0d = ws[offs[9]: offs[9] + 4 * n].view(torch.float32).view(bsz, S, 512).cpu()
         assert torch.equal(y0d, torch.where(keep, y0 * (1.0 / (1.0 - dropout)), torch.zeros_like(y0)))
         mask = keep.float() / (1.0 - dropout)
+    t0 = time.perf_counter()
     v = _views(m, bsz, T)
     zo, yo = _device_forward_values(m, sd, x, bsz, T, v)
+    t1 = time.perf_counter()
     st = {}
     ref_loss, ref_grads, ref_stats, ref_logits = _oracle_f64(sd, x, y, zo, yo, dropout_mask=mask, stages=st)
+    if oracle_time:
+        print(f"B={bsz} T={T}: host z / y {t1 - t0:.1f} s, float64 oracle {time.perf_counter() - t1:.1f} s on {torch.get_num_threads()} threads")
     # the float32 oracle's own distance from the float64 one at the same forward values (printed, not asserted)
     if compare_f32:
         _, g32, _, _ = model_ref.loss_and_grads(sd, x, y, dropout_mask=mask, z_override=zo, y_override=yo)
@@ -190,3 +197,4 @@ def _training_case(sd, bsz, t, dropout=0.0, want_dx=False, compare_f32=True, nor
         assert xd.grad.shape == xd.shape
         assert r <= input_grad_ref.GRAD_BOUND
     ops.check_status()
+    return m

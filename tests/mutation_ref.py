@@ -71,9 +71,9 @@ def _new(model, key, dev):
     return mutated(key, tensor_of(model, key).detach().cpu()).to(dev)
 
 
-def swap_head(model, dev):
-    head = synth.synth_state_dict(NEW_CLASSES, seed=3)
-    fc = nn.Linear(512, NEW_CLASSES)
+def swap_head(model, dev, num_classes=NEW_CLASSES):
+    head = synth.synth_state_dict(num_classes, seed=3)
+    fc = nn.Linear(512, num_classes)
     with torch.no_grad():
         fc.weight.copy_(head["fc.weight"])
         fc.bias.copy_(head["fc.bias"])

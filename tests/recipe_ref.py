@@ -34,6 +34,26 @@ def soft_ce(logits, ya, yb=None, lam=None, eps=0.0):
     return loss, dlogits
 
 
+def loss_case(bsz, ncls, second, seed):
+    """The seeded case of the loss comparisons (tests/test_recipe_gpu.py, tests/test_class_count_gpu.py): logits 3 * randn,
+    labels, with ``second`` a second label and a weight per row (0 in row 0, 1 in row 1, both labels on one class in row 3); rows
+    2 and B - 1 are ignored, and the second label of an ignored row is invalid because it is not read."""
+    g = torch.Generator().manual_seed(seed)
+    logits = torch.randn(bsz, ncls, generator=g) * 3.0
+    ya = torch.randint(0, ncls, (bsz,), generator=g)
+    yb = lam = None
+    if second:
+        yb = torch.randint(0, ncls, (bsz,), generator=g)
+        lam = torch.rand(bsz, generator=g)
+        lam[0], lam[1] = 0.0, 1.0
+        yb[3] = ya[3]                                  # both labels on one class
+    ya[2] = IGNORE                                     # ignored rows (their second label is not read: make it invalid)
+    ya[bsz - 1] = IGNORE
+    if second:
+        yb[2] = 10 ** 6
+    return logits, ya, yb, lam
+
+
 def mix(x, perm, lam, complement=None):
     """lam[b] x[b] + (1 - lam[b]) x[perm[b]] in float64.  ``complement`` (one value per row) replaces the real-number
     1 - lam[b], e.g. by the fp32 difference ``1.0f - lam`` the kernel forms."""

@@ -182,7 +182,8 @@ def _assert_state(got, want, what=""):
     assert (got["bin_conf_sum"][~occ] == 0).all()
 
 
-@pytest.mark.parametrize("c,n_bins,beta", [(31, 15, None), (31, 64, 0.5), (64, 1, 3.0), (2, 15, None), (1, 15, None)])
+@pytest.mark.parametrize("c,n_bins,beta", [(31, 15, None), (31, 64, 0.5), (64, 1, 3.0), (2, 15, None), (1, 15, None), (32, 15, None),
+                                           (33, 15, None)])
 def test_eval_accumulate_three_updates_match_one_reference_pass(c, n_bins, beta):
     parts = [_eval_batch(b, c, n_bins, beta, seed=31 * b + c) for b in (63, 1, 257)]
     acc = metrics.EvalAccumulator(c, n_bins=n_bins, inv_temperature=beta)

@@ -39,21 +39,7 @@ def _model(sd, dropout=0.0):
 
 
 # ---- 1. loss ---------------------------------------------------------------------------------------------------------
-def _loss_case(bsz, ncls, second, seed):
-    g = torch.Generator().manual_seed(seed)
-    logits = torch.randn(bsz, ncls, generator=g) * 3.0
-    ya = torch.randint(0, ncls, (bsz,), generator=g)
-    yb = lam = None
-    if second:
-        yb = torch.randint(0, ncls, (bsz,), generator=g)
-        lam = torch.rand(bsz, generator=g)
-        lam[0], lam[1] = 0.0, 1.0
-        yb[3] = ya[3]                                  # both labels on one class
-    ya[2] = -100                                       # ignored rows (their second label is not read: make it invalid)
-    ya[bsz - 1] = -100
-    if second:
-        yb[2] = 10 ** 6
-    return logits, ya, yb, lam
+_loss_case = recipe_ref.loss_case
 
 
 def _dev(t):

@@ -1,5 +1,5 @@
 """Shared pieces of the training-step parity tests (``test_train_gpu.py``, ``test_large_batch_gpu.py``,
-``test_long_sequence_gpu.py``, ``test_token_range_gpu.py``): views of the step's workspace slots, the values the device's ReLU / max-pool compared (reproduced
+``test_long_sequence_gpu.py``, ``test_token_range_gpu.py``, ``test_class_count_gpu.py``): views of the step's workspace slots, the values the device's ReLU / max-pool compared (reproduced
 bit for bit on the host), the float64 oracle differentiated at those values, and the per-tensor gradient error.  Moved here
 unchanged from ``test_train_gpu.py``, whose module docstring gives the method and the bounds.  ``_training_case`` is the whole
 check of one step at a batch size and a frame count, moved here from ``test_large_batch_gpu.py``."""
@@ -108,7 +108,8 @@ def _grad_errors(m, ref_grads):
     return out
 
 
-def _training_case(sd, bsz, t, dropout=0.0, want_dx=False, compare_f32=True, norm_atol=None, oracle_time=False):
+def _training_case(sd, bsz, t, dropout=0.0, want_dx=False, compare_f32=True, norm_atol=None, oracle_time=False, num_classes=31,
+                   labels=None, out=None):
     """One training step of ``bsz`` clips of ``t`` frames against the float64 oracle differentiated at the device's own z / y
     values: loss 2e-5, logits 5e-5, all 29 gradients and the five intermediate gradients of the workspace (divided by the loss
     scale) max |a - b| <= 2e-3 * rms, norms within 1e-3, BN running statistics rtol 1e-4, the input gradient (``want_dx``)
@@ -118,12 +119,15 @@ def _training_case(sd, bsz, t, dropout=0.0, want_dx=False, compare_f32=True, nor
     absolute term of that tensor's norm bound in place of 1e-7} is for a gradient that is zero in exact arithmetic, where the
     float32 oracle's own rounding noise exceeds 1e-7 at a shape (the caller's docstring gives both figures); the device's, the
     float32 oracle's and the float64 oracle's values of such a tensor are printed.  ``oracle_time`` prints the CPU seconds of the
-    host reproduction of z / y and of the float64 oracle.  Returns the model, its 29 gradients in place, for what a caller
-    asserts on top (``test_token_range_gpu.py``: exact zeros)."""
+    host reproduction of z / y and of the float64 oracle.  ``num_classes`` is the head's size (``sd`` must hold such a head);
+    ``labels`` [bsz] replaces the drawn ``synth.synth_labels(bsz, num_classes, ...)``.  Returns the model, its 29 gradients in
+    place, for what a caller asserts on top (``test_token_range_gpu.py``: exact zeros); ``out`` (a dict) receives the float64
+    oracle's gradients (``ref_grads``) and the printed figures (``test_class_count_gpu.py``: the classifier's gradient row by
+    row)."""
     T, S = t, t // 8
     x = cases.varied_features(bsz, T, seed=3000 + bsz)
-    y = synth.synth_labels(bsz, 31, seed=3001 + bsz)
-    m = CNNAudioGRU(31)
+    y = synth.synth_labels(bsz, num_classes, seed=3001 + bsz) if labels is None else labels
+    m = CNNAudioGRU(num_classes)
     m.load_state_dict(sd)
     m = m.to(DEV).train()
     m.gru.dropout = dropout
@@ -196,5 +200,8 @@ def _training_case(sd, bsz, t, dropout=0.0, want_dx=False, compare_f32=True, nor
         print(f"B={bsz}: max|dfeats - ref| / rms(ref) = {r:.2e}")
         assert xd.grad.shape == xd.shape
         assert r <= input_grad_ref.GRAD_BOUND
+    if out is not None:
+        out.update(ref_grads=ref_grads, loss=lerr, logits=gerr_logits, grad=max(gerr.values()), norm=max(nerr.values()),
+                   stage=max(serr.values()), dx=r if want_dx else None)
     ops.check_status()
     return m

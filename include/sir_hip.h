@@ -341,9 +341,18 @@ int sir_model_set_weights_version(sir_handle* h, uint64_t version);
  * on in-order dispatch.  Tested against the oracle up to batch 1041 (tests/test_large_batch_gpu.py).  Token range: the training step is
  * tested against the float64 oracle from 1 token (batch 1 of 8 frames; token count = batch * (t_frames / 8)) to 10240 tokens (batch 405 of
  * 200 frames, batch 40 of 2048), dense and ragged inference at every length from 8 to 17 frames, 23, 24 and 31
- * (tests/test_token_range_gpu.py).  Untested: token counts above 10240 in training, and batches above 1100.
+ * (tests/test_token_range_gpu.py).  One step runs at batch 2048 of 256 frames (65536 tokens), the first shape at which the conv plan
+ * picks a fallback kernel by itself -- conv2's nine-tap weight gradient: that gradient is checked against a float64 contraction of the
+ * step's own operands, loss and all 29 gradients are finite and no recurrence times out (tests/test_conv_fallback_gpu.py).  Untested
+ * against the oracle of the whole step: token counts above 10240 in training, and batches above 1100.
  * Sequence regimes: 8 <= t_frames <= 2055 on every model entry point, inference and training alike (a shape outside it, or a batch above
- * 65535, is SIR_EINVAL; sir_model_workspace_bytes returns 0).  The GRU runs S = t_frames / 8 steps and the attention kernels hold one
+ * 65535, is SIR_EINVAL; sir_model_workspace_bytes returns 0), with ONE exception, in the training backward: the conv2 / conv3 weight
+ * gradient is SIR_EUNSUPPORTED when batch * t_frames >= 524288 with t_frames >= 258 (conv2; e.g. batch 256 of 2048 frames, 512 of 1024);
+ * for conv3 from batch * t_frames >= 1048576 with t_frames >= 260.  Beyond those products a stage's dz no longer fits the 32-bit byte
+ * offsets of the Winograd weight-gradient kernel, and the nine-tap kernel that takes over holds one map row of at most 128 (conv2) / 64
+ * (conv3) columns.  sir_model_train_bwd, _part (either half), _cfg and _x refuse such a call before anything is launched and write
+ * nothing; with that conv weight's gradient pointer NULL (frozen) the call runs.  The forward and inference have no such limit
+ * (tests/test_conv_fallback_gpu.py).  The GRU runs S = t_frames / 8 steps and the attention kernels hold one
  * score per step in LDS arrays of 256, which is what limits the range: 2055 frames are 256 steps -- 20 s at a 10 ms hop, 65 s at the default
  * 32 ms one.  The step field of a recurrence exchange tag (9 bits, step + 1) ends there as well.  Tested against the oracle up to 2055 frames
  * (tests/test_long_sequence_gpu.py), at batches up to 17 in inference and up to 8 in training.
@@ -360,7 +369,10 @@ int sir_model_set_weights_version(sir_handle* h, uint64_t version);
  *              training forward with bn_frozen[0] (a frozen-statistics fine-tune, sir_amd.explain): the features are NOT looked at;
  *              a non-finite feature gives finite, meaningless logits and loss there.
  *   conv2 / conv3 weights   a transformed weight U = G g G^T with |U| >= 32, or not finite: status bit 3 (SIR_EINVAL at the next
- *              sir_check_status); the outputs are computed from the clamped value.  Below 32 the planes are exact.
+ *              sir_check_status); the outputs are computed from the clamped value.  Below 32 the planes are exact.  That is the fp16
+ *              planes' limit: a stage on its shape fallback (bf16x3 planes, fp32's exponent range) raises no bit for a finite |U| >= 32
+ *              and computes from the exact value -- at U = 40 logits and all 29 gradients hold their float64 bounds
+ *              (tests/test_conv_fallback_gpu.py); which kernels a shape gets is the library's choice, so keep |U| < 32.
  *   GRU weight_ih / weight_hh   an element beyond +-65504 or not finite: status bit 11 (SIR_EINVAL); outputs from the clamped value.
  *   attention, fc   used in fp32 behind the last ReLU: a non-finite value comes out where torch has it (a NaN in fc.weight[j][.]
  *              makes exactly logit column j NaN).
@@ -375,6 +387,9 @@ int sir_model_set_weights_version(sir_handle* h, uint64_t version);
  *              against float64.  The forward does not know what the backward will be asked for, so the bit is raised whatever
  *              follows: logits, loss and the input gradient (sir_model_train_bwd_x) do not read these operands and stay valid.
  *              The conv1 block output feeds the conv2 weight gradient under the same limit of 256 and is NOT checked.
+ *              Bit 12 is raised on the shape fallbacks too, whatever the conv plan: with conv3's weight gradient on the nine-tap bf16x6
+ *              kernel a conv2 block output of 300 leaves all 29 gradients inside their float64 bounds (conv3.weight 1.2e-4 * rms,
+ *              against 0.33 * rms from the clamped value on the Winograd kernel), and the bit is then a false alarm for that call.
  *   dlogits    sir_model_train_bwd* accepts any finite magnitude: one small kernel picks the backward's internal power-of-two scale
  *              from max |dlogits| (workspace slot 39), so gradients are as accurate at (softmax - onehot) ~ 2^-24 as at ~ 1, and a
  *              scaled loss (dlogits x 2^16) does not saturate.  A NaN / infinite dlogits makes the fc gradients (fp32, straight from
@@ -578,8 +593,11 @@ typedef struct sir_model_grads {
  * Operand limits, non-finite features and weights: the paragraph at sir_model_infer (status bits 3, 11, 12, 13).
  * Batch regimes as at sir_model_infer (half chip at 256, full chip at 512, oversubscribed beyond); the step is tested against the float64
  * oracle at batches 257, 512, 528 and 1041 of 24 frames, and from 1 token (batch 1 of 8 frames; token count = batch * (t_frames / 8)) to
- * 10240 tokens (batch 405 of 200 frames, batch 40 of 2048: tests/test_token_range_gpu.py).  Untested: token counts above 10240, and
- * batches above 1100. */
+ * 10240 tokens (batch 405 of 200 frames, batch 40 of 2048: tests/test_token_range_gpu.py).  Batch 2048 of 256 frames runs with a clean
+ * status word, finite results and conv2's weight gradient (there on the nine-tap fallback) checked on its own
+ * (tests/test_conv_fallback_gpu.py).  Untested against the oracle of the whole step: token counts above 10240, and batches above 1100.
+ * The backward's one shape limit inside the accepted range -- the conv2 / conv3 weight gradient of a long sequence in a very large
+ * batch -- is stated at "Sequence regimes" (sir_model_infer). */
 int sir_model_train_fwd(sir_handle* h, const sir_model_weights* w, float* const bn_running_mean[3],
                         float* const bn_running_var[3], const float* feats, int batch, int t_frames,
                         float bn_momentum, float dropout_p, uint64_t dropout_seed, float* logits,
@@ -608,7 +626,9 @@ int sir_ce_loss_soft(sir_handle* h, const float* logits, const int64_t* labels_a
                      void* stream);
 
 /* loss.backward() (train.py:106): all 29 parameter gradients from dlogits and the saved workspace.  dlogits may have any finite
- * magnitude (the internal loss scale follows max |dlogits|: slot 39 below, and the paragraph at sir_model_infer). */
+ * magnitude (the internal loss scale follows max |dlogits|: slot 39 below, and the paragraph at sir_model_infer).
+ * SIR_EUNSUPPORTED, before anything is launched or written, when a wanted conv2 / conv3 weight gradient falls into the one corner of
+ * batch * t_frames the kernels do not cover ("Sequence regimes" at sir_model_infer); this holds for every form of the backward below. */
 int sir_model_train_bwd(sir_handle* h, const sir_model_weights* w, const float* feats, const float* dlogits,
                         int batch, int t_frames, float dropout_p, uint64_t dropout_seed,
                         const sir_model_grads* grads, void* workspace, size_t workspace_bytes, void* stream);

@@ -25,7 +25,8 @@ int conv_wgrad(sir_handle* h, hipStream_t st, bool wino, int B, int H, int W, co
         return SIR_OK;
     }
     const size_t ldsx = wgrad_x6_lds_bytes(CIN, COUT, W);
-    if (ldsx > 160 * 1024 || W > wgrad_x6_max_w(COUT)) { sir_set_error("sir_model_train_bwd: t_frames too large for the weight-gradient tile"); return SIR_EUNSUPPORTED; }
+    // (sir_model_train_bwd_x refuses such a shape before its first launch)
+    if (!wgrad_x6_fits(CIN, COUT, W)) { sir_set_error("sir_model_train_bwd: t_frames too large for the weight-gradient tile"); return SIR_EUNSUPPORTED; }
     SIR_TRY(sir_lds_opt_in(h, (const void*)conv_wgrad_bf16x6_kernel<CIN, COUT>, 160 * 1024));
     // one workgroup and one slab per image (H rows; its four k-split waves add up in LDS)
     hipLaunchKernelGGL((conv_wgrad_bf16x6_kernel<CIN, COUT>), dim3(B), dim3(512), ldsx, st, dz, a, slab, H, W, H);
@@ -439,6 +440,15 @@ extern "C" int sir_model_train_bwd_x(sir_handle* h, const sir_model_weights* w, 
         sir_set_error("sir_model_train_bwd_x: dfeats must be a float buffer of its own");
         return SIR_EINVAL;
     }
+    c.want = bwd_plan(*g, dfeats != nullptr);
+    // A wanted conv2 / conv3 weight gradient whose Winograd gate is closed runs on the nine-tap kernel, which holds one whole map row:
+    // refused here, for either half of a split call, before anything is launched or written (a frozen conv weight launches neither)
+    if ((g->conv_w[1] && !c.d.conv.wgrad2_wino && !wgrad_x6_fits(32, 64, c.d.wp1)) ||
+        (g->conv_w[2] && !c.d.conv.wgrad3_wino && !wgrad_x6_fits(64, 128, c.d.wp2))) {
+        sir_set_error("sir_model_train_bwd: batch=%d t_frames=%d: the conv2 / conv3 weight gradient of a stage beyond 32-bit offsets takes map rows "
+                      "of at most %d / %d columns (t_frames <= 257 / 259)", batch, t_frames, wgrad_x6_max_w(64), wgrad_x6_max_w(128));
+        return SIR_EUNSUPPORTED;
+    }
     if (!h->bwd_side) {                                      // (first use: the only allocating step, as for the exchange buffers)
         SIR_HIP_TRY(hipStreamCreateWithFlags(&h->bwd_side, hipStreamNonBlocking));
         for (auto& e : h->bwd_ev) SIR_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -449,7 +459,6 @@ extern "C" int sir_model_train_bwd_x(sir_handle* h, const sir_model_weights* w, 
     c.two = h->bwd_side != nullptr && h->prof_mode != 1;
     c.side = c.two ? h->bwd_side : c.st;
     c.p = carve(workspace, off);
-    c.want = bwd_plan(*g, dfeats != nullptr);
     c.bsc = c.p.bsc;
     // rows on scales of their own: only where no gradient sums over the batch -- every BatchNorm on its running statistics and no
     // parameter gradient wanted (sir_amd.explain, a crafting pass of an adversary under frozen statistics)

@@ -23,11 +23,18 @@
 
 constexpr int wgrad_x6_kpx(int W) { return (W + 15) / 16 * 16; }
 constexpr int wgrad_x6_arows(int W) { return wgrad_x6_kpx(W) + 8; }                   // pixel rows of one a-image: + halo and shifted reads
-inline size_t wgrad_x6_lds_bytes(int cin, int cout, int W) {
-    return (size_t)3 * wgrad_x6_kpx(W) * cout * 2 + (size_t)9 * wgrad_x6_arows(W) * cin * 2;
-}
 constexpr int wgrad_x6_ksplit(int cin, int cout) { return 8 / ((cout / 32) * (cin / 32)); }   // waves sharing a (co, ci) tile; reduced in the workgroup
+// the dz / a images of one row, and at least the [KSPLIT - 1][tiles][16][64] floats of the k-split reduce that reuses their space
+// (24 KB for 32 -> 64: more than the images of a row of up to 16 pixels, 19.5 KB)
+inline size_t wgrad_x6_lds_bytes(int cin, int cout, int W) {
+    const size_t img = (size_t)3 * wgrad_x6_kpx(W) * cout * 2 + (size_t)9 * wgrad_x6_arows(W) * cin * 2;
+    const int ks = wgrad_x6_ksplit(cin, cout);
+    const size_t red = (size_t)(ks - 1) * (8 / ks) * 16 * 64 * sizeof(float);
+    return img > red ? img : red;
+}
 constexpr int wgrad_x6_max_w(int cout) { return cout >= 128 ? 64 : 128; }   // row widths the register prefetch is sized for
+// a map row of W columns fits the kernel: its LDS images and its register prefetch (t_frames <= 257 for conv2, <= 259 for conv3)
+inline bool wgrad_x6_fits(int cin, int cout, int W) { return wgrad_x6_lds_bytes(cin, cout, W) <= 160 * 1024 && W <= wgrad_x6_max_w(cout); }
 
 template <int CIN, int COUT>
 __global__ __launch_bounds__(512) void conv_wgrad_bf16x6_kernel(const float* __restrict__ dz, const float* __restrict__ a,

@@ -40,6 +40,42 @@ int main() {
 """
 
 
+SRC_ONE = r"""
+#include <cstdio>
+#include <cstdlib>
+#include "model_shape.h"
+bool sir_conv_stage_fits(int conv, bool shape_ok) {          // api.hip
+    static const int forced = getenv("SIR_CONV_FALLBACK") ? atoi(getenv("SIR_CONV_FALLBACK")) : 0;
+    return shape_ok && forced < (conv == 2 ? 1 : 2);
+}
+int main(int argc, char** argv) {
+    for (int i = 1; i + 1 < argc; i += 2) {
+        SirDims d;
+        if (!sir_make_dims(atoi(argv[i]), atoi(argv[i + 1]), &d)) return 2;
+        const SirConvPlan p = sir_conv_plan(&d, false);
+        printf("%d %d: %d%d%d%d%d\n", d.B, d.T, p.fwd_wino, p.dgrad2_wino, p.dgrad3_wino, p.wgrad2_wino, p.wgrad3_wino);
+    }
+    return 0;
+}
+"""
+
+
+def test_first_gate_to_close_by_itself(tmp_path):
+    """The training plan (fwd, dgrad2, dgrad3, wgrad2, wgrad3) with no switch: batch * t_frames = 524288 closes conv2's weight-gradient
+    gate and nothing else -- (2048, 256), the shape test_conv_fallback_gpu.py runs for the nine-tap kernel -- one image less leaves
+    every gate open, and conv3's weight gradient follows at twice the product."""
+    cxx = shutil.which("c++") or shutil.which("g++") or "/opt/rocm/llvm/bin/clang++"
+    (tmp_path / "one.cpp").write_text(SRC_ONE)
+    subprocess.run([cxx, "-std=c++17", "-O1", "-I", CSRC, str(tmp_path / "one.cpp"), "-o", str(tmp_path / "one")], check=True)
+    env = {k: v for k, v in os.environ.items() if k != "SIR_CONV_FALLBACK"}
+    shapes = [(2047, 256), (2048, 256), (256, 2048), (512, 1024), (4095, 256), (4096, 256)]
+    r = subprocess.run([str(tmp_path / "one")] + [str(v) for s in shapes for v in s], env=env, capture_output=True, text=True, check=True)
+    print(r.stdout)
+    got = dict(line.split(": ") for line in r.stdout.splitlines())
+    assert got == {"2047 256": "11111", "2048 256": "11101", "256 2048": "11101", "512 1024": "11101", "4095 256": "11101",
+                   "4096 256": "11100"}
+
+
 @pytest.mark.parametrize("fallback", [None, "1", "2"])
 def test_plan_gates_equal_the_expressions_they_replaced(fallback, tmp_path):
     cxx = shutil.which("c++") or shutil.which("g++") or "/opt/rocm/llvm/bin/clang++"

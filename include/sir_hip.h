@@ -688,7 +688,9 @@ int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* w, const fl
  *              maximum of |dlogits|; the static 2^8 x batch, rounded up to a power of two, while that maximum times the static
  *              scale lies in [2^5, 2^10), else the power of two that puts it into [2^7, 2^8)); pair 1 + b is utterance b's own,
  *              written and used only by a sir_model_train_bwd_x call with all three bn_frozen set and no parameter gradient wanted
- *              (rows are then independent, and each is scaled by its own row of dlogits).  Slots 21..29 carry the scale. */
+ *              (rows are then independent, and each is scaled by its own row of dlogits).  Slots 21..29 carry the scale.
+ *   40  rag    the ragged step (sir_model_train_fwd_ragged): int32 [4][B] -- the validated frames (0 for a length outside [8, T]),
+ *              W1, W2 and S_b of every clip; written by that call and rewritten by sir_model_train_bwd_ragged, untouched otherwise */
 int sir_model_train_workspace_offsets(const sir_handle* h, int batch, int t_frames, size_t* offsets, int n);
 
 /* ---- fine-tuning step -------------------------------------------------------------------------
@@ -742,6 +744,40 @@ int sir_model_train_bwd_x(sir_handle* h, const sir_model_weights* w, const float
                           int batch, int t_frames, float dropout_p, uint64_t dropout_seed,
                           const sir_train_config* cfg, const sir_model_grads* grads, float* dfeats,
                           void* workspace, size_t workspace_bytes, int part, void* stream);
+
+/* ---- the ragged (un-padded) differentiable step --------------------------------------------------
+ * sir_model_infer_ragged's function, differentiable: row b of the logits is what the model gives feats[b][:, :frames[b]] on its
+ * own -- every BatchNorm on its running statistics, the GRU in training mode (the inter-layer dropout mask of the padded step: same
+ * hash, same element index (b * S + t) * 512 + u, applied for t < S_b), the attention softmax over t < S_b -- and the backward is
+ * the gradient of that function.  Widths as for sir_model_infer_ragged: W1 = frames / 2, W2 = W1 / 2, S_b = W2 / 2.
+ *   frames : device int32 [batch], each in [8, t_frames].  A value outside it behaves as in inference: the clip's width counts as 0,
+ *            row b of the logits is NaN and status bit 6 is raised (SIR_EINVAL at the next sir_check_status); the backward treats
+ *            that row's dlogits as zero and writes a zero dfeats row.  Whatever frames holds, nothing is read or written out of
+ *            bounds.  Feature columns >= frames[b] are never read as data.
+ *   cfg    : must set all three bn_frozen.  Anything else, NULL included, is SIR_EUNSUPPORTED before any launch: with batch
+ *            statistics a clip has no result of its own.  The running statistics are read, never written.
+ *   workspace : the one sir_model_workspace_bytes(h, batch, t_frames, 1) sizes; slot 40 (appended) holds the validated frames and
+ *            the three widths of every clip as int32 [4][batch].  Behind a clip's widths a1, a2, x0 (slots 0, 2, 4), y0, y0d, y1
+ *            (8, 9, 10) and every gradient slot are zeros; the saved gates (6, 7) and z2 / z3 (1, 3) are unspecified there.
+ * The chain: the ragged conv1 kernel of inference (+ zeros behind W1), conv2 / conv3 and both input projections at full width on
+ * maps that are zero behind the clip (their kernels, the conv fallback route included, are the padded step's), the BN + ReLU + pool
+ * kernels writing zeros behind W2 / S_b, the ragged form of the recurrence that saves its gates, the ragged attention kernel.
+ * Backward: a length-aware head, the BPTT kernel's ragged form (all S steps under a predicate: zero gate gradients and a held /
+ * dropped carry for t >= S_b, no saved row of such a step used as data), width masks on the pooled gradients (the transposed
+ * convolutions spill one column past a clip's width) in the BatchNorm backward, its frozen dgamma / dbeta sums and conv1's two
+ * kernels, which also write dfeats as zero at columns >= frames[b].  No atomics, fixed summation order: bit-reproducible, and the
+ * one- and two-stream forms agree.
+ * sir_model_train_bwd_ragged: `grads` with the pruning rules of sir_model_train_bwd_cfg, `dfeats` as for sir_model_train_bwd_x,
+ * `part` as for sir_model_train_bwd_part; frames, cfg, dropout_p and dropout_seed those of the forward call.
+ * Every argument is validated before anything is launched or written. */
+int sir_model_train_fwd_ragged(sir_handle* h, const sir_model_weights* w, const float* const bn_running_mean[3],
+                               const float* const bn_running_var[3], const float* feats, const int32_t* frames, int batch,
+                               int t_frames, float dropout_p, uint64_t dropout_seed, const sir_train_config* cfg,
+                               float* logits, void* workspace, size_t workspace_bytes, void* stream);
+int sir_model_train_bwd_ragged(sir_handle* h, const sir_model_weights* w, const float* feats, const int32_t* frames,
+                               const float* dlogits, int batch, int t_frames, float dropout_p, uint64_t dropout_seed,
+                               const sir_train_config* cfg, const sir_model_grads* grads, float* dfeats, void* workspace,
+                               size_t workspace_bytes, int part, void* stream);
 
 /* optimizer.step() for torch.optim.Adam(lr, betas, eps, weight_decay) with coupled L2
  * (train.py:246-250, :107): one multi-tensor launch.  The pointer arrays are HOST arrays of device

@@ -157,6 +157,12 @@ SIGNATURES = {
     "sir_model_train_bwd_x": (C.c_int, [C.c_void_p, C.POINTER(ModelWeights), C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                         C.c_float, C.c_uint64, C.POINTER(TrainConfig), C.POINTER(ModelGrads), C.c_void_p,
                                         C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
+    "sir_model_train_fwd_ragged": (C.c_int, [C.c_void_p, C.POINTER(ModelWeights), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                             C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_uint64, C.POINTER(TrainConfig),
+                                             C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "sir_model_train_bwd_ragged": (C.c_int, [C.c_void_p, C.POINTER(ModelWeights), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                             C.c_float, C.c_uint64, C.POINTER(TrainConfig), C.POINTER(ModelGrads), C.c_void_p,
+                                             C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
     "sir_adam_step": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                 C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int, C.c_float, C.c_float, C.c_float,
                                 C.c_float, C.c_float, C.c_void_p]),

@@ -34,11 +34,18 @@ constexpr size_t BQ_XBUF_PER_CLUSTER = (size_t)2 * 4 * 4 * BQ_BLOCK * 8;      //
 // dbg (timing experiments only, results invalid): bit 0 = do not wait for the granules, bit 1 = skip the MFMAs, bit 2 = skip
 // publish + receive, bit 3 = no dgi / dgh stores, bit 4 = no input loads after the first step; bits 8-12 = delay of the first poll
 // round in units of 64 cycles (results stay valid)
+// RAGGED (sir_model_train_bwd_ragged): utterance b ran nlive[b] <= S steps of its own in the forward (gru_quad_kernel<true, true, true>:
+// h held from there on, the reverse direction started at nlive[b] - 1 from h = 0).  Every cluster still runs all S steps -- the
+// exchange needs the same count in its four workgroups, and S is the same everywhere -- under a predicate: at a step t >= nlive[b] the
+// saved gates, y and dy rows are not read (zeros take their place: those rows were never written), d(h) is zero, so are the gate
+// gradients stored for that row, and what the reverse direction carried out of its last real step is dropped; h(t + 1) of the
+// reverse direction's step nlive[b] - 1 is the zero it started from.
+template <bool RAGGED = false>
 __global__ __launch_bounds__(GQ_THREADS) void gru_bwd_quad_kernel(
     const float* __restrict__ dy, const float* __restrict__ gates, const float* __restrict__ y, const float* __restrict__ whh0,
     const float* __restrict__ whh1, float* __restrict__ dgi, float* __restrict__ dgh, float* __restrict__ bsum_i,
     float* __restrict__ bsum_h, int B, int S, unsigned long long* xbuf, unsigned int* status, unsigned epoch, int dbg,
-    const uint4* __restrict__ wfrag0, const uint4* __restrict__ wfrag1) {
+    const uint4* __restrict__ wfrag0, const uint4* __restrict__ wfrag1, const int* __restrict__ nlive) {
     // wfrag0 / 1: prep_whh_bwd_quad_elem output for direction 0 / 1 (gru_frag_prep.h; required)
     extern __shared__ __attribute__((aligned(16))) unsigned char bqlds[];
     // workgroup -> (quarter, cluster) as in gru_quad_kernel: the four quarters of a cluster on ONE XCD
@@ -77,6 +84,9 @@ __global__ __launch_bounds__(GQ_THREADS) void gru_bwd_quad_kernel(
     const int uq = lane & 15, us = lane >> 4;
     const int bg = grp * GQ_NU + 4 * wv + us;                // the gate role's utterance
     const bool bvalid = bg < B;
+    int nlb_ = S;                                            // steps of the gate role's utterance
+    if constexpr (RAGGED) nlb_ = bvalid ? max(0, min(S, nlive[bg])) : 0;
+    const int nlb = nlb_;
     const int ulg = 4 * uq, ug = q * GQ_UQ + ulg;            // first of the gate role's 4 units: inside the quarter / of the layer
     float* tl = reinterpret_cast<float*>(bqlds + 2 * BQ_BUFB);              // [16 utterances][BQ_TROW] floats
     struct In { float4 r, z, nn, hn, hp, dy; };
@@ -88,13 +98,14 @@ __global__ __launch_bounds__(GQ_THREADS) void gru_bwd_quad_kernel(
         const int step_ = S - 1 - it_;
         const int t_ = dir ? (S - 1 - step_) : step_;
         const int tp_ = dir ? t_ + 1 : t_ - 1;
+        if (RAGGED && t_ >= nlb) return;
         const size_t row_ = (size_t)bg * S + t_;
         const float* gs = gates + (row_ * 2 + dir) * 1024 + ug;
         o.r = *reinterpret_cast<const float4*>(gs);
         o.z = *reinterpret_cast<const float4*>(gs + 256);
         o.nn = *reinterpret_cast<const float4*>(gs + 512);
         o.hn = *reinterpret_cast<const float4*>(gs + 768);
-        if (step_ > 0) o.hp = *reinterpret_cast<const float4*>(y + ((size_t)bg * S + tp_) * 512 + dir * 256 + ug);
+        if (step_ > 0 && (!RAGGED || tp_ < nlb)) o.hp = *reinterpret_cast<const float4*>(y + ((size_t)bg * S + tp_) * 512 + dir * 256 + ug);
         o.dy = *reinterpret_cast<const float4*>(dy + row_ * 512 + dir * 256 + ug);
     };
     In cur, nxt;
@@ -120,7 +131,7 @@ __global__ __launch_bounds__(GQ_THREADS) void gru_bwd_quad_kernel(
         float drp[4], dzp[4], dnp[4], dnr[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-            const float dh = dyv[j] + dhz[j] + dhs[j];
+            const float dh = (RAGGED && t >= nlb) ? 0.0f : dyv[j] + dhz[j] + dhs[j];
             const float dn = dh * (1.0f - zg[j]);
             const float dz = dh * (hp[j] - nn[j]);
             dnp[j] = dn * (1.0f - nn[j] * nn[j]);

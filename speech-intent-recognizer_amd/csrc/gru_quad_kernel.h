@@ -177,7 +177,8 @@ __global__ __launch_bounds__(GQ_THREADS) void gru_quad_kernel(
 
     // gate pre-activations of the input side, fetched one step ahead
     float4 gin[3];
-    const int nlb = (!SAVE && nlive && bvalid) ? nlive[b] : (RAGGED ? 0 : S);
+    // (SAVE && RAGGED: the ragged training step, sir_model_train_fwd_ragged -- gates and y rows are saved for t < nlive[b] alone)
+    const int nlb = ((RAGGED || !SAVE) && nlive && bvalid) ? nlive[b] : (RAGGED ? 0 : S);
     auto load_gi = [&](int t, float4 (&dst)[3]) {
 #pragma unroll
         for (int g = 0; g < 3; ++g) dst[g] = make_float4(0.f, 0.f, 0.f, 0.f);

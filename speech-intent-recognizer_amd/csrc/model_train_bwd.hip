@@ -110,6 +110,7 @@ struct Bwd {
     bool row_scaled;                // every utterance on a scale of its own (the data-only backward under frozen statistics)
     float *scale, *shift, *smean, *sinv, *mdy, *mdyx;      // the [224]-channel BatchNorm arrays (bn1 | bn2 | bn3 at 0, 32, 96) in p.bn, p.bnb
     bool forked, side_marked;       // side has work of this call / its last launch is marked by event 3 (sir_handle::bwd_ev)
+    bool ragged; RagPtrs rg;        // sir_model_train_bwd_ragged: the clips' own widths (TB_RAG, rewritten from `frames` at the head of the call)
 
     int fork(int ev) {              // side continues behind what st holds now
         if (!two) return SIR_OK;
@@ -138,10 +139,11 @@ int bwd_head(Bwd& c) {
     if (c.want.head) {
         SirProfScope prof(c.h, SIR_K_B_HEAD, c.st);
         hipLaunchKernelGGL(bwd_scale_kernel, dim3(c.row_scaled ? (B + 15) / 16 : 1), dim3(1024), 0, c.st, c.dlogits, B, C, sir_bwd_loss_scale_exp(B),
-                           c.row_scaled ? 1 : 0, c.p.bsc);
+                           c.row_scaled ? 1 : 0, c.p.bsc, c.ragged ? c.rg.sb : (const int*)nullptr);
         // (workgroups [B, B + 2 C) are the fc weight / bias gradient: left out when fc is frozen)
         hipLaunchKernelGGL(head_bwd_kernel, dim3(B + (c.want.fc ? 2 * C : 0)), dim3(256), 0, c.st, c.dlogits, c.w->fc_w, (const float*)c.p.y1, c.w->attn_w,
-                           c.w->attn_b, (const float*)c.p.ctx, c.p.dy1, daw_part, dab_part, c.g->fc_w, c.g->fc_b, B, S, C, c.bsc, c.row_scaled ? 1 : 0);
+                           c.w->attn_b, (const float*)c.p.ctx, c.p.dy1, daw_part, dab_part, c.g->fc_w, c.g->fc_b, B, S, C, c.bsc, c.row_scaled ? 1 : 0,
+                           c.ragged ? c.rg.sb : (const int*)nullptr);
         if (c.want.attn)
             hipLaunchKernelGGL(head_colsum_kernel, dim3(9), dim3(256), 0, c.st, (const float*)daw_part, (const float*)dab_part, B, c.g->attn_w, c.g->attn_b);
     }
@@ -247,7 +249,8 @@ int bwd_gru_layer(Bwd& c, int layer) {
     {   SirProfScope prof(c.h, layer ? SIR_K_B_GRU1 : SIR_K_B_GRU0, c.st);
         SIR_TRY(sir_launch_gru_bwd_quad(c.h, c.st, layer ? p.dy1 : p.dy0, layer ? p.g1 : p.g0, layer ? p.y1 : p.y0, c.w->gru_w_hh[2 * layer],
                                         c.w->gru_w_hh[2 * layer + 1], layer ? p.dgi1 : p.dgi, layer ? p.dgh1 : p.dgh, bsum_i, bsum_h, B, S,
-                                        (const char*)p.wr4 + (size_t)(2 * layer) * GRU_FRAG_BYTES, (const char*)p.wr4 + (size_t)(2 * layer + 1) * GRU_FRAG_BYTES));
+                                        (const char*)p.wr4 + (size_t)(2 * layer) * GRU_FRAG_BYTES, (const char*)p.wr4 + (size_t)(2 * layer + 1) * GRU_FRAG_BYTES,
+                                        c.ragged ? c.rg.sb : (const int*)nullptr));
         // bias gradients first: bsum_* alias the slab area used below
         if (want.gru_b[layer])
             hipLaunchKernelGGL(gru_bias_colsum_kernel, dim3(24, 2), dim3(256), 0, c.st, (const float*)bsum_i, (const float*)bsum_h, B,
@@ -284,6 +287,7 @@ struct ConvBlock {
     int nblk, ev;                   // workgroups (= partial sums) of the reduce launch; fork event of the weight gradient
     bool last_on_side;              // no weight gradient follows this block's on the side stream
     int prof_bn, prof_wgrad, prof_dgrad;
+    const int* wlim;                // ragged step: columns of the pooled map that belong to each clip (`da` counts as zero behind them), else NULL
 };
 
 // CIN -> COUT: the forward's channels.  GRU_IN: `da` is in the GRU layout (conv3).  reduce(): launches the block's partial sums of
@@ -304,15 +308,18 @@ int bwd_conv_block(Bwd& c, const ConvBlock& k, Reduce reduce) {
             if (gb)
                 hipLaunchKernelGGL(bn_bwd_finalize_frozen_kernel, dim3(COUT), dim3(256), 0, c.st, (const float2*)c.p.stats, k.nblk, COUT, c.g->bn_w[k.i],
                                    c.g->bn_b[k.i], c.bsc);
-            if (k.need_dz)
+            if (k.need_dz && k.wlim)
+                hipLaunchKernelGGL((bn_bwd_dz_kernel<GRU_IN, true, true>), dim3(dz_grid), dim3(256), 0, c.st, k.z, k.da, scale, shift, (const float*)nullptr,
+                                   (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, k.dz, B, k.H, k.W, COUT, Hp, k.Wp, k.wlim);
+            else if (k.need_dz)
                 hipLaunchKernelGGL((bn_bwd_dz_kernel<GRU_IN, true>), dim3(dz_grid), dim3(256), 0, c.st, k.z, k.da, scale, shift, (const float*)nullptr,
-                                   (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, k.dz, B, k.H, k.W, COUT, Hp, k.Wp);
+                                   (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, k.dz, B, k.H, k.W, COUT, Hp, k.Wp, (const int*)nullptr);
         } else {
             hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(COUT), dim3(256), 0, c.st, (const float2*)c.p.stats, k.nblk, COUT, (double)B * k.H * k.W,
                                c.g->bn_w[k.i], c.g->bn_b[k.i], c.mdy + k.ch, c.mdyx + k.ch, c.bsc);
             if (k.need_dz)
                 hipLaunchKernelGGL(bn_bwd_dz_kernel<GRU_IN>, dim3(dz_grid), dim3(256), 0, c.st, k.z, k.da, scale, shift, c.smean + k.ch, c.sinv + k.ch,
-                                   c.mdy + k.ch, c.mdyx + k.ch, k.dz, B, k.H, k.W, COUT, Hp, k.Wp);
+                                   c.mdy + k.ch, c.mdyx + k.ch, k.dz, B, k.H, k.W, COUT, Hp, k.Wp, (const int*)nullptr);
         }
     }
     if (c.g->conv_w[k.i]) {
@@ -336,7 +343,8 @@ int bwd_conv3(Bwd& c) {
     const TDims& d = c.d;
     const int rows = d.B * d.wp3, rpb = 16;
     ConvBlock k{2, 96, 16, d.wp2, d.wp3, p.z3, p.dx0, p.a2, p.dz3, p.da2, p.wcb3t, &d.conv.geo3, d.conv.wgrad3_wino, d.conv.dgrad3_wino,
-                c.want.dz3, c.want.da2, (rows + rpb - 1) / rpb, 1, !c.g->conv_w[1], SIR_K_B_BN3, SIR_K_B_WGRAD3, SIR_K_B_DGRAD3};
+                c.want.dz3, c.want.da2, (rows + rpb - 1) / rpb, 1, !c.g->conv_w[1], SIR_K_B_BN3, SIR_K_B_WGRAD3, SIR_K_B_DGRAD3,
+                c.ragged ? c.rg.sb : (const int*)nullptr};     // (dx0 is zero behind S_b already: the projection's rows do not spill)
     return bwd_conv_block<64, 128, true>(c, k, [&] {
         hipLaunchKernelGGL(bn_bwd_reduce_pooled_gru_kernel, dim3(k.nblk), dim3(256), 0, c.st, (const float*)p.x0, (const float*)p.dx0,
                            (const float*)p.z3, c.w->bn_w[2], c.w->bn_b[2], c.scale + 96, c.shift + 96, c.smean + 96, c.sinv + 96, p.stats, rows, 16, d.wp2, d.wp3, rpb);
@@ -349,11 +357,12 @@ int bwd_conv2(Bwd& c) {
     const int ppb = 64;
     const size_t npix = (size_t)d.B * 16 * d.wp2;
     ConvBlock k{1, 32, 32, d.wp1, d.wp2, p.z2, p.da2, p.a1, p.dz2, p.da1, p.wcb2t, &d.conv.geo2, d.conv.wgrad2_wino, d.conv.dgrad2_wino,
-                c.want.dz2, c.want.da1, (int)((npix + ppb - 1) / ppb), 2, true, SIR_K_B_BN2, SIR_K_B_WGRAD2, SIR_K_B_DGRAD2};
+                c.want.dz2, c.want.da1, (int)((npix + ppb - 1) / ppb), 2, true, SIR_K_B_BN2, SIR_K_B_WGRAD2, SIR_K_B_DGRAD2,
+                c.ragged ? c.rg.w2 : (const int*)nullptr};
     return bwd_conv_block<32, 64, false>(c, k, [&] {
         hipLaunchKernelGGL(bn_bwd_reduce_pooled_kernel, dim3(k.nblk), dim3(256), 0, c.st, (const float*)p.a2, (const float*)p.da2,
                            (const float*)p.z2, c.w->bn_w[1], c.w->bn_b[1], c.scale + 32, c.shift + 32, c.smean + 32, c.sinv + 32, p.stats, d.B, 32,
-                           d.wp1, 64, 16, d.wp2, ppb);
+                           d.wp1, 64, 16, d.wp2, ppb, k.wlim);
     });
 }
 
@@ -372,8 +381,12 @@ int bwd_conv1(Bwd& c) {
         SirProfScope prof(c.h, SIR_K_B_CONV1, c.st);
         const dim3 g1(d.c1gx, d.c1gy, B);
         const int nblk = d.c1gx * d.c1gy * B;
-        hipLaunchKernelGGL(conv1_bwd_kernel<2>, g1, dim3(256), 0, c.st, c.feats, c.w->conv_w[0], (const float*)p.da1, c.scale, c.shift,
-                           c.smean, c.sinv, (const float*)nullptr, (const float*)nullptr, c1part, 64, T, 32, d.wp1);
+        if (c.ragged)
+            hipLaunchKernelGGL((conv1_bwd_kernel<2, true>), g1, dim3(256), 0, c.st, c.feats, c.w->conv_w[0], (const float*)p.da1, c.scale, c.shift,
+                               c.smean, c.sinv, (const float*)nullptr, (const float*)nullptr, c1part, 64, T, 32, d.wp1, c.rg.w1, c.rg.fw);
+        else
+            hipLaunchKernelGGL(conv1_bwd_kernel<2>, g1, dim3(256), 0, c.st, c.feats, c.w->conv_w[0], (const float*)p.da1, c.scale, c.shift,
+                               c.smean, c.sinv, (const float*)nullptr, (const float*)nullptr, c1part, 64, T, 32, d.wp1, (const int*)nullptr, (const int*)nullptr);
         float* c1tmp = (float*)p.stats;           // [128][352] partial column sums, then [352] totals behind them
         float* c1tot = c1tmp + 128 * 352;
         hipLaunchKernelGGL(colsum_partial_kernel, dim3((352 + 63) / 64, 128), dim3(256), 0, c.st, (const float*)c1part, nblk, 352, 352, c1tmp);
@@ -390,12 +403,18 @@ int bwd_conv1(Bwd& c) {
         // data gradient: dz1 recomputed per tile, transposed 3x3 convolution onto the features (conv1_bwd_data_kernel)
         SirProfScope prof(c.h, SIR_K_B_CONV1_DGRAD, c.st);
         const dim3 gd((T + C1D_TW - 1) / C1D_TW, (64 + C1D_TH - 1) / C1D_TH, B);
-        if (frozen)
+        if (c.ragged)                                        // (frozen: the entry point insists)
+            hipLaunchKernelGGL((conv1_bwd_data_kernel<true, true>), gd, dim3(256), 0, c.st, c.feats, c.w->conv_w[0], (const float*)p.da1, c.scale, c.shift,
+                               (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, c.dfeats, 64, T, 32, d.wp1, c.bsc,
+                               c.row_scaled ? 1 : 0, c.rg.w1, c.rg.fw);
+        else if (frozen)
             hipLaunchKernelGGL(conv1_bwd_data_kernel<true>, gd, dim3(256), 0, c.st, c.feats, c.w->conv_w[0], (const float*)p.da1, c.scale, c.shift,
-                               (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, c.dfeats, 64, T, 32, d.wp1, c.bsc, c.row_scaled ? 1 : 0);
+                               (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, c.dfeats, 64, T, 32, d.wp1, c.bsc, c.row_scaled ? 1 : 0,
+                               (const int*)nullptr, (const int*)nullptr);
         else
             hipLaunchKernelGGL(conv1_bwd_data_kernel<false>, gd, dim3(256), 0, c.st, c.feats, c.w->conv_w[0], (const float*)p.da1, c.scale, c.shift,
-                               c.smean, c.sinv, (const float*)c.mdy, (const float*)c.mdyx, c.dfeats, 64, T, 32, d.wp1, c.bsc, c.row_scaled ? 1 : 0);
+                               c.smean, c.sinv, (const float*)c.mdy, (const float*)c.mdyx, c.dfeats, 64, T, 32, d.wp1, c.bsc, c.row_scaled ? 1 : 0,
+                               (const int*)nullptr, (const int*)nullptr);
     }
     SIR_KCHECK();
     return SIR_OK;
@@ -422,20 +441,20 @@ extern "C" int sir_model_train_bwd_cfg(sir_handle* h, const sir_model_weights* w
     return sir_model_train_bwd_x(h, w, feats, dlogits, batch, t_frames, dropout_p, dropout_seed, cfg, g, nullptr, workspace, workspace_bytes, part, stream_);
 }
 
-extern "C" int sir_model_train_bwd_x(sir_handle* h, const sir_model_weights* w, const float* feats, const float* dlogits,
-                                     int batch, int t_frames, float dropout_p, uint64_t dropout_seed,
-                                     const sir_train_config* cfg, const sir_model_grads* g, float* dfeats, void* workspace,
-                                     size_t workspace_bytes, int part, void* stream_) {
-    if (!cfg) cfg = &kTrainAllLive;
+// frames == NULL: the padded step; else the ragged one (sir_model_train_bwd_ragged: every BatchNorm frozen, the caller has checked)
+static int train_bwd_impl(const char* who, sir_handle* h, const sir_model_weights* w, const float* feats, const int32_t* frames, const float* dlogits,
+                          int batch, int t_frames, float dropout_p, uint64_t dropout_seed,
+                          const sir_train_config* cfg, const sir_model_grads* g, float* dfeats, void* workspace,
+                          size_t workspace_bytes, int part, void* stream_) {
     if (part != SIR_BWD_ALL && part != SIR_BWD_HEAD_GRU && part != SIR_BWD_CNN) {
         sir_set_error("sir_model_train_bwd_part: unknown part %d", part);
         return SIR_EINVAL;
     }
     Bwd c{};
     size_t off[TB_COUNT];
-    int rc = check_common("sir_model_train_bwd", h, w, batch, t_frames, workspace, workspace_bytes, &c.d, off);
+    int rc = check_common(who, h, w, batch, t_frames, workspace, workspace_bytes, &c.d, off);
     if (rc != SIR_OK) return rc;
-    if (!feats || !dlogits || !g) { sir_set_error("sir_model_train_bwd: NULL argument"); return SIR_EINVAL; }
+    if (!feats || !dlogits || !g) { sir_set_error("%s: NULL argument", who); return SIR_EINVAL; }
     if (dfeats && (((uintptr_t)dfeats & 3) != 0 || dfeats == feats)) {
         sir_set_error("sir_model_train_bwd_x: dfeats must be a float buffer of its own");
         return SIR_EINVAL;
@@ -467,6 +486,11 @@ extern "C" int sir_model_train_bwd_x(sir_handle* h, const sir_model_weights* w, 
     c.scale = c.p.bn; c.shift = c.p.bn + 224; c.smean = c.p.bn + 448; c.sinv = c.p.bn + 672;
     c.mdy = c.p.bnb; c.mdyx = c.p.bnb + 224;
     c.y0in = dropout_p > 0.0f ? c.p.y0d : c.p.y0;
+    c.ragged = frames != nullptr;
+    c.rg = rag_ptrs(c.p.rag, c.d.B);
+    if (c.ragged)                                            // (either half of a split call; no status: the forward has reported a bad length)
+        hipLaunchKernelGGL(ragged_widths_kernel, dim3((c.d.B + 255) / 256), dim3(256), 0, c.st, (const int*)frames, c.d.B, c.d.T, c.p.rag,
+                           (unsigned int*)nullptr);
 
     if (part != SIR_BWD_CNN) {
         SIR_TRY(bwd_head(c));
@@ -487,4 +511,26 @@ extern "C" int sir_model_train_bwd_x(sir_handle* h, const sir_model_weights* w, 
     if (c.want.da2) SIR_TRY(bwd_conv2(c));
     if (c.want.da1) SIR_TRY(bwd_conv1(c));
     return c.join();
+}
+
+extern "C" int sir_model_train_bwd_x(sir_handle* h, const sir_model_weights* w, const float* feats, const float* dlogits,
+                                     int batch, int t_frames, float dropout_p, uint64_t dropout_seed,
+                                     const sir_train_config* cfg, const sir_model_grads* g, float* dfeats, void* workspace,
+                                     size_t workspace_bytes, int part, void* stream_) {
+    return train_bwd_impl("sir_model_train_bwd", h, w, feats, nullptr, dlogits, batch, t_frames, dropout_p, dropout_seed, cfg ? cfg : &kTrainAllLive, g,
+                          dfeats, workspace, workspace_bytes, part, stream_);
+}
+
+extern "C" int sir_model_train_bwd_ragged(sir_handle* h, const sir_model_weights* w, const float* feats, const int32_t* frames,
+                                          const float* dlogits, int batch, int t_frames, float dropout_p, uint64_t dropout_seed,
+                                          const sir_train_config* cfg, const sir_model_grads* g, float* dfeats, void* workspace,
+                                          size_t workspace_bytes, int part, void* stream_) {
+    if (!cfg || !cfg->bn_frozen[0] || !cfg->bn_frozen[1] || !cfg->bn_frozen[2]) {
+        sir_set_error("sir_model_train_bwd_ragged: lengths (frames per clip) need every BatchNorm on its frozen running statistics "
+                      "(bn_frozen = {1, 1, 1}): with batch statistics a clip has no gradient of its own");
+        return SIR_EUNSUPPORTED;
+    }
+    if (!frames) { sir_set_error("sir_model_train_bwd_ragged: NULL frames"); return SIR_EINVAL; }
+    return train_bwd_impl("sir_model_train_bwd_ragged", h, w, feats, frames, dlogits, batch, t_frames, dropout_p, dropout_seed, cfg, g, dfeats,
+                          workspace, workspace_bytes, part, stream_);
 }

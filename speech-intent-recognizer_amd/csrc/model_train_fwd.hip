@@ -33,20 +33,28 @@ extern "C" int sir_model_train_fwd(sir_handle* h, const sir_model_weights* w, fl
                                    nullptr, logits, workspace, workspace_bytes, stream_);
 }
 
-extern "C" int sir_model_train_fwd_cfg(sir_handle* h, const sir_model_weights* w, float* const bn_running_mean[3],
-                                       float* const bn_running_var[3], const float* feats, int batch, int t_frames,
-                                       float bn_momentum, float dropout_p, uint64_t dropout_seed, const sir_train_config* cfg,
-                                       float* logits, void* workspace, size_t workspace_bytes, void* stream_) {
-    if (!cfg) cfg = &kTrainAllLive;
+// frames == NULL: the padded step.  Else the ragged one (sir_model_train_fwd_ragged; every BatchNorm frozen -- the caller has checked):
+// clip b alone at its own width frames[b].  conv1 takes its right edge there (the ragged inference kernel); each block's BN + ReLU +
+// pool kernel writes zeros behind the clip's new width, so conv2 / conv3 and the layer-0 projection run unchanged, at full width, on
+// maps whose columns behind a clip are the zeros its own padding would be; the recurrences hold h for t >= S_b and store no row
+// there (the rows are zeroed: ragged_zero_tail_kernel says who reads them); the attention softmax runs over t < S_b.
+static int train_fwd_impl(const char* who, sir_handle* h, const sir_model_weights* w, float* const bn_running_mean[3],
+                          float* const bn_running_var[3], const float* feats, const int32_t* frames, int batch, int t_frames,
+                          float bn_momentum, float dropout_p, uint64_t dropout_seed, const sir_train_config* cfg,
+                          float* logits, void* workspace, size_t workspace_bytes, void* stream_) {
+    const bool ragged = frames != nullptr;
     TDims d;
     size_t off[TB_COUNT];
-    int rc = check_common("sir_model_train_fwd", h, w, batch, t_frames, workspace, workspace_bytes, &d, off);
+    int rc = check_common(who, h, w, batch, t_frames, workspace, workspace_bytes, &d, off);
     if (rc != SIR_OK) return rc;
-    if (!feats || !logits || !bn_running_mean || !bn_running_var) { sir_set_error("sir_model_train_fwd: NULL argument"); return SIR_EINVAL; }
-    if (dropout_p < 0.0f || dropout_p >= 1.0f) { sir_set_error("sir_model_train_fwd: dropout_p=%f", dropout_p); return SIR_EINVAL; }
+    if (!feats || !logits || !bn_running_mean || !bn_running_var) { sir_set_error("%s: NULL argument", who); return SIR_EINVAL; }
+    for (int i = 0; ragged && i < 3; ++i)
+        if (!bn_running_mean[i] || !bn_running_var[i]) { sir_set_error("%s: NULL running statistics", who); return SIR_EINVAL; }
+    if (dropout_p < 0.0f || dropout_p >= 1.0f) { sir_set_error("%s: dropout_p=%f", who, dropout_p); return SIR_EINVAL; }
     hipStream_t st = (hipStream_t)stream_;
     TPtrs p = carve(workspace, off);
     const int B = d.B, S = d.S, T = d.T;
+    const RagPtrs rg = rag_ptrs(p.rag, B);
     float *scale = p.bn, *shift = p.bn + 224, *smean = p.bn + 448, *sinv = p.bn + 672;
 
     // conv2 / conv3 forward and both data gradients run on the producer / consumer Winograd kernel (conv_wino2_f16x3_kernel.h);
@@ -103,8 +111,14 @@ extern "C" int sir_model_train_fwd_cfg(sir_handle* h, const sir_model_weights* w
             hipLaunchKernelGGL(conv1_bn_from_moments_kernel, dim3(1), dim3(64), 0, st, (const double*)p.c1m, w->conv_w[0],
                                (double)B * 64 * T, w->bn_w[0], w->bn_b[0], bn_running_mean[0], bn_running_var[0], bn_momentum, scale, shift, smean, sinv, h->status);
         }
-        hipLaunchKernelGGL(conv1_mfma_bn_relu_pool_kernel, conv1_grid(B, d.wp1), dim3(256), 0, st,
-                           feats, w->conv_w[0], scale, shift, p.a1, 64, T, 32, d.wp1, (const float*)nullptr, B, (const int*)nullptr);
+        if (ragged) {
+            hipLaunchKernelGGL(ragged_widths_kernel, dim3((B + 255) / 256), dim3(256), 0, st, (const int*)frames, B, T, p.rag, h->status);
+            hipLaunchKernelGGL(conv1_mfma_bn_relu_pool_ragged_kernel, conv1_grid(B, d.wp1), dim3(256), 0, st,
+                               feats, w->conv_w[0], scale, shift, p.a1, 64, T, 32, d.wp1, rg.w1, rg.fw);
+            hipLaunchKernelGGL(ragged_zero_tail_kernel, dim3(32, B), dim3(256), 0, st, p.a1, rg.w1, 32, d.wp1, 32, 1);
+        } else
+            hipLaunchKernelGGL(conv1_mfma_bn_relu_pool_kernel, conv1_grid(B, d.wp1), dim3(256), 0, st,
+                               feats, w->conv_w[0], scale, shift, p.a1, 64, T, 32, d.wp1, (const float*)nullptr, B, (const int*)nullptr);
     }
     // conv2 block: raw conv + partial statistics on MFMA, finalize, BN+ReLU+pool
     {
@@ -119,8 +133,12 @@ extern "C" int sir_model_train_fwd_cfg(sir_handle* h, const sir_model_weights* w
             hipLaunchKernelGGL(bn_finalize_kernel, dim3(64), dim3(256), 0, st, (const float2*)p.stats, w2 ? (int)wino2_stat_blocks(B, 32, d.wp1, h->num_cus) : d.c2wx * B, 64,
                                (double)B * 32 * d.wp1, w->bn_w[1], w->bn_b[1], bn_running_mean[1], bn_running_var[1], bn_momentum,
                                scale + 32, shift + 32, smean + 32, sinv + 32, h->status);
-        hipLaunchKernelGGL(bn_relu_pool_kernel<false>, dim3(grid_for((size_t)B * 16 * d.wp2 * 16)), dim3(256), 0, st, p.z2,
-                           scale + 32, shift + 32, p.a2, B, 32, d.wp1, 64, 16, d.wp2, 256.0f, h->status);
+        if (ragged)
+            hipLaunchKernelGGL((bn_relu_pool_kernel<false, true>), dim3(grid_for((size_t)B * 16 * d.wp2 * 16)), dim3(256), 0, st, p.z2,
+                               scale + 32, shift + 32, p.a2, B, 32, d.wp1, 64, 16, d.wp2, 256.0f, h->status, rg.w2);
+        else
+            hipLaunchKernelGGL(bn_relu_pool_kernel<false>, dim3(grid_for((size_t)B * 16 * d.wp2 * 16)), dim3(256), 0, st, p.z2,
+                               scale + 32, shift + 32, p.a2, B, 32, d.wp1, 64, 16, d.wp2, 256.0f, h->status, (const int*)nullptr);
     }
     {
         {   SirProfScope prof(h, SIR_K_T_CONV3, st);
@@ -134,8 +152,12 @@ extern "C" int sir_model_train_fwd_cfg(sir_handle* h, const sir_model_weights* w
             hipLaunchKernelGGL(bn_finalize_kernel, dim3(128), dim3(256), 0, st, (const float2*)p.stats, w2 ? (int)wino2_stat_blocks(B, 16, d.wp2, h->num_cus) : d.c3fx * B, 128,
                                (double)B * 16 * d.wp2, w->bn_w[2], w->bn_b[2], bn_running_mean[2], bn_running_var[2], bn_momentum,
                                scale + 96, shift + 96, smean + 96, sinv + 96, h->status);
-        hipLaunchKernelGGL(bn_relu_pool_kernel<true>, dim3(grid_for((size_t)B * 8 * d.wp3 * 32)), dim3(256), 0, st, p.z3,
-                           scale + 96, shift + 96, p.x0, B, 16, d.wp2, 128, 8, d.wp3, 512.0f, h->status);
+        if (ragged)
+            hipLaunchKernelGGL((bn_relu_pool_kernel<true, true>), dim3(grid_for((size_t)B * 8 * d.wp3 * 32)), dim3(256), 0, st, p.z3,
+                               scale + 96, shift + 96, p.x0, B, 16, d.wp2, 128, 8, d.wp3, 512.0f, h->status, rg.sb);
+        else
+            hipLaunchKernelGGL(bn_relu_pool_kernel<true>, dim3(grid_for((size_t)B * 8 * d.wp3 * 32)), dim3(256), 0, st, p.z3,
+                               scale + 96, shift + 96, p.x0, B, 16, d.wp2, 128, 8, d.wp3, 512.0f, h->status, (const int*)nullptr);
     }
     SIR_KCHECK();
 
@@ -146,8 +168,9 @@ extern "C" int sir_model_train_fwd_cfg(sir_handle* h, const sir_model_weights* w
                                      (const unsigned short*)(p.wsl0 + WS_DIR0), w->gru_b_ih[0], w->gru_b_ih[1], p.gi, 1536, M, 768, 1024));
     }
     {   SirProfScope prof(h, SIR_K_T_GRU0, st);
+        if (ragged) hipLaunchKernelGGL(ragged_zero_tail_kernel, dim3(S, B), dim3(256), 0, st, p.y0, rg.sb, S, 512, 1, 0);
         SIR_TRY(sir_launch_gru_quad(h, st, true, p.gi, w->gru_w_hh[0], w->gru_w_hh[1], w->gru_b_hh[0], w->gru_b_hh[1], p.y0, B, S, p.g0, nullptr,
-                                    (const char*)p.wht, (const char*)p.wht + GRU_FRAG_BYTES));
+                                    (const char*)p.wht, (const char*)p.wht + GRU_FRAG_BYTES, ragged ? rg.sb : nullptr, ragged));
     }
     const float* y0in = p.y0;
     {   SirProfScope prof(h, SIR_K_T_GEMM_IH1, st);
@@ -162,10 +185,17 @@ extern "C" int sir_model_train_fwd_cfg(sir_handle* h, const sir_model_weights* w
                                      (const unsigned short*)(p.wsl1 + WS_DIR1), w->gru_b_ih[2], w->gru_b_ih[3], p.gi, 1536, M, 768, 512));
     }
     {   SirProfScope prof(h, SIR_K_T_GRU1, st);
+        if (ragged) hipLaunchKernelGGL(ragged_zero_tail_kernel, dim3(S, B), dim3(256), 0, st, p.y1, rg.sb, S, 512, 1, 0);
         SIR_TRY(sir_launch_gru_quad(h, st, true, p.gi, w->gru_w_hh[2], w->gru_w_hh[3], w->gru_b_hh[2], w->gru_b_hh[3], p.y1, B, S, p.g1, nullptr,
-                                    (const char*)p.wht + 2 * GRU_FRAG_BYTES, (const char*)p.wht + 3 * GRU_FRAG_BYTES));
+                                    (const char*)p.wht + 2 * GRU_FRAG_BYTES, (const char*)p.wht + 3 * GRU_FRAG_BYTES, ragged ? rg.sb : nullptr, ragged));
     }
     SirProfScope prof_head(h, SIR_K_T_HEAD, st);
+    if (ragged) {                                            // (ctx is saved for the backward; a clip of width 0: NaN logits)
+        hipLaunchKernelGGL(attention_pool_ragged_kernel, dim3(B), dim3(256), 0, st, p.y1, w->attn_w, w->attn_b, p.ctx, S, w->fc_w,
+                           w->fc_b, w->num_classes, logits, (long long*)nullptr, rg.sb, (const int*)nullptr);
+        SIR_KCHECK();
+        return SIR_OK;
+    }
     // live bn1 statistics: the sum of the squared features (a moment of conv1_moments_kernel) is finite only if every feature is; if
     // it is not, every row's logits are NaN -- batch statistics carry one bad feature into all of them (ReLU / max-pool drop NaNs)
     hipLaunchKernelGGL(attention_pool_kernel, dim3(B), dim3(256), 0, st, p.y1, w->attn_w, w->attn_b, p.ctx, S, w->fc_w,
@@ -173,4 +203,27 @@ extern "C" int sir_model_train_fwd_cfg(sir_handle* h, const sir_model_weights* w
                        cfg->bn_frozen[0] ? (const double*)nullptr : (const double*)p.c1m + c1_r_index(4, 4));
     SIR_KCHECK();
     return SIR_OK;
+}
+
+extern "C" int sir_model_train_fwd_cfg(sir_handle* h, const sir_model_weights* w, float* const bn_running_mean[3],
+                                       float* const bn_running_var[3], const float* feats, int batch, int t_frames,
+                                       float bn_momentum, float dropout_p, uint64_t dropout_seed, const sir_train_config* cfg,
+                                       float* logits, void* workspace, size_t workspace_bytes, void* stream_) {
+    return train_fwd_impl("sir_model_train_fwd", h, w, bn_running_mean, bn_running_var, feats, nullptr, batch, t_frames, bn_momentum, dropout_p,
+                          dropout_seed, cfg ? cfg : &kTrainAllLive, logits, workspace, workspace_bytes, stream_);
+}
+
+extern "C" int sir_model_train_fwd_ragged(sir_handle* h, const sir_model_weights* w, const float* const bn_running_mean[3],
+                                          const float* const bn_running_var[3], const float* feats, const int32_t* frames, int batch,
+                                          int t_frames, float dropout_p, uint64_t dropout_seed, const sir_train_config* cfg,
+                                          float* logits, void* workspace, size_t workspace_bytes, void* stream_) {
+    if (!cfg || !cfg->bn_frozen[0] || !cfg->bn_frozen[1] || !cfg->bn_frozen[2]) {
+        sir_set_error("sir_model_train_fwd_ragged: lengths (frames per clip) need every BatchNorm on its frozen running statistics "
+                      "(bn_frozen = {1, 1, 1}): with batch statistics a clip has no result of its own");
+        return SIR_EUNSUPPORTED;
+    }
+    if (!frames) { sir_set_error("sir_model_train_fwd_ragged: NULL frames"); return SIR_EINVAL; }
+    // (frozen blocks read the running statistics and never write them: bn_fold_running_kernel)
+    return train_fwd_impl("sir_model_train_fwd_ragged", h, w, (float* const*)bn_running_mean, (float* const*)bn_running_var, feats, frames,
+                          batch, t_frames, 0.0f, dropout_p, dropout_seed, cfg, logits, workspace, workspace_bytes, stream_);
 }

@@ -255,4 +255,4 @@ int sir_launch_gru_quad(sir_handle* h, hipStream_t st, bool save, const float* g
 void sir_prep_whh_quad(sir_handle* h, hipStream_t st, const float* whh, void* frag);     // -> GRU_FRAG_BYTES (gru_frag_prep.h)
 int sir_launch_gru_bwd_quad(sir_handle* h, hipStream_t st, const float* dy, const float* gates, const float* y, const float* whh0,
                             const float* whh1, float* dgi, float* dgh, float* bsum_i, float* bsum_h, int B, int S,
-                            const void* wfrag0 = nullptr, const void* wfrag1 = nullptr);
+                            const void* wfrag0 = nullptr, const void* wfrag1 = nullptr, const int* nlive = nullptr);

@@ -26,14 +26,15 @@ __device__ __forceinline__ void bwd_scale_pair(unsigned maxbits, int static_exp,
     out[0] = __uint_as_float((unsigned)(127 + g) << 23);
     out[1] = __uint_as_float((unsigned)(127 - g) << 23);
 }
+//   slen (ragged step; else NULL): a row whose clip has slen[b] < 1 steps counts as a row of zeros (its dlogits are not looked at).
 static __global__ __launch_bounds__(1024) void bwd_scale_kernel(const float* __restrict__ dlogits, int B, int C, int static_exp, int per_row,
-                                                                float* __restrict__ bsc) {
+                                                                float* __restrict__ bsc, const int* __restrict__ slen) {
     __shared__ unsigned red[16];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     if (per_row) {
         const int b = blockIdx.x * 16 + wv;
         if (b < B) {
-            unsigned v = lane < C ? (__float_as_uint(dlogits[(size_t)b * C + lane]) & 0x7fffffffu) : 0u;
+            unsigned v = lane < C && !(slen && slen[b] < 1) ? (__float_as_uint(dlogits[(size_t)b * C + lane]) & 0x7fffffffu) : 0u;
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o));
             if (lane == 0) bwd_scale_pair(v, static_exp, bsc + 2 * (1 + b));
@@ -43,7 +44,12 @@ static __global__ __launch_bounds__(1024) void bwd_scale_kernel(const float* __r
     }
     unsigned m = 0u;
     const size_t n = (size_t)B * C;
-    for (size_t i = tid; i < n; i += 1024) m = max(m, __float_as_uint(dlogits[i]) & 0x7fffffffu);
+    if (slen) {
+        for (size_t i = tid; i < n; i += 1024)
+            if (slen[i / C] >= 1) m = max(m, __float_as_uint(dlogits[i]) & 0x7fffffffu);
+    } else {
+        for (size_t i = tid; i < n; i += 1024) m = max(m, __float_as_uint(dlogits[i]) & 0x7fffffffu);
+    }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
     if (lane == 0) red[wv] = m;
@@ -64,11 +70,20 @@ __device__ __forceinline__ void head_bwd_utt(int b, const float* __restrict__ dl
                                              const float* __restrict__ y, const float* __restrict__ aw,
                                              const float* __restrict__ ab, float* __restrict__ dy,
                                              float* __restrict__ daw_part, float* __restrict__ dab_part,
-                                             int S, int C, float gscale) {
+                                             int S, int C, float gscale, int Sl) {
+    // Sl <= S: the utterance's own steps (ragged step; S otherwise) -- scores, softmax and sums over t < Sl, dy rows t >= Sl are zeros
     __shared__ float dctx[512];
     __shared__ float sc[ATT_MAX_S], ds[ATT_MAX_S];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const float* yb = y + (size_t)b * S * 512;
+    if (Sl < 1) {                                             // (whole block, before any barrier: a clip of width 0 -- nothing but zeros)
+        for (int c = tid; c < 512; c += 256) {
+            for (int t = 0; t < S; ++t) dy[((size_t)b * S + t) * 512 + c] = 0.0f;
+            daw_part[(size_t)b * 512 + c] = 0.0f;
+        }
+        if (tid == 0) dab_part[b] = 0.0f;
+        return;
+    }
     for (int c = tid; c < 512; c += 256) {
         float a = 0.0f;
         for (int j = 0; j < C; ++j) a = fmaf(dlogits[(size_t)b * C + j], fcw[(size_t)j * 512 + c], a);
@@ -82,12 +97,12 @@ __device__ __forceinline__ void head_bwd_utt(int b, const float* __restrict__ dl
 #pragma unroll
     for (int i = 0; i < 8; ++i) dc8[i] = dctx[lane + 64 * i];
     // four time steps per wave and round, all 32 loads issued before the first reduction (cf. attention_pool_kernel)
-    for (int t0 = 4 * wv; t0 < S; t0 += 16) {
+    for (int t0 = 4 * wv; t0 < Sl; t0 += 16) {
         float v[4][8];
 #pragma unroll
         for (int k = 0; k < 4; ++k)
 #pragma unroll
-            for (int i = 0; i < 8; ++i) v[k][i] = (t0 + k < S) ? yb[(size_t)(t0 + k) * 512 + lane + 64 * i] : 0.0f;
+            for (int i = 0; i < 8; ++i) v[k][i] = (t0 + k < Sl) ? yb[(size_t)(t0 + k) * 512 + lane + 64 * i] : 0.0f;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             float d = 0.0f, g = 0.0f;
@@ -98,22 +113,22 @@ __device__ __forceinline__ void head_bwd_utt(int b, const float* __restrict__ dl
             }
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) { d += __shfl_xor(d, o); g += __shfl_xor(g, o); }
-            if (lane == 0 && t0 + k < S) { sc[t0 + k] = d + ab[0]; ds[t0 + k] = g; }   // ds holds dw_t for now
+            if (lane == 0 && t0 + k < Sl) { sc[t0 + k] = d + ab[0]; ds[t0 + k] = g; }   // ds holds dw_t for now
         }
     }
     __syncthreads();
     // softmax weights once per time step (thread t)
     __shared__ float ex[ATT_MAX_S];
     float mx = -INFINITY;
-    for (int t = 0; t < S; ++t) mx = fmaxf(mx, sc[t]);
-    for (int t = tid; t < S; t += 256) ex[t] = expf(sc[t] - mx);
+    for (int t = 0; t < Sl; ++t) mx = fmaxf(mx, sc[t]);
+    for (int t = tid; t < Sl; t += 256) ex[t] = expf(sc[t] - mx);
     __syncthreads();
     float den = 0.0f;
-    for (int t = 0; t < S; ++t) den += ex[t];
+    for (int t = 0; t < Sl; ++t) den += ex[t];
     float wdw = 0.0f;
-    for (int t = 0; t < S; ++t) wdw = fmaf(ex[t] / den, ds[t], wdw);
+    for (int t = 0; t < Sl; ++t) wdw = fmaf(ex[t] / den, ds[t], wdw);
     __syncthreads();
-    for (int t = tid; t < S; t += 256) {
+    for (int t = tid; t < Sl; t += 256) {
         const float w = ex[t] / den;
         const float dst = w * (ds[t] - wdw);
         sc[t] = w;                 // now the attention weight
@@ -121,14 +136,15 @@ __device__ __forceinline__ void head_bwd_utt(int b, const float* __restrict__ dl
     }
     __syncthreads();
     float dsum = 0.0f;
-    for (int t = 0; t < S; ++t) dsum += ds[t];
+    for (int t = 0; t < Sl; ++t) dsum += ds[t];
     for (int c = tid; c < 512; c += 256) {
         const float dc = dctx[c], ac = aw[c];
         float da = 0.0f;
-        for (int t = 0; t < S; ++t) {
+        for (int t = 0; t < Sl; ++t) {
             dy[((size_t)b * S + t) * 512 + c] = gscale * fmaf(sc[t], dc, ds[t] * ac);     // (the backward's loss scale: a power of two, exact)
             da = fmaf(ds[t], yb[(size_t)t * 512 + c], da);
         }
+        for (int t = Sl; t < S; ++t) dy[((size_t)b * S + t) * 512 + c] = 0.0f;
         daw_part[(size_t)b * 512 + c] = da;
     }
     if (tid == 0) dab_part[b] = dsum;
@@ -217,16 +233,20 @@ static __global__ __launch_bounds__(256) void colsum_partial_kernel(const float*
 //   grid (C, 2): block (j, half) owns 256 columns c; the dlogits column is staged in LDS once and the loop over
 //   the batch is unrolled so that the ctx loads pipeline (the first version ran one dependent load per iteration)
 __device__ __forceinline__ void fc_wgrad_block(int j, int half, const float* __restrict__ dlogits, const float* __restrict__ ctx,
-                                               float* __restrict__ dw, float* __restrict__ db, int B, int C) {
+                                               float* __restrict__ dw, float* __restrict__ db, int B, int C, const int* __restrict__ slen) {
+    // slen (ragged step; else NULL): a row of a clip without steps counts as dlogits = 0, and its ctx row (NaN) is not used as data
     __shared__ float dl[1024];
     const int c = half * 256 + threadIdx.x;
     float a = 0.0f, sb = 0.0f;
     for (int b0 = 0; b0 < B; b0 += 1024) {
         const int nb = min(1024, B - b0);
         __syncthreads();
-        for (int i = threadIdx.x; i < nb; i += 256) dl[i] = dlogits[(size_t)(b0 + i) * C + j];
+        for (int i = threadIdx.x; i < nb; i += 256) dl[i] = (slen && slen[b0 + i] < 1) ? 0.0f : dlogits[(size_t)(b0 + i) * C + j];
         __syncthreads();
         int b = 0;
+        if (slen) {                                    // (a product with dl == 0 adds nothing: selected away, so that 0 x NaN cannot appear)
+            for (; b < nb; ++b) { a = fmaf(dl[b], dl[b] != 0.0f ? ctx[(size_t)(b0 + b) * 512 + c] : 0.0f, a); sb += dl[b]; }
+        }
         for (; b + 8 <= nb; b += 8) {
             float v[8];
 #pragma unroll
@@ -249,13 +269,16 @@ static __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __res
                                                               const float* __restrict__ ab, const float* __restrict__ ctx,
                                                               float* __restrict__ dy, float* __restrict__ daw_part,
                                                               float* __restrict__ dab_part, float* __restrict__ d_fc_w,
-                                                              float* __restrict__ d_fc_b, int B, int S, int C, const float* __restrict__ bsc, int row_scaled) {
+                                                              float* __restrict__ d_fc_b, int B, int S, int C, const float* __restrict__ bsc, int row_scaled,
+                                                              const int* __restrict__ slen) {
+    // slen (ragged step, sir_model_train_bwd_ragged; else NULL): utterance b has slen[b] <= S steps of its own
     if ((int)blockIdx.x >= B) {
         const int i = blockIdx.x - B;
-        fc_wgrad_block(i >> 1, i & 1, dlogits, ctx, d_fc_w, d_fc_b, B, C);
+        fc_wgrad_block(i >> 1, i & 1, dlogits, ctx, d_fc_w, d_fc_b, B, C, slen);
         return;
     }
-    head_bwd_utt(blockIdx.x, dlogits, fcw, y, aw, ab, dy, daw_part, dab_part, S, C, bsc[row_scaled ? 2 * (1 + blockIdx.x) : 0]);
+    head_bwd_utt(blockIdx.x, dlogits, fcw, y, aw, ab, dy, daw_part, dab_part, S, C, bsc[row_scaled ? 2 * (1 + blockIdx.x) : 0],
+                 slen ? max(0, min(S, slen[blockIdx.x])) : S);
 }
 
 // Reads two buffers and keeps nothing: a software prefetch into the last-level cache, launched on the backward's side stream (model_train_bwd.hip:
@@ -320,7 +343,10 @@ __device__ __forceinline__ bool bn_gamma_ok(float gamma, float beta) { return fa
 static __global__ __launch_bounds__(256) void bn_bwd_reduce_pooled_kernel(
     const float* __restrict__ a, const float* __restrict__ da, const float* __restrict__ z, const float* __restrict__ gamma,
     const float* __restrict__ beta, const float* __restrict__ scale, const float* __restrict__ shift, const float* __restrict__ mean,
-    const float* __restrict__ invstd, float2* __restrict__ part, int B, int H, int W, int C, int Hp, int Wp, int pix_per_block) {
+    const float* __restrict__ invstd, float2* __restrict__ part, int B, int H, int W, int C, int Hp, int Wp, int pix_per_block,
+    const int* __restrict__ wlim) {
+    // wlim (ragged step; else NULL): the pooled gradient of clip b counts as zero at columns >= wlim[b] (the data gradient of the conv
+    // above spills one column past the clip's width)
     __shared__ float rs[256], rq[256];
     const int c4n = C / 4;
     const int lanes_c = c4n < 64 ? c4n : 64;
@@ -337,6 +363,7 @@ static __global__ __launch_bounds__(256) void bn_bwd_reduce_pooled_kernel(
             for (int i = pslot; i < pix_per_block; i += pl) {
                 const size_t p = p0 + i;
                 if (p >= npix) break;
+                if (wlim && (int)(p % Wp) >= wlim[p / ((size_t)Wp * Hp)]) continue;
                 const float4 av = *reinterpret_cast<const float4*>(a + p * C + cc * 4);
                 const float4 g = *reinterpret_cast<const float4*>(da + p * C + cc * 4);
                 const float dx_ = av.x > 0.0f ? g.x : 0.0f, dy_ = av.y > 0.0f ? g.y : 0.0f;
@@ -352,6 +379,7 @@ static __global__ __launch_bounds__(256) void bn_bwd_reduce_pooled_kernel(
                 const size_t p = p0 + i;
                 if (p >= npix) break;
                 const int px = p % Wp, py = (p / Wp) % Hp, b = p / ((size_t)Wp * Hp);
+                if (wlim && px >= wlim[b]) continue;
                 const float4 g = *reinterpret_cast<const float4*>(da + p * C + cc * 4);
                 float4 zz[4], yy[4];
 #pragma unroll
@@ -497,12 +525,14 @@ __device__ __forceinline__ int route_arg(float y00, float y01, float y10, float 
 // neighbours for the routing: 5 loads per output against 1.25 here), the pooled gradient once per window
 // FROZEN (running statistics): dz = gamma * invstd_running * dy -- the mean terms are gone, and with them the mean / invstd /
 // mdy / mdyx reads (pass NULL) and the dependence on the reduce pass; z is still read for the routing
-template <bool GRU_IN, bool FROZEN = false>
+// RAGGED (ragged step): the pooled gradient of clip b counts as zero at columns >= wlim[b] -- `da` is not read there
+template <bool GRU_IN, bool FROZEN = false, bool RAGGED = false>
 __global__ __launch_bounds__(256) void bn_bwd_dz_kernel(const float* __restrict__ z, const float* __restrict__ da,
                                                          const float* __restrict__ scale, const float* __restrict__ shift,
                                                          const float* __restrict__ mean, const float* __restrict__ invstd,
                                                          const float* __restrict__ mdy, const float* __restrict__ mdyx,
-                                                         float* __restrict__ dz, int B, int H, int W, int C, int Hp, int Wp) {
+                                                         float* __restrict__ dz, int B, int H, int W, int C, int Hp, int Wp,
+                                                         const int* __restrict__ wlim = nullptr) {
     const int c4n = C / 4, Hc = (H + 1) / 2, Wc = (W + 1) / 2;           // cells cover an odd last row / column too
     const size_t total = (size_t)B * Hc * Wc * c4n;
     for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
@@ -538,7 +568,7 @@ __global__ __launch_bounds__(256) void bn_bwd_dz_kernel(const float* __restrict_
         }
         float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
         int ax = -1, ay = -1, az = -1, aw = -1;
-        if (cy < Hp && cx < Wp) {                                        // pooled window (all four pixels exist)
+        if (cy < Hp && cx < Wp && (!RAGGED || cx < wlim[b])) {           // pooled window (all four pixels exist)
             g = load_da4<GRU_IN>(da, b, cy, cx, cc, Hp, Wp, C);
             ax = route_arg(fmaf(zq[0].x, s.x, t.x), fmaf(zq[1].x, s.x, t.x), fmaf(zq[2].x, s.x, t.x), fmaf(zq[3].x, s.x, t.x));
             ay = route_arg(fmaf(zq[0].y, s.y, t.y), fmaf(zq[1].y, s.y, t.y), fmaf(zq[2].y, s.y, t.y), fmaf(zq[3].y, s.y, t.y));
@@ -574,13 +604,16 @@ __global__ __launch_bounds__(256) void bn_bwd_dz_kernel(const float* __restrict_
 // MODE 0: pass 1;  MODE 1: pass 2 (needs mdy / mdyx);  MODE 2: both in ONE pass -- (sum dy, sum dy*xhat, A[9]) with
 // A[tap] = sum dy * x_tap, the only data-dependent part of the weight gradient: the mean terms of dz are closed forms in the
 // input moments of conv1_moments_kernel (conv1_bwd_finalize_kernel).
-template <int MODE>
+// RAGGED (ragged step): frame columns >= xlim[b] of clip b are the image edge -- read as zeros, whatever bits they hold, as in the
+// forward -- and the pooled gradient counts as zero at columns >= wlim[b] (conv2's data gradient spills one column past the width).
+template <int MODE, bool RAGGED = false>
 __global__ __launch_bounds__(256) void conv1_bwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                          const float* __restrict__ da, const float* __restrict__ scale,
                                                          const float* __restrict__ shift, const float* __restrict__ mean,
                                                          const float* __restrict__ invstd, const float* __restrict__ mdy,
                                                          const float* __restrict__ mdyx, float* __restrict__ part,
-                                                         int H, int W, int Hp, int Wp) {
+                                                         int H, int W, int Hp, int Wp, const int* __restrict__ wlim = nullptr,
+                                                         const int* __restrict__ xlim = nullptr) {
     constexpr bool WGRAD = MODE == 1;
     constexpr int NV = MODE == 0 ? 2 : (MODE == 1 ? 9 : 11);
     __shared__ float tile[C1_TR * C1_TC];
@@ -588,10 +621,12 @@ __global__ __launch_bounds__(256) void conv1_bwd_kernel(const float* __restrict_
     const int b = blockIdx.z, py0 = blockIdx.y * C1_PROWS, px0 = blockIdx.x * C1_PCOLS;
     const int tid = threadIdx.x, c = tid & 31, slot = tid >> 5;
     const float* xb = x + (size_t)b * H * W;
+    int Wx = W, Wl = Wp;                                      // columns of the image that hold data / of the pooled gradient that count
+    if constexpr (RAGGED) { Wx = max(0, min(W, xlim[b])); Wl = max(0, min(Wp, wlim[b])); }
     for (int i = tid; i < C1_TR * C1_TC; i += 256) {
         const int ty = i / C1_TC, tx = i - ty * C1_TC;
         const int gy = 2 * py0 - 1 + ty, gx = 2 * px0 - 1 + tx;
-        tile[i] = (gy >= 0 && gy < H && gx >= 0 && gx < W) ? xb[(size_t)gy * W + gx] : 0.0f;
+        tile[i] = (gy >= 0 && gy < H && gx >= 0 && gx < Wx) ? xb[(size_t)gy * W + gx] : 0.0f;
     }
     float wk[9];
 #pragma unroll
@@ -622,7 +657,7 @@ __global__ __launch_bounds__(256) void conv1_bwd_kernel(const float* __restrict_
             a[q] = v;
             yv[q] = fmaf(v, s, t);
         }
-        const bool pooled = (py < Hp && px < Wp);
+        const bool pooled = (py < Hp && px < Wl);
         const float g = pooled ? da[(((size_t)b * Hp + py) * Wp + px) * 32 + c] : 0.0f;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
@@ -731,23 +766,29 @@ constexpr int C1D_ZR = C1D_TH + 2, C1D_ZC = C1D_TW + 2;       // dz pixels kept:
 constexpr int C1D_ZS = 20;                                    // floats per dz pixel in LDS: 16 channels + 4 pad
 static_assert(C1D_TH * C1D_TW == 2 * 256, "two output pixels per thread");
 
-template <bool FROZEN>
+// RAGGED (ragged step; FROZEN only): frame columns >= xlim[b] are the image edge (read as zeros, as in the forward), the pooled
+// gradient counts as zero at columns >= wlim[b], and dx is written as zero at columns >= xlim[b] (the transposed convolution spills
+// one column past an even width; the last column of an odd width is inside the clip: conv1 read it, and it keeps its gradient).
+template <bool FROZEN, bool RAGGED = false>
 __global__ __launch_bounds__(256, 3) void conv1_bwd_data_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                               const float* __restrict__ da, const float* __restrict__ scale,
                                                               const float* __restrict__ shift, const float* __restrict__ mean,
                                                               const float* __restrict__ invstd, const float* __restrict__ mdy,
                                                               const float* __restrict__ mdyx, float* __restrict__ dx,
-                                                              int H, int W, int Hp, int Wp, const float* __restrict__ bsc, int row_scaled) {
+                                                              int H, int W, int Hp, int Wp, const float* __restrict__ bsc, int row_scaled,
+                                                              const int* __restrict__ wlim = nullptr, const int* __restrict__ xlim = nullptr) {
     const float unscale = bsc[row_scaled ? 2 * (1 + blockIdx.z) + 1 : 1];    // (the utterance's own scale: bwd_scale_kernel)
     __shared__ float xt[C1D_XR * C1D_XC];
     __shared__ __attribute__((aligned(16))) float dzs[C1D_ZR * C1D_ZC * C1D_ZS];
     const int b = blockIdx.z, h0 = blockIdx.y * C1D_TH, w0 = blockIdx.x * C1D_TW;
     const int tid = threadIdx.x;
     const float* xb = x + (size_t)b * H * W;
+    int Wx = W, Wl = Wp;
+    if constexpr (RAGGED) { Wx = max(0, min(W, xlim[b])); Wl = max(0, min(Wp, wlim[b])); }
     for (int i = tid; i < C1D_XR * C1D_XC; i += 256) {
         const int ty = i / C1D_XC, tx = i - ty * C1D_XC;
         const int gy = h0 - 3 + ty, gx = w0 - 3 + tx;
-        xt[i] = (gy >= 0 && gy < H && gx >= 0 && gx < W) ? xb[(size_t)gy * W + gx] : 0.0f;
+        xt[i] = (gy >= 0 && gy < H && gx >= 0 && gx < Wx) ? xb[(size_t)gy * W + gx] : 0.0f;
     }
     const int lc = tid & 31, rp = tid >> 5;                   // gather: output column, pair of output rows
     float acc0 = 0.0f, acc1 = 0.0f;
@@ -762,7 +803,7 @@ __global__ __launch_bounds__(256, 3) void conv1_bwd_data_kernel(const float* __r
             const int cell = (it * 256 + tid) >> 2;
             wcy[it] = cell / C1D_CC; wcx[it] = cell - wcy[it] * C1D_CC;
             const int gcy = (h0 >> 1) - 1 + wcy[it], gcx = (w0 >> 1) - 1 + wcx[it];
-            const bool pooled = cell < C1D_CR * C1D_CC && gcy >= 0 && gcy < Hp && gcx >= 0 && gcx < Wp;
+            const bool pooled = cell < C1D_CR * C1D_CC && gcy >= 0 && gcy < Hp && gcx >= 0 && gcx < Wl;
             g[it] = pooled ? *reinterpret_cast<const float4*>(da + (((size_t)b * Hp + gcy) * Wp + gcx) * 32 + c0) : make_float4(0.f, 0.f, 0.f, 0.f);
             if (!pooled) wcy[it] |= 0x100;                    // (bit 8: no pooled gradient for this window)
             if (cell >= C1D_CR * C1D_CC) wcy[it] = -1;
@@ -845,8 +886,9 @@ __global__ __launch_bounds__(256, 3) void conv1_bwd_data_kernel(const float* __r
     }
     const int gx = w0 + lc, gy = h0 + 2 * rp;
     if (gx < W) {
-        if (gy < H) dx[((size_t)b * H + gy) * W + gx] = acc0 * unscale;
-        if (gy + 1 < H) dx[((size_t)b * H + gy + 1) * W + gx] = acc1 * unscale;
+        const bool in = !RAGGED || gx < Wx;
+        if (gy < H) dx[((size_t)b * H + gy) * W + gx] = in ? acc0 * unscale : 0.0f;
+        if (gy + 1 < H) dx[((size_t)b * H + gy + 1) * W + gx] = in ? acc1 * unscale : 0.0f;
     }
 }
 

@@ -196,12 +196,14 @@ static __global__ void bn_fold_running_kernel(const float* __restrict__ gamma, c
 // GRU_OUT = false: NHWC [B][Hp][Wp][C];  true: [B][Wp][C*Hp] with feature = c*Hp + py (models.py:55-57)
 // An output that is not below `limit` -- the range inside which the backward's single-accumulator f16x3 contractions take this
 // tensor exactly (a2: wgrad_wino_f16x3_kernel.h, 256; x0: gemm_tn2_f16x3_kernel.h, 512) -- raises bit 12 of the status word.
+// RAGGED (sir_model_train_fwd_ragged): clip b's pooled map is wlim[b] <= Wp columns wide; the columns behind it are written as
+// zeros and their z is not read -- the next stage runs at full width and reads them as the clip's right edge.
 constexpr unsigned int SIR_STATUS_ACT_RANGE = 4096u;
-template <bool GRU_OUT>
+template <bool GRU_OUT, bool RAGGED = false>
 __global__ __launch_bounds__(256) void bn_relu_pool_kernel(const float* __restrict__ z, const float* __restrict__ scale,
                                                             const float* __restrict__ shift, float* __restrict__ out,
                                                             int B, int H, int W, int C, int Hp, int Wp, float limit,
-                                                            unsigned int* __restrict__ status) {
+                                                            unsigned int* __restrict__ status, const int* __restrict__ wlim = nullptr) {
     const int c4n = C / 4;
     bool beyond = false;
     const size_t total = (size_t)B * Hp * Wp * c4n;
@@ -223,10 +225,12 @@ __global__ __launch_bounds__(256) void bn_relu_pool_kernel(const float* __restri
         const float4 s = *reinterpret_cast<const float4*>(scale + c4 * 4);
         const float4 t = *reinterpret_cast<const float4*>(shift + c4 * 4);
         float4 best = make_float4(0.f, 0.f, 0.f, 0.f);
+        const bool live = !RAGGED || px < min(Wp, wlim[b]);
 #pragma unroll
         for (int dy = 0; dy < 2; ++dy)
 #pragma unroll
             for (int dx = 0; dx < 2; ++dx) {
+                if (!live) continue;
                 const float4 v = *reinterpret_cast<const float4*>(
                     z + (((size_t)b * H + 2 * py + dy) * W + 2 * px + dx) * C + c4 * 4);
                 best.x = fmaxf(best.x, fmaf(v.x, s.x, t.x));
@@ -277,6 +281,27 @@ static __global__ __launch_bounds__(256) void dropout_split2h_kernel(const float
         *reinterpret_cast<uint4*>(planes + i) = make_uint4(h0.x, h0.y, h1.x, h1.y);
         *reinterpret_cast<uint4*>(planes + n + i) = make_uint4(l0.x, l0.y, l1.x, l1.y);
     }
+}
+
+// Ragged step: zero where the clip has nothing, so that what runs at full width behind reads zeros, not what an earlier call left.
+//   rows form (cols == 0): a [B][S][row_floats] buffer, rows t >= lim[b] of clip b (the GRU outputs: the ragged recurrence stores no
+//     row behind a clip's last step, and the next projection, both weight-gradient GEMMs and h(t + 1) of the reverse direction's
+//     last step read them);  grid (S, B)
+//   columns form: an NHWC map [B][H][W][C], columns x >= lim[b] (conv1's map: the ragged conv1 kernel stores lim[b] columns);  grid (H, B)
+static __global__ __launch_bounds__(256) void ragged_zero_tail_kernel(float* __restrict__ a, const int* __restrict__ lim, int H, int W, int C,
+                                                                       int cols) {
+    const int b = blockIdx.y, l = max(0, lim[b]);
+    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (!cols) {                                               // H = S rows of W floats
+        const int t = blockIdx.x;
+        if (t < l) return;
+        float4* row = reinterpret_cast<float4*>(a + ((size_t)b * H + t) * W);
+        for (int i = threadIdx.x; i < W / 4; i += 256) row[i] = z4;
+        return;
+    }
+    if (l >= W) return;
+    float4* row = reinterpret_cast<float4*>(a + (((size_t)b * H + blockIdx.x) * W + l) * C);
+    for (int i = threadIdx.x; i < (W - l) * C / 4; i += 256) row[i] = z4;
 }
 
 // W_hh regrouped by 4 gate rows, [192][256][4] (PREP_WHH_BWD)

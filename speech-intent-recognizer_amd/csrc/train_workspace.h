@@ -136,7 +136,8 @@ static inline size_t tws_slab_floats(const TDims& d, bool side) {
     X(DGI1, dgi1, float, B * S * 1536)           /* gate gradients of layer 1 (TB_DGI / TB_DGH hold layer 0's): layer 1's */          \
     X(DGH1, dgh1, float, B * S * 1536)           /*   weight-gradient GEMM may run after layer 0's BPTT */                             \
     X(SLAB2, slab2, float, tws_slab_floats(d, true))         /* GRU weight-gradient slabs when that GEMM runs on the side stream */ \
-    X(BSC, bsc, float, 2 + 2 * B)                /* the backward's loss scale, pairs {scale, 1 / scale}: pair 0 the call's, pair 1 + b utterance b's */
+    X(BSC, bsc, float, 2 + 2 * B)                /* the backward's loss scale, pairs {scale, 1 / scale}: pair 0 the call's, pair 1 + b utterance b's */ \
+    X(RAG, rag, int, 4 * B)                      /* ragged step: [4][B] validated frames, W1, W2, S_b of every clip (ragged_widths_kernel) */
 
 #define SIR_TRAIN_SLOT_ENUM(id, member, type, count) TB_##id,
 enum TrainBuf { SIR_TRAIN_SLOTS(SIR_TRAIN_SLOT_ENUM) TB_COUNT };
@@ -164,6 +165,24 @@ static inline TPtrs carve(void* ws, const size_t* off) {
     p.wcb2t = p.wcb3 + 3 * WCB_W3; p.wcb3t = p.wcb2t + 3 * WCB_W2;
     p.wcb3d = p.wcb3t + 3 * WCB_W3;
     return p;
+}
+
+// Ragged step (sir_model_train_fwd_ragged / sir_model_train_bwd_ragged): the widths of clip b from the GIVEN frames[b], as the tables of
+// the ragged inference call take them (infer_tables.h) -- fw = frames[b], or 0 where it lies outside [8, T]; W1 = fw / 2, W2 = fw / 4,
+// S_b = fw / 8 -- into TB_RAG as [4][B].  A clip of width 0 has no column, no step and NaN logits; it raises bit 6 of the status word
+// (status == NULL, the backward: the forward has raised it already).  Nothing else reads `frames`: whatever it holds, every width the
+// kernels see lies inside the buffers.
+struct RagPtrs { const int *fw, *w1, *w2, *sb; };
+static inline RagPtrs rag_ptrs(const int* rag, int B) { return RagPtrs{rag, rag + B, rag + 2 * (size_t)B, rag + 3 * (size_t)B}; }
+static __global__ __launch_bounds__(256) void ragged_widths_kernel(const int* __restrict__ frames, int B, int T, int* __restrict__ rag,
+                                                                    unsigned int* __restrict__ status) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    const int f = frames[b];
+    const bool ok = f >= 8 && f <= T;
+    const int fw = ok ? f : 0;
+    rag[b] = fw; rag[B + b] = fw >> 1; rag[2 * (size_t)B + b] = fw >> 2; rag[3 * (size_t)B + b] = fw >> 3;
+    if (!ok && status) __hip_atomic_fetch_or(status, 64u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 static const sir_train_config kTrainAllLive = {{0, 0, 0}};      // what a NULL sir_train_config means: nothing frozen

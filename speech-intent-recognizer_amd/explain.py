@@ -13,7 +13,10 @@ The ``*_wave`` forms start from audio: features by ``sir_features_fwd`` (no augm
 ``sir_features_bwd`` carries ``dx`` down to the samples.  Their ``lengths`` are SAMPLE counts of zero-padded clips (what the
 featurizer takes), not the ragged model path; every clip must fit ``t_pad`` frames (``1 + L // 512 <= t_pad``).
 
-Arguments are validated before any device call; there is no CPU path and no ragged (``lengths=``) form.
+Arguments are validated before any device call; there is no CPU path.  Un-padded clips of mixed length have functions of their
+own -- ``input_gradient_ragged``, ``saliency_ragged``, ``fgsm_ragged`` (``sir_model_train_fwd_ragged`` / ``_bwd_ragged``: row ``b``
+is what clip ``b`` gives at its own length, the function ``model.eval()(x, lengths=...)`` scores); the ``lengths=`` keywords of the
+functions for padded batches keep raising.  ``pgd`` and the waveform forms have no ragged form.
 """
 import torch
 
@@ -54,14 +57,98 @@ def _index_vector(v, bsz, name):
     return v
 
 
-def _forward(model, x):
-    """logits of the eval-semantics differentiable forward and the leaf they hang on (``x`` detached, in its own shape)."""
+def _forward(model, x, frames=None):
+    """logits of the eval-semantics differentiable forward and the leaf they hang on (``x`` detached, in its own shape).
+    ``frames`` (device int32 ``[B]``): the ragged step."""
     from . import train_ops
     leaf = x.detach().requires_grad_(True)
+    opts = (_frozen_cfg(), 0.0, False) if frames is None else (_frozen_cfg(), 0.0, False, False, frames)
     with torch.enable_grad():
         # (detached parameters: the node sees no parameter that wants a gradient)
-        logits = train_ops._TrainStep.apply(leaf, model, (_frozen_cfg(), 0.0, False), *[p.detach() for p in train_ops.param_list(model)])
+        logits = train_ops._TrainStep.apply(leaf, model, opts, *[p.detach() for p in train_ops.param_list(model)])
     return logits, leaf
+
+
+def _validate_ragged(model, x, frames):
+    """The checks of ``_validate`` with the clips' own lengths: shape and dtype of ``x``, then ``frames`` (one integer per clip;
+    a host list or CPU tensor must lie in ``[8, T]``, a device tensor is checked by the kernels).  Returns ``frames`` as a
+    tensor, still where it was; the caller checks its other arguments, then the device (``_require_device``)."""
+    if not torch.is_tensor(x) or x.dtype != torch.float32:
+        raise ValueError("x must be a float32 tensor [B,64,T] or [B,1,64,T]")
+    shape = tuple(x.shape)
+    if not ((len(shape) == 3 and shape[1] == 64) or (len(shape) == 4 and shape[1] == 1 and shape[2] == 64)) or shape[-1] < 8:
+        raise ValueError(f"expected [B,64,T] or [B,1,64,T] with T >= 8, got {shape}")
+    if frames is None:
+        raise ValueError("frames must hold one length per clip (for clips of one length use the function without _ragged)")
+    if not torch.is_tensor(frames):
+        frames = torch.as_tensor(list(frames))
+    if frames.is_floating_point() or frames.dtype == torch.bool:
+        raise ValueError("frames must be integers (frames per clip)")
+    if frames.dim() != 1 or frames.numel() != shape[0]:
+        raise ValueError(f"frames must hold one entry per clip: got shape {tuple(frames.shape)} for a batch of {shape[0]}")
+    if not frames.is_cuda:
+        bad = [(i, int(v)) for i, v in enumerate(frames.tolist()) if not 8 <= int(v) <= shape[-1]]
+        if bad:
+            raise ValueError(f"frames outside [8, {shape[-1]}] (clip, frames): {bad[:8]}")
+    return frames
+
+
+def _require_device(model, x):
+    if not _on_device(model, x):
+        raise _native.SirError("tensor is not on a HIP device: this path runs on MI355X only (no CPU fallback)")
+
+
+def _inside(x, frames):
+    """bool ``[B, 1, T]`` (or ``[B, 1, 1, T]``): the columns of each clip below its own length."""
+    m = torch.arange(x.shape[-1], device=x.device)[None, :] < frames[:, None]
+    return m.view((x.shape[0],) + (1,) * (x.dim() - 2) + (x.shape[-1],))
+
+
+def input_gradient_ragged(model, x, frames, target=None):
+    """``input_gradient`` for un-padded clips: row b of ``(logits, dx)`` is what ``input_gradient`` gives
+    ``x[b:b+1, ..., :frames[b]]`` on its own -- the function ``model.eval()(x, lengths=frames)`` scores -- and ``dx`` is zero at
+    columns ``>= frames[b]`` (``sir_model_train_fwd_ragged`` / ``_bwd_ragged``).  Columns behind a clip's length are never read."""
+    frames = _validate_ragged(model, x, frames)
+    bsz = x.shape[0]
+    if target is not None:
+        target = _class_vector(model, target, bsz, "target")
+    _require_device(model, x)
+    frames = frames.to(device=x.device, dtype=torch.int32).contiguous()
+    logits, leaf = _forward(model, x, frames)
+    if target is None:
+        target = logits.detach().argmax(dim=1)
+    target = target.to(device=x.device, dtype=torch.int64)
+    k = (bsz - 1).bit_length()                       # (the seed's power of two: see input_gradient)
+    seed = torch.zeros_like(logits).scatter_(1, target[:, None], 2.0 ** -k)
+    (dx,) = torch.autograd.grad(logits, leaf, grad_outputs=seed)
+    return logits.detach(), dx.mul_(2.0 ** k)
+
+
+def saliency_ragged(model, x, frames, target=None):
+    """``saliency`` for un-padded clips: ``|dx * x|`` of ``input_gradient_ragged``, shape ``[B,64,T]``, zero at columns
+    ``>= frames[b]`` whatever ``x`` holds there."""
+    _, dx = input_gradient_ragged(model, x, frames, target)
+    frames = torch.as_tensor(frames).to(device=x.device)
+    sal = torch.where(_inside(x, frames), dx * x.detach(), torch.zeros((), device=x.device))
+    return sal.abs_().view(x.shape[0], 64, x.shape[-1])
+
+
+def fgsm_ragged(model, x, labels, eps, frames):
+    """``fgsm`` for un-padded clips: the cross-entropy is the mean over the clips of the un-padded function's loss; columns
+    ``>= frames[b]`` come back as they came, bit for bit."""
+    eps = float(eps)
+    if not eps >= 0.0:
+        raise ValueError("eps must be >= 0")
+    frames = _validate_ragged(model, x, frames)
+    labels = _class_vector(model, labels, x.shape[0], "labels")
+    _require_device(model, x)
+    from . import train_ops
+    frames = frames.to(device=x.device, dtype=torch.int32).contiguous()
+    logits, leaf = _forward(model, x, frames)
+    with torch.enable_grad():
+        loss = train_ops.fused_cross_entropy(logits, labels.to(x.device))
+    (dx,) = torch.autograd.grad(loss, leaf)
+    return torch.where(_inside(x, frames), x.detach() + eps * dx.sign_(), x.detach())
 
 
 def input_gradient(model, x, target=None, lengths=None):

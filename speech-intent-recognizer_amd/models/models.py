@@ -87,9 +87,12 @@ class CNNAudioGRU(nn.Module):
     def forward(self, x, lengths=None):
         """x: [B, 64, T] or [B, 1, 64, T] float32 on the GPU -> logits [B, num_classes].
 
-        ``lengths`` (int tensor or list, frames per clip; inference only): the un-padded function -- row b is what the model
+        ``lengths`` (int tensor or list, frames per clip): the un-padded function -- row b is what the model
         gives ``x[b:b+1, ..., :lengths[b]]`` on its own (scripts/test_tts_samples.py feeds each file that way), for a whole
-        batch of mixed-length clips in one launch sequence.
+        batch of mixed-length clips in one launch sequence.  On the differentiable path it needs bn1, bn2 and bn3 in ``eval()``
+        (``finetune.freeze(model, {"bn_stats"})``): logits and gradients are then those of the un-padded function
+        (``sir_model_train_fwd_ragged`` / ``_bwd_ragged``; ``x.grad`` is zero at columns ``>= lengths[b]``).  With live batch
+        statistics a clip has no result of its own, and ``SirError`` is raised.
 
         ``self.training and torch.is_grad_enabled()`` selects the differentiable path, as before; ``model.eval()`` keeps
         calling ``sir_model_infer``.  The differentiable path is differentiable with respect to the 29 parameters and, if
@@ -100,11 +103,8 @@ class CNNAudioGRU(nn.Module):
         inter-layer dropout off, and parameters with ``requires_grad == False`` receive no gradient and cost no backward
         work where it can be skipped.  With every sub-module in training mode and every parameter trainable nothing changes."""
         if self.training and torch.is_grad_enabled():
-            if lengths is not None:
-                raise _native.SirError("lengths (un-padded batch inference) is not available on the differentiable training "
-                                       "path: call model.eval() or run under torch.no_grad()")
             from sir_amd import train_ops
-            return train_ops.forward_train(self, x)
+            return train_ops.forward_train(self, x, lengths=lengths)
         return ops.model_infer(self, x, self._ws, lengths=lengths)
 
     @torch.no_grad()

@@ -214,8 +214,10 @@ class _TrainStep(torch.autograd.Function):
         # opts = (sir_train_config, dropout p, step[, craft]): step == False (sir_amd.explain) draws no dropout key and leaves
         # the step counter and ``mod._sir_last_dropout`` alone; craft == True (``forward_craft``) also keeps the LIVE BatchNorm
         # blocks' running statistics, ``num_batches_tracked`` and the cached-weights epoch as they are
+        # frames (opts[4], device int32 [B] or absent / None): the ragged step, sir_model_train_fwd_ragged / _bwd_ragged
         cfg, dropout_p, step = opts[:3]
         craft = len(opts) > 3 and bool(opts[3])
+        frames = opts[4] if len(opts) > 4 else None
         lib = _native.lib()
         h = get_featurizer().handle
         x_shape = x.shape
@@ -236,16 +238,22 @@ class _TrainStep(torch.autograd.Function):
             seed = dropout_seed(next(_seed_counter))
             mod._sir_last_dropout = (seed, float(dropout_p))  # lets tests rebuild the mask (tests/dropout_host.py)
         momentum = float(mod.bn1.momentum if mod.bn1.momentum is not None else 0.1)
-        rc = lib.sir_model_train_fwd_cfg(h, C.byref(w), rm, rv, x.data_ptr(), bsz, t, momentum, float(dropout_p), seed,
-                                         C.byref(cfg), logits.data_ptr(), ws.data_ptr(), ws.numel(),
-                                         _native.current_stream_ptr())
-        _native.check(rc, "sir_model_train_fwd_cfg")
+        if frames is not None:
+            rc = lib.sir_model_train_fwd_ragged(h, C.byref(w), rm, rv, x.data_ptr(), frames.data_ptr(), bsz, t, float(dropout_p), seed,
+                                                C.byref(cfg), logits.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                _native.current_stream_ptr())
+            _native.check(rc, "sir_model_train_fwd_ragged")
+        else:
+            rc = lib.sir_model_train_fwd_cfg(h, C.byref(w), rm, rv, x.data_ptr(), bsz, t, momentum, float(dropout_p), seed,
+                                             C.byref(cfg), logits.data_ptr(), ws.data_ptr(), ws.numel(),
+                                             _native.current_stream_ptr())
+            _native.check(rc, "sir_model_train_fwd_cfg")
         live = [] if craft else [getattr(mod, f"bn{i + 1}").num_batches_tracked for i in range(3) if not cfg.bn_frozen[i]]
         if live:                                     # frozen statistics: nothing was written, cached layouts stay valid
             ops.bump_weights_epoch()                 # BN running statistics were updated in place
             torch._foreach_add_(live, 1)
         ctx.mod, ctx.x, ctx.seed, ctx.dropout_p, ctx.ws, ctx.cfg = mod, x, seed, float(dropout_p), ws, cfg
-        ctx.x_shape = x_shape
+        ctx.x_shape, ctx.frames = x_shape, frames
         return logits
 
     @staticmethod
@@ -265,6 +273,12 @@ class _TrainStep(torch.autograd.Function):
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
 
         def run(part):
+            if ctx.frames is not None:
+                rc = lib.sir_model_train_bwd_ragged(h, C.byref(w), x.data_ptr(), ctx.frames.data_ptr(), dlogits.data_ptr(), bsz, t,
+                                                    ctx.dropout_p, ctx.seed, C.byref(ctx.cfg), C.byref(gstruct),
+                                                    dx.data_ptr() if dx is not None else None, ctx.ws.data_ptr(), ctx.ws.numel(), part,
+                                                    _native.current_stream_ptr())
+                return _native.check(rc, "sir_model_train_bwd_ragged")
             if dx is None:
                 rc = lib.sir_model_train_bwd_cfg(h, C.byref(w), x.data_ptr(), dlogits.data_ptr(), bsz, t, ctx.dropout_p, ctx.seed,
                                                  C.byref(ctx.cfg), C.byref(gstruct), ctx.ws.data_ptr(), ctx.ws.numel(), part,
@@ -353,16 +367,35 @@ def zero_contribution_step(mod):
             p.grad = v
 
 
-def forward_train(mod, x):
+def ragged_frames(lengths, x):
+    """``lengths`` of a ragged differentiable call as the device int32 ``[B]`` the kernels take: ``ops._as_lengths`` after the
+    shape checks on ``x`` -- a host list or CPU tensor is validated here, before any launch; a device tensor goes through the
+    status word (bad rows come back NaN, ``ops.check_status`` raises)."""
+    xf = ops._as_features(x)
+    return ops._as_lengths(lengths, xf.shape[0], xf.shape[2], x.device)
+
+
+def forward_train(mod, x, lengths=None):
     """Training-mode forward of ``CNNAudioGRU`` (batch-statistics BN, inter-layer dropout
     ``mod.gru.dropout``), differentiable wrt the module's parameters and, if ``x.requires_grad``, wrt ``x`` (``x.grad`` has
     the shape of ``x``; a double backward raises).  The sub-modules' own flags are honoured as torch
     honours them: ``bnK.eval()`` freezes that block's statistics (forward and backward), ``gru.eval()`` turns the dropout
     off, and a parameter with ``requires_grad == False`` gets no gradient -- the backward stops where the trainable
-    parameters stop (``sir_model_train_bwd_cfg``)."""
+    parameters stop (``sir_model_train_bwd_cfg``).
+
+    ``lengths`` (int tensor or list, frames per clip): the un-padded function and its gradient -- row b is what the model gives
+    ``x[b:b+1, ..., :lengths[b]]`` on its own (``sir_model_train_fwd_ragged`` / ``_bwd_ragged``).  It needs bn1, bn2 and bn3 in
+    ``eval()``, which is what ``finetune.freeze(model, {"bn_stats"})`` leaves; otherwise ``SirError``."""
+    cfg, dropout_p = step_config(mod)
+    if lengths is not None and not all(cfg.bn_frozen):
+        raise _native.SirError("lengths (un-padded clips) on the differentiable path need bn1, bn2 and bn3 on their running statistics: "
+                               "freeze them first (finetune.freeze(model, {'bn_stats'}) or bnK.eval()), call model.eval(), or run "
+                               "under torch.no_grad() -- with live batch statistics a clip has no result of its own")
     _native.require_hip(x)
     ops._as_features(x)                              # (shape / dtype checks; the node itself takes x in the caller's shape)
-    return _TrainStep.apply(x, mod, step_config(mod) + (True,), *param_list(mod))
+    if lengths is None:
+        return _TrainStep.apply(x, mod, (cfg, dropout_p, True), *param_list(mod))
+    return _TrainStep.apply(x, mod, (cfg, dropout_p, True, False, ragged_frames(lengths, x)), *param_list(mod))
 
 
 def forward_craft(mod, x):

@@ -155,8 +155,8 @@ def mel_fbank_f64(n_freqs=N_FREQS, f_min=0.0, f_max=8000.0, n_mels=N_MELS, sampl
     return fb
 
 
-def extract_features_f64(wave, stages=False):
-    x = np.asarray(wave, dtype=np.float64)[: int(MAX_DURATION_S * SAMPLE_RATE)]
+def extract_features_f64(wave, stages=False, max_duration=MAX_DURATION_S):
+    x = np.asarray(wave, dtype=np.float64)[: int(max_duration * SAMPLE_RATE)]
     if x.size <= N_FFT // 2:
         return None
     pad = N_FFT // 2

@@ -31,6 +31,12 @@ def features_f64(x, t_pad=None, shift=0, noise=None, time_mask=None, freq_mask=N
     if noise is not None:
         x = x + noise
     xp = torch.nn.functional.pad(x[None, None], (N_FFT // 2, N_FFT // 2), mode="reflect")[0, 0]
+    return features_from_padded_f64(xp, t_pad, time_mask, freq_mask)
+
+
+def features_from_padded_f64(xp, t_pad=None, time_mask=None, freq_mask=None):
+    """``features_f64`` from the reflect-padded clip on (float64 [L + 1024]): differentiated with respect to ``xp`` it tells what
+    each padded position contributes before the padding folds it back onto a sample."""
     frames = xp.unfold(0, N_FFT, HOP) * _WIN                             # [T, 1024]
     spec = torch.fft.rfft(frames, dim=1)
     mel = (spec.real ** 2 + spec.imag ** 2) @ _FB                        # [T, 64]

@@ -16,8 +16,9 @@
 // Noise and the features follow in sir_features_fwd.  Cents 0 / factor 1 are the identity (a copy), not WSOLA at 1.
 //
 // Kernels: wsola_kernel = one 256-thread workgroup per utterance (each utterance is a sequential chain of segments: segment
-// j's tail `ob` depends on off_{j-1}; utterances are independent).  Per segment every thread owns one search candidate and
-// sums its O squared differences from LDS; a wave-shuffle + LDS argmin breaks ties toward the lower index.  The segment's
+// j's tail `ob` depends on off_{j-1}; utterances are independent).  Per segment every thread owns one search candidate (two
+// where W > 256, above 17.4 kHz) and sums its O squared differences from LDS; the thread's own comparison, a wave-shuffle
+// and an LDS argmin all break ties toward the lower index.  The segment's
 // whole source window z[p_j .. p_j + W + S) (1547 samples at 16 kHz) sits in one of two LDS buffers: the next segment's
 // window does not depend on the search (p_{j+1} is known), so its global loads are issued before the search and land in
 // the other buffer after it -- no load latency on the chain.  pitch_resample_kernel = a gather of ~14 taps per output
@@ -77,13 +78,15 @@ __device__ __forceinline__ bool row_factor(int mode, const float* factor, int b,
 
 // One tempo pass.  src rows: [batch][src_stride] (WT = float or PCM16), row length min(lengths[b], max_len), read shifted
 // by shift[b] (optional).  dst rows: [batch][dst_stride] f32, [0, Nc) written, [Nc, cap) zeroed, Nc = min(int(L/f+.5), cap).
+// guard_cents (optional; the speed pass behind a pitch pass): a row whose cents the pitch pass rejected stays rejected here
+// (zeroed, length 0), whatever its tempo.
 template <typename WT>
 __global__ __launch_bounds__(kThreads) void wsola_kernel(const WT* __restrict__ src, long long src_stride, const int* __restrict__ lengths,
                                                          int max_len, const int* __restrict__ shift, int mode,
                                                          const float* __restrict__ factor, float* __restrict__ dst, long long dst_stride,
                                                          int cap, int vec, int* __restrict__ dst_len, int* __restrict__ offsets,
                                                          int max_segments, int pass, unsigned int* __restrict__ status, int S, int W,
-                                                         int O, int H) {
+                                                         int O, int H, const float* __restrict__ guard_cents) {
     __shared__ float reg[2][kMaxRegion];     // source windows z[p_j .. p_j + W + S), double-buffered over j
     __shared__ float ob[2][kMaxO];           // tail of the previous segment, double-buffered over j
     __shared__ float rv[kThreads / SIR_WAVE];
@@ -97,7 +100,7 @@ __global__ __launch_bounds__(kThreads) void wsola_kernel(const WT* __restrict__ 
     float* y = dst + (size_t)b * dst_stride;
 
     double f;
-    if (!row_factor(mode, factor, b, &f)) {
+    if (!row_factor(mode, factor, b, &f) || (guard_cents && !(fabsf(guard_cents[b]) <= kMaxCents))) {
         if (tid == 0) {
             __hip_atomic_fetch_or(status, kStatusBadFactor, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (dst_len) dst_len[b] = 0;
@@ -279,9 +282,9 @@ WsLayout ws_layout(int batch, int max_len) {
 template <typename WT>
 void launch_wsola(hipStream_t st, const WT* src, long long src_stride, const int* lengths, int max_len, const int* shift, int mode,
                   const float* factor, float* dst, long long dst_stride, int cap, int vec, int* dst_len, int* offsets, int max_segments,
-                  int pass, unsigned int* status, const Geom& g, int batch) {
+                  int pass, unsigned int* status, const Geom& g, int batch, const float* guard_cents = nullptr) {
     hipLaunchKernelGGL(wsola_kernel<WT>, dim3(batch), dim3(kThreads), 0, st, src, src_stride, lengths, max_len, shift, mode, factor, dst,
-                       dst_stride, cap, vec, dst_len, offsets, max_segments, pass, status, g.S, g.W, g.O, g.H);
+                       dst_stride, cap, vec, dst_len, offsets, max_segments, pass, status, g.S, g.W, g.O, g.H, guard_cents);
 }
 
 template <typename WT>
@@ -313,7 +316,7 @@ int perturb_impl(sir_handle* h, const WT* wave, int64_t wave_stride, const int32
     rc = sir_check_hip(hipGetLastError(), "pitch_resample_kernel");
     if (rc != SIR_OK || !tempo) return rc;
     launch_wsola<float>(st, yb, w.y_stride, lengths, max_len, nullptr, kModeTempo, tempo, out, (long long)out_stride, max_out_len, out_vec,
-                        out_lengths, offsets_out, max_segments, 1, h->status, g, batch);
+                        out_lengths, offsets_out, max_segments, 1, h->status, g, batch, pitch_cents);
     return sir_check_hip(hipGetLastError(), "wsola_kernel (speed)");
 }
 

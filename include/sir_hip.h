@@ -899,6 +899,81 @@ size_t sir_temperature_fit_workspace_bytes(int n_rows);
 int sir_temperature_fit(sir_handle* h, const float* logits, const int64_t* labels, int n_rows, int num_classes, int iters,
                         float* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- slot heads: one logit row as several independent softmax segments (DESIGN.md section 4 "Slot heads") --------------
+ * A slot layout is n_slots (1 .. 8) segment widths C_0 .. C_{G-1}, each >= 1, with sum C_g == num_classes <= 64.  Slot g owns
+ * the logit columns [start_g, start_g + C_g), start_g = the sum of the widths before it.  Labels are int64 [batch][n_slots],
+ * row-major; entry g lies in [0, C_g), local to the slot, or is -100.  The model is unchanged (fc writes the num_classes logits);
+ * sir_model_infer's argmax stays the argmax over the WHOLE row, which means nothing under a slot layout.
+ * Common to the calls below, as to their single-head relatives:
+ *   slot_sizes : HOST int32[n_slots].
+ *   Every argument is checked before the first launch -- the layout rules above, the sum against num_classes, NULLs, alignment
+ *   (f32 / int32 pointers 4 bytes, int64 labels and the state 8 bytes), k -- and a refused call (SIR_EINVAL; a too small state
+ *   SIR_ENOMEM) writes nothing.  Only kernels are launched (legal under stream capture), nothing allocates, nothing
+ *   synchronises with the host.  No floating-point atomics: results are bit-reproducible run to run.
+ *   Per slot the arithmetic is the single-head call's arithmetic on the segment; what is promised below as "bit-identical to
+ *   X on a contiguous copy of the segment" means X called with logits = the [batch][C_g] copy of the segment's columns, labels =
+ *   column g of the labels, num_classes = C_g.
+ *
+ * sir_ce_loss_slots: sum over slots of weighted soft-target cross-entropies.
+ *   labels_a, labels_b : device int64 [batch][n_slots]; labels_b NULL = no second label
+ *   lam                : device f32[batch], NULL = all 1, read only when labels_b is given; one value per row for all its slots
+ *   label_smoothing    : host float eps in [0, 1); slot g is smoothed with eps / C_g
+ *   slot_weights       : HOST f32[n_slots], finite and >= 0 (else SIR_EINVAL); NULL = all 1
+ *   slot_loss          : optional, device f32[n_slots]: entry g = the mean over the rows whose labels_a[b][g] != -100 of the
+ *                        soft-target cross-entropy of segment g -- sir_ce_loss_soft's loss on that segment (no such row: NaN)
+ *   loss               : device f32[1] = sum_g w_g * slot_loss[g]: fp32 products added in fp32 in slot order, starting from +0
+ *   dlogits            : optional, [batch][num_classes]; segment g = what sir_ce_loss_soft writes for that segment with
+ *                        grad_scale replaced by the fp32 product grad_scale * w_g (a zero weight: zeros on finite logits)
+ *   A -100 in slot g takes the row out of slot g only: zeros in that segment of dlogits, not in that slot's divisor.  Any other
+ *   label of either array outside [0, C_g) makes slot_loss[g] and loss NaN and is reported by sir_check_status (SIR_EINVAL),
+ *   as for sir_ce_loss.  slot_loss[g] and segment g of dlogits are bit-identical to sir_ce_loss_soft on a contiguous copy of
+ *   the segment (which, with labels_b == NULL and label_smoothing == 0, is sir_ce_loss); with n_slots == 1 and a NULL or unit
+ *   weight so is loss.  One workgroup of 256 threads walks the slots in order, one thread per row as sir_ce_loss; widths <= 32
+ *   and > 32 take the register-array lengths sir_ce_loss takes for them and may be mixed in one layout.
+ *
+ * sir_classify_slots: segment-wise softmax + top-k, one wavefront per row walking its slots.
+ *   inv_temperature : DEVICE f32[n_slots], one beta per slot; NULL = all 1
+ *   probs           : optional, [batch][num_classes] = the segment-wise softmax
+ *   topk_idx        : int32 [batch][n_slots][k], topk_prob f32 [batch][n_slots][k], 1 <= k <= 8.  Indices are LOCAL to the slot;
+ *                     ranks >= C_g hold -1 / 0.  Order and softmax are sir_classify's (descending logit, ties by ascending
+ *                     index, den = 1 + rest).
+ *   joint_prob      : optional, f32[batch] = the fp32 product, in slot order, of the slots' rank-0 probabilities
+ *   A NaN or an infinity in segment g of a row makes that slot's outputs of the row NaN / -1 (all k ranks) and the row's
+ *   joint_prob NaN; its other slots and all other rows are unaffected.  Per slot the outputs are bit-identical to sir_classify
+ *   on a contiguous copy of the segment with that slot's beta.
+ *
+ * sir_eval_accumulate_slots adds one batch into `state`, a caller-owned, 8-byte aligned device buffer of
+ *   sir_eval_slots_state_bytes(slot_sizes, n_slots, n_bins) bytes (0 for arguments out of range), zeroed by the caller before
+ *   the first batch.  1 <= n_bins <= 64.  The state is n_slots single-head states back to back -- state g has exactly the
+ *   layout of sir_eval_state_bytes(C_g, n_bins), scratch included -- followed by one joint block, every field 8 bytes wide
+ *   (M = n_bins):
+ *     int64  n                  rows counted jointly
+ *     int64  exact_match        of those, the rows whose every slot's prediction (rank 0) is its label
+ *     int64  slots_correct[9]   entry j: counted rows with exactly j slots right (entries above n_slots stay 0)
+ *     double nll_sum            per counted row the double sum, in slot order, of the slots' fp32 terms log1pf(rest) - d[label]
+ *     int64  bin_count[M]       counted rows by joint confidence: min(M - 1, (int)floorf(joint_prob * M)), joint_prob as
+ *                               sir_classify_slots forms it
+ *     int64  bin_correct[M]     of those, the exact matches
+ *     double bin_conf_sum[M]    sum of joint_prob over the bin's rows
+ *     int64  n_excluded         rows not counted jointly
+ *     double scratch[64][M+1]   the call's own workspace, as in the single-head state
+ *   Slot state g treats row b by labels[b][g] and segment g exactly as sir_eval_accumulate does (n_ignored, bad label -> status
+ *   word, n_nonfinite, counted), with inv_temperature[g] (DEVICE f32[n_slots], NULL = all 1); after identical call sequences
+ *   its integer fields and doubles are bit-identical to sir_eval_accumulate on contiguous copies.  A row counts in the joint
+ *   block iff every slot has a label in [0, C_g) and a finite segment; every other row goes to n_excluded only.  Integer
+ *   fields: integer atomics.  Doubles: the fixed-order scheme of sir_eval_accumulate (the same workgroup and wave map, per slot
+ *   and for the joint block; a closing launch adds the workgroups' partials in order).  Calls into one state must be ordered. */
+int sir_ce_loss_slots(sir_handle* h, const float* logits, const int64_t* labels_a, const int64_t* labels_b, const float* lam,
+                      float label_smoothing, const int32_t* slot_sizes, const float* slot_weights, int n_slots, int batch,
+                      int num_classes, float* loss, float* slot_loss, float* dlogits, float grad_scale, void* stream);
+int sir_classify_slots(sir_handle* h, const float* logits, int batch, int num_classes, const int32_t* slot_sizes, int n_slots,
+                       const float* inv_temperature, int k, float* probs, int32_t* topk_idx, float* topk_prob, float* joint_prob,
+                       void* stream);
+size_t sir_eval_slots_state_bytes(const int32_t* slot_sizes, int n_slots, int n_bins);
+int sir_eval_accumulate_slots(sir_handle* h, const float* logits, const int64_t* labels, int batch, int num_classes,
+                              const int32_t* slot_sizes, int n_slots, const float* inv_temperature, int n_bins, void* state,
+                              size_t state_bytes, void* stream);
+
 /* ---- measurement -----------------------------------------------------------------------------
  * HIP-event timing of the kernels of the path, recorded on the stream they are launched on
  * (bench.py's roofline figures come from here).  mode 0 = off, 1 = every kernel, 2 = only

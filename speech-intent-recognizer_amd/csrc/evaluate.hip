@@ -357,3 +357,319 @@ extern "C" int sir_temperature_fit(sir_handle* h, const float* logits, const int
     }
     return sir_check_hip(hipGetLastError(), "sir_temperature_fit kernels");
 }
+
+// ---- slot heads (include/sir_hip.h "slot heads"): sir_classify_slots, sir_eval_accumulate_slots ---------------------------------
+// One logit row is G independent softmax segments.  Per slot the arithmetic is row_softmax on the segment, lane j holding class
+// start_g + j, so each slot's results carry the bits of the single-head call on a contiguous copy of the segment.
+//   sir_classify_slots        : classify_kernel's grid, the wave of a row walks its slots and multiplies the rank-0
+//                               probabilities in slot order.
+//   sir_eval_accumulate_slots : launch 1, grid (workgroups, G): workgroup (x, g) is eval_accumulate_kernel's workgroup x on
+//                               segment g and column g of the labels, into slot state g -- the same wave / row map, so the
+//                               doubles add up in the same order.  Launch 2, the joint block: the same map once more, the wave
+//                               of a row walks its slots.  Launch 3 adds the workgroups' partials of the G + 1 blocks in order.
+namespace {
+
+constexpr int kMaxSlots = 8;
+
+struct SlotTable {
+    int n;
+    int start[kMaxSlots], size[kMaxSlots];
+    long long base[kMaxSlots + 1];                   // 8-byte word offset of slot state g in the state; [n]: the joint block
+};
+
+// offsets into the joint block, in 8-byte words
+struct JointLayout {
+    int n, exact, slots_correct, nll, bin_count, bin_correct, bin_conf, excluded, scratch, words;
+};
+__host__ __device__ inline JointLayout joint_layout(int M) {
+    JointLayout o;
+    o.n = 0; o.exact = 1; o.slots_correct = 2; o.nll = 11; o.bin_count = 12; o.bin_correct = o.bin_count + M;
+    o.bin_conf = o.bin_correct + M; o.excluded = o.bin_conf + M; o.scratch = o.excluded + 1;
+    o.words = o.scratch + kEvalMaxBlocks * (M + 1);
+    return o;
+}
+
+__global__ __launch_bounds__(kClsWaves * SIR_WAVE) void classify_slots_kernel(const float* __restrict__ logits, int B, int NC, SlotTable tab,
+                                                                               const float* __restrict__ inv_t, int k, float* __restrict__ probs,
+                                                                               int* __restrict__ topk_idx, float* __restrict__ topk_prob,
+                                                                               float* __restrict__ joint_prob) {
+    const int lane = threadIdx.x & (SIR_WAVE - 1), wave = threadIdx.x / SIR_WAVE;
+    const float nan = __builtin_nanf("");
+    const int G = tab.n;
+    for (int b = blockIdx.x * kClsWaves + wave; b < B; b += gridDim.x * kClsWaves) {      // wave-uniform
+        float joint = 1.0f;
+        bool all_finite = true;
+        for (int g = 0; g < G; ++g) {
+            const int start = tab.start[g], C = tab.size[g];
+            const float beta = inv_t ? inv_t[g] : 1.0f;
+            const float l = lane < C ? logits[(size_t)b * NC + start + lane] : 0.0f;
+            const RowSoftmax r = row_softmax(l, lane, C, beta);
+            const float p = r.e / r.den;
+            const size_t out = ((size_t)b * G + g) * k;
+            if (r.finite) {
+                if (lane < C) {
+                    if (probs) probs[(size_t)b * NC + start + lane] = p;
+                    if (r.rank < k) { topk_idx[out + r.rank] = lane; topk_prob[out + r.rank] = p; }
+                } else if (lane < k) { topk_idx[out + lane] = -1; topk_prob[out + lane] = 0.0f; }   // ranks >= C
+                const unsigned long long top = __ballot(lane < C && r.rank == 0);          // exactly one lane
+                const int pred = top ? __ffsll((long long)top) - 1 : 0;
+                joint *= __shfl(p, pred);
+            } else {
+                all_finite = false;
+                if (lane < C && probs) probs[(size_t)b * NC + start + lane] = nan;
+                if (lane < k) { topk_idx[out + lane] = -1; topk_prob[out + lane] = nan; }
+            }
+        }
+        if (joint_prob && lane == 0) joint_prob[b] = all_finite ? joint : nan;
+    }
+}
+
+// eval_accumulate_kernel on segment blockIdx.y: the same statements, with the row's segment at logits + b * NC + start and its
+// label at labels[b * G + g] (restated rather than shared: eval_accumulate_kernel and its code stay as they are)
+__global__ __launch_bounds__(kEvalThreads) void eval_slots_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
+                                                                  int B, int NC, SlotTable tab, const float* __restrict__ inv_t, int M,
+                                                                  unsigned long long* state_all, unsigned int* status) {
+    __shared__ double s_conf[kEvalWaves][64];
+    __shared__ double s_nll[kEvalWaves];
+    __shared__ unsigned int s_bin_count[64], s_bin_correct[64], s_topk[8], s_misc[3];
+    __shared__ unsigned int s_cm[64 * 64];
+    const int lane = threadIdx.x & (SIR_WAVE - 1), wave = threadIdx.x / SIR_WAVE;
+    const int g = blockIdx.y, G = tab.n, start = tab.start[g], C = tab.size[g];
+    unsigned long long* state = state_all + tab.base[g];
+    const float beta = inv_t ? inv_t[g] : 1.0f;
+    const EvalLayout o = eval_layout(C, M);
+    s_conf[wave][lane] = 0.0;
+    for (int i = threadIdx.x; i < C * C; i += kEvalThreads) s_cm[i] = 0u;
+    if (threadIdx.x < 64) { s_bin_count[threadIdx.x] = 0u; s_bin_correct[threadIdx.x] = 0u; }
+    if (threadIdx.x < 8) s_topk[threadIdx.x] = 0u;
+    if (threadIdx.x < 3) s_misc[threadIdx.x] = 0u;
+    __syncthreads();
+    double nll = 0.0;
+    const int first_row = blockIdx.x * kEvalWaves + wave, stride = gridDim.x * kEvalWaves;
+    float l_next = (first_row < B && lane < C) ? logits[(size_t)first_row * NC + start + lane] : 0.0f;
+    long long y_next = first_row < B ? labels[(size_t)first_row * G + g] : 0ll;
+    for (int b = first_row; b < B; b += stride) {                                       // wave-uniform
+        const float l = l_next;
+        const long long y = y_next;
+        const int nb = b + stride;
+        if (nb < B) {
+            l_next = lane < C ? logits[(size_t)nb * NC + start + lane] : 0.0f;
+            y_next = labels[(size_t)nb * G + g];
+        }
+        const RowSoftmax r = row_softmax(l, lane, C, beta);
+        const int kind = row_kind(y, C, r.finite);
+        if (kind != 0) {
+            if (lane == 0) {
+                if (kind == 1) atomicAdd(&s_misc[1], 1u);
+                else if (kind == 3) atomicAdd(&s_misc[2], 1u);
+                else __hip_atomic_fetch_or(status, kStatusBadLabel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            continue;
+        }
+        const int yi = (int)y;
+        const int rank_y = __shfl(r.rank, yi);
+        const float dy = __shfl(r.d, yi);
+        const unsigned long long top = __ballot(lane < C && r.rank == 0);
+        const int pred = top ? __ffsll((long long)top) - 1 : 0;
+        const float pmax = __shfl(r.e, pred) / r.den;
+        int bin = (int)floorf(pmax * (float)M);
+        bin = bin < M - 1 ? bin : M - 1;
+        bin = bin > 0 ? bin : 0;
+        nll += (double)(log1pf(r.rest) - dy);
+        if (lane == 0) {
+            s_conf[wave][bin] += (double)pmax;
+            atomicAdd(&s_misc[0], 1u);
+            atomicAdd(&s_bin_count[bin], 1u);
+            if (pred == yi) atomicAdd(&s_bin_correct[bin], 1u);
+            atomicAdd(&s_cm[yi * C + pred], 1u);
+        }
+        if (lane < 8 && rank_y <= lane) atomicAdd(&s_topk[lane], 1u);
+    }
+    if (lane == 0) s_nll[wave] = nll;
+    __syncthreads();
+    const int t = threadIdx.x;
+    for (int i = t; i < C * C; i += kEvalThreads)
+        if (s_cm[i]) atomicAdd(&state[i], (unsigned long long)s_cm[i]);
+    double* part = reinterpret_cast<double*>(state + o.scratch) + (size_t)blockIdx.x * (M + 1);
+    if (t < M) {
+        double c = 0.0;
+        for (int w = 0; w < kEvalWaves; ++w) c += s_conf[w][t];
+        part[1 + t] = c;
+        if (s_bin_count[t]) atomicAdd(&state[o.bin_count + t], (unsigned long long)s_bin_count[t]);
+        if (s_bin_correct[t]) atomicAdd(&state[o.bin_correct + t], (unsigned long long)s_bin_correct[t]);
+    } else if (t == 64) {
+        double c = 0.0;
+        for (int w = 0; w < kEvalWaves; ++w) c += s_nll[w];
+        part[0] = c;
+    } else if (t >= 128 && t < 136) {
+        if (s_topk[t - 128]) atomicAdd(&state[o.topk + (t - 128)], (unsigned long long)s_topk[t - 128]);
+    } else if (t == 192) {
+        if (s_misc[0]) atomicAdd(&state[o.n], (unsigned long long)s_misc[0]);
+        if (s_misc[1]) atomicAdd(&state[o.ignored], (unsigned long long)s_misc[1]);
+        if (s_misc[2]) atomicAdd(&state[o.nonfinite], (unsigned long long)s_misc[2]);
+    }
+}
+
+// the joint block: a row counts iff every slot has a label in [0, C_g) and a finite segment (the status word is raised by
+// eval_slots_kernel, which sees the same labels)
+__global__ __launch_bounds__(kEvalThreads) void eval_joint_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
+                                                                  int B, int NC, SlotTable tab, const float* __restrict__ inv_t, int M,
+                                                                  unsigned long long* state_all) {
+    __shared__ double s_conf[kEvalWaves][64];
+    __shared__ double s_nll[kEvalWaves];
+    __shared__ unsigned int s_bin_count[64], s_bin_correct[64], s_right[kMaxSlots + 1], s_misc[3];   // misc: n, exact, excluded
+    const int lane = threadIdx.x & (SIR_WAVE - 1), wave = threadIdx.x / SIR_WAVE;
+    const int G = tab.n;
+    unsigned long long* state = state_all + tab.base[G];
+    const JointLayout o = joint_layout(M);
+    s_conf[wave][lane] = 0.0;
+    if (threadIdx.x < 64) { s_bin_count[threadIdx.x] = 0u; s_bin_correct[threadIdx.x] = 0u; }
+    if (threadIdx.x <= kMaxSlots) s_right[threadIdx.x] = 0u;
+    if (threadIdx.x < 3) s_misc[threadIdx.x] = 0u;
+    __syncthreads();
+    double nll = 0.0;                                                                   // the same value on every lane of the wave
+    const int stride = gridDim.x * kEvalWaves;
+    for (int b = blockIdx.x * kEvalWaves + wave; b < B; b += stride) {                  // wave-uniform
+        float joint = 1.0f;
+        double row_nll = 0.0;
+        int right = 0;
+        bool counted = true;
+        for (int g = 0; g < G; ++g) {                                                   // every branch below is wave-uniform
+            const int start = tab.start[g], C = tab.size[g];
+            const float beta = inv_t ? inv_t[g] : 1.0f;
+            const float l = lane < C ? logits[(size_t)b * NC + start + lane] : 0.0f;
+            const long long y = labels[(size_t)b * G + g];
+            const RowSoftmax r = row_softmax(l, lane, C, beta);
+            if (row_kind(y, C, r.finite) != 0) { counted = false; break; }
+            const int yi = (int)y;
+            const float dy = __shfl(r.d, yi);
+            const unsigned long long top = __ballot(lane < C && r.rank == 0);
+            const int pred = top ? __ffsll((long long)top) - 1 : 0;
+            joint *= __shfl(r.e, pred) / r.den;
+            row_nll += (double)(log1pf(r.rest) - dy);
+            right += pred == yi ? 1 : 0;
+        }
+        if (!counted) {
+            if (lane == 0) atomicAdd(&s_misc[2], 1u);
+            continue;
+        }
+        int bin = (int)floorf(joint * (float)M);
+        bin = bin < M - 1 ? bin : M - 1;
+        bin = bin > 0 ? bin : 0;                                                        // (a NaN beta must not index outside the bins)
+        nll += row_nll;
+        if (lane == 0) {
+            s_conf[wave][bin] += (double)joint;                                         // this wave's rows, in row order
+            atomicAdd(&s_misc[0], 1u);
+            atomicAdd(&s_bin_count[bin], 1u);
+            atomicAdd(&s_right[right], 1u);
+            if (right == G) { atomicAdd(&s_misc[1], 1u); atomicAdd(&s_bin_correct[bin], 1u); }
+        }
+    }
+    if (lane == 0) s_nll[wave] = nll;
+    __syncthreads();
+    const int t = threadIdx.x;
+    double* part = reinterpret_cast<double*>(state + o.scratch) + (size_t)blockIdx.x * (M + 1);
+    if (t < M) {
+        double c = 0.0;
+        for (int w = 0; w < kEvalWaves; ++w) c += s_conf[w][t];
+        part[1 + t] = c;
+        if (s_bin_count[t]) atomicAdd(&state[o.bin_count + t], (unsigned long long)s_bin_count[t]);
+        if (s_bin_correct[t]) atomicAdd(&state[o.bin_correct + t], (unsigned long long)s_bin_correct[t]);
+    } else if (t == 64) {
+        double c = 0.0;
+        for (int w = 0; w < kEvalWaves; ++w) c += s_nll[w];
+        part[0] = c;
+    } else if (t >= 128 && t <= 128 + kMaxSlots) {
+        if (s_right[t - 128]) atomicAdd(&state[o.slots_correct + (t - 128)], (unsigned long long)s_right[t - 128]);
+    } else if (t == 192) {
+        if (s_misc[0]) atomicAdd(&state[o.n], (unsigned long long)s_misc[0]);
+        if (s_misc[1]) atomicAdd(&state[o.exact], (unsigned long long)s_misc[1]);
+        if (s_misc[2]) atomicAdd(&state[o.excluded], (unsigned long long)s_misc[2]);
+    }
+}
+
+// eval_finish_kernel for block blockIdx.x of the state: slot state g < n, or the joint block
+__global__ __launch_bounds__(128) void eval_slots_finish_kernel(unsigned long long* state_all, SlotTable tab, int M, int blocks) {
+    const int g = blockIdx.x, t = threadIdx.x;
+    if (t > M) return;
+    unsigned long long* state = state_all + tab.base[g];
+    int scratch, nll, bin_conf;
+    if (g < tab.n) { const EvalLayout o = eval_layout(tab.size[g], M); scratch = o.scratch; nll = o.nll; bin_conf = o.bin_conf; }
+    else { const JointLayout o = joint_layout(M); scratch = o.scratch; nll = o.nll; bin_conf = o.bin_conf; }
+    const double* part = reinterpret_cast<const double*>(state + scratch);
+    double c = 0.0;
+    for (int b = 0; b < blocks; ++b) c += part[(size_t)b * (M + 1) + t];
+    double* dst = reinterpret_cast<double*>(state + (t == 0 ? nll : bin_conf + (t - 1)));
+    *dst += c;
+}
+
+// layout check + word offsets of the G + 1 blocks; returns the state's size in 8-byte words, 0 with `who`'s error set
+size_t slot_table(const char* who, const int32_t* slot_sizes, int n_slots, int num_classes, int n_bins, SlotTable* tab) {
+    if (!sir_slots_check_layout(who, slot_sizes, n_slots, num_classes, tab->start, tab->size)) return 0;
+    tab->n = n_slots;
+    long long words = 0;
+    for (int g = 0; g < n_slots; ++g) {
+        tab->base[g] = words;
+        if (n_bins >= 1 && n_bins <= 64) words += eval_layout(tab->size[g], n_bins).words;
+    }
+    tab->base[n_slots] = words;
+    if (n_bins >= 1 && n_bins <= 64) words += joint_layout(n_bins).words;
+    return (size_t)words;
+}
+
+}  // namespace
+
+extern "C" int sir_classify_slots(sir_handle* h, const float* logits, int batch, int num_classes, const int32_t* slot_sizes, int n_slots,
+                                  const float* inv_temperature, int k, float* probs, int32_t* topk_idx, float* topk_prob, float* joint_prob,
+                                  void* stream) {
+    const char* who = "sir_classify_slots";
+    if (!h || !logits || !topk_idx || !topk_prob) { sir_set_error("%s: NULL argument (h, logits, topk_idx and topk_prob are required)", who); return SIR_EINVAL; }
+    if (batch < 1 || batch > kMaxRows) { sir_set_error("%s: bad shape batch=%d (1..2^30)", who, batch); return SIR_EINVAL; }
+    SlotTable tab;
+    if (!sir_slots_check_layout(who, slot_sizes, n_slots, num_classes, tab.start, tab.size)) return SIR_EINVAL;
+    tab.n = n_slots;
+    if (k < 1 || k > 8) { sir_set_error("%s: k=%d outside [1, 8]", who, k); return SIR_EINVAL; }
+    const uintptr_t bits = (uintptr_t)logits | (uintptr_t)inv_temperature | (uintptr_t)probs | (uintptr_t)topk_idx | (uintptr_t)topk_prob |
+                           (uintptr_t)joint_prob;
+    if (bits & 3u) { sir_set_error("%s: pointers must be 4-byte aligned", who); return SIR_EINVAL; }
+    int blocks = (batch + kClsWaves - 1) / kClsWaves;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(classify_slots_kernel, dim3(blocks), dim3(kClsWaves * SIR_WAVE), 0, (hipStream_t)stream, logits, batch, num_classes, tab,
+                       inv_temperature, k, probs, (int*)topk_idx, topk_prob, joint_prob);
+    return sir_check_hip(hipGetLastError(), "classify_slots_kernel");
+}
+
+extern "C" size_t sir_eval_slots_state_bytes(const int32_t* slot_sizes, int n_slots, int n_bins) {
+    if (!slot_sizes || n_slots < 1 || n_slots > kMaxSlots || n_bins < 1 || n_bins > 64) return 0;
+    long long sum = 0;
+    for (int g = 0; g < n_slots; ++g) sum += slot_sizes[g] >= 1 && slot_sizes[g] <= 64 ? slot_sizes[g] : 65;
+    if (sum > 64) return 0;
+    SlotTable tab;
+    return slot_table("sir_eval_slots_state_bytes", slot_sizes, n_slots, (int)sum, n_bins, &tab) * 8;
+}
+
+extern "C" int sir_eval_accumulate_slots(sir_handle* h, const float* logits, const int64_t* labels, int batch, int num_classes,
+                                         const int32_t* slot_sizes, int n_slots, const float* inv_temperature, int n_bins, void* state,
+                                         size_t state_bytes, void* stream) {
+    const char* who = "sir_eval_accumulate_slots";
+    if (!h || !logits || !labels || !state) { sir_set_error("%s: NULL argument", who); return SIR_EINVAL; }
+    if (batch < 1 || batch > kMaxRows) { sir_set_error("%s: bad shape batch=%d (1..2^30)", who, batch); return SIR_EINVAL; }
+    if (n_bins < 1 || n_bins > 64) { sir_set_error("%s: n_bins=%d outside [1, 64]", who, n_bins); return SIR_EINVAL; }
+    SlotTable tab;
+    const size_t need = slot_table(who, slot_sizes, n_slots, num_classes, n_bins, &tab) * 8;
+    if (!need) return SIR_EINVAL;
+    if ((((uintptr_t)logits | (uintptr_t)inv_temperature) & 3u) || (((uintptr_t)labels | (uintptr_t)state) & 7u)) {
+        sir_set_error("%s: logits / inv_temperature must be 4-byte aligned, labels / state 8-byte aligned", who);
+        return SIR_EINVAL;
+    }
+    if (state_bytes < need) { sir_set_error("%s: state of %zu bytes, %zu needed", who, state_bytes, need); return SIR_ENOMEM; }
+    const hipStream_t st = (hipStream_t)stream;
+    const int blocks = eval_blocks(batch);
+    unsigned long long* words = (unsigned long long*)state;
+    hipLaunchKernelGGL(eval_slots_kernel, dim3(blocks, n_slots), dim3(kEvalThreads), 0, st, logits, (const long long*)labels, batch, num_classes,
+                       tab, inv_temperature, n_bins, words, h->status);
+    hipLaunchKernelGGL(eval_joint_kernel, dim3(blocks), dim3(kEvalThreads), 0, st, logits, (const long long*)labels, batch, num_classes, tab,
+                       inv_temperature, n_bins, words);
+    hipLaunchKernelGGL(eval_slots_finish_kernel, dim3(n_slots + 1), dim3(128), 0, st, words, tab, n_bins, blocks);
+    return sir_check_hip(hipGetLastError(), "sir_eval_accumulate_slots kernels");
+}

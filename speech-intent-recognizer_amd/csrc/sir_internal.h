@@ -231,6 +231,9 @@ struct SirProfScope {
     }
 };
 
+// slots.hip: the slot-layout rules of include/sir_hip.h; fills start[8] / size[8], or sets `who`'s error and returns false
+bool sir_slots_check_layout(const char* who, const int32_t* slot_sizes, int n_slots, int num_classes, int* start, int* size);
+
 // model_train_fwd.hip
 size_t sir_train_workspace_bytes_impl(int batch, int t_frames);
 

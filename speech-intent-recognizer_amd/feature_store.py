@@ -27,10 +27,11 @@ logger = logging.getLogger(__name__)
 
 class FeatureStore:
     """``len(store)`` items of one CSV split on ``device``; ``epoch_batches`` yields ``(mel [B, 64, T] float32, label int64 [B])``
-    device tensors in ``ShardSampler`` order (rank r takes i = r mod world of the shuffled epoch)."""
+    device tensors in ``ShardSampler`` order (rank r takes i = r mod world of the shuffled epoch).  With ``slot_spec`` (a
+    ``slots.SlotSpec``) the labels are int64 [N, G] and a batch's [B, G], gathered by the same ``index_select``."""
 
     def __init__(self, csv_path, label_map_path, device, use_cache=True, cache_dir="data/cached_features",
-                 mel_spec_length=200, stage_items=4096, frontend=None):
+                 mel_spec_length=200, stage_items=4096, frontend=None, slot_spec=None):
         _native.require_hip()
         from .scripts.dataset import FSCIntentDataset
         if mel_spec_length % 4 != 0:
@@ -40,7 +41,8 @@ class FeatureStore:
         from .frontend_config import as_frontend
         fe = as_frontend(frontend)                    # the split's cache file (and any miss) is this front-end's
         ds = FSCIntentDataset(csv_path, label_map_path, is_training=False, use_cache=use_cache, cache_dir=cache_dir,
-                              mel_spec_length=mel_spec_length, n_fft=fe.n_fft, hop_length=fe.hop_length, win_length=fe.win_length)
+                              mel_spec_length=mel_spec_length, n_fft=fe.n_fft, hop_length=fe.hop_length, win_length=fe.win_length,
+                              slot_spec=slot_spec)
         n = len(ds)
         self.n_mels = ds.n_mels
         self.store = torch.zeros((n, self.n_mels, self.t_pad), dtype=torch.float32, device=self.device)
@@ -59,7 +61,7 @@ class FeatureStore:
                 t = min(int(mel.shape[1]), self.t_pad)
                 chunk[i - start, :, :t] = mel[:, :t]
                 frames.append(int(mel.shape[1]))
-                labels.append(ds.label_map.get(ds._labels[i], 0))
+                labels.append(ds.label_map.get(ds._labels[i], 0) if slot_spec is None else ds._slot_labels[i].tolist())
             self.store[start:stop].copy_(chunk, non_blocking=True)
         torch.cuda.synchronize(self.device)
         self.frames = frames                          # un-padded frame counts (host): the size the time mask is drawn along

@@ -30,6 +30,58 @@ def inv_temperature_of(temperature):
     return 1.0 / t
 
 
+def slot_inv_temperature_of(temperature, n_slots):
+    """``temperature`` under a slot layout (None, one T for all slots, or one per slot) -> None or a list of ``1 / T``."""
+    if temperature is None:
+        return None
+    ts = [temperature] * n_slots if isinstance(temperature, (int, float, np.floating, np.integer)) else list(temperature)
+    if len(ts) != n_slots:
+        raise ValueError(f"{len(ts)} temperatures for {n_slots} slots")
+    return [inv_temperature_of(t) for t in ts]
+
+
+def results_from_slot_logits(logits, spec, k=3, inv_temperature=None, min_confidence=None):
+    """``results_from_logits`` under a slot layout (``sir_amd.slots.SlotSpec``): ONE ``sir_classify_slots`` launch and ONE
+    device-to-host copy for all rows of ``logits`` [B, spec.total] -> list of B dicts: the decoded slots (``{column: value}``)
+    plus ``"predicted_label"`` (the reference's ``action_object`` join when the spec has both columns, else all values joined
+    by ``_``), ``"confidence"`` (the joint confidence: the product of the slots' top probabilities), ``"slot_confidence"``
+    (``{column: probability}``) and ``"top_predictions"`` (``{column: [{"label", "probability"}, ...]}``, ``k`` entries, at most
+    the slot's width).  ``inv_temperature``: None, a number, one per slot, or ``slots.fit_slot_temperatures``' device tensor.
+    With ``min_confidence`` set every dict also carries ``"rejected"``: the JOINT confidence is below it (or NaN)."""
+    from sir_amd import slots
+    k = int(k)
+    idx, prob, joint = slots.classify(logits, spec, k=k, inv_temperature=inv_temperature)
+    bsz, g = idx.shape[0], spec.n_slots
+    packed = torch.cat([idx.to(torch.float32).view(bsz, g * k), prob.view(bsz, g * k), joint[:, None]], dim=1).cpu().numpy()
+    idx_h = packed[:, :g * k].astype(np.int64).reshape(bsz, g, k).tolist()          # class indices <= 63 are exact in float32
+    prob_h = packed[:, g * k: 2 * g * k].reshape(bsz, g, k).tolist()
+    joint_h = packed[:, 2 * g * k].tolist()
+    results = []
+    for row_i, row_p, conf in zip(idx_h, prob_h, joint_h):
+        res = spec.decode([slot_i[0] for slot_i in row_i])
+        label = spec.reference_label(res)
+        top = {}
+        for c, vs, slot_i, slot_p in zip(spec.columns, spec.vocab, row_i, row_p):
+            n = min(k, len(vs))
+            top[c] = [{"label": vs[i] if 0 <= i < len(vs) else "Unknown", "probability": p} for i, p in zip(slot_i[:n], slot_p[:n])]
+        res.update({"predicted_label": label if label is not None else "_".join(res[c] for c in spec.columns),
+                    "confidence": conf, "slot_confidence": {c: slot_p[0] for c, slot_p in zip(spec.columns, row_p)},
+                    "top_predictions": top})
+        if min_confidence is not None:
+            res["rejected"] = not (conf >= min_confidence)
+        results.append(res)
+    return results
+
+
+def results_of(logits, inv_label_map, slots=None, temperature=None, min_confidence=None):
+    """The result dictionaries of the callers' device route: ``results_from_slot_logits`` when a slot layout is given,
+    ``results_from_logits`` otherwise; ``temperature`` is the callers' T (under slots: one, or one per slot)."""
+    if slots is not None:
+        return results_from_slot_logits(logits, slots, inv_temperature=slot_inv_temperature_of(temperature, slots.n_slots),
+                                        min_confidence=min_confidence)
+    return results_from_logits(logits, inv_label_map, inv_temperature=inv_temperature_of(temperature), min_confidence=min_confidence)
+
+
 def results_from_logits(logits, inv_label_map, k=3, inv_temperature=None, min_confidence=None):
     """``test_model._result`` for a whole batch: ONE ``sir_classify`` launch and ONE device-to-host copy for all rows of
     ``logits`` [B, C] -> list of B dicts of ``_result``'s shape (``top_predictions`` holds ``k`` entries, at most the number of

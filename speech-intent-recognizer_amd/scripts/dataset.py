@@ -53,7 +53,7 @@ class FSCIntentDataset(Dataset):
 
     def __init__(self, csv_path, label_map_path, is_training=True, augment_prob=0.5,
                  use_cache=True, cache_dir="data/cached_features", mel_spec_length=200,
-                 n_fft=1024, hop_length=512, win_length=None):
+                 n_fft=1024, hop_length=512, win_length=None, slot_spec=None):
         from sir_amd.frontend_config import FrontEnd
         self.frontend = FrontEnd(n_fft, hop_length, win_length)      # (beyond the reference, whose front-end is 1024 / 512 / 1024)
         self.data = pd.read_csv(csv_path)
@@ -63,8 +63,13 @@ class FSCIntentDataset(Dataset):
         self.n_mels = 64
         self.mel_spec_length = mel_spec_length
         self.use_cache = use_cache
-        with open(label_map_path, "r") as f:
-            self.label_map = json.load(f)
+        # slot heads (sir_amd/slots.py; beyond the reference, which joins action and object and drops the location): the label of
+        # an item is then int64 [G], one slot-local index per column of the spec, and the label map is not consulted
+        self.slot_spec = slot_spec
+        self.label_map = {}
+        if slot_spec is None or label_map_path is not None:
+            with open(label_map_path, "r") as f:
+                self.label_map = json.load(f)
         self.in_memory_cache = {}
         self.features_dict = {}
         if use_cache:
@@ -80,7 +85,9 @@ class FSCIntentDataset(Dataset):
         self.time_mask_param = 20
         self.freq_mask_param = 10
         self._paths = self.data["path"].tolist()
-        self._labels = self.data["label"].tolist()
+        if slot_spec is not None:
+            self._slot_labels = slot_spec.encode(self.data)
+        self._labels = self.data["label"].tolist() if (slot_spec is None or "label" in self.data.columns) else [None] * len(self.data)
         self.prefetch_missing()
         logger.info(f"Initialized dataset with {len(self.data)} samples, {len(self.label_map)} classes")
 
@@ -132,7 +139,7 @@ class FSCIntentDataset(Dataset):
 
     def __getitem__(self, idx):
         audio_path = self._paths[idx]
-        label_id = self.label_map.get(self._labels[idx], 0)
+        label_id = self.label_map.get(self._labels[idx], 0) if self.slot_spec is None else torch.from_numpy(self._slot_labels[idx])
         if audio_path in self.in_memory_cache:
             mel_spec = self.in_memory_cache[audio_path]
         elif audio_path in self.features_dict:

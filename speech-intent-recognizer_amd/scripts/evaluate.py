@@ -41,7 +41,8 @@ def predict_loader(model, loader, device, device_metrics=None, collect_logits=Fa
     ordered on its stream; the slots' states are merged on the host at the end -- and the result is
     ``(None, None, state arrays)``: no prediction leaves the device and no per-batch synchronisation is added.
     ``collect_logits=True`` returns ``(logits [N, C] on the device, labels [N] on the device)`` instead (for
-    ``metrics.fit_temperature``)."""
+    ``metrics.fit_temperature``).  A ``device_metrics`` dict with the key ``spec`` (a ``slots.SlotSpec``) makes the
+    accumulators ``slots.SlotEvalAccumulator``s: labels are then [B, G] and the state holds the slots' states and the joint block."""
     from sir_amd.pipeline import BatchPipeline
     model.eval()
     pipe = BatchPipeline(model, n_streams=2)          # consecutive batches alternate over two HIP streams
@@ -49,7 +50,10 @@ def predict_loader(model, loader, device, device_metrics=None, collect_logits=Fa
     if device_metrics is not None or collect_logits:
         accs = None
         if device_metrics is not None:
-            from sir_amd.metrics import EvalAccumulator
+            if "spec" in device_metrics:
+                from sir_amd.slots import SlotEvalAccumulator as EvalAccumulator
+            else:
+                from sir_amd.metrics import EvalAccumulator
             accs = [EvalAccumulator(**device_metrics) for _ in range(pipe.n)]
         return _predict_loader_device(model, loader, device, pipe, accs, collect_logits)
     from sir_amd.scripts.train import HostStager
@@ -92,7 +96,8 @@ def _predict_loader_device(model, loader, device, pipe, accs, collect_logits):
         if not logits_all:
             return None, None
         return torch.cat(logits_all), torch.cat(labels_all)
-    from sir_amd.metrics import merge
+    from sir_amd import metrics, slots
+    merge = slots.merge if isinstance(accs[0], slots.SlotEvalAccumulator) else metrics.merge
     state = accs[0].state_arrays()
     for a in accs[1:]:
         state = merge(state, a.state_arrays())
@@ -126,7 +131,65 @@ def read_temperature_file(path):
     return beta
 
 
+def evaluate_slots(args, config):
+    """``slots: {columns, map, weights}`` together with ``device_metrics: true``: the checkpoint's logit row is read as slot
+    heads (sir_amd/slots.py).  Writes one ``classification_report_<column>.txt`` and ``calibration_<column>.json`` per slot
+    and ``joint_metrics.json`` (exact-match accuracy, joint NLL / ECE / MCE, slots_correct, n_excluded) and returns the
+    exact-match accuracy.  ``slots.map`` must name the ``slot_map.json`` of the training run: the test split's own values
+    would give another class order."""
+    from sir_amd import metrics, slots
+    opts = config["slots"]
+    if not config.get("device_metrics", False):
+        raise ValueError("`slots` needs `device_metrics: true` (the sklearn route knows one label per clip)")
+    if not isinstance(opts, dict) or not opts.get("map"):
+        raise ValueError("`slots.map` must name the slot_map.json of the training run")
+    spec = slots.SlotSpec.load(opts["map"])
+    if config.get("num_labels", spec.total) != spec.total:
+        raise ValueError(f"num_labels is {config['num_labels']}, the slot layout {dict(zip(spec.columns, spec.sizes))} needs {spec.total}")
+    _native.require_hip()
+    from sir_amd.dist_utils import limit_host_threads
+    from sir_amd.frontend_config import FrontEnd
+    from sir_amd.scripts.train import loader_kwargs
+    limit_host_threads(reserve=int(config.get("num_workers", 4)))
+    device = torch.device("cuda", torch.cuda.current_device())
+    model = CNNAudioGRU(num_classes=spec.total).to(device)
+    state = torch.load(args.model_path, map_location=device)
+    if isinstance(state, dict) and "model_state_dict" in state:
+        state = state["model_state_dict"]
+    model.load_state_dict(state)
+    fe = FrontEnd.from_config(config)
+    test_dataset = FSCIntentDataset(csv_path=args.test_csv, label_map_path=None, is_training=False,
+                                    use_cache=config.get("use_feature_cache", True),
+                                    cache_dir=config.get("cache_dir", "data/cached_features"),
+                                    mel_spec_length=int(config.get("mel_spec_length", 200)),
+                                    n_fft=fe.n_fft, hop_length=fe.hop_length, win_length=fe.win_length, slot_spec=spec)
+    test_loader = DataLoader(test_dataset, batch_size=config.get("batch_size", 32), shuffle=False, collate_fn=collate_fn,
+                             **loader_kwargs(config.get("num_workers", 4)))
+    _, _, arrays = predict_loader(model, test_loader, device,
+                                  device_metrics={"spec": spec, "n_bins": int(config.get("calibration_bins", 15))})
+    results_dir = os.path.join(config["save_path"], "evaluation_results")
+    os.makedirs(results_dir, exist_ok=True)
+    for column, vocab, a in zip(spec.columns, spec.vocab, arrays["slots"]):
+        report = metrics.report_from_state(a, list(vocab))
+        text = metrics.format_report(report["classification"])
+        logger.info(f"Slot {column}: accuracy {report['accuracy']:.4f}\n{text}")
+        with open(os.path.join(results_dir, f"classification_report_{column}.txt"), "w") as f:
+            f.write(f"Test Accuracy: {report['accuracy']:.4f}\n\n")
+            f.write(text)
+        with open(os.path.join(results_dir, f"calibration_{column}.json"), "w") as f:
+            json.dump(metrics.calibration_json(report), f, indent=2)
+    joint = slots.joint_report(arrays["joint"])
+    with open(os.path.join(results_dir, "joint_metrics.json"), "w") as f:
+        json.dump(slots.joint_json(joint), f, indent=2)
+    logger.info(f"Exact-match accuracy {joint['exact_match_accuracy']:.4f} over {joint['n']} clips ({joint['n_excluded']} excluded), "
+                f"joint NLL {joint['nll']:.4f}, ECE {joint['ece']:.4f}")
+    logger.info(f"Evaluation results saved to {results_dir}")
+    return joint["exact_match_accuracy"]
+
+
 def evaluate(args, config):
+    if config.get("slots"):
+        return evaluate_slots(args, config)
     _native.require_hip()
     from sir_amd.dist_utils import limit_host_threads
     limit_host_threads(reserve=int(config.get("num_workers", 4)))

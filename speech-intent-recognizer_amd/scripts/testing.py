@@ -159,7 +159,8 @@ class IntentRecognizer:
         ops.check_status()
         return logits
 
-    def recognize_recordings(self, waves_or_paths, pad_to=TRAINED_LENGTH, on_device=False, temperature=None, min_confidence=None):
+    def recognize_recordings(self, waves_or_paths, pad_to=TRAINED_LENGTH, on_device=False, temperature=None, min_confidence=None,
+                             slots=None):
         """waves_or_paths: recordings as 1-D float32 / int16 arrays or tensors at the segmenter's sample rate, or paths of WAVE
         files (decoded, mixed to mono and resampled on the GPU).  -> per recording, the list of its utterances in time order:
         ``{"start": seconds, "end": seconds, "predicted_label", "confidence", "top_predictions"}``; ``None`` for the recordings of
@@ -167,9 +168,16 @@ class IntentRecognizer:
         ``on_device=True``: softmax, confidence and top-3 of all utterances of a group come from one ``sir_classify`` launch and
         one copy (``classify_results.results_from_logits``) instead of several host round trips per utterance; ``temperature`` (T,
         probabilities of ``softmax(logits / T)``) and ``min_confidence`` (every utterance also carries ``"rejected"``) belong
-        to that route: without ``on_device=True`` they raise ``ValueError``."""
+        to that route: without ``on_device=True`` they raise ``ValueError``.
+        ``slots`` (a ``sir_amd.slots.SlotSpec``; implies the device route): the logit row is read as slot heads and every
+        utterance carries ``classify_results.results_from_slot_logits``' dictionary instead (decoded slots, joint
+        ``"confidence"``, per-slot tables); ``temperature`` may hold one T per slot, ``min_confidence`` rejects on the joint value.
+        (``StreamSession.feed`` keeps the single-head results: DESIGN.md section 4 "Slot heads".)"""
         from sir_amd.scripts import classify_results
+        on_device = on_device or slots is not None
         classify_results.check_route(on_device, temperature, min_confidence)
+        if slots is not None:
+            classify_results.slot_inv_temperature_of(temperature, slots.n_slots)
         items = list(waves_or_paths)
         results = [None] * len(items)
         sr = float(self.segmenter.sample_rate)
@@ -181,9 +189,7 @@ class IntentRecognizer:
                 found = [[] for _ in group]
                 batch_res = None
                 if on_device and table.shape[0] > 0:
-                    batch_res = classify_results.results_from_logits(logits, self.inv_label_map,
-                                                                     inv_temperature=classify_results.inv_temperature_of(temperature),
-                                                                     min_confidence=min_confidence)
+                    batch_res = classify_results.results_of(logits, self.inv_label_map, slots, temperature, min_confidence)
                 for row, (r, a, b) in enumerate(table.tolist()):
                     res = batch_res[row] if batch_res is not None else test_model._result(logits[row:row + 1], self.inv_label_map)
                     found[r].append({"start": a / sr, "end": b / sr, **res})

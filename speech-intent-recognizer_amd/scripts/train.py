@@ -41,6 +41,8 @@ def collate_fn(batch):
         labels.append(label)
     if not mel_specs:
         return None, None
+    if torch.is_tensor(labels[0]):                         # slot heads: an item's label is int64 [G]
+        return torch.stack(mel_specs), torch.stack(labels).to(torch.long)
     return torch.stack(mel_specs), torch.tensor(labels, dtype=torch.long)
 
 
@@ -61,8 +63,8 @@ def _loss_fn(criterion):
 def _mixed_loss(loss_fn, output, label, label_b, lam):
     """The loss of a mixed batch: the HIP loss takes both labels; a foreign criterion is weighed as mixup defines it
     (``lam`` holds one value per batch, repeated per row)."""
-    from sir_amd import train_ops
-    if getattr(loss_fn, "func", loss_fn) is train_ops.fused_cross_entropy:
+    from sir_amd import slots, train_ops
+    if getattr(loss_fn, "func", loss_fn) is train_ops.fused_cross_entropy or isinstance(loss_fn, slots.SlotLoss):
         return loss_fn(output, label, label_b, lam)
     return lam[0] * loss_fn(output, label) + (1.0 - lam[0]) * loss_fn(output, label_b)
 
@@ -433,9 +435,36 @@ def run_options(config):
             "resume_path": None if not resume else (latest if resume is True else str(resume))}
 
 
+def slot_options(config, train_csv=None):
+    """The YAML key ``slots: {columns, map, weights}`` (absent by default) -> None or ``{"spec", "weights"}``, on the host.
+    ``map``: a ``slot_map.json`` written by ``SlotSpec.save`` (absent: the vocabularies are built from the training CSV's
+    ``columns``, default action / object / location); ``weights``: one loss weight per slot.  ``num_labels`` must be the sum
+    of the slot widths: the model's ``fc`` writes exactly those logits."""
+    opts = config.get("slots")
+    if not opts:
+        return None
+    from sir_amd import slots
+    if not isinstance(opts, dict):
+        raise ValueError("`slots` must be a mapping with the keys columns / map / weights")
+    unknown = sorted(set(opts) - {"columns", "map", "weights"})
+    if unknown:
+        raise ValueError(f"`slots` has unknown keys {unknown}")
+    columns = tuple(opts.get("columns") or ("action", "object", "location"))
+    if opts.get("map"):
+        spec = slots.SlotSpec.load(opts["map"])
+        if opts.get("columns") and tuple(spec.columns) != columns:
+            raise ValueError(f"`slots.columns` {list(columns)} differ from those of {opts['map']}: {list(spec.columns)}")
+    else:
+        spec = slots.SlotSpec.from_csv(train_csv, columns)
+    num_labels = config.get("num_labels", 31)
+    if num_labels != spec.total:
+        raise ValueError(f"num_labels is {num_labels}, the slot layout {dict(zip(spec.columns, spec.sizes))} needs {spec.total}")
+    return {"spec": spec, "weights": slots.check_weights(opts.get("weights"), spec.n_slots)}
+
+
 def validate(model, val_loader, criterion, device, scaler=None):
     """(avg_loss, accuracy) over the loader (train.py:120-155); under data parallelism the counts are
-    summed over ranks."""
+    summed over ranks.  With 2-D labels (slot heads) the accuracy is the exact-match rate over the slots."""
     from sir_amd import ops, train_ops
     model.eval()
     loss_fn = _loss_fn(criterion)
@@ -451,7 +480,14 @@ def validate(model, val_loader, criterion, device, scaler=None):
             label = stage(label)
             output, predicted = model.predict(mel)
             losses.append(loss_fn(output, label))
-            correct += (predicted == label).sum()
+            if label.dim() == 2:
+                # slot heads (the criterion is a slots.SlotLoss): a clip is right when every slot is (exact match); the argmax
+                # over the whole row means nothing here
+                from sir_amd import slots
+                idx, _, _ = slots.classify(output, criterion.spec, k=1)
+                correct += (idx[:, :, 0] == label).all(dim=1).sum()
+            else:
+                correct += (predicted == label).sum()
             total += label.size(0)
     counts = torch.tensor([int(correct.item()), total], dtype=torch.int64, device=device)
     ops.check_status()                                # the host has just synchronised: surface a timed-out recurrence
@@ -482,6 +518,11 @@ def train(args, config):
     from sir_amd.scripts.dataset import FSCIntentDataset
 
     adv_opts = adversarial_options(config)            # (a bad `adversarial` key raises here, before any device call)
+    # `slots: {columns, map, weights}` (absent by default): slot heads -- the label of a clip is one class per CSV column, the
+    # loss a weighted sum of per-segment cross-entropies, the validation accuracy the exact-match rate (sir_amd/slots.py,
+    # DESIGN.md section 4).  A layout that does not add up to `num_labels` raises here, before any device call.
+    slot_opts = slot_options(config, args.train_csv)
+    slot_spec = slot_opts["spec"] if slot_opts else None
     _native.require_hip()
     train_ops.limit_host_threads(reserve=int(config.get("num_workers", 2)))     # (the DataLoader workers get their share of the CPU quota)
     rank, world, local_rank = train_ops.init_distributed()
@@ -516,21 +557,21 @@ def train(args, config):
     if fused:
         from sir_amd.waveform_store import WaveformStore
         train_store = WaveformStore(args.train_csv, args.label_map, device,
-                                    sample_rate=int(config.get("sample_rate", 16000)))
+                                    sample_rate=int(config.get("sample_rate", 16000)), slot_spec=slot_spec)
     t_pad = int(config.get("mel_spec_length", MAX_LENGTH))
     if hbm_cache:
         from sir_amd.feature_store import FeatureStore
         train_dataset = FeatureStore(args.train_csv, args.label_map, device, use_cache=use_cache, cache_dir=cache_dir, mel_spec_length=t_pad,
-                                     frontend=fe)
+                                     frontend=fe, slot_spec=slot_spec)
         val_dataset = FeatureStore(args.val_csv, args.label_map, device, use_cache=use_cache, cache_dir=cache_dir, mel_spec_length=t_pad,
-                                   frontend=fe)
+                                   frontend=fe, slot_spec=slot_spec)
     else:
         train_dataset = train_store if fused else \
             FSCIntentDataset(csv_path=args.train_csv, label_map_path=args.label_map, is_training=True,
                              augment_prob=config.get("augment_prob", 0.5), use_cache=use_cache, cache_dir=cache_dir,
-                             mel_spec_length=t_pad, **fe_kw)
+                             mel_spec_length=t_pad, slot_spec=slot_spec, **fe_kw)
         val_dataset = FSCIntentDataset(csv_path=args.val_csv, label_map_path=args.label_map, is_training=False,
-                                       use_cache=use_cache, cache_dir=cache_dir, mel_spec_length=t_pad, **fe_kw)
+                                       use_cache=use_cache, cache_dir=cache_dir, mel_spec_length=t_pad, slot_spec=slot_spec, **fe_kw)
     if rank == 0:
         print(f"Datasets loaded - Train: {len(train_dataset)}, Val: {len(val_dataset)}")
 
@@ -569,6 +610,10 @@ def train(args, config):
     opts = run_options(config)
     criterion = nn.CrossEntropyLoss()
     train_criterion = nn.CrossEntropyLoss(label_smoothing=float(config["label_smoothing"])) if config.get("label_smoothing") else criterion
+    if slot_opts:                                     # label smoothing folded in; validation keeps the plain (weighted) slot loss
+        from sir_amd import slots
+        criterion = slots.SlotLoss(slot_spec, slot_opts["weights"])
+        train_criterion = slots.SlotLoss(slot_spec, slot_opts["weights"], float(config.get("label_smoothing") or 0.0))
     mixup = train_ops.Mixup(float(config["mixup"]), seed=seed + 977 * rank) if config.get("mixup") else None
     adversary = None
     if adv_opts:

@@ -33,17 +33,20 @@ class WaveformStore:
     cannot be read keeps its label and an empty waveform (length 0), for which the feature kernel emits the all-zero
     spectrogram the reference substitutes."""
 
-    def __init__(self, csv_path, label_map_path, device, max_duration=5.0, sample_rate=16000, stage_batch=512):
+    def __init__(self, csv_path, label_map_path, device, max_duration=5.0, sample_rate=16000, stage_batch=512, slot_spec=None):
         _native.require_hip()
         from .scripts.precompute_features import AudioFeatureExtractor
         self.device = torch.device(device)
         self.sample_rate = sample_rate
         data = pd.read_csv(csv_path)
-        with open(label_map_path, "r") as f:
-            label_map = json.load(f)
         paths = data["path"].tolist()
-        self.labels = torch.tensor([label_map.get(lab, 0) for lab in data["label"].tolist()], dtype=torch.int64,
-                                   device=self.device)
+        if slot_spec is not None:                     # slot heads (sir_amd/slots.py): labels int64 [N, G], gathered the same way
+            self.labels = torch.from_numpy(slot_spec.encode(data)).to(self.device)
+        else:
+            with open(label_map_path, "r") as f:
+                label_map = json.load(f)
+            self.labels = torch.tensor([label_map.get(lab, 0) for lab in data["label"].tolist()], dtype=torch.int64,
+                                       device=self.device)
         n = len(paths)
         max_samples = int(max_duration * sample_rate)
         ex = AudioFeatureExtractor(sample_rate)

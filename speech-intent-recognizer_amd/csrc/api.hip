@@ -1,5 +1,5 @@
 // C ABI entry points of libsir_hip.so (see include/sir_hip.h): handle management, error state,
-// argument validation.  Kernels live in features.hip / model_*.hip.
+// argument validation.  Kernels live in features_*.hip / model_*.hip.
 #include "sir_internal.h"
 #include "model_shape.h"
 

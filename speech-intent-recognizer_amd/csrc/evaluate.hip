@@ -16,6 +16,7 @@
 //                         g + waves, ...; per-workgroup partials in the workspace) and a one-thread update launch.
 #include <cmath>
 #include "sir_internal.h"
+#include "wave_fft.h"      // wave_sum
 
 namespace {
 
@@ -31,11 +32,6 @@ constexpr unsigned int kStatusBadLabel = 512u;       // api.hip check_status_imp
 __device__ __forceinline__ float wave_max(float x) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o));
-    return x;
-}
-__device__ __forceinline__ float wave_sum(float x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
     return x;
 }
 __device__ __forceinline__ bool is_nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }

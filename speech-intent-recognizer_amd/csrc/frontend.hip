@@ -149,7 +149,7 @@ extern "C" int sir_resample(sir_handle* h, const void* wave, int wave_dtype, int
         sir_set_error("sir_resample: bad sizes or rates (batch %d, max_len %d, %d -> %d Hz)", batch, max_len, orig_freq, new_freq);
         return SIR_EINVAL;
     }
-    if (wave_dtype != SIR_WAVE_F32 && wave_dtype != SIR_WAVE_I16) { sir_set_error("sir_resample: unknown wave dtype %d", wave_dtype); return SIR_EINVAL; }
+    if (!sir_wave_elem_bytes(wave_dtype)) { sir_set_error("sir_resample: unknown wave dtype %d", wave_dtype); return SIR_EINVAL; }
     sir_resample_table tab;
     sir_resample_table* t = &tab;
     if (!get_resample_table(h, orig_freq, new_freq, t)) { sir_set_error("sir_resample: could not build the %d -> %d Hz filter table", orig_freq, new_freq); return SIR_EHIP; }
@@ -173,7 +173,7 @@ extern "C" int sir_mix_to_mono(sir_handle* h, const void* pcm, int dtype, int ch
         sir_set_error("sir_mix_to_mono: bad sizes (batch %d, max_frames %d, channels %d)", batch, max_frames, channels);
         return SIR_EINVAL;
     }
-    if (dtype != SIR_WAVE_F32 && dtype != SIR_WAVE_I16) { sir_set_error("sir_mix_to_mono: unknown dtype %d", dtype); return SIR_EINVAL; }
+    if (!sir_wave_elem_bytes(dtype)) { sir_set_error("sir_mix_to_mono: unknown dtype %d", dtype); return SIR_EINVAL; }
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((max_frames + 255) / 256, batch);
     if (dtype == SIR_WAVE_I16)

@@ -28,6 +28,7 @@
 #include <math.h>
 #include <stdint.h>
 #include "sir_internal.h"
+#include "wave_sample.h"
 
 namespace {
 
@@ -56,10 +57,6 @@ Geom geom_for(int sr) {                // sox tempo.c, default profile: segment 
     g.H = g.S - g.O;
     return g;
 }
-
-template <typename T> __device__ __forceinline__ float to_f32(T v);
-template <> __device__ __forceinline__ float to_f32<float>(float v) { return v; }
-template <> __device__ __forceinline__ float to_f32<short>(short v) { return (float)v * (1.0f / 32768.0f); }
 
 // the row's factor; false = outside the accepted range (row zeroed, status flagged)
 __device__ __forceinline__ bool row_factor(int mode, const float* factor, int b, double* f) {
@@ -343,7 +340,7 @@ extern "C" int sir_wave_perturb(sir_handle* h, const void* wave, int wave_dtype,
                       max_len, (long long)wave_stride, max_out_len, (long long)out_stride);
         return SIR_EINVAL;
     }
-    if (wave_dtype != SIR_WAVE_F32 && wave_dtype != SIR_WAVE_I16) { sir_set_error("sir_wave_perturb: unknown wave dtype %d", wave_dtype); return SIR_EINVAL; }
+    if (!sir_wave_elem_bytes(wave_dtype)) { sir_set_error("sir_wave_perturb: unknown wave dtype %d", wave_dtype); return SIR_EINVAL; }
     if (offsets_out && max_segments <= 0) { sir_set_error("sir_wave_perturb: offsets_out needs max_segments > 0"); return SIR_EINVAL; }
     const int sr = h->cfg.sample_rate;
     const Geom g = sr > 0 ? geom_for(sr) : Geom{0, 0, 0, 0};

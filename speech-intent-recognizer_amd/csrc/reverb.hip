@@ -16,7 +16,7 @@
 // waves work on four consecutive blocks at once ("round"): each transforms its window and stores X_j in an LDS ring of P + 3
 // spectra, one barrier, each multiply-accumulates its block's spectrum from the ring and H, transforms back and stores 512
 // samples, one barrier.  A transform is a 512-point complex FFT of the sample pairs inside ONE wave (three radix-8 passes,
-// two exchanges through the wave's private LDS slab, no workgroup barrier: the scheme and the slab layouts of features.hip)
+// two exchanges through the wave's private LDS slab, no workgroup barrier: the scheme and the slab layouts of the feature kernels, over wave_fft.h)
 // plus the real-FFT untangle; a spectrum is kept as 512 complex values, slot 0 holding the two real bins (X[0], X[512]).
 // LDS: 4 KB x (2 P + 3) + 18 KB of slabs = 158 KB at P = 16 (of 160 KB: one workgroup per CU), 42 KB at P = 2.
 // The noise stage follows in the same workgroup: y is in `out`, the threads re-read it (their own workgroup's stores, fenced)
@@ -26,6 +26,8 @@
 #include <math.h>
 #include <stdint.h>
 #include "sir_internal.h"
+#include "wave_fft.h"
+#include "wave_sample.h"
 
 namespace {
 
@@ -35,41 +37,11 @@ constexpr int kPart = 512;             // taps per RIR partition = samples per o
 constexpr int kMaxRir = 8192;
 constexpr int kMaxParts = kMaxRir / kPart;
 constexpr int kRingExtra = kWaves - 1; // ring slots beyond the partitions: a round's four spectra land before the oldest is dropped
-constexpr int XS = 72;                 // first exchange: row stride (complex), as features.hip
-constexpr int XS2 = 68;                // second exchange: row stride (complex), with the XOR swizzle of ex2_index
 constexpr int kSlab = 8 * XS;          // complex slots of a wave's slab
 constexpr unsigned kStatusBadReverb = 256u;
 
-typedef float cf32 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ cf32 CF(float2 a) { return cf32{a.x, a.y}; }
 __device__ __forceinline__ cf32 cconj(cf32 a) { return cf32{a.x, -a.y}; }
-__device__ __forceinline__ cf32 mul_mi(cf32 a) { return cf32{a.y, -a.x}; }                       // a * (-i)
 __device__ __forceinline__ cf32 mul_pi(cf32 a) { return cf32{-a.y, a.x}; }                       // a * (+i)
-__device__ __forceinline__ cf32 cmul(cf32 a, cf32 b) { return cf32{a.x, a.x} * b + cf32{a.y, a.y} * cf32{-b.y, b.x}; }
-__device__ __forceinline__ int ex2_index(int k2, int j, int m1) { return k2 * XS2 + ((j ^ (m1 >> 1)) + 8 * m1); }
-
-// forward 8-point DFT, natural order in and out
-__device__ __forceinline__ void dft8(cf32 (&v)[8]) {
-    const float R = 0.70710678118654752440f;
-    cf32 a0 = v[0] + v[4], a4 = v[0] - v[4];
-    cf32 a1 = v[1] + v[5], a5 = v[1] - v[5];
-    cf32 a2 = v[2] + v[6], a6 = v[2] - v[6];
-    cf32 a3 = v[3] + v[7], a7 = v[3] - v[7];
-    a5 = (a5 + mul_mi(a5)) * R;
-    a6 = mul_mi(a6);
-    a7 = (mul_mi(a7) - a7) * R;
-    cf32 b0 = a0 + a2, b2 = a0 - a2, b1 = a1 + a3, b3 = mul_mi(a1 - a3);
-    cf32 c0 = a4 + a6, c2 = a4 - a6, c1 = a5 + a7, c3 = mul_mi(a5 - a7);
-    v[0] = b0 + b1; v[4] = b0 - b1; v[2] = b2 + b3; v[6] = b2 - b3;
-    v[1] = c0 + c1; v[5] = c0 - c1; v[3] = c2 + c3; v[7] = c2 - c3;
-}
-
-__device__ __forceinline__ void wave_fence() {
-    // per-wave LDS slab: LDS ops of one wave execute in order, only the compiler must not reorder
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
 // the lane's twiddles: t1[k] = W512^(lane k), t2[k] = W64^((lane & 7) k), tu[j] = W1024^(lane + 64 j)
 struct Twiddles { cf32 t1[8], t2[8], tu[8]; };
 
@@ -139,16 +111,6 @@ __device__ __forceinline__ void irfft1024(cf32 (&v)[8], const Twiddles& tw, cf32
     fft512(v, tw, xb, lane);
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = cconj(v[j]);
-}
-
-template <typename T> __device__ __forceinline__ float to_f32(T v);
-template <> __device__ __forceinline__ float to_f32<float>(float v) { return v; }
-template <> __device__ __forceinline__ float to_f32<short>(short v) { return (float)v * (1.0f / 32768.0f); }
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
 }
 
 struct ReverbArgs {
@@ -336,7 +298,7 @@ extern "C" int sir_wave_reverb_mix(sir_handle* h, const void* wave, int wave_dty
                       (long long)wave_stride, (long long)out_stride);
         return SIR_EINVAL;
     }
-    if (wave_dtype != SIR_WAVE_F32 && wave_dtype != SIR_WAVE_I16) { sir_set_error("sir_wave_reverb_mix: unknown wave dtype %d", wave_dtype); return SIR_EINVAL; }
+    if (!sir_wave_elem_bytes(wave_dtype)) { sir_set_error("sir_wave_reverb_mix: unknown wave dtype %d", wave_dtype); return SIR_EINVAL; }
     if (rir_index) {
         if (max_rir_len < 1 || max_rir_len > kMaxRir) {
             sir_set_error("sir_wave_reverb_mix: max_rir_len %d is outside [1, %d]", max_rir_len, kMaxRir);
@@ -351,7 +313,7 @@ extern "C" int sir_wave_reverb_mix(sir_handle* h, const void* wave, int wave_dty
         sir_set_error("sir_wave_reverb_mix: noise_index needs a bank, offsets and SNRs (n_noise %d, noise_stride %lld)", n_noise, (long long)noise_stride);
         return SIR_EINVAL;
     }
-    const size_t wbytes = wave_dtype == SIR_WAVE_I16 ? 2 : 4;
+    const size_t wbytes = sir_wave_elem_bytes(wave_dtype);
     if (overlap(wave, ((size_t)(batch - 1) * wave_stride + max_len) * wbytes, out, ((size_t)(batch - 1) * out_stride + max_len) * sizeof(float))) {
         sir_set_error("sir_wave_reverb_mix: out overlaps wave (the convolution reads samples behind the ones it writes)");
         return SIR_EINVAL;

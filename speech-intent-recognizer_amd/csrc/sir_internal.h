@@ -41,6 +41,8 @@ static_assert(SIR_K_COUNT_ALL - SIR_K_COUNT == SIR_PROFILE_EXTRA_IDS, "include/s
 
 struct SirProfRec { int id; hipEvent_t e0, e1; };
 static inline size_t sir_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// bytes per sample of a waveform argument, 0 for a wave_dtype that is neither SIR_WAVE_F32 nor SIR_WAVE_I16
+static inline size_t sir_wave_elem_bytes(int wave_dtype) { return wave_dtype == SIR_WAVE_F32 ? 4 : wave_dtype == SIR_WAVE_I16 ? 2 : 0; }
 
 // polyphase resampling filter of one (orig_freq, new_freq) pair (frontend.hip), device tables
 struct sir_resample_table {
@@ -72,7 +74,7 @@ struct sir_handle {
     int4* mel_desc;     // [64] per slot, filters sorted by tap count: {filter (-1 = unused), first FFT bin, taps, offset into melw}
     int mel_nnz;
     // front-end geometry.  `general` = anything but n_fft 1024 / hop 512 / win_length 1024: sir_features_fwd then runs the general
-    // launch pair (features.hip: feat_gen_frames_kernel + feat_gen_norm_kernel) with the tables below, and `window` holds n_fft
+    // launch pair (features_gen.hip: feat_gen_frames_kernel + feat_gen_norm_kernel) with the tables below, and `window` holds n_fft
     // floats, the win_length window centred between zeros.  The specialised kernels keep their SIR_NFFT / SIR_HOP constants.
     int win_length;
     bool general;
@@ -237,9 +239,15 @@ bool sir_slots_check_layout(const char* who, const int32_t* slot_sizes, int n_sl
 // model_train_fwd.hip
 size_t sir_train_workspace_bytes_impl(int batch, int t_frames);
 
-// features.hip
+// features_gen.hip (feat_lds.h: FeatGenLds)
 size_t sir_features_gen_lds_bytes(int n_fft, int mel_nnz);   // dynamic LDS the general frames kernel needs on such a handle
 #define SIR_LDS_BYTES (160 * 1024)                            // per workgroup on gfx950
+// (the general launch pair behind sir_features_launch, and its dB slab: the workspace)
+size_t sir_features_gen_slab_bytes(const sir_handle* h, int batch, int max_len);
+int sir_features_gen_launch(sir_handle* h, const void* wave, int wave_dtype, int64_t wave_stride, const int32_t* lengths, int batch,
+                            int max_len, float* out, int t_pad, float* db_out, void* workspace, const sir_augment* aug,
+                            hipStream_t stream);
+// features_fwd.hip, features_bwd.hip
 int sir_features_launch(sir_handle* h, const void* wave, int wave_dtype, int64_t wave_stride,
                         const int32_t* lengths, int batch, int max_len, float* out, int t_pad,
                         float* db_out, void* workspace, size_t workspace_bytes, const sir_augment* aug,

@@ -264,7 +264,7 @@ bool base_ok(const sir_stream_config* cfg, const char* who) {
                                (double)v.threshold, v.silence_chunks, v.prior_chunks);
         return false;
     }
-    if (cfg->wave_dtype != SIR_WAVE_F32 && cfg->wave_dtype != SIR_WAVE_I16) {
+    if (!sir_wave_elem_bytes(cfg->wave_dtype)) {
         if (who) sir_set_error("%s: bad wave_dtype %d", who, cfg->wave_dtype);
         return false;
     }
@@ -299,7 +299,7 @@ Layout layout(const sir_stream_config* cfg) {
     l.per = chunks_per_push(cfg);
     l.K = l.per + 1;
     l.RC = (long long)cfg->ring_chunks * cfg->vad.chunk_size;
-    const size_t esz = cfg->wave_dtype == SIR_WAVE_I16 ? 2 : 4;
+    const size_t esz = sir_wave_elem_bytes(cfg->wave_dtype);
     l.ring_off = sir_align_up((size_t)cfg->n_streams * sizeof(StreamState), 256);
     l.flags_off = sir_align_up(l.ring_off + (size_t)cfg->n_streams * (size_t)l.RC * esz, 256);    // < 2^16 * 2^33 * 4
     l.total = sir_align_up(l.flags_off + (size_t)cfg->n_streams * l.K, 256);

@@ -331,7 +331,7 @@ extern "C" int sir_vad_segment(sir_handle* h, const void* wave, int wave_dtype, 
         sir_set_error("sir_vad_segment: NULL argument");
         return SIR_EINVAL;
     }
-    if (wave_dtype != SIR_WAVE_F32 && wave_dtype != SIR_WAVE_I16) { sir_set_error("sir_vad_segment: bad wave_dtype %d", wave_dtype); return SIR_EINVAL; }
+    if (!sir_wave_elem_bytes(wave_dtype)) { sir_set_error("sir_vad_segment: bad wave_dtype %d", wave_dtype); return SIR_EINVAL; }
     if (n_rec <= 0 || max_len <= 0 || wave_stride < max_len || seg_cap < 0) {
         sir_set_error("sir_vad_segment: bad sizes (n_rec %d, max_len %d, wave_stride %lld, seg_cap %d)", n_rec, max_len, (long long)wave_stride, seg_cap);
         return SIR_EINVAL;
@@ -366,7 +366,7 @@ extern "C" int sir_vad_gather(sir_handle* h, const void* wave, int wave_dtype, i
                               const int32_t* total, int seg_cap, float* out, int64_t out_stride, int max_clip_len, int32_t* out_lengths,
                               void* stream) {
     if (!h || !wave || !seg_table || !total || !out || !out_lengths) { sir_set_error("sir_vad_gather: NULL argument"); return SIR_EINVAL; }
-    if (wave_dtype != SIR_WAVE_F32 && wave_dtype != SIR_WAVE_I16) { sir_set_error("sir_vad_gather: bad wave_dtype %d", wave_dtype); return SIR_EINVAL; }
+    if (!sir_wave_elem_bytes(wave_dtype)) { sir_set_error("sir_vad_gather: bad wave_dtype %d", wave_dtype); return SIR_EINVAL; }
     if (n_rec <= 0 || wave_stride <= 0 || seg_cap <= 0 || max_clip_len <= 0 || out_stride < max_clip_len ||
         ((long long)max_clip_len + kThreads * 4 - 1) / (kThreads * 4) > 65535) {
         sir_set_error("sir_vad_gather: bad sizes (n_rec %d, wave_stride %lld, seg_cap %d, max_clip_len %d, out_stride %lld)", n_rec,

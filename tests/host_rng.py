@@ -3,7 +3,7 @@ draws to the CPU oracle:
 
 * ``dropout_keep``  -- csrc/train_fwd_kernels.h ``dropout_keep(seed, idx, p)``: the keep mask of the inter-layer GRU dropout
   (reference models/models.py:26-33, ``nn.GRU(dropout=0.5)``), a pure function of (seed, element index);
-* ``gauss_noise``   -- csrc/features.hip ``gauss_pair(seed, b, i >> 1)``: the N(0,1) sample added to sample i of utterance b
+* ``gauss_noise``   -- csrc/feat_common.h ``gauss_pair(seed, b, i >> 1)``: the N(0,1) sample added to sample i of utterance b
   by the fused ``add_noise`` (reference scripts/augment.py:82-96).
 
 Integer parts are bit-exact (wrap-around arithmetic); the Box-Muller transform uses the device's hardware log2 / sqrt /
@@ -44,7 +44,7 @@ def _fmix32(x):
 
 def gauss_noise(seed, b, n):
     """float32 [n]: the standard-normal stream of utterance ``b`` (sample indices 0..n-1).  One Box-Muller draw per
-    sample PAIR p = i >> 1: sample 2p takes r*cos, sample 2p+1 takes r*sin (features.hip ``gauss_pair``)."""
+    sample PAIR p = i >> 1: sample 2p takes r*cos, sample 2p+1 takes r*sin (feat_common.h ``gauss_pair``)."""
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     lo, hi = np.uint32(seed & 0xFFFFFFFF), np.uint32(seed >> 32)
     npair = (n + 1) // 2

@@ -40,9 +40,9 @@ Measured on MI355X (worst over each sweep; the float32 oracle's own figure on th
   backward int16    worst 1.18 at T = 129, L = 66047, median 0.99
 The forward's worst clip is the float32 oracle's worst clip too: the kernel is as far from float64 as ``torch.stft`` in float32
 is, 0.6 of the tolerance.  No frame count, hop offset, row alignment or t_pad stands out, and no defect was found in
-csrc/features.hip.
+csrc/features_fwd.hip / features_bwd.hip (then one file, csrc/features.hip).
 
-Three arithmetic-only mutations of csrc/features.hip, each built once on a scratch copy and run against this module: without the
+Three arithmetic-only mutations of that file (now features_bwd.hip, features_fwd.hip and feat_common.h), each built once on a scratch copy and run against this module: without the
 ``L == (T - 1) * SIR_HOP`` fix-up ``test_backward_folds_the_last_padded_sample`` fails (coefficient -1.000) and nothing else;
 ``q * NW + mf <= T`` in the forward's statistics fails ``test_forward_every_frame_count`` (normalised 1.1e-1 at T = 2) and
 ``test_augmentation_at_the_edges``; ``2 * L - 1 - i`` in ``fetch`` fails the forward (10 dB in the last frame), backward (ratio

@@ -97,7 +97,13 @@ int sir_destroy(sir_handle* h);
  *   length (clamped to max_out_len); out_lengths: optional device int32[batch].
  *   The first call for a rate pair builds the filter table on the host and uploads it (host-synchronous,
  *   two small hipMallocs owned by the handle); later calls only launch.
- * sir_resample_out_len: host helper, ceil(new * length / orig) with gcd-reduced rates (-1 on bad input). */
+ *   lengths[b] above max_len is read as max_len; a NEGATIVE lengths[b] is an empty clip (zero row, out_lengths[b] = 0),
+ *   as a negative frames[b] is for sir_mix_to_mono.  Neither kernel reads a sample at or behind a clip's length.
+ * sir_resample_out_len: host helper, ceil(new * length / orig) with gcd-reduced rates; -1 on bad input (negative length,
+ *   non-positive rate) and -1 when the value does not fit an int (2147483647 samples at 16000 -> 48000).
+ * Tested against a direct float64 evaluation (tests/frontend_edge_ref.py) for sixteen rate pairs -- 44100 / 48000 / 16000 /
+ *   22050 -> 8000, 11025 / 12000 / 32000 / 96000 / 22050 / 44100 -> 16000, 16000 -> 22050 / 48000 / 44100, 8000 -> 48000,
+ *   44100 <-> 48000 -- at every tap of every phase and at the block and clip edges (tests/test_frontend_edge_gpu.py). */
 int sir_mix_to_mono(sir_handle* h, const void* pcm, int dtype, int channels, int64_t clip_stride,
                     const int32_t* frames, int batch, int max_frames, float* out, int64_t out_stride,
                     void* stream);

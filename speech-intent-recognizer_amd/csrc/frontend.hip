@@ -69,7 +69,7 @@ __global__ __launch_bounds__(256) void resample_kernel(const WT* __restrict__ wa
                                                        int max_out_len, int* __restrict__ out_lengths) {
     const int b = blockIdx.y;
     const int j = blockIdx.x * 256 + threadIdx.x;
-    const int len = min(lengths ? lengths[b] : max_len, max_len);
+    const int len = max(min(lengths ? lengths[b] : max_len, max_len), 0);               // a negative length is an empty clip
     const long long target64 = ((long long)nw * len + orig - 1) / orig;                 // ceil(new * len / orig)
     const int target = (int)min(target64, (long long)max_out_len);
     if (j == 0 && out_lengths) out_lengths[b] = target;
@@ -138,7 +138,8 @@ extern "C" int sir_resample_out_len(int length, int orig_freq, int new_freq) {
     if (length < 0 || orig_freq <= 0 || new_freq <= 0) return -1;
     const int g = gcd_int(orig_freq, new_freq);
     const long long orig = orig_freq / g, nw = new_freq / g;
-    return (int)((nw * length + orig - 1) / orig);
+    const long long target = (nw * length + orig - 1) / orig;
+    return target > 2147483647ll ? -1 : (int)target;               // a length that does not fit an int is bad input too
 }
 
 extern "C" int sir_resample(sir_handle* h, const void* wave, int wave_dtype, int64_t wave_stride, const int32_t* lengths, int batch,

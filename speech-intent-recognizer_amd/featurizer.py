@@ -284,6 +284,9 @@ class HipFeaturizer:
             return (wave if wave.dtype == torch.float32 else wave.float() / 32768.0), lengths
         lib = _native.lib()
         max_out = lib.sir_resample_out_len(max_len, int(orig_freq), int(new_freq))
+        if max_out < 0:
+            raise _native.SirError(f"resample: bad rates {orig_freq} -> {new_freq} Hz, or the output of {max_len} samples "
+                                   "does not fit an int32 length")
         out = torch.empty((bsz, max_out), dtype=torch.float32, device=wave.device)
         out_len = torch.empty((bsz,), dtype=torch.int32, device=wave.device)
         rc = lib.sir_resample(self._h, wave.data_ptr(), dt, wave.stride(0), lengths.data_ptr(), bsz, max_len,

@@ -13,6 +13,11 @@ seeded: bursts of 1-3 s of noise separated by 1.5-6 s of near silence, a differe
 Each figure is the median of 5 timed regions between HIP events, behind a warm-up run; a region is one whole run of pushes, its time
 divided by their number.  `total` is not read by the host inside a region (the table is sized for the worst case), so the figures
 are device time per push, not the latency of a host loop.  Prints one JSON object; ``--out FILE`` also writes it there.
+
+``--input-rate HZ`` and / or ``--encoding pcm|ulaw|alaw`` time the stream input stage instead (sir_stream_input_push in front of
+sir_stream_push): one push of a float32 segmenter that is handed 1024 samples at 16 kHz per stream, against one push of a segmenter
+with the front stage that is handed the same 64 ms at the callers' rate and codec (512 bytes at 8 kHz mu-law), same process, raw
+library calls, no host read inside a region, median of 7 regions.
 """
 import argparse
 import ctypes as C
@@ -68,8 +73,78 @@ def make_audio(n_streams, n_chunks, seed, dev):
     return (x.clamp_(-1.0, 1.0) * 32767.0).round_().to(torch.int16).reshape(n_streams, -1)
 
 
+def front_stage(args, dev):
+    """push with and without the stream input stage at the same number of 16 kHz samples"""
+    from sir_amd import g711
+    regions, S, n_push = 7, args.streams, min(args.pushes, 64)
+    rate = args.input_rate or SR
+    enc = args.encoding or "pcm"
+    per_in = 1024 * rate // SR
+    if per_in < 1:
+        raise SystemExit(f"--input-rate {rate}: a push of 64 ms holds no sample")
+    n_chunks = max(n_push, -(-n_push * per_in // 1024))             # enough audio for n_push pushes at either rate
+    pcm = make_audio(S, n_chunks, args.seed, dev)                   # int16 [S, n_chunks * 1024]
+    plain = StreamSegmenter(S, 1024, dtype=torch.float32, device=dev)
+    plain.reset()
+    wave16 = pcm[:, :n_push * 1024].float() / 32768.0
+    src = pcm[:, :n_push * per_in].contiguous()                      # the same kind of signal, read at the callers' rate
+    assert src.shape[1] == n_push * per_in and wave16.shape[1] == n_push * 1024
+    if enc != "pcm":
+        src = torch.from_numpy(g711.encode(src.cpu().numpy(), enc)).to(dev)
+    front = StreamSegmenter(S, per_in, device=dev, input_rate=rate, encoding=enc)
+    front.reset()
+    lib, st = _native.lib(), _native.current_stream_ptr()
+    full16 = torch.full((S,), 1024, dtype=torch.int32, device=dev)
+    full_in = torch.full((S,), per_in, dtype=torch.int32, device=dev)
+    esz = src.element_size()
+
+    def seg_push(ss, ptr, stride, width, lengths):
+        rc = lib.sir_stream_push(ss._handle, ss._state.data_ptr(), ss._state.numel(), C.byref(ss._cfg), ptr, stride, width, lengths.data_ptr(),
+                                 None, None, ss._table.data_ptr(), ss.max_rows, ss._total.data_ptr(), st)
+        _native.check(rc, "sir_stream_push")
+
+    def run_plain():
+        plain.reset()
+        for k in range(n_push):
+            seg_push(plain, wave16.data_ptr() + 4 * 1024 * k, wave16.stride(0), 1024, full16)
+
+    si = front.input
+    conv = front._converted
+    conv_len = torch.zeros((S,), dtype=torch.int32, device=dev)
+
+    def front_only(k):
+        rc = lib.sir_stream_input_push(si._handle, si._state.data_ptr(), si._state.numel(), C.byref(si._cfg), src.data_ptr() + esz * per_in * k,
+                                       src.stride(0), per_in, full_in.data_ptr(), None, conv.data_ptr(), conv.stride(0), conv_len.data_ptr(), st)
+        _native.check(rc, "sir_stream_input_push")
+
+    def run_front(segment=True):
+        front.reset()
+        for k in range(n_push):
+            front_only(k)
+            if segment:
+                seg_push(front, conv.data_ptr(), conv.stride(0), conv.shape[1], conv_len)
+
+    def med(fn):
+        fn()
+        torch.cuda.synchronize()
+        ms = [region_ms(fn) / n_push for _ in range(regions)]
+        return round(float(np.median(ms)), 5), [round(x, 5) for x in ms]
+    plain_ms, plain_raw = med(run_plain)
+    front_ms, front_raw = med(run_front)
+    stage_ms, stage_raw = med(lambda: run_front(False))
+    ops.check_status()
+    return {"device": torch.cuda.get_device_name(0), "streams": S, "pushes_per_region": n_push, "regions": regions,
+            "input_rate": rate, "encoding": enc, "input_dtype": str(si.dtype), "samples_in_per_push": per_in, "samples_16k_per_push": 1024,
+            "front_max_out": si.max_out, "front_state_bytes": si._state.numel(),
+            "statistic": "median over the regions of (HIP-event time of a run of pushes / pushes), ms per push; no host read inside a region",
+            "push_without_front_ms": plain_ms, "push_with_front_ms": front_ms, "front_stage_alone_ms": stage_ms,
+            "regions_ms": {"without_front": plain_raw, "with_front": front_raw, "front_stage_alone": stage_raw}}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--input-rate", type=int, default=None, help="time the stream input stage: the callers' sample rate (Hz)")
+    ap.add_argument("--encoding", type=str, default=None, choices=["pcm", "ulaw", "alaw"], help="time the stream input stage: the callers' codec")
     ap.add_argument("--streams", type=int, default=1024)
     ap.add_argument("--pushes", type=int, default=256, help="consecutive pushes of one timed region (256 = 16.4 s of audio per stream)")
     ap.add_argument("--seed", type=int, default=0)
@@ -77,6 +152,14 @@ def main():
     args = ap.parse_args()
     _native.require_hip()
     dev = torch.device("cuda", 0)
+    if args.input_rate is not None or args.encoding is not None:
+        res = front_stage(args, dev)
+        print(json.dumps(res))
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(json.dumps(res, indent=1) + "\n")
+        return
     S, n_push = args.streams, args.pushes
     wave = make_audio(S, n_push, args.seed, dev)
     ss = StreamSegmenter(S, 1024, dtype=torch.int16, device=dev)

@@ -533,6 +533,57 @@ int sir_stream_gather(sir_handle* h, const void* state, size_t state_bytes, cons
                       const int32_t* total, int seg_cap, float* out, int64_t out_stride, int max_clip_len, int32_t* out_lengths,
                       void* stream);
 
+/* ---- live streams at the caller's rate and codec (DESIGN.md section 4 "Stream input") ----------------------------------
+ * The stage in front of sir_stream_push for audio that does not arrive as PCM at the handle's rate: S independent streams of
+ * G.711 bytes, int16 or float32 at in_rate, each decoded and rate-converted to float32 at out_rate push by push, with the filter
+ * state carried in ONE caller-owned device buffer (`state`, sir_stream_input_state_bytes bytes, 256-byte aligned).  The
+ * concatenation of a stream's outputs over its life is bit for bit what sir_resample returns for the whole decoded stream: it does
+ * not depend on how the samples were cut into pushes.  Conventions are sir_stream_push's: asynchronous on `stream`, nothing
+ * allocates in push (the first reset for a rate pair builds the filter table host-synchronously, as the first sir_resample does),
+ * no atomics, stream s depends on stream s alone, every argument is checked before any launch, a refused call writes nothing and
+ * leaves the state where it was, no profile ids.
+ *   decoding : to a 16-bit linear value v, then x = v / 32768 (exact).  mu-law byte b: u = ~b & 0xFF, t = (((u & 0x0F) << 3) + 0x84)
+ *     << ((u >> 4) & 7), v = (u & 0x80) ? 0x84 - t : t - 0x84.  A-law byte b: a = b ^ 0x55, e = (a >> 4) & 7, m = a & 0x0F,
+ *     t = e ? ((m << 4) + 0x108) << (e - 1) : (m << 4) + 8, v = (a & 0x80) ? t : -t.  I16: s / 32768.  F32: as it is.
+ *   filter   : sir_resample's table for (in_rate, out_rate) -- gcd-reduced orig and nw, width, chain length L, first[p], taps[p][l].
+ *     Output j = q nw + p is the chain acc = fmaf(taps[p][l], x[q orig + first[p] - width + l], acc), l = 0 .. L - 1, from acc = 0,
+ *     with x[i] = 0 for i < 0 and, once the stream is closed at n samples, for i >= n: resample_kernel's chain, tap for tap.
+ *   emission : output j needs need(j) = q orig + first[p] - width + L samples.  E(n) = the largest J with need(j) <= n for all
+ *     j < J.  A stream that has received n samples has emitted exactly the outputs j < E(n): a push that takes it from n0 to n1
+ *     writes outputs E(n0) .. E(n1) - 1 to out[s][0 ..] and their count to out_lengths[s]; columns behind the count are not written.
+ *     m_s = clamp(in_lengths[s], 0, min(in_width, max_in)); only [0, m_s) of row s of `in` ([S][in_stride], elements of in_dtype)
+ *     is read.  m_s == 0 without close: the stream is untouched, out_lengths[s] = 0.
+ *     close[s] != 0 (close == NULL: none), after the append: the outputs up to sir_resample_out_len(n1, in_rate, out_rate) are
+ *     emitted with the zero tail, and the stream's counters return to zero (the slot can take a new caller from position 0).
+ *     in_rate == out_rate: out is the decoded input, out_lengths[s] = m_s, nothing is held back.
+ *   state    : per stream n and the emitted count (int64), and a ring of the most recent H = 2 (2 width + orig) decoded float32
+ *     samples (sample i at ring offset i mod H); H = 0 when the rates are equal.  Never the stream.
+ *   sir_stream_input_max_out: the most outputs one push can emit per stream, ceil(nw (max_in + 3 width + 2 orig) / orig) + 1
+ *     (E(n) >= nw (n - 3 width - 2 orig) / orig and out_len(n + m) < nw (n + m) / orig + 1); max_in when the rates are equal.
+ *     out_stride below it is SIR_EINVAL.  -1 on a bad config or when the value does not fit an int.
+ *   sir_stream_input_reset: zeroes the counters of the streams with mask[s] != 0 (mask == NULL: all).  Must run once before the
+ *     first push.
+ * SIR_EINVAL: NULL pointers, a bad in_dtype, rates <= 0, n_streams outside [1, 65535], max_in outside [1, 2^24], in_width outside
+ * [1, max_in] or above in_stride, a state that is not 256-byte aligned, out_stride below sir_stream_input_max_out, a max_out that
+ * does not fit an int.  state_bytes too small: SIR_ENOMEM.  sir_stream_input_state_bytes returns 0 for a config the calls refuse.
+ * SIR_WAVE_ULAW / SIR_WAVE_ALAW are accepted ONLY here: every other entry point keeps refusing them. */
+#define SIR_WAVE_ULAW 2   /* G.711 mu-law, one byte per sample; accepted ONLY by sir_stream_input_* */
+#define SIR_WAVE_ALAW 3   /* G.711 A-law, likewise */
+typedef struct sir_stream_input_config {
+    int n_streams;   /* S, 1 .. 65535 */
+    int in_dtype;    /* SIR_WAVE_F32 | SIR_WAVE_I16 | SIR_WAVE_ULAW | SIR_WAVE_ALAW */
+    int in_rate;     /* Hz, > 0 */
+    int out_rate;    /* Hz, > 0; == in_rate is legal (decode / copy only) */
+    int max_in;      /* most samples one push may bring per stream, 1 .. 2^24 */
+} sir_stream_input_config;
+int    sir_stream_input_max_out(const sir_stream_input_config* cfg);
+size_t sir_stream_input_state_bytes(const sir_handle* h, const sir_stream_input_config* cfg);
+int    sir_stream_input_reset(sir_handle* h, void* state, size_t state_bytes, const sir_stream_input_config* cfg,
+                              const uint8_t* mask, void* stream);
+int    sir_stream_input_push(sir_handle* h, void* state, size_t state_bytes, const sir_stream_input_config* cfg,
+                             const void* in, int64_t in_stride, int in_width, const int32_t* in_lengths, const uint8_t* close,
+                             float* out, int64_t out_stride, int32_t* out_lengths, void* stream);
+
 /* The GRU recurrence kernels (forward and backward) exchange hidden-state slices between the workgroups of a
  * cluster through tagged granules in global memory and rely on the cluster being co-resident.  A workgroup that
  * spins past its limit (a partitioned / oversubscribed GPU, a stalled peer) sets a device status word owned by the

@@ -19,6 +19,7 @@ SIR_EUNSUPPORTED = -4
 SIR_ETIMEOUT = -5
 SIR_ENOMEM = -2
 WAVE_F32, WAVE_I16 = 0, 1
+WAVE_ULAW, WAVE_ALAW = 2, 3     # G.711, one byte per sample: accepted only by sir_stream_input_*
 BWD_ALL, BWD_HEAD_GRU, BWD_CNN = 0, 1, 2
 STREAM_FORCED, STREAM_FLUSHED = 1, 2     # flags column of a sir_stream_push table row
 PROFILE_EXTRA_IDS = 1           # SIR_PROFILE_EXTRA_IDS: profile ids behind sir_profile_kernel_count() (include/sir_hip.h)
@@ -69,6 +70,10 @@ class StreamConfig(C.Structure):
                 ("ring_chunks", C.c_int)]
 
 
+class StreamInputConfig(C.Structure):
+    _fields_ = [("n_streams", C.c_int), ("in_dtype", C.c_int), ("in_rate", C.c_int), ("out_rate", C.c_int), ("max_in", C.c_int)]
+
+
 class AdvConfig(C.Structure):
     _fields_ = [("eps", C.c_float), ("alpha", C.c_float), ("keep_zero_columns", C.c_int)]
 
@@ -115,6 +120,11 @@ SIGNATURES = {
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "sir_stream_gather": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(StreamConfig), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
                                     C.c_int64, C.c_int, C.c_void_p, C.c_void_p]),
+    "sir_stream_input_max_out": (C.c_int, [C.POINTER(StreamInputConfig)]),
+    "sir_stream_input_state_bytes": (C.c_size_t, [C.c_void_p, C.POINTER(StreamInputConfig)]),
+    "sir_stream_input_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(StreamInputConfig), C.c_void_p, C.c_void_p]),
+    "sir_stream_input_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(StreamInputConfig), C.c_void_p, C.c_int64, C.c_int,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "sir_gather_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
     "sir_mix_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,

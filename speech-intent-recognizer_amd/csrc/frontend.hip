@@ -115,7 +115,7 @@ __global__ __launch_bounds__(256) void mono_kernel(const WT* __restrict__ pcm, i
 
 }  // namespace
 
-static bool get_resample_table(sir_handle* h, int orig_freq, int new_freq, sir_resample_table* out) {
+bool sir_get_resample_table(sir_handle* h, int orig_freq, int new_freq, sir_resample_table* out) {
     for (auto& t : h->resample_tables)
         if (t.orig_freq == orig_freq && t.new_freq == new_freq) { *out = t; return true; }
     HostTable ht = build_table(orig_freq, new_freq);
@@ -153,7 +153,7 @@ extern "C" int sir_resample(sir_handle* h, const void* wave, int wave_dtype, int
     if (!sir_wave_elem_bytes(wave_dtype)) { sir_set_error("sir_resample: unknown wave dtype %d", wave_dtype); return SIR_EINVAL; }
     sir_resample_table tab;
     sir_resample_table* t = &tab;
-    if (!get_resample_table(h, orig_freq, new_freq, t)) { sir_set_error("sir_resample: could not build the %d -> %d Hz filter table", orig_freq, new_freq); return SIR_EHIP; }
+    if (!sir_get_resample_table(h, orig_freq, new_freq, t)) { sir_set_error("sir_resample: could not build the %d -> %d Hz filter table", orig_freq, new_freq); return SIR_EHIP; }
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((max_out_len + 255) / 256, batch);
     if (wave_dtype == SIR_WAVE_I16)

@@ -233,6 +233,10 @@ struct SirProfScope {
     }
 };
 
+// frontend.hip: the handle's table for a rate pair (orig_freq != new_freq), built, uploaded and cached on first use
+// (host-synchronous, two small hipMallocs owned by the handle); later calls only look it up.  false: the build failed.
+bool sir_get_resample_table(sir_handle* h, int orig_freq, int new_freq, sir_resample_table* out);
+
 // slots.hip: the slot-layout rules of include/sir_hip.h; fills start[8] / size[8], or sets `who`'s error and returns false
 bool sir_slots_check_layout(const char* who, const int32_t* slot_sizes, int n_slots, int num_classes, int* start, int* size);
 

@@ -199,40 +199,53 @@ class IntentRecognizer:
         return results
 
     # ---- live streams ----------------------------------------------------------------------------------------------------
-    def open_streams(self, n_streams, max_push=1024, max_utterance=10.0, dtype=torch.float32, pad_to=TRAINED_LENGTH, on_device=False,
-                     temperature=None, min_confidence=None):
+    def open_streams(self, n_streams, max_push=1024, max_utterance=10.0, dtype=None, pad_to=TRAINED_LENGTH, on_device=False,
+                     temperature=None, min_confidence=None, sample_rate=None, encoding=None):
         """What ``MicrophoneListener.listen`` + ``predict`` do for one microphone (testing.py:49-143), for ``n_streams`` sources
-        that deliver at most ``max_push`` samples of ``dtype`` per ``feed``: -> a ``StreamSession``.  The detector takes the
-        listener values of this recogniser's ``segmenter``; an utterance longer than ``max_utterance`` seconds is ended there.
-        ``pad_to`` / ``on_device`` / ``temperature`` / ``min_confidence`` as in ``recognize_recordings``."""
-        return StreamSession(self, n_streams, max_push, max_utterance, dtype, pad_to, on_device, temperature, min_confidence)
+        that deliver at most ``max_push`` samples of ``dtype`` (float32 unless given) per ``feed``: -> a ``StreamSession``.  The
+        detector takes the listener values of this recogniser's ``segmenter``; an utterance longer than ``max_utterance`` seconds
+        is ended there.  ``pad_to`` / ``on_device`` / ``temperature`` / ``min_confidence`` as in ``recognize_recordings``.
+        ``sample_rate`` (Hz, default the segmenter's) / ``encoding`` ("pcm", "ulaw", "alaw"; default "pcm"): the callers' own rate
+        and codec -- e.g. 8000 and "ulaw" for G.711 telephony, fed as bytes.  The streams are then decoded and rate-converted on
+        the GPU with carried filter state (``sir_amd.streaming.StreamInput``), ``max_push`` counts the callers' samples, and
+        ``start`` / ``end`` stay seconds."""
+        return StreamSession(self, n_streams, max_push, max_utterance, dtype, pad_to, on_device, temperature, min_confidence,
+                             sample_rate, encoding)
 
 
 class StreamSession:
     """Utterances of many live streams, scored as they end (``IntentRecognizer.open_streams``)."""
 
-    def __init__(self, recognizer, n_streams, max_push, max_utterance, dtype, pad_to, on_device, temperature, min_confidence):
+    def __init__(self, recognizer, n_streams, max_push, max_utterance, dtype, pad_to, on_device, temperature, min_confidence,
+                 sample_rate=None, encoding=None):
         from sir_amd.scripts import classify_results
         from sir_amd.streaming import StreamSegmenter
         classify_results.check_route(on_device, temperature, min_confidence)
         seg = recognizer.segmenter
         self.recognizer = recognizer
+        if dtype is None and encoding in (None, "pcm"):
+            dtype = torch.float32
         self.segmenter = StreamSegmenter(n_streams, max_push, max_utterance, dtype, recognizer.device, sample_rate=seg.sample_rate,
                                          chunk_size=seg.chunk_size, threshold=seg.threshold, silence_limit=seg.silence_limit,
-                                         prior_recording=seg.prior_recording, flush_tail=seg.flush_tail)
+                                         prior_recording=seg.prior_recording, flush_tail=seg.flush_tail, input_rate=sample_rate,
+                                         encoding=encoding)
         self.pad_to = recognizer.mel_spec_length if pad_to == TRAINED_LENGTH else pad_to
         self.on_device, self.temperature, self.min_confidence = on_device, temperature, min_confidence
         self.last_logits = None
 
     def feed(self, chunks, lengths=None, close=()):
-        """chunks: ``{stream: 1-D array of new samples}`` (streams not named get nothing), or a padded [n_streams, <= max_push]
-        tensor with ``lengths``.  ``close``: the streams that end with this call.  -> the utterances that completed, stream-major
+        """chunks: ``{stream: new samples}`` -- a 1-D int16 / float array, or for G.711 streams ``bytes`` / a uint8 array of codes
+        (streams not named get nothing; samples already in the session's dtype are handed through unconverted, ``bytes`` are read
+        as that dtype) -- or a padded [n_streams, <= max_push] tensor with ``lengths``.  ``close``: the streams that end with this call.  -> the utterances that completed, stream-major
         then by time, as the dictionaries of ``recognize_recordings`` plus ``"stream"`` and ``"forced"`` (the utterance reached
         ``max_utterance`` and was cut there); ``start`` / ``end`` count from the stream's last close.  ``last_logits`` holds the
         logits of the utterances the latest call returned, row for row (None if there were none)."""
         from sir_amd.scripts import classify_results
         seg, reco = self.segmenter, self.recognizer
         if isinstance(chunks, dict):
+            np_dtype = torch.empty(0, dtype=seg.dtype).numpy().dtype
+            chunks = {s: (np.frombuffer(x, dtype=np_dtype).copy() if isinstance(x, (bytes, bytearray, memoryview)) else x)
+                      for s, x in chunks.items()}
             width = max([1] + [int(np.asarray(x).size) for x in chunks.values()])
             host = torch.zeros((seg.n_streams, width), dtype=seg.dtype)
             host_len = torch.zeros((seg.n_streams,), dtype=torch.int32)
@@ -241,6 +254,8 @@ class StreamSession:
                     raise ValueError(f"stream {s!r} outside [0, {seg.n_streams})")
                 x = torch.as_tensor(np.ascontiguousarray(x)).reshape(-1)
                 if x.dtype != seg.dtype:
+                    if seg.dtype == torch.uint8:
+                        raise ValueError(f"stream {s!r}: a G.711 stream is fed uint8 codes or bytes, not {x.dtype}")
                     x = x.float() / 32768.0 if x.dtype == torch.int16 else x.to(seg.dtype)
                 host[int(s), :x.numel()] = x
                 host_len[int(s)] = x.numel()

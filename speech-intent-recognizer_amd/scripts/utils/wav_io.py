@@ -1,7 +1,8 @@
 """Minimal RIFF/WAVE reader and writer (host I/O; stands in for ``torchaudio.load`` /
 ``torchaudio.save`` at scripts/precompute_features.py:47 and scripts/dataset.py:126, which are
-not installable here).  PCM 8/16/24/32-bit and IEEE float32; returns float32 in [-1, 1) with the
-torchaudio normalisation (int16 / 32768) or the raw int16 samples for the PCM16 fast path."""
+not installable here).  PCM 8/16/24/32-bit, IEEE float32 and 8-bit G.711 (format tags 7 mu-law, 6 A-law,
+expanded through ``sir_amd.g711``); returns float32 in [-1, 1) with the torchaudio normalisation
+(int16 / 32768) or the raw int16 samples for the PCM16 / G.711 fast path."""
 import struct
 
 import numpy as np
@@ -23,8 +24,9 @@ def _chunks(buf):
 
 
 def read_wav(path, prefer_int16=False):
-    """-> (samples [channels, frames], sample_rate).  ``prefer_int16`` keeps PCM16 data as int16
-    (the GPU kernel dequantises with the same 1/32768) instead of converting on the host."""
+    """-> (samples [channels, frames], sample_rate).  ``prefer_int16`` keeps PCM16 data, and the
+    16-bit expansion of G.711 data, as int16 (the GPU kernel dequantises with the same 1/32768)
+    instead of converting on the host."""
     with open(path, "rb") as f:
         buf = f.read()
     if len(buf) < 12 or buf[:4] != b"RIFF" or buf[8:12] != b"WAVE":
@@ -54,6 +56,13 @@ def read_wav(path, prefer_int16=False):
     if tag == 1 and bits == 8:
         x = np.frombuffer(raw, dtype=np.uint8, count=(size // ch) * ch).reshape(-1, ch).T
         return torch.from_numpy((x.astype(np.float32) - 128.0) / 128.0), sr
+    if tag in (7, 6) and bits == 8:                              # G.711 mu-law / A-law (telephony): one byte per sample
+        from sir_amd import g711
+        codes = np.frombuffer(raw, dtype=np.uint8, count=(size // ch) * ch).reshape(-1, ch).T
+        x = g711.decode(codes, "ulaw" if tag == 7 else "alaw")
+        if prefer_int16:
+            return torch.from_numpy(np.array(x, dtype=np.int16, order="C")), sr
+        return torch.from_numpy(x.astype(np.float32) / 32768.0), sr
     if tag == 1 and bits == 24:
         n = (size // 3 // ch) * ch
         b = np.frombuffer(raw, dtype=np.uint8, count=n * 3).reshape(-1, 3).astype(np.int32)

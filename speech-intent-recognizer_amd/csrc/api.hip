@@ -337,66 +337,66 @@ static int check_status_impl(sir_handle* h, hipStream_t st, const char* who) {
     if (v == 0) return SIR_OK;
     SIR_HIP_TRY(hipMemsetAsync(h->status, 0, sizeof(v), st));
     SIR_HIP_TRY(hipStreamSynchronize(st));
-    if (v & 1u) {
+    if (v & SIR_STATUS_GRU_TIMEOUT) {
         sir_set_error("%s: a GRU recurrence kernel timed out waiting for a peer workgroup of its cluster (status %u): the "
                       "logits / gradients produced since the last check are invalid", who, v);
         return SIR_ETIMEOUT;
     }
-    if (v & 8u) {
+    if (v & SIR_STATUS_CONV_WEIGHT) {
         sir_set_error("%s: a transformed convolution weight is outside the f16x3 path's range (|U| >= 32, status %u): the outputs "
                       "computed from the clamped value are invalid", who, v);
         return SIR_EINVAL;
     }
-    if (v & 2048u) {
+    if (v & SIR_STATUS_GRU_WEIGHT) {
         sir_set_error("%s: a GRU weight matrix (weight_ih / weight_hh) holds a value that is not finite or lies outside +-65504 (status %u): "
                       "the f16x3 planes were prepared from the clamped value and the outputs computed from them are invalid", who, v);
         return SIR_EINVAL;
     }
-    if (v & 4096u) {
+    if (v & SIR_STATUS_ACT_RANGE) {
         sir_set_error("%s: a training forward wrote an activation beyond the range the backward's weight-gradient contractions take "
                       "exactly (conv2 block output >= 256 or conv3 block output >= 512, status %u): the conv3 / GRU layer-0 WEIGHT gradients "
                       "computed from that workspace are invalid (logits, the loss and the input gradient are not affected)", who, v);
         return SIR_EINVAL;
     }
-    if (v & 8192u) {
+    if (v & SIR_STATUS_BN_PARAM) {
         sir_set_error("%s: a conv1 weight or a BatchNorm weight / bias / running statistic is not finite (status %u): ReLU and max-pool "
                       "drop the NaN, so the logits computed from it are finite and meaningless", who, v);
         return SIR_EINVAL;
     }
-    if (v & 16u) {
+    if (v & SIR_STATUS_PERTURB) {
         sir_set_error("%s: sir_wave_perturb was given a pitch outside [-200, 200] cents or a tempo outside [0.5, 2] (status %u): "
                       "those rows are zero with length 0", who, v);
         return SIR_EINVAL;
     }
-    if (v & 32u) {
+    if (v & SIR_STATUS_MIX_PERM) {
         sir_set_error("%s: sir_mix_features was given a permutation entry outside [0, batch) (status %u): those rows are zero", who, v);
         return SIR_EINVAL;
     }
-    if (v & 64u) {
+    if (v & SIR_STATUS_RAGGED_LENGTH) {
         sir_set_error("%s: sir_model_infer_ragged was given a length outside [8, t_frames] (status %u): those rows' logits are NaN", who, v);
         return SIR_EINVAL;
     }
-    if (v & 128u) {
+    if (v & SIR_STATUS_VAD_ROW) {
         sir_set_error("%s: sir_vad_gather was given a table row whose recording or sample range is outside the batch (status %u): those "
                       "rows are zero with length 0", who, v);
         return SIR_EINVAL;
     }
-    if (v & 256u) {
+    if (v & SIR_STATUS_REVERB) {
         sir_set_error("%s: sir_wave_reverb_mix was given an index outside its bank, a bank length outside its range or a NaN / "
                       "infinite snr_db (status %u): those rows are zero", who, v);
         return SIR_EINVAL;
     }
-    if (v & 512u) {
+    if (v & SIR_STATUS_EVAL_LABEL) {
         sir_set_error("%s: sir_eval_accumulate / sir_temperature_fit saw a label outside [0, num_classes) that is not -100 (status %u): "
                       "those rows were left out", who, v);
         return SIR_EINVAL;
     }
-    if (v & 1024u) {
+    if (v & SIR_STATUS_STREAM_ROW) {
         sir_set_error("%s: sir_stream_gather was given a table row whose stream or sample range is impossible (status %u): those rows "
                       "are zero with length 0", who, v);
         return SIR_EINVAL;
     }
-    if (v & 4u) {
+    if (v & SIR_STATUS_GATHER_INDEX) {
         sir_set_error("%s: sir_gather_features was given an index outside its store (status %u): those rows are zero", who, v);
         return SIR_EINVAL;
     }

@@ -79,7 +79,7 @@ __device__ __forceinline__ int w2_div(int n, const W2Div& d) {
 // word (bit 3: SIR_EINVAL at the next sir_check_status) -- conv weights of this model are O(0.1).
 __device__ __forceinline__ void split_w_f16x3(float u, unsigned short& p0, unsigned short& p1, unsigned int* status) {
     constexpr float LIM = 31.984375f;                       // 65504 / 2048
-    if (status && !(fabsf(u) <= LIM)) __hip_atomic_fetch_or(status, 8u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (status && !(fabsf(u) <= LIM)) __hip_atomic_fetch_or(status, SIR_STATUS_CONV_WEIGHT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     u = __builtin_fminf(__builtin_fmaxf(u, -LIM), LIM);
     const _Float16 hi = (_Float16)u;
     const _Float16 lo = (_Float16)((u - (float)hi) * H3_LO_SCALE);

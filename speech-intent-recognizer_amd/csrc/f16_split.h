@@ -49,7 +49,6 @@ __device__ __forceinline__ void split2h_quad(const float4& v, uint2& h, uint2& l
 
 // Weight preparation only: a GRU matrix element the split would clamp (|w| > 65504) or that is not finite -- the clamp turns a NaN into
 // a finite number -- raises bit 11 of the handle's status word (SIR_EINVAL at the next sir_check_status).  status == NULL: no check.
-constexpr unsigned int SIR_STATUS_GRU_WEIGHT = 2048u;
 __device__ __forceinline__ void split_flag_range(const float4& a, const float4& b, unsigned int* status) {
     if (!status) return;
     const bool ok = fabsf(a.x) <= 65504.0f && fabsf(a.y) <= 65504.0f && fabsf(a.z) <= 65504.0f && fabsf(a.w) <= 65504.0f &&

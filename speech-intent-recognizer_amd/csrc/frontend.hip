@@ -198,7 +198,7 @@ __global__ __launch_bounds__(256) void gather_features_kernel(const float* __res
     long long src = index[b];
     const bool bad = src < 0 || src >= n_store;
     if (bad) {                                              // an index outside the store: zeros + the handle's status word (SIR_EINVAL at the next check)
-        if (threadIdx.x == 0 && blockIdx.x == 0) __hip_atomic_fetch_or(status, 4u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (threadIdx.x == 0 && blockIdx.x == 0) __hip_atomic_fetch_or(status, SIR_STATUS_GATHER_INDEX, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         src = 0;
     }
     const int per = n_mels * t_pad / 4;
@@ -251,7 +251,7 @@ __global__ __launch_bounds__(256) void mix_features_kernel(const float* __restri
     long long src = perm[b];
     const bool bad = src < 0 || src >= (long long)batch;
     if (bad) {                                              // zeros + the handle's status word (SIR_EINVAL at the next check)
-        if (threadIdx.x == 0 && blockIdx.x == 0) __hip_atomic_fetch_or(status, 32u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (threadIdx.x == 0 && blockIdx.x == 0) __hip_atomic_fetch_or(status, SIR_STATUS_MIX_PERM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         src = 0;
     }
     const float l = lam[b], om = 1.0f - l;

@@ -196,7 +196,7 @@ static __global__ __launch_bounds__(1024) void ragged_tables_kernel(const int* _
         fw[u] = f;
         bad |= f == 0;
     }
-    if (bad) __hip_atomic_fetch_or(status, 64u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (bad) __hip_atomic_fetch_or(status, SIR_STATUS_RAGGED_LENGTH, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __syncthreads();                                          // fw is read back below by other threads of this (one) workgroup
     auto need = [&](int u, int& c1, int& c2, int& c3) {
         const int f = fw[u];

@@ -28,7 +28,6 @@ typedef float mk_f32x2 __attribute__((ext_vector_type(2)));
 // A conv1 weight or a BatchNorm weight / bias / statistic that is not finite sits in front of a ReLU and a max-pool that are fmaxf
 // and drop a NaN: the kernels that fold these parameters raise bit 13 of the handle's status word instead (SIR_EINVAL at the next
 // sir_check_status).
-constexpr unsigned int SIR_STATUS_BN_PARAM = 8192u;
 __device__ __forceinline__ bool sir_finite(float v) { return fabsf(v) < INFINITY; }
 __device__ __forceinline__ void sir_flag_bn_param(bool ok, unsigned int* status) {
     if (!ok) __hip_atomic_fetch_or(status, SIR_STATUS_BN_PARAM, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -41,7 +41,6 @@ constexpr float kMaxCents = 200.0f;    // |pitch| bound: sizes the workspace of 
 constexpr double kMaxStretch = 1.1224620483093730;    // 2^(200/1200)
 constexpr float kMinTempo = 0.5f, kMaxTempo = 2.0f;
 constexpr int kTab = 8;                // |n d - k| < 6 / b <= 6.81 at 200 cents, and |fr| <= 0.5: offsets i in [-7, 7]
-constexpr unsigned kStatusBadFactor = 16u;
 
 enum { kModeCents = 0, kModeTempo = 1, kModeCopy = 2 };
 
@@ -99,7 +98,7 @@ __global__ __launch_bounds__(kThreads) void wsola_kernel(const WT* __restrict__ 
     double f;
     if (!row_factor(mode, factor, b, &f) || (guard_cents && !(fabsf(guard_cents[b]) <= kMaxCents))) {
         if (tid == 0) {
-            __hip_atomic_fetch_or(status, kStatusBadFactor, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_or(status, SIR_STATUS_PERTURB, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (dst_len) dst_len[b] = 0;
         }
         for (int i = tid; i < cap; i += kThreads) y[i] = 0.0f;

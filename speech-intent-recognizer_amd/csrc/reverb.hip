@@ -38,7 +38,6 @@ constexpr int kMaxRir = 8192;
 constexpr int kMaxParts = kMaxRir / kPart;
 constexpr int kRingExtra = kWaves - 1; // ring slots beyond the partitions: a round's four spectra land before the oldest is dropped
 constexpr int kSlab = 8 * XS;          // complex slots of a wave's slab
-constexpr unsigned kStatusBadReverb = 256u;
 
 __device__ __forceinline__ cf32 cconj(cf32 a) { return cf32{a.x, -a.y}; }
 __device__ __forceinline__ cf32 mul_pi(cf32 a) { return cf32{-a.y, a.x}; }                       // a * (+i)
@@ -154,7 +153,7 @@ __global__ __launch_bounds__(kThreads) void reverb_mix_kernel(const WT* __restri
     }
     if (bad) {
         if (tid == 0) {
-            __hip_atomic_fetch_or(status, kStatusBadReverb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_or(status, SIR_STATUS_REVERB, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             gain[b] = 0.0f;
         }
         for (int i = tid; i < max_len; i += kThreads) y[i] = 0.0f;

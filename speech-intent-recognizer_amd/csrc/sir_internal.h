@@ -39,6 +39,34 @@ enum SirKernelId {
 };
 static_assert(SIR_K_COUNT_ALL - SIR_K_COUNT == SIR_PROFILE_EXTRA_IDS, "include/sir_hip.h: SIR_PROFILE_EXTRA_IDS");
 
+// Bits of the handle's device status word (sir_handle::status).  A kernel raises one with a relaxed agent-scope fetch_or;
+// api.hip check_status_impl reads and clears the word and turns the bits into an error.  include/sir_hip.h documents several
+// by number: the values are part of the contract and never move.
+enum SirStatusBit : unsigned int {
+    SIR_STATUS_GRU_TIMEOUT   = 1u,      // a GRU recurrence's exchange spin timed out (gru_quad_kernel.h, gru_bwd_quad_kernel.h)
+    SIR_STATUS_CE_LABEL      = 2u,      // cross-entropy label outside [0, C) that is not -100 (ce_loss_rows.h)
+    SIR_STATUS_GATHER_INDEX  = 4u,      // sir_gather_features: index outside the store (frontend.hip)
+    SIR_STATUS_CONV_WEIGHT   = 8u,      // transformed conv weight outside the f16x3 range (conv_wino2_f16x3_kernel.h)
+    SIR_STATUS_PERTURB       = 16u,     // sir_wave_perturb: pitch / tempo outside its range (perturb.hip)
+    SIR_STATUS_MIX_PERM      = 32u,     // sir_mix_features: permutation entry outside the batch (frontend.hip)
+    SIR_STATUS_RAGGED_LENGTH = 64u,     // ragged forward: a length outside [8, t_frames] (infer_tables.h, train_workspace.h)
+    SIR_STATUS_VAD_ROW       = 128u,    // sir_vad_gather: a table row outside the batch (vad.hip)
+    SIR_STATUS_REVERB        = 256u,    // sir_wave_reverb_mix: bad index, bank length or snr_db (reverb.hip)
+    SIR_STATUS_EVAL_LABEL    = 512u,    // sir_eval_accumulate* / sir_temperature_fit: label outside [0, C) that is not -100 (evaluate.hip)
+    SIR_STATUS_STREAM_ROW    = 1024u,   // sir_stream_gather: an impossible table row (stream.hip)
+    SIR_STATUS_GRU_WEIGHT    = 2048u,   // GRU weight not finite or outside +-65504 (f16_split.h)
+    SIR_STATUS_ACT_RANGE     = 4096u,   // training activation beyond the backward's exact range (train_fwd_kernels.h)
+    SIR_STATUS_BN_PARAM      = 8192u,   // conv1 weight / BatchNorm parameter not finite (model_kernels.h)
+};
+
+// Slot heads (include/sir_hip.h "slot heads"): one logit row as up to kMaxSlots softmax segments.  Passed to kernels by
+// value; the loss (slots.hip) and the evaluation (evaluate.hip) extend it with their own per-slot arrays.
+constexpr int kMaxSlots = 8;
+struct SlotTable {
+    int n;
+    int start[kMaxSlots], size[kMaxSlots];           // first column and width of segment g
+};
+
 struct SirProfRec { int id; hipEvent_t e0, e1; };
 static inline size_t sir_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 // bytes per sample of a waveform argument, 0 for a wave_dtype that is neither SIR_WAVE_F32 nor SIR_WAVE_I16

@@ -1,95 +1,21 @@
 // Slot heads, the loss (include/sir_hip.h: sir_ce_loss_slots): one logit row as several independent softmax segments, the
 // weighted sum of their soft-target cross-entropies and its gradient.  (sir_classify_slots and sir_eval_accumulate_slots sit
-// with their single-head relatives in evaluate.hip, whose row helpers they share.)
+// with their single-head relatives in evaluate.hip, where either form of a call wraps the same per-segment function.)
 //
-// The contract is bit identity, per slot, with sir_ce_loss_soft on a contiguous copy of the segment, so the kernel below is
-// ce_loss_kernel (train_loss_optim_kernels.h) run once per slot by ONE workgroup of 256 threads: the same thread-per-row map,
-// the same per-row expressions in the same order on a register array of the same length (32 for widths <= 32, else 64), the
-// same two LDS trees.  Only the addressing differs: a row's segment starts at logits + b * num_classes + start_g and its labels
-// at labels + b * n_slots + g.  The row arithmetic is restated here rather than shared so that ce_loss_kernel and the code
-// generated for it stay untouched.  Slots run one after the other: the total is then one thread's fp32 sum in slot order,
-// with no scratch buffer and no second launch.
+// The contract is bit identity, per slot, with sir_ce_loss_soft on a contiguous copy of the segment.  It holds by construction:
+// the kernel below runs ce_loss_kernel's body (ce_loss_rows.h: the valid-row count, the row arithmetic on a register array of
+// 32 floats for widths <= 32, else 64, the LDS sum) once per slot in ONE workgroup of 256 threads, with the segment's
+// addressing -- a row's segment starts at logits + b * num_classes + start_g, its labels are labels + b * n_slots + g.
+// Slots run one after the other: the total is then one thread's fp32 sum in slot order, with no scratch buffer and no
+// second launch.
 #include <cmath>
-#include "sir_internal.h"
+#include "ce_loss_rows.h"
 
 namespace {
 
-constexpr int kMaxSlots = 8;
-constexpr unsigned int kStatusBadCeLabel = 2u;       // api.hip check_status_impl, as ce_loss_kernel
-
-struct CeSlotTable {
-    int n;
-    int start[kMaxSlots], size[kMaxSlots];
+struct CeSlotTable : SlotTable {
     float gs[kMaxSlots], w[kMaxSlots];               // grad_scale * w_g (fp32 product), w_g
 };
-
-// this thread's rows of one slot -> its partial of the slot's loss sum; writes the slot's segment of dlogits
-template <int CMAX, bool SOFT>
-__device__ __forceinline__ float ce_slot_rows(const float* __restrict__ logits, const long long* __restrict__ labels,
-                                              const long long* __restrict__ labels_b, const float* __restrict__ lam, float eps,
-                                              int B, int NC, int G, int g, int start, int C, float nvalid, float grad_scale,
-                                              float* __restrict__ dlogits, unsigned int* status) {
-    float acc = 0.0f;
-    for (int b = threadIdx.x; b < B; b += 256) {
-        const float* r = logits + (size_t)b * NC + start;
-        const long long yl = labels[(size_t)b * G + g];
-        const bool ignored = yl == -100ll;
-        const bool bad = !ignored && (yl < 0 || yl >= (long long)C);
-        if (bad) __hip_atomic_fetch_or(status, kStatusBadCeLabel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int y = (bad || ignored) ? 0 : (int)yl;
-        if constexpr (SOFT) {
-            const long long yl2 = (labels_b && !ignored) ? labels_b[(size_t)b * G + g] : yl;
-            const bool bad2 = !ignored && (yl2 < 0 || yl2 >= (long long)C);
-            if (bad2) __hip_atomic_fetch_or(status, kStatusBadCeLabel, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int y2 = (bad2 || ignored) ? 0 : (int)yl2;
-            const float lm = (labels_b && lam) ? lam[b] : 1.0f;
-            const float wa = (1.0f - eps) * lm, wb = (1.0f - eps) * (1.0f - lm), u = eps / (float)C;
-            float v[CMAX];
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c) v[c] = c < C ? r[c] : 0.0f;
-            const float ra = r[y], rb = r[y2];
-            float mx = v[0];
-#pragma unroll
-            for (int c = 1; c < CMAX; ++c) if (c < C) mx = fmaxf(mx, v[c]);
-            float den = 0.0f, dsum = 0.0f;
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c) if (c < C) { const float d = v[c] - mx; dsum += d; v[c] = expf(d); den += v[c]; }
-            const float row = logf(den) - (wa * (ra - mx) + wb * (rb - mx) + u * dsum);
-            acc += (bad || bad2) ? __builtin_nanf("") : (ignored ? 0.0f : row);
-            if (dlogits) {
-                const float inv = 1.0f / den, gs = ignored ? 0.0f : grad_scale / nvalid;
-                float* dr = dlogits + (size_t)b * NC + start;
-#pragma unroll
-                for (int c = 0; c < CMAX; ++c)
-                    if (c < C) {
-                        const float q = u + (c == y ? wa : 0.0f) + (c == y2 ? wb : 0.0f);
-                        dr[c] = ignored ? 0.0f : (v[c] * inv - q) * gs;
-                    }
-            }
-            continue;
-        }
-        float v[CMAX];
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c) v[c] = c < C ? r[c] : 0.0f;
-        const float ry = r[y];
-        float mx = v[0];
-#pragma unroll
-        for (int c = 1; c < CMAX; ++c) if (c < C) mx = fmaxf(mx, v[c]);
-        float den = 0.0f;
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c) if (c < C) { v[c] = expf(v[c] - mx); den += v[c]; }
-        const float lse = mx + logf(den);
-        acc += bad ? __builtin_nanf("") : (ignored ? 0.0f : lse - ry);
-        if (dlogits) {
-            const float inv = 1.0f / den, gs = ignored ? 0.0f : grad_scale / nvalid;
-            float* dr = dlogits + (size_t)b * NC + start;
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c)
-                if (c < C) dr[c] = ignored ? 0.0f : (v[c] * inv - (c == y ? 1.0f : 0.0f)) * gs;
-        }
-    }
-    return acc;
-}
 
 template <bool SOFT>
 __global__ __launch_bounds__(256) void ce_loss_slots_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
@@ -103,26 +29,13 @@ __global__ __launch_bounds__(256) void ce_loss_slots_kernel(const float* __restr
     float total = 0.0f;                                                                  // thread 0's alone is used
     for (int g = 0; g < G; ++g) {                                                        // uniform over the workgroup
         const int start = tab.start[g], C = tab.size[g];
-        int nv = 0;
-        for (int b = threadIdx.x; b < B; b += 256) nv += labels[(size_t)b * G + g] != -100ll ? 1 : 0;
-        cnt[threadIdx.x] = nv;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if (threadIdx.x < o) cnt[threadIdx.x] += cnt[threadIdx.x + o];
-            __syncthreads();
-        }
-        const float nvalid = (float)cnt[0];
-        const float acc = C <= 32 ? ce_slot_rows<32, SOFT>(logits, labels, labels_b, lam, eps, B, NC, G, g, start, C, nvalid, tab.gs[g], dlogits, status)
-                                  : ce_slot_rows<64, SOFT>(logits, labels, labels_b, lam, eps, B, NC, G, g, start, C, nvalid, tab.gs[g], dlogits, status);
-        red[threadIdx.x] = acc;
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-            __syncthreads();
-        }
+        const float nvalid = ce_valid_rows(labels, B, G, g, cnt);
+        const float acc = C <= 32 ? ce_rows<32, SOFT>(logits, labels, labels_b, lam, eps, B, NC, start, G, g, C, nvalid, tab.gs[g], dlogits, status)
+                                  : ce_rows<64, SOFT>(logits, labels, labels_b, lam, eps, B, NC, start, G, g, C, nvalid, tab.gs[g], dlogits, status);
+        const float sum = ce_block_sum(acc, red);
         if (threadIdx.x == 0) {
 #pragma clang fp contract(off)                                                           // a rounded product, then a rounded sum: no fma
-            const float sl = red[0] / nvalid;
+            const float sl = sum / nvalid;
             if (slot_loss) slot_loss[g] = sl;
             const float term = tab.w[g] * sl;
             total = total + term;

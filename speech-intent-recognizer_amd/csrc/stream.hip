@@ -21,7 +21,6 @@
 
 namespace {
 
-constexpr unsigned int kStatusBadStreamRow = 1024u;   // sir_stream_gather: an impossible table row (SIR_EINVAL at the next check)
 constexpr int kMaxStreams = 65535;
 constexpr int kMaxIn = 1 << 24;
 constexpr int kMaxChunks = 1 << 20;                   // bound of max_utt_chunks and ring_chunks: every byte count stays far below 2^63
@@ -218,7 +217,7 @@ __global__ __launch_bounds__(kThreads) void stream_gather_kernel(const T* __rest
     const int len = bad ? 0 : (int)(en - st < max_clip ? en - st : max_clip);
     if (head) {
         out_lengths[s] = len;
-        if (bad) __hip_atomic_fetch_or(status, kStatusBadStreamRow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (bad) __hip_atomic_fetch_or(status, SIR_STATUS_STREAM_ROW, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     const int col = (blockIdx.y * kThreads + threadIdx.x) * V;
     if (col >= max_clip) return;

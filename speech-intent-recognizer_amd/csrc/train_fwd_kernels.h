@@ -198,7 +198,6 @@ static __global__ void bn_fold_running_kernel(const float* __restrict__ gamma, c
 // tensor exactly (a2: wgrad_wino_f16x3_kernel.h, 256; x0: gemm_tn2_f16x3_kernel.h, 512) -- raises bit 12 of the status word.
 // RAGGED (sir_model_train_fwd_ragged): clip b's pooled map is wlim[b] <= Wp columns wide; the columns behind it are written as
 // zeros and their z is not read -- the next stage runs at full width and reads them as the clip's right edge.
-constexpr unsigned int SIR_STATUS_ACT_RANGE = 4096u;
 template <bool GRU_OUT, bool RAGGED = false>
 __global__ __launch_bounds__(256) void bn_relu_pool_kernel(const float* __restrict__ z, const float* __restrict__ scale,
                                                             const float* __restrict__ shift, float* __restrict__ out,

@@ -2,15 +2,11 @@
 // gradient norm.  Included by train_loss_optim.hip.
 #pragma once
 #include "sir_internal.h"
+#include "ce_loss_rows.h"
 
 // ------------------------------------------------------------------------------------------
-// cross-entropy (mean) forward + gradient wrt logits:  loss = -mean_b log softmax(l_b)[y_b],
-// dlogits = (softmax - onehot) * grad_scale / (rows whose label is not ignore_index)      (nn.CrossEntropyLoss(), train.py:242)
-// single workgroup, deterministic reduction
-// SOFT (sir_ce_loss_soft): the target of row b is q = (1 - eps) (lam e[ya] + (1 - lam) e[yb]) + eps / C instead of e[ya]
-// (mixup's two labels and label smoothing); loss_b = -sum_c q[c] log softmax[c] = log(den) - sum_c q[c] (l[c] - max) because
-// sum q = 1, dlogits = softmax - q.  SOFT = false is sir_ce_loss's kernel, instruction for instruction: `labels_b`, `lam`
-// and `eps` are not read.
+// cross-entropy (mean) forward + gradient wrt logits (ce_loss_rows.h), a single head: the segment is the whole row.
+// single workgroup, deterministic reduction.  SOFT: sir_ce_loss_soft's targets; SOFT = false is sir_ce_loss's kernel.
 // ------------------------------------------------------------------------------------------
 template <int CMAX, bool SOFT>
 static __global__ __launch_bounds__(256) void ce_loss_kernel(const float* __restrict__ logits, const long long* __restrict__ labels,
@@ -20,86 +16,10 @@ static __global__ __launch_bounds__(256) void ce_loss_kernel(const float* __rest
                                                        float eps) {
     __shared__ float red[256];
     __shared__ int cnt[256];
-    // nn.CrossEntropyLoss() has ignore_index = -100 by default: such a row contributes neither loss nor gradient and the mean is
-    // taken over the remaining rows (all rows ignored: 0 / 0 = NaN, as torch)
-    int nv = 0;
-    for (int b = threadIdx.x; b < B; b += 256) nv += labels[b] != -100ll ? 1 : 0;
-    cnt[threadIdx.x] = nv;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) cnt[threadIdx.x] += cnt[threadIdx.x + o];
-        __syncthreads();
-    }
-    const float nvalid = (float)cnt[0];
-    float acc = 0.0f;
-    for (int b = threadIdx.x; b < B; b += 256) {
-        // the row goes into registers with ALL its loads in flight (C <= CMAX, dispatched by the host): the per-class loops of
-        // the first version waited for one dependent load after the other, 15 us for 256 x 31 logits
-        const float* r = logits + (size_t)b * C;
-        // any OTHER label outside [0, C) (nn.CrossEntropyLoss raises on it; train.py:242): flag the handle's status word (bit 1 ->
-        // SIR_EINVAL at the next sir_check_status) and make the loss NaN instead of reading out of bounds
-        const long long yl = labels[b];
-        const bool ignored = yl == -100ll;
-        const bool bad = !ignored && (yl < 0 || yl >= (long long)C);
-        if (bad) __hip_atomic_fetch_or(status, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int y = (bad || ignored) ? 0 : (int)yl;
-        if constexpr (SOFT) {
-            // the second label of an ignored row is not read; a bad one is flagged like a bad first label
-            const long long yl2 = (labels_b && !ignored) ? labels_b[b] : yl;
-            const bool bad2 = !ignored && (yl2 < 0 || yl2 >= (long long)C);
-            if (bad2) __hip_atomic_fetch_or(status, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const int y2 = (bad2 || ignored) ? 0 : (int)yl2;
-            const float lm = (labels_b && lam) ? lam[b] : 1.0f;
-            const float wa = (1.0f - eps) * lm, wb = (1.0f - eps) * (1.0f - lm), u = eps / (float)C;
-            float v[CMAX];
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c) v[c] = c < C ? r[c] : 0.0f;
-            const float ra = r[y], rb = r[y2];
-            float mx = v[0];
-#pragma unroll
-            for (int c = 1; c < CMAX; ++c) if (c < C) mx = fmaxf(mx, v[c]);
-            float den = 0.0f, dsum = 0.0f;
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c) if (c < C) { const float d = v[c] - mx; dsum += d; v[c] = expf(d); den += v[c]; }
-            const float row = logf(den) - (wa * (ra - mx) + wb * (rb - mx) + u * dsum);
-            acc += (bad || bad2) ? __builtin_nanf("") : (ignored ? 0.0f : row);
-            if (dlogits) {
-                const float inv = 1.0f / den, gs = ignored ? 0.0f : grad_scale / nvalid;
-#pragma unroll
-                for (int c = 0; c < CMAX; ++c)
-                    if (c < C) {
-                        const float q = u + (c == y ? wa : 0.0f) + (c == y2 ? wb : 0.0f);
-                        dlogits[(size_t)b * C + c] = ignored ? 0.0f : (v[c] * inv - q) * gs;
-                    }
-            }
-            continue;
-        }
-        float v[CMAX];
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c) v[c] = c < C ? r[c] : 0.0f;
-        const float ry = r[y];
-        float mx = v[0];
-#pragma unroll
-        for (int c = 1; c < CMAX; ++c) if (c < C) mx = fmaxf(mx, v[c]);
-        float den = 0.0f;
-#pragma unroll
-        for (int c = 0; c < CMAX; ++c) if (c < C) { v[c] = expf(v[c] - mx); den += v[c]; }
-        const float lse = mx + logf(den);
-        acc += bad ? __builtin_nanf("") : (ignored ? 0.0f : lse - ry);
-        if (dlogits) {
-            const float inv = 1.0f / den, gs = ignored ? 0.0f : grad_scale / nvalid;
-#pragma unroll
-            for (int c = 0; c < CMAX; ++c)
-                if (c < C) dlogits[(size_t)b * C + c] = ignored ? 0.0f : (v[c] * inv - (c == y ? 1.0f : 0.0f)) * gs;
-        }
-    }
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) loss[0] = red[0] / nvalid;
+    const float nvalid = ce_valid_rows(labels, B, 1, 0, cnt);
+    const float acc = ce_rows<CMAX, SOFT>(logits, labels, labels_b, lam, eps, B, C, 0, 1, 0, C, nvalid, grad_scale, dlogits, status);
+    const float sum = ce_block_sum(acc, red);
+    if (threadIdx.x == 0) loss[0] = sum / nvalid;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -182,7 +182,7 @@ static __global__ __launch_bounds__(256) void ragged_widths_kernel(const int* __
     const bool ok = f >= 8 && f <= T;
     const int fw = ok ? f : 0;
     rag[b] = fw; rag[B + b] = fw >> 1; rag[2 * (size_t)B + b] = fw >> 2; rag[3 * (size_t)B + b] = fw >> 3;
-    if (!ok && status) __hip_atomic_fetch_or(status, 64u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (!ok && status) __hip_atomic_fetch_or(status, SIR_STATUS_RAGGED_LENGTH, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 static const sir_train_config kTrainAllLive = {{0, 0, 0}};      // what a NULL sir_train_config means: nothing frozen

@@ -17,7 +17,6 @@
 
 namespace {
 
-constexpr unsigned int kStatusBadSegment = 128u;      // sir_vad_gather: a table row outside the batch (SIR_EINVAL at the next check)
 
 // ---- 1. chunk energy -------------------------------------------------------------------------------------------------------
 // One wave owns one 32-bit flag word = 32 consecutive chunks of one recording.  The accumulator, the sub-wave read pattern and the
@@ -211,7 +210,7 @@ __global__ __launch_bounds__(kThreads) void vad_gather_kernel(const T* __restric
     const int len = bad ? 0 : (en - st < max_clip ? en - st : max_clip);
     if (head) {
         out_lengths[s] = len;
-        if (bad) __hip_atomic_fetch_or(status, kStatusBadSegment, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (bad) __hip_atomic_fetch_or(status, SIR_STATUS_VAD_ROW, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     const int col = (blockIdx.y * kThreads + threadIdx.x) * V;
     if (col >= max_clip) return;

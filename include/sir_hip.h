@@ -597,7 +597,8 @@ int    sir_stream_input_push(sir_handle* h, void* state, size_t state_bytes, con
  * The model's operand-range reports (see sir_model_infer) share the word, all SIR_EINVAL: bit 3 (value 8) a transformed conv2 / conv3
  * weight with |U| >= 32 or not finite; bit 11 (2048) a GRU weight matrix element beyond +-65504 or not finite; bit 12 (4096) a
  * training forward whose conv2 / conv3 block output reached 256 / 512 (the weight gradients of that workspace are invalid); bit 13
- * (8192) a conv1 weight or a BatchNorm weight / bias / running statistic that is not finite. */
+ * (8192) a conv1 weight or a BatchNorm weight / bias / running statistic that is not finite.  sir_decode_slots raises bit 14
+ * (16384) for a tuple table with a label outside its slot (SIR_EINVAL). */
 int sir_check_status(sir_handle* h, void* stream);
 
 /* ---- cross-batch pipelining (owned by the library) ------------------------------------------------
@@ -1030,6 +1031,33 @@ size_t sir_eval_slots_state_bytes(const int32_t* slot_sizes, int n_slots, int n_
 int sir_eval_accumulate_slots(sir_handle* h, const float* logits, const int64_t* labels, int batch, int num_classes,
                               const int32_t* slot_sizes, int n_slots, const float* inv_temperature, int n_bins, void* state,
                               size_t state_bytes, void* stream);
+
+/* sir_decode_slots: the k best label TUPLES of every row (DESIGN.md section 4 "Joint decoding"), 1 <= k <= 8, in one launch; one
+ * wavefront per row, nothing allocated, no floating-point atomics, results bit-reproducible.  slot_sizes (HOST) and
+ * inv_temperature (DEVICE f32[n_slots] or NULL) as above.  Every argument is checked before the launch: a refused call
+ * (SIR_EINVAL) writes nothing.
+ *   Per row and slot lp_g[c] = d_c - log1pf(rest_g), d and rest as sir_classify_slots forms them: the fp32 terms of
+ *   sir_eval_accumulate_slots' nll_sum, negated.  A tuple's score is s_t = lp_0[t_0] + lp_1[t_1] + ..., added in fp32 in slot
+ *   order (no fma, no reassociation).
+ *   Constrained (tuples != NULL, 1 <= n_tuples <= 4096): tuples is DEVICE uint8 [n_tuples][8], 8-byte aligned; byte g of a row
+ *   is the slot-local label of slot g, bytes g >= n_slots are 0.  Ranking: descending s_t, equal bits by ascending table row.
+ *     best_index  int32 [batch][k]           the table row
+ *     best_labels int32 [batch][k][n_slots]  that tuple, unpacked
+ *     best_logp   f32   [batch][k]           s_t
+ *     best_prob   f32   [batch][k]           exp(s_t - L), L = logsumexp_t s_t over the table = max + log of a sum taken in a
+ *                                            fixed lane (t = lane, lane + 64, ...) and butterfly order
+ *     valid_mass  f32   [batch], optional    exp(L): the probability the independent heads put on tuples that exist
+ *     tuple_logp  f32   [batch][n_tuples], optional   every s_t
+ *   Ranks >= n_tuples hold -1 / -1 / -inf / 0.  A table byte >= C_g (g < n_slots) raises the status word (bit 14, 16384:
+ *   SIR_EINVAL at the next sir_check_status); that tuple scores -inf, takes no part in L and is never chosen.
+ *   Unconstrained (tuples == NULL, n_tuples == 0, tuple_logp == NULL): the k best tuples of the whole product space by staged
+ *   merging (the k best partial tuples x the next slot's k best labels, exact).  Ties go to the candidate order: partial rank
+ *   major, slot rank minor, a slot's ranks being sir_classify's.  best_index is the tuple's mixed-radix number, slot 0 most
+ *   significant (< 8^8); best_prob = expf(s_t); valid_mass, if given, is 1; ranks beyond prod C_g are padded as above.
+ *   A row with a NaN or an infinity in ANY segment has -1 / NaN in every output; other rows are unaffected. */
+int sir_decode_slots(sir_handle* h, const float* logits, int batch, int num_classes, const int32_t* slot_sizes, int n_slots,
+                     const float* inv_temperature, const uint8_t* tuples, int n_tuples, int k, int32_t* best_index,
+                     int32_t* best_labels, float* best_logp, float* best_prob, float* valid_mass, float* tuple_logp, void* stream);
 
 /* ---- measurement -----------------------------------------------------------------------------
  * HIP-event timing of the kernels of the path, recorded on the stream they are launched on

@@ -201,6 +201,9 @@ SIGNATURES = {
     "sir_eval_slots_state_bytes": (C.c_size_t, [C.POINTER(C.c_int32), C.c_int, C.c_int]),
     "sir_eval_accumulate_slots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int,
                                             C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "sir_decode_slots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_void_p, C.c_void_p,
+                                   C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
     "sir_profile_kernel_count": (C.c_int, []),
     "sir_profile_kernel_name": (C.c_char_p, [C.c_int]),
     "sir_profile_enable": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),

@@ -391,6 +391,11 @@ static int check_status_impl(sir_handle* h, hipStream_t st, const char* who) {
                       "those rows were left out", who, v);
         return SIR_EINVAL;
     }
+    if (v & SIR_STATUS_DECODE_TUPLE) {
+        sir_set_error("%s: sir_decode_slots was given a tuple table with a label outside its slot's [0, C_g) (status %u): those "
+                      "tuples score -inf and were never chosen", who, v);
+        return SIR_EINVAL;
+    }
     if (v & SIR_STATUS_STREAM_ROW) {
         sir_set_error("%s: sir_stream_gather was given a table row whose stream or sample range is impossible (status %u): those rows "
                       "are zero with length 0", who, v);

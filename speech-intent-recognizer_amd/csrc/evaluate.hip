@@ -28,60 +28,20 @@
 //                         g + waves, ...; per-workgroup partials in the workspace) and a one-thread update launch.
 #include <cmath>
 #include "sir_internal.h"
+#include "row_softmax.h"  // row_softmax, wave_max, kClsWaves, classify_blocks
 #include "wave_fft.h"      // wave_sum
 
 namespace {
 
 constexpr int kEvalWaves = 16;                       // waves of the accumulate / fit workgroups
 constexpr int kEvalThreads = kEvalWaves * SIR_WAVE;
-constexpr int kClsWaves = 4;
 constexpr int kFitMaxBlocks = 256;
-constexpr int kMaxRows = 1 << 30;                    // rows per call: row indices and their grid strides stay far inside an int
 constexpr int kEvalMaxBlocks = 64;                   // workgroups of sir_eval_accumulate = partial rows of the state's scratch area
 constexpr int kFitHeader = 64;                       // workspace: {float beta, float nll at beta = 1} then the partials
 
 struct EvalSlotTable : SlotTable {
     long long base[kMaxSlots + 1];                   // 8-byte word offset of slot state g in the state; [n]: the joint block
 };
-
-__device__ __forceinline__ float wave_max(float x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o));
-    return x;
-}
-__device__ __forceinline__ bool is_nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
-
-// One row in one wave.  l: this lane's logit (lanes >= C hold 0 and take no part).  The row maximum is subtracted BEFORE the
-// scaling: d = (l - max l) * beta is one rounding of an (almost always exact) difference, so a small gap keeps its relative
-// precision whatever the magnitude of the logits and of beta; l * beta - max(l * beta) would carry the absolute rounding of
-// the two products.
-struct RowSoftmax {
-    float d, e;             // (l - max l) * beta <= 0, exp(d) (0 on lanes >= C)
-    float rest, den;        // sum of e without the first maximum's exact 1, and 1 + rest: log(den) = log1pf(rest) keeps the small
-                            // tail of a confident row that 1 + rest rounds away
-    int rank;               // of this lane's class (meaningless on lanes >= C and on non-finite rows)
-    bool finite;            // wave-uniform
-};
-
-__device__ __forceinline__ RowSoftmax row_softmax(float l, int lane, int C, float beta) {
-    RowSoftmax r;
-    const bool on = lane < C;
-    r.finite = __ballot(on && is_nonfinite(l)) == 0ull;
-    const float m = wave_max(on ? l : -INFINITY);
-    r.d = (l - m) * beta;
-    r.e = on ? expf(r.d) : 0.0f;
-    const unsigned long long at_max = __ballot(on && l == m);
-    const int first = at_max ? __ffsll((long long)at_max) - 1 : -1;                     // (no lane on a NaN row)
-    r.rest = wave_sum(lane == first ? 0.0f : r.e);
-    r.den = 1.0f + r.rest;
-    int rank = 0;
-    for (int j = 0; j < C; ++j) {
-        const float lj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(l), j));
-        rank += (lj > l || (lj == l && j < lane)) ? 1 : 0;
-    }
-    r.rank = rank;
-    return r;
-}
 
 // One segment of one row in its wave: the C logits at logits + at -> their probabilities at probs + at (probs NULL: not wanted)
 // and the segment's k top-k entries at topk_idx / topk_prob + out.  A finite segment multiplies `joint` by its rank-0
@@ -396,11 +356,6 @@ size_t slot_table(const char* who, const int32_t* slot_sizes, int n_slots, int n
 inline int eval_blocks(int batch) {
     const int b = (batch + kEvalWaves - 1) / kEvalWaves;
     return b > kEvalMaxBlocks ? kEvalMaxBlocks : b;
-}
-
-inline int classify_blocks(int batch) {
-    const int b = (batch + kClsWaves - 1) / kClsWaves;
-    return b > 4096 ? 4096 : b;
 }
 
 inline int fit_blocks(int n_rows) {

@@ -57,6 +57,7 @@ enum SirStatusBit : unsigned int {
     SIR_STATUS_GRU_WEIGHT    = 2048u,   // GRU weight not finite or outside +-65504 (f16_split.h)
     SIR_STATUS_ACT_RANGE     = 4096u,   // training activation beyond the backward's exact range (train_fwd_kernels.h)
     SIR_STATUS_BN_PARAM      = 8192u,   // conv1 weight / BatchNorm parameter not finite (model_kernels.h)
+    SIR_STATUS_DECODE_TUPLE  = 16384u,  // sir_decode_slots: a tuple-table byte outside its slot's [0, C_g) (slots_decode.hip)
 };
 
 // Slot heads (include/sir_hip.h "slot heads"): one logit row as up to kMaxSlots softmax segments.  Passed to kernels by

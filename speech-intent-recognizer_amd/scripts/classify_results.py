@@ -40,16 +40,26 @@ def slot_inv_temperature_of(temperature, n_slots):
     return [inv_temperature_of(t) for t in ts]
 
 
-def results_from_slot_logits(logits, spec, k=3, inv_temperature=None, min_confidence=None):
+def results_from_slot_logits(logits, spec, k=3, inv_temperature=None, min_confidence=None, table=None, decode="independent"):
     """``results_from_logits`` under a slot layout (``sir_amd.slots.SlotSpec``): ONE ``sir_classify_slots`` launch and ONE
     device-to-host copy for all rows of ``logits`` [B, spec.total] -> list of B dicts: the decoded slots (``{column: value}``)
     plus ``"predicted_label"`` (the reference's ``action_object`` join when the spec has both columns, else all values joined
     by ``_``), ``"confidence"`` (the joint confidence: the product of the slots' top probabilities), ``"slot_confidence"``
     (``{column: probability}``) and ``"top_predictions"`` (``{column: [{"label", "probability"}, ...]}``, ``k`` entries, at most
     the slot's width).  ``inv_temperature``: None, a number, one per slot, or ``slots.fit_slot_temperatures``' device tensor.
-    With ``min_confidence`` set every dict also carries ``"rejected"``: the JOINT confidence is below it (or NaN)."""
+    With ``min_confidence`` set every dict also carries ``"rejected"``: the JOINT confidence is below it (or NaN).
+
+    ``decode="joint"`` (ONE ``sir_decode_slots`` launch instead): the decoded slots are those of the best whole TUPLE,
+    ``"confidence"`` is its probability, ``"top_predictions"`` is a list of the ``k`` best tuples (``{"label", "slots":
+    {column: value}, "probability"}``), and ``min_confidence`` rejects on that confidence; there is no ``"slot_confidence"``.
+    With ``table`` (a ``slots.TupleTable``) only the tuples that exist are ranked, the probabilities are the softmax over the
+    table, and ``"valid_mass"`` -- the probability the independent heads put on the table, an out-of-set signal -- is added.
+    A table needs ``decode="joint"``."""
     from sir_amd import slots
     k = int(k)
+    check_decode(decode, table)
+    if decode == "joint":
+        return _joint_results(logits, spec, k, inv_temperature, min_confidence, table)
     idx, prob, joint = slots.classify(logits, spec, k=k, inv_temperature=inv_temperature)
     bsz, g = idx.shape[0], spec.n_slots
     packed = torch.cat([idx.to(torch.float32).view(bsz, g * k), prob.view(bsz, g * k), joint[:, None]], dim=1).cpu().numpy()
@@ -73,12 +83,61 @@ def results_from_slot_logits(logits, spec, k=3, inv_temperature=None, min_confid
     return results
 
 
-def results_of(logits, inv_label_map, slots=None, temperature=None, min_confidence=None):
+def check_decode(decode, table, slots=True):
+    """``decode`` is "independent" or "joint"; a tuple table belongs to joint decoding, and both to a slot layout: a caller's
+    mistake is raised before any device call."""
+    if decode not in ("independent", "joint"):
+        raise ValueError(f'decode must be "independent" or "joint", got {decode!r}')
+    if table is not None and decode != "joint":
+        raise ValueError('a tuple table constrains joint decoding: pass decode="joint" with it')
+    if not slots and (table is not None or decode == "joint"):
+        raise ValueError("tuples= and decode=\"joint\" need a slot layout (slots=)")
+
+
+def tuple_label(spec, decoded):
+    """The name of a decoded tuple: the reference's ``action_object`` join when the spec has both columns, else all values
+    joined by ``_``."""
+    label = spec.reference_label(decoded)
+    return label if label is not None else "_".join(decoded[c] for c in spec.columns)
+
+
+def _joint_results(logits, spec, k, inv_temperature, min_confidence, table):
+    from sir_amd import slots
+    spec = slots._as_spec(spec)
+    out = slots.decode(logits, spec, table=table, k=k, inv_temperature=inv_temperature, want_mass=table is not None)
+    labels, prob = out[1], out[3]
+    bsz, g = labels.shape[0], spec.n_slots
+    cols = [labels.to(torch.float32).view(bsz, k * g), prob] + ([out[4][:, None]] if table is not None else [])
+    packed = torch.cat(cols, dim=1).cpu().numpy()                                     # labels <= 63 are exact in float32
+    lab_h = packed[:, :k * g].astype(np.int64).reshape(bsz, k, g).tolist()
+    prob_h = packed[:, k * g: k * g + k].tolist()
+    mass_h = packed[:, k * g + k].tolist() if table is not None else None
+    results = []
+    for b, (row_l, row_p) in enumerate(zip(lab_h, prob_h)):
+        res = spec.decode(row_l[0])
+        top = []
+        for tup, p in zip(row_l, row_p):
+            if tup[0] < 0 and p == 0.0:                                                   # a rank that does not exist
+                continue
+            d = spec.decode(tup)
+            top.append({"label": tuple_label(spec, d), "slots": d, "probability": p})
+        res.update({"predicted_label": tuple_label(spec, res), "confidence": row_p[0], "top_predictions": top})
+        if mass_h is not None:
+            res["valid_mass"] = mass_h[b]
+        if min_confidence is not None:
+            res["rejected"] = not (row_p[0] >= min_confidence)
+        results.append(res)
+    return results
+
+
+def results_of(logits, inv_label_map, slots=None, temperature=None, min_confidence=None, tuples=None, decode="independent"):
     """The result dictionaries of the callers' device route: ``results_from_slot_logits`` when a slot layout is given,
-    ``results_from_logits`` otherwise; ``temperature`` is the callers' T (under slots: one, or one per slot)."""
+    ``results_from_logits`` otherwise; ``temperature`` is the callers' T (under slots: one, or one per slot); ``tuples`` /
+    ``decode`` are ``results_from_slot_logits``' ``table`` / ``decode``."""
+    check_decode(decode, tuples, slots is not None)
     if slots is not None:
         return results_from_slot_logits(logits, slots, inv_temperature=slot_inv_temperature_of(temperature, slots.n_slots),
-                                        min_confidence=min_confidence)
+                                        min_confidence=min_confidence, table=tuples, decode=decode)
     return results_from_logits(logits, inv_label_map, inv_temperature=inv_temperature_of(temperature), min_confidence=min_confidence)
 
 

@@ -42,20 +42,26 @@ def predict_loader(model, loader, device, device_metrics=None, collect_logits=Fa
     ``(None, None, state arrays)``: no prediction leaves the device and no per-batch synchronisation is added.
     ``collect_logits=True`` returns ``(logits [N, C] on the device, labels [N] on the device)`` instead (for
     ``metrics.fit_temperature``).  A ``device_metrics`` dict with the key ``spec`` (a ``slots.SlotSpec``) makes the
-    accumulators ``slots.SlotEvalAccumulator``s: labels are then [B, G] and the state holds the slots' states and the joint block."""
+    accumulators ``slots.SlotEvalAccumulator``s: labels are then [B, G] and the state holds the slots' states and the joint block;
+    with the further key ``tuples`` (a ``slots.TupleTable``) every batch is also decoded over that table
+    (``slots.ConstrainedEvalAccumulator``) and the state gains the key ``constrained``."""
     from sir_amd.pipeline import BatchPipeline
     model.eval()
     pipe = BatchPipeline(model, n_streams=2)          # consecutive batches alternate over two HIP streams
     preds, labels = [], []
     if device_metrics is not None or collect_logits:
-        accs = None
+        accs = cons = None
         if device_metrics is not None:
+            device_metrics = dict(device_metrics)
+            table = device_metrics.pop("tuples", None)
             if "spec" in device_metrics:
-                from sir_amd.slots import SlotEvalAccumulator as EvalAccumulator
+                from sir_amd.slots import ConstrainedEvalAccumulator, SlotEvalAccumulator as EvalAccumulator
+                if table is not None:
+                    cons = [ConstrainedEvalAccumulator(table=table, **device_metrics) for _ in range(pipe.n)]
             else:
                 from sir_amd.metrics import EvalAccumulator
             accs = [EvalAccumulator(**device_metrics) for _ in range(pipe.n)]
-        return _predict_loader_device(model, loader, device, pipe, accs, collect_logits)
+        return _predict_loader_device(model, loader, device, pipe, accs, collect_logits, cons)
     from sir_amd.scripts.train import HostStager
     stage = HostStager(device, slots=4)               # host batches: persistent pinned ring (see HostStager)
     for i, (mel, label) in enumerate(tqdm(loader, desc="Evaluating")):
@@ -72,7 +78,7 @@ def predict_loader(model, loader, device, device_metrics=None, collect_logits=Fa
     return torch.cat(preds).cpu().numpy(), torch.cat(labels).numpy()
 
 
-def _predict_loader_device(model, loader, device, pipe, accs, collect_logits):
+def _predict_loader_device(model, loader, device, pipe, accs, collect_logits, cons=None):
     from sir_amd import ops
     from sir_amd.scripts.train import HostStager
     stage = HostStager(device, slots=4)
@@ -85,6 +91,8 @@ def _predict_loader_device(model, loader, device, pipe, accs, collect_logits):
             lab = label.to(device=device, dtype=torch.int64, non_blocking=True)
             if accs is not None:
                 accs[slot].update(out[0], lab)
+            if cons is not None:
+                cons[slot].update(out[0], label)          # (the host labels: the table rows are looked up there)
             if collect_logits:
                 logits_all.append(out[0])
                 labels_all.append(lab)
@@ -101,6 +109,10 @@ def _predict_loader_device(model, loader, device, pipe, accs, collect_logits):
     state = accs[0].state_arrays()
     for a in accs[1:]:
         state = merge(state, a.state_arrays())
+    if cons is not None:
+        state["constrained"] = cons[0].state_arrays()
+        for c in cons[1:]:
+            state["constrained"] = slots.merge_constrained(state["constrained"], c.state_arrays())
     return None, None, state
 
 
@@ -136,7 +148,10 @@ def evaluate_slots(args, config):
     heads (sir_amd/slots.py).  Writes one ``classification_report_<column>.txt`` and ``calibration_<column>.json`` per slot
     and ``joint_metrics.json`` (exact-match accuracy, joint NLL / ECE / MCE, slots_correct, n_excluded) and returns the
     exact-match accuracy.  ``slots.map`` must name the ``slot_map.json`` of the training run: the test split's own values
-    would give another class order."""
+    would give another class order.
+    ``slots.tuples`` (the ``slot_tuples.json`` a ``slots.TupleTable`` saved) adds constrained decoding over that table:
+    ``constrained_metrics.json`` (exact match under constrained decoding and the mean ``valid_mass``; for a table of at most 64
+    rows also NLL / ECE / MCE of the posterior over the table) and, for such a table, ``classification_report_intents.txt``."""
     from sir_amd import metrics, slots
     opts = config["slots"]
     if not config.get("device_metrics", False):
@@ -144,6 +159,7 @@ def evaluate_slots(args, config):
     if not isinstance(opts, dict) or not opts.get("map"):
         raise ValueError("`slots.map` must name the slot_map.json of the training run")
     spec = slots.SlotSpec.load(opts["map"])
+    table = slots.TupleTable.load(opts["tuples"], spec) if opts.get("tuples") else None
     if config.get("num_labels", spec.total) != spec.total:
         raise ValueError(f"num_labels is {config['num_labels']}, the slot layout {dict(zip(spec.columns, spec.sizes))} needs {spec.total}")
     _native.require_hip()
@@ -166,7 +182,7 @@ def evaluate_slots(args, config):
     test_loader = DataLoader(test_dataset, batch_size=config.get("batch_size", 32), shuffle=False, collate_fn=collate_fn,
                              **loader_kwargs(config.get("num_workers", 4)))
     _, _, arrays = predict_loader(model, test_loader, device,
-                                  device_metrics={"spec": spec, "n_bins": int(config.get("calibration_bins", 15))})
+                                  device_metrics={"spec": spec, "n_bins": int(config.get("calibration_bins", 15)), "tuples": table})
     results_dir = os.path.join(config["save_path"], "evaluation_results")
     os.makedirs(results_dir, exist_ok=True)
     for column, vocab, a in zip(spec.columns, spec.vocab, arrays["slots"]):
@@ -181,6 +197,16 @@ def evaluate_slots(args, config):
     joint = slots.joint_report(arrays["joint"])
     with open(os.path.join(results_dir, "joint_metrics.json"), "w") as f:
         json.dump(slots.joint_json(joint), f, indent=2)
+    if table is not None:
+        cons, text = slots.constrained_json(arrays["constrained"], table)
+        with open(os.path.join(results_dir, "constrained_metrics.json"), "w") as f:
+            json.dump(cons, f, indent=2)
+        if text is not None:
+            with open(os.path.join(results_dir, "classification_report_intents.txt"), "w") as f:
+                f.write(f"Exact-match accuracy (constrained): {cons['exact_match_accuracy']:.4f}\n\n")
+                f.write(text)
+        logger.info(f"Constrained to {len(table)} tuples: exact-match accuracy {cons['exact_match_accuracy']:.4f} over {cons['n']} clips, "
+                    f"mean valid mass {cons['mean_valid_mass']:.4f}")
     logger.info(f"Exact-match accuracy {joint['exact_match_accuracy']:.4f} over {joint['n']} clips ({joint['n_excluded']} excluded), "
                 f"joint NLL {joint['nll']:.4f}, ECE {joint['ece']:.4f}")
     logger.info(f"Evaluation results saved to {results_dir}")

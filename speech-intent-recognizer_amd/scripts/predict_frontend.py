@@ -33,7 +33,7 @@ def get_extractor(frontend=None):
 
 
 def predict_many(model, audio_paths, label_map, device, pad_to=test_model.MAX_LENGTH, frontend=None, on_device=False,
-                 temperature=None, min_confidence=None, slots=None):
+                 temperature=None, min_confidence=None, slots=None, tuples=None, decode="independent"):
     """One feature pass at ``frontend`` and one forward for all files -> list of result dictionaries / ``None``.
     ``pad_to=None`` needs a single file (un-padded features, ``T >= 8``).  ``on_device``, ``temperature``, ``min_confidence``:
     the results come from ``classify_results.results_from_logits`` (one ``sir_classify`` launch and one copy for the batch instead of
@@ -41,9 +41,11 @@ def predict_many(model, audio_paths, label_map, device, pad_to=test_model.MAX_LE
     ``"rejected"``) belong to that route: without ``on_device=True`` they raise ``ValueError``.  ``slots`` (a ``sir_amd.slots.SlotSpec``; implies the
     device route): the model's logit row is read as slot heads and every result is ``classify_results.results_from_slot_logits``'
     dictionary -- decoded slots, joint ``"confidence"``, per-slot tables; ``temperature`` may then hold one T per slot and
-    ``min_confidence`` rejects on the joint value."""
+    ``min_confidence`` rejects on the joint value.  ``decode="joint"`` (with ``tuples``, a ``slots.TupleTable``: only the tuples
+    that exist) ranks whole label tuples instead, as ``results_from_slot_logits`` describes."""
     on_device = on_device or slots is not None
     classify_results.check_route(on_device, temperature, min_confidence)       # a caller's mistake: raised, not logged
+    classify_results.check_decode(decode, tuples, slots is not None)
     if slots is not None:
         classify_results.slot_inv_temperature_of(temperature, slots.n_slots)   # (likewise, before any device call)
     audio_paths = list(audio_paths)
@@ -63,7 +65,7 @@ def predict_many(model, audio_paths, label_map, device, pad_to=test_model.MAX_LE
             output = model(batch)
         inv = {v: k for k, v in label_map.items()}
         if on_device:
-            for res, i in zip(classify_results.results_of(output, inv, slots, temperature, min_confidence), keep):
+            for res, i in zip(classify_results.results_of(output, inv, slots, temperature, min_confidence, tuples, decode), keep):
                 results[i] = res
         else:
             for row, i in enumerate(keep):

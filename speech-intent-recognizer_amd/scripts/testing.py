@@ -160,7 +160,7 @@ class IntentRecognizer:
         return logits
 
     def recognize_recordings(self, waves_or_paths, pad_to=TRAINED_LENGTH, on_device=False, temperature=None, min_confidence=None,
-                             slots=None):
+                             slots=None, tuples=None, decode="independent"):
         """waves_or_paths: recordings as 1-D float32 / int16 arrays or tensors at the segmenter's sample rate, or paths of WAVE
         files (decoded, mixed to mono and resampled on the GPU).  -> per recording, the list of its utterances in time order:
         ``{"start": seconds, "end": seconds, "predicted_label", "confidence", "top_predictions"}``; ``None`` for the recordings of
@@ -172,10 +172,13 @@ class IntentRecognizer:
         ``slots`` (a ``sir_amd.slots.SlotSpec``; implies the device route): the logit row is read as slot heads and every
         utterance carries ``classify_results.results_from_slot_logits``' dictionary instead (decoded slots, joint
         ``"confidence"``, per-slot tables); ``temperature`` may hold one T per slot, ``min_confidence`` rejects on the joint value.
-        (``StreamSession.feed`` keeps the single-head results: DESIGN.md section 4 "Slot heads".)"""
+        ``decode="joint"`` (with ``tuples``, a ``slots.TupleTable``: only the tuples that exist) ranks whole label tuples
+        instead: the slots of the best tuple, its probability as ``"confidence"``, the k best tuples, ``"valid_mass"`` under a
+        table (``classify_results.results_from_slot_logits``).  ``StreamSession.feed`` takes the same arguments."""
         from sir_amd.scripts import classify_results
         on_device = on_device or slots is not None
         classify_results.check_route(on_device, temperature, min_confidence)
+        classify_results.check_decode(decode, tuples, slots is not None)
         if slots is not None:
             classify_results.slot_inv_temperature_of(temperature, slots.n_slots)
         items = list(waves_or_paths)
@@ -189,7 +192,7 @@ class IntentRecognizer:
                 found = [[] for _ in group]
                 batch_res = None
                 if on_device and table.shape[0] > 0:
-                    batch_res = classify_results.results_of(logits, self.inv_label_map, slots, temperature, min_confidence)
+                    batch_res = classify_results.results_of(logits, self.inv_label_map, slots, temperature, min_confidence, tuples, decode)
                 for row, (r, a, b) in enumerate(table.tolist()):
                     res = batch_res[row] if batch_res is not None else test_model._result(logits[row:row + 1], self.inv_label_map)
                     found[r].append({"start": a / sr, "end": b / sr, **res})
@@ -200,27 +203,33 @@ class IntentRecognizer:
 
     # ---- live streams ----------------------------------------------------------------------------------------------------
     def open_streams(self, n_streams, max_push=1024, max_utterance=10.0, dtype=None, pad_to=TRAINED_LENGTH, on_device=False,
-                     temperature=None, min_confidence=None, sample_rate=None, encoding=None):
+                     temperature=None, min_confidence=None, sample_rate=None, encoding=None, slots=None, tuples=None,
+                     decode="independent"):
         """What ``MicrophoneListener.listen`` + ``predict`` do for one microphone (testing.py:49-143), for ``n_streams`` sources
         that deliver at most ``max_push`` samples of ``dtype`` (float32 unless given) per ``feed``: -> a ``StreamSession``.  The
         detector takes the listener values of this recogniser's ``segmenter``; an utterance longer than ``max_utterance`` seconds
-        is ended there.  ``pad_to`` / ``on_device`` / ``temperature`` / ``min_confidence`` as in ``recognize_recordings``.
+        is ended there.  ``pad_to`` / ``on_device`` / ``temperature`` / ``min_confidence`` / ``slots`` / ``tuples`` / ``decode`` as
+        in ``recognize_recordings``: the session builds its dictionaries through the same ``classify_results.results_of``.
         ``sample_rate`` (Hz, default the segmenter's) / ``encoding`` ("pcm", "ulaw", "alaw"; default "pcm"): the callers' own rate
         and codec -- e.g. 8000 and "ulaw" for G.711 telephony, fed as bytes.  The streams are then decoded and rate-converted on
         the GPU with carried filter state (``sir_amd.streaming.StreamInput``), ``max_push`` counts the callers' samples, and
         ``start`` / ``end`` stay seconds."""
         return StreamSession(self, n_streams, max_push, max_utterance, dtype, pad_to, on_device, temperature, min_confidence,
-                             sample_rate, encoding)
+                             sample_rate, encoding, slots, tuples, decode)
 
 
 class StreamSession:
     """Utterances of many live streams, scored as they end (``IntentRecognizer.open_streams``)."""
 
     def __init__(self, recognizer, n_streams, max_push, max_utterance, dtype, pad_to, on_device, temperature, min_confidence,
-                 sample_rate=None, encoding=None):
+                 sample_rate=None, encoding=None, slots=None, tuples=None, decode="independent"):
         from sir_amd.scripts import classify_results
         from sir_amd.streaming import StreamSegmenter
+        on_device = on_device or slots is not None
         classify_results.check_route(on_device, temperature, min_confidence)
+        classify_results.check_decode(decode, tuples, slots is not None)
+        if slots is not None:
+            classify_results.slot_inv_temperature_of(temperature, slots.n_slots)
         seg = recognizer.segmenter
         self.recognizer = recognizer
         if dtype is None and encoding in (None, "pcm"):
@@ -231,6 +240,7 @@ class StreamSession:
                                          encoding=encoding)
         self.pad_to = recognizer.mel_spec_length if pad_to == TRAINED_LENGTH else pad_to
         self.on_device, self.temperature, self.min_confidence = on_device, temperature, min_confidence
+        self.slots, self.tuples, self.decode = slots, tuples, decode
         self.last_logits = None
 
     def feed(self, chunks, lengths=None, close=()):
@@ -270,9 +280,8 @@ class StreamSession:
         logits = self.last_logits = reco._score_clips(clips, clip_lens, self.pad_to, self.on_device)
         batch_res = None
         if self.on_device:
-            batch_res = classify_results.results_from_logits(logits, reco.inv_label_map,
-                                                             inv_temperature=classify_results.inv_temperature_of(self.temperature),
-                                                             min_confidence=self.min_confidence)
+            batch_res = classify_results.results_of(logits, reco.inv_label_map, self.slots, self.temperature, self.min_confidence,
+                                                    self.tuples, self.decode)
         sr = float(seg.sample_rate)
         found = []
         for row, (s, a, b, flag) in enumerate(host_table.tolist()):

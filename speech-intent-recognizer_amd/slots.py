@@ -337,6 +337,251 @@ def classify(logits, spec, k=1, inv_temperature=None, want_probs=False):
     return (idx, prob, joint, probs) if want_probs else (idx, prob, joint)
 
 
+# ---- joint decoding -----------------------------------------------------------------------------------------------------------
+MAX_TUPLES = 4096
+TUPLE_BYTES = 8
+
+
+def pack_tuples(rows, n_slots):
+    """Label tuples [N, G] -> the table ``sir_decode_slots`` reads: uint8 numpy [N, 8], byte g the slot-local label of slot g,
+    bytes g >= n_slots zero."""
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1, n_slots)
+    packed = np.zeros((rows.shape[0], TUPLE_BYTES), dtype=np.uint8)
+    packed[:, :n_slots] = rows
+    return packed
+
+
+class TupleTable:
+    """The label tuples that exist: what constrained decoding (``decode(..., table=)``) ranks.  Row t of the table is the tuple
+    ``rows[t]`` of slot-local labels; a tie between equal scores goes to the lower row.  Validated on the host: 1 .. 4096 rows,
+    every label inside its slot, no tuple twice."""
+
+    def __init__(self, spec, rows):
+        self.spec = _as_spec(spec)
+        g = self.spec.n_slots
+        try:
+            rows = [tuple(r) for r in rows]
+        except TypeError:
+            raise ValueError("a tuple table needs a sequence of label tuples") from None
+        if not 1 <= len(rows) <= MAX_TUPLES:
+            raise ValueError(f"a tuple table has 1..{MAX_TUPLES} rows, got {len(rows)}")
+        index = {}
+        for t, r in enumerate(rows):
+            if len(r) != g:
+                raise ValueError(f"row {t} has {len(r)} labels for {g} slots")
+            for v, c in zip(r, self.spec.sizes):
+                if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v < c:
+                    raise ValueError(f"row {t}: label {v!r} outside its slot's [0, {c})")
+            r = tuple(int(v) for v in r)
+            if r in index:
+                raise ValueError(f"rows {index[r]} and {t} hold the same tuple {r}")
+            index[r] = t
+        self.rows = tuple(index)                      # (insertion order = row order)
+        self.index = index
+        self.packed = pack_tuples(self.rows, g)
+        self._device = {}
+
+    def __len__(self):
+        return len(self.rows)
+
+    def __eq__(self, other):
+        return isinstance(other, TupleTable) and self.spec == other.spec and self.rows == other.rows
+
+    @classmethod
+    def full(cls, spec):
+        """Every tuple of the product space, in lexicographic order (slot 0 most significant): row t is the tuple whose
+        mixed-radix number is t, unconstrained decoding's ``best_index``.  Refused above 4096 tuples."""
+        import itertools
+        spec = _as_spec(spec)
+        n = int(np.prod([int(c) for c in spec.sizes], dtype=object))
+        if n > MAX_TUPLES:
+            raise ValueError(f"the layout {spec.sizes} has {n} tuples, a table holds at most {MAX_TUPLES}")
+        return cls(spec, itertools.product(*[range(c) for c in spec.sizes]))
+
+    @classmethod
+    def from_dataframe(cls, spec, dataframe):
+        """The distinct tuples the data contains, sorted.  A row with a value outside the spec's vocabularies names no tuple
+        and is left out."""
+        spec = _as_spec(spec)
+        labels = spec.encode(dataframe)
+        known = labels[(labels != IGNORE).all(axis=1)]
+        return cls(spec, sorted({tuple(int(v) for v in r) for r in known}))
+
+    @classmethod
+    def from_csv(cls, spec, csv):
+        import pandas as pd
+        return cls.from_dataframe(spec, pd.read_csv(csv))
+
+    def to_dict(self):
+        return {"columns": list(self.spec.columns), "vocab": {c: list(vs) for c, vs in zip(self.spec.columns, self.spec.vocab)},
+                "tuples": [list(r) for r in self.rows]}
+
+    def save(self, path):
+        with open(path, "w") as f:
+            json.dump(self.to_dict(), f, indent=2)
+
+    @classmethod
+    def load(cls, path, spec=None):
+        """The table of ``save``; with ``spec`` given, the file's layout must be that spec's."""
+        with open(path, "r") as f:
+            d = json.load(f)
+        if not isinstance(d, dict) or not {"columns", "vocab", "tuples"} <= set(d):
+            raise ValueError(f"{path}: not a tuple table (needs 'columns', 'vocab' and 'tuples')")
+        own = SlotSpec(d["columns"], d["vocab"])
+        if spec is not None and own != _as_spec(spec):
+            raise ValueError(f"{path}: the table's slot layout is not the given one")
+        return cls(own if spec is None else spec, d["tuples"])
+
+    def encode(self, labels):
+        """Slot labels [N, G] (numpy or tensor) -> int64 numpy [N]: the table row of each label tuple, -100 for a tuple that is not
+        in the table or has a -100 slot."""
+        if hasattr(labels, "detach"):
+            labels = labels.detach().cpu().numpy()
+        labels = np.asarray(labels, dtype=np.int64)
+        if labels.ndim != 2 or labels.shape[1] != self.spec.n_slots:
+            raise ValueError(f"labels must be [N, {self.spec.n_slots}] (one column per slot), got {labels.shape}")
+        return np.asarray([self.index.get(tuple(r), IGNORE) for r in labels.tolist()], dtype=np.int64).reshape(-1)
+
+    def names(self):
+        """One name per row: the reference's ``action_object`` join where that is unique over the table, else all values joined
+        by ``_``."""
+        decoded = [self.spec.decode(r) for r in self.rows]
+        short = [self.spec.reference_label(d) for d in decoded]
+        if None not in short and len(set(short)) == len(short):
+            return short
+        return ["_".join(d[c] for c in self.spec.columns) for d in decoded]
+
+    def device_tensor(self, device):
+        """The packed table on ``device`` (uint8 [N, 8], uploaded once per device)."""
+        import torch
+        key = str(device)
+        if key not in self._device:
+            self._device[key] = torch.from_numpy(self.packed).to(device)
+        return self._device[key]
+
+
+def decode(logits, spec, table=None, k=1, inv_temperature=None, want_mass=False, want_scores=False):
+    """The k best label tuples of every row in one ``sir_decode_slots`` launch -> ``(best_index int32 [B, k], best_labels int32
+    [B, k, G], best_logp float32 [B, k], best_prob float32 [B, k])``, then ``valid_mass`` [B] with ``want_mass`` and
+    ``tuple_logp`` [B, len(table)] with ``want_scores`` (which needs a table).
+
+    With ``table`` (a ``TupleTable``) only its tuples are ranked, ``best_index`` is the table row and ``best_prob`` the
+    softmax over the table of the tuples' summed log-probabilities; ``valid_mass`` is the probability the independent heads
+    put on the table.  Without one the whole product space is ranked, ``best_index`` is the tuple's mixed-radix number and
+    ``best_prob`` the product of the slots' probabilities.  Ranks that do not exist hold -1 / -1 / -inf / 0; a row with a NaN
+    or an infinity in any segment comes back as -1 / NaN."""
+    import torch
+    from .featurizer import get_featurizer
+    spec = _as_spec(spec)
+    _check_logits(logits, spec)
+    k = _check_k(k)
+    beta = check_inv_temperature(inv_temperature, spec.n_slots)
+    if table is not None:
+        if not isinstance(table, TupleTable):
+            raise ValueError("table must be a slots.TupleTable")
+        if table.spec.sizes != spec.sizes:
+            raise ValueError(f"the table was built for the layout {table.spec.sizes}, the logits are read as {spec.sizes}")
+    elif want_scores:
+        raise ValueError("want_scores returns one score per table row: it needs a table")
+    _native.require_hip(logits)
+    lib = _native.lib()
+    logits = logits.contiguous()
+    beta = _beta_tensor(beta, logits.device)
+    bsz, g, dev = logits.shape[0], spec.n_slots, logits.device
+    tuples = table.device_tensor(dev) if table is not None else None
+    n = len(table) if table is not None else 0
+    index = torch.empty((bsz, k), dtype=torch.int32, device=dev)
+    labels = torch.empty((bsz, k, g), dtype=torch.int32, device=dev)
+    logp = torch.empty((bsz, k), dtype=torch.float32, device=dev)
+    prob = torch.empty((bsz, k), dtype=torch.float32, device=dev)
+    mass = torch.empty((bsz,), dtype=torch.float32, device=dev) if want_mass else None
+    scores = torch.empty((bsz, n), dtype=torch.float32, device=dev) if want_scores else None
+    rc = lib.sir_decode_slots(get_featurizer().handle, logits.data_ptr(), bsz, spec.total, _sizes_array(spec), g,
+                              beta.data_ptr() if beta is not None else None, tuples.data_ptr() if tuples is not None else None, n, k,
+                              index.data_ptr(), labels.data_ptr(), logp.data_ptr(), prob.data_ptr(),
+                              mass.data_ptr() if mass is not None else None, scores.data_ptr() if scores is not None else None,
+                              _native.current_stream_ptr())
+    _native.check(rc, "sir_decode_slots")
+    out = (index, labels, logp, prob)
+    if want_mass:
+        out += (mass,)
+    if want_scores:
+        out += (scores,)
+    return out
+
+
+class ConstrainedEvalAccumulator:
+    """Evaluation under constrained decoding, kept on the device: per batch one ``sir_decode_slots`` launch over ``table``
+    (k = 1, ``valid_mass``, and ``tuple_logp`` for a table of at most 64 rows).  Exact match is counted against
+    ``table.encode(labels)``; for a table of at most 64 rows ``tuple_logp`` and those encoded labels also go to an unchanged
+    ``metrics.EvalAccumulator`` -- the softmax of the tuple scores IS the posterior over the table -- which gives the
+    classification report over the intents and NLL / ECE / MCE of that posterior.  A clip whose tuple is not in the table (or has a
+    -100 slot) is left out of the counts, as a -100 label is elsewhere."""
+
+    def __init__(self, spec, table, n_bins=15, inv_temperature=None):
+        self.spec = _as_spec(spec)
+        if not isinstance(table, TupleTable) or table.spec.sizes != self.spec.sizes:
+            raise ValueError("table must be a slots.TupleTable of the same slot layout")
+        self.table = table
+        self.n_bins = int(n_bins)
+        self._inv_temperature = check_inv_temperature(inv_temperature, self.spec.n_slots)
+        self.posterior = metrics.EvalAccumulator(len(table), n_bins) if len(table) <= MAX_CLASSES else None
+        self._counts = None                  # device int64 {n, exact_match, rows with a finite mass}
+        self._mass = None                    # device float64 {sum of valid_mass}
+
+    def update(self, logits, labels):
+        """Add one batch: logits float32 [B, total] on the device; labels int64 [B, G], on the HOST (they are encoded there, before
+        anything is queued) or on the device (copied back first).  Nothing else comes back."""
+        import torch
+        y = torch.from_numpy(self.table.encode(labels)).to(logits.device, non_blocking=True)
+        if self._counts is None:
+            self._counts = torch.zeros(3, dtype=torch.int64, device=logits.device)
+            self._mass = torch.zeros(1, dtype=torch.float64, device=logits.device)
+        out = decode(logits, self.spec, table=self.table, k=1, inv_temperature=self._inv_temperature, want_mass=True,
+                     want_scores=self.posterior is not None)
+        best, mass = out[0][:, 0].to(torch.int64), out[4]
+        counted = (y != IGNORE) & (best >= 0)
+        finite = torch.isfinite(mass)
+        self._counts += torch.stack([counted.sum(), (counted & (best == y)).sum(), finite.sum()])
+        self._mass += torch.where(finite, mass, torch.zeros_like(mass)).double().sum()
+        if self.posterior is not None:
+            self.posterior.update(out[5], y)
+        return self
+
+    def state_arrays(self):
+        counts = np.zeros(3, dtype=np.int64) if self._counts is None else self._counts.cpu().numpy()
+        mass = 0.0 if self._mass is None else float(self._mass.cpu().numpy()[0])
+        out = {"n": int(counts[0]), "exact_match": int(counts[1]), "mass_rows": int(counts[2]), "mass_sum": mass}
+        if self.posterior is not None:
+            out["posterior"] = self.posterior.state_arrays()
+        return out
+
+
+def merge_constrained(a, b):
+    out = {k: a[k] + b[k] for k in ("n", "exact_match", "mass_rows", "mass_sum")}
+    if "posterior" in a:
+        out["posterior"] = metrics.merge(a["posterior"], b["posterior"])
+    return out
+
+
+def constrained_json(arrays, table):
+    """``constrained_metrics.json`` of scripts/evaluate.py from ``ConstrainedEvalAccumulator.state_arrays()`` -> (dict, the
+    classification report's text or None)."""
+    nan = float("nan")
+    n = arrays["n"]
+    out = {"n": n, "n_tuples": len(table), "exact_match": arrays["exact_match"],
+           "exact_match_accuracy": arrays["exact_match"] / n if n else nan,
+           "mean_valid_mass": arrays["mass_sum"] / arrays["mass_rows"] if arrays["mass_rows"] else nan}
+    text = None
+    if "posterior" in arrays:
+        report = metrics.report_from_state(arrays["posterior"], table.names())
+        calib = metrics.calibration_json(report)
+        out.update({k: calib[k] for k in ("nll", "ece", "mce") if k in calib})
+        out["calibration"] = calib
+        text = metrics.format_report(report["classification"])
+    return out, text
+
+
 # ---- evaluation state ---------------------------------------------------------------------------------------------------------
 def joint_field_words(n_bins):
     """8-byte words of the joint block's fields: n, exact_match, slots_correct [9], nll_sum, three bin tables, n_excluded."""

@@ -152,8 +152,12 @@ int sir_wave_perturb(sir_handle* h, const void* wave, int wave_dtype, int64_t wa
  *   rir_bank / noise_bank: [n][stride] f32 with device int32 lengths[n]; rir_index / noise_index: device int32[batch], NULL
  *   = that effect off for every row (its bank arguments are then ignored); noise_offset / snr_db: device [batch], read
  *   only where noise_index >= 0.
- *   An index outside [-1, n), a bank length outside its range or a NaN / infinite snr_db zeroes that row and is
- *   reported by sir_check_status (SIR_EINVAL); the other rows are unaffected.  max_rir_len > 8192: SIR_EINVAL.
+ *   An index outside [-1, n), a bank length outside its range, a NaN / infinite snr_db or a gain that is not a finite
+ *   float32 (a finite snr_db far below the usable range: g passes FLT_MAX near -770 dB at ordinary levels) zeroes that
+ *   row, reports gain 0 and is reported by sir_check_status (SIR_EINVAL); the other rows are unaffected.  A gain that
+ *   underflows to 0 (snr_db far above the range) is no error: out = y bit for bit, gain 0.  A finite g whose product
+ *   g v overflows float32 is plain float32 arithmetic and is not guarded.  lengths == NULL means max_len for every row;
+ *   batch <= 65535.  max_rir_len > 8192: SIR_EINVAL.
  *   workspace: sir_reverb_workspace_bytes(batch, max_len, max_rir_len) bytes, 256-byte aligned (SIR_ENOMEM otherwise);
  *   its first `batch` floats receive the gain g applied to each row (0 where no noise was added). */
 size_t sir_reverb_workspace_bytes(const sir_handle* h, int batch, int max_len, int max_rir_len);

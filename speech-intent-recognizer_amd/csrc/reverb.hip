@@ -6,7 +6,8 @@
 //           the tail beyond L is dropped, the RIR is used as given; r = -1: y = x, a copy.
 //   noise   out[n] = y[n] + g v[(o + n) mod M], g = sqrt(P_y / (P_v 10^(snr_db / 10))), P_y = mean y^2 over [0, L), P_v = mean
 //           square of the L noise samples actually used; g = 0 when P_y or P_v is 0; v = -1: out = y, a copy.
-//   out[b] is zero on [L, max_len).
+//   out[b] is zero on [L, max_len).  A bad row (an index or a bank length out of range, a non-finite snr_db, a g that is no
+//   finite float32) is zero on [0, max_len) with gain 0 and raises SIR_STATUS_REVERB.
 //
 // reverb_mix_kernel: ONE 256-thread workgroup (4 waves) per row.  Direct form costs L x K multiply-adds (4e8 per 3 s clip at K =
 // 8192), so the convolution is uniformly partitioned overlap-save on the 1024-point real FFT: the RIR is cut into P =
@@ -125,7 +126,7 @@ __global__ __launch_bounds__(kThreads) void reverb_mix_kernel(const WT* __restri
                                                               int max_len, ReverbArgs a, float* __restrict__ out, long long out_stride,
                                                               float* __restrict__ gain, unsigned int* __restrict__ status) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    double* red = reinterpret_cast<double*>(smem);                     // [2][kWaves] + the gain
+    double* red = reinterpret_cast<double*>(smem);                     // [2][kWaves] + the gain + its bad-row flag
     cf32* slabs = reinterpret_cast<cf32*>(red + 2 * kWaves + 2);       // [kWaves][kSlab]
     cf32* Hs = slabs + kWaves * kSlab;                                 // [parts][512]
     cf32* ring = Hs + a.parts * 512;                                   // [parts + kRingExtra][512]
@@ -258,11 +259,23 @@ __global__ __launch_bounds__(kThreads) void reverb_mix_kernel(const WT* __restri
         for (int i = 0; i < kWaves; ++i) { Sy += red[i]; Sv += red[kWaves + i]; }
         double g = 0.0;
         if (Sy > 0.0 && Sv > 0.0) g = sqrt(Sy / (Sv * pow(10.0, (double)snr / 10.0)));   // the 1 / L of both means cancels
-        const float gf = (float)g;
+        float gf = (float)g;
+        // an extreme finite snr_db (10^(snr / 10) underflows to 0 below about -3240 dB, g passes FLT_MAX below about -770 dB
+        // at ordinary levels) gives a gain that is no finite float32: a bad row, as a NaN snr_db is
+        const bool inf_gain = !(fabsf(gf) <= 3.4028234e38f);
+        if (inf_gain) {
+            __hip_atomic_fetch_or(status, SIR_STATUS_REVERB, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            gf = 0.0f;
+        }
         gain[b] = gf;
         red[2 * kWaves] = (double)gf;
+        red[2 * kWaves + 1] = inf_gain ? 1.0 : 0.0;
     }
     __syncthreads();
+    if (red[2 * kWaves + 1] != 0.0) {                                    // block-uniform
+        for (int i = tid; i < L; i += kThreads) y[i] = 0.0f;
+        return;
+    }
     const float g = (float)red[2 * kWaves];
     for (int i = tid; i < L; i += kThreads) y[i] = fmaf(g, vn[(o0 + (unsigned)i) % Mu], y[i]);
 }

@@ -3,13 +3,14 @@
 Shapes cross every boundary of a 512-sample partition and a 1024-point block.  The reverb bound is the issue's condition, max
 |out - oracle| <= 1e-5 |x|_inf |h|_1 per row (about 170 float32 unit roundoffs of the largest value the output can take); every
 case prints the largest ratio it saw (pytest -s) ahead of its assertion."""
-import ctypes as C
+import functools
 
 import numpy as np
 import pytest
 import torch
 
 import reverb_ref as ref
+from reverb_call import NAN, bank as _bank, call, i32 as _i32
 from sir_amd import _native, ops, synth
 from sir_amd.sound_bank import SoundBank
 
@@ -19,7 +20,6 @@ LENGTHS = [0, 1, 511, 512, 513, 1023, 1025, 1537, 5000, 5000, 4097]
 MAX_LEN, STRIDE = 5000, 5008
 RIR_K = [1, 2, 511, 512, 513, 1025, 3000, 8192]
 RIR_INDEX = [3, 0, 1, 2, 3, 4, 5, 6, 7, -1, 7]                   # -1 and repeated RIRs (3 and 7)
-NAN = float("nan")
 
 
 @pytest.fixture(scope="module")
@@ -43,46 +43,7 @@ def data():
     return {"x": x, "x16": synth.to_int16(x), "rirs": rirs, "noises": noises}
 
 
-def _bank(rows, fill=0.0, extra=8):
-    """[n][stride] float32 on the GPU with `fill` behind each row's length, and the lengths"""
-    n = max(len(r) for r in rows)
-    t = torch.full((len(rows), (n + 7) // 8 * 8 + extra), fill, dtype=torch.float32)
-    for i, r in enumerate(rows):
-        t[i, :len(r)] = torch.as_tensor(r)
-    return t.cuda(), torch.tensor([len(r) for r in rows], dtype=torch.int32).cuda()
-
-
-def _i32(v):
-    return None if v is None else torch.tensor(v, dtype=torch.int32).cuda()
-
-
-def _call(fz, wave, lengths, rir=None, rir_index=None, noise=None, noise_index=None, noise_offset=None, snr_db=None, out=None,
-          max_len=MAX_LEN, max_rir_len=None, ws_bytes=None, rir_lengths=None, n_rir=None):
-    """The C entry point with raw tensors (the tests control strides, fills and bad arguments).  -> (rc, out, gain)"""
-    lib = _native.lib()
-    bsz = wave.shape[0]
-    dt = _native.WAVE_I16 if wave.dtype == torch.int16 else _native.WAVE_F32
-    if out is None:
-        out = torch.full((bsz, STRIDE), NAN, dtype=torch.float32, device="cuda")
-    ptr = lambda t: None if t is None else t.data_ptr()
-    rdata, rlen = rir if rir is not None else (None, None)
-    rlen = rir_lengths if rir_lengths is not None else rlen
-    ndata, nlen = noise if noise is not None else (None, None)
-    mrl = max_rir_len if max_rir_len is not None else (int(rlen.max()) if rlen is not None else 0)
-    need = lib.sir_reverb_workspace_bytes(fz.handle, bsz, max_len, min(mrl, 8192))
-    assert need >= 4 * bsz
-    ws = torch.zeros(need if ws_bytes is None else max(ws_bytes, 256), dtype=torch.uint8, device="cuda")
-    snr = None if snr_db is None else torch.tensor(snr_db, dtype=torch.float32).cuda()
-    keep = [_i32(lengths), _i32(rir_index), _i32(noise_index), _i32(noise_offset), snr]
-    rc = lib.sir_wave_reverb_mix(fz.handle, wave.data_ptr(), dt, wave.stride(0), ptr(keep[0]), bsz, max_len,
-                                 ptr(rdata), rdata.stride(0) if rdata is not None else 0, ptr(rlen),
-                                 (rdata.shape[0] if rdata is not None else 0) if n_rir is None else n_rir, mrl, ptr(keep[1]),
-                                 ptr(ndata), ndata.stride(0) if ndata is not None else 0, ptr(nlen),
-                                 ndata.shape[0] if ndata is not None else 0, ptr(keep[2]), ptr(keep[3]), ptr(keep[4]),
-                                 out.data_ptr(), out.stride(0), ws.data_ptr(), ws.numel() if ws_bytes is None else ws_bytes,
-                                 _native.current_stream_ptr())
-    torch.cuda.synchronize()
-    return rc, out, ws[:4 * bsz].view(torch.float32).cpu().numpy().astype(np.float64)
+_call = functools.partial(call, max_len=MAX_LEN, out_stride=STRIDE)     # the file's geometry; a call may still name its own
 
 
 def _wave(x, fill=None):

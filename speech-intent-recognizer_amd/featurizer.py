@@ -11,7 +11,7 @@ import math
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _native
+from . import _native, wave_args
 
 N_FFT = 1024
 HOP = 512
@@ -48,12 +48,10 @@ def _check_wave_grad_args(wave, lengths, t_pad, hop=HOP):
     if not torch.is_tensor(wave) or wave.dtype != torch.float32:
         raise _native.SirError("the differentiable feature path takes a float32 waveform (an int16 tensor cannot carry a "
                                "gradient; dequantise it first: wave.float() / 32768)")
-    if wave.dim() != 2 or wave.shape[0] < 1 or wave.shape[1] < 1 or wave.stride(1) != 1:
+    if not wave_args.is_batch_layout(wave) or wave.numel() == 0:
         raise _native.SirError(f"wave must be [B, L] with unit inner stride, got {tuple(wave.shape)}")
-    if lengths is not None:
-        if not torch.is_tensor(lengths) or lengths.is_floating_point() or lengths.dtype == torch.bool \
-                or lengths.dim() != 1 or lengths.numel() != wave.shape[0]:
-            raise _native.SirError(f"lengths must be an integer tensor with one sample count per clip (batch {wave.shape[0]})")
+    if lengths is not None and not wave_args.is_length_vector(lengths, wave.shape[0]):
+        raise _native.SirError(f"lengths must be an integer tensor with one sample count per clip (batch {wave.shape[0]})")
     t_pad = int(t_pad)
     if t_pad < 1 or 1 + wave.shape[1] // hop > t_pad:
         raise _native.SirError(f"clips of {wave.shape[1]} samples have {1 + wave.shape[1] // hop} frames: the gradient needs "
@@ -109,11 +107,7 @@ class HipFeaturizer:
                                     window.data_ptr(), fb.data_ptr())
         self._h = C.c_void_p()
         _native.check(_native.lib().sir_create_ex(C.byref(cfg), win_length, C.byref(self._h)), "sir_create_ex")
-        # feature workspaces, one per stream that calls: on a general front-end the workspace is the live dB slab between the
-        # two launches, and callers such as BatchPipeline run batches of one featurizer on several streams at once
-        self._ws = {}
-        self._pws = None        # workspace of perturb()
-        self._rws = None        # workspace of reverb_mix()
+        self._scratch = wave_args.StreamScratch()      # workspaces of __call__, perturb and reverb_mix, one per calling stream
         self._pins = 0          # library objects (sir_pipeline) created from this handle that are still alive
 
     def pin(self):
@@ -143,43 +137,16 @@ class HipFeaturizer:
         """wave: [B, L] float32 or int16 on the GPU; lengths: int32 [B] on the GPU (default: all L).
         ``db_out`` (optional, same shape as the result) receives the un-normalised dB values.
         Returns [B, n_mels, t_pad] float32."""
-        _native.require_hip(wave, lengths)
-        if wave.dim() != 2 or wave.stride(1) != 1:
-            raise _native.SirError("wave must be [B, L] with unit inner stride")
-        if wave.dtype == torch.float32:
-            dt = _native.WAVE_F32
-        elif wave.dtype == torch.int16:
-            dt = _native.WAVE_I16
-        else:
-            raise _native.SirError(f"unsupported waveform dtype {wave.dtype}")
-        bsz, max_len = wave.shape
-        if lengths is None:
-            lengths = torch.full((bsz,), max_len, dtype=torch.int32, device=wave.device)
-        lengths = lengths.to(torch.int32).contiguous()
+        dt, bsz, max_len, lengths = wave_args.check_batch("features", wave, lengths)
         if out is None:
             out = torch.empty((bsz, self.n_mels, t_pad), dtype=torch.float32, device=wave.device)
         lib = _native.lib()
-        need = lib.sir_features_workspace_bytes(self._h, bsz, max_len)
-        # (allocated under the calling stream, so the allocator hands a replaced block to that stream only)
-        key = (wave.device, torch.cuda.current_stream(wave.device).cuda_stream)
-        ws = self._ws.get(key)
-        if ws is None or ws.numel() < need:
-            ws = self._ws[key] = torch.empty(need, dtype=torch.uint8, device=wave.device)
-        aug = None
-        keep = []
-        if any(a is not None for a in (shift, noise_sigma, time_mask, freq_mask)):
-            def ptr(t, dtype):
-                if t is None:
-                    return None
-                t = t.to(device=wave.device, dtype=dtype).contiguous()
-                keep.append(t)
-                return t.data_ptr()
-            aug = _native.Augment(ptr(shift, torch.int32), ptr(noise_sigma, torch.float32), int(noise_seed),
-                                  ptr(time_mask, torch.int32), ptr(freq_mask, torch.int32))
+        ws = self._scratch.get(lib.sir_features_workspace_bytes(self._h, bsz, max_len), wave.device)
+        keep = wave_args.Keep(wave.device)
         rc = lib.sir_features_fwd(self._h, wave.data_ptr(), dt, wave.stride(0), lengths.data_ptr(), bsz, max_len,
                                   out.data_ptr(), t_pad, db_out.data_ptr() if db_out is not None else None,
                                   ws.data_ptr(), ws.numel(),
-                                  C.byref(aug) if aug is not None else None, _native.current_stream_ptr())
+                                  keep.augment(shift, noise_sigma, noise_seed, time_mask, freq_mask), _native.current_stream_ptr())
         _native.check(rc, "sir_features_fwd")
         return out
 
@@ -206,59 +173,34 @@ class HipFeaturizer:
         """``sir_features_bwd``: d loss / d wave ``[B, L]`` float32 from ``dout = d loss / d features`` and the ``db_out`` of the
         matching ``__call__`` (same wave -- float32 or int16 --, lengths, t_pad and augmentation arguments).  ``out``
         (optional): float32 ``[B, >= L]`` with unit inner stride; columns from L on are left alone."""
-        _native.require_hip(wave, lengths, db, dout, out)
-        if wave.dim() != 2 or wave.stride(1) != 1:
-            raise _native.SirError("wave must be [B, L] with unit inner stride")
-        dt = {torch.float32: _native.WAVE_F32, torch.int16: _native.WAVE_I16}.get(wave.dtype)
-        if dt is None:
-            raise _native.SirError(f"unsupported waveform dtype {wave.dtype}")
-        bsz, max_len = wave.shape
+        dt, bsz, max_len, lengths = wave_args.check_batch("features_bwd", wave, lengths)
+        _native.require_hip(db, dout)
         shape = (bsz, self.n_mels, int(t_pad))
         for name, t in (("db", db), ("dout", dout)):
             if t.dtype != torch.float32 or tuple(t.shape) != shape:
                 raise _native.SirError(f"{name} must be float32 {shape}, got {t.dtype} {tuple(t.shape)}")
         db, dout = db.contiguous(), dout.contiguous()
-        if lengths is None:
-            lengths = torch.full((bsz,), max_len, dtype=torch.int32, device=wave.device)
-        lengths = lengths.to(torch.int32).contiguous()
-        if out is None:
-            out = torch.empty((bsz, max_len), dtype=torch.float32, device=wave.device)
-        elif out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != bsz or out.stride(1) != 1:
-            raise _native.SirError("out must be float32 [B, >= L] with unit inner stride")
-        keep = []
-
-        def ptr(t, dtype):
-            if t is None:
-                return None
-            t = t.to(device=wave.device, dtype=dtype).contiguous()
-            keep.append(t)
-            return t.data_ptr()
-        aug = None
-        if any(a is not None for a in (shift, noise_sigma, time_mask, freq_mask)):
-            aug = _native.Augment(ptr(shift, torch.int32), ptr(noise_sigma, torch.float32), int(noise_seed),
-                                  ptr(time_mask, torch.int32), ptr(freq_mask, torch.int32))
+        out = wave_args.check_out(out, bsz, max_len, wave.device)
+        keep = wave_args.Keep(wave.device)
         rc = _native.lib().sir_features_bwd(self._h, wave.data_ptr(), dt, wave.stride(0), lengths.data_ptr(), bsz, max_len,
                                             db.data_ptr(), dout.data_ptr(), int(t_pad),
-                                            C.byref(aug) if aug is not None else None, out.data_ptr(),
-                                            out.stride(0) if bsz > 1 else max(out.stride(0), out.shape[1]),
-                                            _native.current_stream_ptr())
+                                            keep.augment(shift, noise_sigma, noise_seed, time_mask, freq_mask), out.data_ptr(),
+                                            wave_args.out_row_stride(out), _native.current_stream_ptr())
         _native.check(rc, "sir_features_bwd")
-        return out[:, :max_len] if out.shape[1] != max_len else out
-
+        return wave_args.first_cols(out, max_len)
 
     # ---- waveform front-end (channel mix-down, sample-rate conversion) -----------------------------
     def mix_to_mono(self, pcm, channels, frames=None):
         """pcm: [B, frames * channels] interleaved int16 or float32 on the GPU -> [B, frames] float32
         (``torch.mean(waveform, dim=0)`` of precompute_features.py:50-51 after torchaudio.load's /32768)."""
         _native.require_hip(pcm, frames)
-        if pcm.dim() != 2 or pcm.stride(1) != 1 or pcm.shape[1] % channels:
-            raise _native.SirError("pcm must be [B, frames * channels] with unit inner stride")
-        dt = {torch.float32: _native.WAVE_F32, torch.int16: _native.WAVE_I16}.get(pcm.dtype)
-        if dt is None:
-            raise _native.SirError(f"unsupported sample dtype {pcm.dtype}")
-        bsz, max_frames = pcm.shape[0], pcm.shape[1] // channels
+        must = "pcm must be [B, frames * channels]"
+        dt, bsz, width = wave_args.check_wave("mix_to_mono", pcm, must, kind="sample")
+        if width % channels:
+            raise _native.SirError(f"mix_to_mono: {must} with unit inner stride")
+        max_frames = width // channels
         if frames is not None:
-            frames = frames.to(torch.int32).contiguous()
+            frames = wave_args.check_lengths("mix_to_mono", frames, bsz)
         out = torch.empty((bsz, max_frames), dtype=torch.float32, device=pcm.device)
         rc = _native.lib().sir_mix_to_mono(self._h, pcm.data_ptr(), dt, channels, pcm.stride(0),
                                            frames.data_ptr() if frames is not None else None, bsz, max_frames,
@@ -270,16 +212,7 @@ class HipFeaturizer:
         """``torchaudio.transforms.Resample(orig_freq, new_freq)`` (precompute_features.py:54-56) for a batch:
         wave [B, L] float32/int16 on the GPU, lengths int32 [B] -> ([B, ceil(new * L / orig)] float32, out lengths)."""
         new_freq = self.sample_rate if new_freq is None else new_freq
-        _native.require_hip(wave, lengths)
-        if wave.dim() != 2 or wave.stride(1) != 1:
-            raise _native.SirError("wave must be [B, L] with unit inner stride")
-        dt = {torch.float32: _native.WAVE_F32, torch.int16: _native.WAVE_I16}.get(wave.dtype)
-        if dt is None:
-            raise _native.SirError(f"unsupported waveform dtype {wave.dtype}")
-        bsz, max_len = wave.shape
-        if lengths is None:
-            lengths = torch.full((bsz,), max_len, dtype=torch.int32, device=wave.device)
-        lengths = lengths.to(torch.int32).contiguous()
+        dt, bsz, max_len, lengths = wave_args.check_batch("resample", wave, lengths)
         if int(orig_freq) == int(new_freq):
             return (wave if wave.dtype == torch.float32 else wave.float() / 32768.0), lengths
         lib = _native.lib()
@@ -304,30 +237,12 @@ class HipFeaturizer:
         tempo are cut there).
         ``offsets_out`` (test hook): int32 [B, 2, max_segments] receives the chosen WSOLA offsets, -1 where unused.
         Returns (out [B, max_out_len] float32, zero beyond each row's length, out_lengths int32 [B])."""
-        _native.require_hip(wave, lengths, offsets_out)
-        if wave.dim() != 2 or wave.stride(1) != 1:
-            raise _native.SirError("wave must be [B, L] with unit inner stride")
-        dt = {torch.float32: _native.WAVE_F32, torch.int16: _native.WAVE_I16}.get(wave.dtype)
-        if dt is None:
-            raise _native.SirError(f"unsupported waveform dtype {wave.dtype}")
-        bsz, max_len = wave.shape
-        if bsz == 0 or max_len == 0:
-            raise _native.SirError("perturb needs a non-empty [B, L] batch")
+        _native.require_hip(offsets_out)
+        dt, bsz, max_len, lengths = wave_args.check_batch("perturb", wave, lengths, refuse_empty=True)
         lib = _native.lib()
-        if lengths is None:
-            lengths = torch.full((bsz,), max_len, dtype=torch.int32, device=wave.device)
-        lengths = lengths.to(torch.int32).contiguous()
-        keep = []
-
-        def ptr(t, dtype):
-            if t is None:
-                return None
-            t = t.to(device=wave.device, dtype=dtype).contiguous()
-            if t.numel() != bsz:
-                raise _native.SirError(f"per-utterance argument of {t.numel()} values for a batch of {bsz}")
-            keep.append(t)
-            return t.data_ptr()
-        p_shift, p_cents, p_tempo = ptr(shift, torch.int32), ptr(pitch_cents, torch.float32), ptr(tempo, torch.float32)
+        keep = wave_args.Keep(wave.device, bsz)
+        p_shift = keep.ptr(shift, torch.int32)
+        p_cents, p_tempo = keep.ptr(pitch_cents, torch.float32), keep.ptr(tempo, torch.float32)
         if max_out_len is None:
             max_out_len = lib.sir_perturb_out_len(max_len, 0.85) if tempo is not None else max_len
             max_out_len = max(max_out_len, max_len)
@@ -336,10 +251,8 @@ class HipFeaturizer:
         out_len = torch.empty((bsz,), dtype=torch.int32, device=wave.device)
         ws, nbytes = None, 0
         if pitch_cents is not None:
-            nbytes = lib.sir_perturb_workspace_bytes(self._h, bsz, max_len)
-            if self._pws is None or self._pws.numel() < nbytes or self._pws.device != wave.device:
-                self._pws = torch.empty(nbytes, dtype=torch.uint8, device=wave.device)
-            ws, nbytes = self._pws.data_ptr(), self._pws.numel()
+            buf = self._scratch.get(lib.sir_perturb_workspace_bytes(self._h, bsz, max_len), wave.device)
+            ws, nbytes = buf.data_ptr(), buf.numel()
         max_seg = 0
         if offsets_out is not None:
             if offsets_out.dtype != torch.int32 or not offsets_out.is_contiguous() or offsets_out.dim() != 3 \
@@ -362,60 +275,37 @@ class HipFeaturizer:
         ``noise_offset`` int32 [B] first noise sample (the noise wraps), ``snr_db`` float32 [B].  A clip keeps its length.
         ``out`` (optional): float32 [B, >= L] with unit inner stride, not overlapping ``wave``; columns from L on are left alone.
         Returns out [B, L] float32, zero beyond each row's length (``return_gain``: also the gain applied to each row's noise)."""
-        _native.require_hip(wave, lengths, out)
-        if wave.dim() != 2 or wave.stride(1) != 1:
-            raise _native.SirError("wave must be [B, L] with unit inner stride")
-        dt = {torch.float32: _native.WAVE_F32, torch.int16: _native.WAVE_I16}.get(wave.dtype)
-        if dt is None:
-            raise _native.SirError(f"unsupported waveform dtype {wave.dtype}")
-        bsz, max_len = wave.shape
-        if bsz == 0 or max_len == 0:
-            raise _native.SirError("reverb_mix needs a non-empty [B, L] batch")
+        dt, bsz, max_len, lengths = wave_args.check_batch("reverb_mix", wave, lengths, refuse_empty=True)
         if (rir_index is not None and rir is None) or (noise_index is not None and noise is None):
             raise _native.SirError("rir_index / noise_index need their SoundBank (rir= / noise=)")
         if noise_index is not None and (noise_offset is None or snr_db is None):
             raise _native.SirError("noise_index needs noise_offset and snr_db")
         lib = _native.lib()
-        if lengths is None:
-            lengths = torch.full((bsz,), max_len, dtype=torch.int32, device=wave.device)
-        lengths = lengths.to(torch.int32).contiguous()
-        keep = []
-
-        def ptr(t, dtype):
-            if t is None:
-                return None
-            t = torch.as_tensor(t).to(device=wave.device, dtype=dtype).contiguous()
-            if t.numel() != bsz:
-                raise _native.SirError(f"per-utterance argument of {t.numel()} values for a batch of {bsz}")
-            keep.append(t)
-            return t.data_ptr()
+        keep = wave_args.Keep(wave.device, bsz)
 
         def bank(b, on):
             if not on:
                 return None, 0, None, 0, 0
             b = b.on(wave.device)
-            keep.append(b)
+            keep.held.append(b)
             return b.data.data_ptr(), b.data.stride(0), b.lengths.data_ptr(), len(b), b.max_len
-        p_ri, p_ni = ptr(rir_index, torch.int32), ptr(noise_index, torch.int32)
-        p_off, p_snr = (ptr(noise_offset, torch.int32), ptr(snr_db, torch.float32)) if noise_index is not None else (None, None)
+        p_ri, p_ni = keep.ptr(rir_index, torch.int32), keep.ptr(noise_index, torch.int32)
+        p_off, p_snr = None, None
+        if noise_index is not None:
+            p_off, p_snr = keep.ptr(noise_offset, torch.int32), keep.ptr(snr_db, torch.float32)
         r_data, r_stride, r_len, n_rir, max_rir = bank(rir, rir_index is not None)
         n_data, n_stride, n_len, n_noise, _ = bank(noise, noise_index is not None)
-        if out is None:
-            out = torch.empty((bsz, max_len), dtype=torch.float32, device=wave.device)
-        elif out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != bsz or out.shape[1] < max_len or out.stride(1) != 1:
-            raise _native.SirError("out must be float32 [B, >= L] with unit inner stride")
-        nbytes = max(lib.sir_reverb_workspace_bytes(self._h, bsz, max_len, max_rir), 256)
-        if self._rws is None or self._rws.numel() < nbytes or self._rws.device != wave.device:
-            self._rws = torch.empty(nbytes, dtype=torch.uint8, device=wave.device)
+        out = wave_args.check_out(out, bsz, max_len, wave.device)
+        ws = self._scratch.get(lib.sir_reverb_workspace_bytes(self._h, bsz, max_len, max_rir), wave.device)
         rc = lib.sir_wave_reverb_mix(self._h, wave.data_ptr(), dt, wave.stride(0), lengths.data_ptr(), bsz, max_len,
                                      r_data, r_stride, r_len, n_rir, max_rir, p_ri,
                                      n_data, n_stride, n_len, n_noise, p_ni, p_off, p_snr,
-                                     out.data_ptr(), out.stride(0) if bsz > 1 else max(out.stride(0), out.shape[1]),
-                                     self._rws.data_ptr(), self._rws.numel(), _native.current_stream_ptr())
+                                     out.data_ptr(), wave_args.out_row_stride(out),
+                                     ws.data_ptr(), ws.numel(), _native.current_stream_ptr())
         _native.check(rc, "sir_wave_reverb_mix")
-        res = out[:, :max_len] if out.shape[1] != max_len else out
+        res = wave_args.first_cols(out, max_len)
         if return_gain:
-            return res, self._rws[:bsz * 4].view(torch.float32).clone()
+            return res, ws[:bsz * 4].view(torch.float32).clone()
         return res
 
 

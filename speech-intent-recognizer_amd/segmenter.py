@@ -11,9 +11,10 @@ import math
 
 import torch
 
-from . import _native
+from . import _native, wave_args
 
 MIN_CHUNK, MAX_CHUNK = 64, 4096
+WAVE_MUST = "wave must be [n_rec, L]"
 
 
 class Segmenter:
@@ -42,26 +43,11 @@ class Segmenter:
         self.silence_chunks = _native.lib().sir_vad_stop_chunks(self.sample_rate, self.chunk_size, silence_limit)
         if self.silence_chunks < 0:
             raise ValueError(f"silence_limit {silence_limit!r} is out of range for chunks of {chunk_size} samples")
-        self._ws = None
+        self._scratch = wave_args.StreamScratch()
         self._seg_cap = 0
 
     def config(self):
         return _native.VadConfig(self.chunk_size, self.threshold, self.silence_chunks, self.prior_chunks, int(self.flush_tail))
-
-    @staticmethod
-    def _check_wave(wave, lengths):
-        _native.require_hip(wave, lengths)
-        if wave.dim() != 2 or wave.stride(1) != 1:
-            raise _native.SirError("wave must be [n_rec, L] with unit inner stride")
-        dt = {torch.float32: _native.WAVE_F32, torch.int16: _native.WAVE_I16}.get(wave.dtype)
-        if dt is None:
-            raise _native.SirError(f"unsupported waveform dtype {wave.dtype}")
-        n_rec, max_len = wave.shape
-        if lengths is None:
-            lengths = torch.full((n_rec,), max_len, dtype=torch.int32, device=wave.device)
-        if lengths.numel() != n_rec:
-            raise _native.SirError(f"lengths must hold one entry per recording: {lengths.numel()} for {n_rec}")
-        return dt, lengths.to(torch.int32).contiguous()
 
     def segment(self, wave, lengths=None, energy_out=None):
         """wave: [n_rec, L] int16 or float32 on the GPU, lengths: int32 [n_rec] on the GPU (default: all L).
@@ -70,8 +56,7 @@ class Segmenter:
         ``total`` is read once -- the one host synchronisation; if the table was too small it is regrown and the call repeated.
         ``energy_out`` (test hook): float32 [n_rec, ceil(L / chunk_size)] receives the chunk energies."""
         from .featurizer import get_featurizer
-        dt, lengths = self._check_wave(wave, lengths)
-        n_rec, max_len = wave.shape
+        dt, n_rec, max_len, lengths = wave_args.check_batch("Segmenter.segment", wave, lengths, "recording", must=WAVE_MUST)
         dev = wave.device
         seg_count = torch.zeros((n_rec,), dtype=torch.int32, device=dev)
         total = torch.zeros((1,), dtype=torch.int32, device=dev)
@@ -87,15 +72,14 @@ class Segmenter:
         need = lib.sir_vad_workspace_bytes(h, n_rec, max_len, self.chunk_size)
         if need == 0:
             raise _native.SirError(f"unsupported shape n_rec={n_rec} samples={max_len}")
-        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = self._scratch.get(need, dev)
         cfg = self.config()
         cap = max(self._seg_cap, self.initial_seg_cap)
         while True:
             table = torch.empty((cap, 3), dtype=torch.int32, device=dev)
             rc = lib.sir_vad_segment(h, wave.data_ptr(), dt, wave.stride(0), lengths.data_ptr(), n_rec, max_len, C.byref(cfg),
                                      energy_out.data_ptr() if energy_out is not None else None, seg_count.data_ptr(),
-                                     table.data_ptr(), cap, total.data_ptr(), self._ws.data_ptr(), self._ws.numel(),
+                                     table.data_ptr(), cap, total.data_ptr(), ws.data_ptr(), ws.numel(),
                                      _native.current_stream_ptr())
             _native.check(rc, "sir_vad_segment")
             n = int(total.item())
@@ -110,17 +94,10 @@ class Segmenter:
         length, clip_lengths int32 [n]).  int16 is dequantised as s / 32768; a segment longer than ``max_clip_len`` samples is
         cut there.  A table row outside the batch gives a zero row and ``ops.check_status()`` raises."""
         from .featurizer import get_featurizer
-        dt, _ = self._check_wave(wave, None)
-        _native.require_hip(table, total)
-        max_clip_len = int(max_clip_len)
-        if max_clip_len <= 0:
-            raise _native.SirError(f"max_clip_len must be positive, got {max_clip_len}")
-        if table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != 3 or total.dtype != torch.int32:
-            raise _native.SirError("table must be int32 [n, 3] and total int32 [1]")
-        table = table.contiguous()
+        _native.require_hip(wave)
+        dt = wave_args.check_wave("Segmenter.gather", wave, WAVE_MUST)[0]
+        table, max_clip_len, out, out_len = wave_args.check_gather(table, total, max_clip_len, torch.int32, 3, wave.device)
         n = table.shape[0]
-        out = torch.empty((n, max_clip_len), dtype=torch.float32, device=wave.device)
-        out_len = torch.empty((n,), dtype=torch.int32, device=wave.device)
         if n == 0:
             return out, out_len
         rc = _native.lib().sir_vad_gather(get_featurizer().handle, wave.data_ptr(), dt, wave.stride(0), wave.shape[0], table.data_ptr(),

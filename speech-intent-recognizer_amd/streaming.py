@@ -15,7 +15,7 @@ import math
 
 import torch
 
-from . import _native
+from . import _native, wave_args
 from .segmenter import Segmenter
 
 MAX_STREAMS = 65535
@@ -50,13 +50,26 @@ def input_dtype(encoding, dtype, pcm_default=torch.int16):
         raise ValueError(f"unknown stream encoding {encoding!r}: one of {ENCODINGS}")
     if encoding == "pcm":
         dtype = pcm_default if dtype is None else dtype
-        code = {torch.float32: _native.WAVE_F32, torch.int16: _native.WAVE_I16}.get(dtype)
+        code = wave_args.WAVE_CODES.get(dtype)
         if code is None:
             raise ValueError(f"unsupported stream dtype {dtype!r} for encoding 'pcm': int16 or float32")
         return dtype, code
     if dtype not in (None, torch.uint8):
         raise ValueError(f"a {encoding!r} stream is pushed as uint8 codes, not {dtype!r}")
     return torch.uint8, _native.WAVE_ULAW if encoding == "ulaw" else _native.WAVE_ALAW
+
+
+def _push_args(owner, who, samples, lengths):
+    """One push of ``owner`` (a ``StreamInput``, or a ``StreamSegmenter`` without one), checked: -> (samples, columns, lengths).
+    ``samples=None`` brings nothing."""
+    if samples is None:
+        samples, lengths = owner._nothing, torch.zeros((owner.n_streams,), dtype=torch.int32, device=owner.device)
+    must = f"samples must be {owner.dtype} [{owner.n_streams}, <= {owner.max_push}]"
+    _, _, width, lengths = wave_args.check_batch(who, samples, lengths, "stream", must=must, rows=owner.n_streams,
+                                                 dtypes={owner.dtype: owner.wave_dtype})
+    if not 1 <= width <= owner.max_push:
+        raise _native.SirError(f"a push brings 1 .. {owner.max_push} columns, got {width}")
+    return samples, width, lengths
 
 
 class StreamInput:
@@ -130,25 +143,9 @@ class StreamInput:
         -> (out float32 [n_streams, max_out], out_lengths int32 [n_streams]); columns behind a row's length are not written.
         No host synchronisation.  ``out``: a float32 [n_streams, >= max_out] tensor to write into instead of a new one."""
         self._ensure()
-        if samples is None:
-            samples, lengths = self._nothing, torch.zeros((self.n_streams,), dtype=torch.int32, device=self.device)
-        _native.require_hip(samples, lengths, out)
-        if samples.dim() != 2 or samples.shape[0] != self.n_streams or samples.stride(1) != 1 or samples.dtype != self.dtype:
-            raise _native.SirError(f"samples must be {self.dtype} [{self.n_streams}, <= {self.max_push}] with unit inner stride")
-        width = samples.shape[1]
-        if not 1 <= width <= self.max_push:
-            raise _native.SirError(f"a push brings 1 .. {self.max_push} columns, got {width}")
-        if lengths is None:
-            lengths = torch.full((self.n_streams,), width, dtype=torch.int32, device=self.device)
-        if lengths.numel() != self.n_streams:
-            raise _native.SirError(f"lengths must hold one entry per stream: {lengths.numel()} for {self.n_streams}")
-        lengths = lengths.to(torch.int32).contiguous()
+        samples, width, lengths = _push_args(self, "StreamInput.push", samples, lengths)
         close = _stream_mask(close, self.n_streams, self.device, "close")
-        if out is None:
-            out = torch.empty((self.n_streams, self.max_out), dtype=torch.float32, device=self.device)
-        elif out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != self.n_streams or out.stride(1) != 1 \
-                or out.shape[1] < self.max_out:
-            raise _native.SirError(f"out must be float32 [{self.n_streams}, >= {self.max_out}] with unit inner stride")
+        out = wave_args.check_out(out, self.n_streams, self.max_out, self.device, f"[{self.n_streams}, >= {self.max_out}]")
         out_len = torch.empty((self.n_streams,), dtype=torch.int32, device=self.device)
         rc = _native.lib().sir_stream_input_push(self._handle, self._state.data_ptr(), self._state.numel(), C.byref(self._cfg),
                                                  samples.data_ptr(), samples.stride(0), width, lengths.data_ptr(),
@@ -264,18 +261,7 @@ class StreamSegmenter:
             # decode and rate-convert first: what the detector is handed is float32 at sample_rate, at most max_out columns
             samples, lengths = self.input.push(samples, lengths, close, out=self._converted)
         else:
-            if samples is None:
-                samples, lengths = self._nothing, torch.zeros((self.n_streams,), dtype=torch.int32, device=self.device)
-            _native.require_hip(samples, lengths)
-            if samples.dim() != 2 or samples.shape[0] != self.n_streams or samples.stride(1) != 1 or samples.dtype != self.dtype:
-                raise _native.SirError(f"samples must be {self.dtype} [{self.n_streams}, <= {self.max_push}] with unit inner stride")
-            if not 1 <= samples.shape[1] <= self.max_push:
-                raise _native.SirError(f"a push brings 1 .. {self.max_push} columns, got {samples.shape[1]}")
-            if lengths is None:
-                lengths = torch.full((self.n_streams,), samples.shape[1], dtype=torch.int32, device=self.device)
-            if lengths.numel() != self.n_streams:
-                raise _native.SirError(f"lengths must hold one entry per stream: {lengths.numel()} for {self.n_streams}")
-            lengths = lengths.to(torch.int32).contiguous()
+            samples, _, lengths = _push_args(self, "StreamSegmenter.push_table", samples, lengths)
         width = samples.shape[1]
         rc = _native.lib().sir_stream_push(self._handle, self._state.data_ptr(), self._state.numel(), C.byref(self._cfg), samples.data_ptr(),
                                            samples.stride(0), width, lengths.data_ptr(), close.data_ptr() if close is not None else None,
@@ -290,16 +276,8 @@ class StreamSegmenter:
         [n, max_clip_len], zero behind each clip's length, clip_lengths int32 [n]).  int16 is dequantised as s / 32768.  An
         impossible row gives a zero row and ``ops.check_status()`` raises."""
         self._ensure()
-        _native.require_hip(table, total)
-        max_clip_len = int(max_clip_len)
-        if max_clip_len <= 0:
-            raise _native.SirError(f"max_clip_len must be positive, got {max_clip_len}")
-        if table.dtype != torch.int64 or table.dim() != 2 or table.shape[1] != 4 or total.dtype != torch.int32:
-            raise _native.SirError("table must be int64 [n, 4] and total int32 [1]")
-        table = table.contiguous()
+        table, max_clip_len, out, out_len = wave_args.check_gather(table, total, max_clip_len, torch.int64, 4, self.device)
         n = table.shape[0]
-        out = torch.empty((n, max_clip_len), dtype=torch.float32, device=self.device)
-        out_len = torch.empty((n,), dtype=torch.int32, device=self.device)
         if n == 0:
             return out, out_len
         rc = _native.lib().sir_stream_gather(self._handle, self._state.data_ptr(), self._state.numel(), C.byref(self._cfg), table.data_ptr(),

@@ -272,6 +272,30 @@ def test_two_runs_are_bit_identical():
     assert np.array_equal(ga[1].view(np.uint32), gb[1].view(np.uint32)) and np.array_equal(ga[2], gb[2])
 
 
+def test_segmenter_on_a_side_stream_equals_the_default_stream():
+    """``Segmenter`` keeps its scratch per calling stream: ``segment`` / ``gather`` on a side stream and on the default stream give
+    the same tables and clips, from two buffers."""
+    w, dw, dl, _, _ = _case(0.2, np.int16)
+    seg = Segmenter(chunk_size=CH, threshold=THR, silence_limit=2 * CH / 16000, prior_recording=CH / 16000)
+    assert (seg.silence_chunks, seg.prior_chunks) == (2, 1)
+
+    def run():
+        table, count, total = seg.segment(dw, dl)
+        return (table, count, total) + seg.gather(dw, table, total, 1003)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        a = run()
+    side.synchronize()
+    b = run()
+    torch.cuda.synchronize()
+    assert a[0].shape[0] > len(LENGTHS) and len(a) == 5
+    assert all(torch.equal(x, y) for x, y in zip(a, b))
+    ops.check_status()
+    bufs = list(seg._scratch.buffers.values())
+    assert len(bufs) == 2 and bufs[0].data_ptr() != bufs[1].data_ptr()
+
+
 def test_bad_arguments():
     lib = _native.lib()
     h = get_featurizer().handle

@@ -198,6 +198,43 @@ def test_perturbed_features_match_oracle(fz):
         assert err <= 1e-4, (b, err)
 
 
+@pytest.mark.parametrize("reverb", [False, True], ids=["perturb", "perturb_reverb"])
+def test_two_pipeline_slots_in_flight_keep_their_own_scratch(fz, reverb):
+    """Two BatchPipeline slots run the wave stages of one featurizer at once, both with a pitch drawn (the perturb workspace is
+    live across three launches) and, with ``reverb``, through ``reverb_mix`` too: each slot's features are bit for bit those
+    of the same calls in line -- the same kernels on the same inputs --, and the two slot streams hold scratch buffers of
+    their own.  Batch B is batch A with rows and parameters reversed, so a slot that read the other's rows would show."""
+    from sir_amd.models.models import CNNAudioGRU
+    from sir_amd.pipeline import BatchPipeline
+    from sir_amd.sound_bank import SoundBank
+    xa = torch.cat([_batch(torch.float32)] * 2).cuda()
+    lens = torch.tensor(LENGTHS * 2, dtype=torch.int32, device="cuda")
+    kwa = dict(zip(("shift", "pitch_cents", "tempo"), (p.cuda() for p in _chain_params())))
+    mix = {}
+    if reverb:                                                   # the bank of test_reverb_gpu.py::test_batch_pipeline_features
+        mix["rir"] = SoundBank([synth.synthetic_rir(0.1, rng=np.random.default_rng(6))], kind="rir")
+        kwa["rir_index"] = torch.tensor([0, -1, 0, 0] * 4, dtype=torch.int32, device="cuda")
+    batches = [(xa, lens, kwa), (xa.flip(0).contiguous(), lens.flip(0).contiguous(), {k: v.flip(0).contiguous() for k, v in kwa.items()})]
+    want = []
+    for x, n, kw in batches:
+        w, wn = fz.perturb(x, n, shift=kw["shift"], pitch_cents=kw["pitch_cents"], tempo=kw["tempo"])
+        if reverb:
+            w = fz.reverb_mix(w, wn, rir_index=kw["rir_index"], **mix)
+        want.append(fz(w, wn, t_pad=200))
+    torch.cuda.synchronize()
+    ops.check_status()
+    pipe = BatchPipeline(CNNAudioGRU(num_classes=31).cuda().eval(), n_streams=2)
+    assert pipe.featurizer is fz
+    got = [pipe.features(i, x, n, t_pad=200, **kw, **mix) for i, (x, n, kw) in enumerate(batches)]
+    pipe.synchronize()
+    ops.check_status()
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1])
+    assert not torch.equal(want[0], want[1])
+    slots = {st.cuda_stream for st in pipe.streams}
+    spans = sorted((buf.data_ptr(), buf.data_ptr() + buf.numel()) for (_, st), buf in fz._scratch.buffers.items() if st in slots)
+    assert len(slots) == 2 and len(spans) == 2 and spans[0][1] <= spans[1][0]
+
+
 def test_train_with_pitch_speed_augment(tmp_path):
     import types
     from test_pipeline_gpu import _make_corpus, _write_splits

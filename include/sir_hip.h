@@ -424,6 +424,18 @@ int sir_model_infer(sir_handle* h, const sir_model_weights* w, const float* feat
 int sir_model_infer_ragged(sir_handle* h, const sir_model_weights* w, const float* feats,
                            const int32_t* frames, int batch, int t_frames, float* logits,
                            int64_t* argmax, void* workspace, size_t workspace_bytes, void* stream);
+/* sir_model_embed: the forward of sir_model_infer (frames == NULL) or of sir_model_infer_ragged (frames: DEVICE int32[batch]),
+ * returning the utterance embedding: the attention-pooled context (models/models.py:63-66), 512 floats per utterance, raw and
+ * un-normalised.  Workspace size, prepared-weight reuse, shape limits and the status word are those of the two calls.
+ * emb    : [batch][512] f32, 16-byte aligned, required.  For every row to which sir_model_infer* gives finite logits it is
+ *          bit-identical to workspace slot 6 (sir_model_workspace_offsets); it is all-NaN for every row those calls make NaN: a
+ *          non-finite feature in the utterance, or a ragged length outside [8, t_frames].  One small kernel behind the head
+ *          (copy + the NaN rule); the forward kernels, their outputs and the workspace contents are exactly sir_model_infer*'s.
+ * logits : [batch][num_classes] or NULL.  When given, logits (and argmax, optional, needs logits) are bit-identical to
+ *          sir_model_infer / sir_model_infer_ragged; with logits == NULL the classifier is not run. */
+int sir_model_embed(sir_handle* h, const sir_model_weights* w, const float* feats, const int32_t* frames /* NULL: padded */,
+                    int batch, int t_frames, float* emb, float* logits, int64_t* argmax, void* workspace,
+                    size_t workspace_bytes, void* stream);
 /* ---- utterance segmentation of long recordings --------------------------------
  * sir_vad_segment replaces, for a whole batch of recordings resident in HBM, the energy detector of the continuous-audio
  * recogniser: MicrophoneListener._calculate_energy / _is_speech (scripts/testing.py:38-47) and the state machine of
@@ -1062,6 +1074,62 @@ int sir_eval_accumulate_slots(sir_handle* h, const float* logits, const int64_t*
 int sir_decode_slots(sir_handle* h, const float* logits, int batch, int num_classes, const int32_t* slot_sizes, int n_slots,
                      const float* inv_temperature, const uint8_t* tuples, int n_tuples, int k, int32_t* best_index,
                      int32_t* best_labels, float* best_logp, float* best_prob, float* valid_mass, float* tuple_logp, void* stream);
+
+/* ---- embeddings and the prototype head (DESIGN.md section 4 "Embeddings and the prototype head", csrc/prototypes.hip) -------
+ * Intents enrolled from examples, with no backward pass: the unit-normalised embeddings (sir_model_embed) of a class's examples
+ * are summed into a bank, the normalised sums are the class prototypes, and a batch is scored by cosine similarity against up
+ * to 4096 prototypes or exemplars in one launch.  Nothing allocates; no floating-point atomics; results bit-reproducible.
+ * Embedding rows are [512] f32, arrays of them 16-byte aligned.  The UNIT VECTOR of a row e is u = e / ||e|| with the norm and
+ * the quotient in double; the row's sum of squares is taken in a fixed order that depends on nothing but the row (element
+ * 8 l + i in lane l: the lane's eight squares in order i, then the xor butterfly over the lanes).  Every argument is checked
+ * before anything is launched; a refused call (SIR_EINVAL: a required pointer NULL, a count outside its range, k > 8, a
+ * misaligned pointer, state_bytes too small, the header's n_classes different from the argument) writes nothing.
+ *
+ * The bank is caller-owned DEVICE memory of sir_proto_state_bytes(n_classes) bytes (0 unless 1 <= n_classes <= 4096), 16-byte
+ * aligned, P = n_classes:
+ *     bytes 0..63   header: int32 n_classes, int32 0, int64 skipped, zeros
+ *     int64  count[P]
+ *     double sum[P][512]
+ * sir_proto_reset lays the state out: it clears count and sum of the classes with mask[p] != 0 (mask: DEVICE uint8[P]; NULL =
+ *   all, which also zeroes `skipped` and needs no valid header).  A class is removed or re-enrolled this way.
+ * sir_proto_accumulate: for each row b in ascending order, sum[labels[b]] += u_b (double), count[labels[b]] += 1.  labels:
+ *   DEVICE int64[batch].  A class's sum is ONE sequential chain in row order (one wavefront per class walks the labels), so THE
+ *   STATE AFTER ENROLLING A SET OF ROWS IS BIT-IDENTICAL HOWEVER THE ROWS WERE CUT INTO CALLS.  A row is skipped, counted in
+ *   `skipped` and leaves everything else untouched when its label is outside [0, n_classes) (-1 is the documented "ignore"), its
+ *   embedding holds a NaN or an infinity, or its norm is zero.  The norm being a double, a finite row at 1e-30 or 1e30 enrols
+ *   like any other.
+ * sir_proto_finalize: protos[p] = fp32(sum[p] / ||sum[p]||) in double, live[p] = 1; a class with count 0 or a zero or
+ *   non-finite sum gets an all-zero row and live[p] = 0.  protos [P][512] f32, live uint8[P], both required.
+ * sir_proto_accumulate, sir_proto_finalize and a masked sir_proto_reset read the header back before they launch: they are
+ * host-synchronous on `stream` and not legal under stream capture.  Calls on one state must be ordered (one stream, or events). */
+size_t sir_proto_state_bytes(int n_classes);
+int sir_proto_reset(sir_handle* h, void* state, size_t state_bytes, int n_classes, const uint8_t* mask /* NULL: all */, void* stream);
+int sir_proto_accumulate(sir_handle* h, void* state, size_t state_bytes, int n_classes, const float* emb, const int64_t* labels,
+                         int batch, void* stream);
+int sir_proto_finalize(sir_handle* h, void* state, size_t state_bytes, int n_classes, float* protos, uint8_t* live, void* stream);
+/* sir_proto_score: one launch, only a kernel (legal under stream capture).  1 <= batch <= 2^30, 1 <= n_protos <= 4096,
+ * 1 <= n_classes <= n_protos, 1 <= k <= 8.
+ *   protos      f32 [n_protos][512]: unit rows (sir_proto_finalize's, or exemplars); finite
+ *   live        DEVICE uint8[n_protos] or NULL (all live)
+ *   proto_class DEVICE int32[n_protos], the class of each prototype, or NULL: class = row, and n_classes must equal n_protos.
+ *               A prototype whose class is outside [0, n_classes) takes no part, like one that is not live.
+ *   scale       DEVICE f32[1] or NULL = 1: used as given, the way sir_classify uses inv_temperature -- the ranking never
+ *               depends on it; a value that is not positive and finite gives the probabilities IEEE arithmetic gives.
+ * Per row: u = the unit vector of emb[b]; sim[p] = <u, protos[p]> in fp32 (an fma chain over the lane's eight elements, then a
+ * fixed butterfly over the lanes); the score of class c is s[c] = max of sim[p] over its live prototypes (one per class: a
+ * nearest-class-mean head; several exemplars: 1-NN); a class with no live prototype is absent.  Classes rank by descending s,
+ * equal scores by ascending class, as sir_classify.
+ *   sims        f32 [batch][n_protos] or NULL: every sim[p], live or not
+ *   topk_class  int32 [batch][k], topk_sim f32 [batch][k] = s, topk_prob f32 [batch][k] = the softmax of scale * s over the
+ *               present classes: expf((s - max s) * scale) / den, den summed in double in a fixed order
+ *   nearest     int32 [batch] or NULL: the lowest live prototype row of the rank-0 class whose sim is that class's score
+ * Ranks beyond the number of present classes hold -1 / 0 / 0 (nearest -1 with no class present).  A row of emb that holds a
+ * NaN or an infinity or has norm zero gives -1 / NaN / NaN, nearest -1 and NaN sims; the other rows are unaffected.
+ * A ROW'S OUTPUTS CARRY THE SAME BITS WHATEVER ITS POSITION IN THE BATCH AND WHATEVER THE BATCH SIZE. */
+int sir_proto_score(sir_handle* h, const float* emb, int batch, const float* protos, const uint8_t* live /* or NULL */,
+                    const int32_t* proto_class /* or NULL: class = row */, int n_protos, int n_classes,
+                    const float* scale /* device scalar or NULL = 1 */, int k, float* sims /* or NULL */, int32_t* topk_class,
+                    float* topk_sim, float* topk_prob, int32_t* nearest /* or NULL */, void* stream);
 
 /* ---- measurement -----------------------------------------------------------------------------
  * HIP-event timing of the kernels of the path, recorded on the stream they are launched on

@@ -58,10 +58,24 @@ extern "C" int sir_model_infer_table_offsets(const sir_handle* h, int batch, int
     return nv;
 }
 
-// frames == nullptr: the padded function with the pad skip (sir_model_infer); else the ragged one (head of this file)
+// sir_model_embed's export: emb[b] = ctx[b] (workspace slot 6, untouched), all-NaN for a row whose logits the head kernel makes NaN --
+// a non-finite feature in the utterance (nonfinite: pad_extent_kernel) or a rejected ragged length (slen[b] < 1; slen NULL: padded)
+static __global__ __launch_bounds__(128) void embed_export_kernel(const float* __restrict__ ctx, const int* __restrict__ nonfinite,
+                                                                  const int* __restrict__ slen, float* __restrict__ emb) {
+    const int b = blockIdx.x;
+    const bool bad = nonfinite[b] != 0 || (slen && slen[b] < 1);
+    const float qnan = __builtin_nanf("");
+    const float4 v = reinterpret_cast<const float4*>(ctx + (size_t)b * 512)[threadIdx.x];
+    reinterpret_cast<float4*>(emb + (size_t)b * 512)[threadIdx.x] = bad ? make_float4(qnan, qnan, qnan, qnan) : v;
+}
+
+// frames == nullptr: the padded function with the pad skip (sir_model_infer); else the ragged one (head of this file).
+// emb != nullptr (sir_model_embed): the context rows are exported behind the head, and logits may then be NULL (no classifier)
 static int model_infer_impl(const char* who, sir_handle* h, const sir_model_weights* w, const float* feats, const int32_t* frames, int batch,
-                            int t_frames, float* logits, int64_t* argmax, void* workspace, size_t workspace_bytes, void* stream_) {
-    if (!h || !w || !feats || !logits || !workspace) { sir_set_error("%s: NULL argument", who); return SIR_EINVAL; }
+                            int t_frames, float* logits, int64_t* argmax, void* workspace, size_t workspace_bytes, void* stream_,
+                            float* emb = nullptr) {
+    if (!h || !w || !feats || (!logits && !emb) || !workspace) { sir_set_error("%s: NULL argument", who); return SIR_EINVAL; }
+    if (emb && (((uintptr_t)emb & 15) != 0)) { sir_set_error("%s: emb must be 16-byte aligned", who); return SIR_EINVAL; }
     Dims d;
     if (!make_dims(batch, t_frames, &d)) {
         sir_set_error("%s: unsupported shape batch=%d t_frames=%d (need " SIR_SHAPE_LIMITS ")", who, batch, t_frames);
@@ -209,6 +223,8 @@ static int model_infer_impl(const char* who, sir_handle* h, const sir_model_weig
         else
             hipLaunchKernelGGL(attention_pool_kernel, dim3(B), dim3(256), 0, st, p.y1, w->attn_w, w->attn_b, p.ctx, S, w->fc_w, w->fc_b,
                                w->num_classes, logits, (long long*)argmax, t.nonfinite, nullptr);
+        if (emb)
+            hipLaunchKernelGGL(embed_export_kernel, dim3(B), dim3(128), 0, st, p.ctx, t.nonfinite, ragged ? t.d3 : (const int*)nullptr, emb);
     }
     SIR_KCHECK();
     return SIR_OK;
@@ -224,4 +240,11 @@ extern "C" int sir_model_infer_ragged(sir_handle* h, const sir_model_weights* w,
                                       void* stream_) {
     if (!frames) { sir_set_error("sir_model_infer_ragged: NULL frames"); return SIR_EINVAL; }
     return model_infer_impl("sir_model_infer_ragged", h, w, feats, frames, batch, t_frames, logits, argmax, workspace, workspace_bytes, stream_);
+}
+
+extern "C" int sir_model_embed(sir_handle* h, const sir_model_weights* w, const float* feats, const int32_t* frames, int batch, int t_frames,
+                               float* emb, float* logits, int64_t* argmax, void* workspace, size_t workspace_bytes, void* stream_) {
+    if (!emb) { sir_set_error("sir_model_embed: NULL emb"); return SIR_EINVAL; }
+    if (argmax && !logits) { sir_set_error("sir_model_embed: argmax needs logits"); return SIR_EINVAL; }
+    return model_infer_impl("sir_model_embed", h, w, feats, frames, batch, t_frames, logits, argmax, workspace, workspace_bytes, stream_, emb);
 }

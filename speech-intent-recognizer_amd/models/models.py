@@ -113,6 +113,13 @@ class CNNAudioGRU(nn.Module):
         return ops.model_infer(self, x, self._ws, want_argmax=True, lengths=lengths)
 
     @torch.no_grad()
+    def embed(self, x, lengths=None):
+        """The utterance embeddings [B, 512]: the attention-pooled context the classifier reads, raw (``ops.model_embed``);
+        the classifier itself is not run.  ``lengths`` as in ``forward``.  ``sir_amd.prototypes.PrototypeBank`` enrols and
+        scores these rows."""
+        return ops.model_embed(self, x, self._ws, lengths=lengths)
+
+    @torch.no_grad()
     def classify(self, x, lengths=None, k=3, inv_temperature=None):
         """The forward plus ``ops.classify`` on the device -> ``(logits [B, C], topk_idx int32 [B, k], topk_prob [B, k])``: the
         ``k`` most probable classes of every clip in order and their softmax probabilities (``topk_idx[:, 0]`` is ``predict``'s

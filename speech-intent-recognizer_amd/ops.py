@@ -240,6 +240,38 @@ def model_infer(mod, x, workspace, want_argmax=False, debug=None, lengths=None):
     return (logits, amax) if want_argmax else logits
 
 
+def model_embed(mod, x, workspace, lengths=None, want_logits=False, debug=None):
+    """The forward of ``model_infer`` returning the utterance embeddings (``sir_model_embed``): the attention-pooled context,
+    [B, 512] float32, raw and un-normalised -- what ``sir_amd.prototypes`` enrols and scores.  A row whose logits
+    ``model_infer`` makes NaN (a non-finite feature, a bad ragged length) is all-NaN.  ``lengths`` as in ``model_infer``.
+    ``want_logits=True`` -> ``(emb, logits, argmax)``, logits and argmax bit-identical to ``model_infer``'s; without it the
+    classifier is not run."""
+    _native.require_hip(x)
+    x = _as_features(x)
+    bsz, _, t = x.shape
+    lib = _native.lib()
+    h = get_featurizer().handle
+    need = lib.sir_model_workspace_bytes(h, bsz, t, 0)
+    if need == 0:
+        raise _native.SirError(f"unsupported shape batch={bsz} frames={t} ({SHAPE_LIMITS})")
+    if lengths is not None:
+        lengths = _as_lengths(lengths, bsz, t, x.device)
+    ws = workspace.get(need, x.device)
+    w, keep = cached_weights(mod)
+    emb = torch.empty((bsz, 512), dtype=torch.float32, device=x.device)
+    logits = torch.empty((bsz, w.num_classes), dtype=torch.float32, device=x.device) if want_logits else None
+    amax = torch.empty((bsz,), dtype=torch.int64, device=x.device) if want_logits else None
+    lib.sir_model_set_weights_version(h, weights_version(mod, keep, workspace))
+    rc = lib.sir_model_embed(h, C.byref(w), x.data_ptr(), lengths.data_ptr() if lengths is not None else None, bsz, t,
+                             emb.data_ptr(), logits.data_ptr() if want_logits else None, amax.data_ptr() if want_logits else None,
+                             ws.data_ptr(), ws.numel(), _native.current_stream_ptr())
+    _native.check(rc, "sir_model_embed")
+    if debug is not None:
+        debug.update(stage_views(ws, bsz, t))
+    del keep
+    return (emb, logits, amax) if want_logits else emb
+
+
 def classify(logits, k=3, inv_temperature=None, want_probs=False):
     """Softmax and top-k of a batch of logits in one ``sir_classify`` launch -> ``(topk_idx int32 [B, k], topk_prob float32
     [B, k])``, classes by descending logit (equal logits: the lower index first), so ``topk_idx[:, 0]`` is the argmax

@@ -141,6 +141,47 @@ def results_of(logits, inv_label_map, slots=None, temperature=None, min_confiden
     return results_from_logits(logits, inv_label_map, inv_temperature=inv_temperature_of(temperature), min_confidence=min_confidence)
 
 
+def check_prototypes(prototypes, min_similarity, slots=None, temperature=None, min_confidence=None):
+    """The callers' ``prototypes=`` / ``min_similarity=`` keywords: the prototype head replaces the ``fc`` head, so it goes with
+    neither a slot layout nor that head's ``temperature`` / ``min_confidence``, and ``min_similarity`` needs a bank.  A
+    caller's mistake is raised before any device call."""
+    if prototypes is None:
+        if min_similarity is not None:
+            raise ValueError("min_similarity= needs prototypes= (a sir_amd.prototypes.PrototypeBank)")
+        return
+    if slots is not None:
+        raise ValueError("prototypes= and slots= are two different heads: pass one of them")
+    if temperature is not None or min_confidence is not None:
+        raise ValueError("temperature= and min_confidence= belong to the fc head: with prototypes= use the bank's scale and "
+                         "min_similarity=")
+    if min_similarity is not None:
+        float(min_similarity)
+
+
+def results_from_prototypes(emb, bank, k=3, scale=None, min_similarity=None):
+    """``results_from_logits`` for the prototype head: ONE ``sir_proto_score`` launch and ONE device-to-host copy for all rows of
+    ``emb`` [B, 512] (``CNNAudioGRU.embed``) against ``bank`` (``sir_amd.prototypes.PrototypeBank``) -> list of B dicts of
+    ``results_from_logits``' shape (labels are the bank's names; ``top_predictions`` holds at most as many entries as classes
+    have a prototype) plus ``"similarity"`` (the rank-0 cosine) and ``"nearest"`` (the prototype row it belongs to).  With
+    ``min_similarity`` set every dict also carries ``"rejected"``: the similarity is below it (or NaN)."""
+    k = int(k)
+    s = bank.score(emb, k=k, scale=scale)
+    packed = torch.cat([s.classes.to(torch.float32), s.nearest.to(torch.float32)[:, None], s.probs, s.sims], dim=1).cpu().numpy()
+    idx_h, near_h = packed[:, :k].astype(np.int64), packed[:, k].astype(np.int64)   # indices <= 4095 are exact in float32
+    prob_h, sim_h = packed[:, k + 1: 2 * k + 1], packed[:, 2 * k + 1:]
+    names = bank.names
+    results = []
+    for row_i, near, row_p, row_s in zip(idx_h.tolist(), near_h.tolist(), prob_h.tolist(), sim_h.tolist()):
+        top = [{"label": names[i] if 0 <= i < len(names) else "Unknown", "probability": p}
+               for i, p in zip(row_i, row_p) if not (i < 0 and p == 0.0)]              # (-1 / 0: a rank that does not exist)
+        res = {"predicted_label": names[row_i[0]] if 0 <= row_i[0] < len(names) else "Unknown", "confidence": row_p[0],
+               "top_predictions": top, "similarity": row_s[0], "nearest": near}
+        if min_similarity is not None:
+            res["rejected"] = not (row_s[0] >= min_similarity)
+        results.append(res)
+    return results
+
+
 def results_from_logits(logits, inv_label_map, k=3, inv_temperature=None, min_confidence=None):
     """``test_model._result`` for a whole batch: ONE ``sir_classify`` launch and ONE device-to-host copy for all rows of
     ``logits`` [B, C] -> list of B dicts of ``_result``'s shape (``top_predictions`` holds ``k`` entries, at most the number of

@@ -7,7 +7,9 @@ YAML key ``device_metrics: true`` (default false) builds the report on the devic
 ``sir_amd.metrics.EvalAccumulator`` behind its forward, the few kilobytes of counts come back once, and
 ``classification_report.txt`` (same text), ``confusion_matrix.png`` plus ``calibration.json`` (top-k accuracy, NLL, ECE / MCE, reliability table) are
 written from them.  ``--fit_temperature VALID_CSV`` fits the softmax temperature on that split (``sir_temperature_fit``)
-and writes ``temperature.json`` beside the checkpoint; ``--temperature_file`` reads one back for the calibration figures."""
+and writes ``temperature.json`` beside the checkpoint; ``--temperature_file`` reads one back for the calibration figures.
+YAML key ``prototypes: bank.npz`` (``scripts/enroll.py`` writes one) also writes ``prototype_metrics.json``: top-1 / top-3 of the
+prototype head on the split beside the ``fc`` head's (``prototype_metrics_file``)."""
 import argparse
 import json
 import logging
@@ -213,8 +215,49 @@ def evaluate_slots(args, config):
     return joint["exact_match_accuracy"]
 
 
+def prototype_metrics_file(model, loader, device, bank_path, inv_label_map, out_path):
+    """YAML key ``prototypes: bank.npz`` (a ``sir_amd.prototypes.PrototypeBank`` file, ``scripts/enroll.py`` writes one): top-1 and
+    top-3 accuracy of the prototype head on the split, beside the ``fc`` head's figures from the same forward passes
+    (``sir_model_embed`` with logits), written to ``prototype_metrics.json``.  A clip counts for the prototype head when its
+    label's name is among the bank's classes' first k; clips whose label the bank does not know are counted (``n_unknown``)
+    and miss."""
+    from sir_amd import ops
+    from sir_amd.prototypes import PrototypeBank
+    bank = PrototypeBank.load(bank_path)
+    model.eval()
+    n = unknown = 0
+    hits = {"prototypes": [0, 0], "fc": [0, 0]}
+    for mel, label in loader:
+        if mel is None or label is None or mel.size(0) == 0:
+            continue
+        emb, logits, _ = ops.model_embed(model, mel.to(device), model._ws, want_logits=True)
+        k = min(3, int(logits.shape[1]))
+        fc_idx, _ = ops.classify(logits, k=k)
+        proto_idx = bank.score(emb, k=3).classes
+        names = [inv_label_map.get(int(v)) for v in label.tolist()]
+        want = torch.tensor([bank._index.get(name, -2) for name in names], dtype=torch.int32, device=device)
+        unknown += int((want < 0).sum().item())
+        for key, idx, truth in (("prototypes", proto_idx, want), ("fc", fc_idx, label.to(device).to(torch.int32))):
+            hit = idx == truth[:, None]
+            hits[key][0] += int(hit[:, 0].sum().item())
+            hits[key][1] += int(hit.any(dim=1).sum().item())
+        n += int(label.numel())
+    ops.check_status()
+    out = {"n": n, "n_unknown": unknown, "bank": os.path.basename(bank_path), "bank_classes": len(bank.names),
+           "prototypes": {"top1": hits["prototypes"][0] / max(n, 1), "top3": hits["prototypes"][1] / max(n, 1)},
+           "fc": {"top1": hits["fc"][0] / max(n, 1), "top3": hits["fc"][1] / max(n, 1)}}
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(out, f, indent=2)
+    logger.info(f"Prototype head: top-1 {out['prototypes']['top1']:.4f}, top-3 {out['prototypes']['top3']:.4f} "
+                f"(fc head: {out['fc']['top1']:.4f} / {out['fc']['top3']:.4f}) -> {out_path}")
+    return out
+
+
 def evaluate(args, config):
     if config.get("slots"):
+        if config.get("prototypes"):
+            raise ValueError("`prototypes` and `slots` are two different heads: evaluate one of them")
         return evaluate_slots(args, config)
     _native.require_hip()
     from sir_amd.dist_utils import limit_host_threads
@@ -256,6 +299,9 @@ def evaluate(args, config):
     if getattr(args, "temperature_file", None):
         inv_temperature = read_temperature_file(args.temperature_file)
     logger.info("Starting evaluation...")
+    if config.get("prototypes"):
+        prototype_metrics_file(model, test_loader, device, config["prototypes"], inv_label_map,
+                               os.path.join(config["save_path"], "evaluation_results", "prototype_metrics.json"))
     if config.get("device_metrics", False):
         return _evaluate_on_device(model, test_loader, device, config, inv_label_map, num_classes, inv_temperature)
     all_preds, all_labels = predict_loader(model, test_loader, device)

@@ -33,7 +33,8 @@ def get_extractor(frontend=None):
 
 
 def predict_many(model, audio_paths, label_map, device, pad_to=test_model.MAX_LENGTH, frontend=None, on_device=False,
-                 temperature=None, min_confidence=None, slots=None, tuples=None, decode="independent"):
+                 temperature=None, min_confidence=None, slots=None, tuples=None, decode="independent", prototypes=None,
+                 min_similarity=None):
     """One feature pass at ``frontend`` and one forward for all files -> list of result dictionaries / ``None``.
     ``pad_to=None`` needs a single file (un-padded features, ``T >= 8``).  ``on_device``, ``temperature``, ``min_confidence``:
     the results come from ``classify_results.results_from_logits`` (one ``sir_classify`` launch and one copy for the batch instead of
@@ -42,8 +43,13 @@ def predict_many(model, audio_paths, label_map, device, pad_to=test_model.MAX_LE
     device route): the model's logit row is read as slot heads and every result is ``classify_results.results_from_slot_logits``'
     dictionary -- decoded slots, joint ``"confidence"``, per-slot tables; ``temperature`` may then hold one T per slot and
     ``min_confidence`` rejects on the joint value.  ``decode="joint"`` (with ``tuples``, a ``slots.TupleTable``: only the tuples
-    that exist) ranks whole label tuples instead, as ``results_from_slot_logits`` describes."""
-    on_device = on_device or slots is not None
+    that exist) ranks whole label tuples instead, as ``results_from_slot_logits`` describes.  ``prototypes`` (a
+    ``sir_amd.prototypes.PrototypeBank``; implies the device route): the prototype head instead of the ``fc`` head -- the model
+    returns embeddings (``model.embed``) and every result is ``classify_results.results_from_prototypes``' dictionary, labels
+    from the bank's names, ``"similarity"`` and ``"nearest"`` added; ``min_similarity`` adds ``"rejected"`` by distance.
+    ``prototypes`` with ``slots`` (or with ``temperature`` / ``min_confidence``) raises ``ValueError``."""
+    classify_results.check_prototypes(prototypes, min_similarity, slots, temperature, min_confidence)
+    on_device = on_device or slots is not None or prototypes is not None
     classify_results.check_route(on_device, temperature, min_confidence)       # a caller's mistake: raised, not logged
     classify_results.check_decode(decode, tuples, slots is not None)
     if slots is not None:
@@ -62,9 +68,12 @@ def predict_many(model, audio_paths, label_map, device, pad_to=test_model.MAX_LE
         else:
             batch = torch.stack([test_model._pad_or_trim(feats[i].unsqueeze(0), pad_to)[0] for i in keep]).to(device)
         with torch.no_grad():
-            output = model(batch)
+            output = model.embed(batch) if prototypes is not None else model(batch)
         inv = {v: k for k, v in label_map.items()}
-        if on_device:
+        if prototypes is not None:
+            for res, i in zip(classify_results.results_from_prototypes(output, prototypes, min_similarity=min_similarity), keep):
+                results[i] = res
+        elif on_device:
             for res, i in zip(classify_results.results_of(output, inv, slots, temperature, min_confidence, tuples, decode), keep):
                 results[i] = res
         else:

@@ -763,6 +763,11 @@ int sir_model_train_bwd_part(sir_handle* h, const sir_model_weights* w, const fl
  *              scale lies in [2^5, 2^10), else the power of two that puts it into [2^7, 2^8)); pair 1 + b is utterance b's own,
  *              written and used only by a sir_model_train_bwd_x call with all three bn_frozen set and no parameter gradient wanted
  *              (rows are then independent, and each is scaled by its own row of dlogits).  Slots 21..29 carry the scale.
+ *              With a gradient at the embedding (sir_model_train_bwd_emb, demb != NULL) the maximum is max(|dlogits|, |demb| * 2^5),
+ *              over the call or over row b of both: the head adds demb to dctx = dlogits fc_w, and at the reference head's
+ *              initialisation (fc_w uniform within +-512^-1/2 = 2^-4.5) max |dctx| is about max |dlogits| * 2^-4.5, so a demb of
+ *              magnitude m loads the fp16 contractions behind the head like a dlogits of m * 2^4.5 -- rounded up to 2^5, the
+ *              side that scales down.  With dlogits all zero the scale follows demb alone.  demb == NULL: the pairs of before.
  *   40  rag    the ragged step (sir_model_train_fwd_ragged): int32 [4][B] -- the validated frames (0 for a length outside [8, T]),
  *              W1, W2 and S_b of every clip; written by that call and rewritten by sir_model_train_bwd_ragged, untouched otherwise */
 int sir_model_train_workspace_offsets(const sir_handle* h, int batch, int t_frames, size_t* offsets, int n);
@@ -852,6 +857,24 @@ int sir_model_train_bwd_ragged(sir_handle* h, const sir_model_weights* w, const 
                                const float* dlogits, int batch, int t_frames, float dropout_p, uint64_t dropout_seed,
                                const sir_train_config* cfg, const sir_model_grads* grads, float* dfeats, void* workspace,
                                size_t workspace_bytes, int part, void* stream);
+
+/* ---- a second gradient entrance, at the embedding ------------------------------------------------
+ * The superset of the backward forms above, for a loss that is put on the 512-float attention-pooled context itself
+ * (sir_proxy_loss) alone or beside the classifier's: frames == NULL is sir_model_train_bwd_x (cfg == NULL: every BatchNorm live),
+ * frames != NULL is sir_model_train_bwd_ragged with its rules for cfg.
+ *   demb    : device f32 [batch][512] = d(loss)/d(ctx), unscaled like dlogits, 16-byte aligned.  The head adds row b of it to the
+ *             dctx it forms from dlogits (dctx = dlogits fc_w + demb); dy1, the attention gradients, the GRU, the CNN and dfeats
+ *             follow unchanged.  It does not enter the fc weight / bias gradient.  NULL: the call IS the form above for that
+ *             combination -- same launches, same bits, slot 39 included.
+ *   dlogits : required as before; a caller without a classifier loss passes zeros.
+ * Ragged: a clip with S_b < 1 ignores its demb row as it ignores its dlogits row (a NaN there does not travel).
+ * The call's loss scale (slot 39) takes max(|dlogits|, |demb| * 2^5) where it took max |dlogits| -- over the call, or in the
+ * per-row mode over row b of both -- so a demb of any finite magnitude, with dlogits zero or not, is as accurate as a dlogits
+ * of the usual one.  Every argument is validated before anything is launched or written. */
+int sir_model_train_bwd_emb(sir_handle* h, const sir_model_weights* w, const float* feats, const int32_t* frames /* NULL: padded */,
+                            const float* dlogits, const float* demb /* or NULL */, int batch, int t_frames, float dropout_p,
+                            uint64_t dropout_seed, const sir_train_config* cfg, const sir_model_grads* grads,
+                            float* dfeats /* or NULL */, void* workspace, size_t workspace_bytes, int part, void* stream);
 
 /* optimizer.step() for torch.optim.Adam(lr, betas, eps, weight_decay) with coupled L2
  * (train.py:246-250, :107): one multi-tensor launch.  The pointer arrays are HOST arrays of device
@@ -1130,6 +1153,31 @@ int sir_proto_score(sir_handle* h, const float* emb, int batch, const float* pro
                     const int32_t* proto_class /* or NULL: class = row */, int n_protos, int n_classes,
                     const float* scale /* device scalar or NULL = 1 */, int k, float* sims /* or NULL */, int32_t* topk_class,
                     float* topk_sim, float* topk_prob, int32_t* nearest /* or NULL */, void* stream);
+
+/* ---- training the embedding: the cosine-proxy loss ------------------------------------------------
+ * A normalised-softmax (AM-softmax / CosFace-style) loss of the embeddings against one learned centre per class, and its
+ * gradients.  With u_b = emb[b] / ||emb[b]|| and q_k = proxies[k] / ||proxies[k]|| (norms and quotients in double, the code of
+ * sir_proto_score; the unit vectors rounded to fp32 as there):
+ *     z[b][k] = scale * (<u_b, q_k> - margin * [k == labels[b]])       (the dot product of sir_proto_score, the same bits)
+ *     loss    = mean over the rows with a label of -log softmax(z[b])[labels[b]]
+ *     dz      = (softmax - onehot) * grad_scale / n_valid
+ *     demb[b]     = (du - <du, u_b> u_b) / ||emb[b]||,     du = scale * sum_k dz[b][k] q_k
+ *     dproxies[k] = (dq - <dq, q_k> q_k) / ||proxies[k]||, dq = scale * sum_b dz[b][k] u_b
+ * 1 <= batch, 1 <= n_proxies <= 4096 (the bank's limit); scale > 0 and margin >= 0 are HOST floats, finite.
+ *   emb      f32 [batch][512], proxies f32 [n_proxies][512] (need not be unit), labels DEVICE int64[batch]
+ *   loss     DEVICE f32[1]; demb f32 [batch][512] or NULL; dproxies f32 [n_proxies][512] or NULL (written, not accumulated)
+ *   workspace  sir_proxy_loss_workspace_bytes(batch, n_proxies) bytes (0 for counts outside the limits), 16-byte aligned
+ * Labels as for sir_ce_loss: -100 takes the row out of the loss, the gradients (a zero demb row) and the divisor (every row
+ * ignored: 0 / 0 = NaN); any other label outside [0, n_proxies) makes the loss NaN, gives the row no gradient and raises the
+ * status bit of sir_ce_loss (SIR_EINVAL at the next sir_check_status).  A row of emb or proxies with a NaN, an infinity or norm
+ * zero has no direction: the loss and that row's gradients are NaN, unless the row of emb is ignored.
+ * No floating atomic and every sum in a fixed order: bit-reproducible, and a row's demb carries the same bits at any position and
+ * batch size for equal n_valid.  Only kernels, no allocation: legal under stream capture.  Every argument is validated before
+ * anything is launched; a refused call (SIR_EINVAL) writes nothing.  These launches carry no profile ids. */
+size_t sir_proxy_loss_workspace_bytes(int batch, int n_proxies);
+int sir_proxy_loss(sir_handle* h, const float* emb, const float* proxies, const int64_t* labels, int batch, int n_proxies,
+                   float scale, float margin, float* loss, float* demb /* or NULL */, float* dproxies /* or NULL */,
+                   float grad_scale, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- measurement -----------------------------------------------------------------------------
  * HIP-event timing of the kernels of the path, recorded on the stream they are launched on

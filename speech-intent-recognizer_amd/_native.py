@@ -181,6 +181,12 @@ SIGNATURES = {
     "sir_model_train_bwd_ragged": (C.c_int, [C.c_void_p, C.POINTER(ModelWeights), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                              C.c_float, C.c_uint64, C.POINTER(TrainConfig), C.POINTER(ModelGrads), C.c_void_p,
                                              C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
+    "sir_model_train_bwd_emb": (C.c_int, [C.c_void_p, C.POINTER(ModelWeights), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                          C.c_int, C.c_float, C.c_uint64, C.POINTER(TrainConfig), C.POINTER(ModelGrads), C.c_void_p,
+                                          C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]),
+    "sir_proxy_loss_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "sir_proxy_loss": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_size_t, C.c_void_p]),
     "sir_adam_step": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                 C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_int, C.c_float, C.c_float, C.c_float,
                                 C.c_float, C.c_float, C.c_void_p]),

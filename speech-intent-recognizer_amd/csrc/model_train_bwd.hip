@@ -102,6 +102,7 @@ struct Bwd {
     hipStream_t st, side;           // the caller's stream; the stream of the weight gradients
     bool two;                       // side is a stream of its own
     const sir_model_weights* w; const sir_model_grads* g; const sir_train_config* cfg;
+    const float* demb;              // d(loss)/d(ctx) [B][512] that enters beside dlogits fc_w (sir_model_train_bwd_emb), or NULL
     const float *feats, *dlogits, *y0in;      // y0in: what GRU layer 1 read (layer 0's output, behind the dropout if there is one)
     float* dfeats;                  // d(loss)/d(feats) [B][64][T], or NULL: not wanted
     float dropout_p; uint64_t dropout_seed;
@@ -139,11 +140,11 @@ int bwd_head(Bwd& c) {
     if (c.want.head) {
         SirProfScope prof(c.h, SIR_K_B_HEAD, c.st);
         hipLaunchKernelGGL(bwd_scale_kernel, dim3(c.row_scaled ? (B + 15) / 16 : 1), dim3(1024), 0, c.st, c.dlogits, B, C, sir_bwd_loss_scale_exp(B),
-                           c.row_scaled ? 1 : 0, c.p.bsc, c.ragged ? c.rg.sb : (const int*)nullptr);
+                           c.row_scaled ? 1 : 0, c.p.bsc, c.ragged ? c.rg.sb : (const int*)nullptr, c.demb);
         // (workgroups [B, B + 2 C) are the fc weight / bias gradient: left out when fc is frozen)
         hipLaunchKernelGGL(head_bwd_kernel, dim3(B + (c.want.fc ? 2 * C : 0)), dim3(256), 0, c.st, c.dlogits, c.w->fc_w, (const float*)c.p.y1, c.w->attn_w,
                            c.w->attn_b, (const float*)c.p.ctx, c.p.dy1, daw_part, dab_part, c.g->fc_w, c.g->fc_b, B, S, C, c.bsc, c.row_scaled ? 1 : 0,
-                           c.ragged ? c.rg.sb : (const int*)nullptr);
+                           c.ragged ? c.rg.sb : (const int*)nullptr, c.demb);
         if (c.want.attn)
             hipLaunchKernelGGL(head_colsum_kernel, dim3(9), dim3(256), 0, c.st, (const float*)daw_part, (const float*)dab_part, B, c.g->attn_w, c.g->attn_b);
     }
@@ -442,8 +443,9 @@ extern "C" int sir_model_train_bwd_cfg(sir_handle* h, const sir_model_weights* w
 }
 
 // frames == NULL: the padded step; else the ragged one (sir_model_train_bwd_ragged: every BatchNorm frozen, the caller has checked)
+// demb == NULL: no gradient enters at the embedding (the four entry points of before)
 static int train_bwd_impl(const char* who, sir_handle* h, const sir_model_weights* w, const float* feats, const int32_t* frames, const float* dlogits,
-                          int batch, int t_frames, float dropout_p, uint64_t dropout_seed,
+                          const float* demb, int batch, int t_frames, float dropout_p, uint64_t dropout_seed,
                           const sir_train_config* cfg, const sir_model_grads* g, float* dfeats, void* workspace,
                           size_t workspace_bytes, int part, void* stream_) {
     if (part != SIR_BWD_ALL && part != SIR_BWD_HEAD_GRU && part != SIR_BWD_CNN) {
@@ -455,6 +457,7 @@ static int train_bwd_impl(const char* who, sir_handle* h, const sir_model_weight
     int rc = check_common(who, h, w, batch, t_frames, workspace, workspace_bytes, &c.d, off);
     if (rc != SIR_OK) return rc;
     if (!feats || !dlogits || !g) { sir_set_error("%s: NULL argument", who); return SIR_EINVAL; }
+    if ((uintptr_t)demb & 15u) { sir_set_error("%s: demb must be 16-byte aligned", who); return SIR_EINVAL; }
     if (dfeats && (((uintptr_t)dfeats & 3) != 0 || dfeats == feats)) {
         sir_set_error("sir_model_train_bwd_x: dfeats must be a float buffer of its own");
         return SIR_EINVAL;
@@ -472,7 +475,7 @@ static int train_bwd_impl(const char* who, sir_handle* h, const sir_model_weight
         SIR_HIP_TRY(hipStreamCreateWithFlags(&h->bwd_side, hipStreamNonBlocking));
         for (auto& e : h->bwd_ev) SIR_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     }
-    c.h = h; c.w = w; c.g = g; c.cfg = cfg; c.feats = feats; c.dlogits = dlogits; c.dfeats = dfeats;
+    c.h = h; c.w = w; c.g = g; c.cfg = cfg; c.feats = feats; c.dlogits = dlogits; c.demb = demb; c.dfeats = dfeats;
     c.dropout_p = dropout_p; c.dropout_seed = dropout_seed;
     c.st = (hipStream_t)stream_;
     c.two = h->bwd_side != nullptr && h->prof_mode != 1;
@@ -517,7 +520,7 @@ extern "C" int sir_model_train_bwd_x(sir_handle* h, const sir_model_weights* w, 
                                      int batch, int t_frames, float dropout_p, uint64_t dropout_seed,
                                      const sir_train_config* cfg, const sir_model_grads* g, float* dfeats, void* workspace,
                                      size_t workspace_bytes, int part, void* stream_) {
-    return train_bwd_impl("sir_model_train_bwd", h, w, feats, nullptr, dlogits, batch, t_frames, dropout_p, dropout_seed, cfg ? cfg : &kTrainAllLive, g,
+    return train_bwd_impl("sir_model_train_bwd", h, w, feats, nullptr, dlogits, nullptr, batch, t_frames, dropout_p, dropout_seed, cfg ? cfg : &kTrainAllLive, g,
                           dfeats, workspace, workspace_bytes, part, stream_);
 }
 
@@ -531,6 +534,24 @@ extern "C" int sir_model_train_bwd_ragged(sir_handle* h, const sir_model_weights
         return SIR_EUNSUPPORTED;
     }
     if (!frames) { sir_set_error("sir_model_train_bwd_ragged: NULL frames"); return SIR_EINVAL; }
-    return train_bwd_impl("sir_model_train_bwd_ragged", h, w, feats, frames, dlogits, batch, t_frames, dropout_p, dropout_seed, cfg, g, dfeats,
+    return train_bwd_impl("sir_model_train_bwd_ragged", h, w, feats, frames, dlogits, nullptr, batch, t_frames, dropout_p, dropout_seed, cfg, g, dfeats,
+                          workspace, workspace_bytes, part, stream_);
+}
+
+// The superset of the forms above: frames == NULL is sir_model_train_bwd_x (cfg == NULL: every BatchNorm live), else
+// sir_model_train_bwd_ragged; demb == NULL is exactly that call.
+extern "C" int sir_model_train_bwd_emb(sir_handle* h, const sir_model_weights* w, const float* feats, const int32_t* frames,
+                                       const float* dlogits, const float* demb, int batch, int t_frames, float dropout_p,
+                                       uint64_t dropout_seed, const sir_train_config* cfg, const sir_model_grads* g, float* dfeats,
+                                       void* workspace, size_t workspace_bytes, int part, void* stream_) {
+    if (!frames)
+        return train_bwd_impl("sir_model_train_bwd_emb", h, w, feats, nullptr, dlogits, demb, batch, t_frames, dropout_p, dropout_seed,
+                              cfg ? cfg : &kTrainAllLive, g, dfeats, workspace, workspace_bytes, part, stream_);
+    if (!cfg || !cfg->bn_frozen[0] || !cfg->bn_frozen[1] || !cfg->bn_frozen[2]) {
+        sir_set_error("sir_model_train_bwd_emb: lengths (frames per clip) need every BatchNorm on its frozen running statistics "
+                      "(bn_frozen = {1, 1, 1}): with batch statistics a clip has no gradient of its own");
+        return SIR_EUNSUPPORTED;
+    }
+    return train_bwd_impl("sir_model_train_bwd_emb", h, w, feats, frames, dlogits, demb, batch, t_frames, dropout_p, dropout_seed, cfg, g, dfeats,
                           workspace, workspace_bytes, part, stream_);
 }

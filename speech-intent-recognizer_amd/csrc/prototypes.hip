@@ -5,7 +5,7 @@
 // the same way: ONE WAVE OWNS A ROW, lane l holds its elements 8 l .. 8 l + 7 (two 16-byte loads).  A row's sum of squares is
 // formed in double -- the lane's eight squares in element order, then the xor butterfly over the 64 lanes (32, 16, ... 1: every
 // lane ends with the same bits) -- so it depends on nothing but the row, and so does the unit vector e / sqrt(sumsq), the quotient
-// taken in double.  sir_proto_accumulate and sir_proto_score share that code (row_norm, unit_elem).
+// taken in double.  sir_proto_accumulate and sir_proto_score share that code (row_norm, unit_elem: unit_rows.h).
 //
 // The bank (caller-owned device state): a 64-byte header {int32 n_classes, int32 0, int64 skipped}, int64 count[P], double
 // sum[P][512].  sir_proto_accumulate runs one wave per CLASS: the wave walks the labels of the batch in row order (64 labels per
@@ -29,13 +29,12 @@
 #include <cmath>
 #include <climits>
 #include "sir_internal.h"
-#include "row_softmax.h"   // is_nonfinite, kMaxRows
+#include "row_softmax.h"   // kMaxRows
+#include "unit_rows.h"     // kDim, kMaxProtos, load_row8, row_norm, unit_elem, wave_sum_f64
 #include "wave_fft.h"      // wave_fence
 
 namespace {
 
-constexpr int kDim = 512;                            // floats of an embedding
-constexpr int kMaxProtos = 4096;
 constexpr int kHeaderBytes = 64;
 constexpr int kScoreWaves = 16;                      // its waves: at the largest bank one workgroup fills a CU's LDS, and the loads
 constexpr int kScoreDepth = 4;                       // in flight are all that hides the latency: 16 waves x 4 prototype rows = 128 KB
@@ -48,38 +47,6 @@ struct ProtoHeader { int n_classes, zero; long long skipped; };
 inline size_t state_bytes_of(int P) { return (size_t)kHeaderBytes + (size_t)P * 8 + (size_t)P * kDim * 8; }
 __host__ __device__ inline long long* state_count(void* state) { return (long long*)((char*)state + kHeaderBytes); }
 __host__ __device__ inline double* state_sum(void* state, int P) { return (double*)((char*)state + kHeaderBytes + (size_t)P * 8); }
-
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// the lane's eight elements of a 512-float row (16-byte aligned)
-__device__ __forceinline__ void load_row8(const float* __restrict__ row, int lane, float (&e)[8]) {
-    const float4 a = reinterpret_cast<const float4*>(row)[2 * lane], b = reinterpret_cast<const float4*>(row)[2 * lane + 1];
-    e[0] = a.x; e[1] = a.y; e[2] = a.z; e[3] = a.w; e[4] = b.x; e[5] = b.y; e[6] = b.z; e[7] = b.w;
-}
-
-// One row in one wave: false (wave-uniform) for a row with a NaN or an infinity or with norm zero; else norm = ||e|| in double.
-// The sum of squares: the lane's eight squares in element order, then the butterfly -- a function of the row alone.
-__device__ __forceinline__ bool row_norm(const float (&e)[8], double& norm) {
-#pragma clang fp contract(off)
-    bool bad = false;
-    double ss = 0.0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        bad = bad || is_nonfinite(e[i]);
-        const double x = (double)e[i];
-        ss += x * x;
-    }
-    ss = wave_sum_f64(ss);
-    const bool ok = __ballot(bad) == 0ull && ss > 0.0;
-    norm = ok ? sqrt(ss) : 1.0;
-    return ok;
-}
-// element i of the unit vector, in double: e / ||e|| as e * (1 / ||e||) would round twice -- the quotient is taken directly
-__device__ __forceinline__ double unit_elem(float e, double norm) { return (double)e / norm; }
 
 // ---- the bank -------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void proto_reset_kernel(void* state, int P, const uint8_t* __restrict__ mask) {

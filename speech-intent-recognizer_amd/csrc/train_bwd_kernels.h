@@ -14,8 +14,22 @@
 //   per_row == 0: one workgroup, pair 0 from the maximum over all of dlogits (pairs 1.. are not written).
 //   per_row != 0: one wave per utterance (16 per workgroup), pair 1 + b from the maximum of row b alone -- for the data-only
 //   backward under frozen statistics, where utterance b's gradients depend on row b of dlogits and nothing else; pair 0 = static.
+//   demb (sir_model_train_bwd_emb; else NULL, and the pairs are bit for bit those of the maximum over dlogits alone): the gradient
+//   that enters at the embedding is counted as a dlogits of |demb| * 2^BSC_EMB_Q.  head_bwd_utt adds demb to dctx = dlogits fc_w,
+//   and at the reference head's initialisation (fc_w uniform within +-512^-1/2 = 2^-4.5) max |dctx| is about max |dlogits| * 2^-4.5:
+//   the one large entry of a row of softmax - onehot times the largest weights of its class.  A demb of magnitude m therefore
+//   loads the contractions behind the head like a dlogits of m * 2^4.5; the exponent is rounded up to 5, to the side that scales
+//   down (the window [BSC_X_LO, BSC_X_HI] has two binades of room either way).  With dlogits all zero the scale follows demb alone.
+//   per_row: row b's maximum is over row b of both arrays.  A non-finite demb, like a non-finite dlogits, keeps the static scale.
 // ------------------------------------------------------------------------------------------
 constexpr int BSC_X_LO = 6, BSC_X_HI = 10;
+constexpr int BSC_EMB_Q = 5;
+// |v| * 2^BSC_EMB_Q as the bits the maximum is taken over (fp32 product: infinity and NaN stay what they are, an overflow becomes
+// infinity and keeps the static scale)
+__device__ __forceinline__ unsigned bwd_scale_emb_bits(float v) { return __float_as_uint(v * (float)(1 << BSC_EMB_Q)) & 0x7fffffffu; }
+__device__ __forceinline__ unsigned bwd_scale_emb_bits4(const float4 v) {
+    return max(max(bwd_scale_emb_bits(v.x), bwd_scale_emb_bits(v.y)), max(bwd_scale_emb_bits(v.z), bwd_scale_emb_bits(v.w)));
+}
 __device__ __forceinline__ void bwd_scale_pair(unsigned maxbits, int static_exp, float* __restrict__ out) {
     const int e = (int)(maxbits >> 23);                       // biased exponent (the sign bit is already cleared)
     int g = static_exp;
@@ -28,13 +42,17 @@ __device__ __forceinline__ void bwd_scale_pair(unsigned maxbits, int static_exp,
 }
 //   slen (ragged step; else NULL): a row whose clip has slen[b] < 1 steps counts as a row of zeros (its dlogits are not looked at).
 static __global__ __launch_bounds__(1024) void bwd_scale_kernel(const float* __restrict__ dlogits, int B, int C, int static_exp, int per_row,
-                                                                float* __restrict__ bsc, const int* __restrict__ slen) {
+                                                                float* __restrict__ bsc, const int* __restrict__ slen, const float* __restrict__ demb) {
     __shared__ unsigned red[16];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     if (per_row) {
         const int b = blockIdx.x * 16 + wv;
         if (b < B) {
             unsigned v = lane < C && !(slen && slen[b] < 1) ? (__float_as_uint(dlogits[(size_t)b * C + lane]) & 0x7fffffffu) : 0u;
+            if (demb && !(slen && slen[b] < 1)) {                 // (wave-uniform) the lane's eight elements of row b: two 16-byte loads
+                const float4* r = reinterpret_cast<const float4*>(demb + (size_t)b * 512) + 2 * lane;
+                v = max(v, max(bwd_scale_emb_bits4(r[0]), bwd_scale_emb_bits4(r[1])));
+            }
 #pragma unroll
             for (int o = 32; o > 0; o >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, o));
             if (lane == 0) bwd_scale_pair(v, static_exp, bsc + 2 * (1 + b));
@@ -50,6 +68,11 @@ static __global__ __launch_bounds__(1024) void bwd_scale_kernel(const float* __r
     } else {
         for (size_t i = tid; i < n; i += 1024) m = max(m, __float_as_uint(dlogits[i]) & 0x7fffffffu);
     }
+    if (demb) {                                                   // 128 float4 per row; a clip without steps (ragged) is not looked at
+        const size_t n4 = (size_t)B * 128;
+        for (size_t i = tid; i < n4; i += 1024)
+            if (!(slen && slen[i >> 7] < 1)) m = max(m, bwd_scale_emb_bits4(reinterpret_cast<const float4*>(demb)[i]));
+    }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
     if (lane == 0) red[wv] = m;
@@ -62,7 +85,8 @@ static __global__ __launch_bounds__(1024) void bwd_scale_kernel(const float* __r
 
 // ------------------------------------------------------------------------------------------
 // head backward: fc + attention pooling (models.py:63-67)
-//   dctx = dlogits fc_w;  w = softmax_t(y a + b);  dw_t = <dctx, y_t>;  ds_t = w_t (dw_t - sum w dw)
+//   dctx = dlogits fc_w (+ demb, the gradient that enters at the embedding: sir_model_train_bwd_emb)
+//   w = softmax_t(y a + b);  dw_t = <dctx, y_t>;  ds_t = w_t (dw_t - sum w dw)
 //   dy_t = w_t dctx + ds_t a;  per-utterance partials of d attention.weight / d attention.bias
 // one workgroup per utterance
 // ------------------------------------------------------------------------------------------
@@ -70,7 +94,7 @@ __device__ __forceinline__ void head_bwd_utt(int b, const float* __restrict__ dl
                                              const float* __restrict__ y, const float* __restrict__ aw,
                                              const float* __restrict__ ab, float* __restrict__ dy,
                                              float* __restrict__ daw_part, float* __restrict__ dab_part,
-                                             int S, int C, float gscale, int Sl) {
+                                             int S, int C, float gscale, int Sl, const float* __restrict__ demb) {
     // Sl <= S: the utterance's own steps (ragged step; S otherwise) -- scores, softmax and sums over t < Sl, dy rows t >= Sl are zeros
     __shared__ float dctx[512];
     __shared__ float sc[ATT_MAX_S], ds[ATT_MAX_S];
@@ -87,6 +111,7 @@ __device__ __forceinline__ void head_bwd_utt(int b, const float* __restrict__ dl
     for (int c = tid; c < 512; c += 256) {
         float a = 0.0f;
         for (int j = 0; j < C; ++j) a = fmaf(dlogits[(size_t)b * C + j], fcw[(size_t)j * 512 + c], a);
+        if (demb) a += demb[(size_t)b * 512 + c];                 // (workgroup-uniform; NULL: the statements of before, the same bits)
         dctx[c] = a;
     }
     float a8[8];
@@ -270,7 +295,7 @@ static __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __res
                                                               float* __restrict__ dy, float* __restrict__ daw_part,
                                                               float* __restrict__ dab_part, float* __restrict__ d_fc_w,
                                                               float* __restrict__ d_fc_b, int B, int S, int C, const float* __restrict__ bsc, int row_scaled,
-                                                              const int* __restrict__ slen) {
+                                                              const int* __restrict__ slen, const float* __restrict__ demb) {
     // slen (ragged step, sir_model_train_bwd_ragged; else NULL): utterance b has slen[b] <= S steps of its own
     if ((int)blockIdx.x >= B) {
         const int i = blockIdx.x - B;
@@ -278,7 +303,7 @@ static __global__ __launch_bounds__(256) void head_bwd_kernel(const float* __res
         return;
     }
     head_bwd_utt(blockIdx.x, dlogits, fcw, y, aw, ab, dy, daw_part, dab_part, S, C, bsc[row_scaled ? 2 * (1 + blockIdx.x) : 0],
-                 slen ? max(0, min(S, slen[blockIdx.x])) : S);
+                 slen ? max(0, min(S, slen[blockIdx.x])) : S, demb);
 }
 
 // Reads two buffers and keeps nothing: a software prefetch into the last-level cache, launched on the backward's side stream (model_train_bwd.hip:

@@ -209,6 +209,8 @@ static inline int check_common(const char* who, sir_handle* h, const sir_model_w
 // maximum stays within [2^5, 2^10), else the power of two that brings it back to [2^7, 2^8) -- any finite dlogits, 2^-24 or 2^16
 // times the usual, gives the same relative accuracy (tests/test_operand_range_gpu.py).  Results are bit-identical to the unscaled
 // backward wherever the arithmetic is fp32 or bf16x6 (scaling by 2^k commutes with every rounding there).
+// A gradient that enters at the embedding (sir_model_train_bwd_emb) takes part in that maximum as |demb| * 2^5: it is added to
+// dctx = dlogits fc_w, which at the reference head's initialisation is about |dlogits| * 2^-4.5 (bwd_scale_kernel has the reason).
 inline int sir_bwd_loss_scale_exp(int batch) {
     int k = 8;
     while ((1 << (k - 8)) < batch && k < 24) ++k;

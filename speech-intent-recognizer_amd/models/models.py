@@ -119,6 +119,18 @@ class CNNAudioGRU(nn.Module):
         scores these rows."""
         return ops.model_embed(self, x, self._ws, lengths=lengths)
 
+    def forward_with_embedding(self, x, lengths=None):
+        """``(logits [B, num_classes], emb [B, 512])`` in one pass, dispatched as ``forward`` is.  On the differentiable path
+        (``self.training and torch.is_grad_enabled()``) both carry a graph (``train_ops.forward_train_embed``): a loss on ``emb``
+        -- ``sir_amd.prototypes.ProxyHead`` -- trains the embedding that ``PrototypeBank`` enrols from, alone or beside the
+        cross-entropy on ``logits``.  Otherwise the two are ``model(x)``'s logits and ``embed``'s rows, bit for bit."""
+        if self.training and torch.is_grad_enabled():
+            from sir_amd import train_ops
+            return train_ops.forward_train_embed(self, x, lengths=lengths)
+        with torch.no_grad():
+            emb, logits, _ = ops.model_embed(self, x, self._ws, lengths=lengths, want_logits=True)
+        return logits, emb
+
     @torch.no_grad()
     def classify(self, x, lengths=None, k=3, inv_temperature=None):
         """The forward plus ``ops.classify`` on the device -> ``(logits [B, C], topk_idx int32 [B, k], topk_prob [B, k])``: the

@@ -270,6 +270,18 @@ class PrototypeBank:
                      **extra)
 
     @classmethod
+    def from_proxies(cls, head):
+        """A mean bank of a trained ``ProxyHead``: one class per proxy, count 1, its sum the unit proxy (normalised in float64),
+        so ``score`` ranks against the centres the loss trained.  No device call; rows of norm zero or not finite stay empty."""
+        bank = cls(head.names)
+        p = head.proxies.detach().to("cpu", torch.float64).numpy()
+        norm = np.sqrt((p * p).sum(axis=1))
+        ok = np.isfinite(p).all(axis=1) & (norm > 0.0)
+        bank._host = {"sum": np.where(ok[:, None], p / np.where(ok, norm, 1.0)[:, None], 0.0),
+                      "count": ok.astype(np.int64), "skipped": 0}
+        return bank
+
+    @classmethod
     def load(cls, path):
         """A saved bank; enrolling into it continues to the bits of an uninterrupted enrolment."""
         with np.load(path, allow_pickle=False) as z:
@@ -308,3 +320,86 @@ def fit_scale(bank, embeddings, labels, iters=20):
                                        _native.current_stream_ptr())
     _native.check(rc, "sir_proto_score")
     return metrics.fit_temperature(sims, labels, iters=iters)
+
+
+class _ProxyLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, emb, proxies, labels, scale, margin, head):
+        lib = _native.lib()
+        _native.require_hip(emb, proxies, labels)
+        if proxies.dim() != 2 or proxies.shape[1] != DIM or proxies.dtype != torch.float32 or not 1 <= proxies.shape[0] <= MAX_PROTOTYPES:
+            raise _native.SirError(f"proxies must be float32 [1..{MAX_PROTOTYPES}, {DIM}], got {tuple(proxies.shape)} {proxies.dtype}")
+        emb, proxies = _emb2d(emb), proxies.contiguous()
+        labels = labels.to(torch.int64).contiguous()
+        bsz, n = emb.shape[0], proxies.shape[0]
+        if labels.dim() != 1 or labels.numel() != bsz:
+            raise _native.SirError(f"{labels.numel()} labels for {bsz} embeddings")
+        need = lib.sir_proxy_loss_workspace_bytes(bsz, n)
+        ws = head._workspace(need, emb.device)
+        loss = torch.empty((), dtype=torch.float32, device=emb.device)
+        demb = torch.empty_like(emb) if ctx.needs_input_grad[0] else None
+        dprox = torch.empty_like(proxies) if ctx.needs_input_grad[1] else None
+        rc = lib.sir_proxy_loss(get_featurizer().handle, emb.data_ptr(), proxies.data_ptr(), labels.data_ptr(), bsz, n, float(scale),
+                                float(margin), loss.data_ptr(), demb.data_ptr() if demb is not None else None,
+                                dprox.data_ptr() if dprox is not None else None, 1.0, ws.data_ptr(), ws.numel(),
+                                _native.current_stream_ptr())
+        _native.check(rc, "sir_proxy_loss")
+        ctx.demb, ctx.dprox = demb, dprox
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        # loss.backward() passes 1.0; a general scalar (a loss weight) is applied by the two multiplies below
+        return (ctx.demb * grad_out if ctx.demb is not None else None, ctx.dprox * grad_out if ctx.dprox is not None else None,
+                None, None, None, None)
+
+
+class ProxyHead(torch.nn.Module):
+    """The cosine-proxy loss on the embeddings (``sir_proxy_loss``): one learned centre per class, ``proxies`` float32
+    ``[n_classes, 512]`` (normal init from ``seed``; they need not stay unit), and ``head(emb, labels)`` = the mean over the
+    labelled rows of ``-log softmax(scale * (cos(emb, proxy_k) - margin * [k == label]))[label]`` -- normalised softmax with
+    ``margin == 0``, AM-softmax / CosFace with a margin.  Labels as for ``fused_cross_entropy`` (-100 ignores a row).  Both
+    gradients are written in the forward, as ``fused_cross_entropy`` writes its own.  ``emb`` is
+    ``model.forward_with_embedding(x)[1]``; ``PrototypeBank.from_proxies(head)`` turns the trained centres into a bank."""
+
+    def __init__(self, n_classes, names=None, scale=16.0, margin=0.0, seed=0):
+        super().__init__()
+        n_classes = int(n_classes)
+        if not 1 <= n_classes <= MAX_PROTOTYPES:
+            raise ValueError(f"n_classes={n_classes} outside [1, {MAX_PROTOTYPES}]")
+        scale, margin = float(scale), float(margin)
+        if not (scale > 0.0 and np.isfinite(scale)):
+            raise ValueError("scale must be positive and finite")
+        if not (margin >= 0.0 and np.isfinite(margin)):
+            raise ValueError("margin must be finite and >= 0")
+        names = [f"class_{i}" for i in range(n_classes)] if names is None else [str(n) for n in names]
+        if len(names) != n_classes or len(set(names)) != n_classes or any(not n for n in names):
+            raise ValueError(f"names must be {n_classes} distinct non-empty strings")
+        self.names, self.scale, self.margin = names, scale, margin
+        gen = torch.Generator().manual_seed(int(seed))
+        self.proxies = torch.nn.Parameter(torch.randn(n_classes, DIM, generator=gen, dtype=torch.float32))
+        self._ws = None
+
+    def _workspace(self, nbytes, device):
+        if self._ws is None or self._ws.numel() < nbytes or self._ws.device != device:
+            self._ws = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+        return self._ws
+
+    def forward(self, emb, labels):
+        return _ProxyLoss.apply(emb, self.proxies, labels, self.scale, self.margin, self)
+
+    @torch.no_grad()
+    def init_from_bank(self, bank):
+        """Start the centres from an enrolled mean bank: row c = the unit mean of class c (float64 on the host, no device
+        call); the bank must name the head's classes in order and have every one enrolled.  -> self."""
+        if bank.exemplars:
+            raise ValueError("init_from_bank takes a mean bank (exemplars=False)")
+        if list(bank.names) != list(self.names):
+            raise ValueError("the bank's names are not the head's")
+        a = bank.state_arrays()
+        norm = np.sqrt((a["sum"] ** 2).sum(axis=1))
+        if not ((a["count"] > 0) & np.isfinite(norm) & (norm > 0.0)).all():
+            raise ValueError("init_from_bank needs every class of the bank enrolled")
+        unit = torch.from_numpy((a["sum"] / norm[:, None]).astype(np.float32))
+        self.proxies.copy_(unit.to(self.proxies.device))
+        return self

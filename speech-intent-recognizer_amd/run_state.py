@@ -92,6 +92,33 @@ def save_run_state(path, model, optimizer, scheduler=None, mixup=None, epoch=0, 
     return path
 
 
+PROXY_HEAD = "proxy_head.pt"
+
+
+def save_proxy_head(directory, head):
+    """The ``metric_loss`` head of a run (``prototypes.ProxyHead``) as ``directory/proxy_head.pt``: proxies, names, scale and
+    margin -- data only, written beside the target and renamed over it like the run state.  ``best_model.pt`` keeps the
+    reference's bare format; the proxies' optimizer state travels in the run state (they are its second parameter group)."""
+    path = os.path.join(os.fspath(directory), PROXY_HEAD)
+    tmp = path + ".tmp"
+    torch.save({"proxies": head.proxies.detach().cpu(), "names": list(head.names), "scale": float(head.scale),
+                "margin": float(head.margin)}, tmp)
+    os.replace(tmp, path)
+    return path
+
+
+def load_proxy_head(directory, head):
+    """Restore ``save_proxy_head``'s file into ``head`` (same class count; the resuming config's scale and margin are kept)."""
+    path = os.path.join(os.fspath(directory), PROXY_HEAD)
+    state = torch.load(path, map_location="cpu", weights_only=True)
+    if tuple(state["proxies"].shape) != tuple(head.proxies.shape):
+        raise ValueError(f"{path} holds proxies {tuple(state['proxies'].shape)}, the run's head {tuple(head.proxies.shape)}")
+    with torch.no_grad():
+        head.proxies.copy_(state["proxies"].to(head.proxies.device))
+    head.names = [str(n) for n in state["names"]]
+    return head
+
+
 def load_run_state(path, model, optimizer, scheduler=None, mixup=None, config=None, rank=None, world=None, map_location=None,
                    adversary=None):
     """Put a saved run state back into fresh objects; every rank calls it and takes its own per-rank entry.  Returns

@@ -127,6 +127,7 @@ def train_epoch(model, train_loader, optimizer, criterion, device, scaler=None, 
     crafting leaves the module untouched and holds no collective, so an empty-shard rank simply skips it."""
     from sir_amd import ops, train_ops
     adversary = train_ops.adversary_of(model)
+    metric = train_ops.metric_loss_of(model)            # (`metric_loss`: never together with mixup or an adversary, train() refuses that)
     model.train()
     loss_fn = _loss_fn(criterion)
     losses = []
@@ -139,6 +140,8 @@ def train_epoch(model, train_loader, optimizer, criterion, device, scaler=None, 
                 # the same update (a bare `continue`, train.py:82-83, would leave them waiting for ever)
                 optimizer.zero_grad(set_to_none=True)
                 train_ops.zero_contribution_step(model)
+                if metric is not None:
+                    metric.zero_contribution()
                 optimizer.step()
             continue
         mel = stage(mel)                                   # host batches: persistent pinned ring (see HostStager)
@@ -152,9 +155,14 @@ def train_epoch(model, train_loader, optimizer, criterion, device, scaler=None, 
         else:
             if adversary is not None:
                 mel = adversary(model, mel, lambda out: loss_fn(out, label))
-            output = model(mel)
-            loss = loss_fn(output, label)
+            if metric is not None:
+                loss = metric.loss(model, mel, label, loss_fn)
+            else:
+                output = model(mel)
+                loss = loss_fn(output, label)
         loss.backward()
+        if metric is not None:
+            metric.sync_grad()
         optimizer.step()
         losses.append(loss.detach())
         if batch_idx % 10 == 0 and not _quiet():
@@ -183,6 +191,7 @@ def train_epoch_waveforms(model, wave_loader, optimizer, criterion, device, t_pa
     from sir_amd import ops, train_ops
     from sir_amd.pipeline import FeaturePrefetcher
     adversary = train_ops.adversary_of(model)
+    metric = train_ops.metric_loss_of(model)
     model.train()
     loss_fn = _loss_fn(criterion)
     pre = FeaturePrefetcher(t_pad=t_pad, frontend=frontend)
@@ -210,8 +219,10 @@ def train_epoch_waveforms(model, wave_loader, optimizer, criterion, device, t_pa
         else:
             if adversary is not None:                   # (a new tensor: the prefetcher's buffer is read, never written)
                 mel = adversary(model, mel, lambda out: loss_fn(out, label))
-            loss = loss_fn(model(mel), label)
+            loss = metric.loss(model, mel, label, loss_fn) if metric is not None else loss_fn(model(mel), label)
         loss.backward()
+        if metric is not None:
+            metric.sync_grad()
         optimizer.step()
         pre.release()
         losses.append(loss.detach())
@@ -395,6 +406,39 @@ def adversarial_options(config):
             "validate": bool(spec.get("validate", False))}
 
 
+def metric_loss_options(config):
+    """The ``metric_loss`` YAML key of ``train()`` -- ``{weight, ce_weight, scale, margin, bank_out}``, absent by default -- on the
+    host, before any device call: None, or the five values with their defaults (weight 1, ce_weight 1, scale 16, margin 0.1,
+    bank_out None).  The step's loss becomes ``ce_weight * CE(logits) + weight * ProxyHead(emb, labels)`` (DESIGN.md section 4,
+    "Training the embedding").  ``ValueError`` for unknown keys, a negative weight, ``scale <= 0``, ``margin < 0``, both weights
+    zero, and for ``metric_loss`` together with ``mixup``, ``adversarial`` or ``slots``: a proxy loss needs one hard label per
+    clip and its own crafting loss, which is out of scope."""
+    spec = config.get("metric_loss")
+    if spec is None or spec is False:
+        return None
+    if not isinstance(spec, dict):
+        raise ValueError("metric_loss: expected a mapping {weight, ce_weight, scale, margin, bank_out}")
+    unknown = set(spec) - {"weight", "ce_weight", "scale", "margin", "bank_out"}
+    if unknown:
+        raise ValueError(f"metric_loss: unknown keys {sorted(unknown)}")
+    for other in ("mixup", "adversarial", "slots"):
+        if config.get(other):
+            raise ValueError(f"metric_loss cannot be combined with {other}: the proxy loss takes one hard label per clip")
+    out = {"weight": float(spec.get("weight", 1.0)), "ce_weight": float(spec.get("ce_weight", 1.0)),
+           "scale": float(spec.get("scale", 16.0)), "margin": float(spec.get("margin", 0.1)), "bank_out": spec.get("bank_out")}
+    if not out["weight"] >= 0.0 or not out["ce_weight"] >= 0.0:
+        raise ValueError("metric_loss: weight and ce_weight must be >= 0")
+    if out["weight"] == 0.0 and out["ce_weight"] == 0.0:
+        raise ValueError("metric_loss: weight and ce_weight are both zero: nothing would be trained")
+    if not (out["scale"] > 0.0 and out["scale"] < float("inf")):
+        raise ValueError("metric_loss: scale must be positive and finite")
+    if not (out["margin"] >= 0.0 and out["margin"] < float("inf")):
+        raise ValueError("metric_loss: margin must be finite and >= 0")
+    if out["bank_out"] is not None and (not isinstance(out["bank_out"], str) or not out["bank_out"]):
+        raise ValueError("metric_loss: bank_out is a file name")
+    return out
+
+
 def validate_robust(model, val_loader, device, eps, **pgd_kw):
     """Robust validation accuracy: the share of the loader's clips still classified correctly after ``explain.pgd`` (eval
     semantics; all-zero padding columns kept) at radius ``eps``; under data parallelism the counts are summed over ranks."""
@@ -518,6 +562,7 @@ def train(args, config):
     from sir_amd.scripts.dataset import FSCIntentDataset
 
     adv_opts = adversarial_options(config)            # (a bad `adversarial` key raises here, before any device call)
+    metric_opts = metric_loss_options(config)         # (and a bad `metric_loss` key, or one beside mixup / adversarial / slots)
     # `slots: {columns, map, weights}` (absent by default): slot heads -- the label of a clip is one class per CSV column, the
     # loss a weighted sum of per-segment cross-entropies, the validation accuracy the exact-match rate (sir_amd/slots.py,
     # DESIGN.md section 4).  A layout that does not add up to `num_labels` raises here, before any device call.
@@ -620,7 +665,21 @@ def train(args, config):
         adversary = train_ops.Adversary(adv_opts["eps"], alpha=adv_opts["alpha"], steps=adv_opts["steps"],
                                         random_start=adv_opts["random_start"], prob=adv_opts["prob"], seed=seed + 1231 * rank)
     train_ops.set_adversary(model, adversary)         # rides on the model: train_epoch / train_epoch_waveforms keep their signatures
-    optimizer = FusedAdam([p for p in model.parameters() if p.requires_grad], lr=float(config.get("lr", 0.0003)),
+    # `metric_loss: {weight, ce_weight, scale, margin, bank_out}` (absent by default): a cosine-proxy loss on the embedding beside
+    # the cross-entropy (prototypes.ProxyHead, DESIGN.md section 4 "Training the embedding").  The proxies are a second parameter
+    # group; their state goes to `proxy_head.pt` beside every checkpoint and, as a PrototypeBank, to `bank_out` at the end.
+    metric = None
+    if metric_opts:
+        from sir_amd.prototypes import ProxyHead
+        head = ProxyHead(int(config.get("num_labels", 31)), scale=metric_opts["scale"], margin=metric_opts["margin"], seed=seed).to(device)
+        if opts["resume_path"]:
+            run_state.load_proxy_head(os.path.dirname(os.path.abspath(opts["resume_path"])), head)
+        train_ops.broadcast_module_(head)
+        metric = train_ops.MetricLoss(head, metric_opts["weight"], metric_opts["ce_weight"])
+    train_ops.set_metric_loss(model, metric)
+    trainable = [p for p in model.parameters() if p.requires_grad]
+    optimizer = FusedAdam(trainable if metric is None else [{"params": trainable}, {"params": [metric.head.proxies]}],
+                          lr=float(config.get("lr", 0.0003)),
                           weight_decay=float(config.get("weight_decay", 0.0001)),
                           max_grad_norm=float(config["clip_grad_norm"]) if config.get("clip_grad_norm") else None,
                           decoupled_weight_decay=opts["decoupled_weight_decay"], ema_decay=opts["ema_decay"],
@@ -698,10 +757,20 @@ def train(args, config):
             run_state.save_run_state(opts["checkpoint_path"], model, optimizer, scheduler, mixup, epoch=epoch,
                                      best_val_acc=best_val_acc, no_improve_count=no_improve_count, config=config,
                                      adversary=adversary)
+            if metric is not None and rank == 0:
+                run_state.save_proxy_head(os.path.dirname(os.path.abspath(opts["checkpoint_path"])), metric.head)
         if no_improve_count >= patience:
             if rank == 0:
                 print(f"Early stopping after {epoch + 1} epochs")
             break
+    if metric is not None and rank == 0:
+        from sir_amd.prototypes import PrototypeBank
+        save_path = config.get("save_path", "checkpoints/")
+        os.makedirs(save_path, exist_ok=True)
+        run_state.save_proxy_head(save_path, metric.head)
+        if metric_opts["bank_out"]:
+            bank_out = metric_opts["bank_out"]
+            PrototypeBank.from_proxies(metric.head).save(bank_out if os.path.isabs(bank_out) else os.path.join(save_path, bank_out))
     if rank == 0:
         print(f"Training completed. Best validation accuracy: {best_val_acc:.4f}")
     train_ops.shutdown_distributed()

@@ -6,6 +6,8 @@ autograd the 29 parameter gradients as views of ONE flat fp32 buffer (3 261 184 
 views are returned, so the update equals single-GPU training on the global batch.
 If ``x.requires_grad`` the backward also returns ``d loss / d x`` (``sir_model_train_bwd_x``: the
 data chain runs down through conv1); it is rank-local and is not exchanged.
+``forward_train_embed`` also returns the 512-float utterance embedding with a graph attached: a loss on it
+(``prototypes.ProxyHead``) enters the backward beside ``dlogits`` (``sir_model_train_bwd_emb``).
 ``fused_cross_entropy`` is the HIP form of the reference's ``nn.CrossEntropyLoss()`` (train.py:242).
 Only pointers move through Python; no arithmetic of the step is done by torch ops.
 """
@@ -254,18 +256,30 @@ class _TrainStep(torch.autograd.Function):
             torch._foreach_add_(live, 1)
         ctx.mod, ctx.x, ctx.seed, ctx.dropout_p, ctx.ws, ctx.cfg = mod, x, seed, float(dropout_p), ws, cfg
         ctx.x_shape, ctx.frames = x_shape, frames
+        if len(opts) > 5 and opts[5]:
+            # want_emb (``forward_train_embed``): the attention-pooled context the forward left in workspace slot 11, copied on the
+            # stream -- the next step reuses the workspace, a view would dangle.  A gradient that is not there stays None.
+            ctx.set_materialize_grads(False)
+            at = _train_offsets(h, bsz, t)[11]
+            return logits, ws[at: at + 4 * bsz * 512].view(torch.float32).view(bsz, 512).clone()
         return logits
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, dlogits):
+    def backward(ctx, dlogits, demb=None):
         lib = _native.lib()
         mod, x = ctx.mod, ctx.x
         h = get_featurizer().handle
         w, keep = ops.cached_weights(mod)
         st = _train_state(mod)
-        dlogits = dlogits.contiguous()
         bsz, _, t = x.shape
+        if dlogits is None:                          # (the two-output node with no loss on the logits: dlogits stays required)
+            if demb is None:
+                return (None, None, None) + (None,) * len(param_list(mod))
+            dlogits = torch.zeros((bsz, w.num_classes), dtype=torch.float32, device=x.device)
+        dlogits = dlogits.contiguous()
+        if demb is not None:
+            demb = demb.to(torch.float32).contiguous()
         grads = st["grads"]
         params = param_list(mod)
         need = ctx.needs_input_grad[3:]
@@ -273,6 +287,12 @@ class _TrainStep(torch.autograd.Function):
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
 
         def run(part):
+            if demb is not None:
+                rc = lib.sir_model_train_bwd_emb(h, C.byref(w), x.data_ptr(), ctx.frames.data_ptr() if ctx.frames is not None else None,
+                                                 dlogits.data_ptr(), demb.data_ptr(), bsz, t, ctx.dropout_p, ctx.seed, C.byref(ctx.cfg),
+                                                 C.byref(gstruct), dx.data_ptr() if dx is not None else None, ctx.ws.data_ptr(),
+                                                 ctx.ws.numel(), part, _native.current_stream_ptr())
+                return _native.check(rc, "sir_model_train_bwd_emb")
             if ctx.frames is not None:
                 rc = lib.sir_model_train_bwd_ragged(h, C.byref(w), x.data_ptr(), ctx.frames.data_ptr(), dlogits.data_ptr(), bsz, t,
                                                     ctx.dropout_p, ctx.seed, C.byref(ctx.cfg), C.byref(gstruct),
@@ -315,6 +335,20 @@ class _TrainStep(torch.autograd.Function):
                     p.grad = v
             return (dx, None, None) + (None,) * len(params)
         return (dx, None, None) + tuple(v if n else None for v, n in zip(grads.views, need))
+
+
+_offsets = {}
+
+
+def _train_offsets(h, bsz, t):
+    """Byte offsets of the training workspace's slots (``sir_model_train_workspace_offsets``), kept per shape."""
+    offs = _offsets.get((bsz, t))
+    if offs is None:
+        buf = (C.c_size_t * 48)()
+        if _native.lib().sir_model_train_workspace_offsets(h, bsz, t, buf, 48) <= 11:
+            raise _native.SirError("sir_model_train_workspace_offsets failed")
+        offs = _offsets[(bsz, t)] = list(buf)
+    return offs
 
 
 def _exchange_and_scale(grads, run, cnn=True, dx=False):
@@ -398,6 +432,22 @@ def forward_train(mod, x, lengths=None):
     return _TrainStep.apply(x, mod, (cfg, dropout_p, True, False, ragged_frames(lengths, x)), *param_list(mod))
 
 
+def forward_train_embed(mod, x, lengths=None):
+    """``forward_train`` with a second output: ``(logits, emb)``, ``emb`` float32 ``[B, 512]`` the attention-pooled context that
+    ``model.embed`` returns in eval, here with the graph attached.  A loss may be put on either or both: the backward hands
+    ``(dlogits, demb)`` to ``sir_model_train_bwd_emb``, which adds ``demb`` to the ``dctx`` it forms from ``dlogits`` (zeros when
+    only the embedding carries a loss) -- same freeze / pruning rules, flat gradient buffer and data-parallel exchange as
+    ``forward_train``.  With no gradient on ``emb`` the step is ``forward_train``'s, bit for bit."""
+    cfg, dropout_p = step_config(mod)
+    if lengths is not None and not all(cfg.bn_frozen):
+        raise _native.SirError("lengths (un-padded clips) on the differentiable path need bn1, bn2 and bn3 on their running statistics: "
+                               "freeze them first (finetune.freeze(model, {'bn_stats'}) or bnK.eval())")
+    _native.require_hip(x)
+    ops._as_features(x)
+    frames = ragged_frames(lengths, x) if lengths is not None else None
+    return _TrainStep.apply(x, mod, (cfg, dropout_p, True, False, frames, True), *param_list(mod))
+
+
 def forward_craft(mod, x):
     """``(logits, leaf)`` of the crafting pass of an adversary: the training-path forward with the module's own flags
     (``bnK.eval()`` blocks on their running statistics, the others on batch statistics) and NO side effect -- inter-layer
@@ -411,6 +461,45 @@ def forward_craft(mod, x):
     with torch.enable_grad():
         logits = _TrainStep.apply(leaf, mod, (bn_config(mod), 0.0, False, True), *[p.detach() for p in param_list(mod)])
     return logits, leaf
+
+
+class MetricLoss:
+    """The ``metric_loss`` of ``train()``: a ``prototypes.ProxyHead`` on the embedding beside the classifier's loss.  It rides on
+    the model like an ``Adversary`` (``set_metric_loss``), so ``train_epoch`` / ``train_epoch_waveforms`` keep the reference's
+    signatures.  ``loss(model, x, label, loss_fn)`` is the step's loss, ``ce_weight * loss_fn(logits, label) + weight *
+    head(emb, label)``, from one ``forward_with_embedding``; ``sync_grad()`` averages the proxies' gradient over the ranks (the
+    model's own gradients are exchanged inside the backward), ``zero_contribution()`` is an empty shard's part in that."""
+
+    def __init__(self, head, weight=1.0, ce_weight=1.0):
+        weight, ce_weight = float(weight), float(ce_weight)
+        if not weight >= 0.0 or not ce_weight >= 0.0:
+            raise ValueError("metric_loss: weight and ce_weight must be >= 0")
+        self.head, self.weight, self.ce_weight = head, weight, ce_weight
+
+    def loss(self, model, x, label, loss_fn):
+        logits, emb = model.forward_with_embedding(x)
+        return self.ce_weight * loss_fn(logits, label) + self.weight * self.head(emb, label)
+
+    def sync_grad(self):
+        if world_size() > 1 and self.head.proxies.grad is not None:
+            all_reduce_mean_(self.head.proxies.grad)
+
+    def zero_contribution(self):
+        self.head.proxies.grad = torch.zeros_like(self.head.proxies)
+        self.sync_grad()
+
+
+def set_metric_loss(mod, metric):
+    """Make ``train_epoch`` / ``train_epoch_waveforms`` add ``metric`` (a ``MetricLoss``; ``None``: stop) to the step's loss.
+    Nothing else reads it: ``validate`` and ``predict`` are unaffected and it is not part of ``state_dict()``."""
+    if metric is not None and not isinstance(metric, MetricLoss):
+        raise TypeError("set_metric_loss takes a train_ops.MetricLoss or None")
+    mod._sir_metric_loss = metric
+    return metric
+
+
+def metric_loss_of(mod):
+    return getattr(mod, "_sir_metric_loss", None)
 
 
 def _adv_check(eps, alpha, *tensors):

@@ -528,11 +528,7 @@ extern "C" int sir_model_train_bwd_ragged(sir_handle* h, const sir_model_weights
                                           const float* dlogits, int batch, int t_frames, float dropout_p, uint64_t dropout_seed,
                                           const sir_train_config* cfg, const sir_model_grads* g, float* dfeats, void* workspace,
                                           size_t workspace_bytes, int part, void* stream_) {
-    if (!cfg || !cfg->bn_frozen[0] || !cfg->bn_frozen[1] || !cfg->bn_frozen[2]) {
-        sir_set_error("sir_model_train_bwd_ragged: lengths (frames per clip) need every BatchNorm on its frozen running statistics "
-                      "(bn_frozen = {1, 1, 1}): with batch statistics a clip has no gradient of its own");
-        return SIR_EUNSUPPORTED;
-    }
+    if (int rc = check_ragged_frozen("sir_model_train_bwd_ragged", cfg, "gradient")) return rc;
     if (!frames) { sir_set_error("sir_model_train_bwd_ragged: NULL frames"); return SIR_EINVAL; }
     return train_bwd_impl("sir_model_train_bwd_ragged", h, w, feats, frames, dlogits, nullptr, batch, t_frames, dropout_p, dropout_seed, cfg, g, dfeats,
                           workspace, workspace_bytes, part, stream_);
@@ -544,14 +540,9 @@ extern "C" int sir_model_train_bwd_emb(sir_handle* h, const sir_model_weights* w
                                        const float* dlogits, const float* demb, int batch, int t_frames, float dropout_p,
                                        uint64_t dropout_seed, const sir_train_config* cfg, const sir_model_grads* g, float* dfeats,
                                        void* workspace, size_t workspace_bytes, int part, void* stream_) {
-    if (!frames)
-        return train_bwd_impl("sir_model_train_bwd_emb", h, w, feats, nullptr, dlogits, demb, batch, t_frames, dropout_p, dropout_seed,
-                              cfg ? cfg : &kTrainAllLive, g, dfeats, workspace, workspace_bytes, part, stream_);
-    if (!cfg || !cfg->bn_frozen[0] || !cfg->bn_frozen[1] || !cfg->bn_frozen[2]) {
-        sir_set_error("sir_model_train_bwd_emb: lengths (frames per clip) need every BatchNorm on its frozen running statistics "
-                      "(bn_frozen = {1, 1, 1}): with batch statistics a clip has no gradient of its own");
-        return SIR_EUNSUPPORTED;
+    if (frames) {
+        if (int rc = check_ragged_frozen("sir_model_train_bwd_emb", cfg, "gradient")) return rc;
     }
-    return train_bwd_impl("sir_model_train_bwd_emb", h, w, feats, frames, dlogits, demb, batch, t_frames, dropout_p, dropout_seed, cfg, g, dfeats,
-                          workspace, workspace_bytes, part, stream_);
+    return train_bwd_impl("sir_model_train_bwd_emb", h, w, feats, frames, dlogits, demb, batch, t_frames, dropout_p, dropout_seed,
+                          cfg ? cfg : &kTrainAllLive, g, dfeats, workspace, workspace_bytes, part, stream_);
 }

@@ -217,11 +217,7 @@ extern "C" int sir_model_train_fwd_ragged(sir_handle* h, const sir_model_weights
                                           const float* const bn_running_var[3], const float* feats, const int32_t* frames, int batch,
                                           int t_frames, float dropout_p, uint64_t dropout_seed, const sir_train_config* cfg,
                                           float* logits, void* workspace, size_t workspace_bytes, void* stream_) {
-    if (!cfg || !cfg->bn_frozen[0] || !cfg->bn_frozen[1] || !cfg->bn_frozen[2]) {
-        sir_set_error("sir_model_train_fwd_ragged: lengths (frames per clip) need every BatchNorm on its frozen running statistics "
-                      "(bn_frozen = {1, 1, 1}): with batch statistics a clip has no result of its own");
-        return SIR_EUNSUPPORTED;
-    }
+    if (int rc = check_ragged_frozen("sir_model_train_fwd_ragged", cfg, "result")) return rc;
     if (!frames) { sir_set_error("sir_model_train_fwd_ragged: NULL frames"); return SIR_EINVAL; }
     // (frozen blocks read the running statistics and never write them: bn_fold_running_kernel)
     return train_fwd_impl("sir_model_train_fwd_ragged", h, w, (float* const*)bn_running_mean, (float* const*)bn_running_var, feats, frames,

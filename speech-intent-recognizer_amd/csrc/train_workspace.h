@@ -199,6 +199,15 @@ static inline int check_common(const char* who, sir_handle* h, const sir_model_w
     return SIR_OK;
 }
 
+// The ragged step (`frames` given) takes every BatchNorm on its running statistics: refused otherwise, before anything is launched
+// or written.  `what`: "result" (forward) or "gradient" (backward).
+static inline int check_ragged_frozen(const char* who, const sir_train_config* cfg, const char* what) {
+    if (cfg && cfg->bn_frozen[0] && cfg->bn_frozen[1] && cfg->bn_frozen[2]) return SIR_OK;
+    sir_set_error("%s: lengths (frames per clip) need every BatchNorm on its frozen running statistics "
+                  "(bn_frozen = {1, 1, 1}): with batch statistics a clip has no %s of its own", who, what);
+    return SIR_EUNSUPPORTED;
+}
+
 // Loss scale of the backward (a power of two, exact in fp32 both ways): head_bwd_kernel multiplies d(loss)/d(GRU output) by it and
 // every kernel that writes a PARAMETER gradient behind it multiplies by its inverse, so that the intermediate gradients -- 1e-5 to
 // 1e-7 at batch 256 unscaled -- sit around 2^-4 .. 2^4: inside fp16's normal range for the f16x3 contractions of the backward

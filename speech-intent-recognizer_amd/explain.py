@@ -5,7 +5,7 @@ Everything here runs the model with EVAL semantics on the differentiable path --
 statistics, no inter-layer dropout, no parameter gradient -- whatever mode the module is in, and leaves the module as it
 found it: sub-module flags, running statistics, ``num_batches_tracked``, the dropout step counter, cached weight layouts
 and every ``p.grad`` are untouched.  The forward is ``sir_model_train_fwd_cfg`` with ``bn_frozen = {1, 1, 1}``, the backward
-``sir_model_train_bwd_x`` with all 29 gradient pointers NULL: the data chain alone, down through conv1
+``sir_model_train_bwd_emb`` with all 29 gradient pointers and ``demb`` NULL: the data chain alone, down through conv1
 (``conv1_bwd_data_kernel``).  With frozen statistics the clips of a batch do not see each other, so row ``b`` of every
 result is what clip ``b`` gives on its own.
 
@@ -14,13 +14,13 @@ The ``*_wave`` forms start from audio: features by ``sir_features_fwd`` (no augm
 featurizer takes), not the ragged model path; every clip must fit ``t_pad`` frames (``1 + L // 512 <= t_pad``).
 
 Arguments are validated before any device call; there is no CPU path.  Un-padded clips of mixed length have functions of their
-own -- ``input_gradient_ragged``, ``saliency_ragged``, ``fgsm_ragged`` (``sir_model_train_fwd_ragged`` / ``_bwd_ragged``: row ``b``
-is what clip ``b`` gives at its own length, the function ``model.eval()(x, lengths=...)`` scores); the ``lengths=`` keywords of the
-functions for padded batches keep raising.  ``pgd`` and the waveform forms have no ragged form.
+own -- ``input_gradient_ragged``, ``saliency_ragged``, ``fgsm_ragged`` (``sir_model_train_fwd_ragged`` / ``frames`` of the backward:
+row ``b`` is what clip ``b`` gives at its own length, the function ``model.eval()(x, lengths=...)`` scores); the ``lengths=``
+keywords of the functions for padded batches keep raising.  ``pgd`` and the waveform forms have no ragged form.
 """
 import torch
 
-from . import _native
+from . import _native, ops
 
 
 def _frozen_cfg():
@@ -34,16 +34,16 @@ def _on_device(model, x):
     return x.is_cuda and next(model.parameters()).is_cuda
 
 
+def _require_device(model, x):
+    if not _on_device(model, x):
+        raise _native.SirError("tensor is not on a HIP device: this path runs on MI355X only (no CPU fallback)")
+
+
 def _validate(model, x, lengths):
     if lengths is not None:
         raise ValueError("lengths= (ragged batches) is not available on the differentiable path: pass clips of one length")
-    if not torch.is_tensor(x) or x.dtype != torch.float32:
-        raise ValueError("x must be a float32 tensor [B,64,T] or [B,1,64,T]")
-    shape = tuple(x.shape)
-    if not ((len(shape) == 3 and shape[1] == 64) or (len(shape) == 4 and shape[1] == 1 and shape[2] == 64)) or shape[-1] < 8:
-        raise ValueError(f"expected [B,64,T] or [B,1,64,T] with T >= 8, got {shape}")
-    if not _on_device(model, x):
-        raise _native.SirError("tensor is not on a HIP device: this path runs on MI355X only (no CPU fallback)")
+    ops.check_feature_batch(x, "x", 8)
+    _require_device(model, x)
 
 
 def _index_vector(v, bsz, name):
@@ -57,12 +57,23 @@ def _index_vector(v, bsz, name):
     return v
 
 
+def _class_vector(model, v, bsz, name):
+    """``_index_vector`` plus, for a host tensor, the range check (a device tensor is checked by the loss kernel / scatter)."""
+    v = _index_vector(v, bsz, name)
+    if not v.is_cuda:
+        ncls = model.fc.weight.shape[0]
+        bad = [(i, int(c)) for i, c in enumerate(v.tolist()) if not 0 <= int(c) < ncls]
+        if bad:
+            raise ValueError(f"{name} outside [0, {ncls}) (clip, class): {bad[:8]}")
+    return v
+
+
 def _forward(model, x, frames=None):
     """logits of the eval-semantics differentiable forward and the leaf they hang on (``x`` detached, in its own shape).
     ``frames`` (device int32 ``[B]``): the ragged step."""
     from . import train_ops
     leaf = x.detach().requires_grad_(True)
-    opts = (_frozen_cfg(), 0.0, False) if frames is None else (_frozen_cfg(), 0.0, False, False, frames)
+    opts = train_ops.StepOptions(cfg=_frozen_cfg(), dropout_p=0.0, step=False, frames=frames)
     with torch.enable_grad():
         # (detached parameters: the node sees no parameter that wants a gradient)
         logits = train_ops._TrainStep.apply(leaf, model, opts, *[p.detach() for p in train_ops.param_list(model)])
@@ -73,29 +84,20 @@ def _validate_ragged(model, x, frames):
     """The checks of ``_validate`` with the clips' own lengths: shape and dtype of ``x``, then ``frames`` (one integer per clip;
     a host list or CPU tensor must lie in ``[8, T]``, a device tensor is checked by the kernels).  Returns ``frames`` as a
     tensor, still where it was; the caller checks its other arguments, then the device (``_require_device``)."""
-    if not torch.is_tensor(x) or x.dtype != torch.float32:
-        raise ValueError("x must be a float32 tensor [B,64,T] or [B,1,64,T]")
-    shape = tuple(x.shape)
-    if not ((len(shape) == 3 and shape[1] == 64) or (len(shape) == 4 and shape[1] == 1 and shape[2] == 64)) or shape[-1] < 8:
-        raise ValueError(f"expected [B,64,T] or [B,1,64,T] with T >= 8, got {shape}")
+    bsz, t = ops.check_feature_batch(x, "x", 8)
     if frames is None:
         raise ValueError("frames must hold one length per clip (for clips of one length use the function without _ragged)")
     if not torch.is_tensor(frames):
         frames = torch.as_tensor(list(frames))
     if frames.is_floating_point() or frames.dtype == torch.bool:
         raise ValueError("frames must be integers (frames per clip)")
-    if frames.dim() != 1 or frames.numel() != shape[0]:
-        raise ValueError(f"frames must hold one entry per clip: got shape {tuple(frames.shape)} for a batch of {shape[0]}")
+    if frames.dim() != 1 or frames.numel() != bsz:
+        raise ValueError(f"frames must hold one entry per clip: got shape {tuple(frames.shape)} for a batch of {bsz}")
     if not frames.is_cuda:
-        bad = [(i, int(v)) for i, v in enumerate(frames.tolist()) if not 8 <= int(v) <= shape[-1]]
+        bad = [(i, int(v)) for i, v in enumerate(frames.tolist()) if not 8 <= int(v) <= t]
         if bad:
-            raise ValueError(f"frames outside [8, {shape[-1]}] (clip, frames): {bad[:8]}")
+            raise ValueError(f"frames outside [8, {t}] (clip, frames): {bad[:8]}")
     return frames
-
-
-def _require_device(model, x):
-    if not _on_device(model, x):
-        raise _native.SirError("tensor is not on a HIP device: this path runs on MI355X only (no CPU fallback)")
 
 
 def _inside(x, frames):
@@ -104,24 +106,60 @@ def _inside(x, frames):
     return m.view((x.shape[0],) + (1,) * (x.dim() - 2) + (x.shape[-1],))
 
 
-def input_gradient_ragged(model, x, frames, target=None):
-    """``input_gradient`` for un-padded clips: row b of ``(logits, dx)`` is what ``input_gradient`` gives
-    ``x[b:b+1, ..., :frames[b]]`` on its own -- the function ``model.eval()(x, lengths=frames)`` scores -- and ``dx`` is zero at
-    columns ``>= frames[b]`` (``sir_model_train_fwd_ragged`` / ``_bwd_ragged``).  Columns behind a clip's length are never read."""
-    frames = _validate_ragged(model, x, frames)
+def _input_gradient(model, x, target, ragged, frames=None, lengths=None):
+    """``input_gradient`` (``lengths``: refused) and ``input_gradient_ragged`` (``frames``).  The padded form checks the device
+    before ``target``, the ragged form after it."""
+    if ragged:
+        frames = _validate_ragged(model, x, frames)
+    else:
+        _validate(model, x, lengths)
     bsz = x.shape[0]
     if target is not None:
         target = _class_vector(model, target, bsz, "target")
-    _require_device(model, x)
-    frames = frames.to(device=x.device, dtype=torch.int32).contiguous()
+    if ragged:
+        _require_device(model, x)
+        frames = frames.to(device=x.device, dtype=torch.int32).contiguous()
     logits, leaf = _forward(model, x, frames)
     if target is None:
         target = logits.detach().argmax(dim=1)
     target = target.to(device=x.device, dtype=torch.int64)
-    k = (bsz - 1).bit_length()                       # (the seed's power of two: see input_gradient)
+    # the backward's internal loss scale is 2^8 x batch (rounded up to a power of two), sized for the 1 / batch of a mean loss:
+    # the one-hot seed carries that power of two, and the result gives it back -- both exact
+    k = (bsz - 1).bit_length()
     seed = torch.zeros_like(logits).scatter_(1, target[:, None], 2.0 ** -k)
     (dx,) = torch.autograd.grad(logits, leaf, grad_outputs=seed)
     return logits.detach(), dx.mul_(2.0 ** k)
+
+
+def _fgsm(model, x, labels, eps, ragged, frames=None, lengths=None):
+    """``fgsm`` (``lengths``: refused) and ``fgsm_ragged`` (``frames``).  Host ``labels`` are range-checked by the ragged form
+    alone: the padded form leaves them to the loss kernel."""
+    from . import train_ops
+    eps = float(eps)
+    if not eps >= 0.0:
+        raise ValueError("eps must be >= 0")
+    if ragged:
+        frames = _validate_ragged(model, x, frames)
+        labels = _class_vector(model, labels, x.shape[0], "labels")
+        _require_device(model, x)
+        frames = frames.to(device=x.device, dtype=torch.int32).contiguous()
+    else:
+        _validate(model, x, lengths)
+        labels = _index_vector(labels, x.shape[0], "labels")
+    logits, leaf = _forward(model, x, frames)
+    with torch.enable_grad():
+        loss = train_ops.fused_cross_entropy(logits, labels.to(x.device))
+    (dx,) = torch.autograd.grad(loss, leaf)
+    adv = x.detach() + eps * dx.sign_()
+    return torch.where(_inside(x, frames), adv, x.detach()) if ragged else adv
+
+
+def input_gradient_ragged(model, x, frames, target=None):
+    """``input_gradient`` for un-padded clips: row b of ``(logits, dx)`` is what ``input_gradient`` gives
+    ``x[b:b+1, ..., :frames[b]]`` on its own -- the function ``model.eval()(x, lengths=frames)`` scores -- and ``dx`` is zero at
+    columns ``>= frames[b]`` (``sir_model_train_fwd_ragged`` / ``frames`` of the backward).  Columns behind a clip's length are
+    never read."""
+    return _input_gradient(model, x, target, True, frames=frames)
 
 
 def saliency_ragged(model, x, frames, target=None):
@@ -136,43 +174,13 @@ def saliency_ragged(model, x, frames, target=None):
 def fgsm_ragged(model, x, labels, eps, frames):
     """``fgsm`` for un-padded clips: the cross-entropy is the mean over the clips of the un-padded function's loss; columns
     ``>= frames[b]`` come back as they came, bit for bit."""
-    eps = float(eps)
-    if not eps >= 0.0:
-        raise ValueError("eps must be >= 0")
-    frames = _validate_ragged(model, x, frames)
-    labels = _class_vector(model, labels, x.shape[0], "labels")
-    _require_device(model, x)
-    from . import train_ops
-    frames = frames.to(device=x.device, dtype=torch.int32).contiguous()
-    logits, leaf = _forward(model, x, frames)
-    with torch.enable_grad():
-        loss = train_ops.fused_cross_entropy(logits, labels.to(x.device))
-    (dx,) = torch.autograd.grad(loss, leaf)
-    return torch.where(_inside(x, frames), x.detach() + eps * dx.sign_(), x.detach())
+    return _fgsm(model, x, labels, eps, True, frames=frames)
 
 
 def input_gradient(model, x, target=None, lengths=None):
     """``(logits, dx)`` with ``dx[b] = d logits[b, target[b]] / d x[b]`` in the shape of ``x``.  ``target``: int tensor
     ``[B]``; ``None`` = each row's own argmax.  ``logits`` are those of ``model.eval()(x)`` (detached)."""
-    _validate(model, x, lengths)
-    bsz = x.shape[0]
-    if target is not None:
-        target = _index_vector(target, bsz, "target")
-        if not target.is_cuda:
-            ncls = model.fc.weight.shape[0]
-            bad = [(i, int(v)) for i, v in enumerate(target.tolist()) if not 0 <= int(v) < ncls]
-            if bad:
-                raise ValueError(f"target outside [0, {ncls}) (clip, class): {bad[:8]}")
-    logits, leaf = _forward(model, x)
-    if target is None:
-        target = logits.detach().argmax(dim=1)
-    target = target.to(device=x.device, dtype=torch.int64)
-    # the backward's internal loss scale is 2^8 x batch (rounded up to a power of two), sized for the 1 / batch of a mean loss:
-    # the one-hot seed carries that power of two, and the result gives it back -- both exact
-    k = (bsz - 1).bit_length()
-    seed = torch.zeros_like(logits).scatter_(1, target[:, None], 2.0 ** -k)
-    (dx,) = torch.autograd.grad(logits, leaf, grad_outputs=seed)
-    return logits.detach(), dx.mul_(2.0 ** k)
+    return _input_gradient(model, x, target, False, lengths=lengths)
 
 
 def saliency(model, x, target=None, lengths=None):
@@ -185,17 +193,7 @@ def saliency(model, x, target=None, lengths=None):
 def fgsm(model, x, labels, eps, lengths=None):
     """The fast-gradient-sign adversarial example ``x + eps * sign(d CE(model(x), labels) / d x)`` (Goodfellow et al. 2015),
     in the shape of ``x``; the cross-entropy is the mean over the batch (``fused_cross_entropy``)."""
-    eps = float(eps)
-    if not eps >= 0.0:
-        raise ValueError("eps must be >= 0")
-    _validate(model, x, lengths)
-    labels = _index_vector(labels, x.shape[0], "labels")
-    from . import train_ops
-    logits, leaf = _forward(model, x)
-    with torch.enable_grad():
-        loss = train_ops.fused_cross_entropy(logits, labels.to(x.device))
-    (dx,) = torch.autograd.grad(loss, leaf)
-    return x.detach() + eps * dx.sign_()
+    return _fgsm(model, x, labels, eps, False, lengths=lengths)
 
 
 def pgd(model, x, labels, eps, alpha=None, steps=10, random_start=False, seed=0, keep_zero_columns=False, lengths=None):
@@ -244,17 +242,6 @@ def robust_accuracy(model, x, labels, eps, **pgd_kw):
 
 
 # ---- down to the waveform -------------------------------------------------------------------------------------------------
-def _class_vector(model, v, bsz, name):
-    """``_index_vector`` plus, for a host tensor, the range check (a device tensor is checked by the loss kernel / scatter)."""
-    v = _index_vector(v, bsz, name)
-    if not v.is_cuda:
-        ncls = model.fc.weight.shape[0]
-        bad = [(i, int(c)) for i, c in enumerate(v.tolist()) if not 0 <= int(c) < ncls]
-        if bad:
-            raise ValueError(f"{name} outside [0, {ncls}) (clip, class): {bad[:8]}")
-    return v
-
-
 def _validate_wave(model, wave, lengths, t_pad):
     from . import featurizer
     if not torch.is_tensor(wave) or wave.dtype != torch.float32 or wave.dim() != 2 or wave.shape[0] < 1 or wave.shape[1] < 1:
@@ -265,8 +252,7 @@ def _validate_wave(model, wave, lengths, t_pad):
                          f"at least that and >= 8 (got {t_pad})")
     if lengths is not None:
         lengths = _index_vector(lengths, wave.shape[0], "lengths")
-    if not _on_device(model, wave):
-        raise _native.SirError("tensor is not on a HIP device: this path runs on MI355X only (no CPU fallback)")
+    _require_device(model, wave)
     return lengths.to(device=wave.device, dtype=torch.int32) if lengths is not None else None, t_pad
 
 

@@ -91,13 +91,13 @@ class CNNAudioGRU(nn.Module):
         gives ``x[b:b+1, ..., :lengths[b]]`` on its own (scripts/test_tts_samples.py feeds each file that way), for a whole
         batch of mixed-length clips in one launch sequence.  On the differentiable path it needs bn1, bn2 and bn3 in ``eval()``
         (``finetune.freeze(model, {"bn_stats"})``): logits and gradients are then those of the un-padded function
-        (``sir_model_train_fwd_ragged`` / ``_bwd_ragged``; ``x.grad`` is zero at columns ``>= lengths[b]``).  With live batch
-        statistics a clip has no result of its own, and ``SirError`` is raised.
+        (``sir_model_train_fwd_ragged`` / ``sir_model_train_bwd_emb`` with ``frames``; ``x.grad`` is zero at columns
+        ``>= lengths[b]``).  With live batch statistics a clip has no result of its own, and ``SirError`` is raised.
 
         ``self.training and torch.is_grad_enabled()`` selects the differentiable path, as before; ``model.eval()`` keeps
         calling ``sir_model_infer``.  The differentiable path is differentiable with respect to the 29 parameters and, if
-        ``x.requires_grad``, with respect to ``x``: ``x.grad`` has the shape of ``x`` (``sir_model_train_bwd_x``; rank-local under
-        data parallelism; a double backward raises).  For the input gradient of a model in ``eval()`` mode -- saliency, FGSM --
+        ``x.requires_grad``, with respect to ``x``: ``x.grad`` has the shape of ``x`` (``dfeats`` of ``sir_model_train_bwd_emb``;
+        rank-local under data parallelism; a double backward raises).  For the input gradient of a model in ``eval()`` mode -- saliency, FGSM --
         see ``sir_amd.explain``.  Inside the differentiable path the sub-modules are consulted the way torch consults
         them: ``bnK.training == False`` uses (and keeps) that block's running statistics, ``gru.training == False`` turns the
         inter-layer dropout off, and parameters with ``requires_grad == False`` receive no gradient and cost no backward

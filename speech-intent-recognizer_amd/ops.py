@@ -187,6 +187,17 @@ def _as_features(x):
     return _f32c(x.contiguous(), "input")
 
 
+def check_feature_batch(x, name, min_frames):
+    """The host check of the functions that validate before any device call (``sir_amd.explain``, ``train_ops.adv_step``): ``x`` is
+    a float32 tensor ``[B,64,T]`` or ``[B,1,64,T]`` with ``T >= min_frames``, else ``ValueError``.  Returns ``(B, T)``."""
+    if not torch.is_tensor(x) or x.dtype != torch.float32:
+        raise ValueError(f"{name} must be a float32 tensor [B,64,T] or [B,1,64,T]")
+    sh = tuple(x.shape)
+    if not ((len(sh) == 3 and sh[1] == 64) or (len(sh) == 4 and sh[1] == 1 and sh[2] == 64)) or sh[-1] < min_frames:
+        raise ValueError(f"{name}: expected [B,64,T] or [B,1,64,T] with T >= {min_frames}, got {sh}")
+    return sh[0], sh[-1]
+
+
 def _as_lengths(lengths, bsz, t, device):
     """``lengths`` of a ragged call as an int32 device tensor [B].  A host list (or a CPU tensor) is validated here and now;
     a device tensor is validated by the kernels (bad rows come back NaN and ``check_status`` raises)."""

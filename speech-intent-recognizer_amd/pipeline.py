@@ -31,6 +31,38 @@ def _library_pipeline(n):
     return _pipelines[key]
 
 
+class HostStager:
+    """Host -> device hand-over of the batches a ``DataLoader`` yields, through a small ring of PERSISTENT pinned buffers.
+
+    ``mel.to(device, non_blocking=True)`` (train.py:86) on what the loader hands over is the slow link of the reference-shaped
+    route on this stack (devtools/dataloader_probe.py on MI355X / ROCm 7 / torch 2.10): a batch that sits in the workers'
+    shared memory copies at ~50 MB/s (``pin_memory=False``: 1 k utt/s), and with ``pin_memory=True`` torch's pinning thread
+    allocates a fresh pinned block per batch, which stalls for ~85 ms whenever the GPU is busy (3 k utt/s with ANY kernel in
+    flight, 112 k with an idle GPU).  Here a batch is copied by the CPU into one of ``slots`` pinned buffers allocated once
+    (13 MB memcpy), sent with an asynchronous copy on the caller's stream, and the buffer is reused after an event says that
+    copy is done.  Tensors already on the device pass through.  (``scripts/train.py`` re-exports it.)"""
+
+    def __init__(self, device, slots=3):
+        self.device, self.slots = device, slots
+        self.bufs, self.events, self.k = {}, {}, 0
+
+    def __call__(self, t):
+        if t.is_cuda:
+            return t
+        key = (tuple(t.shape), t.dtype)
+        if key not in self.bufs:
+            self.bufs[key] = [torch.empty(t.shape, dtype=t.dtype).pin_memory() for _ in range(self.slots)]
+            self.events[key] = [torch.cuda.Event() for _ in range(self.slots)]
+        i = self.k % self.slots
+        self.k += 1
+        buf, ev = self.bufs[key][i], self.events[key][i]
+        ev.synchronize()                                   # (a never-recorded event returns at once)
+        buf.copy_(t)
+        out = buf.to(self.device, non_blocking=True)
+        ev.record()
+        return out
+
+
 def wave_stages(fz, wave, lengths, kw):
     """The waveform stages ahead of the feature kernel, on the current stream: shift -> pitch -> speed (``sir_wave_perturb``)
     when ``kw`` carries ``pitch_cents`` / ``tempo``, then reverb -> background noise (``sir_wave_reverb_mix``) when it carries

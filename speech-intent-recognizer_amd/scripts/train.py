@@ -18,6 +18,8 @@ import yaml
 from torch.utils.data import DataLoader
 from tqdm import tqdm
 
+from sir_amd.pipeline import HostStager  # noqa: F401  (bench.py, scripts/evaluate.py and devtools import it from here)
+
 MAX_LENGTH = 200
 
 
@@ -69,36 +71,23 @@ def _mixed_loss(loss_fn, output, label, label_b, lam):
     return lam[0] * loss_fn(output, label) + (1.0 - lam[0]) * loss_fn(output, label_b)
 
 
-class HostStager:
-    """Host -> device hand-over of the batches a ``DataLoader`` yields, through a small ring of PERSISTENT pinned buffers.
+def _step_loss(model, mel, label, loss_fn, mixup, adversary, metric):
+    """The loss of one training step, for both epoch functions: mixup, then the adversary against the step's own loss (it returns
+    a new tensor: ``mel`` itself -- the prefetcher's buffer -- is read, never written), then the loss of a mixed batch, or
+    ``metric``'s (`metric_loss`: never together with mixup or an adversary, train() refuses that), or the plain one."""
+    if mixup is not None:
+        mel, label_b, lam = mixup(mel, label)
 
-    ``mel.to(device, non_blocking=True)`` (train.py:86) on what the loader hands over is the slow link of the reference-shaped
-    route on this stack (devtools/dataloader_probe.py on MI355X / ROCm 7 / torch 2.10): a batch that sits in the workers'
-    shared memory copies at ~50 MB/s (``pin_memory=False``: 1 k utt/s), and with ``pin_memory=True`` torch's pinning thread
-    allocates a fresh pinned block per batch, which stalls for ~85 ms whenever the GPU is busy (3 k utt/s with ANY kernel in
-    flight, 112 k with an idle GPU).  Here a batch is copied by the CPU into one of ``slots`` pinned buffers allocated once
-    (13 MB memcpy), sent with an asynchronous copy on the caller's stream, and the buffer is reused after an event says that
-    copy is done.  Tensors already on the device pass through."""
-
-    def __init__(self, device, slots=3):
-        self.device, self.slots = device, slots
-        self.bufs, self.events, self.k = {}, {}, 0
-
-    def __call__(self, t):
-        if t.is_cuda:
-            return t
-        key = (tuple(t.shape), t.dtype)
-        if key not in self.bufs:
-            self.bufs[key] = [torch.empty(t.shape, dtype=t.dtype).pin_memory() for _ in range(self.slots)]
-            self.events[key] = [torch.cuda.Event() for _ in range(self.slots)]
-        i = self.k % self.slots
-        self.k += 1
-        buf, ev = self.bufs[key][i], self.events[key][i]
-        ev.synchronize()                                   # (a never-recorded event returns at once)
-        buf.copy_(t)
-        out = buf.to(self.device, non_blocking=True)
-        ev.record()
-        return out
+        def loss_of(out):
+            return _mixed_loss(loss_fn, out, label, label_b, lam)
+    else:
+        def loss_of(out):
+            return loss_fn(out, label)
+    if adversary is not None:
+        mel = adversary(model, mel, loss_of)
+    if metric is not None and mixup is None:
+        return metric.loss(model, mel, label, loss_fn)
+    return loss_of(model(mel))
 
 
 def loader_kwargs(num_workers):
@@ -147,19 +136,7 @@ def train_epoch(model, train_loader, optimizer, criterion, device, scaler=None, 
         mel = stage(mel)                                   # host batches: persistent pinned ring (see HostStager)
         label = stage(label)
         optimizer.zero_grad(set_to_none=True)
-        if mixup is not None:
-            mel, label_b, lam = mixup(mel, label)
-            if adversary is not None:
-                mel = adversary(model, mel, lambda out: _mixed_loss(loss_fn, out, label, label_b, lam))
-            loss = _mixed_loss(loss_fn, model(mel), label, label_b, lam)
-        else:
-            if adversary is not None:
-                mel = adversary(model, mel, lambda out: loss_fn(out, label))
-            if metric is not None:
-                loss = metric.loss(model, mel, label, loss_fn)
-            else:
-                output = model(mel)
-                loss = loss_fn(output, label)
+        loss = _step_loss(model, mel, label, loss_fn, mixup, adversary, metric)
         loss.backward()
         if metric is not None:
             metric.sync_grad()
@@ -211,15 +188,7 @@ def train_epoch_waveforms(model, wave_loader, optimizer, criterion, device, t_pa
     def step():
         mel, label = pre.get(), pending.pop(0)
         optimizer.zero_grad(set_to_none=True)
-        if mixup is not None:
-            mixed, label_b, lam = mixup(mel, label)
-            if adversary is not None:
-                mixed = adversary(model, mixed, lambda out: _mixed_loss(loss_fn, out, label, label_b, lam))
-            loss = _mixed_loss(loss_fn, model(mixed), label, label_b, lam)
-        else:
-            if adversary is not None:                   # (a new tensor: the prefetcher's buffer is read, never written)
-                mel = adversary(model, mel, lambda out: loss_fn(out, label))
-            loss = metric.loss(model, mel, label, loss_fn) if metric is not None else loss_fn(model(mel), label)
+        loss = _step_loss(model, mel, label, loss_fn, mixup, adversary, metric)
         loss.backward()
         if metric is not None:
             metric.sync_grad()

@@ -1,18 +1,20 @@
 """Training-step glue: ``torch.autograd`` nodes around the HIP training kernels.
 
-``forward_train(model, x)`` returns logits whose backward runs ``sir_model_train_bwd`` and hands
-autograd the 29 parameter gradients as views of ONE flat fp32 buffer (3 261 184 elements); with
+``forward_train(model, x)`` returns logits whose backward runs ``sir_model_train_bwd_emb`` (the one backward
+entry point this node calls; the older ones remain for C callers) and hands autograd the 29
+parameter gradients as views of ONE flat fp32 buffer (3 261 184 elements); with
 ``WORLD_SIZE > 1`` that buffer is averaged over ranks with a single RCCL all-reduce before the
 views are returned, so the update equals single-GPU training on the global batch.
-If ``x.requires_grad`` the backward also returns ``d loss / d x`` (``sir_model_train_bwd_x``: the
+If ``x.requires_grad`` the backward also returns ``d loss / d x`` (a non-NULL ``dfeats``: the
 data chain runs down through conv1); it is rank-local and is not exchanged.
 ``forward_train_embed`` also returns the 512-float utterance embedding with a graph attached: a loss on it
-(``prototypes.ProxyHead``) enters the backward beside ``dlogits`` (``sir_model_train_bwd_emb``).
+(``prototypes.ProxyHead``) enters the backward beside ``dlogits`` (a non-NULL ``demb``).
 ``fused_cross_entropy`` is the HIP form of the reference's ``nn.CrossEntropyLoss()`` (train.py:242).
 Only pointers move through Python; no arithmetic of the step is done by torch ops.
 """
 import ctypes as C
 import os
+from typing import NamedTuple
 
 import torch
 from torch.autograd.function import once_differentiable
@@ -21,7 +23,7 @@ from . import _native, ops
 from .dist_utils import (ShardSampler, all_reduce_mean_, all_reduce_sum_, broadcast_module_,  # noqa: F401
                          init_distributed, limit_host_threads, shutdown_distributed, world_size)
 from .featurizer import get_featurizer
-
+from .pipeline import HostStager
 
 
 class _StepCounter:
@@ -210,16 +212,37 @@ def _scratch_running_stats(mod, st, cfg, rm, rv):
             rm[i], rv[i] = scratch[i][0].data_ptr(), scratch[i][1].data_ptr()
 
 
+class StepOptions(NamedTuple):
+    """The settings of one ``_TrainStep``.  ``step == False`` (sir_amd.explain) draws no dropout key and leaves the step counter
+    and ``mod._sir_last_dropout`` alone; ``craft == True`` (``forward_craft``) also keeps the LIVE BatchNorm blocks' running
+    statistics, ``num_batches_tracked`` and the cached-weights epoch as they are.  ``frames`` (device int32 ``[B]``): the ragged
+    step, ``sir_model_train_fwd_ragged`` and a non-NULL ``frames`` of the backward.  ``want_emb`` (``forward_train_embed``): the
+    node returns ``(logits, emb)``."""
+    cfg: _native.TrainConfig
+    dropout_p: float
+    step: bool = True
+    craft: bool = False
+    frames: torch.Tensor = None
+    want_emb: bool = False
+
+
+def _run_forward(lib, h, w, rm, rv, x, momentum, seed, opts, logits, ws):
+    """The step's native forward: ``sir_model_train_fwd_ragged`` when ``opts.frames`` is given (frozen statistics: it takes no
+    momentum), else ``sir_model_train_fwd_cfg``."""
+    bsz, _, t = x.shape
+    head = (h, C.byref(w), rm, rv, x.data_ptr())
+    tail = (float(opts.dropout_p), seed, C.byref(opts.cfg), logits.data_ptr(), ws.data_ptr(), ws.numel(), _native.current_stream_ptr())
+    if opts.frames is not None:
+        rc, who = lib.sir_model_train_fwd_ragged(*head, opts.frames.data_ptr(), bsz, t, *tail), "sir_model_train_fwd_ragged"
+    else:
+        rc, who = lib.sir_model_train_fwd_cfg(*head, bsz, t, momentum, *tail), "sir_model_train_fwd_cfg"
+    _native.check(rc, who)
+
+
 class _TrainStep(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, mod, opts, *params):
-        # opts = (sir_train_config, dropout p, step[, craft]): step == False (sir_amd.explain) draws no dropout key and leaves
-        # the step counter and ``mod._sir_last_dropout`` alone; craft == True (``forward_craft``) also keeps the LIVE BatchNorm
-        # blocks' running statistics, ``num_batches_tracked`` and the cached-weights epoch as they are
-        # frames (opts[4], device int32 [B] or absent / None): the ragged step, sir_model_train_fwd_ragged / _bwd_ragged
-        cfg, dropout_p, step = opts[:3]
-        craft = len(opts) > 3 and bool(opts[3])
-        frames = opts[4] if len(opts) > 4 else None
+        cfg, dropout_p, craft, frames = opts.cfg, opts.dropout_p, opts.craft, opts.frames
         lib = _native.lib()
         h = get_featurizer().handle
         x_shape = x.shape
@@ -236,31 +259,22 @@ class _TrainStep(torch.autograd.Function):
             _scratch_running_stats(mod, st, cfg, rm, rv)
         logits = torch.empty((bsz, w.num_classes), dtype=torch.float32, device=x.device)
         seed = 0
-        if step:
+        if opts.step:
             seed = dropout_seed(next(_seed_counter))
             mod._sir_last_dropout = (seed, float(dropout_p))  # lets tests rebuild the mask (tests/dropout_host.py)
         momentum = float(mod.bn1.momentum if mod.bn1.momentum is not None else 0.1)
-        if frames is not None:
-            rc = lib.sir_model_train_fwd_ragged(h, C.byref(w), rm, rv, x.data_ptr(), frames.data_ptr(), bsz, t, float(dropout_p), seed,
-                                                C.byref(cfg), logits.data_ptr(), ws.data_ptr(), ws.numel(),
-                                                _native.current_stream_ptr())
-            _native.check(rc, "sir_model_train_fwd_ragged")
-        else:
-            rc = lib.sir_model_train_fwd_cfg(h, C.byref(w), rm, rv, x.data_ptr(), bsz, t, momentum, float(dropout_p), seed,
-                                             C.byref(cfg), logits.data_ptr(), ws.data_ptr(), ws.numel(),
-                                             _native.current_stream_ptr())
-            _native.check(rc, "sir_model_train_fwd_cfg")
+        _run_forward(lib, h, w, rm, rv, x, momentum, seed, opts, logits, ws)
         live = [] if craft else [getattr(mod, f"bn{i + 1}").num_batches_tracked for i in range(3) if not cfg.bn_frozen[i]]
         if live:                                     # frozen statistics: nothing was written, cached layouts stay valid
             ops.bump_weights_epoch()                 # BN running statistics were updated in place
             torch._foreach_add_(live, 1)
         ctx.mod, ctx.x, ctx.seed, ctx.dropout_p, ctx.ws, ctx.cfg = mod, x, seed, float(dropout_p), ws, cfg
         ctx.x_shape, ctx.frames = x_shape, frames
-        if len(opts) > 5 and opts[5]:
-            # want_emb (``forward_train_embed``): the attention-pooled context the forward left in workspace slot 11, copied on the
-            # stream -- the next step reuses the workspace, a view would dangle.  A gradient that is not there stays None.
+        if opts.want_emb:
+            # the attention-pooled context the forward left in its workspace slot, copied on the stream -- the next step reuses
+            # the workspace, a view would dangle.  A gradient that is not there stays None.
             ctx.set_materialize_grads(False)
-            at = _train_offsets(h, bsz, t)[11]
+            at = _train_offsets(h, bsz, t)[CTX_SLOT]
             return logits, ws[at: at + 4 * bsz * 512].view(torch.float32).view(bsz, 512).clone()
         return logits
 
@@ -286,28 +300,16 @@ class _TrainStep(torch.autograd.Function):
         # d loss / d x, returned in the caller's shape ([B,64,T] and [B,1,64,T] are the same memory); None: not wanted
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
 
+        def ptr(v):
+            return v.data_ptr() if v is not None else None
+
         def run(part):
-            if demb is not None:
-                rc = lib.sir_model_train_bwd_emb(h, C.byref(w), x.data_ptr(), ctx.frames.data_ptr() if ctx.frames is not None else None,
-                                                 dlogits.data_ptr(), demb.data_ptr(), bsz, t, ctx.dropout_p, ctx.seed, C.byref(ctx.cfg),
-                                                 C.byref(gstruct), dx.data_ptr() if dx is not None else None, ctx.ws.data_ptr(),
-                                                 ctx.ws.numel(), part, _native.current_stream_ptr())
-                return _native.check(rc, "sir_model_train_bwd_emb")
-            if ctx.frames is not None:
-                rc = lib.sir_model_train_bwd_ragged(h, C.byref(w), x.data_ptr(), ctx.frames.data_ptr(), dlogits.data_ptr(), bsz, t,
-                                                    ctx.dropout_p, ctx.seed, C.byref(ctx.cfg), C.byref(gstruct),
-                                                    dx.data_ptr() if dx is not None else None, ctx.ws.data_ptr(), ctx.ws.numel(), part,
-                                                    _native.current_stream_ptr())
-                return _native.check(rc, "sir_model_train_bwd_ragged")
-            if dx is None:
-                rc = lib.sir_model_train_bwd_cfg(h, C.byref(w), x.data_ptr(), dlogits.data_ptr(), bsz, t, ctx.dropout_p, ctx.seed,
-                                                 C.byref(ctx.cfg), C.byref(gstruct), ctx.ws.data_ptr(), ctx.ws.numel(), part,
-                                                 _native.current_stream_ptr())
-                return _native.check(rc, "sir_model_train_bwd_cfg")
-            rc = lib.sir_model_train_bwd_x(h, C.byref(w), x.data_ptr(), dlogits.data_ptr(), bsz, t, ctx.dropout_p, ctx.seed,
-                                           C.byref(ctx.cfg), C.byref(gstruct), dx.data_ptr(),
-                                           ctx.ws.data_ptr(), ctx.ws.numel(), part, _native.current_stream_ptr())
-            _native.check(rc, "sir_model_train_bwd_x")
+            # the one backward of this node (include/sir_hip.h): a NULL frames is the padded step, a NULL demb lets no gradient
+            # in at the embedding, a NULL dfeats writes no input gradient -- same launches and bits as the entry points without them
+            rc = lib.sir_model_train_bwd_emb(h, C.byref(w), x.data_ptr(), ptr(ctx.frames), dlogits.data_ptr(), ptr(demb), bsz, t,
+                                             ctx.dropout_p, ctx.seed, C.byref(ctx.cfg), C.byref(gstruct), ptr(dx), ctx.ws.data_ptr(),
+                                             ctx.ws.numel(), part, _native.current_stream_ptr())
+            _native.check(rc, "sir_model_train_bwd_emb")
 
         if not any(need):
             # only the input gradient is wanted: no parameter gradient is written, so nothing is exchanged between ranks
@@ -338,6 +340,7 @@ class _TrainStep(torch.autograd.Function):
 
 
 _offsets = {}
+CTX_SLOT = 11        # the training workspace's slot of the attention-pooled context, fp32 [B, 512]: the embedding
 
 
 def _train_offsets(h, bsz, t):
@@ -345,7 +348,7 @@ def _train_offsets(h, bsz, t):
     offs = _offsets.get((bsz, t))
     if offs is None:
         buf = (C.c_size_t * 48)()
-        if _native.lib().sir_model_train_workspace_offsets(h, bsz, t, buf, 48) <= 11:
+        if _native.lib().sir_model_train_workspace_offsets(h, bsz, t, buf, 48) <= CTX_SLOT:
             raise _native.SirError("sir_model_train_workspace_offsets failed")
         offs = _offsets[(bsz, t)] = list(buf)
     return offs
@@ -415,21 +418,12 @@ def forward_train(mod, x, lengths=None):
     the shape of ``x``; a double backward raises).  The sub-modules' own flags are honoured as torch
     honours them: ``bnK.eval()`` freezes that block's statistics (forward and backward), ``gru.eval()`` turns the dropout
     off, and a parameter with ``requires_grad == False`` gets no gradient -- the backward stops where the trainable
-    parameters stop (``sir_model_train_bwd_cfg``).
+    parameters stop (a NULL gradient pointer of ``sir_model_train_bwd_emb``, the one backward the node calls).
 
     ``lengths`` (int tensor or list, frames per clip): the un-padded function and its gradient -- row b is what the model gives
-    ``x[b:b+1, ..., :lengths[b]]`` on its own (``sir_model_train_fwd_ragged`` / ``_bwd_ragged``).  It needs bn1, bn2 and bn3 in
-    ``eval()``, which is what ``finetune.freeze(model, {"bn_stats"})`` leaves; otherwise ``SirError``."""
-    cfg, dropout_p = step_config(mod)
-    if lengths is not None and not all(cfg.bn_frozen):
-        raise _native.SirError("lengths (un-padded clips) on the differentiable path need bn1, bn2 and bn3 on their running statistics: "
-                               "freeze them first (finetune.freeze(model, {'bn_stats'}) or bnK.eval()), call model.eval(), or run "
-                               "under torch.no_grad() -- with live batch statistics a clip has no result of its own")
-    _native.require_hip(x)
-    ops._as_features(x)                              # (shape / dtype checks; the node itself takes x in the caller's shape)
-    if lengths is None:
-        return _TrainStep.apply(x, mod, (cfg, dropout_p, True), *param_list(mod))
-    return _TrainStep.apply(x, mod, (cfg, dropout_p, True, False, ragged_frames(lengths, x)), *param_list(mod))
+    ``x[b:b+1, ..., :lengths[b]]`` on its own (``sir_model_train_fwd_ragged`` / ``frames`` of the backward).  It needs bn1, bn2 and
+    bn3 in ``eval()``, which is what ``finetune.freeze(model, {"bn_stats"})`` leaves; otherwise ``SirError``."""
+    return _forward_step(mod, x, lengths, want_emb=False)
 
 
 def forward_train_embed(mod, x, lengths=None):
@@ -438,14 +432,19 @@ def forward_train_embed(mod, x, lengths=None):
     ``(dlogits, demb)`` to ``sir_model_train_bwd_emb``, which adds ``demb`` to the ``dctx`` it forms from ``dlogits`` (zeros when
     only the embedding carries a loss) -- same freeze / pruning rules, flat gradient buffer and data-parallel exchange as
     ``forward_train``.  With no gradient on ``emb`` the step is ``forward_train``'s, bit for bit."""
+    return _forward_step(mod, x, lengths, want_emb=True)
+
+
+def _forward_step(mod, x, lengths, want_emb):
     cfg, dropout_p = step_config(mod)
     if lengths is not None and not all(cfg.bn_frozen):
         raise _native.SirError("lengths (un-padded clips) on the differentiable path need bn1, bn2 and bn3 on their running statistics: "
-                               "freeze them first (finetune.freeze(model, {'bn_stats'}) or bnK.eval())")
+                               "freeze them first (finetune.freeze(model, {'bn_stats'}) or bnK.eval()), call model.eval(), or run "
+                               "under torch.no_grad() -- with live batch statistics a clip has no result of its own")
     _native.require_hip(x)
-    ops._as_features(x)
+    ops._as_features(x)                              # (shape / dtype checks; the node itself takes x in the caller's shape)
     frames = ragged_frames(lengths, x) if lengths is not None else None
-    return _TrainStep.apply(x, mod, (cfg, dropout_p, True, False, frames, True), *param_list(mod))
+    return _TrainStep.apply(x, mod, StepOptions(cfg, dropout_p, frames=frames, want_emb=want_emb), *param_list(mod))
 
 
 def forward_craft(mod, x):
@@ -453,13 +452,14 @@ def forward_craft(mod, x):
     (``bnK.eval()`` blocks on their running statistics, the others on batch statistics) and NO side effect -- inter-layer
     dropout off and no key drawn (``dropout_step()`` unchanged), running statistics, ``num_batches_tracked`` and the
     cached-weights epoch untouched.  ``leaf`` is ``x`` detached with ``requires_grad``; ``torch.autograd.grad(loss, leaf)`` runs
-    ``sir_model_train_bwd_x`` with all 29 gradient pointers NULL: no ``p.grad`` is touched and nothing is exchanged between
+    the backward with all 29 gradient pointers NULL: no ``p.grad`` is touched and nothing is exchanged between
     ranks."""
     _native.require_hip(x)
     ops._as_features(x)
     leaf = x.detach().requires_grad_(True)
+    opts = StepOptions(cfg=bn_config(mod), dropout_p=0.0, step=False, craft=True)
     with torch.enable_grad():
-        logits = _TrainStep.apply(leaf, mod, (bn_config(mod), 0.0, False, True), *[p.detach() for p in param_list(mod)])
+        logits = _TrainStep.apply(leaf, mod, opts, *[p.detach() for p in param_list(mod)])
     return logits, leaf
 
 
@@ -513,14 +513,12 @@ def _adv_check(eps, alpha, *tensors):
     for name, v in tensors:
         if v is None:
             continue
-        if not torch.is_tensor(v) or v.dtype != torch.float32:
-            raise ValueError(f"{name} must be a float32 tensor [B,64,T] or [B,1,64,T]")
-        sh = tuple(v.shape)
-        if not ((len(sh) == 3 and sh[1] == 64) or (len(sh) == 4 and sh[1] == 1 and sh[2] == 64)) or sh[0] < 1 or sh[-1] < 1:
-            raise ValueError(f"{name}: expected [B,64,T] or [B,1,64,T], got {sh}")
-        if shape is not None and (sh[0], sh[-1]) != shape:
-            raise ValueError(f"{name}: shape {sh} does not match x0's batch {shape[0]} and {shape[1]} frames")
-        shape = (sh[0], sh[-1])
+        sh = ops.check_feature_batch(v, name, 1)
+        if sh[0] < 1:
+            raise ValueError(f"{name}: expected at least one clip, got {tuple(v.shape)}")
+        if shape is not None and sh != shape:
+            raise ValueError(f"{name}: shape {tuple(v.shape)} does not match x0's batch {shape[0]} and {shape[1]} frames")
+        shape = sh
     if any(v is not None and not v.is_cuda for _, v in tensors):
         raise _native.SirError("tensor is not on a HIP device: this path runs on MI355X only (no CPU fallback)")
     return eps, alpha, shape
@@ -618,7 +616,6 @@ class Adversary:
         return torch.tensor(flags, dtype=torch.int32), self.rng.getrandbits(64)
 
     def __call__(self, model, x, loss_closure):
-        from .scripts.train import HostStager
         _adv_check(self.eps, self.alpha, ("x", x))
         if self._stage is None or self._stage.device != x.device:
             self._stage = HostStager(x.device)
@@ -727,7 +724,6 @@ class Mixup:
         return torch.tensor(perm, dtype=torch.int64), torch.full((bsz,), lam, dtype=torch.float32)
 
     def __call__(self, x, labels):
-        from .scripts.train import HostStager
         if self._stage is None or self._stage.device != x.device:
             self._stage = HostStager(x.device)
         perm, lam = self.draw(x.shape[0])

@@ -256,8 +256,8 @@ def test_split_backward_writes_the_same_input_gradient(sd, monkeypatch):
         monkeypatch.setattr(train_ops, "world_size", lambda: 2)          # take the two-bucket branch
         monkeypatch.setattr(train_ops, "OVERLAP_GRAD_EXCHANGE", True)
         parts, lib = [], _native.lib()
-        real = lib.sir_model_train_bwd_x
-        monkeypatch.setattr(lib, "sir_model_train_bwd_x", lambda *a: parts.append(a[13]) or real(*a))
+        real = lib.sir_model_train_bwd_emb               # (the one backward the node calls; `part` is argument 15 of its 17)
+        monkeypatch.setattr(lib, "sir_model_train_bwd_emb", lambda *a: parts.append(a[15]) or real(*a))
         m1, dx1 = run()
         assert parts == [_native.BWD_HEAD_GRU, _native.BWD_CNN]
         assert torch.equal(dx1, dx0)

@@ -201,54 +201,105 @@ def _bsc(m, bsz, t, pairs):
     return m._sir_train["ws"].buf[offs[39]: offs[39] + 8 * pairs].view(torch.float32).cpu().clone()
 
 
-@pytest.mark.parametrize("bsz,t,frozen,want_dx", [(3, 24, False, False), (3, 24, False, True), (5, 40, True, True)])
-def test_null_demb_is_the_existing_backward(sd, bsz, t, frozen, want_dx):
-    """``sir_model_train_bwd_emb`` with ``demb == NULL`` against ``_cfg`` (no dfeats), ``_x`` and ``_ragged`` (one length < 8): all 29
-    gradients, dfeats and slot 39 ``torch.equal``."""
-    lib, h = _native.lib(), get_featurizer().handle
-    x = cases.varied_features(bsz, t, seed=40 + bsz).float()
-    y = synth.synth_labels(bsz, 31, seed=41 + bsz).to(DEV)
-    frames = torch.tensor([40, 7, 23, 16, 9], dtype=torch.int32, device=DEV) if frozen else None
-    m = _model(sd, frozen)
-    got = {}
+OLDER = {(False, False): "sir_model_train_bwd_cfg", (False, True): "sir_model_train_bwd_x", (True, True): "sir_model_train_bwd_ragged"}
+NULL_DEMB_CASES = [(3, 24, False, False), (3, 24, False, True), (5, 40, True, True)]
 
-    def forward():
-        train_ops.set_dropout_step(5)
-        xd = x.to(DEV).requires_grad_(want_dx)
-        logits = m(xd, lengths=frames)
+
+class _HandStep:
+    """One case of the two tests below: the Python step once (its ``.grad``s, ``x.grad``, the ``dlogits`` it handed down and slot
+    39), then ``by_hand(fn)``: the same forward again and the backward entry point ``fn`` called by hand on the step's own
+    workspace, into a second ``GradBuffer`` and a ``dfeats`` pre-filled with NaN."""
+
+    def __init__(self, sd, bsz, t, frozen, want_dx, dropout=0.0):
+        self.bsz, self.t, self.want_dx = bsz, t, want_dx
+        self.x = cases.varied_features(bsz, t, seed=40 + bsz).float()
+        y = synth.synth_labels(bsz, 31, seed=41 + bsz).to(DEV)
+        self.frames = torch.tensor([40, 7, 23, 16, 9], dtype=torch.int32, device=DEV) if frozen else None
+        self.m = m = _model(sd, frozen)
+        m.gru.dropout = dropout
+        got = {}
+        m.zero_grad(set_to_none=True)
+        xd, logits = self.forward()
         logits.register_hook(lambda g: got.__setitem__("dlogits", g.detach().clone()))
-        return xd, logits
+        train_ops.fused_cross_entropy(logits, y).backward()
+        torch.cuda.synchronize()
+        self.dlogits = got["dlogits"]
+        self.grads = {n: p.grad.detach().clone() for n, p in m.named_parameters()}
+        self.dx = xd.grad.detach().clone() if want_dx else None
+        self.bsc = _bsc(m, bsz, t, 1)
 
-    m.zero_grad(set_to_none=True)
-    xd, logits = forward()
-    train_ops.fused_cross_entropy(logits, y).backward()
-    torch.cuda.synchronize()
-    ref_grads = {n: p.grad.detach().clone() for n, p in m.named_parameters()}
-    ref_dx = xd.grad.detach().clone() if want_dx else None
-    ref_bsc = _bsc(m, bsz, t, 1)
-    # the same forward again, then the new entry point by hand on the step's own workspace
-    xd, logits = forward()
-    w, keep = ops.cached_weights(m)
-    buf = train_ops.GradBuffer(m)
-    buf.flat.fill_(float("nan"))
-    dx = torch.full_like(xd, float("nan")) if want_dx else None
-    ws = m._sir_train["ws"].buf
-    seed, p_used = m._sir_last_dropout
-    cfg, _ = train_ops.step_config(m)
-    rc = lib.sir_model_train_bwd_emb(h, C.byref(w), ops._as_features(xd.detach()).data_ptr(), frames.data_ptr() if frozen else None,
-                                     got["dlogits"].data_ptr(), None, bsz, t, p_used, seed, C.byref(cfg), C.byref(buf.struct),
-                                     dx.data_ptr() if want_dx else None, ws.data_ptr(), ws.numel(), _native.BWD_ALL,
-                                     _native.current_stream_ptr())
-    _native.check(rc, "sir_model_train_bwd_emb")
-    torch.cuda.synchronize()
-    assert torch.equal(_bsc(m, bsz, t, 1), ref_bsc)
-    for (n, _), v in zip(m.named_parameters(), buf.views):
+    def forward(self):
+        train_ops.set_dropout_step(5)                    # (every forward of the case draws the same mask)
+        xd = self.x.to(DEV).requires_grad_(self.want_dx)
+        return xd, self.m(xd, lengths=self.frames)
+
+    def by_hand(self, fn):
+        lib, h, m = _native.lib(), get_featurizer().handle, self.m
+        xd, _ = self.forward()
+        w, keep = ops.cached_weights(m)
+        buf = train_ops.GradBuffer(m)
+        buf.flat.fill_(float("nan"))
+        dx = torch.full_like(xd, float("nan")) if self.want_dx else None
+        ws = m._sir_train["ws"].buf
+        seed, p_used = m._sir_last_dropout
+        assert p_used == (m.gru.dropout if m.gru.training else 0.0)
+        cfg, _ = train_ops.step_config(m)
+        head = (h, C.byref(w), ops._as_features(xd.detach()).data_ptr())
+        shape = (self.bsz, self.t, p_used, seed, C.byref(cfg), C.byref(buf.struct))
+        tail = (ws.data_ptr(), ws.numel(), _native.BWD_ALL, _native.current_stream_ptr())
+        dl, dxp = self.dlogits.data_ptr(), dx.data_ptr() if self.want_dx else None
+        fp = self.frames.data_ptr() if self.frames is not None else None
+        if fn == "sir_model_train_bwd_cfg":
+            assert dx is None and fp is None
+            rc = lib.sir_model_train_bwd_cfg(*head, dl, *shape, *tail)
+        elif fn == "sir_model_train_bwd_x":
+            assert fp is None
+            rc = lib.sir_model_train_bwd_x(*head, dl, *shape, dxp, *tail)
+        elif fn == "sir_model_train_bwd_ragged":
+            rc = lib.sir_model_train_bwd_ragged(*head, fp, dl, *shape, dxp, *tail)
+        else:
+            assert fn == "sir_model_train_bwd_emb"
+            rc = lib.sir_model_train_bwd_emb(*head, fp, dl, None, *shape, dxp, *tail)
+        _native.check(rc, fn)
+        torch.cuda.synchronize()
+        return dict(zip((n for n, _ in m.named_parameters()), buf.views)), dx, _bsc(m, self.bsz, self.t, 1)
+
+    def expect_bad_length(self):
+        if self.frames is not None:
+            with pytest.raises(_native.SirError):        # (the length 7: status bit 6, as the ragged step documents)
+                ops.check_status()
+
+
+@pytest.mark.parametrize("bsz,t,frozen,want_dx", NULL_DEMB_CASES)
+def test_null_demb_is_the_existing_backward(sd, bsz, t, frozen, want_dx):
+    """``sir_model_train_bwd_emb`` with ``demb == NULL`` against ``_cfg`` (no dfeats), ``_x`` and ``_ragged`` (one length < 8), both
+    called by hand (the Python node itself calls ``_emb``): all 29 gradients, dfeats and slot 39 ``torch.equal``."""
+    step = _HandStep(sd, bsz, t, frozen, want_dx)
+    ref_grads, ref_dx, ref_bsc = step.by_hand(OLDER[(frozen, want_dx)])
+    grads, dx, bsc = step.by_hand("sir_model_train_bwd_emb")
+    assert torch.equal(bsc, ref_bsc)
+    assert len(grads) == 29
+    for n, v in grads.items():
         assert torch.equal(v, ref_grads[n]), n
     if want_dx:
         assert torch.equal(dx, ref_dx)
-    if frozen:
-        with pytest.raises(_native.SirError):            # (the length 7: status bit 6, as the ragged step documents)
-            ops.check_status()
+    step.expect_bad_length()
+
+
+@pytest.mark.parametrize("bsz,t,frozen,want_dx,dropout", [c + (0.0,) for c in NULL_DEMB_CASES] + [(3, 24, False, False, 0.25)])
+def test_python_step_is_the_older_entry_point(sd, bsz, t, frozen, want_dx, dropout):
+    """What ties the Python node to the C contract: ``m(x, lengths=...)`` then ``fused_cross_entropy(...).backward()`` leaves in every
+    ``.grad`` and in ``x.grad`` the bits of the older entry point the case names, called by hand after the same forward with the
+    seed and ``p`` of ``m._sir_last_dropout`` (the fourth case: with inter-layer dropout 0.25)."""
+    step = _HandStep(sd, bsz, t, frozen, want_dx, dropout)
+    ref_grads, ref_dx, ref_bsc = step.by_hand(OLDER[(frozen, want_dx)])
+    assert torch.equal(step.bsc, ref_bsc)
+    assert len(step.grads) == 29
+    for n, v in step.grads.items():
+        assert torch.equal(v, ref_grads[n]), n
+    if want_dx:
+        assert torch.equal(step.dx, ref_dx)
+    step.expect_bad_length()
 
 
 def _joint_step(m, head, x, y, frames, ce, factor):

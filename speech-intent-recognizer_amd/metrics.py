@@ -49,12 +49,18 @@ def unpack_state(words, num_classes, n_bins):
     out = {"confusion": words[:o].reshape(c, c).copy(), "n": int(words[o]), "topk_correct": words[o + 1: o + 9].copy(),
            "nll_sum": float(words[o + 9: o + 10].view(np.float64)[0])}
     o += 10
-    out["bin_count"] = words[o: o + m].copy()
-    out["bin_correct"] = words[o + m: o + 2 * m].copy()
-    out["bin_conf_sum"] = words[o + 2 * m: o + 3 * m].view(np.float64).copy()
+    out.update(unpack_bins(words, o, m))
     out["n_ignored"] = int(words[o + 3 * m])
     out["n_nonfinite"] = int(words[o + 3 * m + 1])
     return out
+
+
+def unpack_bins(words, o, n_bins):
+    """The three bin tables that start at word ``o`` of a raw state (here and in ``slots.unpack_joint``): ``bin_count`` and
+    ``bin_correct`` int64, ``bin_conf_sum`` the doubles behind their bit patterns."""
+    m = n_bins
+    return {"bin_count": words[o: o + m].copy(), "bin_correct": words[o + m: o + 2 * m].copy(),
+            "bin_conf_sum": words[o + 2 * m: o + 3 * m].view(np.float64).copy()}
 
 
 def _check_state(a):
@@ -77,13 +83,17 @@ def merge(a, b):
     _check_state(b)
     if np.asarray(a["confusion"]).shape != np.asarray(b["confusion"]).shape or len(a["bin_count"]) != len(b["bin_count"]):
         raise ValueError("states of different num_classes or n_bins cannot be merged")
+    return add_fields(a, b, _INT_FIELDS, _FLOAT_FIELDS)
+
+
+def add_fields(a, b, int_fields, float_fields):
+    """``{field: a[field] + b[field]}``, the int fields first (``merge`` here, the joint block of ``slots.merge``): scalars
+    come back as Python ``int`` / ``float``, arrays as ``int64`` / ``float64``."""
     out = {}
-    for k in _INT_FIELDS:
-        s = np.asarray(a[k], dtype=np.int64) + np.asarray(b[k], dtype=np.int64)
-        out[k] = int(s) if s.ndim == 0 else s
-    for k in _FLOAT_FIELDS:
-        s = np.asarray(a[k], dtype=np.float64) + np.asarray(b[k], dtype=np.float64)
-        out[k] = float(s) if s.ndim == 0 else s
+    for fields, dtype, scalar in ((int_fields, np.int64, int), (float_fields, np.float64, float)):
+        for k in fields:
+            s = np.asarray(a[k], dtype=dtype) + np.asarray(b[k], dtype=dtype)
+            out[k] = scalar(s) if s.ndim == 0 else s
     return out
 
 
@@ -176,9 +186,27 @@ def report_from_state(arrays, target_names=None):
     n = int(arrays["n"])
     if int(cm.sum()) != n:
         raise ValueError(f"inconsistent state: the confusion matrix holds {int(cm.sum())} rows, n = {n}")
-    count = np.asarray(arrays["bin_count"], dtype=np.int64)
-    correct = np.asarray(arrays["bin_correct"], dtype=np.float64)
-    conf_sum = np.asarray(arrays["bin_conf_sum"], dtype=np.float64)
+    nan = float("nan")
+    ece, mce, reliability = calibration_from_bins(arrays["bin_count"], arrays["bin_correct"], arrays["bin_conf_sum"], n)
+    topk = np.asarray(arrays["topk_correct"], dtype=np.float64)
+    out = {"n": n, "n_ignored": int(arrays["n_ignored"]), "n_nonfinite": int(arrays["n_nonfinite"]), "confusion": cm,
+           "accuracy": float(np.trace(cm)) / n if n else nan,
+           "topk_accuracy": topk / n if n else np.full(TOPK_SLOTS, nan),
+           "nll": float(arrays["nll_sum"]) / n if n else nan,
+           "classification": classification_from_confusion(cm, target_names),
+           "ece": ece, "mce": mce, "reliability": reliability}
+    for k in (1, 3, 5):
+        out[f"top{k}"] = float(out["topk_accuracy"][k - 1])
+    return out
+
+
+def calibration_from_bins(bin_count, bin_correct, bin_conf_sum, n):
+    """The bin tables of a state of ``n`` rows -> ``(ece, mce, reliability)`` in float64, for ``report_from_state`` and
+    ``slots.joint_report``: per-bin accuracy and confidence are NaN in empty bins, ``ece`` is NaN with no rows counted and
+    ``mce`` with no occupied bin."""
+    count = np.asarray(bin_count, dtype=np.int64)
+    correct = np.asarray(bin_correct, dtype=np.float64)
+    conf_sum = np.asarray(bin_conf_sum, dtype=np.float64)
     m = len(count)
     nan = float("nan")
     occupied = count > 0
@@ -186,32 +214,23 @@ def report_from_state(arrays, target_names=None):
         acc_m = np.where(occupied, correct / count, nan)
         conf_m = np.where(occupied, conf_sum / count, nan)
     gap = np.abs(acc_m - conf_m)
-    topk = np.asarray(arrays["topk_correct"], dtype=np.float64)
-    out = {"n": n, "n_ignored": int(arrays["n_ignored"]), "n_nonfinite": int(arrays["n_nonfinite"]), "confusion": cm,
-           "accuracy": float(np.trace(cm)) / n if n else nan,
-           "topk_accuracy": topk / n if n else np.full(TOPK_SLOTS, nan),
-           "nll": float(arrays["nll_sum"]) / n if n else nan,
-           "classification": classification_from_confusion(cm, target_names),
-           "ece": float(np.sum(np.where(occupied, count * gap, 0.0)) / n) if n else nan,
-           "mce": float(np.max(gap[occupied])) if occupied.any() else nan,
-           "reliability": {"lo": np.arange(m) / m, "hi": (np.arange(m) + 1) / m, "count": count,
-                           "accuracy": acc_m, "confidence": conf_m}}
-    for k in (1, 3, 5):
-        out[f"top{k}"] = float(out["topk_accuracy"][k - 1])
-    return out
+    return (float(np.sum(np.where(occupied, count * gap, 0.0)) / n) if n else nan,
+            float(np.max(gap[occupied])) if occupied.any() else nan,
+            {"lo": np.arange(m) / m, "hi": (np.arange(m) + 1) / m, "count": count, "accuracy": acc_m, "confidence": conf_m})
+
+
+def json_list(v):
+    """An array as a JSON-serialisable list, NaN as None."""
+    return [None if (isinstance(x, float) and x != x) else x for x in np.asarray(v).tolist()]
 
 
 def calibration_json(report):
     """The JSON-serialisable calibration part of ``report_from_state``'s result (``calibration.json`` of evaluate.py)."""
     rel = report["reliability"]
-
-    def lst(v):
-        return [None if (isinstance(x, float) and x != x) else x for x in np.asarray(v).tolist()]
-
     return {"n": report["n"], "n_ignored": report["n_ignored"], "n_nonfinite": report["n_nonfinite"],
             "accuracy": report["accuracy"], "top1": report["top1"], "top3": report["top3"], "top5": report["top5"],
             "nll": report["nll"], "ece": report["ece"], "mce": report["mce"],
-            "reliability": {k: lst(rel[k]) for k in ("lo", "hi", "count", "accuracy", "confidence")}}
+            "reliability": {k: json_list(rel[k]) for k in ("lo", "hi", "count", "accuracy", "confidence")}}
 
 
 def _inv_temperature_tensor(inv_temperature, device):
@@ -244,11 +263,45 @@ def _logits_labels(logits, labels):
     return logits.contiguous(), labels.contiguous()
 
 
-class EvalAccumulator:
+class DeviceState:
+    """The device buffer of ``EvalAccumulator`` and ``slots.SlotEvalAccumulator``: int64 words, all zero until the first update.
+    The accumulator says how many bytes the library wants (``_library_bytes``), how many words its Python layout has
+    (``_layout_words``), what to raise when the two disagree (``_layout_error``) and how its ``_inv_temperature`` becomes a
+    device tensor (``_beta_tensor``)."""
+    _state = None
+    _beta = None
+
+    def _ensure(self, device):
+        import torch
+        from . import _native
+        if self._state is None:
+            nbytes = self._library_bytes()
+            if nbytes != 8 * self._layout_words():
+                raise _native.SirError(self._layout_error)
+            self._state = torch.zeros(nbytes // 8, dtype=torch.int64, device=device)
+            self._beta = self._beta_tensor(self._inv_temperature, device)
+        elif self._state.device != device:
+            raise _native.SirError(f"this accumulator lives on {self._state.device}, the batch on {device}")
+
+    def reset(self):
+        if self._state is not None:
+            self._state.zero_()
+        return self
+
+    def _words(self):
+        """The raw state on the host -- the one device-to-host copy (it waits for the updates queued so far)."""
+        if self._state is None:
+            return np.zeros(self._layout_words(), dtype=np.int64)
+        return self._state.cpu().numpy()
+
+
+class EvalAccumulator(DeviceState):
     """Counts and sums of an evaluation, kept on the device.
 
     ``inv_temperature``: None, a positive number or a device scalar (``fit_temperature``'s result) applied to the logits
     before the softmax; the predictions do not depend on it, the confidences and the NLL do."""
+    _layout_error = "sir_eval_state_bytes disagrees with the layout of sir_amd.metrics"
+    _beta_tensor = staticmethod(_inv_temperature_tensor)
 
     def __init__(self, num_classes, n_bins=15, inv_temperature=None):
         _check_sizes(num_classes, n_bins)
@@ -259,20 +312,13 @@ class EvalAccumulator:
         self.num_classes = int(num_classes)
         self.n_bins = int(n_bins)
         self._inv_temperature = inv_temperature
-        self._beta = None
-        self._state = None
 
-    def _ensure(self, device):
-        import torch
+    def _library_bytes(self):
         from . import _native
-        if self._state is None:
-            nbytes = _native.lib().sir_eval_state_bytes(self.num_classes, self.n_bins)
-            if nbytes != 8 * state_words(self.num_classes, self.n_bins):
-                raise _native.SirError("sir_eval_state_bytes disagrees with the layout of sir_amd.metrics")
-            self._state = torch.zeros(nbytes // 8, dtype=torch.int64, device=device)
-            self._beta = _inv_temperature_tensor(self._inv_temperature, device)
-        elif self._state.device != device:
-            raise _native.SirError(f"this accumulator lives on {self._state.device}, the batch on {device}")
+        return _native.lib().sir_eval_state_bytes(self.num_classes, self.n_bins)
+
+    def _layout_words(self):
+        return state_words(self.num_classes, self.n_bins)
 
     def update(self, logits, labels):
         """Add one batch: logits float32 [B, num_classes], labels int64 [B], both on the device.  One launch on the
@@ -291,18 +337,9 @@ class EvalAccumulator:
         _native.check(rc, "sir_eval_accumulate")
         return self
 
-    def reset(self):
-        if self._state is not None:
-            self._state.zero_()
-        return self
-
     def state_arrays(self):
         """The state as a dict of numpy arrays -- the one device-to-host copy (it waits for the updates queued so far)."""
-        if self._state is None:
-            words = np.zeros(state_words(self.num_classes, self.n_bins), dtype=np.int64)
-        else:
-            words = self._state.cpu().numpy()
-        return unpack_state(words, self.num_classes, self.n_bins)
+        return unpack_state(self._words(), self.num_classes, self.n_bins)
 
     def result(self, target_names=None):
         return report_from_state(self.state_arrays(), target_names)

@@ -2,11 +2,14 @@
 
 ``test_model._result`` runs a softmax, an argmax, two ``.item()`` calls and a host argsort per clip.  ``results_from_logits``
 makes ONE ``sir_classify`` launch and ONE device-to-host copy for all rows and returns dictionaries of the same shape.
-``predict_frontend.predict_many`` and ``IntentRecognizer.recognize_recordings`` take ``on_device=True`` and come here;
+``predict_frontend.predict_many``, ``IntentRecognizer.recognize_recordings`` and ``IntentRecognizer.open_streams`` hand their
+result keywords to one ``ResultOptions`` and get their dictionaries from it;
 ``scripts/test_model.py`` and ``scripts/test_tts_samples.py`` keep their per-row route (DESIGN.md section 4 says why they
 gain no keyword): their batched form is ``predict_frontend.predict_many(..., on_device=True)``, which at the default
 front-end extracts the same features and runs the same forward as ``test_model.predict_many``.
 """
+import dataclasses
+
 import numpy as np
 import torch
 
@@ -40,12 +43,29 @@ def slot_inv_temperature_of(temperature, n_slots):
     return [inv_temperature_of(t) for t in ts]
 
 
+def _to_host(*columns):
+    """The ONE device-to-host copy of a builder: 2-D device columns [B, w] -> one float32 tensor -> one ``.cpu()`` -> the columns
+    back as numpy.  An integer column travels as float32 and comes back int64: class indices and slot labels (<= 63) and
+    prototype rows (<= 4095) are small integers, exact in float32."""
+    packed = torch.cat([c.to(torch.float32) for c in columns], dim=1).cpu().numpy()
+    out, o = [], 0
+    for c in columns:
+        part = packed[:, o: o + c.shape[1]]
+        out.append(part if c.dtype == torch.float32 else part.astype(np.int64))
+        o += c.shape[1]
+    return out
+
+
+def _rejected(value, threshold):
+    """The ``"rejected"`` rule of every builder: below the threshold, or NaN."""
+    return not (value >= threshold)
+
+
 def results_from_slot_logits(logits, spec, k=3, inv_temperature=None, min_confidence=None, table=None, decode="independent"):
     """``results_from_logits`` under a slot layout (``sir_amd.slots.SlotSpec``): ONE ``sir_classify_slots`` launch and ONE
     device-to-host copy for all rows of ``logits`` [B, spec.total] -> list of B dicts: the decoded slots (``{column: value}``)
-    plus ``"predicted_label"`` (the reference's ``action_object`` join when the spec has both columns, else all values joined
-    by ``_``), ``"confidence"`` (the joint confidence: the product of the slots' top probabilities), ``"slot_confidence"``
-    (``{column: probability}``) and ``"top_predictions"`` (``{column: [{"label", "probability"}, ...]}``, ``k`` entries, at most
+    plus ``"predicted_label"`` (``tuple_label``), ``"confidence"`` (the joint confidence: the product of the slots' top
+    probabilities), ``"slot_confidence"`` (``{column: probability}``) and ``"top_predictions"`` (``{column: [{"label", "probability"}, ...]}``, ``k`` entries, at most
     the slot's width).  ``inv_temperature``: None, a number, one per slot, or ``slots.fit_slot_temperatures``' device tensor.
     With ``min_confidence`` set every dict also carries ``"rejected"``: the JOINT confidence is below it (or NaN).
 
@@ -62,23 +82,19 @@ def results_from_slot_logits(logits, spec, k=3, inv_temperature=None, min_confid
         return _joint_results(logits, spec, k, inv_temperature, min_confidence, table)
     idx, prob, joint = slots.classify(logits, spec, k=k, inv_temperature=inv_temperature)
     bsz, g = idx.shape[0], spec.n_slots
-    packed = torch.cat([idx.to(torch.float32).view(bsz, g * k), prob.view(bsz, g * k), joint[:, None]], dim=1).cpu().numpy()
-    idx_h = packed[:, :g * k].astype(np.int64).reshape(bsz, g, k).tolist()          # class indices <= 63 are exact in float32
-    prob_h = packed[:, g * k: 2 * g * k].reshape(bsz, g, k).tolist()
-    joint_h = packed[:, 2 * g * k].tolist()
+    idx_h, prob_h, joint_h = _to_host(idx.view(bsz, g * k), prob.view(bsz, g * k), joint[:, None])
     results = []
-    for row_i, row_p, conf in zip(idx_h, prob_h, joint_h):
+    for row_i, row_p, conf in zip(idx_h.reshape(bsz, g, k).tolist(), prob_h.reshape(bsz, g, k).tolist(), joint_h[:, 0].tolist()):
         res = spec.decode([slot_i[0] for slot_i in row_i])
-        label = spec.reference_label(res)
         top = {}
         for c, vs, slot_i, slot_p in zip(spec.columns, spec.vocab, row_i, row_p):
             n = min(k, len(vs))
             top[c] = [{"label": vs[i] if 0 <= i < len(vs) else "Unknown", "probability": p} for i, p in zip(slot_i[:n], slot_p[:n])]
-        res.update({"predicted_label": label if label is not None else "_".join(res[c] for c in spec.columns),
+        res.update({"predicted_label": tuple_label(spec, res),
                     "confidence": conf, "slot_confidence": {c: slot_p[0] for c, slot_p in zip(spec.columns, row_p)},
                     "top_predictions": top})
         if min_confidence is not None:
-            res["rejected"] = not (conf >= min_confidence)
+            res["rejected"] = _rejected(conf, min_confidence)
         results.append(res)
     return results
 
@@ -107,11 +123,9 @@ def _joint_results(logits, spec, k, inv_temperature, min_confidence, table):
     out = slots.decode(logits, spec, table=table, k=k, inv_temperature=inv_temperature, want_mass=table is not None)
     labels, prob = out[1], out[3]
     bsz, g = labels.shape[0], spec.n_slots
-    cols = [labels.to(torch.float32).view(bsz, k * g), prob] + ([out[4][:, None]] if table is not None else [])
-    packed = torch.cat(cols, dim=1).cpu().numpy()                                     # labels <= 63 are exact in float32
-    lab_h = packed[:, :k * g].astype(np.int64).reshape(bsz, k, g).tolist()
-    prob_h = packed[:, k * g: k * g + k].tolist()
-    mass_h = packed[:, k * g + k].tolist() if table is not None else None
+    host = _to_host(labels.view(bsz, k * g), prob, *([out[4][:, None]] if table is not None else []))
+    lab_h, prob_h = host[0].reshape(bsz, k, g).tolist(), host[1].tolist()
+    mass_h = host[2][:, 0].tolist() if table is not None else None
     results = []
     for b, (row_l, row_p) in enumerate(zip(lab_h, prob_h)):
         res = spec.decode(row_l[0])
@@ -125,7 +139,7 @@ def _joint_results(logits, spec, k, inv_temperature, min_confidence, table):
         if mass_h is not None:
             res["valid_mass"] = mass_h[b]
         if min_confidence is not None:
-            res["rejected"] = not (row_p[0] >= min_confidence)
+            res["rejected"] = _rejected(row_p[0], min_confidence)
         results.append(res)
     return results
 
@@ -166,18 +180,16 @@ def results_from_prototypes(emb, bank, k=3, scale=None, min_similarity=None):
     ``min_similarity`` set every dict also carries ``"rejected"``: the similarity is below it (or NaN)."""
     k = int(k)
     s = bank.score(emb, k=k, scale=scale)
-    packed = torch.cat([s.classes.to(torch.float32), s.nearest.to(torch.float32)[:, None], s.probs, s.sims], dim=1).cpu().numpy()
-    idx_h, near_h = packed[:, :k].astype(np.int64), packed[:, k].astype(np.int64)   # indices <= 4095 are exact in float32
-    prob_h, sim_h = packed[:, k + 1: 2 * k + 1], packed[:, 2 * k + 1:]
+    idx_h, near_h, prob_h, sim_h = _to_host(s.classes, s.nearest[:, None], s.probs, s.sims)
     names = bank.names
     results = []
-    for row_i, near, row_p, row_s in zip(idx_h.tolist(), near_h.tolist(), prob_h.tolist(), sim_h.tolist()):
+    for row_i, near, row_p, row_s in zip(idx_h.tolist(), near_h[:, 0].tolist(), prob_h.tolist(), sim_h.tolist()):
         top = [{"label": names[i] if 0 <= i < len(names) else "Unknown", "probability": p}
                for i, p in zip(row_i, row_p) if not (i < 0 and p == 0.0)]              # (-1 / 0: a rank that does not exist)
         res = {"predicted_label": names[row_i[0]] if 0 <= row_i[0] < len(names) else "Unknown", "confidence": row_p[0],
                "top_predictions": top, "similarity": row_s[0], "nearest": near}
         if min_similarity is not None:
-            res["rejected"] = not (row_s[0] >= min_similarity)
+            res["rejected"] = _rejected(row_s[0], min_similarity)
         results.append(res)
     return results
 
@@ -189,13 +201,69 @@ def results_from_logits(logits, inv_label_map, k=3, inv_temperature=None, min_co
     ``metrics.fit_temperature``'s device scalar) calibrates the probabilities; with ``min_confidence`` set every dict also carries ``"rejected"``: the confidence is below it (or NaN)."""
     k = min(int(k), int(logits.shape[1]))
     idx, prob = ops.classify(logits, k=k, inv_temperature=inv_temperature)
-    packed = torch.cat([idx.to(torch.float32), prob], dim=1).cpu().numpy()      # class indices <= 63 are exact in float32
-    idx_h, prob_h = packed[:, :k].astype(np.int64), packed[:, k:]
+    idx_h, prob_h = _to_host(idx, prob)
     results = []
     for row_i, row_p in zip(idx_h.tolist(), prob_h.tolist()):
         res = {"predicted_label": inv_label_map.get(row_i[0], "Unknown"), "confidence": row_p[0],
                "top_predictions": [{"label": inv_label_map.get(i, "Unknown"), "probability": p} for i, p in zip(row_i, row_p)]}
         if min_confidence is not None:
-            res["rejected"] = not (row_p[0] >= min_confidence)
+            res["rejected"] = _rejected(row_p[0], min_confidence)
         results.append(res)
     return results
+
+
+@dataclasses.dataclass(frozen=True, eq=False)
+class ResultOptions:
+    """The result route of ``predict_frontend.predict_many``, ``IntentRecognizer.recognize_recordings`` and
+    ``IntentRecognizer.open_streams``: their eight result keywords, checked once, and the one place that turns a model output
+    into result dictionaries.  A wrong combination raises ``ValueError`` on construction, before any device call.
+
+    ``on_device``: the dictionaries of a batch come from ``results_from_logits`` (one ``sir_classify`` launch and one copy
+    instead of several host round trips per row); without it every row goes through ``test_model._result``.
+    ``temperature`` (T; probabilities of ``softmax(logits / T)``) and ``min_confidence`` (every dictionary also carries
+    ``"rejected"``) belong to the device route: without ``on_device=True`` they are refused.
+    ``slots`` (a ``sir_amd.slots.SlotSpec``; implies the device route): the logit row is read as slot heads and every result
+    is ``results_from_slot_logits``' dictionary -- decoded slots, joint ``"confidence"``, per-slot tables; ``temperature`` may
+    then hold one T per slot and ``min_confidence`` rejects on the joint value.
+    ``decode="joint"`` (with ``tuples``, a ``slots.TupleTable``: only the tuples that exist) ranks whole label tuples
+    instead: the slots of the best tuple, its probability as ``"confidence"``, the k best tuples, ``"valid_mass"`` under a
+    table, as ``results_from_slot_logits`` describes.  Both need ``slots``.
+    ``prototypes`` (a ``sir_amd.prototypes.PrototypeBank``; implies the device route): the prototype head instead of the
+    ``fc`` head -- the model is asked for embeddings (``embed`` is true) and every result is ``results_from_prototypes``'
+    dictionary, labels from the bank's names, ``"similarity"`` and ``"nearest"`` added; ``min_similarity`` adds ``"rejected"``
+    by distance and needs a bank.  ``prototypes`` with ``slots`` (or with ``temperature`` / ``min_confidence``) is refused.
+
+    After construction ``on_device`` is the resolved route (true under ``slots`` or ``prototypes``)."""
+    on_device: bool = False
+    temperature: object = None
+    min_confidence: object = None
+    slots: object = None
+    tuples: object = None
+    decode: str = "independent"
+    prototypes: object = None
+    min_similarity: object = None
+
+    def __post_init__(self):
+        check_prototypes(self.prototypes, self.min_similarity, self.slots, self.temperature, self.min_confidence)
+        object.__setattr__(self, "on_device", bool(self.on_device or self.slots is not None or self.prototypes is not None))
+        check_route(self.on_device, self.temperature, self.min_confidence)
+        check_decode(self.decode, self.tuples, self.slots is not None)
+        if self.slots is not None:
+            slot_inv_temperature_of(self.temperature, self.slots.n_slots)
+
+    @property
+    def embed(self):
+        """The model is to return embeddings (``model.embed``) instead of logits."""
+        return self.prototypes is not None
+
+    def results(self, output, inv_label_map):
+        """``output`` (logits [B, C], or embeddings [B, 512] under ``embed``) -> list of B result dictionaries; none, and no
+        library call, for an output of zero rows."""
+        if output.shape[0] == 0:
+            return []
+        if self.prototypes is not None:
+            return results_from_prototypes(output, self.prototypes, min_similarity=self.min_similarity)
+        if self.on_device:
+            return results_of(output, inv_label_map, self.slots, self.temperature, self.min_confidence, self.tuples, self.decode)
+        from sir_amd.scripts import test_model                                 # (imported here: it loads the model code)
+        return [test_model._result(output[row:row + 1], inv_label_map) for row in range(output.shape[0])]

@@ -23,7 +23,7 @@ from tqdm import tqdm
 from sir_amd import _native
 from sir_amd.models.models import CNNAudioGRU
 from sir_amd.scripts.dataset import FSCIntentDataset
-from sir_amd.scripts.train import collate_fn
+from sir_amd.scripts.train import collate_fn, loader_kwargs
 
 logging.basicConfig(level=logging.INFO, format="%(asctime)s - %(levelname)s - %(message)s")
 logger = logging.getLogger(__name__)
@@ -32,6 +32,43 @@ logger = logging.getLogger(__name__)
 def load_config(config_path):
     with open(config_path, "r") as f:
         return yaml.safe_load(f)
+
+
+def load_checkpoint(model_path, num_classes, device):
+    """A checkpoint (the reference's bare ``state_dict``, or a training checkpoint's ``model_state_dict``) in a
+    ``CNNAudioGRU(num_classes)`` on ``device``."""
+    model = CNNAudioGRU(num_classes=num_classes).to(device)
+    state = torch.load(model_path, map_location=device)
+    if isinstance(state, dict) and "model_state_dict" in state:
+        state = state["model_state_dict"]
+    model.load_state_dict(state)
+    return model
+
+
+def build_loader(csv_path, config, frontend, label_map_path=None, slot_spec=None):
+    """The evaluation loader of a CSV split (not shuffled, no augmentation) from the run's config keys and its front-end; the
+    labels come from the label map, or from ``slot_spec`` as [G] rows."""
+    dataset = FSCIntentDataset(csv_path=csv_path, label_map_path=label_map_path, is_training=False,
+                               use_cache=config.get("use_feature_cache", True),
+                               cache_dir=config.get("cache_dir", "data/cached_features"),
+                               mel_spec_length=int(config.get("mel_spec_length", 200)),
+                               n_fft=frontend.n_fft, hop_length=frontend.hop_length, win_length=frontend.win_length,
+                               slot_spec=slot_spec)
+    return DataLoader(dataset, batch_size=config.get("batch_size", 32), shuffle=False, collate_fn=collate_fn,
+                      **loader_kwargs(config.get("num_workers", 4)))
+
+
+def results_dir_of(config):
+    results_dir = os.path.join(config["save_path"], "evaluation_results")
+    os.makedirs(results_dir, exist_ok=True)
+    return results_dir
+
+
+def write_report(results_dir, name, headline, text):
+    """``name`` in ``results_dir``: the headline, a blank line, the report's text."""
+    with open(os.path.join(results_dir, name), "w") as f:
+        f.write(f"{headline}\n\n")
+        f.write(text)
 
 
 @torch.no_grad()
@@ -47,66 +84,55 @@ def predict_loader(model, loader, device, device_metrics=None, collect_logits=Fa
     accumulators ``slots.SlotEvalAccumulator``s: labels are then [B, G] and the state holds the slots' states and the joint block;
     with the further key ``tuples`` (a ``slots.TupleTable``) every batch is also decoded over that table
     (``slots.ConstrainedEvalAccumulator``) and the state gains the key ``constrained``."""
+    from sir_amd import metrics, ops, slots
     from sir_amd.pipeline import BatchPipeline
+    from sir_amd.scripts.train import HostStager
     model.eval()
     pipe = BatchPipeline(model, n_streams=2)          # consecutive batches alternate over two HIP streams
-    preds, labels = [], []
-    if device_metrics is not None or collect_logits:
-        accs = cons = None
-        if device_metrics is not None:
-            device_metrics = dict(device_metrics)
-            table = device_metrics.pop("tuples", None)
-            if "spec" in device_metrics:
-                from sir_amd.slots import ConstrainedEvalAccumulator, SlotEvalAccumulator as EvalAccumulator
-                if table is not None:
-                    cons = [ConstrainedEvalAccumulator(table=table, **device_metrics) for _ in range(pipe.n)]
-            else:
-                from sir_amd.metrics import EvalAccumulator
-            accs = [EvalAccumulator(**device_metrics) for _ in range(pipe.n)]
-        return _predict_loader_device(model, loader, device, pipe, accs, collect_logits, cons)
-    from sir_amd.scripts.train import HostStager
     stage = HostStager(device, slots=4)               # host batches: persistent pinned ring (see HostStager)
+    on_host = device_metrics is None and not collect_logits
+    accs = cons = None
+    if device_metrics is not None:
+        device_metrics = dict(device_metrics)
+        table = device_metrics.pop("tuples", None)
+        if "spec" in device_metrics:
+            accumulator = slots.SlotEvalAccumulator
+            if table is not None:
+                cons = [slots.ConstrainedEvalAccumulator(table=table, **device_metrics) for _ in range(pipe.n)]
+        else:
+            accumulator = metrics.EvalAccumulator
+        accs = [accumulator(**device_metrics) for _ in range(pipe.n)]
+    outputs, labels = [], []              # the host route's predictions, or the logits ``collect_logits`` asks for
+
+    def keep_predictions(slot, out, label):
+        outputs.append(out[1])
+        labels.append(label)
+
+    def accumulate(slot, out, label):
+        lab = label.to(device=device, dtype=torch.int64, non_blocking=True)
+        if accs is not None:
+            accs[slot].update(out[0], lab)
+        if cons is not None:
+            cons[slot].update(out[0], label)              # (the host labels: the table rows are looked up there)
+        if collect_logits:
+            outputs.append(out[0])
+            labels.append(lab)
+
+    take = keep_predictions if on_host else accumulate
     for i, (mel, label) in enumerate(tqdm(loader, desc="Evaluating")):
         if mel is None or label is None or mel.size(0) == 0:
             continue                      # the reference would crash here (evaluate.py:81); skip instead
-        _, pred = pipe.infer(i, stage(mel))
-        preds.append(pred)
-        labels.append(label)
-    if not preds:
+        pipe.infer(i, stage(mel), then=lambda slot, out, label=label: take(slot, out, label))
+    if on_host and not outputs:
         return [], []
     pipe.synchronize()
-    from sir_amd import ops
-    ops.check_status()                    # a timed-out GRU recurrence would have produced invalid predictions: raise
-    return torch.cat(preds).cpu().numpy(), torch.cat(labels).numpy()
-
-
-def _predict_loader_device(model, loader, device, pipe, accs, collect_logits, cons=None):
-    from sir_amd import ops
-    from sir_amd.scripts.train import HostStager
-    stage = HostStager(device, slots=4)
-    logits_all, labels_all = [], []
-    for i, (mel, label) in enumerate(tqdm(loader, desc="Evaluating")):
-        if mel is None or label is None or mel.size(0) == 0:
-            continue
-
-        def then(slot, out, label=label):
-            lab = label.to(device=device, dtype=torch.int64, non_blocking=True)
-            if accs is not None:
-                accs[slot].update(out[0], lab)
-            if cons is not None:
-                cons[slot].update(out[0], label)          # (the host labels: the table rows are looked up there)
-            if collect_logits:
-                logits_all.append(out[0])
-                labels_all.append(lab)
-
-        pipe.infer(i, stage(mel), then=then)
-    pipe.synchronize()
-    ops.check_status()                    # a timed-out recurrence, or a label outside the classes
+    ops.check_status()                    # a timed-out GRU recurrence (invalid predictions), or a label outside the classes: raise
+    if on_host:
+        return torch.cat(outputs).cpu().numpy(), torch.cat(labels).numpy()
     if collect_logits:
-        if not logits_all:
+        if not outputs:
             return None, None
-        return torch.cat(logits_all), torch.cat(labels_all)
-    from sir_amd import metrics, slots
+        return torch.cat(outputs), torch.cat(labels)
     merge = slots.merge if isinstance(accs[0], slots.SlotEvalAccumulator) else metrics.merge
     state = accs[0].state_arrays()
     for a in accs[1:]:
@@ -167,33 +193,18 @@ def evaluate_slots(args, config):
     _native.require_hip()
     from sir_amd.dist_utils import limit_host_threads
     from sir_amd.frontend_config import FrontEnd
-    from sir_amd.scripts.train import loader_kwargs
     limit_host_threads(reserve=int(config.get("num_workers", 4)))
     device = torch.device("cuda", torch.cuda.current_device())
-    model = CNNAudioGRU(num_classes=spec.total).to(device)
-    state = torch.load(args.model_path, map_location=device)
-    if isinstance(state, dict) and "model_state_dict" in state:
-        state = state["model_state_dict"]
-    model.load_state_dict(state)
-    fe = FrontEnd.from_config(config)
-    test_dataset = FSCIntentDataset(csv_path=args.test_csv, label_map_path=None, is_training=False,
-                                    use_cache=config.get("use_feature_cache", True),
-                                    cache_dir=config.get("cache_dir", "data/cached_features"),
-                                    mel_spec_length=int(config.get("mel_spec_length", 200)),
-                                    n_fft=fe.n_fft, hop_length=fe.hop_length, win_length=fe.win_length, slot_spec=spec)
-    test_loader = DataLoader(test_dataset, batch_size=config.get("batch_size", 32), shuffle=False, collate_fn=collate_fn,
-                             **loader_kwargs(config.get("num_workers", 4)))
+    model = load_checkpoint(args.model_path, spec.total, device)
+    test_loader = build_loader(args.test_csv, config, FrontEnd.from_config(config), slot_spec=spec)
     _, _, arrays = predict_loader(model, test_loader, device,
                                   device_metrics={"spec": spec, "n_bins": int(config.get("calibration_bins", 15)), "tuples": table})
-    results_dir = os.path.join(config["save_path"], "evaluation_results")
-    os.makedirs(results_dir, exist_ok=True)
+    results_dir = results_dir_of(config)
     for column, vocab, a in zip(spec.columns, spec.vocab, arrays["slots"]):
         report = metrics.report_from_state(a, list(vocab))
         text = metrics.format_report(report["classification"])
         logger.info(f"Slot {column}: accuracy {report['accuracy']:.4f}\n{text}")
-        with open(os.path.join(results_dir, f"classification_report_{column}.txt"), "w") as f:
-            f.write(f"Test Accuracy: {report['accuracy']:.4f}\n\n")
-            f.write(text)
+        write_report(results_dir, f"classification_report_{column}.txt", f"Test Accuracy: {report['accuracy']:.4f}", text)
         with open(os.path.join(results_dir, f"calibration_{column}.json"), "w") as f:
             json.dump(metrics.calibration_json(report), f, indent=2)
     joint = slots.joint_report(arrays["joint"])
@@ -204,9 +215,8 @@ def evaluate_slots(args, config):
         with open(os.path.join(results_dir, "constrained_metrics.json"), "w") as f:
             json.dump(cons, f, indent=2)
         if text is not None:
-            with open(os.path.join(results_dir, "classification_report_intents.txt"), "w") as f:
-                f.write(f"Exact-match accuracy (constrained): {cons['exact_match_accuracy']:.4f}\n\n")
-                f.write(text)
+            write_report(results_dir, "classification_report_intents.txt",
+                         f"Exact-match accuracy (constrained): {cons['exact_match_accuracy']:.4f}", text)
         logger.info(f"Constrained to {len(table)} tuples: exact-match accuracy {cons['exact_match_accuracy']:.4f} over {cons['n']} clips, "
                     f"mean valid mass {cons['mean_valid_mass']:.4f}")
     logger.info(f"Exact-match accuracy {joint['exact_match_accuracy']:.4f} over {joint['n']} clips ({joint['n_excluded']} excluded), "
@@ -268,31 +278,14 @@ def evaluate(args, config):
         label_map = json.load(f)
     inv_label_map = {v: k for k, v in label_map.items()}
     num_classes = len(label_map)
-    model = CNNAudioGRU(num_classes=31).to(device)          # 31-way head of the shipped model (evaluate.py:45)
-    state = torch.load(args.model_path, map_location=device)
-    if isinstance(state, dict) and "model_state_dict" in state:
-        state = state["model_state_dict"]
-    model.load_state_dict(state)
+    model = load_checkpoint(args.model_path, 31, device)    # 31-way head of the shipped model (evaluate.py:45)
     logger.info(f"Loaded model from {args.model_path}")
     from sir_amd.frontend_config import FrontEnd
     fe = FrontEnd.from_config(config)       # the checkpoint does not record its front-end: the keys must accompany it
-    test_dataset = FSCIntentDataset(csv_path=args.test_csv, label_map_path=args.label_map, is_training=False,
-                                    use_cache=config.get("use_feature_cache", True),
-                                    cache_dir=config.get("cache_dir", "data/cached_features"),
-                                    mel_spec_length=int(config.get("mel_spec_length", 200)),
-                                    n_fft=fe.n_fft, hop_length=fe.hop_length, win_length=fe.win_length)
-    from sir_amd.scripts.train import loader_kwargs
-    test_loader = DataLoader(test_dataset, batch_size=config.get("batch_size", 32), shuffle=False, collate_fn=collate_fn,
-                             **loader_kwargs(config.get("num_workers", 4)))
+    test_loader = build_loader(args.test_csv, config, fe, args.label_map)
     inv_temperature = None
     if getattr(args, "fit_temperature", None):
-        valid_dataset = FSCIntentDataset(csv_path=args.fit_temperature, label_map_path=args.label_map, is_training=False,
-                                         use_cache=config.get("use_feature_cache", True),
-                                         cache_dir=config.get("cache_dir", "data/cached_features"),
-                                         mel_spec_length=int(config.get("mel_spec_length", 200)),
-                                         n_fft=fe.n_fft, hop_length=fe.hop_length, win_length=fe.win_length)
-        valid_loader = DataLoader(valid_dataset, batch_size=config.get("batch_size", 32), shuffle=False, collate_fn=collate_fn,
-                                  **loader_kwargs(config.get("num_workers", 4)))
+        valid_loader = build_loader(args.fit_temperature, config, fe, args.label_map)
         out_path = os.path.join(os.path.dirname(os.path.abspath(args.model_path)), "temperature.json")
         inv_temperature = fit_temperature_file(model, valid_loader, device, out_path,
                                                source=os.path.basename(args.fit_temperature))["inv_temperature"]
@@ -315,11 +308,8 @@ def evaluate(args, config):
                                        zero_division=0)
     logger.info(f"Classification Report:\n{cls_report}")
     cm = confusion_matrix(all_labels, all_preds, labels=labels_idx)
-    results_dir = os.path.join(config["save_path"], "evaluation_results")
-    os.makedirs(results_dir, exist_ok=True)
-    with open(os.path.join(results_dir, "classification_report.txt"), "w") as f:
-        f.write(f"Test Accuracy: {accuracy:.4f}\n\n")
-        f.write(cls_report)
+    results_dir = results_dir_of(config)
+    write_report(results_dir, "classification_report.txt", f"Test Accuracy: {accuracy:.4f}", cls_report)
     _plot_confusion(cm, target_names, results_dir)
     logger.info(f"Evaluation results saved to {results_dir}")
     return accuracy
@@ -357,12 +347,9 @@ def _evaluate_on_device(model, test_loader, device, config, inv_label_map, num_c
     target_names = [inv_label_map[i] for i in labels_idx]
     cls_report = metrics.format_report(metrics.classification_from_confusion(state["confusion"], target_names, labels=labels_idx))
     logger.info(f"Classification Report:\n{cls_report}")
-    results_dir = os.path.join(config["save_path"], "evaluation_results")
-    os.makedirs(results_dir, exist_ok=True)
-    with open(os.path.join(results_dir, "classification_report.txt"), "w") as f:
-        f.write(f"Test Accuracy: {accuracy:.4f}\n\n")
-        f.write(cls_report)
-    calib = metrics.calibration_json(report)
+    results_dir = results_dir_of(config)
+    write_report(results_dir, "classification_report.txt", f"Test Accuracy: {accuracy:.4f}", cls_report)
+    calib =metrics.calibration_json(report)
     calib["inv_temperature"] = 1.0 if inv_temperature is None else float(inv_temperature)
     with open(os.path.join(results_dir, "calibration.json"), "w") as f:
         json.dump(calib, f, indent=2)

@@ -36,24 +36,10 @@ def predict_many(model, audio_paths, label_map, device, pad_to=test_model.MAX_LE
                  temperature=None, min_confidence=None, slots=None, tuples=None, decode="independent", prototypes=None,
                  min_similarity=None):
     """One feature pass at ``frontend`` and one forward for all files -> list of result dictionaries / ``None``.
-    ``pad_to=None`` needs a single file (un-padded features, ``T >= 8``).  ``on_device``, ``temperature``, ``min_confidence``:
-    the results come from ``classify_results.results_from_logits`` (one ``sir_classify`` launch and one copy for the batch instead of
-    several host round trips per file); ``temperature`` (T; probabilities of ``softmax(logits / T)``) and ``min_confidence`` (adds
-    ``"rejected"``) belong to that route: without ``on_device=True`` they raise ``ValueError``.  ``slots`` (a ``sir_amd.slots.SlotSpec``; implies the
-    device route): the model's logit row is read as slot heads and every result is ``classify_results.results_from_slot_logits``'
-    dictionary -- decoded slots, joint ``"confidence"``, per-slot tables; ``temperature`` may then hold one T per slot and
-    ``min_confidence`` rejects on the joint value.  ``decode="joint"`` (with ``tuples``, a ``slots.TupleTable``: only the tuples
-    that exist) ranks whole label tuples instead, as ``results_from_slot_logits`` describes.  ``prototypes`` (a
-    ``sir_amd.prototypes.PrototypeBank``; implies the device route): the prototype head instead of the ``fc`` head -- the model
-    returns embeddings (``model.embed``) and every result is ``classify_results.results_from_prototypes``' dictionary, labels
-    from the bank's names, ``"similarity"`` and ``"nearest"`` added; ``min_similarity`` adds ``"rejected"`` by distance.
-    ``prototypes`` with ``slots`` (or with ``temperature`` / ``min_confidence``) raises ``ValueError``."""
-    classify_results.check_prototypes(prototypes, min_similarity, slots, temperature, min_confidence)
-    on_device = on_device or slots is not None or prototypes is not None
-    classify_results.check_route(on_device, temperature, min_confidence)       # a caller's mistake: raised, not logged
-    classify_results.check_decode(decode, tuples, slots is not None)
-    if slots is not None:
-        classify_results.slot_inv_temperature_of(temperature, slots.n_slots)   # (likewise, before any device call)
+    ``pad_to=None`` needs a single file (un-padded features, ``T >= 8``).  ``on_device`` ... ``min_similarity`` are the
+    result route, described once on ``classify_results.ResultOptions``: a wrong combination raises ``ValueError`` (a caller's
+    mistake: raised, not logged), before any device call."""
+    opts = classify_results.ResultOptions(on_device, temperature, min_confidence, slots, tuples, decode, prototypes, min_similarity)
     audio_paths = list(audio_paths)
     try:
         feats = get_extractor(frontend).extract_batch(audio_paths, max_duration=600.0)
@@ -68,17 +54,9 @@ def predict_many(model, audio_paths, label_map, device, pad_to=test_model.MAX_LE
         else:
             batch = torch.stack([test_model._pad_or_trim(feats[i].unsqueeze(0), pad_to)[0] for i in keep]).to(device)
         with torch.no_grad():
-            output = model.embed(batch) if prototypes is not None else model(batch)
-        inv = {v: k for k, v in label_map.items()}
-        if prototypes is not None:
-            for res, i in zip(classify_results.results_from_prototypes(output, prototypes, min_similarity=min_similarity), keep):
-                results[i] = res
-        elif on_device:
-            for res, i in zip(classify_results.results_of(output, inv, slots, temperature, min_confidence, tuples, decode), keep):
-                results[i] = res
-        else:
-            for row, i in enumerate(keep):
-                results[i] = test_model._result(output[row:row + 1], inv)
+            output = model.embed(batch) if opts.embed else model(batch)
+        for res, i in zip(opts.results(output, {v: k for k, v in label_map.items()}), keep):
+            results[i] = res
         ops.check_status()
         return results
     except Exception as e:

@@ -23,7 +23,7 @@ import torch
 from sir_amd import ops
 from sir_amd.frontend_config import as_frontend
 from sir_amd.segmenter import Segmenter
-from sir_amd.scripts import test_model, test_tts_samples
+from sir_amd.scripts import classify_results, test_model, test_tts_samples
 
 logger = logging.getLogger(__name__)
 
@@ -167,27 +167,10 @@ class IntentRecognizer:
         files (decoded, mixed to mono and resampled on the GPU).  -> per recording, the list of its utterances in time order:
         ``{"start": seconds, "end": seconds, "predicted_label", "confidence", "top_predictions"}``; ``None`` for the recordings of
         a group that failed (logged, as the reference's ``predict`` does).
-        ``on_device=True``: softmax, confidence and top-3 of all utterances of a group come from one ``sir_classify`` launch and
-        one copy (``classify_results.results_from_logits``) instead of several host round trips per utterance; ``temperature`` (T,
-        probabilities of ``softmax(logits / T)``) and ``min_confidence`` (every utterance also carries ``"rejected"``) belong
-        to that route: without ``on_device=True`` they raise ``ValueError``.
-        ``slots`` (a ``sir_amd.slots.SlotSpec``; implies the device route): the logit row is read as slot heads and every
-        utterance carries ``classify_results.results_from_slot_logits``' dictionary instead (decoded slots, joint
-        ``"confidence"``, per-slot tables); ``temperature`` may hold one T per slot, ``min_confidence`` rejects on the joint value.
-        ``decode="joint"`` (with ``tuples``, a ``slots.TupleTable``: only the tuples that exist) ranks whole label tuples
-        instead: the slots of the best tuple, its probability as ``"confidence"``, the k best tuples, ``"valid_mass"`` under a
-        table (``classify_results.results_from_slot_logits``).  ``StreamSession.feed`` takes the same arguments.
-        ``prototypes`` (a ``sir_amd.prototypes.PrototypeBank``; implies the device route): the prototype head instead of the
-        ``fc`` head -- every utterance carries ``classify_results.results_from_prototypes``' dictionary (labels from the bank,
-        ``"similarity"``, ``"nearest"``), ``min_similarity`` adds ``"rejected"`` by distance; with ``slots`` it raises
-        ``ValueError``."""
-        from sir_amd.scripts import classify_results
-        classify_results.check_prototypes(prototypes, min_similarity, slots, temperature, min_confidence)
-        on_device = on_device or slots is not None or prototypes is not None
-        classify_results.check_route(on_device, temperature, min_confidence)
-        classify_results.check_decode(decode, tuples, slots is not None)
-        if slots is not None:
-            classify_results.slot_inv_temperature_of(temperature, slots.n_slots)
+        ``on_device`` ... ``min_similarity`` are the result route of every utterance's dictionary, described once on
+        ``classify_results.ResultOptions``; a wrong combination raises ``ValueError`` before any device call.  With
+        ``on_device=True`` the utterances of a group share one launch and one copy."""
+        opts = classify_results.ResultOptions(on_device, temperature, min_confidence, slots, tuples, decode, prototypes, min_similarity)
         items = list(waves_or_paths)
         results = [None] * len(items)
         sr = float(self.segmenter.sample_rate)
@@ -195,15 +178,9 @@ class IntentRecognizer:
             group = items[g:g + GROUP]
             try:
                 wave, lens = self._load_group(group)
-                table, logits = self.score_segments(wave, lens, pad_to=pad_to, logits_on_device=on_device, embed=prototypes is not None)
+                table, logits = self.score_segments(wave, lens, pad_to=pad_to, logits_on_device=opts.on_device, embed=opts.embed)
                 found = [[] for _ in group]
-                batch_res = None
-                if prototypes is not None and table.shape[0] > 0:
-                    batch_res = classify_results.results_from_prototypes(logits, prototypes, min_similarity=min_similarity)
-                elif on_device and table.shape[0] > 0:
-                    batch_res = classify_results.results_of(logits, self.inv_label_map, slots, temperature, min_confidence, tuples, decode)
-                for row, (r, a, b) in enumerate(table.tolist()):
-                    res = batch_res[row] if batch_res is not None else test_model._result(logits[row:row + 1], self.inv_label_map)
+                for (r, a, b), res in zip(table.tolist(), opts.results(logits, self.inv_label_map)):
                     found[r].append({"start": a / sr, "end": b / sr, **res})
                 results[g:g + len(group)] = found
             except Exception as e:
@@ -217,8 +194,8 @@ class IntentRecognizer:
         """What ``MicrophoneListener.listen`` + ``predict`` do for one microphone (testing.py:49-143), for ``n_streams`` sources
         that deliver at most ``max_push`` samples of ``dtype`` (float32 unless given) per ``feed``: -> a ``StreamSession``.  The
         detector takes the listener values of this recogniser's ``segmenter``; an utterance longer than ``max_utterance`` seconds
-        is ended there.  ``pad_to`` / ``on_device`` / ``temperature`` / ``min_confidence`` / ``slots`` / ``tuples`` / ``decode`` /
-        ``prototypes`` / ``min_similarity`` as in ``recognize_recordings``: the session builds its dictionaries through the same ``classify_results.results_of``.
+        is ended there.  ``pad_to`` as in ``recognize_recordings``; ``on_device`` ... ``min_similarity`` are the session's
+        result route (``classify_results.ResultOptions``, as there).
         ``sample_rate`` (Hz, default the segmenter's) / ``encoding`` ("pcm", "ulaw", "alaw"; default "pcm"): the callers' own rate
         and codec -- e.g. 8000 and "ulaw" for G.711 telephony, fed as bytes.  The streams are then decoded and rate-converted on
         the GPU with carried filter state (``sir_amd.streaming.StreamInput``), ``max_push`` counts the callers' samples, and
@@ -232,14 +209,9 @@ class StreamSession:
 
     def __init__(self, recognizer, n_streams, max_push, max_utterance, dtype, pad_to, on_device, temperature, min_confidence,
                  sample_rate=None, encoding=None, slots=None, tuples=None, decode="independent", prototypes=None, min_similarity=None):
-        from sir_amd.scripts import classify_results
+        self.opts = classify_results.ResultOptions(on_device, temperature, min_confidence, slots, tuples, decode, prototypes,
+                                                   min_similarity)
         from sir_amd.streaming import StreamSegmenter
-        classify_results.check_prototypes(prototypes, min_similarity, slots, temperature, min_confidence)
-        on_device = on_device or slots is not None or prototypes is not None
-        classify_results.check_route(on_device, temperature, min_confidence)
-        classify_results.check_decode(decode, tuples, slots is not None)
-        if slots is not None:
-            classify_results.slot_inv_temperature_of(temperature, slots.n_slots)
         seg = recognizer.segmenter
         self.recognizer = recognizer
         if dtype is None and encoding in (None, "pcm"):
@@ -249,9 +221,6 @@ class StreamSession:
                                          prior_recording=seg.prior_recording, flush_tail=seg.flush_tail, input_rate=sample_rate,
                                          encoding=encoding)
         self.pad_to = recognizer.mel_spec_length if pad_to == TRAINED_LENGTH else pad_to
-        self.on_device, self.temperature, self.min_confidence = on_device, temperature, min_confidence
-        self.slots, self.tuples, self.decode = slots, tuples, decode
-        self.prototypes, self.min_similarity = prototypes, min_similarity
         self.last_logits = None
 
     def feed(self, chunks, lengths=None, close=()):
@@ -262,7 +231,6 @@ class StreamSession:
         ``max_utterance`` and was cut there); ``start`` / ``end`` count from the stream's last close.  ``last_logits`` holds the
         logits of the utterances the latest call returned, row for row (None if there were none; with ``prototypes`` their
         embeddings)."""
-        from sir_amd.scripts import classify_results
         seg, reco = self.segmenter, self.recognizer
         if isinstance(chunks, dict):
             np_dtype = torch.empty(0, dtype=seg.dtype).numpy().dtype
@@ -289,19 +257,10 @@ class StreamSession:
             return []
         longest = int((host_table[:, 2] - host_table[:, 1]).max())
         clips, clip_lens = seg.gather(table, total, max(1, min(longest, reco._clip_limit(self.pad_to))))
-        logits = self.last_logits = reco._score_clips(clips, clip_lens, self.pad_to, self.on_device, self.prototypes is not None)
-        batch_res = None
-        if self.prototypes is not None:
-            batch_res = classify_results.results_from_prototypes(logits, self.prototypes, min_similarity=self.min_similarity)
-        elif self.on_device:
-            batch_res = classify_results.results_of(logits, reco.inv_label_map, self.slots, self.temperature, self.min_confidence,
-                                                    self.tuples, self.decode)
+        logits = self.last_logits = reco._score_clips(clips, clip_lens, self.pad_to, self.opts.on_device, self.opts.embed)
         sr = float(seg.sample_rate)
-        found = []
-        for row, (s, a, b, flag) in enumerate(host_table.tolist()):
-            res = batch_res[row] if batch_res is not None else test_model._result(logits[row:row + 1], reco.inv_label_map)
-            found.append({"stream": s, "forced": bool(flag & 1), "start": a / sr, "end": b / sr, **res})
-        return found
+        return [{"stream": s, "forced": bool(flag & 1), "start": a / sr, "end": b / sr, **res}
+                for (s, a, b, flag), res in zip(host_table.tolist(), self.opts.results(logits, reco.inv_label_map))]
 
     def close(self, streams):
         """End ``streams`` without new samples: their open utterances are flushed and scored, the slots start again at 0."""

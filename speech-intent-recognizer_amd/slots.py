@@ -608,9 +608,7 @@ def unpack_joint(words, n_bins):
     out = {"n": int(words[0]), "exact_match": int(words[1]), "slots_correct": words[2: o].copy(),
            "nll_sum": float(words[o: o + 1].view(np.float64)[0])}
     o += 1
-    out["bin_count"] = words[o: o + m].copy()
-    out["bin_correct"] = words[o + m: o + 2 * m].copy()
-    out["bin_conf_sum"] = words[o + 2 * m: o + 3 * m].view(np.float64).copy()
+    out.update(metrics.unpack_bins(words, o, m))
     out["n_excluded"] = int(words[o + 3 * m])
     return out
 
@@ -633,13 +631,7 @@ def merge(a, b):
     """The state of the rows of ``a`` and ``b`` together (per-rank shards): every field adds."""
     if len(a["slots"]) != len(b["slots"]) or len(a["joint"]["bin_count"]) != len(b["joint"]["bin_count"]):
         raise ValueError("states of different slot layouts or n_bins cannot be merged")
-    joint = {}
-    for k in _JOINT_INT_FIELDS:
-        s = np.asarray(a["joint"][k], dtype=np.int64) + np.asarray(b["joint"][k], dtype=np.int64)
-        joint[k] = int(s) if s.ndim == 0 else s
-    for k in _JOINT_FLOAT_FIELDS:
-        s = np.asarray(a["joint"][k], dtype=np.float64) + np.asarray(b["joint"][k], dtype=np.float64)
-        joint[k] = float(s) if s.ndim == 0 else s
+    joint = metrics.add_fields(a["joint"], b["joint"], _JOINT_INT_FIELDS, _JOINT_FLOAT_FIELDS)
     return {"slots": [metrics.merge(x, y) for x, y in zip(a["slots"], b["slots"])], "joint": joint}
 
 
@@ -647,62 +639,44 @@ def joint_report(joint):
     """``{n, exact_match_accuracy, nll, ece, mce, slots_correct, n_excluded}`` (+ ``reliability``) from the joint block, in
     float64; ECE / MCE are those of ``metrics.report_from_state`` with the joint confidence and exact match as "correct"."""
     n = int(joint["n"])
-    count = np.asarray(joint["bin_count"], dtype=np.int64)
-    correct = np.asarray(joint["bin_correct"], dtype=np.float64)
-    conf_sum = np.asarray(joint["bin_conf_sum"], dtype=np.float64)
-    if int(count.sum()) != n or int(np.asarray(joint["slots_correct"]).sum()) != n:
+    if int(np.asarray(joint["bin_count"], dtype=np.int64).sum()) != n or int(np.asarray(joint["slots_correct"]).sum()) != n:
         raise ValueError("inconsistent joint block: the bins or slots_correct do not add up to n")
-    m = len(count)
     nan = float("nan")
-    occupied = count > 0
-    with np.errstate(divide="ignore", invalid="ignore"):
-        acc_m = np.where(occupied, correct / count, nan)
-        conf_m = np.where(occupied, conf_sum / count, nan)
-    gap = np.abs(acc_m - conf_m)
+    ece, mce, reliability = metrics.calibration_from_bins(joint["bin_count"], joint["bin_correct"], joint["bin_conf_sum"], n)
     return {"n": n, "n_excluded": int(joint["n_excluded"]),
             "exact_match_accuracy": int(joint["exact_match"]) / n if n else nan,
             "nll": float(joint["nll_sum"]) / n if n else nan,
-            "ece": float(np.sum(np.where(occupied, count * gap, 0.0)) / n) if n else nan,
-            "mce": float(np.max(gap[occupied])) if occupied.any() else nan,
+            "ece": ece, "mce": mce,
             "slots_correct": np.asarray(joint["slots_correct"], dtype=np.int64),
-            "reliability": {"lo": np.arange(m) / m, "hi": (np.arange(m) + 1) / m, "count": count,
-                            "accuracy": acc_m, "confidence": conf_m}}
+            "reliability": reliability}
 
 
 def joint_json(report):
     """The JSON-serialisable form of ``joint_report``'s result (``joint_metrics.json`` of scripts/evaluate.py)."""
-    def lst(v):
-        return [None if (isinstance(x, float) and x != x) else x for x in np.asarray(v).tolist()]
-
     out = {k: report[k] for k in ("n", "n_excluded", "exact_match_accuracy", "nll", "ece", "mce")}
-    out["slots_correct"] = lst(report["slots_correct"])
-    out["reliability"] = {k: lst(v) for k, v in report["reliability"].items()}
+    out["slots_correct"] = metrics.json_list(report["slots_correct"])
+    out["reliability"] = {k: metrics.json_list(v) for k, v in report["reliability"].items()}
     return out
 
 
-class SlotEvalAccumulator:
+class SlotEvalAccumulator(metrics.DeviceState):
     """``metrics.EvalAccumulator`` under a slot layout: one device buffer holding a single-head state per slot and the joint
     block, filled by ``sir_eval_accumulate_slots`` batch by batch with no copy and no synchronisation."""
+    _layout_error = "sir_eval_slots_state_bytes disagrees with the layout of sir_amd.slots"
+    _beta_tensor = staticmethod(_beta_tensor)
 
     def __init__(self, spec, n_bins=15, inv_temperature=None):
         self.spec = _as_spec(spec)
         metrics._check_sizes(1, n_bins)
         self.n_bins = int(n_bins)
         self._inv_temperature = check_inv_temperature(inv_temperature, self.spec.n_slots)
-        self._beta = None
-        self._state = None
         self._merged = None
 
-    def _ensure(self, device):
-        import torch
-        if self._state is None:
-            nbytes = _native.lib().sir_eval_slots_state_bytes(_sizes_array(self.spec), self.spec.n_slots, self.n_bins)
-            if nbytes != 8 * state_words(self.spec.sizes, self.n_bins):
-                raise _native.SirError("sir_eval_slots_state_bytes disagrees with the layout of sir_amd.slots")
-            self._state = torch.zeros(nbytes // 8, dtype=torch.int64, device=device)
-            self._beta = _beta_tensor(self._inv_temperature, device)
-        elif self._state.device != device:
-            raise _native.SirError(f"this accumulator lives on {self._state.device}, the batch on {device}")
+    def _library_bytes(self):
+        return _native.lib().sir_eval_slots_state_bytes(_sizes_array(self.spec), self.spec.n_slots, self.n_bins)
+
+    def _layout_words(self):
+        return state_words(self.spec.sizes, self.n_bins)
 
     def update(self, logits, labels):
         """Add one batch: logits float32 [B, total], labels int64 [B, G], both on the device.  Nothing comes back."""
@@ -720,10 +694,8 @@ class SlotEvalAccumulator:
         return self
 
     def reset(self):
-        if self._state is not None:
-            self._state.zero_()
         self._merged = None
-        return self
+        return super().reset()
 
     def merge(self, arrays):
         """Add another shard's ``state_arrays()`` (data-parallel evaluation: gather the ranks' states, merge on one)."""
@@ -732,11 +704,7 @@ class SlotEvalAccumulator:
 
     def state_arrays(self):
         """``{"slots": [...], "joint": {...}}`` as numpy -- the one device-to-host copy -- plus whatever was merged in."""
-        if self._state is None:
-            words = np.zeros(state_words(self.spec.sizes, self.n_bins), dtype=np.int64)
-        else:
-            words = self._state.cpu().numpy()
-        own = unpack_state(words, self.spec.sizes, self.n_bins)
+        own = unpack_state(self._words(), self.spec.sizes, self.n_bins)
         return own if self._merged is None else merge(own, self._merged)
 
     def result(self, target_names=None):

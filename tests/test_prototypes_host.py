@@ -186,3 +186,48 @@ def test_keyword_checks_are_raised_before_any_device_call():
         reco.recognize_recordings([], prototypes=bank, slots=spec)
     with pytest.raises(ValueError, match="two different heads"):
         reco.open_streams(1, prototypes=bank, slots=spec)
+
+
+_TWO_HEADS = "prototypes= and slots= are two different heads: pass one of them"
+_FC_HEAD = "temperature= and min_confidence= belong to the fc head: with prototypes= use the bank's scale and min_similarity="
+_NEEDS_ROUTE = "temperature= and min_confidence= need on_device=True (the per-row host route knows neither)"
+# (keywords, the whole message); "bank" / "spec" / "table" stand for the objects the test builds
+_REFUSALS = [
+    (dict(prototypes="bank", slots="spec"), _TWO_HEADS),
+    (dict(min_similarity=0.3), "min_similarity= needs prototypes= (a sir_amd.prototypes.PrototypeBank)"),
+    (dict(prototypes="bank", temperature=2.0), _FC_HEAD),
+    (dict(prototypes="bank", min_confidence=0.5), _FC_HEAD),
+    (dict(temperature=2.0), _NEEDS_ROUTE),
+    (dict(min_confidence=0.5), _NEEDS_ROUTE),
+    (dict(decode="joint"), 'tuples= and decode="joint" need a slot layout (slots=)'),
+    (dict(slots="spec", tuples="table"), 'a tuple table constrains joint decoding: pass decode="joint" with it'),
+    (dict(slots="spec", decode="best"), 'decode must be "independent" or "joint", got \'best\''),
+    (dict(slots="spec", temperature=[1.0, 2.0, 4.0]), "3 temperatures for 2 slots"),
+    (dict(slots="spec", temperature=[1.0, 0.0]), "temperature must be a positive finite number, got 0.0"),
+    (dict(prototypes="bank", slots="spec", temperature=2.0), _TWO_HEADS),
+]
+
+
+@pytest.mark.parametrize("keywords, message", _REFUSALS, ids=[" ".join(k) for k, _ in _REFUSALS[:-1]] + ["two rules broken"])
+def test_every_caller_refuses_a_wrong_result_route_with_the_same_message(keywords, message, monkeypatch):
+    from sir_amd import slots
+    from sir_amd.scripts import predict_frontend
+    from sir_amd.scripts.testing import IntentRecognizer
+
+    def no_device(*a, **k):
+        raise AssertionError("a device call before the keyword checks")
+
+    for name in ("lib", "require_hip", "current_stream_ptr"):
+        monkeypatch.setattr(_native, name, no_device)
+    spec = slots.SlotSpec(["action", "object"], [["on", "off"], ["lights", "heat"]])
+    objects = {"bank": PrototypeBank(["a"]), "spec": spec, "table": slots.TupleTable(spec, [(0, 0), (1, 1)])}
+    kw = {k: objects.get(v, v) if isinstance(v, str) else v for k, v in keywords.items()}
+    reco = IntentRecognizer.__new__(IntentRecognizer)
+    callers = {"ResultOptions": lambda: classify_results.ResultOptions(**kw),
+               "predict_many": lambda: predict_frontend.predict_many(None, ["x.wav"], {}, "cuda", **kw),
+               "recognize_recordings": lambda: reco.recognize_recordings([], **kw),
+               "open_streams": lambda: reco.open_streams(1, **kw)}
+    for name, call in callers.items():
+        with pytest.raises(ValueError) as e:
+            call()
+        assert str(e.value) == message, name

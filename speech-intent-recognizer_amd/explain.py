@@ -13,6 +13,10 @@ The ``*_wave`` forms start from audio: features by ``sir_features_fwd`` (no augm
 ``sir_features_bwd`` carries ``dx`` down to the samples.  Their ``lengths`` are SAMPLE counts of zero-padded clips (what the
 featurizer takes), not the ragged model path; every clip must fit ``t_pad`` frames (``1 + L // 512 <= t_pad``).
 
+Every call takes a training workspace of its own for as long as it needs one (``sir_amd.leases``), so it may run between a training
+forward of the same model and that forward's backward; the stale-input checks of the node (``x`` or a parameter changed between
+its forward and its backward: ``RuntimeError``) apply to the calls made here as well.
+
 Arguments are validated before any device call; there is no CPU path.  Un-padded clips of mixed length have functions of their
 own -- ``input_gradient_ragged``, ``saliency_ragged``, ``fgsm_ragged`` (``sir_model_train_fwd_ragged`` / ``frames`` of the backward:
 row ``b`` is what clip ``b`` gives at its own length, the function ``model.eval()(x, lengths=...)`` scores); the ``lengths=``

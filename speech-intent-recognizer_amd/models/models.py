@@ -101,7 +101,16 @@ class CNNAudioGRU(nn.Module):
         see ``sir_amd.explain``.  Inside the differentiable path the sub-modules are consulted the way torch consults
         them: ``bnK.training == False`` uses (and keeps) that block's running statistics, ``gru.training == False`` turns the
         inter-layer dropout off, and parameters with ``requires_grad == False`` receive no gradient and cost no backward
-        work where it can be skipped.  With every sub-module in training mode and every parameter trainable nothing changes."""
+        work where it can be skipped.  With every sub-module in training mode and every parameter trainable nothing changes.
+
+        The differentiable path is an ordinary ``torch.autograd.Function`` node, and any number of them may be live per model:
+        ``(ce(model(x1), y1) + ce(model(x2), y2)).backward()``, backwards in any order, ``explain`` / ``forward_craft`` /
+        ``predict`` between a forward and its backward -- every node keeps a training workspace of its own until the end of its
+        backward (``sir_amd.leases``).  With ``retain_graph=True`` a second backward works while no other forward has run on this
+        model since the first; after one it raises ``RuntimeError`` (its workspace went back to the model and was reused).
+        ``RuntimeError`` too: ``x`` changed in place before the backward, or a parameter changed between a node's forward and
+        its backward (an optimizer step -- ``FusedAdam.step()`` counts process-wide --, an in-place update,
+        ``weights_changed()``)."""
         if self.training and torch.is_grad_enabled():
             from sir_amd import train_ops
             return train_ops.forward_train(self, x, lengths=lengths)

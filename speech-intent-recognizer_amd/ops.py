@@ -103,6 +103,7 @@ def cached_weights(mod):
 
 
 _weights_epoch = [1]
+_params_epoch = [1]       # the bumps of _weights_epoch that wrote parameters (bump_weights_epoch)
 _tensor_version = operator.attrgetter("_version")
 _tensor_address = torch.Tensor.data_ptr              # (unbound, mapped at C level: this runs on every model call)
 _model_tokens = itertools.count(1)
@@ -116,11 +117,15 @@ def new_model_token():
     return next(_model_tokens)
 
 
-def bump_weights_epoch():
+def bump_weights_epoch(parameters=True):
     """Called by everything that rewrites parameters/buffers behind torch's back (the HIP Adam step, the
     training forward's running-statistics update, ``broadcast_module_``'s writes through ``.data``), so that
-    cached derived weight layouts are rebuilt."""
+    cached derived weight layouts are rebuilt.  ``parameters=False`` (the training forward alone): only BatchNorm running
+    statistics were written, which no backward reads -- the parameters epoch, which a live node of the differentiable step
+    compares between its forward and its backward (``train_ops._input_stamp``), stays."""
     _weights_epoch[0] += 1
+    if parameters:
+        _params_epoch[0] += 1
 
 
 def weights_version(mod, keep, workspace=None):

@@ -9,6 +9,9 @@ If ``x.requires_grad`` the backward also returns ``d loss / d x`` (a non-NULL ``
 data chain runs down through conv1); it is rank-local and is not exchanged.
 ``forward_train_embed`` also returns the 512-float utterance embedding with a graph attached: a loss on it
 (``prototypes.ProxyHead``) enters the backward beside ``dlogits`` (a non-NULL ``demb``).
+Any number of nodes per module may be live: each holds a training workspace of its own from its forward to the end of its
+backward (``sir_amd.leases``), nodes that overlapped return clones instead of the shared views, and a backward whose workspace
+has been reused, or whose ``x`` or parameters were changed since its forward, raises ``RuntimeError``.
 ``fused_cross_entropy`` is the HIP form of the reference's ``nn.CrossEntropyLoss()`` (train.py:242).
 Only pointers move through Python; no arithmetic of the step is done by torch ops.
 """
@@ -19,7 +22,7 @@ from typing import NamedTuple
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import _native, ops
+from . import _native, leases, ops
 from .dist_utils import (ShardSampler, all_reduce_mean_, all_reduce_sum_, broadcast_module_,  # noqa: F401
                          init_distributed, limit_host_threads, shutdown_distributed, world_size)
 from .featurizer import get_featurizer
@@ -180,15 +183,27 @@ def _check_same_freeze(need, cfg, device="cuda"):
 
 
 def _train_state(mod):
-    """The module's gradient buffer and training workspace.  The buffer's views are cut for one set of parameters: it is
-    rebuilt whenever the model took a new token since (``ops.cached_weights`` -- call it first -- hands one out when a
-    parameter or sub-module was replaced, e.g. a new head with another class count), never written through stale views."""
+    """The module's gradient buffer, its training workspace and the pool that leases it (and spares) to the nodes.  The
+    buffer's views are cut for one set of parameters: it is rebuilt whenever the model took a new token since
+    (``ops.cached_weights`` -- call it first -- hands one out when a parameter or sub-module was replaced, e.g. a new head
+    with another class count), never written through stale views."""
     st = getattr(mod, "_sir_train", None)
     token = getattr(mod, "_sir_token", None)
     if st is None or st["token"] != token or st["grads"].flat.device != next(mod.parameters()).device:
-        st = {"grads": GradBuffer(mod), "ws": st["ws"] if st is not None else ops.Workspace(), "token": token}
+        ws = st["ws"] if st is not None else ops.Workspace()
+        pool = st.get("pool") if st is not None else None
+        st = {"grads": GradBuffer(mod), "ws": ws, "pool": pool or leases.LeasePool(ws, ops.Workspace), "token": token}
         mod._sir_train = st
     return st
+
+
+def _input_stamp(mod):
+    """What a node's backward must find as its forward left it: torch's in-place version counter of every parameter and the
+    count of parameter writes behind those counters (``ops._params_epoch``: ``FusedAdam.step``, ``weights_changed``,
+    ``broadcast_module_``).  A training forward's own running-statistics update is not counted: a live block's backward uses
+    the batch statistics its forward left in the workspace, a frozen block's the folded scale / shift there, so a second
+    node's forward is no stale input of the first."""
+    return ops._params_epoch[0], tuple(map(ops._tensor_version, param_list(mod)))
 
 
 def _bn_ptr_arrays(mod):
@@ -253,7 +268,10 @@ class _TrainStep(torch.autograd.Function):
         need = lib.sir_model_workspace_bytes(h, bsz, t, 1)
         if need == 0:
             raise _native.SirError(f"unsupported shape batch={bsz} frames={t} ({ops.SHAPE_LIMITS})")
-        ws = st["ws"].get(need, x.device)
+        # a workspace no live node holds: the module's own unless an earlier node has still to run its backward.  ctx is the
+        # lease's only owner, so a node that is dropped without a backward gives the workspace back when it is collected.
+        ctx.lease = lease = st["pool"].take()
+        ws = lease.slot.get(need, x.device)
         rm, rv = _bn_ptr_arrays(mod)
         if craft:
             _scratch_running_stats(mod, st, cfg, rm, rv)
@@ -266,9 +284,13 @@ class _TrainStep(torch.autograd.Function):
         _run_forward(lib, h, w, rm, rv, x, momentum, seed, opts, logits, ws)
         live = [] if craft else [getattr(mod, f"bn{i + 1}").num_batches_tracked for i in range(3) if not cfg.bn_frozen[i]]
         if live:                                     # frozen statistics: nothing was written, cached layouts stay valid
-            ops.bump_weights_epoch()                 # BN running statistics were updated in place
+            ops.bump_weights_epoch(parameters=False) # BN running statistics were updated in place
             torch._foreach_add_(live, 1)
-        ctx.mod, ctx.x, ctx.seed, ctx.dropout_p, ctx.ws, ctx.cfg = mod, x, seed, float(dropout_p), ws, cfg
+        # x through torch's own version check (an in-place change before the backward raises there); the parameters and the
+        # writes torch does not count through the stamp
+        ctx.save_for_backward(x)
+        ctx.stamp = _input_stamp(mod)
+        ctx.mod, ctx.seed, ctx.dropout_p, ctx.ws, ctx.cfg = mod, seed, float(dropout_p), ws, cfg
         ctx.x_shape, ctx.frames = x_shape, frames
         if opts.want_emb:
             # the attention-pooled context the forward left in its workspace slot, copied on the stream -- the next step reuses
@@ -281,8 +303,23 @@ class _TrainStep(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dlogits, demb=None):
+        try:
+            (x,) = ctx.saved_tensors                 # (raises if x was changed in place since the forward)
+            ctx.lease.check()
+            if _input_stamp(ctx.mod) != ctx.stamp:
+                raise RuntimeError("a parameter of the model was changed in place between this node's forward and its backward "
+                                   "(an optimizer step, weights_changed(), a broadcast): the backward would differentiate the "
+                                   "saved activations against the new weights -- run the forward again")
+            return _TrainStep._backward(ctx, x, dlogits, demb)
+        finally:
+            # the end of the node's backward, not the collection of its graph, frees the workspace: in the ordinary loop the
+            # previous loss is still alive when the next forward runs
+            ctx.lease.release()
+
+    @staticmethod
+    def _backward(ctx, x, dlogits, demb):
         lib = _native.lib()
-        mod, x = ctx.mod, ctx.x
+        mod = ctx.mod
         h = get_featurizer().handle
         w, keep = ops.cached_weights(mod)
         st = _train_state(mod)
@@ -329,6 +366,10 @@ class _TrainStep(torch.autograd.Function):
 
         _exchange_and_scale(grads, run, cnn=cnn, dx=dx is not None)
         dx = dx.view(ctx.x_shape) if dx is not None else None
+        if ctx.lease.shared:
+            # another node of this module is or was live beside this one: its kernels write the same flat buffer, and autograd
+            # holds what is returned here by reference until both have run -- tensors of this node's own
+            return (dx, None, None) + tuple(v.clone() if n else None for v, n in zip(grads.views, need))
         if HAND_OVER_GRADS and all(p.grad is None and not _has_grad_hooks(p) for p in params):
             # zero_grad(set_to_none=True) (train.py:90): the views of the flat buffer BECOME the .grad tensors; returning
             # them through autograd would make AccumulateGrad clone all 29 of them (29 copy launches per step)

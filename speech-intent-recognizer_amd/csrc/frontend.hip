@@ -9,29 +9,21 @@
 // window.  The host builds the kernel in float64 exactly as torchaudio does (including its float32 phase
 // term -p / new), casts to float32 and keeps, per phase, only the in-window taps: table [new][L] + first
 // tap index.  The GPU kernel is a gather-FMA over L taps: HBM-bound (4 B in + 4 B out per sample), no LDS.
-#include <math.h>
 #include <algorithm>
 #include <vector>
-#include "sir_internal.h"
+#include "resample_fir.h"
+#include "wave_sample.h"
 
 namespace {
-
-constexpr int kLowpassWidth = 6;
-constexpr double kRolloff = 0.99;
-
-int gcd_int(int a, int b) { while (b) { int t = a % b; a = b; b = t; } return a; }
 
 struct HostTable { int orig, nw, width, L; std::vector<float> taps; std::vector<int> first; };
 
 HostTable build_table(int orig_freq, int new_freq) {
     HostTable t;
-    const int g = gcd_int(orig_freq, new_freq);
-    t.orig = orig_freq / g;
-    t.nw = new_freq / g;
-    const double base = std::min(t.orig, t.nw) * kRolloff;
-    t.width = (int)ceil(kLowpassWidth * (double)t.orig / base);
-    const int K = 2 * t.width + t.orig;
-    const double scale = base / t.orig;
+    const ResampleGeo g = resample_geometry(orig_freq, new_freq);
+    t.orig = g.orig; t.nw = g.nw; t.width = g.width;
+    const int K = g.K;
+    const double base = g.base, scale = base / t.orig;
     std::vector<double> row(K);
     std::vector<int> lo(t.nw), hi(t.nw);
     std::vector<std::vector<float>> rows(t.nw);
@@ -79,16 +71,10 @@ __global__ __launch_bounds__(256) void resample_kernel(const WT* __restrict__ wa
         const int n = j / nw, p = j - n * nw;
         const int base = n * orig + first[p] - width;
         const WT* x = wave + (size_t)b * wave_stride;
-        const float* tp = taps + (size_t)p * L;
-        for (int l = 0; l < L; ++l) {
+        acc = fir_chain(taps + (size_t)p * L, L, [&](int l) {
             const int i = base + l;
-            float v = 0.0f;
-            if (i >= 0 && i < len) {
-                if constexpr (sizeof(WT) == 2) v = (float)x[i] * (1.0f / 32768.0f);
-                else v = x[i];
-            }
-            acc = fmaf(tp[l], v, acc);
-        }
+            return i >= 0 && i < len ? to_f32<WT>(x[i]) : 0.0f;
+        });
     }
     out[(size_t)b * out_stride + j] = acc;
 }
@@ -104,10 +90,7 @@ __global__ __launch_bounds__(256) void mono_kernel(const WT* __restrict__ pcm, i
     float s = 0.0f;
     if (i < n) {
         const WT* x = pcm + (size_t)b * clip_stride + (size_t)i * channels;
-        for (int c = 0; c < channels; ++c) {
-            if constexpr (sizeof(WT) == 2) s += (float)x[c] * (1.0f / 32768.0f);
-            else s += x[c];
-        }
+        for (int c = 0; c < channels; ++c) s += to_f32<WT>(x[c]);
         if (channels > 1) s = s / (float)channels;
     }
     out[(size_t)b * out_stride + i] = s;
@@ -136,9 +119,8 @@ bool sir_get_resample_table(sir_handle* h, int orig_freq, int new_freq, sir_resa
 
 extern "C" int sir_resample_out_len(int length, int orig_freq, int new_freq) {
     if (length < 0 || orig_freq <= 0 || new_freq <= 0) return -1;
-    const int g = gcd_int(orig_freq, new_freq);
-    const long long orig = orig_freq / g, nw = new_freq / g;
-    const long long target = (nw * length + orig - 1) / orig;
+    const ResampleGeo g = resample_geometry(orig_freq, new_freq);
+    const long long target = ((long long)g.nw * length + g.orig - 1) / g.orig;
     return target > 2147483647ll ? -1 : (int)target;               // a length that does not fit an int is bad input too
 }
 
@@ -150,21 +132,19 @@ extern "C" int sir_resample(sir_handle* h, const void* wave, int wave_dtype, int
         sir_set_error("sir_resample: bad sizes or rates (batch %d, max_len %d, %d -> %d Hz)", batch, max_len, orig_freq, new_freq);
         return SIR_EINVAL;
     }
-    if (!sir_wave_elem_bytes(wave_dtype)) { sir_set_error("sir_resample: unknown wave dtype %d", wave_dtype); return SIR_EINVAL; }
+    if (!sir_wave_elem_bytes(wave_dtype)) { sir_set_error("sir_resample: bad wave_dtype %d", wave_dtype); return SIR_EINVAL; }
     sir_resample_table tab;
     sir_resample_table* t = &tab;
     if (!sir_get_resample_table(h, orig_freq, new_freq, t)) { sir_set_error("sir_resample: could not build the %d -> %d Hz filter table", orig_freq, new_freq); return SIR_EHIP; }
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((max_out_len + 255) / 256, batch);
-    if (wave_dtype == SIR_WAVE_I16)
-        hipLaunchKernelGGL(resample_kernel<short>, grid, dim3(256), 0, st, (const short*)wave, (long long)wave_stride, lengths, max_len,
+    return sir_wave_dispatch(wave_dtype, [&](auto tag) {
+        using WT = decltype(tag);
+        hipLaunchKernelGGL(resample_kernel<WT>, grid, dim3(256), 0, st, (const WT*)wave, (long long)wave_stride, lengths, max_len,
                            (const float*)t->taps, (const int*)t->first, t->orig, t->nw, t->width, t->L, out, (long long)out_stride,
                            max_out_len, out_lengths);
-    else
-        hipLaunchKernelGGL(resample_kernel<float>, grid, dim3(256), 0, st, (const float*)wave, (long long)wave_stride, lengths, max_len,
-                           (const float*)t->taps, (const int*)t->first, t->orig, t->nw, t->width, t->L, out, (long long)out_stride,
-                           max_out_len, out_lengths);
-    return sir_check_hip(hipGetLastError(), "resample_kernel");
+        return sir_check_hip(hipGetLastError(), "resample_kernel");
+    });
 }
 
 extern "C" int sir_mix_to_mono(sir_handle* h, const void* pcm, int dtype, int channels, int64_t clip_stride, const int32_t* frames,
@@ -174,16 +154,15 @@ extern "C" int sir_mix_to_mono(sir_handle* h, const void* pcm, int dtype, int ch
         sir_set_error("sir_mix_to_mono: bad sizes (batch %d, max_frames %d, channels %d)", batch, max_frames, channels);
         return SIR_EINVAL;
     }
-    if (!sir_wave_elem_bytes(dtype)) { sir_set_error("sir_mix_to_mono: unknown dtype %d", dtype); return SIR_EINVAL; }
+    if (!sir_wave_elem_bytes(dtype)) { sir_set_error("sir_mix_to_mono: bad wave_dtype %d", dtype); return SIR_EINVAL; }
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid((max_frames + 255) / 256, batch);
-    if (dtype == SIR_WAVE_I16)
-        hipLaunchKernelGGL(mono_kernel<short>, grid, dim3(256), 0, st, (const short*)pcm, channels, (long long)clip_stride, frames, max_frames, out,
+    return sir_wave_dispatch(dtype, [&](auto tag) {
+        using WT = decltype(tag);
+        hipLaunchKernelGGL(mono_kernel<WT>, grid, dim3(256), 0, st, (const WT*)pcm, channels, (long long)clip_stride, frames, max_frames, out,
                            (long long)out_stride);
-    else
-        hipLaunchKernelGGL(mono_kernel<float>, grid, dim3(256), 0, st, (const float*)pcm, channels, (long long)clip_stride, frames, max_frames, out,
-                           (long long)out_stride);
-    return sir_check_hip(hipGetLastError(), "mono_kernel");
+        return sir_check_hip(hipGetLastError(), "mono_kernel");
+    });
 }
 
 // ---- batch assembly from an HBM-resident feature store ------------------------------------------------------------------

@@ -339,7 +339,7 @@ extern "C" int sir_wave_perturb(sir_handle* h, const void* wave, int wave_dtype,
                       max_len, (long long)wave_stride, max_out_len, (long long)out_stride);
         return SIR_EINVAL;
     }
-    if (!sir_wave_elem_bytes(wave_dtype)) { sir_set_error("sir_wave_perturb: unknown wave dtype %d", wave_dtype); return SIR_EINVAL; }
+    if (!sir_wave_elem_bytes(wave_dtype)) { sir_set_error("sir_wave_perturb: bad wave_dtype %d", wave_dtype); return SIR_EINVAL; }
     if (offsets_out && max_segments <= 0) { sir_set_error("sir_wave_perturb: offsets_out needs max_segments > 0"); return SIR_EINVAL; }
     const int sr = h->cfg.sample_rate;
     const Geom g = sr > 0 ? geom_for(sr) : Geom{0, 0, 0, 0};
@@ -357,9 +357,9 @@ extern "C" int sir_wave_perturb(sir_handle* h, const void* wave, int wave_dtype,
     hipStream_t st = (hipStream_t)stream;
     if (offsets_out)
         SIR_HIP_TRY(hipMemsetAsync(offsets_out, 0xff, (size_t)batch * 2 * max_segments * sizeof(int32_t), st));   // -1 = unused
-    if (wave_dtype == SIR_WAVE_I16)
-        return perturb_impl<short>(h, (const short*)wave, wave_stride, lengths, batch, max_len, shift, pitch_cents, tempo, out, out_stride,
-                                   max_out_len, out_lengths, offsets_out, max_segments, workspace, st);
-    return perturb_impl<float>(h, (const float*)wave, wave_stride, lengths, batch, max_len, shift, pitch_cents, tempo, out, out_stride,
-                               max_out_len, out_lengths, offsets_out, max_segments, workspace, st);
+    return sir_wave_dispatch(wave_dtype, [&](auto tag) {
+        using WT = decltype(tag);
+        return perturb_impl<WT>(h, (const WT*)wave, wave_stride, lengths, batch, max_len, shift, pitch_cents, tempo, out, out_stride, max_out_len,
+                                out_lengths, offsets_out, max_segments, workspace, st);
+    });
 }

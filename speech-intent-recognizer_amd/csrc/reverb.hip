@@ -310,7 +310,7 @@ extern "C" int sir_wave_reverb_mix(sir_handle* h, const void* wave, int wave_dty
                       (long long)wave_stride, (long long)out_stride);
         return SIR_EINVAL;
     }
-    if (!sir_wave_elem_bytes(wave_dtype)) { sir_set_error("sir_wave_reverb_mix: unknown wave dtype %d", wave_dtype); return SIR_EINVAL; }
+    if (!sir_wave_elem_bytes(wave_dtype)) { sir_set_error("sir_wave_reverb_mix: bad wave_dtype %d", wave_dtype); return SIR_EINVAL; }
     if (rir_index) {
         if (max_rir_len < 1 || max_rir_len > kMaxRir) {
             sir_set_error("sir_wave_reverb_mix: max_rir_len %d is outside [1, %d]", max_rir_len, kMaxRir);
@@ -344,14 +344,11 @@ extern "C" int sir_wave_reverb_mix(sir_handle* h, const void* wave, int wave_dty
     a.parts = rir_index ? (max_rir_len + kPart - 1) / kPart : 0;
     const size_t lds = lds_bytes(a.parts);
     hipStream_t st = (hipStream_t)stream;
-    if (wave_dtype == SIR_WAVE_I16) {
-        SIR_TRY(sir_lds_opt_in(h, (const void*)reverb_mix_kernel<short>, (int)lds_bytes(kMaxParts)));
-        hipLaunchKernelGGL(reverb_mix_kernel<short>, dim3(batch), dim3(kThreads), lds, st, (const short*)wave, (long long)wave_stride, lengths,
-                           max_len, a, out, (long long)out_stride, (float*)workspace, h->status);
-    } else {
-        SIR_TRY(sir_lds_opt_in(h, (const void*)reverb_mix_kernel<float>, (int)lds_bytes(kMaxParts)));
-        hipLaunchKernelGGL(reverb_mix_kernel<float>, dim3(batch), dim3(kThreads), lds, st, (const float*)wave, (long long)wave_stride, lengths,
-                           max_len, a, out, (long long)out_stride, (float*)workspace, h->status);
-    }
-    return sir_check_hip(hipGetLastError(), "reverb_mix_kernel");
+    return sir_wave_dispatch(wave_dtype, [&](auto tag) {
+        using WT = decltype(tag);
+        SIR_TRY(sir_lds_opt_in(h, (const void*)reverb_mix_kernel<WT>, (int)lds_bytes(kMaxParts)));
+        hipLaunchKernelGGL(reverb_mix_kernel<WT>, dim3(batch), dim3(kThreads), lds, st, (const WT*)wave, (long long)wave_stride, lengths, max_len, a,
+                           out, (long long)out_stride, (float*)workspace, h->status);
+        return sir_check_hip(hipGetLastError(), "reverb_mix_kernel");
+    });
 }

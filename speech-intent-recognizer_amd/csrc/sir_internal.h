@@ -50,10 +50,10 @@ enum SirStatusBit : unsigned int {
     SIR_STATUS_PERTURB       = 16u,     // sir_wave_perturb: pitch / tempo outside its range (perturb.hip)
     SIR_STATUS_MIX_PERM      = 32u,     // sir_mix_features: permutation entry outside the batch (frontend.hip)
     SIR_STATUS_RAGGED_LENGTH = 64u,     // ragged forward: a length outside [8, t_frames] (infer_tables.h, train_workspace.h)
-    SIR_STATUS_VAD_ROW       = 128u,    // sir_vad_gather: a table row outside the batch (vad.hip)
+    SIR_STATUS_VAD_ROW       = 128u,    // sir_vad_gather: a table row outside the batch (clip_gather.h)
     SIR_STATUS_REVERB        = 256u,    // sir_wave_reverb_mix: bad index, bank length or snr_db (reverb.hip)
     SIR_STATUS_EVAL_LABEL    = 512u,    // sir_eval_accumulate* / sir_temperature_fit: label outside [0, C) that is not -100 (evaluate.hip)
-    SIR_STATUS_STREAM_ROW    = 1024u,   // sir_stream_gather: an impossible table row (stream.hip)
+    SIR_STATUS_STREAM_ROW    = 1024u,   // sir_stream_gather: an impossible table row (clip_gather.h)
     SIR_STATUS_GRU_WEIGHT    = 2048u,   // GRU weight not finite or outside +-65504 (f16_split.h)
     SIR_STATUS_ACT_RANGE     = 4096u,   // training activation beyond the backward's exact range (train_fwd_kernels.h)
     SIR_STATUS_BN_PARAM      = 8192u,   // conv1 weight / BatchNorm parameter not finite (model_kernels.h)
@@ -72,6 +72,10 @@ struct SirProfRec { int id; hipEvent_t e0, e1; };
 static inline size_t sir_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 // bytes per sample of a waveform argument, 0 for a wave_dtype that is neither SIR_WAVE_F32 nor SIR_WAVE_I16
 static inline size_t sir_wave_elem_bytes(int wave_dtype) { return wave_dtype == SIR_WAVE_F32 ? 4 : wave_dtype == SIR_WAVE_I16 ? 2 : 0; }
+// a wave_dtype that sir_wave_elem_bytes accepted, as a type: calls f once with a value of the element type (its type is the tag:
+// `[&](auto tag) { using T = decltype(tag); return impl<T>((const T*)wave, ...); }`) and returns what f returns
+template <typename F>
+static inline int sir_wave_dispatch(int wave_dtype, F&& f) { return wave_dtype == SIR_WAVE_I16 ? f((short)0) : f(0.0f); }
 
 // polyphase resampling filter of one (orig_freq, new_freq) pair (frontend.hip), device tables
 struct sir_resample_table {

@@ -7,7 +7,8 @@
 //   2. stream_energy_kernel   one sub-wave per chunk that this push completes: mean |x| -> one flag byte (and, optionally, the energy)
 //   3. stream_segment_kernel  one thread per stream walks its new chunks through the listener's state machine; rows are numbered
 //                             across streams by block scans with a base carried over tiles of 256 streams; the state is committed
-//   4. stream_gather_kernel   cuts the rows of the table out of the rings as zero-tailed float rows, wrap-aware
+//   4. clip_gather_kernel     cuts the rows of the table out of the rings as zero-tailed float rows, wrap-aware (clip_gather.h,
+//                             the kernel of sir_vad_gather with the ring as its source)
 //
 // Kernels 1 and 2 only read the per-stream counters; kernel 3 is the one that moves them.  No atomics on the numbering path.
 //
@@ -15,25 +16,20 @@
 //   StreamState [S]          32 bytes per stream: n, j, first (int64), recording, silence (int32)
 //   ring        [S][R * c]   samples in the push dtype
 //   flags       [S][K]       one byte per chunk the latest push judged, K = ceil(max_in / c) + 1
+#include "clip_gather.h"
+#include "stream_common.h"
 #include "vad_common.h"
 
 #include <math.h>
 
 namespace {
 
-constexpr int kMaxStreams = 65535;
-constexpr int kMaxIn = 1 << 24;
 constexpr int kMaxChunks = 1 << 20;                   // bound of max_utt_chunks and ring_chunks: every byte count stays far below 2^63
 
 struct StreamState { long long n, j, first; int recording, silence; };
 static_assert(sizeof(StreamState) == 32, "state layout (include/sir_hip.h, DESIGN.md section 4)");
 
 struct Layout { int per, K; long long RC; size_t ring_off, flags_off, total; };
-
-__host__ __device__ __forceinline__ int new_samples(int len, int in_width, int max_in) {
-    const int cap = in_width < max_in ? in_width : max_in;
-    return len < 0 ? 0 : (len > cap ? cap : len);
-}
 
 // ---- 1. append -------------------------------------------------------------------------------------------------------------
 // grid (stream, column block).  A thread owns one 16-byte group of the DESTINATION: the ring is 16-byte aligned and R * c is a
@@ -190,88 +186,17 @@ __global__ __launch_bounds__(kThreads) void stream_segment_kernel(StreamState* _
     if (threadIdx.x == 0) total[0] = (int)base;
 }
 
-__global__ __launch_bounds__(kThreads) void stream_reset_kernel(StreamState* __restrict__ state, const unsigned char* __restrict__ mask, int S) {
-    const int s = blockIdx.x * kThreads + threadIdx.x;
-    if (s < S && (mask == nullptr || mask[s] != 0)) state[s] = StreamState{0, 0, 0, 0, 0};
-}
-
-// ---- 4. gather -------------------------------------------------------------------------------------------------------------
-// grid (row, column block) as vad_gather_kernel; position p of a stream is read at ring offset p mod (R * c).  A 16-byte source
-// group starts at a multiple of the vector width and R * c is one, so it never straddles the wrap.
-template <typename T, bool VEC>
-__global__ __launch_bounds__(kThreads) void stream_gather_kernel(const T* __restrict__ ring, long long RC, int S,
-                                                                 const long long* __restrict__ table, const int* __restrict__ total,
-                                                                 int seg_cap, float* __restrict__ out, long long out_stride, int max_clip,
-                                                                 int* __restrict__ out_lengths, unsigned int* __restrict__ status) {
-    constexpr int V = 16 / (int)sizeof(T);
-    const int s = blockIdx.x;
-    int n_valid = total[0];
-    n_valid = n_valid < 0 ? 0 : (n_valid > seg_cap ? seg_cap : n_valid);
-    const bool head = blockIdx.y == 0 && threadIdx.x == 0;
-    if (s >= n_valid) {                                     // not a row of this push: length 0, the row stays as it is
-        if (head) out_lengths[s] = 0;
-        return;
-    }
-    const long long str = table[s * 4LL + 0], st = table[s * 4LL + 1], en = table[s * 4LL + 2];
-    const bool bad = str < 0 || str >= S || st < 0 || en < st || en - st > RC;
-    const int len = bad ? 0 : (int)(en - st < max_clip ? en - st : max_clip);
-    if (head) {
-        out_lengths[s] = len;
-        if (bad) __hip_atomic_fetch_or(status, SIR_STATUS_STREAM_ROW, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    const int col = (blockIdx.y * kThreads + threadIdx.x) * V;
-    if (col >= max_clip) return;
-    float v[V];
-#pragma unroll
-    for (int e = 0; e < V; ++e) v[e] = 0.0f;
-    if (col < len) {
-        const T* row = ring + str * RC;
-        const long long p = (st + col) % RC;
-        if ((st % V) == 0 && col + V <= len) {
-            alignas(16) T t[V];
-            *reinterpret_cast<int4*>(t) = *reinterpret_cast<const int4*>(row + p);
-#pragma unroll
-            for (int e = 0; e < V; ++e) v[e] = deq<T>(t[e]);
-        } else {
-#pragma unroll
-            for (int e = 0; e < V; ++e)
-                if (col + e < len) v[e] = deq<T>(row[(p + e) % RC]);
-        }
-    }
-    float* dst = out + (long long)s * out_stride + col;
-    if (VEC && col + V <= max_clip) {
-#pragma unroll
-        for (int e = 0; e < V; e += 4) *reinterpret_cast<float4*>(dst + e) = make_float4(v[e], v[e + 1], v[e + 2], v[e + 3]);
-    } else {
-#pragma unroll
-        for (int e = 0; e < V; ++e)
-            if (col + e < max_clip) dst[e] = v[e];
-    }
-}
-
 // ---- host ------------------------------------------------------------------------------------------------------------------
 // everything but ring_chunks: what the size helpers need
 bool base_ok(const sir_stream_config* cfg, const char* who) {
     if (!cfg) { if (who) sir_set_error("%s: NULL config", who); return false; }
     const sir_vad_config& v = cfg->vad;
-    if (!chunk_ok(v.chunk_size)) {
-        if (who) sir_set_error("%s: chunk_size %d is not a multiple of 64 in [64, 4096]", who, v.chunk_size);
-        return false;
-    }
-    if (!(v.threshold >= 0.0f) || v.silence_chunks < 0 || v.prior_chunks < 0) {
-        if (who) sir_set_error("%s: bad config (threshold %g must be >= 0 and not NaN, silence_chunks %d and prior_chunks %d >= 0)", who,
-                               (double)v.threshold, v.silence_chunks, v.prior_chunks);
-        return false;
-    }
+    if (!vad_config_ok(who, v)) return false;
     if (!sir_wave_elem_bytes(cfg->wave_dtype)) {
         if (who) sir_set_error("%s: bad wave_dtype %d", who, cfg->wave_dtype);
         return false;
     }
-    if (cfg->n_streams < 1 || cfg->n_streams > kMaxStreams || cfg->max_in < 1 || cfg->max_in > kMaxIn) {
-        if (who) sir_set_error("%s: bad sizes (n_streams %d must be in [1, %d], max_in %d in [1, %d])", who, cfg->n_streams, kMaxStreams,
-                               cfg->max_in, kMaxIn);
-        return false;
-    }
+    if (!stream_limits_ok(who, cfg->n_streams, cfg->max_in)) return false;
     if (cfg->max_utt_chunks <= v.prior_chunks || cfg->max_utt_chunks > kMaxChunks) {
         if (who) sir_set_error("%s: max_utt_chunks %d must be above prior_chunks %d and at most %d", who, cfg->max_utt_chunks, v.prior_chunks,
                                kMaxChunks);
@@ -305,13 +230,6 @@ Layout layout(const sir_stream_config* cfg) {
     return l;
 }
 
-int state_ok(const void* state, size_t state_bytes, const sir_stream_config* cfg, const char* who) {
-    if ((uintptr_t)state % 256 != 0) { sir_set_error("%s: state must be 256-byte aligned", who); return SIR_EINVAL; }
-    const size_t need = layout(cfg).total;
-    if (state_bytes < need) { sir_set_error("%s: state of %zu bytes, %zu needed", who, state_bytes, need); return SIR_ENOMEM; }
-    return SIR_OK;
-}
-
 template <typename T>
 int push_impl(void* state, const sir_stream_config* cfg, const T* in, int64_t in_stride, int in_width, const int32_t* in_lengths,
               const uint8_t* close, float* energy_out, int64_t* seg_table, int seg_cap, int32_t* total, hipStream_t st) {
@@ -338,23 +256,6 @@ int push_impl(void* state, const sir_stream_config* cfg, const T* in, int64_t in
     return sir_check_hip(hipGetLastError(), "stream_segment_kernel");
 }
 
-template <typename T>
-int gather_impl(sir_handle* h, const void* state, const sir_stream_config* cfg, const int64_t* seg_table, const int32_t* total, int seg_cap,
-                float* out, int64_t out_stride, int max_clip_len, int32_t* out_lengths, hipStream_t st) {
-    constexpr int V = 16 / (int)sizeof(T);
-    const Layout l = layout(cfg);
-    const T* ring = (const T*)((const char*)state + l.ring_off);
-    const bool vec = (uintptr_t)out % 16 == 0 && out_stride % 4 == 0;
-    const dim3 grid(seg_cap, (max_clip_len + kThreads * V - 1) / (kThreads * V));
-    if (vec)
-        hipLaunchKernelGGL((stream_gather_kernel<T, true>), grid, dim3(kThreads), 0, st, ring, l.RC, cfg->n_streams, (const long long*)seg_table,
-                           total, seg_cap, out, (long long)out_stride, max_clip_len, out_lengths, h->status);
-    else
-        hipLaunchKernelGGL((stream_gather_kernel<T, false>), grid, dim3(kThreads), 0, st, ring, l.RC, cfg->n_streams, (const long long*)seg_table,
-                           total, seg_cap, out, (long long)out_stride, max_clip_len, out_lengths, h->status);
-    return sir_check_hip(hipGetLastError(), "stream_gather_kernel");
-}
-
 }  // namespace
 
 extern "C" int sir_stream_min_ring_chunks(const sir_stream_config* cfg) {
@@ -377,10 +278,8 @@ extern "C" int sir_stream_reset(sir_handle* h, void* state, size_t state_bytes, 
                                 void* stream) {
     if (!h || !state || !cfg) { sir_set_error("sir_stream_reset: NULL argument"); return SIR_EINVAL; }
     if (!config_ok(cfg, "sir_stream_reset")) return SIR_EINVAL;
-    SIR_TRY(state_ok(state, state_bytes, cfg, "sir_stream_reset"));
-    hipLaunchKernelGGL(stream_reset_kernel, dim3((cfg->n_streams + kThreads - 1) / kThreads), dim3(kThreads), 0, (hipStream_t)stream,
-                       (StreamState*)state, mask, cfg->n_streams);
-    return sir_check_hip(hipGetLastError(), "stream_reset_kernel");
+    SIR_TRY(state_ok("sir_stream_reset", state, state_bytes, layout(cfg).total));
+    return stream_reset_launch((StreamState*)state, mask, cfg->n_streams, (hipStream_t)stream);
 }
 
 extern "C" int sir_stream_push(sir_handle* h, void* state, size_t state_bytes, const sir_stream_config* cfg, const void* in, int64_t in_stride,
@@ -388,23 +287,19 @@ extern "C" int sir_stream_push(sir_handle* h, void* state, size_t state_bytes, c
                                int seg_cap, int32_t* total, void* stream) {
     if (!h || !state || !cfg || !in || !in_lengths || !seg_table || !total) { sir_set_error("sir_stream_push: NULL argument"); return SIR_EINVAL; }
     if (!config_ok(cfg, "sir_stream_push")) return SIR_EINVAL;
-    if (in_width < 1 || in_width > cfg->max_in || in_stride < in_width) {
-        sir_set_error("sir_stream_push: bad sizes (in_width %d must be in [1, max_in %d], in_stride %lld >= in_width)", in_width, cfg->max_in,
-                      (long long)in_stride);
-        return SIR_EINVAL;
-    }
+    if (!push_sizes_ok("sir_stream_push", in_width, cfg->max_in, in_stride)) return SIR_EINVAL;
     const long long rows = (long long)cfg->n_streams * (chunks_per_push(cfg) + 2);
     if (rows > 0x7fffffffll || seg_cap < rows) {
         sir_set_error("sir_stream_push: seg_cap %d is below sir_stream_max_rows = %lld (nothing was launched, the state has not moved)", seg_cap,
                       rows);
         return SIR_EINVAL;
     }
-    SIR_TRY(state_ok(state, state_bytes, cfg, "sir_stream_push"));
-    if (cfg->wave_dtype == SIR_WAVE_I16)
-        return push_impl<short>(state, cfg, (const short*)in, in_stride, in_width, in_lengths, close, energy_out, seg_table, seg_cap, total,
-                                (hipStream_t)stream);
-    return push_impl<float>(state, cfg, (const float*)in, in_stride, in_width, in_lengths, close, energy_out, seg_table, seg_cap, total,
+    SIR_TRY(state_ok("sir_stream_push", state, state_bytes, layout(cfg).total));
+    return sir_wave_dispatch(cfg->wave_dtype, [&](auto tag) {
+        using T = decltype(tag);
+        return push_impl<T>(state, cfg, (const T*)in, in_stride, in_width, in_lengths, close, energy_out, seg_table, seg_cap, total,
                             (hipStream_t)stream);
+    });
 }
 
 extern "C" int sir_stream_gather(sir_handle* h, const void* state, size_t state_bytes, const sir_stream_config* cfg, const int64_t* seg_table,
@@ -412,12 +307,15 @@ extern "C" int sir_stream_gather(sir_handle* h, const void* state, size_t state_
                                  void* stream) {
     if (!h || !state || !cfg || !seg_table || !total || !out || !out_lengths) { sir_set_error("sir_stream_gather: NULL argument"); return SIR_EINVAL; }
     if (!config_ok(cfg, "sir_stream_gather")) return SIR_EINVAL;
-    if (seg_cap <= 0 || max_clip_len <= 0 || out_stride < max_clip_len || ((long long)max_clip_len + kThreads * 4 - 1) / (kThreads * 4) > 65535) {
+    if (!clip_gather_sizes_ok(seg_cap, max_clip_len, out_stride)) {
         sir_set_error("sir_stream_gather: bad sizes (seg_cap %d, max_clip_len %d, out_stride %lld)", seg_cap, max_clip_len, (long long)out_stride);
         return SIR_EINVAL;
     }
-    SIR_TRY(state_ok(state, state_bytes, cfg, "sir_stream_gather"));
-    if (cfg->wave_dtype == SIR_WAVE_I16)
-        return gather_impl<short>(h, state, cfg, seg_table, total, seg_cap, out, out_stride, max_clip_len, out_lengths, (hipStream_t)stream);
-    return gather_impl<float>(h, state, cfg, seg_table, total, seg_cap, out, out_stride, max_clip_len, out_lengths, (hipStream_t)stream);
+    const Layout l = layout(cfg);
+    SIR_TRY(state_ok("sir_stream_gather", state, state_bytes, l.total));
+    return sir_wave_dispatch(cfg->wave_dtype, [&](auto tag) {
+        using T = decltype(tag);
+        const RingClips<T> src{(const T*)((const char*)state + l.ring_off), l.RC, cfg->n_streams, (const long long*)seg_table};
+        return clip_gather_launch<T>(h, src, true, total, seg_cap, out, out_stride, max_clip_len, out_lengths, (hipStream_t)stream);
+    });
 }

@@ -1,7 +1,8 @@
 // Stream input (sir_stream_input_reset, sir_stream_input_push): the stage in front of sir_stream_push for callers whose audio is
 // not PCM at the handle's rate -- 8 kHz G.711 telephony first of all.  S independent streams, each decoded (mu-law / A-law bytes,
-// int16, float32) and rate-converted push by push with sir_resample's own table (frontend.hip) and its fmaf chain, tap for tap:
-// the concatenated outputs of a stream are bit for bit what sir_resample gives for the whole decoded stream, however it was cut.
+// int16, float32: decode of wave_sample.h) and rate-converted push by push with sir_resample's own table (frontend.hip) and its
+// geometry and fmaf chain (resample_fir.h, one copy for both): the concatenated outputs of a stream are bit for bit what
+// sir_resample gives for the whole decoded stream, however it was cut.
 //
 //   1. sin_emit_kernel     grid (output block of 256, stream): a thread computes one output of this push.  Chain positions
 //                          below the stream's n come from its history ring, the rest from the push row, decoded on load.
@@ -17,66 +18,23 @@
 //   ring    [S][H]   float32, decoded sample i of a stream at offset i mod H, H = 2 (2 width + orig); absent when the rates are equal
 // Why H is enough: an output j not yet emitted at n has q(j) >= q(j0), j0 = E(n), and need(j0) > n, so its first chain position
 // q(j) orig + first[p] - width > n - first[p0] - L + first[p] >= n - (K - 1) - K with K = 2 width + orig >= L, first[] in [0, K).
-#include "sir_internal.h"
-
-#include <math.h>
+#include "resample_fir.h"
+#include "stream_common.h"
+#include "wave_sample.h"
 
 namespace {
-
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / SIR_WAVE;
-constexpr int kMaxStreams = 65535;
-constexpr int kMaxIn = 1 << 24;
 
 struct InState { long long n, emitted; };
 static_assert(sizeof(InState) == 16, "state layout (include/sir_hip.h, DESIGN.md section 4)");
 
-struct Geo { int orig, nw, width, K, H; bool copy; };
+// the rate pair's geometry (the one sir_resample's table is built from) and the history ring's length H
+struct Geo : ResampleGeo { int H; bool copy; };
 struct Layout { size_t ring_off, total; };
 
-int gcd_int(int a, int b) { while (b) { int t = a % b; a = b; b = t; } return a; }
-
-// gcd-reduced rates and torchaudio's `width`, the expressions of frontend.hip's build_table (checked against the table at reset / push)
 Geo geometry(const sir_stream_input_config* cfg) {
-    Geo g;
-    const int d = gcd_int(cfg->in_rate, cfg->out_rate);
-    g.orig = cfg->in_rate / d;
-    g.nw = cfg->out_rate / d;
-    g.copy = cfg->in_rate == cfg->out_rate;
-    const double base = (g.orig < g.nw ? g.orig : g.nw) * 0.99;
-    g.width = (int)ceil(6 * (double)g.orig / base);
-    g.K = 2 * g.width + g.orig;
-    g.H = g.copy ? 0 : 2 * g.K;
-    return g;
-}
-
-__host__ __device__ __forceinline__ int new_samples(int len, int in_width, int max_in) {
-    const int cap = in_width < max_in ? in_width : max_in;
-    return len < 0 ? 0 : (len > cap ? cap : len);
-}
-
-// ---- decoding: one element of the push row -> float32 (include/sir_hip.h) ---------------------------------------------------
-template <int DT> struct Elem;
-template <> struct Elem<SIR_WAVE_F32> { typedef float type; };
-template <> struct Elem<SIR_WAVE_I16> { typedef short type; };
-template <> struct Elem<SIR_WAVE_ULAW> { typedef unsigned char type; };
-template <> struct Elem<SIR_WAVE_ALAW> { typedef unsigned char type; };
-
-template <int DT>
-__device__ __forceinline__ float decode(typename Elem<DT>::type x) {
-    if constexpr (DT == SIR_WAVE_F32) {
-        return x;
-    } else if constexpr (DT == SIR_WAVE_I16) {
-        return (float)x * (1.0f / 32768.0f);
-    } else if constexpr (DT == SIR_WAVE_ULAW) {
-        const int u = ~(int)x & 0xFF;
-        const int t = (((u & 0x0F) << 3) + 0x84) << ((u >> 4) & 7);
-        return (float)((u & 0x80) ? 0x84 - t : t - 0x84) * (1.0f / 32768.0f);
-    } else {
-        const int a = (int)x ^ 0x55, e = (a >> 4) & 7, m = a & 0x0F;
-        const int t = e ? ((m << 4) + 0x108) << (e - 1) : (m << 4) + 8;
-        return (float)((a & 0x80) ? t : -t) * (1.0f / 32768.0f);
-    }
+    const ResampleGeo r = resample_geometry(cfg->in_rate, cfg->out_rate);
+    const bool copy = cfg->in_rate == cfg->out_rate;
+    return Geo{r, copy ? 0 : 2 * r.K, copy};
 }
 
 // ---- E(n): outputs a stream of n samples has emitted ----------------------------------------------------------------------------
@@ -108,7 +66,7 @@ __device__ __forceinline__ long long emitted_at(long long n, bool closing, const
 
 // ---- 1. emit ---------------------------------------------------------------------------------------------------------------------
 template <int DT>
-__global__ __launch_bounds__(kThreads) void sin_emit_kernel(const typename Elem<DT>::type* __restrict__ in, long long in_stride, int in_width,
+__global__ __launch_bounds__(kThreads) void sin_emit_kernel(const typename WaveElem<DT>::type* __restrict__ in, long long in_stride, int in_width,
                                                             int max_in, const int* __restrict__ in_lengths,
                                                             const unsigned char* __restrict__ close, const InState* __restrict__ state,
                                                             const float* __restrict__ ring, int H, const float* __restrict__ taps,
@@ -139,11 +97,9 @@ __global__ __launch_bounds__(kThreads) void sin_emit_kernel(const typename Elem<
     const int rel = (int)(base - st.n);                           // in (-H, m + orig + width]: relative to the push row
     const int h0 = (int)(st.n % H);
     const int lo = st.n < H ? -(int)st.n : -H;                    // positions below 0 are zeros; below n - H nothing is asked for
-    const typename Elem<DT>::type* row = in + (long long)s * in_stride;
+    const typename WaveElem<DT>::type* row = in + (long long)s * in_stride;
     const float* hist = ring + (long long)s * H;
-    const float* tp = taps + (size_t)p * L;
-    float acc = 0.0f;
-    for (int l = 0; l < L; ++l) {
+    out[(long long)s * out_stride + k] = fir_chain(taps + (size_t)p * L, L, [&](int l) {
         const int r = rel + l;
         float v = 0.0f;
         if (r >= 0) {
@@ -153,14 +109,13 @@ __global__ __launch_bounds__(kThreads) void sin_emit_kernel(const typename Elem<
             idx += idx < 0 ? H : 0;
             v = hist[idx];
         }
-        acc = fmaf(tp[l], v, acc);
-    }
-    out[(long long)s * out_stride + k] = acc;
+        return v;
+    });
 }
 
 // ---- 2. commit -------------------------------------------------------------------------------------------------------------------
 template <int DT>
-__global__ __launch_bounds__(kThreads) void sin_commit_kernel(const typename Elem<DT>::type* __restrict__ in, long long in_stride, int in_width,
+__global__ __launch_bounds__(kThreads) void sin_commit_kernel(const typename WaveElem<DT>::type* __restrict__ in, long long in_stride, int in_width,
                                                               int max_in, const int* __restrict__ in_lengths,
                                                               const unsigned char* __restrict__ close, InState* __restrict__ state,
                                                               float* __restrict__ ring, int H, const int* __restrict__ first, int orig, int nw,
@@ -179,7 +134,7 @@ __global__ __launch_bounds__(kThreads) void sin_commit_kernel(const typename Ele
     const long long n1 = st.n + m;
     const long long e1 = emitted_at(n1, false, first, orig, nw, width, L, sh);     // (its barriers: every thread has read st)
     const int h0 = (int)(st.n % H);
-    const typename Elem<DT>::type* row = in + (long long)s * in_stride;
+    const typename WaveElem<DT>::type* row = in + (long long)s * in_stride;
     float* hist = ring + (long long)s * H;
     for (int t = (m > H ? m - H : 0) + threadIdx.x; t < m; t += kThreads) hist[(h0 + t) % H] = decode<DT>(row[t]);
     if (threadIdx.x == 0) state[s] = InState{n1, e1};
@@ -187,7 +142,7 @@ __global__ __launch_bounds__(kThreads) void sin_commit_kernel(const typename Ele
 
 // ---- equal rates: decode / copy ----------------------------------------------------------------------------------------------------
 template <int DT>
-__global__ __launch_bounds__(kThreads) void sin_copy_kernel(const typename Elem<DT>::type* __restrict__ in, long long in_stride, int in_width,
+__global__ __launch_bounds__(kThreads) void sin_copy_kernel(const typename WaveElem<DT>::type* __restrict__ in, long long in_stride, int in_width,
                                                             int max_in, const int* __restrict__ in_lengths,
                                                             const unsigned char* __restrict__ close, InState* __restrict__ state,
                                                             float* __restrict__ out, long long out_stride, int* __restrict__ out_lengths) {
@@ -203,11 +158,6 @@ __global__ __launch_bounds__(kThreads) void sin_copy_kernel(const typename Elem<
     if (k < m) out[(long long)s * out_stride + k] = decode<DT>(in[(long long)s * in_stride + k]);
 }
 
-__global__ __launch_bounds__(kThreads) void sin_reset_kernel(InState* __restrict__ state, const unsigned char* __restrict__ mask, int S) {
-    const int s = blockIdx.x * kThreads + threadIdx.x;
-    if (s < S && (mask == nullptr || mask[s] != 0)) state[s] = InState{0, 0};
-}
-
 // ---- host ------------------------------------------------------------------------------------------------------------------------
 bool dtype_ok(int dt) { return dt == SIR_WAVE_F32 || dt == SIR_WAVE_I16 || dt == SIR_WAVE_ULAW || dt == SIR_WAVE_ALAW; }
 
@@ -218,12 +168,7 @@ bool config_ok(const sir_stream_input_config* cfg, const char* who) {
         if (who) sir_set_error("%s: bad rates (%d -> %d Hz)", who, cfg->in_rate, cfg->out_rate);
         return false;
     }
-    if (cfg->n_streams < 1 || cfg->n_streams > kMaxStreams || cfg->max_in < 1 || cfg->max_in > kMaxIn) {
-        if (who) sir_set_error("%s: bad sizes (n_streams %d must be in [1, %d], max_in %d in [1, %d])", who, cfg->n_streams, kMaxStreams,
-                               cfg->max_in, kMaxIn);
-        return false;
-    }
-    return true;
+    return stream_limits_ok(who, cfg->n_streams, cfg->max_in);
 }
 
 // ceil(nw (max_in + 3 width + 2 orig) / orig) + 1 (include/sir_hip.h); -1 when it does not fit an int
@@ -241,22 +186,16 @@ Layout layout(const sir_stream_input_config* cfg, const Geo& g) {
     return l;
 }
 
-int state_ok(const void* state, size_t state_bytes, const sir_stream_input_config* cfg, const Geo& g, const char* who) {
-    if ((uintptr_t)state % 256 != 0) { sir_set_error("%s: state must be 256-byte aligned", who); return SIR_EINVAL; }
-    const size_t need = layout(cfg, g).total;
-    if (state_bytes < need) { sir_set_error("%s: state of %zu bytes, %zu needed", who, state_bytes, need); return SIR_ENOMEM; }
-    return SIR_OK;
-}
-
-// the handle's table of the pair; it must be the geometry the state was sized for
+// the handle's table of the pair.  Its orig / nw / width are g's by construction (resample_geometry); that the kept taps fit the
+// history ring, 1 <= L <= K, is a property of the filter and is checked
 int table_of(sir_handle* h, const sir_stream_input_config* cfg, const Geo& g, sir_resample_table* t, const char* who) {
     if (!sir_get_resample_table(h, cfg->in_rate, cfg->out_rate, t)) {
         sir_set_error("%s: could not build the %d -> %d Hz filter table", who, cfg->in_rate, cfg->out_rate);
         return SIR_EHIP;
     }
-    if (t->orig != g.orig || t->nw != g.nw || t->width != g.width || t->L < 1 || t->L > g.K) {
-        sir_set_error("%s: the %d -> %d Hz table (orig %d, new %d, width %d, L %d) does not have the expected geometry", who, cfg->in_rate,
-                      cfg->out_rate, t->orig, t->nw, t->width, t->L);
+    if (t->L < 1 || t->L > g.K) {
+        sir_set_error("%s: the %d -> %d Hz table (orig %d, new %d, width %d) keeps L = %d taps, outside [1, %d]", who, cfg->in_rate, cfg->out_rate,
+                      t->orig, t->nw, t->width, t->L, g.K);
         return SIR_EUNSUPPORTED;
     }
     return SIR_OK;
@@ -266,7 +205,7 @@ template <int DT>
 int push_impl(void* state, const sir_stream_input_config* cfg, const Geo& g, const sir_resample_table* t, const void* in_v, int64_t in_stride,
               int in_width, const int32_t* in_lengths, const uint8_t* close, float* out, int64_t out_stride, int max_out,
               int32_t* out_lengths, hipStream_t st) {
-    typedef typename Elem<DT>::type T;
+    typedef typename WaveElem<DT>::type T;
     const T* in = (const T*)in_v;
     InState* ss = (InState*)state;
     const int S = cfg->n_streams;
@@ -305,14 +244,12 @@ extern "C" int sir_stream_input_reset(sir_handle* h, void* state, size_t state_b
     if (!config_ok(cfg, "sir_stream_input_reset")) return SIR_EINVAL;
     const Geo g = geometry(cfg);
     if (max_out_of(cfg, g) < 0) { sir_set_error("sir_stream_input_reset: the outputs of one push do not fit an int"); return SIR_EINVAL; }
-    SIR_TRY(state_ok(state, state_bytes, cfg, g, "sir_stream_input_reset"));
+    SIR_TRY(state_ok("sir_stream_input_reset", state, state_bytes, layout(cfg, g).total));
     if (!g.copy) {                                                // the one place a table is built: pushes only look it up
         sir_resample_table t;
         SIR_TRY(table_of(h, cfg, g, &t, "sir_stream_input_reset"));
     }
-    hipLaunchKernelGGL(sin_reset_kernel, dim3((cfg->n_streams + kThreads - 1) / kThreads), dim3(kThreads), 0, (hipStream_t)stream,
-                       (InState*)state, mask, cfg->n_streams);
-    return sir_check_hip(hipGetLastError(), "sin_reset_kernel");
+    return stream_reset_launch((InState*)state, mask, cfg->n_streams, (hipStream_t)stream);
 }
 
 extern "C" int sir_stream_input_push(sir_handle* h, void* state, size_t state_bytes, const sir_stream_input_config* cfg, const void* in,
@@ -320,11 +257,7 @@ extern "C" int sir_stream_input_push(sir_handle* h, void* state, size_t state_by
                                      int64_t out_stride, int32_t* out_lengths, void* stream) {
     if (!h || !state || !cfg || !in || !in_lengths || !out || !out_lengths) { sir_set_error("sir_stream_input_push: NULL argument"); return SIR_EINVAL; }
     if (!config_ok(cfg, "sir_stream_input_push")) return SIR_EINVAL;
-    if (in_width < 1 || in_width > cfg->max_in || in_stride < in_width) {
-        sir_set_error("sir_stream_input_push: bad sizes (in_width %d must be in [1, max_in %d], in_stride %lld >= in_width)", in_width,
-                      cfg->max_in, (long long)in_stride);
-        return SIR_EINVAL;
-    }
+    if (!push_sizes_ok("sir_stream_input_push", in_width, cfg->max_in, in_stride)) return SIR_EINVAL;
     const Geo g = geometry(cfg);
     const long long max_out = max_out_of(cfg, g);
     if (max_out < 0) { sir_set_error("sir_stream_input_push: the outputs of one push do not fit an int"); return SIR_EINVAL; }
@@ -333,7 +266,7 @@ extern "C" int sir_stream_input_push(sir_handle* h, void* state, size_t state_by
                       "not moved)", (long long)out_stride, max_out);
         return SIR_EINVAL;
     }
-    SIR_TRY(state_ok(state, state_bytes, cfg, g, "sir_stream_input_push"));
+    SIR_TRY(state_ok("sir_stream_input_push", state, state_bytes, layout(cfg, g).total));
     sir_resample_table t{};
     if (!g.copy) SIR_TRY(table_of(h, cfg, g, &t, "sir_stream_input_push"));
     hipStream_t st = (hipStream_t)stream;

@@ -4,13 +4,14 @@
 //   1. vad_energy_kernel   one read of every sample: mean |x| per chunk -> packed speech flags (and, optionally, the energies)
 //   2. vad_segment_kernel  the listener's state machine in its data-parallel form, one workgroup per recording, run twice:
 //                          <false> counts the segments, vad_base_kernel turns the counts into base rows, <true> writes the table
-//   3. vad_gather_kernel   cuts the segments out as zero-tailed float rows
+//   3. clip_gather_kernel  cuts the segments out as zero-tailed float rows (clip_gather.h, shared with sir_stream_gather)
 //
 // The state machine (testing.py:84-133) only ever looks at `last`, the index of the latest speech chunk:
 //   trigger at i : speech_i and (no speech chunk before i, or i - last_before(i) > n_stop)
 //   end at j     : last_upto(j) == j - n_stop          (n_stop == 0: every speech chunk ends its own segment)
 // `last` is a prefix maximum, the k-th trigger pairs with the k-th end, so prefix sums of the two flag kinds number the rows.
 // No atomics anywhere on the numbering path: the table order is part of the contract and every output is bit-reproducible.
+#include "clip_gather.h"
 #include "vad_common.h"
 
 #include <math.h>
@@ -189,58 +190,6 @@ __global__ __launch_bounds__(kThreads) void vad_base_kernel(const int* __restric
     if (threadIdx.x == 0) total[0] = tot;
 }
 
-// ---- 3. gather -------------------------------------------------------------------------------------------------------------
-// grid (segment, column block); a thread moves 16 source bytes (8 i16 / 4 f32 samples) and zero-fills behind the clip
-template <typename T, bool VEC>
-__global__ __launch_bounds__(kThreads) void vad_gather_kernel(const T* __restrict__ wave, long long stride, int n_rec,
-                                                              const int* __restrict__ table, const int* __restrict__ total, int seg_cap,
-                                                              float* __restrict__ out, long long out_stride, int max_clip,
-                                                              int* __restrict__ out_lengths, unsigned int* __restrict__ status) {
-    constexpr int V = 16 / (int)sizeof(T);
-    const int s = blockIdx.x;
-    int n_valid = total[0];
-    n_valid = n_valid < 0 ? 0 : (n_valid > seg_cap ? seg_cap : n_valid);
-    const bool head = blockIdx.y == 0 && threadIdx.x == 0;
-    if (s >= n_valid) {                                     // not a segment: length 0, the row stays as it is
-        if (head) out_lengths[s] = 0;
-        return;
-    }
-    const int rec = table[s * 3LL + 0], st = table[s * 3LL + 1], en = table[s * 3LL + 2];
-    const bool bad = rec < 0 || rec >= n_rec || st < 0 || en < st || (long long)en > stride;
-    const int len = bad ? 0 : (en - st < max_clip ? en - st : max_clip);
-    if (head) {
-        out_lengths[s] = len;
-        if (bad) __hip_atomic_fetch_or(status, SIR_STATUS_VAD_ROW, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    const int col = (blockIdx.y * kThreads + threadIdx.x) * V;
-    if (col >= max_clip) return;
-    float v[V];
-#pragma unroll
-    for (int e = 0; e < V; ++e) v[e] = 0.0f;
-    if (col < len) {
-        const T* src = wave + (long long)rec * stride + st + col;
-        if (VEC && (st % V) == 0 && col + V <= len) {
-            alignas(16) T t[V];
-            *reinterpret_cast<int4*>(t) = *reinterpret_cast<const int4*>(src);
-#pragma unroll
-            for (int e = 0; e < V; ++e) v[e] = deq<T>(t[e]);
-        } else {
-#pragma unroll
-            for (int e = 0; e < V; ++e)
-                if (col + e < len) v[e] = deq<T>(src[e]);
-        }
-    }
-    float* dst = out + (long long)s * out_stride + col;
-    if (VEC && col + V <= max_clip) {
-#pragma unroll
-        for (int e = 0; e < V; e += 4) *reinterpret_cast<float4*>(dst + e) = make_float4(v[e], v[e + 1], v[e + 2], v[e + 3]);
-    } else {
-#pragma unroll
-        for (int e = 0; e < V; ++e)
-            if (col + e < max_clip) dst[e] = v[e];
-    }
-}
-
 struct WsLayout { int wpr, max_chunks; size_t flags_off, base_off, total; };
 
 WsLayout ws_layout(int n_rec, int max_len, int c) {
@@ -287,23 +236,6 @@ int segment_impl(sir_handle* h, const T* wave, int64_t wave_stride, const int32_
     return SIR_OK;
 }
 
-template <typename T>
-int gather_impl(sir_handle* h, const T* wave, int64_t wave_stride, int n_rec, const int32_t* seg_table, const int32_t* total, int seg_cap,
-                float* out, int64_t out_stride, int max_clip_len, int32_t* out_lengths, hipStream_t st) {
-    constexpr int V = 16 / (int)sizeof(T);
-    const bool vec = (uintptr_t)wave % 16 == 0 && ((long long)wave_stride * (long long)sizeof(T)) % 16 == 0 && (uintptr_t)out % 16 == 0 &&
-                     out_stride % 4 == 0;
-    const dim3 grid(seg_cap, (max_clip_len + kThreads * V - 1) / (kThreads * V));
-    SirProfScope prof(h, SIR_K_VAD_GATHER, st);
-    if (vec)
-        hipLaunchKernelGGL((vad_gather_kernel<T, true>), grid, dim3(kThreads), 0, st, wave, (long long)wave_stride, n_rec, seg_table, total, seg_cap,
-                           out, (long long)out_stride, max_clip_len, out_lengths, h->status);
-    else
-        hipLaunchKernelGGL((vad_gather_kernel<T, false>), grid, dim3(kThreads), 0, st, wave, (long long)wave_stride, n_rec, seg_table, total,
-                           seg_cap, out, (long long)out_stride, max_clip_len, out_lengths, h->status);
-    return sir_check_hip(hipGetLastError(), "vad_gather_kernel");
-}
-
 }  // namespace
 
 extern "C" int sir_vad_stop_chunks(int sample_rate, int chunk_size, double silence_limit) {
@@ -335,15 +267,7 @@ extern "C" int sir_vad_segment(sir_handle* h, const void* wave, int wave_dtype, 
         sir_set_error("sir_vad_segment: bad sizes (n_rec %d, max_len %d, wave_stride %lld, seg_cap %d)", n_rec, max_len, (long long)wave_stride, seg_cap);
         return SIR_EINVAL;
     }
-    if (!chunk_ok(cfg->chunk_size)) {
-        sir_set_error("sir_vad_segment: chunk_size %d is not a multiple of 64 in [64, 4096]", cfg->chunk_size);
-        return SIR_EINVAL;
-    }
-    if (!(cfg->threshold >= 0.0f) || cfg->silence_chunks < 0 || cfg->prior_chunks < 0) {
-        sir_set_error("sir_vad_segment: bad config (threshold %g must be >= 0 and not NaN, silence_chunks %d and prior_chunks %d >= 0)",
-                      (double)cfg->threshold, cfg->silence_chunks, cfg->prior_chunks);
-        return SIR_EINVAL;
-    }
+    if (!vad_config_ok("sir_vad_segment", *cfg)) return SIR_EINVAL;
     const size_t need = sir_vad_workspace_bytes(h, n_rec, max_len, cfg->chunk_size);
     if ((long long)n_rec * ws_layout(n_rec, max_len, cfg->chunk_size).wpr / kWaves >= (1ll << 31) - 1) {      // the energy kernel's grid
         sir_set_error("sir_vad_segment: batch too large (n_rec %d, max_len %d)", n_rec, max_len);
@@ -354,11 +278,11 @@ extern "C" int sir_vad_segment(sir_handle* h, const void* wave, int wave_dtype, 
         sir_set_error("sir_vad_segment: workspace of %zu bytes, %zu needed", workspace_bytes, need);
         return SIR_ENOMEM;
     }
-    if (wave_dtype == SIR_WAVE_I16)
-        return segment_impl<short>(h, (const short*)wave, wave_stride, lengths, n_rec, max_len, cfg, energy_out, seg_count, seg_table, seg_cap,
-                                   total, workspace, (hipStream_t)stream);
-    return segment_impl<float>(h, (const float*)wave, wave_stride, lengths, n_rec, max_len, cfg, energy_out, seg_count, seg_table, seg_cap, total,
+    return sir_wave_dispatch(wave_dtype, [&](auto tag) {
+        using T = decltype(tag);
+        return segment_impl<T>(h, (const T*)wave, wave_stride, lengths, n_rec, max_len, cfg, energy_out, seg_count, seg_table, seg_cap, total,
                                workspace, (hipStream_t)stream);
+    });
 }
 
 extern "C" int sir_vad_gather(sir_handle* h, const void* wave, int wave_dtype, int64_t wave_stride, int n_rec, const int32_t* seg_table,
@@ -366,15 +290,16 @@ extern "C" int sir_vad_gather(sir_handle* h, const void* wave, int wave_dtype, i
                               void* stream) {
     if (!h || !wave || !seg_table || !total || !out || !out_lengths) { sir_set_error("sir_vad_gather: NULL argument"); return SIR_EINVAL; }
     if (!sir_wave_elem_bytes(wave_dtype)) { sir_set_error("sir_vad_gather: bad wave_dtype %d", wave_dtype); return SIR_EINVAL; }
-    if (n_rec <= 0 || wave_stride <= 0 || seg_cap <= 0 || max_clip_len <= 0 || out_stride < max_clip_len ||
-        ((long long)max_clip_len + kThreads * 4 - 1) / (kThreads * 4) > 65535) {
+    if (n_rec <= 0 || wave_stride <= 0 || !clip_gather_sizes_ok(seg_cap, max_clip_len, out_stride)) {
         sir_set_error("sir_vad_gather: bad sizes (n_rec %d, wave_stride %lld, seg_cap %d, max_clip_len %d, out_stride %lld)", n_rec,
                       (long long)wave_stride, seg_cap, max_clip_len, (long long)out_stride);
         return SIR_EINVAL;
     }
-    if (wave_dtype == SIR_WAVE_I16)
-        return gather_impl<short>(h, (const short*)wave, wave_stride, n_rec, seg_table, total, seg_cap, out, out_stride, max_clip_len, out_lengths,
-                                  (hipStream_t)stream);
-    return gather_impl<float>(h, (const float*)wave, wave_stride, n_rec, seg_table, total, seg_cap, out, out_stride, max_clip_len, out_lengths,
-                              (hipStream_t)stream);
+    SirProfScope prof(h, SIR_K_VAD_GATHER, (hipStream_t)stream);
+    return sir_wave_dispatch(wave_dtype, [&](auto tag) {
+        using T = decltype(tag);
+        const LinearClips<T> src{(const T*)wave, (long long)wave_stride, n_rec, seg_table};
+        const bool src_vec = (uintptr_t)wave % 16 == 0 && ((long long)wave_stride * (long long)sizeof(T)) % 16 == 0;
+        return clip_gather_launch<T>(h, src, src_vec, total, seg_cap, out, out_stride, max_clip_len, out_lengths, (hipStream_t)stream);
+    });
 }

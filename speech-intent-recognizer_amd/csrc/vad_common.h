@@ -1,13 +1,10 @@
-// Device pieces shared by the two energy detectors: vad.hip (whole recordings resident in HBM) and stream.hip (live streams fed
+// Pieces shared by the two energy detectors: vad.hip (whole recordings resident in HBM) and stream.hip (live streams fed
 // push by push).  A chunk must get the same energy bits whichever of the two judges it, so the accumulator, the sub-wave read
-// pattern and the reduction order exist once, here.
+// pattern and the reduction order exist once, here; so do the rules of a sir_vad_config.  (The clip gather: clip_gather.h.)
 #pragma once
-#include "sir_internal.h"
+#include "wave_block.h"
 
 namespace {
-
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / SIR_WAVE;
 
 __device__ __forceinline__ int clamp_len(int len, int max_len) { return len < 0 ? 0 : (len > max_len ? max_len : len); }
 
@@ -100,11 +97,21 @@ __device__ __forceinline__ int block_excl_add(int v, int* sh, int* total) {
     return off + incl - v;
 }
 
-// ---- gather ----------------------------------------------------------------------------------------------------------------
-template <typename T> __device__ __forceinline__ float deq(T v);
-template <> __device__ __forceinline__ float deq<short>(short v) { return (float)v * (1.0f / 32768.0f); }
-template <> __device__ __forceinline__ float deq<float>(float v) { return v; }
-
+// ---- config rules (host) ---------------------------------------------------------------------------------------------------
 bool chunk_ok(int c) { return c >= 64 && c <= 4096 && c % 64 == 0; }
+
+// the rules of a sir_vad_config, for sir_vad_segment and sir_stream_*; a failure is reported in who's name (NULL: silently)
+bool vad_config_ok(const char* who, const sir_vad_config& v) {
+    if (!chunk_ok(v.chunk_size)) {
+        if (who) sir_set_error("%s: chunk_size %d is not a multiple of 64 in [64, 4096]", who, v.chunk_size);
+        return false;
+    }
+    if (!(v.threshold >= 0.0f) || v.silence_chunks < 0 || v.prior_chunks < 0) {
+        if (who) sir_set_error("%s: bad config (threshold %g must be >= 0 and not NaN, silence_chunks %d and prior_chunks %d >= 0)", who,
+                               (double)v.threshold, v.silence_chunks, v.prior_chunks);
+        return false;
+    }
+    return true;
+}
 
 }  // namespace

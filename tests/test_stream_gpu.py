@@ -273,6 +273,27 @@ def test_segments_across_the_ring_wrap(dtype):
     rows, clips, _ = _feed(ss, _plan(recs, [_random_pieces(rng, 5037, 200)]), M * CH, dtype)
     _assert_equals_batch(rows, clips, seg, recs, dtype, M * CH, P, n_stop)
     ops.check_status()
+    # hand-written rows over the R * CH samples the ring still holds (a close moves the counters, not the ring; the detector
+    # only ever starts a clip on a chunk boundary), around position `wrap`, which sits at ring offset 0: an aligned start whose
+    # 16-byte groups meet the wrap, a start off the 16-byte grid with the wrap inside the clip, both cut at max_clip_len, an
+    # aligned start whose clip ends inside a group, a one-sample clip; then a stream outside the slots (a zero row, reported)
+    # and a row at the total (length 0 only).  204 columns: aligned output rows; 203: rows no vector store may touch.
+    x, wrap = recs[0], len(recs[0]) // (R * CH) * (R * CH)
+    assert len(x) - R * CH < wrap - 300 and wrap + 300 < len(x)
+    hand = [(wrap - 128, wrap + 128, 0), (wrap - 107, wrap + 193, 0), (wrap + 64, wrap + 101, 0), (wrap - 298, wrap - 297, 0)]
+    n = len(hand)
+    table = torch.tensor([[0, a, b, f] for a, b, f in hand] + [[1, wrap, wrap + 64, 0], [0, wrap, wrap + 64, 0]], dtype=torch.int64, device=DEV)
+    total = torch.tensor([n + 1], dtype=torch.int32, device=DEV)
+    for max_clip in (204, 203):
+        out, out_len = ss.gather(table, total, max_clip)
+        got, got_len = out.cpu().numpy(), out_len.cpu().numpy()
+        want, want_len = stream_ref.gather(x, hand, max_clip)
+        assert want_len.tolist() == [max_clip, max_clip, 37, 1]
+        assert np.array_equal(got[:n].view(np.uint32), want.view(np.uint32)) and np.array_equal(got_len[:n], want_len)
+        assert not got[n].any() and got_len[n:].tolist() == [0, 0]
+        with pytest.raises(_native.SirError, match="sir_stream_gather"):
+            ops.check_status()
+    ops.check_status()
 
 
 

@@ -243,6 +243,19 @@ def test_gather(dtype):
         assert (out[:total, max_clip:] == 77.0).all()                       # nothing behind max_clip_len
         assert (out[total:] == 77.0).all() and not out_len[total:].any()    # rows at or beyond total: length 0 only
     ops.check_status()                                                      # the rows beyond total were never looked at
+    # hand-written rows (the segmenter only ever starts a clip on a chunk boundary): an aligned start with whole 16-byte groups,
+    # starts off the 16-byte grid, an aligned start whose clip ends inside a group, a clip cut at max_clip_len, an empty clip;
+    # into aligned output rows whose last group is partial (203 of 208) and into rows no vector store may touch (201 apart)
+    hand = np.array([[5, 64, 256], [6, 3, 203], [7, 128, 165], [8, 130, 430], [9, 8, 8], [5, 321, 322]], dtype=np.int32)
+    for max_clip, out_stride in ((203, 208), (200, 201)):
+        rc, out, out_len = _gather_raw(dw, hand, len(hand), len(hand) + 2, max_clip, out_stride=out_stride)
+        assert rc == 0
+        want, want_len = vad_ref.gather(w, hand, max_clip)
+        assert want_len.tolist() == [192, 200, 37, max_clip, 0, 1]
+        assert np.array_equal(out[:len(hand), :max_clip].view(np.uint32), want.view(np.uint32))
+        assert np.array_equal(out_len[:len(hand)], want_len) and not out_len[len(hand):].any()
+        assert (out[:len(hand), max_clip:] == 77.0).all() and (out[len(hand):] == 77.0).all()
+    ops.check_status()
     # corrupted rows: a recording outside the batch, a reversed range, a range past the row -> zero rows + SIR_EINVAL
     bad = ref.copy()
     bad[1, 0] = len(LENGTHS)
